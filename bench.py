@@ -11,8 +11,13 @@ already resident in HBM (2-bit packed): at N = 1 the batch is BASELINE.json conf
 shard of the read set (weak scaling; 8 x 6.25 = the 50 Gbp of BASELINE configs[2] and of the
 metric), k-mer space is radix-sharded over the ranks and one RCCL all-to-all(v) replaces the
 Spark shuffle.  Run without a launcher, `--gpus N` starts its own N ranks (torch.distributed.run)
-and refuses to run when fewer than N GPUs are visible.  After the timed steps the run goes on to
-final contigs once and reports that wall-clock beside the metric.
+and refuses to run when fewer than N GPUs are visible.
+
+A plain run sets up, warms up, times the K steps and prints the line.  With --full the run also
+measures everything else the line can carry: the CPU baseline, the wall-clock to final contigs
+(and the de-duplication, the ASCII ingest, the k = 63 block, the `next_rows` and `strong_50gbp`
+blocks at N = 1).  --dump-outputs DIR writes what the last timed step computed (the surviving
+k-mers and their counts; a fixed, seeded sample of them when they are many) as .npy files.
 """
 import argparse
 import json
@@ -115,7 +120,16 @@ def parse():
                     help="N > 1 (or --force-dist): run the extend stage range-sharded over the ranks with the records resident "
                          "in HBM (reflexiv_amd.dist.sharded_assemble_dev: one RCCL all-to-all of whole records per sortByKey) "
                          "instead of gathering the survivors on rank 0 -- what a genome beyond one GPU needs; k <= 31")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the count stage too: CPU baseline, contigs (dedup, ASCII ingest), k = 63, "
+                         "next_rows, strong_50gbp.  Without it the run times the count stage only (the --no-* flags select "
+                         "within --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64): the surviving "
+                         "k-mers as 32-bit limbs, their counts, and a summary with checksums over all of them")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_contigs = args.no_k63 = args.no_ingest = args.no_next_rows = args.no_strong = True
     if args.strong:
         args.gbp = 50.0 / args.gpus
         if args.gpus == 1:
@@ -289,6 +303,35 @@ def strong_block(args, rfx, torch, reflexiv_amd, dev):
             "per_kernel_ms_last_step": tm,
             "how_to_read": "strong-scaling efficiency at N GPUs on this read set = value(N-GPU line, N x 50/N Gbp) / (N x this value); "
                            "north_star asks >= 6x at N = 8, i.e. value(N = 8) >= 6 x this value"}
+
+
+DUMP_BYTES = 56 << 20          # --dump-outputs: at most this much per rank (the files stay under 64 MB in all at N = 1)
+
+
+def dump_outputs(path, keys, counts, W, m, nd, inst, rank, world):
+    """The last timed step's output (ascending k-mers, W words each, and their counts) as float64 .npy files: keys.npy holds
+    each k-mer as 2W 32-bit limbs (most significant first: exact in float64), counts.npy its count, rows.npy the row of each;
+    when the rows exceed DUMP_BYTES they are a fixed, seeded sample.  summary.npy: kept, distinct, instances, this rank's
+    rows, the sum of all counts and the XOR of all key words (as 32-bit limbs) over every row, sampled or not."""
+    import numpy as np
+    k64 = keys.contiguous().cpu().numpy().view(np.uint64).reshape(-1, W)
+    c = counts.contiguous().cpu().numpy().astype(np.int64)
+    n = len(c)
+    assert k64.shape[0] == n, (k64.shape, n)
+    limbs = np.empty((n, 2 * W), np.uint64)
+    limbs[:, 0::2], limbs[:, 1::2] = k64 >> np.uint64(32), k64 & np.uint64(0xFFFFFFFF)
+    per_row = 8 * (2 * W + 2)
+    rows = np.arange(n)
+    if n * per_row > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(20261016).choice(n, DUMP_BYTES // per_row, replace=False))
+    xor = np.bitwise_xor.reduce(limbs, axis=0) if n else np.zeros(2 * W, np.uint64)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, f"keys{sfx}.npy"), limbs[rows].astype(np.float64))
+    np.save(os.path.join(path, f"counts{sfx}.npy"), c[rows].astype(np.float64))
+    np.save(os.path.join(path, f"rows{sfx}.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, f"summary{sfx}.npy"),
+            np.array([m, nd, inst, n, int(c.sum())] + [int(x) for x in xor], np.float64))
 
 
 def main():
@@ -491,6 +534,9 @@ def main():
                                    else "reflexiv_amd.dist over torch.distributed",
                            "exchange_free": bool((rd.LOCAL_SHORTCUT or capi) and world == 1),
                            "rehearsed_as_rank_of": args.virtual_world if (capi and world == 1 and args.force_dist) else None}
+    if args.dump_outputs:
+        keys_out, counts_out = (shard["keys"], shard["counts"]) if multi else (d_keys[:m * W], d_counts[:m])
+        dump_outputs(args.dump_outputs, keys_out, counts_out, W, m, nd, inst, rank, world)
     if multi and not args.no_contigs and capi:
         # the extend stage behind the C ABI (rfx_dev_sharded_assemble): every sortByKey of the driver is a range shuffle of whole
         # records over the ranks while the record set has more than gather_below records (the library's 32 Mi unless

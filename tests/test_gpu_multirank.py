@@ -78,7 +78,7 @@ def test_bench_multi_gpu_branch_gives_the_one_gpu_answer(k):
     """`bench.py --gpus 2` as the driver launches it (torch.distributed.run, one process per rank), rehearsed with both ranks
     on this box's one GPU: the same reads as a one-GPU run of twice the per-GPU size, so distinct / kept k-mers and the
     contigs must be the same.  (Timing fields of the rehearsal mean nothing and the line says so.)"""
-    common = ["--genome", "200000", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-k63", "--no-ingest", "--k", str(k)]
+    common = ["--full", "--genome", "200000", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-k63", "--no-ingest", "--k", str(k)]
     env1 = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     one = bench_line(["--gpus", "1", "--gbp", "0.04", "--cover", "4"] + common, env1, 1)
     env2 = dict(env1, RFX_RCCL_LIB=build_shim(), RFX_BENCH_SHARED_GPU="1")
