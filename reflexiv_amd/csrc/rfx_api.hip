@@ -479,7 +479,7 @@ int rfx_dev_count_reads_w(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads
     const int64_t N = nk * n_reads;
     if (out_instances) *out_instances = N;
     if (N == 0) return RFX_OK;
-    if (wide_fast_path(k) && !getenv("RFX_WIDE_MATERIALIZE")) {
+    if (wide_fast_path(k)) {
         // level 1 straight from the packed reads: the 16-byte elements are never written unpartitioned
         int64_t m = 0;
         int st = count_wide2_reads(ctx, d_words, n_reads, words_per_read, nk, k, front_clip, min_cov, max_cov, d_out_keys,
@@ -1124,13 +1124,12 @@ int rfx::assemble_impl(rfx_ctx *ctx, bool wide, const uint64_t *d_keys, const in
     int64_t contigNumber = resume ? resume->contig_number : 0;
     int scramble = resume ? resume->scramble : 2;                                 // U/DefaultParam.java:131
     // once the record set is small the rest of the loop runs as two launches per pass with the loop state in HBM
-    static const bool small_off = getenv("RFX_NO_SMALL_PASSES") != nullptr;
     const bool extras = wide && prm->extras != 0;
     bool split_done = false;
     DevRecords unext;                       // UnExtendableReflexivKmer (64 :605); lives outside the alternating arenas
     auto small_tail = [&](bool *took) -> int {
         *took = false;
-        if (small_off || a.n > small_pass_limit() || P > small_pass_max_partitions()) return RFX_OK;
+        if (a.n > small_pass_limit() || P > small_pass_max_partitions()) return RFX_OK;
         if (extras && !split_done && iterations + 1 <= prm->min_iter + 3) return RFX_OK;   // the split of 64 :584-619 comes first
         Arena *saved = tl_arena;
         tl_arena = nullptr;                 // its second record set and scratch outlive the alternating arenas

@@ -392,7 +392,6 @@ int rfx_dev_sharded_count(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_words, co
         if (c->units_per_read <= 0) c->units_per_read = (double)nk / 5.0 + 1.0;
         // the send buffer's layout: bin b = records [pb[b], pe[b]) (the two-pass form packs the bins back to back; level 1's
         // one sweep leaves the slack of its regions between them)
-        const bool try_sweep = !(getenv("RFX_COMM_SWEEP") && atoi(getenv("RFX_COMM_SWEEP")) == 0);
         for (int attempt = 0;; attempt++) {
             const int64_t cap_rec = (int64_t)(c->units_per_read * (double)n_reads) + 4096;
             RFX_TRY(comm_grow(ctx, &c->send, &c->send_bytes, (size_t)cap_rec * uw * 8, ctx->stream, c->xs));
@@ -400,16 +399,15 @@ int rfx_dev_sharded_count(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_words, co
             int st;
             bool swept = false;
             if (wide) {
-                st = try_sweep ? rfx::bucket_wide_records_by_owner_sweep(ctx, d_words, n_reads, words_per_read, nk, k, front_clip, bins, c->send,
-                                                                         cap_rec, pb, pe, &nrec, &swept)
-                               : RFX_OK;
+                st = rfx::bucket_wide_records_by_owner_sweep(ctx, d_words, n_reads, words_per_read, nk, k, front_clip, bins, c->send,
+                                                             cap_rec, pb, pe, &nrec, &swept);
                 if (st == RFX_OK && !swept)
                     st = rfx_dev_bucket_wide_records_by_owner(ctx, d_words, n_reads, words_per_read, read_len, k, front_clip, end_clip, bins,
                                                               c->send, cap_rec, c->d_tab, pb, &nrec);
                 else
                     ScopedTimer::collect(ctx);
             } else {
-                st = try_sweep ? rfx::bucket_records_by_owner_sweep(ctx, &rs, bins, c->send, cap_rec, pb, pe, &nrec, &swept) : RFX_OK;
+                st = rfx::bucket_records_by_owner_sweep(ctx, &rs, bins, c->send, cap_rec, pb, pe, &nrec, &swept);
                 if (st == RFX_OK && !swept) st = rfx::bucket_records_by_owner(ctx, &rs, bins, c->send, cap_rec, c->d_tab, pb, &nrec);
                 ScopedTimer::collect(ctx);
             }

@@ -568,8 +568,7 @@ int sort_records(rfx_ctx *ctx, const DevRecords &in, int P, int key_bits, DevRec
         RFX_HIP(hipGetLastError());
         const int res = k > 0 ? (k - 1) - 31 * (kw - 1) : 31;      // k unknown: every word may use its 62 bits
         bool done = false;
-        static const bool tie_off = getenv("RFX_SORT_TIEFIX") && atoi(getenv("RFX_SORT_TIEFIX")) == 0;
-        if (kw == 2 && !tie_off) {       // (k unknown: res = 31, a prefix that splits less but orders the same)
+        if (kw == 2) {       // (k unknown: res = 31, a prefix that splits less but orders the same)
             // one sort on the first 64 bits, then the runs of equal prefixes mended (see k_tie_fix2)
             DevBuf flag;
             RFX_HIP(flag.alloc(4, ctx->stream));

@@ -252,7 +252,7 @@ struct StageArena {
     Arena *prev;
     bool on = false;
     StageArena(rfx_ctx *ctx, size_t bytes) : prev(tl_arena) {
-        if (tl_arena || (getenv("RFX_COUNT_ARENA") && atoi(getenv("RFX_COUNT_ARENA")) == 0)) return;
+        if (tl_arena) return;
         arena.base = (char *)ctx->ws_get(4, bytes);
         if (arena.base) { arena.cap = bytes; tl_arena = &arena; on = true; }
     }
@@ -264,7 +264,7 @@ struct StageArena {
 // Event pair that accumulates into ctx->timing[name].
 struct ScopedTimer {
     rfx_ctx *ctx; const char *name; hipEvent_t a = nullptr, b = nullptr; bool on;
-    ScopedTimer(rfx_ctx *c, const char *n) : ctx(c), name(n), on(c && c->timing_enabled && !getenv("RFX_NO_TIMING")) {
+    ScopedTimer(rfx_ctx *c, const char *n) : ctx(c), name(n), on(c && c->timing_enabled) {
         if (on) { a = ctx->ev_get(); b = ctx->ev_get(); on = a && b; }
         if (on) (void)hipEventRecord(a, ctx->stream);
     }

@@ -430,64 +430,32 @@ __global__ __launch_bounds__(PT) void k_vb_scatter(const uint64_t *__restrict__ 
 
 // ------------------------------------------------------------------- leaves
 
-#ifndef RFX_LT
-#define RFX_LT 768
-#endif
-#ifndef RFX_LEAF_WAVES_PER_EU
-#define RFX_LEAF_WAVES_PER_EU 6
-#endif
 // 12 waves per workgroup, two workgroups per CU, registers capped for 6 waves per SIMD: the kernel is bound by LDS and
 // issue latency (one workgroup per CU instead of two: 13.1 -> 21.7 ms), and 8 waves with 4 per SIMD measured 13.2 ms
-// against 12.6 (tools/build_variant.sh + tools/ab_many.sh; 10 waves per workgroup: 20 ms)
-constexpr int LT = RFX_LT;              // threads per leaf workgroup
-// RFX_LEAF_QUEUE (experiment, off): probing as a per-wave queue of attempts, as in the two-word leaf -- a key whose
-// first probe met another key is queued with its next slot, and whenever 32 attempts wait they are made together.
-// Measured: 13.3 ms against 12.3 on the bench, 758 ms against 77 on a human-scale share whose tables run at 58 % -- two
-// keys per lane already probe side by side here, and a batch of 32 attempts is half a wave.  (An earlier form that
-// parked the keys and walked 64 whole sequences at once: 12.7 ms and 298 ms.)  What pays in the two-word leaf, where
-// one key per lane went round a ballot loop, does not pay here.
-#ifndef RFX_LEAF_QUEUE
-#define RFX_LEAF_QUEUE 0
-#endif
-constexpr int LQCAP = RFX_LEAF_QUEUE ? 96 : 0;    // attempts a wave has pending (record leaves): < 32 + 64 new ones
-constexpr int LQBATCH = 32;
-// RFX_LEAF_AGG: records of a leaf are first counted in a small LDS table keyed by the WHOLE record (a deep data set
+// against 12.6 (10 waves per workgroup: 20 ms)
+constexpr int LT = 768;                 // threads per leaf workgroup
+constexpr int LEAF_WAVES_PER_EU = 6;
+// (Probing as a per-wave queue of attempts, as in the two-word leaf's first form, measured 13.3 ms against 12.3 on the
+// bench and 758 ms against 77 on a human-scale share whose tables run at 58 % -- two keys per lane already probe side by
+// side here.)
+// Record leaves: records of a leaf are first counted in a small LDS table keyed by the WHOLE record (a deep data set
 // repeats its super-k-mer records: at 1000x four windows in five lie in a record seen before in the same leaf), and
 // only the distinct records are expanded into k-mers, each k-mer inserted once with the record's count as weight.  The
 // table is a cache, not a set: a record that finds no slot in RPROBE probes is expanded on the spot with weight 1.
-#ifndef RFX_LEAF_AGG
-#define RFX_LEAF_AGG 1
-#endif
-#ifndef RFX_WALK_NOUNROLL
-#define RFX_WALK_NOUNROLL 1
-#endif
 constexpr int RSLOTS = 768;             // record slots (one 64-slot block per wave of the workgroup in the sweep)
 constexpr int RPROBE = 4;
-constexpr int LOBUF = RFX_LEAF_QUEUE ? 64 : 512;  // survivors k_leaf_count buffers in LDS between flushes (k-mer and pair leaves)
+constexpr int LOBUF = 512;              // survivors k_leaf_count buffers in LDS between flushes (k-mer and pair leaves)
 // Record leaves: the record table takes the room of that buffer, so 128 survivors wait in a buffer of their own and
 // what a leaf has beyond them goes to the waves' expansion areas, which are idle during the sweep -- and must be free
 // again before the next leaf: a sweep that ends with LOBUF1 / 2 or more waiting flushes.
-constexpr int LOBUF1 = RFX_LEAF_AGG ? 128 : LOBUF;
-constexpr int WSTAGE = 160 + LQCAP + LQCAP / 2;   // u64 words of a wave's private expansion area (record leaves) + its queue
+constexpr int LOBUF1 = 128;
+constexpr int WSTAGE = 160;             // u64 words of a wave's private expansion area (record leaves)
 constexpr int LSTAGE = WSTAGE * (LT / 64);
-#ifndef RFX_LCAP
-#define RFX_LCAP 4096
-#endif
-constexpr int LCAP = RFX_LCAP;          // hash slots: 4096, or 3072 (three quarters of 12 hash bits; probe steps prime to it)
 constexpr int LCAP_BITS = 12;
-static_assert(LCAP == 4096 || LCAP == 3072, "slots");
-__device__ __forceinline__ uint32_t leaf_slot(uint32_t g) {
-    const uint32_t x = g >> (32 - LCAP_BITS);
-    return LCAP == 4096 ? x : (x * 3u) >> 2;
-}
-__device__ __forceinline__ uint32_t leaf_step(uint32_t g) {
-    return LCAP == 4096 ? (((g >> 8) & (LCAP - 1)) | 1u) : ((g >> 8) & 511u) * 6u + 1u;      // (6 t + 1 is prime to 2^10 x 3)
-}
-__device__ __forceinline__ uint32_t leaf_next(uint32_t slot, uint32_t step) {
-    if (LCAP == 4096) return (slot + step) & (LCAP - 1);
-    const uint32_t x = slot + step;
-    return x >= (uint32_t)LCAP ? x - LCAP : x;
-}
+constexpr int LCAP = 1 << LCAP_BITS;    // hash slots
+__device__ __forceinline__ uint32_t leaf_slot(uint32_t g) { return g >> (32 - LCAP_BITS); }
+__device__ __forceinline__ uint32_t leaf_step(uint32_t g) { return ((g >> 8) & (LCAP - 1)) | 1u; }   // odd: prime to LCAP
+__device__ __forceinline__ uint32_t leaf_next(uint32_t slot, uint32_t step) { return (slot + step) & (LCAP - 1); }
 constexpr int LPROBE = 48;              // a probe sequence this long means the table is too full: split the leaf
 constexpr uint64_t EMPTY = ~0ULL;
 constexpr int LSTACK = 48;
@@ -502,10 +470,6 @@ struct CountOut {
     unsigned long long n_passes;     // table passes run (>= non-empty leaves)
     unsigned long long n_overflow;   // passes abandoned because the table filled up
     unsigned long long n_leaves;     // non-empty leaves
-    unsigned long long t_wait, t_all; // RFX_LEAF_DBG & 32: clocks waves spent at the two barriers of a leaf / in the kernel
-    // RFX_LEAF_DBG & 128: the record table -- records counted in it / expanded on the spot, occupied slots at the sweeps,
-    // windows expanded on the spot / from the table (against the instances: what the table saved)
-    unsigned long long r_placed, r_direct, r_slots, w_direct, w_table;
 };
 
 // Persistent workgroups each walk a CONTIGUOUS chunk of leaf buckets, i.e. one contiguous
@@ -549,10 +513,7 @@ template <> struct LeafElem<2> {
 };
 template <> struct LeafElem<1> {
     using T = Rec;
-#ifndef RFX_RPF
-#define RFX_RPF 1
-#endif
-    static constexpr int PER_LANE = RFX_RPF; // 64-record steps a wave holds in registers per leaf
+    static constexpr int PER_LANE = 1;       // 64-record steps a wave holds in registers per leaf
     __device__ static __forceinline__ T none() { return Rec{0, 0}; }
     __device__ static __forceinline__ uint64_t key(const T &e) { return e.w0; }
     __device__ static __forceinline__ uint32_t weight(const T &) { return 1u; }
@@ -589,20 +550,20 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
 // KC: the k-mer length as a compile-time constant (0 = the run-time argument): the window shifts, the reverse
 // complement's alignment and the masks of the record path fold into immediates
 template <int ELEM, int KC = 0>
-__global__ __launch_bounds__(LT, RFX_LEAF_WAVES_PER_EU) void k_leaf_count(const typename LeafElem<ELEM>::T *__restrict__ keys,
+__global__ __launch_bounds__(LT, LEAF_WAVES_PER_EU) void k_leaf_count(const typename LeafElem<ELEM>::T *__restrict__ keys,
                                                    const uint64_t *__restrict__ leaf_off, const uint64_t *__restrict__ leaf_end, int64_t nleaf,
                                                    const uint64_t *__restrict__ sl_begin, const uint64_t *__restrict__ sl_end,
                                                    uint64_t heavy, uint64_t n_elems, int k_rt,
                                                    int min_cov, int max_cov, int apply_filter,
                                                    uint64_t *__restrict__ out_keys, int32_t *__restrict__ out_counts,
-                                                   unsigned long long cap, CountOut *__restrict__ co, int dbg,
+                                                   unsigned long long cap, CountOut *__restrict__ co,
                                                    int pair_out, uint32_t presplit) {
     constexpr bool RECS = ELEM == 1;
     const int k = KC ? KC : k_rt;
     __shared__ __attribute__((aligned(16))) unsigned long long tkey[LCAP];
     __shared__ __attribute__((aligned(16))) uint32_t tcnt[LCAP];
     constexpr int OB1 = RECS ? LOBUF1 : LOBUF;                                   // survivors in the buffer of their own
-    constexpr int OB2 = RECS && RFX_LEAF_AGG && !RFX_LEAF_QUEUE ? (LSTAGE * 8) / 12 : 0;   // ... in the expansion areas (see LOBUF1)
+    constexpr int OB2 = RECS ? (LSTAGE * 8) / 12 : 0;                             // ... in the expansion areas (see LOBUF1)
     constexpr int OBT = OB1 + OB2;
     __shared__ unsigned long long obk[OB1];
     __shared__ int32_t obc[OB1];
@@ -622,17 +583,14 @@ __global__ __launch_bounds__(LT, RFX_LEAF_WAVES_PER_EU) void k_leaf_count(const 
         if (OB2 == 0 || i < (uint32_t)OB1) { obk[i] = key; obc[i] = c; }
         else { obk2[i - OB1] = key; obc2[i - OB1] = c; }
     };
-    constexpr bool AGG = RECS && RFX_LEAF_AGG != 0;
-    static_assert(!AGG || RSLOTS == 64 * (LT / 64), "one block of record slots per wave");
+    static_assert(RSLOTS == 64 * (LT / 64), "one block of record slots per wave");
     // record table: rA = bases 0..31 of the record, rBC = [63..32] bases 32..45 | windows - 1, [31..0] the count
-    __shared__ unsigned long long rA[AGG ? RSLOTS : 1], rBC[AGG ? RSLOTS : 1];
+    __shared__ unsigned long long rA[RECS ? RSLOTS : 1], rBC[RECS ? RSLOTS : 1];
     // whether the table pays is a property of the data set (its depth): the workgroup adds up, over its first leaves, how
     // many records met an entry that was already there, and goes without the table when that is under half of them
     // (measured break-even: a 47x data set, 37 % met one, ran 85 ms with the table and 81 without)
     __shared__ uint32_t agg_on, agg_saved, agg_total;
     uint32_t my_distinct = 0;                                                // every thread
-    long long t_wait = 0;
-    const long long t_begin = (dbg & 32) ? clock64() : 0;
     unsigned long long my_passes = 0, my_overflows = 0;                      // thread 0 only
     const int lane_ = threadIdx.x & 63;
     const int wave_ = threadIdx.x >> 6;
@@ -654,7 +612,7 @@ __global__ __launch_bounds__(LT, RFX_LEAF_WAVES_PER_EU) void k_leaf_count(const 
     };
 
     for (int i = threadIdx.x; i < LCAP; i += LT) { tkey[i] = EMPTY; tcnt[i] = 0; }
-    if constexpr (AGG) for (int i = threadIdx.x; i < RSLOTS; i += LT) { rA[i] = EMPTY; rBC[i] = EMPTY; }
+    if constexpr (RECS) for (int i = threadIdx.x; i < RSLOTS; i += LT) { rA[i] = EMPTY; rBC[i] = EMPTY; }
     if (threadIdx.x == 0) {
         ob_n = 0; ob_lim = 0xffffffffu; overflow = 0; sp = 0;
         blk_base = NOBLK; blk_next = NOBLK; blk_pos = PBLOCK; have_next = 0; need_grab = 1;
@@ -716,41 +674,6 @@ __global__ __launch_bounds__(LT, RFX_LEAF_WAVES_PER_EU) void k_leaf_count(const 
 
     // one table pass over the leaf [begin, end): inserts the keys selected by (S, s); no barriers
     auto run_pass = [&](uint32_t S, uint32_t s, bool first, uint64_t begin_next, uint64_t end_next) __attribute__((always_inline)) {
-        uint32_t qn = 0;                 // keys parked in this wave's queue (wave-uniform; < 64 between rounds)
-        // Two keys per lane probe in lock-step so that two LDS compare-and-swaps are in flight.  A key
-        // is done when its slot held EMPTY (claimed) or the key itself; either way its count goes up.
-        // There is no occupancy counter: a probe sequence longer than LPROBE flags the pass as
-        // overflowing (the table is too full to be worth probing) and the leaf is split.
-        // the top n <= LQBATCH entries of the wave's queue: one probe each, what is not finished goes back
-        auto attempts = [&](uint32_t n) __attribute__((always_inline)) {
-            if constexpr (RECS && LQCAP > 0) {
-                uint64_t *wq = stage + wave_ * WSTAGE + 160;
-                uint32_t *wqs = (uint32_t *)(wq + LQCAP);
-                qn -= n;
-                const bool v = (uint32_t)lane_ < n;
-                const uint64_t key = v ? wq[qn + lane_] : 0;
-                const uint32_t st = v ? wqs[qn + lane_] : 0u;
-                __builtin_amdgcn_wave_barrier();
-                uint32_t slot = st & 0xffffu, probe = st >> 16;
-                bool done = !v;
-                if (v) {
-                    const unsigned long long p = atomicCAS(&tkey[slot], EMPTY, (unsigned long long)key);
-                    if (p == EMPTY || p == key) { atomicAdd(&tcnt[slot], 1u); done = true; }
-                    else {
-                        const uint32_t g = ((uint32_t)key ^ __builtin_rotateleft32((uint32_t)(key >> 32), 13)) * 0x9E3779B1u;
-                        slot = leaf_next(slot, (dbg & 16) ? 1u : leaf_step(g));
-                        if (++probe >= (uint32_t)LPROBE) { overflow = 1; done = true; }
-                    }
-                }
-                const uint64_t m = __ballot(!done);
-                if (m) {
-                    const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                    if (!done) { wq[qn + r] = key; wqs[qn + r] = slot | (probe << 16); }
-                    qn += (uint32_t)__popcll(m);
-                }
-                __builtin_amdgcn_wave_barrier();
-            }
-        };
         auto insert2 = [&](uint64_t keyA, bool a, uint64_t keyB, bool b, uint32_t wA, uint32_t wB) __attribute__((always_inline)) {
             const uint32_t gA = ((uint32_t)keyA ^ __builtin_rotateleft32((uint32_t)(keyA >> 32), 13)) * 0x9E3779B1u;
             const uint32_t gB = ((uint32_t)keyB ^ __builtin_rotateleft32((uint32_t)(keyB >> 32), 13)) * 0x9E3779B1u;
@@ -771,13 +694,11 @@ __global__ __launch_bounds__(LT, RFX_LEAF_WAVES_PER_EU) void k_leaf_count(const 
             // (double hashing: an odd step from other hash bits -- the wave waits for its longest probe sequence,
             // and linear probing's clusters make that one long in a leaf that fills its table)
             auto walk = [&](uint64_t key, uint32_t slot, uint32_t w, uint32_t g) __attribute__((always_inline)) {
-                const uint32_t step = (dbg & 16) ? 1u : leaf_step(g);
+                const uint32_t step = leaf_step(g);
                 // (rounds 1-2 left this loop to the compiler's full unroll -- 2 % faster then; with the record table in
                 // front of it few keys walk at all, and the rolled loop takes the kernel from 69 KB to a third, 1264 spilled
                 // SGPRs to 45)
-#if RFX_WALK_NOUNROLL
 #pragma nounroll
-#endif
                 for (int probe = 1;; probe++) {
                     slot = leaf_next(slot, step);
                     const unsigned long long p = atomicCAS(&tkey[slot], EMPTY, (unsigned long long)key);
@@ -786,38 +707,8 @@ __global__ __launch_bounds__(LT, RFX_LEAF_WAVES_PER_EU) void k_leaf_count(const 
                 }
             };
             // (one loop per key; a single loop walking a lane's two sequences one after the other measured 10 % slower)
-            if constexpr (RECS && LQCAP > 0) {
-                uint64_t *wq = stage + wave_ * WSTAGE + 160;
-                uint32_t *wqs = (uint32_t *)(wq + LQCAP);
-#pragma nounroll
-                for (int ph = 0; ph < 2; ph++) {
-                    const bool u = ph == 0 ? !dA : !dB;
-                    const uint64_t m = __ballot(u);
-                    if (m) {
-                        const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                        if (u) {
-                            const uint32_t g = ph == 0 ? gA : gB;
-                            wq[qn + r] = ph == 0 ? keyA : keyB;
-                            wqs[qn + r] = leaf_next(ph == 0 ? slotA : slotB, (dbg & 16) ? 1u : leaf_step(g)) | (1u << 16);
-                        }
-                        qn += (uint32_t)__popcll(m);
-                        __builtin_amdgcn_wave_barrier();
-#pragma nounroll
-                        while (qn >= (uint32_t)LQBATCH) attempts((uint32_t)LQBATCH);
-                    }
-                }
-            } else {
-                if (!dA) walk(keyA, slotA, wA, gA);
-                if (!dB) walk(keyB, slotB, wB, gB);
-            }
-        };
-        // the attempts still pending when the wave has been through its share of the leaf
-        auto drain_queue = [&]() __attribute__((always_inline)) {
-            if constexpr (RECS && LQCAP > 0) {
-#pragma nounroll
-                while (qn > 0u && !__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
-                    attempts(qn < (uint32_t)LQBATCH ? qn : (uint32_t)LQBATCH);
-            }
+            if (!dA) walk(keyA, slotA, wA, gA);
+            if (!dB) walk(keyB, slotB, wB, gB);
         };
         if constexpr (RECS) {
             // Records: every wave takes an equal contiguous share of the leaf and walks it 64 records
@@ -891,10 +782,6 @@ __global__ __launch_bounds__(LT, RFX_LEAF_WAVES_PER_EU) void k_leaf_count(const 
             };
             // (weight: how many times the record was seen; lands in the upper bits of the record's first output position)
             auto step = [&](const Rec rcur, const bool valid, const uint32_t /*weight: 1*/) __attribute__((always_inline)) {
-                if (dbg & 1) {       // ablation: stream only
-                    if (rcur.w0 == 0x123456789ULL) overflow = 1;
-                    return;
-                }
                 const uint32_t nwin = valid ? (uint32_t)rec_len(rcur) : 0u;
                 const uint32_t x = wave_incl_scan(nwin);
                 const uint32_t off = x - nwin;
@@ -906,12 +793,9 @@ __global__ __launch_bounds__(LT, RFX_LEAF_WAVES_PER_EU) void k_leaf_count(const 
                     const uint32_t s0 = (uint32_t)(rcur.w0 >> 32), s1 = (uint32_t)rcur.w0, s2 = (uint32_t)(rcur.w1 >> 32);
                     // (a record is found by its ordinal among the records that have windows: with the record table the
                     // lanes without any are not only the tail)
-                    uint32_t ord = (uint32_t)lane_;
-                    if constexpr (AGG) {
-                        const uint64_t vm = __ballot(nwin != 0u);
-                        ord = __builtin_amdgcn_mbcnt_hi((uint32_t)(vm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)vm, 0u));
-                    }
-                    if (!AGG || nwin)
+                    const uint64_t vm = __ballot(nwin != 0u);
+                    const uint32_t ord = __builtin_amdgcn_mbcnt_hi((uint32_t)(vm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)vm, 0u));
+                    if (nwin)
                         wrec[ord] = make_uint4(s0 >> 1, __builtin_amdgcn_alignbit(s0, s1, 1), __builtin_amdgcn_alignbit(s1, s2, 1), off);
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -926,10 +810,6 @@ __global__ __launch_bounds__(LT, RFX_LEAF_WAVES_PER_EU) void k_leaf_count(const 
                     const bool v0 = j0 < total, v1 = j1 < total;
                     uint32_t g0, g1;
                     const uint64_t c0 = kmer_at_pos(v0 ? j0 : 0, g0, std::false_type{}), c1 = kmer_at_pos(v1 ? j1 : 0, g1, std::false_type{});
-                    if (dbg & 2) {       // ablation: expand, no table
-                        if ((v0 && c0 == 0x123456789ULL) || (v1 && c1 == 0x123456789ULL)) overflow = 1;
-                        continue;
-                    }
                     insert2(c0, v0, c1, v1, g0, g1);
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -959,20 +839,12 @@ __global__ __launch_bounds__(LT, RFX_LEAF_WAVES_PER_EU) void k_leaf_count(const 
                     const bool v0 = j0 < total, v1 = j1 < total;
                     uint32_t g0, g1;
                     const uint64_t c0 = kmer_at_pos(v0 ? j0 : 0, g0, std::true_type{}), c1 = kmer_at_pos(v1 ? j1 : 0, g1, std::true_type{});
-                    if (dbg & 2) {       // ablation: expand, no table
-                        if ((v0 && c0 == 0x123456789ULL) || (v1 && c1 == 0x123456789ULL)) overflow = 1;
-                        continue;
-                    }
                     insert2(c0, v0, c1, v1, g0, g1);
                 }
                 __builtin_amdgcn_wave_barrier();
                 parked = 0;
             };
             auto park = [&](const Rec rcur, const bool valid, const uint32_t weight) __attribute__((always_inline)) {
-                if (dbg & 1) {       // ablation: stream only
-                    if (rcur.w0 == 0x123456789ULL) overflow = 1;
-                    return;
-                }
                 const uint64_t vm = __ballot(valid);
                 if (!vm) return;
                 const uint32_t d = (uint32_t)__popcll(vm);
@@ -987,20 +859,17 @@ __global__ __launch_bounds__(LT, RFX_LEAF_WAVES_PER_EU) void k_leaf_count(const 
                 parked += d;
             };
             // the record table takes the leaf's single pass; the hash-selected parts of a split leaf expand every record
-            const bool agg = AGG && S == 1 && !(dbg & 64) && (agg_on || (dbg & 512));
+            const bool agg = S == 1 && agg_on;
             uint32_t hits = 0;                                            // records of this wave that found a slot (uniform)
             // count the record in the record table; false = no slot for it (or not eligible): expand it now
             auto place = [&](const Rec &r, bool valid) __attribute__((always_inline)) -> bool {
-                if constexpr (!AGG) return false;
                 if (!agg || !valid || r.w0 == EMPTY) return false;
                 // (the bases behind the record's last window are whatever followed in the read: not part of its identity)
                 uint32_t b = (uint32_t)(r.w1 >> 32);
-                if (!(dbg & 256)) {
-                    const uint32_t nw = (b & 15u) + 1u;                       // k - 1 + nw bases are the record's
-                    const int used = 2 * (k - 1 + (int)nw) - 64;              // ... of them in b's 28 base bits (<= 0: none)
-                    const uint32_t keep = used >= 28 ? 0xfffffff0u : used <= 0 ? 0u : ~(0xffffffffu >> used);
-                    b = (b & keep) | (b & 15u);
-                }
+                const uint32_t nw = (b & 15u) + 1u;                           // k - 1 + nw bases are the record's
+                const int used = 2 * (k - 1 + (int)nw) - 64;                  // ... of them in b's 28 base bits (<= 0: none)
+                const uint32_t keep = used >= 28 ? 0xfffffff0u : used <= 0 ? 0u : ~(0xffffffffu >> used);
+                b = (b & keep) | (b & 15u);
                 const uint32_t h = ((uint32_t)r.w0 ^ __builtin_rotateleft32((uint32_t)(r.w0 >> 32), 13) ^ __builtin_rotateleft32(b, 7)) * 0x9E3779B1u;
                 // (admitting a record only at its second sighting -- a bit per record hash -- keeps the records seen once
                 // out of the table, 267 instead of 463 of its slots in use, but every record seen again is then expanded
@@ -1017,76 +886,41 @@ __global__ __launch_bounds__(LT, RFX_LEAF_WAVES_PER_EU) void k_leaf_count(const 
                 }
                 return false;
             };
-            auto rstat = [&](bool placed, bool direct, const Rec &r) {
-                const uint32_t w = direct ? (uint32_t)rec_len(r) : 0u;
-                uint32_t ws_ = w;
-                for (int o = 32; o > 0; o >>= 1) ws_ += __shfl_xor(ws_, o, 64);
-                const uint64_t mp = __ballot(placed), md = __ballot(direct);
-                if (lane_ == 0) {
-                    atomicAdd(&co->r_placed, (unsigned long long)__popcll(mp));
-                    atomicAdd(&co->r_direct, (unsigned long long)__popcll(md));
-                    atomicAdd(&co->w_direct, (unsigned long long)ws_);
-                }
-            };
-            if constexpr (AGG) {
-                static_assert(RPF == 1, "the first 64-record step of a wave comes from registers");
-                Rec rr = cur[0];
-                for (uint64_t r0 = ws; r0 < we; r0 += 64) {
-                    // an overflowing pass is abandoned: stop feeding a table that is filling up
-                    if (__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
-                    const bool valid = r0 + lane_ < we;
-                    // (the wave's next 64 records travel while these are counted)
-                    const Rec nx = r0 + 64 + lane_ < we ? keys[r0 + 64 + lane_] : Rec{0, 0};
-                    if (agg) {
-                        const bool placed = place(rr, valid);
-                        hits += (uint32_t)__popcll(__ballot(placed));
-                        if (dbg & 128) rstat(placed, valid && !placed, rr);
-                        park(rr, valid && !placed, 1u);
-                    } else step(rr, valid, 1u);          // (a shallow data set, or a hash-selected part of a split leaf)
-                    rr = nx;
-                }
-                if (agg) {
-                    // every record of the leaf has been counted: the distinct ones become weighted k-mers (the wave takes
-                    // its block of slots and leaves it empty, whatever became of the pass); what the wave still has
-                    // parked goes with them
-                    __syncthreads();
-                    const uint32_t slot = (uint32_t)(wave_ * 64 + lane_);
-                    const unsigned long long a_ = rA[slot], bc = rBC[slot];
-                    const bool have = bc != EMPTY;
-                    if (a_ != EMPTY) { rA[slot] = EMPTY; rBC[slot] = EMPTY; }
-                    {
-                        const uint32_t used = (uint32_t)__popcll(__ballot(have));
-                        if (lane_ == 0 && hits != used) atomicAdd(&agg_saved, hits - used);      // (modulo 2^32: the sum is >= 0)
-                    }
-                    if (dbg & 128) {
-                        uint32_t w = have ? (uint32_t)((bc >> 32) & 15) + 1u : 0u;
-                        for (int o = 32; o > 0; o >>= 1) w += __shfl_xor(w, o, 64);
-                        const uint64_t mh = __ballot(have);
-                        if (lane_ == 0) { atomicAdd(&co->r_slots, (unsigned long long)__popcll(mh)); atomicAdd(&co->w_table, (unsigned long long)w); }
-                    }
-                    if (!__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
-                        park(Rec{(uint64_t)a_, (uint64_t)(bc >> 32) << 32}, have, (uint32_t)bc);
-                }
-#pragma nounroll
-                while (parked) flush_parked();
-            } else {
-#pragma unroll
-                for (int i = 0; i < RPF; i++) {
-                    const uint64_t r0 = ws + 64u * i;
-                    // an overflowing pass is abandoned: stop feeding a table that is filling up
-                    if (r0 < we && !__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) step(cur[i], r0 + lane_ < we, 1u);
-                }
-                for (uint64_t r0 = ws + 64u * RPF; r0 < we; r0 += 64) {
-                    if (__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
-                    const bool valid = r0 + lane_ < we;
-                    step(valid ? keys[r0 + lane_] : Rec{0, 0}, valid, 1u);
-                }
-                drain_queue();
-            }
-        } else {
-            for (uint64_t base = begin; base < end; base += (uint64_t)LT * NB) {
+            static_assert(RPF == 1, "the first 64-record step of a wave comes from registers");
+            Rec rr = cur[0];
+            for (uint64_t r0 = ws; r0 < we; r0 += 64) {
                 // an overflowing pass is abandoned: stop feeding a table that is filling up
                 if (__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
+                const bool valid = r0 + lane_ < we;
+                // (the wave's next 64 records travel while these are counted)
+                const Rec nx = r0 + 64 + lane_ < we ? keys[r0 + 64 + lane_] : Rec{0, 0};
+                if (agg) {
+                    const bool placed = place(rr, valid);
+                    hits += (uint32_t)__popcll(__ballot(placed));
+                    park(rr, valid && !placed, 1u);
+                } else step(rr, valid, 1u);          // (a shallow data set, or a hash-selected part of a split leaf)
+                rr = nx;
+            }
+            if (agg) {
+                // every record of the leaf has been counted: the distinct ones become weighted k-mers (the wave takes
+                // its block of slots and leaves it empty, whatever became of the pass); what the wave still has
+                // parked goes with them
+                __syncthreads();
+                const uint32_t slot = (uint32_t)(wave_ * 64 + lane_);
+                const unsigned long long a_ = rA[slot], bc = rBC[slot];
+                const bool have = bc != EMPTY;
+                if (a_ != EMPTY) { rA[slot] = EMPTY; rBC[slot] = EMPTY; }
+                {
+                    const uint32_t used = (uint32_t)__popcll(__ballot(have));
+                    if (lane_ == 0 && hits != used) atomicAdd(&agg_saved, hits - used);      // (modulo 2^32: the sum is >= 0)
+                }
+                if (!__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
+                    park(Rec{(uint64_t)a_, (uint64_t)(bc >> 32) << 32}, have, (uint32_t)bc);
+            }
+#pragma nounroll
+            while (parked) flush_parked();
+        } else {
+            for (uint64_t base = begin; base < end; base += (uint64_t)LT * NB) {
                 Elem kc[NB];
                 if (pf == base) {
 #pragma unroll
@@ -1101,10 +935,10 @@ __global__ __launch_bounds__(LT, RFX_LEAF_WAVES_PER_EU) void k_leaf_count(const 
                 // next batch of this leaf, or the first batch of the next leaf
                 const uint64_t nxt = base + (uint64_t)LT * NB < end ? base + (uint64_t)LT * NB : begin_next;
                 if (nxt < stream_end && nxt != pf) prefetch(nxt);
-                if (dbg & 1) {       // ablation: stream only
-                    if (LeafElem<ELEM>::key(kc[0]) == 0x123456789ULL) overflow = 1;
-                    continue;
-                }
+                // an overflowing pass is abandoned: stop feeding a table that is filling up.  (The rest of the leaf
+                // still streams through, so the next leaf's first batch stays in flight.  A `break` at the top of the
+                // loop measured 18 spilled VGPRs instead of 11 in k_leaf_count<0>, and one VGPR more in <2>.)
+                if (__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) continue;
                 static_assert(RECS || NB % 2 == 0, "pairs");
 #pragma unroll
                 for (int j = 0; j + 1 < NB; j += 2)
@@ -1174,8 +1008,7 @@ __global__ __launch_bounds__(LT, RFX_LEAF_WAVES_PER_EU) void k_leaf_count(const 
             *(ulonglong2 *)&tkey[4 * c4] = make_ulonglong2(EMPTY, EMPTY);
             *(ulonglong2 *)&tkey[4 * c4 + 2] = make_ulonglong2(EMPTY, EMPTY);
         }
-        if (dbg & 32) { const long long t0 = clock64(); __syncthreads(); t_wait += clock64() - t0; }
-        else __syncthreads();
+        __syncthreads();
         const uint32_t raw = ob_n, lim = ob_lim;      // stable until the next emit_pass
         if (raw >= (uint32_t)OB1 / 2 || lim != 0xffffffffu) flush();
     };
@@ -1201,8 +1034,7 @@ __global__ __launch_bounds__(LT, RFX_LEAF_WAVES_PER_EU) void k_leaf_count(const 
             run_pass(S, s, first, begin_next, end_next);        // (an empty leaf still hands the prefetch chain on)
             first = false;
             if (begin == end) break;
-            if (dbg & 32) { const long long t0 = clock64(); __syncthreads(); t_wait += clock64() - t0; }
-            else __syncthreads();
+            __syncthreads();
             const bool ov = overflow != 0;
             if (threadIdx.x == 0) my_passes++;
             if (!ov) {
@@ -1219,7 +1051,7 @@ __global__ __launch_bounds__(LT, RFX_LEAF_WAVES_PER_EU) void k_leaf_count(const 
                 // (before emit_pass, whose closing barrier stands between this store and the next leaf's read of ps_eff:
                 // after it, a workgroup whose threads saw different thresholds would disagree on S and on its barriers)
                 if (threadIdx.x == 0 && S == 1 && end - begin > (uint64_t)ps_eff * 3 / 4 && ps_eff < (1u << 24)) ps_eff += ps_eff / 64 + 1;
-                if constexpr (AGG) {
+                if constexpr (RECS) {
                     if (threadIdx.x == 0 && S == 1 && agg_on) {
                         agg_total += (uint32_t)(end - begin);
                         if (agg_total >= 8192u) {
@@ -1283,51 +1115,26 @@ __global__ __launch_bounds__(LT, RFX_LEAF_WAVES_PER_EU) void k_leaf_count(const 
         atomicAdd(&co->n_passes, my_passes);
         if (my_overflows) atomicAdd(&co->n_overflow, my_overflows);
     }
-    if ((dbg & 32) && lane_ == 0) {
-        atomicAdd(&co->t_wait, (unsigned long long)t_wait);
-        atomicAdd(&co->t_all, (unsigned long long)(clock64() - t_begin));
-    }
 }
 
-// ---- leaves of the k > 32 path: two-word keys.  No 128-bit LDS atomic exists, so a slot is
-// claimed through its count word: 0 = empty, WLOCK = being written, otherwise the count.  The
-// claimer writes both key words and then publishes count 1; a lane that meets WLOCK tries the same
-// slot again on the next trip round a loop that the WHOLE WAVE leaves together (ballot) -- so the
-// publish of a neighbouring lane can never sit on an exit path the spinning lane keeps it from
-// reaching -- and a lane that meets a count compares the (now immutable) key words.  Same structure otherwise: persistent workgroups over
-// contiguous leaf chunks, two barriers per leaf, table sweep, split on overflow.
-#ifndef RFX_WCAP_BITS
-#define RFX_WCAP_BITS 12
-#endif
-#ifndef RFX_WLT
-#define RFX_WLT 1024
-#endif
-#ifndef RFX_WCAP_X3
-#define RFX_WCAP_X3 0
-#endif
-constexpr int WCAP_BITS = RFX_WCAP_BITS;
-constexpr int WCAP = RFX_WCAP_X3 ? 3 << (WCAP_BITS - 1) : 1 << WCAP_BITS;     // 2^bits slots, or three halves of that
-__device__ __forceinline__ uint32_t wide_slot(uint32_t g) {
-    return RFX_WCAP_X3 ? ((g >> (31 - WCAP_BITS)) * 3u) >> 2 : g >> (32 - WCAP_BITS);
-}
-__device__ __forceinline__ uint32_t wide_step(uint32_t g) {          // prime to the slot count
-    return RFX_WCAP_X3 ? ((g >> 8) & ((1u << (WCAP_BITS - 2)) - 1u)) * 6u + 1u : (((g >> 8) & (WCAP - 1)) | 1u);
-}
-__device__ __forceinline__ uint32_t wide_next(uint32_t slot, uint32_t step) {
-    if (!RFX_WCAP_X3) return (slot + step) & (WCAP - 1);
-    const uint32_t x = slot + step;
-    return x >= (uint32_t)WCAP ? x - WCAP : x;
-}
-// 1024 threads, 4096 slots, a queue of probe attempts per wave (RFX_WIDE_QUEUE) and a 64-entry survivor buffer -- all the
-// LDS there is: 31.1 ms at k = 63 (768 threads: 34.0, 896: 33.1).  Measured on the
-// way: 1024 threads and 4096 slots 44.2 ms, 768 threads and 6144 slots (RFX_WCAP_X3: the site-laden leaves split less
-// often) 39.5 ms, two workgroups of 2048 slots per CU 55 ms, 512 threads with the queue 41.5 ms
-constexpr int WLT = RFX_WLT;            // threads per workgroup
-#ifndef RFX_WOBUF
-#define RFX_WOBUF 64
-#endif
-constexpr int WOBUF = RFX_WOBUF;        // survivors buffered in LDS between flushes
-constexpr uint32_t WLOCK = 0xFFFFFFFFu;
+// ---- leaves of the k > 32 path: two-word keys.  No 128-bit LDS atomic exists, so the two key words of a slot are
+// claimed by two 64-bit compare-and-swaps, one after the other -- word 0 first; a key that meets its own word 0 (or an
+// empty one) goes on to word 1, one that meets another value in either moves to its next slot -- so whatever order the
+// claims land in a slot names ONE key, nothing is ever locked, nobody spins, and a compare-and-swap's return value IS
+// the key word (no 16-byte read to compare).  EMPTY = all ones in both words: word 1 holds k - 32 <= 31 bases, and
+// word 0 of a CANONICAL k-mer is never 32 T's (its reverse complement would begin with at most 31 T's and an A, and be
+// the smaller one).  Same structure otherwise: persistent workgroups over contiguous leaf chunks, two barriers per leaf,
+// table sweep, split on overflow.
+// 1024 threads, 4096 slots and a 64-entry survivor buffer take all the LDS there is (measured at k = 63 with the
+// lock-based first form: 31.1 ms; 768 threads 34.0, 896 threads 33.1, 768 threads and 6144 slots 39.5, two workgroups
+// of 2048 slots per CU 55)
+constexpr int WCAP_BITS = 12;
+constexpr int WCAP = 1 << WCAP_BITS;    // hash slots
+__device__ __forceinline__ uint32_t wide_slot(uint32_t g) { return g >> (32 - WCAP_BITS); }
+__device__ __forceinline__ uint32_t wide_step(uint32_t g) { return ((g >> 8) & (WCAP - 1)) | 1u; }   // odd: prime to WCAP
+__device__ __forceinline__ uint32_t wide_next(uint32_t slot, uint32_t step) { return (slot + step) & (WCAP - 1); }
+constexpr int WLT = 1024;               // threads per workgroup
+constexpr int WOBUF = 64;               // survivors buffered in LDS between flushes
 
 // canonical two-word k-mer (counter layout: word0 = bases 0..31, word1 = the last t = k - 32 bases,
 // right-aligned) of window j of a record's base string -- compareLongArrayBlocks' order
@@ -1347,37 +1154,13 @@ __device__ __forceinline__ void wrec_kmer(const WRec &r, uint32_t j, int t, uint
     *k1 = fwd ? f1 : r1;
 }
 
-// RFX_WIDE_LOCKFREE (round 3): the two key words of a slot are claimed by two 64-bit compare-and-swaps, one after the
-// other -- word 0 first; a key that meets its own word 0 (or an empty one) goes on to word 1, one that meets another
-// value in either moves to its next slot -- so whatever order the claims land in a slot names ONE key, nothing is ever
-// locked, nobody spins, and a compare-and-swap's return value IS the key word (no 16-byte read to compare).  EMPTY = all
-// ones in both words: word 1 holds k - 32 <= 31 bases, and word 0 of a CANONICAL k-mer is never 32 T's (its reverse
-// complement would begin with at most 31 T's and an A, and be the smaller one).  With no lock there is no loop the wave
-// must leave together and no need for the queue of attempts that replaced it.
-#ifndef RFX_WIDE_LOCKFREE
-#define RFX_WIDE_LOCKFREE 1
-#endif
-#ifndef RFX_WIDE_QUEUE
-#define RFX_WIDE_QUEUE (RFX_WIDE_LOCKFREE ? 0 : 1)
-#endif
-constexpr int WQCAP = RFX_WIDE_QUEUE ? 128 : 0;   // probe attempts a wave has pending (record leaves)
-// RFX_WIDE_AGG: the record table of the two-word leaf (see RFX_LEAF_AGG): a slot is (bases 0..31, bases 32..63, the
-// rest of the record's own bases | windows - 1 | count), claimed field by field -- a record that meets a slot whose
-// fields are not all its own moves on, so whatever order the claims land in, a slot names one record.
-#ifndef RFX_WIDE_AGG
-#define RFX_WIDE_AGG 1
-#endif
-#ifndef RFX_WRSLOTS
-#define RFX_WRSLOTS 1024
-#endif
-constexpr int WRSLOTS = RFX_WRSLOTS;    // record slots: 1024 (every wave sweeps a block of 64; 768: 26.9 ms instead of 26.1 at k = 63), 768 or 512
-constexpr int WRMAX = 8191;             // records of a leaf that goes through the table (a weight takes 13 bits of a queue entry)
-#ifndef RFX_WPARK
-#define RFX_WPARK (RFX_WIDE_AGG && RFX_WIDE_QUEUE ? 32 : 64)
-#endif
-constexpr int WPARK = RFX_WPARK;        // records a wave parks before it expands them
-constexpr int WWS0 = WPARK * 4 + 32;    // u64 words of a wave's expansion area: the parked records + head bits + prefix counts
-constexpr int WWS = WWS0 + WQCAP * 2 + WQCAP / 2;   // ... + the queue: 16-byte keys, then 4-byte (slot | probes << 16)
+// The record table of the two-word leaf (see k_leaf_count): a slot is (bases 0..31, bases 32..63, the rest of the
+// record's own bases | windows - 1 | count), claimed field by field -- a record that meets a slot whose fields are not
+// all its own moves on, so whatever order the claims land in, a slot names one record.
+constexpr int WRSLOTS = 1024;           // record slots: every wave sweeps a block of 64 (768: 26.9 ms instead of 26.1 at k = 63)
+constexpr int WRMAX = 8191;             // records of a leaf that goes through the table
+constexpr int WPARK = 64;               // records a wave parks before it expands them
+constexpr int WWS = WPARK * 4 + 32;     // u64 words of a wave's expansion area: the parked records + head bits + prefix counts
 
 // RECS: the leaf's elements are super-k-mer records (WRec) expanded here, k-mer by k-mer, balanced over the
 // lanes as in k_leaf_count<1>; else two-word k-mers (Rec = {word0, word1}).
@@ -1388,15 +1171,11 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wide(const std::conditional_
                                                         uint64_t *__restrict__ out_keys, int64_t *__restrict__ out_counts,
                                                         unsigned long long cap, CountOut *__restrict__ co, uint32_t presplit) {
     __shared__ __attribute__((aligned(32))) uint64_t wstage[RECS ? WWS * (WLT / 64) : 4];
-    const bool dh = !(presplit & 0x20000000u);
     __shared__ uint32_t ps_eff;              // records one table takes (starts at `presplit`, shrinks on overflow)
-    constexpr bool LF = RFX_WIDE_LOCKFREE != 0;
-    __shared__ __attribute__((aligned(16))) ulonglong2 tk[LF ? 1 : WCAP];     // (lock form) both key words of a slot in one 16-byte LDS access
-    __shared__ unsigned long long tk0[LF ? WCAP : 1], tk1[LF ? WCAP : 1];       // (lock-free form) a plane per key word
+    __shared__ unsigned long long tk0[WCAP], tk1[WCAP];                          // a plane per key word
     __shared__ uint32_t tcnt[WCAP];
-    constexpr bool WAGG = RECS && RFX_WIDE_AGG != 0;
-    static_assert(!WAGG || ((WQCAP > 0 || LF) && WRSLOTS % 64 == 0 && WRSLOTS <= WLT), "record table");
-    __shared__ unsigned long long rA[WAGG ? WRSLOTS : 1], rB[WAGG ? WRSLOTS : 1], rCC[WAGG ? WRSLOTS : 1];
+    static_assert(WRSLOTS % 64 == 0 && WRSLOTS <= WLT, "record table");
+    __shared__ unsigned long long rA[RECS ? WRSLOTS : 1], rB[RECS ? WRSLOTS : 1], rCC[RECS ? WRSLOTS : 1];
     __shared__ uint32_t agg_on, agg_saved, agg_total;       // (as in k_leaf_count)
     __shared__ unsigned long long obh[WOBUF], obl[WOBUF];
     __shared__ uint32_t obc[WOBUF];
@@ -1411,11 +1190,11 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wide(const std::conditional_
     const int64_t l1 = (int64_t)(((unsigned long long)(blockIdx.x + 1) * (unsigned long long)nleaf) / gridDim.x);
     if (l0 >= l1) return;
     for (int i = threadIdx.x; i < WCAP; i += WLT) tcnt[i] = 0;
-    if constexpr (LF) for (int i = threadIdx.x; i < WCAP; i += WLT) { tk0[i] = EMPTY; tk1[i] = EMPTY; }
-    if constexpr (WAGG) for (int i = threadIdx.x; i < WRSLOTS; i += WLT) { rA[i] = EMPTY; rB[i] = EMPTY; rCC[i] = EMPTY; }
+    for (int i = threadIdx.x; i < WCAP; i += WLT) { tk0[i] = EMPTY; tk1[i] = EMPTY; }
+    if constexpr (RECS) for (int i = threadIdx.x; i < WRSLOTS; i += WLT) { rA[i] = EMPTY; rB[i] = EMPTY; rCC[i] = EMPTY; }
     if (threadIdx.x == 0) {
         ob_n = 0; ob_lim = 0xffffffffu; overflow = 0; sp = 0;
-        ps_eff = (presplit & 0xffffffu) ? (presplit & 0xffffffu) : 0xffffffffu;
+        ps_eff = presplit ? presplit : 0xffffffffu;
         agg_on = 1; agg_saved = 0; agg_total = 0;
     }
     __syncthreads();
@@ -1463,140 +1242,37 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wide(const std::conditional_
             }
         }
         while (begin != end) {
-            // one pass: the keys selected by (S, s) go into the table
-            // one key into the table.  The first probe is straight-line code (nine in ten meet the key itself);
-            // the rest runs in a loop the WHOLE WAVE leaves together (ballot): a lane that leaves a loop early
-            // waits at the exit for the others, and code on an exit path -- a `break` after the publish -- runs
-            // only then, so a lane spinning on a lock its neighbour holds would spin for ever.  Here every
-            // publish sits inside an iteration every lane completes, and the claim of a first probe is
-            // published before anyone waits.
-            // lock-free form: the first probe straight-line (most keys are in the table already), the rest in a loop of the
-            // lane's own
+            // one pass: the keys selected by (S, s) go into the table.  One key into the table: the first probe
+            // straight-line (most keys are in the table already), the rest in a loop of the lane's own.  Double hashing:
+            // an odd step from other hash bits (the whole wave waits for its longest probe sequence, and linear
+            // probing's clusters make that one long when a leaf fills its table).
+            // (wgt: the k-mer stands for that many instances -- the count of the record it was cut from)
             auto insertw = [&](const uint64_t w0, const uint64_t w1, bool v, const uint32_t wgt) __attribute__((always_inline)) {
-                if constexpr (LF) {
-                    const uint32_t g = ((uint32_t)w0 ^ __builtin_rotateleft32((uint32_t)(w0 >> 32), 13) ^
-                                        ((uint32_t)w1 * 0x85EBCA6Bu) ^ (uint32_t)(w1 >> 32)) * 0x9E3779B1u;
-                    v = v && ((g >> 4) & ((S - 1u) & 0xffffu)) == s;       // (one part: mask 0, s = 0)
-                    uint32_t slot = wide_slot(g);
-                    bool done = !v;
-                    if (v) {
-                        const unsigned long long p0 = atomicCAS(&tk0[slot], EMPTY, (unsigned long long)w0);
-                        if (p0 == EMPTY || p0 == w0) {
-                            const unsigned long long p1 = atomicCAS(&tk1[slot], EMPTY, (unsigned long long)w1);
-                            if (p1 == EMPTY || p1 == w1) { atomicAdd(&tcnt[slot], wgt); done = true; }
-                        }
-                    }
-                    if (!done) {
-                        const uint32_t step = dh ? wide_step(g) : 1u;
-#pragma nounroll
-                        for (int probe = 1;; probe++) {
-                            slot = wide_next(slot, step);
-                            const unsigned long long p0 = atomicCAS(&tk0[slot], EMPTY, (unsigned long long)w0);
-                            if (p0 == EMPTY || p0 == w0) {
-                                const unsigned long long p1 = atomicCAS(&tk1[slot], EMPTY, (unsigned long long)w1);
-                                if (p1 == EMPTY || p1 == w1) { atomicAdd(&tcnt[slot], wgt); break; }
-                            }
-                            if (probe >= LPROBE) { overflow = 1; break; }
-                        }
-                    }
-                }
-            };
-            auto insert1 = [&](const uint64_t w0, const uint64_t w1, bool v) __attribute__((always_inline)) {
-                if constexpr (LF) { insertw(w0, w1, v, 1u); return; }
                 const uint32_t g = ((uint32_t)w0 ^ __builtin_rotateleft32((uint32_t)(w0 >> 32), 13) ^
                                     ((uint32_t)w1 * 0x85EBCA6Bu) ^ (uint32_t)(w1 >> 32)) * 0x9E3779B1u;
                 v = v && ((g >> 4) & ((S - 1u) & 0xffffu)) == s;       // (one part: mask 0, s = 0)
                 uint32_t slot = wide_slot(g);
-                // double hashing: an odd step from other hash bits (the whole wave waits for its longest probe
-                // sequence, and linear probing's clusters make that one long when a leaf fills its table)
-                const uint32_t step = dh ? wide_step(g) : 1u;
-                uint32_t c = 1u;
-                if (v) c = atomicCAS(&tcnt[slot], 0u, WLOCK);
-                if (v && c == 0u) {                                   // claimed: write the key, publish count 1
-                    tk[slot] = make_ulonglong2(w0, w1);
-                    __threadfence_block();
-                    atomicExch(&tcnt[slot], 1u);
-                }
-                const bool h = v && c != 0u && c != WLOCK;
-                const ulonglong2 t01 = h ? tk[slot] : make_ulonglong2(0, 0);
-                const bool hit = h && t01.x == w0 && t01.y == w1;
-                if (hit) atomicAdd(&tcnt[slot], 1u);
-                int probe = 0;
-                bool done = !v || c == 0u || hit;
-                while (__ballot(!done)) {
-                    if (!done) {
-                        if (c == 0u) {
-                            tk[slot] = make_ulonglong2(w0, w1);
-                            __threadfence_block();
-                            atomicExch(&tcnt[slot], 1u);
-                            done = true;
-                        } else if (c != WLOCK) {
-                            const ulonglong2 t = tk[slot];
-                            if (t.x == w0 && t.y == w1) { atomicAdd(&tcnt[slot], 1u); done = true; }
-                            else {
-                                slot = wide_next(slot, step);
-                                if (++probe >= LPROBE) { overflow = 1; done = true; }
-                            }
-                        }
-                        if (!done) c = atomicCAS(&tcnt[slot], 0u, WLOCK);   // next slot, or the same one while it is being written
-                    }
-                }
-            };
-            // Record leaves, RFX_WIDE_QUEUE: probing as a queue of ATTEMPTS.  An attempt looks at one slot: empty -> claim,
-            // write the key, publish; the key itself -> count; another key -> the next slot of the sequence; a slot
-            // being written -> the same slot again.  An attempt that did not finish the key goes (back) to the wave's
-            // queue, and whenever 64 wait they are made together, one per lane.  No lane ever waits for another, so there is
-            // no loop the wave must leave together, and the wave pays the AVERAGE number of probes per key instead of
-            // the longest sequence among 64 in every round (site-laden leaves run their tables at 60-80 %).
-            uint32_t qn = 0;
-            ulonglong2 *wqk = (ulonglong2 *)(wstage + (size_t)(threadIdx.x >> 6) * WWS + WWS0);
-            uint32_t *wqs = (uint32_t *)(wqk + WQCAP);
-            // (wgt: the k-mer stands for that many instances -- the count of the record it was cut from)
-            auto attempt = [&](const uint64_t w0, const uint64_t w1, uint32_t slot, uint32_t probe, bool v, uint32_t wgt) __attribute__((always_inline)) {
-                uint32_t c = 1u;
-                if (v) c = atomicCAS(&tcnt[slot], 0u, WLOCK);
                 bool done = !v;
                 if (v) {
-                    if (c == 0u) {
-                        tk[slot] = make_ulonglong2(w0, w1);
-                        __threadfence_block();
-                        atomicExch(&tcnt[slot], wgt);
-                        done = true;
-                    } else if (c != WLOCK) {
-                        const ulonglong2 t = tk[slot];
-                        if (t.x == w0 && t.y == w1) { atomicAdd(&tcnt[slot], wgt); done = true; }
-                        else {
-                            const uint32_t g = ((uint32_t)w0 ^ __builtin_rotateleft32((uint32_t)(w0 >> 32), 13) ^
-                                                ((uint32_t)w1 * 0x85EBCA6Bu) ^ (uint32_t)(w1 >> 32)) * 0x9E3779B1u;
-                            slot = wide_next(slot, dh ? wide_step(g) : 1u);
-                            if (++probe >= (uint32_t)LPROBE) { overflow = 1; done = true; }
-                        }
+                    const unsigned long long p0 = atomicCAS(&tk0[slot], EMPTY, (unsigned long long)w0);
+                    if (p0 == EMPTY || p0 == w0) {
+                        const unsigned long long p1 = atomicCAS(&tk1[slot], EMPTY, (unsigned long long)w1);
+                        if (p1 == EMPTY || p1 == w1) { atomicAdd(&tcnt[slot], wgt); done = true; }
                     }
                 }
-                const uint64_t m = __ballot(!done);
-                if (m) {
-                    const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                    if (!done) { wqk[qn + r] = make_ulonglong2(w0, w1); wqs[qn + r] = slot | (probe << 13) | (wgt << 19); }
-                    qn += (uint32_t)__popcll(m);
-                }
-                __builtin_amdgcn_wave_barrier();
-            };
-            auto pending = [&](uint32_t n) __attribute__((always_inline)) {      // the top n <= 64 entries of the queue
-                qn -= n;
-                const bool v = (uint32_t)lane_ < n;
-                const ulonglong2 key = v ? wqk[qn + lane_] : make_ulonglong2(0, 0);
-                const uint32_t st = v ? wqs[qn + lane_] : 0u;
-                __builtin_amdgcn_wave_barrier();
-                attempt(key.x, key.y, st & 0x1fffu, (st >> 13) & 63u, v, st >> 19);
-            };
-            static_assert(WCAP <= 8192 && LPROBE < 64, "a queue entry: 13 bits of slot, 6 of probes, 13 of weight");
-            auto insertq = [&](const uint64_t w0, const uint64_t w1, bool v, uint32_t wgt) __attribute__((always_inline)) {
-                const uint32_t g = ((uint32_t)w0 ^ __builtin_rotateleft32((uint32_t)(w0 >> 32), 13) ^
-                                    ((uint32_t)w1 * 0x85EBCA6Bu) ^ (uint32_t)(w1 >> 32)) * 0x9E3779B1u;
-                v = v && ((g >> 4) & ((S - 1u) & 0xffffu)) == s;       // (one part: mask 0, s = 0)
-                attempt(w0, w1, wide_slot(g), 0u, v, wgt);
+                if (!done) {
+                    const uint32_t step = wide_step(g);
 #pragma nounroll
-                while (qn >= 64u) pending(64u);
+                    for (int probe = 1;; probe++) {
+                        slot = wide_next(slot, step);
+                        const unsigned long long p0 = atomicCAS(&tk0[slot], EMPTY, (unsigned long long)w0);
+                        if (p0 == EMPTY || p0 == w0) {
+                            const unsigned long long p1 = atomicCAS(&tk1[slot], EMPTY, (unsigned long long)w1);
+                            if (p1 == EMPTY || p1 == w1) { atomicAdd(&tcnt[slot], wgt); break; }
+                        }
+                        if (probe >= LPROBE) { overflow = 1; break; }
+                    }
+                }
             };
             if constexpr (RECS) {
                 // every wave takes an equal contiguous share of the leaf, 64 records at a time.  A record is first counted
@@ -1613,7 +1289,7 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wide(const std::conditional_
                 uint32_t *wbits = (uint32_t *)(wrec + WPARK);
                 uint32_t *wcum = wbits + 32;
                 const int t = k - 32;
-                const bool agg = WAGG && n <= (uint64_t)WRMAX && !(presplit & 0x10000000u) && agg_on;      // (every hash-selected part of a split leaf too)
+                const bool agg = n <= (uint64_t)WRMAX && agg_on;      // (every hash-selected part of a split leaf too)
                 uint32_t hits = 0;
                 uint32_t parked = 0;                                 // wave-uniform
                 auto kmer_at_pos = [&](uint32_t j, uint64_t *k0, uint64_t *k1, uint32_t *wgt) __attribute__((always_inline)) {
@@ -1647,13 +1323,7 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wide(const std::conditional_
                         uint64_t a0, a1;
                         uint32_t wg;
                         kmer_at_pos(va ? ja : 0, &a0, &a1, &wg);
-                        if (presplit & 0x40000000u) {                       // ablation (RFX_WIDE_DBG=1): expand, no table
-                            if (va && (a0 ^ a1) == 0x123456789ULL) overflow = 1;
-                            continue;
-                        }
-                        if constexpr (LF) insertw(a0, a1, va, wg);
-                        else if constexpr (WQCAP > 0) insertq(a0, a1, va, wg);
-                        else insert1(a0, a1, va);
+                        insertw(a0, a1, va, wg);
                     }
                     __builtin_amdgcn_wave_barrier();
                     parked = 0;
@@ -1675,7 +1345,6 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wide(const std::conditional_
                 };
                 // the record's own bases: k - 1 + windows of them; what follows in b1 / b2 is whatever followed in the read
                 auto place = [&](const WRec &r, bool valid) __attribute__((always_inline)) -> bool {
-                    if constexpr (!WAGG) return false;
                     if (!agg || !valid) return false;
                     const uint32_t nw1 = (uint32_t)(r.hd >> 32) & 15u;
                     const int ub = 2 * (k + (int)nw1);                             // bits of the base string in use (66..156)
@@ -1684,8 +1353,8 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wide(const std::conditional_
                     if (r.b0 == EMPTY || b1 == EMPTY) return false;
                     const uint32_t h = ((uint32_t)r.b0 ^ __builtin_rotateleft32((uint32_t)(r.b0 >> 32), 13) ^ __builtin_rotateleft32((uint32_t)b1, 7) ^
                                         __builtin_rotateleft32((uint32_t)(b1 >> 32), 19) ^ (c * 0x85EBCA6Bu)) * 0x9E3779B1u;
-                    uint32_t slot = WRSLOTS == 768 ? ((h >> 22) * 3u) >> 2 : WRSLOTS == 1024 ? h >> 22 : h >> 23;
-                    static_assert(WRSLOTS == 768 || WRSLOTS == 512 || WRSLOTS == 1024, "slot = three quarters of ten hash bits, ten, or nine");
+                    uint32_t slot = h >> 22;
+                    static_assert(WRSLOTS == 1024, "slot = ten hash bits");
 #pragma unroll
                     for (int probe = 0; probe < RPROBE; probe++) {
                         const unsigned long long pa = atomicCAS(&rA[slot], EMPTY, (unsigned long long)r.b0);
@@ -1715,51 +1384,32 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wide(const std::conditional_
                     nxt = r0 + 64 + lane_ < we ? elems[r0 + 64 + lane_] : WRec{0, 0, 0, 0};   // travels during the expansion
                     const bool un = valid && !place(rc, valid);
                     hits += (uint32_t)__popcll(__ballot(valid && !un));
-                    if (presplit & 0x08000000u) {                           // RFX_WIDE_DBG=... statistics
-                        const uint64_t mp = __ballot(valid && !un), md = __ballot(un);
-                        if (lane_ == 0) { atomicAdd(&co->r_placed, (unsigned long long)__popcll(mp)); atomicAdd(&co->r_direct, (unsigned long long)__popcll(md)); }
-                    }
-                    if constexpr (WPARK >= 64) park(rc, un, 1u);
-                    else {
-#pragma nounroll
-                        for (int hf = 0; hf < 64 / WPARK; hf++) park(rc, un && lane_ / WPARK == hf, 1u);
-                    }
+                    park(rc, un, 1u);
                 }
-                if constexpr (WAGG) {
-                    if (agg) {
-                        __syncthreads();                             // every record of the leaf is counted
-                        const uint32_t slot = (uint32_t)(wave_ * 64 + lane_);
-                        const bool mine = slot < (uint32_t)WRSLOTS;
-                        const unsigned long long a_ = mine ? rA[slot] : EMPTY, b_ = mine ? rB[slot] : EMPTY, cc = mine ? rCC[slot] : EMPTY;
-                        const bool have = cc != EMPTY;
-                        if (a_ != EMPTY) { rA[slot] = EMPTY; rB[slot] = EMPTY; rCC[slot] = EMPTY; }
-                        {
-                            const uint32_t used = (uint32_t)__popcll(__ballot(have));
-                            if (lane_ == 0 && hits != used) atomicAdd(&agg_saved, hits - used);
-                        }
-                        if (presplit & 0x08000000u) {
-                            const uint64_t mh = __ballot(have);
-                            if (lane_ == 0) atomicAdd(&co->r_slots, (unsigned long long)__popcll(mh));
-                        }
-                        if (!__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
-                            const uint32_t c = (uint32_t)(cc >> 32);
-                            const WRec rr{(uint64_t)a_, (uint64_t)b_, (uint64_t)(c & 0xfffffff0u) << 32, (uint64_t)(c & 15u) << 32};
-#pragma nounroll
-                            for (int hf = 0; hf < 64 / WPARK; hf++) park(rr, have && lane_ / WPARK == hf, (uint32_t)cc);
-                        }
+                if (agg) {
+                    __syncthreads();                             // every record of the leaf is counted
+                    const uint32_t slot = (uint32_t)(wave_ * 64 + lane_);
+                    const bool mine = slot < (uint32_t)WRSLOTS;
+                    const unsigned long long a_ = mine ? rA[slot] : EMPTY, b_ = mine ? rB[slot] : EMPTY, cc = mine ? rCC[slot] : EMPTY;
+                    const bool have = cc != EMPTY;
+                    if (a_ != EMPTY) { rA[slot] = EMPTY; rB[slot] = EMPTY; rCC[slot] = EMPTY; }
+                    {
+                        const uint32_t used = (uint32_t)__popcll(__ballot(have));
+                        if (lane_ == 0 && hits != used) atomicAdd(&agg_saved, hits - used);
+                    }
+                    if (!__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
+                        const uint32_t c = (uint32_t)(cc >> 32);
+                        const WRec rr{(uint64_t)a_, (uint64_t)b_, (uint64_t)(c & 0xfffffff0u) << 32, (uint64_t)(c & 15u) << 32};
+                        park(rr, have, (uint32_t)cc);
                     }
                 }
 #pragma nounroll
                 while (parked) flush_parked();
-                if constexpr (WQCAP > 0) {
-#pragma nounroll
-                    while (qn > 0u && !__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) pending(qn < 64u ? qn : 64u);
-                }
             } else {
                 for (uint64_t i = begin + threadIdx.x; i < end; i += WLT) {
                     if (__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
                     const Rec e = elems[i];
-                    insert1(e.w0, e.w1, true);
+                    insertw(e.w0, e.w1, true, 1u);
                 }
             }
             __syncthreads();
@@ -1769,7 +1419,7 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wide(const std::conditional_
                 // (the threshold moves BEFORE the sweep, whose closing barrier stands between this store and the next
                 // leaf's read of ps_eff: threads that saw different thresholds would disagree on S and on their barriers)
                 if (RECS && threadIdx.x == 0 && S == 1 && end - begin > (uint64_t)ps_eff * 3 / 4 && ps_eff < (1u << 24)) ps_eff += ps_eff / 64 + 1;
-                if constexpr (WAGG) {
+                if constexpr (RECS) {
                     if (threadIdx.x == 0 && agg_on && end - begin <= (uint64_t)WRMAX) {
                         agg_total += (uint32_t)(end - begin);
                         if (agg_total >= 8192u) {
@@ -1796,7 +1446,7 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wide(const std::conditional_
                         if (lane_ == leader) b0 = atomicAdd(&ob_n, cntw);
                         b0 = (uint32_t)__builtin_amdgcn_readlane((int)b0, leader);
                         if (b0 + cntw <= (uint32_t)WOBUF) {
-                            if (keep) { const ulonglong2 t = LF ? make_ulonglong2(tk0[slot], tk1[slot]) : tk[slot]; obh[b0 + r] = t.x; obl[b0 + r] = t.y; obc[b0 + r] = c; }
+                            if (keep) { const uint64_t t0 = tk0[slot], t1 = tk1[slot]; obh[b0 + r] = t0; obl[b0 + r] = t1; obc[b0 + r] = c; }
                         } else {
                             uint32_t glo = 0, ghi = 0;
                             if (lane_ == leader) {
@@ -1808,20 +1458,20 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wide(const std::conditional_
                             ghi = (uint32_t)__builtin_amdgcn_readlane((int)ghi, leader);
                             const unsigned long long pos = (((unsigned long long)ghi << 32) | glo) + r;
                             if (keep && pos < cap) {
-                                const ulonglong2 t = LF ? make_ulonglong2(tk0[slot], tk1[slot]) : tk[slot];
-                                out_keys[2 * pos] = t.x; out_keys[2 * pos + 1] = t.y; out_counts[pos] = (int64_t)c;
+                                const uint64_t t0 = tk0[slot], t1 = tk1[slot];
+                                out_keys[2 * pos] = t0; out_keys[2 * pos + 1] = t1; out_counts[pos] = (int64_t)c;
                             }
                         }
                     }
                     tcnt[slot] = 0;
-                    if constexpr (LF) { if (c) { tk0[slot] = EMPTY; tk1[slot] = EMPTY; } }
+                    if (c) { tk0[slot] = EMPTY; tk1[slot] = EMPTY; }
                 }
                 __syncthreads();
                 const uint32_t raw = ob_n, lim = ob_lim;
                 if (raw >= (uint32_t)WOBUF / 2 || lim != 0xffffffffu) flush();
                 if (S == 1) break;
             } else {
-                for (int i = threadIdx.x; i < WCAP; i += WLT) { tcnt[i] = 0; if constexpr (LF) { tk0[i] = EMPTY; tk1[i] = EMPTY; } }
+                for (int i = threadIdx.x; i < WCAP; i += WLT) { tcnt[i] = 0; tk0[i] = EMPTY; tk1[i] = EMPTY; }
                 __syncthreads();
                 if (threadIdx.x == 0) {
                     my_overflows++;
@@ -1917,38 +1567,16 @@ __global__ void k_reduce_partials(const uint64_t *__restrict__ pk, const uint32_
 constexpr int SK_M = 13;
 constexpr int SK_MIN_W = 9;           // record path for k = 21..31 (W = k - 12 m-mers per window)
 constexpr int SKT = 1024;             // threads per workgroup of the reads -> records kernels
-#ifndef RFX_SK_ROLL
-#define RFX_SK_ROLL 0               // 1: the m-mers rolled a base at a time (rounds 1-2)
-#endif
-#ifndef SK_HIST_RUNLOOP
-#define SK_HIST_RUNLOOP false
-#endif
-#ifndef SK_SCATTER_RUNLOOP
-#define SK_SCATTER_RUNLOOP true
-#endif
-#ifndef SK_DESC_RUNLOOP
-#define SK_DESC_RUNLOOP true
-#endif
 
 // order of the m-mers: a bijection of the canonical 26-bit m-mer onto 32 bits (odd multiplier,
 // xor-shift), so two different m-mers never tie and a plain 32-bit minimum picks the minimiser;
 // the value itself (not the m-mer) names the bucket
-// (RFX_MMER_KEY24, round 3: ONE full-rate instruction, v_mad_u32_u24 -- the low 24 bits of the m-mer times a 24-bit odd
+// (round 3: ONE full-rate instruction, v_mad_u32_u24 -- the low 24 bits of the m-mer times a 24-bit odd
 // constant, plus the m-mer (which brings in its first base, bits 24-25) -- instead of a quarter-rate 32-bit multiply, a
 // shift and an xor: 34 m-mers per segment make this 15 % of level 1's issue cycles.  Not a bijection any more, and it need
 // not be one: the value, not the m-mer, names the run and its bucket, so two m-mers that tie simply share a run -- the
 // bucket is still a function of the canonical k-mer.)
-#ifndef RFX_MMER_KEY24
-#define RFX_MMER_KEY24 1
-#endif
-__device__ __forceinline__ uint32_t mmer_key(uint32_t canon) {
-#if RFX_MMER_KEY24
-    return __umul24(canon, 0x9E3779u) + canon;
-#else
-    uint32_t h = canon * 0x9E3779B1u;
-    return h ^ (h >> 15);
-#endif
-}
+__device__ __forceinline__ uint32_t mmer_key(uint32_t canon) { return __umul24(canon, 0x9E3779u) + canon; }
 
 // digit of a record at a level that follows `used` radix bits
 __device__ __forceinline__ unsigned rec_digit(uint32_t hdr, int used, int bits) {
@@ -1978,23 +1606,10 @@ __device__ __forceinline__ void seg_runs(const ReadSrc &s, int nk_r, int sgm, co
     constexpr int M2 = 2 * SK_M;
     const uint32_t mmask = (1u << M2) - 1;
     uint32_t val[NM];
-#if RFX_SK_ROLL
-    uint32_t fm = (uint32_t)(hi >> (64 - M2));
-    uint32_t rm = (uint32_t)revcomp((uint64_t)fm, SK_M);
-#pragma unroll
-    for (int j = 0; j < NM; j++) {
-        val[j] = mmer_key(fm < rm ? fm : rm);
-        // base M + j of the 64-base stream (hi, lo): compile-time position
-        const int pos = SK_M + j;
-        const uint32_t b = pos < 32 ? (uint32_t)(hi >> (62 - 2 * pos)) & 3u : (uint32_t)(lo >> (62 - 2 * (pos - 32))) & 3u;
-        fm = ((fm << 2) | b) & mmask;
-        rm = (rm >> 2) | ((b ^ 3u) << (M2 - 2));
-    }
-#else
     // Every m-mer is CUT out of the 64-base stream, and its reverse complement out of the stream's reverse complement
     // (made once: the complement of m-mer j is the m-mer at base 51 - j of it), at compile-time positions: a bit-field
     // extract when the 26 bits lie in one 32-bit word, a funnel shift and a shift otherwise -- 3.5 instructions for the
-    // pair instead of the 6 of rolling both through a base at a time.
+    // pair instead of the 6 of rolling both through a base at a time (rounds 1-2).
     static_assert(SK_M == 13 && NM <= 50, "positions below");
     const uint64_t rhi = revcomp(lo, 32), rlo = revcomp(hi, 32);
     const uint32_t FW[4] = {(uint32_t)(hi >> 32), (uint32_t)hi, (uint32_t)(lo >> 32), (uint32_t)lo};
@@ -2009,7 +1624,6 @@ __device__ __forceinline__ void seg_runs(const ReadSrc &s, int nk_r, int sgm, co
         const uint32_t fm = cut(FW, j), rm = cut(RW, 64 - SK_M - j);
         val[j] = mmer_key(fm < rm ? fm : rm);
     }
-#endif
     // per-window minimiser = sliding minimum over W m-mers (van Herk: suffix minima and prefix minima
     // inside blocks of W m-mers; a window spans at most two blocks)
     uint32_t wm[PK];
@@ -2134,7 +1748,7 @@ template <int W, bool DESC>
 __global__ __launch_bounds__(SKT) void k_sk_hist(ReadSrc s, Level lv, uint64_t *__restrict__ blockhist,
                                                  uint32_t *__restrict__ desc) {
     __shared__ uint32_t h[1 << MAX_BITS];
-    __shared__ uint32_t wmcol[DESC && SK_DESC_RUNLOOP ? PK * SKT : 1];      // per-window minimisers, one column per thread
+    __shared__ uint32_t wmcol[DESC ? PK * SKT : 1];      // per-window minimisers, one column per thread
     const int nb = lv.n_owners > 0 ? lv.n_owners : (1 << lv.bits);
     for (int i = threadIdx.x; i < nb; i += SKT) h[i] = 0;
     __syncthreads();
@@ -2153,7 +1767,7 @@ __global__ __launch_bounds__(SKT) void k_sk_hist(ReadSrc s, Level lv, uint64_t *
             // run loop: the r-th run of every lane is handled in the same iteration, so the header
             // stores of a wave go to consecutive words
             uint32_t own[2] = {0, 0};                    // owner mode: the runs' owners, 8 bits each
-            seg_runs<W, SK_DESC_RUNLOOP>(s, read_nk(s, q.r), q.sgm, w, [&](int i0, int, uint32_t canon) {
+            seg_runs<W, true>(s, read_nk(s, q.r), q.sgm, w, [&](int i0, int, uint32_t canon) {
                 const uint64_t h64 = mmer_hash64(canon);
                 const uint32_t hdr = (uint32_t)((h64 << OWNER_BITS) >> 32);
                 const unsigned d = lv.n_owners > 0 ? (unsigned)__umul64hi(h64, (uint64_t)lv.n_owners) : rec_digit(hdr, 0, lv.bits);
@@ -2163,14 +1777,14 @@ __global__ __launch_bounds__(SKT) void k_sk_hist(ReadSrc s, Level lv, uint64_t *
                     if (nr < 4) own[0] |= d << (8 * nr); else own[1] |= d << (8 * (nr - 4));
                 }
                 mask |= 1u << i0; nr++;
-            }, &hi, &lo, SK_DESC_RUNLOOP ? wmcol : nullptr);
+            }, &hi, &lo, wmcol);
             desc[g] = mask | (nr << 16);
             if (lv.n_owners > 0) {
                 desc[(int64_t)(1 + SKD) * s.n_threads + g] = own[0];
                 desc[(int64_t)(2 + SKD) * s.n_threads + g] = own[1];
             }
         } else {
-            seg_runs<W, SK_HIST_RUNLOOP>(s, read_nk(s, q.r), q.sgm, w, [&](int, int, uint32_t canon) { atomicAdd(&h[sk_digit(canon, lv)], 1u); }, &hi, &lo);
+            seg_runs<W, false>(s, read_nk(s, q.r), q.sgm, w, [&](int, int, uint32_t canon) { atomicAdd(&h[sk_digit(canon, lv)], 1u); }, &hi, &lo);
         }
         q.r += dq; q.sgm += dr;
         if (q.sgm >= s.segs) { q.sgm -= s.segs; q.r++; }
@@ -2253,7 +1867,7 @@ __global__ __launch_bounds__(SKT, WIDE ? 4 : 8) void k_sk_scatter(ReadSrc s, Lev
             };
             // `hi`/`lo` are written before the first emit() runs (seg_runs stores them first)
             auto recompute = [&]() __attribute__((always_inline)) {
-                seg_runs<W, SK_SCATTER_RUNLOOP>(s, read_nk(s, q.r), q.sgm, w, [&](int i0, int n, uint32_t canon) {
+                seg_runs<W, true>(s, read_nk(s, q.r), q.sgm, w, [&](int i0, int n, uint32_t canon) {
                     const uint64_t h = mmer_hash64(canon);
                     const unsigned d = lv.n_owners > 0 ? (unsigned)__umul64hi(h, (uint64_t)lv.n_owners)
                                                        : rec_digit((uint32_t)((h << OWNER_BITS) >> 32), 0, lv.bits);
@@ -2319,21 +1933,6 @@ __global__ __launch_bounds__(SKT, WIDE ? 4 : 8) void k_sk_scatter(ReadSrc s, Lev
 // What a workgroup leaves unused of its last two extents are HOLES; k_fix_holes moves the records at the end of every
 // bucket into the holes before it, so the next level reads a gap-free [seg_begin, seg_end) per bucket.  A region that
 // runs out (a sample that missed the skew) raises `overflow` and the caller falls back to the two-pass form.
-#ifndef RFX_DRAIN_UNROLL
-#define RFX_DRAIN_UNROLL 1
-#endif
-#ifndef RFX_OS_A32
-#define RFX_OS_A32 4                 // records per aligned burst of the 16-slot rings (4 = 64 bytes, 8 = 128)
-#endif
-#ifndef RFX_OS_T32
-#define RFX_OS_T32 512               // threads per workgroup of the sweep with 32 windows per thread
-#endif
-#ifndef RFX_OS_LPB
-#define RFX_OS_LPB 4                 // lanes that drain a bin there (8: a lane per ring slot)
-#endif
-#ifndef RFX_OS_LPB_WIDE
-#define RFX_OS_LPB_WIDE 4            // ... of the 32-byte records of k = 33..63 (8: part1 9.95 instead of 9.80 ms)
-#endif
 constexpr int OSE_MIN = 64, OSE_MAX = 256;   // records per extent: a round must not put more than one extent of one
                                          // workgroup into one bucket (5 records on average at 512 buckets); the sampled
                                          // histogram picks 64, 128 or 256 by the busiest bucket, or no sweep at all
@@ -2366,7 +1965,7 @@ __global__ __launch_bounds__(SKT) void k_sk_sample_hist(ReadSrc s, Level lv, int
             q.sgm = (int)(g - q.r * s.segs);
             uint64_t w[3], hi, lo;
             seg_load<SEG>(s, q, w);
-            seg_runs<W, SK_HIST_RUNLOOP, SEG>(s, read_nk(s, q.r), q.sgm, w, [&](int, int, uint32_t canon) { atomicAdd(&h[sk_digit(canon, lv)], 1u); }, &hi, &lo);
+            seg_runs<W, false, SEG>(s, read_nk(s, q.r), q.sgm, w, [&](int, int, uint32_t canon) { atomicAdd(&h[sk_digit(canon, lv)], 1u); }, &hi, &lo);
         }
     }
     __syncthreads();
@@ -2422,15 +2021,13 @@ __global__ __launch_bounds__(1024) void k_plan_regions(const unsigned long long 
 // saved went into the CU standing still at the round's two barriers.  Hence T = 512 threads: two workgroups per CU again,
 // a tile brings a bucket what it did before, and the rings stay at 8 slots.)
 template <int SEG, bool WIDE> struct OsGeo {
-    static constexpr int T = SEG > 16 && !WIDE ? RFX_OS_T32 : SKT;           // threads per workgroup = segments per tile
-    static constexpr int B = SEG > 16 && !WIDE && T == SKT ? 16 : SKB, A = SEG > 16 && !WIDE && T == SKT ? RFX_OS_A32 : SKA;
+    static constexpr int T = SEG > 16 && !WIDE ? 512 : SKT;                  // threads per workgroup = segments per tile
 };
 template <int W, bool WIDE = false, int SEG = 16>
-__global__ __launch_bounds__((OsGeo<SEG, WIDE>::T), WIDE ? 4 : SEG > 16 ? (OsGeo<SEG, WIDE>::T == SKT ? 4 : OsGeo<SEG, WIDE>::T / 128) : 8) void k_sk_onesweep(ReadSrc s, Level lv, OneSweep os,
+__global__ __launch_bounds__((OsGeo<SEG, WIDE>::T), WIDE || SEG > 16 ? 4 : 8) void k_sk_onesweep(ReadSrc s, Level lv, OneSweep os,
                                                                std::conditional_t<WIDE, WRec, Rec> *__restrict__ out) {
     using RT = std::conditional_t<WIDE, WRec, Rec>;
-    constexpr int SKB = OsGeo<SEG, WIDE>::B, SKA = OsGeo<SEG, WIDE>::A;      // (shadow the file-wide ring geometry
-    constexpr int SKT = OsGeo<SEG, WIDE>::T;                                  //  and workgroup size)
+    constexpr int SKT = OsGeo<SEG, WIDE>::T;                                  // (shadows the file-wide workgroup size)
     extern __shared__ __attribute__((aligned(32))) unsigned char sk_smem[];
     const int nb = 1 << lv.bits;
 #define buf ((RT *)sk_smem)
@@ -2469,10 +2066,11 @@ __global__ __launch_bounds__((OsGeo<SEG, WIDE>::T), WIDE ? 4 : SEG > 16 ? (OsGeo
     __syncthreads();
     // LPB lanes drain a bin, each every LPB-th record of what waits: eight lanes (one record each) in rounds 1-2; four
     // with 32 windows per thread -- a bin's bookkeeping is done by half as many lanes, and four lanes are one aligned
-    // 64-byte line, the unit the rings hand out anyway
-    constexpr int LPB = SEG > 16 && !WIDE ? RFX_OS_LPB : WIDE ? RFX_OS_LPB_WIDE : SKB;
+    // 64-byte line, the unit the rings hand out anyway -- and four for the 32-byte records of k = 33..63 (eight: part1
+    // 9.95 instead of 9.80 ms)
+    constexpr int LPB = SEG > 16 || WIDE ? 4 : SKB;
     auto drain = [&](bool final) __attribute__((always_inline)) {
-#pragma unroll RFX_DRAIN_UNROLL
+#pragma nounroll
         for (int d = threadIdx.x / LPB; d < nb; d += SKT / LPB) {
             const int j = threadIdx.x % LPB;
             const uint32_t h = head[d], t = tail[d], cs = cstart[d], cb = cbase[d], nx = nbase[d];
@@ -2483,15 +2081,11 @@ __global__ __launch_bounds__((OsGeo<SEG, WIDE>::T), WIDE ? 4 : SEG > 16 ? (OsGeo
                 if (e < h) e = h;
                 nh = e;
             }
-#ifdef RFX_OS_ABL_NOSTORE
-            { const uint32_t g = h + j; if (g < e && g == 0xFFFFFFF0u) out[phys(g, cs, cb, nx)] = buf[(size_t)d * SKB + (g & (SKB - 1))]; }
-#else
 #pragma unroll
             for (int q = 0; q < SKB / LPB; q++) {
                 const uint32_t g = h + j + q * LPB;
                 if (g < e) out[phys(g, cs, cb, nx)] = buf[(size_t)d * SKB + (g & (SKB - 1))];
             }
-#endif
             if (j == 0) {
                 head[d] = nh;
                 // extents that lie wholly behind the stored position are done with: move up (the 8 lanes of this
@@ -2524,7 +2118,7 @@ __global__ __launch_bounds__((OsGeo<SEG, WIDE>::T), WIDE ? 4 : SEG > 16 ? (OsGeo
             q.sgm = (int)(g - q.r * s.segs);
             uint64_t w[3], hi = 0, lo = 0;
             seg_load<SEG>(s, q, w);
-            seg_runs<W, SK_SCATTER_RUNLOOP, SEG>(s, read_nk(s, q.r), q.sgm, w, [&](int i0, int n, uint32_t canon) {
+            seg_runs<W, true, SEG>(s, read_nk(s, q.r), q.sgm, w, [&](int i0, int n, uint32_t canon) {
                 const uint64_t hh = mmer_hash64(canon);
                 const uint32_t hdr = (uint32_t)((hh << OWNER_BITS) >> 32);
                 // (by owner: the owner's bucket is 2^sub_bits bins here, so that a round still brings a bin a handful of
@@ -2781,7 +2375,7 @@ __global__ __launch_bounds__(WCT) void k_rec_scatter_wc(const typename LevelElem
     __syncthreads();
     // B adjacent lanes drain one bin: everything up to the last aligned boundary (all of it at the end)
     auto drain = [&](bool final) __attribute__((always_inline)) {
-#pragma unroll RFX_DRAIN_UNROLL
+#pragma nounroll
         for (int d = threadIdx.x / B; d < nb; d += WCT / B) {
             const int j = threadIdx.x % B;
             const unsigned long long h = head[d], t = tail[d];
@@ -2894,7 +2488,7 @@ __global__ __launch_bounds__(WCT) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     unsigned long long *lim = head + nb;
     uint32_t *h = (uint32_t *)(lim + nb);
     auto drain = [&](bool final) __attribute__((always_inline)) {
-#pragma unroll RFX_DRAIN_UNROLL
+#pragma nounroll
         for (int d = threadIdx.x / B; d < nb; d += WCT / B) {
             const int j = threadIdx.x % B;
             const unsigned long long hd = head[d], lm = lim[d];
@@ -3057,7 +2651,7 @@ __global__ __launch_bounds__(WCT) void k_rec_l2sweep(const typename LevelElem<MO
     }
     __syncthreads();
     auto drain = [&](bool final) __attribute__((always_inline)) {
-#pragma unroll RFX_DRAIN_UNROLL
+#pragma nounroll
         for (int d = threadIdx.x / B; d < nb; d += WCT / B) {
             const int j = threadIdx.x % B;
             const unsigned long long h = head[d], lm = lim[d];
@@ -3478,7 +3072,6 @@ static int finish_leaves(rfx_ctx *ctx, const typename LeafElem<ELEM>::T *elems, 
         unsigned long long a = 0, b = 0, c = 0;
         if (sscanf(e, "%llu,%llu,%llu", &a, &b, &c) == 3 && a && b && c) { heavy = a; slice = b; pcap_min = c; }
     }
-    const int dbg = getenv("RFX_LEAF_DBG") ? atoi(getenv("RFX_LEAF_DBG")) : 0;
     // records beyond which a leaf starts in 2, 4, .. parts (a record holds ~0.5 distinct k-mers at high coverage,
     // a table takes ~3300 keys before probe sequences run long); measured neutral for pairs and not used there
     const uint32_t presplit = getenv("RFX_PRESPLIT") ? (uint32_t)atoi(getenv("RFX_PRESPLIT")) : ELEM == 1 ? 8000u : 0u;
@@ -3496,15 +3089,13 @@ static int finish_leaves(rfx_ctx *ctx, const typename LeafElem<ELEM>::T *elems, 
         // many more workgroups than fit (2 per CU are resident): a workgroup's contiguous chunk of leaves is
         // short, and the chunks even out what the leaves' sizes do not (leaf 14.6 -> 13.3 ms against 2 per CU)
         // (pair output: every workgroup leaves part of its last block(s) as holes, so fewer of them)
-        const int leaf_per_cu = getenv("RFX_LEAF_PER_CU") ? std::max(1, atoi(getenv("RFX_LEAF_PER_CU"))) : pair_out ? 4 : 32;
+        const int leaf_per_cu = pair_out ? 4 : 32;
         int64_t grid = std::min<int64_t>(nleaf, (int64_t)ctx->num_cu * leaf_per_cu);      // persistent, <= 78 KB LDS each
-        static const bool kc_off = getenv("RFX_LEAF_KC") && atoi(getenv("RFX_LEAF_KC")) == 0;
         auto *kern = k_leaf_count<ELEM, 0>;
-        if (RECS && k == 31 && !kc_off) kern = k_leaf_count<ELEM, RECS ? 31 : 0>;
-        static const int extra_lds = getenv("RFX_LEAF_EXTRA_LDS") ? atoi(getenv("RFX_LEAF_EXTRA_LDS")) : 0;   // occupancy experiment
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(LT), (size_t)extra_lds, ctx->stream, elems, d_leaf_off, d_leaf_end, nleaf,
+        if (RECS && k == 31) kern = k_leaf_count<ELEM, RECS ? 31 : 0>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(LT), 0, ctx->stream, elems, d_leaf_off, d_leaf_end, nleaf,
                            (const uint64_t *)nullptr, (const uint64_t *)nullptr, heavy, (uint64_t)elem_count, k, min_cov,
-                           max_cov, apply, d_out_keys, d_out_counts, (unsigned long long)cap, co_buf.as<CountOut>(), dbg,
+                           max_cov, apply, d_out_keys, d_out_counts, (unsigned long long)cap, co_buf.as<CountOut>(),
                            (int)pair_out, presplit);
         RFX_HIP(hipGetLastError());
     }
@@ -3530,7 +3121,7 @@ static int finish_leaves(rfx_ctx *ctx, const typename LeafElem<ELEM>::T *elems, 
                 hipLaunchKernelGGL(k_leaf_count<ELEM>, dim3((unsigned)grid), dim3(LT), 0, ctx->stream, elems, d_leaf_off, d_leaf_end,
                                    (int64_t)n_slices, (const uint64_t *)sb.as<uint64_t>(), (const uint64_t *)se.as<uint64_t>(),
                                    (uint64_t)0, (uint64_t)elem_count, k, min_cov, max_cov, 0, pk.as<uint64_t>(),
-                                   pc.as<int32_t>(), (unsigned long long)pcap, co2.as<CountOut>(), dbg, 0, 0u);
+                                   pc.as<int32_t>(), (unsigned long long)pcap, co2.as<CountOut>(), 0, 0u);
                 RFX_HIP(hipGetLastError());
             }
             RFX_HIP(hipMemcpyAsync(&c2, co2.p, sizeof c2, hipMemcpyDeviceToHost, ctx->stream));
@@ -3564,11 +3155,6 @@ static int finish_leaves(rfx_ctx *ctx, const typename LeafElem<ELEM>::T *elems, 
     // table statistics of the last count call, read back by tests through rfx_last_count_timing (launches = the number)
     ctx->timing["stat_leaves"].launches += nleaf; ctx->timing["stat_passes"].launches += (int64_t)co.n_passes;
     ctx->timing["stat_overflows"].launches += (int64_t)co.n_overflow;
-    if (dbg & 128)
-        fprintf(stderr, "record table: %llu records counted in it, %llu expanded on the spot (%llu windows), %llu slots swept (%llu windows), %.2f per leaf\n",
-                co.r_placed, co.r_direct, co.w_direct, co.r_slots, co.w_table, (double)co.r_slots / (double)std::max<int64_t>(nleaf, 1));
-    if (dbg & 32)
-        fprintf(stderr, "leaf waves: %.1f %% of their clocks at the leaf barriers\n", 100.0 * (double)co.t_wait / (double)std::max<unsigned long long>(co.t_all, 1));
     if (co.n_failed) { ctx->last_error = "leaf split depth exhausted"; ScopedTimer::collect(ctx); return RFX_E_LIMIT; }
     if ((int64_t)co.n_out > cap) { ScopedTimer::collect(ctx); return RFX_E_CAP; }
     if ((int64_t)co.n_out > (int64_t)0xFFFFFFFFLL) { ScopedTimer::collect(ctx); return RFX_E_LIMIT; }
@@ -3587,9 +3173,8 @@ static int finish_leaves(rfx_ctx *ctx, const typename LeafElem<ELEM>::T *elems, 
     return RFX_OK;
 }
 
-// super-k-mer records are used for k = 28..31 (W = k - 12 in 16..19); RFX_SUPERKMER=0 disables them
+// super-k-mer records are used for k = 28..31 (W = k - 12 in 16..19)
 static bool superkmer_enabled(int k) {
-    if (const char *e = getenv("RFX_SUPERKMER")) if (atoi(e) == 0) return false;
     return k >= SK_M + SK_MIN_W - 1 && k <= 31;
 }
 
@@ -3640,8 +3225,7 @@ static int records_from_reads(rfx_ctx *ctx, const ReadSrc &rsrc, const Level &lv
     const size_t sk_lds = (size_t)nb * (SKB * sizeof(Rec) + 16);
     // two workgroups fit a CU when the rings are small; four times as many are launched then (the rest queue
     // behind the first and even out the tail: hist1 5.0 -> 4.6 ms)
-    int per_cu = sk_lds <= 80 * 1024 ? 8 : 1;
-    if (const char *e = getenv("RFX_SK_PER_CU")) per_cu = std::max(1, atoi(e));
+    const int per_cu = sk_lds <= 80 * 1024 ? 8 : 1;
     const unsigned G = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(rsrc.n_threads, SKT), (int64_t)ctx->num_cu * per_cu));
     DevBuf bh, scanned;
     RFX_HIP(bh.alloc((size_t)nb * G * 8, ctx->stream));
@@ -3693,9 +3277,8 @@ static int records_onesweep(rfx_ctx *ctx, const ReadSrc &rsrc_in, const Level &l
     *done = false;
     const int nb = 1 << lv.bits;
     const int W = rsrc_in.k - SK_M + 1;
-    // 32 windows per thread (seg_runs; RFX_SK_SEG=16: the 16 of rounds 1-2).  The k = 33..63 records keep 16.
-    // (its 16-slot rings fit the LDS up to 512 buckets)
-    const bool seg32 = !WIDE && nb <= 512 && !(getenv("RFX_SK_SEG") && atoi(getenv("RFX_SK_SEG")) == 16);
+    // 32 windows per thread (seg_runs; 16 in rounds 1-2) up to 512 buckets.  The k = 33..63 records keep 16.
+    const bool seg32 = !WIDE && nb <= 512;
     ReadSrc rsrc = rsrc_in;
     if (seg32) {
         rsrc.segs = rsrc.nk > 0 ? (rsrc.nk + 31) / 32 : 1;
@@ -3704,12 +3287,12 @@ static int records_onesweep(rfx_ctx *ctx, const ReadSrc &rsrc_in, const Level &l
     const int OST = seg32 ? OsGeo<32, false>::T : SKT;            // threads per workgroup of the sweep = segments per tile
     const int64_t ntile = ceil_div(rsrc.n_threads, OST);
     const int64_t ntile_s = ceil_div(rsrc.n_threads, SKT);        // (the sampled histogram keeps tiles of SKT segments)
-    // two workgroups per CU (one when a workgroup fills the CU); fewer on small inputs (every workgroup holds three extents
+    // two workgroups per CU (one for the 32-byte records); fewer on small inputs (every workgroup holds three extents
     // per bucket: at least 32 tiles each)
-    const int per_cu = WIDE || (seg32 && OST == SKT) ? 1 : 2;
+    const int per_cu = WIDE ? 1 : 2;
     const int G = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(OS_MAXG, (int64_t)ctx->num_cu * per_cu),
                                                                 std::max<int64_t>(std::min<int64_t>(ntile, 64), ntile / 32)));
-    int sample = getenv("RFX_SK_SAMPLE") ? std::max(1, atoi(getenv("RFX_SK_SAMPLE"))) : 32;
+    int sample = 32;
     if (ntile_s < 64 * (int64_t)sample) sample = (int)std::max<int64_t>(1, ntile_s / 64);      // small inputs: at least 64 tiles
     const int64_t n_sampled = ceil_div(ntile_s, sample);
     const int cap_pct = getenv("RFX_SK_ONESWEEP_CAP") ? std::max(1, atoi(getenv("RFX_SK_ONESWEEP_CAP"))) : 100;
@@ -3757,7 +3340,7 @@ static int records_onesweep(rfx_ctx *ctx, const ReadSrc &rsrc_in, const Level &l
     }
     const OneSweep os{reg_start.as<uint64_t>(), reg_cap.as<uint32_t>(), cursor.as<unsigned long long>(), holes.as<uint64_t>(), d_overflow,
                       (uint64_t)h_tot[0], hist.as<unsigned long long>() + nb + 1, ose, (uint32_t)ose_shift};
-    const size_t lds = (size_t)nb * ((seg32 ? OsGeo<32, false>::B : SKB) * sizeof(Rec) + 24);
+    const size_t lds = (size_t)nb * (SKB * sizeof(Rec) + 24);
     {
         ScopedTimer t(ctx, pn);
         if constexpr (WIDE) {                  // the central window is 30 or 31 bases: W = 18 or 19
@@ -3916,8 +3499,7 @@ static int partition_record_levels(rfx_ctx *ctx, const typename LevelElem<MODE>:
             }
         }
         const int64_t total_tiles = ceil_div(std::max<int64_t>(n_recs, 1), PTILE);
-        int tpb = (int)std::min<int64_t>(32, std::max<int64_t>(1, total_tiles / ((int64_t)ctx->num_cu * 8)));
-        if (const char *e = getenv("RFX_TPB")) tpb = std::max(1, atoi(e));
+        const int tpb = (int)std::min<int64_t>(32, std::max<int64_t>(1, total_tiles / ((int64_t)ctx->num_cu * 8)));
         const int64_t v_bound = ceil_div(std::max<int64_t>(n_recs, 1), (int64_t)tpb * PTILE) + nseg;
         DevBuf nvb, vb_start, table, scanned;
         RFX_HIP(nvb.alloc((size_t)nseg * 8, ctx->stream));
@@ -3949,7 +3531,7 @@ static int partition_record_levels(rfx_ctx *ctx, const typename LevelElem<MODE>:
         if (!dst) { ctx->last_error = "workspace allocation failed"; return RFX_E_HIP; }
         {
             ScopedTimer t(ctx, pn);
-            const bool wc = !(getenv("RFX_WC") && atoi(getenv("RFX_WC")) == 0) && lv.bits >= 4;
+            const bool wc = lv.bits >= 4;
             if (wc && MODE == 3) {                   // 32-byte records: 8 slots per bin fill the LDS at 512 bins
                 if (lv.bits > 9) {                   // 1024 bins: 4 slots each (64-byte lines)
                     const size_t lds = (size_t)nb * (4 * sizeof(Rec) + 16);
@@ -3962,7 +3544,7 @@ static int partition_record_levels(rfx_ctx *ctx, const typename LevelElem<MODE>:
                     hipLaunchKernelGGL((k_rec_scatter_wc<8, MODE>), dim3((unsigned)v_bound), dim3(WCT), lds, ctx->stream, cur, vm, lv,
                                        used, (const uint64_t *)scanned.as<uint64_t>(), dst);
                 }
-            } else if (wc && lv.bits <= 9 && !(getenv("RFX_WC_B") && atoi(getenv("RFX_WC_B")) == 8)) {
+            } else if (wc && lv.bits <= 9) {
                 const size_t lds = (size_t)nb * (16 * sizeof(Rec) + 16);
                 RFX_HIP(hipFuncSetAttribute((const void *)k_rec_scatter_wc<16, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                 hipLaunchKernelGGL((k_rec_scatter_wc<16, MODE>), dim3((unsigned)v_bound), dim3(WCT), lds, ctx->stream, cur, vm, lv,
@@ -4173,7 +3755,7 @@ static int count_reads_superkmer(rfx_ctx *ctx, const ReadStore *reads, int min_c
     if (out_distinct) *out_distinct = 0;
     if (n <= 0) return RFX_OK;
     std::vector<int> bits;
-    plan_levels(n, true, bits, 16384.0);           // measured best for the record leaf with double hashing + pre-split (tools/bits_sweep.sh)
+    plan_levels(n, true, bits, 16384.0);           // measured best for the record leaf with double hashing + pre-split
     // (20 bits and more put 1024 bins on level 1 and one workgroup per CU there, the rings fill the LDS.  Measured on one
     // GPU: 20 Gbp of the 4.64 Mbp genome 138.8 ms with 10 + 10 bits, 131.7 with 9 + 10 and leaves twice as large, 139
     // with three levels; 18.75 Gbp of a 400 Mbp genome -- 2.5e9 distinct k-mers, a human-scale share -- 238 ms with
@@ -4282,8 +3864,7 @@ int count_filter(rfx_ctx *ctx, const ReadStore *reads, const uint64_t *d_kmers, 
             // virtual workgroups of tpb tiles inside every parent; table rows -> scan -> private cursors
             const int nb = 1 << lv.bits;
             const int64_t total_tiles = ceil_div(n, PTILE);
-            int tpb = (int)std::min<int64_t>(32, std::max<int64_t>(1, total_tiles / ((int64_t)ctx->num_cu * 8)));
-            if (const char *e = getenv("RFX_TPB")) tpb = std::max(1, atoi(e));
+            const int tpb = (int)std::min<int64_t>(32, std::max<int64_t>(1, total_tiles / ((int64_t)ctx->num_cu * 8)));
             const int64_t v_bound = ceil_div(n, (int64_t)tpb * PTILE) + nseg;
             DevBuf nvb, vb_start, table, scanned;
             RFX_HIP(nvb.alloc((size_t)nseg * 8, ctx->stream));
@@ -4612,14 +4193,10 @@ static int finish_wide2(rfx_ctx *ctx, const std::conditional_t<RECS, WRec, Rec> 
     RFX_HIP(hipMemsetAsync(co_buf.p, 0, sizeof(CountOut), ctx->stream));
     {
         ScopedTimer t(ctx, "leaf");
-        const int wleaf_per_cu = getenv("RFX_WLEAF_PER_CU") ? std::max(1, atoi(getenv("RFX_WLEAF_PER_CU"))) : 1;
-        const int64_t grid = std::min<int64_t>(nseg, (int64_t)ctx->num_cu * wleaf_per_cu);
+        const int64_t grid = std::min<int64_t>(nseg, (int64_t)ctx->num_cu);          // one workgroup per CU
         hipLaunchKernelGGL(k_leaf_count_wide<RECS>, dim3((unsigned)grid), dim3(WLT), 0, ctx->stream, cur, d_leaf_off, d_leaf_end, nseg, k,
                            min_cov, max_cov, d_out_keys, d_out_counts, (unsigned long long)cap, co_buf.as<CountOut>(),
-                           (uint32_t)(getenv("RFX_WIDE_PRESPLIT") ? atoi(getenv("RFX_WIDE_PRESPLIT")) : 2600) |
-                               (getenv("RFX_WIDE_DBG") ? (uint32_t)atoi(getenv("RFX_WIDE_DBG")) << 30 : 0u) |
-                               (getenv("RFX_WIDE_LINEAR") ? 0x20000000u : 0u) | (getenv("RFX_WIDE_NOAGG") ? 0x10000000u : 0u) |
-                               (getenv("RFX_WIDE_STATS") ? 0x08000000u : 0u));
+                           (uint32_t)(getenv("RFX_WIDE_PRESPLIT") ? atoi(getenv("RFX_WIDE_PRESPLIT")) : 2600));
         RFX_HIP(hipGetLastError());
     }
     CountOut co{};
@@ -4627,9 +4204,6 @@ static int finish_wide2(rfx_ctx *ctx, const std::conditional_t<RECS, WRec, Rec> 
     RFX_TRY(sync_checked(ctx));
     if (getenv("RFX_TRACE"))
         fprintf(stderr, "wide leaves: %lld buckets, %llu table passes, %llu overflowed\n", (long long)nseg, co.n_passes, co.n_overflow);
-    if (getenv("RFX_WIDE_STATS"))
-        fprintf(stderr, "wide record table: %llu records counted in it, %llu expanded on the spot, %llu slots swept (%.1f per leaf)\n",
-                co.r_placed, co.r_direct, co.r_slots, (double)co.r_slots / (double)std::max<int64_t>(nseg, 1));
     ctx->timing["stat_leaves"].launches += nseg; ctx->timing["stat_passes"].launches += (int64_t)co.n_passes;
     ctx->timing["stat_overflows"].launches += (int64_t)co.n_overflow;
     if (out_n) *out_n = (int64_t)co.n_out;
@@ -4744,7 +4318,7 @@ static ReadSrc wide_read_src(const uint64_t *d_words, int64_t n_reads, int wpr, 
 }
 
 static void plan_wide_record_levels(int64_t n, std::vector<int> &bits) {
-    plan_levels(n, true, bits, 6144.0);          // measured best of 3072 .. 49152 (tools/w63_sweep.sh)
+    plan_levels(n, true, bits, 6144.0);          // measured best of 3072 .. 49152
     int B = 0;
     for (int b : bits) B += b;
     if (getenv("RFX_LEVEL_BITS")) return;

@@ -260,15 +260,13 @@ int exclusive_scan_u64(rfx_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, int6
     return scan_impl<uint64_t>(ctx, d_in, d_out, n);
 }
 int exclusive_scan_u32_to_u64(rfx_ctx *ctx, const uint32_t *d_in, uint64_t *d_out, int64_t n) {
-    static const bool off = getenv("RFX_SCAN_LOOKBACK") && atoi(getenv("RFX_SCAN_LOOKBACK")) == 0;
-    if (n > SCAN_TILE && !off) return scan_lookback(ctx, d_in, nullptr, d_out, nullptr, n);
+    if (n > SCAN_TILE) return scan_lookback(ctx, d_in, nullptr, d_out, nullptr, n);
     return scan_impl<uint32_t>(ctx, d_in, d_out, n);
 }
 int exclusive_scan2_u32_to_u64(rfx_ctx *ctx, const uint32_t *d_in_a, const uint32_t *d_in_b, uint64_t *d_out_a,
                                uint64_t *d_out_b, int64_t n) {
-    static const bool off = getenv("RFX_SCAN_LOOKBACK") && atoi(getenv("RFX_SCAN_LOOKBACK")) == 0;
-    if (n > 0 && !off) return scan_lookback(ctx, d_in_a, d_in_b, d_out_a, d_out_b, n);
-    RFX_TRY(scan_impl<uint32_t>(ctx, d_in_a, d_out_a, n));
+    if (n > 0) return scan_lookback(ctx, d_in_a, d_in_b, d_out_a, d_out_b, n);
+    RFX_TRY(scan_impl<uint32_t>(ctx, d_in_a, d_out_a, n));      // (n = 0: the totals are zero)
     return scan_impl<uint32_t>(ctx, d_in_b, d_out_b, n);
 }
 

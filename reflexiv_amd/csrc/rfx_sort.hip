@@ -362,9 +362,8 @@ int sort_pairs(rfx_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, int64_t n, int 
     uint64_t *sk = d_keys, *dk = d_tmp_keys;
     uint32_t *sv = d_vals, *dv = d_tmp_vals;
     const bool inline_scan = ntiles <= 64;           // <= 128 K pairs
-    static const bool msd_off = getenv("RFX_SORT_MSD") && atoi(getenv("RFX_SORT_MSD")) == 0;
     const SegMap nomap{nullptr, nullptr, 256};
-    if (n > ((int64_t)1 << 26) && n < ((int64_t)1 << 32) && key_bits > 24 && !msd_off) {
+    if (n > ((int64_t)1 << 26) && n < ((int64_t)1 << 32) && key_bits > 24) {
         // Beyond 2^26 pairs (the 4.5e8 survivors of a human-scale share): THREE stable MSD levels -- 8 bits, 8 bits, then as
         // many as bring a bucket to ~1000 pairs -- and the final buckets on chip: 85 -> ~25 ms where the eight LSD passes
         // ran at 1.3 TB/s.  The second level's 65536 buckets are the parents of the third (SegMap::NP).  Skewed keys (a
@@ -435,7 +434,7 @@ int sort_pairs(rfx_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, int64_t n, int 
         // skewed: (dk, dv) hold a stable regrouping of the input; the LSD passes finish it from there
         std::swap(sk, dk);
         std::swap(sv, dv);
-    } else if (ntiles > 192 && key_bits > 16 && n <= ((int64_t)1 << 26) && !msd_off) {
+    } else if (ntiles > 192 && key_bits > 16 && n <= ((int64_t)1 << 26)) {
         // Large inputs: TWO stable MSD levels (8 bits, then as many as bring a bucket to ~1000 pairs), then every
         // final bucket is finished on chip -- ~90 B of HBM traffic per pair instead of 32 B x (key_bits / 8) LSD passes.
         // A bucket larger than a tile (skewed keys) sends the whole thing down the LSD passes below instead, which
@@ -483,7 +482,7 @@ int sort_pairs(rfx_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, int64_t n, int 
         }
         // skewed: (sk, sv) = (d_keys, d_vals) hold a stable regrouping of the input; the LSD passes finish it
     }
-    if (ntiles <= 192 && key_bits > 8 && !msd_off) {
+    if (ntiles <= 192 && key_bits > 8) {
         // top digit first; the 4-byte readback decides (a bucket larger than a tile -- skewed keys -- takes
         // the LSD passes below instead)
         const int shift = key_bits - 8;

@@ -223,7 +223,7 @@ int kmer_counts_per_read_w(rfx_ctx *ctx, const int64_t *d_read_off, int64_t n_re
 int extract_w(rfx_ctx *ctx, const uint64_t *d_words, int wpr, const uint64_t *d_kmer_off, int64_t nk_uniform,
               int64_t n_reads, int k, int fc, uint64_t *d_soa, int64_t N, int aos) {
     if (n_reads <= 0 || N <= 0) return RFX_OK;
-    if (!d_kmer_off && aos && k / 32 + 1 == 2 && !getenv("RFX_WIDE_NOROLL")) {
+    if (!d_kmer_off && aos && k / 32 + 1 == 2) {
         const int64_t total = n_reads * ceil_div(nk_uniform, WSEG);
         const int64_t blocks = std::min<int64_t>(ceil_div(total, 256), (int64_t)ctx->num_cu * 32);
         hipLaunchKernelGGL(k_extract_w2_roll, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_words, wpr, nk_uniform,
@@ -259,7 +259,7 @@ int soa_to_aos(rfx_ctx *ctx, const uint64_t *d_soa, int64_t n, int W, uint64_t *
 }
 
 bool wide_fast_path(int k) {
-    return k / 32 + 1 == 2 && !(getenv("RFX_WIDE_SORT") && atoi(getenv("RFX_WIDE_SORT")) == 1);
+    return k / 32 + 1 == 2;
 }
 
 // k = 33..63: the bucketed path (hash digits, write-combining scatters, LDS-table leaves with two-word

@@ -2,7 +2,7 @@
 """Interleaved A/B of count-stage variants in ONE process on ONE device (env overrides are read
 per call by the library): prints the median per-kernel milliseconds of each variant.
 
-    python tools/ab_count.py --gbp 5 --rounds 3 "RFX_LEVEL_BITS=9,10" "RFX_LEVEL_BITS=9,10 RFX_TPB=8"
+    python tools/ab_count.py --gbp 5 --rounds 3 "RFX_LEVEL_BITS=9,10" "RFX_LEVEL_BITS=8,10"
 """
 import argparse
 import os

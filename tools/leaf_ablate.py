@@ -1,5 +1,6 @@
-"""Leaf-kernel ablations in ONE process (the RFX_* knobs are read per call): k = 31 and k = 63 on the config-2 reads.
-RFX_LEAF_DBG bits: 1 stream (+ record table) only, 2 expand but no k-mer table, 64 no record table, 128 record-table statistics."""
+"""Leaf-kernel timings in ONE process (the RFX_* knobs are read per call): k = 31 and k = 63 on the config-2 reads.
+Modes: all (default: k = 31, k = 63 and a RFX_WIDE_PRESPLIT sweep), 31, 63, 63one (one k = 63 count: pmc_wide.sh), bits
+(level-bit plans and leaf targets at k = 31)."""
 import sys, time, torch, os
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import reflexiv_amd
@@ -39,28 +40,10 @@ def run(k, env, reps=3):
 which = sys.argv[1] if len(sys.argv) > 1 else "all"
 if which in ("all", "31"):
     run(31, {})
-    run(31, {"RFX_LEAF_DBG": "128"}, 1)
-    run(31, {"RFX_LEAF_DBG": "1"})
-    run(31, {"RFX_LEAF_DBG": "2"})
-    run(31, {"RFX_LEAF_DBG": "64"})
-    run(31, {"RFX_LEAF_DBG": "66"})
-    run(31, {"RFX_LEAF_DBG": "65"})
 if which in ("all", "63"):
     run(63, {})
-    run(63, {"RFX_WIDE_STATS": "1", "RFX_TRACE": "1"}, 1)
-    run(63, {"RFX_WIDE_DBG": "1"})
-    run(63, {"RFX_WIDE_NOAGG": "1"})
-    run(63, {"RFX_WIDE_NOAGG": "1", "RFX_WIDE_DBG": "1"})
     for ps in (1600, 2000, 3200, 4000):
         run(63, {"RFX_WIDE_PRESPLIT": str(ps)})
-if which == "seg":
-    for _ in range(2):
-        run(31, {"RFX_TRACE": "1"}, 2)
-        run(31, {"RFX_SK_SEG": "16", "RFX_TRACE": "1"}, 2)
-    run(25, {})
-    run(25, {"RFX_SK_SEG": "16"})
-    run(21, {})
-    run(21, {"RFX_SK_SEG": "16"})
 if which == "63one":
     run(63, {}, 1)
 if which == "bits":
