@@ -266,12 +266,25 @@ int rfx_dev_count_reads_w(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads
                           int64_t *out_n, int64_t *out_distinct, int64_t *out_instances);
 
 /* The same for reads of different lengths (real FASTQ): d_read_len[i] bases in read i, as
- * rfx_dev_encode_reads writes them; max_read_len <= 32 * words_per_read bounds them. */
+ * rfx_dev_encode_reads writes them; max_read_len <= 32 * words_per_read bounds them.  Every d_read_len[i] must be
+ * <= max_read_len (the call cannot check it: the windows of a longer read beyond those of max_read_len are lost
+ * while *out_instances still counts them); this holds for rfx_dev_count_reads_ragged_w as well. */
 int rfx_dev_count_reads_ragged(rfx_ctx *ctx, const uint64_t *d_words, const uint32_t *d_read_len,
                                int64_t n_reads, int words_per_read, int max_read_len, int k,
                                int front_clip, int end_clip, int min_cov, int max_cov, int twin,
                                uint64_t *d_out_keys, int32_t *d_out_counts, int64_t cap,
                                int64_t *out_n, int64_t *out_distinct, int64_t *out_instances);
+
+/* k = 33..63 twin of rfx_dev_count_reads_ragged, with the output of rfx_dev_count_reads_w (ascending, 2 words per
+ * key, int64 counts).  A read emits the k > 31 counter's windows of its own length: none when
+ * len - k - end_clip + 1 <= 0 (P/ReflexivDataFrameCounter64.java:410) -- so a read of k (k + 1) bases emits 1 (2),
+ * unlike the k <= 31 rule.  No base at or past d_read_len[i] reaches a k-mer: the words past a read's length may
+ * hold anything (they may be loaded, but nothing of them is used).  RFX_E_CAP: *out_n = the survivors' need. */
+int rfx_dev_count_reads_ragged_w(rfx_ctx *ctx, const uint64_t *d_words, const uint32_t *d_read_len,
+                                 int64_t n_reads, int words_per_read, int max_read_len, int k,
+                                 int front_clip, int end_clip, int min_cov, int max_cov,
+                                 uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap,
+                                 int64_t *out_n, int64_t *out_distinct, int64_t *out_instances);
 
 /* Multi-GPU exchange support for k = 33..63: the canonical two-word k-mers of packed reads (16-byte
  * elements {word0, word1}) written contiguously per owner (owner = mulhi(hash(k-mer), n_owners)),
@@ -358,7 +371,7 @@ int rfx_dev_merge_pairs(rfx_ctx *ctx, const void *d_pairs, int64_t n_pairs, int 
  *   rfx_comm_all_reduce_i64 sum (op 0) / max (op 1) of up to 8 host int64 over the ranks, in place (count() of the
  *                           stop rule, totals, a barrier)
  *   rfx_dev_sharded_count   collective: this rank's packed reads in HBM (d_read_len: per-read lengths for ragged reads,
- *                           k = 21..31, or NULL = every read has read_len bases) -> its shard of the filtered (k-mer, count) list,
+ *                           k = 21..31 and 33..63, read_len their maximum; or NULL = every read has read_len bases) -> its shard of the filtered (k-mer, count) list,
  *                           ascending (d_out_counts: int32 for k <= 31, int64 beyond, as the fused calls; k / 32 + 1 words per
  *                           key).  k = 21..31 and 33..63 exchange super-k-mer records in generations; every other k of the
  *                           counters (3..20, 65..125; not a multiple of 32) exchanges its k-mer instances in one go;
@@ -400,7 +413,8 @@ int rfx_dev_sharded_assemble(rfx_ctx *ctx, rfx_comm *comm, const uint64_t *d_key
  * Spark executor per GPU calls with ITS partition of the reads): upload + 2-bit encode (any read lengths), the sharded
  * count above, then rfx_dev_sharded_assemble (gather_below as there: a bacterial genome's survivors go to rank 0 at once,
  * a record set that does not fit one GPU stays sharded).  The contig text arrives on rank 0 (*out_len = 0 on the others;
- * RFX_E_CAP on every rank, see there).  k = 21..31.  Collective. */
+ * RFX_E_CAP on every rank, see there).  k = 21..31, and k = 33..63 as rfx_assemble_reads takes it (int64 counts, then
+ * KmerBinarizer + the count filter on every rank's shard, then the k > 31 driver on (k-1)/31+1-word keys).  Collective. */
 int rfx_sharded_assemble_reads(rfx_ctx *ctx, rfx_comm *comm, const uint8_t *bases, const int64_t *read_off, int64_t n_reads,
                                const rfx_params *prm, int generations, int64_t gather_below, char *out, int64_t cap,
                                int64_t *out_len, int64_t *out_contigs, int64_t *trace, int64_t trace_cap, int64_t *n_trace,
@@ -469,8 +483,10 @@ int rfx_assemble_counts_w(rfx_ctx *ctx, const uint64_t *kmers, const int32_t *co
 
 /* The whole resident path from ASCII reads in host memory (any lengths) to the contig text:
  * upload, 2-bit encode, extract + count + filter (prm->min_cov .. max_cov), the driver above --
- * nothing but the reads goes up and nothing but the text comes back.  k <= 31.
- * out_kept (optional) = number of k-mers that passed the coverage filter. */
+ * nothing but the reads goes up and nothing but the text comes back.  k <= 31, and k = 33..63: the reference's two-step
+ * route there (`counter -kmer K` then `run -kmerc ... -kmer K`): rfx_dev_count_reads_w (_ragged_w for reads of different
+ * lengths) with the min_cov .. max_cov filter, rfx_dev_counter_to_asm with the same bounds, rfx_dev_assemble_w.
+ * out_kept (optional) = number of k-mers that passed the coverage filter(s): those handed to the driver. */
 int rfx_assemble_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_off, int64_t n_reads,
                        const rfx_params *prm, char *out, int64_t cap, int64_t *out_len,
                        int64_t *out_contigs, int64_t *trace, int64_t trace_cap, int64_t *n_trace,

@@ -68,6 +68,11 @@ public final class Rfx {
     public static native void extrasOperator(long ctx, int op, RfxRecords in, long[] partStart, int k, RfxRecords out, long[] outPartStart);
     public static native byte[] contigsText(long ctx, RfxRecords in, int k, int minContig, int twin);
 
+    /**
+     * The whole resident path in one call (rfx_assemble_reads): ASCII reads of any length -> contig text.  k <= 31, and
+     * k = 33..63 as the reference's `counter -kmer K` then `run -kmerc ... -kmer K` (the k &gt; 31 counter, KmerBinarizer +
+     * the count filter, ReflexivDSMain64.assemblyFromKmer); params[P_K] passes k through.
+     */
     public static native byte[] assembleReads(long ctx, byte[] bases, long[] readOff, int[] params);
 
     /** ReflexivDSDynamicKmerDedup.assemblyFromKmer on a run's contig text: every contig once (rfx_dedup_contig_text) */
@@ -90,7 +95,8 @@ public final class Rfx {
     public static native void commDestroy(long comm);
     public static native void commAllReduce(long ctx, long comm, long[] vals, int op);
     // gatherBelow: the extend stage (every sortByKey) stays range-sharded over the GPUs while the record set has more records
-    // than this; then rank 0 finishes (-1: the library's default, 0: never gather before the loop ends)
+    // than this; then rank 0 finishes (-1: the library's default, 0: never gather before the loop ends).  k = 21..31 and 33..63
+    // (the latter as assembleReads takes it)
     public static native byte[] shardedAssembleReads(long ctx, long comm, byte[] bases, long[] readOff, int[] params, int generations,
                                                      long gatherBelow, long[] totals);
 }

@@ -130,15 +130,19 @@ public class ReflexivGpuMain implements Serializable {
     /**
      * Resident form: the whole path in one native call per GPU (rfx_assemble_reads).  The reads of the job are
      * collected to the driver's GPU; for read sets beyond one GPU see {@link #assemblyResidentSharded(int)}.
+     * k = 33..63: the reference's `counter -kmer K` then `run -kmerc ... -kmer K` -- the reads as the counter takes them
+     * ({@link CounterSeqLine}) and the text under Assemble_k (ReflexivDSMain64.java:820-824).
      */
     public void assemblyResident() {
         JavaSparkContext sc = new JavaSparkContext(setSparkConfiguration());
-        JavaRDD<String> FastqRDD = sc.textFile(param.inputFqPath).map(new FastqFilterWithQual()).filter(new FastqUnitFilter());
+        final boolean wide = param.kmerSize > 31;
+        JavaRDD<String> FastqRDD = wide ? sc.textFile(param.inputFqPath).filter(new CounterSeqLine())
+                : sc.textFile(param.inputFqPath).map(new FastqFilterWithQual()).filter(new FastqUnitFilter());
         List<String> units = FastqRDD.collect();
         ByteArrayOutputStream bases = new ByteArrayOutputStream();
         long[] readOff = new long[units.size() + 1];
         for (int i = 0; i < units.size(); i++) {
-            byte[] seq = units.get(i).split("\\n")[1].getBytes(StandardCharsets.US_ASCII);
+            byte[] seq = (wide ? units.get(i) : units.get(i).split("\\n")[1]).getBytes(StandardCharsets.US_ASCII);
             bases.write(seq, 0, seq.length);
             readOff[i + 1] = bases.size();
         }
@@ -152,7 +156,7 @@ public class ReflexivGpuMain implements Serializable {
         List<String> one = new ArrayList<String>();
         String s = new String(text, StandardCharsets.US_ASCII);
         one.add(s.endsWith("\n") ? s.substring(0, s.length() - 1) : s);
-        sc.parallelize(one, 1).saveAsTextFile(param.outputPath);
+        sc.parallelize(one, 1).saveAsTextFile(wide ? param.outputPath + "/Assemble_" + param.kmerSize : param.outputPath);
         sc.stop();
     }
 
@@ -165,8 +169,9 @@ public class ReflexivGpuMain implements Serializable {
      */
     public void assemblyResidentSharded(final int nGpus) {
         JavaSparkContext sc = new JavaSparkContext(setSparkConfiguration());
-        JavaRDD<String> FastqRDD = sc.textFile(param.inputFqPath).map(new FastqFilterWithQual()).filter(new FastqUnitFilter())
-                .repartition(nGpus);
+        final boolean wide = param.kmerSize > 31;                           // (as in assemblyResident)
+        JavaRDD<String> FastqRDD = (wide ? sc.textFile(param.inputFqPath).filter(new CounterSeqLine())
+                : sc.textFile(param.inputFqPath).map(new FastqFilterWithQual()).filter(new FastqUnitFilter())).repartition(nGpus);
         final int[] prm = Rfx.defaultParams();
         prm[Rfx.P_K] = param.kmerSize; prm[Rfx.P_MIN_COV] = param.minKmerCoverage; prm[Rfx.P_MAX_COV] = param.maxKmerCoverage;
         prm[Rfx.P_MIN_ERROR_COV] = param.minErrorCoverage; prm[Rfx.P_MIN_CONTIG] = param.minContig;
@@ -177,7 +182,7 @@ public class ReflexivGpuMain implements Serializable {
         scala.reflect.ClassTag<String> tag = scala.reflect.ClassTag$.MODULE$.apply(String.class);
         JavaRDD<String> ContigRDD = JavaRDD.fromRDD(
                 FastqRDD.rdd().barrier().mapPartitions(new ShardedResident(prm, nGpus), false, tag), tag);
-        ContigRDD.filter(new NonEmpty()).coalesce(1).saveAsTextFile(param.outputPath);
+        ContigRDD.filter(new NonEmpty()).coalesce(1).saveAsTextFile(wide ? param.outputPath + "/Assemble_" + param.kmerSize : param.outputPath);
         sc.stop();
     }
 
@@ -185,11 +190,24 @@ public class ReflexivGpuMain implements Serializable {
         public Boolean call(String s) { return s != null && !s.isEmpty(); }
     }
 
+    /**
+     * The counter's line filter (ReflexivDataFrameCounter64's reader, P/ReflexivDataFrameCounter.java:238-290): a sequence
+     * line has more than 20 characters, does not start with '@' or '+', and has A, T, C, G or N at 0, 4, 9, 14 and 19.
+     */
+    static class CounterSeqLine implements Function<String, Boolean>, Serializable {
+        private static boolean seq(char a) { return a == 'A' || a == 'T' || a == 'C' || a == 'G' || a == 'N'; }
+        public Boolean call(String s) {
+            return s.length() > 20 && s.charAt(0) != '@' && s.charAt(0) != '+' && seq(s.charAt(0)) && seq(s.charAt(4))
+                    && seq(s.charAt(9)) && seq(s.charAt(14)) && seq(s.charAt(19));
+        }
+    }
+
     static class ShardedResident extends scala.runtime.AbstractFunction1<scala.collection.Iterator<String>, scala.collection.Iterator<String>>
             implements Serializable {
         private final int[] prm;
         private final int nGpus;
-        ShardedResident(int[] prm, int nGpus) { this.prm = prm; this.nGpus = nGpus; }
+        private final boolean wide;                                            // k > 31: the units are sequence lines
+        ShardedResident(int[] prm, int nGpus) { this.prm = prm; this.nGpus = nGpus; this.wide = prm[Rfx.P_K] > 31; }
 
         public scala.collection.Iterator<String> apply(scala.collection.Iterator<String> it) {
             return scala.collection.JavaConverters.asScalaIteratorConverter(call(scala.collection.JavaConverters.asJavaIteratorConverter(it).asJava())).asScala();
@@ -202,7 +220,8 @@ public class ReflexivGpuMain implements Serializable {
             List<Long> off = new ArrayList<Long>();
             off.add(0L);
             while (units.hasNext()) {
-                byte[] seq = units.next().split("\\n")[1].getBytes(StandardCharsets.US_ASCII);
+                String u = units.next();
+                byte[] seq = (wide ? u : u.split("\\n")[1]).getBytes(StandardCharsets.US_ASCII);
                 bases.write(seq, 0, seq.length);
                 off.add((long) bases.size());
             }

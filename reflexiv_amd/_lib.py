@@ -59,7 +59,7 @@ SYMBOLS = [
     "rfx_dev_count_records", "rfx_dev_assemble", "rfx_dev_synth_genome",
     "rfx_dev_synth_reads", "rfx_dev_sort_pairs", "rfx_last_count_timing",
     "rfx_extract_canon_w", "rfx_count_filter_w", "rfx_kmers_per_read_w", "rfx_dev_count_reads_w",
-    "rfx_dev_count_reads_ragged", "rfx_assemble_reads", "rfx_dev_bucket_wide_by_owner", "rfx_dev_count_wide_elems",
+    "rfx_dev_count_reads_ragged", "rfx_dev_count_reads_ragged_w", "rfx_assemble_reads", "rfx_dev_bucket_wide_by_owner", "rfx_dev_count_wide_elems",
     "rfx_dev_combine_reads", "rfx_dev_bucket_pairs_by_owner", "rfx_dev_merge_pairs",
     "rfx_dev_bucket_wide_records_by_owner", "rfx_dev_count_wide_records",
     "rfx_extras_operator", "rfx_assemble_counts_w", "rfx_dev_rc_expand_subkmer", "rfx_dev_sort_records", "rfx_dev_fork_filter",

@@ -5,6 +5,8 @@
 #include <algorithm>
 #include <cstring>
 
+#include <hip/hip_runtime_api.h>
+
 namespace reflexiv {
 
 rfx_records ReflexivSubKmerRDD::view() {
@@ -276,7 +278,9 @@ std::string ReflexivMain::assemblyResident(const std::string &fastqText, std::ve
     if (!param.bubble)
         throw std::runtime_error("-bubble (no fork filtering) is unusable in the reference too (SURVEY.md C.6)");
     std::vector<uint8_t> bases; std::vector<int64_t> readOff;
-    FastqFilterWithQual{*this}.call(fastqText, bases, readOff);
+    // k > 31: the reads as `counter` takes them (ReflexivDataFrameCounter64), the first step of the two-step route
+    if (param.kmerSize > 31) DSFastqFilterOnlySeq{*this}.call(fastqText, bases, readOff);
+    else FastqFilterWithQual{*this}.call(fastqText, bases, readOff);
     rfx_params prm;
     rfx_default_params(&prm);
     prm.k = param.kmerSize; prm.min_cov = param.minKmerCoverage; prm.max_cov = param.maxKmerCoverage;
@@ -426,7 +430,9 @@ std::string ReflexivMain::assemblyResidentSharded(const std::string &fastqText, 
     if (!param.bubble)
         throw std::runtime_error("-bubble (no fork filtering) is unusable in the reference too (SURVEY.md C.6)");
     std::vector<uint8_t> bases; std::vector<int64_t> readOff;
-    FastqFilterWithQual{*this}.call(fastqText, bases, readOff);
+    // k > 31: the reads as `counter` takes them (ReflexivDataFrameCounter64), the first step of the two-step route
+    if (param.kmerSize > 31) DSFastqFilterOnlySeq{*this}.call(fastqText, bases, readOff);
+    else FastqFilterWithQual{*this}.call(fastqText, bases, readOff);
     rfx_params prm;
     rfx_default_params(&prm);
     prm.k = param.kmerSize; prm.min_cov = param.minKmerCoverage; prm.max_cov = param.maxKmerCoverage;
@@ -583,25 +589,91 @@ std::string ReflexivMain::assemblyFromKmer64(const std::string &csvText, std::ve
     return out;
 }
 
+// the k > 31 counter's rows "KMER,count" (P/ReflexivDataFrameCounter64.java:222-233), ascending k-mers
+std::string ReflexivMain::countRows64(const std::vector<uint64_t> &keys, const std::vector<int64_t> &cnt) {
+    const int W = param.kmerSize / 32 + 1;
+    std::string out;
+    DSBinaryKmerToString toString{*this};
+    for (size_t i = 0; i < cnt.size(); i++) {
+        out += toString.call(keys.data() + i * W);
+        out.push_back(',');
+        out += std::to_string(cnt[i]);
+        out.push_back('\n');
+    }
+    return out;
+}
+
+// `counter --resident` at k = 33..63: the same rows as counter(), the reads packed and counted in HBM
+// (rfx_dev_count_reads_w for reads of one length, rfx_dev_count_reads_ragged_w otherwise)
+std::string ReflexivMain::counterResident(const std::string &fastqText) {
+    const int k = param.kmerSize;
+    if (k < 33 || k > 63) throw std::runtime_error("counter --resident: -kmer 33..63");
+    std::vector<uint8_t> bases; std::vector<int64_t> readOff;
+    DSFastqFilterOnlySeq{*this}.call(fastqText, bases, readOff);      // as counter()
+    const int64_t nr = (int64_t)readOff.size() - 1;
+    if (nr <= 0) return std::string();
+    int64_t maxlen = 1, minlen = INT64_MAX;
+    for (int64_t r = 0; r < nr; r++) {
+        const int64_t l = readOff[r + 1] - readOff[r];
+        maxlen = std::max(maxlen, l); minlen = std::min(minlen, l);
+    }
+    const int wpr = (int)((maxlen + 31) / 32);
+    struct Dev {                                                       // device buffers of this call
+        std::vector<void *> ps;
+        void *get(size_t bytes) {
+            void *p = nullptr;
+            if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) throw std::runtime_error("counter --resident: hipMalloc failed");
+            ps.push_back(p);
+            return p;
+        }
+        ~Dev() { for (void *p : ps) (void)hipFree(p); }
+    } dev;
+    auto up = [](void *d, const void *h, size_t bytes) {
+        if (bytes && hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("counter --resident: upload failed");
+    };
+    auto down = [](void *h, const void *d, size_t bytes) {
+        if (bytes && hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("counter --resident: download failed");
+    };
+    check(rfx_ctx_sync(ctx), "rfx_ctx_sync");
+    auto *d_bases = (uint8_t *)dev.get(bases.size());
+    auto *d_off = (int64_t *)dev.get((size_t)(nr + 1) * 8);
+    auto *d_words = (uint64_t *)dev.get((size_t)nr * wpr * 8);
+    auto *d_len = (uint32_t *)dev.get((size_t)nr * 4);
+    up(d_bases, bases.data(), bases.size());
+    up(d_off, readOff.data(), (size_t)(nr + 1) * 8);
+    check(rfx_dev_encode_reads(ctx, d_bases, d_off, nr, wpr, d_words, d_len), "rfx_dev_encode_reads");
+    const bool uniform = minlen == maxlen;
+    int64_t cap = std::max<int64_t>(1 << 16, (int64_t)bases.size() / 8), m = 0, dist = 0, inst = 0;
+    uint64_t *d_keys = nullptr; int64_t *d_counts = nullptr;
+    for (;;) {                                                         // grow on RFX_E_CAP (*out_n = the need)
+        d_keys = (uint64_t *)dev.get((size_t)cap * 16);
+        d_counts = (int64_t *)dev.get((size_t)cap * 8);
+        const int st = uniform
+            ? rfx_dev_count_reads_w(ctx, d_words, nr, wpr, (int)maxlen, k, param.frontClip, param.endClip, param.minKmerCoverage,
+                                    param.maxKmerCoverage, d_keys, d_counts, cap, &m, &dist, &inst)
+            : rfx_dev_count_reads_ragged_w(ctx, d_words, d_len, nr, wpr, (int)maxlen, k, param.frontClip, param.endClip,
+                                           param.minKmerCoverage, param.maxKmerCoverage, d_keys, d_counts, cap, &m, &dist, &inst);
+        if (st == RFX_E_CAP && m > cap) { cap = m; continue; }
+        check(st, uniform ? "rfx_dev_count_reads_w" : "rfx_dev_count_reads_ragged_w");
+        break;
+    }
+    check(rfx_ctx_sync(ctx), "rfx_ctx_sync");
+    std::vector<uint64_t> keys((size_t)m * 2); std::vector<int64_t> cnt((size_t)m);
+    down(keys.data(), d_keys, (size_t)m * 16);
+    down(cnt.data(), d_counts, (size_t)m * 8);
+    return countRows64(keys, cnt);
+}
+
 // P/ReflexivCounter.java:109-191: k-mer, count text lines
 std::string ReflexivMain::counter(const std::string &fastqText) {
     static const char NUC[4] = {'A', 'C', 'G', 'T'};
     std::vector<uint8_t> bases; std::vector<int64_t> readOff;
     DSFastqFilterOnlySeq{*this}.call(fastqText, bases, readOff);      // P/ReflexivDataFrameCounter.java:170-173
     if (param.kmerSize > 31) {                       // P/ReflexivDataFrameCounter64.java:133-232
-        const int W = param.kmerSize / 32 + 1;
         std::vector<uint64_t> kmers = ReverseComplementKmerBinaryExtractionFromDataset64{*this}.call(bases, readOff);
         std::vector<uint64_t> keys; std::vector<int64_t> cnt;
         KmerBlocksCount{*this}.call(kmers, keys, cnt);
-        std::string out;
-        DSBinaryKmerToString toString{*this};
-        for (size_t i = 0; i < cnt.size(); i++) {
-            out += toString.call(keys.data() + i * W);
-            out.push_back(',');
-            out += std::to_string(cnt[i]);
-            out.push_back('\n');
-        }
-        return out;
+        return countRows64(keys, cnt);
     }
     std::vector<uint64_t> kmers = ReverseComplementKmerBinaryExtraction{*this}.call(bases, readOff);
     KmerBinaryRDD counts = KmerCounting_KmerCoverageFilter{*this}.call(kmers);

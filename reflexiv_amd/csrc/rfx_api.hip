@@ -853,6 +853,35 @@ int rfx_dev_count_reads_ragged(rfx_ctx *ctx, const uint64_t *d_words, const uint
                         out_distinct);
 } RFX_API_CATCH(ctx)
 
+int rfx_dev_count_reads_ragged_w(rfx_ctx *ctx, const uint64_t *d_words, const uint32_t *d_read_len, int64_t n_reads,
+                                 int words_per_read, int max_read_len, int k, int front_clip, int end_clip, int min_cov,
+                                 int max_cov, uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap, int64_t *out_n,
+                                 int64_t *out_distinct, int64_t *out_instances) try {
+    if (!ctx || !out_n || n_reads < 0 || (n_reads > 0 && (!d_words || !d_read_len))) return RFX_E_ARG;
+    RFX_TRY(check_k_w(k));
+    if (!wide_fast_path(k) || front_clip < 0 || end_clip < 0 || max_read_len < 0 || words_per_read * 32 < max_read_len)
+        return RFX_E_ARG;                                      // k = 33..63 (two-word k-mers)
+    RFX_HIP(hipSetDevice(ctx->device));
+    *out_n = 0;
+    if (out_distinct) *out_distinct = 0;
+    if (out_instances) *out_instances = 0;
+    ctx->timing.clear();
+    // segments per read from the longest read; every read emits what its own length allows (counter64 skip rule)
+    const int64_t nk = kmers_per_read_w(max_read_len, k, front_clip, end_clip);
+    int64_t n_inst = 0;
+    RFX_TRY(ragged_instances(ctx, d_read_len, n_reads, k, front_clip, end_clip, &n_inst, true));
+    if (out_instances) *out_instances = n_inst;
+    if (n_inst == 0 || nk <= 0) return RFX_OK;
+    int64_t m = 0;
+    int st = count_wide2_reads(ctx, d_words, n_reads, words_per_read, nk, k, front_clip, min_cov, max_cov, d_out_keys,
+                               d_out_counts, cap, &m, out_distinct, d_read_len, end_clip, n_inst);
+    *out_n = m;
+    if (st == RFX_OK) st = order_wide2(ctx, d_out_keys, d_out_counts, m, k);
+    RFX_TRY(sync_checked(ctx));
+    ScopedTimer::collect(ctx);
+    return st;
+} RFX_API_CATCH(ctx)
+
 int rfx_dev_bucket_wide_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int words_per_read, int read_len,
                                  int k, int front_clip, int end_clip, int n_owners, void *d_out_elems, int64_t cap_elems,
                                  int64_t *d_owner_off, int64_t *h_owner_off) try {
@@ -1364,7 +1393,13 @@ int rfx_assemble_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_o
                        const rfx_params *prm, char *out, int64_t cap, int64_t *out_len, int64_t *out_contigs,
                        int64_t *trace, int64_t trace_cap, int64_t *n_trace, int64_t *out_kept) try {
     if (!ctx || !read_off || !prm || !out_len || n_reads < 0) return RFX_E_ARG;
-    RFX_TRY(check_k(prm->k));
+    const bool wide = prm->k > 31;                 // k = 33..63: the k > 31 counter and driver (below)
+    if (wide) {
+        RFX_TRY(check_k_w(prm->k));
+        if (!wide_fast_path(prm->k)) return RFX_E_ARG;
+    } else {
+        RFX_TRY(check_k(prm->k));
+    }
     RFX_HIP(hipSetDevice(ctx->device));
     const bool verbose = getenv("RFX_TRACE") != nullptr;
     auto now_ms = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
@@ -1459,6 +1494,40 @@ int rfx_assemble_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_o
     const double t_up = now_ms();
     if (verbose) fprintf(stderr, "assemble_reads: upload queued + length scan %.1f ms, until the last chunk is encoded %.1f ms more (%.1f GB/s of ASCII in all)\n",
                          t_scan - t_in, t_up - t_scan, nb / ((t_up - t_in) * 1e6));
+    if (wide) {
+        // the two-step route of the reference at k > 31 (`counter -kmer K`, then `run -kmerc ... -kmer K`):
+        // ReflexivDataFrameCounter64's count and filter, KmerBinarizer + the from-counts filter, ReflexivDSMain64's driver
+        const int k = prm->k, aw = asm_words(k);
+        int64_t m = 0, dist = 0, inst = 0;
+        int64_t kcap = std::max<int64_t>(1 << 20, (uniform ? kmers_per_read_w((int)maxlen, k, prm->front_clip, prm->end_clip) * n_reads
+                                                            : (int64_t)nb) / 8);
+        DevBuf wk, wc;
+        for (;;) {                                  // survivors are few; grow on RFX_E_CAP
+            RFX_HIP(wk.alloc((size_t)kcap * 2 * 8, ctx->stream));
+            RFX_HIP(wc.alloc((size_t)kcap * 8, ctx->stream));
+            const int st = uniform
+                ? rfx_dev_count_reads_w(ctx, d_words.as<uint64_t>(), n_reads, wpr, (int)maxlen, k, prm->front_clip, prm->end_clip,
+                                        prm->min_cov, prm->max_cov, wk.as<uint64_t>(), wc.as<int64_t>(), kcap, &m, &dist, &inst)
+                : rfx_dev_count_reads_ragged_w(ctx, d_words.as<uint64_t>(), d_len.as<uint32_t>(), n_reads, wpr, (int)maxlen, k,
+                                               prm->front_clip, prm->end_clip, prm->min_cov, prm->max_cov, wk.as<uint64_t>(),
+                                               wc.as<int64_t>(), kcap, &m, &dist, &inst);
+            if (st == RFX_E_CAP && m > kcap) { kcap = m; continue; }
+            RFX_TRY(st);
+            break;
+        }
+        DevBuf ak, ac;
+        RFX_HIP(ak.alloc((size_t)std::max<int64_t>(m, 1) * aw * 8, ctx->stream));
+        RFX_HIP(ac.alloc((size_t)std::max<int64_t>(m, 1) * 4, ctx->stream));
+        int64_t m2 = 0;
+        RFX_TRY(counter_to_asm(ctx, wk.as<uint64_t>(), wc.as<int64_t>(), m, k, prm->min_cov, prm->max_cov, ak.as<uint64_t>(),
+                               ac.as<int32_t>(), &m2));
+        RFX_TRY(sync_checked(ctx));
+        wk.release(); wc.release();
+        if (out_kept) *out_kept = m2;
+        if (verbose) fprintf(stderr, "assemble_reads: count %.1f ms (%lld instances, %lld kept)\n", now_ms() - t_up, (long long)inst, (long long)m2);
+        return rfx_dev_assemble_w(ctx, ak.as<uint64_t>(), ac.as<int32_t>(), m2, prm, out, cap, out_len, out_contigs, trace,
+                                  trace_cap, n_trace);
+    }
     int64_t n_inst = 0;
     if (!uniform) {
         rs.read_len_arr = d_len.as<uint32_t>();

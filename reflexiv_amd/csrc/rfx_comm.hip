@@ -343,11 +343,10 @@ int rfx_dev_sharded_count(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_words, co
         return RFX_E_ARG;
     comm_options(c);
     const bool wide = k > 32;
-    if (wide && d_read_len) { ctx->last_error = "ragged reads: k <= 31 only on the device path"; return RFX_E_ARG; }
     if (wide ? (k > 63) : (k < 21 || k > 31)) {
         // outside the record path the k-mer instances themselves travel (one-word k-mers up to k = 31, the counter's three- and
         // four-word k-mers up to k = 125); k a multiple of 32 is no k of the reference's counters either
-        if (d_read_len) { ctx->last_error = "ragged reads: k = 21..31 only on the sharded device path"; return RFX_E_ARG; }
+        if (d_read_len) { ctx->last_error = "ragged reads: k = 21..31 and 33..63 only on the sharded device path"; return RFX_E_ARG; }
         if (k < 3 || k > 125 || k % 32 == 0) { ctx->last_error = "rfx_dev_sharded_count: k = 3..125, not a multiple of 32"; return RFX_E_ARG; }
         RFX_HIP(hipSetDevice(ctx->device));
         return sharded_count_kmers(ctx, c, d_words, n_reads, words_per_read, read_len, k, front_clip, end_clip, min_cov, max_cov, twin,
@@ -386,7 +385,7 @@ int rfx_dev_sharded_count(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_words, co
     auto bucket = [&]() -> int {
         if (d_read_len) {
             rs.read_len_arr = d_read_len;
-            RFX_TRY(rfx::ragged_instances(ctx, d_read_len, n_reads, k, front_clip, end_clip, &rs.n_instances));
+            RFX_TRY(rfx::ragged_instances(ctx, d_read_len, n_reads, k, front_clip, end_clip, &rs.n_instances, wide));
             inst = rs.n_instances;
         }
         if (c->units_per_read <= 0) c->units_per_read = (double)nk / 5.0 + 1.0;
@@ -400,11 +399,15 @@ int rfx_dev_sharded_count(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_words, co
             bool swept = false;
             if (wide) {
                 st = rfx::bucket_wide_records_by_owner_sweep(ctx, d_words, n_reads, words_per_read, nk, k, front_clip, bins, c->send,
-                                                             cap_rec, pb, pe, &nrec, &swept);
-                if (st == RFX_OK && !swept)
+                                                             cap_rec, pb, pe, &nrec, &swept, d_read_len, end_clip);
+                if (st == RFX_OK && !swept && !d_read_len)
                     st = rfx_dev_bucket_wide_records_by_owner(ctx, d_words, n_reads, words_per_read, read_len, k, front_clip, end_clip, bins,
                                                               c->send, cap_rec, c->d_tab, pb, &nrec);
-                else
+                else if (st == RFX_OK && !swept) {           // ragged reads: the same two-pass form with their lengths
+                    st = rfx::bucket_wide_records_by_owner(ctx, d_words, n_reads, words_per_read, nk, k, front_clip, bins, c->send, cap_rec,
+                                                           c->d_tab, pb, &nrec, d_read_len, end_clip);
+                    ScopedTimer::collect(ctx);
+                } else
                     ScopedTimer::collect(ctx);
             } else {
                 st = rfx::bucket_records_by_owner_sweep(ctx, &rs, bins, c->send, cap_rec, pb, pe, &nrec, &swept);
@@ -650,13 +653,17 @@ int rfx_dev_gather_shards(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_keys, con
 
 // The whole resident path on several GPUs from ASCII reads in host memory: every rank uploads and encodes ITS reads
 // (any lengths), rfx_dev_sharded_count, the shards gathered on rank 0, the driver there (rfx_dev_assemble) -> the
-// contig text on rank 0 (*out_len = 0 elsewhere).  k = 21..31.  Collective.  out_totals[3] as rfx_dev_sharded_count.
+// contig text on rank 0 (*out_len = 0 elsewhere).  k = 21..31; k = 33..63 through the k > 31 counter (two-word keys, int64
+// counts), KmerBinarizer + the from-counts filter on every rank's shard and the k > 31 driver, as rfx_assemble_reads does on one
+// GPU.  Collective.  out_totals[3] as rfx_dev_sharded_count.
 int rfx_sharded_assemble_reads(rfx_ctx *ctx, rfx_comm *c, const uint8_t *bases, const int64_t *read_off, int64_t n_reads,
                                const rfx_params *prm, int generations, int64_t gather_below, char *out, int64_t cap, int64_t *out_len,
                                int64_t *out_contigs, int64_t *trace, int64_t trace_cap, int64_t *n_trace, int64_t *out_totals) try {
     if (!ctx || !c || c->ctx != ctx || !read_off || !prm || !out_len || n_reads < 0) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     const int k = prm->k;
+    const bool wide = k > 32;                                         // (k > 63 is refused by the count below, on every rank)
+    const int kw = wide ? 2 : 1, cb = wide ? 8 : 4;                   // counter key words and count bytes
     const int64_t nb = n_reads ? read_off[n_reads] - read_off[0] : 0;
     int64_t maxlen = 1;
     for (int64_t r = 0; r < n_reads; r++) maxlen = std::max(maxlen, read_off[r + 1] - read_off[r]);
@@ -695,7 +702,7 @@ int rfx_sharded_assemble_reads(rfx_ctx *ctx, rfx_comm *c, const uint8_t *bases, 
     int64_t kcap = std::max<int64_t>(1 << 20, nb / 8), m = 0, tot[3] = {0, 0, 0};
     for (;;) {                                                        // survivors are few; every rank grows together
         int st = RFX_OK;
-        if (d_keys.alloc((size_t)kcap * 8, ctx->stream) != hipSuccess || d_counts.alloc((size_t)kcap * 4, ctx->stream) != hipSuccess) {
+        if (d_keys.alloc((size_t)kcap * 8 * kw, ctx->stream) != hipSuccess || d_counts.alloc((size_t)kcap * cb, ctx->stream) != hipSuccess) {
             ctx->last_error = "rfx_sharded_assemble_reads: no room for the shard";
             st = RFX_E_HIP;
         }
@@ -714,6 +721,30 @@ int rfx_sharded_assemble_reads(rfx_ctx *ctx, rfx_comm *c, const uint8_t *bases, 
     }
     if (out_totals) { out_totals[0] = tot[0]; out_totals[1] = tot[1]; out_totals[2] = tot[2]; }
     d_words.release(); d_len.release();
+    if (wide) {
+        // KmerBinarizer + the from-counts filter (P/ReflexivDSMain64.java:458-478) on this rank's shard: a k-mer and its count
+        // live on one rank, so the shards stay disjoint; the driver takes the (k-1)/31+1-word keys in any order
+        int st = RFX_OK;
+        int64_t m2 = 0;
+        const int aw = rfx::asm_words(k);
+        if (g_keys.alloc((size_t)std::max<int64_t>(m, 1) * aw * 8, ctx->stream) != hipSuccess ||
+            g_counts.alloc((size_t)std::max<int64_t>(m, 1) * 4, ctx->stream) != hipSuccess) {
+            ctx->last_error = "rfx_sharded_assemble_reads: no room for the binarized shard";
+            st = RFX_E_HIP;
+        }
+        if (st == RFX_OK) {
+            try {
+                st = rfx::counter_to_asm(ctx, d_keys.as<uint64_t>(), d_counts.as<int64_t>(), m, k, prm->min_cov, prm->max_cov,
+                                         g_keys.as<uint64_t>(), g_counts.as<int32_t>(), &m2);
+                if (st == RFX_OK) st = sync_checked(ctx);
+            } catch (...) { st = rfx_api_exception(ctx, "rfx_sharded_assemble_reads"); }
+        }
+        if (st != RFX_OK) (void)hipStreamSynchronize(ctx->stream);
+        RFX_TRY(agree(st, "KmerBinarizer"));
+        d_keys.release(); d_counts.release();
+        return rfx_dev_sharded_assemble(ctx, c, g_keys.as<uint64_t>(), g_counts.as<int32_t>(), m2, prm, gather_below, out, cap, out_len,
+                                        out_contigs, trace, trace_cap, n_trace);
+    }
     // the extend stage: the range shuffle of sortByKey over the ranks while the record set is larger than `gather_below`,
     // the rest on rank 0 (rfx_shard.hip; a bacterial genome's few million survivors go to rank 0 at once).  Its outcome is
     // every rank's: a text buffer that is too short on rank 0 is RFX_E_CAP with *out_len = the length needed on EVERY rank,

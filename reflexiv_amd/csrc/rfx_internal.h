@@ -313,8 +313,9 @@ struct ReadStore {
     const uint32_t *read_len_arr = nullptr;
     int64_t n_instances = -1;
 };
+// wide: the k > 31 counter's skip rule (k = 33..63 reads; kmers_per_read_w), else the k <= 31 one
 int ragged_instances(rfx_ctx *ctx, const uint32_t *d_read_len, int64_t n_reads, int k, int front_clip,
-                         int end_clip, int64_t *out_total);
+                         int end_clip, int64_t *out_total, bool wide = false);
 int64_t kmers_per_read(int read_len, int k, int front_clip, int end_clip);
 int encode_reads(rfx_ctx *ctx, const uint8_t *d_bases, const int64_t *d_read_off, int64_t n_reads,
                  int words_per_read, uint64_t *d_words, uint32_t *d_read_len);
@@ -337,7 +338,7 @@ int bucket_records_by_owner_sweep(rfx_ctx *ctx, const ReadStore *reads, int n_ow
                                   int64_t *h_begin, int64_t *h_end, int64_t *out_n_records, bool *done);
 int bucket_wide_records_by_owner_sweep(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
                                        int n_owners, void *d_out, int64_t cap_records, int64_t *h_begin, int64_t *h_end,
-                                       int64_t *out_n_records, bool *done);
+                                       int64_t *out_n_records, bool *done, const uint32_t *d_read_len = nullptr, int ec = 0);
 int bucket_records_by_owner(rfx_ctx *ctx, const ReadStore *reads, int n_owners, void *d_out, int64_t cap_records,
                             int64_t *d_owner_off, int64_t *h_owner_off, int64_t *out_n_records);
 int count_records(rfx_ctx *ctx, const void *d_records, int64_t n_records, int64_t n_instances_hint, int k,
@@ -345,15 +346,16 @@ int count_records(rfx_ctx *ctx, const void *d_records, int64_t n_records, int64_
                   int64_t *out_n, int64_t *out_distinct);
 int bucket_wide_records_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
                                  int n_owners, void *d_out, int64_t cap_records, int64_t *d_owner_off, int64_t *h_owner_off,
-                                 int64_t *out_n_records);
+                                 int64_t *out_n_records, const uint32_t *d_read_len = nullptr, int ec = 0);
 int count_wide_records(rfx_ctx *ctx, const void *d_records, int64_t n_records, int64_t n_instances_hint, int k, int min_cov,
                        int max_cov, uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap, int64_t *out_n,
                        int64_t *out_distinct);
 int count_wide2(rfx_ctx *ctx, const void *d_elems, int64_t n, int min_cov, int max_cov, uint64_t *d_out_keys,
                 int64_t *d_out_counts, int64_t cap, int64_t *out_n, int64_t *out_distinct);
+// ragged reads: d_read_len (per-read lengths; nk = the longest read's k-mers), their end clip and instances
 int count_wide2_reads(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
                       int min_cov, int max_cov, uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap, int64_t *out_n,
-                      int64_t *out_distinct);
+                      int64_t *out_distinct, const uint32_t *d_read_len = nullptr, int ec = 0, int64_t n_inst = -1);
 int bucket_wide_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
                          int n_owners, void *d_out, int64_t cap_elems, int64_t *d_owner_off, int64_t *h_owner_off);
 int synth_genome(rfx_ctx *ctx, uint64_t seed, int64_t genome_len, uint64_t *d_genome);

@@ -66,6 +66,14 @@ __device__ __host__ __forceinline__ int64_t nk_of(int64_t len, int k, int fc, in
     return m > 0 ? m : 0;
 }
 
+// the same for the k > 31 counter (P/ReflexivDataFrameCounter64.java:410, nk_of_w in rfx_wide.hip): a read
+// of length k (k + 1) emits one (two) k-mers there, none at k <= 31
+__device__ __host__ __forceinline__ int64_t nk_of_wide(int64_t len, int k, int fc, int ec) {
+    if (len - k - ec + 1 <= 0 || fc > len) return 0;
+    int64_t m = (len - ec - fc) - (k - 1);
+    return m > 0 ? m : 0;
+}
+
 __global__ void k_nk_per_read(const int64_t *__restrict__ read_off, int64_t n_reads, int k, int fc,
                               int ec, uint64_t *__restrict__ nk) {
     int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -76,6 +84,12 @@ __global__ void k_nk_from_len(const uint32_t *__restrict__ len, int64_t n_reads,
                               uint64_t *__restrict__ nk) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r < n_reads) nk[r] = (uint64_t)nk_of((int64_t)len[r], k, fc, ec);
+}
+
+__global__ void k_nk_from_len_w(const uint32_t *__restrict__ len, int64_t n_reads, int k, int fc, int ec,
+                                uint64_t *__restrict__ nk) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < n_reads) nk[r] = (uint64_t)nk_of_wide((int64_t)len[r], k, fc, ec);
 }
 
 // K1 in the reference's emission order: one wave per read, lanes over window positions.
@@ -181,8 +195,12 @@ struct ReadSrc {
     int wfl;                       // k = 33..63 records: bases of the k-mer on either side of the central window (else 0)
 };
 
-// k-mers read r emits
+// k-mers read r emits.  WIDE: a k = 33..63 source, whose k / fc describe the central window -- the k-mers are
+// counted on the real k (k + 2 wfl) and front clip with the counter64 skip rule (a compile-time choice: the
+// k <= 31 kernels carry none of it)
+template <bool WIDE = false>
 __device__ __forceinline__ int read_nk(const ReadSrc &s, int64_t r) {
+    if constexpr (WIDE) return s.len_arr ? (int)nk_of_wide((int64_t)s.len_arr[r], s.k + 2 * s.wfl, s.fc - s.wfl, s.ec) : s.nk;
     return s.len_arr ? (int)nk_of((int64_t)s.len_arr[r], s.k, s.fc, s.ec) : s.nk;
 }
 
@@ -1744,7 +1762,8 @@ __device__ __forceinline__ unsigned sk_digit(uint32_t canon, const Level &lv) {
 // runs (0.02 %) makes its wave recompute.
 constexpr int SKD = 8;
 
-template <int W, bool DESC>
+// WIDE: a k = 33..63 source (read_nk)
+template <int W, bool DESC, bool WIDE = false>
 __global__ __launch_bounds__(SKT) void k_sk_hist(ReadSrc s, Level lv, uint64_t *__restrict__ blockhist,
                                                  uint32_t *__restrict__ desc) {
     __shared__ uint32_t h[1 << MAX_BITS];
@@ -1767,7 +1786,7 @@ __global__ __launch_bounds__(SKT) void k_sk_hist(ReadSrc s, Level lv, uint64_t *
             // run loop: the r-th run of every lane is handled in the same iteration, so the header
             // stores of a wave go to consecutive words
             uint32_t own[2] = {0, 0};                    // owner mode: the runs' owners, 8 bits each
-            seg_runs<W, true>(s, read_nk(s, q.r), q.sgm, w, [&](int i0, int, uint32_t canon) {
+            seg_runs<W, true>(s, read_nk<WIDE>(s, q.r), q.sgm, w, [&](int i0, int, uint32_t canon) {
                 const uint64_t h64 = mmer_hash64(canon);
                 const uint32_t hdr = (uint32_t)((h64 << OWNER_BITS) >> 32);
                 const unsigned d = lv.n_owners > 0 ? (unsigned)__umul64hi(h64, (uint64_t)lv.n_owners) : rec_digit(hdr, 0, lv.bits);
@@ -1784,7 +1803,7 @@ __global__ __launch_bounds__(SKT) void k_sk_hist(ReadSrc s, Level lv, uint64_t *
                 desc[(int64_t)(2 + SKD) * s.n_threads + g] = own[1];
             }
         } else {
-            seg_runs<W, false>(s, read_nk(s, q.r), q.sgm, w, [&](int, int, uint32_t canon) { atomicAdd(&h[sk_digit(canon, lv)], 1u); }, &hi, &lo);
+            seg_runs<W, false>(s, read_nk<WIDE>(s, q.r), q.sgm, w, [&](int, int, uint32_t canon) { atomicAdd(&h[sk_digit(canon, lv)], 1u); }, &hi, &lo);
         }
         q.r += dq; q.sgm += dr;
         if (q.sgm >= s.segs) { q.sgm -= s.segs; q.r++; }
@@ -1867,7 +1886,7 @@ __global__ __launch_bounds__(SKT, WIDE ? 4 : 8) void k_sk_scatter(ReadSrc s, Lev
             };
             // `hi`/`lo` are written before the first emit() runs (seg_runs stores them first)
             auto recompute = [&]() __attribute__((always_inline)) {
-                seg_runs<W, true>(s, read_nk(s, q.r), q.sgm, w, [&](int i0, int n, uint32_t canon) {
+                seg_runs<W, true>(s, read_nk<WIDE>(s, q.r), q.sgm, w, [&](int i0, int n, uint32_t canon) {
                     const uint64_t h = mmer_hash64(canon);
                     const unsigned d = lv.n_owners > 0 ? (unsigned)__umul64hi(h, (uint64_t)lv.n_owners)
                                                        : rec_digit((uint32_t)((h << OWNER_BITS) >> 32), 0, lv.bits);
@@ -1882,7 +1901,7 @@ __global__ __launch_bounds__(SKT, WIDE ? 4 : 8) void k_sk_scatter(ReadSrc s, Lev
                 } else if (nr) {
                     // the 64 bases from the segment's first window on (as seg_runs forms them)
                     const int p0 = q.sgm * PK;
-                    int v = read_nk(s, q.r) - p0;
+                    int v = read_nk<WIDE>(s, q.r) - p0;
                     v = v > PK ? PK : v;
                     const int sh = 2 * ((s.fc + p0) & 31);
                     hi = sh ? (w[0] << sh) | (w[1] >> (64 - sh)) : w[0];
@@ -1950,7 +1969,7 @@ struct OneSweep {
     uint32_t ose, ose_shift;             // records per extent (a power of two)
 };
 
-template <int W, int SEG = 16>
+template <int W, int SEG = 16, bool WIDE = false>
 __global__ __launch_bounds__(SKT) void k_sk_sample_hist(ReadSrc s, Level lv, int sample, unsigned long long *__restrict__ hist) {
     __shared__ uint32_t h[1 << MAX_BITS];
     const int nb = 1 << lv.bits;
@@ -1965,7 +1984,7 @@ __global__ __launch_bounds__(SKT) void k_sk_sample_hist(ReadSrc s, Level lv, int
             q.sgm = (int)(g - q.r * s.segs);
             uint64_t w[3], hi, lo;
             seg_load<SEG>(s, q, w);
-            seg_runs<W, false, SEG>(s, read_nk(s, q.r), q.sgm, w, [&](int, int, uint32_t canon) { atomicAdd(&h[sk_digit(canon, lv)], 1u); }, &hi, &lo);
+            seg_runs<W, false, SEG>(s, read_nk<WIDE>(s, q.r), q.sgm, w, [&](int, int, uint32_t canon) { atomicAdd(&h[sk_digit(canon, lv)], 1u); }, &hi, &lo);
         }
     }
     __syncthreads();
@@ -2118,7 +2137,7 @@ __global__ __launch_bounds__((OsGeo<SEG, WIDE>::T), WIDE || SEG > 16 ? 4 : 8) vo
             q.sgm = (int)(g - q.r * s.segs);
             uint64_t w[3], hi = 0, lo = 0;
             seg_load<SEG>(s, q, w);
-            seg_runs<W, true, SEG>(s, read_nk(s, q.r), q.sgm, w, [&](int i0, int n, uint32_t canon) {
+            seg_runs<W, true, SEG>(s, read_nk<WIDE>(s, q.r), q.sgm, w, [&](int i0, int n, uint32_t canon) {
                 const uint64_t hh = mmer_hash64(canon);
                 const uint32_t hdr = (uint32_t)((hh << OWNER_BITS) >> 32);
                 // (by owner: the owner's bucket is 2^sub_bits bins here, so that a round still brings a bin a handful of
@@ -2973,14 +2992,14 @@ int extract_ordered_packed(rfx_ctx *ctx, const uint64_t *d_words, int wpr, const
 }
 
 int ragged_instances(rfx_ctx *ctx, const uint32_t *d_read_len, int64_t n_reads, int k, int front_clip,
-                         int end_clip, int64_t *out_total) {
+                         int end_clip, int64_t *out_total, bool wide) {
     *out_total = 0;
     if (n_reads <= 0) return RFX_OK;
     DevBuf nk, off;
     RFX_HIP(nk.alloc((size_t)n_reads * 8, ctx->stream));
     RFX_HIP(off.alloc((size_t)(n_reads + 1) * 8, ctx->stream));
-    hipLaunchKernelGGL(k_nk_from_len, dim3((unsigned)ceil_div(n_reads, 256)), dim3(256), 0, ctx->stream, d_read_len, n_reads,
-                       k, front_clip, end_clip, nk.as<uint64_t>());
+    hipLaunchKernelGGL(wide ? k_nk_from_len_w : k_nk_from_len, dim3((unsigned)ceil_div(n_reads, 256)), dim3(256), 0, ctx->stream,
+                       d_read_len, n_reads, k, front_clip, end_clip, nk.as<uint64_t>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u64(ctx, nk.as<uint64_t>(), off.as<uint64_t>(), n_reads));
     uint64_t t = 0;
@@ -3179,8 +3198,13 @@ static bool superkmer_enabled(int k) {
 }
 
 #define RFX_SK_W_CASES(X) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18)
-template <bool DESC, class... Args>
+template <bool DESC, bool WIDE = false, class... Args>
 static void launch_sk_hist(int W, dim3 grid, hipStream_t st, Args... args) {
+    if constexpr (WIDE) {                  // the central window is 30 or 31 bases: W = 18 or 19
+        if (W == 18) hipLaunchKernelGGL((k_sk_hist<18, DESC, true>), grid, dim3(SKT), 0, st, args...);
+        else hipLaunchKernelGGL((k_sk_hist<19, DESC, true>), grid, dim3(SKT), 0, st, args...);
+        return;
+    }
     switch (W) {
 #define X(w) case w: hipLaunchKernelGGL((k_sk_hist<w, DESC>), grid, dim3(SKT), 0, st, args...); break;
         RFX_SK_W_CASES(X)
@@ -3237,8 +3261,8 @@ static int records_from_reads(rfx_ctx *ctx, const ReadSrc &rsrc, const Level &lv
     if (want_desc) desc = (uint32_t *)ctx->ws_get(use_ws && ws_slot == 1 ? 0 : 1, (size_t)(3 + SKD) * 4 * (size_t)rsrc.n_threads);
     {
         ScopedTimer t(ctx, hn);
-        if (desc) launch_sk_hist<true>(W, dim3(G), ctx->stream, rsrc, lv, bh.as<uint64_t>(), desc);
-        else launch_sk_hist<false>(W, dim3(G), ctx->stream, rsrc, lv, bh.as<uint64_t>(), (uint32_t *)nullptr);
+        if (desc) launch_sk_hist<true, WIDE>(W, dim3(G), ctx->stream, rsrc, lv, bh.as<uint64_t>(), desc);
+        else launch_sk_hist<false, WIDE>(W, dim3(G), ctx->stream, rsrc, lv, bh.as<uint64_t>(), (uint32_t *)nullptr);
         RFX_HIP(hipGetLastError());
     }
     RFX_TRY(exclusive_scan_u64(ctx, bh.as<uint64_t>(), scanned.as<uint64_t>(), (int64_t)nb * G));
@@ -3308,7 +3332,10 @@ static int records_onesweep(rfx_ctx *ctx, const ReadSrc &rsrc_in, const Level &l
     {
         ScopedTimer t(ctx, hn);
         const dim3 gs((unsigned)std::min<int64_t>(n_sampled, (int64_t)ctx->num_cu * 8));
-        switch (W) {
+        if constexpr (WIDE) {
+            if (W == 18) hipLaunchKernelGGL((k_sk_sample_hist<18, 16, true>), gs, dim3(SKT), 0, ctx->stream, rsrc, lv, sample, hist.as<unsigned long long>());
+            else hipLaunchKernelGGL((k_sk_sample_hist<19, 16, true>), gs, dim3(SKT), 0, ctx->stream, rsrc, lv, sample, hist.as<unsigned long long>());
+        } else switch (W) {
 #define X(w) case w: if (seg32) hipLaunchKernelGGL((k_sk_sample_hist<w, 32>), gs, dim3(SKT), 0, ctx->stream, rsrc, lv, sample, hist.as<unsigned long long>()); \
                      else hipLaunchKernelGGL((k_sk_sample_hist<w>), gs, dim3(SKT), 0, ctx->stream, rsrc, lv, sample, hist.as<unsigned long long>()); break;
             RFX_SK_W_CASES(X)
@@ -4305,7 +4332,10 @@ static bool wide_records_enabled(int k) {
     return !(e && atoi(e) == 0) && k >= 33 && k <= 63;
 }
 
-static ReadSrc wide_read_src(const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc) {
+// ragged reads (d_read_len != nullptr): nk = the k-mers of the longest read (the segments per read), every read
+// emits nk_of_wide(its length) of them (read_nk<true>)
+static ReadSrc wide_read_src(const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
+                             const uint32_t *d_read_len = nullptr, int ec = 0) {
     ReadSrc s{};
     const int c = (k & 1) ? 31 : 30;               // central window; (k - c) / 2 bases of the k-mer on either side
     s.words = d_words; s.n_reads = n_reads; s.wpr = wpr;
@@ -4314,6 +4344,7 @@ static ReadSrc wide_read_src(const uint64_t *d_words, int64_t n_reads, int wpr, 
     s.nk = (int)nk;
     s.segs = s.nk > 0 ? (s.nk + PK - 1) / PK : 1;
     s.n_threads = s.n_reads * s.segs;
+    s.len_arr = d_read_len; s.ec = ec;
     return s;
 }
 
@@ -4329,11 +4360,13 @@ static void plan_wide_record_levels(int64_t n, std::vector<int> &bits) {
     for (int rest = B - 9; rest > 0; rest -= MAX_BITS) bits.push_back(std::min(rest, MAX_BITS));
 }
 
+// ragged reads: d_read_len and end_clip as in wide_read_src, n_inst = the k-mer instances (ragged_instances_w)
 static int count_wide2_reads_records(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
                                      int min_cov, int max_cov, uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap,
-                                     int64_t *out_n, int64_t *out_distinct) {
-    const int64_t n = nk * n_reads;
-    ReadSrc rsrc = wide_read_src(d_words, n_reads, wpr, nk, k, fc);
+                                     int64_t *out_n, int64_t *out_distinct, const uint32_t *d_read_len = nullptr, int end_clip = 0,
+                                     int64_t n_inst = -1) {
+    const int64_t n = d_read_len ? n_inst : nk * n_reads;
+    ReadSrc rsrc = wide_read_src(d_words, n_reads, wpr, nk, k, fc, d_read_len, end_clip);
     std::vector<int> bits;
     plan_wide_record_levels(n, bits);
     Level lv{};
@@ -4364,7 +4397,7 @@ static int count_wide2_reads_records(rfx_ctx *ctx, const uint64_t *d_words, int6
 // across the exchange instead of 16), and the count of records that arrived
 int bucket_wide_records_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
                                  int n_owners, void *d_out, int64_t cap_records, int64_t *d_owner_off, int64_t *h_owner_off,
-                                 int64_t *out_n_records) {
+                                 int64_t *out_n_records, const uint32_t *d_read_len, int ec) {
     StageArena stage_arena(ctx, (size_t)256 << 20);       // temporaries of this call (see StageArena)
     if (n_owners < 1 || n_owners > 64 || k < 33 || k > 63) return RFX_E_ARG;
     if (out_n_records) *out_n_records = 0;
@@ -4373,7 +4406,7 @@ int bucket_wide_records_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t 
         if (h_owner_off) memset(h_owner_off, 0, (size_t)(n_owners + 1) * 8);
         return RFX_OK;
     }
-    ReadSrc rsrc = wide_read_src(d_words, n_reads, wpr, nk, k, fc);
+    ReadSrc rsrc = wide_read_src(d_words, n_reads, wpr, nk, k, fc, d_read_len, ec);
     Level lv{};
     lv.n_owners = n_owners;
     WRec *recs = nullptr;
@@ -4392,11 +4425,11 @@ int bucket_wide_records_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t 
 // the same for the 32-byte records of k = 33..63 (bucket_wide_records_by_owner)
 int bucket_wide_records_by_owner_sweep(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
                                        int n_owners, void *d_out, int64_t cap_records, int64_t *h_begin, int64_t *h_end,
-                                       int64_t *out_n_records, bool *done) {
+                                       int64_t *out_n_records, bool *done, const uint32_t *d_read_len, int ec) {
     *done = false;
     if (n_owners < 1 || n_owners > 64 || k < 33 || k > 63) return RFX_E_ARG;
     if (nk <= 0 || n_reads <= 0) return RFX_OK;
-    return owner_sweep<true>(ctx, wide_read_src(d_words, n_reads, wpr, nk, k, fc), n_owners, d_out, cap_records, h_begin, h_end,
+    return owner_sweep<true>(ctx, wide_read_src(d_words, n_reads, wpr, nk, k, fc, d_read_len, ec), n_owners, d_out, cap_records, h_begin, h_end,
                              out_n_records, done);
 }
 
@@ -4425,15 +4458,23 @@ int count_wide_records(rfx_ctx *ctx, const void *d_records, int64_t n_records, i
     return finish_wide2<true>(ctx, cur, loff, nleaf, min_cov, max_cov, d_out_keys, d_out_counts, cap, out_n, out_distinct, k, lend);
 }
 
-// k = 33..63 from packed uniform reads: level 1 straight from the reads, then count_wide2's levels/leaves
+// k = 33..63 from packed reads of one length (d_read_len == nullptr) or of per-read lengths (nk = the longest read's
+// k-mers, n_inst = the instances of all, end_clip the clip they were counted with): level 1 straight from the reads, then
+// count_wide2's levels/leaves.  Ragged reads always take the record path: the element path's level 1 (wide_level1)
+// reads every read as nk windows long, so RFX_WIDE_RECORDS=0 does not apply to them.
 int count_wide2_reads(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
                       int min_cov, int max_cov, uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap, int64_t *out_n,
-                      int64_t *out_distinct) {
+                      int64_t *out_distinct, const uint32_t *d_read_len, int ec, int64_t n_inst) {
     StageArena stage_arena(ctx, (size_t)256 << 20);       // temporaries of this call (see StageArena)
     if (out_n) *out_n = 0;
     if (out_distinct) *out_distinct = 0;
-    const int64_t n = nk * n_reads;
-    if (n <= 0) return RFX_OK;
+    const int64_t n = d_read_len ? n_inst : nk * n_reads;
+    if (n <= 0 || nk <= 0) return RFX_OK;
+    if (d_read_len) {
+        if (k < 33 || k > 63) return RFX_E_ARG;
+        return count_wide2_reads_records(ctx, d_words, n_reads, wpr, nk, k, fc, min_cov, max_cov, d_out_keys, d_out_counts, cap,
+                                         out_n, out_distinct, d_read_len, ec, n_inst);
+    }
     if (wide_records_enabled(k))
         return count_wide2_reads_records(ctx, d_words, n_reads, wpr, nk, k, fc, min_cov, max_cov, d_out_keys, d_out_counts, cap,
                                          out_n, out_distinct);
