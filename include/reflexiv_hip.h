@@ -257,7 +257,9 @@ int rfx_dev_count_reads(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads,
                         uint64_t *d_out_keys, int32_t *d_out_counts, int64_t cap,
                         int64_t *out_n, int64_t *out_distinct, int64_t *out_instances);
 
-/* k > 31 twin of rfx_dev_count_reads (all device pointers; d_out_keys: cap*W words). */
+/* k > 31 twin of rfx_dev_count_reads (all device pointers; d_out_keys: cap*W words, W = k/32+1, ascending).  k = 33..127
+ * (W = 2..4) count on the bucketed LDS-table path with no limit on the instances per call (only the survivors are sorted:
+ * fewer than 2^32, else RFX_E_LIMIT); W >= 5 (k >= 128) keeps the sort path (fewer than 2^32 instances per call). */
 int64_t rfx_kmers_per_read_w(int read_len, int k, int front_clip, int end_clip);
 int rfx_dev_count_reads_w(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads,
                           int words_per_read, int read_len, int k, int front_clip, int end_clip,
@@ -275,8 +277,8 @@ int rfx_dev_count_reads_ragged(rfx_ctx *ctx, const uint64_t *d_words, const uint
                                uint64_t *d_out_keys, int32_t *d_out_counts, int64_t cap,
                                int64_t *out_n, int64_t *out_distinct, int64_t *out_instances);
 
-/* k = 33..63 twin of rfx_dev_count_reads_ragged, with the output of rfx_dev_count_reads_w (ascending, 2 words per
- * key, int64 counts).  A read emits the k > 31 counter's windows of its own length: none when
+/* k = 33..127 (not 64 or 96) twin of rfx_dev_count_reads_ragged, with the output of rfx_dev_count_reads_w (ascending,
+ * k/32+1 words per key, int64 counts).  A read emits the k > 31 counter's windows of its own length: none when
  * len - k - end_clip + 1 <= 0 (P/ReflexivDataFrameCounter64.java:410) -- so a read of k (k + 1) bases emits 1 (2),
  * unlike the k <= 31 rule.  No base at or past d_read_len[i] reaches a k-mer: the words past a read's length may
  * hold anything (they may be loaded, but nothing of them is used).  RFX_E_CAP: *out_n = the survivors' need. */
@@ -294,6 +296,8 @@ int rfx_dev_bucket_wide_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t 
                                  int words_per_read, int read_len, int k, int front_clip, int end_clip,
                                  int n_owners, void *d_out_elems, int64_t cap_elems,
                                  int64_t *d_owner_off, int64_t *h_owner_off);
+/* (rfx_count_filter_w on host arrays, and the sharded count's receiver at k = 65..125, count three- and four-word k-mers
+ * straight from such AoS elements with the same bucketed path.) */
 int rfx_dev_count_wide_elems(rfx_ctx *ctx, const void *d_elems, int64_t n_elems, int k,
                              int min_cov, int max_cov,
                              uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap,
@@ -371,10 +375,11 @@ int rfx_dev_merge_pairs(rfx_ctx *ctx, const void *d_pairs, int64_t n_pairs, int 
  *   rfx_comm_all_reduce_i64 sum (op 0) / max (op 1) of up to 8 host int64 over the ranks, in place (count() of the
  *                           stop rule, totals, a barrier)
  *   rfx_dev_sharded_count   collective: this rank's packed reads in HBM (d_read_len: per-read lengths for ragged reads,
- *                           k = 21..31 and 33..63, read_len their maximum; or NULL = every read has read_len bases) -> its shard of the filtered (k-mer, count) list,
+ *                           k = 21..31 and 33..125, read_len their maximum; or NULL = every read has read_len bases) -> its shard of the filtered (k-mer, count) list,
  *                           ascending (d_out_counts: int32 for k <= 31, int64 beyond, as the fused calls; k / 32 + 1 words per
  *                           key).  k = 21..31 and 33..63 exchange super-k-mer records in generations; every other k of the
- *                           counters (3..20, 65..125; not a multiple of 32) exchanges its k-mer instances in one go;
+ *                           counters (3..20, 65..125; not a multiple of 32) exchanges its k-mer instances in one go (at
+                           65..125 bucketed by owner straight from the reads and counted with the bucketed path);
  *                           out_totals[3] = instances, distinct, survivors over ALL ranks.  `generations` (1..8) cuts
  *                           the hash space so that generation g is counted while g+1.. travel.  RFX_E_CAP -- on
  *                           EVERY rank when the shard of ANY rank did not fit -- with *out_n = what this rank needs.
@@ -413,7 +418,7 @@ int rfx_dev_sharded_assemble(rfx_ctx *ctx, rfx_comm *comm, const uint64_t *d_key
  * Spark executor per GPU calls with ITS partition of the reads): upload + 2-bit encode (any read lengths), the sharded
  * count above, then rfx_dev_sharded_assemble (gather_below as there: a bacterial genome's survivors go to rank 0 at once,
  * a record set that does not fit one GPU stays sharded).  The contig text arrives on rank 0 (*out_len = 0 on the others;
- * RFX_E_CAP on every rank, see there).  k = 21..31, and k = 33..63 as rfx_assemble_reads takes it (int64 counts, then
+ * RFX_E_CAP on every rank, see there).  k = 21..31, and k = 33..124 as rfx_assemble_reads takes it (int64 counts, then
  * KmerBinarizer + the count filter on every rank's shard, then the k > 31 driver on (k-1)/31+1-word keys).  Collective. */
 int rfx_sharded_assemble_reads(rfx_ctx *ctx, rfx_comm *comm, const uint8_t *bases, const int64_t *read_off, int64_t n_reads,
                                const rfx_params *prm, int generations, int64_t gather_below, char *out, int64_t cap,
@@ -452,7 +457,7 @@ int rfx_dev_assemble(rfx_ctx *ctx, const uint64_t *d_keys, const int32_t *d_coun
                      const rfx_params *prm, char *out, int64_t cap, int64_t *out_len,
                      int64_t *out_contigs, int64_t *trace, int64_t trace_cap, int64_t *n_trace);
 
-/* k = 33..63: put (two-word k-mer, count) pairs that are in any order (e.g. the shards of the hash-partitioned count
+/* k = 33..127 (not 64 or 96): put (k/32+1-word k-mer, count) pairs that are in any order (e.g. the shards of the hash-partitioned count
  * gathered from several GPUs) into ascending k-mer order in place -- the order rfx_dev_count_reads_w returns and the
  * from-counts driver expects (order contract: ascending by base string). */
 int rfx_dev_order_kmers_w(rfx_ctx *ctx, uint64_t *d_keys, int64_t *d_counts, int64_t n, int k);
@@ -483,7 +488,7 @@ int rfx_assemble_counts_w(rfx_ctx *ctx, const uint64_t *kmers, const int32_t *co
 
 /* The whole resident path from ASCII reads in host memory (any lengths) to the contig text:
  * upload, 2-bit encode, extract + count + filter (prm->min_cov .. max_cov), the driver above --
- * nothing but the reads goes up and nothing but the text comes back.  k <= 31, and k = 33..63: the reference's two-step
+ * nothing but the reads goes up and nothing but the text comes back.  k <= 31, and k = 33..125 (not 64 or 96): the reference's two-step
  * route there (`counter -kmer K` then `run -kmerc ... -kmer K`): rfx_dev_count_reads_w (_ragged_w for reads of different
  * lengths) with the min_cov .. max_cov filter, rfx_dev_counter_to_asm with the same bounds, rfx_dev_assemble_w.
  * out_kept (optional) = number of k-mers that passed the coverage filter(s): those handed to the driver. */

@@ -70,7 +70,7 @@ public final class Rfx {
 
     /**
      * The whole resident path in one call (rfx_assemble_reads): ASCII reads of any length -> contig text.  k <= 31, and
-     * k = 33..63 as the reference's `counter -kmer K` then `run -kmerc ... -kmer K` (the k &gt; 31 counter, KmerBinarizer +
+     * k = 33..125 (not 64 or 96) as the reference's `counter -kmer K` then `run -kmerc ... -kmer K` (the k &gt; 31 counter, KmerBinarizer +
      * the count filter, ReflexivDSMain64.assemblyFromKmer); params[P_K] passes k through.
      */
     public static native byte[] assembleReads(long ctx, byte[] bases, long[] readOff, int[] params);
@@ -95,7 +95,7 @@ public final class Rfx {
     public static native void commDestroy(long comm);
     public static native void commAllReduce(long ctx, long comm, long[] vals, int op);
     // gatherBelow: the extend stage (every sortByKey) stays range-sharded over the GPUs while the record set has more records
-    // than this; then rank 0 finishes (-1: the library's default, 0: never gather before the loop ends).  k = 21..31 and 33..63
+    // than this; then rank 0 finishes (-1: the library's default, 0: never gather before the loop ends).  k = 21..31 and 33..124
     // (the latter as assembleReads takes it)
     public static native byte[] shardedAssembleReads(long ctx, long comm, byte[] bases, long[] readOff, int[] params, int generations,
                                                      long gatherBelow, long[] totals);

@@ -130,7 +130,7 @@ public class ReflexivGpuMain implements Serializable {
     /**
      * Resident form: the whole path in one native call per GPU (rfx_assemble_reads).  The reads of the job are
      * collected to the driver's GPU; for read sets beyond one GPU see {@link #assemblyResidentSharded(int)}.
-     * k = 33..63: the reference's `counter -kmer K` then `run -kmerc ... -kmer K` -- the reads as the counter takes them
+     * k = 33..100 (not 64 or 96): the reference's `counter -kmer K` then `run -kmerc ... -kmer K` -- the reads as the counter takes them
      * ({@link CounterSeqLine}) and the text under Assemble_k (ReflexivDSMain64.java:820-824).
      */
     public void assemblyResident() {

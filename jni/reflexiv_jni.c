@@ -398,7 +398,7 @@ JNIEXPORT jbyteArray JNICALL RFX_CLASS(contigsText)(JNIEnv *env, jclass c, jlong
 /* ---------------------------------------------------------------------------- resident pipeline */
 
 /* The whole path (P/ReflexivMain.java:95-322) in one call: ASCII reads of any length up, contig text back.
- * params: int[13] in rfx_params field order (Rfx.defaultParams()).  k <= 31, and k = 33..63 as `counter -kmer K` followed by
+ * params: int[13] in rfx_params field order (Rfx.defaultParams()).  k <= 31, and k = 33..125 (not 64 or 96) as `counter -kmer K` followed by
  * `run -kmerc ... -kmer K` (rfx_assemble_reads). */
 JNIEXPORT jbyteArray JNICALL RFX_CLASS(assembleReads)(JNIEnv *env, jclass c, jlong h, jbyteArray bases, jlongArray readOff, jintArray params) {
     (void)c;

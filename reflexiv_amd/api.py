@@ -286,8 +286,9 @@ class Reflexiv:
     def count_reads_ragged_w_dev(self, d_words: int, d_read_len: int, n_reads: int, words_per_read: int, max_read_len: int,
                                  k: int, d_out_keys: int, d_out_counts: int, cap: int, min_cov=2, max_cov=10_000_000,
                                  front_clip=0, end_clip=0):
-        """count_reads_w_dev (k = 33..63) for reads of different lengths (d_read_len: uint32 per read, as encode_reads_dev
-        writes) -> (n_survivors, n_distinct, n_instances); keys cap*2 words, counts int64, ascending."""
+        """count_reads_w_dev (k = 33..127, not a multiple of 32) for reads of different lengths (d_read_len: uint32 per read, as
+        encode_reads_dev writes) -> (n_survivors, n_distinct, n_instances); keys cap*W words (W = k//32 + 1), counts int64,
+        ascending."""
         n, d, inst = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         st = self.L.rfx_dev_count_reads_ragged_w(self.ctx, C.c_void_p(d_words), C.c_void_p(d_read_len), C.c_int64(n_reads),
                                                  words_per_read, max_read_len, k, front_clip, end_clip, min_cov, max_cov,
@@ -599,7 +600,7 @@ class Reflexiv:
         return str(memoryview(buf)[:ln.value], "ascii"), int(nc.value), [int(x) for x in trace[:ntr.value]]
 
     def order_kmers_w_dev(self, d_keys: int, d_counts: int, n: int, k: int):
-        """k = 33..63: (two-word k-mer, int64 count) pairs in any order -> ascending k-mer order, in place."""
+        """k = 33..127, not 64 or 96: (W-word k-mer, int64 count) pairs in any order -> ascending k-mer order, in place."""
         self._check(self.L.rfx_dev_order_kmers_w(self.ctx, C.c_void_p(d_keys), C.c_void_p(d_counts), C.c_int64(n), k),
                     "rfx_dev_order_kmers_w")
 
@@ -642,7 +643,7 @@ class Reflexiv:
 
     def assemble_reads_ptr(self, bases_ptr: int, n_bases: int, read_off, prm: Params):
         """rfx_assemble_reads: ASCII reads in HOST memory (any lengths; bases_ptr may be pinned memory) -> upload, 2-bit
-        encode, count / filter, the driver -> (text, n_contigs, trace, kept).  k <= 31; k = 33..63 as the reference's
+        encode, count / filter, the driver -> (text, n_contigs, trace, kept).  k <= 31; k = 33..125 (not 64 or 96) as the reference's
         `counter -kmer K` then `run -kmerc ... -kmer K` (the k > 31 counter, KmerBinarizer + the count filter, the k > 31
         driver; kept = the k-mers handed to the driver)."""
         read_off = np.ascontiguousarray(read_off, np.int64)
@@ -837,7 +838,7 @@ class Reflexiv:
 
     def sharded_assemble_reads(self, bases, read_off, prm: Params, generations: int = 4, text_cap: int = None, gather_below: int = -1):
         """collective (rfx_sharded_assemble_reads): this rank's ASCII reads -> (text, n_contigs, trace, totals); text on rank 0.
-        k = 21..31 and 33..63 (the latter as assemble_reads takes it).
+        k = 21..31 and 33..124, not 64 or 96 (the latter as assemble_reads takes it).
         A text buffer that is too short on rank 0 is RFX_E_CAP on EVERY rank (with the length rank 0 needs), so the retry below
         re-enters the collective on all ranks together; text_cap forces a first size (tests)."""
         bases = np.ascontiguousarray(bases, np.uint8)

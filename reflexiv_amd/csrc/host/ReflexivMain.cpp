@@ -603,11 +603,11 @@ std::string ReflexivMain::countRows64(const std::vector<uint64_t> &keys, const s
     return out;
 }
 
-// `counter --resident` at k = 33..63: the same rows as counter(), the reads packed and counted in HBM
+// `counter --resident` at k = 33..100 (not a multiple of 32): the same rows as counter(), the reads packed and counted in HBM
 // (rfx_dev_count_reads_w for reads of one length, rfx_dev_count_reads_ragged_w otherwise)
 std::string ReflexivMain::counterResident(const std::string &fastqText) {
-    const int k = param.kmerSize;
-    if (k < 33 || k > 63) throw std::runtime_error("counter --resident: -kmer 33..63");
+    const int k = param.kmerSize, W = k / 32 + 1;
+    if (k < 33 || k > 100 || k % 32 == 0) throw std::runtime_error("counter --resident: -kmer 33..100, not 64 or 96");
     std::vector<uint8_t> bases; std::vector<int64_t> readOff;
     DSFastqFilterOnlySeq{*this}.call(fastqText, bases, readOff);      // as counter()
     const int64_t nr = (int64_t)readOff.size() - 1;
@@ -646,7 +646,7 @@ std::string ReflexivMain::counterResident(const std::string &fastqText) {
     int64_t cap = std::max<int64_t>(1 << 16, (int64_t)bases.size() / 8), m = 0, dist = 0, inst = 0;
     uint64_t *d_keys = nullptr; int64_t *d_counts = nullptr;
     for (;;) {                                                         // grow on RFX_E_CAP (*out_n = the need)
-        d_keys = (uint64_t *)dev.get((size_t)cap * 16);
+        d_keys = (uint64_t *)dev.get((size_t)cap * 8 * W);
         d_counts = (int64_t *)dev.get((size_t)cap * 8);
         const int st = uniform
             ? rfx_dev_count_reads_w(ctx, d_words, nr, wpr, (int)maxlen, k, param.frontClip, param.endClip, param.minKmerCoverage,
@@ -658,8 +658,8 @@ std::string ReflexivMain::counterResident(const std::string &fastqText) {
         break;
     }
     check(rfx_ctx_sync(ctx), "rfx_ctx_sync");
-    std::vector<uint64_t> keys((size_t)m * 2); std::vector<int64_t> cnt((size_t)m);
-    down(keys.data(), d_keys, (size_t)m * 16);
+    std::vector<uint64_t> keys((size_t)m * W); std::vector<int64_t> cnt((size_t)m);
+    down(keys.data(), d_keys, (size_t)m * 8 * W);
     down(cnt.data(), d_counts, (size_t)m * 8);
     return countRows64(keys, cnt);
 }

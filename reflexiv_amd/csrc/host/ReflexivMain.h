@@ -117,7 +117,7 @@ public:
     // ---- drivers
     // assembly(): P/ReflexivMain.java:95-322 from FASTQ text to the contig text of saveAsTextFile
     std::string assembly(const std::string &fastqText, std::vector<int64_t> *trace = nullptr);
-    // the same result through ONE call (rfx_assemble_reads): reads go up, contig text comes back.  k = 33..63: what
+    // the same result through ONE call (rfx_assemble_reads): reads go up, contig text comes back.  k = 33..100: what
     // `counter` followed by `run -kmerc` gives (the counter's FASTQ reader; also assemblyResidentSharded)
     std::string assemblyResident(const std::string &fastqText, std::vector<int64_t> *trace = nullptr);
     // the same on the nGpus GPUs of this node: one host thread, context and RCCL communicator per GPU, every thread passes its
@@ -129,7 +129,7 @@ public:
     std::string assemblyResidentSharded(const std::string &fastqText, int nGpus, std::vector<int64_t> *trace = nullptr, int64_t gatherBelow = -1);
     // ReflexivCounter.assembly(): P/ReflexivCounter.java:109-191 -> lines "KMER,count"
     std::string counter(const std::string &fastqText);
-    // `counter --resident` at k = 33..63: the same CSV, counted in HBM (rfx_dev_count_reads_w / rfx_dev_count_reads_ragged_w)
+    // `counter --resident` at k = 33..100: the same CSV, counted in HBM (rfx_dev_count_reads_w / rfx_dev_count_reads_ragged_w)
     std::string counterResident(const std::string &fastqText);
     std::string countRows64(const std::vector<uint64_t> &keys, const std::vector<int64_t> &cnt);
     std::string assemblyFromCounts(const KmerBinaryRDD &counts, std::vector<int64_t> *trace = nullptr);

@@ -60,7 +60,7 @@ int main(int argc, char **argv) {
             // M/Main.java:74-78 -> Pipelines.reflexivDSMainPipe(): -kmerc routes to assemblyFromKmer()
             // k > 31: Pipelines.reflexivDSMainPipe64() -> ReflexivDSMain64.assemblyFromKmer(), output under Assemble_<k>
             // (P/ReflexivDSMain64.java:820-824); only the from-counts route exists for k > 31 -- and --resident,
-            // which is that route (`counter`, then `run -kmerc`) fused into one call on the device (k = 33..63)
+            // which is that route (`counter`, then `run -kmerc`) fused into one call on the device (k = 33..100, not 64 or 96)
             if (param.kmerSize > 31) {
                 if (param.inputKmerPath.empty() && !param.resident)
                     throw std::runtime_error("-kmer > 31 needs -kmerc (counter -> run -kmerc; the reference's run -fastq is inconsistent for k > 31)");
@@ -86,9 +86,9 @@ int main(int argc, char **argv) {
             dir += "/Assembly_intermediate"; mkdir(dir.c_str(), 0755);
             dir += "/01Iteration" + std::to_string(param.startIteration) + "_" + std::to_string(param.endIteration); mkdir(dir.c_str(), 0755);
         } else if (cmd == "counter") {
-            // --resident at k = 33..63: the same rows through the device count of the packed reads
-            out = param.resident && param.kmerSize >= 33 && param.kmerSize <= 63 ? m.counterResident(read_all(param.inputFqPath))
-                                                                              : m.counter(read_all(param.inputFqPath));
+            // --resident at k = 33..100 (not 64 or 96): the same rows through the device count of the packed reads
+            out = param.resident && param.kmerSize >= 33 && param.kmerSize % 32 != 0 ? m.counterResident(read_all(param.inputFqPath))
+                                                                                   : m.counter(read_all(param.inputFqPath));
             dir += "/Count_" + std::to_string(param.kmerSize);               // P/ReflexivDataFrameCounter.java:222-233
             mkdir(dir.c_str(), 0755);
         } else throw std::runtime_error("unknown command " + cmd);

@@ -439,7 +439,7 @@ int rfx_count_filter_w(rfx_ctx *ctx, const uint64_t *kmers, int64_t n, int k, in
     RFX_HIP(d_counts.alloc((size_t)n * 8, ctx->stream));
     RFX_HIP(hipMemcpyAsync(d_in.p, kmers, (size_t)n * W * 8, hipMemcpyHostToDevice, ctx->stream));
     int64_t m = 0, dist = 0;
-    if (wide_fast_path(k)) {
+    if (wide_elem_path(k)) {                  // k = 33..127: the bucketed count on the AoS elements
         RFX_TRY(count_filter_w2(ctx, d_in.as<uint64_t>(), n, k, min_cov, max_cov, d_keys.as<uint64_t>(), d_counts.as<int64_t>(),
                                 n, &m, &dist));
     } else {
@@ -484,6 +484,17 @@ int rfx_dev_count_reads_w(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads
         int64_t m = 0;
         int st = count_wide2_reads(ctx, d_words, n_reads, words_per_read, nk, k, front_clip, min_cov, max_cov, d_out_keys,
                                    d_out_counts, cap, &m, out_distinct);
+        *out_n = m;
+        if (st == RFX_OK) st = order_wide2(ctx, d_out_keys, d_out_counts, m, k);
+        RFX_TRY(sync_checked(ctx));
+        ScopedTimer::collect(ctx);
+        return st;
+    }
+    if (wide_elem_path(k)) {
+        // k = 65..127 (three- and four-word k-mers): the same element path, level 1 from the packed reads
+        int64_t m = 0;
+        int st = count_wide_n_from_reads(ctx, d_words, n_reads, words_per_read, nk, k, front_clip, min_cov, max_cov, d_out_keys,
+                                         d_out_counts, cap, &m, out_distinct);
         *out_n = m;
         if (st == RFX_OK) st = order_wide2(ctx, d_out_keys, d_out_counts, m, k);
         RFX_TRY(sync_checked(ctx));
@@ -859,8 +870,8 @@ int rfx_dev_count_reads_ragged_w(rfx_ctx *ctx, const uint64_t *d_words, const ui
                                  int64_t *out_distinct, int64_t *out_instances) try {
     if (!ctx || !out_n || n_reads < 0 || (n_reads > 0 && (!d_words || !d_read_len))) return RFX_E_ARG;
     RFX_TRY(check_k_w(k));
-    if (!wide_fast_path(k) || front_clip < 0 || end_clip < 0 || max_read_len < 0 || words_per_read * 32 < max_read_len)
-        return RFX_E_ARG;                                      // k = 33..63 (two-word k-mers)
+    if (!wide_elem_path(k) || front_clip < 0 || end_clip < 0 || max_read_len < 0 || words_per_read * 32 < max_read_len)
+        return RFX_E_ARG;                                      // k = 33..127 (two- to four-word k-mers)
     RFX_HIP(hipSetDevice(ctx->device));
     *out_n = 0;
     if (out_distinct) *out_distinct = 0;
@@ -873,8 +884,11 @@ int rfx_dev_count_reads_ragged_w(rfx_ctx *ctx, const uint64_t *d_words, const ui
     if (out_instances) *out_instances = n_inst;
     if (n_inst == 0 || nk <= 0) return RFX_OK;
     int64_t m = 0;
-    int st = count_wide2_reads(ctx, d_words, n_reads, words_per_read, nk, k, front_clip, min_cov, max_cov, d_out_keys,
-                               d_out_counts, cap, &m, out_distinct, d_read_len, end_clip, n_inst);
+    int st = wide_fast_path(k)
+        ? count_wide2_reads(ctx, d_words, n_reads, words_per_read, nk, k, front_clip, min_cov, max_cov, d_out_keys, d_out_counts,
+                            cap, &m, out_distinct, d_read_len, end_clip, n_inst)
+        : count_wide_n_from_reads(ctx, d_words, n_reads, words_per_read, nk, k, front_clip, min_cov, max_cov, d_out_keys,
+                                  d_out_counts, cap, &m, out_distinct, d_read_len, end_clip, n_inst);
     *out_n = m;
     if (st == RFX_OK) st = order_wide2(ctx, d_out_keys, d_out_counts, m, k);
     RFX_TRY(sync_checked(ctx));
@@ -1375,7 +1389,7 @@ int rfx_assemble_counts_w(rfx_ctx *ctx, const uint64_t *kmers, const int32_t *co
 int rfx_dev_order_kmers_w(rfx_ctx *ctx, uint64_t *d_keys, int64_t *d_counts, int64_t n, int k) try {
     if (!ctx || n < 0 || (n > 0 && (!d_keys || !d_counts))) return RFX_E_ARG;
     RFX_TRY(check_k_w(k));
-    if (!wide_fast_path(k)) return RFX_E_ARG;
+    if (!wide_elem_path(k)) return RFX_E_ARG;                      // k = 33..127 (two- to four-word keys)
     RFX_HIP(hipSetDevice(ctx->device));
     return order_wide2(ctx, d_keys, d_counts, n, k);
 } RFX_API_CATCH(ctx)
@@ -1393,10 +1407,10 @@ int rfx_assemble_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_o
                        const rfx_params *prm, char *out, int64_t cap, int64_t *out_len, int64_t *out_contigs,
                        int64_t *trace, int64_t trace_cap, int64_t *n_trace, int64_t *out_kept) try {
     if (!ctx || !read_off || !prm || !out_len || n_reads < 0) return RFX_E_ARG;
-    const bool wide = prm->k > 31;                 // k = 33..63: the k > 31 counter and driver (below)
+    const bool wide = prm->k > 31;                 // k = 33..125: the k > 31 counter and driver (below)
     if (wide) {
         RFX_TRY(check_k_w(prm->k));
-        if (!wide_fast_path(prm->k)) return RFX_E_ARG;
+        if (!wide_elem_path(prm->k) || prm->k > 125) return RFX_E_ARG;
     } else {
         RFX_TRY(check_k(prm->k));
     }
@@ -1497,13 +1511,13 @@ int rfx_assemble_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_o
     if (wide) {
         // the two-step route of the reference at k > 31 (`counter -kmer K`, then `run -kmerc ... -kmer K`):
         // ReflexivDataFrameCounter64's count and filter, KmerBinarizer + the from-counts filter, ReflexivDSMain64's driver
-        const int k = prm->k, aw = asm_words(k);
+        const int k = prm->k, aw = asm_words(k), kw = k / 32 + 1;     // driver and counter key words
         int64_t m = 0, dist = 0, inst = 0;
         int64_t kcap = std::max<int64_t>(1 << 20, (uniform ? kmers_per_read_w((int)maxlen, k, prm->front_clip, prm->end_clip) * n_reads
                                                             : (int64_t)nb) / 8);
         DevBuf wk, wc;
         for (;;) {                                  // survivors are few; grow on RFX_E_CAP
-            RFX_HIP(wk.alloc((size_t)kcap * 2 * 8, ctx->stream));
+            RFX_HIP(wk.alloc((size_t)kcap * kw * 8, ctx->stream));
             RFX_HIP(wc.alloc((size_t)kcap * 8, ctx->stream));
             const int st = uniform
                 ? rfx_dev_count_reads_w(ctx, d_words.as<uint64_t>(), n_reads, wpr, (int)maxlen, k, prm->front_clip, prm->end_clip,

@@ -214,23 +214,32 @@ __global__ void k_owner_counts(const uint64_t *__restrict__ sorted_owner, int64_
 }
 }  // namespace
 
+// d_read_len: per-read lengths (k = 65..125 only; read_len = the longest read)
 static int sharded_count_kmers(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_words, int64_t n_reads, int wpr, int read_len, int k, int fc, int ec,
                                int min_cov, int max_cov, int twin, uint64_t *d_out_keys, void *d_out_counts, int64_t cap, int64_t *out_n,
-                               int64_t *out_totals) {
+                               int64_t *out_totals, const uint32_t *d_read_len = nullptr) {
     const int world = c->world, me = c->rank;
     const bool wide = k > 32;
     const int W = wide ? k / 32 + 1 : 1;
+    const bool elems = wide && rfx::wide_elem_path(k);        // W = 3, 4: level 1 of the count buckets by owner, the count takes the shard
     NcclApi &n = nccl();
     const int64_t nk = wide ? rfx::kmers_per_read_w(read_len, k, fc, ec) : rfx::kmers_per_read(read_len, k, fc, ec);
-    const int64_t N = nk * n_reads;
+    int64_t N = nk * n_reads;
     int64_t hoff[65];
     for (int i = 0; i <= 64; i++) hoff[i] = 0;
     DevBuf units;                                             // this rank's k-mers grouped by owner (AoS, W words each)
     // this rank's own part (its failure travels in the matrix)
     auto bucket = [&]() -> int {
-        if (N >= ((int64_t)1 << 32)) { ctx->last_error = "rfx_dev_sharded_count (k-mer units): at most 2^32 - 1 instances per rank and call"; return RFX_E_LIMIT; }
+        if (d_read_len) RFX_TRY(rfx::ragged_instances(ctx, d_read_len, n_reads, k, fc, ec, &N, true));
+        if (N >= ((int64_t)1 << 32) && !elems) { ctx->last_error = "rfx_dev_sharded_count (k-mer units): at most 2^32 - 1 instances per rank and call"; return RFX_E_LIMIT; }
         RFX_HIP(units.alloc((size_t)std::max<int64_t>(1, N) * W * 8, ctx->stream));
         if (N == 0) return RFX_OK;
+        if (elems) {
+            DevBuf doff;
+            RFX_HIP(doff.alloc((size_t)(world + 1) * 8, ctx->stream));
+            return rfx::bucket_wide_n_by_owner(ctx, d_words, n_reads, wpr, nk, k, fc, d_read_len, ec, world, units.as<uint64_t>(),
+                                               doff.as<int64_t>(), hoff);
+        }
         if (!wide) {
             rfx::ReadStore rs{d_words, n_reads, wpr, read_len, k, fc, ec};
             DevBuf doff;
@@ -291,7 +300,7 @@ static int sharded_count_kmers(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_word
     DevBuf recv, soa;
     int st_recv = RFX_OK;
     if (recv.alloc((size_t)std::max<int64_t>(1, n_in) * W * 8, ctx->stream) != hipSuccess) { st_recv = RFX_E_HIP; ctx->last_error = "rfx_dev_sharded_count: no room for what arrives"; }
-    if (n_in >= ((int64_t)1 << 32)) { st_recv = RFX_E_LIMIT; ctx->last_error = "rfx_dev_sharded_count (k-mer units): a shard of 2^32 instances or more"; }
+    if (n_in >= ((int64_t)1 << 32) && !elems) { st_recv = RFX_E_LIMIT; ctx->last_error = "rfx_dev_sharded_count (k-mer units): a shard of 2^32 instances or more"; }
     {
         int64_t bad[1] = {st_recv != RFX_OK ? 1 : 0};
         RFX_TRY(rfx_comm_all_reduce_i64(c, bad, 1, 1));
@@ -310,6 +319,8 @@ static int sharded_count_kmers(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_word
     ctx->timing.clear();
     if (!wide) {
         st_cnt = rfx::count_filter(ctx, nullptr, recv.as<uint64_t>(), n_in, min_cov, max_cov, twin, nullptr, 0, d_out_keys, (int32_t *)d_out_counts, cap, &m, &distinct);
+    } else if (elems) {                                       // straight from the AoS elements, as count_filter_w2 does for W = 2
+        st_cnt = rfx::count_filter_w2(ctx, recv.as<uint64_t>(), n_in, k, min_cov, max_cov, d_out_keys, (int64_t *)d_out_counts, cap, &m, &distinct);
     } else {
         auto cnt = [&]() -> int {
             RFX_HIP(soa.alloc((size_t)std::max<int64_t>(1, n_in) * W * 8, ctx->stream));
@@ -345,12 +356,13 @@ int rfx_dev_sharded_count(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_words, co
     const bool wide = k > 32;
     if (wide ? (k > 63) : (k < 21 || k > 31)) {
         // outside the record path the k-mer instances themselves travel (one-word k-mers up to k = 31, the counter's three- and
-        // four-word k-mers up to k = 125); k a multiple of 32 is no k of the reference's counters either
-        if (d_read_len) { ctx->last_error = "ragged reads: k = 21..31 and 33..63 only on the sharded device path"; return RFX_E_ARG; }
+        // four-word k-mers up to k = 125, bucketed by owner and counted by the element path); k a multiple of 32 is no k of the
+        // reference's counters either
         if (k < 3 || k > 125 || k % 32 == 0) { ctx->last_error = "rfx_dev_sharded_count: k = 3..125, not a multiple of 32"; return RFX_E_ARG; }
+        if (d_read_len && k < 65) { ctx->last_error = "ragged reads: k = 21..31 and 33..125 only on the sharded device path"; return RFX_E_ARG; }
         RFX_HIP(hipSetDevice(ctx->device));
         return sharded_count_kmers(ctx, c, d_words, n_reads, words_per_read, read_len, k, front_clip, end_clip, min_cov, max_cov, twin,
-                                   d_out_keys, d_out_counts, cap, out_n, out_totals);
+                                   d_out_keys, d_out_counts, cap, out_n, out_totals, d_read_len);
     }
     const int world = c->world, me = c->rank;
     int G = generations;
@@ -653,17 +665,19 @@ int rfx_dev_gather_shards(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_keys, con
 
 // The whole resident path on several GPUs from ASCII reads in host memory: every rank uploads and encodes ITS reads
 // (any lengths), rfx_dev_sharded_count, the shards gathered on rank 0, the driver there (rfx_dev_assemble) -> the
-// contig text on rank 0 (*out_len = 0 elsewhere).  k = 21..31; k = 33..63 through the k > 31 counter (two-word keys, int64
-// counts), KmerBinarizer + the from-counts filter on every rank's shard and the k > 31 driver, as rfx_assemble_reads does on one
-// GPU.  Collective.  out_totals[3] as rfx_dev_sharded_count.
+// contig text on rank 0 (*out_len = 0 elsewhere).  k = 21..31; k = 33..124 (not a multiple of 32) through the k > 31 counter
+// (k/32+1-word keys, int64 counts), KmerBinarizer + the from-counts filter on every rank's shard and the k > 31 driver, as
+// rfx_assemble_reads does on one GPU (k = 125 would need five-word driver keys: rfx_dev_sharded_assemble takes four).
+// Collective.  out_totals[3] as rfx_dev_sharded_count.
 int rfx_sharded_assemble_reads(rfx_ctx *ctx, rfx_comm *c, const uint8_t *bases, const int64_t *read_off, int64_t n_reads,
                                const rfx_params *prm, int generations, int64_t gather_below, char *out, int64_t cap, int64_t *out_len,
                                int64_t *out_contigs, int64_t *trace, int64_t trace_cap, int64_t *n_trace, int64_t *out_totals) try {
     if (!ctx || !c || c->ctx != ctx || !read_off || !prm || !out_len || n_reads < 0) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     const int k = prm->k;
-    const bool wide = k > 32;                                         // (k > 63 is refused by the count below, on every rank)
-    const int kw = wide ? 2 : 1, cb = wide ? 8 : 4;                   // counter key words and count bytes
+    const bool wide = k > 32;                                         // (other k are refused by the count below, on every rank)
+    if (k > 124) { ctx->last_error = "rfx_sharded_assemble_reads: k = 21..31 or 33..124"; return RFX_E_ARG; }
+    const int kw = wide ? k / 32 + 1 : 1, cb = wide ? 8 : 4;          // counter key words and count bytes
     const int64_t nb = n_reads ? read_off[n_reads] - read_off[0] : 0;
     int64_t maxlen = 1;
     for (int64_t r = 0; r < n_reads; r++) maxlen = std::max(maxlen, read_off[r + 1] - read_off[r]);

@@ -358,6 +358,16 @@ int count_wide2_reads(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, in
                       int64_t *out_distinct, const uint32_t *d_read_len = nullptr, int ec = 0, int64_t n_inst = -1);
 int bucket_wide_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
                          int n_owners, void *d_out, int64_t cap_elems, int64_t *d_owner_off, int64_t *h_owner_off);
+// k = 65..127 (W = 3, 4; rfx_kmer.hip): AoS W-word elements -> distinct keys and counts, unordered; the same from packed
+// reads (uniform, or d_read_len with nk = the longest read's k-mers and n_inst their instances); the k-mers of packed reads
+// grouped by owning rank (AoS elements, offsets as bucket_wide_by_owner)
+int count_wide_elems(rfx_ctx *ctx, const void *d_elems, int64_t n, int k, int min_cov, int max_cov, uint64_t *d_out_keys,
+                     int64_t *d_out_counts, int64_t cap, int64_t *out_n, int64_t *out_distinct);
+int count_wide_n_from_reads(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
+                            int min_cov, int max_cov, uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap, int64_t *out_n,
+                            int64_t *out_distinct, const uint32_t *d_read_len = nullptr, int ec = 0, int64_t n_inst = -1);
+int bucket_wide_n_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
+                           const uint32_t *d_read_len, int ec, int n_owners, void *d_out, int64_t *d_owner_off, int64_t *h_owner_off);
 int synth_genome(rfx_ctx *ctx, uint64_t seed, int64_t genome_len, uint64_t *d_genome);
 int synth_reads(rfx_ctx *ctx, uint64_t seed, const uint64_t *d_genome, int64_t genome_len,
                 int64_t first_read, int64_t n_reads, int read_len, uint32_t err, int words_per_read,
@@ -371,6 +381,8 @@ int kmer_counts_per_read_w(rfx_ctx *ctx, const int64_t *d_read_off, int64_t n_re
 int extract_w(rfx_ctx *ctx, const uint64_t *d_words, int wpr, const uint64_t *d_kmer_off, int64_t nk_uniform,
               int64_t n_reads, int k, int fc, uint64_t *d_soa, int64_t N, int aos = 0);
 bool wide_fast_path(int k);
+bool wide_elem_path(int k);      // W = 2..4 (k = 33..127, k % 32 != 0): the bucketed count on the device
+// (the survivors of W = 2..4 ordered; N AoS elements of W = 2..4 words counted, filtered and ordered)
 int order_wide2(rfx_ctx *ctx, uint64_t *d_out_keys, int64_t *d_out_counts, int64_t m, int k);
 int count_filter_w2(rfx_ctx *ctx, const uint64_t *d_elems, int64_t N, int k, int min_cov, int max_cov,
                     uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap, int64_t *out_n, int64_t *out_distinct);

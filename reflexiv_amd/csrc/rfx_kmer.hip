@@ -2307,12 +2307,25 @@ __device__ __forceinline__ uint64_t wide_hash(uint64_t hi, uint64_t lo) {
 // local digits, as on the k <= 31 path)
 // MODE 0: super-k-mer records (digit from the header), 1: two-word k-mers (hash of both words),
 // 2: (k-mer, partial count) pairs (kmer_hash of the key; with lv.n_owners > 0 the digit is the owner)
+// MODE 4, 5: three- and four-word k-mers of k = 65..127 (24- and 32-byte elements {word0, ..., word W-1}, the counter's
+// layout; hash of all words)
+template <int W> struct KmerW { uint64_t w[W]; };
+template <int W>
+__device__ __forceinline__ uint64_t wide_hash_n(const KmerW<W> &r) {
+    uint64_t x = r.w[0];
+#pragma unroll
+    for (int i = 1; i < W; i++) { x ^= r.w[i] * 0x9E3779B97F4A7C15ULL; x *= 0xD6E8FEB86659FD93ULL; x ^= x >> 32; }
+    return x;
+}
 template <int MODE> struct LevelElem { using T = Rec; };
 template <> struct LevelElem<3> { using T = WRec; };          // MODE 3: super-k-mer records of the k = 33..63 path
+template <> struct LevelElem<4> { using T = KmerW<3>; };
+template <> struct LevelElem<5> { using T = KmerW<4>; };
 template <int MODE, class E>
 __device__ __forceinline__ unsigned level_digit(const E &r, int used, const Level &lv) {
     const int bits = lv.bits;
-    if constexpr (MODE == 3) return rec_digit((uint32_t)r.hd, used, bits);
+    if constexpr (MODE >= 4) return bits ? (unsigned)(((wide_hash_n(r) << OWNER_BITS) << used) >> (64 - bits)) : 0u;
+    else if constexpr (MODE == 3) return rec_digit((uint32_t)r.hd, used, bits);
     else if constexpr (MODE == 1) return bits ? (unsigned)(((wide_hash(r.w0, r.w1) << OWNER_BITS) << used) >> (64 - bits)) : 0u;
     else if constexpr (MODE == 2) {
         if (lv.n_owners > 0) return (unsigned)__umul64hi(kmer_hash(r.w0), (uint64_t)lv.n_owners);
@@ -2901,6 +2914,347 @@ __global__ __launch_bounds__(W2T) void k_w2_scatter(WideSrc s, Level lv, const u
 #undef buf
 #undef tail
 #undef head
+}
+
+// ---- k = 65..127: three- and four-word k-mers (W = 3, 4; k % 32 != 0) through the element path of k = 33..63.
+// Level 1 rolls the W-word k-mer and its reverse complement through a thread's 16 windows of one read (uniform or per-read
+// lengths: the counter64 skip rule, nk_of_wide), 24- or 32-byte elements leave through write-combining rings; the record
+// levels (MODE 4, 5) and the LDS-table leaves (k_leaf_count_wn) follow.  The k <= 63 kernels are separate and unchanged.
+struct WideSrcN {
+    const uint64_t *words;
+    const uint32_t *len_arr;       // per-read lengths, or nullptr: every read emits nk windows
+    int64_t n_reads, nk, segs, total;
+    int wpr, k, fc, ec;
+};
+constexpr int WNB = 8;             // ring slots per bin at W = 3, 4 (512 bins x 8 x 32 B + cursors: 136 KiB of LDS)
+
+template <int W> struct WNState { uint64_t f[W], r[W], nxt; int v, j; };
+
+template <int W>
+__device__ __forceinline__ void wn_init(const WideSrcN &s, int64_t g, WNState<W> &st) {
+    st.v = 0; st.j = 0;
+    if (g >= s.total) return;
+    const int64_t r = g / s.segs;
+    const int p0 = (int)(g - r * s.segs) * W2SEG;
+    // (a read longer than the longest one announced emits what the segments cover: no base past nk's windows is read)
+    int64_t nkr = s.len_arr ? nk_of_wide((int64_t)s.len_arr[r], s.k, s.fc, s.ec) : s.nk;
+    nkr = nkr < s.nk ? nkr : s.nk;
+    if (nkr <= p0) return;
+    const int v = nkr - p0 > W2SEG ? W2SEG : (int)(nkr - p0);
+    const int res = s.k & 31;
+    const uint64_t *w = s.words + r * s.wpr;
+    const int b = s.fc + p0;
+    // counter layout (rfx_wide.hip k_extract_w): words 0..W-2 hold 32 bases, the last one `res` bases right-aligned; the
+    // reverse complement is laid out the same way
+#pragma unroll
+    for (int i = 0; i < W - 1; i++) {
+        st.f[i] = kmer_at(w, b + 32 * i, 32);
+        st.r[i] = revcomp(kmer_at(w, b + s.k - 32 * (i + 1), 32), 32);
+    }
+    st.f[W - 1] = kmer_at(w, b + 32 * (W - 1), res);
+    st.r[W - 1] = revcomp(kmer_at(w, b, res), res);
+    st.nxt = v > 1 ? kmer_at(w, b + s.k, v - 1) : 0;     // the v - 1 bases that enter, right-aligned
+    st.v = v;
+}
+// canonical element of the current window (compareLongArrayBlocks: word-wise unsigned, ties -> forward), then one base on
+template <int W>
+__device__ __forceinline__ KmerW<W> wn_step(WNState<W> &st, int res, uint64_t mres) {
+    bool use_f = st.f[W - 1] <= st.r[W - 1];
+#pragma unroll
+    for (int i = W - 2; i >= 0; i--) use_f = st.f[i] != st.r[i] ? st.f[i] < st.r[i] : use_f;
+    KmerW<W> e;
+#pragma unroll
+    for (int i = 0; i < W; i++) e.w[i] = use_f ? st.f[i] : st.r[i];
+    if (st.j + 1 < st.v) {
+        const uint64_t nb = (st.nxt >> (2 * (st.v - 2 - st.j))) & 3;
+        // forward: the base string one base to the left, nb in at the end
+        const uint64_t cf = st.f[W - 1] >> (2 * (res - 1));
+#pragma unroll
+        for (int i = 0; i < W - 2; i++) st.f[i] = (st.f[i] << 2) | (st.f[i + 1] >> 62);
+        st.f[W - 2] = (st.f[W - 2] << 2) | cf;
+        st.f[W - 1] = ((st.f[W - 1] << 2) | nb) & mres;
+        // reverse complement: one base to the right, the complement of nb in at the front
+        st.r[W - 1] = (st.r[W - 1] >> 2) | ((st.r[W - 2] & 3) << (2 * (res - 1)));
+#pragma unroll
+        for (int i = W - 2; i >= 1; i--) st.r[i] = (st.r[i] >> 2) | ((st.r[i - 1] & 3) << 62);
+        st.r[0] = (st.r[0] >> 2) | ((nb ^ 3) << 62);
+    }
+    st.j++;
+    return e;
+}
+
+template <int W>
+__device__ __forceinline__ unsigned wn_level1_digit(const KmerW<W> &e, const Level &lv) {
+    if (lv.n_owners > 0) return (unsigned)__umul64hi(wide_hash_n(e), (uint64_t)lv.n_owners);
+    return level_digit<W + 1>(e, 0, lv);          // (MODE 4, 5)
+}
+
+template <int W>
+__global__ __launch_bounds__(W2T) void k_wn_hist(WideSrcN s, Level lv, uint64_t *__restrict__ blockhist) {
+    __shared__ uint32_t h[1 << MAX_BITS];
+    const int nb = lv.n_owners > 0 ? lv.n_owners : (1 << lv.bits);
+    for (int i = threadIdx.x; i < nb; i += W2T) h[i] = 0;
+    __syncthreads();
+    const int res = s.k & 31;
+    const uint64_t mres = low_mask(res);
+    for (int64_t g = (int64_t)blockIdx.x * W2T + threadIdx.x; g < s.total; g += (int64_t)gridDim.x * W2T) {
+        WNState<W> st;
+        wn_init<W>(s, g, st);
+        while (st.j < st.v) atomicAdd(&h[wn_level1_digit<W>(wn_step<W>(st, res, mres), lv)], 1u);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nb; i += W2T) blockhist[(int64_t)i * gridDim.x + blockIdx.x] = h[i];
+}
+
+// (as k_w2_scatter, with WNB ring slots per bin)
+template <int W>
+__global__ __launch_bounds__(W2T) void k_wn_scatter(WideSrcN s, Level lv, const uint64_t *__restrict__ scanned,
+                                                    KmerW<W> *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char wn_smem[];
+    const int nb = lv.n_owners > 0 ? lv.n_owners : (1 << lv.bits);
+    KmerW<W> *buf = (KmerW<W> *)wn_smem;
+    unsigned long long *tail = (unsigned long long *)(wn_smem + (size_t)nb * WNB * sizeof(KmerW<W>));
+    unsigned long long *head = tail + nb;
+    for (int i = threadIdx.x; i < nb; i += W2T) tail[i] = head[i] = scanned[(int64_t)i * gridDim.x + blockIdx.x];
+    __syncthreads();
+    const int res = s.k & 31;
+    const uint64_t mres = low_mask(res);
+    const int64_t stride = (int64_t)gridDim.x * W2T;
+    for (int64_t gb = (int64_t)blockIdx.x * W2T; gb < s.total; gb += stride) {
+        WNState<W> st;
+        wn_init<W>(s, gb + threadIdx.x, st);
+        for (int blk = 0; blk < W2SEG / W2_STEPS; blk++) {
+#pragma unroll
+            for (int q = 0; q < W2_STEPS; q++) {
+                if (st.j < st.v) {
+                    const KmerW<W> e = wn_step<W>(st, res, mres);
+                    const unsigned d = wn_level1_digit<W>(e, lv);
+                    const unsigned long long pos = atomicAdd(&tail[d], 1ULL);
+                    if (pos - head[d] < (unsigned long long)WNB) buf[(size_t)d * WNB + (pos & (WNB - 1))] = e;
+                    else out[pos] = e;
+                }
+            }
+            __syncthreads();
+            const bool final = gb + stride >= s.total && blk == W2SEG / W2_STEPS - 1;
+            for (int d = threadIdx.x / WNB; d < nb; d += W2T / WNB) {
+                const int j = threadIdx.x % WNB;
+                const unsigned long long h = head[d], t = tail[d];
+                unsigned long long e, nh;
+                if (t - h > (unsigned long long)WNB) { e = h + WNB; nh = t; }
+                else {
+                    e = final ? t : (t & ~(unsigned long long)(W2A - 1));
+                    if (e < h) e = h;
+                    nh = e;
+                }
+                const unsigned long long g = h + j;
+                if (g < e) out[g] = buf[(size_t)d * WNB + (g & (WNB - 1))];
+                if (j == 0) head[d] = nh;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// ---- leaves of k = 65..127: an LDS hash table with W key planes (4096 slots: 112 KiB of keys and counts at W = 3, 144 KiB
+// at W = 4; one 1024-thread workgroup per CU, as k_leaf_count_wide).
+// Claiming a slot.  The two-word leaf claims key words one by one against EMPTY = all ones, which is safe there only because
+// no canonical k <= 63 k-mer has an all-ones word 0 or last word.  Here a middle word holds 32 bases (32 T's are all ones), and
+// from k = 64 on so can word 0 (T^32 ... A^32 is its own reverse complement's equal in word 0).  So only the LAST word is
+// compared against EMPTY: it holds k % 32 <= 31 bases, its top two bits are always zero, and no key's last word is all ones.
+//   1. CAS of the last word against EMPTY.  The one lane that gets EMPTY back owns the slot: it writes words 0..W-2 and then
+//      PUBLISHES them with its count add (release; the count of a claimed slot is 0 until then, >= 1 after).
+//   2. A lane that gets its own last word back reads the count (acquire).  0: the owner has not published yet -- try the same
+//      slot again (the owner finishes in the same straight-line stretch of its own loop iteration, so this never waits on a
+//      lane of its own wave that cannot run).  Else it compares words 0..W-2: all equal -> count add, done.
+//   3. Any other outcome: the next slot of the probe sequence.
+// A slot's key words are written once, by its owner, before anyone compares them; two keys can never share a slot.  (A wait
+// that outlasts WSPIN tries -- a count wrapped to 0 by 2^32 instances of one key -- is treated as an overflow: the leaf splits,
+// and a key that still cannot settle ends in RFX_E_LIMIT, never in a hang.)
+constexpr int WSPIN = 1 << 16;
+template <int W>
+__device__ __forceinline__ uint32_t leaf_hash_n(const KmerW<W> &e) {
+    uint64_t x = e.w[0];
+#pragma unroll
+    for (int i = 1; i < W; i++) x = ((x ^ (x >> 31)) * 0xBF58476D1CE4E5B9ULL) ^ e.w[i];
+    x = (x ^ (x >> 30)) * 0x94D049BB133111EBULL;
+    return (uint32_t)(x >> 32);
+}
+
+template <int W>
+__global__ __launch_bounds__(WLT) void k_leaf_count_wn(const KmerW<W> *__restrict__ elems, const uint64_t *__restrict__ leaf_off,
+                                                      const uint64_t *__restrict__ leaf_end, int64_t nleaf, int min_cov, int max_cov,
+                                                      uint64_t *__restrict__ out_keys, int64_t *__restrict__ out_counts,
+                                                      unsigned long long cap, CountOut *__restrict__ co, uint32_t presplit) {
+    __shared__ unsigned long long tk[W][WCAP];           // a plane per key word; tk[W - 1] is the claim word
+    __shared__ uint32_t tcnt[WCAP];
+    __shared__ unsigned long long obk[WOBUF * W];
+    __shared__ uint32_t obc[WOBUF];
+    __shared__ uint32_t stackS[LSTACK], stacks[LSTACK];
+    __shared__ int sp;
+    __shared__ uint32_t overflow, ob_n, ob_lim, ps_eff;
+    __shared__ unsigned long long g_emit;
+    uint32_t my_distinct = 0;
+    unsigned long long my_passes = 0, my_overflows = 0;
+    const int lane_ = threadIdx.x & 63;
+    const int64_t l0 = (int64_t)(((unsigned long long)blockIdx.x * (unsigned long long)nleaf) / gridDim.x);
+    const int64_t l1 = (int64_t)(((unsigned long long)(blockIdx.x + 1) * (unsigned long long)nleaf) / gridDim.x);
+    if (l0 >= l1) return;
+    for (int i = threadIdx.x; i < WCAP; i += WLT) { tcnt[i] = 0; tk[W - 1][i] = EMPTY; }
+    if (threadIdx.x == 0) {
+        ob_n = 0; ob_lim = 0xffffffffu; overflow = 0; sp = 0;
+        ps_eff = presplit ? presplit : 0xffffffffu;
+    }
+    __syncthreads();
+
+    auto flush = [&]() {
+        __syncthreads();
+        const uint32_t cntv = ob_n < ob_lim ? ob_n : ob_lim;
+        if (ob_n == 0) return;
+        if (threadIdx.x == 0 && cntv) g_emit = atomicAdd(&co->n_out, (unsigned long long)cntv);
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < cntv * W; i += WLT) {
+            const unsigned long long pos = g_emit + i / W;
+            if (pos < cap) out_keys[g_emit * W + i] = obk[i];
+        }
+        for (uint32_t i = threadIdx.x; i < cntv; i += WLT) {
+            const unsigned long long pos = g_emit + i;
+            if (pos < cap) out_counts[pos] = (int64_t)obc[i];
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) { ob_n = 0; ob_lim = 0xffffffffu; }
+        __syncthreads();
+    };
+
+    for (int64_t leaf = l0; leaf < l1; leaf++) {
+        const uint64_t begin = leaf_off[leaf], end = leaf_end[leaf];
+        uint32_t S = 1, s = 0;
+        // a leaf with many elements will not fit one table: start it in 2, 4, ... hash-selected parts
+        if (end - begin > (uint64_t)ps_eff) {
+            while ((end - begin) > (uint64_t)ps_eff * S && S < 16) S *= 2;
+            if (S > 1) {
+                __syncthreads();
+                if (threadIdx.x == 0) for (uint32_t q = S - 1; q >= 1; q--) { stackS[sp] = S; stacks[sp] = q; sp++; }
+                __syncthreads();
+            }
+        }
+        while (begin != end) {
+            // one pass: the keys selected by (S, s) go into the table (double hashing, as k_leaf_count_wide; claims above)
+            for (uint64_t i = begin + threadIdx.x; i < end; i += WLT) {
+                if (__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
+                const KmerW<W> e = elems[i];
+                const uint32_t g = leaf_hash_n<W>(e);
+                if (((g >> 4) & ((S - 1u) & 0xffffu)) != s) continue;          // (one part: mask 0, s = 0)
+                uint32_t slot = wide_slot(g);
+                const uint32_t step = wide_step(g);
+                int probe = 0, spin = 0;
+#pragma nounroll
+                for (;;) {
+                    const unsigned long long p = atomicCAS(&tk[W - 1][slot], EMPTY, (unsigned long long)e.w[W - 1]);
+                    if (p == EMPTY) {
+#pragma unroll
+                        for (int j = 0; j < W - 1; j++) tk[j][slot] = e.w[j];
+                        __hip_atomic_fetch_add(&tcnt[slot], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        break;
+                    }
+                    if (p == e.w[W - 1]) {
+                        if (__hip_atomic_load(&tcnt[slot], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) {
+                            if (++spin >= WSPIN) { overflow = 1; break; }
+                            continue;                                  // claimed, not yet published
+                        }
+                        bool eq = true;
+#pragma unroll
+                        for (int j = 0; j < W - 1; j++) eq = eq && tk[j][slot] == e.w[j];
+                        if (eq) { atomicAdd(&tcnt[slot], 1u); break; }
+                    }
+                    if (++probe >= LPROBE) { overflow = 1; break; }
+                    slot = wide_next(slot, step);
+                }
+            }
+            __syncthreads();
+            const bool ov = overflow != 0;
+            if (threadIdx.x == 0) my_passes++;
+            if (!ov) {
+                // (the threshold moves before the sweep, whose closing barrier stands between this store and the next leaf's read)
+                if (threadIdx.x == 0 && S == 1 && end - begin > (uint64_t)ps_eff * 3 / 4 && ps_eff < (1u << 24)) ps_eff += ps_eff / 64 + 1;
+                // sweep: survivors -> LDS buffer (one add per wave), slots reset
+                for (int base = 0; base < WCAP; base += WLT) {
+                    const int slot = base + threadIdx.x;
+                    const uint32_t c = tcnt[slot];
+                    my_distinct += c != 0;
+                    bool keep = c != 0;                              // counter64 filters :197-205
+                    if (min_cov > 1 && c < (uint32_t)min_cov) keep = false;
+                    if (max_cov < 10000000 && c > (uint32_t)max_cov) keep = false;
+                    const uint64_t km = __ballot(keep);
+                    if (km) {
+                        const uint32_t cntw = (uint32_t)__popcll(km);
+                        const int leader = __ffsll((unsigned long long)km) - 1;
+                        const uint32_t r = (uint32_t)__popcll(km & ((1ULL << lane_) - 1));
+                        uint32_t b0 = 0;
+                        if (lane_ == leader) b0 = atomicAdd(&ob_n, cntw);
+                        b0 = (uint32_t)__builtin_amdgcn_readlane((int)b0, leader);
+                        if (b0 + cntw <= (uint32_t)WOBUF) {
+                            if (keep) {
+#pragma unroll
+                                for (int j = 0; j < W; j++) obk[(b0 + r) * W + j] = tk[j][slot];
+                                obc[b0 + r] = c;
+                            }
+                        } else {
+                            uint32_t glo = 0, ghi = 0;
+                            if (lane_ == leader) {
+                                atomicMin(&ob_lim, b0);
+                                const unsigned long long gg = atomicAdd(&co->n_out, (unsigned long long)cntw);
+                                glo = (uint32_t)gg; ghi = (uint32_t)(gg >> 32);
+                            }
+                            glo = (uint32_t)__builtin_amdgcn_readlane((int)glo, leader);
+                            ghi = (uint32_t)__builtin_amdgcn_readlane((int)ghi, leader);
+                            const unsigned long long pos = (((unsigned long long)ghi << 32) | glo) + r;
+                            if (keep && pos < cap) {
+#pragma unroll
+                                for (int j = 0; j < W; j++) out_keys[W * pos + j] = tk[j][slot];
+                                out_counts[pos] = (int64_t)c;
+                            }
+                        }
+                    }
+                    tcnt[slot] = 0;
+                    if (c) tk[W - 1][slot] = EMPTY;
+                }
+                __syncthreads();
+                const uint32_t raw = ob_n, lim = ob_lim;
+                if (raw >= (uint32_t)WOBUF / 2 || lim != 0xffffffffu) flush();
+                if (S == 1) break;
+            } else {
+                for (int i = threadIdx.x; i < WCAP; i += WLT) { tcnt[i] = 0; tk[W - 1][i] = EMPTY; }
+                __syncthreads();
+                if (threadIdx.x == 0) {
+                    my_overflows++;
+                    overflow = 0;
+                    if ((end - begin) / S < 2ull * ps_eff && ps_eff > 64) ps_eff -= ps_eff / 8;
+                    if (sp + 2 <= LSTACK && S < (1u << 16)) {
+                        stackS[sp] = 2 * S; stacks[sp] = s + S; sp++;
+                        stackS[sp] = 2 * S; stacks[sp] = s;     sp++;
+                    } else {
+                        atomicAdd(&co->n_failed, 1ULL);
+                    }
+                }
+                __syncthreads();
+            }
+            if (sp == 0) break;
+            S = stackS[sp - 1]; s = stacks[sp - 1];
+            __syncthreads();
+            if (threadIdx.x == 0) sp--;
+        }
+    }
+    flush();
+    {
+        uint32_t d = my_distinct;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+        if (lane_ == 0 && d) atomicAdd(&co->n_distinct, (unsigned long long)d);
+    }
+    if (threadIdx.x == 0) {
+        atomicAdd(&co->n_passes, my_passes);
+        if (my_overflows) atomicAdd(&co->n_overflow, my_overflows);
+    }
 }
 
 // ------------------------------------------------------------ synthetic reads
@@ -3508,7 +3862,7 @@ static int partition_record_levels(rfx_ctx *ctx, const typename LevelElem<MODE>:
         const int64_t nchild = nseg << lv.bits;
         // one unpartitioned array (what a rank received): the level in one sweep, regions from a sample, when the caller can take
         // segment ends (records_resweep)
-        if (nseg == 1 && seg_end_buf && seg_end_out && !seg_end_cur) {
+        if constexpr (MODE < 4) if (nseg == 1 && seg_end_buf && seg_end_out && !seg_end_cur) {      // (not for MODE 4, 5)
             bool swept = false;
             const Rec *dst_s = nullptr;
             RFX_HIP(seg_next->alloc((size_t)(nchild + 1) * 8, ctx->stream));
@@ -3559,7 +3913,7 @@ static int partition_record_levels(rfx_ctx *ctx, const typename LevelElem<MODE>:
         {
             ScopedTimer t(ctx, pn);
             const bool wc = lv.bits >= 4;
-            if (wc && MODE == 3) {                   // 32-byte records: 8 slots per bin fill the LDS at 512 bins
+            if (wc && (MODE == 3 || MODE >= 4)) {    // 32-byte records (24, 32-byte k-mers): 8 slots per bin fill the LDS at 512 bins
                 if (lv.bits > 9) {                   // 1024 bins: 4 slots each (64-byte lines)
                     const size_t lds = (size_t)nb * (4 * sizeof(Rec) + 16);
                     RFX_HIP(hipFuncSetAttribute((const void *)k_rec_scatter_wc<4, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -4500,6 +4854,182 @@ int count_wide2_reads(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, in
     RFX_TRY(partition_record_levels<1>(ctx, dst, n, 0, bits, 1, lv.bits, &seg_cur, &seg_next, &nseg, &cur));
     return finish_wide2(ctx, cur, (const uint64_t *)seg_cur->as<uint64_t>(), nseg, min_cov, max_cov, d_out_keys, d_out_counts,
                         cap, out_n, out_distinct);
+}
+
+// ---- k = 65..127 (W = 3, 4): the element path of k = 33..63 on W-word keys
+
+template <int W>
+static int finish_wide_n(rfx_ctx *ctx, const KmerW<W> *cur, const uint64_t *d_leaf_off, int64_t nseg, int min_cov, int max_cov,
+                         uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap, int64_t *out_n, int64_t *out_distinct) {
+    DevBuf co_buf;
+    RFX_HIP(co_buf.alloc(sizeof(CountOut), ctx->stream));
+    RFX_HIP(hipMemsetAsync(co_buf.p, 0, sizeof(CountOut), ctx->stream));
+    {
+        ScopedTimer t(ctx, "leaf");
+        const int64_t grid = std::min<int64_t>(nseg, (int64_t)ctx->num_cu);          // one workgroup per CU
+        // (elements one table takes before a leaf starts in parts: none by default -- the levels aim at WIDE_N_TARGET)
+        hipLaunchKernelGGL(k_leaf_count_wn<W>, dim3((unsigned)grid), dim3(WLT), 0, ctx->stream, cur, d_leaf_off, d_leaf_off + 1, nseg,
+                           min_cov, max_cov, d_out_keys, d_out_counts, (unsigned long long)cap, co_buf.as<CountOut>(),
+                           (uint32_t)(getenv("RFX_WIDE_PRESPLIT") ? atoi(getenv("RFX_WIDE_PRESPLIT")) : 0));
+        RFX_HIP(hipGetLastError());
+    }
+    CountOut co{};
+    RFX_HIP(hipMemcpyAsync(&co, co_buf.p, sizeof co, hipMemcpyDeviceToHost, ctx->stream));
+    RFX_TRY(sync_checked(ctx));
+    if (getenv("RFX_TRACE"))
+        fprintf(stderr, "wide leaves (W = %d): %lld buckets, %llu table passes, %llu overflowed\n", W, (long long)nseg, co.n_passes, co.n_overflow);
+    ctx->timing["stat_leaves"].launches += nseg; ctx->timing["stat_passes"].launches += (int64_t)co.n_passes;
+    ctx->timing["stat_overflows"].launches += (int64_t)co.n_overflow;
+    if (out_n) *out_n = (int64_t)co.n_out;
+    if (out_distinct) *out_distinct = (int64_t)co.n_distinct;
+    if (co.n_failed) { ctx->last_error = "leaf split depth exhausted"; return RFX_E_LIMIT; }
+    if ((int64_t)co.n_out > cap) return RFX_E_CAP;
+    return RFX_OK;
+}
+
+constexpr double WIDE_N_TARGET = 8192.0;            // elements per leaf: a 4096-slot table; overflowing leaves split
+
+// level 1 from packed reads: W-word elements grouped by `lv` (radix digit or owner) in d_dst, group offsets in d_seg_off[nb + 1]
+template <int W>
+static int wide_level1_n(rfx_ctx *ctx, const WideSrcN &ws, const Level &lv, KmerW<W> *d_dst, uint64_t *d_seg_off) {
+    const int nb = lv.n_owners > 0 ? lv.n_owners : (1 << lv.bits);
+    const unsigned G = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(ws.total, W2T), (int64_t)ctx->num_cu));
+    DevBuf bh, scanned;
+    RFX_HIP(bh.alloc((size_t)nb * G * 8, ctx->stream));
+    RFX_HIP(scanned.alloc(((size_t)nb * G + 1) * 8, ctx->stream));
+    {
+        ScopedTimer t(ctx, "hist1");
+        hipLaunchKernelGGL(k_wn_hist<W>, dim3(G), dim3(W2T), 0, ctx->stream, ws, lv, bh.as<uint64_t>());
+        RFX_HIP(hipGetLastError());
+    }
+    RFX_TRY(exclusive_scan_u64(ctx, bh.as<uint64_t>(), scanned.as<uint64_t>(), (int64_t)nb * G));
+    hipLaunchKernelGGL(k_bin_offsets, dim3((unsigned)ceil_div(nb + 1, 256)), dim3(256), 0, ctx->stream,
+                       (const uint64_t *)scanned.as<uint64_t>(), nb, (int64_t)G, d_seg_off);
+    RFX_HIP(hipGetLastError());
+    {
+        ScopedTimer t(ctx, "part1");
+        const size_t lds = (size_t)nb * (WNB * sizeof(KmerW<W>) + 16);
+        RFX_HIP(hipFuncSetAttribute((const void *)k_wn_scatter<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(k_wn_scatter<W>, dim3(G), dim3(W2T), lds, ctx->stream, ws, lv, (const uint64_t *)scanned.as<uint64_t>(),
+                           d_dst);
+        RFX_HIP(hipGetLastError());
+    }
+    return RFX_OK;
+}
+
+static WideSrcN wide_src_n(const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc, const uint32_t *d_read_len,
+                           int ec) {
+    WideSrcN ws{d_words, d_read_len, n_reads, nk, ceil_div(nk, W2SEG), 0, wpr, k, fc, ec};
+    ws.total = n_reads * ws.segs;
+    return ws;
+}
+
+template <int W>
+static int count_wide_n(rfx_ctx *ctx, const void *d_elems, int64_t n, int min_cov, int max_cov, uint64_t *d_out_keys,
+                        int64_t *d_out_counts, int64_t cap, int64_t *out_n, int64_t *out_distinct) {
+    StageArena stage_arena(ctx, (size_t)256 << 20);       // temporaries of this call (see StageArena)
+    std::vector<int> bits;
+    plan_levels(n, false, bits, WIDE_N_TARGET);
+    if (bits.empty()) bits.push_back(0);
+    DevBuf segA, segB;
+    uint64_t seg_init[2] = {0, (uint64_t)n};
+    RFX_HIP(segA.alloc(2 * 8, ctx->stream));
+    RFX_HIP(hipMemcpyAsync(segA.p, seg_init, 16, hipMemcpyHostToDevice, ctx->stream));
+    RFX_TRY(sync_checked(ctx));
+    DevBuf *seg_cur = &segA, *seg_next = &segB;
+    int64_t nseg = 1;
+    const KmerW<W> *cur = nullptr;
+    RFX_TRY(partition_record_levels<W + 1>(ctx, (const KmerW<W> *)d_elems, n, 1, bits, 0, 0, &seg_cur, &seg_next, &nseg, &cur));
+    return finish_wide_n<W>(ctx, cur, (const uint64_t *)seg_cur->as<uint64_t>(), nseg, min_cov, max_cov, d_out_keys, d_out_counts,
+                            cap, out_n, out_distinct);
+}
+
+// k = 65..127: n canonical W-word k-mers (AoS elements of W words) -> distinct keys with counts, unordered
+int count_wide_elems(rfx_ctx *ctx, const void *d_elems, int64_t n, int k, int min_cov, int max_cov, uint64_t *d_out_keys,
+                     int64_t *d_out_counts, int64_t cap, int64_t *out_n, int64_t *out_distinct) {
+    if (out_n) *out_n = 0;
+    if (out_distinct) *out_distinct = 0;
+    if (n <= 0) return RFX_OK;
+    const int W = k / 32 + 1;
+    if (k % 32 == 0 || (W != 3 && W != 4)) return RFX_E_ARG;
+    return W == 3 ? count_wide_n<3>(ctx, d_elems, n, min_cov, max_cov, d_out_keys, d_out_counts, cap, out_n, out_distinct)
+                  : count_wide_n<4>(ctx, d_elems, n, min_cov, max_cov, d_out_keys, d_out_counts, cap, out_n, out_distinct);
+}
+
+template <int W>
+static int count_wide_n_reads(rfx_ctx *ctx, const WideSrcN &ws, int64_t n, int min_cov, int max_cov, uint64_t *d_out_keys,
+                              int64_t *d_out_counts, int64_t cap, int64_t *out_n, int64_t *out_distinct) {
+    std::vector<int> bits;
+    plan_levels(n, true, bits, WIDE_N_TARGET);
+    if (bits[0] > 9) {                               // the level-1 rings hold 512 bins: move the excess down
+        const int extra = bits[0] - 9;
+        bits[0] = 9;
+        if (bits.size() == 1) bits.push_back(extra); else bits[1] += extra;
+        if (bits[1] > MAX_BITS) { bits.push_back(bits[1] - MAX_BITS); bits[1] = MAX_BITS; }
+    }
+    Level lv{};
+    lv.bits = bits[0];
+    const int nb = 1 << lv.bits;
+    DevBuf segA, segB;
+    RFX_HIP(segA.alloc(((size_t)nb + 1) * 8, ctx->stream));
+    KmerW<W> *dst = (KmerW<W> *)ctx->ws_get(0, (size_t)n * sizeof(KmerW<W>));
+    if (!dst) { ctx->last_error = "workspace allocation failed"; return RFX_E_HIP; }
+    RFX_TRY(wide_level1_n<W>(ctx, ws, lv, dst, segA.as<uint64_t>()));
+    if (ws.len_arr) {
+        // what level 1 wrote (a read longer than the announced longest one emits only the windows its segments cover)
+        uint64_t wrote = 0;
+        RFX_HIP(hipMemcpyAsync(&wrote, segA.as<uint64_t>() + nb, 8, hipMemcpyDeviceToHost, ctx->stream));
+        RFX_TRY(sync_checked(ctx));
+        n = (int64_t)wrote;
+    }
+    DevBuf *seg_cur = &segA, *seg_next = &segB;
+    int64_t nseg = nb;
+    const KmerW<W> *cur = nullptr;
+    RFX_TRY(partition_record_levels<W + 1>(ctx, dst, n, 0, bits, 1, lv.bits, &seg_cur, &seg_next, &nseg, &cur));
+    return finish_wide_n<W>(ctx, cur, (const uint64_t *)seg_cur->as<uint64_t>(), nseg, min_cov, max_cov, d_out_keys, d_out_counts,
+                            cap, out_n, out_distinct);
+}
+
+// k = 65..127 from packed reads, uniform (d_read_len == nullptr; n_inst unused) or ragged (nk = the longest read's k-mers, n_inst
+// = the instances of all, end_clip the clip they were counted with).  Level 1 reads the packed reads directly; unordered output.
+int count_wide_n_from_reads(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
+                            int min_cov, int max_cov, uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap, int64_t *out_n,
+                            int64_t *out_distinct, const uint32_t *d_read_len, int ec, int64_t n_inst) {
+    StageArena stage_arena(ctx, (size_t)256 << 20);       // temporaries of this call (see StageArena)
+    if (out_n) *out_n = 0;
+    if (out_distinct) *out_distinct = 0;
+    const int64_t n = d_read_len ? n_inst : nk * n_reads;
+    if (n <= 0 || nk <= 0) return RFX_OK;
+    const int W = k / 32 + 1;
+    if (k % 32 == 0 || (W != 3 && W != 4)) return RFX_E_ARG;
+    const WideSrcN ws = wide_src_n(d_words, n_reads, wpr, nk, k, fc, d_read_len, ec);
+    return W == 3 ? count_wide_n_reads<3>(ctx, ws, n, min_cov, max_cov, d_out_keys, d_out_counts, cap, out_n, out_distinct)
+                  : count_wide_n_reads<4>(ctx, ws, n, min_cov, max_cov, d_out_keys, d_out_counts, cap, out_n, out_distinct);
+}
+
+// multi-GPU support: the W-word k-mers (W = 3, 4) of packed reads (uniform, or per-read lengths with nk = the longest read's
+// k-mers) grouped by owning rank: d_out holds them as AoS W-word elements, d_owner_off[n_owners + 1] (and h_owner_off) the
+// groups' offsets.  Same kernels as the count's level 1, digit = mulhi(hash, n_owners).
+int bucket_wide_n_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
+                           const uint32_t *d_read_len, int ec, int n_owners, void *d_out, int64_t *d_owner_off, int64_t *h_owner_off) {
+    StageArena stage_arena(ctx, (size_t)256 << 20);       // temporaries of this call (see StageArena)
+    const int W = k / 32 + 1;
+    if (n_owners < 1 || n_owners > 64 || k % 32 == 0 || (W != 3 && W != 4)) return RFX_E_ARG;
+    if (nk <= 0 || n_reads <= 0) {
+        RFX_HIP(hipMemsetAsync(d_owner_off, 0, (size_t)(n_owners + 1) * 8, ctx->stream));
+        if (h_owner_off) memset(h_owner_off, 0, (size_t)(n_owners + 1) * 8);
+        return RFX_OK;
+    }
+    Level lv{};
+    lv.n_owners = n_owners;
+    const WideSrcN ws = wide_src_n(d_words, n_reads, wpr, nk, k, fc, d_read_len, ec);
+    if (W == 3) RFX_TRY(wide_level1_n<3>(ctx, ws, lv, (KmerW<3> *)d_out, reinterpret_cast<uint64_t *>(d_owner_off)));
+    else RFX_TRY(wide_level1_n<4>(ctx, ws, lv, (KmerW<4> *)d_out, reinterpret_cast<uint64_t *>(d_owner_off)));
+    if (h_owner_off) {
+        RFX_HIP(hipMemcpyAsync(h_owner_off, d_owner_off, (size_t)(n_owners + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+        RFX_TRY(sync_checked(ctx));
+    }
+    return RFX_OK;
 }
 
 int synth_genome(rfx_ctx *ctx, uint64_t seed, int64_t genome_len, uint64_t *d_genome) {

@@ -10,9 +10,10 @@
 // structure of arrays (word w of k-mer i at [w*N + i]); the C ABI speaks the reference's array of
 // W longs per k-mer.
 //
-// This round's k > 31 count is the plain exact formulation -- LSD radix sort of the W words through a
-// 32-bit permutation, equal-key run heads, scan, compaction -- not the bucketed LDS-table path of
-// k <= 31: ~70 B of workspace per instance, N < 2^32 per call.  
+// k = 33..127 (W = 2..4) count through the bucketed LDS-table path of rfx_kmer.hip (count_wide2, count_wide_elems;
+// DESIGN.md sections 8, 12); only the survivors are sorted here (order_wide).  W >= 5 (k >= 128, beyond the CLI's range)
+// keeps the plain exact formulation -- LSD radix sort of the W words through a 32-bit permutation, equal-key run heads,
+// scan, compaction: ~70 B of workspace per instance, N < 2^32 per call.  
 #include "rfx_internal.h"
 #include "rfx_device.h"
 
@@ -200,6 +201,16 @@ __global__ void k_permute_w2(const uint64_t *__restrict__ aos, const int64_t *__
     ocnt[i] = cnt[s];
 }
 
+// the same for W words
+__global__ void k_permute_wn(const uint64_t *__restrict__ aos, const int64_t *__restrict__ cnt, const uint32_t *__restrict__ idx,
+                             int64_t m, int W, uint64_t *__restrict__ oaos, int64_t *__restrict__ ocnt) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const int64_t s = idx[i];
+    for (int w = 0; w < W; w++) oaos[W * i + w] = aos[W * s + w];
+    ocnt[i] = cnt[s];
+}
+
 inline unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, ceil_div(n, 256)); }
 
 }  // namespace
@@ -262,51 +273,67 @@ bool wide_fast_path(int k) {
     return k / 32 + 1 == 2;
 }
 
-// k = 33..63: the bucketed path (hash digits, write-combining scatters, LDS-table leaves with two-word
-// keys: rfx_kmer.hip count_wide2) on N elements {word0, word1}; the survivors are then put in
-// ascending order.
+bool wide_elem_path(int k) {
+    const int W = k / 32 + 1;
+    return k > 32 && k % 32 != 0 && W <= 4;
+}
+
+// k = 33..127 (W = 2..4): the bucketed path (hash digits, write-combining scatters, LDS-table leaves with W-word keys:
+// rfx_kmer.hip count_wide2 / count_wide_elems) on N AoS elements of W words; the survivors are then put in ascending order.
+// (W = 2 keeps its limit of 2^32 - 1 instances per call; W = 3, 4 have none.)
 int count_filter_w2(rfx_ctx *ctx, const uint64_t *d_elems, int64_t N, int k, int min_cov, int max_cov,
                     uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap, int64_t *out_n, int64_t *out_distinct) {
     *out_n = 0;
     if (out_distinct) *out_distinct = 0;
     if (N <= 0) return RFX_OK;
-    if (N >= (1LL << 32)) { ctx->last_error = "k > 31 count: at most 2^32-1 instances per call"; return RFX_E_ARG; }
     int64_t m = 0;
-    const int st = count_wide2(ctx, d_elems, N, min_cov, max_cov, d_out_keys, d_out_counts, cap, &m, out_distinct);
+    int st;
+    if (wide_fast_path(k)) {
+        if (N >= (1LL << 32)) { ctx->last_error = "k > 31 count: at most 2^32-1 instances per call"; return RFX_E_ARG; }
+        st = count_wide2(ctx, d_elems, N, min_cov, max_cov, d_out_keys, d_out_counts, cap, &m, out_distinct);
+    } else {
+        st = count_wide_elems(ctx, d_elems, N, k, min_cov, max_cov, d_out_keys, d_out_counts, cap, &m, out_distinct);
+    }
     *out_n = m;
     if (st != RFX_OK) return st;
     return order_wide2(ctx, d_out_keys, d_out_counts, m, k);
 }
 
-// survivors of the fast path (unordered, AoS) -> ascending by (word0, word1)
+// survivors of the bucketed path (unordered, AoS of W = k/32+1 words, W = 2..4) -> ascending by (word0, ..., word W-1):
+// an LSD sort of the survivors' words through a 32-bit permutation
 int order_wide2(rfx_ctx *ctx, uint64_t *d_out_keys, int64_t *d_out_counts, int64_t m, int k) {
     if (m <= 1) return RFX_OK;
-    if (m >= (1LL << 32)) { ctx->last_error = "k > 31 count: too many survivors to order"; return RFX_E_LIMIT; }
-    const int res = k % 32;
+    if (m >= (1LL << 32)) { ctx->last_error = "k > 31 count: too many survivors to order (2^32 or more)"; return RFX_E_LIMIT; }
+    const int res = k % 32, W = k / 32 + 1;
     ScopedTimer t(ctx, "sort");
     DevBuf soa, idx, idx2, keys, keys2, oaos, ocnt;
-    RFX_HIP(soa.alloc((size_t)m * 16, ctx->stream));
+    RFX_HIP(soa.alloc((size_t)m * 8 * W, ctx->stream));
     RFX_HIP(idx.alloc((size_t)m * 4, ctx->stream));
     RFX_HIP(idx2.alloc((size_t)m * 4, ctx->stream));
     RFX_HIP(keys.alloc((size_t)m * 8, ctx->stream));
     RFX_HIP(keys2.alloc((size_t)m * 8, ctx->stream));
-    RFX_TRY(aos_to_soa(ctx, d_out_keys, m, 2, soa.as<uint64_t>()));
+    RFX_TRY(aos_to_soa(ctx, d_out_keys, m, W, soa.as<uint64_t>()));
     hipLaunchKernelGGL(k_iota, dim3(grid_for(m)), dim3(256), 0, ctx->stream, idx.as<uint32_t>(), m);
     RFX_HIP(hipGetLastError());
-    for (int w = 1; w >= 0; w--) {
+    for (int w = W - 1; w >= 0; w--) {
         hipLaunchKernelGGL(k_gather_u64, dim3(grid_for(m)), dim3(256), 0, ctx->stream, soa.as<uint64_t>() + (int64_t)w * m,
                            (const uint32_t *)idx.as<uint32_t>(), m, keys.as<uint64_t>());
         RFX_HIP(hipGetLastError());
-        RFX_TRY(sort_pairs(ctx, keys.as<uint64_t>(), idx.as<uint32_t>(), m, w == 1 ? 2 * res : 64, keys2.as<uint64_t>(),
+        RFX_TRY(sort_pairs(ctx, keys.as<uint64_t>(), idx.as<uint32_t>(), m, w == W - 1 ? 2 * res : 64, keys2.as<uint64_t>(),
                            idx2.as<uint32_t>()));
     }
-    RFX_HIP(oaos.alloc((size_t)m * 16, ctx->stream));
+    RFX_HIP(oaos.alloc((size_t)m * 8 * W, ctx->stream));
     RFX_HIP(ocnt.alloc((size_t)m * 8, ctx->stream));
-    hipLaunchKernelGGL(k_permute_w2, dim3(grid_for(m)), dim3(256), 0, ctx->stream, (const uint64_t *)d_out_keys,
-                       (const int64_t *)d_out_counts, (const uint32_t *)idx.as<uint32_t>(), m, oaos.as<uint64_t>(),
-                       ocnt.as<int64_t>());
+    if (W == 2)
+        hipLaunchKernelGGL(k_permute_w2, dim3(grid_for(m)), dim3(256), 0, ctx->stream, (const uint64_t *)d_out_keys,
+                           (const int64_t *)d_out_counts, (const uint32_t *)idx.as<uint32_t>(), m, oaos.as<uint64_t>(),
+                           ocnt.as<int64_t>());
+    else
+        hipLaunchKernelGGL(k_permute_wn, dim3(grid_for(m)), dim3(256), 0, ctx->stream, (const uint64_t *)d_out_keys,
+                           (const int64_t *)d_out_counts, (const uint32_t *)idx.as<uint32_t>(), m, W, oaos.as<uint64_t>(),
+                           ocnt.as<int64_t>());
     RFX_HIP(hipGetLastError());
-    RFX_HIP(hipMemcpyAsync(d_out_keys, oaos.p, (size_t)m * 16, hipMemcpyDeviceToDevice, ctx->stream));
+    RFX_HIP(hipMemcpyAsync(d_out_keys, oaos.p, (size_t)m * 8 * W, hipMemcpyDeviceToDevice, ctx->stream));
     RFX_HIP(hipMemcpyAsync(d_out_counts, ocnt.p, (size_t)m * 8, hipMemcpyDeviceToDevice, ctx->stream));
     t.stop();
     RFX_TRY(sync_checked(ctx));
@@ -320,15 +347,15 @@ int count_filter_w(rfx_ctx *ctx, uint64_t *d_soa, int64_t N, int k, int min_cov,
     *out_n = 0;
     if (out_distinct) *out_distinct = 0;
     if (N <= 0) return RFX_OK;
-    if (N >= (1LL << 32)) { ctx->last_error = "k > 31 count: at most 2^32-1 instances per call"; return RFX_E_ARG; }
     const int W = k / 32 + 1, res = k % 32;
-    if (wide_fast_path(k)) {
+    if (wide_elem_path(k)) {                          // W = 2..4: the bucketed path on AoS elements
         DevBuf elems;
-        RFX_HIP(elems.alloc((size_t)N * 16, ctx->stream));
-        RFX_TRY(soa_to_aos(ctx, d_soa, N, 2, elems.as<uint64_t>()));
+        RFX_HIP(elems.alloc((size_t)N * 8 * W, ctx->stream));
+        RFX_TRY(soa_to_aos(ctx, d_soa, N, W, elems.as<uint64_t>()));
         return count_filter_w2(ctx, elems.as<uint64_t>(), N, k, min_cov, max_cov, d_out_keys, d_out_counts, cap, out_n,
                                out_distinct);
     }
+    if (N >= (1LL << 32)) { ctx->last_error = "k > 31 count: at most 2^32-1 instances per call"; return RFX_E_ARG; }
     DevBuf idx, idx2, keys, keys2, sorted, head, pos;
     RFX_HIP(idx.alloc((size_t)N * 4, ctx->stream));
     RFX_HIP(idx2.alloc((size_t)N * 4, ctx->stream));
