@@ -16,8 +16,24 @@
  *    context's stream, for callers that keep the data resident (the Python/torch
  *    harness, the C++ driver, the multi-GPU path);
  *  - return value: RFX_OK or a negative rfx_status; never aborts, never falls back to a
- *    CPU path.  RFX_E_CAP means an output buffer was too small: *out_n (and *out_words)
- *    hold the needed size, nothing else was written;
+ *    CPU path.  A k outside the entry's range, a negative clip and words_per_read * 32 <
+ *    read_len are refused with RFX_E_ARG before anything is launched or written (*out_n and
+ *    its like included).  RFX_E_CAP means an output buffer was too small: *out_n (and
+ *    *out_words, *out_len) hold the needed size -- what to call again with.  What else was
+ *    written depends on the family (DESIGN.md "Capacity contract"):
+ *      - rfx_extract_canon[_w], rfx_count_filter[_w], every rfx_records and rfx_dyn_records
+ *        output (host and rfx_dev_*), the survivor arrays of rfx_dedup_contigs, and the sort
+ *        path of rfx_dev_count_reads_w (k >= 129) check before they copy or emit: no output
+ *        array was written;
+ *      - rfx_dev_count_reads[_ragged][_w], rfx_dev_count_kmers, rfx_dev_count_records,
+ *        rfx_dev_count_wide_records, rfx_dev_count_wide_elems, rfx_dev_merge_pairs and
+ *        rfx_dev_combine_reads (d_out_pairs; the scratch buffer is the callee's) know their
+ *        survivors only after the leaves have emitted them: the first `cap` entries of the
+ *        output arrays are unspecified, nothing at or past `cap` is written;
+ *      - text buffers (rfx_contigs_text, rfx_dev_assemble[_w], rfx_assemble_counts_w,
+ *        rfx_assemble_reads, the sharded drivers, rfx_dedup_contigs / rfx_dedup_contig_text)
+ *        are filled up to `cap`: the bytes below it are unspecified (a prefix of the text),
+ *        nothing at or past `cap` is written;
  *  - re-entrant per context; one context = one device + one HIP stream.
  *
  * Record layout = the reference's: key is the (k-1)-mer, 2 bits per
@@ -73,7 +89,7 @@ typedef struct {
 /* Flat record set.  n and the pointers are filled by the caller on input; on output the
  * callee sets n (and ext_off[n] words of ext).  cap_n / cap_words are the capacities of
  * the caller's output buffers (ext_off needs cap_n + 1 entries); on RFX_E_CAP nothing is
- * written except need_n / need_words. */
+ * written except need_n / need_words (and key_words); no array is touched. */
 typedef struct {
     int64_t   n;
     uint64_t *key;
@@ -296,8 +312,8 @@ int rfx_dev_bucket_wide_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t 
                                  int words_per_read, int read_len, int k, int front_clip, int end_clip,
                                  int n_owners, void *d_out_elems, int64_t cap_elems,
                                  int64_t *d_owner_off, int64_t *h_owner_off);
-/* (rfx_count_filter_w on host arrays, and the sharded count's receiver at k = 65..125, count three- and four-word k-mers
- * straight from such AoS elements with the same bucketed path.) */
+/* rfx_dev_count_wide_elems also takes k = 65..127 (not 96): elements of k/32+1 words, counted with the same bucketed path
+ * (as rfx_count_filter_w on host arrays and the sharded count's receiver at k = 65..125 do). */
 int rfx_dev_count_wide_elems(rfx_ctx *ctx, const void *d_elems, int64_t n_elems, int k,
                              int min_cov, int max_cov,
                              uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap,

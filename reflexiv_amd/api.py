@@ -22,6 +22,13 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _cap_error(where, need, detail) -> RfxError:
+    """the RfxError of an RFX_E_CAP return; .need = the capacity the call reported (what to retry with)"""
+    e = RfxError(RFX_E_CAP, where, detail)
+    e.need = int(need)
+    return e
+
+
 @dataclass
 class Records:
     """Flat SoA record set (include/reflexiv_hip.h rfx_records)."""
@@ -279,7 +286,7 @@ class Reflexiv:
                                           C.c_void_p(d_out_counts), C.c_int64(cap), C.byref(n), C.byref(d),
                                           C.byref(inst))
         if st == RFX_E_CAP:
-            raise RfxError(st, "rfx_dev_count_reads_w", f"needs room for {n.value} survivors, cap is {cap}")
+            raise _cap_error("rfx_dev_count_reads_w", n.value, f"needs room for {n.value} survivors, cap is {cap}")
         self._check(st, "rfx_dev_count_reads_w")
         return int(n.value), int(d.value), int(inst.value)
 
@@ -295,7 +302,7 @@ class Reflexiv:
                                                  C.c_void_p(d_out_keys), C.c_void_p(d_out_counts), C.c_int64(cap),
                                                  C.byref(n), C.byref(d), C.byref(inst))
         if st == RFX_E_CAP:
-            raise RfxError(st, "rfx_dev_count_reads_ragged_w", f"needs room for {n.value} survivors, cap is {cap}")
+            raise _cap_error("rfx_dev_count_reads_ragged_w", n.value, f"needs room for {n.value} survivors, cap is {cap}")
         self._check(st, "rfx_dev_count_reads_ragged_w")
         return int(n.value), int(d.value), int(inst.value)
 
@@ -430,7 +437,7 @@ class Reflexiv:
                                         C.c_void_p(d_out_keys), C.c_void_p(d_out_counts), C.c_int64(cap),
                                         C.byref(n), C.byref(d), C.byref(inst))
         if st == RFX_E_CAP:
-            raise RfxError(st, "rfx_dev_count_reads", f"needs room for {n.value} survivors, cap is {cap}")
+            raise _cap_error("rfx_dev_count_reads", n.value, f"needs room for {n.value} survivors, cap is {cap}")
         self._check(st, "rfx_dev_count_reads")
         return int(n.value), int(d.value), int(inst.value)
 
@@ -444,7 +451,7 @@ class Reflexiv:
                                                twin, C.c_void_p(d_out_keys), C.c_void_p(d_out_counts), C.c_int64(cap),
                                                C.byref(n), C.byref(d), C.byref(inst))
         if st == RFX_E_CAP:
-            raise RfxError(st, "rfx_dev_count_reads_ragged", f"needs room for {n.value} survivors, cap is {cap}")
+            raise _cap_error("rfx_dev_count_reads_ragged", n.value, f"needs room for {n.value} survivors, cap is {cap}")
         self._check(st, "rfx_dev_count_reads_ragged")
         return int(n.value), int(d.value), int(inst.value)
 
@@ -465,7 +472,7 @@ class Reflexiv:
                                              C.c_void_p(d_out_keys), C.c_void_p(d_out_counts), C.c_int64(cap),
                                              C.byref(m), C.byref(d))
         if st == RFX_E_CAP:
-            raise RfxError(st, "rfx_dev_count_wide_elems", f"needs room for {m.value} survivors, cap is {cap}")
+            raise _cap_error("rfx_dev_count_wide_elems", m.value, f"needs room for {m.value} survivors, cap is {cap}")
         self._check(st, "rfx_dev_count_wide_elems")
         return int(m.value), int(d.value)
 
@@ -476,7 +483,7 @@ class Reflexiv:
                                         C.c_int64(0), C.c_void_p(d_out_keys), C.c_void_p(d_out_counts),
                                         C.c_int64(cap), C.byref(m), C.byref(d))
         if st == RFX_E_CAP:
-            raise RfxError(st, "rfx_dev_count_kmers", f"needs room for {m.value} survivors, cap is {cap}")
+            raise _cap_error("rfx_dev_count_kmers", m.value, f"needs room for {m.value} survivors, cap is {cap}")
         self._check(st, "rfx_dev_count_kmers")
         return int(m.value), int(d.value)
 
@@ -513,7 +520,7 @@ class Reflexiv:
                                           C.c_void_p(d_out_keys), C.c_void_p(d_out_counts), C.c_int64(cap),
                                           C.byref(m), C.byref(d))
         if st == RFX_E_CAP:
-            raise RfxError(st, "rfx_dev_count_records", f"needs room for {m.value} survivors, cap is {cap}")
+            raise _cap_error("rfx_dev_count_records", m.value, f"needs room for {m.value} survivors, cap is {cap}")
         self._check(st, "rfx_dev_count_records")
         return int(m.value), int(d.value)
 
@@ -538,7 +545,7 @@ class Reflexiv:
                                                C.c_int64(n_instances_hint), k, min_cov, max_cov, C.c_void_p(d_out_keys),
                                                C.c_void_p(d_out_counts), C.c_int64(cap), C.byref(m), C.byref(d))
         if st == RFX_E_CAP:
-            raise RfxError(st, "rfx_dev_count_wide_records", f"needs room for {m.value} survivors, cap is {cap}")
+            raise _cap_error("rfx_dev_count_wide_records", m.value, f"needs room for {m.value} survivors, cap is {cap}")
         self._check(st, "rfx_dev_count_wide_records")
         return int(m.value), int(d.value)
 
@@ -576,7 +583,7 @@ class Reflexiv:
                                         C.c_void_p(d_out_keys), C.c_void_p(d_out_counts), C.c_int64(cap),
                                         C.byref(m), C.byref(d))
         if st == RFX_E_CAP:
-            raise RfxError(st, "rfx_dev_merge_pairs", f"needs room for {m.value} survivors, cap is {cap}")
+            raise _cap_error("rfx_dev_merge_pairs", m.value, f"needs room for {m.value} survivors, cap is {cap}")
         self._check(st, "rfx_dev_merge_pairs")
         return int(m.value), int(d.value)
 
@@ -658,6 +665,8 @@ class Reflexiv:
             if st == RFX_E_CAP and ln.value > cap:
                 buf, cap = self._text_buffer(int(ln.value))
                 continue
+            if st == RFX_E_CAP:
+                raise _cap_error("rfx_assemble_reads", ln.value, f"needs room for {ln.value} bytes of text, cap is {cap}")
             self._check(st, "rfx_assemble_reads")
             return str(memoryview(buf)[:ln.value], "ascii"), int(nc.value), [int(x) for x in trace[:ntr.value]], int(kept.value)
 

@@ -840,7 +840,7 @@ int rfx_dev_count_reads(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, 
                         int k, int front_clip, int end_clip, int min_cov, int max_cov, int twin,
                         void *d_workspace, int64_t workspace_bytes, uint64_t *d_out_keys, int32_t *d_out_counts,
                         int64_t cap, int64_t *out_n, int64_t *out_distinct, int64_t *out_instances) try {
-    if (!ctx || !d_words || n_reads < 0 || words_per_read * 32 < read_len) return RFX_E_ARG;
+    if (!ctx || !d_words || n_reads < 0 || words_per_read * 32 < read_len || front_clip < 0 || end_clip < 0) return RFX_E_ARG;
     RFX_TRY(check_k(k));
     RFX_HIP(hipSetDevice(ctx->device));
     ReadStore rs{d_words, n_reads, words_per_read, read_len, k, front_clip, end_clip};
@@ -853,7 +853,8 @@ int rfx_dev_count_reads_ragged(rfx_ctx *ctx, const uint64_t *d_words, const uint
                                int words_per_read, int max_read_len, int k, int front_clip, int end_clip, int min_cov,
                                int max_cov, int twin, uint64_t *d_out_keys, int32_t *d_out_counts, int64_t cap,
                                int64_t *out_n, int64_t *out_distinct, int64_t *out_instances) try {
-    if (!ctx || !d_words || !d_read_len || n_reads < 0 || words_per_read * 32 < max_read_len) return RFX_E_ARG;
+    if (!ctx || !d_words || !d_read_len || n_reads < 0 || words_per_read * 32 < max_read_len || front_clip < 0 || end_clip < 0)
+        return RFX_E_ARG;
     RFX_TRY(check_k(k));
     RFX_HIP(hipSetDevice(ctx->device));
     ReadStore rs{d_words, n_reads, words_per_read, max_read_len, k, front_clip, end_clip};
@@ -947,7 +948,7 @@ int rfx_dev_count_wide_elems(rfx_ctx *ctx, const void *d_elems, int64_t n_elems,
                              int64_t *out_distinct) try {
     if (!ctx || !out_n || n_elems < 0 || (n_elems > 0 && !d_elems)) return RFX_E_ARG;
     RFX_TRY(check_k_w(k));
-    if (!wide_fast_path(k)) return RFX_E_ARG;
+    if (!wide_elem_path(k)) return RFX_E_ARG;                      // k = 33..127 (two- to four-word elements)
     RFX_HIP(hipSetDevice(ctx->device));
     ctx->timing.clear();
     const int st = count_filter_w2(ctx, (const uint64_t *)d_elems, n_elems, k, min_cov, max_cov, d_out_keys, d_out_counts,
@@ -969,7 +970,8 @@ int rfx_dev_count_kmers(rfx_ctx *ctx, const uint64_t *d_kmers, int64_t n, int mi
 int rfx_dev_bucket_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int words_per_read,
                             int read_len, int k, int front_clip, int end_clip, int n_owners, uint64_t *d_out,
                             int64_t cap, int64_t *d_owner_off, int64_t *h_owner_off) try {
-    if (!ctx || !d_words || !d_owner_off) return RFX_E_ARG;
+    if (!ctx || !d_words || !d_owner_off || n_reads < 0 || words_per_read * 32 < read_len || front_clip < 0 || end_clip < 0)
+        return RFX_E_ARG;
     RFX_TRY(check_k(k));
     RFX_HIP(hipSetDevice(ctx->device));
     ReadStore rs{d_words, n_reads, words_per_read, read_len, k, front_clip, end_clip};
@@ -980,7 +982,8 @@ int rfx_dev_bucket_records_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64
                                     int read_len, int k, int front_clip, int end_clip, int n_owners,
                                     void *d_out_records, int64_t cap_records, int64_t *d_owner_off,
                                     int64_t *h_owner_off, int64_t *out_n_records) try {
-    if (!ctx || !d_words || !d_owner_off) return RFX_E_ARG;
+    if (!ctx || !d_words || !d_owner_off || n_reads < 0 || words_per_read * 32 < read_len || front_clip < 0 || end_clip < 0)
+        return RFX_E_ARG;
     RFX_TRY(check_k(k));
     RFX_HIP(hipSetDevice(ctx->device));
     ReadStore rs{d_words, n_reads, words_per_read, read_len, k, front_clip, end_clip};
@@ -1006,7 +1009,7 @@ int rfx_dev_combine_reads(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads
                           int64_t cap_pairs, int64_t *d_owner_off, int64_t *h_owner_off, int64_t *out_n,
                           int64_t *out_instances) try {
     if (!ctx || !d_words || !d_owner_off || n_reads < 0 || words_per_read * 32 < read_len || cap_pairs < 0) return RFX_E_ARG;
-    if (n_owners < 1 || n_owners > 64) return RFX_E_ARG;
+    if (n_owners < 1 || n_owners > 64 || front_clip < 0 || end_clip < 0) return RFX_E_ARG;
     RFX_TRY(check_k(k));
     RFX_HIP(hipSetDevice(ctx->device));
     ReadStore rs{d_words, n_reads, words_per_read, read_len, k, front_clip, end_clip};
@@ -1403,10 +1406,20 @@ int rfx_dev_counter_to_asm(rfx_ctx *ctx, const uint64_t *d_keys32, const int64_t
     return counter_to_asm(ctx, d_keys32, d_counts64, n, k, min_cov, max_cov, d_out_kmers, d_out_counts, out_n);
 } RFX_API_CATCH(ctx)
 
+// first capacity of rfx_assemble_reads' survivor buffers; both count loops grow it to the reported need on RFX_E_CAP
+// (RFX_ASSEMBLE_KCAP: test knob, a first capacity below the survivors so that a small input takes the retry)
+static int64_t assemble_first_kcap(int64_t instances) {
+    if (const char *e = getenv("RFX_ASSEMBLE_KCAP")) {
+        const long long v = atoll(e);
+        if (v > 0) return (int64_t)v;
+    }
+    return std::max<int64_t>(1 << 20, instances / 8);
+}
+
 int rfx_assemble_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_off, int64_t n_reads,
                        const rfx_params *prm, char *out, int64_t cap, int64_t *out_len, int64_t *out_contigs,
                        int64_t *trace, int64_t trace_cap, int64_t *n_trace, int64_t *out_kept) try {
-    if (!ctx || !read_off || !prm || !out_len || n_reads < 0) return RFX_E_ARG;
+    if (!ctx || !read_off || !prm || !out_len || n_reads < 0 || prm->front_clip < 0 || prm->end_clip < 0) return RFX_E_ARG;
     const bool wide = prm->k > 31;                 // k = 33..125: the k > 31 counter and driver (below)
     if (wide) {
         RFX_TRY(check_k_w(prm->k));
@@ -1513,8 +1526,8 @@ int rfx_assemble_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_o
         // ReflexivDataFrameCounter64's count and filter, KmerBinarizer + the from-counts filter, ReflexivDSMain64's driver
         const int k = prm->k, aw = asm_words(k), kw = k / 32 + 1;     // driver and counter key words
         int64_t m = 0, dist = 0, inst = 0;
-        int64_t kcap = std::max<int64_t>(1 << 20, (uniform ? kmers_per_read_w((int)maxlen, k, prm->front_clip, prm->end_clip) * n_reads
-                                                            : (int64_t)nb) / 8);
+        int64_t kcap = assemble_first_kcap(uniform ? kmers_per_read_w((int)maxlen, k, prm->front_clip, prm->end_clip) * n_reads
+                                                   : (int64_t)nb);
         DevBuf wk, wc;
         for (;;) {                                  // survivors are few; grow on RFX_E_CAP
             RFX_HIP(wk.alloc((size_t)kcap * kw * 8, ctx->stream));
@@ -1549,7 +1562,7 @@ int rfx_assemble_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_o
         n_inst = rs.n_instances;
     } else n_inst = kmers_per_read((int)maxlen, prm->k, prm->front_clip, prm->end_clip) * n_reads;
     int64_t m = 0, dist = 0;
-    int64_t kcap = std::max<int64_t>(1 << 20, n_inst / 8);
+    int64_t kcap = assemble_first_kcap(n_inst);
     for (;;) {                                      // survivors are few; grow on RFX_E_CAP
         RFX_HIP(d_keys.alloc((size_t)kcap * 8, ctx->stream));
         RFX_HIP(d_counts.alloc((size_t)kcap * 4, ctx->stream));
