@@ -548,7 +548,8 @@ int rfx_dedup_contig_text(rfx_ctx *ctx, const char *contig_text, int64_t len, in
  *                              FirstFour.assemblyFromKmer (:137-224) = random_reflection 1, passes_first_four 4, no
  *                              iterations (end < start); Iteration.assemblyFromKmer (:134-205) = iterations start..end
  * Outputs: caller-allocated arrays of cap_n records / cap_key / cap_ext bases; n / need_key / need_ext are set; RFX_E_CAP
- * when a capacity is short.  Keys of more than 124 bases: RFX_E_LIMIT (the reference's k-mer list ends at 95). */
+ * when a capacity is short.  Keys of more than 124 bases: RFX_E_LIMIT from each of the four (the reference's k-mer list ends
+ * at 95); P outside 1..63: RFX_E_ARG.  A call that returns either writes nothing. */
 typedef struct {
     int64_t n;
     uint8_t *key; int64_t *key_off;      /* key i = key[key_off[i] .. key_off[i+1]) */

@@ -374,6 +374,13 @@ static int dyn_download(rfx_ctx *ctx, const DynDev &d, rfx_dyn_records *h) {
     return RFX_OK;
 }
 
+// the entries that form no blocks refuse a key the sort would refuse (more than DYN_MAXB blocks), before anything is written
+static int dyn_keys_within_limit(rfx_ctx *ctx, const rfx_dyn_records *h) {
+    for (int64_t i = 0; i < h->n; i++)
+        if (h->key_off[i + 1] - h->key_off[i] > 31 * DYN_MAXB) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
+    return RFX_OK;
+}
+
 #define GRID(n) dim3((unsigned)ceil_div(std::max<int64_t>((n), 1), 256)), dim3(256), 0, ctx->stream
 
 // sort("k-1") + the cut into P logical partitions: in -> out (sorted), d_ps[P + 1]; *lmin = the shortest key
@@ -614,6 +621,7 @@ int rfx_dyn_binarize(rfx_ctx *ctx, const char *text, const int64_t *row_off, int
 int rfx_dyn_random_reflection(rfx_ctx *ctx, const rfx_dyn_records *in, const int64_t *part_start, int P, rfx_dyn_records *out) try {
     if (!ctx || !in || !out || !part_start || P < 1 || P > 63) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
+    RFX_TRY(dyn_keys_within_limit(ctx, in));
     DynDev a, b;
     DevBuf ps;
     RFX_TRY(dyn_upload(ctx, in, a));
@@ -628,6 +636,7 @@ int rfx_dyn_extend_pass(rfx_ctx *ctx, const rfx_dyn_records *in, const int64_t *
     if (!ctx || !in || !out || !part_start || P < 1 || P > 63 || (stage != 0 && stage != 1) || (start_marker != 1 && start_marker != 2))
         return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
+    RFX_TRY(dyn_keys_within_limit(ctx, in));
     DynDev a, b;
     DevBuf ps, ops;
     RFX_TRY(dyn_upload(ctx, in, a));

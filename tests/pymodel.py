@@ -358,3 +358,219 @@ def assemble_w(kmers, counts, k, P=4, min_err=8, min_iter=15, max_iter=150, trac
             recs = stable_sort(flip_all_w(recs, m, sub))
             recs = key_filter_w("longer", recs, ps(recs), sub)
     return stable_sort(recs)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The dynamic-k passes (P/ReflexivDSDynamicKmerFirstFour.java, P/ReflexivDSDynamicKmerIteration.java) on
+# base strings: a third statement next to oracle/reflexiv_dynamic.c and the kernels, written from the reference's
+# DSExtendReflexivKmerToArrayLoop.call (Iteration:501-656) and reflexivExtend (:783-945), which NAMES EVERY DECISION it
+# takes.  Records are (key_str, marker, ext_str, left, right) as above; keys have any length.  Blocks appear only in the
+# order of sort("k-1").
+
+DYN_LABELS_ALWAYS = (
+    "unrelated", "same marker",
+    "forward row: both negative", "forward row: both non-negative", "forward row: own distance", "forward row: holder's distance",
+    "forward row: no merge",
+    "reflected row: both negative", "reflected row: both non-negative", "reflected row: own distance", "reflected row: holder's distance",
+    "reflected row: no merge",
+    "merge: ends inherited", "merge: bubble on the left", "merge: bubble on the right", "merge: extra > 0", "clamp")
+# given beside the decision's own name: a distance that reaches past the partner's extension but not past the longer key's
+# extra bases, so that `- extra` alone decides
+DYN_LABELS_EXTRA_DECIDES = ("forward row: extra bars holder's distance", "reflected row: extra bars own distance")
+DYN_LABELS_BELOW_61 = ("forward row shorter: emitted", "holder shorter: kept")
+DYN_LABELS_FROM_61 = ("forward row shorter: dropped", "holder shorter: dropped")
+
+
+def dyn_labels(stage, start_iteration):
+    """every label the walk can give in a configuration"""
+    return DYN_LABELS_ALWAYS + (DYN_LABELS_FROM_61 if stage == 1 and start_iteration >= 61 else DYN_LABELS_BELOW_61)
+
+
+def dyn_blocks(key):
+    """a key as Spark holds it: left-aligned 31-base blocks, 01 after the last base, each block a SIGNED long"""
+    out = []
+    for b in range(0, max(len(key), 1), 31):
+        part = key[b:b + 31]
+        bits = "".join(format(NUC.index(c), "02b") for c in part)
+        if b + 31 >= len(key):
+            bits += "01"
+        v = int(bits.ljust(64, "0"), 2)
+        out.append(v - (1 << 64) if v >> 63 else v)
+    return tuple(out)
+
+
+def dyn_sort(recs):
+    """sort("k-1") on array<long>: element by element, a proper prefix first -- the order of Python tuples; stable"""
+    return sorted(recs, key=lambda r: dyn_blocks(r[0]))
+
+
+def dyn_partition_starts(recs, P):
+    return partition_starts([r[0] for r in recs], P)
+
+
+def dyn_clamp(v):
+    return max(-30000, min(30000, v))
+
+
+def dyn_flip(r, m):
+    """singleKmerRandomizer: the record in orientation m, its key length kept"""
+    key, mk, ext, left, right = r
+    if mk == m:
+        return r
+    seq = key + ext if mk == 1 else ext + key
+    n = len(key)
+    return (seq[:n], 1, seq[n:], left, right) if m == 1 else (seq[len(seq) - n:], 2, seq[:len(seq) - n], left, right)
+
+
+def dyn_merge(F, R, d, m, labels):
+    """reflexivExtend: forward F + reflected R with bubble distance d, in orientation m; the longer key's length is kept"""
+    extra = max(0, len(F[0]) - len(R[0]))
+    longer = F[0] if len(F[0]) >= len(R[0]) else R[0]
+    if d < 0:
+        labels.append("merge: ends inherited")
+        left = R[3] if R[3] >= 0 else F[3] - len(R[2])
+        right = F[4] if F[4] >= 0 else R[4] - len(F[2]) - extra
+    elif F[3] > 0:
+        labels.append("merge: bubble on the left")
+        left = d
+        right = F[4] if F[4] >= 0 else R[4] - len(F[2]) - extra
+    else:
+        labels.append("merge: bubble on the right")
+        left = R[3] if R[3] >= 0 else F[3] - len(R[2])
+        right = d - extra
+    if extra > 0:
+        labels.append("merge: extra > 0")
+    if dyn_clamp(left) != left or dyn_clamp(right) != right:
+        labels.append("clamp")
+    whole = R[2] + longer + F[2]
+    n = len(longer)
+    if m == 1:
+        return (whole[:n], 1, whole[n:], dyn_clamp(left), dyn_clamp(right))
+    return (whole[len(whole) - n:], 2, whole[:len(whole) - n], dyn_clamp(left), dyn_clamp(right))
+
+
+def dyn_extend_pass(recs, starts, stage=0, start_iteration=5, start_marker=2):
+    """One pass over sorted records, a fresh walk per partition -> (records, output partition starts, labels).  stage 0:
+    DSExtendReflexivKmer (FirstFour), 1: DSExtendReflexivKmerToArrayLoop (Iteration); from start_iteration 61 on a shorter
+    forward record is dropped.  labels holds one name per decision (and the merge's own names after it), in walk order."""
+    late = stage == 1 and start_iteration >= 61
+    out, ostarts, labels = [], [], []
+    for p in range(len(starts) - 1):
+        ostarts.append(len(out))
+        m = start_marker
+        holder = None
+
+        def emit(r):
+            nonlocal m
+            out.append(r)
+            m = 3 - m
+        for s in recs[starts[p]:starts[p + 1]]:
+            if holder is None:
+                holder = s
+                continue
+            n = min(len(s[0]), len(holder[0]))
+            if s[0][:n] != holder[0][:n]:
+                labels.append("unrelated")
+                emit(dyn_flip(holder, m))
+                holder = s
+                continue
+            if s[1] == holder[1]:
+                labels.append("same marker")
+                emit(dyn_flip(s, m))
+                continue
+            ls, lh = len(s[0]), len(holder[0])
+            if s[1] == 1:                                   # the row is forward, the holder reflected
+                side, F, R = "forward row", s, holder
+                if ls < lh:
+                    labels.append("forward row shorter: " + ("dropped" if late else "emitted"))
+                    if not late:
+                        emit(dyn_flip(s, m))
+                    continue
+                extra = ls - lh
+                own = s[3] - len(holder[2]) if s[3] >= 0 else -1
+                other = holder[4] - len(s[2]) if holder[4] >= 0 else -1
+                other_ok = holder[4] >= 0 and other - extra >= 0
+                barred = "forward row: extra bars holder's distance" if other >= 0 and not other_ok and not (s[3] >= 0 and own >= 0) else None
+                both_neg, both_pos = s[3] < 0 and holder[4] < 0, s[3] >= 0 and holder[4] >= 0
+            else:                                           # the row is reflected, the holder forward
+                side, F, R = "reflected row", holder, s
+                if lh < ls:
+                    labels.append("holder shorter: " + ("dropped" if late else "kept"))
+                    if late:
+                        holder = None
+                    emit(dyn_flip(s, m))
+                    continue
+                extra = lh - ls
+                own = s[4] - len(holder[2]) if s[4] >= 0 else -1
+                barred = "reflected row: extra bars own distance" if own >= 0 and own - extra < 0 and holder[3] < 0 else None
+                own = own if own - extra >= 0 else -1
+                other = holder[3] - len(s[2]) if holder[3] >= 0 else -1
+                other_ok = other >= 0
+                both_neg, both_pos = s[4] < 0 and holder[3] < 0, s[4] >= 0 and holder[3] >= 0
+            if barred and not both_neg and not both_pos:
+                labels.append(barred)
+            if both_neg or both_pos:
+                labels.append(side + (": both negative" if both_neg else ": both non-negative"))
+                d = -1
+            elif own >= 0:
+                labels.append(side + ": own distance")
+                d = own
+            elif other_ok:
+                labels.append(side + ": holder's distance")
+                d = other
+            else:
+                labels.append(side + ": no merge")
+                emit(dyn_flip(s, m))
+                continue
+            emit(dyn_merge(F, R, d, m, labels))
+            holder = None
+        if holder is not None:
+            emit(dyn_flip(holder, m))
+    ostarts.append(len(out))
+    return out, ostarts, labels
+
+
+def dyn_random_reflection(recs, starts):
+    out = []
+    for p in range(len(starts) - 1):
+        for i, r in enumerate(recs[starts[p]:starts[p + 1]]):
+            out.append(dyn_flip(r, 2 - i % 2))
+    return out
+
+
+def dyn_census(labels):
+    from collections import Counter
+    return Counter(labels)
+
+
+DYN_EDGE_LENGTHS = (22, 30, 31, 32, 40, 61, 62, 63, 80, 92, 93, 94)
+DYN_WIDE_LENGTHS = DYN_EDGE_LENGTHS + (95, 110, 123, 124)
+DYN_ATTR_VALUES = (-29990, -40, -7, -1, 0, 2, 9, 21, 30, 44, 55, 70, 130, 29990)
+
+
+def dyn_crafted_attribute(rng):
+    """half from DYN_ATTR_VALUES, half from -49..-1"""
+    return int(rng.choice(DYN_ATTR_VALUES)) if rng.integers(0, 2) else -int(rng.integers(1, 50))
+
+
+def dyn_crafted_families(rng, n_families, lengths=DYN_EDGE_LENGTHS, ext_max=40, family_len=None):
+    """Crafted records for the pass rules: a family is a random string; its 1..6 records have keys that are prefixes of it
+    (one in seven with the last base changed: unrelated inside a family; one in three as long as the one before: equal
+    keys), either marker, an extension of 1..ext_max
+    bases, and left / right from dyn_crafted_attribute (negatives, 0, positives below and above an extension's length, and
+    the pair next to the +-30000 clamp).  rng: numpy Generator.  Families stay together, their order and their records' order
+    are random."""
+    family_len = family_len or max(lengths)
+    recs = []
+    for _ in range(n_families):
+        fam = "".join(NUC[b] for b in rng.integers(0, 4, family_len))
+        n = 0
+        for _ in range(int(rng.integers(1, 7))):
+            n = n if n and rng.integers(0, 3) == 0 else int(rng.choice(lengths))      # (one in three repeats a length: equal keys)
+            key = fam[:n]
+            if rng.integers(0, 7) == 0:
+                key = key[:-1] + NUC[(NUC.index(key[-1]) + int(rng.integers(1, 4))) % 4]
+            ext = "".join(NUC[b] for b in rng.integers(0, 4, int(rng.integers(1, ext_max + 1))))
+            left, right = (dyn_crafted_attribute(rng) for _ in range(2))
+            recs.append((key, int(rng.integers(1, 3)), ext, left, right))
+    return recs

@@ -1,12 +1,12 @@
 """Conformance of tools/java2py.py -- the translator that runs the reference's own operator classes to make
-tests/golden/{reference,dedup,dynamic}_vectors.npz -- against facts of the Java Language Specification, INDEPENDENTLY of
+tests/golden/{reference,dedup,dynamic,dynamic_edge}_vectors.npz -- against facts of the Java Language Specification, INDEPENDENTLY of
 the oracle: every expected value below is written out by hand from the JLS rule it cites (or is plain two's-complement
 arithmetic), none is computed by oracle/ or by the code under test.
 
 Part 1: the integer model `J` and the runtime shims, fact by fact.
 Part 2: one tiny hand-written Java class per statement / expression kind the operator classes use, translated from its
         source TEXT exactly as the generators translate the reference's classes, with a known answer.
-Part 3 (skipped when /root/reference is absent, e.g. on the GPU box): the three fixture generators re-run in a scratch
+Part 3 (skipped when /root/reference is absent, e.g. on the GPU box): the four fixture generators re-run in a scratch
         directory give files bit-identical to the committed ones.
 """
 import os
@@ -316,12 +316,12 @@ REF = "/root/reference"
 
 @pytest.mark.skipif(not os.path.isdir(REF), reason="the reference's sources are not on this box")
 def test_regenerated_vectors_equal_the_committed_files(tmp_path):
-    """The three fixture generators run again (the reference's classes translated and executed afresh, side by side to keep
+    """The four fixture generators run again (the reference's classes translated and executed afresh, side by side to keep
     the CPU suite short) must reproduce the committed .npz files array for array: the fixtures are what the generators make
     from the reference TODAY, with today's translator -- not a leftover."""
     golden = os.path.join(ROOT, "tests", "golden")
     jobs = [("make_dedup_vectors.py", "dedup_vectors.npz", ["--jobs", "5"]), ("make_dynamic_vectors.py", "dynamic_vectors.npz", []),
-            ("make_reference_vectors.py", "reference_vectors.npz", [])]
+            ("make_reference_vectors.py", "reference_vectors.npz", []), ("make_dynamic_edge_vectors.py", "dynamic_edge_vectors.npz", [])]
     procs = [(name, subprocess.Popen([sys.executable, os.path.join(golden, script), "--out", str(tmp_path / name)] + extra, cwd=ROOT,
                                      stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)) for script, name, extra in jobs]
     try:
