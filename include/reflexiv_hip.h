@@ -575,6 +575,55 @@ int rfx_dyn_bases_to_blocks(const uint8_t *bases, int n, int64_t *out, int cap);
 int64_t rfx_dyn_attribute(int marker, int left, int right);
 void rfx_dyn_attribute_unpack(int64_t attribute, int *marker, int *left, int *right);
 
+/* The same passes on a PACKED record set that stays in HBM.  Every pointer of rfx_dyn_packed is a DEVICE
+ * pointer into arrays the caller allocated; the struct itself lives on the host.  Bases are 2 bits each, 32 to a word, the
+ * first in the two highest bits -- the convention of the 2-bit read store (rfx_dev_encode_reads).  INVARIANT: every bit past
+ * a key's or an extension's last base is 0, and so is every unused key word; every producer writes those bits (it never
+ * relies on zeroed memory) and every consumer compares whole words.  Keys hold at most 124 bases in RFX_DYN_KEY_WORDS words.
+ * CAPACITY: no pass needs more records or more extension words than its input -- a flip keeps both lengths (the same
+ * multiset of extension lengths, the same word count), a merge of extensions of a and b bases gives ceil((a+b)/32) <=
+ * ceil(a/32) + ceil(b/32) words -- so an output with cap_n >= in.n and cap_words >= in.ext_off[in.n] always suffices for
+ * sort, random reflection, extend pass and run; rfx_dev_dyn_pack needs cap_words >= n + ext bases / 32 at most,
+ * rfx_dev_dyn_binarize cap_words >= n_rows + text bytes / 32 at most.
+ *   rfx_dev_dyn_pack / _unpack    host base codes (rfx_dyn_records) <-> the packed set
+ *   rfx_dev_dyn_binarize          rfx_dyn_binarize with the text and the row offsets (n_rows + 1, into d_text) in HBM
+ *   rfx_dev_dyn_sort / _random_reflection / _extend_pass / _run
+ *                                 operator for operator and argument for argument the host forms above; part starts are
+ *                                 device arrays of P + 1 entries, `trace` is a host array
+ *   rfx_dev_dyn_to_text           DSBinarySubKmerWith{Short,Long}ExtensionToString (FirstFour:226-263): rows
+ *                                 "SUBKMER,marker|left|right,EXTENSION\n" into a device buffer; *out_len = the text's length
+ *   rfx_dyn_run_text              host text in, host text out, everything between packed and in HBM: upload, binarize
+ *                                 (form 0 / 1), run, to-text, one copy back -- for the dynamic-k passes what rfx_assemble_reads
+ *                                 is for the fixed path
+ * All run on the context's stream and return after it has drained.  P outside 1..63, a null pointer, a bad form / stage /
+ * start_marker: RFX_E_ARG; a key of more than 124 bases: RFX_E_LIMIT (pack, binarize and every operator); a short output:
+ * RFX_E_CAP with n / need_words (or *out_len) set.  In each of these cases no output array was written, except that the two
+ * text buffers follow the text-buffer rule (filled up to cap, nothing at or past it).  n = 0 is valid everywhere. */
+#define RFX_DYN_KEY_WORDS 4
+typedef struct {
+    int64_t   n;
+    uint64_t *key;      /* n * 4 words; base j of key i in key[4*i + j/32] at bits 63-2*(j%32)..62-2*(j%32)   */
+    uint8_t  *key_len;  /* bases, <= 124                                                                    */
+    uint64_t *ext;      /* record i = words [ext_off[i], ext_off[i+1]), same 32-bases-per-word form         */
+    int64_t  *ext_off;  /* n + 1 entries, in WORDS: every extension starts on a word                        */
+    int32_t  *ext_len;  /* bases; ext_off[i+1] - ext_off[i] = (ext_len[i] + 31) / 32                         */
+    int32_t  *marker, *left, *right;
+    int64_t   cap_n, cap_words, need_words;
+} rfx_dyn_packed;       /* every pointer is a DEVICE pointer */
+int rfx_dev_dyn_pack(rfx_ctx *ctx, const rfx_dyn_records *host_in, rfx_dyn_packed *d_out);
+int rfx_dev_dyn_unpack(rfx_ctx *ctx, const rfx_dyn_packed *d_in, rfx_dyn_records *host_out);
+int rfx_dev_dyn_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, int form, rfx_dyn_packed *d_out);
+int rfx_dev_dyn_sort(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int P, rfx_dyn_packed *d_out, int64_t *d_part_start);
+int rfx_dev_dyn_random_reflection(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const int64_t *d_part_start, int P, rfx_dyn_packed *d_out);
+int rfx_dev_dyn_extend_pass(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const int64_t *d_part_start, int P, int stage, int start_iteration,
+                            int start_marker, rfx_dyn_packed *d_out, int64_t *d_out_part_start);
+int rfx_dev_dyn_run(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int P, int random_reflection, int passes_first_four, int start_iteration,
+                    int end_iteration, rfx_dyn_packed *d_out, int64_t *trace, int64_t trace_cap, int64_t *n_trace);
+int rfx_dev_dyn_to_text(rfx_ctx *ctx, const rfx_dyn_packed *d_in, char *d_text, int64_t cap, int64_t *out_len);
+int rfx_dyn_run_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int form, int P, int random_reflection,
+                     int passes_first_four, int start_iteration, int end_iteration, char *out, int64_t cap, int64_t *out_len, int64_t *trace,
+                     int64_t trace_cap, int64_t *n_trace);
+
 /* Synthetic reads: integer-only counter-based generator, bit-identical to
  * oracle/reflexiv_oracle.c orc_synth_*.  Writes packed reads straight into HBM. */
 int rfx_dev_synth_genome(rfx_ctx *ctx, uint64_t seed, int64_t genome_len, uint64_t *d_genome);

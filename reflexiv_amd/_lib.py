@@ -39,6 +39,13 @@ class CDynRecords(C.Structure):
                 ("cap_ext", C.c_int64), ("need_key", C.c_int64), ("need_ext", C.c_int64)]
 
 
+class CDynPacked(C.Structure):
+    """rfx_dyn_packed: every pointer is a DEVICE pointer."""
+    _fields_ = [("n", C.c_int64), ("key", C.c_void_p), ("key_len", C.c_void_p), ("ext", C.c_void_p), ("ext_off", C.c_void_p),
+                ("ext_len", C.c_void_p), ("marker", C.c_void_p), ("left", C.c_void_p), ("right", C.c_void_p), ("cap_n", C.c_int64),
+                ("cap_words", C.c_int64), ("need_words", C.c_int64)]
+
+
 class CRecords(C.Structure):
     """rfx_records."""
     _fields_ = [("n", C.c_int64), ("key", C.c_void_p), ("marker", C.c_void_p), ("ext_off", C.c_void_p),
@@ -69,7 +76,23 @@ SYMBOLS = [
     "rfx_dedup_contigs", "rfx_dedup_contig_text",
     "rfx_dyn_binarize", "rfx_dyn_sort", "rfx_dyn_random_reflection", "rfx_dyn_extend_pass", "rfx_dyn_run",
     "rfx_dyn_blocks_to_bases", "rfx_dyn_bases_to_blocks", "rfx_dyn_attribute", "rfx_dyn_attribute_unpack",
+    "rfx_dev_dyn_pack", "rfx_dev_dyn_unpack", "rfx_dev_dyn_binarize", "rfx_dev_dyn_sort", "rfx_dev_dyn_random_reflection",
+    "rfx_dev_dyn_extend_pass", "rfx_dev_dyn_run", "rfx_dev_dyn_to_text", "rfx_dyn_run_text",
 ]
+
+# prototypes of the packed dynamic-k entry points (ctx, then as include/reflexiv_hip.h declares them)
+_PK, _HR, _I, _L, _P = "PK", "HR", C.c_int, C.c_int64, C.c_void_p
+_DYN_PACKED_ARGS = {
+    "rfx_dev_dyn_pack": (_HR, _PK),
+    "rfx_dev_dyn_unpack": (_PK, _HR),
+    "rfx_dev_dyn_binarize": (_P, _P, _L, _I, _PK),
+    "rfx_dev_dyn_sort": (_PK, _I, _PK, _P),
+    "rfx_dev_dyn_random_reflection": (_PK, _P, _I, _PK),
+    "rfx_dev_dyn_extend_pass": (_PK, _P, _I, _I, _I, _I, _PK, _P),
+    "rfx_dev_dyn_run": (_PK, _I, _I, _I, _I, _I, _PK, _P, _L, _P),
+    "rfx_dev_dyn_to_text": (_PK, _P, _L, _P),
+    "rfx_dyn_run_text": (_P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _L, _P),
+}
 
 
 def build(force: bool = False) -> str:
@@ -112,6 +135,11 @@ def lib():
             if name == "rfx_dyn_attribute":
                 fn.restype = C.c_int64
                 fn.argtypes = [C.c_int, C.c_int, C.c_int]
+                continue
+            if name in _DYN_PACKED_ARGS:
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p] + [C.POINTER(CDynPacked) if a == _PK else C.POINTER(CDynRecords) if a == _HR else a
+                                              for a in _DYN_PACKED_ARGS[name]]
                 continue
             if name == "rfx_dyn_attribute_unpack":
                 fn.restype = None

@@ -155,6 +155,51 @@ class DynRecords:
         return DynRecords.from_text(keys, exts, mk, lf, rt)
 
 
+class DynPacked:
+    """The packed dynamic-k record set (rfx_dyn_packed) over torch tensors in HBM: four key words per record and word-aligned
+    extensions, 32 bases per word, first base in the two highest bits, every bit past the last base 0.  Capacities are the
+    tensors' sizes; `n` is the number of records in use, the extension words in use are ext_off[n]."""
+    FIELDS = ("key", "key_len", "ext", "ext_off", "ext_len", "marker", "left", "right")
+
+    def __init__(self, cap_n: int, cap_words: int, device="cuda"):
+        import torch
+        self.cap_n, self.cap_words, self.n = int(cap_n), int(cap_words), 0
+        m, w = max(1, self.cap_n), max(1, self.cap_words)
+        self.key = torch.empty(m * 4, dtype=torch.int64, device=device)       # (uint64 words, held as int64 bit patterns)
+        self.key_len = torch.empty(m, dtype=torch.uint8, device=device)
+        self.ext = torch.empty(w, dtype=torch.int64, device=device)
+        self.ext_off = torch.empty(self.cap_n + 1, dtype=torch.int64, device=device)   # (empty, not zeros: no kernel of torch's stream may
+                                                                                      # still be pending when the library writes here)
+        self.ext_len = torch.empty(m, dtype=torch.int32, device=device)
+        self.marker = torch.empty(m, dtype=torch.int32, device=device)
+        self.left = torch.empty(m, dtype=torch.int32, device=device)
+        self.right = torch.empty(m, dtype=torch.int32, device=device)
+
+    @property
+    def words(self) -> int:
+        """extension words in use (reads ext_off[n] back)"""
+        return int(self.ext_off[self.n].item()) if self.n else 0
+
+    def tensors(self):
+        return [getattr(self, f) for f in self.FIELDS]
+
+    def _c(self) -> "_lib.CDynPacked":
+        c = _lib.CDynPacked()
+        c.n = self.n
+        for f in self.FIELDS:
+            setattr(c, f, getattr(self, f).data_ptr())
+        c.cap_n, c.cap_words, c.need_words = self.cap_n, self.cap_words, 0
+        return c
+
+    def host(self):
+        """the raw arrays in use, as numpy: (key [n, 4] uint64, key_len, ext uint64, ext_off, ext_len, marker, left, right)"""
+        n = self.n
+        w = self.words
+        return (self.key[:4 * n].cpu().numpy().view(np.uint64).reshape(n, 4), self.key_len[:n].cpu().numpy(),
+                self.ext[:w].cpu().numpy().view(np.uint64), self.ext_off[:n + 1].cpu().numpy(), self.ext_len[:n].cpu().numpy(),
+                self.marker[:n].cpu().numpy(), self.left[:n].cpu().numpy(), self.right[:n].cpu().numpy())
+
+
 def as_records(r) -> Records:
     """Accept any object with key/marker/ext_off/ext/left/right arrays (e.g. the oracle's Records)."""
     return Records(np.ascontiguousarray(r.key, np.uint64), np.ascontiguousarray(r.marker, np.int32),
@@ -736,6 +781,135 @@ class Reflexiv:
                              lambda co: (P, int(random_reflection), passes_first_four, start_iteration, end_iteration, C.byref(co), _p(trace),
                                          C.c_int64(len(trace)), C.byref(ntr)))
         return out, [int(x) for x in trace[:ntr.value]]
+
+    # ---- the same passes on a packed record set that stays in HBM (rfx_dev_dyn_*)
+    def _dyn_dev_call(self, fn, name, out: "DynPacked", args_of):
+        """one rfx_dev_dyn_* call into `out` (grown and called again on RFX_E_CAP) -> out"""
+        while True:
+            co = out._c()
+            t0 = time.perf_counter()
+            st = fn(self.ctx, *args_of(co))
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
+            if st == RFX_E_CAP:
+                out = DynPacked(max(out.cap_n, int(co.n)), max(out.cap_words, int(co.need_words)), out.key.device)
+                continue
+            self._check(st, name)
+            out.n = int(co.n)
+            return out
+
+    def dyn_pack(self, r: DynRecords, out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_dyn_pack: host base codes -> a packed set in HBM"""
+        out = out or DynPacked(r.n, r.n + len(r.ext) // 32)
+        ci = r._c()
+        return self._dyn_dev_call(self.L.rfx_dev_dyn_pack, "rfx_dev_dyn_pack", out, lambda co: (C.byref(ci), C.byref(co)))
+
+    def dyn_unpack(self, d: "DynPacked") -> DynRecords:
+        """rfx_dev_dyn_unpack: a packed set -> host base codes"""
+        cap_n, cap_k, cap_e = d.n, 124 * d.n + 64, 32 * d.words + 64
+        ci = d._c()
+        while True:
+            out = DynRecords.empty(cap_n, cap_k, cap_e)
+            co = out._c()
+            co.cap_n, co.cap_key, co.cap_ext = cap_n, cap_k, cap_e
+            t0 = time.perf_counter()
+            st = self.L.rfx_dev_dyn_unpack(self.ctx, C.byref(ci), C.byref(co))
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3
+            if st == RFX_E_CAP:
+                cap_n, cap_k, cap_e = max(cap_n, int(co.n)), max(cap_k, int(co.need_key)), max(cap_e, int(co.need_ext))
+                continue
+            self._check(st, "rfx_dev_dyn_unpack")
+            return out._trim(co)
+
+    def dyn_binarize_dev(self, d_text, d_row_off, form: int, out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_dyn_binarize: text (torch uint8 tensor in HBM) + row offsets (torch int64 tensor, n_rows + 1) -> a packed set"""
+        n_rows = int(d_row_off.numel()) - 1
+        out = out or DynPacked(n_rows, n_rows + int(d_text.numel()) // 32)
+        return self._dyn_dev_call(self.L.rfx_dev_dyn_binarize, "rfx_dev_dyn_binarize", out,
+                                  lambda co: (d_text.data_ptr(), d_row_off.data_ptr(), n_rows, form, C.byref(co)))
+
+    def dyn_sort_dev(self, d: "DynPacked", P: int, out: "DynPacked" = None):
+        """rfx_dev_dyn_sort -> (sorted DynPacked, part_start: torch int64 [P + 1] in HBM)"""
+        import torch
+        ps = torch.empty(max(P, 0) + 1, dtype=torch.int64, device=d.key.device)
+        ci = d._c()
+        out = self._dyn_dev_call(self.L.rfx_dev_dyn_sort, "rfx_dev_dyn_sort", out or DynPacked(d.n, d.words),
+                                 lambda co: (C.byref(ci), P, C.byref(co), ps.data_ptr()))
+        return out, ps
+
+    def dyn_random_reflection_dev(self, d: "DynPacked", d_part_start, out: "DynPacked" = None) -> "DynPacked":
+        ci = d._c()
+        P = int(d_part_start.numel()) - 1
+        return self._dyn_dev_call(self.L.rfx_dev_dyn_random_reflection, "rfx_dev_dyn_random_reflection", out or DynPacked(d.n, d.words),
+                                  lambda co: (C.byref(ci), d_part_start.data_ptr(), P, C.byref(co)))
+
+    def dyn_extend_pass_dev(self, d: "DynPacked", d_part_start, stage=0, start_iteration=5, start_marker=2, out: "DynPacked" = None):
+        """rfx_dev_dyn_extend_pass -> (DynPacked, out_part_start: torch int64 [P + 1] in HBM)"""
+        import torch
+        ci = d._c()
+        P = int(d_part_start.numel()) - 1
+        ops = torch.empty(P + 1, dtype=torch.int64, device=d.key.device)
+        out = self._dyn_dev_call(self.L.rfx_dev_dyn_extend_pass, "rfx_dev_dyn_extend_pass", out or DynPacked(d.n, d.words),
+                                 lambda co: (C.byref(ci), d_part_start.data_ptr(), P, stage, start_iteration, start_marker, C.byref(co),
+                                             ops.data_ptr()))
+        return out, ops
+
+    def dyn_run_dev(self, d: "DynPacked", P=1, random_reflection=False, passes_first_four=0, start_iteration=1, end_iteration=0,
+                    out: "DynPacked" = None):
+        """rfx_dev_dyn_run -> (DynPacked, [records after each pass])"""
+        ci = d._c()
+        trace = np.zeros(256, np.int64)
+        ntr = C.c_int64(0)
+        out = self._dyn_dev_call(self.L.rfx_dev_dyn_run, "rfx_dev_dyn_run", out or DynPacked(d.n, d.words),
+                                 lambda co: (C.byref(ci), P, int(random_reflection), passes_first_four, start_iteration, end_iteration,
+                                             C.byref(co), trace.ctypes.data, len(trace), C.addressof(ntr)))
+        return out, [int(x) for x in trace[:ntr.value]]
+
+    def dyn_to_text_dev(self, d: "DynPacked", d_text=None):
+        """rfx_dev_dyn_to_text -> (torch uint8 tensor in HBM holding the rows "SUBKMER,m|l|r,EXTENSION\\n", its length)"""
+        import torch
+        ci = d._c()
+        ln = C.c_int64(0)
+        if d_text is None:
+            d_text = torch.empty(max(1, 160 * d.n + 32 * d.words + 64), dtype=torch.uint8, device=d.key.device)
+        while True:
+            t0 = time.perf_counter()
+            st = self.L.rfx_dev_dyn_to_text(self.ctx, C.byref(ci), d_text.data_ptr(), int(d_text.numel()), C.addressof(ln))
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3
+            if st == RFX_E_CAP:
+                d_text = torch.empty(ln.value, dtype=torch.uint8, device=d.key.device)
+                continue
+            self._check(st, "rfx_dev_dyn_to_text")
+            return d_text, int(ln.value)
+
+    def dyn_run_text(self, text: bytes, form: int, P=1, random_reflection=False, passes_first_four=0, start_iteration=1, end_iteration=0):
+        """rfx_dyn_run_text: the rows of a hand-over file (bytes; one row per line, empty lines skipped) -> (the output rows as
+        bytes, [records after each pass]); binarizer, passes and the text writer on the device, on the packed set"""
+        text = bytes(text)
+        buf = np.frombuffer(text, np.uint8)
+        # the line scan: a row starts at every non-empty line and runs to the next one (the line ends and any empty lines behind
+        # it are the row's tail, which the device parser drops)
+        ends = np.flatnonzero(buf == 10)
+        starts = np.concatenate([[0], ends + 1]).astype(np.int64)
+        stops = np.concatenate([ends, [len(buf)]]).astype(np.int64)
+        stops = stops - ((stops > starts) & (buf[np.maximum(stops - 1, 0)] == 13) if len(buf) else 0)
+        starts = starts[stops > starts]
+        n_rows = len(starts)
+        off = np.concatenate([starts, [len(buf)]]).astype(np.int64)
+        cap = len(buf) + 32 * n_rows + 64
+        trace = np.zeros(256, np.int64)
+        ntr, ln = C.c_int64(0), C.c_int64(0)
+        while True:
+            out = np.empty(max(1, cap), np.uint8)
+            t0 = time.perf_counter()
+            st = self.L.rfx_dyn_run_text(self.ctx, text, off.ctypes.data, n_rows, form, P, int(random_reflection), passes_first_four,
+                                         start_iteration, end_iteration, out.ctypes.data, cap, C.addressof(ln), trace.ctypes.data,
+                                         len(trace), C.addressof(ntr))
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
+            if st == RFX_E_CAP and ln.value > cap:
+                cap = ln.value
+                continue
+            self._check(st, "rfx_dyn_run_text")
+            return out[:ln.value].tobytes(), [int(x) for x in trace[:ntr.value]]
 
     # ------------------------------------------------ f-4: contig RC de-duplication
     def dedup_contigs(self, contigs, min_contig=500):

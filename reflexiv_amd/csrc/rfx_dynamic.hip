@@ -5,19 +5,25 @@
 //
 // The third record layout -- keys of ANY length as left-aligned 31-base blocks with a 01 terminator, an attribute long
 // (marker << 62 | left << 32 | right, negatives as 30000 - v), extensions in the same left-aligned form -- is what a Row
-// carries; in HBM a record set is base strings (one byte per base, offsets) + marker / left / right, and blocks are formed
-// where the reference's behaviour depends on them: the ORDER of sort("k-1") (array<long>: element by element as signed
-// longs, a proper prefix first).
+// carries.  In HBM a record set is PACKED (rfx_dyn_packed): four 64-bit key words per record and
+// word-aligned extensions, 32 bases per word, first base in the two highest bits, every bit past the last base 0 and every
+// unused key word 0.  Every producer here writes those zeros; every consumer compares whole words and relies on them.
+// The 31-base blocks are formed (by shifts, from the words) only where the reference's behaviour depends on them: the ORDER
+// of sort("k-1") (array<long>: element by element as signed longs, a proper prefix first).
 //
 // One pass = the scan of SURVEY.md B.5 with a one-row holder, except that a row meets the holder when their keys are EQUAL
 // OR ONE IS A PREFIX OF THE OTHER (dynamicSubKmerComparator), so equal-key runs are no longer the unit of work.  What is:
 // a FAMILY -- a maximal run of sorted rows that agree on their first Lmin bases, Lmin = the shortest key of the set.  A row
 // can only be related to an earlier row through a common prefix of at least Lmin bases, and everything between two related
-// rows shares that prefix, so no holder ever survives a family boundary.  Kernels: k_dyn_blocks (the sort keys),
-// the library's stable radix sort (block count, then block 3 .. block 0), k_dyn_heads, k_dyn_walk<COUNT / WRITE> (the
-// owner of a family head walks it with the reference's rules; the decisions do not depend on the toggling orientation,
-// which is the parity of the emission rank inside the partition: a prefix sum, as on the fixed-k path), k_dyn_sizes, and
-// k_dyn_emit (one thread per output record writes its bases).
+// rows shares that prefix, so no holder ever survives a family boundary.  Kernels: k_dyn_keys (the sort keys and the set's
+// shortest / longest key), the library's stable radix sort (block count, then the blocks the set has, last to first),
+// k_dyn_heads, k_dyn_walk<COUNT / WRITE> (the owner of a family head walks it with the reference's rules; the decisions do
+// not depend on the toggling orientation, which is the parity of the emission rank inside the partition: a prefix sum, as on
+// the fixed-k path), k_dyn_sizes (lengths, attributes and word counts of the emissions), and k_dyn_emit_key / k_dyn_emit_ext:
+// ONE THREAD PER OUTPUT WORD, which reads its 32 bases from the concatenation of up to three packed segments (dyn_cat32).
+// The gather behind the sort is the same emission with "copy" descriptors.  No pass needs more records or more extension
+// words than its input (a flip keeps both lengths, a merge gives ceil((a+b)/32) <= ceil(a/32) + ceil(b/32)), so the output
+// of a pass is allocated from its input's sizes and no host wait sits between the sizes and the emission.
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -27,151 +33,202 @@ using namespace rfx;
 
 namespace {
 
-constexpr int DYN_MAXB = 4;            // blocks per key: keys up to 124 bases (the reference's k-mer list ends at 95)
+#define DYN_KW RFX_DYN_KEY_WORDS            /* key words per record */
+#define DYN_MAXB 4                          // 31-base blocks per key: keys up to 124 bases (the reference's k-mer list ends at 95)
+#define DYN_MAXK (31 * DYN_MAXB)
 
-struct DynDev {                       // a record set in HBM
-    int64_t n = 0, nk = 0, ne = 0;    // records, key bases, extension bases
-    DevBuf key, key_off, ext, ext_off, marker, left, right;
+struct DynDev {                       // a packed record set in HBM
+    int64_t n = 0, words = 0;         // records; a BOUND on the extension words (the exact count is ext_off[n], in HBM)
+    DevBuf key, key_len, ext, ext_off, ext_len, marker, left, right;
 };
+// what the kernels take
+struct DynView {
+    const uint64_t *key; const uint8_t *key_len; const uint64_t *ext; const int64_t *ext_off; const int32_t *ext_len, *marker, *left, *right;
+};
+struct DynOut {
+    uint64_t *key; uint8_t *key_len; uint64_t *ext; int64_t *ext_off; int32_t *ext_len, *marker, *left, *right;
+};
+static DynView dyn_view(const DynDev &d) {
+    return DynView{d.key.as<uint64_t>(), d.key_len.as<uint8_t>(), d.ext.as<uint64_t>(), d.ext_off.as<int64_t>(), d.ext_len.as<int32_t>(),
+                   d.marker.as<int32_t>(), d.left.as<int32_t>(), d.right.as<int32_t>()};
+}
+static DynOut dyn_out(const DynDev &d) {
+    return DynOut{d.key.as<uint64_t>(), d.key_len.as<uint8_t>(), d.ext.as<uint64_t>(), d.ext_off.as<int64_t>(), d.ext_len.as<int32_t>(),
+                  d.marker.as<int32_t>(), d.left.as<int32_t>(), d.right.as<int32_t>()};
+}
 
 static void buf_swap(DevBuf &x, DevBuf &y) { std::swap(x.p, y.p); std::swap(x.s, y.s); std::swap(x.borrowed, y.borrowed); }
 static void dyn_swap(DynDev &x, DynDev &y) {
-    std::swap(x.n, y.n); std::swap(x.nk, y.nk); std::swap(x.ne, y.ne);
-    buf_swap(x.key, y.key); buf_swap(x.key_off, y.key_off); buf_swap(x.ext, y.ext); buf_swap(x.ext_off, y.ext_off);
-    buf_swap(x.marker, y.marker); buf_swap(x.left, y.left); buf_swap(x.right, y.right);
+    std::swap(x.n, y.n); std::swap(x.words, y.words);
+    buf_swap(x.key, y.key); buf_swap(x.key_len, y.key_len); buf_swap(x.ext, y.ext); buf_swap(x.ext_off, y.ext_off);
+    buf_swap(x.ext_len, y.ext_len); buf_swap(x.marker, y.marker); buf_swap(x.left, y.left); buf_swap(x.right, y.right);
 }
 
-static int dyn_alloc(rfx_ctx *ctx, DynDev &d, int64_t n, int64_t nk, int64_t ne) {
-    RFX_HIP(d.key.alloc((size_t)std::max<int64_t>(nk, 1), ctx->stream));
-    RFX_HIP(d.ext.alloc((size_t)std::max<int64_t>(ne, 1), ctx->stream));
-    RFX_HIP(d.key_off.alloc((size_t)(n + 1) * 8, ctx->stream));
+static int dyn_alloc(rfx_ctx *ctx, DynDev &d, int64_t n, int64_t words) {
+    const size_t m = (size_t)std::max<int64_t>(n, 1);
+    RFX_HIP(d.key.alloc(m * DYN_KW * 8, ctx->stream));
+    RFX_HIP(d.key_len.alloc(m, ctx->stream));
+    RFX_HIP(d.ext.alloc((size_t)std::max<int64_t>(words, 1) * 8, ctx->stream));
     RFX_HIP(d.ext_off.alloc((size_t)(n + 1) * 8, ctx->stream));
-    RFX_HIP(d.marker.alloc((size_t)std::max<int64_t>(n, 1) * 4, ctx->stream));
-    RFX_HIP(d.left.alloc((size_t)std::max<int64_t>(n, 1) * 4, ctx->stream));
-    RFX_HIP(d.right.alloc((size_t)std::max<int64_t>(n, 1) * 4, ctx->stream));
-    d.n = n; d.nk = nk; d.ne = ne;
+    RFX_HIP(d.ext_len.alloc(m * 4, ctx->stream));
+    RFX_HIP(d.marker.alloc(m * 4, ctx->stream));
+    RFX_HIP(d.left.alloc(m * 4, ctx->stream));
+    RFX_HIP(d.right.alloc(m * 4, ctx->stream));
+    d.n = n; d.words = words;
     return RFX_OK;
 }
 
-__device__ __forceinline__ uint64_t dyn_block(const uint8_t *s, int n, int j) {
-    uint64_t x = 0;
-    const int b0 = 31 * j;
-    int m = n - b0;
-    if (m > 31) m = 31;
-    for (int i = 0; i < m; i++) x |= (uint64_t)s[b0 + i] << (2 * (31 - i));
-    if (b0 + 31 >= n) x |= 1ULL << (2 * (31 - m));
-    return x;
+// ---- words ----------------------------------------------------------------------------------------------------------------
+// the first m of 32 bases, the rest 0
+__device__ __forceinline__ uint64_t dyn_keep(uint64_t x, int m) { return m >= 32 ? x : m <= 0 ? 0ull : x & ~(~0ull >> (2 * m)); }
+// the 32 bases that start at base t of one packed segment of len bases (t < 0: the segment begins -t bases into the window);
+// 0 where the segment has no base -- the zero padding of the layout does the masking
+__device__ __forceinline__ uint64_t dyn_seg32(const uint64_t *__restrict__ w, int len, int t) {
+    if (len <= 0 || t >= len || t <= -32) return 0ull;
+    if (t < 0) return w[0] >> (2 * -t);
+    const int wi = t >> 5, sh = (t & 31) * 2;
+    uint64_t r = w[wi] << sh;
+    if (sh && wi + 1 < ((len + 31) >> 5)) r |= w[wi + 1] >> (64 - sh);
+    return r;
+}
+// up to three packed segments, each a word pointer and a length in bases: key + ext, ext + key, P + L + S of a merge
+struct DynCat { const uint64_t *w0, *w1, *w2; int l0, l1, l2; };
+// the 32 bases that start at base t of the concatenation (0 past its end)
+__device__ __forceinline__ uint64_t dyn_cat32(const DynCat &c, int t) {
+    return dyn_seg32(c.w0, c.l0, t) | dyn_seg32(c.w1, c.l1, t - c.l0) | dyn_seg32(c.w2, c.l2, t - c.l0 - c.l1);
+}
+// the first n (<= 124) bases of two keys are equal: whole words, then one masked word
+__device__ __forceinline__ bool dyn_prefix_equal(const uint64_t *__restrict__ a, const uint64_t *__restrict__ b, int n) {
+    if (n > DYN_MAXK) n = DYN_MAXK;
+    const int fw = n >> 5, r = n & 31;
+    for (int j = 0; j < DYN_KW - 1; j++) if (j < fw && a[j] != b[j]) return false;
+    return r == 0 || dyn_keep(a[fw] ^ b[fw], r) == 0;
+}
+__device__ __forceinline__ bool dyn_keys_equal(const uint64_t *__restrict__ key, const uint8_t *__restrict__ len, int64_t a, int64_t b) {
+    const uint64_t *x = key + DYN_KW * a, *y = key + DYN_KW * b;
+    return len[a] == len[b] && x[0] == y[0] && x[1] == y[1] && x[2] == y[2] && x[3] == y[3];
+}
+// the largest i < n with off[i] <= x (off[0] = 0 <= x): the record that owns word / byte x; records of size 0 are skipped
+template <class T>
+__device__ __forceinline__ int64_t dyn_find(const T *__restrict__ off, int64_t n, int64_t x) {
+    int64_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int64_t)off[mid] <= x) lo = mid; else hi = mid;
+    }
+    return lo;
 }
 
-// sort keys: block j with the sign bit flipped (Spark compares signed longs), 0 past the last block; the block count
-__global__ __launch_bounds__(256) void k_dyn_blocks(const uint8_t *__restrict__ key, const int64_t *__restrict__ off, int64_t n,
-                                                    uint64_t *__restrict__ blk /* [DYN_MAXB][n] */, uint64_t *__restrict__ nblk,
-                                                    uint32_t *__restrict__ perm, int *__restrict__ too_long, uint32_t *__restrict__ min_len) {
+// flags of a call, in HBM: [0] a key longer than 124 bases, [1] the shortest key, [2] the longest key, [3] a malformed input
+// (offsets that run backwards), [4..5] a 64-bit total put there by k_dyn_put_total: one small read-back for all of them
+struct DynFlags { uint32_t too_long, min_len, max_len, bad; uint64_t total; };
+static int dyn_flags_init(rfx_ctx *ctx, DevBuf &flags) {
+    RFX_HIP(flags.alloc(sizeof(DynFlags), ctx->stream));
+    RFX_HIP(hipMemsetAsync(flags.p, 0, sizeof(DynFlags), ctx->stream));
+    RFX_HIP(hipMemsetAsync((char *)flags.p + 4, 0xFF, 4, ctx->stream));
+    return RFX_OK;
+}
+__global__ void k_dyn_put_total(const uint64_t *__restrict__ src, uint32_t *__restrict__ flags) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) ((uint64_t *)flags)[2] = *src;
+}
+static int dyn_flags_read(rfx_ctx *ctx, const DevBuf &flags, const uint64_t *d_total, DynFlags *h) {
+    if (d_total) {
+        hipLaunchKernelGGL(k_dyn_put_total, dim3(1), dim3(1), 0, ctx->stream, d_total, flags.as<uint32_t>());
+        RFX_HIP(hipGetLastError());
+    }
+    return small_readback(ctx, h, flags.p, sizeof(DynFlags));
+}
+__device__ __forceinline__ void dyn_note_lengths(uint32_t *__restrict__ flags, bool live, int len) {
+    uint32_t lo = live ? (uint32_t)len : 0xFFFFFFFFu, hi = live ? (uint32_t)len : 0u;
+    for (int d = 32; d > 0; d >>= 1) {
+        lo = min(lo, (uint32_t)__shfl_xor((int)lo, d, 64));
+        hi = max(hi, (uint32_t)__shfl_xor((int)hi, d, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (lo != 0xFFFFFFFFu) atomicMin(flags + 1, lo);
+        atomicMax(flags + 2, hi);
+        if (hi > (uint32_t)DYN_MAXK) atomicOr(flags, 1u);
+    }
+}
+
+// block j of a key from its words: bases 31 j .. 31 j + 30 in bits 63..2, the 01 terminator behind the last base of the last
+// block (bit 0 when that block is full) -- what Row carries and rfx_dyn_bases_to_blocks writes
+__device__ __forceinline__ uint64_t dyn_block(const uint64_t *__restrict__ w, int len, int j) {
+    const int b0 = 31 * j;
+    int m = len - b0;
+    if (m > 31) m = 31;
+    uint64_t x = dyn_seg32(w, len, b0) & ~3ull;
+    if (b0 + 31 >= len) x |= 1ull << (2 * (31 - m));
+    return x;
+}
+// sort keys: block j with the sign bit flipped (Spark compares signed longs), 0 past the last block; the block count; and the
+// set's shortest and longest key.  blk == nullptr: the lengths only (the operators that do not sort)
+__global__ __launch_bounds__(256) void k_dyn_keys(const uint64_t *__restrict__ key, const uint8_t *__restrict__ key_len, int64_t n,
+                                                  uint64_t *__restrict__ blk /* [DYN_MAXB][n] */, uint64_t *__restrict__ nblk,
+                                                  uint32_t *__restrict__ perm, uint32_t *__restrict__ flags) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int len = (int)(off[i + 1] - off[i]);
-    const int nb = len <= 0 ? 1 : (len - 1) / 31 + 1;
-    if (nb > DYN_MAXB) { *too_long = 1; }
-    const uint8_t *s = key + off[i];
-    for (int j = 0; j < DYN_MAXB; j++) blk[(int64_t)j * n + i] = j < nb ? (dyn_block(s, len, j) ^ 0x8000000000000000ull) : 0ull;
+    const bool live = i < n;
+    const int len = live ? (int)key_len[i] : 0;
+    dyn_note_lengths(flags, live, len);
+    if (!live || !blk) return;
+    const int use = len > DYN_MAXK ? DYN_MAXK : len;
+    const int nb = use <= 0 ? 1 : (use - 1) / 31 + 1;
+    const uint64_t *w = key + DYN_KW * i;
+    for (int j = 0; j < DYN_MAXB; j++) blk[(int64_t)j * n + i] = j < nb ? (dyn_block(w, use, j) ^ 0x8000000000000000ull) : 0ull;
     nblk[i] = (uint64_t)nb;
     perm[i] = (uint32_t)i;
-    atomicMin(min_len, (uint32_t)len);
 }
 __global__ __launch_bounds__(256) void k_dyn_gather_u64(const uint64_t *__restrict__ src, const uint32_t *__restrict__ perm, int64_t n,
                                                         uint64_t *__restrict__ dst) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = src[perm[i]];
 }
-// record sizes through a permutation (for the scans of the gather)
-__global__ __launch_bounds__(256) void k_dyn_perm_sizes(const int64_t *__restrict__ koff, const int64_t *__restrict__ eoff,
-                                                        const uint32_t *__restrict__ perm, int64_t n, uint64_t *__restrict__ ks,
-                                                        uint64_t *__restrict__ es) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t p = perm[i];
-    ks[i] = (uint64_t)(koff[p + 1] - koff[p]);
-    es[i] = (uint64_t)(eoff[p + 1] - eoff[p]);
-}
-__global__ __launch_bounds__(256) void k_dyn_gather(const uint8_t *__restrict__ key, const int64_t *__restrict__ koff,
-                                                    const uint8_t *__restrict__ ext, const int64_t *__restrict__ eoff,
-                                                    const int32_t *__restrict__ marker, const int32_t *__restrict__ left,
-                                                    const int32_t *__restrict__ right, const uint32_t *__restrict__ perm, int64_t n,
-                                                    const uint64_t *__restrict__ nko, const uint64_t *__restrict__ neo, uint8_t *__restrict__ okey,
-                                                    int64_t *__restrict__ okoff, uint8_t *__restrict__ oext, int64_t *__restrict__ oeoff,
-                                                    int32_t *__restrict__ omarker, int32_t *__restrict__ oleft, int32_t *__restrict__ oright) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > n) return;
-    if (i == n) { okoff[n] = (int64_t)nko[n]; oeoff[n] = (int64_t)neo[n]; return; }
-    const uint32_t p = perm[i];
-    const int64_t kb = koff[p], kn = koff[p + 1] - kb, eb = eoff[p], en = eoff[p + 1] - eb;
-    const int64_t ko = (int64_t)nko[i], eo = (int64_t)neo[i];
-    okoff[i] = ko; oeoff[i] = eo;
-    for (int64_t j = 0; j < kn; j++) okey[ko + j] = key[kb + j];
-    for (int64_t j = 0; j < en; j++) oext[eo + j] = ext[eb + j];
-    omarker[i] = marker[p]; oleft[i] = left[p]; oright[i] = right[p];
-}
 
-__device__ __forceinline__ bool dyn_keys_equal(const uint8_t *key, const int64_t *off, int64_t a, int64_t b) {
-    const int64_t la = off[a + 1] - off[a], lb = off[b + 1] - off[b];
-    if (la != lb) return false;
-    const uint8_t *x = key + off[a], *y = key + off[b];
-    for (int64_t j = 0; j < la; j++) if (x[j] != y[j]) return false;
-    return true;
-}
 // logical partition p starts at floor(p*n/P), moved forward past equal keys (the order contract)
-__global__ void k_dyn_part_starts(const uint8_t *__restrict__ key, const int64_t *__restrict__ off, int64_t n, int P, int64_t *__restrict__ ps) {
+__global__ void k_dyn_part_starts(const uint64_t *__restrict__ key, const uint8_t *__restrict__ key_len, int64_t n, int P, int64_t *__restrict__ ps) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     int64_t prev = 0;
     for (int p = 0; p < P; p++) {
         int64_t s = (int64_t)p * n / P;
         if (s < prev) s = prev;
-        while (s > 0 && s < n && dyn_keys_equal(key, off, s, s - 1)) s++;
+        while (s > 0 && s < n && dyn_keys_equal(key, key_len, s, s - 1)) s++;
         ps[p] = s; prev = s;
     }
     ps[P] = n;
 }
 
 // a row heads a family when it opens a partition or differs from its predecessor inside the first lmin bases
-__global__ __launch_bounds__(256) void k_dyn_heads(const uint8_t *__restrict__ key, const int64_t *__restrict__ off, int64_t n,
-                                                   const int64_t *__restrict__ ps, int P, uint32_t lmin, uint32_t *__restrict__ head) {
+__global__ __launch_bounds__(256) void k_dyn_heads(const uint64_t *__restrict__ key, int64_t n, const int64_t *__restrict__ ps, int P,
+                                                   uint32_t lmin, uint32_t *__restrict__ head) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     bool h = i == 0;
     for (int p = 0; p <= P && !h; p++) h = ps[p] == i;
-    if (!h) {
-        const uint8_t *a = key + off[i], *b = key + off[i - 1];
-        for (uint32_t j = 0; j < lmin && !h; j++) h = a[j] != b[j];
-    }
+    if (!h) h = !dyn_prefix_equal(key + DYN_KW * i, key + DYN_KW * (i - 1), (int)lmin);
     head[i] = h ? 1u : 0u;
 }
 
 // an emission: the source record(s) and what is done with them (the orientation is decided by the emission's rank)
-struct DynDesc { int32_t kind; int32_t bubble; int64_t a, b; };    // kind 0: flip record a; 1: merge forward a + reflected b
+struct DynDesc { int32_t kind; int32_t bubble; int64_t a, b; };    // kind 0: flip record a; 1: merge forward a + reflected b; 2: copy a
 
-struct DynRow { const uint8_t *key; int klen; int elen; int marker, left, right; int64_t idx; };
+struct DynRow { const uint64_t *key; int klen; int elen; int marker, left, right; int64_t idx; };
 
-__device__ __forceinline__ DynRow dyn_row(const uint8_t *key, const int64_t *koff, const int64_t *eoff, const int32_t *marker,
-                                          const int32_t *left, const int32_t *right, int64_t q) {
+__device__ __forceinline__ DynRow dyn_row(const DynView &v, int64_t q) {
     DynRow r;
-    r.key = key + koff[q]; r.klen = (int)(koff[q + 1] - koff[q]); r.elen = (int)(eoff[q + 1] - eoff[q]);
-    r.marker = marker[q]; r.left = left[q]; r.right = right[q]; r.idx = q;
+    r.key = v.key + DYN_KW * q; r.klen = (int)v.key_len[q]; r.elen = v.ext_len[q];
+    r.marker = v.marker[q]; r.left = v.left[q]; r.right = v.right[q]; r.idx = q;
     return r;
 }
+// equal, or one a prefix of the other
 __device__ __forceinline__ bool dyn_related(const DynRow &a, const DynRow &b) {
-    const int n = a.klen < b.klen ? a.klen : b.klen;
-    for (int j = 0; j < n; j++) if (a.key[j] != b.key[j]) return false;
-    return true;
+    return dyn_prefix_equal(a.key, b.key, a.klen < b.klen ? a.klen : b.klen);
 }
 
 // DSExtendReflexivKmer.call (FirstFour:1603-1763) / DSExtendReflexivKmerToArrayLoop.call (Iteration:487-...) over one family.
 // WRITE = false: counts the family's emissions into cnt[head]; WRITE = true: writes descriptors at base[head] + rank.
 template <bool WRITE>
-__global__ __launch_bounds__(128) void k_dyn_walk(const uint8_t *__restrict__ key, const int64_t *__restrict__ koff,
-                                                  const int64_t *__restrict__ eoff, const int32_t *__restrict__ marker,
-                                                  const int32_t *__restrict__ left, const int32_t *__restrict__ right, int64_t n,
-                                                  const uint32_t *__restrict__ head, int stage, int start_iteration, uint32_t *__restrict__ cnt,
-                                                  const uint64_t *__restrict__ base, DynDesc *__restrict__ desc) {
+__global__ __launch_bounds__(128) void k_dyn_walk(const DynView v, int64_t n, const uint32_t *__restrict__ head, int stage, int start_iteration,
+                                                  uint32_t *__restrict__ cnt, const uint64_t *__restrict__ base, DynDesc *__restrict__ desc) {
     const int64_t q0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q0 >= n) return;
     if (!head[q0]) { if (!WRITE) cnt[q0] = 0; return; }
@@ -184,7 +241,7 @@ __global__ __launch_bounds__(128) void k_dyn_walk(const uint8_t *__restrict__ ke
     bool have = false;
     DynRow h{};
     for (int64_t q = q0; q < n && (q == q0 || !head[q]); q++) {
-        const DynRow s = dyn_row(key, koff, eoff, marker, left, right, q);
+        const DynRow s = dyn_row(v, q);
         if (!have) { h = s; have = true; continue; }
         if (!dyn_related(s, h)) { emit(0, h.idx, -1, 0); h = s; continue; }
         if (s.marker == h.marker) { emit(0, s.idx, -1, 0); continue; }
@@ -226,7 +283,7 @@ __global__ __launch_bounds__(128) void k_dyn_walk(const uint8_t *__restrict__ ke
 __device__ __forceinline__ int32_t dyn_clamp(int32_t v) { return v >= 30000 ? 30000 : v <= -30000 ? -30000 : v; }
 
 // emission e of partition p (pbase[p] = rank of the partition's first emission) goes out in orientation
-// m = start_marker toggled (e - pbase[p]) times; sizes first, then the bases
+// m = start_marker toggled (e - pbase[p]) times
 __device__ __forceinline__ int dyn_orientation(int64_t e, const uint64_t *pbase, int P, int start_marker) {
     int p = 0;
     for (int t = 1; t < P; t++) if ((int64_t)pbase[t] <= e) p = t;          // the last partition that starts at or before e
@@ -234,97 +291,106 @@ __device__ __forceinline__ int dyn_orientation(int64_t e, const uint64_t *pbase,
     return (r & 1) ? 3 - start_marker : start_marker;
 }
 
-__global__ __launch_bounds__(256) void k_dyn_sizes(const DynDesc *__restrict__ desc, int64_t ne, const int64_t *__restrict__ koff,
-                                                   const int64_t *__restrict__ eoff, uint64_t *__restrict__ ks, uint64_t *__restrict__ es) {
+// what output record e is made of: key' = bases [kstart, kstart + klen) and ext' = bases [estart, estart + elen) of a
+// concatenation.  singleKmerRandomizer (FirstFour:1857-1930) / reflexivExtend (:1957-2120):
+//   flip 1 -> 2   key + ext:   key' = its last |key| bases, ext' = its first |ext|   (any lengths, as Iteration's array form;
+//   flip 2 -> 1   ext + key:   key' = its first |key| bases, ext' = the rest          FirstFour's single-long form is the same
+//   no flip, copy key + ext:   as they are                                            while |ext| <= |key|)
+//   merge         P + L + S (reflected extension, the longer key, forward extension):
+//                 m = 2: key' = the last |L| bases, ext' = the rest;  m = 1: key' = the first |L| bases, ext' = the rest
+struct DynPlan { DynCat c; int kstart, klen, estart, elen; };
+__device__ __forceinline__ const uint64_t *dyn_ext_ptr(const DynView &v, int64_t q) { return v.ext + v.ext_off[q]; }
+__device__ __forceinline__ DynPlan dyn_plan(const DynView &v, const DynDesc d, int m) {
+    DynPlan p;
+    if (d.kind != 1) {
+        const int kl = (int)v.key_len[d.a], el = v.ext_len[d.a], mk = v.marker[d.a];
+        const uint64_t *K = v.key + DYN_KW * d.a, *E = dyn_ext_ptr(v, d.a);
+        p.klen = kl; p.elen = el;
+        p.c.w2 = nullptr; p.c.l2 = 0;
+        if (d.kind == 0 && mk == 1 && m == 2) { p.c.w0 = K; p.c.l0 = kl; p.c.w1 = E; p.c.l1 = el; p.kstart = el; p.estart = 0; }
+        else if (d.kind == 0 && mk == 2 && m == 1) { p.c.w0 = E; p.c.l0 = el; p.c.w1 = K; p.c.l1 = kl; p.kstart = 0; p.estart = kl; }
+        else { p.c.w0 = K; p.c.l0 = kl; p.c.w1 = E; p.c.l1 = el; p.kstart = 0; p.estart = kl; }
+        return p;
+    }
+    const int64_t f = d.a, r = d.b;
+    const int kf = (int)v.key_len[f], kr = (int)v.key_len[r];
+    const int S = v.ext_len[f], Pn = v.ext_len[r];
+    const int Ln = kf >= kr ? kf : kr;
+    p.c.w0 = dyn_ext_ptr(v, r); p.c.l0 = Pn;
+    p.c.w1 = v.key + DYN_KW * (kf >= kr ? f : r); p.c.l1 = Ln;
+    p.c.w2 = dyn_ext_ptr(v, f); p.c.l2 = S;
+    p.klen = Ln; p.elen = Pn + S;
+    if (m == 2) { p.kstart = Pn + S; p.estart = 0; } else { p.kstart = 0; p.estart = Ln; }
+    return p;
+}
+
+// lengths, attributes and extension words of every emission (the bubble arithmetic of the merge is here)
+__global__ __launch_bounds__(256) void k_dyn_sizes(const DynDesc *__restrict__ desc, int64_t ne, const DynView v, const uint64_t *__restrict__ pbase,
+                                                   int P, int start_marker, const DynOut o, uint32_t *__restrict__ ew) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= ne) return;
     const DynDesc d = desc[e];
-    if (d.kind == 0) {
-        ks[e] = (uint64_t)(koff[d.a + 1] - koff[d.a]);
-        es[e] = (uint64_t)(eoff[d.a + 1] - eoff[d.a]);
-    } else {
-        const int64_t kf = koff[d.a + 1] - koff[d.a], kr = koff[d.b + 1] - koff[d.b];
-        ks[e] = (uint64_t)(kf >= kr ? kf : kr);                  // the longer key's length is kept
-        es[e] = (uint64_t)((eoff[d.a + 1] - eoff[d.a]) + (eoff[d.b + 1] - eoff[d.b]));
-    }
-}
-
-// singleKmerRandomizer (FirstFour:1857-1930) / reflexivExtend (:1957-2120) at base level: output record e
-__global__ __launch_bounds__(256) void k_dyn_emit(const DynDesc *__restrict__ desc, int64_t ne, const uint8_t *__restrict__ key,
-                                                  const int64_t *__restrict__ koff, const uint8_t *__restrict__ ext,
-                                                  const int64_t *__restrict__ eoff, const int32_t *__restrict__ marker,
-                                                  const int32_t *__restrict__ left, const int32_t *__restrict__ right,
-                                                  const uint64_t *__restrict__ pbase, int P, int start_marker, const uint64_t *__restrict__ oko,
-                                                  const uint64_t *__restrict__ oeo, uint8_t *__restrict__ okey, int64_t *__restrict__ okoff,
-                                                  uint8_t *__restrict__ oext, int64_t *__restrict__ oeoff, int32_t *__restrict__ omarker,
-                                                  int32_t *__restrict__ oleft, int32_t *__restrict__ oright) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e > ne) return;
-    if (e == ne) { okoff[ne] = (int64_t)oko[ne]; oeoff[ne] = (int64_t)oeo[ne]; return; }
-    const DynDesc d = desc[e];
-    const int m = dyn_orientation(e, pbase, P, start_marker);
-    uint8_t *ok = okey + oko[e], *oe = oext + oeo[e];
-    okoff[e] = (int64_t)oko[e]; oeoff[e] = (int64_t)oeo[e];
-    if (d.kind == 0) {
-        const uint8_t *K = key + koff[d.a], *E = ext + eoff[d.a];
-        const int kl = (int)(koff[d.a + 1] - koff[d.a]), el = (int)(eoff[d.a + 1] - eoff[d.a]);
-        const int mk = marker[d.a];
-        oleft[e] = left[d.a]; oright[e] = right[d.a];
-        // (any lengths, as Iteration's array form: combined = key + ext, key' = combined[|ext|:], ext' = combined[:|ext|]; the
-        // reflected record the other way round.  FirstFour's single-long form is the same while |ext| <= |key|.)
-        if (mk == 1 && m == 2) {
-            auto c = [&](int t) -> uint8_t { return t < kl ? K[t] : E[t - kl]; };
-            for (int j = 0; j < kl; j++) ok[j] = c(el + j);
-            for (int j = 0; j < el; j++) oe[j] = c(j);
-            omarker[e] = 2;
-        } else if (mk == 2 && m == 1) {
-            auto c = [&](int t) -> uint8_t { return t < el ? E[t] : K[t - el]; };
-            for (int j = 0; j < kl; j++) ok[j] = c(j);
-            for (int j = 0; j < el; j++) oe[j] = c(kl + j);
-            omarker[e] = 1;
-        } else {
-            for (int j = 0; j < kl; j++) ok[j] = K[j];
-            for (int j = 0; j < el; j++) oe[j] = E[j];
-            omarker[e] = mk;
-        }
+    const int m = d.kind == 2 ? 0 : dyn_orientation(e, pbase, P, start_marker);
+    if (d.kind != 1) {
+        const int kl = (int)v.key_len[d.a], el = v.ext_len[d.a], mk = v.marker[d.a];
+        o.key_len[e] = (uint8_t)kl; o.ext_len[e] = el; ew[e] = (uint32_t)((el + 31) >> 5);
+        o.left[e] = v.left[d.a]; o.right[e] = v.right[d.a];
+        o.marker[e] = (d.kind == 0 && mk == 1 && m == 2) ? 2 : (d.kind == 0 && mk == 2 && m == 1) ? 1 : mk;
         return;
     }
-    // merge: forward a + reflected b; the longer key L is kept; whole = P + L + S
     const int64_t f = d.a, r = d.b;
-    const int kf = (int)(koff[f + 1] - koff[f]), kr = (int)(koff[r + 1] - koff[r]);
-    const int S = (int)(eoff[f + 1] - eoff[f]), Pn = (int)(eoff[r + 1] - eoff[r]);
-    const uint8_t *L = kf >= kr ? key + koff[f] : key + koff[r];
-    const int Ln = kf >= kr ? kf : kr;
-    const uint8_t *Sx = ext + eoff[f], *Px = ext + eoff[r];
+    const int kf = (int)v.key_len[f], kr = (int)v.key_len[r];
+    const int S = v.ext_len[f], Pn = v.ext_len[r];
     const int extra = kf > kr ? kf - kr : 0;
+    const int lf_f = v.left[f], lf_r = v.left[r], rt_f = v.right[f], rt_r = v.right[r];
     int lf, rt;
     if (d.bubble < 0) {
-        lf = left[r] >= 0 ? left[r] : left[f] - Pn;
-        rt = right[f] >= 0 ? right[f] : right[r] - S - extra;
-    } else if (left[f] > 0) {
+        lf = lf_r >= 0 ? lf_r : lf_f - Pn;
+        rt = rt_f >= 0 ? rt_f : rt_r - S - extra;
+    } else if (lf_f > 0) {
         lf = d.bubble;
-        rt = right[f] >= 0 ? right[f] : right[r] - S - extra;
+        rt = rt_f >= 0 ? rt_f : rt_r - S - extra;
     } else {
-        lf = left[r] >= 0 ? left[r] : left[f] - Pn;
+        lf = lf_r >= 0 ? lf_r : lf_f - Pn;
         rt = d.bubble - extra;
     }
-    oleft[e] = dyn_clamp(lf); oright[e] = dyn_clamp(rt);
-    omarker[e] = m;
-    // position t of whole = P + L + S
-    auto whole = [&](int t) -> uint8_t { return t < Pn ? Px[t] : t < Pn + Ln ? L[t - Pn] : Sx[t - Pn - Ln]; };
-    if (m == 2) {                                                  // key' = (L + S)[|S|:], ext' = P + (L + S)[:|S|]
-        for (int j = 0; j < Ln; j++) ok[j] = whole(Pn + S + j);
-        for (int j = 0; j < Pn + S; j++) oe[j] = whole(j);
-    } else {                                                       // key' = (P + L)[:|L|], ext' = (P + L)[|L|:] + S
-        for (int j = 0; j < Ln; j++) ok[j] = whole(j);
-        for (int j = 0; j < Pn + S; j++) oe[j] = whole(Ln + j);
-    }
+    o.left[e] = dyn_clamp(lf); o.right[e] = dyn_clamp(rt); o.marker[e] = m;
+    o.key_len[e] = (uint8_t)(kf >= kr ? kf : kr);               // the longer key's length is kept
+    o.ext_len[e] = Pn + S; ew[e] = (uint32_t)((Pn + S + 31) >> 5);
+}
+// one thread per output key word: all DYN_KW words of every record are written, the unused ones as 0
+__global__ __launch_bounds__(256) void k_dyn_emit_key(const DynDesc *__restrict__ desc, int64_t ne, const DynView v, const uint64_t *__restrict__ pbase,
+                                                      int P, int start_marker, uint64_t *__restrict__ okey) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ne * DYN_KW) return;
+    const int64_t e = t / DYN_KW;
+    const int j = (int)(t % DYN_KW);
+    const DynDesc d = desc[e];
+    const DynPlan p = dyn_plan(v, d, d.kind == 2 ? 0 : dyn_orientation(e, pbase, P, start_marker));
+    okey[t] = dyn_keep(dyn_cat32(p.c, p.kstart + 32 * j), p.klen - 32 * j);
+}
+// one thread per output extension word; its record through the scan of the word counts.  The grid covers the input's word
+// bound; the exact total is oeoff[ne]
+__global__ __launch_bounds__(256) void k_dyn_emit_ext(const DynDesc *__restrict__ desc, int64_t ne, const DynView v, const uint64_t *__restrict__ pbase,
+                                                      int P, int start_marker, const int64_t *__restrict__ oeoff, uint64_t *__restrict__ oext) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ne <= 0 || w >= oeoff[ne]) return;
+    const int64_t e = dyn_find(oeoff, ne, w);
+    const int j = (int)(w - oeoff[e]);
+    const DynDesc d = desc[e];
+    const DynPlan p = dyn_plan(v, d, d.kind == 2 ? 0 : dyn_orientation(e, pbase, P, start_marker));
+    oext[w] = dyn_keep(dyn_cat32(p.c, p.estart + 32 * j), p.elen - 32 * j);
 }
 
 // DSkmerRandomReflection.call (FirstFour:2518-2524): row q of partition p in orientation 2, 1, 2, ... by its rank
 __global__ __launch_bounds__(256) void k_dyn_identity_desc(int64_t n, DynDesc *__restrict__ desc) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) desc[i] = DynDesc{0, 0, i, -1};
+}
+// the gather behind the sort: output record i is a copy of record perm[i]
+__global__ __launch_bounds__(256) void k_dyn_perm_desc(const uint32_t *__restrict__ perm, int64_t n, DynDesc *__restrict__ desc) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) desc[i] = DynDesc{2, 0, (int64_t)perm[i], -1};
 }
 __global__ void k_dyn_copy_u64(const int64_t *__restrict__ src, int n, uint64_t *__restrict__ dst) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -340,127 +406,89 @@ __global__ void k_dyn_pbase(const int64_t *__restrict__ ps, int P, const uint64_
     if (out_ps) out_ps[p] = (int64_t)v;
 }
 
-static int dyn_upload(rfx_ctx *ctx, const rfx_dyn_records *h, DynDev &d) {
-    const int64_t n = h->n;
-    const int64_t nk = n ? h->key_off[n] : 0, ne = n ? h->ext_off[n] : 0;
-    RFX_TRY(dyn_alloc(ctx, d, n, nk, ne));
-    if (nk) RFX_HIP(hipMemcpyAsync(d.key.p, h->key, (size_t)nk, hipMemcpyHostToDevice, ctx->stream));
-    if (ne) RFX_HIP(hipMemcpyAsync(d.ext.p, h->ext, (size_t)ne, hipMemcpyHostToDevice, ctx->stream));
-    if (n) {
-        RFX_HIP(hipMemcpyAsync(d.key_off.p, h->key_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        RFX_HIP(hipMemcpyAsync(d.ext_off.p, h->ext_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        RFX_HIP(hipMemcpyAsync(d.marker.p, h->marker, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-        RFX_HIP(hipMemcpyAsync(d.left.p, h->left, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-        RFX_HIP(hipMemcpyAsync(d.right.p, h->right, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        RFX_HIP(hipMemsetAsync(d.key_off.p, 0, 8, ctx->stream));
-        RFX_HIP(hipMemsetAsync(d.ext_off.p, 0, 8, ctx->stream));
-    }
-    return RFX_OK;
-}
-static int dyn_download(rfx_ctx *ctx, const DynDev &d, rfx_dyn_records *h) {
-    h->n = d.n; h->need_key = d.nk; h->need_ext = d.ne;
-    if (d.n > h->cap_n || d.nk > h->cap_key || d.ne > h->cap_ext) return RFX_E_CAP;
-    if (d.nk) RFX_HIP(hipMemcpyAsync(h->key, d.key.p, (size_t)d.nk, hipMemcpyDeviceToHost, ctx->stream));
-    if (d.ne) RFX_HIP(hipMemcpyAsync(h->ext, d.ext.p, (size_t)d.ne, hipMemcpyDeviceToHost, ctx->stream));
-    RFX_HIP(hipMemcpyAsync(h->key_off, d.key_off.p, (size_t)(d.n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    RFX_HIP(hipMemcpyAsync(h->ext_off, d.ext_off.p, (size_t)(d.n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (d.n) {
-        RFX_HIP(hipMemcpyAsync(h->marker, d.marker.p, (size_t)d.n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        RFX_HIP(hipMemcpyAsync(h->left, d.left.p, (size_t)d.n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        RFX_HIP(hipMemcpyAsync(h->right, d.right.p, (size_t)d.n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    RFX_TRY(sync_checked(ctx));
-    return RFX_OK;
-}
-
-// the entries that form no blocks refuse a key the sort would refuse (more than DYN_MAXB blocks), before anything is written
-static int dyn_keys_within_limit(rfx_ctx *ctx, const rfx_dyn_records *h) {
-    for (int64_t i = 0; i < h->n; i++)
-        if (h->key_off[i + 1] - h->key_off[i] > 31 * DYN_MAXB) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
-    return RFX_OK;
-}
-
 #define GRID(n) dim3((unsigned)ceil_div(std::max<int64_t>((n), 1), 256)), dim3(256), 0, ctx->stream
+
+// descriptors -> the output record set; no host wait: the output is bounded by the input (ne <= in.n emissions of a pass,
+// in.words extension words)
+static int dyn_emit(rfx_ctx *ctx, const DynDev &in, const DevBuf &desc, int64_t ne, const uint64_t *d_pbase, int P, int start_marker, DynDev &out) {
+    DevBuf ew;
+    RFX_HIP(ew.alloc((size_t)std::max<int64_t>(ne, 1) * 4, ctx->stream));
+    RFX_TRY(dyn_alloc(ctx, out, ne, in.words));
+    const DynView v = dyn_view(in);
+    if (ne > 0) {
+        hipLaunchKernelGGL(k_dyn_sizes, GRID(ne), (const DynDesc *)desc.as<DynDesc>(), ne, v, d_pbase, P, start_marker, dyn_out(out), ew.as<uint32_t>());
+        RFX_HIP(hipGetLastError());
+    }
+    RFX_TRY(exclusive_scan_u32_to_u64(ctx, ew.as<uint32_t>(), out.ext_off.as<uint64_t>(), ne));
+    if (ne > 0) {
+        hipLaunchKernelGGL(k_dyn_emit_key, GRID(ne * DYN_KW), (const DynDesc *)desc.as<DynDesc>(), ne, v, d_pbase, P, start_marker, out.key.as<uint64_t>());
+        RFX_HIP(hipGetLastError());
+        if (in.words > 0) {
+            hipLaunchKernelGGL(k_dyn_emit_ext, GRID(in.words), (const DynDesc *)desc.as<DynDesc>(), ne, v, d_pbase, P, start_marker,
+                               (const int64_t *)out.ext_off.as<int64_t>(), out.ext.as<uint64_t>());
+            RFX_HIP(hipGetLastError());
+        }
+    }
+    return RFX_OK;
+}
+
+// the set's key lengths without a sort: too long -> RFX_E_LIMIT; *lmin = the shortest key (0 for an empty set)
+static int dyn_check_lengths(rfx_ctx *ctx, const DynDev &in, uint32_t *lmin) {
+    *lmin = 0;
+    if (in.n == 0) return RFX_OK;
+    DevBuf flags;
+    RFX_TRY(dyn_flags_init(ctx, flags));
+    hipLaunchKernelGGL(k_dyn_keys, GRID(in.n), (const uint64_t *)in.key.as<uint64_t>(), (const uint8_t *)in.key_len.as<uint8_t>(), in.n,
+                       (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, flags.as<uint32_t>());
+    RFX_HIP(hipGetLastError());
+    DynFlags h{};
+    RFX_TRY(dyn_flags_read(ctx, flags, nullptr, &h));
+    if (h.too_long) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
+    *lmin = h.min_len;
+    return RFX_OK;
+}
 
 // sort("k-1") + the cut into P logical partitions: in -> out (sorted), d_ps[P + 1]; *lmin = the shortest key
 static int dyn_sort(rfx_ctx *ctx, const DynDev &in, int P, DynDev &out, DevBuf &d_ps, uint32_t *lmin) {
     const int64_t n = in.n;
     RFX_HIP(d_ps.alloc((size_t)(P + 1) * 8, ctx->stream));
-    RFX_TRY(dyn_alloc(ctx, out, n, in.nk, in.ne));
     *lmin = 0;
     if (n == 0) {
+        RFX_TRY(dyn_alloc(ctx, out, 0, 0));
         RFX_HIP(hipMemsetAsync(d_ps.p, 0, (size_t)(P + 1) * 8, ctx->stream));
-        RFX_HIP(hipMemsetAsync(out.key_off.p, 0, 8, ctx->stream));
         RFX_HIP(hipMemsetAsync(out.ext_off.p, 0, 8, ctx->stream));
         return RFX_OK;
     }
     if (n >= ((int64_t)1 << 32)) { ctx->last_error = "dynamic-k sort: more than 2^32 records"; return RFX_E_LIMIT; }
-    DevBuf blk, nblk, perm, tk, tv, keys, flags, ks, es, kso, eso;
+    DevBuf blk, nblk, perm, tk, tv, keys, flags, desc;
     RFX_HIP(blk.alloc((size_t)DYN_MAXB * n * 8, ctx->stream)); RFX_HIP(nblk.alloc((size_t)n * 8, ctx->stream));
     RFX_HIP(perm.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(tk.alloc((size_t)n * 8, ctx->stream)); RFX_HIP(tv.alloc((size_t)n * 4, ctx->stream));
-    RFX_HIP(keys.alloc((size_t)n * 8, ctx->stream)); RFX_HIP(flags.alloc(16, ctx->stream));
-    RFX_HIP(hipMemsetAsync(flags.p, 0, 4, ctx->stream));
-    RFX_HIP(hipMemsetAsync((char *)flags.p + 4, 0xFF, 4, ctx->stream));
-    hipLaunchKernelGGL(k_dyn_blocks, GRID(n), in.key.as<uint8_t>(), in.key_off.as<int64_t>(), n, blk.as<uint64_t>(), nblk.as<uint64_t>(),
-                       perm.as<uint32_t>(), flags.as<int>(), flags.as<uint32_t>() + 1);
+    RFX_HIP(keys.alloc((size_t)n * 8, ctx->stream));
+    RFX_TRY(dyn_flags_init(ctx, flags));
+    hipLaunchKernelGGL(k_dyn_keys, GRID(n), (const uint64_t *)in.key.as<uint64_t>(), (const uint8_t *)in.key_len.as<uint8_t>(), n, blk.as<uint64_t>(),
+                       nblk.as<uint64_t>(), perm.as<uint32_t>(), flags.as<uint32_t>());
     RFX_HIP(hipGetLastError());
-    // LSD: the block count (a proper prefix first when every shared block is equal), then block 3 .. block 0
-    for (int pass = -1; pass < DYN_MAXB; pass++) {
-        const uint64_t *src = pass < 0 ? nblk.as<uint64_t>() : blk.as<uint64_t>() + (int64_t)(DYN_MAXB - 1 - pass) * n;
+    DynFlags h{};
+    RFX_TRY(dyn_flags_read(ctx, flags, nullptr, &h));
+    if (h.too_long) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
+    *lmin = h.min_len;
+    // LSD: the block count (a proper prefix first when every shared block is equal), then the blocks, last to first.  A block
+    // no key of the set reaches is 0 for every record and a stable sort on it is the identity: skipped
+    const int nb_max = h.max_len == 0 ? 1 : ((int)h.max_len - 1) / 31 + 1;
+    for (int pass = -1; pass < nb_max; pass++) {
+        const uint64_t *src = pass < 0 ? nblk.as<uint64_t>() : blk.as<uint64_t>() + (int64_t)(nb_max - 1 - pass) * n;
+        if (pass < 0 && nb_max == 1) continue;                    // (every key has one block)
         hipLaunchKernelGGL(k_dyn_gather_u64, GRID(n), src, (const uint32_t *)perm.as<uint32_t>(), n, keys.as<uint64_t>());
         RFX_HIP(hipGetLastError());
         RFX_TRY(sort_pairs(ctx, keys.as<uint64_t>(), perm.as<uint32_t>(), n, pass < 0 ? 8 : 64, tk.as<uint64_t>(), tv.as<uint32_t>()));
     }
-    int h_flags[2] = {0, 0};
-    RFX_HIP(hipMemcpyAsync(h_flags, flags.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    RFX_TRY(sync_checked(ctx));
-    if (h_flags[0]) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
-    *lmin = (uint32_t)h_flags[1];
-    // gather the records through the permutation
-    RFX_HIP(ks.alloc((size_t)n * 8, ctx->stream)); RFX_HIP(es.alloc((size_t)n * 8, ctx->stream));
-    RFX_HIP(kso.alloc((size_t)(n + 1) * 8, ctx->stream)); RFX_HIP(eso.alloc((size_t)(n + 1) * 8, ctx->stream));
-    hipLaunchKernelGGL(k_dyn_perm_sizes, GRID(n), (const int64_t *)in.key_off.as<int64_t>(), (const int64_t *)in.ext_off.as<int64_t>(),
-                       (const uint32_t *)perm.as<uint32_t>(), n, ks.as<uint64_t>(), es.as<uint64_t>());
+    // gather the records through the permutation: the emission with "copy" descriptors
+    RFX_HIP(desc.alloc((size_t)n * sizeof(DynDesc), ctx->stream));
+    hipLaunchKernelGGL(k_dyn_perm_desc, GRID(n), (const uint32_t *)perm.as<uint32_t>(), n, desc.as<DynDesc>());
     RFX_HIP(hipGetLastError());
-    RFX_TRY(exclusive_scan_u64(ctx, ks.as<uint64_t>(), kso.as<uint64_t>(), n));
-    RFX_TRY(exclusive_scan_u64(ctx, es.as<uint64_t>(), eso.as<uint64_t>(), n));
-    hipLaunchKernelGGL(k_dyn_gather, GRID(n + 1), (const uint8_t *)in.key.as<uint8_t>(), (const int64_t *)in.key_off.as<int64_t>(),
-                       (const uint8_t *)in.ext.as<uint8_t>(), (const int64_t *)in.ext_off.as<int64_t>(), (const int32_t *)in.marker.as<int32_t>(),
-                       (const int32_t *)in.left.as<int32_t>(), (const int32_t *)in.right.as<int32_t>(), (const uint32_t *)perm.as<uint32_t>(), n,
-                       (const uint64_t *)kso.as<uint64_t>(), (const uint64_t *)eso.as<uint64_t>(), out.key.as<uint8_t>(), out.key_off.as<int64_t>(),
-                       out.ext.as<uint8_t>(), out.ext_off.as<int64_t>(), out.marker.as<int32_t>(), out.left.as<int32_t>(), out.right.as<int32_t>());
-    RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_dyn_part_starts, dim3(1), dim3(1), 0, ctx->stream, (const uint8_t *)out.key.as<uint8_t>(),
-                       (const int64_t *)out.key_off.as<int64_t>(), n, P, d_ps.as<int64_t>());
-    RFX_HIP(hipGetLastError());
-    RFX_TRY(sync_checked(ctx));
-    return RFX_OK;
-}
-
-// descriptors -> the output record set
-static int dyn_emit(rfx_ctx *ctx, const DynDev &in, const DevBuf &desc, int64_t ne, const DevBuf &pbase, int P, int start_marker, DynDev &out) {
-    DevBuf ks, es, kso, eso;
-    RFX_HIP(ks.alloc((size_t)std::max<int64_t>(ne, 1) * 8, ctx->stream)); RFX_HIP(es.alloc((size_t)std::max<int64_t>(ne, 1) * 8, ctx->stream));
-    RFX_HIP(kso.alloc((size_t)(ne + 1) * 8, ctx->stream)); RFX_HIP(eso.alloc((size_t)(ne + 1) * 8, ctx->stream));
-    if (ne > 0) {
-        hipLaunchKernelGGL(k_dyn_sizes, GRID(ne), (const DynDesc *)desc.as<DynDesc>(), ne, (const int64_t *)in.key_off.as<int64_t>(),
-                           (const int64_t *)in.ext_off.as<int64_t>(), ks.as<uint64_t>(), es.as<uint64_t>());
-        RFX_HIP(hipGetLastError());
-    }
-    RFX_TRY(exclusive_scan_u64(ctx, ks.as<uint64_t>(), kso.as<uint64_t>(), ne));
-    RFX_TRY(exclusive_scan_u64(ctx, es.as<uint64_t>(), eso.as<uint64_t>(), ne));
-    uint64_t tot[2] = {0, 0};
-    RFX_HIP(hipMemcpyAsync(&tot[0], kso.as<uint64_t>() + ne, 8, hipMemcpyDeviceToHost, ctx->stream));
-    RFX_HIP(hipMemcpyAsync(&tot[1], eso.as<uint64_t>() + ne, 8, hipMemcpyDeviceToHost, ctx->stream));
-    RFX_TRY(sync_checked(ctx));
-    RFX_TRY(dyn_alloc(ctx, out, ne, (int64_t)tot[0], (int64_t)tot[1]));
-    hipLaunchKernelGGL(k_dyn_emit, GRID(ne + 1), (const DynDesc *)desc.as<DynDesc>(), ne, (const uint8_t *)in.key.as<uint8_t>(),
-                       (const int64_t *)in.key_off.as<int64_t>(), (const uint8_t *)in.ext.as<uint8_t>(), (const int64_t *)in.ext_off.as<int64_t>(),
-                       (const int32_t *)in.marker.as<int32_t>(), (const int32_t *)in.left.as<int32_t>(), (const int32_t *)in.right.as<int32_t>(),
-                       (const uint64_t *)pbase.as<uint64_t>(), P, start_marker, (const uint64_t *)kso.as<uint64_t>(), (const uint64_t *)eso.as<uint64_t>(),
-                       out.key.as<uint8_t>(), out.key_off.as<int64_t>(), out.ext.as<uint8_t>(), out.ext_off.as<int64_t>(), out.marker.as<int32_t>(),
-                       out.left.as<int32_t>(), out.right.as<int32_t>());
+    RFX_TRY(dyn_emit(ctx, in, desc, n, nullptr, P, 0, out));
+    hipLaunchKernelGGL(k_dyn_part_starts, dim3(1), dim3(1), 0, ctx->stream, (const uint64_t *)out.key.as<uint64_t>(),
+                       (const uint8_t *)out.key_len.as<uint8_t>(), n, P, d_ps.as<int64_t>());
     RFX_HIP(hipGetLastError());
     return RFX_OK;
 }
@@ -475,30 +503,25 @@ static int dyn_pass(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, 
         RFX_HIP(hipMemsetAsync(pbase.p, 0, (size_t)(P + 1) * 8, ctx->stream));
         if (d_out_ps) RFX_HIP(hipMemsetAsync(d_out_ps, 0, (size_t)(P + 1) * 8, ctx->stream));
         RFX_HIP(desc.alloc(sizeof(DynDesc), ctx->stream));
-        return dyn_emit(ctx, in, desc, 0, pbase, P, start_marker, out);
+        return dyn_emit(ctx, in, desc, 0, pbase.as<uint64_t>(), P, start_marker, out);
     }
     RFX_HIP(head.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(cnt.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(base.alloc((size_t)(n + 1) * 8, ctx->stream));
     RFX_HIP(desc.alloc((size_t)n * sizeof(DynDesc), ctx->stream));
-    hipLaunchKernelGGL(k_dyn_heads, GRID(n), (const uint8_t *)in.key.as<uint8_t>(), (const int64_t *)in.key_off.as<int64_t>(), n, d_ps, P, lmin,
-                       head.as<uint32_t>());
+    const DynView v = dyn_view(in);
+    hipLaunchKernelGGL(k_dyn_heads, GRID(n), v.key, n, d_ps, P, lmin, head.as<uint32_t>());
     RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_dyn_walk<false>, dim3((unsigned)ceil_div(n, 128)), dim3(128), 0, ctx->stream, (const uint8_t *)in.key.as<uint8_t>(),
-                       (const int64_t *)in.key_off.as<int64_t>(), (const int64_t *)in.ext_off.as<int64_t>(), (const int32_t *)in.marker.as<int32_t>(),
-                       (const int32_t *)in.left.as<int32_t>(), (const int32_t *)in.right.as<int32_t>(), n, (const uint32_t *)head.as<uint32_t>(), stage,
+    hipLaunchKernelGGL(k_dyn_walk<false>, dim3((unsigned)ceil_div(n, 128)), dim3(128), 0, ctx->stream, v, n, (const uint32_t *)head.as<uint32_t>(), stage,
                        start_iteration, cnt.as<uint32_t>(), (const uint64_t *)nullptr, (DynDesc *)nullptr);
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, cnt.as<uint32_t>(), base.as<uint64_t>(), n));
     uint64_t ne = 0;
-    RFX_HIP(hipMemcpyAsync(&ne, base.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    RFX_TRY(sync_checked(ctx));
-    hipLaunchKernelGGL(k_dyn_walk<true>, dim3((unsigned)ceil_div(n, 128)), dim3(128), 0, ctx->stream, (const uint8_t *)in.key.as<uint8_t>(),
-                       (const int64_t *)in.key_off.as<int64_t>(), (const int64_t *)in.ext_off.as<int64_t>(), (const int32_t *)in.marker.as<int32_t>(),
-                       (const int32_t *)in.left.as<int32_t>(), (const int32_t *)in.right.as<int32_t>(), n, (const uint32_t *)head.as<uint32_t>(), stage,
+    RFX_TRY(small_readback(ctx, &ne, base.as<uint64_t>() + n, 8));
+    hipLaunchKernelGGL(k_dyn_walk<true>, dim3((unsigned)ceil_div(n, 128)), dim3(128), 0, ctx->stream, v, n, (const uint32_t *)head.as<uint32_t>(), stage,
                        start_iteration, (uint32_t *)nullptr, (const uint64_t *)base.as<uint64_t>(), desc.as<DynDesc>());
     RFX_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_dyn_pbase, dim3(1), dim3(64), 0, ctx->stream, d_ps, P, (const uint64_t *)base.as<uint64_t>(), n, ne, pbase.as<uint64_t>(), d_out_ps);
     RFX_HIP(hipGetLastError());
-    return dyn_emit(ctx, in, desc, (int64_t)ne, pbase, P, start_marker, out);
+    return dyn_emit(ctx, in, desc, (int64_t)ne, pbase.as<uint64_t>(), P, start_marker, out);
 }
 
 static int dyn_reflect(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, DynDev &out) {
@@ -508,30 +531,197 @@ static int dyn_reflect(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int 
     hipLaunchKernelGGL(k_dyn_identity_desc, GRID(in.n), in.n, desc.as<DynDesc>());
     hipLaunchKernelGGL(k_dyn_copy_u64, dim3(1), dim3(64), 0, ctx->stream, d_ps, P + 1, pbase.as<uint64_t>());
     RFX_HIP(hipGetLastError());
-    return dyn_emit(ctx, in, desc, in.n, pbase, P, 2, out);
+    return dyn_emit(ctx, in, desc, in.n, pbase.as<uint64_t>(), P, 2, out);
 }
 
-}  // namespace
+// ---- host base codes <-> the packed set ---------------------------------------------------------------------------------------
+// sizes: key_len / ext_len / extension words of every record from the host form's offsets
+__global__ __launch_bounds__(256) void k_dyn_pack_sizes(const int64_t *__restrict__ koff, const int64_t *__restrict__ eoff, int64_t n,
+                                                        uint8_t *__restrict__ key_len, int32_t *__restrict__ ext_len, uint32_t *__restrict__ ew,
+                                                        uint32_t *__restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < n;
+    int64_t kl = live ? koff[i + 1] - koff[i] : 0, el = live ? eoff[i + 1] - eoff[i] : 0;
+    if (live && (kl < 0 || el < 0 || el > 0x7FFFFFE0ll)) { atomicOr(flags + 3, 1u); kl = kl < 0 ? 0 : kl; el = 0; }
+    dyn_note_lengths(flags, live, (int)(kl > 255 ? 255 : kl));
+    if (!live) return;
+    key_len[i] = (uint8_t)(kl > 255 ? 255 : kl);
+    ext_len[i] = (int32_t)el;
+    ew[i] = (uint32_t)((el + 31) >> 5);
+}
+// 32 base codes (one byte each) -> one word, the first in the two highest bits; cnt < 32: the rest 0
+__device__ __forceinline__ uint64_t dyn_pack32(const uint8_t *__restrict__ s, int cnt) {
+    uint64_t x = 0;
+    for (int i = 0; i < 32; i++) if (i < cnt) x |= (uint64_t)(s[i] & 3) << (62 - 2 * i);
+    return x;
+}
+__global__ __launch_bounds__(256) void k_dyn_pack_key(const uint8_t *__restrict__ key, const int64_t *__restrict__ koff, const uint8_t *__restrict__ key_len,
+                                                      int64_t n, uint64_t *__restrict__ okey) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * DYN_KW) return;
+    const int64_t i = t / DYN_KW;
+    const int j = (int)(t % DYN_KW);
+    const int cnt = (int)key_len[i] - 32 * j;
+    okey[t] = cnt > 0 ? dyn_pack32(key + koff[i] + 32 * j, cnt) : 0ull;
+}
+__global__ __launch_bounds__(256) void k_dyn_pack_ext(const uint8_t *__restrict__ ext, const int64_t *__restrict__ eoff, const int32_t *__restrict__ ext_len,
+                                                      int64_t n, const int64_t *__restrict__ oeoff, uint64_t *__restrict__ oext) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n <= 0 || w >= oeoff[n]) return;
+    const int64_t i = dyn_find(oeoff, n, w);
+    const int j = (int)(w - oeoff[i]);
+    oext[w] = dyn_pack32(ext + eoff[i] + 32 * (int64_t)j, ext_len[i] - 32 * j);
+}
 
-extern "C" {
+// host record set -> a packed set in HBM (the library's own buffers).  A key of more than 124 bases: RFX_E_LIMIT
+static int dyn_pack_host(rfx_ctx *ctx, const rfx_dyn_records *h, DynDev &d) {
+    const int64_t n = h->n;
+    if (n < 0 || (n > 0 && (!h->key_off || !h->ext_off || !h->marker || !h->left || !h->right))) return RFX_E_ARG;
+    const int64_t nk = n ? h->key_off[n] : 0, ne = n ? h->ext_off[n] : 0;
+    if (nk < 0 || ne < 0 || (nk > 0 && !h->key) || (ne > 0 && !h->ext)) return RFX_E_ARG;
+    RFX_TRY(dyn_alloc(ctx, d, n, n + ne / 32));
+    if (n == 0) {
+        RFX_HIP(hipMemsetAsync(d.ext_off.p, 0, 8, ctx->stream));
+        return RFX_OK;
+    }
+    DevBuf kb, eb, ko, eo, ew, flags;
+    RFX_HIP(kb.alloc((size_t)std::max<int64_t>(nk, 1), ctx->stream)); RFX_HIP(eb.alloc((size_t)std::max<int64_t>(ne, 1), ctx->stream));
+    RFX_HIP(ko.alloc((size_t)(n + 1) * 8, ctx->stream)); RFX_HIP(eo.alloc((size_t)(n + 1) * 8, ctx->stream));
+    RFX_HIP(ew.alloc((size_t)n * 4, ctx->stream));
+    RFX_TRY(dyn_flags_init(ctx, flags));
+    if (nk) RFX_HIP(hipMemcpyAsync(kb.p, h->key, (size_t)nk, hipMemcpyHostToDevice, ctx->stream));
+    if (ne) RFX_HIP(hipMemcpyAsync(eb.p, h->ext, (size_t)ne, hipMemcpyHostToDevice, ctx->stream));
+    RFX_HIP(hipMemcpyAsync(ko.p, h->key_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    RFX_HIP(hipMemcpyAsync(eo.p, h->ext_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    RFX_HIP(hipMemcpyAsync(d.marker.p, h->marker, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    RFX_HIP(hipMemcpyAsync(d.left.p, h->left, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    RFX_HIP(hipMemcpyAsync(d.right.p, h->right, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_dyn_pack_sizes, GRID(n), (const int64_t *)ko.as<int64_t>(), (const int64_t *)eo.as<int64_t>(), n, d.key_len.as<uint8_t>(),
+                       d.ext_len.as<int32_t>(), ew.as<uint32_t>(), flags.as<uint32_t>());
+    RFX_HIP(hipGetLastError());
+    RFX_TRY(exclusive_scan_u32_to_u64(ctx, ew.as<uint32_t>(), d.ext_off.as<uint64_t>(), n));
+    DynFlags f{};
+    RFX_TRY(dyn_flags_read(ctx, flags, nullptr, &f));
+    if (f.bad) { ctx->last_error = "dynamic-k: record offsets that run backwards"; return RFX_E_ARG; }
+    if (f.too_long) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
+    hipLaunchKernelGGL(k_dyn_pack_key, GRID(n * DYN_KW), (const uint8_t *)kb.as<uint8_t>(), (const int64_t *)ko.as<int64_t>(),
+                       (const uint8_t *)d.key_len.as<uint8_t>(), n, d.key.as<uint64_t>());
+    RFX_HIP(hipGetLastError());
+    if (d.words > 0) {
+        hipLaunchKernelGGL(k_dyn_pack_ext, GRID(d.words), (const uint8_t *)eb.as<uint8_t>(), (const int64_t *)eo.as<int64_t>(),
+                           (const int32_t *)d.ext_len.as<int32_t>(), n, (const int64_t *)d.ext_off.as<int64_t>(), d.ext.as<uint64_t>());
+        RFX_HIP(hipGetLastError());
+    }
+    return sync_checked(ctx);                                     // (the staging buffers are read by the copies queued above)
+}
 
-int rfx_dyn_sort(rfx_ctx *ctx, const rfx_dyn_records *in, int P, rfx_dyn_records *out, int64_t *part_start) try {
-    if (!ctx || !in || !out || !part_start || P < 1 || P > 63) return RFX_E_ARG;
-    RFX_HIP(hipSetDevice(ctx->device));
-    DynDev a, b;
-    DevBuf ps;
-    uint32_t lmin = 0;
-    RFX_TRY(dyn_upload(ctx, in, a));
-    RFX_TRY(dyn_sort(ctx, a, P, b, ps, &lmin));
-    RFX_HIP(hipMemcpyAsync(part_start, ps.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    return dyn_download(ctx, b, out);
-} RFX_API_CATCH(ctx)
+__global__ __launch_bounds__(256) void k_dyn_unpack_sizes(const uint8_t *__restrict__ key_len, const int32_t *__restrict__ ext_len, int64_t n,
+                                                          uint32_t *__restrict__ ks, uint32_t *__restrict__ es) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    ks[i] = (uint32_t)key_len[i];
+    es[i] = (uint32_t)ext_len[i];
+}
+// one thread per output base: its record through the scan of the lengths.  word_off == nullptr: DYN_KW words per record
+__global__ __launch_bounds__(256) void k_dyn_unpack_bases(const uint64_t *__restrict__ words, const int64_t *__restrict__ word_off, const uint64_t *__restrict__ boff,
+                                                          int64_t n, int64_t total, uint8_t *__restrict__ out) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= total) return;
+    const int64_t i = dyn_find(boff, n, b);
+    const int64_t t = b - (int64_t)boff[i];
+    const uint64_t *w = words + (word_off ? word_off[i] : DYN_KW * i);
+    out[b] = (uint8_t)((w[t >> 5] >> (62 - 2 * (int)(t & 31))) & 3);
+}
+
+// a packed set -> the caller's host arrays; checks every capacity before anything is copied
+static int dyn_unpack_host(rfx_ctx *ctx, const DynDev &d, rfx_dyn_records *h) {
+    const int64_t n = d.n;
+    DevBuf ks, es, kso, eso, kb, eb;
+    RFX_HIP(ks.alloc((size_t)std::max<int64_t>(n, 1) * 4, ctx->stream)); RFX_HIP(es.alloc((size_t)std::max<int64_t>(n, 1) * 4, ctx->stream));
+    RFX_HIP(kso.alloc((size_t)(n + 1) * 8, ctx->stream)); RFX_HIP(eso.alloc((size_t)(n + 1) * 8, ctx->stream));
+    if (n > 0) {
+        hipLaunchKernelGGL(k_dyn_unpack_sizes, GRID(n), (const uint8_t *)d.key_len.as<uint8_t>(), (const int32_t *)d.ext_len.as<int32_t>(), n,
+                           ks.as<uint32_t>(), es.as<uint32_t>());
+        RFX_HIP(hipGetLastError());
+    }
+    RFX_TRY(exclusive_scan2_u32_to_u64(ctx, ks.as<uint32_t>(), es.as<uint32_t>(), kso.as<uint64_t>(), eso.as<uint64_t>(), n));
+    uint64_t tot[2] = {0, 0};
+    RFX_HIP(hipMemcpyAsync(&tot[0], kso.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    RFX_HIP(hipMemcpyAsync(&tot[1], eso.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    RFX_TRY(sync_checked(ctx));
+    const int64_t nk = (int64_t)tot[0], ne = (int64_t)tot[1];
+    h->n = n; h->need_key = nk; h->need_ext = ne;
+    if (n > h->cap_n || nk > h->cap_key || ne > h->cap_ext) return RFX_E_CAP;
+    RFX_HIP(kb.alloc((size_t)std::max<int64_t>(nk, 1), ctx->stream)); RFX_HIP(eb.alloc((size_t)std::max<int64_t>(ne, 1), ctx->stream));
+    if (nk) {
+        hipLaunchKernelGGL(k_dyn_unpack_bases, GRID(nk), (const uint64_t *)d.key.as<uint64_t>(), (const int64_t *)nullptr, (const uint64_t *)kso.as<uint64_t>(),
+                           n, nk, kb.as<uint8_t>());
+        RFX_HIP(hipGetLastError());
+        RFX_HIP(hipMemcpyAsync(h->key, kb.p, (size_t)nk, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (ne) {
+        hipLaunchKernelGGL(k_dyn_unpack_bases, GRID(ne), (const uint64_t *)d.ext.as<uint64_t>(), (const int64_t *)d.ext_off.as<int64_t>(),
+                           (const uint64_t *)eso.as<uint64_t>(), n, ne, eb.as<uint8_t>());
+        RFX_HIP(hipGetLastError());
+        RFX_HIP(hipMemcpyAsync(h->ext, eb.p, (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    RFX_HIP(hipMemcpyAsync(h->key_off, kso.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RFX_HIP(hipMemcpyAsync(h->ext_off, eso.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (n) {
+        RFX_HIP(hipMemcpyAsync(h->marker, d.marker.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        RFX_HIP(hipMemcpyAsync(h->left, d.left.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        RFX_HIP(hipMemcpyAsync(h->right, d.right.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return sync_checked(ctx);
+}
+
+// ---- the caller's packed arrays (rfx_dyn_packed, device pointers) <-> DynDev ---------------------------------------------------
+static bool dyn_packed_out_ok(const rfx_dyn_packed *p) {           // an output: its arrays (n is the callee's to set)
+    return p && p->key && p->key_len && p->ext && p->ext_off && p->ext_len && p->marker && p->left && p->right;
+}
+static bool dyn_packed_ok(const rfx_dyn_packed *p) { return dyn_packed_out_ok(p) && p->n >= 0; }
+// a view of the caller's input set: nothing is copied, nothing is freed
+static int dyn_borrow(rfx_ctx *ctx, const rfx_dyn_packed *p, DynDev &d) {
+    auto b = [&](DevBuf &x, void *q) { x.release(); x.p = q; x.s = ctx->stream; x.borrowed = true; };
+    b(d.key, p->key); b(d.key_len, p->key_len); b(d.ext, p->ext); b(d.ext_off, p->ext_off); b(d.ext_len, p->ext_len);
+    b(d.marker, p->marker); b(d.left, p->left); b(d.right, p->right);
+    d.n = p->n; d.words = 0;
+    if (p->n > 0) {
+        int64_t w = 0;
+        RFX_TRY(small_readback(ctx, &w, p->ext_off + p->n, 8));
+        if (w < 0) return RFX_E_ARG;
+        d.words = w;
+    }
+    return RFX_OK;
+}
+// the result into the caller's arrays; checks both capacities before anything is copied
+static int dyn_store(rfx_ctx *ctx, const DynDev &d, rfx_dyn_packed *o) {
+    const int64_t n = d.n;
+    int64_t words = 0;
+    if (n > 0) RFX_TRY(small_readback(ctx, &words, d.ext_off.as<int64_t>() + n, 8));
+    o->n = n; o->need_words = words;
+    if (n > o->cap_n || words > o->cap_words) return RFX_E_CAP;
+    if (n > 0) {
+        RFX_HIP(hipMemcpyAsync(o->key, d.key.p, (size_t)n * DYN_KW * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        RFX_HIP(hipMemcpyAsync(o->key_len, d.key_len.p, (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
+        if (words) RFX_HIP(hipMemcpyAsync(o->ext, d.ext.p, (size_t)words * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        RFX_HIP(hipMemcpyAsync(o->ext_off, d.ext_off.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        RFX_HIP(hipMemcpyAsync(o->ext_len, d.ext_len.p, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        RFX_HIP(hipMemcpyAsync(o->marker, d.marker.p, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        RFX_HIP(hipMemcpyAsync(o->left, d.left.p, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        RFX_HIP(hipMemcpyAsync(o->right, d.right.p, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+        RFX_HIP(hipMemsetAsync(o->ext_off, 0, 8, ctx->stream));
+    }
+    return sync_checked(ctx);
+}
 
 // ---- DynamicKmerBinarizerFromReducedToSubKmer (FirstFour :2931-3016; Iteration's twin) on the device: the text rows of the hand-over
 // files -> records.  A row is its fields joined by ',': form 0 = (k-mer, "m|l|r") -- key = the k-mer without its last base, extension =
 // that base, orientation 1 --, form 1 = (sub-k-mer, "m|l|r", extension).  A leading '(' of the first field and a trailing ')' of the
 // attribute are dropped (the tuple text Spark writes); left / right are read back clamped to +-30000 (buildingAlongFromThreeInt
-// :2340-2366); A0 C1 G2, anything else 3.  One thread per row, twice: sizes (+ the attribute), then the bases.
+// :2340-2366); A0 C1 G2, anything else 3.  Sizes (one thread per row: the cut, the attribute, where key and extension begin in the
+// text), a scan of the extension words, then the fill: one thread per output word packs its 32 letters.
 struct DynRowCut { int64_t f0, f0e, f1, f1e, f2, f2e; };     // the three fields' [begin, end) in the text
 __device__ __forceinline__ DynRowCut dyn_row_cut(const char *__restrict__ t, int64_t b, int64_t e) {
     while (e > b && (t[e - 1] == '\n' || t[e - 1] == '\r')) e--;
@@ -551,123 +741,193 @@ __device__ __forceinline__ int dyn_parse_int(const char *__restrict__ t, int64_t
     if (i < e && t[i] == '|') i++;
     return (int)(neg ? -v : v);
 }
-__global__ void k_dyn_bin_sizes(const char *__restrict__ text, const int64_t *__restrict__ row_off, int64_t n, int form,
-                                uint32_t *__restrict__ klen, uint32_t *__restrict__ elen, int32_t *__restrict__ marker,
-                                int32_t *__restrict__ left, int32_t *__restrict__ right) {
+__global__ __launch_bounds__(256) void k_dyn_bin_sizes(const char *__restrict__ text, const int64_t *__restrict__ row_off, int64_t n, int form,
+                                                       const DynOut o, int64_t *__restrict__ kbeg, int64_t *__restrict__ ebeg, uint32_t *__restrict__ ew,
+                                                       uint32_t *__restrict__ flags) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    const DynRowCut c = dyn_row_cut(text, row_off[r], row_off[r + 1]);
-    const int64_t l0 = c.f0e - c.f0;
-    if (form == 0) { klen[r] = (uint32_t)(l0 > 0 ? l0 - 1 : 0); elen[r] = l0 > 0 ? 1u : 0u; }
-    else { klen[r] = (uint32_t)l0; elen[r] = (uint32_t)(c.f2e - c.f2); }
-    int64_t i = c.f1;
-    const int m = dyn_parse_int(text, i, c.f1e), l = dyn_parse_int(text, i, c.f1e), rr = dyn_parse_int(text, i, c.f1e);
-    marker[r] = form == 0 ? 1 : m;
-    left[r] = l < -30000 ? -30000 : l > 30000 ? 30000 : l;
-    right[r] = rr < -30000 ? -30000 : rr > 30000 ? 30000 : rr;
+    const bool live = r < n;
+    int64_t kl = 0, el = 0;
+    if (live) {
+        int64_t b = row_off[r], e = row_off[r + 1];
+        if (e < b) { atomicOr(flags + 3, 1u); e = b; }
+        const DynRowCut c = dyn_row_cut(text, b, e);
+        const int64_t l0 = c.f0e - c.f0;
+        if (form == 0) { kl = l0 > 0 ? l0 - 1 : 0; el = l0 > 0 ? 1 : 0; ebeg[r] = c.f0 + kl; }
+        else { kl = l0; el = c.f2e - c.f2; ebeg[r] = c.f2; }
+        if (el > 0x7FFFFFE0ll) { atomicOr(flags + 3, 1u); el = 0; }
+        kbeg[r] = c.f0;
+        int64_t i = c.f1;
+        const int m = dyn_parse_int(text, i, c.f1e), l = dyn_parse_int(text, i, c.f1e), rr = dyn_parse_int(text, i, c.f1e);
+        o.marker[r] = form == 0 ? 1 : m;
+        o.left[r] = l < -30000 ? -30000 : l > 30000 ? 30000 : l;
+        o.right[r] = rr < -30000 ? -30000 : rr > 30000 ? 30000 : rr;
+        o.key_len[r] = (uint8_t)(kl > 255 ? 255 : kl);
+        o.ext_len[r] = (int32_t)el;
+        ew[r] = (uint32_t)((el + 31) >> 5);
+    }
+    dyn_note_lengths(flags, live, (int)(kl > 255 ? 255 : kl));
 }
-__device__ __forceinline__ uint8_t dyn_code(char ch) { return ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : 3; }
-__global__ void k_dyn_bin_fill(const char *__restrict__ text, const int64_t *__restrict__ row_off, int64_t n, int form,
-                               const uint64_t *__restrict__ key_off, const uint64_t *__restrict__ ext_off, uint8_t *__restrict__ key,
-                               uint8_t *__restrict__ ext) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    const DynRowCut c = dyn_row_cut(text, row_off[r], row_off[r + 1]);
-    const int64_t nk = (int64_t)(key_off[r + 1] - key_off[r]), ne = (int64_t)(ext_off[r + 1] - ext_off[r]);
-    for (int64_t j = 0; j < nk; j++) key[key_off[r] + j] = dyn_code(text[c.f0 + j]);
-    const int64_t es = form == 0 ? c.f0 + nk : c.f2;
-    for (int64_t j = 0; j < ne; j++) ext[ext_off[r] + j] = dyn_code(text[es + j]);
+__device__ __forceinline__ uint64_t dyn_code32(const char *__restrict__ s, int cnt) {
+    uint64_t x = 0;
+    for (int i = 0; i < 32; i++) if (i < cnt) { const char ch = s[i]; x |= (uint64_t)(ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : 3) << (62 - 2 * i); }
+    return x;
+}
+__global__ __launch_bounds__(256) void k_dyn_bin_key(const char *__restrict__ text, const int64_t *__restrict__ kbeg, const uint8_t *__restrict__ key_len,
+                                                     int64_t n, uint64_t *__restrict__ okey) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * DYN_KW) return;
+    const int64_t r = t / DYN_KW;
+    const int j = (int)(t % DYN_KW);
+    const int cnt = (int)key_len[r] - 32 * j;
+    okey[t] = cnt > 0 ? dyn_code32(text + kbeg[r] + 32 * j, cnt) : 0ull;
+}
+__global__ __launch_bounds__(256) void k_dyn_bin_ext(const char *__restrict__ text, const int64_t *__restrict__ ebeg, const int32_t *__restrict__ ext_len,
+                                                     int64_t n, const int64_t *__restrict__ oeoff, uint64_t *__restrict__ oext) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n <= 0 || w >= oeoff[n]) return;
+    const int64_t r = dyn_find(oeoff, n, w);
+    const int j = (int)(w - oeoff[r]);
+    oext[w] = dyn_code32(text + ebeg[r] + 32 * (int64_t)j, ext_len[r] - 32 * j);
 }
 
-int rfx_dyn_binarize(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int form, rfx_dyn_records *out) try {
-    if (!ctx || !out || n_rows < 0 || (n_rows > 0 && (!text || !row_off)) || (form != 0 && form != 1)) return RFX_E_ARG;
-    RFX_HIP(hipSetDevice(ctx->device));
+// text in HBM (row r = d_text[d_row_off[r], d_row_off[r + 1])) -> a packed set in the library's own buffers
+static int dyn_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, int form, DynDev &d) {
+    if (n == 0) {
+        RFX_TRY(dyn_alloc(ctx, d, 0, 0));
+        RFX_HIP(hipMemsetAsync(d.ext_off.p, 0, 8, ctx->stream));
+        return RFX_OK;
+    }
+    DevBuf kbeg, ebeg, ew, flags;
+    const size_t m = (size_t)n;
+    // (everything but the extension words, whose number the scan gives)
+    RFX_HIP(d.key.alloc(m * DYN_KW * 8, ctx->stream)); RFX_HIP(d.key_len.alloc(m, ctx->stream)); RFX_HIP(d.ext_off.alloc((m + 1) * 8, ctx->stream));
+    RFX_HIP(d.ext_len.alloc(m * 4, ctx->stream)); RFX_HIP(d.marker.alloc(m * 4, ctx->stream)); RFX_HIP(d.left.alloc(m * 4, ctx->stream));
+    RFX_HIP(d.right.alloc(m * 4, ctx->stream));
+    RFX_HIP(kbeg.alloc(m * 8, ctx->stream)); RFX_HIP(ebeg.alloc(m * 8, ctx->stream)); RFX_HIP(ew.alloc(m * 4, ctx->stream));
+    RFX_TRY(dyn_flags_init(ctx, flags));
+    d.n = n;
+    hipLaunchKernelGGL(k_dyn_bin_sizes, GRID(n), d_text, d_row_off, n, form, dyn_out(d), kbeg.as<int64_t>(), ebeg.as<int64_t>(), ew.as<uint32_t>(),
+                       flags.as<uint32_t>());
+    RFX_HIP(hipGetLastError());
+    RFX_TRY(exclusive_scan_u32_to_u64(ctx, ew.as<uint32_t>(), d.ext_off.as<uint64_t>(), n));
+    DynFlags f{};
+    RFX_TRY(dyn_flags_read(ctx, flags, d.ext_off.as<uint64_t>() + n, &f));
+    if (f.bad) { ctx->last_error = "dynamic-k binarizer: row offsets that run backwards"; return RFX_E_ARG; }
+    if (f.too_long) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
+    d.words = (int64_t)f.total;
+    RFX_HIP(d.ext.alloc((size_t)std::max<int64_t>(d.words, 1) * 8, ctx->stream));
+    hipLaunchKernelGGL(k_dyn_bin_key, GRID(n * DYN_KW), d_text, (const int64_t *)kbeg.as<int64_t>(), (const uint8_t *)d.key_len.as<uint8_t>(), n,
+                       d.key.as<uint64_t>());
+    RFX_HIP(hipGetLastError());
+    if (d.words > 0) {
+        hipLaunchKernelGGL(k_dyn_bin_ext, GRID(d.words), d_text, (const int64_t *)ebeg.as<int64_t>(), (const int32_t *)d.ext_len.as<int32_t>(), n,
+                           (const int64_t *)d.ext_off.as<int64_t>(), d.ext.as<uint64_t>());
+        RFX_HIP(hipGetLastError());
+    }
+    return RFX_OK;
+}
+// host text -> HBM: the rows' bytes and their offsets relative to the first row
+static int dyn_upload_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, DevBuf &d_text, DevBuf &d_off) {
     for (int64_t i = 0; i < n_rows; i++) if (row_off[i + 1] < row_off[i]) return RFX_E_ARG;
     const int64_t nb = n_rows ? row_off[n_rows] - row_off[0] : 0;
-    DevBuf d_text, d_off, klen, elen;
-    DynDev d;
     RFX_HIP(d_text.alloc((size_t)std::max<int64_t>(nb, 1), ctx->stream));
     RFX_HIP(d_off.alloc((size_t)(n_rows + 1) * 8, ctx->stream));
-    RFX_HIP(klen.alloc((size_t)std::max<int64_t>(n_rows, 1) * 4, ctx->stream));
-    RFX_HIP(elen.alloc((size_t)std::max<int64_t>(n_rows, 1) * 4, ctx->stream));
-    // (records first with room for every byte of the text: the sizes are known only after the first kernel)
-    RFX_TRY(dyn_alloc(ctx, d, n_rows, nb, nb));
-    if (n_rows == 0) {
-        RFX_HIP(hipMemsetAsync(d.key_off.p, 0, 8, ctx->stream));
-        RFX_HIP(hipMemsetAsync(d.ext_off.p, 0, 8, ctx->stream));
-        d.nk = d.ne = 0;
-        return dyn_download(ctx, d, out);
-    }
+    if (n_rows == 0) return RFX_OK;
     std::vector<int64_t> rel((size_t)n_rows + 1);
     for (int64_t i = 0; i <= n_rows; i++) rel[(size_t)i] = row_off[i] - row_off[0];
     if (nb) RFX_HIP(hipMemcpyAsync(d_text.p, text + row_off[0], (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
     RFX_HIP(hipMemcpyAsync(d_off.p, rel.data(), (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_dyn_bin_sizes, GRID(n_rows), (const char *)d_text.p, (const int64_t *)d_off.as<int64_t>(), n_rows, form,
-                       klen.as<uint32_t>(), elen.as<uint32_t>(), d.marker.as<int32_t>(), d.left.as<int32_t>(), d.right.as<int32_t>());
-    RFX_HIP(hipGetLastError());
-    RFX_TRY(exclusive_scan_u32_to_u64(ctx, klen.as<uint32_t>(), d.key_off.as<uint64_t>(), n_rows));
-    RFX_TRY(exclusive_scan_u32_to_u64(ctx, elen.as<uint32_t>(), d.ext_off.as<uint64_t>(), n_rows));
-    hipLaunchKernelGGL(k_dyn_bin_fill, GRID(n_rows), (const char *)d_text.p, (const int64_t *)d_off.as<int64_t>(), n_rows, form,
-                       (const uint64_t *)d.key_off.as<uint64_t>(), (const uint64_t *)d.ext_off.as<uint64_t>(), d.key.as<uint8_t>(), d.ext.as<uint8_t>());
-    RFX_HIP(hipGetLastError());
-    uint64_t tot[2] = {0, 0};
-    RFX_HIP(hipMemcpyAsync(&tot[0], d.key_off.as<uint64_t>() + n_rows, 8, hipMemcpyDeviceToHost, ctx->stream));
-    RFX_HIP(hipMemcpyAsync(&tot[1], d.ext_off.as<uint64_t>() + n_rows, 8, hipMemcpyDeviceToHost, ctx->stream));
-    RFX_TRY(sync_checked(ctx));
-    d.nk = (int64_t)tot[0]; d.ne = (int64_t)tot[1];
-    return dyn_download(ctx, d, out);
-} RFX_API_CATCH(ctx)
+    return sync_checked(ctx);                                     // (rel is read by the copy)
+}
 
-int rfx_dyn_random_reflection(rfx_ctx *ctx, const rfx_dyn_records *in, const int64_t *part_start, int P, rfx_dyn_records *out) try {
-    if (!ctx || !in || !out || !part_start || P < 1 || P > 63) return RFX_E_ARG;
-    RFX_HIP(hipSetDevice(ctx->device));
-    RFX_TRY(dyn_keys_within_limit(ctx, in));
-    DynDev a, b;
-    DevBuf ps;
-    RFX_TRY(dyn_upload(ctx, in, a));
-    RFX_HIP(ps.alloc((size_t)(P + 1) * 8, ctx->stream));
-    RFX_HIP(hipMemcpyAsync(ps.p, part_start, (size_t)(P + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    RFX_TRY(dyn_reflect(ctx, a, ps.as<int64_t>(), P, b));
-    return dyn_download(ctx, b, out);
-} RFX_API_CATCH(ctx)
-
-int rfx_dyn_extend_pass(rfx_ctx *ctx, const rfx_dyn_records *in, const int64_t *part_start, int P, int stage, int start_iteration,
-                        int start_marker, rfx_dyn_records *out, int64_t *out_part_start) try {
-    if (!ctx || !in || !out || !part_start || P < 1 || P > 63 || (stage != 0 && stage != 1) || (start_marker != 1 && start_marker != 2))
-        return RFX_E_ARG;
-    RFX_HIP(hipSetDevice(ctx->device));
-    RFX_TRY(dyn_keys_within_limit(ctx, in));
-    DynDev a, b;
-    DevBuf ps, ops;
-    RFX_TRY(dyn_upload(ctx, in, a));
-    RFX_HIP(ps.alloc((size_t)(P + 1) * 8, ctx->stream)); RFX_HIP(ops.alloc((size_t)(P + 1) * 8, ctx->stream));
-    RFX_HIP(hipMemcpyAsync(ps.p, part_start, (size_t)(P + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    int64_t lmin = INT64_MAX;
-    for (int64_t i = 0; i < in->n; i++) lmin = std::min(lmin, in->key_off[i + 1] - in->key_off[i]);
-    if (in->n == 0) lmin = 0;
-    RFX_TRY(dyn_pass(ctx, a, ps.as<int64_t>(), P, (uint32_t)lmin, stage, start_iteration, start_marker, b, ops.as<int64_t>()));
-    if (out_part_start) RFX_HIP(hipMemcpyAsync(out_part_start, ops.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    return dyn_download(ctx, b, out);
-} RFX_API_CATCH(ctx)
+// ---- DSBinarySubKmerWith{Short,Long}ExtensionToString (FirstFour:226-263): rows "SUBKMER,marker|left|right,EXTENSION\n" ----------
+__device__ __forceinline__ int dyn_int_chars(int v) {              // characters of std::to_string(v)
+    int64_t a = v < 0 ? -(int64_t)v : (int64_t)v;
+    int c = v < 0 ? 2 : 1;
+    while (a >= 10) { a /= 10; c++; }
+    return c;
+}
+__device__ __forceinline__ char dyn_int_char(int v, int q) {        // its character q
+    if (v < 0) { if (q == 0) return '-'; q--; }
+    int64_t a = v < 0 ? -(int64_t)v : (int64_t)v;
+    int c = 1;
+    for (int64_t t = a; t >= 10; t /= 10) c++;
+    for (int s = c - 1 - q; s > 0; s--) a /= 10;
+    return (char)('0' + a % 10);
+}
+__global__ __launch_bounds__(256) void k_dyn_text_sizes(const DynView v, int64_t n, uint64_t *__restrict__ sz) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    sz[i] = (uint64_t)v.key_len[i] + (uint64_t)v.ext_len[i] + 5 + dyn_int_chars(v.marker[i]) + dyn_int_chars(v.left[i]) + dyn_int_chars(v.right[i]);
+}
+// one thread per output byte, up to lim (the smaller of the text's length and the buffer)
+__global__ __launch_bounds__(256) void k_dyn_text_fill(const DynView v, int64_t n, const uint64_t *__restrict__ toff, int64_t lim, char *__restrict__ out) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= lim) return;
+    const int64_t i = dyn_find(toff, n, b);
+    int64_t q = b - (int64_t)toff[i];
+    const int kl = (int)v.key_len[i], el = v.ext_len[i];
+    char ch;
+    if (q < kl) ch = "ACGT"[(v.key[DYN_KW * i + (q >> 5)] >> (62 - 2 * (int)(q & 31))) & 3];
+    else {
+        q -= kl;
+        const int m = v.marker[i], l = v.left[i], r = v.right[i];
+        const int cm = dyn_int_chars(m), cl = dyn_int_chars(l), cr = dyn_int_chars(r);
+        if (q == 0) ch = ',';
+        else if (q < 1 + cm) ch = dyn_int_char(m, (int)q - 1);
+        else if (q == 1 + cm) ch = '|';
+        else if (q < 2 + cm + cl) ch = dyn_int_char(l, (int)q - 2 - cm);
+        else if (q == 2 + cm + cl) ch = '|';
+        else if (q < 3 + cm + cl + cr) ch = dyn_int_char(r, (int)q - 3 - cm - cl);
+        else if (q == 3 + cm + cl + cr) ch = ',';
+        else {
+            q -= 4 + cm + cl + cr;
+            ch = q < el ? "ACGT"[(v.ext[v.ext_off[i] + (q >> 5)] >> (62 - 2 * (int)(q & 31))) & 3] : '\n';
+        }
+    }
+    out[b] = ch;
+}
+// the text of a set into d_text (filled up to cap); *total = its length
+static int dyn_to_text(rfx_ctx *ctx, const DynDev &d, char *d_text, int64_t cap, int64_t *total, DevBuf *own) {
+    const int64_t n = d.n;
+    *total = 0;
+    if (n == 0) return RFX_OK;
+    DevBuf sz, toff;
+    RFX_HIP(sz.alloc((size_t)n * 8, ctx->stream)); RFX_HIP(toff.alloc((size_t)(n + 1) * 8, ctx->stream));
+    const DynView v = dyn_view(d);
+    hipLaunchKernelGGL(k_dyn_text_sizes, GRID(n), v, n, sz.as<uint64_t>());
+    RFX_HIP(hipGetLastError());
+    RFX_TRY(exclusive_scan_u64(ctx, sz.as<uint64_t>(), toff.as<uint64_t>(), n));
+    uint64_t t = 0;
+    RFX_TRY(small_readback(ctx, &t, toff.as<uint64_t>() + n, 8));
+    *total = (int64_t)t;
+    if (own) {                                                    // (the driver: a buffer of the library's, as long as the text)
+        RFX_HIP(own->alloc((size_t)std::max<int64_t>(*total, 1), ctx->stream));
+        d_text = own->as<char>(); cap = *total;
+    }
+    const int64_t lim = std::min<int64_t>(*total, cap);
+    if (lim > 0) {
+        hipLaunchKernelGGL(k_dyn_text_fill, GRID(lim), v, n, (const uint64_t *)toff.as<uint64_t>(), lim, d_text);
+        RFX_HIP(hipGetLastError());
+    }
+    return sync_checked(ctx);
+}
 
 // The drivers, records resident in HBM between the operators.  FirstFour.assemblyFromKmer (:137-224): binarized records
 // (key = the k-mer without its last base, extension = that base, orientation 1) -> DSkmerRandomReflection on P equal
 // shares -> 4 x (sort, DSExtendReflexivKmer).  Iteration.assemblyFromKmer (:134-205): (end - start + 1) x (sort,
-// DSExtendReflexivKmerToArrayLoop).  passes_first_four / start / end select what runs; out = the final records.
-int rfx_dyn_run(rfx_ctx *ctx, const rfx_dyn_records *in, int P, int random_reflection, int passes_first_four, int start_iteration,
-                int end_iteration, rfx_dyn_records *out, int64_t *trace, int64_t trace_cap, int64_t *n_trace) try {
-    if (!ctx || !in || !out || P < 1 || P > 63 || passes_first_four < 0) return RFX_E_ARG;
-    RFX_HIP(hipSetDevice(ctx->device));
-    DynDev a, b;
+// DSExtendReflexivKmerToArrayLoop).  passes_first_four / start / end select what runs; a = the set, replaced by the result.
+static int dyn_run(rfx_ctx *ctx, DynDev &a, int P, int random_reflection, int passes_first_four, int start_iteration, int end_iteration,
+                   int64_t *trace, int64_t trace_cap, int64_t *n_trace) {
     DevBuf ps;
     int64_t nt = 0;
-    RFX_TRY(dyn_upload(ctx, in, a));
     if (random_reflection) {
         std::vector<int64_t> st((size_t)P + 1);
         for (int p = 0; p <= P; p++) st[(size_t)p] = p == P ? a.n : (int64_t)(((__int128)p * (__int128)a.n) / P);
         RFX_HIP(ps.alloc((size_t)(P + 1) * 8, ctx->stream));
         RFX_HIP(hipMemcpyAsync(ps.p, st.data(), (size_t)(P + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
         RFX_TRY(sync_checked(ctx));
+        DynDev b;
         RFX_TRY(dyn_reflect(ctx, a, ps.as<int64_t>(), P, b));
         dyn_swap(a, b);
     }
@@ -686,7 +946,192 @@ int rfx_dyn_run(rfx_ctx *ctx, const rfx_dyn_records *in, int P, int random_refle
     for (int i = 0; i < passes_first_four; i++) RFX_TRY(one(0, 0));
     for (int it = start_iteration; end_iteration >= start_iteration && it <= end_iteration; it++) RFX_TRY(one(1, start_iteration));
     if (n_trace) *n_trace = nt;
-    return dyn_download(ctx, a, out);
+    return RFX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- the packed set in the caller's device arrays ------------------------------------------------------------------------------
+int rfx_dev_dyn_pack(rfx_ctx *ctx, const rfx_dyn_records *host_in, rfx_dyn_packed *d_out) try {
+    if (!ctx || !host_in || !dyn_packed_out_ok(d_out)) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a;
+    RFX_TRY(dyn_pack_host(ctx, host_in, a));
+    return dyn_store(ctx, a, d_out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_dyn_unpack(rfx_ctx *ctx, const rfx_dyn_packed *d_in, rfx_dyn_records *host_out) try {
+    if (!ctx || !dyn_packed_ok(d_in) || !host_out) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a;
+    uint32_t lmin = 0;
+    RFX_TRY(dyn_borrow(ctx, d_in, a));
+    RFX_TRY(dyn_check_lengths(ctx, a, &lmin));
+    return dyn_unpack_host(ctx, a, host_out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_dyn_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, int form, rfx_dyn_packed *d_out) try {
+    if (!ctx || !dyn_packed_out_ok(d_out) || n_rows < 0 || (n_rows > 0 && (!d_text || !d_row_off)) || (form != 0 && form != 1)) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a;
+    RFX_TRY(dyn_binarize(ctx, d_text, d_row_off, n_rows, form, a));
+    return dyn_store(ctx, a, d_out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_dyn_sort(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int P, rfx_dyn_packed *d_out, int64_t *d_part_start) try {
+    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out) || !d_part_start || P < 1 || P > 63) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a, b;
+    DevBuf ps;
+    uint32_t lmin = 0;
+    RFX_TRY(dyn_borrow(ctx, d_in, a));
+    RFX_TRY(dyn_sort(ctx, a, P, b, ps, &lmin));
+    RFX_TRY(dyn_store(ctx, b, d_out));
+    RFX_HIP(hipMemcpyAsync(d_part_start, ps.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    return sync_checked(ctx);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_dyn_random_reflection(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const int64_t *d_part_start, int P, rfx_dyn_packed *d_out) try {
+    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out) || !d_part_start || P < 1 || P > 63) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a, b;
+    uint32_t lmin = 0;
+    RFX_TRY(dyn_borrow(ctx, d_in, a));
+    RFX_TRY(dyn_check_lengths(ctx, a, &lmin));
+    RFX_TRY(dyn_reflect(ctx, a, d_part_start, P, b));
+    return dyn_store(ctx, b, d_out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_dyn_extend_pass(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const int64_t *d_part_start, int P, int stage, int start_iteration,
+                            int start_marker, rfx_dyn_packed *d_out, int64_t *d_out_part_start) try {
+    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out) || !d_part_start || P < 1 || P > 63 || (stage != 0 && stage != 1) ||
+        (start_marker != 1 && start_marker != 2))
+        return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a, b;
+    DevBuf ops;
+    uint32_t lmin = 0;
+    RFX_TRY(dyn_borrow(ctx, d_in, a));
+    RFX_TRY(dyn_check_lengths(ctx, a, &lmin));
+    RFX_HIP(ops.alloc((size_t)(P + 1) * 8, ctx->stream));
+    RFX_TRY(dyn_pass(ctx, a, d_part_start, P, lmin, stage, start_iteration, start_marker, b, ops.as<int64_t>()));
+    RFX_TRY(dyn_store(ctx, b, d_out));
+    if (d_out_part_start) RFX_HIP(hipMemcpyAsync(d_out_part_start, ops.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    return sync_checked(ctx);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_dyn_run(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int P, int random_reflection, int passes_first_four, int start_iteration,
+                    int end_iteration, rfx_dyn_packed *d_out, int64_t *trace, int64_t trace_cap, int64_t *n_trace) try {
+    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out) || P < 1 || P > 63 || passes_first_four < 0) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a;
+    uint32_t lmin = 0;
+    RFX_TRY(dyn_borrow(ctx, d_in, a));
+    RFX_TRY(dyn_check_lengths(ctx, a, &lmin));
+    RFX_TRY(dyn_run(ctx, a, P, random_reflection, passes_first_four, start_iteration, end_iteration, trace, trace_cap, n_trace));
+    return dyn_store(ctx, a, d_out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_dyn_to_text(rfx_ctx *ctx, const rfx_dyn_packed *d_in, char *d_text, int64_t cap, int64_t *out_len) try {
+    if (!ctx || !dyn_packed_ok(d_in) || !out_len || cap < 0 || (cap > 0 && !d_text)) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a;
+    uint32_t lmin = 0;
+    int64_t total = 0;
+    RFX_TRY(dyn_borrow(ctx, d_in, a));
+    RFX_TRY(dyn_check_lengths(ctx, a, &lmin));
+    RFX_TRY(dyn_to_text(ctx, a, d_text, cap, &total, nullptr));
+    *out_len = total;
+    return total > cap ? RFX_E_CAP : RFX_OK;
+} RFX_API_CATCH(ctx)
+
+// host text in, host text out; everything between packed and in HBM: upload, binarize, run, to-text, one copy back
+int rfx_dyn_run_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int form, int P, int random_reflection,
+                     int passes_first_four, int start_iteration, int end_iteration, char *out, int64_t cap, int64_t *out_len, int64_t *trace,
+                     int64_t trace_cap, int64_t *n_trace) try {
+    if (!ctx || n_rows < 0 || (n_rows > 0 && (!text || !row_off)) || (form != 0 && form != 1) || P < 1 || P > 63 || passes_first_four < 0 ||
+        !out_len || cap < 0 || (cap > 0 && !out))
+        return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DevBuf d_text, d_off, d_out;
+    DynDev a;
+    int64_t total = 0;
+    RFX_TRY(dyn_upload_text(ctx, text, row_off, n_rows, d_text, d_off));
+    RFX_TRY(dyn_binarize(ctx, (const char *)d_text.p, (const int64_t *)d_off.as<int64_t>(), n_rows, form, a));
+    RFX_TRY(dyn_run(ctx, a, P, random_reflection, passes_first_four, start_iteration, end_iteration, trace, trace_cap, n_trace));
+    RFX_TRY(dyn_to_text(ctx, a, nullptr, 0, &total, &d_out));
+    *out_len = total;
+    const int64_t lim = std::min<int64_t>(total, cap);
+    if (lim > 0) RFX_HIP(hipMemcpyAsync(out, d_out.p, (size_t)lim, hipMemcpyDeviceToHost, ctx->stream));
+    RFX_TRY(sync_checked(ctx));
+    return total > cap ? RFX_E_CAP : RFX_OK;
+} RFX_API_CATCH(ctx)
+
+// ---- the host forms: pack -> the same kernels -> unpack -----------------------------------------------------------------------
+int rfx_dyn_binarize(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int form, rfx_dyn_records *out) try {
+    if (!ctx || !out || n_rows < 0 || (n_rows > 0 && (!text || !row_off)) || (form != 0 && form != 1)) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DevBuf d_text, d_off;
+    DynDev a;
+    RFX_TRY(dyn_upload_text(ctx, text, row_off, n_rows, d_text, d_off));
+    RFX_TRY(dyn_binarize(ctx, (const char *)d_text.p, (const int64_t *)d_off.as<int64_t>(), n_rows, form, a));
+    return dyn_unpack_host(ctx, a, out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dyn_sort(rfx_ctx *ctx, const rfx_dyn_records *in, int P, rfx_dyn_records *out, int64_t *part_start) try {
+    if (!ctx || !in || !out || !part_start || P < 1 || P > 63) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a, b;
+    DevBuf ps;
+    uint32_t lmin = 0;
+    RFX_TRY(dyn_pack_host(ctx, in, a));
+    RFX_TRY(dyn_sort(ctx, a, P, b, ps, &lmin));
+    RFX_TRY(dyn_unpack_host(ctx, b, out));
+    RFX_HIP(hipMemcpyAsync(part_start, ps.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    return sync_checked(ctx);
+} RFX_API_CATCH(ctx)
+
+int rfx_dyn_random_reflection(rfx_ctx *ctx, const rfx_dyn_records *in, const int64_t *part_start, int P, rfx_dyn_records *out) try {
+    if (!ctx || !in || !out || !part_start || P < 1 || P > 63) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a, b;
+    DevBuf ps;
+    RFX_TRY(dyn_pack_host(ctx, in, a));
+    RFX_HIP(ps.alloc((size_t)(P + 1) * 8, ctx->stream));
+    RFX_HIP(hipMemcpyAsync(ps.p, part_start, (size_t)(P + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    RFX_TRY(dyn_reflect(ctx, a, ps.as<int64_t>(), P, b));
+    return dyn_unpack_host(ctx, b, out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dyn_extend_pass(rfx_ctx *ctx, const rfx_dyn_records *in, const int64_t *part_start, int P, int stage, int start_iteration,
+                        int start_marker, rfx_dyn_records *out, int64_t *out_part_start) try {
+    if (!ctx || !in || !out || !part_start || P < 1 || P > 63 || (stage != 0 && stage != 1) || (start_marker != 1 && start_marker != 2))
+        return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a, b;
+    DevBuf ps, ops;
+    RFX_TRY(dyn_pack_host(ctx, in, a));
+    RFX_HIP(ps.alloc((size_t)(P + 1) * 8, ctx->stream)); RFX_HIP(ops.alloc((size_t)(P + 1) * 8, ctx->stream));
+    RFX_HIP(hipMemcpyAsync(ps.p, part_start, (size_t)(P + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    int64_t lmin = INT64_MAX;
+    for (int64_t i = 0; i < in->n; i++) lmin = std::min(lmin, in->key_off[i + 1] - in->key_off[i]);
+    if (in->n == 0) lmin = 0;
+    RFX_TRY(dyn_pass(ctx, a, ps.as<int64_t>(), P, (uint32_t)lmin, stage, start_iteration, start_marker, b, ops.as<int64_t>()));
+    RFX_TRY(dyn_unpack_host(ctx, b, out));
+    if (out_part_start) RFX_HIP(hipMemcpyAsync(out_part_start, ops.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    return sync_checked(ctx);
+} RFX_API_CATCH(ctx)
+
+int rfx_dyn_run(rfx_ctx *ctx, const rfx_dyn_records *in, int P, int random_reflection, int passes_first_four, int start_iteration,
+                int end_iteration, rfx_dyn_records *out, int64_t *trace, int64_t trace_cap, int64_t *n_trace) try {
+    if (!ctx || !in || !out || P < 1 || P > 63 || passes_first_four < 0) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a;
+    RFX_TRY(dyn_pack_host(ctx, in, a));
+    RFX_TRY(dyn_run(ctx, a, P, random_reflection, passes_first_four, start_iteration, end_iteration, trace, trace_cap, n_trace));
+    return dyn_unpack_host(ctx, a, out);
 } RFX_API_CATCH(ctx)
 
 // ---- the Row form of the third layout (what a JNI shim converts between) -----------------------------------------------
