@@ -307,7 +307,9 @@ int rfx_dev_count_reads_ragged_w(rfx_ctx *ctx, const uint64_t *d_words, const ui
 /* Multi-GPU exchange support for k = 33..63: the canonical two-word k-mers of packed reads (16-byte
  * elements {word0, word1}) written contiguously per owner (owner = mulhi(hash(k-mer), n_owners)),
  * d_owner_off[n_owners+1] element offsets; and the count of such elements after the exchange
- * (any order) -> ascending (2 words per key, int64 counts), as rfx_dev_count_reads_w returns them. */
+ * (any order) -> ascending (2 words per key, int64 counts), as rfx_dev_count_reads_w returns them.
+ * Two-word elements move as 128-bit units: d_out_elems, and d_elems at k = 33..63, lie at multiples of 16 bytes
+ * (every element offset of such a buffer, e.g. an owner's bucket d_out_elems + 16 * d_owner_off[o], is one). */
 int rfx_dev_bucket_wide_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads,
                                  int words_per_read, int read_len, int k, int front_clip, int end_clip,
                                  int n_owners, void *d_out_elems, int64_t cap_elems,

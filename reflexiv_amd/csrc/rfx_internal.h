@@ -350,17 +350,16 @@ int bucket_wide_records_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t 
 int count_wide_records(rfx_ctx *ctx, const void *d_records, int64_t n_records, int64_t n_instances_hint, int k, int min_cov,
                        int max_cov, uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap, int64_t *out_n,
                        int64_t *out_distinct);
-int count_wide2(rfx_ctx *ctx, const void *d_elems, int64_t n, int min_cov, int max_cov, uint64_t *d_out_keys,
-                int64_t *d_out_counts, int64_t cap, int64_t *out_n, int64_t *out_distinct);
 // ragged reads: d_read_len (per-read lengths; nk = the longest read's k-mers), their end clip and instances
 int count_wide2_reads(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
                       int min_cov, int max_cov, uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap, int64_t *out_n,
                       int64_t *out_distinct, const uint32_t *d_read_len = nullptr, int ec = 0, int64_t n_inst = -1);
 int bucket_wide_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
                          int n_owners, void *d_out, int64_t cap_elems, int64_t *d_owner_off, int64_t *h_owner_off);
-// k = 65..127 (W = 3, 4; rfx_kmer.hip): AoS W-word elements -> distinct keys and counts, unordered; the same from packed
-// reads (uniform, or d_read_len with nk = the longest read's k-mers and n_inst their instances); the k-mers of packed reads
-// grouped by owning rank (AoS elements, offsets as bucket_wide_by_owner)
+// the element path (rfx_kmer.hip): AoS W-word elements (W = 2..4: k = 33..127; two-word elements at 16-byte multiples) ->
+// distinct keys and counts, unordered; the same from packed reads at W = 3, 4 (uniform, or d_read_len with nk = the longest
+// read's k-mers and n_inst their instances; W = 2 goes through count_wide2_reads); the k-mers of packed reads grouped by
+// owning rank (W = 2..4; AoS elements, offsets as bucket_wide_by_owner)
 int count_wide_elems(rfx_ctx *ctx, const void *d_elems, int64_t n, int k, int min_cov, int max_cov, uint64_t *d_out_keys,
                      int64_t *d_out_counts, int64_t cap, int64_t *out_n, int64_t *out_distinct);
 int count_wide_n_from_reads(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,

@@ -1135,7 +1135,8 @@ __global__ __launch_bounds__(LT, LEAF_WAVES_PER_EU) void k_leaf_count(const type
     }
 }
 
-// ---- leaves of the k > 32 path: two-word keys.  No 128-bit LDS atomic exists, so the two key words of a slot are
+// ---- leaves of the k = 33..63 record path: two-word keys expanded from super-k-mer records (two-word ELEMENTS are counted by
+// k_leaf_count_wn<2>, which shares the constants below).  No 128-bit LDS atomic exists, so the two key words of a slot are
 // claimed by two 64-bit compare-and-swaps, one after the other -- word 0 first; a key that meets its own word 0 (or an
 // empty one) goes on to word 1, one that meets another value in either moves to its next slot -- so whatever order the
 // claims land in a slot names ONE key, nothing is ever locked, nobody spins, and a compare-and-swap's return value IS
@@ -1180,20 +1181,19 @@ constexpr int WRMAX = 8191;             // records of a leaf that goes through t
 constexpr int WPARK = 64;               // records a wave parks before it expands them
 constexpr int WWS = WPARK * 4 + 32;     // u64 words of a wave's expansion area: the parked records + head bits + prefix counts
 
-// RECS: the leaf's elements are super-k-mer records (WRec) expanded here, k-mer by k-mer, balanced over the
-// lanes as in k_leaf_count<1>; else two-word k-mers (Rec = {word0, word1}).
-template <bool RECS>
-__global__ __launch_bounds__(WLT) void k_leaf_count_wide(const std::conditional_t<RECS, WRec, Rec> *__restrict__ elems,
+// The leaf's elements are super-k-mer records (WRec) expanded here, k-mer by k-mer, balanced over the lanes as in
+// k_leaf_count<1>.  (Two-word k-mer ELEMENTS go through k_leaf_count_wn<2>.)
+__global__ __launch_bounds__(WLT) void k_leaf_count_wrec(const WRec *__restrict__ elems,
                                                         const uint64_t *__restrict__ leaf_off, const uint64_t *__restrict__ leaf_end,
                                                         int64_t nleaf, int k, int min_cov, int max_cov,
                                                         uint64_t *__restrict__ out_keys, int64_t *__restrict__ out_counts,
                                                         unsigned long long cap, CountOut *__restrict__ co, uint32_t presplit) {
-    __shared__ __attribute__((aligned(32))) uint64_t wstage[RECS ? WWS * (WLT / 64) : 4];
+    __shared__ __attribute__((aligned(32))) uint64_t wstage[WWS * (WLT / 64)];
     __shared__ uint32_t ps_eff;              // records one table takes (starts at `presplit`, shrinks on overflow)
     __shared__ unsigned long long tk0[WCAP], tk1[WCAP];                          // a plane per key word
     __shared__ uint32_t tcnt[WCAP];
     static_assert(WRSLOTS % 64 == 0 && WRSLOTS <= WLT, "record table");
-    __shared__ unsigned long long rA[RECS ? WRSLOTS : 1], rB[RECS ? WRSLOTS : 1], rCC[RECS ? WRSLOTS : 1];
+    __shared__ unsigned long long rA[WRSLOTS], rB[WRSLOTS], rCC[WRSLOTS];
     __shared__ uint32_t agg_on, agg_saved, agg_total;       // (as in k_leaf_count)
     __shared__ unsigned long long obh[WOBUF], obl[WOBUF];
     __shared__ uint32_t obc[WOBUF];
@@ -1209,7 +1209,7 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wide(const std::conditional_
     if (l0 >= l1) return;
     for (int i = threadIdx.x; i < WCAP; i += WLT) tcnt[i] = 0;
     for (int i = threadIdx.x; i < WCAP; i += WLT) { tk0[i] = EMPTY; tk1[i] = EMPTY; }
-    if constexpr (RECS) for (int i = threadIdx.x; i < WRSLOTS; i += WLT) { rA[i] = EMPTY; rB[i] = EMPTY; rCC[i] = EMPTY; }
+    for (int i = threadIdx.x; i < WRSLOTS; i += WLT) { rA[i] = EMPTY; rB[i] = EMPTY; rCC[i] = EMPTY; }
     if (threadIdx.x == 0) {
         ob_n = 0; ob_lim = 0xffffffffu; overflow = 0; sp = 0;
         ps_eff = presplit ? presplit : 0xffffffffu;
@@ -1234,29 +1234,26 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wide(const std::conditional_
 
     // (records: the wave's first 64 records of a leaf are loaded while the leaf before it is counted -- 2048 leaves per
     // workgroup, and after every one of them all sixteen waves stood waiting for memory at the same moment)
-    using ElemT = std::conditional_t<RECS, WRec, Rec>;
-    ElemT pre{};
+    WRec pre{};
     bool first_pass = true;
-    auto wave_first = [&](uint64_t b, uint64_t e) __attribute__((always_inline)) -> ElemT {
+    auto wave_first = [&](uint64_t b, uint64_t e) __attribute__((always_inline)) -> WRec {
         constexpr int NWV0 = WLT / 64;
         const uint64_t n0 = e - b, w0 = b + n0 * (threadIdx.x >> 6) / NWV0, w1 = b + n0 * ((threadIdx.x >> 6) + 1) / NWV0;
-        return w0 + lane_ < w1 ? elems[w0 + lane_] : ElemT{};
+        return w0 + lane_ < w1 ? elems[w0 + lane_] : WRec{};
     };
-    if constexpr (RECS) pre = wave_first(leaf_off[l0], leaf_end[l0]);       // (leaf_end = leaf_off + 1 unless the last level left slack)
+    pre = wave_first(leaf_off[l0], leaf_end[l0]);       // (leaf_end = leaf_off + 1 unless the last level left slack)
     for (int64_t leaf = l0; leaf < l1; leaf++) {
         const uint64_t begin = leaf_off[leaf], end = leaf_end[leaf];
         uint32_t S = 1, s = 0;
         first_pass = true;
-        if constexpr (RECS) {
-            // a leaf with many records will not fit one table: start it in 2, 4, ... hash-selected parts
-            // instead of finding that out from an abandoned pass (presplit = records one table takes)
-            if (end - begin > (uint64_t)ps_eff) {
-                while ((end - begin) > (uint64_t)ps_eff * S && S < 16) S *= 2;
-                if (S > 1) {
-                    __syncthreads();
-                    if (threadIdx.x == 0) for (uint32_t q = S - 1; q >= 1; q--) { stackS[sp] = S; stacks[sp] = q; sp++; }
-                    __syncthreads();
-                }
+        // a leaf with many records will not fit one table: start it in 2, 4, ... hash-selected parts
+        // instead of finding that out from an abandoned pass (presplit = records one table takes)
+        if (end - begin > (uint64_t)ps_eff) {
+            while ((end - begin) > (uint64_t)ps_eff * S && S < 16) S *= 2;
+            if (S > 1) {
+                __syncthreads();
+                if (threadIdx.x == 0) for (uint32_t q = S - 1; q >= 1; q--) { stackS[sp] = S; stacks[sp] = q; sp++; }
+                __syncthreads();
             }
         }
         while (begin != end) {
@@ -1292,158 +1289,148 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wide(const std::conditional_
                     }
                 }
             };
-            if constexpr (RECS) {
-                // every wave takes an equal contiguous share of the leaf, 64 records at a time.  A record is first counted
-                // in the record table; what finds no slot there is PARKED in the wave's LDS area, and whenever the area is
-                // full the parked records are expanded: a bit per output position marks where each record's windows
-                // start, and lane j extracts the k-mer at position j (its record by a prefix popcount of those bits).
-                // After the leaf's last record (one barrier) the table's slots are parked and expanded the same way, every
-                // k-mer weighing what its record counted.
-                constexpr int NWV = WLT / 64;
-                const int wave_ = threadIdx.x >> 6;
-                const uint64_t n = end - begin;
-                const uint64_t ws = begin + n * wave_ / NWV, we = begin + n * (wave_ + 1) / NWV;
-                WRec *wrec = (WRec *)(wstage + (size_t)wave_ * WWS);
-                uint32_t *wbits = (uint32_t *)(wrec + WPARK);
-                uint32_t *wcum = wbits + 32;
-                const int t = k - 32;
-                const bool agg = n <= (uint64_t)WRMAX && agg_on;      // (every hash-selected part of a split leaf too)
-                uint32_t hits = 0;
-                uint32_t parked = 0;                                 // wave-uniform
-                auto kmer_at_pos = [&](uint32_t j, uint64_t *k0, uint64_t *k1, uint32_t *wgt) __attribute__((always_inline)) {
-                    const uint32_t wd = wbits[j >> 5];
-                    const uint32_t ri = wcum[j >> 5] + (uint32_t)__popc(wd & (0xffffffffu >> (31 - (j & 31)))) - 1u;
-                    const WRec rr = wrec[ri];
-                    *wgt = (uint32_t)rr.hd >> 11;
-                    wrec_kmer(rr, j - ((uint32_t)rr.hd & 2047u), t, k0, k1);
-                };
-                auto flush_parked = [&]() __attribute__((always_inline)) {
-                    __builtin_amdgcn_wave_barrier();
-                    const uint32_t w4 = (uint32_t)lane_ < parked ? (uint32_t)wrec[lane_].hd : 0u;      // windows | weight << 11
-                    const uint32_t nwin = w4 & 31u;
-                    const uint32_t x = wave_incl_scan(nwin);
-                    const uint32_t off = x - nwin;
-                    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
-                    if (lane_ < 32) wbits[lane_] = 0;
-                    __builtin_amdgcn_wave_barrier();
-                    if (nwin) { atomicOr(&wbits[off >> 5], 1u << (off & 31)); *(uint32_t *)&wrec[lane_].hd = off | (w4 & ~2047u); }
-                    __builtin_amdgcn_wave_barrier();
-                    {
-                        const uint32_t c = (uint32_t)__popc(wbits[lane_ & 31]);
-                        const uint32_t y = wave_incl_scan(c);
-                        if (lane_ < 32) wcum[lane_] = y - c;
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    // (one k-mer per lane and round: pairing them, as the k <= 31 leaf does, measured 3 ms slower here)
-                    for (uint32_t wb = 0; wb < total; wb += 64) {
-                        const uint32_t ja = wb + lane_;
-                        const bool va = ja < total;
-                        uint64_t a0, a1;
-                        uint32_t wg;
-                        kmer_at_pos(va ? ja : 0, &a0, &a1, &wg);
-                        insertw(a0, a1, va, wg);
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    parked = 0;
-                };
-                // (valid in at most WPARK lanes)
-                auto park = [&](const WRec &rc, const bool valid, const uint32_t weight) __attribute__((always_inline)) {
-                    const uint64_t vm = __ballot(valid);
-                    if (!vm) return;
-                    const uint32_t d = (uint32_t)__popcll(vm);
+            // every wave takes an equal contiguous share of the leaf, 64 records at a time.  A record is first counted
+            // in the record table; what finds no slot there is PARKED in the wave's LDS area, and whenever the area is
+            // full the parked records are expanded: a bit per output position marks where each record's windows
+            // start, and lane j extracts the k-mer at position j (its record by a prefix popcount of those bits).
+            // After the leaf's last record (one barrier) the table's slots are parked and expanded the same way, every
+            // k-mer weighing what its record counted.
+            constexpr int NWV = WLT / 64;
+            const int wave_ = threadIdx.x >> 6;
+            const uint64_t n = end - begin;
+            const uint64_t ws = begin + n * wave_ / NWV, we = begin + n * (wave_ + 1) / NWV;
+            WRec *wrec = (WRec *)(wstage + (size_t)wave_ * WWS);
+            uint32_t *wbits = (uint32_t *)(wrec + WPARK);
+            uint32_t *wcum = wbits + 32;
+            const int t = k - 32;
+            const bool agg = n <= (uint64_t)WRMAX && agg_on;      // (every hash-selected part of a split leaf too)
+            uint32_t hits = 0;
+            uint32_t parked = 0;                                 // wave-uniform
+            auto kmer_at_pos = [&](uint32_t j, uint64_t *k0, uint64_t *k1, uint32_t *wgt) __attribute__((always_inline)) {
+                const uint32_t wd = wbits[j >> 5];
+                const uint32_t ri = wcum[j >> 5] + (uint32_t)__popc(wd & (0xffffffffu >> (31 - (j & 31)))) - 1u;
+                const WRec rr = wrec[ri];
+                *wgt = (uint32_t)rr.hd >> 11;
+                wrec_kmer(rr, j - ((uint32_t)rr.hd & 2047u), t, k0, k1);
+            };
+            auto flush_parked = [&]() __attribute__((always_inline)) {
+                __builtin_amdgcn_wave_barrier();
+                const uint32_t w4 = (uint32_t)lane_ < parked ? (uint32_t)wrec[lane_].hd : 0u;      // windows | weight << 11
+                const uint32_t nwin = w4 & 31u;
+                const uint32_t x = wave_incl_scan(nwin);
+                const uint32_t off = x - nwin;
+                const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+                if (lane_ < 32) wbits[lane_] = 0;
+                __builtin_amdgcn_wave_barrier();
+                if (nwin) { atomicOr(&wbits[off >> 5], 1u << (off & 31)); *(uint32_t *)&wrec[lane_].hd = off | (w4 & ~2047u); }
+                __builtin_amdgcn_wave_barrier();
+                {
+                    const uint32_t c = (uint32_t)__popc(wbits[lane_ & 31]);
+                    const uint32_t y = wave_incl_scan(c);
+                    if (lane_ < 32) wcum[lane_] = y - c;
+                }
+                __builtin_amdgcn_wave_barrier();
+                // (one k-mer per lane and round: pairing them, as the k <= 31 leaf does, measured 3 ms slower here)
+                for (uint32_t wb = 0; wb < total; wb += 64) {
+                    const uint32_t ja = wb + lane_;
+                    const bool va = ja < total;
+                    uint64_t a0, a1;
+                    uint32_t wg;
+                    kmer_at_pos(va ? ja : 0, &a0, &a1, &wg);
+                    insertw(a0, a1, va, wg);
+                }
+                __builtin_amdgcn_wave_barrier();
+                parked = 0;
+            };
+            // (valid in at most WPARK lanes)
+            auto park = [&](const WRec &rc, const bool valid, const uint32_t weight) __attribute__((always_inline)) {
+                const uint64_t vm = __ballot(valid);
+                if (!vm) return;
+                const uint32_t d = (uint32_t)__popcll(vm);
 #pragma nounroll
-                    while (parked + d > (uint32_t)WPARK) flush_parked();      // (once; a loop so that the body is not duplicated)
-                    if (valid) {
-                        const uint32_t ord = parked + __builtin_amdgcn_mbcnt_hi((uint32_t)(vm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)vm, 0u));
-                        WRec r2 = rc;
-                        r2.hd = (rc.hd & ~0xffffffffULL) | (uint64_t)((uint32_t)rec_len(rc) | (weight << 11));
-                        wrec[ord] = r2;
-                    }
-                    parked += d;
-                };
-                // the record's own bases: k - 1 + windows of them; what follows in b1 / b2 is whatever followed in the read
-                auto place = [&](const WRec &r, bool valid) __attribute__((always_inline)) -> bool {
-                    if (!agg || !valid) return false;
-                    const uint32_t nw1 = (uint32_t)(r.hd >> 32) & 15u;
-                    const int ub = 2 * (k + (int)nw1);                             // bits of the base string in use (66..156)
-                    const uint64_t b1 = ub >= 128 ? r.b1 : r.b1 & ~(~0ULL >> (ub - 64));
-                    const uint32_t c = (ub > 128 ? (uint32_t)(r.b2 >> 32) & ~(0xffffffffu >> (ub - 128)) & 0xfffffff0u : 0u) | nw1;
-                    if (r.b0 == EMPTY || b1 == EMPTY) return false;
-                    const uint32_t h = ((uint32_t)r.b0 ^ __builtin_rotateleft32((uint32_t)(r.b0 >> 32), 13) ^ __builtin_rotateleft32((uint32_t)b1, 7) ^
-                                        __builtin_rotateleft32((uint32_t)(b1 >> 32), 19) ^ (c * 0x85EBCA6Bu)) * 0x9E3779B1u;
-                    uint32_t slot = h >> 22;
-                    static_assert(WRSLOTS == 1024, "slot = ten hash bits");
+                while (parked + d > (uint32_t)WPARK) flush_parked();      // (once; a loop so that the body is not duplicated)
+                if (valid) {
+                    const uint32_t ord = parked + __builtin_amdgcn_mbcnt_hi((uint32_t)(vm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)vm, 0u));
+                    WRec r2 = rc;
+                    r2.hd = (rc.hd & ~0xffffffffULL) | (uint64_t)((uint32_t)rec_len(rc) | (weight << 11));
+                    wrec[ord] = r2;
+                }
+                parked += d;
+            };
+            // the record's own bases: k - 1 + windows of them; what follows in b1 / b2 is whatever followed in the read
+            auto place = [&](const WRec &r, bool valid) __attribute__((always_inline)) -> bool {
+                if (!agg || !valid) return false;
+                const uint32_t nw1 = (uint32_t)(r.hd >> 32) & 15u;
+                const int ub = 2 * (k + (int)nw1);                             // bits of the base string in use (66..156)
+                const uint64_t b1 = ub >= 128 ? r.b1 : r.b1 & ~(~0ULL >> (ub - 64));
+                const uint32_t c = (ub > 128 ? (uint32_t)(r.b2 >> 32) & ~(0xffffffffu >> (ub - 128)) & 0xfffffff0u : 0u) | nw1;
+                if (r.b0 == EMPTY || b1 == EMPTY) return false;
+                const uint32_t h = ((uint32_t)r.b0 ^ __builtin_rotateleft32((uint32_t)(r.b0 >> 32), 13) ^ __builtin_rotateleft32((uint32_t)b1, 7) ^
+                                    __builtin_rotateleft32((uint32_t)(b1 >> 32), 19) ^ (c * 0x85EBCA6Bu)) * 0x9E3779B1u;
+                uint32_t slot = h >> 22;
+                static_assert(WRSLOTS == 1024, "slot = ten hash bits");
 #pragma unroll
-                    for (int probe = 0; probe < RPROBE; probe++) {
-                        const unsigned long long pa = atomicCAS(&rA[slot], EMPTY, (unsigned long long)r.b0);
-                        if (pa == EMPTY || pa == r.b0) {
-                            const unsigned long long pb = atomicCAS(&rB[slot], EMPTY, (unsigned long long)b1);
-                            if (pb == EMPTY || pb == b1) {
-                                const unsigned long long pc = atomicCAS(&rCC[slot], EMPTY, (unsigned long long)c << 32);
-                                if (pc == EMPTY || (uint32_t)(pc >> 32) == c) { atomicAdd((uint32_t *)&rCC[slot], 1u); return true; }
-                            }
+                for (int probe = 0; probe < RPROBE; probe++) {
+                    const unsigned long long pa = atomicCAS(&rA[slot], EMPTY, (unsigned long long)r.b0);
+                    if (pa == EMPTY || pa == r.b0) {
+                        const unsigned long long pb = atomicCAS(&rB[slot], EMPTY, (unsigned long long)b1);
+                        if (pb == EMPTY || pb == b1) {
+                            const unsigned long long pc = atomicCAS(&rCC[slot], EMPTY, (unsigned long long)c << 32);
+                            if (pc == EMPTY || (uint32_t)(pc >> 32) == c) { atomicAdd((uint32_t *)&rCC[slot], 1u); return true; }
                         }
-                        slot = slot + 1u == (uint32_t)WRSLOTS ? 0u : slot + 1u;
                     }
-                    return false;
-                };
-                WRec nxt;
-                if (first_pass) {
-                    nxt = pre;
-                    if (leaf + 1 < l1) pre = wave_first(leaf_off[leaf + 1], leaf_end[leaf + 1]);      // travels while this leaf is counted
-                } else {
-                    nxt = ws + lane_ < we ? elems[ws + lane_] : WRec{0, 0, 0, 0};          // (a later part of a split leaf)
+                    slot = slot + 1u == (uint32_t)WRSLOTS ? 0u : slot + 1u;
                 }
-                first_pass = false;
-                for (uint64_t r0 = ws; r0 < we; r0 += 64) {
-                    if (__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
-                    const bool valid = r0 + lane_ < we;
-                    const WRec rc = nxt;
-                    nxt = r0 + 64 + lane_ < we ? elems[r0 + 64 + lane_] : WRec{0, 0, 0, 0};   // travels during the expansion
-                    const bool un = valid && !place(rc, valid);
-                    hits += (uint32_t)__popcll(__ballot(valid && !un));
-                    park(rc, un, 1u);
-                }
-                if (agg) {
-                    __syncthreads();                             // every record of the leaf is counted
-                    const uint32_t slot = (uint32_t)(wave_ * 64 + lane_);
-                    const bool mine = slot < (uint32_t)WRSLOTS;
-                    const unsigned long long a_ = mine ? rA[slot] : EMPTY, b_ = mine ? rB[slot] : EMPTY, cc = mine ? rCC[slot] : EMPTY;
-                    const bool have = cc != EMPTY;
-                    if (a_ != EMPTY) { rA[slot] = EMPTY; rB[slot] = EMPTY; rCC[slot] = EMPTY; }
-                    {
-                        const uint32_t used = (uint32_t)__popcll(__ballot(have));
-                        if (lane_ == 0 && hits != used) atomicAdd(&agg_saved, hits - used);
-                    }
-                    if (!__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
-                        const uint32_t c = (uint32_t)(cc >> 32);
-                        const WRec rr{(uint64_t)a_, (uint64_t)b_, (uint64_t)(c & 0xfffffff0u) << 32, (uint64_t)(c & 15u) << 32};
-                        park(rr, have, (uint32_t)cc);
-                    }
-                }
-#pragma nounroll
-                while (parked) flush_parked();
+                return false;
+            };
+            WRec nxt;
+            if (first_pass) {
+                nxt = pre;
+                if (leaf + 1 < l1) pre = wave_first(leaf_off[leaf + 1], leaf_end[leaf + 1]);      // travels while this leaf is counted
             } else {
-                for (uint64_t i = begin + threadIdx.x; i < end; i += WLT) {
-                    if (__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
-                    const Rec e = elems[i];
-                    insertw(e.w0, e.w1, true, 1u);
+                nxt = ws + lane_ < we ? elems[ws + lane_] : WRec{0, 0, 0, 0};          // (a later part of a split leaf)
+            }
+            first_pass = false;
+            for (uint64_t r0 = ws; r0 < we; r0 += 64) {
+                if (__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
+                const bool valid = r0 + lane_ < we;
+                const WRec rc = nxt;
+                nxt = r0 + 64 + lane_ < we ? elems[r0 + 64 + lane_] : WRec{0, 0, 0, 0};   // travels during the expansion
+                const bool un = valid && !place(rc, valid);
+                hits += (uint32_t)__popcll(__ballot(valid && !un));
+                park(rc, un, 1u);
+            }
+            if (agg) {
+                __syncthreads();                             // every record of the leaf is counted
+                const uint32_t slot = (uint32_t)(wave_ * 64 + lane_);
+                const bool mine = slot < (uint32_t)WRSLOTS;
+                const unsigned long long a_ = mine ? rA[slot] : EMPTY, b_ = mine ? rB[slot] : EMPTY, cc = mine ? rCC[slot] : EMPTY;
+                const bool have = cc != EMPTY;
+                if (a_ != EMPTY) { rA[slot] = EMPTY; rB[slot] = EMPTY; rCC[slot] = EMPTY; }
+                {
+                    const uint32_t used = (uint32_t)__popcll(__ballot(have));
+                    if (lane_ == 0 && hits != used) atomicAdd(&agg_saved, hits - used);
+                }
+                if (!__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
+                    const uint32_t c = (uint32_t)(cc >> 32);
+                    const WRec rr{(uint64_t)a_, (uint64_t)b_, (uint64_t)(c & 0xfffffff0u) << 32, (uint64_t)(c & 15u) << 32};
+                    park(rr, have, (uint32_t)cc);
                 }
             }
+#pragma nounroll
+            while (parked) flush_parked();
             __syncthreads();
             const bool ov = overflow != 0;
             if (threadIdx.x == 0) my_passes++;
             if (!ov) {
                 // (the threshold moves BEFORE the sweep, whose closing barrier stands between this store and the next
                 // leaf's read of ps_eff: threads that saw different thresholds would disagree on S and on their barriers)
-                if (RECS && threadIdx.x == 0 && S == 1 && end - begin > (uint64_t)ps_eff * 3 / 4 && ps_eff < (1u << 24)) ps_eff += ps_eff / 64 + 1;
-                if constexpr (RECS) {
-                    if (threadIdx.x == 0 && agg_on && end - begin <= (uint64_t)WRMAX) {
-                        agg_total += (uint32_t)(end - begin);
-                        if (agg_total >= 8192u) {
-                            if (agg_saved * 2u < agg_total) agg_on = 0;
-                            agg_total = 0; agg_saved = 0;
-                        }
+                if (threadIdx.x == 0 && S == 1 && end - begin > (uint64_t)ps_eff * 3 / 4 && ps_eff < (1u << 24)) ps_eff += ps_eff / 64 + 1;
+                if (threadIdx.x == 0 && agg_on && end - begin <= (uint64_t)WRMAX) {
+                    agg_total += (uint32_t)(end - begin);
+                    if (agg_total >= 8192u) {
+                        if (agg_saved * 2u < agg_total) agg_on = 0;
+                        agg_total = 0; agg_saved = 0;
                     }
                 }
                 // sweep: survivors -> LDS buffer (one add per wave), slots reset
@@ -1494,9 +1481,7 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wide(const std::conditional_
                 if (threadIdx.x == 0) {
                     my_overflows++;
                     overflow = 0;
-                    if constexpr (RECS) {
-                        if ((end - begin) / S < 2ull * ps_eff && ps_eff > 64) ps_eff -= ps_eff / 8;
-                    }
+                    if ((end - begin) / S < 2ull * ps_eff && ps_eff > 64) ps_eff -= ps_eff / 8;
                     if (sp + 2 <= LSTACK && S < (1u << 16)) {
                         stackS[sp] = 2 * S; stacks[sp] = s + S; sp++;
                         stackS[sp] = 2 * S; stacks[sp] = s;     sp++;
@@ -1511,9 +1496,7 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wide(const std::conditional_
             __syncthreads();
             if (threadIdx.x == 0) sp--;
         }
-        if constexpr (RECS) {
-            if (first_pass && leaf + 1 < l1) pre = wave_first(leaf_off[leaf + 1], leaf_end[leaf + 1]);     // (an empty leaf hands the chain on)
-        }
+        if (first_pass && leaf + 1 < l1) pre = wave_first(leaf_off[leaf + 1], leaf_end[leaf + 1]);     // (an empty leaf hands the chain on)
     }
     flush();
     {
@@ -2296,20 +2279,11 @@ __global__ __launch_bounds__(FH_T) void k_fix_holes(OneSweep os, int G, RT *__re
     }
 }
 
-// 16-byte elements of the k > 32 path (two-word canonical k-mers, rfx_wide.hip) go through the same
-// level kernels; their digits come from a hash of both words
-__device__ __forceinline__ uint64_t wide_hash(uint64_t hi, uint64_t lo) {
-    uint64_t x = hi ^ (lo * 0x9E3779B97F4A7C15ULL);
-    x *= 0xD6E8FEB86659FD93ULL;
-    return x ^ (x >> 32);
-}
-// (the top OWNER_BITS of the hash pick the owning GPU -- mulhi(hash, n_owners) -- and are skipped by the
-// local digits, as on the k <= 31 path)
-// MODE 0: super-k-mer records (digit from the header), 1: two-word k-mers (hash of both words),
-// 2: (k-mer, partial count) pairs (kmer_hash of the key; with lv.n_owners > 0 the digit is the owner)
-// MODE 4, 5: three- and four-word k-mers of k = 65..127 (24- and 32-byte elements {word0, ..., word W-1}, the counter's
-// layout; hash of all words)
+// The W-word canonical k-mers of the k > 32 element path (W = 2..4: k = 33..127, k % 32 != 0; rfx_wide.hip) go through the
+// same level kernels as AoS elements {word0, ..., word W-1} (the counter's layout); their digits come from a hash of all
+// words.  The two-word element is 16-byte aligned, so the level kernels move it with 128-bit loads and stores.
 template <int W> struct KmerW { uint64_t w[W]; };
+template <> struct alignas(16) KmerW<2> { uint64_t w[2]; };
 template <int W>
 __device__ __forceinline__ uint64_t wide_hash_n(const KmerW<W> &r) {
     uint64_t x = r.w[0];
@@ -2317,16 +2291,22 @@ __device__ __forceinline__ uint64_t wide_hash_n(const KmerW<W> &r) {
     for (int i = 1; i < W; i++) { x ^= r.w[i] * 0x9E3779B97F4A7C15ULL; x *= 0xD6E8FEB86659FD93ULL; x ^= x >> 32; }
     return x;
 }
+// (the top OWNER_BITS of the hash pick the owning GPU -- mulhi(hash, n_owners) -- and are skipped by the
+// local digits, as on the k <= 31 path)
+// MODE 0: super-k-mer records (digit from the header), 2: (k-mer, partial count) pairs (kmer_hash of the key; with
+// lv.n_owners > 0 the digit is the owner), 3: the 32-byte super-k-mer records of the k = 33..63 path,
+// MODE 1, 4, 5: W = 2, 3, 4-word k-mers (16-, 24- and 32-byte elements; WIDE_MODE<W>)
 template <int MODE> struct LevelElem { using T = Rec; };
-template <> struct LevelElem<3> { using T = WRec; };          // MODE 3: super-k-mer records of the k = 33..63 path
+template <> struct LevelElem<1> { using T = KmerW<2>; };
+template <> struct LevelElem<3> { using T = WRec; };
 template <> struct LevelElem<4> { using T = KmerW<3>; };
 template <> struct LevelElem<5> { using T = KmerW<4>; };
+template <int W> constexpr int WIDE_MODE = W == 2 ? 1 : W + 1;
 template <int MODE, class E>
 __device__ __forceinline__ unsigned level_digit(const E &r, int used, const Level &lv) {
     const int bits = lv.bits;
-    if constexpr (MODE >= 4) return bits ? (unsigned)(((wide_hash_n(r) << OWNER_BITS) << used) >> (64 - bits)) : 0u;
+    if constexpr (MODE == 1 || MODE >= 4) return bits ? (unsigned)(((wide_hash_n(r) << OWNER_BITS) << used) >> (64 - bits)) : 0u;
     else if constexpr (MODE == 3) return rec_digit((uint32_t)r.hd, used, bits);
-    else if constexpr (MODE == 1) return bits ? (unsigned)(((wide_hash(r.w0, r.w1) << OWNER_BITS) << used) >> (64 - bits)) : 0u;
     else if constexpr (MODE == 2) {
         if (lv.n_owners > 0) return (unsigned)__umul64hi(kmer_hash(r.w0), (uint64_t)lv.n_owners);
         return bits ? (unsigned)((local_hash(r.w0) << used) >> (64 - bits)) : 0u;
@@ -2336,10 +2316,6 @@ template <int MODE>
 __device__ __forceinline__ int level_bins(const Level &lv) {
     if constexpr (MODE == 2) return lv.n_owners > 0 ? lv.n_owners : 1 << lv.bits;
     else return 1 << lv.bits;
-}
-__device__ __forceinline__ unsigned wide_level1_digit(const Rec &r, const Level &lv) {
-    if (lv.n_owners > 0) return (unsigned)__umul64hi(wide_hash(r.w0, r.w1), (uint64_t)lv.n_owners);
-    return level_digit<1>(r, 0, lv);
 }
 
 // levels >= 2 on records: virtual workgroups as for k-mers, digit from the record header
@@ -2809,124 +2785,22 @@ __global__ __launch_bounds__(L2F_T) void k_l2_spill_fix(L2Plan pl, uint64_t *__r
     }
 }
 
-// ---- level 1 of the k = 33..63 path straight from the packed reads (uniform length): a thread owns
-// 16 consecutive windows of one read and rolls the two-word k-mer and its reverse complement through
-// them; the histogram kernel counts digits, the scatter kernel feeds write-combining rings (drained
-// every W2_STEPS windows).  The 16-byte elements are never written unpartitioned.
-struct WideSrc { const uint64_t *words; int64_t n_reads, nk, segs, total; int wpr, k, fc; };
-constexpr int W2SEG = 16, W2_STEPS = 4, W2T = 1024, W2B = 16, W2A = 4;
-
-struct W2State { uint64_t f0, f1, r0, r1, nxt; int v, j; };
-
-__device__ __forceinline__ void w2_init(const WideSrc &s, int64_t g, W2State &st) {
-    st.v = 0; st.j = 0;
-    if (g >= s.total) return;
-    const int64_t r = g / s.segs;
-    const int p0 = (int)(g - r * s.segs) * W2SEG;
-    int v = (int)(s.nk - p0);
-    v = v > W2SEG ? W2SEG : v;
-    const int res = s.k - 32;
-    const uint64_t *w = s.words + r * s.wpr;
-    const int b = s.fc + p0;
-    st.f0 = kmer_at(w, b, 32); st.f1 = kmer_at(w, b + 32, res);
-    st.r0 = revcomp(kmer_at(w, b + s.k - 32, 32), 32); st.r1 = revcomp(kmer_at(w, b, res), res);
-    st.nxt = v > 1 ? kmer_at(w, b + s.k, v - 1) : 0;
-    st.v = v;
-}
-// canonical element of the current window, then roll one base on
-__device__ __forceinline__ Rec w2_step(W2State &st, int res, uint64_t mres) {
-    const bool use_f = st.f0 != st.r0 ? st.f0 < st.r0 : st.f1 <= st.r1;          // ties -> forward
-    const Rec e{use_f ? st.f0 : st.r0, use_f ? st.f1 : st.r1};
-    if (st.j + 1 < st.v) {
-        const uint64_t nb = (st.nxt >> (2 * (st.v - 2 - st.j))) & 3;
-        const uint64_t cf = st.f1 >> (2 * (res - 1));
-        st.f1 = ((st.f1 << 2) | nb) & mres;
-        st.f0 = (st.f0 << 2) | cf;
-        const uint64_t cr = st.r0 & 3;
-        st.r0 = (st.r0 >> 2) | ((nb ^ 3) << 62);
-        st.r1 = (st.r1 >> 2) | (cr << (2 * (res - 1)));
-    }
-    st.j++;
-    return e;
-}
-
-__global__ __launch_bounds__(W2T) void k_w2_hist(WideSrc s, Level lv, uint64_t *__restrict__ blockhist) {
-    __shared__ uint32_t h[1 << MAX_BITS];
-    const int nb = lv.n_owners > 0 ? lv.n_owners : (1 << lv.bits);
-    for (int i = threadIdx.x; i < nb; i += W2T) h[i] = 0;
-    __syncthreads();
-    const int res = s.k - 32;
-    const uint64_t mres = low_mask(res);
-    for (int64_t g = (int64_t)blockIdx.x * W2T + threadIdx.x; g < s.total; g += (int64_t)gridDim.x * W2T) {
-        W2State st;
-        w2_init(s, g, st);
-        while (st.j < st.v) atomicAdd(&h[wide_level1_digit(w2_step(st, res, mres), lv)], 1u);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < nb; i += W2T) blockhist[(int64_t)i * gridDim.x + blockIdx.x] = h[i];
-}
-
-__global__ __launch_bounds__(W2T) void k_w2_scatter(WideSrc s, Level lv, const uint64_t *__restrict__ scanned,
-                                                    Rec *__restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char w2_smem[];
-    const int nb = lv.n_owners > 0 ? lv.n_owners : (1 << lv.bits);
-#define buf ((Rec *)w2_smem)
-#define tail ((unsigned long long *)(w2_smem + (size_t)nb * W2B * sizeof(Rec)))
-#define head (tail + nb)
-    for (int i = threadIdx.x; i < nb; i += W2T) tail[i] = head[i] = scanned[(int64_t)i * gridDim.x + blockIdx.x];
-    __syncthreads();
-    const int res = s.k - 32;
-    const uint64_t mres = low_mask(res);
-    const int64_t stride = (int64_t)gridDim.x * W2T;
-    for (int64_t gb = (int64_t)blockIdx.x * W2T; gb < s.total; gb += stride) {
-        W2State st;
-        w2_init(s, gb + threadIdx.x, st);
-        for (int blk = 0; blk < W2SEG / W2_STEPS; blk++) {
-#pragma unroll
-            for (int q = 0; q < W2_STEPS; q++) {
-                if (st.j < st.v) {
-                    const Rec e = w2_step(st, res, mres);
-                    const unsigned d = wide_level1_digit(e, lv);
-                    const unsigned long long pos = atomicAdd(&tail[d], 1ULL);
-                    if (pos - head[d] < (unsigned long long)W2B) buf[(size_t)d * W2B + (pos & (W2B - 1))] = e;
-                    else out[pos] = e;
-                }
-            }
-            __syncthreads();
-            const bool final = gb + stride >= s.total && blk == W2SEG / W2_STEPS - 1;
-            for (int d = threadIdx.x / W2B; d < nb; d += W2T / W2B) {
-                const int j = threadIdx.x % W2B;
-                const unsigned long long h = head[d], t = tail[d];
-                unsigned long long e, nh;
-                if (t - h > (unsigned long long)W2B) { e = h + W2B; nh = t; }
-                else {
-                    e = final ? t : (t & ~(unsigned long long)(W2A - 1));
-                    if (e < h) e = h;
-                    nh = e;
-                }
-                const unsigned long long g = h + j;
-                if (g < e) out[g] = buf[(size_t)d * W2B + (g & (W2B - 1))];
-                if (j == 0) head[d] = nh;
-            }
-            __syncthreads();
-        }
-    }
-#undef buf
-#undef tail
-#undef head
-}
-
-// ---- k = 65..127: three- and four-word k-mers (W = 3, 4; k % 32 != 0) through the element path of k = 33..63.
-// Level 1 rolls the W-word k-mer and its reverse complement through a thread's 16 windows of one read (uniform or per-read
-// lengths: the counter64 skip rule, nk_of_wide), 24- or 32-byte elements leave through write-combining rings; the record
-// levels (MODE 4, 5) and the LDS-table leaves (k_leaf_count_wn) follow.  The k <= 63 kernels are separate and unchanged.
+// ---- the element path of k = 33..127 (W = 2..4 words per k-mer, k % 32 != 0).  From reads, k = 33..63 takes the
+// super-k-mer records by default; this path serves it under RFX_WIDE_RECORDS=0, k = 65..127 always, and caller-supplied
+// elements of every W.
+// Level 1 straight from the packed reads (uniform or per-read lengths: the counter64 skip rule, nk_of_wide): a thread owns 16
+// consecutive windows of one read and rolls the W-word k-mer and its reverse complement through them; the histogram kernel
+// counts digits, the scatter kernel feeds write-combining rings (drained every WL1_STEPS windows), so the elements are never
+// written unpartitioned.  The record levels (MODE 1, 4, 5) and the LDS-table leaves (k_leaf_count_wn) follow.
 struct WideSrcN {
     const uint64_t *words;
     const uint32_t *len_arr;       // per-read lengths, or nullptr: every read emits nk windows
     int64_t n_reads, nk, segs, total;
     int wpr, k, fc, ec;
 };
-constexpr int WNB = 8;             // ring slots per bin at W = 3, 4 (512 bins x 8 x 32 B + cursors: 136 KiB of LDS)
+constexpr int WL1_SEG = 16, WL1_STEPS = 4, WL1_T = 1024, WL1_A = 4;      // windows per thread, per drain; threads; drain alignment
+// ring slots per bin: 512 bins x (16 x 16 B | 8 x 24 B | 8 x 32 B) + 16 B of cursors = 136, 104 and 136 KiB of LDS
+template <int W> constexpr int WL1_B = W == 2 ? 16 : 8;
 
 template <int W> struct WNState { uint64_t f[W], r[W], nxt; int v, j; };
 
@@ -2935,12 +2809,12 @@ __device__ __forceinline__ void wn_init(const WideSrcN &s, int64_t g, WNState<W>
     st.v = 0; st.j = 0;
     if (g >= s.total) return;
     const int64_t r = g / s.segs;
-    const int p0 = (int)(g - r * s.segs) * W2SEG;
+    const int p0 = (int)(g - r * s.segs) * WL1_SEG;
     // (a read longer than the longest one announced emits what the segments cover: no base past nk's windows is read)
     int64_t nkr = s.len_arr ? nk_of_wide((int64_t)s.len_arr[r], s.k, s.fc, s.ec) : s.nk;
     nkr = nkr < s.nk ? nkr : s.nk;
     if (nkr <= p0) return;
-    const int v = nkr - p0 > W2SEG ? W2SEG : (int)(nkr - p0);
+    const int v = nkr - p0 > WL1_SEG ? WL1_SEG : (int)(nkr - p0);
     const int res = s.k & 31;
     const uint64_t *w = s.words + r * s.wpr;
     const int b = s.fc + p0;
@@ -2986,46 +2860,46 @@ __device__ __forceinline__ KmerW<W> wn_step(WNState<W> &st, int res, uint64_t mr
 template <int W>
 __device__ __forceinline__ unsigned wn_level1_digit(const KmerW<W> &e, const Level &lv) {
     if (lv.n_owners > 0) return (unsigned)__umul64hi(wide_hash_n(e), (uint64_t)lv.n_owners);
-    return level_digit<W + 1>(e, 0, lv);          // (MODE 4, 5)
+    return level_digit<WIDE_MODE<W>>(e, 0, lv);
 }
 
 template <int W>
-__global__ __launch_bounds__(W2T) void k_wn_hist(WideSrcN s, Level lv, uint64_t *__restrict__ blockhist) {
+__global__ __launch_bounds__(WL1_T) void k_wn_hist(WideSrcN s, Level lv, uint64_t *__restrict__ blockhist) {
     __shared__ uint32_t h[1 << MAX_BITS];
     const int nb = lv.n_owners > 0 ? lv.n_owners : (1 << lv.bits);
-    for (int i = threadIdx.x; i < nb; i += W2T) h[i] = 0;
+    for (int i = threadIdx.x; i < nb; i += WL1_T) h[i] = 0;
     __syncthreads();
     const int res = s.k & 31;
     const uint64_t mres = low_mask(res);
-    for (int64_t g = (int64_t)blockIdx.x * W2T + threadIdx.x; g < s.total; g += (int64_t)gridDim.x * W2T) {
+    for (int64_t g = (int64_t)blockIdx.x * WL1_T + threadIdx.x; g < s.total; g += (int64_t)gridDim.x * WL1_T) {
         WNState<W> st;
         wn_init<W>(s, g, st);
         while (st.j < st.v) atomicAdd(&h[wn_level1_digit<W>(wn_step<W>(st, res, mres), lv)], 1u);
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < nb; i += W2T) blockhist[(int64_t)i * gridDim.x + blockIdx.x] = h[i];
+    for (int i = threadIdx.x; i < nb; i += WL1_T) blockhist[(int64_t)i * gridDim.x + blockIdx.x] = h[i];
 }
 
-// (as k_w2_scatter, with WNB ring slots per bin)
 template <int W>
-__global__ __launch_bounds__(W2T) void k_wn_scatter(WideSrcN s, Level lv, const uint64_t *__restrict__ scanned,
+__global__ __launch_bounds__(WL1_T) void k_wn_scatter(WideSrcN s, Level lv, const uint64_t *__restrict__ scanned,
                                                     KmerW<W> *__restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char wn_smem[];
     const int nb = lv.n_owners > 0 ? lv.n_owners : (1 << lv.bits);
+    constexpr int WNB = WL1_B<W>;
     KmerW<W> *buf = (KmerW<W> *)wn_smem;
     unsigned long long *tail = (unsigned long long *)(wn_smem + (size_t)nb * WNB * sizeof(KmerW<W>));
     unsigned long long *head = tail + nb;
-    for (int i = threadIdx.x; i < nb; i += W2T) tail[i] = head[i] = scanned[(int64_t)i * gridDim.x + blockIdx.x];
+    for (int i = threadIdx.x; i < nb; i += WL1_T) tail[i] = head[i] = scanned[(int64_t)i * gridDim.x + blockIdx.x];
     __syncthreads();
     const int res = s.k & 31;
     const uint64_t mres = low_mask(res);
-    const int64_t stride = (int64_t)gridDim.x * W2T;
-    for (int64_t gb = (int64_t)blockIdx.x * W2T; gb < s.total; gb += stride) {
+    const int64_t stride = (int64_t)gridDim.x * WL1_T;
+    for (int64_t gb = (int64_t)blockIdx.x * WL1_T; gb < s.total; gb += stride) {
         WNState<W> st;
         wn_init<W>(s, gb + threadIdx.x, st);
-        for (int blk = 0; blk < W2SEG / W2_STEPS; blk++) {
+        for (int blk = 0; blk < WL1_SEG / WL1_STEPS; blk++) {
 #pragma unroll
-            for (int q = 0; q < W2_STEPS; q++) {
+            for (int q = 0; q < WL1_STEPS; q++) {
                 if (st.j < st.v) {
                     const KmerW<W> e = wn_step<W>(st, res, mres);
                     const unsigned d = wn_level1_digit<W>(e, lv);
@@ -3035,14 +2909,14 @@ __global__ __launch_bounds__(W2T) void k_wn_scatter(WideSrcN s, Level lv, const 
                 }
             }
             __syncthreads();
-            const bool final = gb + stride >= s.total && blk == W2SEG / W2_STEPS - 1;
-            for (int d = threadIdx.x / WNB; d < nb; d += W2T / WNB) {
+            const bool final = gb + stride >= s.total && blk == WL1_SEG / WL1_STEPS - 1;
+            for (int d = threadIdx.x / WNB; d < nb; d += WL1_T / WNB) {
                 const int j = threadIdx.x % WNB;
                 const unsigned long long h = head[d], t = tail[d];
                 unsigned long long e, nh;
                 if (t - h > (unsigned long long)WNB) { e = h + WNB; nh = t; }
                 else {
-                    e = final ? t : (t & ~(unsigned long long)(W2A - 1));
+                    e = final ? t : (t & ~(unsigned long long)(WL1_A - 1));
                     if (e < h) e = h;
                     nh = e;
                 }
@@ -3055,12 +2929,13 @@ __global__ __launch_bounds__(W2T) void k_wn_scatter(WideSrcN s, Level lv, const 
     }
 }
 
-// ---- leaves of k = 65..127: an LDS hash table with W key planes (4096 slots: 112 KiB of keys and counts at W = 3, 144 KiB
-// at W = 4; one 1024-thread workgroup per CU, as k_leaf_count_wide).
-// Claiming a slot.  The two-word leaf claims key words one by one against EMPTY = all ones, which is safe there only because
-// no canonical k <= 63 k-mer has an all-ones word 0 or last word.  Here a middle word holds 32 bases (32 T's are all ones), and
-// from k = 64 on so can word 0 (T^32 ... A^32 is its own reverse complement's equal in word 0).  So only the LAST word is
-// compared against EMPTY: it holds k % 32 <= 31 bases, its top two bits are always zero, and no key's last word is all ones.
+// ---- leaves of the element path (W = 2..4): an LDS hash table with W key planes (4096 slots: 80 KiB of keys and counts at
+// W = 2, 112 KiB at W = 3, 144 KiB at W = 4; one 1024-thread workgroup per CU, as k_leaf_count_wrec).
+// Claiming a slot.  The record leaf's k-mer table claims its two key words one by one against EMPTY = all ones, which is safe
+// there only because no canonical k <= 63 k-mer has an all-ones word 0 or last word.  From W = 3 on a middle word holds 32
+// bases (32 T's are all ones), and from k = 64 on so can word 0 (T^32 ... A^32 is its own reverse complement's equal in word
+// 0).  So at W = 3, 4 only the LAST word is compared against EMPTY: it holds k % 32 <= 31 bases, its top two bits are always
+// zero, and no key's last word is all ones.
 //   1. CAS of the last word against EMPTY.  The one lane that gets EMPTY back owns the slot: it writes words 0..W-2 and then
 //      PUBLISHES them with its count add (release; the count of a claimed slot is 0 until then, >= 1 after).
 //   2. A lane that gets its own last word back reads the count (acquire).  0: the owner has not published yet -- try the same
@@ -3070,6 +2945,10 @@ __global__ __launch_bounds__(W2T) void k_wn_scatter(WideSrcN s, Level lv, const 
 // A slot's key words are written once, by its owner, before anyone compares them; two keys can never share a slot.  (A wait
 // that outlasts WSPIN tries -- a count wrapped to 0 by 2^32 instances of one key -- is treated as an overflow: the leaf splits,
 // and a key that still cannot settle ends in RFX_E_LIMIT, never in a hang.)
+// W = 2 is the one width at which the word-by-word claim of the record leaf's table is safe (k <= 63), and there it is the
+// faster one: the scheme above is correct at W = 2 too (it needs nothing of word 0), but its leaf stage measured 20.5 ms against
+// 17.7 ms at k = 63 on 2.9e9 instances, so k_leaf_count_wn<2> claims word 0, then word 1, by
+// compare-and-swap against EMPTY: nobody waits, nothing is published, and both planes are reset with a slot.
 constexpr int WSPIN = 1 << 16;
 template <int W>
 __device__ __forceinline__ uint32_t leaf_hash_n(const KmerW<W> &e) {
@@ -3099,7 +2978,7 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wn(const KmerW<W> *__restric
     const int64_t l0 = (int64_t)(((unsigned long long)blockIdx.x * (unsigned long long)nleaf) / gridDim.x);
     const int64_t l1 = (int64_t)(((unsigned long long)(blockIdx.x + 1) * (unsigned long long)nleaf) / gridDim.x);
     if (l0 >= l1) return;
-    for (int i = threadIdx.x; i < WCAP; i += WLT) { tcnt[i] = 0; tk[W - 1][i] = EMPTY; }
+    for (int i = threadIdx.x; i < WCAP; i += WLT) { tcnt[i] = 0; tk[W - 1][i] = EMPTY; if constexpr (W == 2) tk[0][i] = EMPTY; }
     if (threadIdx.x == 0) {
         ob_n = 0; ob_lim = 0xffffffffu; overflow = 0; sp = 0;
         ps_eff = presplit ? presplit : 0xffffffffu;
@@ -3138,7 +3017,7 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wn(const KmerW<W> *__restric
             }
         }
         while (begin != end) {
-            // one pass: the keys selected by (S, s) go into the table (double hashing, as k_leaf_count_wide; claims above)
+            // one pass: the keys selected by (S, s) go into the table (double hashing, as k_leaf_count_wrec; claims above)
             for (uint64_t i = begin + threadIdx.x; i < end; i += WLT) {
                 if (__hip_atomic_load(&overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
                 const KmerW<W> e = elems[i];
@@ -3149,6 +3028,17 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wn(const KmerW<W> *__restric
                 int probe = 0, spin = 0;
 #pragma nounroll
                 for (;;) {
+                    if constexpr (W == 2) {
+                        // (both words against EMPTY, word 0 first: see "Claiming a slot" above)
+                        const unsigned long long p0 = atomicCAS(&tk[0][slot], EMPTY, (unsigned long long)e.w[0]);
+                        if (p0 == EMPTY || p0 == e.w[0]) {
+                            const unsigned long long p1 = atomicCAS(&tk[1][slot], EMPTY, (unsigned long long)e.w[1]);
+                            if (p1 == EMPTY || p1 == e.w[1]) { atomicAdd(&tcnt[slot], 1u); break; }
+                        }
+                        if (++probe >= LPROBE) { overflow = 1; break; }
+                        slot = wide_next(slot, step);
+                        continue;
+                    }
                     const unsigned long long p = atomicCAS(&tk[W - 1][slot], EMPTY, (unsigned long long)e.w[W - 1]);
                     if (p == EMPTY) {
 #pragma unroll
@@ -3216,14 +3106,14 @@ __global__ __launch_bounds__(WLT) void k_leaf_count_wn(const KmerW<W> *__restric
                         }
                     }
                     tcnt[slot] = 0;
-                    if (c) tk[W - 1][slot] = EMPTY;
+                    if (c) { tk[W - 1][slot] = EMPTY; if constexpr (W == 2) tk[0][slot] = EMPTY; }
                 }
                 __syncthreads();
                 const uint32_t raw = ob_n, lim = ob_lim;
                 if (raw >= (uint32_t)WOBUF / 2 || lim != 0xffffffffu) flush();
                 if (S == 1) break;
             } else {
-                for (int i = threadIdx.x; i < WCAP; i += WLT) { tcnt[i] = 0; tk[W - 1][i] = EMPTY; }
+                for (int i = threadIdx.x; i < WCAP; i += WLT) { tcnt[i] = 0; tk[W - 1][i] = EMPTY; if constexpr (W == 2) tk[0][i] = EMPTY; }
                 __syncthreads();
                 if (threadIdx.x == 0) {
                     my_overflows++;
@@ -4163,6 +4053,21 @@ static int count_reads_superkmer(rfx_ctx *ctx, const ReadStore *reads, int min_c
                                 swept ? (const uint64_t *)segE.as<uint64_t>() : nullptr);
 }
 
+// the segment table of input that is not partitioned yet: one segment [0, n)
+static int one_segment(rfx_ctx *ctx, DevBuf &seg, int64_t n) {
+    const uint64_t seg_init[2] = {0, (uint64_t)n};
+    RFX_HIP(seg.alloc(2 * 8, ctx->stream));
+    RFX_HIP(hipMemcpyAsync(seg.p, seg_init, 16, hipMemcpyHostToDevice, ctx->stream));
+    return sync_checked(ctx);       // seg_init lives on the stack
+}
+
+// nothing to bucket: every owner's group is empty
+static int zero_owner_offsets(rfx_ctx *ctx, int n_owners, int64_t *d_owner_off, int64_t *h_owner_off) {
+    RFX_HIP(hipMemsetAsync(d_owner_off, 0, (size_t)(n_owners + 1) * 8, ctx->stream));
+    if (h_owner_off) memset(h_owner_off, 0, (size_t)(n_owners + 1) * 8);
+    return RFX_OK;
+}
+
 int count_filter(rfx_ctx *ctx, const ReadStore *reads, const uint64_t *d_kmers, int64_t n,
                  int min_cov, int max_cov, int twin, void *ws, int64_t ws_bytes,
                  uint64_t *d_out_keys, int32_t *d_out_counts, int64_t cap,
@@ -4190,10 +4095,7 @@ int count_filter(rfx_ctx *ctx, const ReadStore *reads, const uint64_t *d_kmers, 
     RFX_TRY(set_scatter_attrs(ctx));
 
     DevBuf bufA, bufB, segA, segB, co_buf;
-    uint64_t seg_init[2] = {0, (uint64_t)n};
-    RFX_HIP(segA.alloc(2 * 8, ctx->stream));
-    RFX_HIP(hipMemcpyAsync(segA.p, seg_init, 16, hipMemcpyHostToDevice, ctx->stream));
-    RFX_TRY(sync_checked(ctx));     // seg_init lives on the stack
+    RFX_TRY(one_segment(ctx, segA, n));
     int64_t nseg = 1;
     DevBuf *seg_cur = &segA, *seg_next = &segB;
     DevBuf *out_buf = &bufA, *in_buf = &bufB;
@@ -4329,11 +4231,7 @@ int bucket_records_by_owner(rfx_ctx *ctx, const ReadStore *reads, int n_owners, 
     if (n_owners < 1 || n_owners > 64 || !superkmer_enabled(reads->k)) return RFX_E_ARG;
     ReadSrc rsrc = make_read_src(reads);
     if (out_n_records) *out_n_records = 0;
-    if (rsrc.nk <= 0 || reads->n_reads <= 0) {
-        RFX_HIP(hipMemsetAsync(d_owner_off, 0, (size_t)(n_owners + 1) * 8, ctx->stream));
-        if (h_owner_off) memset(h_owner_off, 0, (size_t)(n_owners + 1) * 8);
-        return RFX_OK;
-    }
+    if (rsrc.nk <= 0 || reads->n_reads <= 0) return zero_owner_offsets(ctx, n_owners, d_owner_off, h_owner_off);
     Level lv{};
     lv.n_owners = n_owners;
     Rec *recs = nullptr;
@@ -4464,10 +4362,7 @@ int count_records(rfx_ctx *ctx, const void *d_records, int64_t n_records, int64_
     std::vector<int> bits;
     plan_levels(n_inst, false, bits, 16384.0);
     DevBuf segA, segB;
-    uint64_t seg_init[2] = {0, (uint64_t)n_records};
-    RFX_HIP(segA.alloc(2 * 8, ctx->stream));
-    RFX_HIP(hipMemcpyAsync(segA.p, seg_init, 16, hipMemcpyHostToDevice, ctx->stream));
-    RFX_TRY(sync_checked(ctx));
+    RFX_TRY(one_segment(ctx, segA, n_records));
     // slot -1: the caller's buffer; the first level writes workspace slot 0
     return count_records_levels(ctx, (const Rec *)d_records, n_records, 1, bits, 0, 0, &segA, &segB, 1, k, min_cov,
                                 max_cov, twin, d_out_keys, d_out_counts, cap, out_n, out_distinct);
@@ -4481,19 +4376,12 @@ int bucket_pairs_by_owner(rfx_ctx *ctx, const void *d_pairs, int64_t n, int n_ow
                           int64_t *d_owner_off, int64_t *h_owner_off) {
     StageArena stage_arena(ctx, (size_t)256 << 20);       // temporaries of this call (see StageArena)
     if (n_owners < 1 || n_owners > 64 || n < 0) return RFX_E_ARG;
-    if (n == 0) {
-        RFX_HIP(hipMemsetAsync(d_owner_off, 0, (size_t)(n_owners + 1) * 8, ctx->stream));
-        if (h_owner_off) memset(h_owner_off, 0, (size_t)(n_owners + 1) * 8);
-        return RFX_OK;
-    }
+    if (n == 0) return zero_owner_offsets(ctx, n_owners, d_owner_off, h_owner_off);
     Level lv{};
     lv.n_owners = n_owners;
     const int nb = n_owners;
     DevBuf seg, nvb, vb_start, table, scanned;
-    uint64_t seg_init[2] = {0, (uint64_t)n};
-    RFX_HIP(seg.alloc(16, ctx->stream));
-    RFX_HIP(hipMemcpyAsync(seg.p, seg_init, 16, hipMemcpyHostToDevice, ctx->stream));
-    RFX_TRY(sync_checked(ctx));
+    RFX_TRY(one_segment(ctx, seg, n));
     const int64_t total_tiles = ceil_div(n, PTILE);
     const int tpb = (int)std::min<int64_t>(32, std::max<int64_t>(1, total_tiles / ((int64_t)ctx->num_cu * 8)));
     const int64_t v_bound = ceil_div(n, (int64_t)tpb * PTILE) + 1;
@@ -4552,10 +4440,7 @@ int merge_pairs(rfx_ctx *ctx, const void *d_pairs, int64_t n, int k, int min_cov
     std::vector<int> bits;
     plan_levels(n, false, bits, 2048.0);           // pairs are mostly distinct keys: ~half-full tables
     DevBuf segA, segB;
-    uint64_t seg_init[2] = {0, (uint64_t)n};
-    RFX_HIP(segA.alloc(2 * 8, ctx->stream));
-    RFX_HIP(hipMemcpyAsync(segA.p, seg_init, 16, hipMemcpyHostToDevice, ctx->stream));
-    RFX_TRY(sync_checked(ctx));
+    RFX_TRY(one_segment(ctx, segA, n));
     DevBuf *seg_cur = &segA, *seg_next = &segB;
     int64_t nseg = 1;
     const Rec *cur = nullptr;
@@ -4564,22 +4449,8 @@ int merge_pairs(rfx_ctx *ctx, const void *d_pairs, int64_t n, int k, int min_cov
                             d_out_keys, d_out_counts, cap, out_n, out_distinct);
 }
 
-template <bool RECS = false>
-static int finish_wide2(rfx_ctx *ctx, const std::conditional_t<RECS, WRec, Rec> *cur, const uint64_t *d_leaf_off, int64_t nseg,
-                        int min_cov, int max_cov, uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap, int64_t *out_n,
-                        int64_t *out_distinct, int k = 63, const uint64_t *d_leaf_end = nullptr) {
-    if (!d_leaf_end) d_leaf_end = d_leaf_off + 1;
-    DevBuf co_buf;
-    RFX_HIP(co_buf.alloc(sizeof(CountOut), ctx->stream));
-    RFX_HIP(hipMemsetAsync(co_buf.p, 0, sizeof(CountOut), ctx->stream));
-    {
-        ScopedTimer t(ctx, "leaf");
-        const int64_t grid = std::min<int64_t>(nseg, (int64_t)ctx->num_cu);          // one workgroup per CU
-        hipLaunchKernelGGL(k_leaf_count_wide<RECS>, dim3((unsigned)grid), dim3(WLT), 0, ctx->stream, cur, d_leaf_off, d_leaf_end, nseg, k,
-                           min_cov, max_cov, d_out_keys, d_out_counts, (unsigned long long)cap, co_buf.as<CountOut>(),
-                           (uint32_t)(getenv("RFX_WIDE_PRESPLIT") ? atoi(getenv("RFX_WIDE_PRESPLIT")) : 2600));
-        RFX_HIP(hipGetLastError());
-    }
+// what the leaves of a k > 32 count left in `co_buf`: totals to the caller, statistics to ctx->timing
+static int wide_leaves_done(rfx_ctx *ctx, const DevBuf &co_buf, int64_t nseg, int64_t cap, int64_t *out_n, int64_t *out_distinct) {
     CountOut co{};
     RFX_HIP(hipMemcpyAsync(&co, co_buf.p, sizeof co, hipMemcpyDeviceToHost, ctx->stream));
     RFX_TRY(sync_checked(ctx));
@@ -4594,84 +4465,24 @@ static int finish_wide2(rfx_ctx *ctx, const std::conditional_t<RECS, WRec, Rec> 
     return RFX_OK;
 }
 
-// k = 33..63: n two-word canonical k-mers (16-byte elements {word0, word1}) -> distinct keys with
-// counts, unordered.  Same bucket structure as the k <= 31 record path: hash digits, exact
-// histograms, write-combining scatters, LDS-table leaves.
-int count_wide2(rfx_ctx *ctx, const void *d_elems, int64_t n, int min_cov, int max_cov, uint64_t *d_out_keys,
-                int64_t *d_out_counts, int64_t cap, int64_t *out_n, int64_t *out_distinct) {
-    StageArena stage_arena(ctx, (size_t)256 << 20);       // temporaries of this call (see StageArena)
-    if (out_n) *out_n = 0;
-    if (out_distinct) *out_distinct = 0;
-    if (n <= 0) return RFX_OK;
-    std::vector<int> bits;
-    plan_levels(n, false, bits, 8192.0);             // a 4096-slot table per leaf; overflowing leaves split
-    if (bits.empty()) bits.push_back(0);
-    DevBuf segA, segB;
-    uint64_t seg_init[2] = {0, (uint64_t)n};
-    RFX_HIP(segA.alloc(2 * 8, ctx->stream));
-    RFX_HIP(hipMemcpyAsync(segA.p, seg_init, 16, hipMemcpyHostToDevice, ctx->stream));
-    RFX_TRY(sync_checked(ctx));
-    DevBuf *seg_cur = &segA, *seg_next = &segB;
-    int64_t nseg = 1;
-    const Rec *cur = nullptr;
-    RFX_TRY(partition_record_levels<1>(ctx, (const Rec *)d_elems, n, 1, bits, 0, 0, &seg_cur, &seg_next, &nseg, &cur));
-    return finish_wide2(ctx, cur, (const uint64_t *)seg_cur->as<uint64_t>(), nseg, min_cov, max_cov, d_out_keys, d_out_counts,
-                        cap, out_n, out_distinct);
-}
-
-// level 1 of the k = 33..63 path: packed uniform reads -> two-word elements grouped by `lv`
-// (radix digit or owner) in d_dst, group offsets in d_seg_off[nb + 1]
-static int wide_level1(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
-                       const Level &lv, Rec *d_dst, uint64_t *d_seg_off) {
-    const int nb = lv.n_owners > 0 ? lv.n_owners : (1 << lv.bits);
-    WideSrc ws{d_words, n_reads, nk, ceil_div(nk, W2SEG), 0, wpr, k, fc};
-    ws.total = n_reads * ws.segs;
-    const unsigned G = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(ws.total, W2T), (int64_t)ctx->num_cu));
-    DevBuf bh, scanned;
-    RFX_HIP(bh.alloc((size_t)nb * G * 8, ctx->stream));
-    RFX_HIP(scanned.alloc(((size_t)nb * G + 1) * 8, ctx->stream));
+// the record leaves (d_leaf_end: where each leaf's records end when the last level left slack behind them, else nullptr: leaf
+// l ends where leaf l + 1 begins)
+static int finish_wide_records(rfx_ctx *ctx, const WRec *cur, const uint64_t *d_leaf_off, const uint64_t *d_leaf_end, int64_t nseg,
+                               int k, int min_cov, int max_cov, uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap,
+                               int64_t *out_n, int64_t *out_distinct) {
+    if (!d_leaf_end) d_leaf_end = d_leaf_off + 1;
+    DevBuf co_buf;
+    RFX_HIP(co_buf.alloc(sizeof(CountOut), ctx->stream));
+    RFX_HIP(hipMemsetAsync(co_buf.p, 0, sizeof(CountOut), ctx->stream));
     {
-        ScopedTimer t(ctx, "hist1");
-        hipLaunchKernelGGL(k_w2_hist, dim3(G), dim3(W2T), 0, ctx->stream, ws, lv, bh.as<uint64_t>());
+        ScopedTimer t(ctx, "leaf");
+        const int64_t grid = std::min<int64_t>(nseg, (int64_t)ctx->num_cu);          // one workgroup per CU
+        hipLaunchKernelGGL(k_leaf_count_wrec, dim3((unsigned)grid), dim3(WLT), 0, ctx->stream, cur, d_leaf_off, d_leaf_end, nseg, k,
+                           min_cov, max_cov, d_out_keys, d_out_counts, (unsigned long long)cap, co_buf.as<CountOut>(),
+                           (uint32_t)(getenv("RFX_WIDE_PRESPLIT") ? atoi(getenv("RFX_WIDE_PRESPLIT")) : 2600));
         RFX_HIP(hipGetLastError());
     }
-    RFX_TRY(exclusive_scan_u64(ctx, bh.as<uint64_t>(), scanned.as<uint64_t>(), (int64_t)nb * G));
-    hipLaunchKernelGGL(k_bin_offsets, dim3((unsigned)ceil_div(nb + 1, 256)), dim3(256), 0, ctx->stream,
-                       (const uint64_t *)scanned.as<uint64_t>(), nb, (int64_t)G, d_seg_off);
-    RFX_HIP(hipGetLastError());
-    {
-        ScopedTimer t(ctx, "part1");
-        const size_t lds = (size_t)nb * (W2B * sizeof(Rec) + 16);
-        RFX_HIP(hipFuncSetAttribute((const void *)k_w2_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_w2_scatter, dim3(G), dim3(W2T), lds, ctx->stream, ws, lv, (const uint64_t *)scanned.as<uint64_t>(),
-                           d_dst);
-        RFX_HIP(hipGetLastError());
-    }
-    return RFX_OK;
-}
-
-// multi-GPU support: the two-word k-mers of packed uniform reads, grouped by owning rank
-int bucket_wide_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
-                         int n_owners, void *d_out, int64_t cap_elems, int64_t *d_owner_off, int64_t *h_owner_off) {
-    StageArena stage_arena(ctx, (size_t)256 << 20);       // temporaries of this call (see StageArena)
-    if (n_owners < 1 || n_owners > 64) return RFX_E_ARG;
-    const int64_t n = nk * n_reads;
-    if (n > cap_elems) return RFX_E_CAP;
-    if (n <= 0) {
-        RFX_HIP(hipMemsetAsync(d_owner_off, 0, (size_t)(n_owners + 1) * 8, ctx->stream));
-        if (h_owner_off) memset(h_owner_off, 0, (size_t)(n_owners + 1) * 8);
-        return RFX_OK;
-    }
-    ctx->timing.clear();
-    Level lv{};
-    lv.n_owners = n_owners;
-    RFX_TRY(wide_level1(ctx, d_words, n_reads, wpr, nk, k, fc, lv, (Rec *)d_out, reinterpret_cast<uint64_t *>(d_owner_off)));
-    if (h_owner_off) {
-        RFX_HIP(hipMemcpyAsync(h_owner_off, d_owner_off, (size_t)(n_owners + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-        RFX_TRY(sync_checked(ctx));
-    }
-    ScopedTimer::collect(ctx);
-    return RFX_OK;
+    return wide_leaves_done(ctx, co_buf, nseg, cap, out_n, out_distinct);
 }
 
 // k = 33..63 through super-k-mer records (the default): the k = 31 / 30 front end on the CENTRAL window of
@@ -4744,7 +4555,7 @@ static int count_wide2_reads_records(rfx_ctx *ctx, const uint64_t *d_words, int6
     DevBuf cstart, le;
     RFX_TRY(partition_to_leaves<3>(ctx, recs, R, 0, bits, 1, lv.bits, &segA, &segB, (int64_t)1 << lv.bits,
                                    swept ? (const uint64_t *)segE.as<uint64_t>() : nullptr, &cur, &ec, &loff, &lend, &nleaf, cstart, le));
-    return finish_wide2<true>(ctx, cur, loff, nleaf, min_cov, max_cov, d_out_keys, d_out_counts, cap, out_n, out_distinct, k, lend);
+    return finish_wide_records(ctx, cur, loff, lend, nleaf, k, min_cov, max_cov, d_out_keys, d_out_counts, cap, out_n, out_distinct);
 }
 
 // multi-GPU, k = 33..63: the 32-byte records grouped by the owner of their minimiser (~5 B per instance
@@ -4755,11 +4566,7 @@ int bucket_wide_records_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t 
     StageArena stage_arena(ctx, (size_t)256 << 20);       // temporaries of this call (see StageArena)
     if (n_owners < 1 || n_owners > 64 || k < 33 || k > 63) return RFX_E_ARG;
     if (out_n_records) *out_n_records = 0;
-    if (nk <= 0 || n_reads <= 0) {
-        RFX_HIP(hipMemsetAsync(d_owner_off, 0, (size_t)(n_owners + 1) * 8, ctx->stream));
-        if (h_owner_off) memset(h_owner_off, 0, (size_t)(n_owners + 1) * 8);
-        return RFX_OK;
-    }
+    if (nk <= 0 || n_reads <= 0) return zero_owner_offsets(ctx, n_owners, d_owner_off, h_owner_off);
     ReadSrc rsrc = wide_read_src(d_words, n_reads, wpr, nk, k, fc, d_read_len, ec);
     Level lv{};
     lv.n_owners = n_owners;
@@ -4799,68 +4606,30 @@ int count_wide_records(rfx_ctx *ctx, const void *d_records, int64_t n_records, i
     std::vector<int> bits;
     plan_wide_record_levels(n_instances_hint > 0 ? n_instances_hint : n_records * 6, bits);
     DevBuf segA, segB;
-    uint64_t seg_init[2] = {0, (uint64_t)n_records};
-    RFX_HIP(segA.alloc(2 * 8, ctx->stream));
-    RFX_HIP(hipMemcpyAsync(segA.p, seg_init, 16, hipMemcpyHostToDevice, ctx->stream));
-    RFX_TRY(sync_checked(ctx));
+    RFX_TRY(one_segment(ctx, segA, n_records));
     const WRec *cur = nullptr;
     const uint64_t *loff = nullptr, *lend = nullptr;
     int64_t ec = 0, nleaf = 0;
     DevBuf cstart, le;
     RFX_TRY(partition_to_leaves<3>(ctx, (const WRec *)d_records, n_records, 1, bits, 0, 0, &segA, &segB, 1, nullptr, &cur, &ec, &loff, &lend, &nleaf,
                                    cstart, le));
-    return finish_wide2<true>(ctx, cur, loff, nleaf, min_cov, max_cov, d_out_keys, d_out_counts, cap, out_n, out_distinct, k, lend);
+    return finish_wide_records(ctx, cur, loff, lend, nleaf, k, min_cov, max_cov, d_out_keys, d_out_counts, cap, out_n, out_distinct);
 }
 
-// k = 33..63 from packed reads of one length (d_read_len == nullptr) or of per-read lengths (nk = the longest read's
-// k-mers, n_inst = the instances of all, end_clip the clip they were counted with): level 1 straight from the reads, then
-// count_wide2's levels/leaves.  Ragged reads always take the record path: the element path's level 1 (wide_level1)
-// reads every read as nk windows long, so RFX_WIDE_RECORDS=0 does not apply to them.
-int count_wide2_reads(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
-                      int min_cov, int max_cov, uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap, int64_t *out_n,
-                      int64_t *out_distinct, const uint32_t *d_read_len, int ec, int64_t n_inst) {
-    StageArena stage_arena(ctx, (size_t)256 << 20);       // temporaries of this call (see StageArena)
-    if (out_n) *out_n = 0;
-    if (out_distinct) *out_distinct = 0;
-    const int64_t n = d_read_len ? n_inst : nk * n_reads;
-    if (n <= 0 || nk <= 0) return RFX_OK;
-    if (d_read_len) {
-        if (k < 33 || k > 63) return RFX_E_ARG;
-        return count_wide2_reads_records(ctx, d_words, n_reads, wpr, nk, k, fc, min_cov, max_cov, d_out_keys, d_out_counts, cap,
-                                         out_n, out_distinct, d_read_len, ec, n_inst);
-    }
-    if (wide_records_enabled(k))
-        return count_wide2_reads_records(ctx, d_words, n_reads, wpr, nk, k, fc, min_cov, max_cov, d_out_keys, d_out_counts, cap,
-                                         out_n, out_distinct);
-    std::vector<int> bits;
-    plan_levels(n, true, bits, 8192.0);
-    if (bits[0] > 9) {                               // the level-1 rings hold 512 bins: move the excess down
-        const int extra = bits[0] - 9;
-        bits[0] = 9;
-        if (bits.size() == 1) bits.push_back(extra); else bits[1] += extra;
-        if (bits[1] > MAX_BITS) { bits.push_back(bits[1] - MAX_BITS); bits[1] = MAX_BITS; }
-    }
-    Level lv{};
-    lv.bits = bits[0];
-    const int nb = 1 << lv.bits;
-    DevBuf segA, segB;
-    RFX_HIP(segA.alloc(((size_t)nb + 1) * 8, ctx->stream));
-    Rec *dst = (Rec *)ctx->ws_get(0, (size_t)n * sizeof(Rec));
-    if (!dst) { ctx->last_error = "workspace allocation failed"; return RFX_E_HIP; }
-    RFX_TRY(wide_level1(ctx, d_words, n_reads, wpr, nk, k, fc, lv, dst, segA.as<uint64_t>()));
-    DevBuf *seg_cur = &segA, *seg_next = &segB;
-    int64_t nseg = nb;
-    const Rec *cur = nullptr;
-    RFX_TRY(partition_record_levels<1>(ctx, dst, n, 0, bits, 1, lv.bits, &seg_cur, &seg_next, &nseg, &cur));
-    return finish_wide2(ctx, cur, (const uint64_t *)seg_cur->as<uint64_t>(), nseg, min_cov, max_cov, d_out_keys, d_out_counts,
-                        cap, out_n, out_distinct);
+// ---- the element path of k = 33..127 (W = 2..4) on the host
+
+// f(std::integral_constant<int, W>) for the word count of a k of the element path (k = 33..127, k % 32 != 0: W = 2..4)
+template <class F>
+static int with_word_count(int k, F &&f) {
+    const int W = k / 32 + 1;
+    if (k % 32 == 0 || W < 2 || W > 4) return RFX_E_ARG;
+    return W == 2 ? f(std::integral_constant<int, 2>{}) : W == 3 ? f(std::integral_constant<int, 3>{}) : f(std::integral_constant<int, 4>{});
 }
 
-// ---- k = 65..127 (W = 3, 4): the element path of k = 33..63 on W-word keys
-
+// the element leaves: nseg + 1 offsets, distinct W-word keys with counts out, unordered
 template <int W>
-static int finish_wide_n(rfx_ctx *ctx, const KmerW<W> *cur, const uint64_t *d_leaf_off, int64_t nseg, int min_cov, int max_cov,
-                         uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap, int64_t *out_n, int64_t *out_distinct) {
+static int finish_wide(rfx_ctx *ctx, const KmerW<W> *cur, const uint64_t *d_leaf_off, int64_t nseg, int min_cov, int max_cov,
+                       uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap, int64_t *out_n, int64_t *out_distinct) {
     DevBuf co_buf;
     RFX_HIP(co_buf.alloc(sizeof(CountOut), ctx->stream));
     RFX_HIP(hipMemsetAsync(co_buf.p, 0, sizeof(CountOut), ctx->stream));
@@ -4873,18 +4642,7 @@ static int finish_wide_n(rfx_ctx *ctx, const KmerW<W> *cur, const uint64_t *d_le
                            (uint32_t)(getenv("RFX_WIDE_PRESPLIT") ? atoi(getenv("RFX_WIDE_PRESPLIT")) : 0));
         RFX_HIP(hipGetLastError());
     }
-    CountOut co{};
-    RFX_HIP(hipMemcpyAsync(&co, co_buf.p, sizeof co, hipMemcpyDeviceToHost, ctx->stream));
-    RFX_TRY(sync_checked(ctx));
-    if (getenv("RFX_TRACE"))
-        fprintf(stderr, "wide leaves (W = %d): %lld buckets, %llu table passes, %llu overflowed\n", W, (long long)nseg, co.n_passes, co.n_overflow);
-    ctx->timing["stat_leaves"].launches += nseg; ctx->timing["stat_passes"].launches += (int64_t)co.n_passes;
-    ctx->timing["stat_overflows"].launches += (int64_t)co.n_overflow;
-    if (out_n) *out_n = (int64_t)co.n_out;
-    if (out_distinct) *out_distinct = (int64_t)co.n_distinct;
-    if (co.n_failed) { ctx->last_error = "leaf split depth exhausted"; return RFX_E_LIMIT; }
-    if ((int64_t)co.n_out > cap) return RFX_E_CAP;
-    return RFX_OK;
+    return wide_leaves_done(ctx, co_buf, nseg, cap, out_n, out_distinct);
 }
 
 constexpr double WIDE_N_TARGET = 8192.0;            // elements per leaf: a 4096-slot table; overflowing leaves split
@@ -4893,13 +4651,13 @@ constexpr double WIDE_N_TARGET = 8192.0;            // elements per leaf: a 4096
 template <int W>
 static int wide_level1_n(rfx_ctx *ctx, const WideSrcN &ws, const Level &lv, KmerW<W> *d_dst, uint64_t *d_seg_off) {
     const int nb = lv.n_owners > 0 ? lv.n_owners : (1 << lv.bits);
-    const unsigned G = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(ws.total, W2T), (int64_t)ctx->num_cu));
+    const unsigned G = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(ws.total, WL1_T), (int64_t)ctx->num_cu));
     DevBuf bh, scanned;
     RFX_HIP(bh.alloc((size_t)nb * G * 8, ctx->stream));
     RFX_HIP(scanned.alloc(((size_t)nb * G + 1) * 8, ctx->stream));
     {
         ScopedTimer t(ctx, "hist1");
-        hipLaunchKernelGGL(k_wn_hist<W>, dim3(G), dim3(W2T), 0, ctx->stream, ws, lv, bh.as<uint64_t>());
+        hipLaunchKernelGGL(k_wn_hist<W>, dim3(G), dim3(WL1_T), 0, ctx->stream, ws, lv, bh.as<uint64_t>());
         RFX_HIP(hipGetLastError());
     }
     RFX_TRY(exclusive_scan_u64(ctx, bh.as<uint64_t>(), scanned.as<uint64_t>(), (int64_t)nb * G));
@@ -4908,9 +4666,9 @@ static int wide_level1_n(rfx_ctx *ctx, const WideSrcN &ws, const Level &lv, Kmer
     RFX_HIP(hipGetLastError());
     {
         ScopedTimer t(ctx, "part1");
-        const size_t lds = (size_t)nb * (WNB * sizeof(KmerW<W>) + 16);
+        const size_t lds = (size_t)nb * (WL1_B<W> * sizeof(KmerW<W>) + 16);
         RFX_HIP(hipFuncSetAttribute((const void *)k_wn_scatter<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_wn_scatter<W>, dim3(G), dim3(W2T), lds, ctx->stream, ws, lv, (const uint64_t *)scanned.as<uint64_t>(),
+        hipLaunchKernelGGL(k_wn_scatter<W>, dim3(G), dim3(WL1_T), lds, ctx->stream, ws, lv, (const uint64_t *)scanned.as<uint64_t>(),
                            d_dst);
         RFX_HIP(hipGetLastError());
     }
@@ -4919,7 +4677,7 @@ static int wide_level1_n(rfx_ctx *ctx, const WideSrcN &ws, const Level &lv, Kmer
 
 static WideSrcN wide_src_n(const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc, const uint32_t *d_read_len,
                            int ec) {
-    WideSrcN ws{d_words, d_read_len, n_reads, nk, ceil_div(nk, W2SEG), 0, wpr, k, fc, ec};
+    WideSrcN ws{d_words, d_read_len, n_reads, nk, ceil_div(nk, WL1_SEG), 0, wpr, k, fc, ec};
     ws.total = n_reads * ws.segs;
     return ws;
 }
@@ -4932,28 +4690,26 @@ static int count_wide_n(rfx_ctx *ctx, const void *d_elems, int64_t n, int min_co
     plan_levels(n, false, bits, WIDE_N_TARGET);
     if (bits.empty()) bits.push_back(0);
     DevBuf segA, segB;
-    uint64_t seg_init[2] = {0, (uint64_t)n};
-    RFX_HIP(segA.alloc(2 * 8, ctx->stream));
-    RFX_HIP(hipMemcpyAsync(segA.p, seg_init, 16, hipMemcpyHostToDevice, ctx->stream));
-    RFX_TRY(sync_checked(ctx));
+    RFX_TRY(one_segment(ctx, segA, n));
     DevBuf *seg_cur = &segA, *seg_next = &segB;
     int64_t nseg = 1;
     const KmerW<W> *cur = nullptr;
-    RFX_TRY(partition_record_levels<W + 1>(ctx, (const KmerW<W> *)d_elems, n, 1, bits, 0, 0, &seg_cur, &seg_next, &nseg, &cur));
-    return finish_wide_n<W>(ctx, cur, (const uint64_t *)seg_cur->as<uint64_t>(), nseg, min_cov, max_cov, d_out_keys, d_out_counts,
-                            cap, out_n, out_distinct);
+    RFX_TRY(partition_record_levels<WIDE_MODE<W>>(ctx, (const KmerW<W> *)d_elems, n, 1, bits, 0, 0, &seg_cur, &seg_next, &nseg, &cur));
+    return finish_wide<W>(ctx, cur, (const uint64_t *)seg_cur->as<uint64_t>(), nseg, min_cov, max_cov, d_out_keys, d_out_counts,
+                          cap, out_n, out_distinct);
 }
 
-// k = 65..127: n canonical W-word k-mers (AoS elements of W words) -> distinct keys with counts, unordered
+// k = 33..127 (k % 32 != 0): n canonical W-word k-mers (AoS elements of W = 2..4 words; two-word elements at 16-byte
+// multiples) -> distinct keys with counts, unordered.  Same bucket structure as the k <= 31 record path: hash digits, exact
+// histograms, write-combining scatters, LDS-table leaves.
 int count_wide_elems(rfx_ctx *ctx, const void *d_elems, int64_t n, int k, int min_cov, int max_cov, uint64_t *d_out_keys,
                      int64_t *d_out_counts, int64_t cap, int64_t *out_n, int64_t *out_distinct) {
     if (out_n) *out_n = 0;
     if (out_distinct) *out_distinct = 0;
     if (n <= 0) return RFX_OK;
-    const int W = k / 32 + 1;
-    if (k % 32 == 0 || (W != 3 && W != 4)) return RFX_E_ARG;
-    return W == 3 ? count_wide_n<3>(ctx, d_elems, n, min_cov, max_cov, d_out_keys, d_out_counts, cap, out_n, out_distinct)
-                  : count_wide_n<4>(ctx, d_elems, n, min_cov, max_cov, d_out_keys, d_out_counts, cap, out_n, out_distinct);
+    return with_word_count(k, [&](auto w) {
+        return count_wide_n<decltype(w)::value>(ctx, d_elems, n, min_cov, max_cov, d_out_keys, d_out_counts, cap, out_n, out_distinct);
+    });
 }
 
 template <int W>
@@ -4985,9 +4741,9 @@ static int count_wide_n_reads(rfx_ctx *ctx, const WideSrcN &ws, int64_t n, int m
     DevBuf *seg_cur = &segA, *seg_next = &segB;
     int64_t nseg = nb;
     const KmerW<W> *cur = nullptr;
-    RFX_TRY(partition_record_levels<W + 1>(ctx, dst, n, 0, bits, 1, lv.bits, &seg_cur, &seg_next, &nseg, &cur));
-    return finish_wide_n<W>(ctx, cur, (const uint64_t *)seg_cur->as<uint64_t>(), nseg, min_cov, max_cov, d_out_keys, d_out_counts,
-                            cap, out_n, out_distinct);
+    RFX_TRY(partition_record_levels<WIDE_MODE<W>>(ctx, dst, n, 0, bits, 1, lv.bits, &seg_cur, &seg_next, &nseg, &cur));
+    return finish_wide<W>(ctx, cur, (const uint64_t *)seg_cur->as<uint64_t>(), nseg, min_cov, max_cov, d_out_keys, d_out_counts,
+                          cap, out_n, out_distinct);
 }
 
 // k = 65..127 from packed reads, uniform (d_read_len == nullptr; n_inst unused) or ragged (nk = the longest read's k-mers, n_inst
@@ -5000,36 +4756,70 @@ int count_wide_n_from_reads(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_rea
     if (out_distinct) *out_distinct = 0;
     const int64_t n = d_read_len ? n_inst : nk * n_reads;
     if (n <= 0 || nk <= 0) return RFX_OK;
-    const int W = k / 32 + 1;
-    if (k % 32 == 0 || (W != 3 && W != 4)) return RFX_E_ARG;
+    if (k < 65) return RFX_E_ARG;                    // (k = 33..63 comes through count_wide2_reads: records first)
     const WideSrcN ws = wide_src_n(d_words, n_reads, wpr, nk, k, fc, d_read_len, ec);
-    return W == 3 ? count_wide_n_reads<3>(ctx, ws, n, min_cov, max_cov, d_out_keys, d_out_counts, cap, out_n, out_distinct)
-                  : count_wide_n_reads<4>(ctx, ws, n, min_cov, max_cov, d_out_keys, d_out_counts, cap, out_n, out_distinct);
+    return with_word_count(k, [&](auto w) {
+        return count_wide_n_reads<decltype(w)::value>(ctx, ws, n, min_cov, max_cov, d_out_keys, d_out_counts, cap, out_n, out_distinct);
+    });
 }
 
-// multi-GPU support: the W-word k-mers (W = 3, 4) of packed reads (uniform, or per-read lengths with nk = the longest read's
+// multi-GPU support: the W-word k-mers (W = 2..4) of packed reads (uniform, or per-read lengths with nk = the longest read's
 // k-mers) grouped by owning rank: d_out holds them as AoS W-word elements, d_owner_off[n_owners + 1] (and h_owner_off) the
 // groups' offsets.  Same kernels as the count's level 1, digit = mulhi(hash, n_owners).
 int bucket_wide_n_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
                            const uint32_t *d_read_len, int ec, int n_owners, void *d_out, int64_t *d_owner_off, int64_t *h_owner_off) {
     StageArena stage_arena(ctx, (size_t)256 << 20);       // temporaries of this call (see StageArena)
-    const int W = k / 32 + 1;
-    if (n_owners < 1 || n_owners > 64 || k % 32 == 0 || (W != 3 && W != 4)) return RFX_E_ARG;
-    if (nk <= 0 || n_reads <= 0) {
-        RFX_HIP(hipMemsetAsync(d_owner_off, 0, (size_t)(n_owners + 1) * 8, ctx->stream));
-        if (h_owner_off) memset(h_owner_off, 0, (size_t)(n_owners + 1) * 8);
+    if (n_owners < 1 || n_owners > 64) return RFX_E_ARG;
+    return with_word_count(k, [&](auto w) -> int {
+        constexpr int W = decltype(w)::value;
+        if (nk <= 0 || n_reads <= 0) return zero_owner_offsets(ctx, n_owners, d_owner_off, h_owner_off);
+        Level lv{};
+        lv.n_owners = n_owners;
+        const WideSrcN ws = wide_src_n(d_words, n_reads, wpr, nk, k, fc, d_read_len, ec);
+        RFX_TRY(wide_level1_n<W>(ctx, ws, lv, (KmerW<W> *)d_out, reinterpret_cast<uint64_t *>(d_owner_off)));
+        if (h_owner_off) {
+            RFX_HIP(hipMemcpyAsync(h_owner_off, d_owner_off, (size_t)(n_owners + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+            RFX_TRY(sync_checked(ctx));
+        }
         return RFX_OK;
-    }
-    Level lv{};
-    lv.n_owners = n_owners;
-    const WideSrcN ws = wide_src_n(d_words, n_reads, wpr, nk, k, fc, d_read_len, ec);
-    if (W == 3) RFX_TRY(wide_level1_n<3>(ctx, ws, lv, (KmerW<3> *)d_out, reinterpret_cast<uint64_t *>(d_owner_off)));
-    else RFX_TRY(wide_level1_n<4>(ctx, ws, lv, (KmerW<4> *)d_out, reinterpret_cast<uint64_t *>(d_owner_off)));
-    if (h_owner_off) {
-        RFX_HIP(hipMemcpyAsync(h_owner_off, d_owner_off, (size_t)(n_owners + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-        RFX_TRY(sync_checked(ctx));
-    }
+    });
+}
+
+// the two-word k-mers of packed uniform reads (k = 33..63), grouped by owning rank into the caller's cap_elems elements
+int bucket_wide_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
+                         int n_owners, void *d_out, int64_t cap_elems, int64_t *d_owner_off, int64_t *h_owner_off) {
+    if (n_owners < 1 || n_owners > 64) return RFX_E_ARG;
+    const int64_t n = nk * n_reads;
+    if (n > cap_elems) return RFX_E_CAP;
+    if (n <= 0) return zero_owner_offsets(ctx, n_owners, d_owner_off, h_owner_off);
+    ctx->timing.clear();
+    RFX_TRY(bucket_wide_n_by_owner(ctx, d_words, n_reads, wpr, nk, k, fc, nullptr, 0, n_owners, d_out, d_owner_off, h_owner_off));
+    ScopedTimer::collect(ctx);
     return RFX_OK;
+}
+
+// k = 33..63 from packed reads of one length (d_read_len == nullptr) or of per-read lengths (nk = the longest read's
+// k-mers, n_inst = the instances of all, end_clip the clip they were counted with): level 1 straight from the reads, then
+// the element path's levels and leaves (count_wide_n_reads<2>).  Ragged reads always take the record path: RFX_WIDE_RECORDS=0
+// does not apply to them.
+int count_wide2_reads(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
+                      int min_cov, int max_cov, uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap, int64_t *out_n,
+                      int64_t *out_distinct, const uint32_t *d_read_len, int ec, int64_t n_inst) {
+    StageArena stage_arena(ctx, (size_t)256 << 20);       // temporaries of this call (see StageArena)
+    if (out_n) *out_n = 0;
+    if (out_distinct) *out_distinct = 0;
+    const int64_t n = d_read_len ? n_inst : nk * n_reads;
+    if (n <= 0 || nk <= 0) return RFX_OK;
+    if (d_read_len) {
+        if (k < 33 || k > 63) return RFX_E_ARG;
+        return count_wide2_reads_records(ctx, d_words, n_reads, wpr, nk, k, fc, min_cov, max_cov, d_out_keys, d_out_counts, cap,
+                                         out_n, out_distinct, d_read_len, ec, n_inst);
+    }
+    if (wide_records_enabled(k))
+        return count_wide2_reads_records(ctx, d_words, n_reads, wpr, nk, k, fc, min_cov, max_cov, d_out_keys, d_out_counts, cap,
+                                         out_n, out_distinct);
+    return count_wide_n_reads<2>(ctx, wide_src_n(d_words, n_reads, wpr, nk, k, fc, nullptr, 0), n, min_cov, max_cov, d_out_keys,
+                                 d_out_counts, cap, out_n, out_distinct);
 }
 
 int synth_genome(rfx_ctx *ctx, uint64_t seed, int64_t genome_len, uint64_t *d_genome) {

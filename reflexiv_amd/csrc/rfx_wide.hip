@@ -10,8 +10,8 @@
 // structure of arrays (word w of k-mer i at [w*N + i]); the C ABI speaks the reference's array of
 // W longs per k-mer.
 //
-// k = 33..127 (W = 2..4) count through the bucketed LDS-table path of rfx_kmer.hip (count_wide2, count_wide_elems;
-// DESIGN.md sections 8, 12); only the survivors are sorted here (order_wide).  W >= 5 (k >= 128, beyond the CLI's range)
+// k = 33..127 (W = 2..4) count through the one bucketed LDS-table element path of rfx_kmer.hip (count_wide_elems on AoS
+// elements; from reads, k = 33..63 takes its super-k-mer records first: DESIGN.md sections 8, 12); only the survivors are sorted here (order_wide).  W >= 5 (k >= 128, beyond the CLI's range)
 // keeps the plain exact formulation -- LSD radix sort of the W words through a 32-bit permutation, equal-key run heads,
 // scan, compaction: ~70 B of workspace per instance, N < 2^32 per call.  
 #include "rfx_internal.h"
@@ -279,7 +279,7 @@ bool wide_elem_path(int k) {
 }
 
 // k = 33..127 (W = 2..4): the bucketed path (hash digits, write-combining scatters, LDS-table leaves with W-word keys:
-// rfx_kmer.hip count_wide2 / count_wide_elems) on N AoS elements of W words; the survivors are then put in ascending order.
+// rfx_kmer.hip count_wide_elems) on N AoS elements of W words; the survivors are then put in ascending order.
 // (W = 2 keeps its limit of 2^32 - 1 instances per call; W = 3, 4 have none.)
 int count_filter_w2(rfx_ctx *ctx, const uint64_t *d_elems, int64_t N, int k, int min_cov, int max_cov,
                     uint64_t *d_out_keys, int64_t *d_out_counts, int64_t cap, int64_t *out_n, int64_t *out_distinct) {
@@ -287,13 +287,8 @@ int count_filter_w2(rfx_ctx *ctx, const uint64_t *d_elems, int64_t N, int k, int
     if (out_distinct) *out_distinct = 0;
     if (N <= 0) return RFX_OK;
     int64_t m = 0;
-    int st;
-    if (wide_fast_path(k)) {
-        if (N >= (1LL << 32)) { ctx->last_error = "k > 31 count: at most 2^32-1 instances per call"; return RFX_E_ARG; }
-        st = count_wide2(ctx, d_elems, N, min_cov, max_cov, d_out_keys, d_out_counts, cap, &m, out_distinct);
-    } else {
-        st = count_wide_elems(ctx, d_elems, N, k, min_cov, max_cov, d_out_keys, d_out_counts, cap, &m, out_distinct);
-    }
+    if (wide_fast_path(k) && N >= (1LL << 32)) { ctx->last_error = "k > 31 count: at most 2^32-1 instances per call"; return RFX_E_ARG; }
+    const int st = count_wide_elems(ctx, d_elems, N, k, min_cov, max_cov, d_out_keys, d_out_counts, cap, &m, out_distinct);
     *out_n = m;
     if (st != RFX_OK) return st;
     return order_wide2(ctx, d_out_keys, d_out_counts, m, k);

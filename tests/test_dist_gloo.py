@@ -33,7 +33,7 @@ def owner_of(kmers, n):
 
 
 def wide_hash(hi, lo):
-    """reflexiv_amd/csrc/rfx_kmer.hip wide_hash (two-word k-mers, k = 33..63)"""
+    """reflexiv_amd/csrc/rfx_kmer.hip wide_hash_n at W = 2 (two-word k-mers, k = 33..63)"""
     with np.errstate(over="ignore"):
         x = hi.astype(np.uint64) ^ (lo.astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15))
         x = x * np.uint64(0xD6E8FEB86659FD93)

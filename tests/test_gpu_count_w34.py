@@ -1,5 +1,6 @@
-"""Three- and four-word k-mers (k = 65..127, not 96) on the device: the element path of k = 33..63 on W = 3, 4 words
-(level 1 straight from the packed reads, record levels on a hash of all words, LDS-table leaves with W key planes).
+"""Three- and four-word k-mers (k = 65..127, not 96) on the device: the W-word element path at W = 3, 4 (W = 2:
+tests/test_gpu_count_w2_elems.py;
+level 1 straight from the packed reads, record levels on a hash of all words, LDS-table leaves with W key planes).
 rfx_dev_count_reads_w / rfx_dev_count_reads_ragged_w against the oracle's k > 31 counter, rfx_assemble_reads against the
 reference's two-step route (`counter -kmer K`, then `run -kmerc ... -kmer K`) and the reference-made k = 95 vector, and the
 CLI's --resident twins.  Bit-exact (integer work)."""
@@ -135,11 +136,9 @@ def test_uniform_count_runs_the_leaf_kernels(rfx, torch_mod):
     assert np.array_equal(dc[:m].cpu().numpy(), wc)
 
 
-@pytest.mark.parametrize("k", [67, 95, 100, 127])
-def test_all_ones_and_all_zeros_middle_words(rfx, torch_mod, k):
-    """runs of >= 32 T's and A's (and mixed runs) on both strands, so that word 1 (and word 2 at W = 4) -- and, from k = 64
-    on, word 0 -- is all ones or all zeros: such keys must never share a table slot (the leaves claim slots by the last
-    word, which is never all ones)"""
+def t_and_a_run_reads(k, uniform_len=None):
+    """1200 reads of runs of 30..79 T's and A's, short mixed runs and random stretches, on both strands; k..219 bases each, or
+    uniform_len"""
     rng = np.random.default_rng(k)
     reads = []
     for i in range(1200):
@@ -154,9 +153,17 @@ def test_all_ones_and_all_zeros_middle_words(rfx, torch_mod, k):
                 parts.append("".join(rng.choice(list("AT"), size=int(rng.integers(1, 6)))))
             else:
                 parts.append("".join(rng.choice(list("ACGT"), size=int(rng.integers(1, 20)))))
-        s = "".join(parts)[:int(rng.integers(k, 220))]
+        s = "".join(parts)[:uniform_len or int(rng.integers(k, 220))]
         reads.append(s if rng.random() < 0.5 else "".join(COMP[c] for c in reversed(s)))
-    bases, off = reads_of(reads)
+    return reads_of(reads)
+
+
+@pytest.mark.parametrize("k", [67, 95, 100, 127])
+def test_all_ones_and_all_zeros_middle_words(rfx, torch_mod, k):
+    """runs of >= 32 T's and A's (and mixed runs) on both strands, so that word 1 (and word 2 at W = 4) -- and, from k = 64
+    on, word 0 -- is all ones or all zeros: such keys must never share a table slot (the leaves claim slots by the last
+    word, which is never all ones)"""
+    bases, off = t_and_a_run_reads(k)
     km = O.extract_canon_w(bases, off, k)
     W = k // 32 + 1
     ones = np.uint64(0xFFFFFFFFFFFFFFFF)

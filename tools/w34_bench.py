@@ -5,9 +5,11 @@ measurement runs in a child process of its own; the children of the two builds a
 --reps timed calls.  Prints one JSON line: per k and build the median, min and max ms, instances, ns per instance, the
 workspace high-water (rfx_ctx_workspace_bytes, and hipMemGetInfo's used bytes), the fraction of 8 TB/s that the algorithmic
 bytes make (0.25 + 16 W B per instance, 8 W + 8 B per survivor), and the sha256 of the survivors' keys
-and counts, which must be the same on both sides.
+and counts, which must be the same on both sides; and the medians of the stages' device times (ctx timing: hist1, part1, the
+later levels, leaf, sort).  --wide-records 0 sets RFX_WIDE_RECORDS=0 in the children, so that k = 33..63 (--ks 63,47) takes the
+same element path at W = 2 instead of its super-k-mer records.
 
-    python tools/w34_bench.py [--ks 81,95,97] [--gbp 5] [--reps 5] [--warmup 2] [--rounds 2] [--ab ROOT]"""
+    python tools/w34_bench.py [--ks 81,95,97] [--wide-records 0] [--gbp 5] [--reps 5] [--warmup 2] [--rounds 2] [--ab ROOT]"""
 import argparse
 import json
 import os
@@ -41,7 +43,7 @@ def child(a):
     dc = torch.empty(cap, dtype=torch.int64, device="cuda")
     torch.cuda.synchronize()
     free0, total = torch.cuda.mem_get_info()
-    times, used_hw, ws_hw, r = [], 0, 0, None
+    times, stages, used_hw, ws_hw, r = [], [], 0, 0, None
     for rep in range(a.warmup + a.reps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -53,13 +55,18 @@ def child(a):
         ws_hw = max(ws_hw, rfx.workspace_bytes())
         if rep >= a.warmup:
             times.append(dt)
+            t = rfx.count_timing()
+            stages.append({"hist1": t.get("hist1", (0, 0))[0], "part1": t.get("part1", (0, 0))[0],
+                           "levels": sum(v[0] for nm, v in t.items()
+                                         if nm.startswith(("hist", "part")) and nm not in ("hist1", "part1")),
+                           "leaf": t.get("leaf", (0, 0))[0], "sort": t.get("sort", (0, 0))[0]})
     m, nd, inst = r
     h = hashlib.sha256()
     h.update(dk[:W * m].cpu().numpy().tobytes())
     h.update(dc[:m].cpu().numpy().tobytes())
     t = rfx.count_timing()
     rfx.close()
-    print(json.dumps({"times": times, "instances": inst, "distinct": nd, "kept": m, "sha256": h.hexdigest(),
+    print(json.dumps({"times": times, "stages": stages, "instances": inst, "distinct": nd, "kept": m, "sha256": h.hexdigest(),
                       "workspace_bytes": ws_hw, "mem_used_bytes": used_hw, "leaf": "leaf" in t, "sort_path": "count_w" in t}))
 
 
@@ -69,13 +76,15 @@ def summarise(k, runs):
     r0 = runs[-1]
     med = ts[len(ts) // 2]
     algo = (0.25 + 16 * W) * r0["instances"] + (8 * W + 8) * r0["kept"]
+    st = [x for r in runs for x in r["stages"]]
+    stage_ms = {nm: round(sorted(x[nm] for x in st)[len(st) // 2], 2) for nm in st[0]}
     return {"ms_median": round(med, 2), "ms_min": round(ts[0], 2), "ms_max": round(ts[-1], 2), "reps": len(ts),
             "instances": r0["instances"], "distinct": r0["distinct"], "kept": r0["kept"],
             "ns_per_instance": round(med * 1e6 / max(1, r0["instances"]), 4),
             "workspace_gib": round(max(r["workspace_bytes"] for r in runs) / 2**30, 2),
             "mem_used_gib": round(max(r["mem_used_bytes"] for r in runs) / 2**30, 2),
             "frac_of_8TBps": round(algo / (med * 1e-3) / 8e12, 4), "sha256": r0["sha256"], "leaf": r0["leaf"],
-            "sort_path": r0["sort_path"]}
+            "sort_path": r0["sort_path"], "stage_ms_median": stage_ms}
 
 
 def main():
@@ -89,6 +98,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--wide-records", choices=["0", "1"], default=None, help="RFX_WIDE_RECORDS of the children (k = 33..63)")
     ap.add_argument("--ab", default=None, help="the other build's root (holds reflexiv_amd/)")
     ap.add_argument("--root", default=HERE)
     ap.add_argument("--child", action="store_true")
@@ -99,7 +109,7 @@ def main():
     sides = {"this": HERE}
     if a.ab:
         sides["other"] = os.path.abspath(a.ab)
-    out = {"gbp": a.gbp, "cover": a.cover, "reps_per_child": a.reps, "warmup": a.warmup, "rounds": a.rounds}
+    out = {"gbp": a.gbp, "cover": a.cover, "wide_records": a.wide_records, "reps_per_child": a.reps, "warmup": a.warmup, "rounds": a.rounds}
     for k in [int(x) for x in a.ks.split(",")]:
         runs = {s: [] for s in sides}
         for rnd in range(a.rounds):
@@ -107,7 +117,8 @@ def main():
                 cmd = [sys.executable, os.path.abspath(__file__), "--child", "--root", root, "--k", str(k), "--gbp", str(a.gbp),
                        "--genome", str(a.genome), "--cover", str(a.cover), "--reps", str(a.reps), "--warmup", str(a.warmup),
                        "--seed", str(a.seed)]
-                p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout)
+                env = dict(os.environ, **({"RFX_WIDE_RECORDS": a.wide_records} if a.wide_records else {}))
+                p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout, env=env)
                 if p.returncode != 0:
                     out[f"k{k}_{s}_error"] = (p.stdout + p.stderr)[-1500:]
                     print(json.dumps(out), flush=True)
