@@ -1589,17 +1589,40 @@ __device__ __forceinline__ unsigned rec_digit(uint32_t hdr, int used, int bits) 
 // evaluate 68, pays the per-segment work once, and -- what counts downstream -- a read is cut into records at half as
 // many places that only depend on where the read happened to start: 19 % fewer records, and more of them identical from
 // read to read.  Runs stay <= 16 windows (four bits in the record): a longer one is cut 16 windows after its start.
+//
+// SEG = 32 MERGES ACROSS SEGMENT EDGES.  Nine times in ten the minimiser does not change where a thread's 32 windows end,
+// and the cut there is one more record for every level behind this one.  So the TAIL of a full segment (its last run after
+// the 16-window cut, t windows) and the HEAD of the same read's next segment (its first run after the cut, b windows) are
+// one run when their keys are equal: the tail's owner emits min(16, t + b) windows -- the cap counts from where the run
+// started -- and the head starts that many minus t windows later, or is dropped when nothing is left of it.  A full
+// segment has at least two runs (32 windows, none longer than 16), so head and tail are different runs and what a lane
+// does never depends on more than its two neighbours.  Segments of a read are consecutive lanes: the four values (tail key
+// and length, head key and length) and the bases past the thread's 64 (the top of the next lane's `lo`, *nx_out) are
+// swapped with the neighbour lanes, and both lanes evaluate the same predicate on the same values.  Nothing merges across
+// a wave's edge (a read of 5 segments straddles one; any cut is correct), and a segment without windows (ragged sets, the
+// lanes past the last read) offers nothing.  EVERY LANE OF THE WAVE MUST CALL with SEG = 32 (nk_r = 0 where there is no
+// segment): the exchange reads no register of an inactive lane.
+// What holds in either form, and is all that the levels behind rely on:
+//   * every window of every read lies in exactly one record;
+//   * a record has 1..16 windows, all with the same minimiser key;
+//   * the bucket is the hash of that key only.
+// Which lane emits a record does not matter downstream.
 template <int W, bool RUNLOOP, int SEG = 16, class F>
 __device__ __forceinline__ void seg_runs(const ReadSrc &s, int nk_r, int sgm, const uint64_t (&w)[3], F &&emit,
-                                         uint64_t *hi_out, uint64_t *lo_out, uint32_t *wm_lds = nullptr) {
+                                         uint64_t *hi_out, uint64_t *lo_out, uint32_t *wm_lds = nullptr, uint32_t *nx_out = nullptr) {
     static_assert(SEG == 16 || SEG == 32, "segment");
     constexpr int PK = SEG;                        // (shadows the file-wide 16 inside this function)
+    constexpr bool MERGE = SEG == 32;
+    static_assert(!MERGE || RUNLOOP, "the merged cut walks the run-start bits");
     constexpr int NM = PK + W - 1;                 // m-mers a segment can touch (<= 34, or <= 50)
     static_assert(NM + SK_M - 1 <= 64, "the segment's bases lie in (hi, lo)");
     const int p0 = sgm * PK;
     int v = nk_r - p0;
     v = v > PK ? PK : v;
-    if (v <= 0) return;                            // a short read of a ragged set: no window in this segment
+    if constexpr (MERGE) {
+        v = v < 0 ? 0 : v;
+        if (!__any(v > 0)) return;                 // (the same for the whole wave)
+    } else if (v <= 0) return;                     // a short read of a ragged set: no window in this segment
     const int sh = 2 * ((s.fc + p0) & 31);
     const uint64_t hi = sh ? (w[0] << sh) | (w[1] >> (64 - sh)) : w[0];
     const uint64_t lo = sh ? (w[1] << sh) | (w[2] >> (64 - sh)) : w[1];
@@ -1667,15 +1690,38 @@ __device__ __forceinline__ void seg_runs(const ReadSrc &s, int nk_r, int sgm, co
     uint32_t starts = 1u;
 #pragma unroll
     for (int i = 1; i < PK; i++) starts |= (uint32_t)(wm[i] != wm[i - 1]) << i;
-    starts &= 0xffffffffu >> (32 - v);                 // (1 <= v <= PK: the windows the read has in this segment)
+    const uint32_t vmask = v ? 0xffffffffu >> (32 - v) : 0u;    // (v <= PK: the windows the read has in this segment)
+    starts &= vmask;
     if constexpr (PK > 16) {
         // no run longer than 16 windows: `cov` = the windows within 15 of a start at or before them; the lowest window
         // that is not lies exactly 16 after a start and becomes one (bit 0 is set, so whatever is not covered lies in
         // the upper half, and the new start covers all that is left of it)
         uint32_t cov = starts;
         cov |= cov << 1; cov |= cov << 2; cov |= cov << 4; cov |= cov << 8;
-        const uint32_t unc = ~cov & (0xffffffffu >> (32 - v));
+        const uint32_t unc = ~cov & vmask;
         starts |= unc & (0u - unc);
+    }
+    int vend = v;                                      // where the segment's last run ends
+    if constexpr (MERGE) {
+        const int lane = (int)(threadIdx.x & 63);
+        const uint32_t rest = starts & (starts - 1);
+        const int b = !v ? 0 : rest ? __ffs((int)rest) - 1 : v;            // head: 1..16 windows, 0 = none
+        const int t = v == PK ? __clz((int)starts) + 1 : 0;                // tail of a FULL segment: 1..16 windows, 0 = none
+        const uint32_t hk = wm[0], tk = wm[PK - 1];
+        // down: the next lane's head key, and its head length below the 13 bases that follow this lane's 64 (a record
+        // holds 46 bases from a window <= 31); up: the previous lane's tail
+        const uint32_t hk_n = (uint32_t)__shfl_down((int)hk, 1);
+        const uint32_t pk_n = (uint32_t)__shfl_down((int)(((uint32_t)(lo >> 32) & 0xFFFFFFC0u) | (uint32_t)b), 1);
+        const uint32_t tk_p = (uint32_t)__shfl_up((int)tk, 1);
+        const int t_p = __shfl_up(t, 1);
+        const bool next_same = lane < 63 && sgm + 1 < s.segs, prev_same = lane > 0 && sgm > 0;   // the same read, the same wave
+        const int b_n = (int)(pk_n & 31u);
+        if (nx_out) *nx_out = next_same ? pk_n & 0xFFFFFFC0u : 0u;
+        if (next_same && t > 0 && b_n > 0 && tk == hk_n) vend = v + (16 - t < b_n ? 16 - t : b_n);
+        if (prev_same && t_p > 0 && b > 0 && tk_p == hk) {
+            const int a = 16 - t_p < b ? 16 - t_p : b;                     // windows of the head that the tail's owner emits
+            if (a > 0) starts = (starts & ~1u) | (a < b ? 1u << a : 0u);
+        }
     }
     if (wm_lds) {
 #pragma unroll
@@ -1699,7 +1745,7 @@ __device__ __forceinline__ void seg_runs(const ReadSrc &s, int nk_r, int sgm, co
     while (starts) {
         const int i0 = __ffs((int)starts) - 1;
         starts &= starts - 1;
-        const int i1 = starts ? __ffs((int)starts) - 1 : v;
+        const int i1 = starts ? __ffs((int)starts) - 1 : vend;
         // wm[i0]: a register array cannot be indexed at run time -- through the thread's own LDS column
         // when the caller has one (16 conflict-free stores, one load per run), else a compare-select chain
         uint32_t key;
@@ -1960,15 +2006,20 @@ __global__ __launch_bounds__(SKT) void k_sk_sample_hist(ReadSrc s, Level lv, int
     __syncthreads();
     const int64_t ntile = (s.n_threads + SKT - 1) / SKT;
     for (int64_t T = (int64_t)blockIdx.x * sample; T < ntile; T += (int64_t)gridDim.x * sample) {
+        // (32 windows per thread: the runs the sweep will cut, merged across segment edges -- every lane calls seg_runs)
         const int64_t g = T * SKT + threadIdx.x;
-        if (g < s.n_threads) {
-            SegPos q;
+        const bool in = g < s.n_threads;
+        SegPos q{0, 0};
+        int nk_r = 0;
+        uint64_t w[3] = {0, 0, 0}, hi, lo;
+        if (in) {
             q.r = g / s.segs;
             q.sgm = (int)(g - q.r * s.segs);
-            uint64_t w[3], hi, lo;
             seg_load<SEG>(s, q, w);
-            seg_runs<W, false, SEG>(s, read_nk<WIDE>(s, q.r), q.sgm, w, [&](int, int, uint32_t canon) { atomicAdd(&h[sk_digit(canon, lv)], 1u); }, &hi, &lo);
+            nk_r = read_nk<WIDE>(s, q.r);
         }
+        if (SEG == 32 || in)
+            seg_runs<W, SEG == 32, SEG>(s, nk_r, q.sgm, w, [&](int, int, uint32_t canon) { atomicAdd(&h[sk_digit(canon, lv)], 1u); }, &hi, &lo);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < nb; i += SKT) if (h[i]) atomicAdd(&hist[i], (unsigned long long)h[i]);
@@ -2113,14 +2164,22 @@ __global__ __launch_bounds__((OsGeo<SEG, WIDE>::T), WIDE || SEG > 16 ? 4 : 8) vo
         const bool ask = my_d < nb && pbase[my_d] == NONE;
         uint32_t req = DUMP;
         if (ask) req = grab(my_d);
+        // (SEG = 32: every lane calls seg_runs, which swaps run ends with the neighbour lanes; a lane past the last
+        // segment brings no windows)
         const int64_t g = T * SKT + threadIdx.x;
-        if (g < s.n_threads) {
-            SegPos q;
+        const bool in = g < s.n_threads;
+        SegPos q{0, 0};
+        int nk_r = 0;
+        uint64_t w[3] = {0, 0, 0}, hi = 0, lo = 0;
+        uint32_t past = 0;                              // the 13 bases after (hi, lo), from the next lane (SEG = 32)
+        if (in) {
             q.r = g / s.segs;
             q.sgm = (int)(g - q.r * s.segs);
-            uint64_t w[3], hi = 0, lo = 0;
             seg_load<SEG>(s, q, w);
-            seg_runs<W, true, SEG>(s, read_nk<WIDE>(s, q.r), q.sgm, w, [&](int i0, int n, uint32_t canon) {
+            nk_r = read_nk<WIDE>(s, q.r);
+        }
+        if (SEG == 32 || in) {
+            seg_runs<W, true, SEG>(s, nk_r, q.sgm, w, [&](int i0, int n, uint32_t canon) {
                 const uint64_t hh = mmer_hash64(canon);
                 const uint32_t hdr = (uint32_t)((hh << OWNER_BITS) >> 32);
                 // (by owner: the owner's bucket is 2^sub_bits bins here, so that a round still brings a bin a handful of
@@ -2140,9 +2199,11 @@ __global__ __launch_bounds__((OsGeo<SEG, WIDE>::T), WIDE || SEG > 16 ? 4 : 8) vo
                     r.b2 = sft ? (a2 << sft) | (a3 >> (64 - sft)) : a2;
                     r.hd = ((uint64_t)(n - 1) << 32) | (uint64_t)hdr;
                 } else {
+                    // (a run that starts after window 18 reaches into the next lane's bases -- a merged tail needs them)
                     const int sft = 2 * i0;
+                    const uint64_t x = (uint64_t)past << 32;
                     r.w0 = sft ? (hi << sft) | (lo >> (64 - sft)) : hi;
-                    r.w1 = ((lo << sft) & 0xFFFFFFF000000000ULL) | ((uint64_t)(n - 1) << 32) | (uint64_t)hdr;
+                    r.w1 = ((sft ? (lo << sft) | (x >> (64 - sft)) : lo) & 0xFFFFFFF000000000ULL) | ((uint64_t)(n - 1) << 32) | (uint64_t)hdr;
                 }
                 const uint32_t pos = atomicAdd(&tail[d], 1u);
                 if (pos - head[d] < (uint32_t)SKB) buf[(size_t)d * SKB + (pos & (SKB - 1))] = r;
@@ -2151,7 +2212,7 @@ __global__ __launch_bounds__((OsGeo<SEG, WIDE>::T), WIDE || SEG > 16 ? 4 : 8) vo
                     if (pos - cs < 2u * OSE) out[phys(pos, cs, cbase[d], nbase[d])] = r;
                     else *os.overflow = 1;             // more than the two extents in hand take: the caller starts over
                 }
-            }, &hi, &lo);
+            }, &hi, &lo, nullptr, &past);
         }
         if (threadIdx.x == SKT - 1) tile_lds[rnd & 1] = t_next;
         if (ask) pbase[my_d] = req;
@@ -3652,6 +3713,7 @@ static int records_onesweep(rfx_ctx *ctx, const ReadSrc &rsrc_in, const Level &l
     if (h_over) return RFX_OK;
     *out_recs = dst;
     *n_recs = (int64_t)h_tot[1];
+    ctx->timing["stat_records"].launches += (int64_t)h_tot[1];           // records the sweep wrote (the merged cut's yardstick)
     *done = true;
     return RFX_OK;
 }
