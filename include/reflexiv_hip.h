@@ -22,7 +22,8 @@
  *    *out_words, *out_len) hold the needed size -- what to call again with.  What else was
  *    written depends on the family (DESIGN.md "Capacity contract"):
  *      - rfx_extract_canon[_w], rfx_count_filter[_w], every rfx_records and rfx_dyn_records
- *        output (host and rfx_dev_*), the survivor arrays of rfx_dedup_contigs, and the sort
+ *        output (host and rfx_dev_*), every rfx_contigs_packed output, the survivor arrays of
+ *        rfx_dedup_contigs and rfx_dev_contigs_unpack, and the sort
  *        path of rfx_dev_count_reads_w (k >= 129) check before they copy or emit: no output
  *        array was written;
  *      - rfx_dev_count_reads[_ragged][_w], rfx_dev_count_kmers, rfx_dev_count_records,
@@ -31,7 +32,8 @@
  *        survivors only after the leaves have emitted them: the first `cap` entries of the
  *        output arrays are unspecified, nothing at or past `cap` is written;
  *      - text buffers (rfx_contigs_text, rfx_dev_assemble[_w], rfx_assemble_counts_w,
- *        rfx_assemble_reads, the sharded drivers, rfx_dedup_contigs / rfx_dedup_contig_text)
+ *        rfx_assemble_reads, the sharded drivers, rfx_dedup_contigs / rfx_dedup_contig_text,
+ *        rfx_dev_contigs_to_text)
  *        are filled up to `cap`: the bytes below it are unspecified (a prefix of the text),
  *        nothing at or past `cap` is written;
  *  - re-entrant per context; one context = one device + one HIP stream.
@@ -531,6 +533,52 @@ int rfx_dedup_contigs(rfx_ctx *ctx, const uint8_t *bases_ascii, const int64_t *c
                       char *text, int64_t text_cap, int64_t *text_len, int64_t *round_n);
 int rfx_dedup_contig_text(rfx_ctx *ctx, const char *contig_text, int64_t len, int min_contig, char *out, int64_t cap,
                           int64_t *out_len, int64_t *out_contigs, int64_t *round_n);
+
+/* The same de-duplication on a PACKED contig set that stays in HBM.  Every pointer of rfx_contigs_packed
+ * is a DEVICE pointer into arrays the caller allocated; the struct itself lives on the host.  Bases are 2 bits each, 32 to a
+ * word, the first in the two highest bits -- the convention of the 2-bit read store and of rfx_dyn_packed --, codes A0 C1 G2,
+ * anything else 3 (nucleotideValue), so a letter that is not ACGT comes back as T.  Every contig starts on a word and
+ * word_off[0] = 0.  INVARIANT: every bit past a contig's last base is 0; every producer writes those bits (it never relies on
+ * zeroed memory).  The two host forms above are pack (or from-text) -> these kernels -> unpack / to-text.
+ *   rfx_dev_contigs_pack       host ASCII + offsets -> the packed set; needs cap_n >= n and cap_words >= n + bases / 32 at most
+ *   rfx_dev_contigs_unpack     the packed set -> host ASCII + offsets (*out_n contigs; RFX_E_CAP when a capacity is short,
+ *                              nothing written but *out_n)
+ *   rfx_dev_contigs_from_text  the contig text the path writes, already in HBM (d_text, len bytes) -> the packed set: a line
+ *                              that begins with '>' opens a contig, every other line behind the first header is that contig's
+ *                              bases at any line width, '\r' is dropped, lines ahead of the first header are ignored, a header
+ *                              followed by a header or by the end is a contig of 0 bases that keeps its position (ids are
+ *                              positions).  Needs cap_n >= the headers and cap_words >= headers + len / 32 at most; a text of
+ *                              2^32 bytes or more: RFX_E_LIMIT
+ *   rfx_dev_contigs_to_text    TagRowContigDSID + changeLine (:3397-3443) into a device buffer: ">Contig-<len>-<idx>\n" + the
+ *                              sequence in lines of 10,000,000 bases for the contigs of at least min_contig bases, idx = the
+ *                              position among ALL contigs of the set; *out_len = the text's length, *out_contigs (optional) =
+ *                              the contigs written; text-buffer rule: filled up to cap, nothing at or past it, RFX_E_CAP with
+ *                              *out_len = the need
+ *   rfx_dev_dedup_contigs      the three rounds, packed in, packed out; round_n[3] (optional, host) = contigs left after each
+ * CAPACITY of rfx_dev_dedup_contigs: a merge of a and b bases needs ceil((a+b)/32) <= ceil(a/32) + ceil(b/32) words and removes a
+ * contig, so an output with cap_n >= in.n and cap_words >= in.word_off[in.n] suffices whenever no marker row is left over.  A
+ * leftover marker row (a contig named by two or more candidate pairs of one round) adds a contig of at most 62 bases = 2
+ * words.  A contig of at least 300 bases is named by at most 155 candidate pairs a round (310 probe rows, two per pair), which
+ * leave at most 77 rows; rows are shorter than 300 bases and never probe, and the contigs of at least 300 bases never grow in
+ * number.  So with n300 = the input contigs of at least 300 bases, cap_n >= in.n + 231 * n300 and cap_words >=
+ * in.word_off[in.n] + 462 * n300 ALWAYS suffice.  On a short output: RFX_E_CAP with need_n / need_words set -- what to call
+ * again with -- and no output array written.
+ * All run on the context's stream and return after it has drained.  A null pointer, a negative count, or an input whose
+ * word_off and len disagree: RFX_E_ARG; 2^32 marker rows or 2^30 merges in one step: RFX_E_LIMIT.  n = 0 is valid everywhere. */
+typedef struct {
+    int64_t   n;
+    uint64_t *words;     /* contig i = words [word_off[i], word_off[i+1]) */
+    int64_t  *word_off;  /* n + 1 entries, in WORDS: every contig starts on a word */
+    int64_t  *len;       /* bases; word_off[i+1] - word_off[i] = (len[i] + 31) / 32 */
+    int64_t   cap_n, cap_words, need_n, need_words;
+} rfx_contigs_packed;    /* every pointer is a DEVICE pointer, the struct lives on the host */
+int rfx_dev_contigs_pack(rfx_ctx *ctx, const uint8_t *bases_ascii, const int64_t *contig_off, int64_t n, rfx_contigs_packed *d_out);
+int rfx_dev_contigs_unpack(rfx_ctx *ctx, const rfx_contigs_packed *d_in, uint8_t *out_bases_ascii, int64_t cap_bases, int64_t *out_off,
+                           int64_t cap_contigs, int64_t *out_n);
+int rfx_dev_contigs_from_text(rfx_ctx *ctx, const char *d_text, int64_t len, rfx_contigs_packed *d_out);
+int rfx_dev_contigs_to_text(rfx_ctx *ctx, const rfx_contigs_packed *d_in, int min_contig, char *d_text, int64_t cap, int64_t *out_len,
+                            int64_t *out_contigs);
+int rfx_dev_dedup_contigs(rfx_ctx *ctx, const rfx_contigs_packed *d_in, rfx_contigs_packed *d_out, int64_t *round_n);
 
 /* The dynamic-k record format and passes: P/ReflexivDSDynamicKmerFirstFour.java (DSkmerRandomReflection
  * :2509-2762, DSExtendReflexivKmer :1581-2373) and P/ReflexivDSDynamicKmerIteration.java (DSExtendReflexivKmerToArrayLoop

@@ -46,6 +46,12 @@ class CDynPacked(C.Structure):
                 ("cap_words", C.c_int64), ("need_words", C.c_int64)]
 
 
+class CContigsPacked(C.Structure):
+    """rfx_contigs_packed: every pointer is a DEVICE pointer."""
+    _fields_ = [("n", C.c_int64), ("words", C.c_void_p), ("word_off", C.c_void_p), ("len", C.c_void_p), ("cap_n", C.c_int64),
+                ("cap_words", C.c_int64), ("need_n", C.c_int64), ("need_words", C.c_int64)]
+
+
 class CRecords(C.Structure):
     """rfx_records."""
     _fields_ = [("n", C.c_int64), ("key", C.c_void_p), ("marker", C.c_void_p), ("ext_off", C.c_void_p),
@@ -74,14 +80,15 @@ SYMBOLS = [
     "rfx_comm_unique_id", "rfx_comm_init", "rfx_comm_destroy", "rfx_comm_rank", "rfx_comm_world", "rfx_comm_last_bytes_bucketed",
     "rfx_comm_all_reduce_i64", "rfx_dev_sharded_count", "rfx_dev_gather_shards", "rfx_sharded_assemble_reads", "rfx_dev_sharded_assemble",
     "rfx_dedup_contigs", "rfx_dedup_contig_text",
+    "rfx_dev_contigs_pack", "rfx_dev_contigs_unpack", "rfx_dev_contigs_from_text", "rfx_dev_contigs_to_text", "rfx_dev_dedup_contigs",
     "rfx_dyn_binarize", "rfx_dyn_sort", "rfx_dyn_random_reflection", "rfx_dyn_extend_pass", "rfx_dyn_run",
     "rfx_dyn_blocks_to_bases", "rfx_dyn_bases_to_blocks", "rfx_dyn_attribute", "rfx_dyn_attribute_unpack",
     "rfx_dev_dyn_pack", "rfx_dev_dyn_unpack", "rfx_dev_dyn_binarize", "rfx_dev_dyn_sort", "rfx_dev_dyn_random_reflection",
     "rfx_dev_dyn_extend_pass", "rfx_dev_dyn_run", "rfx_dev_dyn_to_text", "rfx_dyn_run_text",
 ]
 
-# prototypes of the packed dynamic-k entry points (ctx, then as include/reflexiv_hip.h declares them)
-_PK, _HR, _I, _L, _P = "PK", "HR", C.c_int, C.c_int64, C.c_void_p
+# prototypes of the packed entry points (ctx, then as include/reflexiv_hip.h declares them)
+_PK, _HR, _CP, _I, _L, _P = "PK", "HR", "CP", C.c_int, C.c_int64, C.c_void_p
 _DYN_PACKED_ARGS = {
     "rfx_dev_dyn_pack": (_HR, _PK),
     "rfx_dev_dyn_unpack": (_PK, _HR),
@@ -92,6 +99,12 @@ _DYN_PACKED_ARGS = {
     "rfx_dev_dyn_run": (_PK, _I, _I, _I, _I, _I, _PK, _P, _L, _P),
     "rfx_dev_dyn_to_text": (_PK, _P, _L, _P),
     "rfx_dyn_run_text": (_P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _L, _P),
+    # the packed contig set of the de-duplication (rfx_contigs_packed)
+    "rfx_dev_contigs_pack": (_P, _P, _L, _CP),
+    "rfx_dev_contigs_unpack": (_CP, _P, _L, _P, _L, _P),
+    "rfx_dev_contigs_from_text": (_P, _L, _CP),
+    "rfx_dev_contigs_to_text": (_CP, _I, _P, _L, _P, _P),
+    "rfx_dev_dedup_contigs": (_CP, _CP, _P),
 }
 
 
@@ -138,8 +151,8 @@ def lib():
                 continue
             if name in _DYN_PACKED_ARGS:
                 fn.restype = C.c_int
-                fn.argtypes = [C.c_void_p] + [C.POINTER(CDynPacked) if a == _PK else C.POINTER(CDynRecords) if a == _HR else a
-                                              for a in _DYN_PACKED_ARGS[name]]
+                fn.argtypes = [C.c_void_p] + [C.POINTER(CDynPacked) if a == _PK else C.POINTER(CDynRecords) if a == _HR else
+                                              C.POINTER(CContigsPacked) if a == _CP else a for a in _DYN_PACKED_ARGS[name]]
                 continue
             if name == "rfx_dyn_attribute_unpack":
                 fn.restype = None

@@ -200,6 +200,40 @@ class DynPacked:
                 self.marker[:n].cpu().numpy(), self.left[:n].cpu().numpy(), self.right[:n].cpu().numpy())
 
 
+class ContigsPacked:
+    """The packed contig set of the de-duplication (rfx_contigs_packed) over torch tensors in HBM: 32 bases per word, the first base
+    in the two highest bits, every contig on a word, every bit past its last base 0.  Capacities are the tensors' sizes; `n` is
+    the number of contigs in use, the words in use are word_off[n]."""
+    FIELDS = ("words_t", "word_off", "len")
+
+    def __init__(self, cap_n: int, cap_words: int, device="cuda"):
+        import torch
+        self.cap_n, self.cap_words, self.n = int(cap_n), int(cap_words), 0
+        self.words_t = torch.empty(max(1, self.cap_words), dtype=torch.int64, device=device)   # (uint64 words, held as int64 bit patterns)
+        self.word_off = torch.empty(self.cap_n + 1, dtype=torch.int64, device=device)
+        self.len = torch.empty(max(1, self.cap_n), dtype=torch.int64, device=device)
+
+    @property
+    def words(self) -> int:
+        """words in use (reads word_off[n] back)"""
+        return int(self.word_off[self.n].item()) if self.n else 0
+
+    def tensors(self):
+        return [getattr(self, f) for f in self.FIELDS]
+
+    def _c(self) -> "_lib.CContigsPacked":
+        c = _lib.CContigsPacked()
+        c.n = self.n
+        c.words, c.word_off, c.len = self.words_t.data_ptr(), self.word_off.data_ptr(), self.len.data_ptr()
+        c.cap_n, c.cap_words, c.need_n, c.need_words = self.cap_n, self.cap_words, 0, 0
+        return c
+
+    def host(self):
+        """the raw arrays in use, as numpy: (words uint64, word_off, len)"""
+        n = self.n
+        return (self.words_t[:self.words].cpu().numpy().view(np.uint64), self.word_off[:n + 1].cpu().numpy(), self.len[:n].cpu().numpy())
+
+
 def as_records(r) -> Records:
     """Accept any object with key/marker/ext_off/ext/left/right arrays (e.g. the oracle's Records)."""
     return Records(np.ascontiguousarray(r.key, np.uint64), np.ascontiguousarray(r.marker, np.int32),
@@ -944,6 +978,76 @@ class Reflexiv:
         self._check(self.L.rfx_dedup_contig_text(self.ctx, src, C.c_int64(len(src)), min_contig, _p(out), C.c_int64(cap), C.byref(ln),
                                                  C.byref(nc), rn), "rfx_dedup_contig_text")
         return bytes(out[:ln.value]).decode(), int(nc.value), [int(x) for x in rn]
+
+    # ---- the same on a packed contig set that stays in HBM (rfx_dev_contigs_*, rfx_dev_dedup_contigs)
+    def _contigs_dev_call(self, fn, name, out: "ContigsPacked", args_of):
+        """one call with a packed output into `out` (grown and called again on RFX_E_CAP) -> out"""
+        while True:
+            co = out._c()
+            t0 = time.perf_counter()
+            st = fn(self.ctx, *args_of(co))
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
+            if st == RFX_E_CAP:
+                out = ContigsPacked(max(out.cap_n, int(co.need_n)), max(out.cap_words, int(co.need_words)), out.word_off.device)
+                continue
+            self._check(st, name)
+            out.n = int(co.n)
+            return out
+
+    def contigs_pack(self, contigs, out: "ContigsPacked" = None) -> "ContigsPacked":
+        """rfx_dev_contigs_pack: a list of contig strings -> a packed set in HBM (a letter that is not ACGT is code 3)"""
+        n = len(contigs)
+        off = np.zeros(n + 1, np.int64)
+        off[1:] = np.cumsum([len(c) for c in contigs])
+        bases = np.frombuffer("".join(contigs).encode(), np.uint8) if off[-1] else np.zeros(1, np.uint8)
+        out = out or ContigsPacked(n, n + int(off[-1]) // 32)
+        return self._contigs_dev_call(self.L.rfx_dev_contigs_pack, "rfx_dev_contigs_pack", out,
+                                      lambda co: (bases.ctypes.data, off.ctypes.data, n, C.byref(co)))
+
+    def contigs_unpack(self, d: "ContigsPacked"):
+        """rfx_dev_contigs_unpack: a packed set -> the list of contig strings"""
+        ci = d._c()
+        cap_b, cap_n = 32 * d.words + 64, d.n
+        ob, oo, m = np.empty(cap_b, np.uint8), np.empty(cap_n + 1, np.int64), C.c_int64(0)
+        t0 = time.perf_counter()
+        st = self.L.rfx_dev_contigs_unpack(self.ctx, C.byref(ci), ob.ctypes.data, cap_b, oo.ctypes.data, cap_n, C.addressof(m))
+        self.last_call_ms = (time.perf_counter() - t0) * 1e3
+        self._check(st, "rfx_dev_contigs_unpack")
+        return [bytes(ob[oo[i]:oo[i + 1]]).decode() for i in range(int(m.value))]
+
+    def contigs_from_text_dev(self, d_text, length: int = None, out: "ContigsPacked" = None) -> "ContigsPacked":
+        """rfx_dev_contigs_from_text: the contig text the path writes (torch uint8 tensor in HBM) -> a packed set"""
+        length = int(d_text.numel()) if length is None else int(length)
+        out = out or ContigsPacked(max(16, length // 64), length // 32 + max(16, length // 64))
+        return self._contigs_dev_call(self.L.rfx_dev_contigs_from_text, "rfx_dev_contigs_from_text", out,
+                                      lambda co: (d_text.data_ptr(), length, C.byref(co)))
+
+    def contigs_to_text_dev(self, d: "ContigsPacked", min_contig=500, d_text=None):
+        """rfx_dev_contigs_to_text -> (torch uint8 tensor in HBM holding ">Contig-<len>-<idx>\n" + sequence, its length, the
+        contigs written)"""
+        import torch
+        ci = d._c()
+        ln, nc = C.c_int64(0), C.c_int64(0)
+        if d_text is None:
+            d_text = torch.empty(max(1, 64 * d.n + 33 * d.words + 64), dtype=torch.uint8, device=d.word_off.device)
+        while True:
+            t0 = time.perf_counter()
+            st = self.L.rfx_dev_contigs_to_text(self.ctx, C.byref(ci), min_contig, d_text.data_ptr(), int(d_text.numel()), C.addressof(ln),
+                                                C.addressof(nc))
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3
+            if st == RFX_E_CAP:
+                d_text = torch.empty(ln.value, dtype=torch.uint8, device=d.word_off.device)
+                continue
+            self._check(st, "rfx_dev_contigs_to_text")
+            return d_text, int(ln.value), int(nc.value)
+
+    def dedup_dev(self, d: "ContigsPacked", out: "ContigsPacked" = None):
+        """rfx_dev_dedup_contigs: the three rounds, packed in, packed out -> (ContigsPacked, [contigs after round 1, 2, 3])"""
+        ci = d._c()
+        rn = (C.c_int64 * 3)()
+        out = self._contigs_dev_call(self.L.rfx_dev_dedup_contigs, "rfx_dev_dedup_contigs", out or ContigsPacked(d.n, d.words),
+                                     lambda co: (C.byref(ci), C.byref(co), C.addressof(rn)))
+        return out, [int(x) for x in rn]
 
     # ------------------------------------------------ several GPUs: the RCCL exchange behind the C ABI
     @staticmethod
