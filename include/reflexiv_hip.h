@@ -674,6 +674,70 @@ int rfx_dyn_run_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int
                      int passes_first_four, int start_iteration, int end_iteration, char *out, int64_t cap, int64_t *out_len, int64_t *trace,
                      int64_t trace_cap, int64_t *n_trace);
 
+/* The k-mer sorting stage (Count_<k>_sorted) on the same PACKED record sets in HBM:
+ * P/ReflexivDSKmerLeftAndRightSorting.java `assemblyFromKmer` (:105-243) with param.bubble == true and param.minErrorCoverage > 0.
+ * It is the link between the counter's `KMER,count` rows and the `KMER,marker|left|right` rows rfx_dyn_binarize form 0 reads.
+ *   rfx_dev_ksort_binarize     steps 1-4: DynamicKmerBinarizer (:1666-1764; a leading '(' of the k-mer and a trailing ')' of the
+ *                              count dropped, A0 C1 G2 anything else 3, a count of 10 or more digits reads as 1,000,000,000),
+ *                              filter(count <= maxKmerCoverage) (:178-184; no lower bound, as in the reference),
+ *                              DSKmerReverseComplement (:1569-1664), DSForwardSubKmerExtraction (:906-979): two records per kept
+ *                              row, the k-mer's and then its reverse complement's, in row order; key = the k-mer without its last
+ *                              base, extension = that base, marker 1, left = right = the count clamped to 30000
+ *   rfx_dev_ksort_fork_filter  reflected 0: DSFilterForkSubKmerWithErrorCorrection (:426-624), 1:
+ *                              DSFilterForkReflectedSubKmerWithErrorCorrection (:693-904) over a SORTED set (rfx_dev_dyn_sort, any P):
+ *                              one survivor per run of equal keys
+ *   rfx_dev_ksort_reflect      step 6, DSReflectedSubKmerExtractionFromForward (:1096-1179): key' = key[1:] + extension,
+ *                              extension' = key[0], marker 2
+ *   rfx_dev_ksort_full_kmers   step 8, DSSubKmerToFullKmer (:1301-1568): marker 2 extension + key, marker 1 key + extension; the
+ *                              result has key = the k-mer, no extension (ext_len 0), marker 1
+ *   rfx_dev_ksort_to_text      step 9, DSBinaryFullKmerArrayToString (:246-354): rows "KMER,1|left|right\n" of the records whose key
+ *                              has k bases into a device buffer; *out_len = the text's length, *n_out = its rows; d_row_off
+ *                              (nullable, a device array of d_in->n + 1 entries at least) receives the n_out + 1 row offsets, so
+ *                              that d_text and d_row_off can go straight to rfx_dev_dyn_binarize form 0
+ *   rfx_dev_ksort_run          steps 1-8 with the set resident between the operators (the two sort("k-1") are rfx_dev_dyn_sort's);
+ *                              bubble == 0 skips steps 5-7, as the driver does (:195)
+ *   rfx_ksort_text             host text in, host text out: upload, run, to-text, one copy back
+ * SUPPORTED k: 8..124 (the sub-k-mer and the k-mer held as a key fit the 124-base key) except (k - 1) % 31 == 0, i.e. 32, 63 and
+ * 94, where the reference's own classes are broken (DSForwardSubKmerExtraction special-cases currentSubKmerSize == 31 only, and
+ * wrongly: tests/golden/ksort_vectors.npz `refused_k`).  Those and k outside 8..124: RFX_E_ARG.
+ * DEVIATIONS, both stated: (1) one call handles ONE k -- a row whose k-mer has another length is dropped at the binarizer; the
+ * reference would carry a row of another LISTED length through both folds (where subKmerSlotComparator on block arrays of
+ * unequal length is not well defined) and drop it at step 9; its own pipeline never writes a mixed file.  (2) A count with a sign
+ * is refused (Integer.parseInt would take it).  The folds reset at every new key and equal keys never straddle a Spark range
+ * partition, so the stage takes no partition count.
+ * CONTRACTS.  Every output set keeps the rfx_dyn_packed invariant (every bit past the last base 0, every unused key word 0; the
+ * producers write those bits).  Capacities from the input alone: binarize and run cap_n >= 2 n_rows and cap_words >= 2 n_rows
+ * (a one-base extension takes one word); the other operators cap_n >= in.n and cap_words >= in.ext_off[in.n]; full_kmers' (and
+ * run's) cap_words may be 0.  A short output: RFX_E_CAP with n and need_words (or *out_len) set and no output array written; the
+ * two text buffers follow the text-buffer rule (filled up to cap, nothing at or past it).  RFX_E_ARG, nothing written: a row
+ * without a comma; a count field that is not 1 or more decimal digits, optionally followed by ')' (the reference throws) -- both
+ * for EVERY row, kept or dropped; min_error_cov <= 0 (the reference's classes without error correction read a long column with
+ * getInt and cannot run); min_repeat_fold < 1; max_k < 1; a null pointer; for fork_filter and reflect a set whose keys are not
+ * all of one length; for fork_filter, reflect and full_kmers a record whose extension is not one base.  n_rows = 0 and n = 0 are
+ * valid everywhere.  Row ends follow rfx_dyn_binarize's rule: a trailing newline is ignored.  All run on the context's stream
+ * and return after it has drained. */
+typedef struct {
+    int    k;                /* the k of this call                                                               */
+    int    max_k;            /* the LAST k of the k list (param.kmerListInt): the markers are max_k + 3          */
+    int    min_error_cov;    /* minErrorCoverage, E                                                              */
+    int    max_cov;          /* maxKmerCoverage                                                                  */
+    int    bubble;           /* param.bubble                                                                     */
+    double min_repeat_fold;  /* minRepeatFold, F: compared in double                                             */
+} rfx_ksort_params;
+void rfx_ksort_default_params(rfx_ksort_params *p, int k);   /* max_k 95, E 8, max_cov 10000000, F 1.5, bubble 1 */
+int rfx_dev_ksort_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, const rfx_ksort_params *params,
+                           rfx_dyn_packed *d_out);
+int rfx_dev_ksort_fork_filter(rfx_ctx *ctx, int reflected, const rfx_dyn_packed *d_sorted, const rfx_ksort_params *params,
+                              rfx_dyn_packed *d_out);
+int rfx_dev_ksort_reflect(rfx_ctx *ctx, const rfx_dyn_packed *d_in, rfx_dyn_packed *d_out);
+int rfx_dev_ksort_full_kmers(rfx_ctx *ctx, const rfx_dyn_packed *d_in, rfx_dyn_packed *d_out);
+int rfx_dev_ksort_to_text(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int k, char *d_text, int64_t cap, int64_t *out_len, int64_t *d_row_off,
+                          int64_t *n_out);
+int rfx_dev_ksort_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, const rfx_ksort_params *params,
+                      rfx_dyn_packed *d_out);
+int rfx_ksort_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, const rfx_ksort_params *params, char *out,
+                   int64_t cap, int64_t *out_len);
+
 /* Synthetic reads: integer-only counter-based generator, bit-identical to
  * oracle/reflexiv_oracle.c orc_synth_*.  Writes packed reads straight into HBM. */
 int rfx_dev_synth_genome(rfx_ctx *ctx, uint64_t seed, int64_t genome_len, uint64_t *d_genome);

@@ -46,6 +46,12 @@ class CDynPacked(C.Structure):
                 ("cap_words", C.c_int64), ("need_words", C.c_int64)]
 
 
+class CKsortParams(C.Structure):
+    """rfx_ksort_params."""
+    _fields_ = [("k", C.c_int), ("max_k", C.c_int), ("min_error_cov", C.c_int), ("max_cov", C.c_int), ("bubble", C.c_int),
+                ("min_repeat_fold", C.c_double)]
+
+
 class CContigsPacked(C.Structure):
     """rfx_contigs_packed: every pointer is a DEVICE pointer."""
     _fields_ = [("n", C.c_int64), ("words", C.c_void_p), ("word_off", C.c_void_p), ("len", C.c_void_p), ("cap_n", C.c_int64),
@@ -85,10 +91,12 @@ SYMBOLS = [
     "rfx_dyn_blocks_to_bases", "rfx_dyn_bases_to_blocks", "rfx_dyn_attribute", "rfx_dyn_attribute_unpack",
     "rfx_dev_dyn_pack", "rfx_dev_dyn_unpack", "rfx_dev_dyn_binarize", "rfx_dev_dyn_sort", "rfx_dev_dyn_random_reflection",
     "rfx_dev_dyn_extend_pass", "rfx_dev_dyn_run", "rfx_dev_dyn_to_text", "rfx_dyn_run_text",
+    "rfx_ksort_default_params", "rfx_dev_ksort_binarize", "rfx_dev_ksort_fork_filter", "rfx_dev_ksort_reflect",
+    "rfx_dev_ksort_full_kmers", "rfx_dev_ksort_to_text", "rfx_dev_ksort_run", "rfx_ksort_text",
 ]
 
 # prototypes of the packed entry points (ctx, then as include/reflexiv_hip.h declares them)
-_PK, _HR, _CP, _I, _L, _P = "PK", "HR", "CP", C.c_int, C.c_int64, C.c_void_p
+_PK, _HR, _CP, _KP, _I, _L, _P = "PK", "HR", "CP", "KP", C.c_int, C.c_int64, C.c_void_p
 _DYN_PACKED_ARGS = {
     "rfx_dev_dyn_pack": (_HR, _PK),
     "rfx_dev_dyn_unpack": (_PK, _HR),
@@ -99,6 +107,14 @@ _DYN_PACKED_ARGS = {
     "rfx_dev_dyn_run": (_PK, _I, _I, _I, _I, _I, _PK, _P, _L, _P),
     "rfx_dev_dyn_to_text": (_PK, _P, _L, _P),
     "rfx_dyn_run_text": (_P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _L, _P),
+    # the k-mer sorting stage on the same packed sets (rfx_ksort_params)
+    "rfx_dev_ksort_binarize": (_P, _P, _L, _KP, _PK),
+    "rfx_dev_ksort_fork_filter": (_I, _PK, _KP, _PK),
+    "rfx_dev_ksort_reflect": (_PK, _PK),
+    "rfx_dev_ksort_full_kmers": (_PK, _PK),
+    "rfx_dev_ksort_to_text": (_PK, _I, _P, _L, _P, _P, _P),
+    "rfx_dev_ksort_run": (_P, _P, _L, _KP, _PK),
+    "rfx_ksort_text": (_P, _P, _L, _KP, _P, _L, _P),
     # the packed contig set of the de-duplication (rfx_contigs_packed)
     "rfx_dev_contigs_pack": (_P, _P, _L, _CP),
     "rfx_dev_contigs_unpack": (_CP, _P, _L, _P, _L, _P),
@@ -152,10 +168,14 @@ def lib():
             if name in _DYN_PACKED_ARGS:
                 fn.restype = C.c_int
                 fn.argtypes = [C.c_void_p] + [C.POINTER(CDynPacked) if a == _PK else C.POINTER(CDynRecords) if a == _HR else
-                                              C.POINTER(CContigsPacked) if a == _CP else a for a in _DYN_PACKED_ARGS[name]]
+                                              C.POINTER(CContigsPacked) if a == _CP else C.POINTER(CKsortParams) if a == _KP else a for a in _DYN_PACKED_ARGS[name]]
                 continue
             if name == "rfx_dyn_attribute_unpack":
                 fn.restype = None
+                continue
+            if name == "rfx_ksort_default_params":
+                fn.restype = None
+                fn.argtypes = [C.POINTER(CKsortParams), C.c_int]
                 continue
             if name in ("rfx_comm_last_bytes_bucketed", "rfx_ctx_workspace_bytes"):
                 fn.restype = C.c_int64

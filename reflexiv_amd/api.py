@@ -945,6 +945,88 @@ class Reflexiv:
             self._check(st, "rfx_dyn_run_text")
             return out[:ln.value].tobytes(), [int(x) for x in trace[:ntr.value]]
 
+    # ---- the k-mer sorting stage (Count_<k>_sorted) on the same packed sets (rfx_dev_ksort_*)
+    def ksort_params(self, k: int, **kw) -> "_lib.CKsortParams":
+        """rfx_ksort_default_params (max_k 95, min_error_cov 8, max_cov 10000000, min_repeat_fold 1.5, bubble 1), then **kw"""
+        p = _lib.CKsortParams()
+        self.L.rfx_ksort_default_params(C.byref(p), int(k))
+        for a, b in kw.items():
+            if a not in dict(p._fields_):
+                raise TypeError(f"rfx_ksort_params has no field {a!r}")
+            setattr(p, a, b)
+        return p
+
+    def ksort_binarize(self, d_text, d_row_off, params, out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_ksort_binarize: `KMER,count` rows (torch uint8 tensor in HBM + int64 row offsets, n_rows + 1) -> two records per
+        kept row"""
+        n_rows = int(d_row_off.numel()) - 1
+        return self._dyn_dev_call(self.L.rfx_dev_ksort_binarize, "rfx_dev_ksort_binarize", out or DynPacked(2 * n_rows, 2 * n_rows),
+                                  lambda co: (d_text.data_ptr(), d_row_off.data_ptr(), n_rows, C.byref(params), C.byref(co)))
+
+    def ksort_fork_filter(self, d: "DynPacked", reflected: bool, params, out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_ksort_fork_filter over a sorted set: one survivor per run of equal keys"""
+        ci = d._c()
+        return self._dyn_dev_call(self.L.rfx_dev_ksort_fork_filter, "rfx_dev_ksort_fork_filter", out or DynPacked(d.n, d.n),
+                                  lambda co: (int(reflected), C.byref(ci), C.byref(params), C.byref(co)))
+
+    def ksort_reflect(self, d: "DynPacked", out: "DynPacked" = None) -> "DynPacked":
+        ci = d._c()
+        return self._dyn_dev_call(self.L.rfx_dev_ksort_reflect, "rfx_dev_ksort_reflect", out or DynPacked(d.n, d.n),
+                                  lambda co: (C.byref(ci), C.byref(co)))
+
+    def ksort_full_kmers(self, d: "DynPacked", out: "DynPacked" = None) -> "DynPacked":
+        ci = d._c()
+        return self._dyn_dev_call(self.L.rfx_dev_ksort_full_kmers, "rfx_dev_ksort_full_kmers", out or DynPacked(d.n, 0),
+                                  lambda co: (C.byref(ci), C.byref(co)))
+
+    def ksort_run(self, d_text, d_row_off, params, out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_ksort_run: steps 1-8 with the set resident in HBM -> the full k-mers"""
+        n_rows = int(d_row_off.numel()) - 1
+        return self._dyn_dev_call(self.L.rfx_dev_ksort_run, "rfx_dev_ksort_run", out or DynPacked(2 * n_rows, 0),
+                                  lambda co: (d_text.data_ptr(), d_row_off.data_ptr(), n_rows, C.byref(params), C.byref(co)))
+
+    def ksort_to_text_dev(self, d: "DynPacked", k: int, d_text=None, want_offsets=True):
+        """rfx_dev_ksort_to_text -> (torch uint8 tensor in HBM holding the rows "KMER,1|l|r\n", its length, the row offsets
+        (torch int64 in HBM, rows + 1 entries in use; None without want_offsets), the rows)"""
+        import torch
+        ci = d._c()
+        ln, nr = C.c_int64(0), C.c_int64(0)
+        if d_text is None:
+            d_text = torch.empty(max(1, (k + 24) * d.n), dtype=torch.uint8, device=d.key.device)
+        d_off = torch.empty(d.n + 1, dtype=torch.int64, device=d.key.device) if want_offsets else None
+        while True:
+            t0 = time.perf_counter()
+            st = self.L.rfx_dev_ksort_to_text(self.ctx, C.byref(ci), int(k), d_text.data_ptr(), int(d_text.numel()), C.addressof(ln),
+                                              d_off.data_ptr() if want_offsets else None, C.addressof(nr))
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
+            if st == RFX_E_CAP:
+                d_text = torch.empty(ln.value, dtype=torch.uint8, device=d.key.device)
+                continue
+            self._check(st, "rfx_dev_ksort_to_text")
+            return d_text, int(ln.value), d_off, int(nr.value)
+
+    def ksort_text(self, text: bytes, params) -> bytes:
+        """rfx_ksort_text: the rows of a counts file (bytes, one `KMER,count` row per line) -> the rows of Count_<k>_sorted"""
+        text = bytes(text)
+        buf = np.frombuffer(text, np.uint8)
+        ends = np.flatnonzero(buf == 10)
+        starts = np.concatenate([[0], ends + 1]).astype(np.int64)
+        starts = starts[starts < len(buf)]
+        n_rows = len(starts)
+        off = np.concatenate([starts, [len(buf)]]).astype(np.int64)
+        cap = 2 * (len(buf) + 24 * n_rows) + 64
+        ln = C.c_int64(0)
+        while True:
+            out = np.empty(max(1, cap), np.uint8)
+            t0 = time.perf_counter()
+            st = self.L.rfx_ksort_text(self.ctx, text, off.ctypes.data, n_rows, C.byref(params), out.ctypes.data, cap, C.addressof(ln))
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
+            if st == RFX_E_CAP and ln.value > cap:
+                cap = ln.value
+                continue
+            self._check(st, "rfx_ksort_text")
+            return out[:ln.value].tobytes()
+
     # ------------------------------------------------ f-4: contig RC de-duplication
     def dedup_contigs(self, contigs, min_contig=500):
         """rfx_dedup_contigs (P/ReflexivDSDynamicKmerDedup.java :138-339) on a list of contig strings (ids = positions) ->

@@ -17,6 +17,8 @@ struct DefaultParam {
     int minKmerCoverage = 2;                 // -cover       :103
     int maxKmerCoverage = 10000000;          // -maxcov      :104
     int minErrorCoverage = 4 * 2;            // -error       :105 (not touched by -cover, Parameter.java:482)
+    double minRepeatFold = 1.5;              //              :107 (no flag in the reference either)
+    std::string kmerList = "23,31,41,53,67,81,95";   // -klist   :87; `sort` reads its LAST entry (param.kmerListInt, :157-160)
     int minContig = 500;                     // -mincontig   :107
     bool bubble = true;                      // -bubble clears it (Parameter.java:422-424)
     int partitions = 0;                      // -partition   :112
@@ -54,6 +56,7 @@ inline DefaultParam importCommandLine(const std::vector<std::string> &args) {
             if (k < 1 || k > 100) throw std::runtime_error("Parameter kmer should be set between 1-100");
             p.setKmerSize(k);
         } else if (a == "-cover") p.minKmerCoverage = std::stoi(need(i++));
+        else if (a == "-klist") p.kmerList = need(i++);
         else if (a == "-maxcov") p.maxKmerCoverage = std::stoi(need(i++));
         else if (a == "-error") p.minErrorCoverage = std::stoi(need(i++));
         else if (a == "-mincontig") p.minContig = std::stoi(need(i++));

@@ -355,6 +355,36 @@ std::string ReflexivMain::assemblyDynamicIteration(const std::string &csvText, i
     return dynRunText(ctx, csvText, false, std::max(1, param.logicalPartitions), 0, 0, startIteration, endIteration, trace);
 }
 
+std::string ReflexivMain::kmerSorting(const std::string &csvText) {
+    std::string rows;
+    std::vector<int64_t> off{0};
+    for (size_t pos = 0; pos < csvText.size();) {                  // one row per non-empty line
+        size_t e = csvText.find('\n', pos);
+        if (e == std::string::npos) e = csvText.size();
+        size_t le = e;
+        if (le > pos && csvText[le - 1] == '\r') le--;
+        if (le > pos) { rows.append(csvText, pos, le - pos); off.push_back((int64_t)rows.size()); }
+        pos = e + 1;
+    }
+    rfx_ksort_params prm;
+    rfx_ksort_default_params(&prm, param.kmerSize);
+    const size_t c = param.kmerList.rfind(',');                    // maxKmerSize = kmerListInt[length - 1]
+    prm.max_k = std::stoi(param.kmerList.substr(c == std::string::npos ? 0 : c + 1));
+    prm.min_error_cov = param.minErrorCoverage; prm.max_cov = param.maxKmerCoverage; prm.bubble = param.bubble ? 1 : 0;
+    prm.min_repeat_fold = param.minRepeatFold;
+    const int64_t n = (int64_t)off.size() - 1;
+    std::string out(2 * (rows.size() + 24 * (size_t)n) + 64, '\0');
+    int64_t len = 0;
+    for (;;) {
+        const int st = rfx_ksort_text(ctx, rows.data(), off.data(), n, &prm, out.data(), (int64_t)out.size(), &len);
+        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
+        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_ksort_text: ") + rfx_last_error(ctx));
+        break;
+    }
+    out.resize((size_t)len);
+    return out;
+}
+
 std::string ReflexivMain::dedupContigText(const std::string &contigText) {
     std::string out(contigText.size() + 4096, '\0');
     int64_t len = 0, nc = 0;

@@ -155,6 +155,10 @@ public:
     std::string assemblyDynamicFirstFour(const std::string &csvText, std::vector<int64_t> *trace = nullptr);
     std::string assemblyDynamicIteration(const std::string &csvText, int startIteration, int endIteration,
                                          std::vector<int64_t> *trace = nullptr);
+    // ReflexivDSKmerLeftAndRightSorting.assemblyFromKmer (P/ReflexivDSKmerLeftAndRightSorting.java:105-243) -- `sort -kmerc COUNTS
+    // -kmer K`: CSV rows "KMER,count" of `counter` -> the rows "KMER,1|left|right" of Count_<K>_sorted, which `firstfour` reads.
+    // One call (rfx_ksort_text): binarizer, reverse complement, both sorts, both fork filters and the text writer on the device.
+    std::string kmerSorting(const std::string &csvText);
 
     rfx_ctx *ctx = nullptr;
     DefaultParam param;

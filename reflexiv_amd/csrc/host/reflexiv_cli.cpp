@@ -1,4 +1,5 @@
-// reflexiv_cli.cpp -- `reflexiv_host run|counter -fastq F [-kmer K -cover C ...] -outfile O`
+// reflexiv_cli.cpp -- `reflexiv_host run|counter -fastq F [-kmer K -cover C ...] -outfile O`,
+// `reflexiv_host sort -kmerc COUNTS -kmer K [-klist 23,31,...] -outfile O` (Count_<K>_sorted), `firstfour`, `iteration`
 // the two launcher sub-commands of bin/reflexiv:252-271 that reach the hot path
 // (M/Main.java:59-79, M/MainOfCounter.java:60-80), on one MI355X instead of spark-submit.
 #include <zlib.h>
@@ -27,10 +28,15 @@ static std::string slurp(const std::string &path) {
 
 int main(int argc, char **argv) {
     try {
-        if (argc < 2) { std::cerr << "usage: reflexiv_host <run|counter|firstfour|iteration> -fastq F[,F2...] -outfile DIR [-kmer 31 -cover 2 ...]\n"; return 2; }
+        if (argc < 2) { std::cerr << "usage: reflexiv_host <run|counter|sort|firstfour|iteration> -fastq F[,F2...] -outfile DIR [-kmer 31 -cover 2 ...]\n"
+                                   "       reflexiv_host sort -kmerc COUNTS -kmer K [-klist 23,31,41,53,67,81,95] -outfile DIR\n"; return 2; }
         std::string cmd = argv[1];
         std::vector<std::string> args(argv + 2, argv + argc);
         reflexiv::DefaultParam param = reflexiv::importCommandLine(args);
+        if (cmd == "sort" && (param.inputKmerPath.empty() || param.outputPath.empty()))
+            throw std::runtime_error("sort needs -kmerc COUNTS -kmer K [-klist 23,31,...] -outfile DIR");
+        if (cmd == "sort" && (param.kmerSize < 8 || (param.kmerSize - 1) % 31 == 0))
+            throw std::runtime_error("sort: -kmer " + std::to_string(param.kmerSize) + " is not supported (8..124 except 32, 63, 94)");
         if (param.outputPath.empty()) throw std::runtime_error("-outfile is required");
         if (param.inputFqPath.empty() && param.inputKmerPath.empty()) throw std::runtime_error("-fastq or -kmerc is required");
         auto read_all = [&](const std::string &paths) {
@@ -75,6 +81,11 @@ int main(int argc, char **argv) {
                   : param.resident          ? m.assemblyResident(read_all(param.inputFqPath))
                                             : m.assembly(read_all(param.inputFqPath));
             if (param.dedup) out = m.dedupContigText(out);
+        } else if (cmd == "sort") {
+            // Pipelines.reflexivLeftAndRightSortingPipe(): rows "KMER,count" -> Count_<k>_sorted
+            // (P/ReflexivDSKmerLeftAndRightSorting.java:228-240)
+            out = m.kmerSorting(read_all(param.inputKmerPath));
+            dir += "/Count_" + std::to_string(param.kmerSize) + "_sorted"; mkdir(dir.c_str(), 0755);
         } else if (cmd == "firstfour") {
             // Pipelines.reflexivDSDynamicKmerFirstFourPipe(): rows "KMER,marker|left|right" of the reduction -> 00firstFour
             out = m.assemblyDynamicFirstFour(read_all(param.inputKmerPath));
@@ -92,7 +103,7 @@ int main(int argc, char **argv) {
             dir += "/Count_" + std::to_string(param.kmerSize);               // P/ReflexivDataFrameCounter.java:222-233
             mkdir(dir.c_str(), 0755);
         } else throw std::runtime_error("unknown command " + cmd);
-        std::ofstream(dir + (cmd == "counter" || cmd == "firstfour" || cmd == "iteration" ? "/part-00000.csv" : "/part-00000"), std::ios::binary) << out;   // saveAsTextFile / csv
+        std::ofstream(dir + (cmd == "counter" || cmd == "sort" || cmd == "firstfour" || cmd == "iteration" ? "/part-00000.csv" : "/part-00000"), std::ios::binary) << out;   // saveAsTextFile / csv
         std::ofstream(dir + "/_SUCCESS", std::ios::binary);
         return 0;
     } catch (const std::exception &e) {

@@ -37,26 +37,7 @@ namespace {
 #define DYN_MAXB 4                          // 31-base blocks per key: keys up to 124 bases (the reference's k-mer list ends at 95)
 #define DYN_MAXK (31 * DYN_MAXB)
 
-struct DynDev {                       // a packed record set in HBM
-    int64_t n = 0, words = 0;         // records; a BOUND on the extension words (the exact count is ext_off[n], in HBM)
-    DevBuf key, key_len, ext, ext_off, ext_len, marker, left, right;
-};
-// what the kernels take
-struct DynView {
-    const uint64_t *key; const uint8_t *key_len; const uint64_t *ext; const int64_t *ext_off; const int32_t *ext_len, *marker, *left, *right;
-};
-struct DynOut {
-    uint64_t *key; uint8_t *key_len; uint64_t *ext; int64_t *ext_off; int32_t *ext_len, *marker, *left, *right;
-};
-static DynView dyn_view(const DynDev &d) {
-    return DynView{d.key.as<uint64_t>(), d.key_len.as<uint8_t>(), d.ext.as<uint64_t>(), d.ext_off.as<int64_t>(), d.ext_len.as<int32_t>(),
-                   d.marker.as<int32_t>(), d.left.as<int32_t>(), d.right.as<int32_t>()};
-}
-static DynOut dyn_out(const DynDev &d) {
-    return DynOut{d.key.as<uint64_t>(), d.key_len.as<uint8_t>(), d.ext.as<uint64_t>(), d.ext_off.as<int64_t>(), d.ext_len.as<int32_t>(),
-                  d.marker.as<int32_t>(), d.left.as<int32_t>(), d.right.as<int32_t>()};
-}
-
+// (DynDev, DynView, DynOut, dyn_view and dyn_out: rfx_internal.h -- rfx_ksort.hip works on the same sets)
 static void buf_swap(DevBuf &x, DevBuf &y) { std::swap(x.p, y.p); std::swap(x.s, y.s); std::swap(x.borrowed, y.borrowed); }
 static void dyn_swap(DynDev &x, DynDev &y) {
     std::swap(x.n, y.n); std::swap(x.words, y.words);
@@ -64,7 +45,9 @@ static void dyn_swap(DynDev &x, DynDev &y) {
     buf_swap(x.ext_len, y.ext_len); buf_swap(x.marker, y.marker); buf_swap(x.left, y.left); buf_swap(x.right, y.right);
 }
 
-static int dyn_alloc(rfx_ctx *ctx, DynDev &d, int64_t n, int64_t words) {
+}  // namespace
+// (the functions defined as rfx::... are the ones rfx_ksort.hip shares: rfx_internal.h declares them)
+int rfx::dyn_alloc(rfx_ctx *ctx, DynDev &d, int64_t n, int64_t words) {
     const size_t m = (size_t)std::max<int64_t>(n, 1);
     RFX_HIP(d.key.alloc(m * DYN_KW * 8, ctx->stream));
     RFX_HIP(d.key_len.alloc(m, ctx->stream));
@@ -77,6 +60,7 @@ static int dyn_alloc(rfx_ctx *ctx, DynDev &d, int64_t n, int64_t words) {
     d.n = n; d.words = words;
     return RFX_OK;
 }
+namespace {
 
 // ---- words ----------------------------------------------------------------------------------------------------------------
 // the first m of 32 bases, the rest 0
@@ -448,8 +432,9 @@ static int dyn_check_lengths(rfx_ctx *ctx, const DynDev &in, uint32_t *lmin) {
     return RFX_OK;
 }
 
+}  // namespace
 // sort("k-1") + the cut into P logical partitions: in -> out (sorted), d_ps[P + 1]; *lmin = the shortest key
-static int dyn_sort(rfx_ctx *ctx, const DynDev &in, int P, DynDev &out, DevBuf &d_ps, uint32_t *lmin) {
+int rfx::dyn_sort(rfx_ctx *ctx, const DynDev &in, int P, DynDev &out, DevBuf &d_ps, uint32_t *lmin) {
     const int64_t n = in.n;
     RFX_HIP(d_ps.alloc((size_t)(P + 1) * 8, ctx->stream));
     *lmin = 0;
@@ -492,6 +477,7 @@ static int dyn_sort(rfx_ctx *ctx, const DynDev &in, int P, DynDev &out, DevBuf &
     RFX_HIP(hipGetLastError());
     return RFX_OK;
 }
+namespace {
 
 // one pass over sorted records: in (sorted), d_ps -> out, d_out_ps (optional)
 static int dyn_pass(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, uint32_t lmin, int stage, int start_iteration, int start_marker,
@@ -680,8 +666,9 @@ static bool dyn_packed_out_ok(const rfx_dyn_packed *p) {           // an output:
     return p && p->key && p->key_len && p->ext && p->ext_off && p->ext_len && p->marker && p->left && p->right;
 }
 static bool dyn_packed_ok(const rfx_dyn_packed *p) { return dyn_packed_out_ok(p) && p->n >= 0; }
+}  // namespace
 // a view of the caller's input set: nothing is copied, nothing is freed
-static int dyn_borrow(rfx_ctx *ctx, const rfx_dyn_packed *p, DynDev &d) {
+int rfx::dyn_borrow(rfx_ctx *ctx, const rfx_dyn_packed *p, DynDev &d) {
     auto b = [&](DevBuf &x, void *q) { x.release(); x.p = q; x.s = ctx->stream; x.borrowed = true; };
     b(d.key, p->key); b(d.key_len, p->key_len); b(d.ext, p->ext); b(d.ext_off, p->ext_off); b(d.ext_len, p->ext_len);
     b(d.marker, p->marker); b(d.left, p->left); b(d.right, p->right);
@@ -695,7 +682,7 @@ static int dyn_borrow(rfx_ctx *ctx, const rfx_dyn_packed *p, DynDev &d) {
     return RFX_OK;
 }
 // the result into the caller's arrays; checks both capacities before anything is copied
-static int dyn_store(rfx_ctx *ctx, const DynDev &d, rfx_dyn_packed *o) {
+int rfx::dyn_store(rfx_ctx *ctx, const DynDev &d, rfx_dyn_packed *o) {
     const int64_t n = d.n;
     int64_t words = 0;
     if (n > 0) RFX_TRY(small_readback(ctx, &words, d.ext_off.as<int64_t>() + n, 8));
@@ -715,6 +702,7 @@ static int dyn_store(rfx_ctx *ctx, const DynDev &d, rfx_dyn_packed *o) {
     }
     return sync_checked(ctx);
 }
+namespace {
 
 // ---- DynamicKmerBinarizerFromReducedToSubKmer (FirstFour :2931-3016; Iteration's twin) on the device: the text rows of the hand-over
 // files -> records.  A row is its fields joined by ',': form 0 = (k-mer, "m|l|r") -- key = the k-mer without its last base, extension =
@@ -826,8 +814,9 @@ static int dyn_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_o
     }
     return RFX_OK;
 }
+}  // namespace
 // host text -> HBM: the rows' bytes and their offsets relative to the first row
-static int dyn_upload_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, DevBuf &d_text, DevBuf &d_off) {
+int rfx::dyn_upload_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, DevBuf &d_text, DevBuf &d_off) {
     for (int64_t i = 0; i < n_rows; i++) if (row_off[i + 1] < row_off[i]) return RFX_E_ARG;
     const int64_t nb = n_rows ? row_off[n_rows] - row_off[0] : 0;
     RFX_HIP(d_text.alloc((size_t)std::max<int64_t>(nb, 1), ctx->stream));
@@ -839,6 +828,7 @@ static int dyn_upload_text(rfx_ctx *ctx, const char *text, const int64_t *row_of
     RFX_HIP(hipMemcpyAsync(d_off.p, rel.data(), (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     return sync_checked(ctx);                                     // (rel is read by the copy)
 }
+namespace {
 
 // ---- DSBinarySubKmerWith{Short,Long}ExtensionToString (FirstFour:226-263): rows "SUBKMER,marker|left|right,EXTENSION\n" ----------
 __device__ __forceinline__ int dyn_int_chars(int v) {              // characters of std::to_string(v)

@@ -451,4 +451,33 @@ int small_passes(rfx_ctx *ctx, DevRecords &recs, int k, int twin, bool wide, int
 int small_pass_limit();
 int small_pass_max_partitions();
 
+// ---- rfx_dynamic.hip : a packed dynamic-k record set in HBM (rfx_dyn_packed), shared with rfx_ksort.hip
+struct DynDev {                       // a packed record set in HBM
+    int64_t n = 0, words = 0;         // records; a BOUND on the extension words (the exact count is ext_off[n], in HBM)
+    DevBuf key, key_len, ext, ext_off, ext_len, marker, left, right;
+};
+// what the kernels take
+struct DynView {
+    const uint64_t *key; const uint8_t *key_len; const uint64_t *ext; const int64_t *ext_off; const int32_t *ext_len, *marker, *left, *right;
+};
+struct DynOut {
+    uint64_t *key; uint8_t *key_len; uint64_t *ext; int64_t *ext_off; int32_t *ext_len, *marker, *left, *right;
+};
+inline DynView dyn_view(const DynDev &d) {
+    return DynView{d.key.as<uint64_t>(), d.key_len.as<uint8_t>(), d.ext.as<uint64_t>(), d.ext_off.as<int64_t>(), d.ext_len.as<int32_t>(),
+                   d.marker.as<int32_t>(), d.left.as<int32_t>(), d.right.as<int32_t>()};
+}
+inline DynOut dyn_out(const DynDev &d) {
+    return DynOut{d.key.as<uint64_t>(), d.key_len.as<uint8_t>(), d.ext.as<uint64_t>(), d.ext_off.as<int64_t>(), d.ext_len.as<int32_t>(),
+                  d.marker.as<int32_t>(), d.left.as<int32_t>(), d.right.as<int32_t>()};
+}
+int dyn_alloc(rfx_ctx *ctx, DynDev &d, int64_t n, int64_t words);
+// sort("k-1") + the cut into P logical partitions: in -> out (sorted), d_ps[P + 1]; *lmin = the shortest key
+int dyn_sort(rfx_ctx *ctx, const DynDev &in, int P, DynDev &out, DevBuf &d_ps, uint32_t *lmin);
+// a view of the caller's input set (nothing copied, nothing freed) / the result into the caller's arrays (both capacities are
+// checked before anything is copied) / host text rows -> HBM with offsets relative to the first row
+int dyn_borrow(rfx_ctx *ctx, const rfx_dyn_packed *p, DynDev &d);
+int dyn_store(rfx_ctx *ctx, const DynDev &d, rfx_dyn_packed *o);
+int dyn_upload_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, DevBuf &d_text, DevBuf &d_off);
+
 }  // namespace rfx

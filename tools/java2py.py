@@ -941,8 +941,9 @@ class J:
     def __radd__(self, o): return J._o(o)._bin(self, lambda a, b: a + b)
     def __sub__(self, o): return self._bin(o, lambda a, b: a - b)
     def __rsub__(self, o): return J._o(o)._bin(self, lambda a, b: a - b)
-    def __mul__(self, o): return self._bin(o, lambda a, b: a * b)
-    def __rmul__(self, o): return J._o(o)._bin(self, lambda a, b: a * b)
+    # a Java double operand (a Python float) promotes the product to double: int * double, double * int
+    def __mul__(self, o): return float(self.v) * o if isinstance(o, float) else self._bin(o, lambda a, b: a * b)
+    def __rmul__(self, o): return o * float(self.v) if isinstance(o, float) else J._o(o)._bin(self, lambda a, b: a * b)
     def __and__(self, o): return self._bin(o, lambda a, b: a & b)
     def __rand__(self, o): return J._o(o)._bin(self, lambda a, b: a & b)
     def __or__(self, o): return self._bin(o, lambda a, b: a | b)
@@ -987,10 +988,11 @@ class J:
 
     def __neg__(self): return J(-self.v, self.w)
     def __invert__(self): return J(~self.v, self.w)
-    def __lt__(self, o): return self.v < J._o(o).v
-    def __le__(self, o): return self.v <= J._o(o).v
-    def __gt__(self, o): return self.v > J._o(o).v
-    def __ge__(self, o): return self.v >= J._o(o).v
+    # (against a double the int is compared as a double; `double < int` reaches these reflected)
+    def __lt__(self, o): return float(self.v) < o if isinstance(o, float) else self.v < J._o(o).v
+    def __le__(self, o): return float(self.v) <= o if isinstance(o, float) else self.v <= J._o(o).v
+    def __gt__(self, o): return float(self.v) > o if isinstance(o, float) else self.v > J._o(o).v
+    def __ge__(self, o): return float(self.v) >= o if isinstance(o, float) else self.v >= J._o(o).v
     def __eq__(self, o): return o is not None and not isinstance(o, str) and self.v == J._o(o).v
     def __ne__(self, o): return not self.__eq__(o)
 
