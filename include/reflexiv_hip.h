@@ -738,6 +738,76 @@ int rfx_dev_ksort_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off
 int rfx_ksort_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, const rfx_ksort_params *params, char *out,
                    int64_t cap, int64_t *out_len);
 
+/* The k-mer reduction stage (Count_<k1>_reduced and the rewritten Count_<k2>_sorted / Count_<k2>_reduced) on
+ * the same PACKED record sets in HBM: P/ReflexivDSDynamicKmerRuduction.java `assemblyFromKmer` (:143-287).  It compares the sorted
+ * k-mers of two consecutive k of the k list, k1 < k2, and adjusts markers and variants of the longer ones; its inputs are two texts
+ * of the k-mer sorting stage, its outputs feed rfx_dyn_binarize form 0.
+ *   rfx_dev_reduce_union          DynamicKmerBinarizerFromSorted (:3175-3303) on both texts (rows "KMER,marker|left|right", a leading
+ *                                 '(' and a trailing ')' dropped, A0 C1 G2 anything else 3, left / right clamped to +-30000) and the
+ *                                 union (:202): the records of the LONGER text first, then the shorter one's, each in row order;
+ *                                 key = the whole k-mer, no extension (ext_len 0), the marker as the text has it
+ *   rfx_dev_reduce_left_prepare   LeftLongerToShorterComparisonPreparation (:860-888): key' = the first len - 1 bases REVERSED,
+ *                                 extension' = the last base, marker 1
+ *   rfx_dev_reduce_adjust         right 0: LeftLongerKmerVariantAdjustment (:1889-2245), 1:
+ *                                 RightLongerKmerVariantAdjustmentAndNeutralization (:1203-1574) over a SORTED set (rfx_dev_dyn_sort)
+ *                                 and its P partition starts.  A three-row window whose two pending rows are NOT given up at a new
+ *                                 key, only at a partition's end -- the result depends on the cuts, so P and the starts are part of
+ *                                 the call; d_out_part_start receives the P + 1 starts of the output.  The reference's quirks are
+ *                                 kept: the left flush of a long row then a short row that fails the prefix test adds neither; the
+ *                                 right adjustment drops the shorter row after a prefix test that holds, and one row of three when
+ *                                 extensions coincide; an adjusted row takes the other row's extension and a -1 marker when the
+ *                                 other's is negative and its own is not
+ *   rfx_dev_reduce_right_prepare  RightLongerToShorterComparisonAndNeutralizationPreparation (:509-545): the key reversed back, joined
+ *                                 with the extension (behind it for marker 1, ahead of it otherwise), the first base cut off as the
+ *                                 new extension, marker 2; a map, so the partition starts of its input hold for its output
+ *   rfx_dev_reduce_full_kmers     DSSubKmerToFullKmer (:2923-2968): as rfx_dev_ksort_full_kmers
+ *   rfx_dev_reduce_neutralize     ShorterKmerNeutralization (:2563-2731, the code that is live) over a set of full k-mers SORTED by
+ *                                 rfx_dev_dyn_sort and its P partition starts: a row is compared with the last KEPT row of its
+ *                                 partition -- equal lengths keep it, a k1-mer that is a prefix of a kept k2-mer is dropped, a k2-mer
+ *                                 whose prefix is the kept k1-mer replaces it
+ *   rfx_dev_reduce_run            the whole driver, two device texts in, the final set of full k-mers out, resident between the
+ *                                 operators (the three sorts are rfx_dev_dyn_sort's with the caller's P).  The two output files are
+ *                                 rfx_dev_ksort_to_text of that set with k = k1 and with k = k2 (DSBinaryFullKmerArrayToStringShort /
+ *                                 ...Long, :289-316 / :401-428, print what DSBinaryFullKmerArrayToString prints)
+ *   rfx_reduce_text               two host texts in, two host texts out: upload, run, to-text twice, one copy back each
+ * max_k is the LAST k of the k list: it decides only whether the second output is called Count_<k2>_reduced (k2 == max_k) or
+ * Count_<k2>_sorted (:257-283); the callers that write files use it, the records do not depend on it.
+ * SUPPORTED k: 8 <= k1 < k2 <= 124 (k2 itself is held as a key).  Unlike the sorting stage's, this stage's classes are sound
+ * where k or k - 1 is a multiple of 31 (31, 32, 62, 63, 93, 94 as either member of the pair: tests/golden/reduce_vectors.npz
+ * `probe_k`), so no pair inside that range is refused.  Anything else, and max_k < k2: RFX_E_ARG.
+ * DEVIATIONS, both stated: (1) one call handles ONE pair -- a row whose k-mer is neither k1 nor k2 long is dropped at the binarizer;
+ * the reference would carry a row of another LISTED length through (its own pipeline never writes one).  (2) A malformed attribute
+ * reads as rfx_dyn_binarize reads it (a missing number is 0) where the reference throws.
+ * CONTRACTS.  Every output set keeps the rfx_dyn_packed invariant.  Capacities from the input alone, no operator emits more rows
+ * than it reads: union and run cap_n >= n_short + n_long, cap_words 0; left_prepare, adjust and right_prepare cap_n >= in.n and
+ * cap_words >= in.n (a one-base extension takes one word); full_kmers and neutralize cap_n >= in.n, cap_words 0.  A short
+ * output: RFX_E_CAP with n and need_words set and nothing written (the part starts neither); rfx_reduce_text with a short buffer:
+ * RFX_E_CAP with BOTH lengths set and NEITHER buffer written.  RFX_E_ARG, nothing written: P outside 1..63; a bad pair; a row
+ * without a comma; a set with a key length other than the two the operator expects (k1 and k2 for left_prepare and neutralize,
+ * k1 - 1 and k2 - 1 for the others) or with extensions other than it expects (none for left_prepare and neutralize, one base for
+ * the others); partition starts that do not run from 0 to n without going backwards; a null pointer.  n = 0 is valid everywhere.
+ * All run on the context's stream and return after it has drained. */
+typedef struct {
+    int k1;      /* the shorter k of the pair (param.kmerSize1)                                    */
+    int k2;      /* the longer k (param.kmerSize2)                                                 */
+    int max_k;   /* the LAST k of the k list: names the second output, nothing else                */
+} rfx_reduce_params;
+void rfx_reduce_default_params(rfx_reduce_params *p, int k1, int k2);   /* max_k = max(95, k2) */
+int rfx_dev_reduce_union(rfx_ctx *ctx, const char *d_text_short, const int64_t *d_row_off_short, int64_t n_short, const char *d_text_long,
+                         const int64_t *d_row_off_long, int64_t n_long, const rfx_reduce_params *params, rfx_dyn_packed *d_out);
+int rfx_dev_reduce_left_prepare(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rfx_reduce_params *params, rfx_dyn_packed *d_out);
+int rfx_dev_reduce_adjust(rfx_ctx *ctx, int right, const rfx_dyn_packed *d_sorted, const int64_t *d_part_start, int P,
+                          const rfx_reduce_params *params, rfx_dyn_packed *d_out, int64_t *d_out_part_start);
+int rfx_dev_reduce_right_prepare(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rfx_reduce_params *params, rfx_dyn_packed *d_out);
+int rfx_dev_reduce_full_kmers(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rfx_reduce_params *params, rfx_dyn_packed *d_out);
+int rfx_dev_reduce_neutralize(rfx_ctx *ctx, const rfx_dyn_packed *d_sorted, const int64_t *d_part_start, int P,
+                              const rfx_reduce_params *params, rfx_dyn_packed *d_out, int64_t *d_out_part_start);
+int rfx_dev_reduce_run(rfx_ctx *ctx, const char *d_text_short, const int64_t *d_row_off_short, int64_t n_short, const char *d_text_long,
+                       const int64_t *d_row_off_long, int64_t n_long, int P, const rfx_reduce_params *params, rfx_dyn_packed *d_out);
+int rfx_reduce_text(rfx_ctx *ctx, const char *text_short, const int64_t *row_off_short, int64_t n_short, const char *text_long,
+                    const int64_t *row_off_long, int64_t n_long, int P, const rfx_reduce_params *params, char *out_short, int64_t cap_short,
+                    int64_t *out_len_short, char *out_long, int64_t cap_long, int64_t *out_len_long);
+
 /* Synthetic reads: integer-only counter-based generator, bit-identical to
  * oracle/reflexiv_oracle.c orc_synth_*.  Writes packed reads straight into HBM. */
 int rfx_dev_synth_genome(rfx_ctx *ctx, uint64_t seed, int64_t genome_len, uint64_t *d_genome);

@@ -52,6 +52,11 @@ class CKsortParams(C.Structure):
                 ("min_repeat_fold", C.c_double)]
 
 
+class CReduceParams(C.Structure):
+    """rfx_reduce_params."""
+    _fields_ = [("k1", C.c_int), ("k2", C.c_int), ("max_k", C.c_int)]
+
+
 class CContigsPacked(C.Structure):
     """rfx_contigs_packed: every pointer is a DEVICE pointer."""
     _fields_ = [("n", C.c_int64), ("words", C.c_void_p), ("word_off", C.c_void_p), ("len", C.c_void_p), ("cap_n", C.c_int64),
@@ -93,10 +98,12 @@ SYMBOLS = [
     "rfx_dev_dyn_extend_pass", "rfx_dev_dyn_run", "rfx_dev_dyn_to_text", "rfx_dyn_run_text",
     "rfx_ksort_default_params", "rfx_dev_ksort_binarize", "rfx_dev_ksort_fork_filter", "rfx_dev_ksort_reflect",
     "rfx_dev_ksort_full_kmers", "rfx_dev_ksort_to_text", "rfx_dev_ksort_run", "rfx_ksort_text",
+    "rfx_reduce_default_params", "rfx_dev_reduce_union", "rfx_dev_reduce_left_prepare", "rfx_dev_reduce_adjust",
+    "rfx_dev_reduce_right_prepare", "rfx_dev_reduce_full_kmers", "rfx_dev_reduce_neutralize", "rfx_dev_reduce_run", "rfx_reduce_text",
 ]
 
 # prototypes of the packed entry points (ctx, then as include/reflexiv_hip.h declares them)
-_PK, _HR, _CP, _KP, _I, _L, _P = "PK", "HR", "CP", "KP", C.c_int, C.c_int64, C.c_void_p
+_PK, _HR, _CP, _KP, _RP, _I, _L, _P = "PK", "HR", "CP", "KP", "RP", C.c_int, C.c_int64, C.c_void_p
 _DYN_PACKED_ARGS = {
     "rfx_dev_dyn_pack": (_HR, _PK),
     "rfx_dev_dyn_unpack": (_PK, _HR),
@@ -115,6 +122,15 @@ _DYN_PACKED_ARGS = {
     "rfx_dev_ksort_to_text": (_PK, _I, _P, _L, _P, _P, _P),
     "rfx_dev_ksort_run": (_P, _P, _L, _KP, _PK),
     "rfx_ksort_text": (_P, _P, _L, _KP, _P, _L, _P),
+    # the k-mer reduction stage on the same packed sets (rfx_reduce_params)
+    "rfx_dev_reduce_union": (_P, _P, _L, _P, _P, _L, _RP, _PK),
+    "rfx_dev_reduce_left_prepare": (_PK, _RP, _PK),
+    "rfx_dev_reduce_adjust": (_I, _PK, _P, _I, _RP, _PK, _P),
+    "rfx_dev_reduce_right_prepare": (_PK, _RP, _PK),
+    "rfx_dev_reduce_full_kmers": (_PK, _RP, _PK),
+    "rfx_dev_reduce_neutralize": (_PK, _P, _I, _RP, _PK, _P),
+    "rfx_dev_reduce_run": (_P, _P, _L, _P, _P, _L, _I, _RP, _PK),
+    "rfx_reduce_text": (_P, _P, _L, _P, _P, _L, _I, _RP, _P, _L, _P, _P, _L, _P),
     # the packed contig set of the de-duplication (rfx_contigs_packed)
     "rfx_dev_contigs_pack": (_P, _P, _L, _CP),
     "rfx_dev_contigs_unpack": (_CP, _P, _L, _P, _L, _P),
@@ -168,7 +184,7 @@ def lib():
             if name in _DYN_PACKED_ARGS:
                 fn.restype = C.c_int
                 fn.argtypes = [C.c_void_p] + [C.POINTER(CDynPacked) if a == _PK else C.POINTER(CDynRecords) if a == _HR else
-                                              C.POINTER(CContigsPacked) if a == _CP else C.POINTER(CKsortParams) if a == _KP else a for a in _DYN_PACKED_ARGS[name]]
+                                              C.POINTER(CContigsPacked) if a == _CP else C.POINTER(CKsortParams) if a == _KP else C.POINTER(CReduceParams) if a == _RP else a for a in _DYN_PACKED_ARGS[name]]
                 continue
             if name == "rfx_dyn_attribute_unpack":
                 fn.restype = None
@@ -176,6 +192,10 @@ def lib():
             if name == "rfx_ksort_default_params":
                 fn.restype = None
                 fn.argtypes = [C.POINTER(CKsortParams), C.c_int]
+                continue
+            if name == "rfx_reduce_default_params":
+                fn.restype = None
+                fn.argtypes = [C.POINTER(CReduceParams), C.c_int, C.c_int]
                 continue
             if name in ("rfx_comm_last_bytes_bucketed", "rfx_ctx_workspace_bytes"):
                 fn.restype = C.c_int64

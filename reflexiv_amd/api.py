@@ -1027,6 +1027,97 @@ class Reflexiv:
             self._check(st, "rfx_ksort_text")
             return out[:ln.value].tobytes()
 
+    # ---- the k-mer reduction stage (Count_<k1>_reduced, Count_<k2>_sorted / _reduced) on the same packed sets (rfx_dev_reduce_*,
+    # DESIGN.md section 18)
+    def reduce_params(self, k1: int, k2: int, **kw) -> "_lib.CReduceParams":
+        """rfx_reduce_default_params (max_k = max(95, k2)), then **kw"""
+        p = _lib.CReduceParams()
+        self.L.rfx_reduce_default_params(C.byref(p), int(k1), int(k2))
+        for a, b in kw.items():
+            if a not in dict(p._fields_):
+                raise TypeError(f"rfx_reduce_params has no field {a!r}")
+            setattr(p, a, b)
+        return p
+
+    def reduce_union(self, d_text_short, d_off_short, d_text_long, d_off_long, params, out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_reduce_union: two `KMER,m|l|r` texts (torch uint8 tensors in HBM + int64 row offsets, rows + 1) -> the full k-mer
+        records of the longer text, then the shorter one's"""
+        ns, nl = int(d_off_short.numel()) - 1, int(d_off_long.numel()) - 1
+        return self._dyn_dev_call(self.L.rfx_dev_reduce_union, "rfx_dev_reduce_union", out or DynPacked(ns + nl, 0),
+                                  lambda co: (d_text_short.data_ptr(), d_off_short.data_ptr(), ns, d_text_long.data_ptr(), d_off_long.data_ptr(), nl,
+                                              C.byref(params), C.byref(co)))
+
+    def reduce_left_prepare(self, d: "DynPacked", params, out: "DynPacked" = None) -> "DynPacked":
+        ci = d._c()
+        return self._dyn_dev_call(self.L.rfx_dev_reduce_left_prepare, "rfx_dev_reduce_left_prepare", out or DynPacked(d.n, d.n),
+                                  lambda co: (C.byref(ci), C.byref(params), C.byref(co)))
+
+    def reduce_right_prepare(self, d: "DynPacked", params, out: "DynPacked" = None) -> "DynPacked":
+        ci = d._c()
+        return self._dyn_dev_call(self.L.rfx_dev_reduce_right_prepare, "rfx_dev_reduce_right_prepare", out or DynPacked(d.n, d.n),
+                                  lambda co: (C.byref(ci), C.byref(params), C.byref(co)))
+
+    def reduce_adjust(self, d: "DynPacked", right: bool, d_part_start, params, out: "DynPacked" = None):
+        """rfx_dev_reduce_adjust over a sorted set and its partition starts -> (DynPacked, out_part_start: torch int64 [P + 1] in HBM)"""
+        import torch
+        ci = d._c()
+        P = int(d_part_start.numel()) - 1
+        ops = torch.empty(max(P, 0) + 1, dtype=torch.int64, device=d.key.device)
+        out = self._dyn_dev_call(self.L.rfx_dev_reduce_adjust, "rfx_dev_reduce_adjust", out or DynPacked(d.n, d.n),
+                                 lambda co: (int(right), C.byref(ci), d_part_start.data_ptr(), P, C.byref(params), C.byref(co), ops.data_ptr()))
+        return out, ops
+
+    def reduce_full_kmers(self, d: "DynPacked", params, out: "DynPacked" = None) -> "DynPacked":
+        ci = d._c()
+        return self._dyn_dev_call(self.L.rfx_dev_reduce_full_kmers, "rfx_dev_reduce_full_kmers", out or DynPacked(d.n, 0),
+                                  lambda co: (C.byref(ci), C.byref(params), C.byref(co)))
+
+    def reduce_neutralize(self, d: "DynPacked", d_part_start, params, out: "DynPacked" = None):
+        """rfx_dev_reduce_neutralize over a sorted set of full k-mers -> (DynPacked, out_part_start: torch int64 [P + 1] in HBM)"""
+        import torch
+        ci = d._c()
+        P = int(d_part_start.numel()) - 1
+        ops = torch.empty(max(P, 0) + 1, dtype=torch.int64, device=d.key.device)
+        out = self._dyn_dev_call(self.L.rfx_dev_reduce_neutralize, "rfx_dev_reduce_neutralize", out or DynPacked(d.n, 0),
+                                 lambda co: (C.byref(ci), d_part_start.data_ptr(), P, C.byref(params), C.byref(co), ops.data_ptr()))
+        return out, ops
+
+    def reduce_run(self, d_text_short, d_off_short, d_text_long, d_off_long, P: int, params, out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_reduce_run: the whole driver with the set resident in HBM -> the final full k-mers (both lengths; the two
+        output texts are ksort_to_text_dev of it with k = k1 and with k = k2)"""
+        ns, nl = int(d_off_short.numel()) - 1, int(d_off_long.numel()) - 1
+        return self._dyn_dev_call(self.L.rfx_dev_reduce_run, "rfx_dev_reduce_run", out or DynPacked(ns + nl, 0),
+                                  lambda co: (d_text_short.data_ptr(), d_off_short.data_ptr(), ns, d_text_long.data_ptr(), d_off_long.data_ptr(), nl,
+                                              int(P), C.byref(params), C.byref(co)))
+
+    @staticmethod
+    def _row_offsets(text: bytes):
+        buf = np.frombuffer(text, np.uint8)
+        ends = np.flatnonzero(buf == 10)
+        starts = np.concatenate([[0], ends + 1]).astype(np.int64)
+        starts = starts[starts < len(buf)]
+        return np.concatenate([starts, [len(buf)]]).astype(np.int64), len(starts)
+
+    def reduce_text(self, text_short: bytes, text_long: bytes, P: int, params):
+        """rfx_reduce_text: the rows of Count_<k1>_sorted and Count_<k2>_sorted (bytes, one `KMER,m|l|r` row per line) -> (the rows
+        of Count_<k1>_reduced, the rows of the rewritten Count_<k2>_sorted / Count_<k2>_reduced)"""
+        ts, tl = bytes(text_short), bytes(text_long)
+        offs, ns = self._row_offsets(ts)
+        offl, nl = self._row_offsets(tl)
+        cap1, cap2 = len(ts) + ns + 64, len(tl) + nl + 64      # (an edited marker may grow a row by one character)
+        l1, l2 = C.c_int64(0), C.c_int64(0)
+        while True:
+            o1, o2 = np.empty(max(1, cap1), np.uint8), np.empty(max(1, cap2), np.uint8)
+            t0 = time.perf_counter()
+            st = self.L.rfx_reduce_text(self.ctx, ts, offs.ctypes.data, ns, tl, offl.ctypes.data, nl, int(P), C.byref(params), o1.ctypes.data, cap1,
+                                        C.addressof(l1), o2.ctypes.data, cap2, C.addressof(l2))
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
+            if st == RFX_E_CAP and (l1.value > cap1 or l2.value > cap2):
+                cap1, cap2 = max(cap1, l1.value), max(cap2, l2.value)
+                continue
+            self._check(st, "rfx_reduce_text")
+            return o1[:l1.value].tobytes(), o2[:l2.value].tobytes()
+
     # ------------------------------------------------ f-4: contig RC de-duplication
     def dedup_contigs(self, contigs, min_contig=500):
         """rfx_dedup_contigs (P/ReflexivDSDynamicKmerDedup.java :138-339) on a list of contig strings (ids = positions) ->

@@ -11,6 +11,8 @@ namespace reflexiv {
 struct DefaultParam {
     std::string inputFqPath;                 // -fastq
     std::string inputKmerPath;               // -kmerc
+    std::string inputKmerPath2;              // -kmerc2      the LONGER k-mers of `reduce` (param.inputKmerPath2)
+    int kmerSize2 = 0;                       // -kmer2       the longer k of `reduce` (param.kmerSize2); -kmer is kmerSize1 there
     std::string outputPath;                  // -outfile
     int kmerSize = 31;                       // -kmer        DefaultParam.java:74
     int subKmerSize = 30;                    //              :75
@@ -50,6 +52,8 @@ inline DefaultParam importCommandLine(const std::vector<std::string> &args) {
         const std::string &a = args[i];
         if (a == "-fastq") p.inputFqPath = need(i++);
         else if (a == "-kmerc") p.inputKmerPath = need(i++);
+        else if (a == "-kmerc2") p.inputKmerPath2 = need(i++);
+        else if (a == "-kmer2") p.kmerSize2 = std::stoi(need(i++));
         else if (a == "-outfile") p.outputPath = need(i++);
         else if (a == "-kmer") {
             int k = std::stoi(need(i++));

@@ -385,6 +385,53 @@ std::string ReflexivMain::kmerSorting(const std::string &csvText) {
     return out;
 }
 
+namespace {
+// one row per non-empty line, the line ends dropped
+void rowsOf(const std::string &csvText, std::string &rows, std::vector<int64_t> &off) {
+    off.assign(1, 0);
+    for (size_t pos = 0; pos < csvText.size();) {
+        size_t e = csvText.find('\n', pos);
+        if (e == std::string::npos) e = csvText.size();
+        size_t le = e;
+        if (le > pos && csvText[le - 1] == '\r') le--;
+        if (le > pos) { rows.append(csvText, pos, le - pos); off.push_back((int64_t)rows.size()); }
+        pos = e + 1;
+    }
+}
+}  // namespace
+
+int ReflexivMain::lastKmerOfList() const {
+    const size_t c = param.kmerList.rfind(',');
+    return std::stoi(param.kmerList.substr(c == std::string::npos ? 0 : c + 1));
+}
+
+void ReflexivMain::kmerReduction(const std::string &shortText, const std::string &longText, int k1, int k2, int partitions, std::string *reducedShort,
+                                 std::string *rewrittenLong) {
+    std::string rs, rl;
+    std::vector<int64_t> os, ol;
+    rowsOf(shortText, rs, os);
+    rowsOf(longText, rl, ol);
+    rfx_reduce_params prm;
+    rfx_reduce_default_params(&prm, k1, k2);
+    prm.max_k = std::max(k2, lastKmerOfList());
+    const int64_t ns = (int64_t)os.size() - 1, nl = (int64_t)ol.size() - 1;
+    // (a row comes back with its newline, and an edited marker may be one character longer)
+    std::string o1(rs.size() + 2 * (size_t)ns + 64, '\0'), o2(rl.size() + 2 * (size_t)nl + 64, '\0');
+    int64_t l1 = 0, l2 = 0;
+    for (;;) {
+        const int st = rfx_reduce_text(ctx, rs.data(), os.data(), ns, rl.data(), ol.data(), nl, partitions, &prm, o1.data(), (int64_t)o1.size(), &l1,
+                                       o2.data(), (int64_t)o2.size(), &l2);
+        if (st == RFX_E_CAP && (l1 > (int64_t)o1.size() || l2 > (int64_t)o2.size())) {
+            o1.assign((size_t)std::max<int64_t>(l1, (int64_t)o1.size()), '\0'); o2.assign((size_t)std::max<int64_t>(l2, (int64_t)o2.size()), '\0');
+            continue;
+        }
+        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_reduce_text: ") + rfx_last_error(ctx));
+        break;
+    }
+    o1.resize((size_t)l1); o2.resize((size_t)l2);
+    *reducedShort = std::move(o1); *rewrittenLong = std::move(o2);
+}
+
 std::string ReflexivMain::dedupContigText(const std::string &contigText) {
     std::string out(contigText.size() + 4096, '\0');
     int64_t len = 0, nc = 0;

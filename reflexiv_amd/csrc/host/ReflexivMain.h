@@ -159,6 +159,12 @@ public:
     // -kmer K`: CSV rows "KMER,count" of `counter` -> the rows "KMER,1|left|right" of Count_<K>_sorted, which `firstfour` reads.
     // One call (rfx_ksort_text): binarizer, reverse complement, both sorts, both fork filters and the text writer on the device.
     std::string kmerSorting(const std::string &csvText);
+    // ReflexivDSDynamicKmerRuduction.assemblyFromKmer (P/ReflexivDSDynamicKmerRuduction.java:143-287) -- `reduce`: the rows
+    // "KMER,marker|left|right" of Count_<k1>_sorted and Count_<k2>_sorted -> the rows of Count_<k1>_reduced (reducedShort) and of the
+    // rewritten Count_<k2>_sorted / Count_<k2>_reduced (rewrittenLong).  One call (rfx_reduce_text): everything between on the device.
+    void kmerReduction(const std::string &shortText, const std::string &longText, int k1, int k2, int partitions, std::string *reducedShort,
+                       std::string *rewrittenLong);
+    int lastKmerOfList() const;                      // param.kmerListInt[length - 1]
 
     rfx_ctx *ctx = nullptr;
     DefaultParam param;

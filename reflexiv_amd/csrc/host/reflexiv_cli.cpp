@@ -1,5 +1,8 @@
 // reflexiv_cli.cpp -- `reflexiv_host run|counter -fastq F [-kmer K -cover C ...] -outfile O`,
-// `reflexiv_host sort -kmerc COUNTS -kmer K [-klist 23,31,...] -outfile O` (Count_<K>_sorted), `firstfour`, `iteration`
+// `reflexiv_host sort -kmerc COUNTS -kmer K [-klist 23,31,...] -outfile O` (Count_<K>_sorted), `firstfour`, `iteration`,
+// `reflexiv_host reduce -kmerc SHORT -kmerc2 LONG -kmer K1 -kmer2 K2 [-klist ...] -partition P -outfile O` (Count_<K1>_reduced and
+// Count_<K2>_sorted, or Count_<K2>_reduced when K2 is the last k of the list), `reflexiv_host reduce -kmerc DIR -klist ... -partition P
+// -outfile O` (DIR/Count_<k> of every k of the list: each through `sort`, then the pairs in the list's order)
 // the two launcher sub-commands of bin/reflexiv:252-271 that reach the hot path
 // (M/Main.java:59-79, M/MainOfCounter.java:60-80), on one MI355X instead of spark-submit.
 #include <zlib.h>
@@ -29,7 +32,9 @@ static std::string slurp(const std::string &path) {
 int main(int argc, char **argv) {
     try {
         if (argc < 2) { std::cerr << "usage: reflexiv_host <run|counter|sort|firstfour|iteration> -fastq F[,F2...] -outfile DIR [-kmer 31 -cover 2 ...]\n"
-                                   "       reflexiv_host sort -kmerc COUNTS -kmer K [-klist 23,31,41,53,67,81,95] -outfile DIR\n"; return 2; }
+                                   "       reflexiv_host sort -kmerc COUNTS -kmer K [-klist 23,31,41,53,67,81,95] -outfile DIR\n"
+                                   "       reflexiv_host reduce -kmerc SHORT -kmerc2 LONG -kmer K1 -kmer2 K2 [-klist ...] -partition P -outfile DIR\n"
+                                   "       reflexiv_host reduce -kmerc COUNTS_DIR -klist K1,K2,... -partition P -outfile DIR\n"; return 2; }
         std::string cmd = argv[1];
         std::vector<std::string> args(argv + 2, argv + argc);
         reflexiv::DefaultParam param = reflexiv::importCommandLine(args);
@@ -37,6 +42,12 @@ int main(int argc, char **argv) {
             throw std::runtime_error("sort needs -kmerc COUNTS -kmer K [-klist 23,31,...] -outfile DIR");
         if (cmd == "sort" && (param.kmerSize < 8 || (param.kmerSize - 1) % 31 == 0))
             throw std::runtime_error("sort: -kmer " + std::to_string(param.kmerSize) + " is not supported (8..124 except 32, 63, 94)");
+        if (cmd == "reduce" && (param.inputKmerPath.empty() || param.outputPath.empty()))
+            throw std::runtime_error("reduce needs -kmerc SHORT -kmerc2 LONG -kmer K1 -kmer2 K2 [-klist ...] -partition P -outfile DIR, or -kmerc COUNTS_DIR "
+                                     "-klist K1,K2,... -partition P -outfile DIR");
+        if (cmd == "reduce" && !param.inputKmerPath2.empty() && (param.kmerSize < 8 || param.kmerSize >= param.kmerSize2 || param.kmerSize2 > 124))
+            throw std::runtime_error("reduce: the pair -kmer " + std::to_string(param.kmerSize) + " -kmer2 " + std::to_string(param.kmerSize2) +
+                                     " is not supported (8 <= k1 < k2 <= 124)");
         if (param.outputPath.empty()) throw std::runtime_error("-outfile is required");
         if (param.inputFqPath.empty() && param.inputKmerPath.empty()) throw std::runtime_error("-fastq or -kmerc is required");
         auto read_all = [&](const std::string &paths) {
@@ -86,6 +97,41 @@ int main(int argc, char **argv) {
             // (P/ReflexivDSKmerLeftAndRightSorting.java:228-240)
             out = m.kmerSorting(read_all(param.inputKmerPath));
             dir += "/Count_" + std::to_string(param.kmerSize) + "_sorted"; mkdir(dir.c_str(), 0755);
+        } else if (cmd == "reduce") {
+            // Pipelines.reflexivDSDynamicKmerReductionPipe() (Pipelines.java:1343-1365 walks the pairs of the k list); the second output
+            // is Count_<k2>_reduced when k2 is the last k of the list, Count_<k2>_sorted otherwise (P/ReflexivDSDynamicKmerRuduction.java:257-283)
+            const int P = param.partitions > 0 ? param.partitions : param.logicalPartitions;
+            if (P < 1 || P > 63) throw std::runtime_error("reduce: -partition must be 1..63");
+            auto write = [&](const std::string &name, const std::string &text) {
+                const std::string d = param.outputPath + "/" + name;
+                mkdir(d.c_str(), 0755);
+                std::ofstream(d + "/part-00000.csv", std::ios::binary) << text;
+                std::ofstream(d + "/_SUCCESS", std::ios::binary);
+            };
+            auto pair = [&](const std::string &s, const std::string &l, int k1, int k2) {
+                if (k1 < 8 || k1 >= k2 || k2 > 124) throw std::runtime_error("reduce: the pair " + std::to_string(k1) + ", " + std::to_string(k2) + " is not supported (8 <= k1 < k2 <= 124)");
+                std::string o1, o2;
+                m.kmerReduction(s, l, k1, k2, P, &o1, &o2);
+                write("Count_" + std::to_string(k1) + "_reduced", o1);
+                write("Count_" + std::to_string(k2) + (k2 == m.lastKmerOfList() ? "_reduced" : "_sorted"), o2);
+                return o2;
+            };
+            if (!param.inputKmerPath2.empty()) {
+                pair(read_all(param.inputKmerPath), read_all(param.inputKmerPath2), param.kmerSize, param.kmerSize2);
+            } else {
+                std::vector<int> ks;
+                std::stringstream ss(param.kmerList);
+                for (std::string one; std::getline(ss, one, ',');) ks.push_back(std::stoi(one));
+                if (ks.size() < 2) throw std::runtime_error("reduce: -klist needs two k at least");
+                auto sorted = [&](int k) {
+                    if (k < 8 || k > 124 || (k - 1) % 31 == 0) throw std::runtime_error("reduce: the sorting stage does not support k = " + std::to_string(k));
+                    m.param.setKmerSize(k);
+                    return m.kmerSorting(read_all(param.inputKmerPath + "/Count_" + std::to_string(k)));
+                };
+                std::string cur = sorted(ks[0]);
+                for (size_t i = 1; i < ks.size(); i++) cur = pair(cur, sorted(ks[i]), ks[i - 1], ks[i]);
+            }
+            return 0;
         } else if (cmd == "firstfour") {
             // Pipelines.reflexivDSDynamicKmerFirstFourPipe(): rows "KMER,marker|left|right" of the reduction -> 00firstFour
             out = m.assemblyDynamicFirstFour(read_all(param.inputKmerPath));

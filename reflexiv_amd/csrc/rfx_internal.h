@@ -480,4 +480,9 @@ int dyn_borrow(rfx_ctx *ctx, const rfx_dyn_packed *p, DynDev &d);
 int dyn_store(rfx_ctx *ctx, const DynDev &d, rfx_dyn_packed *o);
 int dyn_upload_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, DevBuf &d_text, DevBuf &d_off);
 
+// ---- rfx_ksort.hip, shared with rfx_reduce.hip: sub-k-mers -> full k-mers (marker 2: extension + key, marker 1: key + extension; every
+// extension one base) / the rows "KMER,marker|left|right\n" of the records whose key has k bases (own: a buffer of the library's)
+int ks_set_full_kmers(rfx_ctx *ctx, const DynDev &in, DynDev &out);
+int ks_set_to_text(rfx_ctx *ctx, const DynDev &d, int k, char *d_text, int64_t cap, int64_t *total, int64_t *d_row_off, int64_t *n_rows, DevBuf *own);
+
 }  // namespace rfx

@@ -522,6 +522,12 @@ static int ks_to_text(rfx_ctx *ctx, const DynDev &d, int k, char *d_text, int64_
 
 }  // namespace
 
+// DSSubKmerToFullKmer and the text writer for the reduction stage (rfx_reduce.hip), whose classes of the same names are these
+int rfx::ks_set_full_kmers(rfx_ctx *ctx, const DynDev &in, DynDev &out) { return ks_map(ctx, true, in, out); }
+int rfx::ks_set_to_text(rfx_ctx *ctx, const DynDev &d, int k, char *d_text, int64_t cap, int64_t *total, int64_t *d_row_off, int64_t *n_rows, DevBuf *own) {
+    return ks_to_text(ctx, d, k, d_text, cap, total, d_row_off, n_rows, own);
+}
+
 extern "C" {
 
 void rfx_ksort_default_params(rfx_ksort_params *p, int k) try {
