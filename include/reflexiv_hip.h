@@ -808,6 +808,75 @@ int rfx_reduce_text(rfx_ctx *ctx, const char *text_short, const int64_t *row_off
                     const int64_t *row_off_long, int64_t n_long, int P, const rfx_reduce_params *params, char *out_short, int64_t cap_short,
                     int64_t *out_len_short, char *out_long, int64_t cap_long, int64_t *out_len_long);
 
+/* The contig fixing stage (Assembly_intermediate/04Fixing) on the same PACKED record sets in HBM:
+ * P/ReflexivDSDynamicKmerFixing.java `assemblyFromKmer` (:125-260).  It is the stage directly behind the last dynamic-k iteration: its
+ * input is the text rfx_dev_dyn_to_text writes ("SUBKMER,marker|left|right,EXTENSION" rows), its output has the same form.
+ * max_k = param.maxKmerSize = the LAST k of the k list; FixedKmerSize = 31 everywhere, so every key behind the contig ends has 30 bases.
+ *   rfx_dev_fix_binarize      step 1, DynamicKmerBinarizerFromReducedToSubKmer (:3106-3203): rfx_dev_dyn_binarize form 1, then a row whose
+ *                             sub-k-mer and extension together have fewer than 2 max_k bases is dropped (:3141)
+ *   rfx_dev_fix_contig_ends   steps 2-3, DSExtractFixingKmerFromContigEnds (:1190-1256) + DSgetFixingLongKmer (:520-541) + DSgetFixingKmer
+ *                             (:857-874).  The contig is key + extension for marker 1, extension + key otherwise, L bases; one of
+ *                             L < 2 max_k gives nothing.  d_kmers receives the end 31-mers as 62-bit values (the first base in bits
+ *                             61..60), contig by contig in the reference's emission order: for i = 0 .. max_k - 31 bases [i, i + 31) and
+ *                             then bases [L - i - 31, L - i); *n_kmers = their count.  d_out_long receives one record per contig: the
+ *                             trimmed contig, bases [max_k - 30, L - (max_k - 30)), cut key = its first 30 bases, extension = the rest,
+ *                             marker 1, left and right each replaced by max_k + 3 where the input's was > 0 (:1240-1247)
+ *   rfx_dev_fix_kmer_set      steps 4-5 up to the union: groupBy("kmer").count() (:206; the count is never read: distinct),
+ *                             DSFixingKmerLeftAndRightMarkerAssignment (:1857-1878; key = the first 30 bases, extension = the last base,
+ *                             attribute 1|-1|-1) and union (:213): the distinct 31-mers' records first, then d_long's.  d_kmers is read,
+ *                             not changed; a value of 2^62 or more is RFX_E_ARG
+ *   rfx_dev_fix_fork_filter   reflected 0: step 6, DSFilterForkSubKmerWithErrorCorrection (:2057-2116), 1: step 8,
+ *                             DSFilterForkReflectedSubKmerWithErrorCorrection (:2232-2283) over a SORTED set (rfx_dev_dyn_sort) and its P
+ *                             partition starts; d_out_part_start receives the P + 1 starts of the output (step 9's first pass runs on
+ *                             them).  Within a partition, a run of equal keys that holds a row longer than one base keeps exactly those
+ *                             rows, in order; any other run keeps its LAST row of the smallest base code.  The two classes are one text
+ *                             (the base compared is the extension's first), so `reflected` is checked and selects nothing
+ *   rfx_dev_fix_reflect       step 7, DSChangingFixingKmerToReflectedKmer (:1571-1608): key = the LAST 30 bases of the contig, extension =
+ *                             its front, marker 2, left and right kept
+ *   rfx_dev_fix_run           steps 1-9 with the set resident between the operators: the above, the two sort("k-1") (rfx_dev_dyn_sort with
+ *                             the caller's P), then DSExtendFixingKmerLoop (:2371-3104) once on the right fold's partitions WITHOUT a sort
+ *                             and behind a sort min(max_iteration + 1, 17) more times (:229-243; there is no stop rule).  With every key
+ *                             30 bases long the loop is rfx_dev_dyn_extend_pass with stage 1 and a start_iteration below 61, reused
+ *                             unchanged: no prefix relation, `extra` = 0, the stage branches out of reach -- every loop pass of every case
+ *                             of tests/golden/fixing_vectors.npz agrees.  randomReflexivMarker starts at 2 in every partition, at 1 when
+ *                             scramble == 3 (:2407-2409).  The output file is rfx_dev_dyn_to_text of the result
+ *                             (DSBinaryFixingKmerWithLongExtensionToString, :262-299)
+ *   rfx_fix_text              host text in, host text out: upload, run, to-text, one copy each way
+ * DEVIATIONS, all stated: (1) a row whose sub-k-mer exceeds 124 bases is RFX_E_LIMIT for the set, kept or dropped, where the reference
+ * would carry it.  (2) A ')' behind the EXTENSION is dropped, as rfx_dyn_binarize form 1 drops it; the reference drops one behind the
+ * attribute only and would read that one as a base.  A malformed attribute reads as rfx_dyn_binarize reads it where the reference throws.
+ * (3) groupBy's output order is Spark's hash order; rfx_dev_fix_kmer_set emits the distinct 31-mers in ascending order.  Nothing from the
+ * first fold on depends on it (the one-base rows of a key are distinct 31-mers, so the smallest base code is one row whatever the
+ * order): tests/golden/make_fixing_vectors.py runs every case under two orders and fails if a later stage differs.
+ * CONTRACTS.  Every output set keeps the rfx_dyn_packed invariant.  Capacities from the input alone: binarize cap_n >= n_rows and
+ * cap_words >= n_rows + text bytes / 32; contig ends cap_kmers >= 2 (max_k - 30) in.n, cap_n >= in.n and cap_words >=
+ * in.ext_off[in.n] + 4 in.n -- together n (2 (max_k - 30) + 1) items; kmer_set cap_n >= n_kmers + long.n and cap_words >= n_kmers +
+ * long.ext_off[long.n]; fork_filter and reflect cap_n >= in.n and cap_words >= in.ext_off[in.n]; run cap_n >= n_rows (2 (max_k - 30) +
+ * 1) and cap_words >= cap_n + text bytes / 32.  A short output: RFX_E_CAP with n and need_words (*n_kmers, *out_len) set and nothing
+ * written, the part starts neither; contig_ends checks both of its outputs before it writes either.  RFX_E_ARG, nothing written: max_k
+ * outside 31..124; max_iteration < -1 (-1 runs the unsorted first pass only); P outside 1..63; partition starts that do not run
+ * from 0 to n without going backwards (read back and checked before a kernel indexes with them); a key that is not 30 bases long, or a
+ * record without an extension, where kmer_set, fork_filter and reflect expect them; a null pointer.  n_rows = 0 and n = 0 are valid
+ * everywhere.  All run on the context's stream and return after it has drained. */
+typedef struct {
+    int max_k;           /* the LAST k of the k list (param.maxKmerSize)                                      */
+    int scramble;        /* param.scramble: 3 starts the loop's marker at 1, anything else at 2               */
+    int max_iteration;   /* param.maximumIteration: min(max_iteration + 1, 17) sort + loop rounds             */
+} rfx_fix_params;
+void rfx_fix_default_params(rfx_fix_params *p, int max_k);   /* scramble 2, max_iteration 150 */
+int rfx_dev_fix_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, const rfx_fix_params *params,
+                         rfx_dyn_packed *d_out);
+int rfx_dev_fix_contig_ends(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rfx_fix_params *params, rfx_dyn_packed *d_out_long, uint64_t *d_kmers,
+                            int64_t cap_kmers, int64_t *n_kmers);
+int rfx_dev_fix_kmer_set(rfx_ctx *ctx, const uint64_t *d_kmers, int64_t n_kmers, const rfx_dyn_packed *d_long, rfx_dyn_packed *d_out);
+int rfx_dev_fix_fork_filter(rfx_ctx *ctx, int reflected, const rfx_dyn_packed *d_sorted, const int64_t *d_part_start, int P, rfx_dyn_packed *d_out,
+                            int64_t *d_out_part_start);
+int rfx_dev_fix_reflect(rfx_ctx *ctx, const rfx_dyn_packed *d_in, rfx_dyn_packed *d_out);
+int rfx_dev_fix_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, int P, const rfx_fix_params *params,
+                    rfx_dyn_packed *d_out);
+int rfx_fix_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
+                 int64_t *out_len);
+
 /* Synthetic reads: integer-only counter-based generator, bit-identical to
  * oracle/reflexiv_oracle.c orc_synth_*.  Writes packed reads straight into HBM. */
 int rfx_dev_synth_genome(rfx_ctx *ctx, uint64_t seed, int64_t genome_len, uint64_t *d_genome);

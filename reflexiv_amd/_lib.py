@@ -57,6 +57,11 @@ class CReduceParams(C.Structure):
     _fields_ = [("k1", C.c_int), ("k2", C.c_int), ("max_k", C.c_int)]
 
 
+class CFixParams(C.Structure):
+    """rfx_fix_params."""
+    _fields_ = [("max_k", C.c_int), ("scramble", C.c_int), ("max_iteration", C.c_int)]
+
+
 class CContigsPacked(C.Structure):
     """rfx_contigs_packed: every pointer is a DEVICE pointer."""
     _fields_ = [("n", C.c_int64), ("words", C.c_void_p), ("word_off", C.c_void_p), ("len", C.c_void_p), ("cap_n", C.c_int64),
@@ -100,10 +105,12 @@ SYMBOLS = [
     "rfx_dev_ksort_full_kmers", "rfx_dev_ksort_to_text", "rfx_dev_ksort_run", "rfx_ksort_text",
     "rfx_reduce_default_params", "rfx_dev_reduce_union", "rfx_dev_reduce_left_prepare", "rfx_dev_reduce_adjust",
     "rfx_dev_reduce_right_prepare", "rfx_dev_reduce_full_kmers", "rfx_dev_reduce_neutralize", "rfx_dev_reduce_run", "rfx_reduce_text",
+    "rfx_fix_default_params", "rfx_dev_fix_binarize", "rfx_dev_fix_contig_ends", "rfx_dev_fix_kmer_set", "rfx_dev_fix_fork_filter",
+    "rfx_dev_fix_reflect", "rfx_dev_fix_run", "rfx_fix_text",
 ]
 
 # prototypes of the packed entry points (ctx, then as include/reflexiv_hip.h declares them)
-_PK, _HR, _CP, _KP, _RP, _I, _L, _P = "PK", "HR", "CP", "KP", "RP", C.c_int, C.c_int64, C.c_void_p
+_PK, _HR, _CP, _KP, _RP, _FP, _I, _L, _P = "PK", "HR", "CP", "KP", "RP", "FP", C.c_int, C.c_int64, C.c_void_p
 _DYN_PACKED_ARGS = {
     "rfx_dev_dyn_pack": (_HR, _PK),
     "rfx_dev_dyn_unpack": (_PK, _HR),
@@ -131,6 +138,14 @@ _DYN_PACKED_ARGS = {
     "rfx_dev_reduce_neutralize": (_PK, _P, _I, _RP, _PK, _P),
     "rfx_dev_reduce_run": (_P, _P, _L, _P, _P, _L, _I, _RP, _PK),
     "rfx_reduce_text": (_P, _P, _L, _P, _P, _L, _I, _RP, _P, _L, _P, _P, _L, _P),
+    # the contig fixing stage on the same packed sets (rfx_fix_params)
+    "rfx_dev_fix_binarize": (_P, _P, _L, _FP, _PK),
+    "rfx_dev_fix_contig_ends": (_PK, _FP, _PK, _P, _L, _P),
+    "rfx_dev_fix_kmer_set": (_P, _L, _PK, _PK),
+    "rfx_dev_fix_fork_filter": (_I, _PK, _P, _I, _PK, _P),
+    "rfx_dev_fix_reflect": (_PK, _PK),
+    "rfx_dev_fix_run": (_P, _P, _L, _I, _FP, _PK),
+    "rfx_fix_text": (_P, _P, _L, _I, _FP, _P, _L, _P),
     # the packed contig set of the de-duplication (rfx_contigs_packed)
     "rfx_dev_contigs_pack": (_P, _P, _L, _CP),
     "rfx_dev_contigs_unpack": (_CP, _P, _L, _P, _L, _P),
@@ -184,7 +199,8 @@ def lib():
             if name in _DYN_PACKED_ARGS:
                 fn.restype = C.c_int
                 fn.argtypes = [C.c_void_p] + [C.POINTER(CDynPacked) if a == _PK else C.POINTER(CDynRecords) if a == _HR else
-                                              C.POINTER(CContigsPacked) if a == _CP else C.POINTER(CKsortParams) if a == _KP else C.POINTER(CReduceParams) if a == _RP else a for a in _DYN_PACKED_ARGS[name]]
+                                              C.POINTER(CContigsPacked) if a == _CP else C.POINTER(CKsortParams) if a == _KP else C.POINTER(CReduceParams) if a == _RP else
+                                              C.POINTER(CFixParams) if a == _FP else a for a in _DYN_PACKED_ARGS[name]]
                 continue
             if name == "rfx_dyn_attribute_unpack":
                 fn.restype = None
@@ -196,6 +212,10 @@ def lib():
             if name == "rfx_reduce_default_params":
                 fn.restype = None
                 fn.argtypes = [C.POINTER(CReduceParams), C.c_int, C.c_int]
+                continue
+            if name == "rfx_fix_default_params":
+                fn.restype = None
+                fn.argtypes = [C.POINTER(CFixParams), C.c_int]
                 continue
             if name in ("rfx_comm_last_bytes_bucketed", "rfx_ctx_workspace_bytes"):
                 fn.restype = C.c_int64

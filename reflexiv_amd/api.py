@@ -1118,6 +1118,99 @@ class Reflexiv:
             self._check(st, "rfx_reduce_text")
             return o1[:l1.value].tobytes(), o2[:l2.value].tobytes()
 
+    # ---- the contig fixing stage (Assembly_intermediate/04Fixing) on the same packed sets (rfx_dev_fix_*)
+    def fix_params(self, max_k: int, **kw) -> "_lib.CFixParams":
+        """rfx_fix_default_params (scramble 2, max_iteration 150), then **kw"""
+        p = _lib.CFixParams()
+        self.L.rfx_fix_default_params(C.byref(p), int(max_k))
+        for a, b in kw.items():
+            if a not in dict(p._fields_):
+                raise TypeError(f"rfx_fix_params has no field {a!r}")
+            setattr(p, a, b)
+        return p
+
+    def fix_binarize(self, d_text, d_row_off, params, out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_fix_binarize: `SUBKMER,m|l|r,EXTENSION` rows (torch uint8 tensor in HBM + int64 row offsets, n_rows + 1) -> the
+        records of the rows that hold 2 max_k bases or more"""
+        n_rows = int(d_row_off.numel()) - 1
+        return self._dyn_dev_call(self.L.rfx_dev_fix_binarize, "rfx_dev_fix_binarize", out or DynPacked(n_rows, n_rows + int(d_text.numel()) // 32),
+                                  lambda co: (d_text.data_ptr(), d_row_off.data_ptr(), n_rows, C.byref(params), C.byref(co)))
+
+    def fix_contig_ends(self, d: "DynPacked", params, out: "DynPacked" = None, d_kmers=None):
+        """rfx_dev_fix_contig_ends -> (the long records: the trimmed contigs cut key 30 / rest, the end 31-mers in emission order:
+        torch int64 tensor in HBM holding 62-bit values, their count)"""
+        import torch
+        ci = d._c()
+        nk = C.c_int64(0)
+        if d_kmers is None:
+            d_kmers = torch.empty(max(1, 2 * (int(params.max_k) - 30) * d.n), dtype=torch.int64, device=d.key.device)
+
+        def args(co):
+            return (C.byref(ci), C.byref(params), C.byref(co), d_kmers.data_ptr(), int(d_kmers.numel()), C.addressof(nk))
+        out = out or DynPacked(d.n, d.words + 4 * d.n)
+        while True:
+            co = out._c()
+            t0 = time.perf_counter()
+            st = self.L.rfx_dev_fix_contig_ends(self.ctx, *args(co))
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
+            if st == RFX_E_CAP:
+                if nk.value > d_kmers.numel():
+                    d_kmers = torch.empty(nk.value, dtype=torch.int64, device=d.key.device)
+                if int(co.n) > out.cap_n or int(co.need_words) > out.cap_words:
+                    out = DynPacked(max(out.cap_n, int(co.n)), max(out.cap_words, int(co.need_words)), out.key.device)
+                continue
+            self._check(st, "rfx_dev_fix_contig_ends")
+            out.n = int(co.n)
+            return out, d_kmers, int(nk.value)
+
+    def fix_kmer_set(self, d_kmers, n_kmers: int, d_long: "DynPacked", out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_fix_kmer_set: the distinct 31-mers as one-base records (ascending), then the long records"""
+        ci = d_long._c()
+        out = out or DynPacked(n_kmers + d_long.n, n_kmers + d_long.words)
+        return self._dyn_dev_call(self.L.rfx_dev_fix_kmer_set, "rfx_dev_fix_kmer_set", out,
+                                  lambda co: (d_kmers.data_ptr() if n_kmers else None, int(n_kmers), C.byref(ci), C.byref(co)))
+
+    def fix_fork_filter(self, d: "DynPacked", reflected: bool, d_part_start, out: "DynPacked" = None):
+        """rfx_dev_fix_fork_filter over a sorted set and its partition starts -> (DynPacked, out_part_start: torch int64 [P + 1] in HBM)"""
+        import torch
+        ci = d._c()
+        P = int(d_part_start.numel()) - 1
+        ops = torch.empty(max(P, 0) + 1, dtype=torch.int64, device=d.key.device)
+        out = self._dyn_dev_call(self.L.rfx_dev_fix_fork_filter, "rfx_dev_fix_fork_filter", out or DynPacked(d.n, d.words),
+                                 lambda co: (int(reflected), C.byref(ci), d_part_start.data_ptr(), P, C.byref(co), ops.data_ptr()))
+        return out, ops
+
+    def fix_reflect(self, d: "DynPacked", out: "DynPacked" = None) -> "DynPacked":
+        ci = d._c()
+        return self._dyn_dev_call(self.L.rfx_dev_fix_reflect, "rfx_dev_fix_reflect", out or DynPacked(d.n, d.words),
+                                  lambda co: (C.byref(ci), C.byref(co)))
+
+    def fix_run(self, d_text, d_row_off, P: int, params, out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_fix_run: steps 1-9 with the set resident in HBM -> the set behind the last loop pass (the output file is
+        dyn_to_text_dev of it)"""
+        n_rows = int(d_row_off.numel()) - 1
+        cap_n = n_rows * (2 * (int(params.max_k) - 30) + 1)
+        return self._dyn_dev_call(self.L.rfx_dev_fix_run, "rfx_dev_fix_run", out or DynPacked(cap_n, cap_n + int(d_text.numel()) // 32),
+                                  lambda co: (d_text.data_ptr(), d_row_off.data_ptr(), n_rows, int(P), C.byref(params), C.byref(co)))
+
+    def fix_text(self, text: bytes, P: int, params) -> bytes:
+        """rfx_fix_text: the rows of the last iteration's output (bytes, one `SUBKMER,m|l|r,EXTENSION` row per line) -> the rows of
+        04Fixing"""
+        text = bytes(text)
+        off, n_rows = self._row_offsets(text)
+        cap = len(text) + 48 * n_rows * (2 * (int(params.max_k) - 30) + 1) + 64
+        ln = C.c_int64(0)
+        while True:
+            out = np.empty(max(1, cap), np.uint8)
+            t0 = time.perf_counter()
+            st = self.L.rfx_fix_text(self.ctx, text, off.ctypes.data, n_rows, int(P), C.byref(params), out.ctypes.data, cap, C.addressof(ln))
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
+            if st == RFX_E_CAP and ln.value > cap:
+                cap = ln.value
+                continue
+            self._check(st, "rfx_fix_text")
+            return out[:ln.value].tobytes()
+
     # ------------------------------------------------ f-4: contig RC de-duplication
     def dedup_contigs(self, contigs, min_contig=500):
         """rfx_dedup_contigs (P/ReflexivDSDynamicKmerDedup.java :138-339) on a list of contig strings (ids = positions) ->

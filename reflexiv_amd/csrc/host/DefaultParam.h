@@ -26,6 +26,7 @@ struct DefaultParam {
     int partitions = 0;                      // -partition   :112
     int maximumIteration = 150;              // -maxiter     :114
     int minimumIteration = 15;               // -miniter     :115
+    int scramble = 2;                        // -scramble    :131; 3 starts the fixing loop's marker at 1
     int frontClip = 0;                       // -clipf       :119
     int endClip = 0;                         // -clipe       :120
     int shufflePartition = 200;              // -partitionredu :122
@@ -66,6 +67,7 @@ inline DefaultParam importCommandLine(const std::vector<std::string> &args) {
         else if (a == "-mincontig") p.minContig = std::stoi(need(i++));
         else if (a == "-miniter") p.minimumIteration = std::stoi(need(i++));
         else if (a == "-maxiter") p.maximumIteration = std::stoi(need(i++));
+        else if (a == "-scramble") p.scramble = std::stoi(need(i++));
         else if (a == "-clipf") p.frontClip = std::stoi(need(i++));
         else if (a == "-clipe") p.endClip = std::stoi(need(i++));
         else if (a == "-partition") p.partitions = std::stoi(need(i++));

@@ -432,6 +432,29 @@ void ReflexivMain::kmerReduction(const std::string &shortText, const std::string
     *reducedShort = std::move(o1); *rewrittenLong = std::move(o2);
 }
 
+std::string ReflexivMain::contigFixing(const std::string &csvText, int partitions) {
+    std::string rows;
+    std::vector<int64_t> off;
+    rowsOf(csvText, rows, off);
+    const int64_t n = (int64_t)off.size() - 1;
+    for (int64_t i = 0; i < n; i++)
+        if (std::count(rows.begin() + off[(size_t)i], rows.begin() + off[(size_t)i + 1], ',') < 2)
+            throw std::runtime_error("fixing row: " + rows.substr((size_t)off[(size_t)i], (size_t)(off[(size_t)i + 1] - off[(size_t)i])));
+    rfx_fix_params prm;
+    rfx_fix_default_params(&prm, lastKmerOfList());
+    prm.scramble = param.scramble; prm.max_iteration = param.maximumIteration;
+    std::string out(rows.size() + 64 * (size_t)n + 64, '\0');
+    int64_t len = 0;
+    for (;;) {
+        const int st = rfx_fix_text(ctx, rows.data(), off.data(), n, partitions, &prm, out.data(), (int64_t)out.size(), &len);
+        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
+        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_fix_text: ") + rfx_last_error(ctx));
+        break;
+    }
+    out.resize((size_t)len);
+    return out;
+}
+
 std::string ReflexivMain::dedupContigText(const std::string &contigText) {
     std::string out(contigText.size() + 4096, '\0');
     int64_t len = 0, nc = 0;

@@ -164,6 +164,10 @@ public:
     // rewritten Count_<k2>_sorted / Count_<k2>_reduced (rewrittenLong).  One call (rfx_reduce_text): everything between on the device.
     void kmerReduction(const std::string &shortText, const std::string &longText, int k1, int k2, int partitions, std::string *reducedShort,
                        std::string *rewrittenLong);
+    // ReflexivDSDynamicKmerFixing.assemblyFromKmer (P/ReflexivDSDynamicKmerFixing.java:125-260) -- `fixing`: the rows
+    // "SUBKMER,marker|left|right,EXTENSION" of the last iteration's output -> the rows of Assembly_intermediate/04Fixing.  One call
+    // (rfx_fix_text): everything between on the device.  maxKmerSize is the last k of the k list.
+    std::string contigFixing(const std::string &csvText, int partitions);
     int lastKmerOfList() const;                      // param.kmerListInt[length - 1]
 
     rfx_ctx *ctx = nullptr;

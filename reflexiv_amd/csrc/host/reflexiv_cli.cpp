@@ -2,7 +2,8 @@
 // `reflexiv_host sort -kmerc COUNTS -kmer K [-klist 23,31,...] -outfile O` (Count_<K>_sorted), `firstfour`, `iteration`,
 // `reflexiv_host reduce -kmerc SHORT -kmerc2 LONG -kmer K1 -kmer2 K2 [-klist ...] -partition P -outfile O` (Count_<K1>_reduced and
 // Count_<K2>_sorted, or Count_<K2>_reduced when K2 is the last k of the list), `reflexiv_host reduce -kmerc DIR -klist ... -partition P
-// -outfile O` (DIR/Count_<k> of every k of the list: each through `sort`, then the pairs in the list's order)
+// -outfile O` (DIR/Count_<k> of every k of the list: each through `sort`, then the pairs in the list's order),
+// `reflexiv_host fixing -kmerc ITERATION_OUT [-klist ...] -partition P -outfile O` (O/Assembly_intermediate/04Fixing)
 // the two launcher sub-commands of bin/reflexiv:252-271 that reach the hot path
 // (M/Main.java:59-79, M/MainOfCounter.java:60-80), on one MI355X instead of spark-submit.
 #include <zlib.h>
@@ -34,7 +35,8 @@ int main(int argc, char **argv) {
         if (argc < 2) { std::cerr << "usage: reflexiv_host <run|counter|sort|firstfour|iteration> -fastq F[,F2...] -outfile DIR [-kmer 31 -cover 2 ...]\n"
                                    "       reflexiv_host sort -kmerc COUNTS -kmer K [-klist 23,31,41,53,67,81,95] -outfile DIR\n"
                                    "       reflexiv_host reduce -kmerc SHORT -kmerc2 LONG -kmer K1 -kmer2 K2 [-klist ...] -partition P -outfile DIR\n"
-                                   "       reflexiv_host reduce -kmerc COUNTS_DIR -klist K1,K2,... -partition P -outfile DIR\n"; return 2; }
+                                   "       reflexiv_host reduce -kmerc COUNTS_DIR -klist K1,K2,... -partition P -outfile DIR\n"
+                                   "       reflexiv_host fixing -kmerc ITERATION_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"; return 2; }
         std::string cmd = argv[1];
         std::vector<std::string> args(argv + 2, argv + argc);
         reflexiv::DefaultParam param = reflexiv::importCommandLine(args);
@@ -48,6 +50,8 @@ int main(int argc, char **argv) {
         if (cmd == "reduce" && !param.inputKmerPath2.empty() && (param.kmerSize < 8 || param.kmerSize >= param.kmerSize2 || param.kmerSize2 > 124))
             throw std::runtime_error("reduce: the pair -kmer " + std::to_string(param.kmerSize) + " -kmer2 " + std::to_string(param.kmerSize2) +
                                      " is not supported (8 <= k1 < k2 <= 124)");
+        if (cmd == "fixing" && (param.inputKmerPath.empty() || param.outputPath.empty()))
+            throw std::runtime_error("fixing needs -kmerc ITERATION_OUT [-klist 23,31,...] -partition P [-maxiter M -scramble S] -outfile DIR");
         if (param.outputPath.empty()) throw std::runtime_error("-outfile is required");
         if (param.inputFqPath.empty() && param.inputKmerPath.empty()) throw std::runtime_error("-fastq or -kmerc is required");
         auto read_all = [&](const std::string &paths) {
@@ -142,6 +146,15 @@ int main(int argc, char **argv) {
             out = m.assemblyDynamicIteration(read_all(param.inputKmerPath), param.startIteration, param.endIteration);
             dir += "/Assembly_intermediate"; mkdir(dir.c_str(), 0755);
             dir += "/01Iteration" + std::to_string(param.startIteration) + "_" + std::to_string(param.endIteration); mkdir(dir.c_str(), 0755);
+        } else if (cmd == "fixing") {
+            // Pipelines.reflexivDSDynamicAssemblyStepsPipe() behind the last iteration (Pipelines.java:840-1291): the rows of
+            // 01Iteration<start>_<end> -> 04Fixing; maxKmerSize is the last k of the list
+            const int P = param.partitions > 0 ? param.partitions : param.logicalPartitions;
+            if (P < 1 || P > 63) throw std::runtime_error("fixing: -partition must be 1..63");
+            if (m.lastKmerOfList() < 31 || m.lastKmerOfList() > 124) throw std::runtime_error("fixing: the last k of -klist must be 31..124");
+            out = m.contigFixing(read_all(param.inputKmerPath), P);
+            dir += "/Assembly_intermediate"; mkdir(dir.c_str(), 0755);
+            dir += "/04Fixing"; mkdir(dir.c_str(), 0755);
         } else if (cmd == "counter") {
             // --resident at k = 33..100 (not 64 or 96): the same rows through the device count of the packed reads
             out = param.resident && param.kmerSize >= 33 && param.kmerSize % 32 != 0 ? m.counterResident(read_all(param.inputFqPath))
@@ -149,7 +162,7 @@ int main(int argc, char **argv) {
             dir += "/Count_" + std::to_string(param.kmerSize);               // P/ReflexivDataFrameCounter.java:222-233
             mkdir(dir.c_str(), 0755);
         } else throw std::runtime_error("unknown command " + cmd);
-        std::ofstream(dir + (cmd == "counter" || cmd == "sort" || cmd == "firstfour" || cmd == "iteration" ? "/part-00000.csv" : "/part-00000"), std::ios::binary) << out;   // saveAsTextFile / csv
+        std::ofstream(dir + (cmd == "counter" || cmd == "sort" || cmd == "firstfour" || cmd == "iteration" || cmd == "fixing" ? "/part-00000.csv" : "/part-00000"), std::ios::binary) << out;   // saveAsTextFile / csv
         std::ofstream(dir + "/_SUCCESS", std::ios::binary);
         return 0;
     } catch (const std::exception &e) {

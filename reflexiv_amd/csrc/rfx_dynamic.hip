@@ -63,6 +63,8 @@ int rfx::dyn_alloc(rfx_ctx *ctx, DynDev &d, int64_t n, int64_t words) {
 namespace {
 
 // ---- words ----------------------------------------------------------------------------------------------------------------
+// (dyn_keep, dyn_seg32, dyn_cat32 and dyn_find have twins in rfx_fixing.hip -- fx_keep, fx_seg32, fx_cat32, fx_find: the layout's
+// funnel shift and its zero padding.  The two copies must stay identical.)
 // the first m of 32 bases, the rest 0
 __device__ __forceinline__ uint64_t dyn_keep(uint64_t x, int m) { return m >= 32 ? x : m <= 0 ? 0ull : x & ~(~0ull >> (2 * m)); }
 // the 32 bases that start at base t of one packed segment of len bases (t < 0: the segment begins -t bases into the window);
@@ -477,11 +479,9 @@ int rfx::dyn_sort(rfx_ctx *ctx, const DynDev &in, int P, DynDev &out, DevBuf &d_
     RFX_HIP(hipGetLastError());
     return RFX_OK;
 }
-namespace {
-
 // one pass over sorted records: in (sorted), d_ps -> out, d_out_ps (optional)
-static int dyn_pass(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, uint32_t lmin, int stage, int start_iteration, int start_marker,
-                    DynDev &out, int64_t *d_out_ps) {
+int rfx::dyn_pass(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, uint32_t lmin, int stage, int start_iteration, int start_marker,
+                  DynDev &out, int64_t *d_out_ps) {
     const int64_t n = in.n;
     DevBuf head, cnt, base, desc, pbase;
     RFX_HIP(pbase.alloc((size_t)(P + 1) * 8, ctx->stream));
@@ -509,6 +509,7 @@ static int dyn_pass(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, 
     RFX_HIP(hipGetLastError());
     return dyn_emit(ctx, in, desc, (int64_t)ne, pbase.as<uint64_t>(), P, start_marker, out);
 }
+namespace {
 
 static int dyn_reflect(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, DynDev &out) {
     DevBuf desc, pbase;
@@ -778,8 +779,9 @@ __global__ __launch_bounds__(256) void k_dyn_bin_ext(const char *__restrict__ te
     oext[w] = dyn_code32(text + ebeg[r] + 32 * (int64_t)j, ext_len[r] - 32 * j);
 }
 
+}  // namespace
 // text in HBM (row r = d_text[d_row_off[r], d_row_off[r + 1])) -> a packed set in the library's own buffers
-static int dyn_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, int form, DynDev &d) {
+int rfx::dyn_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, int form, DynDev &d) {
     if (n == 0) {
         RFX_TRY(dyn_alloc(ctx, d, 0, 0));
         RFX_HIP(hipMemsetAsync(d.ext_off.p, 0, 8, ctx->stream));
@@ -814,7 +816,6 @@ static int dyn_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_o
     }
     return RFX_OK;
 }
-}  // namespace
 // host text -> HBM: the rows' bytes and their offsets relative to the first row
 int rfx::dyn_upload_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, DevBuf &d_text, DevBuf &d_off) {
     for (int64_t i = 0; i < n_rows; i++) if (row_off[i + 1] < row_off[i]) return RFX_E_ARG;
@@ -877,8 +878,9 @@ __global__ __launch_bounds__(256) void k_dyn_text_fill(const DynView v, int64_t 
     }
     out[b] = ch;
 }
+}  // namespace
 // the text of a set into d_text (filled up to cap); *total = its length
-static int dyn_to_text(rfx_ctx *ctx, const DynDev &d, char *d_text, int64_t cap, int64_t *total, DevBuf *own) {
+int rfx::dyn_to_text(rfx_ctx *ctx, const DynDev &d, char *d_text, int64_t cap, int64_t *total, DevBuf *own) {
     const int64_t n = d.n;
     *total = 0;
     if (n == 0) return RFX_OK;
@@ -902,6 +904,7 @@ static int dyn_to_text(rfx_ctx *ctx, const DynDev &d, char *d_text, int64_t cap,
     }
     return sync_checked(ctx);
 }
+namespace {
 
 // The drivers, records resident in HBM between the operators.  FirstFour.assemblyFromKmer (:137-224): binarized records
 // (key = the k-mer without its last base, extension = that base, orientation 1) -> DSkmerRandomReflection on P equal

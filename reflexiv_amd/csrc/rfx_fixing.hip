@@ -1,0 +1,625 @@
+// rfx_fixing.hip -- the contig fixing stage (Assembly_intermediate/04Fixing) on packed record sets that stay in HBM (DESIGN.md
+// section 19): P/ReflexivDSDynamicKmerFixing.java, driver `assemblyFromKmer` :125-260 --
+// DynamicKmerBinarizerFromReducedToSubKmer (:3106-3203), DSExtractFixingKmerFromContigEnds (:1190-1256), DSgetFixingLongKmer
+// (:520-541), DSgetFixingKmer (:857-874), groupBy("kmer").count() (:206), DSFixingKmerLeftAndRightMarkerAssignment (:1857-1878),
+// union (:213), sort("k-1"), DSFilterForkSubKmerWithErrorCorrection (:2057-2116), DSChangingFixingKmerToReflectedKmer
+// (:1571-1608), sort("k-1"), DSFilterForkReflectedSubKmerWithErrorCorrection (:2232-2283), DSExtendFixingKmerLoop (:2371-3104)
+// once on the fold's partitions and then behind a sort min(maximumIteration + 1, 17) times (:229-243), and
+// DSBinaryFixingKmerWithLongExtensionToString (:262-299).
+//
+// The record sets are rfx_dyn_packed (rfx_dynamic.hip): four key words per record, 32 bases per word, the first base in the two
+// highest bits, every bit past the last base 0 and every unused key word 0 -- every producer here writes those zeros.  From the
+// contig ends on every key has FixedKmerSize - 1 = 30 bases in ONE word, which is also the one signed long the reference sorts by.
+// The sorts are rfx_dynamic.hip's (dyn_sort), and so are the binarizer (form 1), the loop and the text writer (dyn_binarize,
+// dyn_pass, dyn_to_text, all unchanged): with every key 30 bases long the loop is the dynamic-k pass with no prefix relation,
+// `extra` = 0 and the stage branches out of reach, which tests/golden/fixing_vectors.npz decides stage by stage.
+//
+// New here is the work on whole contigs, thousands of bases long and skewed in length, so no thread loops over one.  The contig
+// ends: a scan of per-contig output counts, then one thread per 31-mer (a funnel shift out of key||extension or extension||key)
+// and one thread per output WORD of a trimmed contig, its record found through the scanned word offsets.  The distinct 31-mers:
+// the 62-bit values through the radix sort, head flags, a scan, and the heads straight into one-base records.  The two folds
+// have a closed form per run of equal keys inside a partition -- a run with a row longer than one base keeps exactly those rows,
+// in order; any other run keeps its LAST row of the smallest base code -- so they are flags, one 64-bit atomicMin per row of a
+// run of two or more, and a compaction; no walk.  The reflection re-cuts the same concatenation, one thread per output word.
+//
+// DEVIATIONS from the reference, stated in the header too: a row whose sub-k-mer exceeds 124 bases is RFX_E_LIMIT for the set
+// (the reference would carry it); a ')' behind the extension is dropped as rfx_dyn_binarize form 1 drops it (the reference
+// reads it as a base); the distinct 31-mers come out in ascending order where Spark's groupBy gives its hash order (nothing
+// from the first fold on depends on it: the vector generator runs every case under two orders).
+#include <algorithm>
+#include <string>
+#include <vector>
+#include "rfx_internal.h"
+
+using namespace rfx;
+
+namespace {
+
+#define FX_KW RFX_DYN_KEY_WORDS
+#define FX_GRID(n) dim3((unsigned)ceil_div(std::max<int64_t>((n), 1), 256)), dim3(256), 0, ctx->stream
+#define FX_K 31                      // FixedKmerSize
+#define FX_KEY (FX_K - 1)            // the key of every record behind the contig ends
+
+// flags of a call, in HBM: what is wrong with the input, and three 64-bit totals: one small read-back for all of them
+struct FxFlags { uint32_t bad, pad; uint64_t t0, t1, t2; };
+enum { FX_BAD_KEY = 1, FX_BAD_EXT = 2, FX_BAD_VALUE = 4 };
+
+static int fx_flags_init(rfx_ctx *ctx, DevBuf &flags) {
+    RFX_HIP(flags.alloc(sizeof(FxFlags), ctx->stream));
+    RFX_HIP(hipMemsetAsync(flags.p, 0, sizeof(FxFlags), ctx->stream));
+    return RFX_OK;
+}
+__global__ void k_fx_put_totals(const uint64_t *__restrict__ a, const uint64_t *__restrict__ b, const uint64_t *__restrict__ c, uint64_t *__restrict__ flags) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) { flags[1] = a ? *a : 0ull; flags[2] = b ? *b : 0ull; flags[3] = c ? *c : 0ull; }
+}
+static int fx_flags_read(rfx_ctx *ctx, const DevBuf &flags, const uint64_t *a, const uint64_t *b, const uint64_t *c, FxFlags *h) {
+    hipLaunchKernelGGL(k_fx_put_totals, dim3(1), dim3(1), 0, ctx->stream, a, b, c, flags.as<uint64_t>());
+    RFX_HIP(hipGetLastError());
+    return small_readback(ctx, h, flags.p, sizeof(FxFlags));
+}
+
+// ---- words (rfx_dynamic.hip's forms) ---------------------------------------------------------------------------------------------------
+// (fx_keep, fx_seg32, fx_cat32 and fx_find are the twins of rfx_dynamic.hip's dyn_keep, dyn_seg32, dyn_cat32 and dyn_find, which stay
+// private to that file: the two copies must stay identical.)
+// the first m of 32 bases, the rest 0
+__device__ __forceinline__ uint64_t fx_keep(uint64_t x, int m) { return m >= 32 ? x : m <= 0 ? 0ull : x & ~(~0ull >> (2 * m)); }
+// the 32 bases that start at base t of one packed segment of len bases (t < 0: the segment begins -t bases into the window); 0
+// where the segment has no base -- the zero padding of the layout does the masking
+__device__ __forceinline__ uint64_t fx_seg32(const uint64_t *__restrict__ w, int len, int t) {
+    if (len <= 0 || t >= len || t <= -32) return 0ull;
+    if (t < 0) return w[0] >> (2 * -t);
+    const int wi = t >> 5, sh = (t & 31) * 2;
+    uint64_t r = w[wi] << sh;
+    if (sh && wi + 1 < ((len + 31) >> 5)) r |= w[wi + 1] >> (64 - sh);
+    return r;
+}
+// a contig as its record holds it: key || extension for marker 1, extension || key otherwise
+struct FxCat { const uint64_t *w0, *w1; int l0, l1; };
+__device__ __forceinline__ FxCat fx_contig(const DynView &v, int64_t i) {
+    const uint64_t *k = v.key + FX_KW * i, *e = v.ext + v.ext_off[i];
+    const int kl = (int)v.key_len[i], el = v.ext_len[i];
+    return v.marker[i] == 1 ? FxCat{k, e, kl, el} : FxCat{e, k, el, kl};
+}
+// the 32 bases that start at base t of the contig (0 past its end)
+__device__ __forceinline__ uint64_t fx_cat32(const FxCat &c, int t) { return fx_seg32(c.w0, c.l0, t) | fx_seg32(c.w1, c.l1, t - c.l0); }
+// the largest i < n with off[i] <= x (off[0] = 0 <= x): the record that owns word / item x; records of size 0 are skipped
+__device__ __forceinline__ int64_t fx_find(const uint64_t *__restrict__ off, int64_t n, int64_t x) {
+    int64_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int64_t)off[mid] <= x) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// ---- a compaction: output record q := input record idx[q] -------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_fx_index(const uint32_t *__restrict__ keep, const uint64_t *__restrict__ rank, int64_t n, int64_t *__restrict__ idx) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && keep[i]) idx[rank[i]] = i;
+}
+__global__ __launch_bounds__(256) void k_fx_gather_rec(const DynView v, const int64_t *__restrict__ idx, int64_t m, const DynOut o, uint32_t *__restrict__ ew) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= m) return;
+    const int64_t i = idx[q];
+    const uint64_t *s = v.key + FX_KW * i;
+    uint64_t *d = o.key + FX_KW * q;
+    d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3];
+    o.key_len[q] = v.key_len[i];
+    o.ext_len[q] = v.ext_len[i];
+    o.marker[q] = v.marker[i]; o.left[q] = v.left[i]; o.right[q] = v.right[i];
+    ew[q] = (uint32_t)((v.ext_len[i] + 31) >> 5);
+}
+// one thread per output extension word (the grid covers a bound; the exact count is ooff[m])
+__global__ __launch_bounds__(256) void k_fx_gather_ext(const DynView v, const int64_t *__restrict__ idx, int64_t m, const uint64_t *__restrict__ ooff,
+                                                       uint64_t *__restrict__ oext) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m <= 0 || w >= (int64_t)ooff[m]) return;
+    const int64_t q = fx_find(ooff, m, w);
+    oext[w] = v.ext[v.ext_off[idx[q]] + (w - (int64_t)ooff[q])];
+}
+
+// ---- step 1: the length filter behind the binarizer ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_fx_long_enough(const uint8_t *__restrict__ key_len, const int32_t *__restrict__ ext_len, int64_t n, int min_len,
+                                                        uint32_t *__restrict__ keep) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) keep[i] = (int64_t)key_len[i] + ext_len[i] >= min_len ? 1u : 0u;
+}
+
+// ---- steps 2-3: the contig ends -----------------------------------------------------------------------------------------------------------
+// per contig: its 31-mers (0 or 2 (max_k - 30)), whether it gives a long record, and that record's extension words
+__global__ __launch_bounds__(256) void k_fx_ends_sizes(const uint8_t *__restrict__ key_len, const int32_t *__restrict__ ext_len, int64_t n, int max_k,
+                                                       uint32_t *__restrict__ nk, uint32_t *__restrict__ nl, uint32_t *__restrict__ nw) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t L = (int64_t)key_len[i] + ext_len[i];
+    const bool ok = L >= 2 * max_k;
+    const int cut = max_k - FX_KEY;
+    nk[i] = ok ? (uint32_t)(2 * cut) : 0u;
+    nl[i] = ok ? 1u : 0u;
+    nw[i] = ok ? (uint32_t)((L - 2 * cut - FX_KEY + 31) >> 5) : 0u;
+}
+// one thread per 31-mer: item 2 j of contig i = bases [j, j + 31), item 2 j + 1 = bases [L - j - 31, L - j); the value holds its
+// first base in bits 61..60
+__global__ __launch_bounds__(256) void k_fx_ends_kmers(const DynView v, int64_t n, const uint64_t *__restrict__ koff, uint64_t *__restrict__ out) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)koff[n]) return;
+    const int64_t i = fx_find(koff, n, t);
+    const int j = (int)(t - (int64_t)koff[i]);
+    const FxCat c = fx_contig(v, i);
+    const int L = c.l0 + c.l1;
+    out[t] = fx_cat32(c, (j & 1) ? L - (j >> 1) - FX_K : (j >> 1)) >> 2;
+}
+// the trimmed contigs, bases [cut, L - cut) cut key 30 / rest: threads [0, 4 m) write the key words and the record's fields,
+// threads [4 m, 4 m + words) one extension word each
+__global__ __launch_bounds__(256) void k_fx_ends_long(const DynView v, int64_t n, int max_k, const uint64_t *__restrict__ loff, const uint64_t *__restrict__ woff,
+                                                      const DynOut o) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t m = (int64_t)loff[n], words = (int64_t)woff[n];
+    const int cut = max_k - FX_KEY;
+    if (t == 0) o.ext_off[m] = words;
+    if (t < FX_KW * m) {
+        const int64_t q = t / FX_KW, i = fx_find(loff, n, q);
+        const int j = (int)(t % FX_KW);
+        const FxCat c = fx_contig(v, i);
+        o.key[t] = j == 0 ? fx_keep(fx_cat32(c, cut), FX_KEY) : 0ull;
+        if (j == 0) {
+            const int l = v.left[i], r = v.right[i];
+            o.key_len[q] = (uint8_t)FX_KEY;
+            o.ext_off[q] = (int64_t)woff[i];
+            o.ext_len[q] = c.l0 + c.l1 - 2 * cut - FX_KEY;
+            o.marker[q] = 1; o.left[q] = l > 0 ? max_k + 3 : l; o.right[q] = r > 0 ? max_k + 3 : r;
+        }
+    } else if (t - FX_KW * m < words) {
+        const int64_t w = t - FX_KW * m, i = fx_find(woff, n, w);
+        const int64_t r = w - (int64_t)woff[i];
+        const FxCat c = fx_contig(v, i);
+        const int el = c.l0 + c.l1 - 2 * cut - FX_KEY;
+        o.ext[w] = fx_keep(fx_cat32(c, cut + FX_KEY + (int)(32 * r)), el - (int)(32 * r));
+    }
+}
+
+// ---- steps 4-5: the distinct 31-mers as records, then the long records -------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_fx_iota(int64_t n, uint32_t *__restrict__ v) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) v[i] = (uint32_t)i;
+}
+// (a value of 2^62 or more is no 31-mer: the sort orders 62 bits only, so it is refused, not compared)
+__global__ __launch_bounds__(256) void k_fx_value_heads(const uint64_t *__restrict__ val, int64_t n, uint32_t *__restrict__ head, uint32_t *__restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    head[i] = (i == 0 || val[i] != val[i - 1]) ? 1u : 0u;
+    if (val[i] >> (2 * FX_K)) atomicOr(flags, (uint32_t)FX_BAD_VALUE);
+}
+// a head writes record rank[i]: key = the first 30 bases, extension = the last base, attribute (1, -1, -1)
+__global__ __launch_bounds__(256) void k_fx_set_kmers(const uint64_t *__restrict__ val, const uint32_t *__restrict__ head, const uint64_t *__restrict__ rank,
+                                                      int64_t n, const DynOut o) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !head[i]) return;
+    const int64_t q = (int64_t)rank[i];
+    const uint64_t x = val[i] << 2;
+    uint64_t *d = o.key + FX_KW * q;
+    d[0] = fx_keep(x, FX_KEY); d[1] = 0; d[2] = 0; d[3] = 0;
+    o.key_len[q] = (uint8_t)FX_KEY;
+    o.ext[q] = (x << (2 * FX_KEY)) & (3ull << 62);
+    o.ext_off[q] = q;
+    o.ext_len[q] = 1;
+    o.marker[q] = 1; o.left[q] = -1; o.right[q] = -1;
+}
+// the long records behind the d one-base records: record base + i, its words moved by base (a one-base record takes one word)
+__global__ __launch_bounds__(256) void k_fx_set_long(const DynView v, int64_t n, int64_t words, int64_t base, const DynOut o) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t == 0) o.ext_off[base + n] = base + words;
+    if (t < n) {
+        const uint64_t *s = v.key + FX_KW * t;
+        uint64_t *d = o.key + FX_KW * (base + t);
+        d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3];
+        o.key_len[base + t] = v.key_len[t];
+        o.ext_off[base + t] = base + v.ext_off[t];
+        o.ext_len[base + t] = v.ext_len[t];
+        o.marker[base + t] = v.marker[t]; o.left[base + t] = v.left[t]; o.right[base + t] = v.right[t];
+    }
+    if (t < words) o.ext[base + t] = v.ext[t];
+}
+
+// ---- what the folds and the reflection ask of their input: keys of 30 bases, extensions of one base or more -------------------------------
+__global__ __launch_bounds__(256) void k_fx_check(const DynView v, int64_t n, uint32_t *__restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t bad = ((int)v.key_len[i] != FX_KEY ? (uint32_t)FX_BAD_KEY : 0u) | (v.ext_len[i] < 1 ? (uint32_t)FX_BAD_EXT : 0u);
+    if (bad) atomicOr(flags, bad);
+}
+
+// ---- steps 6 and 8: the two folds ---------------------------------------------------------------------------------------------------------
+// the first row of every partition that has rows (head is zeroed before)
+__global__ void k_fx_part_heads(const int64_t *__restrict__ ps, int P, uint32_t *__restrict__ head) {
+    const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (p < P && ps[p] < ps[p + 1]) atomicOr(head + ps[p], 1u);
+}
+__global__ __launch_bounds__(256) void k_fx_key_heads(const uint64_t *__restrict__ key, int64_t n, uint32_t *__restrict__ head) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (i == 0 || key[FX_KW * i] != key[FX_KW * (i - 1)]) head[i] = 1u;      // (a partition's first row holds 1 already)
+}
+// a row's word in its run's contest: 0 for a row longer than one base, else the base code and then the row's index counted down --
+// the smallest one is the LAST row of the smallest code.  Runs of one row are settled here.
+__device__ __forceinline__ uint64_t fx_fold_word(const DynView &v, int64_t i) {
+    if (v.ext_len[i] > 1) return 0ull;
+    return (1ull << 40) | ((v.ext[v.ext_off[i]] >> 62) << 32) | (uint64_t)(uint32_t)~(uint32_t)i;
+}
+__global__ __launch_bounds__(256) void k_fx_fold_contest(const DynView v, int64_t n, const uint32_t *__restrict__ head, const uint64_t *__restrict__ run,
+                                                         unsigned long long *__restrict__ best) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (head[i] && (i + 1 == n || head[i + 1])) return;            // a run of one
+    atomicMin(best + (run[i + 1] - 1), (unsigned long long)fx_fold_word(v, i));
+}
+__global__ __launch_bounds__(256) void k_fx_fold_keep(const DynView v, int64_t n, const uint32_t *__restrict__ head, const uint64_t *__restrict__ run,
+                                                      const unsigned long long *__restrict__ best, uint32_t *__restrict__ keep) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t kp = 1u;
+    if (!(head[i] && (i + 1 == n || head[i + 1]))) {
+        const uint64_t w = fx_fold_word(v, i);
+        kp = (w == 0ull || best[run[i + 1] - 1] == w) ? 1u : 0u;
+    }
+    keep[i] = kp;
+}
+// where the partitions begin in the output: P + 1 entries
+__global__ void k_fx_out_ps(const int64_t *__restrict__ ps, int P, const uint64_t *__restrict__ rank, int64_t *__restrict__ out_ps) {
+    const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (p <= P) out_ps[p] = (int64_t)rank[ps[p]];
+}
+
+// ---- step 7: DSChangingFixingKmerToReflectedKmer -- key = the LAST 30 bases of the contig, extension = its front, marker 2.  The key
+// has 30 bases before and after, so every extension keeps its length and its words: threads [0, 4 n) write the key words and the
+// fields, threads [4 n, 4 n + words) one extension word each
+__global__ __launch_bounds__(256) void k_fx_reflect(const DynView v, int64_t n, const DynOut o) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t words = v.ext_off[n];
+    if (t == 0) o.ext_off[n] = words;
+    if (t < FX_KW * n) {
+        const int64_t i = t / FX_KW;
+        const int j = (int)(t % FX_KW);
+        const FxCat c = fx_contig(v, i);
+        o.key[t] = j == 0 ? fx_keep(fx_cat32(c, c.l0 + c.l1 - FX_KEY), FX_KEY) : 0ull;
+        if (j == 0) {
+            o.key_len[i] = (uint8_t)FX_KEY;
+            o.ext_off[i] = v.ext_off[i];
+            o.ext_len[i] = v.ext_len[i];
+            o.marker[i] = 2; o.left[i] = v.left[i]; o.right[i] = v.right[i];
+        }
+    } else if (t - FX_KW * n < words) {
+        const int64_t w = t - FX_KW * n, i = fx_find((const uint64_t *)v.ext_off, n, w);
+        const int64_t r = w - v.ext_off[i];
+        o.ext[w] = fx_keep(fx_cat32(fx_contig(v, i), (int)(32 * r)), v.ext_len[i] - (int)(32 * r));
+    }
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------------------
+struct FxParams { int max_k, scramble, max_iteration; };
+
+static int fx_params(rfx_ctx *ctx, const rfx_fix_params *p, FxParams *o) {
+    if (!p) return RFX_E_ARG;
+    if (p->max_k < FX_K || p->max_k > 124) { ctx->last_error = "contig fixing: max_k must be 31..124"; return RFX_E_ARG; }
+    if (p->max_iteration < -1) { ctx->last_error = "contig fixing: max_iteration below -1"; return RFX_E_ARG; }
+    *o = FxParams{p->max_k, p->scramble, p->max_iteration};
+    return RFX_OK;
+}
+static bool fx_out_ok(const rfx_dyn_packed *p) {
+    return p && p->key && p->key_len && p->ext && p->ext_off && p->ext_len && p->marker && p->left && p->right;
+}
+static bool fx_in_ok(const rfx_dyn_packed *p) { return fx_out_ok(p) && p->n >= 0; }
+static bool fx_text_ok(const char *t, const int64_t *off, int64_t n) { return n >= 0 && (n == 0 || (t && off)); }
+static int fx_empty(rfx_ctx *ctx, DynDev &d) {
+    RFX_TRY(dyn_alloc(ctx, d, 0, 0));
+    RFX_HIP(hipMemsetAsync(d.ext_off.p, 0, 8, ctx->stream));
+    return RFX_OK;
+}
+// keys of 30 bases, extensions of one base or more
+static int fx_check(rfx_ctx *ctx, const DynDev &in) {
+    if (in.n == 0) return RFX_OK;
+    DevBuf flags;
+    RFX_TRY(fx_flags_init(ctx, flags));
+    hipLaunchKernelGGL(k_fx_check, FX_GRID(in.n), dyn_view(in), in.n, flags.as<uint32_t>());
+    RFX_HIP(hipGetLastError());
+    FxFlags f{};
+    RFX_TRY(fx_flags_read(ctx, flags, nullptr, nullptr, nullptr, &f));
+    if (f.bad) {
+        ctx->last_error = f.bad & FX_BAD_KEY ? "contig fixing: a key that is not 30 bases long" : "contig fixing: a record without an extension";
+        return RFX_E_ARG;
+    }
+    return RFX_OK;
+}
+// the caller's partition starts: P + 1 entries, 0 first, n last, never running backwards -- read back and checked BEFORE a kernel
+// indexes with them
+static int fx_check_starts(rfx_ctx *ctx, const int64_t *d_ps, int P, int64_t n) {
+    int64_t h[65];
+    RFX_TRY(small_readback(ctx, h, d_ps, (size_t)(P + 1) * 8));
+    bool ok = h[0] == 0 && h[P] == n;
+    for (int p = 0; p < P && ok; p++) ok = h[p] <= h[p + 1];
+    if (!ok) { ctx->last_error = "contig fixing: partition starts that do not run from 0 to n"; return RFX_E_ARG; }
+    return RFX_OK;
+}
+// the kept records of a set, in order (keep / rank: n flags and their exclusive scan, rank[n] = m)
+static int fx_compact(rfx_ctx *ctx, const DynDev &in, const DevBuf &keep, const DevBuf &rank, int64_t m, DynDev &out) {
+    if (m == 0) return fx_empty(ctx, out);
+    const int64_t n = in.n;
+    DevBuf idx, ew;
+    RFX_HIP(idx.alloc((size_t)m * 8, ctx->stream)); RFX_HIP(ew.alloc((size_t)m * 4, ctx->stream));
+    RFX_TRY(dyn_alloc(ctx, out, m, in.words));
+    const DynView v = dyn_view(in);
+    hipLaunchKernelGGL(k_fx_index, FX_GRID(n), (const uint32_t *)keep.as<uint32_t>(), (const uint64_t *)rank.as<uint64_t>(), n, idx.as<int64_t>());
+    RFX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_fx_gather_rec, FX_GRID(m), v, (const int64_t *)idx.as<int64_t>(), m, dyn_out(out), ew.as<uint32_t>());
+    RFX_HIP(hipGetLastError());
+    RFX_TRY(exclusive_scan_u32_to_u64(ctx, ew.as<uint32_t>(), out.ext_off.as<uint64_t>(), m));
+    if (in.words > 0) {
+        hipLaunchKernelGGL(k_fx_gather_ext, FX_GRID(in.words), v, (const int64_t *)idx.as<int64_t>(), m, (const uint64_t *)out.ext_off.as<uint64_t>(),
+                           out.ext.as<uint64_t>());
+        RFX_HIP(hipGetLastError());
+    }
+    return RFX_OK;
+}
+
+// step 1: the binarizer (form 1) and its length filter
+static int fx_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, const FxParams &prm, DynDev &out) {
+    if (n == 0) return fx_empty(ctx, out);
+    if (n >= ((int64_t)1 << 31)) { ctx->last_error = "contig fixing: 2^31 rows or more"; return RFX_E_LIMIT; }
+    DynDev a;
+    RFX_TRY(dyn_binarize(ctx, d_text, d_row_off, n, 1, a));
+    DevBuf keep, rank;
+    RFX_HIP(keep.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(rank.alloc((size_t)(n + 1) * 8, ctx->stream));
+    hipLaunchKernelGGL(k_fx_long_enough, FX_GRID(n), (const uint8_t *)a.key_len.as<uint8_t>(), (const int32_t *)a.ext_len.as<int32_t>(), n, 2 * prm.max_k,
+                       keep.as<uint32_t>());
+    RFX_HIP(hipGetLastError());
+    RFX_TRY(exclusive_scan_u32_to_u64(ctx, keep.as<uint32_t>(), rank.as<uint64_t>(), n));
+    uint64_t m = 0;
+    RFX_TRY(small_readback(ctx, &m, rank.as<uint64_t>() + n, 8));
+    return fx_compact(ctx, a, keep, rank, (int64_t)m, out);
+}
+
+// steps 2-3: the long records, and the 31-mers in emission order (contig by contig, i = 0 .. max_k - 31, left then right)
+static int fx_contig_ends(rfx_ctx *ctx, const DynDev &in, const FxParams &prm, DynDev &out, DevBuf &kmers, int64_t *n_kmers) {
+    const int64_t n = in.n;
+    *n_kmers = 0;
+    RFX_HIP(kmers.alloc(8, ctx->stream));
+    if (n == 0) return fx_empty(ctx, out);
+    DevBuf nk, nl, nw, koff, loff, woff, flags;
+    RFX_HIP(nk.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(nl.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(nw.alloc((size_t)n * 4, ctx->stream));
+    RFX_HIP(koff.alloc((size_t)(n + 1) * 8, ctx->stream)); RFX_HIP(loff.alloc((size_t)(n + 1) * 8, ctx->stream));
+    RFX_HIP(woff.alloc((size_t)(n + 1) * 8, ctx->stream));
+    RFX_TRY(fx_flags_init(ctx, flags));
+    const DynView v = dyn_view(in);
+    hipLaunchKernelGGL(k_fx_ends_sizes, FX_GRID(n), v.key_len, v.ext_len, n, prm.max_k, nk.as<uint32_t>(), nl.as<uint32_t>(), nw.as<uint32_t>());
+    RFX_HIP(hipGetLastError());
+    RFX_TRY(exclusive_scan2_u32_to_u64(ctx, nk.as<uint32_t>(), nl.as<uint32_t>(), koff.as<uint64_t>(), loff.as<uint64_t>(), n));
+    RFX_TRY(exclusive_scan_u32_to_u64(ctx, nw.as<uint32_t>(), woff.as<uint64_t>(), n));
+    FxFlags f{};
+    RFX_TRY(fx_flags_read(ctx, flags, koff.as<uint64_t>() + n, loff.as<uint64_t>() + n, woff.as<uint64_t>() + n, &f));
+    const int64_t n31 = (int64_t)f.t0, m = (int64_t)f.t1, words = (int64_t)f.t2;
+    *n_kmers = n31;
+    if (m == 0) return fx_empty(ctx, out);
+    RFX_HIP(kmers.alloc((size_t)n31 * 8, ctx->stream));
+    RFX_TRY(dyn_alloc(ctx, out, m, words));
+    hipLaunchKernelGGL(k_fx_ends_kmers, FX_GRID(n31), v, n, (const uint64_t *)koff.as<uint64_t>(), kmers.as<uint64_t>());
+    RFX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_fx_ends_long, FX_GRID(FX_KW * m + words), v, n, prm.max_k, (const uint64_t *)loff.as<uint64_t>(), (const uint64_t *)woff.as<uint64_t>(),
+                       dyn_out(out));
+    RFX_HIP(hipGetLastError());
+    return RFX_OK;
+}
+
+// steps 4-5 up to the union: the distinct 31-mers as one-base records (ascending), then the long records.  d_kmers is left as it is
+static int fx_kmer_set(rfx_ctx *ctx, const uint64_t *d_kmers, int64_t n31, const DynDev &lng, DynDev &out) {
+    if (n31 >= ((int64_t)1 << 32)) { ctx->last_error = "contig fixing: 2^32 end 31-mers or more"; return RFX_E_LIMIT; }
+    int64_t d = 0;
+    DevBuf val, idx, tk, tv, head, rank;
+    if (n31 > 0) {
+        RFX_HIP(val.alloc((size_t)n31 * 8, ctx->stream)); RFX_HIP(idx.alloc((size_t)n31 * 4, ctx->stream)); RFX_HIP(tk.alloc((size_t)n31 * 8, ctx->stream));
+        RFX_HIP(tv.alloc((size_t)n31 * 4, ctx->stream)); RFX_HIP(head.alloc((size_t)n31 * 4, ctx->stream)); RFX_HIP(rank.alloc((size_t)(n31 + 1) * 8, ctx->stream));
+        RFX_HIP(hipMemcpyAsync(val.p, d_kmers, (size_t)n31 * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_fx_iota, FX_GRID(n31), n31, idx.as<uint32_t>());
+        RFX_HIP(hipGetLastError());
+        RFX_TRY(sort_pairs(ctx, val.as<uint64_t>(), idx.as<uint32_t>(), n31, 2 * FX_K, tk.as<uint64_t>(), tv.as<uint32_t>()));
+        DevBuf flags;
+        RFX_TRY(fx_flags_init(ctx, flags));
+        hipLaunchKernelGGL(k_fx_value_heads, FX_GRID(n31), (const uint64_t *)val.as<uint64_t>(), n31, head.as<uint32_t>(), flags.as<uint32_t>());
+        RFX_HIP(hipGetLastError());
+        RFX_TRY(exclusive_scan_u32_to_u64(ctx, head.as<uint32_t>(), rank.as<uint64_t>(), n31));
+        FxFlags f{};
+        RFX_TRY(fx_flags_read(ctx, flags, rank.as<uint64_t>() + n31, nullptr, nullptr, &f));
+        if (f.bad) { ctx->last_error = "contig fixing: a 31-mer value of 2^62 or more"; return RFX_E_ARG; }
+        d = (int64_t)f.t0;
+    }
+    if (d + lng.n == 0) return fx_empty(ctx, out);
+    RFX_TRY(dyn_alloc(ctx, out, d + lng.n, d + lng.words));
+    if (d > 0) {
+        hipLaunchKernelGGL(k_fx_set_kmers, FX_GRID(n31), (const uint64_t *)val.as<uint64_t>(), (const uint32_t *)head.as<uint32_t>(),
+                           (const uint64_t *)rank.as<uint64_t>(), n31, dyn_out(out));
+        RFX_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_fx_set_long, FX_GRID(std::max(lng.n, lng.words)), dyn_view(lng), lng.n, lng.words, d, dyn_out(out));
+    RFX_HIP(hipGetLastError());
+    return RFX_OK;
+}
+
+// steps 6 and 8 over a sorted set cut into P partitions.  The two classes are one text (the base compared is the extension's first,
+// which is a one-base extension's only one), so `reflected` selects nothing here
+static int fx_fold(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, DynDev &out, DevBuf &out_ps) {
+    const int64_t n = in.n;
+    RFX_HIP(out_ps.alloc((size_t)(P + 1) * 8, ctx->stream));
+    RFX_TRY(fx_check_starts(ctx, d_ps, P, n));
+    if (n == 0) {
+        RFX_HIP(hipMemsetAsync(out_ps.p, 0, (size_t)(P + 1) * 8, ctx->stream));
+        return fx_empty(ctx, out);
+    }
+    if (n >= ((int64_t)1 << 32)) { ctx->last_error = "contig fixing: 2^32 records or more"; return RFX_E_LIMIT; }
+    RFX_TRY(fx_check(ctx, in));
+    DevBuf head, run, best, keep, rank;
+    RFX_HIP(head.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(run.alloc((size_t)(n + 1) * 8, ctx->stream)); RFX_HIP(best.alloc((size_t)n * 8, ctx->stream));
+    RFX_HIP(keep.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(rank.alloc((size_t)(n + 1) * 8, ctx->stream));
+    RFX_HIP(hipMemsetAsync(head.p, 0, (size_t)n * 4, ctx->stream));
+    RFX_HIP(hipMemsetAsync(best.p, 0xFF, (size_t)n * 8, ctx->stream));
+    const DynView v = dyn_view(in);
+    hipLaunchKernelGGL(k_fx_part_heads, dim3(1), dim3(64), 0, ctx->stream, d_ps, P, head.as<uint32_t>());
+    RFX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_fx_key_heads, FX_GRID(n), v.key, n, head.as<uint32_t>());
+    RFX_HIP(hipGetLastError());
+    RFX_TRY(exclusive_scan_u32_to_u64(ctx, head.as<uint32_t>(), run.as<uint64_t>(), n));
+    hipLaunchKernelGGL(k_fx_fold_contest, FX_GRID(n), v, n, (const uint32_t *)head.as<uint32_t>(), (const uint64_t *)run.as<uint64_t>(),
+                       best.as<unsigned long long>());
+    RFX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_fx_fold_keep, FX_GRID(n), v, n, (const uint32_t *)head.as<uint32_t>(), (const uint64_t *)run.as<uint64_t>(),
+                       (const unsigned long long *)best.as<unsigned long long>(), keep.as<uint32_t>());
+    RFX_HIP(hipGetLastError());
+    RFX_TRY(exclusive_scan_u32_to_u64(ctx, keep.as<uint32_t>(), rank.as<uint64_t>(), n));
+    uint64_t m = 0;
+    RFX_TRY(small_readback(ctx, &m, rank.as<uint64_t>() + n, 8));
+    hipLaunchKernelGGL(k_fx_out_ps, dim3(1), dim3(64), 0, ctx->stream, d_ps, P, (const uint64_t *)rank.as<uint64_t>(), out_ps.as<int64_t>());
+    RFX_HIP(hipGetLastError());
+    return fx_compact(ctx, in, keep, rank, (int64_t)m, out);
+}
+
+// step 7
+static int fx_reflect(rfx_ctx *ctx, const DynDev &in, DynDev &out) {
+    const int64_t n = in.n;
+    if (n == 0) return fx_empty(ctx, out);
+    RFX_TRY(fx_check(ctx, in));
+    RFX_TRY(dyn_alloc(ctx, out, n, in.words));
+    hipLaunchKernelGGL(k_fx_reflect, FX_GRID(FX_KW * n + in.words), dyn_view(in), n, dyn_out(out));
+    RFX_HIP(hipGetLastError());
+    return RFX_OK;
+}
+
+// steps 1-9; the set stays in HBM between the operators.  The loop is the dynamic-k pass below iteration 61 (stage 1): once on the right
+// fold's partitions without a sort, then behind a sort min(max_iteration + 1, 17) times
+static int fx_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, int P, const FxParams &prm, DynDev &out) {
+    DynDev a, b;
+    DevBuf kmers, ps, ops;
+    int64_t n31 = 0;
+    uint32_t lmin = 0;
+    const int start_marker = prm.scramble == 3 ? 1 : 2;
+    RFX_TRY(fx_binarize(ctx, d_text, d_row_off, n_rows, prm, a));
+    RFX_TRY(fx_contig_ends(ctx, a, prm, b, kmers, &n31));
+    RFX_TRY(fx_kmer_set(ctx, kmers.as<uint64_t>(), n31, b, a));
+    RFX_TRY(dyn_sort(ctx, a, P, b, ps, &lmin));
+    RFX_TRY(fx_fold(ctx, b, ps.as<int64_t>(), P, a, ops));
+    RFX_TRY(fx_reflect(ctx, a, b));
+    RFX_TRY(dyn_sort(ctx, b, P, a, ps, &lmin));
+    RFX_TRY(fx_fold(ctx, a, ps.as<int64_t>(), P, b, ops));
+    RFX_TRY(dyn_pass(ctx, b, ops.as<int64_t>(), P, b.n ? FX_KEY : 0, 1, 5, start_marker, out, nullptr));
+    const int rounds = std::min(prm.max_iteration + 1, 17);
+    for (int it = 0; it < rounds; it++) {
+        DynDev s;
+        RFX_TRY(dyn_sort(ctx, out, P, s, ps, &lmin));
+        RFX_TRY(dyn_pass(ctx, s, ps.as<int64_t>(), P, lmin, 1, 5, start_marker, out, nullptr));
+        RFX_TRY(sync_checked(ctx));                               // (s and the pass's temporaries are read until here)
+    }
+    return RFX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void rfx_fix_default_params(rfx_fix_params *p, int max_k) try {
+    if (!p) return;
+    p->max_k = max_k; p->scramble = 2; p->max_iteration = 150;
+} RFX_API_CATCH_VOID(nullptr)
+
+int rfx_dev_fix_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, const rfx_fix_params *params,
+                         rfx_dyn_packed *d_out) try {
+    if (!ctx || !fx_out_ok(d_out) || !fx_text_ok(d_text, d_row_off, n_rows)) return RFX_E_ARG;
+    FxParams prm;
+    RFX_TRY(fx_params(ctx, params, &prm));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a;
+    RFX_TRY(fx_binarize(ctx, d_text, d_row_off, n_rows, prm, a));
+    return dyn_store(ctx, a, d_out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_fix_contig_ends(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rfx_fix_params *params, rfx_dyn_packed *d_out_long, uint64_t *d_kmers,
+                            int64_t cap_kmers, int64_t *n_kmers) try {
+    if (!ctx || !fx_in_ok(d_in) || !fx_out_ok(d_out_long) || !n_kmers || cap_kmers < 0 || (cap_kmers > 0 && !d_kmers)) return RFX_E_ARG;
+    FxParams prm;
+    RFX_TRY(fx_params(ctx, params, &prm));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a, b;
+    DevBuf kmers;
+    int64_t n31 = 0, words = 0;
+    RFX_TRY(dyn_borrow(ctx, d_in, a));
+    RFX_TRY(fx_contig_ends(ctx, a, prm, b, kmers, &n31));
+    *n_kmers = n31;
+    if (b.n > 0) RFX_TRY(small_readback(ctx, &words, b.ext_off.as<int64_t>() + b.n, 8));
+    if (n31 > cap_kmers || b.n > d_out_long->cap_n || words > d_out_long->cap_words) {      // (both outputs are checked before either is written)
+        d_out_long->n = b.n; d_out_long->need_words = words;
+        return RFX_E_CAP;
+    }
+    if (n31 > 0) RFX_HIP(hipMemcpyAsync(d_kmers, kmers.p, (size_t)n31 * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    return dyn_store(ctx, b, d_out_long);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_fix_kmer_set(rfx_ctx *ctx, const uint64_t *d_kmers, int64_t n_kmers, const rfx_dyn_packed *d_long, rfx_dyn_packed *d_out) try {
+    if (!ctx || n_kmers < 0 || (n_kmers > 0 && !d_kmers) || !fx_in_ok(d_long) || !fx_out_ok(d_out)) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a, b;
+    RFX_TRY(dyn_borrow(ctx, d_long, a));
+    RFX_TRY(fx_check(ctx, a));
+    RFX_TRY(fx_kmer_set(ctx, d_kmers, n_kmers, a, b));
+    return dyn_store(ctx, b, d_out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_fix_fork_filter(rfx_ctx *ctx, int reflected, const rfx_dyn_packed *d_sorted, const int64_t *d_part_start, int P, rfx_dyn_packed *d_out,
+                            int64_t *d_out_part_start) try {
+    if (!ctx || !fx_in_ok(d_sorted) || !fx_out_ok(d_out) || !d_part_start || !d_out_part_start || P < 1 || P > 63 || (reflected != 0 && reflected != 1))
+        return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a, b;
+    DevBuf ops;
+    RFX_TRY(dyn_borrow(ctx, d_sorted, a));
+    RFX_TRY(fx_fold(ctx, a, d_part_start, P, b, ops));
+    RFX_TRY(dyn_store(ctx, b, d_out));                                // (both capacities are checked before anything is copied)
+    RFX_HIP(hipMemcpyAsync(d_out_part_start, ops.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    return sync_checked(ctx);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_fix_reflect(rfx_ctx *ctx, const rfx_dyn_packed *d_in, rfx_dyn_packed *d_out) try {
+    if (!ctx || !fx_in_ok(d_in) || !fx_out_ok(d_out)) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a, b;
+    RFX_TRY(dyn_borrow(ctx, d_in, a));
+    RFX_TRY(fx_reflect(ctx, a, b));
+    return dyn_store(ctx, b, d_out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_fix_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, int P, const rfx_fix_params *params,
+                    rfx_dyn_packed *d_out) try {
+    if (!ctx || !fx_out_ok(d_out) || !fx_text_ok(d_text, d_row_off, n_rows) || P < 1 || P > 63) return RFX_E_ARG;
+    FxParams prm;
+    RFX_TRY(fx_params(ctx, params, &prm));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a;
+    RFX_TRY(fx_run(ctx, d_text, d_row_off, n_rows, P, prm, a));
+    return dyn_store(ctx, a, d_out);
+} RFX_API_CATCH(ctx)
+
+// host text in, host text out; everything between packed and in HBM: upload, run, to-text, one copy back
+int rfx_fix_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
+                 int64_t *out_len) try {
+    if (!ctx || !fx_text_ok(text, row_off, n_rows) || P < 1 || P > 63 || !out_len || cap < 0 || (cap > 0 && !out)) return RFX_E_ARG;
+    FxParams prm;
+    RFX_TRY(fx_params(ctx, params, &prm));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DevBuf d_text, d_off, d_o;
+    DynDev a;
+    int64_t total = 0;
+    RFX_TRY(dyn_upload_text(ctx, text, row_off, n_rows, d_text, d_off));
+    RFX_TRY(fx_run(ctx, (const char *)d_text.p, (const int64_t *)d_off.as<int64_t>(), n_rows, P, prm, a));
+    RFX_TRY(dyn_to_text(ctx, a, nullptr, 0, &total, &d_o));
+    *out_len = total;
+    if (total > cap) return RFX_E_CAP;                                // (nothing written)
+    if (total > 0) RFX_HIP(hipMemcpyAsync(out, d_o.p, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    return sync_checked(ctx);
+} RFX_API_CATCH(ctx)
+
+}  // extern "C"

@@ -479,6 +479,13 @@ int dyn_sort(rfx_ctx *ctx, const DynDev &in, int P, DynDev &out, DevBuf &d_ps, u
 int dyn_borrow(rfx_ctx *ctx, const rfx_dyn_packed *p, DynDev &d);
 int dyn_store(rfx_ctx *ctx, const DynDev &d, rfx_dyn_packed *o);
 int dyn_upload_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, DevBuf &d_text, DevBuf &d_off);
+// shared with rfx_fixing.hip: the text rows of a hand-over file in HBM -> a packed set (form 0 / 1 of rfx_dyn_binarize) / one extend
+// pass over a sorted set and its P partition starts (lmin = the set's shortest key; d_out_ps optional) / the rows
+// "SUBKMER,marker|left|right,EXTENSION\n" (own: a buffer of the library's)
+int dyn_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, int form, DynDev &d);
+int dyn_pass(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, uint32_t lmin, int stage, int start_iteration, int start_marker,
+             DynDev &out, int64_t *d_out_ps);
+int dyn_to_text(rfx_ctx *ctx, const DynDev &d, char *d_text, int64_t cap, int64_t *total, DevBuf *own);
 
 // ---- rfx_ksort.hip, shared with rfx_reduce.hip: sub-k-mers -> full k-mers (marker 2: extension + key, marker 1: key + extension; every
 // extension one base) / the rows "KMER,marker|left|right\n" of the records whose key has k bases (own: a buffer of the library's)
