@@ -96,7 +96,28 @@ static void put(const rfx_fsm_step &st, const Row *const rows[3], Out *dst) {
         else dst[q++] = plain(*rows[j]);
     }
 }
-static void scanned(bool right, const Row *r, int n, const std::vector<int> &ps, int block, std::vector<Out> &out) {
+// agg[b] := the composite of the aggregates before b, as k_rd_scan_aggs computes it with one block of T threads
+static void scan_aggs_as_the_kernel(std::vector<unsigned> &agg, int nb, int T) {
+    const long per = ((long)nb + T - 1) / T;
+    std::vector<unsigned> sh(T), x(T);
+    auto b0_of = [&](int t) { return (long)t * per; };
+    auto b1_of = [&](int t) { const long b0 = (long)t * per; return b0 + per < nb ? b0 + per : (long)nb; };
+    for (int t = 0; t < T; t++) {
+        unsigned m = RFX_FSM_IDENTITY;
+        for (long b = b0_of(t); b < b1_of(t); b++) m = rfx_fsm_compose(m, agg[b]);
+        sh[t] = m;
+    }
+    for (int d = 1; d < T; d <<= 1) {                                // rd_block_scan: every thread reads, then every thread writes
+        for (int t = 0; t < T; t++) x[t] = t >= d ? rfx_fsm_compose(sh[t - d], sh[t]) : sh[t];
+        sh = x;
+    }
+    for (int t = 0; t < T; t++) {
+        unsigned run = t ? sh[t - 1] : RFX_FSM_IDENTITY;
+        for (long b = b0_of(t); b < b1_of(t); b++) { const unsigned v = agg[b]; agg[b] = run; run = rfx_fsm_compose(run, v); }
+    }
+}
+// T == 0: the aggregates are scanned by a running composite; T > 0: in the kernel's form with T threads
+static void scanned(bool right, const Row *r, int n, const std::vector<int> &ps, int block, int T, std::vector<Out> &out) {
     static std::vector<unsigned char> start, end;
     start.assign(n, 0); end.assign(n, 0);
     for (size_t p = 0; p + 1 < ps.size(); p++) if (ps[p] < ps[p + 1]) { start[ps[p]] = 1; end[ps[p + 1] - 1] = 1; }
@@ -107,8 +128,11 @@ static void scanned(bool right, const Row *r, int n, const std::vector<int> &ps,
     const int nb = (n + block - 1) / block;
     agg.assign(nb, RFX_FSM_IDENTITY);
     for (int b = 0; b < nb; b++) for (int i = b * block; i < n && i < (b + 1) * block; i++) agg[b] = rfx_fsm_compose(agg[b], map[i]);
-    unsigned run = RFX_FSM_IDENTITY;
-    for (int b = 0; b < nb; b++) { const unsigned t = agg[b]; agg[b] = run; run = rfx_fsm_compose(run, t); }
+    if (T > 0) scan_aggs_as_the_kernel(agg, nb, T);
+    else {
+        unsigned run = RFX_FSM_IDENTITY;
+        for (int b = 0; b < nb; b++) { const unsigned t = agg[b]; agg[b] = run; run = rfx_fsm_compose(run, t); }
+    }
     for (int b = 0; b < nb; b++) {
         unsigned m = agg[b];
         for (int i = b * block; i < n && i < (b + 1) * block; i++) { state[i] = rfx_fsm_apply(m, 0u); m = rfx_fsm_compose(m, map[i]); }
@@ -142,18 +166,22 @@ static void scanned(bool right, const Row *r, int n, const std::vector<int> &ps,
 }
 
 static long checked = 0;
-static void check(const std::vector<Row> &rows, const std::vector<int> &ps, int block) {
+static void check(const std::vector<Row> &rows, const std::vector<int> &ps, int block, int T) {
     for (int right = 0; right < 2; right++) {
         static std::vector<Out> a, b;
-        a.clear(); b.clear();
+        a.clear();
         for (size_t p = 0; p + 1 < ps.size(); p++) sequential(right != 0, rows.data() + ps[p], ps[p + 1] - ps[p], a);
-        scanned(right != 0, rows.data(), (int)rows.size(), ps, block, b);
-        if (!(a == b)) {
-            std::printf("MISMATCH right=%d n=%zu partitions=%zu block=%d: %zu vs %zu rows\n", right, rows.size(), ps.size() - 1, block, a.size(), b.size());
-            for (const Row &r : rows) std::printf("  row %d: %c g%d mk%d e%d\n", r.id, r.s ? 'S' : 'L', r.g, r.mk, r.ext);
-            std::exit(1);
+        for (int form = 0; form < (T > 0 ? 2 : 1); form++) {                     // the running composite, then (T > 0) the kernel's form
+            b.clear();
+            scanned(right != 0, rows.data(), (int)rows.size(), ps, block, form ? T : 0, b);
+            if (!(a == b)) {
+                std::printf("MISMATCH right=%d n=%zu partitions=%zu block=%d T=%d: %zu vs %zu rows\n", right, rows.size(), ps.size() - 1, block, form ? T : 0,
+                            a.size(), b.size());
+                if (rows.size() <= 64) for (const Row &r : rows) std::printf("  row %d: %c g%d mk%d e%d\n", r.id, r.s ? 'S' : 'L', r.g, r.mk, r.ext);
+                std::exit(1);
+            }
+            checked++;
         }
-        checked++;
     }
 }
 static Row symbol(int sym, int id) { return Row{(sym & 1) != 0, (sym >> 1) & 1, (sym >> 3) & 1 ? -1 : 5, (sym >> 2) & 1, id}; }
@@ -173,14 +201,13 @@ int main() {
                 if (A == 4) sym |= (((i * 5 + pat) >> 1) & 1 ? 4 : 0) | (((i + pat) & 1) ? 8 : 0);   // extension and sign from it
                 rows[i] = symbol(sym, i);
             }
-            check(rows, {0, n}, 3);                                             // one partition, blocks of 3: aggregates from 4 rows on
-            if (n >= 3 && code % 7 == 0) check(rows, {0, 0, n / 2, n / 2, n}, 2);    // cut in two, empty partitions between
+            check(rows, {0, n}, 3, n <= 5 || code % 8 == 0 ? 4 : 0);            // one partition, blocks of 3: aggregates from 4 rows on
+            if (n >= 3 && code % 7 == 0) check(rows, {0, 0, n / 2, n / 2, n}, 2, 2);    // cut in two, empty partitions between
         }
     }
     uint64_t x = 0x9E3779B97F4A7C15ull;
     auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; };
-    for (int t = 0; t < 40; t++) {
-        const int n = 10000;
+    auto random_rows = [&](int t, int n) {
         std::vector<Row> rows(n);
         const int long_bias = t % 4;                                             // 3: mostly long rows, state 2 for long stretches
         for (int i = 0; i < n; i++) {
@@ -189,13 +216,32 @@ int main() {
             rows[i] = symbol(sym, i);
             if (long_bias >= 2) rows[i].g = 0;                                   // one group: every prefix test passes
         }
+        return rows;
+    };
+    auto random_cuts = [&](int t, int n) {
         const int P = 1 + (int)(rnd() % 63);
         std::vector<int> ps(P + 1, 0);
         for (int p = 1; p < P; p++) ps[p] = (int)(rnd() % (n + 1));
         ps[P] = n;
         for (int p = 1; p < P; p++) for (int q = p + 1; q < P; q++) if (ps[q] < ps[p]) { const int s = ps[p]; ps[p] = ps[q]; ps[q] = s; }
         if (t % 5 == 0 && P > 3) ps[2] = ps[1];                                  // an empty partition
-        check(rows, ps, 256);
+        return ps;
+    };
+    for (int t = 0; t < 40; t++) {
+        const int n = 10000;
+        const std::vector<Row> rows = random_rows(t, n);
+        check(rows, random_cuts(t, n), 256, 256);
+        check(rows, random_cuts(t, n), 4, 4);                                    // per = 625
+        for (int m = 1; m <= 50; m++) {                                          // 1 .. 13 blocks of 4 on 4 threads: per = 1 .. 4
+            const std::vector<Row> head(rows.begin(), rows.begin() + m);
+            check(head, {0, m}, 4, 4);
+            if (m >= 8) check(head, {0, 5, 5, m - 2, m}, 4, 4);
+        }
+    }
+    for (int t = 0; t < 4; t++) for (int n : {65537, 131073}) {                  // 257 and 513 blocks on 256 threads: per = 2 and 3
+        const std::vector<Row> rows = random_rows(t, n);
+        check(rows, {0, n}, 256, 256);
+        check(rows, random_cuts(t, n), 256, 256);
     }
     std::printf("ok %ld comparisons\n", checked);
     return 0;
