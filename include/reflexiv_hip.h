@@ -33,7 +33,7 @@
  *        output arrays are unspecified, nothing at or past `cap` is written;
  *      - text buffers (rfx_contigs_text, rfx_dev_assemble[_w], rfx_assemble_counts_w,
  *        rfx_assemble_reads, the sharded drivers, rfx_dedup_contigs / rfx_dedup_contig_text,
- *        rfx_dev_contigs_to_text)
+ *        rfx_dev_contigs_to_text, rfx_dev_fix2_to_text, rfx_dev_fix2_ends_text)
  *        are filled up to `cap`: the bytes below it are unspecified (a prefix of the text),
  *        nothing at or past `cap` is written;
  *  - re-entrant per context; one context = one device + one HIP stream.
@@ -861,7 +861,8 @@ int rfx_reduce_text(rfx_ctx *ctx, const char *text_short, const int64_t *row_off
 typedef struct {
     int max_k;           /* the LAST k of the k list (param.maxKmerSize)                                      */
     int scramble;        /* param.scramble: 3 starts the loop's marker at 1, anything else at 2               */
-    int max_iteration;   /* param.maximumIteration: min(max_iteration + 1, 17) sort + loop rounds             */
+    int max_iteration;   /* param.maximumIteration: min(max_iteration + 1, 17) sort + loop rounds; the second   */
+                         /* stage (rfx_*fix2_*) caps them at 29                                               */
 } rfx_fix_params;
 void rfx_fix_default_params(rfx_fix_params *p, int max_k);   /* scramble 2, max_iteration 150 */
 int rfx_dev_fix_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, const rfx_fix_params *params,
@@ -876,6 +877,50 @@ int rfx_dev_fix_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, 
                     rfx_dyn_packed *d_out);
 int rfx_fix_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
                  int64_t *out_len);
+
+/* The SECOND contig fixing stage (Assembly_intermediate/05FixingAgain and 06ContigEnds) on the same packed sets in
+ * HBM: P/ReflexivDSDynamicKmerFixingRoundTwo.java `assemblyFromKmer` (:138-263).  Its input is the text of 04Fixing -- or the packed set
+ * rfx_dev_fix_run leaves, with no text in between.  It is the last stage ahead of the Mapping stage, which needs an external aligner.
+ *   rfx_dev_fix2_binarize     DynamicKmerBinarizerFromReducedToSubKmer (:562-752): rfx_dev_dyn_binarize form 1, NO length filter
+ *   rfx_dev_fix2_run          min(max_iteration + 1, 29) x (sort("k-1") with the caller's P, DSExtendFixingKmerLoop) (:203-213); every
+ *                             round sits behind a sort; max_iteration = -1 gives zero rounds, which copy the set.  The loop is the one
+ *                             of the first stage, i.e. rfx_dev_dyn_extend_pass with stage 1 and a start_iteration below 61, reused
+ *                             unchanged: every pass of every case of tests/golden/fixing2_vectors.npz agrees
+ *   rfx_dev_fix2_contigs      DSBinaryFixingKmerWithLongExtensionToString (:293-560) without the text: key || extension for marker 1,
+ *                             extension || key otherwise, the contigs of at least 2 max_k bases in input order as a packed contig set
+ *                             (rfx_contigs_packed, its invariant included: what rfx_dev_dedup_contigs and rfx_dev_contigs_unpack
+ *                             take); d_left / d_right (cap_n entries each) receive every kept contig's left / right
+ *   rfx_dev_fix2_to_text      zipWithIndex + TagStringContigRDDID (:987-1005): the rows of 05FixingAgain,
+ *                             "Contig_<L>_<left>_<right>_<idx>,<contig>\n", idx = the position in the set (the rank among the KEPT
+ *                             contigs), left / right in decimal as rfx_dev_dyn_to_text prints them
+ *   rfx_dev_fix2_ends_text    DSExtractContigEndsForAlignment (:265-291): the lines of 06ContigEnds; a contig of 400 bases or more gives
+ *                             ">ID-L\n" + bases [0, 200) + "\n" + ">ID-R\n" + bases [L - 200, L) + "\n", a shorter one ">ID\n" + the
+ *                             contig + "\n"; ID = "Contig_<L>_<left>_<right>_<idx>"
+ *   rfx_fix2_text             host text in, both host texts out: one upload, binarize, run, contigs, both texts, one copy back each
+ * DEVIATION, stated: the reference keeps the key in ONE long and would cut a longer key to it; here a row whose sub-k-mer is not 30
+ * bases long, or a row without an extension, is RFX_E_ARG for the set (binarize, run and rfx_fix2_text), as in the first stage.  A ')'
+ * behind the extension is dropped as rfx_dyn_binarize form 1 drops it.
+ * CONTRACTS.  binarize: cap_n >= n_rows and cap_words >= n_rows + text bytes / 32.  run: cap_n >= in.n and cap_words >=
+ * in.ext_off[in.n] (no pass needs more than its input).  contigs: the kept contigs need sum ceil((key_len + ext_len) / 32) words, and
+ * ceil((a + b) / 32) <= ceil(a / 32) + ceil(b / 32), so cap_n >= in.n and cap_words >= in.ext_off[in.n] + sum ceil(key_len / 32) always
+ * suffice: in.ext_off[in.n] + in.n for the 30-base keys of this stage, in.ext_off[in.n] + 4 in.n for any set (rfx_dev_fix2_contigs
+ * takes keys of any length up to 124 bases).  A short output: RFX_E_CAP with n and need_words (contigs: need_n and need_words) set and
+ * nothing written, d_left / d_right neither.  The two text writers follow the text-buffer rule: filled up to cap, nothing at or past it,
+ * RFX_E_CAP with *out_len = the need; d_text may have any alignment.  rfx_fix2_text with a short buffer: RFX_E_CAP with BOTH lengths
+ * set and NEITHER buffer written.  RFX_E_ARG, nothing written: max_k outside 31..124; max_iteration < -1; P outside 1..63; a key that
+ * is not 30 bases long or a record without an extension (binarize, run); a contig set whose word_off and len disagree (the text
+ * writers); a null pointer.  RFX_E_LIMIT: a sub-k-mer of more than 124 bases, 2^31 rows / records / contigs or more, a contig of 2^30
+ * bases or more.  n_rows = 0 and n = 0 are valid everywhere.  All run on the context's stream and return after it has drained. */
+int rfx_dev_fix2_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, rfx_dyn_packed *d_out);
+int rfx_dev_fix2_run(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int P, const rfx_fix_params *params, rfx_dyn_packed *d_out);
+int rfx_dev_fix2_contigs(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rfx_fix_params *params, rfx_contigs_packed *d_out, int32_t *d_left,
+                         int32_t *d_right);
+int rfx_dev_fix2_to_text(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, char *d_text, int64_t cap,
+                         int64_t *out_len);
+int rfx_dev_fix2_ends_text(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, char *d_text, int64_t cap,
+                           int64_t *out_len);
+int rfx_fix2_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
+                  int64_t *out_len, char *ends_out, int64_t ends_cap, int64_t *ends_len);
 
 /* Synthetic reads: integer-only counter-based generator, bit-identical to
  * oracle/reflexiv_oracle.c orc_synth_*.  Writes packed reads straight into HBM. */

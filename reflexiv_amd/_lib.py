@@ -107,6 +107,7 @@ SYMBOLS = [
     "rfx_dev_reduce_right_prepare", "rfx_dev_reduce_full_kmers", "rfx_dev_reduce_neutralize", "rfx_dev_reduce_run", "rfx_reduce_text",
     "rfx_fix_default_params", "rfx_dev_fix_binarize", "rfx_dev_fix_contig_ends", "rfx_dev_fix_kmer_set", "rfx_dev_fix_fork_filter",
     "rfx_dev_fix_reflect", "rfx_dev_fix_run", "rfx_fix_text",
+    "rfx_dev_fix2_binarize", "rfx_dev_fix2_run", "rfx_dev_fix2_contigs", "rfx_dev_fix2_to_text", "rfx_dev_fix2_ends_text", "rfx_fix2_text",
 ]
 
 # prototypes of the packed entry points (ctx, then as include/reflexiv_hip.h declares them)
@@ -146,6 +147,13 @@ _DYN_PACKED_ARGS = {
     "rfx_dev_fix_reflect": (_PK, _PK),
     "rfx_dev_fix_run": (_P, _P, _L, _I, _FP, _PK),
     "rfx_fix_text": (_P, _P, _L, _I, _FP, _P, _L, _P),
+    # the second contig fixing stage: packed sets in, a packed contig set and the two texts out
+    "rfx_dev_fix2_binarize": (_P, _P, _L, _PK),
+    "rfx_dev_fix2_run": (_PK, _I, _FP, _PK),
+    "rfx_dev_fix2_contigs": (_PK, _FP, _CP, _P, _P),
+    "rfx_dev_fix2_to_text": (_CP, _P, _P, _P, _L, _P),
+    "rfx_dev_fix2_ends_text": (_CP, _P, _P, _P, _L, _P),
+    "rfx_fix2_text": (_P, _P, _L, _I, _FP, _P, _L, _P, _P, _L, _P),
     # the packed contig set of the de-duplication (rfx_contigs_packed)
     "rfx_dev_contigs_pack": (_P, _P, _L, _CP),
     "rfx_dev_contigs_unpack": (_CP, _P, _L, _P, _L, _P),

@@ -1211,6 +1211,86 @@ class Reflexiv:
             self._check(st, "rfx_fix_text")
             return out[:ln.value].tobytes()
 
+    # ---- the second contig fixing stage (05FixingAgain, 06ContigEnds) on the same packed sets (rfx_dev_fix2_*)
+    def fix2_binarize(self, d_text, d_row_off, out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_fix2_binarize: the rows of 04Fixing (torch uint8 tensor in HBM + int64 row offsets, n_rows + 1) -> their records;
+        no length filter"""
+        n_rows = int(d_row_off.numel()) - 1
+        return self._dyn_dev_call(self.L.rfx_dev_fix2_binarize, "rfx_dev_fix2_binarize", out or DynPacked(n_rows, n_rows + int(d_text.numel()) // 32),
+                                  lambda co: (d_text.data_ptr(), d_row_off.data_ptr(), n_rows, C.byref(co)))
+
+    def fix2_run(self, d: "DynPacked", P: int, params, out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_fix2_run: min(max_iteration + 1, 29) x (sort, loop) on a packed set -- the output of fix_run feeds it as it is"""
+        ci = d._c()
+        return self._dyn_dev_call(self.L.rfx_dev_fix2_run, "rfx_dev_fix2_run", out or DynPacked(d.n, d.words),
+                                  lambda co: (C.byref(ci), int(P), C.byref(params), C.byref(co)))
+
+    def fix2_contigs(self, d: "DynPacked", params, out: "ContigsPacked" = None, d_left=None, d_right=None):
+        """rfx_dev_fix2_contigs -> (the contigs of at least 2 max_k bases as a ContigsPacked, left, right: torch int32 tensors in HBM,
+        cap_n entries each)"""
+        import torch
+        ci = d._c()
+        out = out or ContigsPacked(d.n, d.words + 4 * d.n, d.key.device)
+        while True:
+            if d_left is None or d_left.numel() < max(1, out.cap_n):
+                d_left = torch.empty(max(1, out.cap_n), dtype=torch.int32, device=d.key.device)
+            if d_right is None or d_right.numel() < max(1, out.cap_n):
+                d_right = torch.empty(max(1, out.cap_n), dtype=torch.int32, device=d.key.device)
+            co = out._c()
+            t0 = time.perf_counter()
+            st = self.L.rfx_dev_fix2_contigs(self.ctx, C.byref(ci), C.byref(params), C.byref(co), d_left.data_ptr(), d_right.data_ptr())
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
+            if st == RFX_E_CAP:
+                out = ContigsPacked(max(out.cap_n, int(co.need_n)), max(out.cap_words, int(co.need_words)), d.key.device)
+                continue
+            self._check(st, "rfx_dev_fix2_contigs")
+            out.n = int(co.n)
+            return out, d_left, d_right
+
+    def _fix2_text_dev(self, fn, name, c: "ContigsPacked", d_left, d_right, d_text):
+        import torch
+        ci = c._c()
+        ln = C.c_int64(0)
+        if d_text is None:
+            d_text = torch.empty(max(1, 96 * c.n + 32 * c.words + 64), dtype=torch.uint8, device=c.word_off.device)
+        while True:
+            t0 = time.perf_counter()
+            st = fn(self.ctx, C.byref(ci), d_left.data_ptr(), d_right.data_ptr(), d_text.data_ptr(), int(d_text.numel()), C.addressof(ln))
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
+            if st == RFX_E_CAP:
+                d_text = torch.empty(ln.value, dtype=torch.uint8, device=c.word_off.device)
+                continue
+            self._check(st, name)
+            return d_text, int(ln.value)
+
+    def fix2_to_text(self, c: "ContigsPacked", d_left, d_right, d_text=None):
+        """rfx_dev_fix2_to_text -> (torch uint8 tensor in HBM holding the rows "Contig_<L>_<left>_<right>_<idx>,<contig>\\n" of
+        05FixingAgain, its length)"""
+        return self._fix2_text_dev(self.L.rfx_dev_fix2_to_text, "rfx_dev_fix2_to_text", c, d_left, d_right, d_text)
+
+    def fix2_ends_text(self, c: "ContigsPacked", d_left, d_right, d_text=None):
+        """rfx_dev_fix2_ends_text -> (torch uint8 tensor in HBM holding the lines of 06ContigEnds, its length)"""
+        return self._fix2_text_dev(self.L.rfx_dev_fix2_ends_text, "rfx_dev_fix2_ends_text", c, d_left, d_right, d_text)
+
+    def fix2_text(self, text: bytes, P: int, params):
+        """rfx_fix2_text: the rows of 04Fixing (bytes, one `SUBKMER,m|l|r,EXTENSION` row per line) -> (the rows of 05FixingAgain, the
+        lines of 06ContigEnds), both as bytes"""
+        text = bytes(text)
+        off, n_rows = self._row_offsets(text)
+        cap1 = cap2 = len(text) + 64 * n_rows + 64
+        l1, l2 = C.c_int64(0), C.c_int64(0)
+        while True:
+            o1, o2 = np.empty(max(1, cap1), np.uint8), np.empty(max(1, cap2), np.uint8)
+            t0 = time.perf_counter()
+            st = self.L.rfx_fix2_text(self.ctx, text, off.ctypes.data, n_rows, int(P), C.byref(params), o1.ctypes.data, cap1, C.addressof(l1),
+                                      o2.ctypes.data, cap2, C.addressof(l2))
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
+            if st == RFX_E_CAP and (l1.value > cap1 or l2.value > cap2):
+                cap1, cap2 = max(cap1, l1.value), max(cap2, l2.value)
+                continue
+            self._check(st, "rfx_fix2_text")
+            return o1[:l1.value].tobytes(), o2[:l2.value].tobytes()
+
     # ------------------------------------------------ f-4: contig RC de-duplication
     def dedup_contigs(self, contigs, min_contig=500):
         """rfx_dedup_contigs (P/ReflexivDSDynamicKmerDedup.java :138-339) on a list of contig strings (ids = positions) ->

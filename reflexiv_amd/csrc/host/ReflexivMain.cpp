@@ -455,6 +455,33 @@ std::string ReflexivMain::contigFixing(const std::string &csvText, int partition
     return out;
 }
 
+void ReflexivMain::contigFixingRoundTwo(const std::string &csvText, int partitions, std::string *contigRows, std::string *contigEnds) {
+    std::string rows;
+    std::vector<int64_t> off;
+    rowsOf(csvText, rows, off);
+    const int64_t n = (int64_t)off.size() - 1;
+    for (int64_t i = 0; i < n; i++)
+        if (std::count(rows.begin() + off[(size_t)i], rows.begin() + off[(size_t)i + 1], ',') < 2)
+            throw std::runtime_error("fixing2 row: " + rows.substr((size_t)off[(size_t)i], (size_t)(off[(size_t)i + 1] - off[(size_t)i])));
+    rfx_fix_params prm;
+    rfx_fix_default_params(&prm, lastKmerOfList());
+    prm.scramble = param.scramble; prm.max_iteration = param.maximumIteration;
+    std::string o1(rows.size() + 64 * (size_t)n + 64, '\0'), o2(rows.size() + 64 * (size_t)n + 64, '\0');
+    int64_t l1 = 0, l2 = 0;
+    for (;;) {
+        const int st = rfx_fix2_text(ctx, rows.data(), off.data(), n, partitions, &prm, o1.data(), (int64_t)o1.size(), &l1, o2.data(), (int64_t)o2.size(), &l2);
+        if (st == RFX_E_CAP && (l1 > (int64_t)o1.size() || l2 > (int64_t)o2.size())) {
+            if (l1 > (int64_t)o1.size()) o1.assign((size_t)l1, '\0');
+            if (l2 > (int64_t)o2.size()) o2.assign((size_t)l2, '\0');
+            continue;
+        }
+        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_fix2_text: ") + rfx_last_error(ctx));
+        break;
+    }
+    o1.resize((size_t)l1); o2.resize((size_t)l2);
+    *contigRows = std::move(o1); *contigEnds = std::move(o2);
+}
+
 std::string ReflexivMain::dedupContigText(const std::string &contigText) {
     std::string out(contigText.size() + 4096, '\0');
     int64_t len = 0, nc = 0;

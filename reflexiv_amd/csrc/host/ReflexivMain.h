@@ -168,6 +168,10 @@ public:
     // "SUBKMER,marker|left|right,EXTENSION" of the last iteration's output -> the rows of Assembly_intermediate/04Fixing.  One call
     // (rfx_fix_text): everything between on the device.  maxKmerSize is the last k of the k list.
     std::string contigFixing(const std::string &csvText, int partitions);
+    // ReflexivDSDynamicKmerFixingRoundTwo.assemblyFromKmer (P/ReflexivDSDynamicKmerFixingRoundTwo.java:138-263) -- `fixing2`: the rows of
+    // 04Fixing -> the rows "ID,contig" of Assembly_intermediate/05FixingAgain and the FASTA of contig ends of 06ContigEnds.  One call
+    // (rfx_fix2_text): everything between on the device.  maxKmerSize is the last k of the k list.
+    void contigFixingRoundTwo(const std::string &csvText, int partitions, std::string *contigRows, std::string *contigEnds);
     int lastKmerOfList() const;                      // param.kmerListInt[length - 1]
 
     rfx_ctx *ctx = nullptr;

@@ -3,7 +3,8 @@
 // `reflexiv_host reduce -kmerc SHORT -kmerc2 LONG -kmer K1 -kmer2 K2 [-klist ...] -partition P -outfile O` (Count_<K1>_reduced and
 // Count_<K2>_sorted, or Count_<K2>_reduced when K2 is the last k of the list), `reflexiv_host reduce -kmerc DIR -klist ... -partition P
 // -outfile O` (DIR/Count_<k> of every k of the list: each through `sort`, then the pairs in the list's order),
-// `reflexiv_host fixing -kmerc ITERATION_OUT [-klist ...] -partition P -outfile O` (O/Assembly_intermediate/04Fixing)
+// `reflexiv_host fixing -kmerc ITERATION_OUT [-klist ...] -partition P -outfile O` (O/Assembly_intermediate/04Fixing),
+// `reflexiv_host fixing2 -kmerc O/Assembly_intermediate/04Fixing [-klist ...] -partition P -outfile O` (05FixingAgain and 06ContigEnds)
 // the two launcher sub-commands of bin/reflexiv:252-271 that reach the hot path
 // (M/Main.java:59-79, M/MainOfCounter.java:60-80), on one MI355X instead of spark-submit.
 #include <zlib.h>
@@ -36,7 +37,8 @@ int main(int argc, char **argv) {
                                    "       reflexiv_host sort -kmerc COUNTS -kmer K [-klist 23,31,41,53,67,81,95] -outfile DIR\n"
                                    "       reflexiv_host reduce -kmerc SHORT -kmerc2 LONG -kmer K1 -kmer2 K2 [-klist ...] -partition P -outfile DIR\n"
                                    "       reflexiv_host reduce -kmerc COUNTS_DIR -klist K1,K2,... -partition P -outfile DIR\n"
-                                   "       reflexiv_host fixing -kmerc ITERATION_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"; return 2; }
+                                   "       reflexiv_host fixing -kmerc ITERATION_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"
+                                   "       reflexiv_host fixing2 -kmerc FIXING_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"; return 2; }
         std::string cmd = argv[1];
         std::vector<std::string> args(argv + 2, argv + argc);
         reflexiv::DefaultParam param = reflexiv::importCommandLine(args);
@@ -52,6 +54,8 @@ int main(int argc, char **argv) {
                                      " is not supported (8 <= k1 < k2 <= 124)");
         if (cmd == "fixing" && (param.inputKmerPath.empty() || param.outputPath.empty()))
             throw std::runtime_error("fixing needs -kmerc ITERATION_OUT [-klist 23,31,...] -partition P [-maxiter M -scramble S] -outfile DIR");
+        if (cmd == "fixing2" && (param.inputKmerPath.empty() || param.outputPath.empty()))
+            throw std::runtime_error("fixing2 needs -kmerc FIXING_OUT [-klist 23,31,...] -partition P [-maxiter M -scramble S] -outfile DIR");
         if (param.outputPath.empty()) throw std::runtime_error("-outfile is required");
         if (param.inputFqPath.empty() && param.inputKmerPath.empty()) throw std::runtime_error("-fastq or -kmerc is required");
         auto read_all = [&](const std::string &paths) {
@@ -155,6 +159,22 @@ int main(int argc, char **argv) {
             out = m.contigFixing(read_all(param.inputKmerPath), P);
             dir += "/Assembly_intermediate"; mkdir(dir.c_str(), 0755);
             dir += "/04Fixing"; mkdir(dir.c_str(), 0755);
+        } else if (cmd == "fixing2") {
+            // the step behind it (Pipelines.java:840-1291): the rows of 04Fixing -> 05FixingAgain (rows "ID,contig") and 06ContigEnds (the
+            // FASTA of contig ends an aligner reads); maxKmerSize is the last k of the list
+            const int P = param.partitions > 0 ? param.partitions : param.logicalPartitions;
+            if (P < 1 || P > 63) throw std::runtime_error("fixing2: -partition must be 1..63");
+            if (m.lastKmerOfList() < 31 || m.lastKmerOfList() > 124) throw std::runtime_error("fixing2: the last k of -klist must be 31..124");
+            std::string contigRows, contigEnds;
+            m.contigFixingRoundTwo(read_all(param.inputKmerPath), P, &contigRows, &contigEnds);
+            dir += "/Assembly_intermediate"; mkdir(dir.c_str(), 0755);
+            for (int f = 0; f < 2; f++) {
+                const std::string d = dir + (f ? "/06ContigEnds" : "/05FixingAgain");
+                mkdir(d.c_str(), 0755);
+                std::ofstream(d + (f ? "/part-00000" : "/part-00000.csv"), std::ios::binary) << (f ? contigEnds : contigRows);
+                std::ofstream(d + "/_SUCCESS", std::ios::binary);
+            }
+            return 0;
         } else if (cmd == "counter") {
             // --resident at k = 33..100 (not 64 or 96): the same rows through the device count of the packed reads
             out = param.resident && param.kmerSize >= 33 && param.kmerSize % 32 != 0 ? m.counterResident(read_all(param.inputFqPath))

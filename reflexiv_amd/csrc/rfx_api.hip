@@ -1579,3 +1579,104 @@ int rfx_assemble_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_o
 } RFX_API_CATCH(ctx)
 
 }  // extern "C"
+
+// ---- the second contig fixing stage (rfx_fixing2.hip) -----------------------------------------------------------
+namespace {
+bool fx2_set_ok(const rfx_dyn_packed *p) { return p && p->key && p->key_len && p->ext && p->ext_off && p->ext_len && p->marker && p->left && p->right; }
+bool fx2_contigs_ok(const rfx_contigs_packed *p) { return p && p->words && p->word_off && p->len; }
+int fx2_params(rfx_ctx *ctx, const rfx_fix_params *p, int P) {
+    if (!p || P < 1 || P > 63) return RFX_E_ARG;
+    if (p->max_k < 31 || p->max_k > 124) { ctx->last_error = "contig fixing, round two: max_k must be 31..124"; return RFX_E_ARG; }
+    if (p->max_iteration < -1) { ctx->last_error = "contig fixing, round two: max_iteration below -1"; return RFX_E_ARG; }
+    return RFX_OK;
+}
+int fx2_text_call(rfx_ctx *ctx, int ends, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, char *d_text, int64_t cap,
+                  int64_t *out_len) {
+    if (!ctx || !fx2_contigs_ok(d_in) || d_in->n < 0 || (d_in->n > 0 && (!d_left || !d_right)) || !out_len || cap < 0 || (cap > 0 && !d_text)) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    const Fx2View v{d_in->n, d_in->words, d_in->word_off, d_in->len, d_left, d_right};
+    int64_t total = 0;
+    RFX_TRY(fx2_text(ctx, v, ends, d_text, cap, &total, nullptr));
+    *out_len = total;
+    return total > cap ? RFX_E_CAP : RFX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rfx_dev_fix2_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, rfx_dyn_packed *d_out) try {
+    if (!ctx || !fx2_set_ok(d_out) || n_rows < 0 || (n_rows > 0 && (!d_text || !d_row_off))) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a;
+    RFX_TRY(fx2_binarize(ctx, d_text, d_row_off, n_rows, a));
+    return dyn_store(ctx, a, d_out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_fix2_run(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int P, const rfx_fix_params *params, rfx_dyn_packed *d_out) try {
+    if (!ctx || !fx2_set_ok(d_in) || d_in->n < 0 || !fx2_set_ok(d_out)) return RFX_E_ARG;
+    RFX_TRY(fx2_params(ctx, params, P));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a, b;
+    RFX_TRY(dyn_borrow(ctx, d_in, a));
+    RFX_TRY(fx2_run(ctx, a, P, params->scramble, params->max_iteration, b));
+    return dyn_store(ctx, b, d_out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_fix2_contigs(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rfx_fix_params *params, rfx_contigs_packed *d_out, int32_t *d_left,
+                         int32_t *d_right) try {
+    if (!ctx || !fx2_set_ok(d_in) || d_in->n < 0 || !fx2_contigs_ok(d_out) || !d_left || !d_right) return RFX_E_ARG;
+    RFX_TRY(fx2_params(ctx, params, 1));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a;
+    Fx2Plan plan;
+    RFX_TRY(dyn_borrow(ctx, d_in, a));
+    RFX_TRY(fx2_contigs_plan(ctx, a, params->max_k, plan));
+    d_out->need_n = plan.m; d_out->need_words = plan.words;
+    if (plan.m > d_out->cap_n || plan.words > d_out->cap_words) return RFX_E_CAP;       // (nothing written)
+    RFX_TRY(fx2_contigs_fill(ctx, a, plan, d_out->words, d_out->word_off, d_out->len, d_left, d_right));
+    d_out->n = plan.m;
+    return sync_checked(ctx);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_fix2_to_text(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, char *d_text, int64_t cap,
+                         int64_t *out_len) try {
+    return fx2_text_call(ctx, 0, d_in, d_left, d_right, d_text, cap, out_len);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_fix2_ends_text(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, char *d_text, int64_t cap,
+                           int64_t *out_len) try {
+    return fx2_text_call(ctx, 1, d_in, d_left, d_right, d_text, cap, out_len);
+} RFX_API_CATCH(ctx)
+
+// host text in, both host texts out; everything between packed and in HBM: one upload, binarize, run, the contigs, both texts, one
+// copy back each.  A short buffer: RFX_E_CAP with BOTH lengths set and NEITHER buffer written
+int rfx_fix2_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
+                  int64_t *out_len, char *ends_out, int64_t ends_cap, int64_t *ends_len) try {
+    if (!ctx || n_rows < 0 || (n_rows > 0 && (!text || !row_off)) || !out_len || !ends_len || cap < 0 || (cap > 0 && !out) || ends_cap < 0 ||
+        (ends_cap > 0 && !ends_out))
+        return RFX_E_ARG;
+    RFX_TRY(fx2_params(ctx, params, P));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DevBuf d_text, d_off, d_rows, d_ends, w, woff, len, left, right;
+    DynDev a, b;
+    Fx2Plan plan;
+    int64_t t_rows = 0, t_ends = 0;
+    RFX_TRY(dyn_upload_text(ctx, text, row_off, n_rows, d_text, d_off));
+    RFX_TRY(fx2_binarize(ctx, (const char *)d_text.p, (const int64_t *)d_off.as<int64_t>(), n_rows, a));
+    RFX_TRY(fx2_run(ctx, a, P, params->scramble, params->max_iteration, b));
+    RFX_TRY(fx2_contigs_plan(ctx, b, params->max_k, plan));
+    const size_t m = (size_t)std::max<int64_t>(plan.m, 1);
+    RFX_HIP(w.alloc((size_t)std::max<int64_t>(plan.words, 1) * 8, ctx->stream)); RFX_HIP(woff.alloc((m + 1) * 8, ctx->stream));
+    RFX_HIP(len.alloc(m * 8, ctx->stream)); RFX_HIP(left.alloc(m * 4, ctx->stream)); RFX_HIP(right.alloc(m * 4, ctx->stream));
+    RFX_TRY(fx2_contigs_fill(ctx, b, plan, w.as<uint64_t>(), woff.as<int64_t>(), len.as<int64_t>(), left.as<int32_t>(), right.as<int32_t>()));
+    const Fx2View v{plan.m, w.as<uint64_t>(), woff.as<int64_t>(), len.as<int64_t>(), left.as<int32_t>(), right.as<int32_t>()};
+    RFX_TRY(fx2_text(ctx, v, 0, nullptr, 0, &t_rows, &d_rows));
+    RFX_TRY(fx2_text(ctx, v, 1, nullptr, 0, &t_ends, &d_ends));
+    *out_len = t_rows; *ends_len = t_ends;
+    if (t_rows > cap || t_ends > ends_cap) return RFX_E_CAP;         // (nothing written)
+    if (t_rows > 0) RFX_HIP(hipMemcpyAsync(out, d_rows.p, (size_t)t_rows, hipMemcpyDeviceToHost, ctx->stream));
+    if (t_ends > 0) RFX_HIP(hipMemcpyAsync(ends_out, d_ends.p, (size_t)t_ends, hipMemcpyDeviceToHost, ctx->stream));
+    return sync_checked(ctx);
+} RFX_API_CATCH(ctx)
+
+}  // extern "C"

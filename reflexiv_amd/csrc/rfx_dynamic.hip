@@ -63,7 +63,7 @@ int rfx::dyn_alloc(rfx_ctx *ctx, DynDev &d, int64_t n, int64_t words) {
 namespace {
 
 // ---- words ----------------------------------------------------------------------------------------------------------------
-// (dyn_keep, dyn_seg32, dyn_cat32 and dyn_find have twins in rfx_fixing.hip -- fx_keep, fx_seg32, fx_cat32, fx_find: the layout's
+// (dyn_keep, dyn_seg32, dyn_cat32 and dyn_find have twins in rfx_fix_words.h -- fx_keep, fx_seg32, fx_cat32, fx_find: the layout's
 // funnel shift and its zero padding.  The two copies must stay identical.)
 // the first m of 32 bases, the rest 0
 __device__ __forceinline__ uint64_t dyn_keep(uint64_t x, int m) { return m >= 32 ? x : m <= 0 ? 0ull : x & ~(~0ull >> (2 * m)); }

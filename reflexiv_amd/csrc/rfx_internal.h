@@ -492,4 +492,18 @@ int dyn_to_text(rfx_ctx *ctx, const DynDev &d, char *d_text, int64_t cap, int64_
 int ks_set_full_kmers(rfx_ctx *ctx, const DynDev &in, DynDev &out);
 int ks_set_to_text(rfx_ctx *ctx, const DynDev &d, int k, char *d_text, int64_t cap, int64_t *total, int64_t *d_row_off, int64_t *n_rows, DevBuf *own);
 
+// ---- rfx_fixing2.hip : the second contig fixing stage; its entry points are in rfx_api.hip
+// text rows -> a packed set (form 1, no length filter; keys of 30 bases and extensions of one base or more, RFX_E_ARG otherwise) /
+// min(max_iteration + 1, 29) x (sort, loop) on a set of such records, zero rounds copy it / the contigs of at least 2 max_k bases:
+// what they take (plan), then into arrays that hold it (fill) / the rows of 05FixingAgain (ends 0) or the lines of 06ContigEnds
+// (ends 1) of a packed contig set (own: a buffer of the library's)
+struct Fx2Plan { int64_t m = 0, words = 0; DevBuf keep, rank, woff; };
+struct Fx2View { int64_t n; const uint64_t *w; const int64_t *woff, *len; const int32_t *left, *right; };
+int fx2_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, DynDev &out);
+int fx2_run(rfx_ctx *ctx, const DynDev &in, int P, int scramble, int max_iteration, DynDev &out);
+int fx2_contigs_plan(rfx_ctx *ctx, const DynDev &in, int max_k, Fx2Plan &plan);
+int fx2_contigs_fill(rfx_ctx *ctx, const DynDev &in, const Fx2Plan &plan, uint64_t *d_words, int64_t *d_word_off, int64_t *d_len, int32_t *d_left,
+                     int32_t *d_right);
+int fx2_text(rfx_ctx *ctx, const Fx2View &v, int ends, char *d_text, int64_t cap, int64_t *total, DevBuf *own);
+
 }  // namespace rfx
