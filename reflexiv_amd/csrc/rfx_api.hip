@@ -1582,7 +1582,6 @@ int rfx_assemble_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_o
 
 // ---- the second contig fixing stage (rfx_fixing2.hip) -----------------------------------------------------------
 namespace {
-bool fx2_set_ok(const rfx_dyn_packed *p) { return p && p->key && p->key_len && p->ext && p->ext_off && p->ext_len && p->marker && p->left && p->right; }
 bool fx2_contigs_ok(const rfx_contigs_packed *p) { return p && p->words && p->word_off && p->len; }
 int fx2_params(rfx_ctx *ctx, const rfx_fix_params *p, int P) {
     if (!p || P < 1 || P > 63) return RFX_E_ARG;
@@ -1605,7 +1604,7 @@ int fx2_text_call(rfx_ctx *ctx, int ends, const rfx_contigs_packed *d_in, const 
 extern "C" {
 
 int rfx_dev_fix2_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, rfx_dyn_packed *d_out) try {
-    if (!ctx || !fx2_set_ok(d_out) || n_rows < 0 || (n_rows > 0 && (!d_text || !d_row_off))) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_out_ok(d_out) || n_rows < 0 || (n_rows > 0 && (!d_text || !d_row_off))) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a;
     RFX_TRY(fx2_binarize(ctx, d_text, d_row_off, n_rows, a));
@@ -1613,7 +1612,7 @@ int rfx_dev_fix2_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row
 } RFX_API_CATCH(ctx)
 
 int rfx_dev_fix2_run(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int P, const rfx_fix_params *params, rfx_dyn_packed *d_out) try {
-    if (!ctx || !fx2_set_ok(d_in) || d_in->n < 0 || !fx2_set_ok(d_out)) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_out_ok(d_in) || d_in->n < 0 || !dyn_packed_out_ok(d_out)) return RFX_E_ARG;
     RFX_TRY(fx2_params(ctx, params, P));
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a, b;
@@ -1624,7 +1623,7 @@ int rfx_dev_fix2_run(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int P, const rfx_
 
 int rfx_dev_fix2_contigs(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rfx_fix_params *params, rfx_contigs_packed *d_out, int32_t *d_left,
                          int32_t *d_right) try {
-    if (!ctx || !fx2_set_ok(d_in) || d_in->n < 0 || !fx2_contigs_ok(d_out) || !d_left || !d_right) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_out_ok(d_in) || d_in->n < 0 || !fx2_contigs_ok(d_out) || !d_left || !d_right) return RFX_E_ARG;
     RFX_TRY(fx2_params(ctx, params, 1));
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a;

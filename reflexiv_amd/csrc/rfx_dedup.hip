@@ -34,8 +34,6 @@ using namespace rfx;
 
 namespace {
 
-#define DD_GRID(n) dim3((unsigned)ceil_div(std::max<int64_t>((n), 1), 256)), dim3(256), 0, ctx->stream
-
 constexpr int M31 = 31;
 
 __host__ __device__ __forceinline__ int64_t dd_attr3(int marker, int64_t left, int64_t right) {     // :2908-2934
@@ -104,13 +102,6 @@ inline int64_t dd_probe_positions(int64_t L) {
     return t;
 }
 
-// the largest i < n with off[i] <= x (off[0] <= x): the contig / descriptor that owns word or thread x; entries of size 0 are skipped
-__device__ __forceinline__ int64_t dd_owner(const int64_t *__restrict__ off, int64_t n, int64_t x) {
-    int64_t lo = 0, hi = n;
-    while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (off[mid] <= x) lo = mid; else hi = mid; }
-    return lo;
-}
-
 // one thread per marker row, in the reference's emission order: contig after contig; inside a contig the seeds (block
 // starts, ascending), then window after window, position after position (forward probe, then its reverse complement, when
 // both strands are probed).  A marker is one 32-base window of the packed contig.
@@ -120,7 +111,7 @@ __global__ __launch_bounds__(256) void k_dd_markers(const uint64_t *__restrict__
                                                     uint64_t *__restrict__ key, uint32_t *__restrict__ val, int64_t *__restrict__ attr) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_markers) return;
-    const int64_t c = dd_owner(moff, n_contigs, t), L = clen[c];
+    const int64_t c = pk_find(moff, n_contigs, t), L = clen[c];
     const uint64_t *s = pool + cwoff[c];
     int64_t j = t - moff[c];
     const int64_t nb = (L - 1) / 31 + 1, nseed = (nb - 1) + (L % 31 == 0 ? 1 : 0);
@@ -367,7 +358,7 @@ __global__ __launch_bounds__(256) void k_dd_pack(const uint8_t *__restrict__ asc
                                                  const int64_t *__restrict__ clen, int64_t n, int64_t total, uint64_t *__restrict__ out) {
     const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= total) return;
-    const int64_t c = dd_owner(woff, n, w), j = w - woff[c];
+    const int64_t c = pk_find(woff, n, w), j = w - woff[c];
     const int64_t cnt = clen[c] - 32 * j;
     const uint8_t *s = ascii + boff[c] + 32 * j;
     uint64_t x = 0;
@@ -380,7 +371,7 @@ __global__ __launch_bounds__(256) void k_dd_unpack(const uint64_t *__restrict__ 
                                                    const int64_t *__restrict__ boff, int64_t n, int64_t total, uint8_t *__restrict__ out) {
     const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= total) return;
-    const int64_t c = dd_owner(woff, n, w), j = w - woff[c];
+    const int64_t c = pk_find(woff, n, w), j = w - woff[c];
     const int64_t cnt = clen[c] - 32 * j;
     const uint64_t x = words[w];
     uint8_t *d = out + boff[c] + 32 * j;
@@ -416,7 +407,7 @@ static int dd_pack_host(rfx_ctx *ctx, const uint8_t *bases, const int64_t *off, 
         RFX_HIP(stage.alloc((size_t)nb, ctx->stream)); RFX_HIP(boff.alloc((size_t)(n + 1) * 8, ctx->stream));
         RFX_HIP(hipMemcpyAsync(stage.p, bases + off[0], (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
         RFX_HIP(hipMemcpyAsync(boff.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_dd_pack, DD_GRID(d.words), (const uint8_t *)stage.as<uint8_t>(), (const int64_t *)boff.as<int64_t>(),
+        hipLaunchKernelGGL(k_dd_pack, RFX_GRID(d.words), (const uint8_t *)stage.as<uint8_t>(), (const int64_t *)boff.as<int64_t>(),
                            (const int64_t *)d.woff.as<int64_t>(), (const int64_t *)d.len.as<int64_t>(), n, d.words, d.w.as<uint64_t>());
         RFX_HIP(hipGetLastError());
         RFX_TRY(sync_checked(ctx));                               // (`rel` and the staging buffers are read until here)
@@ -433,7 +424,7 @@ static int dd_unpack_host(rfx_ctx *ctx, const DdSet &d, uint8_t *out_bases, int6
     DevBuf stage, d_boff;
     RFX_HIP(stage.alloc((size_t)nb, ctx->stream)); RFX_HIP(d_boff.alloc((size_t)(d.n + 1) * 8, ctx->stream));
     RFX_HIP(hipMemcpyAsync(d_boff.p, boff.data(), (size_t)(d.n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_dd_unpack, DD_GRID(d.words), (const uint64_t *)d.w.as<uint64_t>(), (const int64_t *)d.woff.as<int64_t>(),
+    hipLaunchKernelGGL(k_dd_unpack, RFX_GRID(d.words), (const uint64_t *)d.w.as<uint64_t>(), (const int64_t *)d.woff.as<int64_t>(),
                        (const int64_t *)d.len.as<int64_t>(), (const int64_t *)d_boff.as<int64_t>(), d.n, d.words, stage.as<uint8_t>());
     RFX_HIP(hipGetLastError());
     RFX_HIP(hipMemcpyAsync(out_bases, stage.p, (size_t)nb, hipMemcpyDeviceToHost, ctx->stream));
@@ -482,7 +473,7 @@ __global__ __launch_bounds__(256) void k_dd_text_fill(const char *__restrict__ t
                                                       uint64_t *__restrict__ out) {
     const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= total) return;
-    const int64_t c = dd_owner(woff, n, w), j = w - woff[c];
+    const int64_t c = pk_find(woff, n, w), j = w - woff[c];
     int64_t cnt = clen[c] - 32 * j;
     if (cnt > 32) cnt = 32;
     const uint64_t g = gb[hpos[c]] + (uint64_t)(32 * j);          // this word's first base, counted over the whole text
@@ -507,7 +498,7 @@ static int dd_from_text(rfx_ctx *ctx, const char *d_text, int64_t len, DdSet &d)
     if (len > 0) {
         DevBuf v;
         RFX_HIP(v.alloc((size_t)len * 8, ctx->stream)); RFX_HIP(pv.alloc((size_t)(len + 1) * 8, ctx->stream));
-        hipLaunchKernelGGL(k_dd_text_starts, DD_GRID(len), d_text, len, v.as<uint64_t>());
+        hipLaunchKernelGGL(k_dd_text_starts, RFX_GRID(len), d_text, len, v.as<uint64_t>());
         RFX_HIP(hipGetLastError());
         RFX_TRY(exclusive_scan_u64(ctx, v.as<uint64_t>(), pv.as<uint64_t>(), len));
         uint64_t tot = 0;
@@ -518,8 +509,8 @@ static int dd_from_text(rfx_ctx *ctx, const char *d_text, int64_t len, DdSet &d)
             DevBuf isb;
             RFX_HIP(hdrline.alloc((size_t)nl, ctx->stream)); RFX_HIP(hpos.alloc((size_t)n * 8, ctx->stream));
             RFX_HIP(isb.alloc((size_t)len * 4, ctx->stream)); RFX_HIP(gb.alloc((size_t)(len + 1) * 8, ctx->stream));
-            hipLaunchKernelGGL(k_dd_text_lines, DD_GRID(len), d_text, len, (const uint64_t *)pv.as<uint64_t>(), hdrline.as<uint8_t>(), hpos.as<int64_t>());
-            hipLaunchKernelGGL(k_dd_text_isbase, DD_GRID(len), d_text, len, (const uint64_t *)pv.as<uint64_t>(), (const uint8_t *)hdrline.as<uint8_t>(),
+            hipLaunchKernelGGL(k_dd_text_lines, RFX_GRID(len), d_text, len, (const uint64_t *)pv.as<uint64_t>(), hdrline.as<uint8_t>(), hpos.as<int64_t>());
+            hipLaunchKernelGGL(k_dd_text_isbase, RFX_GRID(len), d_text, len, (const uint64_t *)pv.as<uint64_t>(), (const uint8_t *)hdrline.as<uint8_t>(),
                                isb.as<uint32_t>());
             RFX_HIP(hipGetLastError());
             RFX_TRY(exclusive_scan_u32_to_u64(ctx, isb.as<uint32_t>(), gb.as<uint64_t>(), len));
@@ -535,7 +526,7 @@ static int dd_from_text(rfx_ctx *ctx, const char *d_text, int64_t len, DdSet &d)
     }
     DevBuf cw;
     RFX_HIP(cw.alloc((size_t)n * 8, ctx->stream));
-    hipLaunchKernelGGL(k_dd_text_sizes, DD_GRID(n), (const int64_t *)hpos.as<int64_t>(), n, (const uint64_t *)gb.as<uint64_t>(), len, d.len.as<int64_t>(),
+    hipLaunchKernelGGL(k_dd_text_sizes, RFX_GRID(n), (const int64_t *)hpos.as<int64_t>(), n, (const uint64_t *)gb.as<uint64_t>(), len, d.len.as<int64_t>(),
                        cw.as<uint64_t>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u64(ctx, cw.as<uint64_t>(), d.woff.as<uint64_t>(), n));
@@ -546,7 +537,7 @@ static int dd_from_text(rfx_ctx *ctx, const char *d_text, int64_t len, DdSet &d)
     d.words = d.h_woff[(size_t)n];
     RFX_HIP(d.w.alloc((size_t)std::max<int64_t>(d.words, 1) * 8, ctx->stream));
     if (d.words > 0) {
-        hipLaunchKernelGGL(k_dd_text_fill, DD_GRID(d.words), d_text, len, (const uint64_t *)gb.as<uint64_t>(), (const int64_t *)hpos.as<int64_t>(),
+        hipLaunchKernelGGL(k_dd_text_fill, RFX_GRID(d.words), d_text, len, (const uint64_t *)gb.as<uint64_t>(), (const int64_t *)hpos.as<int64_t>(),
                            (const int64_t *)d.len.as<int64_t>(), (const int64_t *)d.woff.as<int64_t>(), n, d.words, d.w.as<uint64_t>());
         RFX_HIP(hipGetLastError());
     }
@@ -593,7 +584,7 @@ __global__ __launch_bounds__(256) void k_dd_out_bases(const uint64_t *__restrict
                                                       char *__restrict__ out) {
     const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= total) return;
-    const int64_t c = dd_owner(woff, n, w), j = w - woff[c], L = clen[c];
+    const int64_t c = pk_find(woff, n, w), j = w - woff[c], L = clen[c];
     if (L < min_contig) return;
     const int64_t cnt = L - 32 * j, b0 = 32 * j;
     int64_t line = b0 / DD_LINE, next = (line + 1) * DD_LINE;     // (a word may straddle a line break)
@@ -616,7 +607,7 @@ static int dd_to_text(rfx_ctx *ctx, const DdSet &d, int64_t min_contig, char *d_
     if (n == 0) return RFX_OK;
     DevBuf sz, toff;
     RFX_HIP(sz.alloc((size_t)n * 8, ctx->stream)); RFX_HIP(toff.alloc((size_t)(n + 1) * 8, ctx->stream));
-    hipLaunchKernelGGL(k_dd_out_sizes, DD_GRID(n), (const int64_t *)d.len.as<int64_t>(), n, min_contig, sz.as<uint64_t>());
+    hipLaunchKernelGGL(k_dd_out_sizes, RFX_GRID(n), (const int64_t *)d.len.as<int64_t>(), n, min_contig, sz.as<uint64_t>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u64(ctx, sz.as<uint64_t>(), toff.as<uint64_t>(), n));
     uint64_t t = 0;
@@ -628,9 +619,9 @@ static int dd_to_text(rfx_ctx *ctx, const DdSet &d, int64_t min_contig, char *d_
     }
     const int64_t lim = std::min<int64_t>(*total, cap);
     if (lim > 0) {
-        hipLaunchKernelGGL(k_dd_out_heads, DD_GRID(n), (const int64_t *)d.len.as<int64_t>(), n, min_contig, (const uint64_t *)toff.as<uint64_t>(), lim, d_text);
+        hipLaunchKernelGGL(k_dd_out_heads, RFX_GRID(n), (const int64_t *)d.len.as<int64_t>(), n, min_contig, (const uint64_t *)toff.as<uint64_t>(), lim, d_text);
         if (d.words > 0)
-            hipLaunchKernelGGL(k_dd_out_bases, DD_GRID(d.words), (const uint64_t *)d.w.as<uint64_t>(), (const int64_t *)d.woff.as<int64_t>(),
+            hipLaunchKernelGGL(k_dd_out_bases, RFX_GRID(d.words), (const uint64_t *)d.w.as<uint64_t>(), (const int64_t *)d.woff.as<int64_t>(),
                                (const int64_t *)d.len.as<int64_t>(), n, d.words, min_contig, (const uint64_t *)toff.as<uint64_t>(), lim, d_text);
         RFX_HIP(hipGetLastError());
     }
@@ -714,15 +705,15 @@ static int dedup_run(rfx_ctx *ctx, const DdSet &in, DdSet &out, int64_t *round_n
             RFX_HIP(attr.alloc((size_t)M * 8, ctx->stream)); RFX_HIP(pair.alloc((size_t)M * 8, ctx->stream));
             RFX_HIP(pk.alloc((size_t)M * 8, ctx->stream)); RFX_HIP(ck.alloc((size_t)M * 8, ctx->stream));
             RFX_HIP(pcnt.alloc(16, ctx->stream));
-            hipLaunchKernelGGL(k_dd_markers, DD_GRID(M), pin, (const int64_t *)dm, (const int64_t *)(dm + nc), (const int64_t *)(dm + 2 * nc),
+            hipLaunchKernelGGL(k_dd_markers, RFX_GRID(M), pin, (const int64_t *)dm, (const int64_t *)(dm + nc), (const int64_t *)(dm + 2 * nc),
                                (const int64_t *)(dm + 3 * nc), nc, M, both, key.as<uint64_t>(), val.as<uint32_t>(), attr.as<int64_t>());
             RFX_HIP(hipGetLastError());
             RFX_TRY(sort_pairs(ctx, key.as<uint64_t>(), val.as<uint32_t>(), M, 64, tk.as<uint64_t>(), tv.as<uint32_t>()));
-            hipLaunchKernelGGL(k_dd_select, DD_GRID(M), (const uint64_t *)key.as<uint64_t>(), (const uint32_t *)val.as<uint32_t>(),
+            hipLaunchKernelGGL(k_dd_select, RFX_GRID(M), (const uint64_t *)key.as<uint64_t>(), (const uint32_t *)val.as<uint32_t>(),
                                (const int64_t *)attr.as<int64_t>(), M, pair.as<int64_t>());
             RFX_HIP(hipGetLastError());
             RFX_HIP(hipMemsetAsync(pcnt.p, 0, 16, ctx->stream));
-            hipLaunchKernelGGL(k_dd_compact_pairs, DD_GRID(M), (const int64_t *)pair.as<int64_t>(), M, pk.as<uint64_t>(), pcnt.as<unsigned long long>());
+            hipLaunchKernelGGL(k_dd_compact_pairs, RFX_GRID(M), (const int64_t *)pair.as<int64_t>(), M, pk.as<uint64_t>(), pcnt.as<unsigned long long>());
             RFX_HIP(hipGetLastError());
             unsigned long long np = 0;
             RFX_HIP(hipMemcpyAsync(&np, pcnt.p, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -730,7 +721,7 @@ static int dedup_run(rfx_ctx *ctx, const DdSet &in, DdSet &out, int64_t *round_n
             if (np > 1) {
                 RFX_TRY(sort_pairs(ctx, pk.as<uint64_t>(), val.as<uint32_t>(), (int64_t)np, 64, tk.as<uint64_t>(), tv.as<uint32_t>()));
                 RFX_HIP(hipMemsetAsync(pcnt.p, 0, 16, ctx->stream));
-                hipLaunchKernelGGL(k_dd_pair_runs, DD_GRID((int64_t)np), (const uint64_t *)pk.as<uint64_t>(), (int64_t)np, ck.as<uint64_t>(),
+                hipLaunchKernelGGL(k_dd_pair_runs, RFX_GRID((int64_t)np), (const uint64_t *)pk.as<uint64_t>(), (int64_t)np, ck.as<uint64_t>(),
                                    pcnt.as<unsigned long long>());
                 RFX_HIP(hipGetLastError());
                 unsigned long long ncand = 0;
@@ -825,7 +816,7 @@ static int dedup_run(rfx_ctx *ctx, const DdSet &in, DdSet &out, int64_t *round_n
             if (eb.empty() || pre == 0) return RFX_OK;
             RFX_HIP(d_eb.alloc(eb.size() * sizeof(EmitB), ctx->stream));
             RFX_HIP(hipMemcpyAsync(d_eb.p, eb.data(), eb.size() * sizeof(EmitB), hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(k_dd_emit, DD_GRID(pre), (const EmitB *)d_eb.as<EmitB>(), (int64_t)eb.size(), pre);
+            hipLaunchKernelGGL(k_dd_emit, RFX_GRID(pre), (const EmitB *)d_eb.as<EmitB>(), (int64_t)eb.size(), pre);
             RFX_HIP(hipGetLastError());
             RFX_TRY(sync_checked(ctx));                       // (`eb` is read by the queued copy until here)
             return RFX_OK;
@@ -857,9 +848,9 @@ static int dedup_run(rfx_ctx *ctx, const DdSet &in, DdSet &out, int64_t *round_n
             RFX_HIP(d_dval.alloc(dcap * 4, ctx->stream)); RFX_HIP(d_dvtmp.alloc(dcap * 4, ctx->stream));
             RFX_HIP(d_seg.alloc((size_t)(nm + 1) * 8, ctx->stream)); RFX_HIP(d_fd.alloc((size_t)nm * 4, ctx->stream));
             RFX_HIP(hipMemcpyAsync(d_mb.p, mb.data(), (size_t)nm * sizeof(MergeB), hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(k_dd_fill, DD_GRID(tslots), d_tkey.as<uint32_t>(), DD_EMPTY, tslots);
-            hipLaunchKernelGGL(k_dd_fill, DD_GRID(tslots), d_tpos.as<uint32_t>(), 0xFFFFFFFFu, tslots);
-            hipLaunchKernelGGL(k_dd_seed_insert_b, DD_GRID(sthreads), (const MergeB *)d_mb.as<MergeB>(), nm, sthreads, d_tkey.as<uint32_t>(), d_tpos.as<int32_t>());
+            hipLaunchKernelGGL(k_dd_fill, RFX_GRID(tslots), d_tkey.as<uint32_t>(), DD_EMPTY, tslots);
+            hipLaunchKernelGGL(k_dd_fill, RFX_GRID(tslots), d_tpos.as<uint32_t>(), 0xFFFFFFFFu, tslots);
+            hipLaunchKernelGGL(k_dd_seed_insert_b, RFX_GRID(sthreads), (const MergeB *)d_mb.as<MergeB>(), nm, sthreads, d_tkey.as<uint32_t>(), d_tpos.as<int32_t>());
             RFX_HIP(hipGetLastError());
             RFX_HIP(hipMemsetAsync(d_cnt.p, 0, 16, ctx->stream));
             int key_bits = 33;
@@ -867,7 +858,7 @@ static int dedup_run(rfx_ctx *ctx, const DdSet &in, DdSet &out, int64_t *round_n
             std::vector<int32_t> fd((size_t)nm, -1);
             // one query pass of the active merges + the vote on every active merge's (grown) list -> fd
             auto query_vote_b = [&]() -> int {
-                hipLaunchKernelGGL(k_dd_query_b, DD_GRID(qthreads), (const MergeB *)d_mb.as<MergeB>(), nm, qthreads, (const uint32_t *)d_tkey.as<uint32_t>(),
+                hipLaunchKernelGGL(k_dd_query_b, RFX_GRID(qthreads), (const MergeB *)d_mb.as<MergeB>(), nm, qthreads, (const uint32_t *)d_tkey.as<uint32_t>(),
                                    (const int32_t *)d_tpos.as<int32_t>(), d_dist.as<uint64_t>(), d_cnt.as<unsigned long long>());
                 RFX_HIP(hipGetLastError());
                 unsigned long long c = 0;
@@ -875,7 +866,7 @@ static int dedup_run(rfx_ctx *ctx, const DdSet &in, DdSet &out, int64_t *round_n
                 RFX_TRY(sync_checked(ctx));
                 // (a second pass appends to a SORTED prefix: the whole list is sorted again, as Collections.sort does)
                 RFX_TRY(sort_pairs(ctx, d_dist.as<uint64_t>(), d_dval.as<uint32_t>(), (int64_t)c, key_bits, d_dtmp.as<uint64_t>(), d_dvtmp.as<uint32_t>()));
-                hipLaunchKernelGGL(k_dd_seg_bounds, DD_GRID(nm + 1), (const uint64_t *)d_dist.as<uint64_t>(), (int64_t)c, nm, d_seg.as<int64_t>());
+                hipLaunchKernelGGL(k_dd_seg_bounds, RFX_GRID(nm + 1), (const uint64_t *)d_dist.as<uint64_t>(), (int64_t)c, nm, d_seg.as<int64_t>());
                 hipLaunchKernelGGL(k_dd_vote, dim3((unsigned)nm), dim3(64), 0, ctx->stream, (const uint64_t *)d_dist.as<uint64_t>(),
                                    (const int64_t *)d_seg.as<int64_t>(), (const MergeB *)d_mb.as<MergeB>(), (int64_t)0, 0, d_fd.as<int32_t>());
                 RFX_HIP(hipGetLastError());

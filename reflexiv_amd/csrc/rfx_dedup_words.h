@@ -4,16 +4,10 @@
 // program can compile it with the two words defined away (tests/dedup_words_main.cpp compares every helper with a byte model).
 #pragma once
 #include <stdint.h>
+#include "rfx_packed_words.h"     // pk_rev2.  Positions here are 64-bit (a contig is not bounded by 2^31 bases), so dd_keep / dd_seg32 stay
 
 // the first m of 32 bases, the rest 0
 __host__ __device__ inline uint64_t dd_keep(uint64_t x, int64_t m) { return m >= 32 ? x : m <= 0 ? 0ull : x & ~(~0ull >> (2 * m)); }
-
-// the 32 two-bit groups of a word in reverse order
-__host__ __device__ inline uint64_t dd_rev2(uint64_t x) {
-    x = ((x >> 2) & 0x3333333333333333ull) | ((x & 0x3333333333333333ull) << 2);
-    x = ((x >> 4) & 0x0F0F0F0F0F0F0F0Full) | ((x & 0x0F0F0F0F0F0F0F0Full) << 4);
-    return __builtin_bswap64(x);
-}
 
 // the 32 bases that start at base t of a contig of len bases (t < 0: the contig begins -t bases into the window); 0 where the
 // contig has no base -- the zero padding of the layout does the masking.  One or two word loads and two shifts.
@@ -30,7 +24,7 @@ __host__ __device__ inline uint64_t dd_seg32(const uint64_t *w, int64_t len, int
 // complemented, 0 past the end
 __host__ __device__ inline uint64_t dd_seg32_rc(const uint64_t *w, int64_t len, int64_t t) {
     if (len <= 0 || t >= len || t < 0) return 0ull;
-    return dd_keep(~dd_rev2(dd_seg32(w, len, len - 32 - t)), len - t);
+    return dd_keep(~pk_rev2(dd_seg32(w, len, len - 32 - t)), len - t);
 }
 __host__ __device__ inline uint64_t dd_strand32(const uint64_t *w, int64_t len, int rc, int64_t t) {
     return rc ? dd_seg32_rc(w, len, t) : dd_seg32(w, len, t);
@@ -50,7 +44,7 @@ __host__ __device__ inline uint64_t dd_cat32(const DdSeg &a, const DdSeg &b, int
 // the marker 31-mer at base p (p + 31 <= len): 31 bases above the 01 pair; and the 31-mer of its reverse complement
 // (binaryLongReverseComplementary :2877-2906)
 __host__ __device__ inline uint64_t dd_mer31(const uint64_t *w, int64_t len, int64_t p) { return (dd_seg32(w, len, p) & ~3ull) | 1ull; }
-__host__ __device__ inline uint64_t dd_mer31_rc(uint64_t m) { return (~dd_rev2(m) << 2) | 1ull; }
+__host__ __device__ inline uint64_t dd_mer31_rc(uint64_t m) { return (~pk_rev2(m) << 2) | 1ull; }
 
 // the 15-mer seed at base p (>= 0) of a strand of a contig of n bases.  Past the end the block's 01 terminator reads as one C,
 // then A's (what (int)(leftShiftOutFromArray(leftShiftArray(c, p), 15)[0] >>> 2*(32-15)) yields there): with zero padding

@@ -28,12 +28,13 @@
 #include <string>
 #include <vector>
 #include "rfx_internal.h"
+#include "rfx_packed_words.h"
 
 using namespace rfx;
 
 namespace {
 
-#define DYN_KW RFX_DYN_KEY_WORDS            /* key words per record */
+#define DYN_KW PK_KW                        /* key words per record */
 #define DYN_MAXB 4                          // 31-base blocks per key: keys up to 124 bases (the reference's k-mer list ends at 95)
 #define DYN_MAXK (31 * DYN_MAXB)
 
@@ -63,78 +64,30 @@ int rfx::dyn_alloc(rfx_ctx *ctx, DynDev &d, int64_t n, int64_t words) {
 namespace {
 
 // ---- words ----------------------------------------------------------------------------------------------------------------
-// (dyn_keep, dyn_seg32, dyn_cat32 and dyn_find have twins in rfx_fix_words.h -- fx_keep, fx_seg32, fx_cat32, fx_find: the layout's
-// funnel shift and its zero padding.  The two copies must stay identical.)
-// the first m of 32 bases, the rest 0
-__device__ __forceinline__ uint64_t dyn_keep(uint64_t x, int m) { return m >= 32 ? x : m <= 0 ? 0ull : x & ~(~0ull >> (2 * m)); }
-// the 32 bases that start at base t of one packed segment of len bases (t < 0: the segment begins -t bases into the window);
-// 0 where the segment has no base -- the zero padding of the layout does the masking
-__device__ __forceinline__ uint64_t dyn_seg32(const uint64_t *__restrict__ w, int len, int t) {
-    if (len <= 0 || t >= len || t <= -32) return 0ull;
-    if (t < 0) return w[0] >> (2 * -t);
-    const int wi = t >> 5, sh = (t & 31) * 2;
-    uint64_t r = w[wi] << sh;
-    if (sh && wi + 1 < ((len + 31) >> 5)) r |= w[wi + 1] >> (64 - sh);
-    return r;
-}
+// (pk_keep, pk_seg32, pk_find, the integer text and the flags of a call: rfx_packed_words.h, rfx_internal.h)
 // up to three packed segments, each a word pointer and a length in bases: key + ext, ext + key, P + L + S of a merge
 struct DynCat { const uint64_t *w0, *w1, *w2; int l0, l1, l2; };
 // the 32 bases that start at base t of the concatenation (0 past its end)
 __device__ __forceinline__ uint64_t dyn_cat32(const DynCat &c, int t) {
-    return dyn_seg32(c.w0, c.l0, t) | dyn_seg32(c.w1, c.l1, t - c.l0) | dyn_seg32(c.w2, c.l2, t - c.l0 - c.l1);
+    return pk_seg32(c.w0, c.l0, t) | pk_seg32(c.w1, c.l1, t - c.l0) | pk_seg32(c.w2, c.l2, t - c.l0 - c.l1);
 }
 // the first n (<= 124) bases of two keys are equal: whole words, then one masked word
 __device__ __forceinline__ bool dyn_prefix_equal(const uint64_t *__restrict__ a, const uint64_t *__restrict__ b, int n) {
     if (n > DYN_MAXK) n = DYN_MAXK;
     const int fw = n >> 5, r = n & 31;
     for (int j = 0; j < DYN_KW - 1; j++) if (j < fw && a[j] != b[j]) return false;
-    return r == 0 || dyn_keep(a[fw] ^ b[fw], r) == 0;
+    return r == 0 || pk_keep(a[fw] ^ b[fw], r) == 0;
 }
 __device__ __forceinline__ bool dyn_keys_equal(const uint64_t *__restrict__ key, const uint8_t *__restrict__ len, int64_t a, int64_t b) {
     const uint64_t *x = key + DYN_KW * a, *y = key + DYN_KW * b;
     return len[a] == len[b] && x[0] == y[0] && x[1] == y[1] && x[2] == y[2] && x[3] == y[3];
 }
-// the largest i < n with off[i] <= x (off[0] = 0 <= x): the record that owns word / byte x; records of size 0 are skipped
-template <class T>
-__device__ __forceinline__ int64_t dyn_find(const T *__restrict__ off, int64_t n, int64_t x) {
-    int64_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)off[mid] <= x) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// flags of a call, in HBM: [0] a key longer than 124 bases, [1] the shortest key, [2] the longest key, [3] a malformed input
-// (offsets that run backwards), [4..5] a 64-bit total put there by k_dyn_put_total: one small read-back for all of them
-struct DynFlags { uint32_t too_long, min_len, max_len, bad; uint64_t total; };
-static int dyn_flags_init(rfx_ctx *ctx, DevBuf &flags) {
-    RFX_HIP(flags.alloc(sizeof(DynFlags), ctx->stream));
-    RFX_HIP(hipMemsetAsync(flags.p, 0, sizeof(DynFlags), ctx->stream));
-    RFX_HIP(hipMemsetAsync((char *)flags.p + 4, 0xFF, 4, ctx->stream));
-    return RFX_OK;
-}
-__global__ void k_dyn_put_total(const uint64_t *__restrict__ src, uint32_t *__restrict__ flags) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) ((uint64_t *)flags)[2] = *src;
-}
-static int dyn_flags_read(rfx_ctx *ctx, const DevBuf &flags, const uint64_t *d_total, DynFlags *h) {
-    if (d_total) {
-        hipLaunchKernelGGL(k_dyn_put_total, dim3(1), dim3(1), 0, ctx->stream, d_total, flags.as<uint32_t>());
-        RFX_HIP(hipGetLastError());
-    }
-    return small_readback(ctx, h, flags.p, sizeof(DynFlags));
-}
-__device__ __forceinline__ void dyn_note_lengths(uint32_t *__restrict__ flags, bool live, int len) {
-    uint32_t lo = live ? (uint32_t)len : 0xFFFFFFFFu, hi = live ? (uint32_t)len : 0u;
-    for (int d = 32; d > 0; d >>= 1) {
-        lo = min(lo, (uint32_t)__shfl_xor((int)lo, d, 64));
-        hi = max(hi, (uint32_t)__shfl_xor((int)hi, d, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (lo != 0xFFFFFFFFu) atomicMin(flags + 1, lo);
-        atomicMax(flags + 2, hi);
-        if (hi > (uint32_t)DYN_MAXK) atomicOr(flags, 1u);
-    }
+// what is wrong with a call's input (CallFlags::bad): a key longer than 124 bases, offsets that run backwards
+enum { DYN_TOO_LONG = 1, DYN_BAD_OFFSETS = 2 };
+// the set's shortest / longest key into the flags; a key past DYN_MAXK is refused
+__device__ __forceinline__ void dyn_note_lengths(CallFlags *__restrict__ flags, bool live, int len) {
+    pk_note_lengths(&flags->min_len, &flags->max_len, live, len);
+    if (live && len > DYN_MAXK) atomicOr(&flags->bad, (uint32_t)DYN_TOO_LONG);
 }
 
 // block j of a key from its words: bases 31 j .. 31 j + 30 in bits 63..2, the 01 terminator behind the last base of the last
@@ -143,7 +96,7 @@ __device__ __forceinline__ uint64_t dyn_block(const uint64_t *__restrict__ w, in
     const int b0 = 31 * j;
     int m = len - b0;
     if (m > 31) m = 31;
-    uint64_t x = dyn_seg32(w, len, b0) & ~3ull;
+    uint64_t x = pk_seg32(w, len, b0) & ~3ull;
     if (b0 + 31 >= len) x |= 1ull << (2 * (31 - m));
     return x;
 }
@@ -151,7 +104,7 @@ __device__ __forceinline__ uint64_t dyn_block(const uint64_t *__restrict__ w, in
 // set's shortest and longest key.  blk == nullptr: the lengths only (the operators that do not sort)
 __global__ __launch_bounds__(256) void k_dyn_keys(const uint64_t *__restrict__ key, const uint8_t *__restrict__ key_len, int64_t n,
                                                   uint64_t *__restrict__ blk /* [DYN_MAXB][n] */, uint64_t *__restrict__ nblk,
-                                                  uint32_t *__restrict__ perm, uint32_t *__restrict__ flags) {
+                                                  uint32_t *__restrict__ perm, CallFlags *__restrict__ flags) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = i < n;
     const int len = live ? (int)key_len[i] : 0;
@@ -266,8 +219,6 @@ __global__ __launch_bounds__(128) void k_dyn_walk(const DynView v, int64_t n, co
     if (!WRITE) cnt[q0] = rank;
 }
 
-__device__ __forceinline__ int32_t dyn_clamp(int32_t v) { return v >= 30000 ? 30000 : v <= -30000 ? -30000 : v; }
-
 // emission e of partition p (pbase[p] = rank of the partition's first emission) goes out in orientation
 // m = start_marker toggled (e - pbase[p]) times
 __device__ __forceinline__ int dyn_orientation(int64_t e, const uint64_t *pbase, int P, int start_marker) {
@@ -340,7 +291,7 @@ __global__ __launch_bounds__(256) void k_dyn_sizes(const DynDesc *__restrict__ d
         lf = lf_r >= 0 ? lf_r : lf_f - Pn;
         rt = d.bubble - extra;
     }
-    o.left[e] = dyn_clamp(lf); o.right[e] = dyn_clamp(rt); o.marker[e] = m;
+    o.left[e] = pk_clamp(lf); o.right[e] = pk_clamp(rt); o.marker[e] = m;
     o.key_len[e] = (uint8_t)(kf >= kr ? kf : kr);               // the longer key's length is kept
     o.ext_len[e] = Pn + S; ew[e] = (uint32_t)((Pn + S + 31) >> 5);
 }
@@ -353,7 +304,7 @@ __global__ __launch_bounds__(256) void k_dyn_emit_key(const DynDesc *__restrict_
     const int j = (int)(t % DYN_KW);
     const DynDesc d = desc[e];
     const DynPlan p = dyn_plan(v, d, d.kind == 2 ? 0 : dyn_orientation(e, pbase, P, start_marker));
-    okey[t] = dyn_keep(dyn_cat32(p.c, p.kstart + 32 * j), p.klen - 32 * j);
+    okey[t] = pk_keep(dyn_cat32(p.c, p.kstart + 32 * j), p.klen - 32 * j);
 }
 // one thread per output extension word; its record through the scan of the word counts.  The grid covers the input's word
 // bound; the exact total is oeoff[ne]
@@ -361,11 +312,11 @@ __global__ __launch_bounds__(256) void k_dyn_emit_ext(const DynDesc *__restrict_
                                                       int P, int start_marker, const int64_t *__restrict__ oeoff, uint64_t *__restrict__ oext) {
     const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (ne <= 0 || w >= oeoff[ne]) return;
-    const int64_t e = dyn_find(oeoff, ne, w);
+    const int64_t e = pk_find(oeoff, ne, w);
     const int j = (int)(w - oeoff[e]);
     const DynDesc d = desc[e];
     const DynPlan p = dyn_plan(v, d, d.kind == 2 ? 0 : dyn_orientation(e, pbase, P, start_marker));
-    oext[w] = dyn_keep(dyn_cat32(p.c, p.estart + 32 * j), p.elen - 32 * j);
+    oext[w] = pk_keep(dyn_cat32(p.c, p.estart + 32 * j), p.elen - 32 * j);
 }
 
 // DSkmerRandomReflection.call (FirstFour:2518-2524): row q of partition p in orientation 2, 1, 2, ... by its rank
@@ -392,8 +343,6 @@ __global__ void k_dyn_pbase(const int64_t *__restrict__ ps, int P, const uint64_
     if (out_ps) out_ps[p] = (int64_t)v;
 }
 
-#define GRID(n) dim3((unsigned)ceil_div(std::max<int64_t>((n), 1), 256)), dim3(256), 0, ctx->stream
-
 // descriptors -> the output record set; no host wait: the output is bounded by the input (ne <= in.n emissions of a pass,
 // in.words extension words)
 static int dyn_emit(rfx_ctx *ctx, const DynDev &in, const DevBuf &desc, int64_t ne, const uint64_t *d_pbase, int P, int start_marker, DynDev &out) {
@@ -402,15 +351,15 @@ static int dyn_emit(rfx_ctx *ctx, const DynDev &in, const DevBuf &desc, int64_t 
     RFX_TRY(dyn_alloc(ctx, out, ne, in.words));
     const DynView v = dyn_view(in);
     if (ne > 0) {
-        hipLaunchKernelGGL(k_dyn_sizes, GRID(ne), (const DynDesc *)desc.as<DynDesc>(), ne, v, d_pbase, P, start_marker, dyn_out(out), ew.as<uint32_t>());
+        hipLaunchKernelGGL(k_dyn_sizes, RFX_GRID(ne), (const DynDesc *)desc.as<DynDesc>(), ne, v, d_pbase, P, start_marker, dyn_out(out), ew.as<uint32_t>());
         RFX_HIP(hipGetLastError());
     }
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, ew.as<uint32_t>(), out.ext_off.as<uint64_t>(), ne));
     if (ne > 0) {
-        hipLaunchKernelGGL(k_dyn_emit_key, GRID(ne * DYN_KW), (const DynDesc *)desc.as<DynDesc>(), ne, v, d_pbase, P, start_marker, out.key.as<uint64_t>());
+        hipLaunchKernelGGL(k_dyn_emit_key, RFX_GRID(ne * DYN_KW), (const DynDesc *)desc.as<DynDesc>(), ne, v, d_pbase, P, start_marker, out.key.as<uint64_t>());
         RFX_HIP(hipGetLastError());
         if (in.words > 0) {
-            hipLaunchKernelGGL(k_dyn_emit_ext, GRID(in.words), (const DynDesc *)desc.as<DynDesc>(), ne, v, d_pbase, P, start_marker,
+            hipLaunchKernelGGL(k_dyn_emit_ext, RFX_GRID(in.words), (const DynDesc *)desc.as<DynDesc>(), ne, v, d_pbase, P, start_marker,
                                (const int64_t *)out.ext_off.as<int64_t>(), out.ext.as<uint64_t>());
             RFX_HIP(hipGetLastError());
         }
@@ -423,13 +372,13 @@ static int dyn_check_lengths(rfx_ctx *ctx, const DynDev &in, uint32_t *lmin) {
     *lmin = 0;
     if (in.n == 0) return RFX_OK;
     DevBuf flags;
-    RFX_TRY(dyn_flags_init(ctx, flags));
-    hipLaunchKernelGGL(k_dyn_keys, GRID(in.n), (const uint64_t *)in.key.as<uint64_t>(), (const uint8_t *)in.key_len.as<uint8_t>(), in.n,
-                       (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, flags.as<uint32_t>());
+    RFX_TRY(call_flags_init(ctx, flags));
+    hipLaunchKernelGGL(k_dyn_keys, RFX_GRID(in.n), (const uint64_t *)in.key.as<uint64_t>(), (const uint8_t *)in.key_len.as<uint8_t>(), in.n,
+                       (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, flags.as<CallFlags>());
     RFX_HIP(hipGetLastError());
-    DynFlags h{};
-    RFX_TRY(dyn_flags_read(ctx, flags, nullptr, &h));
-    if (h.too_long) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
+    CallFlags h{};
+    RFX_TRY(call_flags_read(ctx, flags, nullptr, nullptr, nullptr, &h));
+    if (h.bad & DYN_TOO_LONG) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
     *lmin = h.min_len;
     return RFX_OK;
 }
@@ -451,13 +400,13 @@ int rfx::dyn_sort(rfx_ctx *ctx, const DynDev &in, int P, DynDev &out, DevBuf &d_
     RFX_HIP(blk.alloc((size_t)DYN_MAXB * n * 8, ctx->stream)); RFX_HIP(nblk.alloc((size_t)n * 8, ctx->stream));
     RFX_HIP(perm.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(tk.alloc((size_t)n * 8, ctx->stream)); RFX_HIP(tv.alloc((size_t)n * 4, ctx->stream));
     RFX_HIP(keys.alloc((size_t)n * 8, ctx->stream));
-    RFX_TRY(dyn_flags_init(ctx, flags));
-    hipLaunchKernelGGL(k_dyn_keys, GRID(n), (const uint64_t *)in.key.as<uint64_t>(), (const uint8_t *)in.key_len.as<uint8_t>(), n, blk.as<uint64_t>(),
-                       nblk.as<uint64_t>(), perm.as<uint32_t>(), flags.as<uint32_t>());
+    RFX_TRY(call_flags_init(ctx, flags));
+    hipLaunchKernelGGL(k_dyn_keys, RFX_GRID(n), (const uint64_t *)in.key.as<uint64_t>(), (const uint8_t *)in.key_len.as<uint8_t>(), n, blk.as<uint64_t>(),
+                       nblk.as<uint64_t>(), perm.as<uint32_t>(), flags.as<CallFlags>());
     RFX_HIP(hipGetLastError());
-    DynFlags h{};
-    RFX_TRY(dyn_flags_read(ctx, flags, nullptr, &h));
-    if (h.too_long) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
+    CallFlags h{};
+    RFX_TRY(call_flags_read(ctx, flags, nullptr, nullptr, nullptr, &h));
+    if (h.bad & DYN_TOO_LONG) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
     *lmin = h.min_len;
     // LSD: the block count (a proper prefix first when every shared block is equal), then the blocks, last to first.  A block
     // no key of the set reaches is 0 for every record and a stable sort on it is the identity: skipped
@@ -465,13 +414,13 @@ int rfx::dyn_sort(rfx_ctx *ctx, const DynDev &in, int P, DynDev &out, DevBuf &d_
     for (int pass = -1; pass < nb_max; pass++) {
         const uint64_t *src = pass < 0 ? nblk.as<uint64_t>() : blk.as<uint64_t>() + (int64_t)(nb_max - 1 - pass) * n;
         if (pass < 0 && nb_max == 1) continue;                    // (every key has one block)
-        hipLaunchKernelGGL(k_dyn_gather_u64, GRID(n), src, (const uint32_t *)perm.as<uint32_t>(), n, keys.as<uint64_t>());
+        hipLaunchKernelGGL(k_dyn_gather_u64, RFX_GRID(n), src, (const uint32_t *)perm.as<uint32_t>(), n, keys.as<uint64_t>());
         RFX_HIP(hipGetLastError());
         RFX_TRY(sort_pairs(ctx, keys.as<uint64_t>(), perm.as<uint32_t>(), n, pass < 0 ? 8 : 64, tk.as<uint64_t>(), tv.as<uint32_t>()));
     }
     // gather the records through the permutation: the emission with "copy" descriptors
     RFX_HIP(desc.alloc((size_t)n * sizeof(DynDesc), ctx->stream));
-    hipLaunchKernelGGL(k_dyn_perm_desc, GRID(n), (const uint32_t *)perm.as<uint32_t>(), n, desc.as<DynDesc>());
+    hipLaunchKernelGGL(k_dyn_perm_desc, RFX_GRID(n), (const uint32_t *)perm.as<uint32_t>(), n, desc.as<DynDesc>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(dyn_emit(ctx, in, desc, n, nullptr, P, 0, out));
     hipLaunchKernelGGL(k_dyn_part_starts, dim3(1), dim3(1), 0, ctx->stream, (const uint64_t *)out.key.as<uint64_t>(),
@@ -494,7 +443,7 @@ int rfx::dyn_pass(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, ui
     RFX_HIP(head.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(cnt.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(base.alloc((size_t)(n + 1) * 8, ctx->stream));
     RFX_HIP(desc.alloc((size_t)n * sizeof(DynDesc), ctx->stream));
     const DynView v = dyn_view(in);
-    hipLaunchKernelGGL(k_dyn_heads, GRID(n), v.key, n, d_ps, P, lmin, head.as<uint32_t>());
+    hipLaunchKernelGGL(k_dyn_heads, RFX_GRID(n), v.key, n, d_ps, P, lmin, head.as<uint32_t>());
     RFX_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_dyn_walk<false>, dim3((unsigned)ceil_div(n, 128)), dim3(128), 0, ctx->stream, v, n, (const uint32_t *)head.as<uint32_t>(), stage,
                        start_iteration, cnt.as<uint32_t>(), (const uint64_t *)nullptr, (DynDesc *)nullptr);
@@ -515,7 +464,7 @@ static int dyn_reflect(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int 
     DevBuf desc, pbase;
     RFX_HIP(desc.alloc((size_t)std::max<int64_t>(in.n, 1) * sizeof(DynDesc), ctx->stream));
     RFX_HIP(pbase.alloc((size_t)(P + 1) * 8, ctx->stream));
-    hipLaunchKernelGGL(k_dyn_identity_desc, GRID(in.n), in.n, desc.as<DynDesc>());
+    hipLaunchKernelGGL(k_dyn_identity_desc, RFX_GRID(in.n), in.n, desc.as<DynDesc>());
     hipLaunchKernelGGL(k_dyn_copy_u64, dim3(1), dim3(64), 0, ctx->stream, d_ps, P + 1, pbase.as<uint64_t>());
     RFX_HIP(hipGetLastError());
     return dyn_emit(ctx, in, desc, in.n, pbase.as<uint64_t>(), P, 2, out);
@@ -525,11 +474,11 @@ static int dyn_reflect(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int 
 // sizes: key_len / ext_len / extension words of every record from the host form's offsets
 __global__ __launch_bounds__(256) void k_dyn_pack_sizes(const int64_t *__restrict__ koff, const int64_t *__restrict__ eoff, int64_t n,
                                                         uint8_t *__restrict__ key_len, int32_t *__restrict__ ext_len, uint32_t *__restrict__ ew,
-                                                        uint32_t *__restrict__ flags) {
+                                                        CallFlags *__restrict__ flags) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = i < n;
     int64_t kl = live ? koff[i + 1] - koff[i] : 0, el = live ? eoff[i + 1] - eoff[i] : 0;
-    if (live && (kl < 0 || el < 0 || el > 0x7FFFFFE0ll)) { atomicOr(flags + 3, 1u); kl = kl < 0 ? 0 : kl; el = 0; }
+    if (live && (kl < 0 || el < 0 || el > 0x7FFFFFE0ll)) { atomicOr(&flags->bad, (uint32_t)DYN_BAD_OFFSETS); kl = kl < 0 ? 0 : kl; el = 0; }
     dyn_note_lengths(flags, live, (int)(kl > 255 ? 255 : kl));
     if (!live) return;
     key_len[i] = (uint8_t)(kl > 255 ? 255 : kl);
@@ -555,7 +504,7 @@ __global__ __launch_bounds__(256) void k_dyn_pack_ext(const uint8_t *__restrict_
                                                       int64_t n, const int64_t *__restrict__ oeoff, uint64_t *__restrict__ oext) {
     const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (n <= 0 || w >= oeoff[n]) return;
-    const int64_t i = dyn_find(oeoff, n, w);
+    const int64_t i = pk_find(oeoff, n, w);
     const int j = (int)(w - oeoff[i]);
     oext[w] = dyn_pack32(ext + eoff[i] + 32 * (int64_t)j, ext_len[i] - 32 * j);
 }
@@ -575,7 +524,7 @@ static int dyn_pack_host(rfx_ctx *ctx, const rfx_dyn_records *h, DynDev &d) {
     RFX_HIP(kb.alloc((size_t)std::max<int64_t>(nk, 1), ctx->stream)); RFX_HIP(eb.alloc((size_t)std::max<int64_t>(ne, 1), ctx->stream));
     RFX_HIP(ko.alloc((size_t)(n + 1) * 8, ctx->stream)); RFX_HIP(eo.alloc((size_t)(n + 1) * 8, ctx->stream));
     RFX_HIP(ew.alloc((size_t)n * 4, ctx->stream));
-    RFX_TRY(dyn_flags_init(ctx, flags));
+    RFX_TRY(call_flags_init(ctx, flags));
     if (nk) RFX_HIP(hipMemcpyAsync(kb.p, h->key, (size_t)nk, hipMemcpyHostToDevice, ctx->stream));
     if (ne) RFX_HIP(hipMemcpyAsync(eb.p, h->ext, (size_t)ne, hipMemcpyHostToDevice, ctx->stream));
     RFX_HIP(hipMemcpyAsync(ko.p, h->key_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -583,19 +532,19 @@ static int dyn_pack_host(rfx_ctx *ctx, const rfx_dyn_records *h, DynDev &d) {
     RFX_HIP(hipMemcpyAsync(d.marker.p, h->marker, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     RFX_HIP(hipMemcpyAsync(d.left.p, h->left, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     RFX_HIP(hipMemcpyAsync(d.right.p, h->right, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_dyn_pack_sizes, GRID(n), (const int64_t *)ko.as<int64_t>(), (const int64_t *)eo.as<int64_t>(), n, d.key_len.as<uint8_t>(),
-                       d.ext_len.as<int32_t>(), ew.as<uint32_t>(), flags.as<uint32_t>());
+    hipLaunchKernelGGL(k_dyn_pack_sizes, RFX_GRID(n), (const int64_t *)ko.as<int64_t>(), (const int64_t *)eo.as<int64_t>(), n, d.key_len.as<uint8_t>(),
+                       d.ext_len.as<int32_t>(), ew.as<uint32_t>(), flags.as<CallFlags>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, ew.as<uint32_t>(), d.ext_off.as<uint64_t>(), n));
-    DynFlags f{};
-    RFX_TRY(dyn_flags_read(ctx, flags, nullptr, &f));
-    if (f.bad) { ctx->last_error = "dynamic-k: record offsets that run backwards"; return RFX_E_ARG; }
-    if (f.too_long) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
-    hipLaunchKernelGGL(k_dyn_pack_key, GRID(n * DYN_KW), (const uint8_t *)kb.as<uint8_t>(), (const int64_t *)ko.as<int64_t>(),
+    CallFlags f{};
+    RFX_TRY(call_flags_read(ctx, flags, nullptr, nullptr, nullptr, &f));
+    if (f.bad & DYN_BAD_OFFSETS) { ctx->last_error = "dynamic-k: record offsets that run backwards"; return RFX_E_ARG; }
+    if (f.bad & DYN_TOO_LONG) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
+    hipLaunchKernelGGL(k_dyn_pack_key, RFX_GRID(n * DYN_KW), (const uint8_t *)kb.as<uint8_t>(), (const int64_t *)ko.as<int64_t>(),
                        (const uint8_t *)d.key_len.as<uint8_t>(), n, d.key.as<uint64_t>());
     RFX_HIP(hipGetLastError());
     if (d.words > 0) {
-        hipLaunchKernelGGL(k_dyn_pack_ext, GRID(d.words), (const uint8_t *)eb.as<uint8_t>(), (const int64_t *)eo.as<int64_t>(),
+        hipLaunchKernelGGL(k_dyn_pack_ext, RFX_GRID(d.words), (const uint8_t *)eb.as<uint8_t>(), (const int64_t *)eo.as<int64_t>(),
                            (const int32_t *)d.ext_len.as<int32_t>(), n, (const int64_t *)d.ext_off.as<int64_t>(), d.ext.as<uint64_t>());
         RFX_HIP(hipGetLastError());
     }
@@ -614,7 +563,7 @@ __global__ __launch_bounds__(256) void k_dyn_unpack_bases(const uint64_t *__rest
                                                           int64_t n, int64_t total, uint8_t *__restrict__ out) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= total) return;
-    const int64_t i = dyn_find(boff, n, b);
+    const int64_t i = pk_find(boff, n, b);
     const int64_t t = b - (int64_t)boff[i];
     const uint64_t *w = words + (word_off ? word_off[i] : DYN_KW * i);
     out[b] = (uint8_t)((w[t >> 5] >> (62 - 2 * (int)(t & 31))) & 3);
@@ -627,7 +576,7 @@ static int dyn_unpack_host(rfx_ctx *ctx, const DynDev &d, rfx_dyn_records *h) {
     RFX_HIP(ks.alloc((size_t)std::max<int64_t>(n, 1) * 4, ctx->stream)); RFX_HIP(es.alloc((size_t)std::max<int64_t>(n, 1) * 4, ctx->stream));
     RFX_HIP(kso.alloc((size_t)(n + 1) * 8, ctx->stream)); RFX_HIP(eso.alloc((size_t)(n + 1) * 8, ctx->stream));
     if (n > 0) {
-        hipLaunchKernelGGL(k_dyn_unpack_sizes, GRID(n), (const uint8_t *)d.key_len.as<uint8_t>(), (const int32_t *)d.ext_len.as<int32_t>(), n,
+        hipLaunchKernelGGL(k_dyn_unpack_sizes, RFX_GRID(n), (const uint8_t *)d.key_len.as<uint8_t>(), (const int32_t *)d.ext_len.as<int32_t>(), n,
                            ks.as<uint32_t>(), es.as<uint32_t>());
         RFX_HIP(hipGetLastError());
     }
@@ -641,13 +590,13 @@ static int dyn_unpack_host(rfx_ctx *ctx, const DynDev &d, rfx_dyn_records *h) {
     if (n > h->cap_n || nk > h->cap_key || ne > h->cap_ext) return RFX_E_CAP;
     RFX_HIP(kb.alloc((size_t)std::max<int64_t>(nk, 1), ctx->stream)); RFX_HIP(eb.alloc((size_t)std::max<int64_t>(ne, 1), ctx->stream));
     if (nk) {
-        hipLaunchKernelGGL(k_dyn_unpack_bases, GRID(nk), (const uint64_t *)d.key.as<uint64_t>(), (const int64_t *)nullptr, (const uint64_t *)kso.as<uint64_t>(),
+        hipLaunchKernelGGL(k_dyn_unpack_bases, RFX_GRID(nk), (const uint64_t *)d.key.as<uint64_t>(), (const int64_t *)nullptr, (const uint64_t *)kso.as<uint64_t>(),
                            n, nk, kb.as<uint8_t>());
         RFX_HIP(hipGetLastError());
         RFX_HIP(hipMemcpyAsync(h->key, kb.p, (size_t)nk, hipMemcpyDeviceToHost, ctx->stream));
     }
     if (ne) {
-        hipLaunchKernelGGL(k_dyn_unpack_bases, GRID(ne), (const uint64_t *)d.ext.as<uint64_t>(), (const int64_t *)d.ext_off.as<int64_t>(),
+        hipLaunchKernelGGL(k_dyn_unpack_bases, RFX_GRID(ne), (const uint64_t *)d.ext.as<uint64_t>(), (const int64_t *)d.ext_off.as<int64_t>(),
                            (const uint64_t *)eso.as<uint64_t>(), n, ne, eb.as<uint8_t>());
         RFX_HIP(hipGetLastError());
         RFX_HIP(hipMemcpyAsync(h->ext, eb.p, (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
@@ -662,12 +611,45 @@ static int dyn_unpack_host(rfx_ctx *ctx, const DynDev &d, rfx_dyn_records *h) {
     return sync_checked(ctx);
 }
 
-// ---- the caller's packed arrays (rfx_dyn_packed, device pointers) <-> DynDev ---------------------------------------------------
-static bool dyn_packed_out_ok(const rfx_dyn_packed *p) {           // an output: its arrays (n is the callee's to set)
+}  // namespace
+// ---- what every stage on packed sets shares (rfx_internal.h): the host checks, the empty set, the flags of a call ------------------
+bool rfx::dyn_packed_out_ok(const rfx_dyn_packed *p) {
     return p && p->key && p->key_len && p->ext && p->ext_off && p->ext_len && p->marker && p->left && p->right;
 }
-static bool dyn_packed_ok(const rfx_dyn_packed *p) { return dyn_packed_out_ok(p) && p->n >= 0; }
+bool rfx::dyn_packed_ok(const rfx_dyn_packed *p) { return dyn_packed_out_ok(p) && p->n >= 0; }
+bool rfx::text_rows_ok(const char *text, const int64_t *row_off, int64_t n) { return n >= 0 && (n == 0 || (text && row_off)); }
+int rfx::dyn_empty(rfx_ctx *ctx, DynDev &d) {
+    RFX_TRY(dyn_alloc(ctx, d, 0, 0));
+    RFX_HIP(hipMemsetAsync(d.ext_off.p, 0, 8, ctx->stream));
+    return RFX_OK;
+}
+int rfx::check_part_starts(rfx_ctx *ctx, const int64_t *d_ps, int P, int64_t n, const char *stage_name) {
+    int64_t h[65];
+    RFX_TRY(small_readback(ctx, h, d_ps, (size_t)(P + 1) * 8));
+    bool ok = h[0] == 0 && h[P] == n;
+    for (int p = 0; p < P && ok; p++) ok = h[p] <= h[p + 1];
+    if (!ok) { ctx->last_error = std::string(stage_name) + ": partition starts that do not run from 0 to n"; return RFX_E_ARG; }
+    return RFX_OK;
+}
+int rfx::call_flags_init(rfx_ctx *ctx, DevBuf &flags) {
+    RFX_HIP(flags.alloc(sizeof(CallFlags), ctx->stream));
+    RFX_HIP(hipMemsetAsync(flags.p, 0, sizeof(CallFlags), ctx->stream));
+    RFX_HIP(hipMemsetAsync(&flags.as<CallFlags>()->min_len, 0xFF, 4, ctx->stream));
+    return RFX_OK;
+}
+namespace {
+__global__ void k_put_totals(const uint64_t *__restrict__ a, const uint64_t *__restrict__ b, const uint64_t *__restrict__ c, CallFlags *__restrict__ flags) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) { flags->total[0] = a ? *a : 0ull; flags->total[1] = b ? *b : 0ull; flags->total[2] = c ? *c : 0ull; }
+}
 }  // namespace
+int rfx::call_flags_read(rfx_ctx *ctx, const DevBuf &flags, const uint64_t *d_t0, const uint64_t *d_t1, const uint64_t *d_t2, CallFlags *h) {
+    if (d_t0 || d_t1 || d_t2) {
+        hipLaunchKernelGGL(k_put_totals, dim3(1), dim3(1), 0, ctx->stream, d_t0, d_t1, d_t2, flags.as<CallFlags>());
+        RFX_HIP(hipGetLastError());
+    }
+    return small_readback(ctx, h, flags.p, sizeof(CallFlags));
+}
+// ---- the caller's packed arrays (rfx_dyn_packed, device pointers) <-> DynDev ---------------------------------------------------
 // a view of the caller's input set: nothing is copied, nothing is freed
 int rfx::dyn_borrow(rfx_ctx *ctx, const rfx_dyn_packed *p, DynDev &d) {
     auto b = [&](DevBuf &x, void *q) { x.release(); x.p = q; x.s = ctx->stream; x.borrowed = true; };
@@ -722,34 +704,26 @@ __device__ __forceinline__ DynRowCut dyn_row_cut(const char *__restrict__ t, int
     if (c.f2e > c.f2 && t[c.f2e - 1] == ')') c.f2e--;
     return c;
 }
-__device__ __forceinline__ int dyn_parse_int(const char *__restrict__ t, int64_t &i, int64_t e) {
-    bool neg = false;
-    if (i < e && (t[i] == '-' || t[i] == '+')) { neg = t[i] == '-'; i++; }
-    long long v = 0;
-    while (i < e && t[i] >= '0' && t[i] <= '9') { if (v < 100000000LL) v = v * 10 + (t[i] - '0'); i++; }
-    if (i < e && t[i] == '|') i++;
-    return (int)(neg ? -v : v);
-}
 __global__ __launch_bounds__(256) void k_dyn_bin_sizes(const char *__restrict__ text, const int64_t *__restrict__ row_off, int64_t n, int form,
                                                        const DynOut o, int64_t *__restrict__ kbeg, int64_t *__restrict__ ebeg, uint32_t *__restrict__ ew,
-                                                       uint32_t *__restrict__ flags) {
+                                                       CallFlags *__restrict__ flags) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = r < n;
     int64_t kl = 0, el = 0;
     if (live) {
         int64_t b = row_off[r], e = row_off[r + 1];
-        if (e < b) { atomicOr(flags + 3, 1u); e = b; }
+        if (e < b) { atomicOr(&flags->bad, (uint32_t)DYN_BAD_OFFSETS); e = b; }
         const DynRowCut c = dyn_row_cut(text, b, e);
         const int64_t l0 = c.f0e - c.f0;
         if (form == 0) { kl = l0 > 0 ? l0 - 1 : 0; el = l0 > 0 ? 1 : 0; ebeg[r] = c.f0 + kl; }
         else { kl = l0; el = c.f2e - c.f2; ebeg[r] = c.f2; }
-        if (el > 0x7FFFFFE0ll) { atomicOr(flags + 3, 1u); el = 0; }
+        if (el > 0x7FFFFFE0ll) { atomicOr(&flags->bad, (uint32_t)DYN_BAD_OFFSETS); el = 0; }
         kbeg[r] = c.f0;
         int64_t i = c.f1;
-        const int m = dyn_parse_int(text, i, c.f1e), l = dyn_parse_int(text, i, c.f1e), rr = dyn_parse_int(text, i, c.f1e);
+        const int m = pk_parse_int(text, i, c.f1e), l = pk_parse_int(text, i, c.f1e), rr = pk_parse_int(text, i, c.f1e);
         o.marker[r] = form == 0 ? 1 : m;
-        o.left[r] = l < -30000 ? -30000 : l > 30000 ? 30000 : l;
-        o.right[r] = rr < -30000 ? -30000 : rr > 30000 ? 30000 : rr;
+        o.left[r] = pk_clamp(l);
+        o.right[r] = pk_clamp(rr);
         o.key_len[r] = (uint8_t)(kl > 255 ? 255 : kl);
         o.ext_len[r] = (int32_t)el;
         ew[r] = (uint32_t)((el + 31) >> 5);
@@ -758,7 +732,7 @@ __global__ __launch_bounds__(256) void k_dyn_bin_sizes(const char *__restrict__ 
 }
 __device__ __forceinline__ uint64_t dyn_code32(const char *__restrict__ s, int cnt) {
     uint64_t x = 0;
-    for (int i = 0; i < 32; i++) if (i < cnt) { const char ch = s[i]; x |= (uint64_t)(ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : 3) << (62 - 2 * i); }
+    for (int i = 0; i < 32; i++) if (i < cnt) { const char ch = s[i]; x |= pk_code(ch) << (62 - 2 * i); }
     return x;
 }
 __global__ __launch_bounds__(256) void k_dyn_bin_key(const char *__restrict__ text, const int64_t *__restrict__ kbeg, const uint8_t *__restrict__ key_len,
@@ -774,7 +748,7 @@ __global__ __launch_bounds__(256) void k_dyn_bin_ext(const char *__restrict__ te
                                                      int64_t n, const int64_t *__restrict__ oeoff, uint64_t *__restrict__ oext) {
     const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (n <= 0 || w >= oeoff[n]) return;
-    const int64_t r = dyn_find(oeoff, n, w);
+    const int64_t r = pk_find(oeoff, n, w);
     const int j = (int)(w - oeoff[r]);
     oext[w] = dyn_code32(text + ebeg[r] + 32 * (int64_t)j, ext_len[r] - 32 * j);
 }
@@ -794,23 +768,23 @@ int rfx::dyn_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off
     RFX_HIP(d.ext_len.alloc(m * 4, ctx->stream)); RFX_HIP(d.marker.alloc(m * 4, ctx->stream)); RFX_HIP(d.left.alloc(m * 4, ctx->stream));
     RFX_HIP(d.right.alloc(m * 4, ctx->stream));
     RFX_HIP(kbeg.alloc(m * 8, ctx->stream)); RFX_HIP(ebeg.alloc(m * 8, ctx->stream)); RFX_HIP(ew.alloc(m * 4, ctx->stream));
-    RFX_TRY(dyn_flags_init(ctx, flags));
+    RFX_TRY(call_flags_init(ctx, flags));
     d.n = n;
-    hipLaunchKernelGGL(k_dyn_bin_sizes, GRID(n), d_text, d_row_off, n, form, dyn_out(d), kbeg.as<int64_t>(), ebeg.as<int64_t>(), ew.as<uint32_t>(),
-                       flags.as<uint32_t>());
+    hipLaunchKernelGGL(k_dyn_bin_sizes, RFX_GRID(n), d_text, d_row_off, n, form, dyn_out(d), kbeg.as<int64_t>(), ebeg.as<int64_t>(), ew.as<uint32_t>(),
+                       flags.as<CallFlags>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, ew.as<uint32_t>(), d.ext_off.as<uint64_t>(), n));
-    DynFlags f{};
-    RFX_TRY(dyn_flags_read(ctx, flags, d.ext_off.as<uint64_t>() + n, &f));
-    if (f.bad) { ctx->last_error = "dynamic-k binarizer: row offsets that run backwards"; return RFX_E_ARG; }
-    if (f.too_long) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
-    d.words = (int64_t)f.total;
+    CallFlags f{};
+    RFX_TRY(call_flags_read(ctx, flags, d.ext_off.as<uint64_t>() + n, nullptr, nullptr, &f));
+    if (f.bad & DYN_BAD_OFFSETS) { ctx->last_error = "dynamic-k binarizer: row offsets that run backwards"; return RFX_E_ARG; }
+    if (f.bad & DYN_TOO_LONG) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
+    d.words = (int64_t)f.total[0];
     RFX_HIP(d.ext.alloc((size_t)std::max<int64_t>(d.words, 1) * 8, ctx->stream));
-    hipLaunchKernelGGL(k_dyn_bin_key, GRID(n * DYN_KW), d_text, (const int64_t *)kbeg.as<int64_t>(), (const uint8_t *)d.key_len.as<uint8_t>(), n,
+    hipLaunchKernelGGL(k_dyn_bin_key, RFX_GRID(n * DYN_KW), d_text, (const int64_t *)kbeg.as<int64_t>(), (const uint8_t *)d.key_len.as<uint8_t>(), n,
                        d.key.as<uint64_t>());
     RFX_HIP(hipGetLastError());
     if (d.words > 0) {
-        hipLaunchKernelGGL(k_dyn_bin_ext, GRID(d.words), d_text, (const int64_t *)ebeg.as<int64_t>(), (const int32_t *)d.ext_len.as<int32_t>(), n,
+        hipLaunchKernelGGL(k_dyn_bin_ext, RFX_GRID(d.words), d_text, (const int64_t *)ebeg.as<int64_t>(), (const int32_t *)d.ext_len.as<int32_t>(), n,
                            (const int64_t *)d.ext_off.as<int64_t>(), d.ext.as<uint64_t>());
         RFX_HIP(hipGetLastError());
     }
@@ -832,48 +806,34 @@ int rfx::dyn_upload_text(rfx_ctx *ctx, const char *text, const int64_t *row_off,
 namespace {
 
 // ---- DSBinarySubKmerWith{Short,Long}ExtensionToString (FirstFour:226-263): rows "SUBKMER,marker|left|right,EXTENSION\n" ----------
-__device__ __forceinline__ int dyn_int_chars(int v) {              // characters of std::to_string(v)
-    int64_t a = v < 0 ? -(int64_t)v : (int64_t)v;
-    int c = v < 0 ? 2 : 1;
-    while (a >= 10) { a /= 10; c++; }
-    return c;
-}
-__device__ __forceinline__ char dyn_int_char(int v, int q) {        // its character q
-    if (v < 0) { if (q == 0) return '-'; q--; }
-    int64_t a = v < 0 ? -(int64_t)v : (int64_t)v;
-    int c = 1;
-    for (int64_t t = a; t >= 10; t /= 10) c++;
-    for (int s = c - 1 - q; s > 0; s--) a /= 10;
-    return (char)('0' + a % 10);
-}
 __global__ __launch_bounds__(256) void k_dyn_text_sizes(const DynView v, int64_t n, uint64_t *__restrict__ sz) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    sz[i] = (uint64_t)v.key_len[i] + (uint64_t)v.ext_len[i] + 5 + dyn_int_chars(v.marker[i]) + dyn_int_chars(v.left[i]) + dyn_int_chars(v.right[i]);
+    sz[i] = (uint64_t)v.key_len[i] + (uint64_t)v.ext_len[i] + 5 + pk_int_chars(v.marker[i]) + pk_int_chars(v.left[i]) + pk_int_chars(v.right[i]);
 }
 // one thread per output byte, up to lim (the smaller of the text's length and the buffer)
 __global__ __launch_bounds__(256) void k_dyn_text_fill(const DynView v, int64_t n, const uint64_t *__restrict__ toff, int64_t lim, char *__restrict__ out) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= lim) return;
-    const int64_t i = dyn_find(toff, n, b);
+    const int64_t i = pk_find(toff, n, b);
     int64_t q = b - (int64_t)toff[i];
     const int kl = (int)v.key_len[i], el = v.ext_len[i];
     char ch;
-    if (q < kl) ch = "ACGT"[(v.key[DYN_KW * i + (q >> 5)] >> (62 - 2 * (int)(q & 31))) & 3];
+    if (q < kl) ch = (char)pk_letter(pk_base_of(v.key + DYN_KW * i, (int)q));
     else {
         q -= kl;
         const int m = v.marker[i], l = v.left[i], r = v.right[i];
-        const int cm = dyn_int_chars(m), cl = dyn_int_chars(l), cr = dyn_int_chars(r);
+        const int cm = pk_int_chars(m), cl = pk_int_chars(l), cr = pk_int_chars(r);
         if (q == 0) ch = ',';
-        else if (q < 1 + cm) ch = dyn_int_char(m, (int)q - 1);
+        else if (q < 1 + cm) ch = pk_int_char(m, (int)q - 1);
         else if (q == 1 + cm) ch = '|';
-        else if (q < 2 + cm + cl) ch = dyn_int_char(l, (int)q - 2 - cm);
+        else if (q < 2 + cm + cl) ch = pk_int_char(l, (int)q - 2 - cm);
         else if (q == 2 + cm + cl) ch = '|';
-        else if (q < 3 + cm + cl + cr) ch = dyn_int_char(r, (int)q - 3 - cm - cl);
+        else if (q < 3 + cm + cl + cr) ch = pk_int_char(r, (int)q - 3 - cm - cl);
         else if (q == 3 + cm + cl + cr) ch = ',';
         else {
             q -= 4 + cm + cl + cr;
-            ch = q < el ? "ACGT"[(v.ext[v.ext_off[i] + (q >> 5)] >> (62 - 2 * (int)(q & 31))) & 3] : '\n';
+            ch = q < el ? (char)pk_letter(pk_base_of(v.ext + v.ext_off[i], (int)q)) : '\n';
         }
     }
     out[b] = ch;
@@ -887,7 +847,7 @@ int rfx::dyn_to_text(rfx_ctx *ctx, const DynDev &d, char *d_text, int64_t cap, i
     DevBuf sz, toff;
     RFX_HIP(sz.alloc((size_t)n * 8, ctx->stream)); RFX_HIP(toff.alloc((size_t)(n + 1) * 8, ctx->stream));
     const DynView v = dyn_view(d);
-    hipLaunchKernelGGL(k_dyn_text_sizes, GRID(n), v, n, sz.as<uint64_t>());
+    hipLaunchKernelGGL(k_dyn_text_sizes, RFX_GRID(n), v, n, sz.as<uint64_t>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u64(ctx, sz.as<uint64_t>(), toff.as<uint64_t>(), n));
     uint64_t t = 0;
@@ -899,7 +859,7 @@ int rfx::dyn_to_text(rfx_ctx *ctx, const DynDev &d, char *d_text, int64_t cap, i
     }
     const int64_t lim = std::min<int64_t>(*total, cap);
     if (lim > 0) {
-        hipLaunchKernelGGL(k_dyn_text_fill, GRID(lim), v, n, (const uint64_t *)toff.as<uint64_t>(), lim, d_text);
+        hipLaunchKernelGGL(k_dyn_text_fill, RFX_GRID(lim), v, n, (const uint64_t *)toff.as<uint64_t>(), lim, d_text);
         RFX_HIP(hipGetLastError());
     }
     return sync_checked(ctx);

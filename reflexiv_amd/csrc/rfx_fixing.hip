@@ -30,33 +30,17 @@
 #include <string>
 #include <vector>
 #include "rfx_internal.h"
-#include "rfx_fix_words.h"
+#include "rfx_packed_words.h"
 
 using namespace rfx;
 
 namespace {
 
-#define FX_GRID(n) dim3((unsigned)ceil_div(std::max<int64_t>((n), 1), 256)), dim3(256), 0, ctx->stream
 #define FX_K 31                      // FixedKmerSize
 #define FX_KEY (FX_K - 1)            // the key of every record behind the contig ends
 
-// flags of a call, in HBM: what is wrong with the input, and three 64-bit totals: one small read-back for all of them
-struct FxFlags { uint32_t bad, pad; uint64_t t0, t1, t2; };
+// what is wrong with a call's input (CallFlags::bad)
 enum { FX_BAD_KEY = 1, FX_BAD_EXT = 2, FX_BAD_VALUE = 4 };
-
-static int fx_flags_init(rfx_ctx *ctx, DevBuf &flags) {
-    RFX_HIP(flags.alloc(sizeof(FxFlags), ctx->stream));
-    RFX_HIP(hipMemsetAsync(flags.p, 0, sizeof(FxFlags), ctx->stream));
-    return RFX_OK;
-}
-__global__ void k_fx_put_totals(const uint64_t *__restrict__ a, const uint64_t *__restrict__ b, const uint64_t *__restrict__ c, uint64_t *__restrict__ flags) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) { flags[1] = a ? *a : 0ull; flags[2] = b ? *b : 0ull; flags[3] = c ? *c : 0ull; }
-}
-static int fx_flags_read(rfx_ctx *ctx, const DevBuf &flags, const uint64_t *a, const uint64_t *b, const uint64_t *c, FxFlags *h) {
-    hipLaunchKernelGGL(k_fx_put_totals, dim3(1), dim3(1), 0, ctx->stream, a, b, c, flags.as<uint64_t>());
-    RFX_HIP(hipGetLastError());
-    return small_readback(ctx, h, flags.p, sizeof(FxFlags));
-}
 
 // ---- a compaction: output record q := input record idx[q] -------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_fx_index(const uint32_t *__restrict__ keep, const uint64_t *__restrict__ rank, int64_t n, int64_t *__restrict__ idx) {
@@ -67,8 +51,8 @@ __global__ __launch_bounds__(256) void k_fx_gather_rec(const DynView v, const in
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= m) return;
     const int64_t i = idx[q];
-    const uint64_t *s = v.key + FX_KW * i;
-    uint64_t *d = o.key + FX_KW * q;
+    const uint64_t *s = v.key + PK_KW * i;
+    uint64_t *d = o.key + PK_KW * q;
     d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3];
     o.key_len[q] = v.key_len[i];
     o.ext_len[q] = v.ext_len[i];
@@ -80,7 +64,7 @@ __global__ __launch_bounds__(256) void k_fx_gather_ext(const DynView v, const in
                                                        uint64_t *__restrict__ oext) {
     const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (m <= 0 || w >= (int64_t)ooff[m]) return;
-    const int64_t q = fx_find(ooff, m, w);
+    const int64_t q = pk_find(ooff, m, w);
     oext[w] = v.ext[v.ext_off[idx[q]] + (w - (int64_t)ooff[q])];
 }
 
@@ -109,7 +93,7 @@ __global__ __launch_bounds__(256) void k_fx_ends_sizes(const uint8_t *__restrict
 __global__ __launch_bounds__(256) void k_fx_ends_kmers(const DynView v, int64_t n, const uint64_t *__restrict__ koff, uint64_t *__restrict__ out) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (int64_t)koff[n]) return;
-    const int64_t i = fx_find(koff, n, t);
+    const int64_t i = pk_find(koff, n, t);
     const int j = (int)(t - (int64_t)koff[i]);
     const FxCat c = fx_contig(v, i);
     const int L = c.l0 + c.l1;
@@ -123,11 +107,11 @@ __global__ __launch_bounds__(256) void k_fx_ends_long(const DynView v, int64_t n
     const int64_t m = (int64_t)loff[n], words = (int64_t)woff[n];
     const int cut = max_k - FX_KEY;
     if (t == 0) o.ext_off[m] = words;
-    if (t < FX_KW * m) {
-        const int64_t q = t / FX_KW, i = fx_find(loff, n, q);
-        const int j = (int)(t % FX_KW);
+    if (t < PK_KW * m) {
+        const int64_t q = t / PK_KW, i = pk_find(loff, n, q);
+        const int j = (int)(t % PK_KW);
         const FxCat c = fx_contig(v, i);
-        o.key[t] = j == 0 ? fx_keep(fx_cat32(c, cut), FX_KEY) : 0ull;
+        o.key[t] = j == 0 ? pk_keep(fx_cat32(c, cut), FX_KEY) : 0ull;
         if (j == 0) {
             const int l = v.left[i], r = v.right[i];
             o.key_len[q] = (uint8_t)FX_KEY;
@@ -135,12 +119,12 @@ __global__ __launch_bounds__(256) void k_fx_ends_long(const DynView v, int64_t n
             o.ext_len[q] = c.l0 + c.l1 - 2 * cut - FX_KEY;
             o.marker[q] = 1; o.left[q] = l > 0 ? max_k + 3 : l; o.right[q] = r > 0 ? max_k + 3 : r;
         }
-    } else if (t - FX_KW * m < words) {
-        const int64_t w = t - FX_KW * m, i = fx_find(woff, n, w);
+    } else if (t - PK_KW * m < words) {
+        const int64_t w = t - PK_KW * m, i = pk_find(woff, n, w);
         const int64_t r = w - (int64_t)woff[i];
         const FxCat c = fx_contig(v, i);
         const int el = c.l0 + c.l1 - 2 * cut - FX_KEY;
-        o.ext[w] = fx_keep(fx_cat32(c, cut + FX_KEY + (int)(32 * r)), el - (int)(32 * r));
+        o.ext[w] = pk_keep(fx_cat32(c, cut + FX_KEY + (int)(32 * r)), el - (int)(32 * r));
     }
 }
 
@@ -150,11 +134,11 @@ __global__ __launch_bounds__(256) void k_fx_iota(int64_t n, uint32_t *__restrict
     if (i < n) v[i] = (uint32_t)i;
 }
 // (a value of 2^62 or more is no 31-mer: the sort orders 62 bits only, so it is refused, not compared)
-__global__ __launch_bounds__(256) void k_fx_value_heads(const uint64_t *__restrict__ val, int64_t n, uint32_t *__restrict__ head, uint32_t *__restrict__ flags) {
+__global__ __launch_bounds__(256) void k_fx_value_heads(const uint64_t *__restrict__ val, int64_t n, uint32_t *__restrict__ head, CallFlags *__restrict__ flags) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     head[i] = (i == 0 || val[i] != val[i - 1]) ? 1u : 0u;
-    if (val[i] >> (2 * FX_K)) atomicOr(flags, (uint32_t)FX_BAD_VALUE);
+    if (val[i] >> (2 * FX_K)) atomicOr(&flags->bad, (uint32_t)FX_BAD_VALUE);
 }
 // a head writes record rank[i]: key = the first 30 bases, extension = the last base, attribute (1, -1, -1)
 __global__ __launch_bounds__(256) void k_fx_set_kmers(const uint64_t *__restrict__ val, const uint32_t *__restrict__ head, const uint64_t *__restrict__ rank,
@@ -163,8 +147,8 @@ __global__ __launch_bounds__(256) void k_fx_set_kmers(const uint64_t *__restrict
     if (i >= n || !head[i]) return;
     const int64_t q = (int64_t)rank[i];
     const uint64_t x = val[i] << 2;
-    uint64_t *d = o.key + FX_KW * q;
-    d[0] = fx_keep(x, FX_KEY); d[1] = 0; d[2] = 0; d[3] = 0;
+    uint64_t *d = o.key + PK_KW * q;
+    d[0] = pk_keep(x, FX_KEY); d[1] = 0; d[2] = 0; d[3] = 0;
     o.key_len[q] = (uint8_t)FX_KEY;
     o.ext[q] = (x << (2 * FX_KEY)) & (3ull << 62);
     o.ext_off[q] = q;
@@ -176,8 +160,8 @@ __global__ __launch_bounds__(256) void k_fx_set_long(const DynView v, int64_t n,
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t == 0) o.ext_off[base + n] = base + words;
     if (t < n) {
-        const uint64_t *s = v.key + FX_KW * t;
-        uint64_t *d = o.key + FX_KW * (base + t);
+        const uint64_t *s = v.key + PK_KW * t;
+        uint64_t *d = o.key + PK_KW * (base + t);
         d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3];
         o.key_len[base + t] = v.key_len[t];
         o.ext_off[base + t] = base + v.ext_off[t];
@@ -188,11 +172,11 @@ __global__ __launch_bounds__(256) void k_fx_set_long(const DynView v, int64_t n,
 }
 
 // ---- what the folds and the reflection ask of their input: keys of 30 bases, extensions of one base or more -------------------------------
-__global__ __launch_bounds__(256) void k_fx_check(const DynView v, int64_t n, uint32_t *__restrict__ flags) {
+__global__ __launch_bounds__(256) void k_fx_check(const DynView v, int64_t n, CallFlags *__restrict__ flags) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t bad = ((int)v.key_len[i] != FX_KEY ? (uint32_t)FX_BAD_KEY : 0u) | (v.ext_len[i] < 1 ? (uint32_t)FX_BAD_EXT : 0u);
-    if (bad) atomicOr(flags, bad);
+    if (bad) atomicOr(&flags->bad, bad);
 }
 
 // ---- steps 6 and 8: the two folds ---------------------------------------------------------------------------------------------------------
@@ -204,7 +188,7 @@ __global__ void k_fx_part_heads(const int64_t *__restrict__ ps, int P, uint32_t 
 __global__ __launch_bounds__(256) void k_fx_key_heads(const uint64_t *__restrict__ key, int64_t n, uint32_t *__restrict__ head) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    if (i == 0 || key[FX_KW * i] != key[FX_KW * (i - 1)]) head[i] = 1u;      // (a partition's first row holds 1 already)
+    if (i == 0 || key[PK_KW * i] != key[PK_KW * (i - 1)]) head[i] = 1u;      // (a partition's first row holds 1 already)
 }
 // a row's word in its run's contest: 0 for a row longer than one base, else the base code and then the row's index counted down --
 // the smallest one is the LAST row of the smallest code.  Runs of one row are settled here.
@@ -243,21 +227,21 @@ __global__ __launch_bounds__(256) void k_fx_reflect(const DynView v, int64_t n, 
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t words = v.ext_off[n];
     if (t == 0) o.ext_off[n] = words;
-    if (t < FX_KW * n) {
-        const int64_t i = t / FX_KW;
-        const int j = (int)(t % FX_KW);
+    if (t < PK_KW * n) {
+        const int64_t i = t / PK_KW;
+        const int j = (int)(t % PK_KW);
         const FxCat c = fx_contig(v, i);
-        o.key[t] = j == 0 ? fx_keep(fx_cat32(c, c.l0 + c.l1 - FX_KEY), FX_KEY) : 0ull;
+        o.key[t] = j == 0 ? pk_keep(fx_cat32(c, c.l0 + c.l1 - FX_KEY), FX_KEY) : 0ull;
         if (j == 0) {
             o.key_len[i] = (uint8_t)FX_KEY;
             o.ext_off[i] = v.ext_off[i];
             o.ext_len[i] = v.ext_len[i];
             o.marker[i] = 2; o.left[i] = v.left[i]; o.right[i] = v.right[i];
         }
-    } else if (t - FX_KW * n < words) {
-        const int64_t w = t - FX_KW * n, i = fx_find((const uint64_t *)v.ext_off, n, w);
+    } else if (t - PK_KW * n < words) {
+        const int64_t w = t - PK_KW * n, i = pk_find(v.ext_off, n, w);
         const int64_t r = w - v.ext_off[i];
-        o.ext[w] = fx_keep(fx_cat32(fx_contig(v, i), (int)(32 * r)), v.ext_len[i] - (int)(32 * r));
+        o.ext[w] = pk_keep(fx_cat32(fx_contig(v, i), (int)(32 * r)), v.ext_len[i] - (int)(32 * r));
     }
 }
 
@@ -271,56 +255,36 @@ static int fx_params(rfx_ctx *ctx, const rfx_fix_params *p, FxParams *o) {
     *o = FxParams{p->max_k, p->scramble, p->max_iteration};
     return RFX_OK;
 }
-static bool fx_out_ok(const rfx_dyn_packed *p) {
-    return p && p->key && p->key_len && p->ext && p->ext_off && p->ext_len && p->marker && p->left && p->right;
-}
-static bool fx_in_ok(const rfx_dyn_packed *p) { return fx_out_ok(p) && p->n >= 0; }
-static bool fx_text_ok(const char *t, const int64_t *off, int64_t n) { return n >= 0 && (n == 0 || (t && off)); }
-static int fx_empty(rfx_ctx *ctx, DynDev &d) {
-    RFX_TRY(dyn_alloc(ctx, d, 0, 0));
-    RFX_HIP(hipMemsetAsync(d.ext_off.p, 0, 8, ctx->stream));
-    return RFX_OK;
-}
 // keys of 30 bases, extensions of one base or more
 static int fx_check(rfx_ctx *ctx, const DynDev &in) {
     if (in.n == 0) return RFX_OK;
     DevBuf flags;
-    RFX_TRY(fx_flags_init(ctx, flags));
-    hipLaunchKernelGGL(k_fx_check, FX_GRID(in.n), dyn_view(in), in.n, flags.as<uint32_t>());
+    RFX_TRY(call_flags_init(ctx, flags));
+    hipLaunchKernelGGL(k_fx_check, RFX_GRID(in.n), dyn_view(in), in.n, flags.as<CallFlags>());
     RFX_HIP(hipGetLastError());
-    FxFlags f{};
-    RFX_TRY(fx_flags_read(ctx, flags, nullptr, nullptr, nullptr, &f));
+    CallFlags f{};
+    RFX_TRY(call_flags_read(ctx, flags, nullptr, nullptr, nullptr, &f));
     if (f.bad) {
         ctx->last_error = f.bad & FX_BAD_KEY ? "contig fixing: a key that is not 30 bases long" : "contig fixing: a record without an extension";
         return RFX_E_ARG;
     }
     return RFX_OK;
 }
-// the caller's partition starts: P + 1 entries, 0 first, n last, never running backwards -- read back and checked BEFORE a kernel
-// indexes with them
-static int fx_check_starts(rfx_ctx *ctx, const int64_t *d_ps, int P, int64_t n) {
-    int64_t h[65];
-    RFX_TRY(small_readback(ctx, h, d_ps, (size_t)(P + 1) * 8));
-    bool ok = h[0] == 0 && h[P] == n;
-    for (int p = 0; p < P && ok; p++) ok = h[p] <= h[p + 1];
-    if (!ok) { ctx->last_error = "contig fixing: partition starts that do not run from 0 to n"; return RFX_E_ARG; }
-    return RFX_OK;
-}
 // the kept records of a set, in order (keep / rank: n flags and their exclusive scan, rank[n] = m)
 static int fx_compact(rfx_ctx *ctx, const DynDev &in, const DevBuf &keep, const DevBuf &rank, int64_t m, DynDev &out) {
-    if (m == 0) return fx_empty(ctx, out);
+    if (m == 0) return dyn_empty(ctx, out);
     const int64_t n = in.n;
     DevBuf idx, ew;
     RFX_HIP(idx.alloc((size_t)m * 8, ctx->stream)); RFX_HIP(ew.alloc((size_t)m * 4, ctx->stream));
     RFX_TRY(dyn_alloc(ctx, out, m, in.words));
     const DynView v = dyn_view(in);
-    hipLaunchKernelGGL(k_fx_index, FX_GRID(n), (const uint32_t *)keep.as<uint32_t>(), (const uint64_t *)rank.as<uint64_t>(), n, idx.as<int64_t>());
+    hipLaunchKernelGGL(k_fx_index, RFX_GRID(n), (const uint32_t *)keep.as<uint32_t>(), (const uint64_t *)rank.as<uint64_t>(), n, idx.as<int64_t>());
     RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_fx_gather_rec, FX_GRID(m), v, (const int64_t *)idx.as<int64_t>(), m, dyn_out(out), ew.as<uint32_t>());
+    hipLaunchKernelGGL(k_fx_gather_rec, RFX_GRID(m), v, (const int64_t *)idx.as<int64_t>(), m, dyn_out(out), ew.as<uint32_t>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, ew.as<uint32_t>(), out.ext_off.as<uint64_t>(), m));
     if (in.words > 0) {
-        hipLaunchKernelGGL(k_fx_gather_ext, FX_GRID(in.words), v, (const int64_t *)idx.as<int64_t>(), m, (const uint64_t *)out.ext_off.as<uint64_t>(),
+        hipLaunchKernelGGL(k_fx_gather_ext, RFX_GRID(in.words), v, (const int64_t *)idx.as<int64_t>(), m, (const uint64_t *)out.ext_off.as<uint64_t>(),
                            out.ext.as<uint64_t>());
         RFX_HIP(hipGetLastError());
     }
@@ -329,13 +293,13 @@ static int fx_compact(rfx_ctx *ctx, const DynDev &in, const DevBuf &keep, const 
 
 // step 1: the binarizer (form 1) and its length filter
 static int fx_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, const FxParams &prm, DynDev &out) {
-    if (n == 0) return fx_empty(ctx, out);
+    if (n == 0) return dyn_empty(ctx, out);
     if (n >= ((int64_t)1 << 31)) { ctx->last_error = "contig fixing: 2^31 rows or more"; return RFX_E_LIMIT; }
     DynDev a;
     RFX_TRY(dyn_binarize(ctx, d_text, d_row_off, n, 1, a));
     DevBuf keep, rank;
     RFX_HIP(keep.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(rank.alloc((size_t)(n + 1) * 8, ctx->stream));
-    hipLaunchKernelGGL(k_fx_long_enough, FX_GRID(n), (const uint8_t *)a.key_len.as<uint8_t>(), (const int32_t *)a.ext_len.as<int32_t>(), n, 2 * prm.max_k,
+    hipLaunchKernelGGL(k_fx_long_enough, RFX_GRID(n), (const uint8_t *)a.key_len.as<uint8_t>(), (const int32_t *)a.ext_len.as<int32_t>(), n, 2 * prm.max_k,
                        keep.as<uint32_t>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, keep.as<uint32_t>(), rank.as<uint64_t>(), n));
@@ -349,27 +313,27 @@ static int fx_contig_ends(rfx_ctx *ctx, const DynDev &in, const FxParams &prm, D
     const int64_t n = in.n;
     *n_kmers = 0;
     RFX_HIP(kmers.alloc(8, ctx->stream));
-    if (n == 0) return fx_empty(ctx, out);
+    if (n == 0) return dyn_empty(ctx, out);
     DevBuf nk, nl, nw, koff, loff, woff, flags;
     RFX_HIP(nk.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(nl.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(nw.alloc((size_t)n * 4, ctx->stream));
     RFX_HIP(koff.alloc((size_t)(n + 1) * 8, ctx->stream)); RFX_HIP(loff.alloc((size_t)(n + 1) * 8, ctx->stream));
     RFX_HIP(woff.alloc((size_t)(n + 1) * 8, ctx->stream));
-    RFX_TRY(fx_flags_init(ctx, flags));
+    RFX_TRY(call_flags_init(ctx, flags));
     const DynView v = dyn_view(in);
-    hipLaunchKernelGGL(k_fx_ends_sizes, FX_GRID(n), v.key_len, v.ext_len, n, prm.max_k, nk.as<uint32_t>(), nl.as<uint32_t>(), nw.as<uint32_t>());
+    hipLaunchKernelGGL(k_fx_ends_sizes, RFX_GRID(n), v.key_len, v.ext_len, n, prm.max_k, nk.as<uint32_t>(), nl.as<uint32_t>(), nw.as<uint32_t>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan2_u32_to_u64(ctx, nk.as<uint32_t>(), nl.as<uint32_t>(), koff.as<uint64_t>(), loff.as<uint64_t>(), n));
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, nw.as<uint32_t>(), woff.as<uint64_t>(), n));
-    FxFlags f{};
-    RFX_TRY(fx_flags_read(ctx, flags, koff.as<uint64_t>() + n, loff.as<uint64_t>() + n, woff.as<uint64_t>() + n, &f));
-    const int64_t n31 = (int64_t)f.t0, m = (int64_t)f.t1, words = (int64_t)f.t2;
+    CallFlags f{};
+    RFX_TRY(call_flags_read(ctx, flags, koff.as<uint64_t>() + n, loff.as<uint64_t>() + n, woff.as<uint64_t>() + n, &f));
+    const int64_t n31 = (int64_t)f.total[0], m = (int64_t)f.total[1], words = (int64_t)f.total[2];
     *n_kmers = n31;
-    if (m == 0) return fx_empty(ctx, out);
+    if (m == 0) return dyn_empty(ctx, out);
     RFX_HIP(kmers.alloc((size_t)n31 * 8, ctx->stream));
     RFX_TRY(dyn_alloc(ctx, out, m, words));
-    hipLaunchKernelGGL(k_fx_ends_kmers, FX_GRID(n31), v, n, (const uint64_t *)koff.as<uint64_t>(), kmers.as<uint64_t>());
+    hipLaunchKernelGGL(k_fx_ends_kmers, RFX_GRID(n31), v, n, (const uint64_t *)koff.as<uint64_t>(), kmers.as<uint64_t>());
     RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_fx_ends_long, FX_GRID(FX_KW * m + words), v, n, prm.max_k, (const uint64_t *)loff.as<uint64_t>(), (const uint64_t *)woff.as<uint64_t>(),
+    hipLaunchKernelGGL(k_fx_ends_long, RFX_GRID(PK_KW * m + words), v, n, prm.max_k, (const uint64_t *)loff.as<uint64_t>(), (const uint64_t *)woff.as<uint64_t>(),
                        dyn_out(out));
     RFX_HIP(hipGetLastError());
     return RFX_OK;
@@ -384,27 +348,27 @@ static int fx_kmer_set(rfx_ctx *ctx, const uint64_t *d_kmers, int64_t n31, const
         RFX_HIP(val.alloc((size_t)n31 * 8, ctx->stream)); RFX_HIP(idx.alloc((size_t)n31 * 4, ctx->stream)); RFX_HIP(tk.alloc((size_t)n31 * 8, ctx->stream));
         RFX_HIP(tv.alloc((size_t)n31 * 4, ctx->stream)); RFX_HIP(head.alloc((size_t)n31 * 4, ctx->stream)); RFX_HIP(rank.alloc((size_t)(n31 + 1) * 8, ctx->stream));
         RFX_HIP(hipMemcpyAsync(val.p, d_kmers, (size_t)n31 * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_fx_iota, FX_GRID(n31), n31, idx.as<uint32_t>());
+        hipLaunchKernelGGL(k_fx_iota, RFX_GRID(n31), n31, idx.as<uint32_t>());
         RFX_HIP(hipGetLastError());
         RFX_TRY(sort_pairs(ctx, val.as<uint64_t>(), idx.as<uint32_t>(), n31, 2 * FX_K, tk.as<uint64_t>(), tv.as<uint32_t>()));
         DevBuf flags;
-        RFX_TRY(fx_flags_init(ctx, flags));
-        hipLaunchKernelGGL(k_fx_value_heads, FX_GRID(n31), (const uint64_t *)val.as<uint64_t>(), n31, head.as<uint32_t>(), flags.as<uint32_t>());
+        RFX_TRY(call_flags_init(ctx, flags));
+        hipLaunchKernelGGL(k_fx_value_heads, RFX_GRID(n31), (const uint64_t *)val.as<uint64_t>(), n31, head.as<uint32_t>(), flags.as<CallFlags>());
         RFX_HIP(hipGetLastError());
         RFX_TRY(exclusive_scan_u32_to_u64(ctx, head.as<uint32_t>(), rank.as<uint64_t>(), n31));
-        FxFlags f{};
-        RFX_TRY(fx_flags_read(ctx, flags, rank.as<uint64_t>() + n31, nullptr, nullptr, &f));
+        CallFlags f{};
+        RFX_TRY(call_flags_read(ctx, flags, rank.as<uint64_t>() + n31, nullptr, nullptr, &f));
         if (f.bad) { ctx->last_error = "contig fixing: a 31-mer value of 2^62 or more"; return RFX_E_ARG; }
-        d = (int64_t)f.t0;
+        d = (int64_t)f.total[0];
     }
-    if (d + lng.n == 0) return fx_empty(ctx, out);
+    if (d + lng.n == 0) return dyn_empty(ctx, out);
     RFX_TRY(dyn_alloc(ctx, out, d + lng.n, d + lng.words));
     if (d > 0) {
-        hipLaunchKernelGGL(k_fx_set_kmers, FX_GRID(n31), (const uint64_t *)val.as<uint64_t>(), (const uint32_t *)head.as<uint32_t>(),
+        hipLaunchKernelGGL(k_fx_set_kmers, RFX_GRID(n31), (const uint64_t *)val.as<uint64_t>(), (const uint32_t *)head.as<uint32_t>(),
                            (const uint64_t *)rank.as<uint64_t>(), n31, dyn_out(out));
         RFX_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_fx_set_long, FX_GRID(std::max(lng.n, lng.words)), dyn_view(lng), lng.n, lng.words, d, dyn_out(out));
+    hipLaunchKernelGGL(k_fx_set_long, RFX_GRID(std::max(lng.n, lng.words)), dyn_view(lng), lng.n, lng.words, d, dyn_out(out));
     RFX_HIP(hipGetLastError());
     return RFX_OK;
 }
@@ -414,10 +378,10 @@ static int fx_kmer_set(rfx_ctx *ctx, const uint64_t *d_kmers, int64_t n31, const
 static int fx_fold(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, DynDev &out, DevBuf &out_ps) {
     const int64_t n = in.n;
     RFX_HIP(out_ps.alloc((size_t)(P + 1) * 8, ctx->stream));
-    RFX_TRY(fx_check_starts(ctx, d_ps, P, n));
+    RFX_TRY(check_part_starts(ctx, d_ps, P, n, "contig fixing"));
     if (n == 0) {
         RFX_HIP(hipMemsetAsync(out_ps.p, 0, (size_t)(P + 1) * 8, ctx->stream));
-        return fx_empty(ctx, out);
+        return dyn_empty(ctx, out);
     }
     if (n >= ((int64_t)1 << 32)) { ctx->last_error = "contig fixing: 2^32 records or more"; return RFX_E_LIMIT; }
     RFX_TRY(fx_check(ctx, in));
@@ -429,13 +393,13 @@ static int fx_fold(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, D
     const DynView v = dyn_view(in);
     hipLaunchKernelGGL(k_fx_part_heads, dim3(1), dim3(64), 0, ctx->stream, d_ps, P, head.as<uint32_t>());
     RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_fx_key_heads, FX_GRID(n), v.key, n, head.as<uint32_t>());
+    hipLaunchKernelGGL(k_fx_key_heads, RFX_GRID(n), v.key, n, head.as<uint32_t>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, head.as<uint32_t>(), run.as<uint64_t>(), n));
-    hipLaunchKernelGGL(k_fx_fold_contest, FX_GRID(n), v, n, (const uint32_t *)head.as<uint32_t>(), (const uint64_t *)run.as<uint64_t>(),
+    hipLaunchKernelGGL(k_fx_fold_contest, RFX_GRID(n), v, n, (const uint32_t *)head.as<uint32_t>(), (const uint64_t *)run.as<uint64_t>(),
                        best.as<unsigned long long>());
     RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_fx_fold_keep, FX_GRID(n), v, n, (const uint32_t *)head.as<uint32_t>(), (const uint64_t *)run.as<uint64_t>(),
+    hipLaunchKernelGGL(k_fx_fold_keep, RFX_GRID(n), v, n, (const uint32_t *)head.as<uint32_t>(), (const uint64_t *)run.as<uint64_t>(),
                        (const unsigned long long *)best.as<unsigned long long>(), keep.as<uint32_t>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, keep.as<uint32_t>(), rank.as<uint64_t>(), n));
@@ -449,10 +413,10 @@ static int fx_fold(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, D
 // step 7
 static int fx_reflect(rfx_ctx *ctx, const DynDev &in, DynDev &out) {
     const int64_t n = in.n;
-    if (n == 0) return fx_empty(ctx, out);
+    if (n == 0) return dyn_empty(ctx, out);
     RFX_TRY(fx_check(ctx, in));
     RFX_TRY(dyn_alloc(ctx, out, n, in.words));
-    hipLaunchKernelGGL(k_fx_reflect, FX_GRID(FX_KW * n + in.words), dyn_view(in), n, dyn_out(out));
+    hipLaunchKernelGGL(k_fx_reflect, RFX_GRID(PK_KW * n + in.words), dyn_view(in), n, dyn_out(out));
     RFX_HIP(hipGetLastError());
     return RFX_OK;
 }
@@ -495,7 +459,7 @@ void rfx_fix_default_params(rfx_fix_params *p, int max_k) try {
 
 int rfx_dev_fix_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, const rfx_fix_params *params,
                          rfx_dyn_packed *d_out) try {
-    if (!ctx || !fx_out_ok(d_out) || !fx_text_ok(d_text, d_row_off, n_rows)) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_out_ok(d_out) || !text_rows_ok(d_text, d_row_off, n_rows)) return RFX_E_ARG;
     FxParams prm;
     RFX_TRY(fx_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -506,7 +470,7 @@ int rfx_dev_fix_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_
 
 int rfx_dev_fix_contig_ends(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rfx_fix_params *params, rfx_dyn_packed *d_out_long, uint64_t *d_kmers,
                             int64_t cap_kmers, int64_t *n_kmers) try {
-    if (!ctx || !fx_in_ok(d_in) || !fx_out_ok(d_out_long) || !n_kmers || cap_kmers < 0 || (cap_kmers > 0 && !d_kmers)) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out_long) || !n_kmers || cap_kmers < 0 || (cap_kmers > 0 && !d_kmers)) return RFX_E_ARG;
     FxParams prm;
     RFX_TRY(fx_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -526,7 +490,7 @@ int rfx_dev_fix_contig_ends(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rfx_
 } RFX_API_CATCH(ctx)
 
 int rfx_dev_fix_kmer_set(rfx_ctx *ctx, const uint64_t *d_kmers, int64_t n_kmers, const rfx_dyn_packed *d_long, rfx_dyn_packed *d_out) try {
-    if (!ctx || n_kmers < 0 || (n_kmers > 0 && !d_kmers) || !fx_in_ok(d_long) || !fx_out_ok(d_out)) return RFX_E_ARG;
+    if (!ctx || n_kmers < 0 || (n_kmers > 0 && !d_kmers) || !dyn_packed_ok(d_long) || !dyn_packed_out_ok(d_out)) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a, b;
     RFX_TRY(dyn_borrow(ctx, d_long, a));
@@ -537,7 +501,7 @@ int rfx_dev_fix_kmer_set(rfx_ctx *ctx, const uint64_t *d_kmers, int64_t n_kmers,
 
 int rfx_dev_fix_fork_filter(rfx_ctx *ctx, int reflected, const rfx_dyn_packed *d_sorted, const int64_t *d_part_start, int P, rfx_dyn_packed *d_out,
                             int64_t *d_out_part_start) try {
-    if (!ctx || !fx_in_ok(d_sorted) || !fx_out_ok(d_out) || !d_part_start || !d_out_part_start || P < 1 || P > 63 || (reflected != 0 && reflected != 1))
+    if (!ctx || !dyn_packed_ok(d_sorted) || !dyn_packed_out_ok(d_out) || !d_part_start || !d_out_part_start || P < 1 || P > 63 || (reflected != 0 && reflected != 1))
         return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a, b;
@@ -550,7 +514,7 @@ int rfx_dev_fix_fork_filter(rfx_ctx *ctx, int reflected, const rfx_dyn_packed *d
 } RFX_API_CATCH(ctx)
 
 int rfx_dev_fix_reflect(rfx_ctx *ctx, const rfx_dyn_packed *d_in, rfx_dyn_packed *d_out) try {
-    if (!ctx || !fx_in_ok(d_in) || !fx_out_ok(d_out)) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out)) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a, b;
     RFX_TRY(dyn_borrow(ctx, d_in, a));
@@ -560,7 +524,7 @@ int rfx_dev_fix_reflect(rfx_ctx *ctx, const rfx_dyn_packed *d_in, rfx_dyn_packed
 
 int rfx_dev_fix_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, int P, const rfx_fix_params *params,
                     rfx_dyn_packed *d_out) try {
-    if (!ctx || !fx_out_ok(d_out) || !fx_text_ok(d_text, d_row_off, n_rows) || P < 1 || P > 63) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_out_ok(d_out) || !text_rows_ok(d_text, d_row_off, n_rows) || P < 1 || P > 63) return RFX_E_ARG;
     FxParams prm;
     RFX_TRY(fx_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -572,7 +536,7 @@ int rfx_dev_fix_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, 
 // host text in, host text out; everything between packed and in HBM: upload, run, to-text, one copy back
 int rfx_fix_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
                  int64_t *out_len) try {
-    if (!ctx || !fx_text_ok(text, row_off, n_rows) || P < 1 || P > 63 || !out_len || cap < 0 || (cap > 0 && !out)) return RFX_E_ARG;
+    if (!ctx || !text_rows_ok(text, row_off, n_rows) || P < 1 || P > 63 || !out_len || cap < 0 || (cap > 0 && !out)) return RFX_E_ARG;
     FxParams prm;
     RFX_TRY(fx_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));

@@ -19,52 +19,36 @@
 //                    buffer's unaligned head, the one at its tail and the one at `cap` store bytes.
 #include <algorithm>
 #include "rfx_internal.h"
-#include "rfx_fix_words.h"
+#include "rfx_packed_words.h"
 
 using namespace rfx;
 
 namespace {
 
-#define FX2_GRID(n) dim3((unsigned)ceil_div(std::max<int64_t>((n), 1), 256)), dim3(256), 0, ctx->stream
 #define FX2_KEY 30                   // FixedKmerSize - 1: the key of every record of 04Fixing
 #define FX2_END 200                  // bases of a contig end (:278-279); a contig of 2 FX2_END bases or more gives two ends
 
-// flags of a call, in HBM: what is wrong with the input, and two 64-bit totals: one small read-back for all of them
-struct Fx2Flags { uint64_t bad, t0, t1; };
+// what is wrong with a call's input (CallFlags::bad)
 enum { FX2_BAD_KEY = 1, FX2_BAD_EXT = 2, FX2_BAD_LAYOUT = 4, FX2_TOO_LONG = 8 };
-
-static int fx2_flags_init(rfx_ctx *ctx, DevBuf &flags) {
-    RFX_HIP(flags.alloc(sizeof(Fx2Flags), ctx->stream));
-    RFX_HIP(hipMemsetAsync(flags.p, 0, sizeof(Fx2Flags), ctx->stream));
-    return RFX_OK;
-}
-__global__ void k_fx2_put_totals(const uint64_t *__restrict__ a, const uint64_t *__restrict__ b, uint64_t *__restrict__ flags) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) { flags[1] = a ? *a : 0ull; flags[2] = b ? *b : 0ull; }
-}
-static int fx2_flags_read(rfx_ctx *ctx, const DevBuf &flags, const uint64_t *a, const uint64_t *b, Fx2Flags *h) {
-    hipLaunchKernelGGL(k_fx2_put_totals, dim3(1), dim3(1), 0, ctx->stream, a, b, flags.as<uint64_t>());
-    RFX_HIP(hipGetLastError());
-    return small_readback(ctx, h, flags.p, sizeof(Fx2Flags));
-}
 
 // ---- what the stage asks of its records: keys of 30 bases (ONE long in the reference), extensions of one base or more -----------
 __global__ __launch_bounds__(256) void k_fx2_check(const uint8_t *__restrict__ key_len, const int32_t *__restrict__ ext_len, int64_t n,
-                                                   unsigned long long *__restrict__ flags) {
+                                                   CallFlags *__restrict__ flags) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const unsigned long long bad = ((int)key_len[i] != FX2_KEY ? FX2_BAD_KEY : 0) | (ext_len[i] < 1 ? FX2_BAD_EXT : 0);
-    if (bad) atomicOr(flags, bad);
+    const uint32_t bad = ((int)key_len[i] != FX2_KEY ? (uint32_t)FX2_BAD_KEY : 0u) | (ext_len[i] < 1 ? (uint32_t)FX2_BAD_EXT : 0u);
+    if (bad) atomicOr(&flags->bad, bad);
 }
 
 // ---- step 3: the contigs -----------------------------------------------------------------------------------------------------
 // per record: whether its contig is kept (key_len + ext_len >= 2 max_k) and the words it takes
 __global__ __launch_bounds__(256) void k_fx2_cat_sizes(const uint8_t *__restrict__ key_len, const int32_t *__restrict__ ext_len, int64_t n, int min_len,
-                                                       uint32_t *__restrict__ keep, uint32_t *__restrict__ nw, unsigned long long *__restrict__ flags) {
+                                                       uint32_t *__restrict__ keep, uint32_t *__restrict__ nw, CallFlags *__restrict__ flags) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int64_t L = (int64_t)key_len[i] + ext_len[i];
-    if (ext_len[i] < 0) atomicOr(flags, (unsigned long long)FX2_BAD_EXT);
-    if (L >= ((int64_t)1 << 30)) atomicOr(flags, (unsigned long long)FX2_TOO_LONG);
+    if (ext_len[i] < 0) atomicOr(&flags->bad, (uint32_t)FX2_BAD_EXT);
+    if (L >= ((int64_t)1 << 30)) atomicOr(&flags->bad, (uint32_t)FX2_TOO_LONG);
     const bool ok = ext_len[i] >= 0 && L < ((int64_t)1 << 30) && L >= min_len;
     keep[i] = ok ? 1u : 0u;
     nw[i] = ok ? (uint32_t)((L + 31) >> 5) : 0u;
@@ -84,51 +68,37 @@ __global__ __launch_bounds__(256) void k_fx2_cat(const DynView v, int64_t n, con
         olen[q] = (int64_t)v.key_len[t] + v.ext_len[t];
         oleft[q] = v.left[t]; oright[q] = v.right[t];
     } else if (t - n < words) {
-        const int64_t w = t - n, i = fx_find(woff, n, w);
+        const int64_t w = t - n, i = pk_find(woff, n, w);
         const int r = (int)(w - (int64_t)woff[i]);
         const FxCat c = fx_contig(v, i);
-        ow[w] = fx_keep(fx_cat32(c, 32 * r), c.l0 + c.l1 - 32 * r);
+        ow[w] = pk_keep(fx_cat32(c, 32 * r), c.l0 + c.l1 - 32 * r);
     }
 }
 
 // ---- steps 4-5: the two texts ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int fx2_int_chars(int v) {               // characters of std::to_string(v)
-    int64_t a = v < 0 ? -(int64_t)v : (int64_t)v;
-    int c = v < 0 ? 2 : 1;
-    while (a >= 10) { a /= 10; c++; }
-    return c;
-}
-__device__ __forceinline__ char fx2_int_char(int v, int q) {         // its character q
-    if (v < 0) { if (q == 0) return '-'; q--; }
-    uint32_t a = v < 0 ? (uint32_t)(-(int64_t)v) : (uint32_t)v;
-    int c = 1;
-    for (uint32_t t = a; t >= 10; t /= 10) c++;
-    for (int s = c - 1 - q; s > 0; s--) a /= 10;
-    return (char)('0' + a % 10);
-}
 // a record of either text: "Contig_<L>_<left>_<right>_<idx>" is its ID of h characters
 struct Fx2Rec { int L, left, right, idx, cL, cl, cr, h; const uint64_t *w; };
 __device__ __forceinline__ Fx2Rec fx2_rec(const uint64_t *__restrict__ words, const int64_t *__restrict__ woff, const int64_t *__restrict__ len,
                                           const int32_t *__restrict__ left, const int32_t *__restrict__ right, int64_t i) {
     Fx2Rec r;
     r.L = (int)len[i]; r.left = left[i]; r.right = right[i]; r.idx = (int)i;
-    r.cL = fx2_int_chars(r.L); r.cl = fx2_int_chars(r.left); r.cr = fx2_int_chars(r.right);
-    r.h = 7 + r.cL + 1 + r.cl + 1 + r.cr + 1 + fx2_int_chars(r.idx);
+    r.cL = pk_int_chars(r.L); r.cl = pk_int_chars(r.left); r.cr = pk_int_chars(r.right);
+    r.h = 7 + r.cL + 1 + r.cl + 1 + r.cr + 1 + pk_int_chars(r.idx);
     r.w = words + woff[i];
     return r;
 }
 __device__ __forceinline__ char fx2_id_char(const Fx2Rec &r, int q) {
     if (q < 7) return "Contig_"[q];
     q -= 7;
-    if (q < r.cL) return fx2_int_char(r.L, q);
+    if (q < r.cL) return pk_int_char(r.L, q);
     q -= r.cL;
     if (q == 0) return '_';
-    if (q < 1 + r.cl) return fx2_int_char(r.left, q - 1);
+    if (q < 1 + r.cl) return pk_int_char(r.left, q - 1);
     q -= 1 + r.cl;
     if (q == 0) return '_';
-    if (q < 1 + r.cr) return fx2_int_char(r.right, q - 1);
+    if (q < 1 + r.cr) return pk_int_char(r.right, q - 1);
     q -= 1 + r.cr;
-    return q == 0 ? '_' : fx2_int_char(r.idx, q - 1);
+    return q == 0 ? '_' : pk_int_char(r.idx, q - 1);
 }
 // bytes of a record.  ends 0: "<ID>,<contig>\n".  ends 1: L >= 400 gives ">ID-L\n" + bases [0, 200) + "\n" + ">ID-R\n" + bases
 // [L - 200, L) + "\n", anything shorter ">ID\n" + the contig + "\n"
@@ -170,21 +140,19 @@ __device__ __forceinline__ char fx2_byte(const Fx2Rec &r, int ends, int64_t q, i
     *t = (right ? r.L - FX2_END : 0) + (int)q; *run = FX2_END - (int)q;
     return 0;
 }
-__device__ __forceinline__ uint32_t fx2_letter(uint32_t code) { return (0x54474341u >> (8 * code)) & 0xFFu; }       // "ACGT"
-__device__ __forceinline__ uint32_t fx2_base(const uint64_t *__restrict__ w, int t) { return (uint32_t)(w[t >> 5] >> (62 - 2 * (t & 31))) & 3u; }
 
 // per contig: the bytes of its record; the layout the header promises is checked here, before anything indexes with it
 __global__ __launch_bounds__(256) void k_fx2_text_sizes(const int64_t *__restrict__ woff, const int64_t *__restrict__ len, const int32_t *__restrict__ left,
                                                         const int32_t *__restrict__ right, int64_t n, int ends, uint64_t *__restrict__ sz,
-                                                        unsigned long long *__restrict__ flags) {
+                                                        CallFlags *__restrict__ flags) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int64_t L = len[i];
     const bool bad = L < 0 || woff[i + 1] - woff[i] != ((L + 31) >> 5) || (i == 0 && woff[0] != 0);
-    if (bad) atomicOr(flags, (unsigned long long)FX2_BAD_LAYOUT);
-    if (!bad && L >= ((int64_t)1 << 30)) atomicOr(flags, (unsigned long long)FX2_TOO_LONG);
+    if (bad) atomicOr(&flags->bad, (uint32_t)FX2_BAD_LAYOUT);
+    if (!bad && L >= ((int64_t)1 << 30)) atomicOr(&flags->bad, (uint32_t)FX2_TOO_LONG);
     const int Lc = bad || L >= ((int64_t)1 << 30) ? 0 : (int)L;
-    const int h = 7 + fx2_int_chars(Lc) + 1 + fx2_int_chars(left[i]) + 1 + fx2_int_chars(right[i]) + 1 + fx2_int_chars((int)i);
+    const int h = 7 + pk_int_chars(Lc) + 1 + pk_int_chars(left[i]) + 1 + pk_int_chars(right[i]) + 1 + pk_int_chars((int)i);
     sz[i] = (uint64_t)fx2_rec_bytes(Lc, h, ends);
 }
 // one thread per 16-byte chunk of the destination: chunk c holds the text's bytes [16 c - skew, 16 c - skew + 16) cut to [0, lim),
@@ -197,7 +165,7 @@ __global__ __launch_bounds__(256) void k_fx2_text_fill(const uint64_t *__restric
     const int64_t start = 16 * c - skew;
     const int64_t b0 = start < 0 ? 0 : start, b1 = start + 16 < lim ? start + 16 : lim;
     const bool whole = b1 - b0 == 16;
-    int64_t i = fx_find(toff, n, b0);
+    int64_t i = pk_find(toff, n, b0);
     Fx2Rec r = fx2_rec(words, woff, len, left, right, i);
     int64_t q = b0 - (int64_t)toff[i], next = (int64_t)toff[i + 1];
     uint32_t o[4] = {0u, 0u, 0u, 0u};
@@ -210,7 +178,7 @@ __global__ __launch_bounds__(256) void k_fx2_text_fill(const uint64_t *__restric
         if (sh > 32) x |= r.w[wi + 1] >> (64 - sh);
         const uint32_t y = (uint32_t)(x >> 32);
 #pragma unroll
-        for (int j = 0; j < 16; j++) o[j >> 2] |= fx2_letter((y >> (30 - 2 * j)) & 3u) << (8 * (j & 3));
+        for (int j = 0; j < 16; j++) o[j >> 2] |= pk_letter((y >> (30 - 2 * j)) & 3u) << (8 * (j & 3));
     } else {
 #pragma unroll
         for (int j = 0; j < 16; j++) {
@@ -222,7 +190,7 @@ __global__ __launch_bounds__(256) void k_fx2_text_fill(const uint64_t *__restric
                     q = 0; next = (int64_t)toff[i + 1];
                 }
                 char ch = fx2_byte(r, ends, q, &t, &run);
-                if (ch == 0) ch = (char)fx2_letter(fx2_base(r.w, t));
+                if (ch == 0) ch = (char)pk_letter(pk_base_of(r.w, t));
                 o[j >> 2] |= (uint32_t)(uint8_t)ch << (8 * (j & 3));
                 q++;
             }
@@ -236,21 +204,16 @@ __global__ __launch_bounds__(256) void k_fx2_text_fill(const uint64_t *__restric
     }
 }
 
-static int fx2_empty(rfx_ctx *ctx, DynDev &d) {
-    RFX_TRY(dyn_alloc(ctx, d, 0, 0));
-    RFX_HIP(hipMemsetAsync(d.ext_off.p, 0, 8, ctx->stream));
-    return RFX_OK;
-}
 // keys of 30 bases, extensions of one base or more
 static int fx2_check(rfx_ctx *ctx, const DynDev &in) {
     if (in.n == 0) return RFX_OK;
     DevBuf flags;
-    RFX_TRY(fx2_flags_init(ctx, flags));
-    hipLaunchKernelGGL(k_fx2_check, FX2_GRID(in.n), (const uint8_t *)in.key_len.as<uint8_t>(), (const int32_t *)in.ext_len.as<int32_t>(), in.n,
-                       flags.as<unsigned long long>());
+    RFX_TRY(call_flags_init(ctx, flags));
+    hipLaunchKernelGGL(k_fx2_check, RFX_GRID(in.n), (const uint8_t *)in.key_len.as<uint8_t>(), (const int32_t *)in.ext_len.as<int32_t>(), in.n,
+                       flags.as<CallFlags>());
     RFX_HIP(hipGetLastError());
-    Fx2Flags f{};
-    RFX_TRY(fx2_flags_read(ctx, flags, nullptr, nullptr, &f));
+    CallFlags f{};
+    RFX_TRY(call_flags_read(ctx, flags, nullptr, nullptr, nullptr, &f));
     if (f.bad) {
         ctx->last_error = f.bad & FX2_BAD_KEY ? "contig fixing, round two: a key that is not 30 bases long" : "contig fixing, round two: a record without an extension";
         return RFX_E_ARG;
@@ -262,7 +225,7 @@ static int fx2_check(rfx_ctx *ctx, const DynDev &in) {
 
 // step 1: the binarizer (form 1), no length filter; a key that is not 30 bases long or a row without an extension is refused
 int rfx::fx2_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, DynDev &out) {
-    if (n == 0) return fx2_empty(ctx, out);
+    if (n == 0) return dyn_empty(ctx, out);
     if (n >= ((int64_t)1 << 31)) { ctx->last_error = "contig fixing, round two: 2^31 rows or more"; return RFX_E_LIMIT; }
     RFX_TRY(dyn_binarize(ctx, d_text, d_row_off, n, 1, out));
     return fx2_check(ctx, out);
@@ -271,7 +234,7 @@ int rfx::fx2_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off
 // step 2: min(max_iteration + 1, 29) x (sort, loop), the set resident in HBM; zero rounds copy the set.  The loop is the dynamic-k
 // pass below iteration 61 (stage 1), as in rfx_fixing.hip
 int rfx::fx2_run(rfx_ctx *ctx, const DynDev &in, int P, int scramble, int max_iteration, DynDev &out) {
-    if (in.n == 0) return fx2_empty(ctx, out);
+    if (in.n == 0) return dyn_empty(ctx, out);
     RFX_TRY(fx2_check(ctx, in));
     const int rounds = std::min(max_iteration + 1, 29);
     const int start_marker = scramble == 3 ? 1 : 2;
@@ -279,7 +242,7 @@ int rfx::fx2_run(rfx_ctx *ctx, const DynDev &in, int P, int scramble, int max_it
         const int64_t n = in.n, words = in.words;
         RFX_TRY(dyn_alloc(ctx, out, n, words));
         auto cp = [&](DevBuf &d, const DevBuf &s, size_t bytes) { return bytes ? hipMemcpyAsync(d.p, s.p, bytes, hipMemcpyDeviceToDevice, ctx->stream) : hipSuccess; };
-        RFX_HIP(cp(out.key, in.key, (size_t)n * FX_KW * 8)); RFX_HIP(cp(out.key_len, in.key_len, (size_t)n));
+        RFX_HIP(cp(out.key, in.key, (size_t)n * PK_KW * 8)); RFX_HIP(cp(out.key_len, in.key_len, (size_t)n));
         RFX_HIP(cp(out.ext, in.ext, (size_t)words * 8)); RFX_HIP(cp(out.ext_off, in.ext_off, (size_t)(n + 1) * 8));
         RFX_HIP(cp(out.ext_len, in.ext_len, (size_t)n * 4)); RFX_HIP(cp(out.marker, in.marker, (size_t)n * 4));
         RFX_HIP(cp(out.left, in.left, (size_t)n * 4)); RFX_HIP(cp(out.right, in.right, (size_t)n * 4));
@@ -307,16 +270,16 @@ int rfx::fx2_contigs_plan(rfx_ctx *ctx, const DynDev &in, int max_k, Fx2Plan &pl
     DevBuf nw, flags;
     RFX_HIP(plan.keep.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(nw.alloc((size_t)n * 4, ctx->stream));
     RFX_HIP(plan.rank.alloc((size_t)(n + 1) * 8, ctx->stream)); RFX_HIP(plan.woff.alloc((size_t)(n + 1) * 8, ctx->stream));
-    RFX_TRY(fx2_flags_init(ctx, flags));
-    hipLaunchKernelGGL(k_fx2_cat_sizes, FX2_GRID(n), (const uint8_t *)in.key_len.as<uint8_t>(), (const int32_t *)in.ext_len.as<int32_t>(), n, 2 * max_k,
-                       plan.keep.as<uint32_t>(), nw.as<uint32_t>(), flags.as<unsigned long long>());
+    RFX_TRY(call_flags_init(ctx, flags));
+    hipLaunchKernelGGL(k_fx2_cat_sizes, RFX_GRID(n), (const uint8_t *)in.key_len.as<uint8_t>(), (const int32_t *)in.ext_len.as<int32_t>(), n, 2 * max_k,
+                       plan.keep.as<uint32_t>(), nw.as<uint32_t>(), flags.as<CallFlags>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan2_u32_to_u64(ctx, plan.keep.as<uint32_t>(), nw.as<uint32_t>(), plan.rank.as<uint64_t>(), plan.woff.as<uint64_t>(), n));
-    Fx2Flags f{};
-    RFX_TRY(fx2_flags_read(ctx, flags, plan.rank.as<uint64_t>() + n, plan.woff.as<uint64_t>() + n, &f));
+    CallFlags f{};
+    RFX_TRY(call_flags_read(ctx, flags, plan.rank.as<uint64_t>() + n, plan.woff.as<uint64_t>() + n, nullptr, &f));
     if (f.bad & FX2_BAD_EXT) { ctx->last_error = "contig fixing, round two: a negative extension length"; return RFX_E_ARG; }
     if (f.bad & FX2_TOO_LONG) { ctx->last_error = "contig fixing, round two: a contig of 2^30 bases or more"; return RFX_E_LIMIT; }
-    plan.m = (int64_t)f.t0; plan.words = (int64_t)f.t1;
+    plan.m = (int64_t)f.total[0]; plan.words = (int64_t)f.total[1];
     return RFX_OK;
 }
 // second half: the kept contigs into arrays that hold plan.m contigs (word_off: plan.m + 1) and plan.words words
@@ -327,7 +290,7 @@ int rfx::fx2_contigs_fill(rfx_ctx *ctx, const DynDev &in, const Fx2Plan &plan, u
         RFX_HIP(hipMemsetAsync(d_word_off, 0, 8, ctx->stream));
         return RFX_OK;
     }
-    hipLaunchKernelGGL(k_fx2_cat, FX2_GRID(n + plan.words), dyn_view(in), n, (const uint32_t *)plan.keep.as<uint32_t>(), (const uint64_t *)plan.rank.as<uint64_t>(),
+    hipLaunchKernelGGL(k_fx2_cat, RFX_GRID(n + plan.words), dyn_view(in), n, (const uint32_t *)plan.keep.as<uint32_t>(), (const uint64_t *)plan.rank.as<uint64_t>(),
                        (const uint64_t *)plan.woff.as<uint64_t>(), d_words, d_word_off, d_len, d_left, d_right);
     RFX_HIP(hipGetLastError());
     return RFX_OK;
@@ -342,15 +305,15 @@ int rfx::fx2_text(rfx_ctx *ctx, const Fx2View &v, int ends, char *d_text, int64_
     if (n >= ((int64_t)1 << 31)) { ctx->last_error = "contig fixing, round two: 2^31 contigs or more"; return RFX_E_LIMIT; }
     DevBuf sz, toff, flags;
     RFX_HIP(sz.alloc((size_t)n * 8, ctx->stream)); RFX_HIP(toff.alloc((size_t)(n + 1) * 8, ctx->stream));
-    RFX_TRY(fx2_flags_init(ctx, flags));
-    hipLaunchKernelGGL(k_fx2_text_sizes, FX2_GRID(n), v.woff, v.len, v.left, v.right, n, ends, sz.as<uint64_t>(), flags.as<unsigned long long>());
+    RFX_TRY(call_flags_init(ctx, flags));
+    hipLaunchKernelGGL(k_fx2_text_sizes, RFX_GRID(n), v.woff, v.len, v.left, v.right, n, ends, sz.as<uint64_t>(), flags.as<CallFlags>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u64(ctx, sz.as<uint64_t>(), toff.as<uint64_t>(), n));
-    Fx2Flags f{};
-    RFX_TRY(fx2_flags_read(ctx, flags, toff.as<uint64_t>() + n, nullptr, &f));
+    CallFlags f{};
+    RFX_TRY(call_flags_read(ctx, flags, toff.as<uint64_t>() + n, nullptr, nullptr, &f));
     if (f.bad & FX2_BAD_LAYOUT) { ctx->last_error = "contigs: word_off and len disagree (word_off[0] = 0, word_off[i+1] - word_off[i] = (len[i] + 31) / 32)"; return RFX_E_ARG; }
     if (f.bad & FX2_TOO_LONG) { ctx->last_error = "contig fixing, round two: a contig of 2^30 bases or more"; return RFX_E_LIMIT; }
-    *total = (int64_t)f.t0;
+    *total = (int64_t)f.total[0];
     if (own) {
         RFX_HIP(own->alloc((size_t)std::max<int64_t>(*total, 1), ctx->stream));
         d_text = own->as<char>(); cap = *total;
@@ -359,7 +322,7 @@ int rfx::fx2_text(rfx_ctx *ctx, const Fx2View &v, int ends, char *d_text, int64_
     if (lim > 0) {
         const int skew = (int)((uintptr_t)d_text & 15);
         const int64_t chunks = ceil_div(lim + skew, 16);
-        hipLaunchKernelGGL(k_fx2_text_fill, FX2_GRID(chunks), v.w, v.woff, v.len, v.left, v.right, n, ends, (const uint64_t *)toff.as<uint64_t>(), lim, skew, chunks,
+        hipLaunchKernelGGL(k_fx2_text_fill, RFX_GRID(chunks), v.w, v.woff, v.len, v.left, v.right, n, ends, (const uint64_t *)toff.as<uint64_t>(), lim, skew, chunks,
                            d_text);
         RFX_HIP(hipGetLastError());
     }

@@ -6,6 +6,7 @@
 #include <string.h>
 #include <stdlib.h>
 #include <time.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 #include <map>
@@ -290,6 +291,8 @@ struct ScopedTimer {
 };
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// the launch shape of the one-thread-per-item kernels: ceil(n / 256) blocks (one for n = 0) of 256 threads on the context's stream
+#define RFX_GRID(n) dim3((unsigned)ceil_div(std::max<int64_t>((n), 1), 256)), dim3(256), 0, ctx->stream
 
 namespace rfx {
 
@@ -451,7 +454,7 @@ int small_passes(rfx_ctx *ctx, DevRecords &recs, int k, int twin, bool wide, int
 int small_pass_limit();
 int small_pass_max_partitions();
 
-// ---- rfx_dynamic.hip : a packed dynamic-k record set in HBM (rfx_dyn_packed), shared with rfx_ksort.hip
+// ---- rfx_dynamic.hip : a packed dynamic-k record set in HBM (rfx_dyn_packed), shared with every stage on packed sets
 struct DynDev {                       // a packed record set in HBM
     int64_t n = 0, words = 0;         // records; a BOUND on the extension words (the exact count is ext_off[n], in HBM)
     DevBuf key, key_len, ext, ext_off, ext_len, marker, left, right;
@@ -472,6 +475,22 @@ inline DynOut dyn_out(const DynDev &d) {
                   d.marker.as<int32_t>(), d.left.as<int32_t>(), d.right.as<int32_t>()};
 }
 int dyn_alloc(rfx_ctx *ctx, DynDev &d, int64_t n, int64_t words);
+// The flags of one call of a stage on packed sets, in HBM: what is wrong with the input (a mask of the stage's own bits), the
+// shortest and the longest key (pk_note_lengths, rfx_packed_words.h) and up to three 64-bit totals -- one small read-back for all of
+// them.  call_flags_init: zeros, min_len = 2^32 - 1.  call_flags_read: one one-thread launch (k_put_totals) copies *t0, *t1, *t2
+// (each may be nullptr: 0) into total[], then the read-back; everything queued before it has completed on return.
+struct CallFlags { uint32_t bad, min_len, max_len, pad; uint64_t total[3]; };
+int call_flags_init(rfx_ctx *ctx, DevBuf &flags);
+int call_flags_read(rfx_ctx *ctx, const DevBuf &flags, const uint64_t *d_t0, const uint64_t *d_t1, const uint64_t *d_t2, CallFlags *h);
+// host checks of the entry points and operators: a caller's output set has its arrays (n is the callee's to set) / an input set
+// has them and n >= 0 / text rows are (n >= 0, and pointers where n > 0) / an empty set in the library's own buffers / the
+// caller's partition starts -- P + 1 entries, 0 first, n last, never running backwards -- read back and checked BEFORE a kernel
+// indexes with them ("<stage>: partition starts that do not run from 0 to n")
+bool dyn_packed_out_ok(const rfx_dyn_packed *p);
+bool dyn_packed_ok(const rfx_dyn_packed *p);
+bool text_rows_ok(const char *text, const int64_t *row_off, int64_t n);
+int dyn_empty(rfx_ctx *ctx, DynDev &d);
+int check_part_starts(rfx_ctx *ctx, const int64_t *d_ps, int P, int64_t n, const char *stage_name);
 // sort("k-1") + the cut into P logical partitions: in -> out (sorted), d_ps[P + 1]; *lmin = the shortest key
 int dyn_sort(rfx_ctx *ctx, const DynDev &in, int P, DynDev &out, DevBuf &d_ps, uint32_t *lmin);
 // a view of the caller's input set (nothing copied, nothing freed) / the result into the caller's arrays (both capacities are

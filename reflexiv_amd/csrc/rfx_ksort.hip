@@ -27,104 +27,20 @@
 #include <string>
 #include <vector>
 #include "rfx_internal.h"
+#include "rfx_packed_words.h"
 
 using namespace rfx;
 
 namespace {
 
-#define KS_KW RFX_DYN_KEY_WORDS
-#define KS_GRID(n) dim3((unsigned)ceil_div(std::max<int64_t>((n), 1), 256)), dim3(256), 0, ctx->stream
-#define KS_CLAMP 30000
+#define KS_KW PK_KW
 
-// flags of a call, in HBM: [0] a malformed input, [1] the shortest key, [2] the longest key, [3] unused, [4..5] a 64-bit total
-struct KsFlags { uint32_t bad, min_len, max_len, pad; uint64_t total; };
+// what is wrong with a call's input (CallFlags::bad)
 enum { KS_BAD_OFFSETS = 1, KS_BAD_COMMA = 2, KS_BAD_COUNT = 4, KS_BAD_EXT = 8 };
-
-static int ks_flags_init(rfx_ctx *ctx, DevBuf &flags) {
-    RFX_HIP(flags.alloc(sizeof(KsFlags), ctx->stream));
-    RFX_HIP(hipMemsetAsync(flags.p, 0, sizeof(KsFlags), ctx->stream));
-    RFX_HIP(hipMemsetAsync((char *)flags.p + 4, 0xFF, 4, ctx->stream));
-    return RFX_OK;
-}
-__global__ void k_ks_put_total(const uint64_t *__restrict__ src, uint32_t *__restrict__ flags) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) ((uint64_t *)flags)[2] = *src;
-}
-static int ks_flags_read(rfx_ctx *ctx, const DevBuf &flags, const uint64_t *d_total, KsFlags *h) {
-    if (d_total) {
-        hipLaunchKernelGGL(k_ks_put_total, dim3(1), dim3(1), 0, ctx->stream, d_total, flags.as<uint32_t>());
-        RFX_HIP(hipGetLastError());
-    }
-    return small_readback(ctx, h, flags.p, sizeof(KsFlags));
-}
 
 struct KsParams { int k, M, E, max_cov; double F; };
 
-// ---- words ----------------------------------------------------------------------------------------------------------------------
-// the first m of 32 bases, the rest 0
-__device__ __forceinline__ uint64_t ks_keep(uint64_t x, int m) { return m >= 32 ? x : m <= 0 ? 0ull : x & ~(~0ull >> (2 * m)); }
-// the 32 two-bit groups of a word in reverse order
-__device__ __forceinline__ uint64_t ks_rev2(uint64_t x) {
-    x = ((x >> 2) & 0x3333333333333333ull) | ((x & 0x3333333333333333ull) << 2);
-    x = ((x >> 4) & 0x0F0F0F0F0F0F0F0Full) | ((x & 0x0F0F0F0F0F0F0F0Full) << 4);
-    x = ((x >> 8) & 0x00FF00FF00FF00FFull) | ((x & 0x00FF00FF00FF00FFull) << 8);
-    x = ((x >> 16) & 0x0000FFFF0000FFFFull) | ((x & 0x0000FFFF0000FFFFull) << 16);
-    return (x >> 32) | (x << 32);
-}
-struct Ks4 { uint64_t w0, w1, w2, w3; };
-__device__ __forceinline__ uint64_t ks_word(const Ks4 &a, int j) { return j == 0 ? a.w0 : j == 1 ? a.w1 : j == 2 ? a.w2 : j == 3 ? a.w3 : 0ull; }
-__device__ __forceinline__ void ks_or(Ks4 &a, int j, uint64_t v) {
-    a.w0 |= j == 0 ? v : 0ull; a.w1 |= j == 1 ? v : 0ull; a.w2 |= j == 2 ? v : 0ull; a.w3 |= j == 3 ? v : 0ull;
-}
-// base p (0..127) of four words / a base code at position p of a word set
-__device__ __forceinline__ uint64_t ks_base(const Ks4 &a, int p) { return (ks_word(a, p >> 5) >> (62 - 2 * (p & 31))) & 3ull; }
-__device__ __forceinline__ uint64_t ks_at(uint64_t code, int p) { return code << (62 - 2 * (p & 31)); }
-// the 128 bases moved s bases (0..127) towards the front, zeros behind
-__device__ __forceinline__ Ks4 ks_shl(const Ks4 &a, int s) {
-    const int ws = s >> 5, bs = (s & 31) * 2;
-    Ks4 r;
-    uint64_t lo;
-    lo = ks_word(a, ws + 1); r.w0 = (ks_word(a, ws) << bs) | (bs ? lo >> (64 - bs) : 0ull);
-    lo = ks_word(a, ws + 2); r.w1 = (ks_word(a, ws + 1) << bs) | (bs ? lo >> (64 - bs) : 0ull);
-    lo = ks_word(a, ws + 3); r.w2 = (ks_word(a, ws + 2) << bs) | (bs ? lo >> (64 - bs) : 0ull);
-    r.w3 = ks_word(a, ws + 3) << bs;
-    return r;
-}
-// the first len bases kept, everything behind them 0
-__device__ __forceinline__ Ks4 ks_keep4(const Ks4 &a, int len) {
-    return Ks4{ks_keep(a.w0, len), ks_keep(a.w1, len - 32), ks_keep(a.w2, len - 64), ks_keep(a.w3, len - 96)};
-}
-__device__ __forceinline__ Ks4 ks_load(const uint64_t *__restrict__ key, int64_t i) {
-    const uint64_t *p = key + KS_KW * i;
-    return Ks4{p[0], p[1], p[2], p[3]};
-}
-__device__ __forceinline__ void ks_store(uint64_t *__restrict__ key, int64_t i, const Ks4 &a) {
-    uint64_t *p = key + KS_KW * i;
-    p[0] = a.w0; p[1] = a.w1; p[2] = a.w2; p[3] = a.w3;
-}
-__device__ __forceinline__ void ks_note_lengths(uint32_t *__restrict__ flags, bool live, int len) {
-    uint32_t lo = live ? (uint32_t)len : 0xFFFFFFFFu, hi = live ? (uint32_t)len : 0u;
-    for (int d = 32; d > 0; d >>= 1) {
-        lo = min(lo, (uint32_t)__shfl_xor((int)lo, d, 64));
-        hi = max(hi, (uint32_t)__shfl_xor((int)hi, d, 64));
-    }
-    // one wave, one pair of atomics -- and only while they would still move the value: min and max are monotone, so a plain
-    // (possibly stale) read can only ask for an atomic too many.  With every wave of 9 million records hitting the two words, the
-    // unconditional form cost 3.3 ms a launch
-    if ((threadIdx.x & 63) == 0) {
-        const volatile uint32_t *f = flags;
-        if (lo < f[1]) atomicMin(flags + 1, lo);
-        if (hi > f[2]) atomicMax(flags + 2, hi);
-    }
-}
-// the largest i < n with off[i] <= x (off[0] = 0 <= x): the record that owns byte x; records of size 0 are skipped
-__device__ __forceinline__ int64_t ks_find(const uint64_t *__restrict__ off, int64_t n, int64_t x) {
-    int64_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)off[mid] <= x) lo = mid; else hi = mid;
-    }
-    return lo;
-}
+// (the word forms -- Pk4, pk_shl, pk_keep4, pk_rev2, pk_note_lengths, pk_find -- are rfx_packed_words.h's)
 
 // ---- steps 1-4: DynamicKmerBinarizer, the count filter, DSKmerReverseComplement, DSForwardSubKmerExtraction ---------------------
 // One thread per row.  The row ends ahead of its trailing newline; the first ',' cuts it; a leading '(' of the k-mer and a
@@ -132,7 +48,7 @@ __device__ __forceinline__ int64_t ks_find(const uint64_t *__restrict__ off, int
 // throws; a sign is refused too), 10 or more of them read as 1,000,000,000.  keep = the k-mer has k letters and count <= max_cov.
 __global__ __launch_bounds__(256) void k_ks_bin_sizes(const char *__restrict__ text, const int64_t *__restrict__ row_off, int64_t n, const KsParams prm,
                                                       uint32_t *__restrict__ keep, int64_t *__restrict__ kbeg, int32_t *__restrict__ cnt,
-                                                      uint32_t *__restrict__ flags) {
+                                                      CallFlags *__restrict__ flags) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     int64_t b = row_off[r], e = row_off[r + 1];
@@ -159,12 +75,12 @@ __global__ __launch_bounds__(256) void k_ks_bin_sizes(const char *__restrict__ t
         if (!digits) bad |= KS_BAD_COUNT;
         if (nd >= 10) v = 1000000000;
         kp = (c - kb == prm.k && v <= prm.max_cov) ? 1u : 0u;
-        cv = (int32_t)(v > KS_CLAMP ? KS_CLAMP : v);                 // buildingAlongFromThreeInt clamps what it stores
+        cv = pk_clamp((int32_t)v);                 // buildingAlongFromThreeInt clamps what it stores
         kbeg[r] = kb;
     }
     keep[r] = bad ? 0u : kp;
     cnt[r] = cv;
-    if (bad) atomicOr(flags, bad);
+    if (bad) atomicOr(&flags->bad, bad);
 }
 // One thread per row; a kept row writes records 2 s and 2 s + 1 (s = its rank among the kept rows): the k-mer's and then its
 // reverse complement's.  key = the first k - 1 bases, extension = base k - 1 at the top of one word, marker 1, left = right =
@@ -177,21 +93,21 @@ __global__ __launch_bounds__(256) void k_ks_bin_emit(const char *__restrict__ te
     if (r >= n || !keep[r]) return;
     const int k = prm.k;
     const char *s = text + kbeg[r];
-    Ks4 f{0, 0, 0, 0};
+    Pk4 f{0, 0, 0, 0};
     for (int j = 0; j < k; j++) {
         const char ch = s[j];
-        ks_or(f, j >> 5, ks_at((uint64_t)(ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : 3), j));
+        pk_or(f, j >> 5, pk_at(pk_code(ch), j));
     }
     // reverse complement: complement every base, reverse the 128 groups (the k-mer is then the LAST k), move it to the front
-    const Ks4 rv{ks_rev2(~f.w3), ks_rev2(~f.w2), ks_rev2(~f.w1), ks_rev2(~f.w0)};
-    const Ks4 rc = ks_keep4(ks_shl(rv, 128 - k), k);
+    const Pk4 rv{pk_rev2(~f.w3), pk_rev2(~f.w2), pk_rev2(~f.w1), pk_rev2(~f.w0)};
+    const Pk4 rc = pk_keep4(pk_shl(rv, 128 - k), k);
     const int32_t c = cnt[r];
     for (int h = 0; h < 2; h++) {
-        const Ks4 &w = h ? rc : f;
+        const Pk4 &w = h ? rc : f;
         const int64_t q = 2 * (int64_t)slot[r] + h;
-        ks_store(o.key, q, ks_keep4(w, k - 1));
+        pk_store(o.key, q, pk_keep4(w, k - 1));
         o.key_len[q] = (uint8_t)(k - 1);
-        o.ext[q] = ks_base(w, k - 1) << 62;
+        o.ext[q] = pk_base(w, k - 1) << 62;
         o.ext_off[q] = q;
         o.ext_len[q] = 1;
         o.marker[q] = 1; o.left[q] = c; o.right[q] = c;
@@ -200,7 +116,7 @@ __global__ __launch_bounds__(256) void k_ks_bin_emit(const char *__restrict__ te
 
 // ---- steps 5 and 7: the two folds over runs of equal keys -----------------------------------------------------------------------
 // head[i] = record i opens a run; the set's key lengths and "every extension is one base" go into the flags
-__global__ __launch_bounds__(256) void k_ks_heads(const DynView v, int64_t n, uint32_t *__restrict__ head, uint32_t *__restrict__ flags) {
+__global__ __launch_bounds__(256) void k_ks_heads(const DynView v, int64_t n, uint32_t *__restrict__ head, CallFlags *__restrict__ flags) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = i < n;
     int len = 0;
@@ -212,16 +128,16 @@ __global__ __launch_bounds__(256) void k_ks_heads(const DynView v, int64_t n, ui
             h = v.key_len[i - 1] != v.key_len[i] || x[0] != y[0] || x[1] != y[1] || x[2] != y[2] || x[3] != y[3];
         }
         head[i] = h ? 1u : 0u;
-        if (v.ext_len[i] != 1) atomicOr(flags, (uint32_t)KS_BAD_EXT);
+        if (v.ext_len[i] != 1) atomicOr(&flags->bad, (uint32_t)KS_BAD_EXT);
     }
-    ks_note_lengths(flags, live, len);
+    pk_note_lengths(&flags->min_len, &flags->max_len, live, len);
 }
 // lengths and extension lengths only (reflect, full k-mers): need_ext = every extension must be one base
-__global__ __launch_bounds__(256) void k_ks_lengths(const DynView v, int64_t n, uint32_t *__restrict__ flags) {
+__global__ __launch_bounds__(256) void k_ks_lengths(const DynView v, int64_t n, CallFlags *__restrict__ flags) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = i < n;
-    if (live && v.ext_len[i] != 1) atomicOr(flags, (uint32_t)KS_BAD_EXT);
-    ks_note_lengths(flags, live, live ? (int)v.key_len[i] : 0);
+    if (live && v.ext_len[i] != 1) atomicOr(&flags->bad, (uint32_t)KS_BAD_EXT);
+    pk_note_lengths(&flags->min_len, &flags->max_len, live, live ? (int)v.key_len[i] : 0);
 }
 // The thread at a run's head walks the run -- any length, across block edges -- and writes the survivor at the run's rank.
 // FORWARD (DSFilterForkSubKmerWithErrorCorrection): state (ext, left, right); extensions compare as signed longs of the block
@@ -254,7 +170,7 @@ __global__ __launch_bounds__(256) void k_ks_fold(const DynView v, int64_t n, con
         }
     }
     const int64_t q = (int64_t)rank[i];
-    ks_store(o.key, q, ks_load(v.key, i));
+    pk_store(o.key, q, pk_load(v.key, i));
     o.key_len[q] = v.key_len[i];
     o.ext[q] = (uint64_t)se << 62;
     o.ext_off[q] = q;
@@ -268,10 +184,10 @@ __global__ __launch_bounds__(256) void k_ks_reflect(const DynView v, int64_t n, 
     if (i == 0) o.ext_off[n] = n;
     if (i >= n) return;
     const int len = (int)v.key_len[i];
-    const Ks4 w = ks_load(v.key, i);
-    Ks4 r = ks_shl(w, 1);                                            // (the bits behind the last base are 0: so is base len - 1 now)
-    ks_or(r, (len - 1) >> 5, ks_at(v.ext[v.ext_off[i]] >> 62, len - 1));
-    ks_store(o.key, i, ks_keep4(r, len));
+    const Pk4 w = pk_load(v.key, i);
+    Pk4 r = pk_shl(w, 1);                                            // (the bits behind the last base are 0: so is base len - 1 now)
+    pk_or(r, (len - 1) >> 5, pk_at(v.ext[v.ext_off[i]] >> 62, len - 1));
+    pk_store(o.key, i, pk_keep4(r, len));
     o.key_len[i] = (uint8_t)len;
     o.ext[i] = w.w0 & (3ull << 62);
     o.ext_off[i] = i;
@@ -284,12 +200,12 @@ __global__ __launch_bounds__(256) void k_ks_full(const DynView v, int64_t n, con
     if (i == 0) o.ext_off[n] = 0;
     if (i >= n) return;
     const int len = (int)v.key_len[i];
-    const Ks4 w = ks_load(v.key, i);
+    const Pk4 w = pk_load(v.key, i);
     const uint64_t e = v.ext[v.ext_off[i]] >> 62;
-    Ks4 r;
-    if (v.marker[i] == 2) r = Ks4{(w.w0 >> 2) | (e << 62), (w.w1 >> 2) | (w.w0 << 62), (w.w2 >> 2) | (w.w1 << 62), (w.w3 >> 2) | (w.w2 << 62)};
-    else { r = w; ks_or(r, len >> 5, ks_at(e, len)); }
-    ks_store(o.key, i, ks_keep4(r, len + 1));
+    Pk4 r;
+    if (v.marker[i] == 2) r = Pk4{(w.w0 >> 2) | (e << 62), (w.w1 >> 2) | (w.w0 << 62), (w.w2 >> 2) | (w.w1 << 62), (w.w3 >> 2) | (w.w2 << 62)};
+    else { r = w; pk_or(r, len >> 5, pk_at(e, len)); }
+    pk_store(o.key, i, pk_keep4(r, len + 1));
     o.key_len[i] = (uint8_t)(len + 1);
     o.ext_off[i] = 0;
     o.ext_len[i] = 0;
@@ -297,26 +213,12 @@ __global__ __launch_bounds__(256) void k_ks_full(const DynView v, int64_t n, con
 }
 
 // ---- step 9: DSBinaryFullKmerArrayToString -- rows "KMER,marker|left|right\n" of the records whose key has k bases ----------------
-__device__ __forceinline__ int ks_int_chars(int v) {
-    int64_t a = v < 0 ? -(int64_t)v : (int64_t)v;
-    int c = v < 0 ? 2 : 1;
-    while (a >= 10) { a /= 10; c++; }
-    return c;
-}
-__device__ __forceinline__ char ks_int_char(int v, int q) {
-    if (v < 0) { if (q == 0) return '-'; q--; }
-    int64_t a = v < 0 ? -(int64_t)v : (int64_t)v;
-    int c = 1;
-    for (int64_t t = a; t >= 10; t /= 10) c++;
-    for (int s = c - 1 - q; s > 0; s--) a /= 10;
-    return (char)('0' + a % 10);
-}
 __global__ __launch_bounds__(256) void k_ks_text_sizes(const DynView v, int64_t n, int k, uint64_t *__restrict__ sz, uint32_t *__restrict__ keep) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const bool kp = (int)v.key_len[i] == k;
     keep[i] = kp ? 1u : 0u;
-    sz[i] = kp ? (uint64_t)(k + 4 + ks_int_chars(v.marker[i]) + ks_int_chars(v.left[i]) + ks_int_chars(v.right[i])) : 0ull;
+    sz[i] = kp ? (uint64_t)(k + 4 + pk_int_chars(v.marker[i]) + pk_int_chars(v.left[i]) + pk_int_chars(v.right[i])) : 0ull;
 }
 // the row offsets of the written rows: n_out + 1 entries
 __global__ __launch_bounds__(256) void k_ks_text_offsets(const uint32_t *__restrict__ keep, const uint64_t *__restrict__ rank, const uint64_t *__restrict__ toff,
@@ -329,17 +231,17 @@ __global__ __launch_bounds__(256) void k_ks_text_offsets(const uint32_t *__restr
 struct KsRow { int kl, m, l, r, cm, cl, cr; };
 __device__ __forceinline__ KsRow ks_row(const DynView &v, int64_t i) {
     const int m = v.marker[i], l = v.left[i], r = v.right[i];
-    return KsRow{(int)v.key_len[i], m, l, r, ks_int_chars(m), ks_int_chars(l), ks_int_chars(r)};
+    return KsRow{(int)v.key_len[i], m, l, r, pk_int_chars(m), pk_int_chars(l), pk_int_chars(r)};
 }
 __device__ __forceinline__ char ks_row_char(const DynView &v, int64_t i, const KsRow &w, int q) {
-    if (q < w.kl) return "ACGT"[(v.key[KS_KW * i + (q >> 5)] >> (62 - 2 * (q & 31))) & 3];
+    if (q < w.kl) return (char)pk_letter(pk_base_of(v.key + KS_KW * i, q));
     q -= w.kl;
     if (q == 0) return ',';
-    if (q < 1 + w.cm) return ks_int_char(w.m, q - 1);
+    if (q < 1 + w.cm) return pk_int_char(w.m, q - 1);
     if (q == 1 + w.cm) return '|';
-    if (q < 2 + w.cm + w.cl) return ks_int_char(w.l, q - 2 - w.cm);
+    if (q < 2 + w.cm + w.cl) return pk_int_char(w.l, q - 2 - w.cm);
     if (q == 2 + w.cm + w.cl) return '|';
-    if (q < 3 + w.cm + w.cl + w.cr) return ks_int_char(w.r, q - 3 - w.cm - w.cl);
+    if (q < 3 + w.cm + w.cl + w.cr) return pk_int_char(w.r, q - 3 - w.cm - w.cl);
     return '\n';
 }
 // one thread per chunk of 8 output bytes, up to lim (the smaller of the text's length and the buffer): one search for the row
@@ -349,7 +251,7 @@ __global__ __launch_bounds__(256) void k_ks_text_fill(const DynView v, int64_t n
     const int64_t b0 = 8 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
     if (b0 >= lim) return;
     const int cnt = lim - b0 < 8 ? (int)(lim - b0) : 8;
-    int64_t i = ks_find(toff, n, b0), beg = (int64_t)toff[i], end = (int64_t)toff[i + 1];
+    int64_t i = pk_find(toff, n, b0), beg = (int64_t)toff[i], end = (int64_t)toff[i + 1];
     KsRow w = ks_row(v, i);
     uint64_t pack = 0;
     for (int j = 0; j < 8; j++) {
@@ -372,17 +274,8 @@ static int ks_params(rfx_ctx *ctx, const rfx_ksort_params *p, KsParams *o) {
     if (!ks_k_ok(p->k)) { ctx->last_error = "k-mer sorting: k outside 8..124 or (k - 1) % 31 == 0 (32, 63, 94: the reference's classes are broken there)"; return RFX_E_ARG; }
     if (p->min_error_cov <= 0) { ctx->last_error = "k-mer sorting: min_error_cov <= 0 (the reference's classes without error correction cannot run)"; return RFX_E_ARG; }
     if (!(p->min_repeat_fold >= 1.0) || !std::isfinite(p->min_repeat_fold)) { ctx->last_error = "k-mer sorting: min_repeat_fold < 1"; return RFX_E_ARG; }
-    if (p->max_k < 1 || p->max_k + 3 > KS_CLAMP || p->max_cov < 0) { ctx->last_error = "k-mer sorting: max_k or max_cov out of range"; return RFX_E_ARG; }
+    if (p->max_k < 1 || p->max_k + 3 > PK_CLAMP || p->max_cov < 0) { ctx->last_error = "k-mer sorting: max_k or max_cov out of range"; return RFX_E_ARG; }
     *o = KsParams{p->k, p->max_k + 3, p->min_error_cov, p->max_cov, p->min_repeat_fold};
-    return RFX_OK;
-}
-static bool ks_out_ok(const rfx_dyn_packed *p) {
-    return p && p->key && p->key_len && p->ext && p->ext_off && p->ext_len && p->marker && p->left && p->right;
-}
-static bool ks_in_ok(const rfx_dyn_packed *p) { return ks_out_ok(p) && p->n >= 0; }
-static int ks_empty(rfx_ctx *ctx, DynDev &d) {
-    RFX_TRY(dyn_alloc(ctx, d, 0, 0));
-    RFX_HIP(hipMemsetAsync(d.ext_off.p, 0, 8, ctx->stream));
     return RFX_OK;
 }
 static int ks_bad(rfx_ctx *ctx, uint32_t bad) {
@@ -395,29 +288,29 @@ static int ks_bad(rfx_ctx *ctx, uint32_t bad) {
 
 // steps 1-4: text in HBM -> a packed set in the library's own buffers
 static int ks_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, const KsParams &prm, DynDev &d) {
-    if (n == 0) return ks_empty(ctx, d);
+    if (n == 0) return dyn_empty(ctx, d);
     if (n >= ((int64_t)1 << 31)) { ctx->last_error = "k-mer sorting: 2^31 rows or more"; return RFX_E_LIMIT; }
     DevBuf keep, slot, kbeg, cnt, flags;
     RFX_HIP(keep.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(slot.alloc((size_t)(n + 1) * 8, ctx->stream));
     RFX_HIP(kbeg.alloc((size_t)n * 8, ctx->stream)); RFX_HIP(cnt.alloc((size_t)n * 4, ctx->stream));
-    RFX_TRY(ks_flags_init(ctx, flags));
-    hipLaunchKernelGGL(k_ks_bin_sizes, KS_GRID(n), d_text, d_row_off, n, prm, keep.as<uint32_t>(), kbeg.as<int64_t>(), cnt.as<int32_t>(), flags.as<uint32_t>());
+    RFX_TRY(call_flags_init(ctx, flags));
+    hipLaunchKernelGGL(k_ks_bin_sizes, RFX_GRID(n), d_text, d_row_off, n, prm, keep.as<uint32_t>(), kbeg.as<int64_t>(), cnt.as<int32_t>(), flags.as<CallFlags>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, keep.as<uint32_t>(), slot.as<uint64_t>(), n));
-    KsFlags f{};
-    RFX_TRY(ks_flags_read(ctx, flags, slot.as<uint64_t>() + n, &f));
+    CallFlags f{};
+    RFX_TRY(call_flags_read(ctx, flags, slot.as<uint64_t>() + n, nullptr, nullptr, &f));
     if (f.bad) return ks_bad(ctx, f.bad);
-    const int64_t n_out = 2 * (int64_t)f.total;
-    if (n_out == 0) return ks_empty(ctx, d);
+    const int64_t n_out = 2 * (int64_t)f.total[0];
+    if (n_out == 0) return dyn_empty(ctx, d);
     RFX_TRY(dyn_alloc(ctx, d, n_out, n_out));
-    hipLaunchKernelGGL(k_ks_bin_emit, KS_GRID(n), d_text, n, prm, (const uint32_t *)keep.as<uint32_t>(), (const uint64_t *)slot.as<uint64_t>(),
+    hipLaunchKernelGGL(k_ks_bin_emit, RFX_GRID(n), d_text, n, prm, (const uint32_t *)keep.as<uint32_t>(), (const uint64_t *)slot.as<uint64_t>(),
                        (const int64_t *)kbeg.as<int64_t>(), (const int32_t *)cnt.as<int32_t>(), n_out, dyn_out(d));
     RFX_HIP(hipGetLastError());
     return RFX_OK;
 }
 
 // what an operator asks of its input: every extension one base; one_len: keys all of one length; max_len: the longest key allowed
-static int ks_check(rfx_ctx *ctx, const KsFlags &f, bool one_len, int max_len) {
+static int ks_check(rfx_ctx *ctx, const CallFlags &f, bool one_len, int max_len) {
     if (f.bad) return ks_bad(ctx, f.bad);
     if (one_len && f.min_len != f.max_len) { ctx->last_error = "k-mer sorting: keys of more than one length"; return RFX_E_ARG; }
     if (f.min_len < 1 || (int)f.max_len > max_len) { ctx->last_error = "k-mer sorting: a key of 0 bases or too long"; return RFX_E_ARG; }
@@ -427,21 +320,21 @@ static int ks_check(rfx_ctx *ctx, const KsFlags &f, bool one_len, int max_len) {
 // one fold over a sorted set
 static int ks_fold(rfx_ctx *ctx, bool reflected, const DynDev &in, const KsParams &prm, DynDev &out) {
     const int64_t n = in.n;
-    if (n == 0) return ks_empty(ctx, out);
+    if (n == 0) return dyn_empty(ctx, out);
     DevBuf head, rank, flags;
     RFX_HIP(head.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(rank.alloc((size_t)(n + 1) * 8, ctx->stream));
-    RFX_TRY(ks_flags_init(ctx, flags));
+    RFX_TRY(call_flags_init(ctx, flags));
     const DynView v = dyn_view(in);
-    hipLaunchKernelGGL(k_ks_heads, KS_GRID(n), v, n, head.as<uint32_t>(), flags.as<uint32_t>());
+    hipLaunchKernelGGL(k_ks_heads, RFX_GRID(n), v, n, head.as<uint32_t>(), flags.as<CallFlags>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, head.as<uint32_t>(), rank.as<uint64_t>(), n));
-    KsFlags f{};
-    RFX_TRY(ks_flags_read(ctx, flags, rank.as<uint64_t>() + n, &f));
+    CallFlags f{};
+    RFX_TRY(call_flags_read(ctx, flags, rank.as<uint64_t>() + n, nullptr, nullptr, &f));
     RFX_TRY(ks_check(ctx, f, true, 124));
-    const int64_t ns = (int64_t)f.total;
+    const int64_t ns = (int64_t)f.total[0];
     RFX_TRY(dyn_alloc(ctx, out, ns, ns));
-    if (reflected) hipLaunchKernelGGL(k_ks_fold<true>, KS_GRID(n), v, n, (const uint32_t *)head.as<uint32_t>(), (const uint64_t *)rank.as<uint64_t>(), prm, dyn_out(out));
-    else hipLaunchKernelGGL(k_ks_fold<false>, KS_GRID(n), v, n, (const uint32_t *)head.as<uint32_t>(), (const uint64_t *)rank.as<uint64_t>(), prm, dyn_out(out));
+    if (reflected) hipLaunchKernelGGL(k_ks_fold<true>, RFX_GRID(n), v, n, (const uint32_t *)head.as<uint32_t>(), (const uint64_t *)rank.as<uint64_t>(), prm, dyn_out(out));
+    else hipLaunchKernelGGL(k_ks_fold<false>, RFX_GRID(n), v, n, (const uint32_t *)head.as<uint32_t>(), (const uint64_t *)rank.as<uint64_t>(), prm, dyn_out(out));
     RFX_HIP(hipGetLastError());
     return RFX_OK;
 }
@@ -449,18 +342,18 @@ static int ks_fold(rfx_ctx *ctx, bool reflected, const DynDev &in, const KsParam
 // step 6 (full == false) / step 8 (full == true)
 static int ks_map(rfx_ctx *ctx, bool full, const DynDev &in, DynDev &out) {
     const int64_t n = in.n;
-    if (n == 0) return ks_empty(ctx, out);
+    if (n == 0) return dyn_empty(ctx, out);
     DevBuf flags;
-    RFX_TRY(ks_flags_init(ctx, flags));
+    RFX_TRY(call_flags_init(ctx, flags));
     const DynView v = dyn_view(in);
-    hipLaunchKernelGGL(k_ks_lengths, KS_GRID(n), v, n, flags.as<uint32_t>());
+    hipLaunchKernelGGL(k_ks_lengths, RFX_GRID(n), v, n, flags.as<CallFlags>());
     RFX_HIP(hipGetLastError());
-    KsFlags f{};
-    RFX_TRY(ks_flags_read(ctx, flags, nullptr, &f));
+    CallFlags f{};
+    RFX_TRY(call_flags_read(ctx, flags, nullptr, nullptr, nullptr, &f));
     RFX_TRY(ks_check(ctx, f, !full, full ? 123 : 124));
     RFX_TRY(dyn_alloc(ctx, out, n, full ? 0 : n));
-    if (full) hipLaunchKernelGGL(k_ks_full, KS_GRID(n), v, n, dyn_out(out));
-    else hipLaunchKernelGGL(k_ks_reflect, KS_GRID(n), v, n, dyn_out(out));
+    if (full) hipLaunchKernelGGL(k_ks_full, RFX_GRID(n), v, n, dyn_out(out));
+    else hipLaunchKernelGGL(k_ks_reflect, RFX_GRID(n), v, n, dyn_out(out));
     RFX_HIP(hipGetLastError());
     return RFX_OK;
 }
@@ -495,7 +388,7 @@ static int ks_to_text(rfx_ctx *ctx, const DynDev &d, int k, char *d_text, int64_
     RFX_HIP(sz.alloc((size_t)n * 8, ctx->stream)); RFX_HIP(toff.alloc((size_t)(n + 1) * 8, ctx->stream));
     RFX_HIP(keep.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(rank.alloc((size_t)(n + 1) * 8, ctx->stream));
     const DynView v = dyn_view(d);
-    hipLaunchKernelGGL(k_ks_text_sizes, KS_GRID(n), v, n, k, sz.as<uint64_t>(), keep.as<uint32_t>());
+    hipLaunchKernelGGL(k_ks_text_sizes, RFX_GRID(n), v, n, k, sz.as<uint64_t>(), keep.as<uint32_t>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u64(ctx, sz.as<uint64_t>(), toff.as<uint64_t>(), n));
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, keep.as<uint32_t>(), rank.as<uint64_t>(), n));
@@ -508,13 +401,13 @@ static int ks_to_text(rfx_ctx *ctx, const DynDev &d, int k, char *d_text, int64_
         d_text = own->as<char>(); cap = *total;
     }
     if (d_row_off) {
-        hipLaunchKernelGGL(k_ks_text_offsets, KS_GRID(n), (const uint32_t *)keep.as<uint32_t>(), (const uint64_t *)rank.as<uint64_t>(),
+        hipLaunchKernelGGL(k_ks_text_offsets, RFX_GRID(n), (const uint32_t *)keep.as<uint32_t>(), (const uint64_t *)rank.as<uint64_t>(),
                            (const uint64_t *)toff.as<uint64_t>(), n, d_row_off);
         RFX_HIP(hipGetLastError());
     }
     const int64_t lim = std::min<int64_t>(*total, cap);
     if (lim > 0) {
-        hipLaunchKernelGGL(k_ks_text_fill, KS_GRID(ceil_div(lim, 8)), v, n, (const uint64_t *)toff.as<uint64_t>(), lim, d_text);
+        hipLaunchKernelGGL(k_ks_text_fill, RFX_GRID(ceil_div(lim, 8)), v, n, (const uint64_t *)toff.as<uint64_t>(), lim, d_text);
         RFX_HIP(hipGetLastError());
     }
     return sync_checked(ctx);
@@ -537,7 +430,7 @@ void rfx_ksort_default_params(rfx_ksort_params *p, int k) try {
 
 int rfx_dev_ksort_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, const rfx_ksort_params *params,
                            rfx_dyn_packed *d_out) try {
-    if (!ctx || !ks_out_ok(d_out) || n_rows < 0 || (n_rows > 0 && (!d_text || !d_row_off))) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_out_ok(d_out) || n_rows < 0 || (n_rows > 0 && (!d_text || !d_row_off))) return RFX_E_ARG;
     KsParams prm;
     RFX_TRY(ks_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -548,7 +441,7 @@ int rfx_dev_ksort_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_ro
 
 int rfx_dev_ksort_fork_filter(rfx_ctx *ctx, int reflected, const rfx_dyn_packed *d_sorted, const rfx_ksort_params *params,
                               rfx_dyn_packed *d_out) try {
-    if (!ctx || !ks_in_ok(d_sorted) || !ks_out_ok(d_out) || (reflected != 0 && reflected != 1)) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_ok(d_sorted) || !dyn_packed_out_ok(d_out) || (reflected != 0 && reflected != 1)) return RFX_E_ARG;
     KsParams prm;
     RFX_TRY(ks_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -559,7 +452,7 @@ int rfx_dev_ksort_fork_filter(rfx_ctx *ctx, int reflected, const rfx_dyn_packed 
 } RFX_API_CATCH(ctx)
 
 int rfx_dev_ksort_reflect(rfx_ctx *ctx, const rfx_dyn_packed *d_in, rfx_dyn_packed *d_out) try {
-    if (!ctx || !ks_in_ok(d_in) || !ks_out_ok(d_out)) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out)) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a, b;
     RFX_TRY(dyn_borrow(ctx, d_in, a));
@@ -568,7 +461,7 @@ int rfx_dev_ksort_reflect(rfx_ctx *ctx, const rfx_dyn_packed *d_in, rfx_dyn_pack
 } RFX_API_CATCH(ctx)
 
 int rfx_dev_ksort_full_kmers(rfx_ctx *ctx, const rfx_dyn_packed *d_in, rfx_dyn_packed *d_out) try {
-    if (!ctx || !ks_in_ok(d_in) || !ks_out_ok(d_out)) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out)) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a, b;
     RFX_TRY(dyn_borrow(ctx, d_in, a));
@@ -578,7 +471,7 @@ int rfx_dev_ksort_full_kmers(rfx_ctx *ctx, const rfx_dyn_packed *d_in, rfx_dyn_p
 
 int rfx_dev_ksort_to_text(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int k, char *d_text, int64_t cap, int64_t *out_len, int64_t *d_row_off,
                           int64_t *n_out) try {
-    if (!ctx || !ks_in_ok(d_in) || !out_len || !n_out || cap < 0 || (cap > 0 && !d_text) || k < 1 || k > 124) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_ok(d_in) || !out_len || !n_out || cap < 0 || (cap > 0 && !d_text) || k < 1 || k > 124) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a;
     int64_t total = 0, rows = 0;
@@ -590,7 +483,7 @@ int rfx_dev_ksort_to_text(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int k, char 
 
 int rfx_dev_ksort_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, const rfx_ksort_params *params,
                       rfx_dyn_packed *d_out) try {
-    if (!ctx || !ks_out_ok(d_out) || n_rows < 0 || (n_rows > 0 && (!d_text || !d_row_off))) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_out_ok(d_out) || n_rows < 0 || (n_rows > 0 && (!d_text || !d_row_off))) return RFX_E_ARG;
     KsParams prm;
     RFX_TRY(ks_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));

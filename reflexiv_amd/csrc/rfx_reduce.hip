@@ -33,91 +33,24 @@
 #include <string>
 #include <vector>
 #include "rfx_internal.h"
+#include "rfx_packed_words.h"
 #include "rfx_reduce_fsm.h"
 
 using namespace rfx;
 
 namespace {
 
-#define RD_KW RFX_DYN_KEY_WORDS
-#define RD_GRID(n) dim3((unsigned)ceil_div(std::max<int64_t>((n), 1), 256)), dim3(256), 0, ctx->stream
-#define RD_CLAMP 30000
+#define RD_KW PK_KW
 
-// flags of a call, in HBM: [0] what is wrong with the input, [1] unused, [2..3] a 64-bit total
-struct RdFlags { uint32_t bad, pad; uint64_t total; };
+// what is wrong with a call's input (CallFlags::bad)
 enum { RD_BAD_OFFSETS = 1, RD_BAD_COMMA = 2, RD_BAD_LEN = 4, RD_BAD_EXT = 8 };
 // a row's word of the window pass: bit 0 the row opens a partition, bit 1 it ends one, bits 8..16 the nine bits of
 // rfx_reduce_fsm.h for rows i - 2, i - 1, i, bits 20..21 the state ahead of the row
 enum { RD_START = 1, RD_END = 2, RD_IN_SHIFT = 8, RD_STATE_SHIFT = 20 };
 
-static int rd_flags_init(rfx_ctx *ctx, DevBuf &flags) {
-    RFX_HIP(flags.alloc(sizeof(RdFlags), ctx->stream));
-    RFX_HIP(hipMemsetAsync(flags.p, 0, sizeof(RdFlags), ctx->stream));
-    return RFX_OK;
-}
-__global__ void k_rd_put_total(const uint64_t *__restrict__ src, uint32_t *__restrict__ flags) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) ((uint64_t *)flags)[1] = *src;
-}
-static int rd_flags_read(rfx_ctx *ctx, const DevBuf &flags, const uint64_t *d_total, RdFlags *h) {
-    if (d_total) {
-        hipLaunchKernelGGL(k_rd_put_total, dim3(1), dim3(1), 0, ctx->stream, d_total, flags.as<uint32_t>());
-        RFX_HIP(hipGetLastError());
-    }
-    return small_readback(ctx, h, flags.p, sizeof(RdFlags));
-}
-
 struct RdParams { int k1, k2; };
 
-// ---- words (rfx_ksort.hip's forms: four named registers, never an indexed array) ---------------------------------------------------
-__device__ __forceinline__ uint64_t rd_keep(uint64_t x, int m) { return m >= 32 ? x : m <= 0 ? 0ull : x & ~(~0ull >> (2 * m)); }
-__device__ __forceinline__ uint64_t rd_rev2(uint64_t x) {
-    x = ((x >> 2) & 0x3333333333333333ull) | ((x & 0x3333333333333333ull) << 2);
-    x = ((x >> 4) & 0x0F0F0F0F0F0F0F0Full) | ((x & 0x0F0F0F0F0F0F0F0Full) << 4);
-    x = ((x >> 8) & 0x00FF00FF00FF00FFull) | ((x & 0x00FF00FF00FF00FFull) << 8);
-    x = ((x >> 16) & 0x0000FFFF0000FFFFull) | ((x & 0x0000FFFF0000FFFFull) << 16);
-    return (x >> 32) | (x << 32);
-}
-struct Rd4 { uint64_t w0, w1, w2, w3; };
-__device__ __forceinline__ uint64_t rd_word(const Rd4 &a, int j) { return j == 0 ? a.w0 : j == 1 ? a.w1 : j == 2 ? a.w2 : j == 3 ? a.w3 : 0ull; }
-__device__ __forceinline__ void rd_or(Rd4 &a, int j, uint64_t v) {
-    a.w0 |= j == 0 ? v : 0ull; a.w1 |= j == 1 ? v : 0ull; a.w2 |= j == 2 ? v : 0ull; a.w3 |= j == 3 ? v : 0ull;
-}
-__device__ __forceinline__ uint64_t rd_base(const Rd4 &a, int p) { return (rd_word(a, p >> 5) >> (62 - 2 * (p & 31))) & 3ull; }
-__device__ __forceinline__ uint64_t rd_at(uint64_t code, int p) { return code << (62 - 2 * (p & 31)); }
-// the 128 bases moved s bases (0..127) towards the front, zeros behind
-__device__ __forceinline__ Rd4 rd_shl(const Rd4 &a, int s) {
-    const int ws = s >> 5, bs = (s & 31) * 2;
-    Rd4 r;
-    uint64_t lo;
-    lo = rd_word(a, ws + 1); r.w0 = (rd_word(a, ws) << bs) | (bs ? lo >> (64 - bs) : 0ull);
-    lo = rd_word(a, ws + 2); r.w1 = (rd_word(a, ws + 1) << bs) | (bs ? lo >> (64 - bs) : 0ull);
-    lo = rd_word(a, ws + 3); r.w2 = (rd_word(a, ws + 2) << bs) | (bs ? lo >> (64 - bs) : 0ull);
-    r.w3 = rd_word(a, ws + 3) << bs;
-    return r;
-}
-__device__ __forceinline__ Rd4 rd_keep4(const Rd4 &a, int len) {
-    return Rd4{rd_keep(a.w0, len), rd_keep(a.w1, len - 32), rd_keep(a.w2, len - 64), rd_keep(a.w3, len - 96)};
-}
-// the first len (0..128) bases in reverse order at the front, zeros behind: reverse all 128 groups (the bases are then the LAST
-// len), move them to the front
-__device__ __forceinline__ Rd4 rd_reverse(const Rd4 &a, int len) {
-    const Rd4 rv{rd_rev2(a.w3), rd_rev2(a.w2), rd_rev2(a.w1), rd_rev2(a.w0)};
-    return len <= 0 ? Rd4{0, 0, 0, 0} : rd_keep4(rd_shl(rv, 128 - len), len);
-}
-__device__ __forceinline__ Rd4 rd_load(const uint64_t *__restrict__ key, int64_t i) {
-    const uint64_t *p = key + RD_KW * i;
-    return Rd4{p[0], p[1], p[2], p[3]};
-}
-__device__ __forceinline__ void rd_store(uint64_t *__restrict__ key, int64_t i, const Rd4 &a) {
-    uint64_t *p = key + RD_KW * i;
-    p[0] = a.w0; p[1] = a.w1; p[2] = a.w2; p[3] = a.w3;
-}
-// dynamicSubKmerComparator: the shorter key is a prefix of the longer one (the padding is 0 on both sides)
-__device__ __forceinline__ bool rd_prefix(const Rd4 &x, int lx, const Rd4 &y, int ly) {
-    const int m = lx < ly ? lx : ly;
-    const Rd4 a = rd_keep4(x, m), b = rd_keep4(y, m);
-    return a.w0 == b.w0 && a.w1 == b.w1 && a.w2 == b.w2 && a.w3 == b.w3;
-}
+// (the word forms -- Pk4, pk_reverse, pk_prefix, pk_shl, pk_keep4 -- are rfx_packed_words.h's)
 // the partition of row i: the largest p < P with ps[p] <= i (ps[0] = 0); its rows are [ps[p], ps[p + 1])
 __device__ __forceinline__ int rd_part_of(const int64_t *__restrict__ ps, int P, int64_t i) {
     int lo = 0, hi = P;
@@ -131,17 +64,9 @@ __device__ __forceinline__ int rd_part_of(const int64_t *__restrict__ ps, int P,
 // ---- step 1: DynamicKmerBinarizerFromSorted, and the union ----------------------------------------------------------------------------
 // One thread per row "KMER,marker|left|right": the row ends ahead of its newline, the first ',' cuts it, a leading '(' of the k-mer
 // and a trailing ')' of the attribute are dropped; keep = the k-mer has k1 or k2 letters; left / right clamped to +-30000.
-__device__ __forceinline__ int rd_parse_int(const char *__restrict__ t, int64_t &i, int64_t e) {
-    bool neg = false;
-    if (i < e && (t[i] == '-' || t[i] == '+')) { neg = t[i] == '-'; i++; }
-    long long v = 0;
-    while (i < e && t[i] >= '0' && t[i] <= '9') { if (v < 100000000LL) v = v * 10 + (t[i] - '0'); i++; }
-    if (i < e && t[i] == '|') i++;
-    return (int)(neg ? -v : v);
-}
 __global__ __launch_bounds__(256) void k_rd_bin_sizes(const char *__restrict__ text, const int64_t *__restrict__ row_off, int64_t n, const RdParams prm,
                                                       uint32_t *__restrict__ keep, int64_t *__restrict__ kbeg, int32_t *__restrict__ mlr,
-                                                      uint32_t *__restrict__ flags) {
+                                                      CallFlags *__restrict__ flags) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     int64_t b = row_off[r], e = row_off[r + 1];
@@ -157,15 +82,15 @@ __global__ __launch_bounds__(256) void k_rd_bin_sizes(const char *__restrict__ t
         if (kb < c && text[kb] == '(') kb++;
         if (ae > c + 1 && text[ae - 1] == ')') ae--;
         int64_t i = c + 1;
-        const int m = rd_parse_int(text, i, ae), l = rd_parse_int(text, i, ae), rr = rd_parse_int(text, i, ae);
+        const int m = pk_parse_int(text, i, ae), l = pk_parse_int(text, i, ae), rr = pk_parse_int(text, i, ae);
         mlr[3 * r] = m;
-        mlr[3 * r + 1] = l < -RD_CLAMP ? -RD_CLAMP : l > RD_CLAMP ? RD_CLAMP : l;
-        mlr[3 * r + 2] = rr < -RD_CLAMP ? -RD_CLAMP : rr > RD_CLAMP ? RD_CLAMP : rr;
+        mlr[3 * r + 1] = pk_clamp(l);
+        mlr[3 * r + 2] = pk_clamp(rr);
         kp = (c - kb == prm.k1 || c - kb == prm.k2) ? 1u : 0u;
         kbeg[r] = kb;
         keep[r] = (uint32_t)(kp ? c - kb : 0);                          // (the length of a kept row, 0 of a dropped one)
     }
-    if (bad) { keep[r] = 0; atomicOr(flags, bad); }
+    if (bad) { keep[r] = 0; atomicOr(&flags->bad, bad); }
 }
 __global__ __launch_bounds__(256) void k_rd_bin_flag(const uint32_t *__restrict__ len, int64_t n, uint32_t *__restrict__ keep) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -179,13 +104,13 @@ __global__ __launch_bounds__(256) void k_rd_bin_emit(const char *__restrict__ te
     if (r >= n || !len[r]) return;
     const int k = (int)len[r];
     const char *s = text + kbeg[r];
-    Rd4 f{0, 0, 0, 0};
+    Pk4 f{0, 0, 0, 0};
     for (int j = 0; j < k; j++) {
         const char ch = s[j];
-        rd_or(f, j >> 5, rd_at((uint64_t)(ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : 3), j));
+        pk_or(f, j >> 5, pk_at(pk_code(ch), j));
     }
     const int64_t q = base + (int64_t)slot[r];
-    rd_store(o.key, q, f);
+    pk_store(o.key, q, f);
     o.key_len[q] = (uint8_t)k;
     o.ext_off[q] = 0;
     o.ext_len[q] = 0;
@@ -193,13 +118,13 @@ __global__ __launch_bounds__(256) void k_rd_bin_emit(const char *__restrict__ te
 }
 
 // ---- what an operator asks of its input: keys of la or lb bases, every extension of ext_len bases ------------------------------------
-__global__ __launch_bounds__(256) void k_rd_check(const DynView v, int64_t n, int la, int lb, int ext_len, uint32_t *__restrict__ flags) {
+__global__ __launch_bounds__(256) void k_rd_check(const DynView v, int64_t n, int la, int lb, int ext_len, CallFlags *__restrict__ flags) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int len = (int)v.key_len[i];
     uint32_t bad = (len != la && len != lb) ? (uint32_t)RD_BAD_LEN : 0u;
     if (v.ext_len[i] != ext_len) bad |= RD_BAD_EXT;
-    if (bad) atomicOr(flags, bad);
+    if (bad) atomicOr(&flags->bad, bad);
 }
 
 // ---- step 3: LeftLongerToShorterComparisonPreparation -- key' = the first len - 1 bases REVERSED, extension' = the last base, marker 1
@@ -208,10 +133,10 @@ __global__ __launch_bounds__(256) void k_rd_left_prep(const DynView v, int64_t n
     if (i == 0) o.ext_off[n] = n;
     if (i >= n) return;
     const int len = (int)v.key_len[i];
-    const Rd4 w = rd_load(v.key, i);
-    rd_store(o.key, i, rd_reverse(w, len - 1));
+    const Pk4 w = pk_load(v.key, i);
+    pk_store(o.key, i, pk_reverse(w, len - 1));
     o.key_len[i] = (uint8_t)(len - 1);
-    o.ext[i] = rd_base(w, len - 1) << 62;
+    o.ext[i] = pk_base(w, len - 1) << 62;
     o.ext_off[i] = i;
     o.ext_len[i] = 1;
     o.marker[i] = 1; o.left[i] = v.left[i]; o.right[i] = v.right[i];
@@ -223,12 +148,12 @@ __global__ __launch_bounds__(256) void k_rd_right_prep(const DynView v, int64_t 
     if (i == 0) o.ext_off[n] = n;
     if (i >= n) return;
     const int len = (int)v.key_len[i];
-    const Rd4 w = rd_reverse(rd_load(v.key, i), len);
+    const Pk4 w = pk_reverse(pk_load(v.key, i), len);
     const uint64_t e = v.ext[v.ext_off[i]] >> 62;
-    Rd4 c;                                                           // len + 1 <= 125 bases
-    if (v.marker[i] == 1) { c = w; rd_or(c, len >> 5, rd_at(e, len)); }
-    else c = Rd4{(w.w0 >> 2) | (e << 62), (w.w1 >> 2) | (w.w0 << 62), (w.w2 >> 2) | (w.w1 << 62), (w.w3 >> 2) | (w.w2 << 62)};
-    rd_store(o.key, i, rd_keep4(rd_shl(c, 1), len));
+    Pk4 c;                                                           // len + 1 <= 125 bases
+    if (v.marker[i] == 1) { c = w; pk_or(c, len >> 5, pk_at(e, len)); }
+    else c = Pk4{(w.w0 >> 2) | (e << 62), (w.w1 >> 2) | (w.w0 << 62), (w.w2 >> 2) | (w.w1 << 62), (w.w3 >> 2) | (w.w2 << 62)};
+    pk_store(o.key, i, pk_keep4(pk_shl(c, 1), len));
     o.key_len[i] = (uint8_t)len;
     o.ext[i] = c.w0 & (3ull << 62);
     o.ext_off[i] = i;
@@ -250,19 +175,19 @@ __global__ __launch_bounds__(256) void k_rd_window(const DynView v, int64_t n, i
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int lc = (int)v.key_len[i];
-    const Rd4 c = rd_load(v.key, i);
+    const Pk4 c = pk_load(v.key, i);
     const uint64_t ec = v.ext[v.ext_off[i]] >> 62;
     unsigned in = lc == short_len ? RFX_FSM_SC : 0;
     if (i >= 1) {
         const int lb = (int)v.key_len[i - 1];
-        const Rd4 b = rd_load(v.key, i - 1);
+        const Pk4 b = pk_load(v.key, i - 1);
         const uint64_t eb = v.ext[v.ext_off[i - 1]] >> 62;
-        in |= (lb == short_len ? RFX_FSM_SB : 0) | (rd_prefix(b, lb, c, lc) ? RFX_FSM_PBC : 0) | (eb == ec ? RFX_FSM_EBC : 0);
+        in |= (lb == short_len ? RFX_FSM_SB : 0) | (pk_prefix(b, lb, c, lc) ? RFX_FSM_PBC : 0) | (eb == ec ? RFX_FSM_EBC : 0);
         if (i >= 2) {
             const int la = (int)v.key_len[i - 2];
-            const Rd4 a = rd_load(v.key, i - 2);
+            const Pk4 a = pk_load(v.key, i - 2);
             const uint64_t ea = v.ext[v.ext_off[i - 2]] >> 62;
-            in |= (la == short_len ? RFX_FSM_SA : 0) | (rd_prefix(a, la, b, lb) ? RFX_FSM_PAB : 0) | (rd_prefix(a, la, c, lc) ? RFX_FSM_PAC : 0) |
+            in |= (la == short_len ? RFX_FSM_SA : 0) | (pk_prefix(a, la, b, lb) ? RFX_FSM_PAB : 0) | (pk_prefix(a, la, c, lc) ? RFX_FSM_PAC : 0) |
                   (ea == eb ? RFX_FSM_EAB : 0) | (ea == ec ? RFX_FSM_EAC : 0);
         }
     }
@@ -338,7 +263,7 @@ __global__ __launch_bounds__(256) void k_rd_scan_apply(const uint8_t *__restrict
 // where the other's is negative and its own is not -- the right marker in the left adjustment, the left one in the right
 template <bool RIGHT>
 __device__ __forceinline__ void rd_put(const DynView &v, const DynOut &o, int64_t q, int64_t j, int64_t src) {
-    rd_store(o.key, q, rd_load(v.key, j));
+    pk_store(o.key, q, pk_load(v.key, j));
     o.key_len[q] = v.key_len[j];
     o.ext[q] = v.ext[v.ext_off[src >= 0 ? src : j]] & (3ull << 62);
     o.ext_off[q] = q;
@@ -395,7 +320,7 @@ __global__ __launch_bounds__(256) void k_rd_nt_break(const DynView v, int64_t n,
     if (!isl[i]) {
         if (lrank[i] > 0) j = lidx[lrank[i] - 1];
         if (j < ps[rd_part_of(ps, P, i)]) j = -1;
-        b = (j < 0 || !rd_prefix(rd_load(v.key, i), (int)v.key_len[i], rd_load(v.key, j), (int)v.key_len[j])) ? 1u : 0u;
+        b = (j < 0 || !pk_prefix(pk_load(v.key, i), (int)v.key_len[i], pk_load(v.key, j), (int)v.key_len[j])) ? 1u : 0u;
     }
     near[i] = j;
     brk[i] = b;
@@ -410,7 +335,7 @@ __global__ __launch_bounds__(256) void k_rd_nt_keep(const DynView v, int64_t n, 
         const bool dropped = j >= 0 && cbrk[i + 1] == cbrk[j + 1];    // no row in (j, i] breaks the stretch
         const int64_t end = ps[rd_part_of(ps, P, i) + 1];
         const bool replaced = i + 1 < end && isl[i + 1] &&
-                              rd_prefix(rd_load(v.key, i), (int)v.key_len[i], rd_load(v.key, i + 1), (int)v.key_len[i + 1]);
+                              pk_prefix(pk_load(v.key, i), (int)v.key_len[i], pk_load(v.key, i + 1), (int)v.key_len[i + 1]);
         kp = (dropped || replaced) ? 0u : 1u;
     }
     keep[i] = kp;
@@ -422,7 +347,7 @@ __global__ __launch_bounds__(256) void k_rd_compact(const DynView v, int64_t n, 
     if (i == 0) o.ext_off[rank[n]] = 0;
     if (i >= n || !keep[i]) return;
     const int64_t q = (int64_t)rank[i];
-    rd_store(o.key, q, rd_load(v.key, i));
+    pk_store(o.key, q, pk_load(v.key, i));
     o.key_len[q] = v.key_len[i];
     o.ext_off[q] = 0;
     o.ext_len[q] = 0;
@@ -433,17 +358,8 @@ __global__ __launch_bounds__(256) void k_rd_compact(const DynView v, int64_t n, 
 static int rd_params(rfx_ctx *ctx, const rfx_reduce_params *p, RdParams *o) {
     if (!p) return RFX_E_ARG;
     if (p->k1 < 8 || p->k1 >= p->k2 || p->k2 > 124) { ctx->last_error = "k-mer reduction: k1 and k2 must be 8 <= k1 < k2 <= 124"; return RFX_E_ARG; }
-    if (p->max_k < p->k2 || p->max_k + 3 > RD_CLAMP) { ctx->last_error = "k-mer reduction: max_k below k2 or out of range"; return RFX_E_ARG; }
+    if (p->max_k < p->k2 || p->max_k + 3 > PK_CLAMP) { ctx->last_error = "k-mer reduction: max_k below k2 or out of range"; return RFX_E_ARG; }
     *o = RdParams{p->k1, p->k2};
-    return RFX_OK;
-}
-static bool rd_out_ok(const rfx_dyn_packed *p) {
-    return p && p->key && p->key_len && p->ext && p->ext_off && p->ext_len && p->marker && p->left && p->right;
-}
-static bool rd_in_ok(const rfx_dyn_packed *p) { return rd_out_ok(p) && p->n >= 0; }
-static int rd_empty(rfx_ctx *ctx, DynDev &d) {
-    RFX_TRY(dyn_alloc(ctx, d, 0, 0));
-    RFX_HIP(hipMemsetAsync(d.ext_off.p, 0, 8, ctx->stream));
     return RFX_OK;
 }
 static int rd_bad(rfx_ctx *ctx, uint32_t bad) {
@@ -455,24 +371,13 @@ static int rd_bad(rfx_ctx *ctx, uint32_t bad) {
 }
 static int rd_check(rfx_ctx *ctx, const DynDev &in, int la, int lb, int ext_len) {
     DevBuf flags;
-    RFX_TRY(rd_flags_init(ctx, flags));
-    hipLaunchKernelGGL(k_rd_check, RD_GRID(in.n), dyn_view(in), in.n, la, lb, ext_len, flags.as<uint32_t>());
+    RFX_TRY(call_flags_init(ctx, flags));
+    hipLaunchKernelGGL(k_rd_check, RFX_GRID(in.n), dyn_view(in), in.n, la, lb, ext_len, flags.as<CallFlags>());
     RFX_HIP(hipGetLastError());
-    RdFlags f{};
-    RFX_TRY(rd_flags_read(ctx, flags, nullptr, &f));
+    CallFlags f{};
+    RFX_TRY(call_flags_read(ctx, flags, nullptr, nullptr, nullptr, &f));
     return f.bad ? rd_bad(ctx, f.bad) : RFX_OK;
 }
-// the caller's partition starts: P + 1 entries, 0 first, n last, never running backwards -- read back and checked BEFORE a kernel
-// indexes with them
-static int rd_check_starts(rfx_ctx *ctx, const int64_t *d_ps, int P, int64_t n) {
-    int64_t h[65];
-    RFX_TRY(small_readback(ctx, h, d_ps, (size_t)(P + 1) * 8));
-    bool ok = h[0] == 0 && h[P] == n;
-    for (int p = 0; p < P && ok; p++) ok = h[p] <= h[p + 1];
-    if (!ok) { ctx->last_error = "k-mer reduction: partition starts that do not run from 0 to n"; return RFX_E_ARG; }
-    return RFX_OK;
-}
-
 // one text's rows into records [base, base + kept) of d (allocated by the caller for n rows more)
 struct RdBin { DevBuf len, keep, slot, kbeg, mlr; int64_t kept = 0; };
 static int rd_bin_sizes(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, const RdParams &prm, RdBin &b) {
@@ -483,22 +388,22 @@ static int rd_bin_sizes(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_o
     RFX_HIP(b.len.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(b.keep.alloc((size_t)n * 4, ctx->stream));
     RFX_HIP(b.slot.alloc((size_t)(n + 1) * 8, ctx->stream)); RFX_HIP(b.kbeg.alloc((size_t)n * 8, ctx->stream));
     RFX_HIP(b.mlr.alloc((size_t)n * 12, ctx->stream));
-    RFX_TRY(rd_flags_init(ctx, flags));
-    hipLaunchKernelGGL(k_rd_bin_sizes, RD_GRID(n), d_text, d_row_off, n, prm, b.len.as<uint32_t>(), b.kbeg.as<int64_t>(), b.mlr.as<int32_t>(),
-                       flags.as<uint32_t>());
+    RFX_TRY(call_flags_init(ctx, flags));
+    hipLaunchKernelGGL(k_rd_bin_sizes, RFX_GRID(n), d_text, d_row_off, n, prm, b.len.as<uint32_t>(), b.kbeg.as<int64_t>(), b.mlr.as<int32_t>(),
+                       flags.as<CallFlags>());
     RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_rd_bin_flag, RD_GRID(n), (const uint32_t *)b.len.as<uint32_t>(), n, b.keep.as<uint32_t>());
+    hipLaunchKernelGGL(k_rd_bin_flag, RFX_GRID(n), (const uint32_t *)b.len.as<uint32_t>(), n, b.keep.as<uint32_t>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, b.keep.as<uint32_t>(), b.slot.as<uint64_t>(), n));
-    RdFlags f{};
-    RFX_TRY(rd_flags_read(ctx, flags, b.slot.as<uint64_t>() + n, &f));
+    CallFlags f{};
+    RFX_TRY(call_flags_read(ctx, flags, b.slot.as<uint64_t>() + n, nullptr, nullptr, &f));
     if (f.bad) return rd_bad(ctx, f.bad);
-    b.kept = (int64_t)f.total;
+    b.kept = (int64_t)f.total[0];
     return RFX_OK;
 }
 static int rd_bin_emit(rfx_ctx *ctx, const char *d_text, int64_t n, const RdBin &b, int64_t base, DynDev &d) {
     if (n == 0 || b.kept == 0) return RFX_OK;
-    hipLaunchKernelGGL(k_rd_bin_emit, RD_GRID(n), d_text, n, (const uint32_t *)b.len.as<uint32_t>(), (const uint64_t *)b.slot.as<uint64_t>(),
+    hipLaunchKernelGGL(k_rd_bin_emit, RFX_GRID(n), d_text, n, (const uint32_t *)b.len.as<uint32_t>(), (const uint64_t *)b.slot.as<uint64_t>(),
                        (const int64_t *)b.kbeg.as<int64_t>(), (const int32_t *)b.mlr.as<int32_t>(), base, dyn_out(d));
     RFX_HIP(hipGetLastError());
     return RFX_OK;
@@ -510,7 +415,7 @@ static int rd_union(rfx_ctx *ctx, const char *d_ts, const int64_t *d_os, int64_t
     RFX_TRY(rd_bin_sizes(ctx, d_tl, d_ol, nl, prm, bl));
     RFX_TRY(rd_bin_sizes(ctx, d_ts, d_os, ns, prm, bs));
     const int64_t n = bl.kept + bs.kept;
-    if (n == 0) return rd_empty(ctx, d);
+    if (n == 0) return dyn_empty(ctx, d);
     RFX_TRY(dyn_alloc(ctx, d, n, 0));
     RFX_HIP(hipMemsetAsync(d.ext_off.as<int64_t>() + n, 0, 8, ctx->stream));
     RFX_TRY(rd_bin_emit(ctx, d_tl, nl, bl, 0, d));
@@ -519,11 +424,11 @@ static int rd_union(rfx_ctx *ctx, const char *d_ts, const int64_t *d_os, int64_t
 // step 3 (right == false, on full k-mers) / step 6 (right == true, on sub-k-mers)
 static int rd_prepare(rfx_ctx *ctx, bool right, const DynDev &in, const RdParams &prm, DynDev &out) {
     const int64_t n = in.n;
-    if (n == 0) return rd_empty(ctx, out);
+    if (n == 0) return dyn_empty(ctx, out);
     RFX_TRY(right ? rd_check(ctx, in, prm.k1 - 1, prm.k2 - 1, 1) : rd_check(ctx, in, prm.k1, prm.k2, 0));
     RFX_TRY(dyn_alloc(ctx, out, n, n));
-    if (right) hipLaunchKernelGGL(k_rd_right_prep, RD_GRID(n), dyn_view(in), n, dyn_out(out));
-    else hipLaunchKernelGGL(k_rd_left_prep, RD_GRID(n), dyn_view(in), n, dyn_out(out));
+    if (right) hipLaunchKernelGGL(k_rd_right_prep, RFX_GRID(n), dyn_view(in), n, dyn_out(out));
+    else hipLaunchKernelGGL(k_rd_left_prep, RFX_GRID(n), dyn_view(in), n, dyn_out(out));
     RFX_HIP(hipGetLastError());
     return RFX_OK;
 }
@@ -534,9 +439,9 @@ static int rd_adjust_t(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int 
     RFX_HIP(out_ps.alloc((size_t)(P + 1) * 8, ctx->stream));
     if (n == 0) {
         RFX_HIP(hipMemsetAsync(out_ps.p, 0, (size_t)(P + 1) * 8, ctx->stream));
-        return rd_empty(ctx, out);
+        return dyn_empty(ctx, out);
     }
-    RFX_TRY(rd_check_starts(ctx, d_ps, P, n));
+    RFX_TRY(check_part_starts(ctx, d_ps, P, n, "k-mer reduction"));
     RFX_TRY(rd_check(ctx, in, prm.k1 - 1, prm.k2 - 1, 1));
     const int64_t nb = ceil_div(n, 256);
     DevBuf info, maps, agg, cnt, off;
@@ -546,13 +451,13 @@ static int rd_adjust_t(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int 
     const DynView v = dyn_view(in);
     hipLaunchKernelGGL(k_rd_marks, dim3(1), dim3(64), 0, ctx->stream, d_ps, P, info.as<uint32_t>());
     RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_rd_window<RIGHT>, RD_GRID(n), v, n, prm.k1 - 1, info.as<uint32_t>(), maps.as<uint8_t>());
+    hipLaunchKernelGGL(k_rd_window<RIGHT>, RFX_GRID(n), v, n, prm.k1 - 1, info.as<uint32_t>(), maps.as<uint8_t>());
     RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_rd_scan_reduce, RD_GRID(n), (const uint8_t *)maps.as<uint8_t>(), n, agg.as<uint8_t>());
+    hipLaunchKernelGGL(k_rd_scan_reduce, RFX_GRID(n), (const uint8_t *)maps.as<uint8_t>(), n, agg.as<uint8_t>());
     RFX_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_rd_scan_aggs, dim3(1), dim3(256), 0, ctx->stream, agg.as<uint8_t>(), nb);
     RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_rd_scan_apply<RIGHT>, RD_GRID(n), (const uint8_t *)maps.as<uint8_t>(), (const uint8_t *)agg.as<uint8_t>(), n, info.as<uint32_t>(),
+    hipLaunchKernelGGL(k_rd_scan_apply<RIGHT>, RFX_GRID(n), (const uint8_t *)maps.as<uint8_t>(), (const uint8_t *)agg.as<uint8_t>(), n, info.as<uint32_t>(),
                        cnt.as<uint32_t>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, cnt.as<uint32_t>(), off.as<uint64_t>(), n));
@@ -560,7 +465,7 @@ static int rd_adjust_t(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int 
     RFX_TRY(small_readback(ctx, &total, off.as<uint64_t>() + n, 8));
     if ((int64_t)total > n) { ctx->last_error = "k-mer reduction: an adjustment would write more rows than it read"; return RFX_E_STATE; }
     RFX_TRY(dyn_alloc(ctx, out, (int64_t)total, (int64_t)total));
-    hipLaunchKernelGGL(k_rd_emit<RIGHT>, RD_GRID(n), v, n, (const uint32_t *)info.as<uint32_t>(), (const uint64_t *)off.as<uint64_t>(), dyn_out(out));
+    hipLaunchKernelGGL(k_rd_emit<RIGHT>, RFX_GRID(n), v, n, (const uint32_t *)info.as<uint32_t>(), (const uint64_t *)off.as<uint64_t>(), dyn_out(out));
     RFX_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_rd_out_ps, dim3(1), dim3(64), 0, ctx->stream, d_ps, P, (const uint64_t *)off.as<uint64_t>(), out_ps.as<int64_t>());
     RFX_HIP(hipGetLastError());
@@ -575,32 +480,32 @@ static int rd_neutralize(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, in
     RFX_HIP(out_ps.alloc((size_t)(P + 1) * 8, ctx->stream));
     if (n == 0) {
         RFX_HIP(hipMemsetAsync(out_ps.p, 0, (size_t)(P + 1) * 8, ctx->stream));
-        return rd_empty(ctx, out);
+        return dyn_empty(ctx, out);
     }
-    RFX_TRY(rd_check_starts(ctx, d_ps, P, n));
+    RFX_TRY(check_part_starts(ctx, d_ps, P, n, "k-mer reduction"));
     RFX_TRY(rd_check(ctx, in, prm.k1, prm.k2, 0));
     DevBuf isl, lrank, lidx, near, brk, cbrk, keep, rank;
     RFX_HIP(isl.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(lrank.alloc((size_t)(n + 1) * 8, ctx->stream)); RFX_HIP(lidx.alloc((size_t)n * 8, ctx->stream));
     RFX_HIP(near.alloc((size_t)n * 8, ctx->stream)); RFX_HIP(brk.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(cbrk.alloc((size_t)(n + 1) * 8, ctx->stream));
     RFX_HIP(keep.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(rank.alloc((size_t)(n + 1) * 8, ctx->stream));
     const DynView v = dyn_view(in);
-    hipLaunchKernelGGL(k_rd_nt_long, RD_GRID(n), v, n, prm.k2, isl.as<uint32_t>());
+    hipLaunchKernelGGL(k_rd_nt_long, RFX_GRID(n), v, n, prm.k2, isl.as<uint32_t>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, isl.as<uint32_t>(), lrank.as<uint64_t>(), n));
-    hipLaunchKernelGGL(k_rd_nt_scatter, RD_GRID(n), (const uint32_t *)isl.as<uint32_t>(), (const uint64_t *)lrank.as<uint64_t>(), n, lidx.as<int64_t>());
+    hipLaunchKernelGGL(k_rd_nt_scatter, RFX_GRID(n), (const uint32_t *)isl.as<uint32_t>(), (const uint64_t *)lrank.as<uint64_t>(), n, lidx.as<int64_t>());
     RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_rd_nt_break, RD_GRID(n), v, n, (const uint32_t *)isl.as<uint32_t>(), (const uint64_t *)lrank.as<uint64_t>(),
+    hipLaunchKernelGGL(k_rd_nt_break, RFX_GRID(n), v, n, (const uint32_t *)isl.as<uint32_t>(), (const uint64_t *)lrank.as<uint64_t>(),
                        (const int64_t *)lidx.as<int64_t>(), d_ps, P, near.as<int64_t>(), brk.as<uint32_t>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, brk.as<uint32_t>(), cbrk.as<uint64_t>(), n));
-    hipLaunchKernelGGL(k_rd_nt_keep, RD_GRID(n), v, n, (const uint32_t *)isl.as<uint32_t>(), (const int64_t *)near.as<int64_t>(),
+    hipLaunchKernelGGL(k_rd_nt_keep, RFX_GRID(n), v, n, (const uint32_t *)isl.as<uint32_t>(), (const int64_t *)near.as<int64_t>(),
                        (const uint64_t *)cbrk.as<uint64_t>(), d_ps, P, keep.as<uint32_t>());
     RFX_HIP(hipGetLastError());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, keep.as<uint32_t>(), rank.as<uint64_t>(), n));
     uint64_t total = 0;
     RFX_TRY(small_readback(ctx, &total, rank.as<uint64_t>() + n, 8));
     RFX_TRY(dyn_alloc(ctx, out, (int64_t)total, 0));
-    hipLaunchKernelGGL(k_rd_compact, RD_GRID(n), v, n, (const uint32_t *)keep.as<uint32_t>(), (const uint64_t *)rank.as<uint64_t>(), dyn_out(out));
+    hipLaunchKernelGGL(k_rd_compact, RFX_GRID(n), v, n, (const uint32_t *)keep.as<uint32_t>(), (const uint64_t *)rank.as<uint64_t>(), dyn_out(out));
     RFX_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_rd_out_ps, dim3(1), dim3(64), 0, ctx->stream, d_ps, P, (const uint64_t *)rank.as<uint64_t>(), out_ps.as<int64_t>());
     RFX_HIP(hipGetLastError());
@@ -625,8 +530,6 @@ static int rd_run(rfx_ctx *ctx, const char *d_ts, const int64_t *d_os, int64_t n
     return rd_neutralize(ctx, a, ps.as<int64_t>(), P, prm, out, ops);
 }
 
-static bool rd_text_ok(const char *t, const int64_t *off, int64_t n) { return n >= 0 && (n == 0 || (t && off)); }
-
 }  // namespace
 
 extern "C" {
@@ -638,7 +541,7 @@ void rfx_reduce_default_params(rfx_reduce_params *p, int k1, int k2) try {
 
 int rfx_dev_reduce_union(rfx_ctx *ctx, const char *d_text_short, const int64_t *d_row_off_short, int64_t n_short, const char *d_text_long,
                          const int64_t *d_row_off_long, int64_t n_long, const rfx_reduce_params *params, rfx_dyn_packed *d_out) try {
-    if (!ctx || !rd_out_ok(d_out) || !rd_text_ok(d_text_short, d_row_off_short, n_short) || !rd_text_ok(d_text_long, d_row_off_long, n_long)) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_out_ok(d_out) || !text_rows_ok(d_text_short, d_row_off_short, n_short) || !text_rows_ok(d_text_long, d_row_off_long, n_long)) return RFX_E_ARG;
     RdParams prm;
     RFX_TRY(rd_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -648,7 +551,7 @@ int rfx_dev_reduce_union(rfx_ctx *ctx, const char *d_text_short, const int64_t *
 } RFX_API_CATCH(ctx)
 
 int rfx_dev_reduce_left_prepare(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rfx_reduce_params *params, rfx_dyn_packed *d_out) try {
-    if (!ctx || !rd_in_ok(d_in) || !rd_out_ok(d_out)) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out)) return RFX_E_ARG;
     RdParams prm;
     RFX_TRY(rd_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -659,7 +562,7 @@ int rfx_dev_reduce_left_prepare(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const 
 } RFX_API_CATCH(ctx)
 
 int rfx_dev_reduce_right_prepare(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rfx_reduce_params *params, rfx_dyn_packed *d_out) try {
-    if (!ctx || !rd_in_ok(d_in) || !rd_out_ok(d_out)) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out)) return RFX_E_ARG;
     RdParams prm;
     RFX_TRY(rd_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -671,7 +574,7 @@ int rfx_dev_reduce_right_prepare(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const
 
 int rfx_dev_reduce_adjust(rfx_ctx *ctx, int right, const rfx_dyn_packed *d_sorted, const int64_t *d_part_start, int P, const rfx_reduce_params *params,
                           rfx_dyn_packed *d_out, int64_t *d_out_part_start) try {
-    if (!ctx || !rd_in_ok(d_sorted) || !rd_out_ok(d_out) || !d_part_start || !d_out_part_start || P < 1 || P > 63 || (right != 0 && right != 1)) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_ok(d_sorted) || !dyn_packed_out_ok(d_out) || !d_part_start || !d_out_part_start || P < 1 || P > 63 || (right != 0 && right != 1)) return RFX_E_ARG;
     RdParams prm;
     RFX_TRY(rd_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -685,7 +588,7 @@ int rfx_dev_reduce_adjust(rfx_ctx *ctx, int right, const rfx_dyn_packed *d_sorte
 } RFX_API_CATCH(ctx)
 
 int rfx_dev_reduce_full_kmers(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rfx_reduce_params *params, rfx_dyn_packed *d_out) try {
-    if (!ctx || !rd_in_ok(d_in) || !rd_out_ok(d_out)) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out)) return RFX_E_ARG;
     RdParams prm;
     RFX_TRY(rd_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -698,7 +601,7 @@ int rfx_dev_reduce_full_kmers(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rf
 
 int rfx_dev_reduce_neutralize(rfx_ctx *ctx, const rfx_dyn_packed *d_sorted, const int64_t *d_part_start, int P, const rfx_reduce_params *params,
                               rfx_dyn_packed *d_out, int64_t *d_out_part_start) try {
-    if (!ctx || !rd_in_ok(d_sorted) || !rd_out_ok(d_out) || !d_part_start || !d_out_part_start || P < 1 || P > 63) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_ok(d_sorted) || !dyn_packed_out_ok(d_out) || !d_part_start || !d_out_part_start || P < 1 || P > 63) return RFX_E_ARG;
     RdParams prm;
     RFX_TRY(rd_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -713,7 +616,7 @@ int rfx_dev_reduce_neutralize(rfx_ctx *ctx, const rfx_dyn_packed *d_sorted, cons
 
 int rfx_dev_reduce_run(rfx_ctx *ctx, const char *d_text_short, const int64_t *d_row_off_short, int64_t n_short, const char *d_text_long,
                        const int64_t *d_row_off_long, int64_t n_long, int P, const rfx_reduce_params *params, rfx_dyn_packed *d_out) try {
-    if (!ctx || !rd_out_ok(d_out) || !rd_text_ok(d_text_short, d_row_off_short, n_short) || !rd_text_ok(d_text_long, d_row_off_long, n_long) ||
+    if (!ctx || !dyn_packed_out_ok(d_out) || !text_rows_ok(d_text_short, d_row_off_short, n_short) || !text_rows_ok(d_text_long, d_row_off_long, n_long) ||
         P < 1 || P > 63) return RFX_E_ARG;
     RdParams prm;
     RFX_TRY(rd_params(ctx, params, &prm));
@@ -727,7 +630,7 @@ int rfx_dev_reduce_run(rfx_ctx *ctx, const char *d_text_short, const int64_t *d_
 int rfx_reduce_text(rfx_ctx *ctx, const char *text_short, const int64_t *row_off_short, int64_t n_short, const char *text_long,
                     const int64_t *row_off_long, int64_t n_long, int P, const rfx_reduce_params *params, char *out_short, int64_t cap_short,
                     int64_t *out_len_short, char *out_long, int64_t cap_long, int64_t *out_len_long) try {
-    if (!ctx || !rd_text_ok(text_short, row_off_short, n_short) || !rd_text_ok(text_long, row_off_long, n_long) || P < 1 || P > 63 || !out_len_short ||
+    if (!ctx || !text_rows_ok(text_short, row_off_short, n_short) || !text_rows_ok(text_long, row_off_long, n_long) || P < 1 || P > 63 || !out_len_short ||
         !out_len_long || cap_short < 0 || cap_long < 0 || (cap_short > 0 && !out_short) || (cap_long > 0 && !out_long)) return RFX_E_ARG;
     RdParams prm;
     RFX_TRY(rd_params(ctx, params, &prm));
