@@ -898,22 +898,55 @@ class Reflexiv:
                                              C.byref(co), trace.ctypes.data, len(trace), C.addressof(ntr)))
         return out, [int(x) for x in trace[:ntr.value]]
 
+    def _params(self, struct, default_fn, c_name, *args, **kw):
+        """a parameter struct: the library's defaults for `args`, then **kw"""
+        p = struct()
+        default_fn(C.byref(p), *(int(a) for a in args))
+        for a, b in kw.items():
+            if a not in dict(p._fields_):
+                raise TypeError(f"{c_name} has no field {a!r}")
+            setattr(p, a, b)
+        return p
+
+    def _host_text_call(self, name, caps, call):
+        """one host-text entry point with len(caps) output texts: call(outs, caps, lens) -> its status.  On RFX_E_CAP every buffer
+        grows to the length the call reported and the call is made again -> the texts as bytes"""
+        caps = list(caps)
+        lens = [C.c_int64(0) for _ in caps]
+        while True:
+            outs = [np.empty(max(1, c), np.uint8) for c in caps]
+            t0 = time.perf_counter()
+            st = call(outs, caps, lens)
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
+            if st == RFX_E_CAP and any(ln.value > c for ln, c in zip(lens, caps)):
+                caps = [max(c, ln.value) for ln, c in zip(lens, caps)]
+                continue
+            self._check(st, name)
+            return [o[:ln.value].tobytes() for o, ln in zip(outs, lens)]
+
+    def _dev_text_call(self, name, d_text, call):
+        """one device-text entry point: call(d_text, ln) -> its status.  On RFX_E_CAP d_text is replaced by one of the length
+        the call reported and the call is made again -> (d_text, the text's length)"""
+        import torch
+        ln = C.c_int64(0)
+        while True:
+            t0 = time.perf_counter()
+            st = call(d_text, ln)
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
+            if st == RFX_E_CAP:
+                d_text = torch.empty(ln.value, dtype=torch.uint8, device=d_text.device)
+                continue
+            self._check(st, name)
+            return d_text, int(ln.value)
+
     def dyn_to_text_dev(self, d: "DynPacked", d_text=None):
         """rfx_dev_dyn_to_text -> (torch uint8 tensor in HBM holding the rows "SUBKMER,m|l|r,EXTENSION\\n", its length)"""
         import torch
         ci = d._c()
-        ln = C.c_int64(0)
         if d_text is None:
             d_text = torch.empty(max(1, 160 * d.n + 32 * d.words + 64), dtype=torch.uint8, device=d.key.device)
-        while True:
-            t0 = time.perf_counter()
-            st = self.L.rfx_dev_dyn_to_text(self.ctx, C.byref(ci), d_text.data_ptr(), int(d_text.numel()), C.addressof(ln))
-            self.last_call_ms = (time.perf_counter() - t0) * 1e3
-            if st == RFX_E_CAP:
-                d_text = torch.empty(ln.value, dtype=torch.uint8, device=d.key.device)
-                continue
-            self._check(st, "rfx_dev_dyn_to_text")
-            return d_text, int(ln.value)
+        return self._dev_text_call("rfx_dev_dyn_to_text", d_text, lambda t, ln: self.L.rfx_dev_dyn_to_text(
+            self.ctx, C.byref(ci), t.data_ptr(), int(t.numel()), C.addressof(ln)))
 
     def dyn_run_text(self, text: bytes, form: int, P=1, random_reflection=False, passes_first_four=0, start_iteration=1, end_iteration=0):
         """rfx_dyn_run_text: the rows of a hand-over file (bytes; one row per line, empty lines skipped) -> (the output rows as
@@ -931,30 +964,16 @@ class Reflexiv:
         off = np.concatenate([starts, [len(buf)]]).astype(np.int64)
         cap = len(buf) + 32 * n_rows + 64
         trace = np.zeros(256, np.int64)
-        ntr, ln = C.c_int64(0), C.c_int64(0)
-        while True:
-            out = np.empty(max(1, cap), np.uint8)
-            t0 = time.perf_counter()
-            st = self.L.rfx_dyn_run_text(self.ctx, text, off.ctypes.data, n_rows, form, P, int(random_reflection), passes_first_four,
-                                         start_iteration, end_iteration, out.ctypes.data, cap, C.addressof(ln), trace.ctypes.data,
-                                         len(trace), C.addressof(ntr))
-            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
-            if st == RFX_E_CAP and ln.value > cap:
-                cap = ln.value
-                continue
-            self._check(st, "rfx_dyn_run_text")
-            return out[:ln.value].tobytes(), [int(x) for x in trace[:ntr.value]]
+        ntr = C.c_int64(0)
+        out, = self._host_text_call("rfx_dyn_run_text", [cap], lambda o, c, ln: self.L.rfx_dyn_run_text(
+            self.ctx, text, off.ctypes.data, n_rows, form, P, int(random_reflection), passes_first_four, start_iteration, end_iteration,
+            o[0].ctypes.data, c[0], C.addressof(ln[0]), trace.ctypes.data, len(trace), C.addressof(ntr)))
+        return out, [int(x) for x in trace[:ntr.value]]
 
     # ---- the k-mer sorting stage (Count_<k>_sorted) on the same packed sets (rfx_dev_ksort_*)
     def ksort_params(self, k: int, **kw) -> "_lib.CKsortParams":
         """rfx_ksort_default_params (max_k 95, min_error_cov 8, max_cov 10000000, min_repeat_fold 1.5, bubble 1), then **kw"""
-        p = _lib.CKsortParams()
-        self.L.rfx_ksort_default_params(C.byref(p), int(k))
-        for a, b in kw.items():
-            if a not in dict(p._fields_):
-                raise TypeError(f"rfx_ksort_params has no field {a!r}")
-            setattr(p, a, b)
-        return p
+        return self._params(_lib.CKsortParams, self.L.rfx_ksort_default_params, "rfx_ksort_params", k, **kw)
 
     def ksort_binarize(self, d_text, d_row_off, params, out: "DynPacked" = None) -> "DynPacked":
         """rfx_dev_ksort_binarize: `KMER,count` rows (torch uint8 tensor in HBM + int64 row offsets, n_rows + 1) -> two records per
@@ -990,54 +1009,28 @@ class Reflexiv:
         (torch int64 in HBM, rows + 1 entries in use; None without want_offsets), the rows)"""
         import torch
         ci = d._c()
-        ln, nr = C.c_int64(0), C.c_int64(0)
+        nr = C.c_int64(0)
         if d_text is None:
             d_text = torch.empty(max(1, (k + 24) * d.n), dtype=torch.uint8, device=d.key.device)
         d_off = torch.empty(d.n + 1, dtype=torch.int64, device=d.key.device) if want_offsets else None
-        while True:
-            t0 = time.perf_counter()
-            st = self.L.rfx_dev_ksort_to_text(self.ctx, C.byref(ci), int(k), d_text.data_ptr(), int(d_text.numel()), C.addressof(ln),
-                                              d_off.data_ptr() if want_offsets else None, C.addressof(nr))
-            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
-            if st == RFX_E_CAP:
-                d_text = torch.empty(ln.value, dtype=torch.uint8, device=d.key.device)
-                continue
-            self._check(st, "rfx_dev_ksort_to_text")
-            return d_text, int(ln.value), d_off, int(nr.value)
+        d_text, n = self._dev_text_call("rfx_dev_ksort_to_text", d_text, lambda t, ln: self.L.rfx_dev_ksort_to_text(
+            self.ctx, C.byref(ci), int(k), t.data_ptr(), int(t.numel()), C.addressof(ln), d_off.data_ptr() if want_offsets else None,
+            C.addressof(nr)))
+        return d_text, n, d_off, int(nr.value)
 
     def ksort_text(self, text: bytes, params) -> bytes:
         """rfx_ksort_text: the rows of a counts file (bytes, one `KMER,count` row per line) -> the rows of Count_<k>_sorted"""
         text = bytes(text)
-        buf = np.frombuffer(text, np.uint8)
-        ends = np.flatnonzero(buf == 10)
-        starts = np.concatenate([[0], ends + 1]).astype(np.int64)
-        starts = starts[starts < len(buf)]
-        n_rows = len(starts)
-        off = np.concatenate([starts, [len(buf)]]).astype(np.int64)
-        cap = 2 * (len(buf) + 24 * n_rows) + 64
-        ln = C.c_int64(0)
-        while True:
-            out = np.empty(max(1, cap), np.uint8)
-            t0 = time.perf_counter()
-            st = self.L.rfx_ksort_text(self.ctx, text, off.ctypes.data, n_rows, C.byref(params), out.ctypes.data, cap, C.addressof(ln))
-            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
-            if st == RFX_E_CAP and ln.value > cap:
-                cap = ln.value
-                continue
-            self._check(st, "rfx_ksort_text")
-            return out[:ln.value].tobytes()
+        off, n_rows = self._row_offsets(text)
+        cap = 2 * (len(text) + 24 * n_rows) + 64
+        return self._host_text_call("rfx_ksort_text", [cap], lambda o, c, ln: self.L.rfx_ksort_text(
+            self.ctx, text, off.ctypes.data, n_rows, C.byref(params), o[0].ctypes.data, c[0], C.addressof(ln[0])))[0]
 
     # ---- the k-mer reduction stage (Count_<k1>_reduced, Count_<k2>_sorted / _reduced) on the same packed sets (rfx_dev_reduce_*,
     # DESIGN.md section 18)
     def reduce_params(self, k1: int, k2: int, **kw) -> "_lib.CReduceParams":
         """rfx_reduce_default_params (max_k = max(95, k2)), then **kw"""
-        p = _lib.CReduceParams()
-        self.L.rfx_reduce_default_params(C.byref(p), int(k1), int(k2))
-        for a, b in kw.items():
-            if a not in dict(p._fields_):
-                raise TypeError(f"rfx_reduce_params has no field {a!r}")
-            setattr(p, a, b)
-        return p
+        return self._params(_lib.CReduceParams, self.L.rfx_reduce_default_params, "rfx_reduce_params", k1, k2, **kw)
 
     def reduce_union(self, d_text_short, d_off_short, d_text_long, d_off_long, params, out: "DynPacked" = None) -> "DynPacked":
         """rfx_dev_reduce_union: two `KMER,m|l|r` texts (torch uint8 tensors in HBM + int64 row offsets, rows + 1) -> the full k-mer
@@ -1105,29 +1098,14 @@ class Reflexiv:
         offs, ns = self._row_offsets(ts)
         offl, nl = self._row_offsets(tl)
         cap1, cap2 = len(ts) + ns + 64, len(tl) + nl + 64      # (an edited marker may grow a row by one character)
-        l1, l2 = C.c_int64(0), C.c_int64(0)
-        while True:
-            o1, o2 = np.empty(max(1, cap1), np.uint8), np.empty(max(1, cap2), np.uint8)
-            t0 = time.perf_counter()
-            st = self.L.rfx_reduce_text(self.ctx, ts, offs.ctypes.data, ns, tl, offl.ctypes.data, nl, int(P), C.byref(params), o1.ctypes.data, cap1,
-                                        C.addressof(l1), o2.ctypes.data, cap2, C.addressof(l2))
-            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
-            if st == RFX_E_CAP and (l1.value > cap1 or l2.value > cap2):
-                cap1, cap2 = max(cap1, l1.value), max(cap2, l2.value)
-                continue
-            self._check(st, "rfx_reduce_text")
-            return o1[:l1.value].tobytes(), o2[:l2.value].tobytes()
+        return tuple(self._host_text_call("rfx_reduce_text", [cap1, cap2], lambda o, c, ln: self.L.rfx_reduce_text(
+            self.ctx, ts, offs.ctypes.data, ns, tl, offl.ctypes.data, nl, int(P), C.byref(params), o[0].ctypes.data, c[0], C.addressof(ln[0]),
+            o[1].ctypes.data, c[1], C.addressof(ln[1]))))
 
     # ---- the contig fixing stage (Assembly_intermediate/04Fixing) on the same packed sets (rfx_dev_fix_*)
     def fix_params(self, max_k: int, **kw) -> "_lib.CFixParams":
         """rfx_fix_default_params (scramble 2, max_iteration 150), then **kw"""
-        p = _lib.CFixParams()
-        self.L.rfx_fix_default_params(C.byref(p), int(max_k))
-        for a, b in kw.items():
-            if a not in dict(p._fields_):
-                raise TypeError(f"rfx_fix_params has no field {a!r}")
-            setattr(p, a, b)
-        return p
+        return self._params(_lib.CFixParams, self.L.rfx_fix_default_params, "rfx_fix_params", max_k, **kw)
 
     def fix_binarize(self, d_text, d_row_off, params, out: "DynPacked" = None) -> "DynPacked":
         """rfx_dev_fix_binarize: `SUBKMER,m|l|r,EXTENSION` rows (torch uint8 tensor in HBM + int64 row offsets, n_rows + 1) -> the
@@ -1199,17 +1177,8 @@ class Reflexiv:
         text = bytes(text)
         off, n_rows = self._row_offsets(text)
         cap = len(text) + 48 * n_rows * (2 * (int(params.max_k) - 30) + 1) + 64
-        ln = C.c_int64(0)
-        while True:
-            out = np.empty(max(1, cap), np.uint8)
-            t0 = time.perf_counter()
-            st = self.L.rfx_fix_text(self.ctx, text, off.ctypes.data, n_rows, int(P), C.byref(params), out.ctypes.data, cap, C.addressof(ln))
-            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
-            if st == RFX_E_CAP and ln.value > cap:
-                cap = ln.value
-                continue
-            self._check(st, "rfx_fix_text")
-            return out[:ln.value].tobytes()
+        return self._host_text_call("rfx_fix_text", [cap], lambda o, c, ln: self.L.rfx_fix_text(
+            self.ctx, text, off.ctypes.data, n_rows, int(P), C.byref(params), o[0].ctypes.data, c[0], C.addressof(ln[0])))[0]
 
     # ---- the second contig fixing stage (05FixingAgain, 06ContigEnds) on the same packed sets (rfx_dev_fix2_*)
     def fix2_binarize(self, d_text, d_row_off, out: "DynPacked" = None) -> "DynPacked":
@@ -1250,18 +1219,10 @@ class Reflexiv:
     def _fix2_text_dev(self, fn, name, c: "ContigsPacked", d_left, d_right, d_text):
         import torch
         ci = c._c()
-        ln = C.c_int64(0)
         if d_text is None:
             d_text = torch.empty(max(1, 96 * c.n + 32 * c.words + 64), dtype=torch.uint8, device=c.word_off.device)
-        while True:
-            t0 = time.perf_counter()
-            st = fn(self.ctx, C.byref(ci), d_left.data_ptr(), d_right.data_ptr(), d_text.data_ptr(), int(d_text.numel()), C.addressof(ln))
-            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
-            if st == RFX_E_CAP:
-                d_text = torch.empty(ln.value, dtype=torch.uint8, device=c.word_off.device)
-                continue
-            self._check(st, name)
-            return d_text, int(ln.value)
+        return self._dev_text_call(name, d_text, lambda t, ln: fn(
+            self.ctx, C.byref(ci), d_left.data_ptr(), d_right.data_ptr(), t.data_ptr(), int(t.numel()), C.addressof(ln)))
 
     def fix2_to_text(self, c: "ContigsPacked", d_left, d_right, d_text=None):
         """rfx_dev_fix2_to_text -> (torch uint8 tensor in HBM holding the rows "Contig_<L>_<left>_<right>_<idx>,<contig>\\n" of
@@ -1278,18 +1239,9 @@ class Reflexiv:
         text = bytes(text)
         off, n_rows = self._row_offsets(text)
         cap1 = cap2 = len(text) + 64 * n_rows + 64
-        l1, l2 = C.c_int64(0), C.c_int64(0)
-        while True:
-            o1, o2 = np.empty(max(1, cap1), np.uint8), np.empty(max(1, cap2), np.uint8)
-            t0 = time.perf_counter()
-            st = self.L.rfx_fix2_text(self.ctx, text, off.ctypes.data, n_rows, int(P), C.byref(params), o1.ctypes.data, cap1, C.addressof(l1),
-                                      o2.ctypes.data, cap2, C.addressof(l2))
-            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
-            if st == RFX_E_CAP and (l1.value > cap1 or l2.value > cap2):
-                cap1, cap2 = max(cap1, l1.value), max(cap2, l2.value)
-                continue
-            self._check(st, "rfx_fix2_text")
-            return o1[:l1.value].tobytes(), o2[:l2.value].tobytes()
+        return tuple(self._host_text_call("rfx_fix2_text", [cap1, cap2], lambda o, c, ln: self.L.rfx_fix2_text(
+            self.ctx, text, off.ctypes.data, n_rows, int(P), C.byref(params), o[0].ctypes.data, c[0], C.addressof(ln[0]), o[1].ctypes.data, c[1],
+            C.addressof(ln[1]))))
 
     # ------------------------------------------------ f-4: contig RC de-duplication
     def dedup_contigs(self, contigs, min_contig=500):
@@ -1373,19 +1325,12 @@ class Reflexiv:
         contigs written)"""
         import torch
         ci = d._c()
-        ln, nc = C.c_int64(0), C.c_int64(0)
+        nc = C.c_int64(0)
         if d_text is None:
             d_text = torch.empty(max(1, 64 * d.n + 33 * d.words + 64), dtype=torch.uint8, device=d.word_off.device)
-        while True:
-            t0 = time.perf_counter()
-            st = self.L.rfx_dev_contigs_to_text(self.ctx, C.byref(ci), min_contig, d_text.data_ptr(), int(d_text.numel()), C.addressof(ln),
-                                                C.addressof(nc))
-            self.last_call_ms = (time.perf_counter() - t0) * 1e3
-            if st == RFX_E_CAP:
-                d_text = torch.empty(ln.value, dtype=torch.uint8, device=d.word_off.device)
-                continue
-            self._check(st, "rfx_dev_contigs_to_text")
-            return d_text, int(ln.value), int(nc.value)
+        d_text, n = self._dev_text_call("rfx_dev_contigs_to_text", d_text, lambda t, ln: self.L.rfx_dev_contigs_to_text(
+            self.ctx, C.byref(ci), min_contig, t.data_ptr(), int(t.numel()), C.addressof(ln), C.addressof(nc)))
+        return d_text, n, int(nc.value)
 
     def dedup_dev(self, d: "ContigsPacked", out: "ContigsPacked" = None):
         """rfx_dev_dedup_contigs: the three rounds, packed in, packed out -> (ContigsPacked, [contigs after round 1, 2, 3])"""

@@ -353,10 +353,10 @@ int rfx_extract_canon(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_of
     const int wpr = (int)std::max<int64_t>(1, (maxlen + 31) / 32);
     DevBuf d_bases, d_off, d_words, d_nk, d_koff, d_out;
     RFX_HIP(d_bases.alloc((size_t)nb, ctx->stream));
-    RFX_HIP(d_off.alloc((size_t)(n_reads + 1) * 8, ctx->stream));
-    RFX_HIP(d_words.alloc((size_t)n_reads * wpr * 8, ctx->stream));
-    RFX_HIP(d_nk.alloc((size_t)n_reads * 8, ctx->stream));
-    RFX_HIP(d_koff.alloc((size_t)(n_reads + 1) * 8, ctx->stream));
+    RFX_ALLOC(d_off, int64_t, n_reads + 1);
+    RFX_ALLOC(d_words, uint64_t, (size_t)n_reads * wpr);
+    RFX_ALLOC(d_nk, uint64_t, n_reads);
+    RFX_ALLOC(d_koff, uint64_t, n_reads + 1);
     // offsets are rebased to the first read
     std::vector<int64_t> off((size_t)n_reads + 1);
     for (int64_t r = 0; r <= n_reads; r++) off[(size_t)r] = read_off[r] - read_off[0];
@@ -372,7 +372,7 @@ int rfx_extract_canon(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_of
     if ((int64_t)total > cap) return RFX_E_CAP;
     if (total == 0) return RFX_OK;
     if (!out_kmers) return RFX_E_ARG;
-    RFX_HIP(d_out.alloc((size_t)total * 8, ctx->stream));
+    RFX_ALLOC(d_out, uint64_t, total);
     RFX_TRY(extract_ordered_packed(ctx, d_words.as<uint64_t>(), wpr, d_koff.as<uint64_t>(), n_reads, k, front_clip,
                                    d_out.as<uint64_t>()));
     RFX_HIP(hipMemcpyAsync(out_kmers, d_out.p, (size_t)total * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -395,10 +395,10 @@ int rfx_extract_canon_w(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_
     const int wpr = (int)std::max<int64_t>(1, (maxlen + 31) / 32);
     DevBuf d_bases, d_off, d_words, d_nk, d_koff, d_soa, d_out;
     RFX_HIP(d_bases.alloc((size_t)nb, ctx->stream));
-    RFX_HIP(d_off.alloc((size_t)(n_reads + 1) * 8, ctx->stream));
-    RFX_HIP(d_words.alloc((size_t)n_reads * wpr * 8, ctx->stream));
-    RFX_HIP(d_nk.alloc((size_t)n_reads * 8, ctx->stream));
-    RFX_HIP(d_koff.alloc((size_t)(n_reads + 1) * 8, ctx->stream));
+    RFX_ALLOC(d_off, int64_t, n_reads + 1);
+    RFX_ALLOC(d_words, uint64_t, (size_t)n_reads * wpr);
+    RFX_ALLOC(d_nk, uint64_t, n_reads);
+    RFX_ALLOC(d_koff, uint64_t, n_reads + 1);
     std::vector<int64_t> off((size_t)n_reads + 1);
     for (int64_t r = 0; r <= n_reads; r++) off[(size_t)r] = read_off[r] - read_off[0];
     if (nb > 0) RFX_HIP(hipMemcpyAsync(d_bases.p, bases + read_off[0], (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
@@ -413,8 +413,8 @@ int rfx_extract_canon_w(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_
     if ((int64_t)total > cap) return RFX_E_CAP;
     if (total == 0) return RFX_OK;
     if (!out_kmers) return RFX_E_ARG;
-    RFX_HIP(d_soa.alloc((size_t)total * W * 8, ctx->stream));
-    RFX_HIP(d_out.alloc((size_t)total * W * 8, ctx->stream));
+    RFX_ALLOC(d_soa, uint64_t, (size_t)total * W);
+    RFX_ALLOC(d_out, uint64_t, (size_t)total * W);
     RFX_TRY(extract_w(ctx, d_words.as<uint64_t>(), wpr, d_koff.as<uint64_t>(), 0, n_reads, k, front_clip,
                       d_soa.as<uint64_t>(), (int64_t)total));
     RFX_TRY(soa_to_aos(ctx, d_soa.as<uint64_t>(), (int64_t)total, W, d_out.as<uint64_t>()));
@@ -433,10 +433,10 @@ int rfx_count_filter_w(rfx_ctx *ctx, const uint64_t *kmers, int64_t n, int k, in
     if (n == 0) return RFX_OK;
     const int W = k / 32 + 1;
     DevBuf d_in, d_soa, d_keys, d_counts;
-    RFX_HIP(d_in.alloc((size_t)n * W * 8, ctx->stream));
-    RFX_HIP(d_soa.alloc((size_t)n * W * 8, ctx->stream));
-    RFX_HIP(d_keys.alloc((size_t)n * W * 8, ctx->stream));
-    RFX_HIP(d_counts.alloc((size_t)n * 8, ctx->stream));
+    RFX_ALLOC(d_in, uint64_t, (size_t)n * W);
+    RFX_ALLOC(d_soa, uint64_t, (size_t)n * W);
+    RFX_ALLOC(d_keys, uint64_t, (size_t)n * W);
+    RFX_ALLOC(d_counts, int64_t, n);
     RFX_HIP(hipMemcpyAsync(d_in.p, kmers, (size_t)n * W * 8, hipMemcpyHostToDevice, ctx->stream));
     int64_t m = 0, dist = 0;
     if (wide_elem_path(k)) {                  // k = 33..127: the bucketed count on the AoS elements
@@ -502,7 +502,7 @@ int rfx_dev_count_reads_w(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads
         return st;
     }
     DevBuf d_soa;
-    RFX_HIP(d_soa.alloc((size_t)N * W * 8, ctx->stream));
+    RFX_ALLOC(d_soa, uint64_t, (size_t)N * W);
     const bool fast = wide_fast_path(k);
     {
         ScopedTimer t(ctx, "extract_w");
@@ -531,11 +531,11 @@ int rfx_count_filter(rfx_ctx *ctx, const uint64_t *kmers, int64_t n, int min_cov
     if (out_distinct) *out_distinct = 0;
     if (n == 0) return RFX_OK;
     DevBuf d_in, d_keys, d_counts;
-    RFX_HIP(d_in.alloc((size_t)n * 8, ctx->stream));
+    RFX_ALLOC(d_in, uint64_t, n);
     // at most n survivors; the device path reports the needed size if cap is smaller
     const int64_t dcap = n;
-    RFX_HIP(d_keys.alloc((size_t)dcap * 8, ctx->stream));
-    RFX_HIP(d_counts.alloc((size_t)dcap * 4, ctx->stream));
+    RFX_ALLOC(d_keys, uint64_t, dcap);
+    RFX_ALLOC(d_counts, int32_t, dcap);
     RFX_HIP(hipMemcpyAsync(d_in.p, kmers, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     int64_t m = 0, dist = 0;
     RFX_TRY(count_filter(ctx, nullptr, d_in.as<uint64_t>(), n, min_cov, max_cov, twin, nullptr, 0,
@@ -559,7 +559,7 @@ int rfx_rc_expand_subkmer(rfx_ctx *ctx, const uint64_t *kmers, const int32_t *co
     DevBuf dk, dc;
     const int aw = asm_words(k);
     RFX_HIP(dk.alloc((size_t)n * 8 * aw, ctx->stream));
-    RFX_HIP(dc.alloc((size_t)n * 4, ctx->stream));
+    RFX_ALLOC(dc, int32_t, n);
     if (n > 0) {
         RFX_HIP(hipMemcpyAsync(dk.p, kmers, (size_t)n * 8 * aw, hipMemcpyHostToDevice, ctx->stream));
         RFX_HIP(hipMemcpyAsync(dc.p, counts, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -813,8 +813,7 @@ int rfx_dev_lower_bound(rfx_ctx *ctx, const uint64_t *d_sorted_keys, int64_t n, 
     if (!ctx || n < 0 || m < 0 || (m > 0 && (!d_values || !d_out)) || (n > 0 && !d_sorted_keys)) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     if (m == 0) return RFX_OK;
-    hipLaunchKernelGGL(k_lower_bound, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, ctx->stream, d_sorted_keys, n, d_values, m, upper, d_out);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH(k_lower_bound, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, d_sorted_keys, n, d_values, m, upper, d_out);
     RFX_TRY(sync_checked(ctx));
     return RFX_OK;
 } RFX_API_CATCH(ctx)
@@ -1380,7 +1379,7 @@ int rfx_assemble_counts_w(rfx_ctx *ctx, const uint64_t *kmers, const int32_t *co
     const int aw = asm_words(prm->k);
     DevBuf dk, dc;
     RFX_HIP(dk.alloc((size_t)std::max<int64_t>(n, 1) * 8 * aw, ctx->stream));
-    RFX_HIP(dc.alloc((size_t)std::max<int64_t>(n, 1) * 4, ctx->stream));
+    RFX_ALLOC(dc, int32_t, std::max<int64_t>(n, 1));
     if (n > 0) {
         RFX_HIP(hipMemcpyAsync(dk.p, kmers, (size_t)n * 8 * aw, hipMemcpyHostToDevice, ctx->stream));
         RFX_HIP(hipMemcpyAsync(dc.p, counts, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -1530,8 +1529,8 @@ int rfx_assemble_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_o
                                                    : (int64_t)nb);
         DevBuf wk, wc;
         for (;;) {                                  // survivors are few; grow on RFX_E_CAP
-            RFX_HIP(wk.alloc((size_t)kcap * kw * 8, ctx->stream));
-            RFX_HIP(wc.alloc((size_t)kcap * 8, ctx->stream));
+            RFX_ALLOC(wk, uint64_t, (size_t)kcap * kw);
+            RFX_ALLOC(wc, int64_t, kcap);
             const int st = uniform
                 ? rfx_dev_count_reads_w(ctx, d_words.as<uint64_t>(), n_reads, wpr, (int)maxlen, k, prm->front_clip, prm->end_clip,
                                         prm->min_cov, prm->max_cov, wk.as<uint64_t>(), wc.as<int64_t>(), kcap, &m, &dist, &inst)
@@ -1543,8 +1542,8 @@ int rfx_assemble_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_o
             break;
         }
         DevBuf ak, ac;
-        RFX_HIP(ak.alloc((size_t)std::max<int64_t>(m, 1) * aw * 8, ctx->stream));
-        RFX_HIP(ac.alloc((size_t)std::max<int64_t>(m, 1) * 4, ctx->stream));
+        RFX_ALLOC(ak, uint64_t, (size_t)std::max<int64_t>(m, 1) * aw);
+        RFX_ALLOC(ac, int32_t, std::max<int64_t>(m, 1));
         int64_t m2 = 0;
         RFX_TRY(counter_to_asm(ctx, wk.as<uint64_t>(), wc.as<int64_t>(), m, k, prm->min_cov, prm->max_cov, ak.as<uint64_t>(),
                                ac.as<int32_t>(), &m2));
@@ -1564,8 +1563,8 @@ int rfx_assemble_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_o
     int64_t m = 0, dist = 0;
     int64_t kcap = assemble_first_kcap(n_inst);
     for (;;) {                                      // survivors are few; grow on RFX_E_CAP
-        RFX_HIP(d_keys.alloc((size_t)kcap * 8, ctx->stream));
-        RFX_HIP(d_counts.alloc((size_t)kcap * 4, ctx->stream));
+        RFX_ALLOC(d_keys, uint64_t, kcap);
+        RFX_ALLOC(d_counts, int32_t, kcap);
         const int st = count_filter(ctx, &rs, nullptr, 0, prm->min_cov, prm->max_cov, prm->twin, nullptr, 0,
                                     d_keys.as<uint64_t>(), d_counts.as<int32_t>(), kcap, &m, &dist);
         if (st == RFX_E_CAP && m > kcap) { kcap = m; continue; }
@@ -1584,7 +1583,7 @@ int rfx_assemble_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_o
 namespace {
 bool fx2_contigs_ok(const rfx_contigs_packed *p) { return p && p->words && p->word_off && p->len; }
 int fx2_params(rfx_ctx *ctx, const rfx_fix_params *p, int P) {
-    if (!p || P < 1 || P > 63) return RFX_E_ARG;
+    if (!p || !parts_ok(P)) return RFX_E_ARG;
     if (p->max_k < 31 || p->max_k > 124) { ctx->last_error = "contig fixing, round two: max_k must be 31..124"; return RFX_E_ARG; }
     if (p->max_iteration < -1) { ctx->last_error = "contig fixing, round two: max_iteration below -1"; return RFX_E_ARG; }
     return RFX_OK;
@@ -1604,7 +1603,7 @@ int fx2_text_call(rfx_ctx *ctx, int ends, const rfx_contigs_packed *d_in, const 
 extern "C" {
 
 int rfx_dev_fix2_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, rfx_dyn_packed *d_out) try {
-    if (!ctx || !dyn_packed_out_ok(d_out) || n_rows < 0 || (n_rows > 0 && (!d_text || !d_row_off))) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_out_ok(d_out) || !text_rows_ok(d_text, d_row_off, n_rows)) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a;
     RFX_TRY(fx2_binarize(ctx, d_text, d_row_off, n_rows, a));
@@ -1651,7 +1650,7 @@ int rfx_dev_fix2_ends_text(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const i
 // copy back each.  A short buffer: RFX_E_CAP with BOTH lengths set and NEITHER buffer written
 int rfx_fix2_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
                   int64_t *out_len, char *ends_out, int64_t ends_cap, int64_t *ends_len) try {
-    if (!ctx || n_rows < 0 || (n_rows > 0 && (!text || !row_off)) || !out_len || !ends_len || cap < 0 || (cap > 0 && !out) || ends_cap < 0 ||
+    if (!ctx || !text_rows_ok(text, row_off, n_rows) || !out_len || !ends_len || cap < 0 || (cap > 0 && !out) || ends_cap < 0 ||
         (ends_cap > 0 && !ends_out))
         return RFX_E_ARG;
     RFX_TRY(fx2_params(ctx, params, P));
@@ -1661,21 +1660,17 @@ int rfx_fix2_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_
     Fx2Plan plan;
     int64_t t_rows = 0, t_ends = 0;
     RFX_TRY(dyn_upload_text(ctx, text, row_off, n_rows, d_text, d_off));
-    RFX_TRY(fx2_binarize(ctx, (const char *)d_text.p, (const int64_t *)d_off.as<int64_t>(), n_rows, a));
+    RFX_TRY(fx2_binarize(ctx, (const char *)d_text.p, d_off.as<int64_t>(), n_rows, a));
     RFX_TRY(fx2_run(ctx, a, P, params->scramble, params->max_iteration, b));
     RFX_TRY(fx2_contigs_plan(ctx, b, params->max_k, plan));
     const size_t m = (size_t)std::max<int64_t>(plan.m, 1);
-    RFX_HIP(w.alloc((size_t)std::max<int64_t>(plan.words, 1) * 8, ctx->stream)); RFX_HIP(woff.alloc((m + 1) * 8, ctx->stream));
-    RFX_HIP(len.alloc(m * 8, ctx->stream)); RFX_HIP(left.alloc(m * 4, ctx->stream)); RFX_HIP(right.alloc(m * 4, ctx->stream));
+    RFX_ALLOC(w, uint64_t, std::max<int64_t>(plan.words, 1)); RFX_ALLOC(woff, int64_t, m + 1);
+    RFX_ALLOC(len, int64_t, m); RFX_ALLOC(left, int32_t, m); RFX_ALLOC(right, int32_t, m);
     RFX_TRY(fx2_contigs_fill(ctx, b, plan, w.as<uint64_t>(), woff.as<int64_t>(), len.as<int64_t>(), left.as<int32_t>(), right.as<int32_t>()));
     const Fx2View v{plan.m, w.as<uint64_t>(), woff.as<int64_t>(), len.as<int64_t>(), left.as<int32_t>(), right.as<int32_t>()};
     RFX_TRY(fx2_text(ctx, v, 0, nullptr, 0, &t_rows, &d_rows));
     RFX_TRY(fx2_text(ctx, v, 1, nullptr, 0, &t_ends, &d_ends));
-    *out_len = t_rows; *ends_len = t_ends;
-    if (t_rows > cap || t_ends > ends_cap) return RFX_E_CAP;         // (nothing written)
-    if (t_rows > 0) RFX_HIP(hipMemcpyAsync(out, d_rows.p, (size_t)t_rows, hipMemcpyDeviceToHost, ctx->stream));
-    if (t_ends > 0) RFX_HIP(hipMemcpyAsync(ends_out, d_ends.p, (size_t)t_ends, hipMemcpyDeviceToHost, ctx->stream));
-    return sync_checked(ctx);
+    return text_to_host(ctx, {{d_rows, t_rows, out, cap, out_len}, {d_ends, t_ends, ends_out, ends_cap, ends_len}}, false);
 } RFX_API_CATCH(ctx)
 
 }  // extern "C"

@@ -232,37 +232,34 @@ static int sharded_count_kmers(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_word
     auto bucket = [&]() -> int {
         if (d_read_len) RFX_TRY(rfx::ragged_instances(ctx, d_read_len, n_reads, k, fc, ec, &N, true));
         if (N >= ((int64_t)1 << 32) && !elems) { ctx->last_error = "rfx_dev_sharded_count (k-mer units): at most 2^32 - 1 instances per rank and call"; return RFX_E_LIMIT; }
-        RFX_HIP(units.alloc((size_t)std::max<int64_t>(1, N) * W * 8, ctx->stream));
+        RFX_ALLOC(units, uint64_t, (size_t)std::max<int64_t>(1, N) * W);
         if (N == 0) return RFX_OK;
         if (elems) {
             DevBuf doff;
-            RFX_HIP(doff.alloc((size_t)(world + 1) * 8, ctx->stream));
+            RFX_ALLOC(doff, int64_t, world + 1);
             return rfx::bucket_wide_n_by_owner(ctx, d_words, n_reads, wpr, nk, k, fc, d_read_len, ec, world, units.as<uint64_t>(),
                                                doff.as<int64_t>(), hoff);
         }
         if (!wide) {
             rfx::ReadStore rs{d_words, n_reads, wpr, read_len, k, fc, ec};
             DevBuf doff;
-            RFX_HIP(doff.alloc((size_t)(world + 1) * 8, ctx->stream));
+            RFX_ALLOC(doff, int64_t, world + 1);
             RFX_TRY(rfx::bucket_by_owner(ctx, &rs, world, units.as<uint64_t>(), N, doff.as<int64_t>(), hoff));
             return RFX_OK;
         }
         DevBuf aos, owner, idx, tk, tv, doff;
-        RFX_HIP(aos.alloc((size_t)N * W * 8, ctx->stream));
-        RFX_HIP(owner.alloc((size_t)N * 8, ctx->stream));
-        RFX_HIP(idx.alloc((size_t)N * 4, ctx->stream));
-        RFX_HIP(tk.alloc((size_t)N * 8, ctx->stream));
-        RFX_HIP(tv.alloc((size_t)N * 4, ctx->stream));
-        RFX_HIP(doff.alloc((size_t)(world + 1) * 8, ctx->stream));
+        RFX_ALLOC(aos, uint64_t, (size_t)N * W);
+        RFX_ALLOC(owner, uint64_t, N);
+        RFX_ALLOC(idx, uint32_t, N);
+        RFX_ALLOC(tk, uint64_t, N);
+        RFX_ALLOC(tv, uint32_t, N);
+        RFX_ALLOC(doff, int64_t, world + 1);
         RFX_TRY(rfx::extract_w(ctx, d_words, wpr, nullptr, nk, n_reads, k, fc, aos.as<uint64_t>(), N, 1));
         const unsigned g = (unsigned)ceil_div(N, 256);
-        hipLaunchKernelGGL(k_owner_w, dim3(g), dim3(256), 0, ctx->stream, (const uint64_t *)aos.as<uint64_t>(), N, W, world, owner.as<uint64_t>(), idx.as<uint32_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_owner_w, dim3(g), dim3(256), 0, aos.as<uint64_t>(), N, W, world, owner.as<uint64_t>(), idx.as<uint32_t>());
         RFX_TRY(rfx::sort_pairs(ctx, owner.as<uint64_t>(), idx.as<uint32_t>(), N, 8, tk.as<uint64_t>(), tv.as<uint32_t>()));
-        hipLaunchKernelGGL(k_gather_w, dim3(g), dim3(256), 0, ctx->stream, (const uint64_t *)aos.as<uint64_t>(), (const uint32_t *)idx.as<uint32_t>(), N, W, units.as<uint64_t>());
-        RFX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_owner_counts, dim3(1), dim3(128), 0, ctx->stream, (const uint64_t *)owner.as<uint64_t>(), N, world, doff.as<int64_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_gather_w, dim3(g), dim3(256), 0, aos.as<uint64_t>(), idx.as<uint32_t>(), N, W, units.as<uint64_t>());
+        RFX_LAUNCH(k_owner_counts, dim3(1), dim3(128), 0, owner.as<uint64_t>(), N, world, doff.as<int64_t>());
         RFX_HIP(hipMemcpyAsync(hoff, doff.p, (size_t)(world + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
         RFX_TRY(sync_checked(ctx));
         return RFX_OK;
@@ -323,7 +320,7 @@ static int sharded_count_kmers(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_word
         st_cnt = rfx::count_filter_w2(ctx, recv.as<uint64_t>(), n_in, k, min_cov, max_cov, d_out_keys, (int64_t *)d_out_counts, cap, &m, &distinct);
     } else {
         auto cnt = [&]() -> int {
-            RFX_HIP(soa.alloc((size_t)std::max<int64_t>(1, n_in) * W * 8, ctx->stream));
+            RFX_ALLOC(soa, uint64_t, (size_t)std::max<int64_t>(1, n_in) * W);
             if (n_in > 0) RFX_TRY(rfx::aos_to_soa(ctx, recv.as<uint64_t>(), n_in, W, soa.as<uint64_t>()));
             return rfx::count_filter_w(ctx, soa.as<uint64_t>(), n_in, k, min_cov, max_cov, d_out_keys, (int64_t *)d_out_counts, cap, &m, &distinct);
         };
@@ -567,8 +564,8 @@ int rfx_dev_sharded_count(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_words, co
                 RFX_TRY(sync_checked(ctx));
             } else {
                 DevBuf tk, tv;
-                RFX_HIP(tk.alloc((size_t)m * 8, ctx->stream));
-                RFX_HIP(tv.alloc((size_t)m * 4, ctx->stream));
+                RFX_ALLOC(tk, uint64_t, m);
+                RFX_ALLOC(tv, uint32_t, m);
                 RFX_TRY(rfx_dev_sort_pairs(ctx, d_out_keys, (uint32_t *)d_out_counts, m, 2 * k, tk.as<uint64_t>(), tv.as<uint32_t>()));
                 RFX_TRY(sync_checked(ctx));
             }
@@ -690,9 +687,9 @@ int rfx_sharded_assemble_reads(rfx_ctx *ctx, rfx_comm *c, const uint8_t *bases, 
     // so that a rank that cannot go on does not leave its peers waiting inside one
     auto prepare = [&]() -> int {
         RFX_HIP(d_bases.alloc((size_t)std::max<int64_t>(nb, 1), ctx->stream));
-        RFX_HIP(d_off.alloc((size_t)(n_reads + 1) * 8, ctx->stream));
-        RFX_HIP(d_words.alloc((size_t)std::max<int64_t>(n_reads, 1) * wpr * 8, ctx->stream));
-        RFX_HIP(d_len.alloc((size_t)std::max<int64_t>(n_reads, 1) * 4, ctx->stream));
+        RFX_ALLOC(d_off, int64_t, n_reads + 1);
+        RFX_ALLOC(d_words, uint64_t, (size_t)std::max<int64_t>(n_reads, 1) * wpr);
+        RFX_ALLOC(d_len, uint32_t, std::max<int64_t>(n_reads, 1));
         std::vector<int64_t> off((size_t)n_reads + 1, 0);
         for (int64_t r = 0; r <= n_reads && n_reads > 0; r++) off[(size_t)r] = read_off[r] - read_off[0];
         if (nb > 0) RFX_HIP(hipMemcpyAsync(d_bases.p, bases + read_off[0], (size_t)nb, hipMemcpyHostToDevice, ctx->stream));

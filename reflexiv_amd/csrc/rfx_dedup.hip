@@ -380,8 +380,8 @@ __global__ __launch_bounds__(256) void k_dd_unpack(const uint64_t *__restrict__ 
 }
 
 static int dd_alloc_meta(rfx_ctx *ctx, DdSet &d) {               // the device copies of h_woff / h_len
-    RFX_HIP(d.woff.alloc((size_t)(d.n + 1) * 8, ctx->stream));
-    RFX_HIP(d.len.alloc((size_t)std::max<int64_t>(d.n, 1) * 8, ctx->stream));
+    RFX_ALLOC(d.woff, int64_t, d.n + 1);
+    RFX_ALLOC(d.len, int64_t, std::max<int64_t>(d.n, 1));
     RFX_HIP(hipMemcpyAsync(d.woff.p, d.h_woff.data(), (size_t)(d.n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     if (d.n) RFX_HIP(hipMemcpyAsync(d.len.p, d.h_len.data(), (size_t)d.n * 8, hipMemcpyHostToDevice, ctx->stream));
     return RFX_OK;
@@ -400,16 +400,15 @@ static int dd_pack_host(rfx_ctx *ctx, const uint8_t *bases, const int64_t *off, 
     }
     d.words = d.h_woff[(size_t)n];
     const int64_t nb = rel[(size_t)n];
-    RFX_HIP(d.w.alloc((size_t)std::max<int64_t>(d.words, 1) * 8, ctx->stream));
+    RFX_ALLOC(d.w, uint64_t, std::max<int64_t>(d.words, 1));
     RFX_TRY(dd_alloc_meta(ctx, d));
     if (d.words > 0) {
         DevBuf stage, boff;
-        RFX_HIP(stage.alloc((size_t)nb, ctx->stream)); RFX_HIP(boff.alloc((size_t)(n + 1) * 8, ctx->stream));
+        RFX_HIP(stage.alloc((size_t)nb, ctx->stream)); RFX_ALLOC(boff, int64_t, n + 1);
         RFX_HIP(hipMemcpyAsync(stage.p, bases + off[0], (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
         RFX_HIP(hipMemcpyAsync(boff.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_dd_pack, RFX_GRID(d.words), (const uint8_t *)stage.as<uint8_t>(), (const int64_t *)boff.as<int64_t>(),
-                           (const int64_t *)d.woff.as<int64_t>(), (const int64_t *)d.len.as<int64_t>(), n, d.words, d.w.as<uint64_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_dd_pack, d.words, stage.as<uint8_t>(), boff.as<int64_t>(),
+                     d.woff.as<int64_t>(), d.len.as<int64_t>(), n, d.words, d.w.as<uint64_t>());
         RFX_TRY(sync_checked(ctx));                               // (`rel` and the staging buffers are read until here)
     }
     return sync_checked(ctx);
@@ -422,11 +421,10 @@ static int dd_unpack_host(rfx_ctx *ctx, const DdSet &d, uint8_t *out_bases, int6
     for (int64_t i = 0; i <= d.n; i++) out_off[i] = boff[(size_t)i];
     if (nb == 0) return RFX_OK;
     DevBuf stage, d_boff;
-    RFX_HIP(stage.alloc((size_t)nb, ctx->stream)); RFX_HIP(d_boff.alloc((size_t)(d.n + 1) * 8, ctx->stream));
+    RFX_HIP(stage.alloc((size_t)nb, ctx->stream)); RFX_ALLOC(d_boff, int64_t, d.n + 1);
     RFX_HIP(hipMemcpyAsync(d_boff.p, boff.data(), (size_t)(d.n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_dd_unpack, RFX_GRID(d.words), (const uint64_t *)d.w.as<uint64_t>(), (const int64_t *)d.woff.as<int64_t>(),
-                       (const int64_t *)d.len.as<int64_t>(), (const int64_t *)d_boff.as<int64_t>(), d.n, d.words, stage.as<uint8_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_dd_unpack, d.words, d.w.as<uint64_t>(), d.woff.as<int64_t>(),
+                 d.len.as<int64_t>(), d_boff.as<int64_t>(), d.n, d.words, stage.as<uint8_t>());
     RFX_HIP(hipMemcpyAsync(out_bases, stage.p, (size_t)nb, hipMemcpyDeviceToHost, ctx->stream));
     return sync_checked(ctx);
 }
@@ -497,9 +495,8 @@ static int dd_from_text(rfx_ctx *ctx, const char *d_text, int64_t len, DdSet &d)
     DevBuf pv, hdrline, hpos, gb;
     if (len > 0) {
         DevBuf v;
-        RFX_HIP(v.alloc((size_t)len * 8, ctx->stream)); RFX_HIP(pv.alloc((size_t)(len + 1) * 8, ctx->stream));
-        hipLaunchKernelGGL(k_dd_text_starts, RFX_GRID(len), d_text, len, v.as<uint64_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_ALLOC(v, uint64_t, len); RFX_ALLOC(pv, uint64_t, len + 1);
+        RFX_LAUNCH_N(k_dd_text_starts, len, d_text, len, v.as<uint64_t>());
         RFX_TRY(exclusive_scan_u64(ctx, v.as<uint64_t>(), pv.as<uint64_t>(), len));
         uint64_t tot = 0;
         RFX_TRY(small_readback(ctx, &tot, pv.as<uint64_t>() + len, 8));
@@ -507,39 +504,36 @@ static int dd_from_text(rfx_ctx *ctx, const char *d_text, int64_t len, DdSet &d)
         const int64_t nl = (int64_t)(uint32_t)tot;
         if (n > 0) {
             DevBuf isb;
-            RFX_HIP(hdrline.alloc((size_t)nl, ctx->stream)); RFX_HIP(hpos.alloc((size_t)n * 8, ctx->stream));
-            RFX_HIP(isb.alloc((size_t)len * 4, ctx->stream)); RFX_HIP(gb.alloc((size_t)(len + 1) * 8, ctx->stream));
-            hipLaunchKernelGGL(k_dd_text_lines, RFX_GRID(len), d_text, len, (const uint64_t *)pv.as<uint64_t>(), hdrline.as<uint8_t>(), hpos.as<int64_t>());
-            hipLaunchKernelGGL(k_dd_text_isbase, RFX_GRID(len), d_text, len, (const uint64_t *)pv.as<uint64_t>(), (const uint8_t *)hdrline.as<uint8_t>(),
-                               isb.as<uint32_t>());
-            RFX_HIP(hipGetLastError());
+            RFX_HIP(hdrline.alloc((size_t)nl, ctx->stream)); RFX_ALLOC(hpos, int64_t, n);
+            RFX_ALLOC(isb, uint32_t, len); RFX_ALLOC(gb, uint64_t, len + 1);
+            RFX_LAUNCH_N(k_dd_text_lines, len, d_text, len, pv.as<uint64_t>(), hdrline.as<uint8_t>(), hpos.as<int64_t>());
+            RFX_LAUNCH_N(k_dd_text_isbase, len, d_text, len, pv.as<uint64_t>(), hdrline.as<uint8_t>(),
+                         isb.as<uint32_t>());
             RFX_TRY(exclusive_scan_u32_to_u64(ctx, isb.as<uint32_t>(), gb.as<uint64_t>(), len));
         }
     }
     d.n = n;
-    RFX_HIP(d.woff.alloc((size_t)(n + 1) * 8, ctx->stream));
-    RFX_HIP(d.len.alloc((size_t)std::max<int64_t>(n, 1) * 8, ctx->stream));
+    RFX_ALLOC(d.woff, uint64_t, n + 1);
+    RFX_ALLOC(d.len, int64_t, std::max<int64_t>(n, 1));
     if (n == 0) {
         RFX_HIP(d.w.alloc(8, ctx->stream));
         RFX_HIP(hipMemsetAsync(d.woff.p, 0, 8, ctx->stream));
         return sync_checked(ctx);
     }
     DevBuf cw;
-    RFX_HIP(cw.alloc((size_t)n * 8, ctx->stream));
-    hipLaunchKernelGGL(k_dd_text_sizes, RFX_GRID(n), (const int64_t *)hpos.as<int64_t>(), n, (const uint64_t *)gb.as<uint64_t>(), len, d.len.as<int64_t>(),
-                       cw.as<uint64_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_ALLOC(cw, uint64_t, n);
+    RFX_LAUNCH_N(k_dd_text_sizes, n, hpos.as<int64_t>(), n, gb.as<uint64_t>(), len, d.len.as<int64_t>(),
+                 cw.as<uint64_t>());
     RFX_TRY(exclusive_scan_u64(ctx, cw.as<uint64_t>(), d.woff.as<uint64_t>(), n));
     d.h_woff.resize((size_t)n + 1); d.h_len.resize((size_t)n);
     RFX_HIP(hipMemcpyAsync(d.h_woff.data(), d.woff.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
     RFX_HIP(hipMemcpyAsync(d.h_len.data(), d.len.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
     RFX_TRY(sync_checked(ctx));
     d.words = d.h_woff[(size_t)n];
-    RFX_HIP(d.w.alloc((size_t)std::max<int64_t>(d.words, 1) * 8, ctx->stream));
+    RFX_ALLOC(d.w, uint64_t, std::max<int64_t>(d.words, 1));
     if (d.words > 0) {
-        hipLaunchKernelGGL(k_dd_text_fill, RFX_GRID(d.words), d_text, len, (const uint64_t *)gb.as<uint64_t>(), (const int64_t *)hpos.as<int64_t>(),
-                           (const int64_t *)d.len.as<int64_t>(), (const int64_t *)d.woff.as<int64_t>(), n, d.words, d.w.as<uint64_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_dd_text_fill, d.words, d_text, len, gb.as<uint64_t>(), hpos.as<int64_t>(),
+                     d.len.as<int64_t>(), d.woff.as<int64_t>(), n, d.words, d.w.as<uint64_t>());
     }
     return sync_checked(ctx);
 }
@@ -606,9 +600,8 @@ static int dd_to_text(rfx_ctx *ctx, const DdSet &d, int64_t min_contig, char *d_
     *total = 0;
     if (n == 0) return RFX_OK;
     DevBuf sz, toff;
-    RFX_HIP(sz.alloc((size_t)n * 8, ctx->stream)); RFX_HIP(toff.alloc((size_t)(n + 1) * 8, ctx->stream));
-    hipLaunchKernelGGL(k_dd_out_sizes, RFX_GRID(n), (const int64_t *)d.len.as<int64_t>(), n, min_contig, sz.as<uint64_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_ALLOC(sz, uint64_t, n); RFX_ALLOC(toff, uint64_t, n + 1);
+    RFX_LAUNCH_N(k_dd_out_sizes, n, d.len.as<int64_t>(), n, min_contig, sz.as<uint64_t>());
     RFX_TRY(exclusive_scan_u64(ctx, sz.as<uint64_t>(), toff.as<uint64_t>(), n));
     uint64_t t = 0;
     RFX_TRY(small_readback(ctx, &t, toff.as<uint64_t>() + n, 8));
@@ -619,11 +612,10 @@ static int dd_to_text(rfx_ctx *ctx, const DdSet &d, int64_t min_contig, char *d_
     }
     const int64_t lim = std::min<int64_t>(*total, cap);
     if (lim > 0) {
-        hipLaunchKernelGGL(k_dd_out_heads, RFX_GRID(n), (const int64_t *)d.len.as<int64_t>(), n, min_contig, (const uint64_t *)toff.as<uint64_t>(), lim, d_text);
+        RFX_LAUNCH_N(k_dd_out_heads, n, d.len.as<int64_t>(), n, min_contig, toff.as<uint64_t>(), lim, d_text);
         if (d.words > 0)
-            hipLaunchKernelGGL(k_dd_out_bases, RFX_GRID(d.words), (const uint64_t *)d.w.as<uint64_t>(), (const int64_t *)d.woff.as<int64_t>(),
-                               (const int64_t *)d.len.as<int64_t>(), n, d.words, min_contig, (const uint64_t *)toff.as<uint64_t>(), lim, d_text);
-        RFX_HIP(hipGetLastError());
+            RFX_LAUNCH_N(k_dd_out_bases, d.words, d.w.as<uint64_t>(), d.woff.as<int64_t>(),
+                         d.len.as<int64_t>(), n, d.words, min_contig, toff.as<uint64_t>(), lim, d_text);
     }
     return sync_checked(ctx);
 }
@@ -694,36 +686,32 @@ static int dedup_run(rfx_ctx *ctx, const DdSet &in, DdSet &out, int64_t *round_n
         std::vector<uint64_t> cand;                         // pair ids seen at least twice, ascending
         if (M > 0) {
             DevBuf d_meta, key, val, attr, tk, tv, pair, pk, pcnt, ck;
-            RFX_HIP(d_meta.alloc((size_t)(4 * nc + 1) * 8, ctx->stream));
+            RFX_ALLOC(d_meta, int64_t, 4 * nc + 1);
             int64_t *dm = d_meta.as<int64_t>();
             RFX_HIP(hipMemcpyAsync(dm, coff.data(), (size_t)nc * 8, hipMemcpyHostToDevice, ctx->stream));
             RFX_HIP(hipMemcpyAsync(dm + nc, clen.data(), (size_t)nc * 8, hipMemcpyHostToDevice, ctx->stream));
             RFX_HIP(hipMemcpyAsync(dm + 2 * nc, cid.data(), (size_t)nc * 8, hipMemcpyHostToDevice, ctx->stream));
             RFX_HIP(hipMemcpyAsync(dm + 3 * nc, moff.data(), (size_t)(nc + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-            RFX_HIP(key.alloc((size_t)M * 8, ctx->stream)); RFX_HIP(tk.alloc((size_t)M * 8, ctx->stream));
-            RFX_HIP(val.alloc((size_t)M * 4, ctx->stream)); RFX_HIP(tv.alloc((size_t)M * 4, ctx->stream));
-            RFX_HIP(attr.alloc((size_t)M * 8, ctx->stream)); RFX_HIP(pair.alloc((size_t)M * 8, ctx->stream));
-            RFX_HIP(pk.alloc((size_t)M * 8, ctx->stream)); RFX_HIP(ck.alloc((size_t)M * 8, ctx->stream));
+            RFX_ALLOC(key, uint64_t, M); RFX_ALLOC(tk, uint64_t, M);
+            RFX_ALLOC(val, uint32_t, M); RFX_ALLOC(tv, uint32_t, M);
+            RFX_ALLOC(attr, int64_t, M); RFX_ALLOC(pair, int64_t, M);
+            RFX_ALLOC(pk, uint64_t, M); RFX_ALLOC(ck, uint64_t, M);
             RFX_HIP(pcnt.alloc(16, ctx->stream));
-            hipLaunchKernelGGL(k_dd_markers, RFX_GRID(M), pin, (const int64_t *)dm, (const int64_t *)(dm + nc), (const int64_t *)(dm + 2 * nc),
-                               (const int64_t *)(dm + 3 * nc), nc, M, both, key.as<uint64_t>(), val.as<uint32_t>(), attr.as<int64_t>());
-            RFX_HIP(hipGetLastError());
+            RFX_LAUNCH_N(k_dd_markers, M, pin, (const int64_t *)dm, (const int64_t *)(dm + nc), (const int64_t *)(dm + 2 * nc),
+                         (const int64_t *)(dm + 3 * nc), nc, M, both, key.as<uint64_t>(), val.as<uint32_t>(), attr.as<int64_t>());
             RFX_TRY(sort_pairs(ctx, key.as<uint64_t>(), val.as<uint32_t>(), M, 64, tk.as<uint64_t>(), tv.as<uint32_t>()));
-            hipLaunchKernelGGL(k_dd_select, RFX_GRID(M), (const uint64_t *)key.as<uint64_t>(), (const uint32_t *)val.as<uint32_t>(),
-                               (const int64_t *)attr.as<int64_t>(), M, pair.as<int64_t>());
-            RFX_HIP(hipGetLastError());
+            RFX_LAUNCH_N(k_dd_select, M, key.as<uint64_t>(), val.as<uint32_t>(),
+                         attr.as<int64_t>(), M, pair.as<int64_t>());
             RFX_HIP(hipMemsetAsync(pcnt.p, 0, 16, ctx->stream));
-            hipLaunchKernelGGL(k_dd_compact_pairs, RFX_GRID(M), (const int64_t *)pair.as<int64_t>(), M, pk.as<uint64_t>(), pcnt.as<unsigned long long>());
-            RFX_HIP(hipGetLastError());
+            RFX_LAUNCH_N(k_dd_compact_pairs, M, pair.as<int64_t>(), M, pk.as<uint64_t>(), pcnt.as<unsigned long long>());
             unsigned long long np = 0;
             RFX_HIP(hipMemcpyAsync(&np, pcnt.p, 8, hipMemcpyDeviceToHost, ctx->stream));
             RFX_TRY(sync_checked(ctx));
             if (np > 1) {
                 RFX_TRY(sort_pairs(ctx, pk.as<uint64_t>(), val.as<uint32_t>(), (int64_t)np, 64, tk.as<uint64_t>(), tv.as<uint32_t>()));
                 RFX_HIP(hipMemsetAsync(pcnt.p, 0, 16, ctx->stream));
-                hipLaunchKernelGGL(k_dd_pair_runs, RFX_GRID((int64_t)np), (const uint64_t *)pk.as<uint64_t>(), (int64_t)np, ck.as<uint64_t>(),
-                                   pcnt.as<unsigned long long>());
-                RFX_HIP(hipGetLastError());
+                RFX_LAUNCH_N(k_dd_pair_runs, (int64_t)np, pk.as<uint64_t>(), (int64_t)np, ck.as<uint64_t>(),
+                             pcnt.as<unsigned long long>());
                 unsigned long long ncand = 0;
                 RFX_HIP(hipMemcpyAsync(&ncand, pcnt.p, 8, hipMemcpyDeviceToHost, ctx->stream));
                 RFX_TRY(sync_checked(ctx));
@@ -773,7 +761,7 @@ static int dedup_run(rfx_ctx *ctx, const DdSet &in, DdSet &out, int64_t *round_n
         }
         DevBuf d_mrows;
         if (!mrow.empty()) {
-            RFX_HIP(d_mrows.alloc(mwords.size() * 8, ctx->stream));
+            RFX_ALLOC(d_mrows, uint64_t, mwords.size());
             RFX_HIP(hipMemcpyAsync(d_mrows.p, mwords.data(), mwords.size() * 8, hipMemcpyHostToDevice, ctx->stream));
             for (size_t q = 0; q < mrow.size(); q++) rows[mrow[q]].w = d_mrows.as<uint64_t>() + 2 * q;
         }
@@ -806,7 +794,7 @@ static int dedup_run(rfx_ctx *ctx, const DdSet &in, DdSet &out, int64_t *round_n
             g0 = g1;
         }
         DevBuf workA, workB;
-        RFX_HIP(workA.alloc((size_t)std::max<int64_t>(wused, 1) * 8, ctx->stream)); RFX_HIP(workB.alloc((size_t)std::max<int64_t>(wused, 1) * 8, ctx->stream));
+        RFX_ALLOC(workA, uint64_t, std::max<int64_t>(wused, 1)); RFX_ALLOC(workB, uint64_t, std::max<int64_t>(wused, 1));
         uint64_t *const wa = workA.as<uint64_t>(), *const wb = workB.as<uint64_t>();
         DevBuf d_mb, d_eb, d_tkey, d_tpos, d_dist, d_dtmp, d_dval, d_dvtmp, d_cnt, d_seg, d_fd;
         RFX_HIP(d_cnt.alloc(16, ctx->stream));
@@ -814,10 +802,9 @@ static int dedup_run(rfx_ctx *ctx, const DdSet &in, DdSet &out, int64_t *round_n
             int64_t pre = 0;
             for (auto &e : eb) { e.pre = pre; pre += (e.a.n + e.b.n + 31) / 32; }
             if (eb.empty() || pre == 0) return RFX_OK;
-            RFX_HIP(d_eb.alloc(eb.size() * sizeof(EmitB), ctx->stream));
+            RFX_ALLOC(d_eb, EmitB, eb.size());
             RFX_HIP(hipMemcpyAsync(d_eb.p, eb.data(), eb.size() * sizeof(EmitB), hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(k_dd_emit, RFX_GRID(pre), (const EmitB *)d_eb.as<EmitB>(), (int64_t)eb.size(), pre);
-            RFX_HIP(hipGetLastError());
+            RFX_LAUNCH_N(k_dd_emit, pre, d_eb.as<EmitB>(), (int64_t)eb.size(), pre);
             RFX_TRY(sync_checked(ctx));                       // (`eb` is read by the queued copy until here)
             return RFX_OK;
         };
@@ -841,35 +828,32 @@ static int dedup_run(rfx_ctx *ctx, const DdSet &in, DdSet &out, int64_t *round_n
                 tslots += (int64_t)want; sthreads += G.ln / 15 + 1; qthreads += std::max<int64_t>(M.sn, 1);
             }
             if (nm == 0) continue;
-            RFX_HIP(d_mb.alloc((size_t)nm * sizeof(MergeB), ctx->stream));
-            RFX_HIP(d_tkey.alloc((size_t)tslots * 4, ctx->stream)); RFX_HIP(d_tpos.alloc((size_t)tslots * 4, ctx->stream));
+            RFX_ALLOC(d_mb, MergeB, nm);
+            RFX_ALLOC(d_tkey, uint32_t, tslots); RFX_ALLOC(d_tpos, uint32_t, tslots);
             const size_t dcap = (size_t)qthreads * 2 + 16;    // (two query passes may append)
-            RFX_HIP(d_dist.alloc(dcap * 8, ctx->stream)); RFX_HIP(d_dtmp.alloc(dcap * 8, ctx->stream));
-            RFX_HIP(d_dval.alloc(dcap * 4, ctx->stream)); RFX_HIP(d_dvtmp.alloc(dcap * 4, ctx->stream));
-            RFX_HIP(d_seg.alloc((size_t)(nm + 1) * 8, ctx->stream)); RFX_HIP(d_fd.alloc((size_t)nm * 4, ctx->stream));
+            RFX_ALLOC(d_dist, uint64_t, dcap); RFX_ALLOC(d_dtmp, uint64_t, dcap);
+            RFX_ALLOC(d_dval, uint32_t, dcap); RFX_ALLOC(d_dvtmp, uint32_t, dcap);
+            RFX_ALLOC(d_seg, int64_t, nm + 1); RFX_ALLOC(d_fd, int32_t, nm);
             RFX_HIP(hipMemcpyAsync(d_mb.p, mb.data(), (size_t)nm * sizeof(MergeB), hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(k_dd_fill, RFX_GRID(tslots), d_tkey.as<uint32_t>(), DD_EMPTY, tslots);
-            hipLaunchKernelGGL(k_dd_fill, RFX_GRID(tslots), d_tpos.as<uint32_t>(), 0xFFFFFFFFu, tslots);
-            hipLaunchKernelGGL(k_dd_seed_insert_b, RFX_GRID(sthreads), (const MergeB *)d_mb.as<MergeB>(), nm, sthreads, d_tkey.as<uint32_t>(), d_tpos.as<int32_t>());
-            RFX_HIP(hipGetLastError());
+            RFX_LAUNCH_N(k_dd_fill, tslots, d_tkey.as<uint32_t>(), DD_EMPTY, tslots);
+            RFX_LAUNCH_N(k_dd_fill, tslots, d_tpos.as<uint32_t>(), 0xFFFFFFFFu, tslots);
+            RFX_LAUNCH_N(k_dd_seed_insert_b, sthreads, d_mb.as<MergeB>(), nm, sthreads, d_tkey.as<uint32_t>(), d_tpos.as<int32_t>());
             RFX_HIP(hipMemsetAsync(d_cnt.p, 0, 16, ctx->stream));
             int key_bits = 33;
             while (((int64_t)1 << (key_bits - 33)) < nm) key_bits++;
             std::vector<int32_t> fd((size_t)nm, -1);
             // one query pass of the active merges + the vote on every active merge's (grown) list -> fd
             auto query_vote_b = [&]() -> int {
-                hipLaunchKernelGGL(k_dd_query_b, RFX_GRID(qthreads), (const MergeB *)d_mb.as<MergeB>(), nm, qthreads, (const uint32_t *)d_tkey.as<uint32_t>(),
-                                   (const int32_t *)d_tpos.as<int32_t>(), d_dist.as<uint64_t>(), d_cnt.as<unsigned long long>());
-                RFX_HIP(hipGetLastError());
+                RFX_LAUNCH_N(k_dd_query_b, qthreads, d_mb.as<MergeB>(), nm, qthreads, d_tkey.as<uint32_t>(),
+                             d_tpos.as<int32_t>(), d_dist.as<uint64_t>(), d_cnt.as<unsigned long long>());
                 unsigned long long c = 0;
                 RFX_HIP(hipMemcpyAsync(&c, d_cnt.p, 8, hipMemcpyDeviceToHost, ctx->stream));
                 RFX_TRY(sync_checked(ctx));
                 // (a second pass appends to a SORTED prefix: the whole list is sorted again, as Collections.sort does)
                 RFX_TRY(sort_pairs(ctx, d_dist.as<uint64_t>(), d_dval.as<uint32_t>(), (int64_t)c, key_bits, d_dtmp.as<uint64_t>(), d_dvtmp.as<uint32_t>()));
-                hipLaunchKernelGGL(k_dd_seg_bounds, RFX_GRID(nm + 1), (const uint64_t *)d_dist.as<uint64_t>(), (int64_t)c, nm, d_seg.as<int64_t>());
-                hipLaunchKernelGGL(k_dd_vote, dim3((unsigned)nm), dim3(64), 0, ctx->stream, (const uint64_t *)d_dist.as<uint64_t>(),
-                                   (const int64_t *)d_seg.as<int64_t>(), (const MergeB *)d_mb.as<MergeB>(), (int64_t)0, 0, d_fd.as<int32_t>());
-                RFX_HIP(hipGetLastError());
+                RFX_LAUNCH_N(k_dd_seg_bounds, nm + 1, d_dist.as<uint64_t>(), (int64_t)c, nm, d_seg.as<int64_t>());
+                RFX_LAUNCH(k_dd_vote, dim3((unsigned)nm), dim3(64), 0, d_dist.as<uint64_t>(),
+                           d_seg.as<int64_t>(), d_mb.as<MergeB>(), (int64_t)0, 0, d_fd.as<int32_t>());
                 std::vector<int32_t> got((size_t)nm);
                 RFX_HIP(hipMemcpyAsync(got.data(), d_fd.p, (size_t)nm * 4, hipMemcpyDeviceToHost, ctx->stream));
                 RFX_TRY(sync_checked(ctx));
@@ -937,7 +921,7 @@ static int dedup_run(rfx_ctx *ctx, const DdSet &in, DdSet &out, int64_t *round_n
             emit(G.lng, G.ln);
         }
         DevBuf &pool = pools[rnd & 1];                        // (round 3 takes the slot of round 1's output, which nobody reads any more)
-        RFX_HIP(pool.alloc((size_t)std::max<int64_t>(out_words, 1) * 8, ctx->stream));
+        RFX_ALLOC(pool, uint64_t, std::max<int64_t>(out_words, 1));
         for (auto &e : eb) e.dst = pool.as<uint64_t>() + e.pre;
         RFX_TRY(run_emits(eb));
         RFX_TRY(sync_checked(ctx));

@@ -50,14 +50,14 @@ static void dyn_swap(DynDev &x, DynDev &y) {
 // (the functions defined as rfx::... are the ones rfx_ksort.hip shares: rfx_internal.h declares them)
 int rfx::dyn_alloc(rfx_ctx *ctx, DynDev &d, int64_t n, int64_t words) {
     const size_t m = (size_t)std::max<int64_t>(n, 1);
-    RFX_HIP(d.key.alloc(m * DYN_KW * 8, ctx->stream));
+    RFX_ALLOC(d.key, uint64_t, m * DYN_KW);
     RFX_HIP(d.key_len.alloc(m, ctx->stream));
-    RFX_HIP(d.ext.alloc((size_t)std::max<int64_t>(words, 1) * 8, ctx->stream));
-    RFX_HIP(d.ext_off.alloc((size_t)(n + 1) * 8, ctx->stream));
-    RFX_HIP(d.ext_len.alloc(m * 4, ctx->stream));
-    RFX_HIP(d.marker.alloc(m * 4, ctx->stream));
-    RFX_HIP(d.left.alloc(m * 4, ctx->stream));
-    RFX_HIP(d.right.alloc(m * 4, ctx->stream));
+    RFX_ALLOC(d.ext, uint64_t, std::max<int64_t>(words, 1));
+    RFX_ALLOC(d.ext_off, uint64_t, n + 1);
+    RFX_ALLOC(d.ext_len, int32_t, m);
+    RFX_ALLOC(d.marker, int32_t, m);
+    RFX_ALLOC(d.left, int32_t, m);
+    RFX_ALLOC(d.right, int32_t, m);
     d.n = n; d.words = words;
     return RFX_OK;
 }
@@ -347,21 +347,18 @@ __global__ void k_dyn_pbase(const int64_t *__restrict__ ps, int P, const uint64_
 // in.words extension words)
 static int dyn_emit(rfx_ctx *ctx, const DynDev &in, const DevBuf &desc, int64_t ne, const uint64_t *d_pbase, int P, int start_marker, DynDev &out) {
     DevBuf ew;
-    RFX_HIP(ew.alloc((size_t)std::max<int64_t>(ne, 1) * 4, ctx->stream));
+    RFX_ALLOC(ew, uint32_t, std::max<int64_t>(ne, 1));
     RFX_TRY(dyn_alloc(ctx, out, ne, in.words));
     const DynView v = dyn_view(in);
     if (ne > 0) {
-        hipLaunchKernelGGL(k_dyn_sizes, RFX_GRID(ne), (const DynDesc *)desc.as<DynDesc>(), ne, v, d_pbase, P, start_marker, dyn_out(out), ew.as<uint32_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_dyn_sizes, ne, desc.as<DynDesc>(), ne, v, d_pbase, P, start_marker, dyn_out(out), ew.as<uint32_t>());
     }
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, ew.as<uint32_t>(), out.ext_off.as<uint64_t>(), ne));
     if (ne > 0) {
-        hipLaunchKernelGGL(k_dyn_emit_key, RFX_GRID(ne * DYN_KW), (const DynDesc *)desc.as<DynDesc>(), ne, v, d_pbase, P, start_marker, out.key.as<uint64_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_dyn_emit_key, ne * DYN_KW, desc.as<DynDesc>(), ne, v, d_pbase, P, start_marker, out.key.as<uint64_t>());
         if (in.words > 0) {
-            hipLaunchKernelGGL(k_dyn_emit_ext, RFX_GRID(in.words), (const DynDesc *)desc.as<DynDesc>(), ne, v, d_pbase, P, start_marker,
-                               (const int64_t *)out.ext_off.as<int64_t>(), out.ext.as<uint64_t>());
-            RFX_HIP(hipGetLastError());
+            RFX_LAUNCH_N(k_dyn_emit_ext, in.words, desc.as<DynDesc>(), ne, v, d_pbase, P, start_marker,
+                         out.ext_off.as<int64_t>(), out.ext.as<uint64_t>());
         }
     }
     return RFX_OK;
@@ -373,9 +370,8 @@ static int dyn_check_lengths(rfx_ctx *ctx, const DynDev &in, uint32_t *lmin) {
     if (in.n == 0) return RFX_OK;
     DevBuf flags;
     RFX_TRY(call_flags_init(ctx, flags));
-    hipLaunchKernelGGL(k_dyn_keys, RFX_GRID(in.n), (const uint64_t *)in.key.as<uint64_t>(), (const uint8_t *)in.key_len.as<uint8_t>(), in.n,
-                       (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, flags.as<CallFlags>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_dyn_keys, in.n, in.key.as<uint64_t>(), in.key_len.as<uint8_t>(), in.n,
+                 (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, flags.as<CallFlags>());
     CallFlags h{};
     RFX_TRY(call_flags_read(ctx, flags, nullptr, nullptr, nullptr, &h));
     if (h.bad & DYN_TOO_LONG) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
@@ -387,23 +383,17 @@ static int dyn_check_lengths(rfx_ctx *ctx, const DynDev &in, uint32_t *lmin) {
 // sort("k-1") + the cut into P logical partitions: in -> out (sorted), d_ps[P + 1]; *lmin = the shortest key
 int rfx::dyn_sort(rfx_ctx *ctx, const DynDev &in, int P, DynDev &out, DevBuf &d_ps, uint32_t *lmin) {
     const int64_t n = in.n;
-    RFX_HIP(d_ps.alloc((size_t)(P + 1) * 8, ctx->stream));
+    RFX_TRY(part_starts_alloc(ctx, d_ps, P, n == 0));
     *lmin = 0;
-    if (n == 0) {
-        RFX_TRY(dyn_alloc(ctx, out, 0, 0));
-        RFX_HIP(hipMemsetAsync(d_ps.p, 0, (size_t)(P + 1) * 8, ctx->stream));
-        RFX_HIP(hipMemsetAsync(out.ext_off.p, 0, 8, ctx->stream));
-        return RFX_OK;
-    }
+    if (n == 0) return dyn_empty(ctx, out);
     if (n >= ((int64_t)1 << 32)) { ctx->last_error = "dynamic-k sort: more than 2^32 records"; return RFX_E_LIMIT; }
     DevBuf blk, nblk, perm, tk, tv, keys, flags, desc;
-    RFX_HIP(blk.alloc((size_t)DYN_MAXB * n * 8, ctx->stream)); RFX_HIP(nblk.alloc((size_t)n * 8, ctx->stream));
-    RFX_HIP(perm.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(tk.alloc((size_t)n * 8, ctx->stream)); RFX_HIP(tv.alloc((size_t)n * 4, ctx->stream));
-    RFX_HIP(keys.alloc((size_t)n * 8, ctx->stream));
+    RFX_ALLOC(blk, uint64_t, (size_t)DYN_MAXB * n); RFX_ALLOC(nblk, uint64_t, n);
+    RFX_ALLOC(perm, uint32_t, n); RFX_ALLOC(tk, uint64_t, n); RFX_ALLOC(tv, uint32_t, n);
+    RFX_ALLOC(keys, uint64_t, n);
     RFX_TRY(call_flags_init(ctx, flags));
-    hipLaunchKernelGGL(k_dyn_keys, RFX_GRID(n), (const uint64_t *)in.key.as<uint64_t>(), (const uint8_t *)in.key_len.as<uint8_t>(), n, blk.as<uint64_t>(),
-                       nblk.as<uint64_t>(), perm.as<uint32_t>(), flags.as<CallFlags>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_dyn_keys, n, in.key.as<uint64_t>(), in.key_len.as<uint8_t>(), n, blk.as<uint64_t>(),
+                 nblk.as<uint64_t>(), perm.as<uint32_t>(), flags.as<CallFlags>());
     CallFlags h{};
     RFX_TRY(call_flags_read(ctx, flags, nullptr, nullptr, nullptr, &h));
     if (h.bad & DYN_TOO_LONG) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
@@ -414,18 +404,15 @@ int rfx::dyn_sort(rfx_ctx *ctx, const DynDev &in, int P, DynDev &out, DevBuf &d_
     for (int pass = -1; pass < nb_max; pass++) {
         const uint64_t *src = pass < 0 ? nblk.as<uint64_t>() : blk.as<uint64_t>() + (int64_t)(nb_max - 1 - pass) * n;
         if (pass < 0 && nb_max == 1) continue;                    // (every key has one block)
-        hipLaunchKernelGGL(k_dyn_gather_u64, RFX_GRID(n), src, (const uint32_t *)perm.as<uint32_t>(), n, keys.as<uint64_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_dyn_gather_u64, n, src, perm.as<uint32_t>(), n, keys.as<uint64_t>());
         RFX_TRY(sort_pairs(ctx, keys.as<uint64_t>(), perm.as<uint32_t>(), n, pass < 0 ? 8 : 64, tk.as<uint64_t>(), tv.as<uint32_t>()));
     }
     // gather the records through the permutation: the emission with "copy" descriptors
-    RFX_HIP(desc.alloc((size_t)n * sizeof(DynDesc), ctx->stream));
-    hipLaunchKernelGGL(k_dyn_perm_desc, RFX_GRID(n), (const uint32_t *)perm.as<uint32_t>(), n, desc.as<DynDesc>());
-    RFX_HIP(hipGetLastError());
+    RFX_ALLOC(desc, DynDesc, n);
+    RFX_LAUNCH_N(k_dyn_perm_desc, n, perm.as<uint32_t>(), n, desc.as<DynDesc>());
     RFX_TRY(dyn_emit(ctx, in, desc, n, nullptr, P, 0, out));
-    hipLaunchKernelGGL(k_dyn_part_starts, dim3(1), dim3(1), 0, ctx->stream, (const uint64_t *)out.key.as<uint64_t>(),
-                       (const uint8_t *)out.key_len.as<uint8_t>(), n, P, d_ps.as<int64_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH(k_dyn_part_starts, dim3(1), dim3(1), 0, out.key.as<uint64_t>(),
+               out.key_len.as<uint8_t>(), n, P, d_ps.as<int64_t>());
     return RFX_OK;
 }
 // one pass over sorted records: in (sorted), d_ps -> out, d_out_ps (optional)
@@ -433,40 +420,34 @@ int rfx::dyn_pass(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, ui
                   DynDev &out, int64_t *d_out_ps) {
     const int64_t n = in.n;
     DevBuf head, cnt, base, desc, pbase;
-    RFX_HIP(pbase.alloc((size_t)(P + 1) * 8, ctx->stream));
+    RFX_ALLOC(pbase, uint64_t, P + 1);
     if (n == 0) {
         RFX_HIP(hipMemsetAsync(pbase.p, 0, (size_t)(P + 1) * 8, ctx->stream));
         if (d_out_ps) RFX_HIP(hipMemsetAsync(d_out_ps, 0, (size_t)(P + 1) * 8, ctx->stream));
         RFX_HIP(desc.alloc(sizeof(DynDesc), ctx->stream));
         return dyn_emit(ctx, in, desc, 0, pbase.as<uint64_t>(), P, start_marker, out);
     }
-    RFX_HIP(head.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(cnt.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(base.alloc((size_t)(n + 1) * 8, ctx->stream));
-    RFX_HIP(desc.alloc((size_t)n * sizeof(DynDesc), ctx->stream));
+    RFX_ALLOC(head, uint32_t, n); RFX_ALLOC(cnt, uint32_t, n); RFX_ALLOC(base, uint64_t, n + 1);
+    RFX_ALLOC(desc, DynDesc, n);
     const DynView v = dyn_view(in);
-    hipLaunchKernelGGL(k_dyn_heads, RFX_GRID(n), v.key, n, d_ps, P, lmin, head.as<uint32_t>());
-    RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_dyn_walk<false>, dim3((unsigned)ceil_div(n, 128)), dim3(128), 0, ctx->stream, v, n, (const uint32_t *)head.as<uint32_t>(), stage,
-                       start_iteration, cnt.as<uint32_t>(), (const uint64_t *)nullptr, (DynDesc *)nullptr);
-    RFX_HIP(hipGetLastError());
-    RFX_TRY(exclusive_scan_u32_to_u64(ctx, cnt.as<uint32_t>(), base.as<uint64_t>(), n));
-    uint64_t ne = 0;
-    RFX_TRY(small_readback(ctx, &ne, base.as<uint64_t>() + n, 8));
-    hipLaunchKernelGGL(k_dyn_walk<true>, dim3((unsigned)ceil_div(n, 128)), dim3(128), 0, ctx->stream, v, n, (const uint32_t *)head.as<uint32_t>(), stage,
-                       start_iteration, (uint32_t *)nullptr, (const uint64_t *)base.as<uint64_t>(), desc.as<DynDesc>());
-    RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_dyn_pbase, dim3(1), dim3(64), 0, ctx->stream, d_ps, P, (const uint64_t *)base.as<uint64_t>(), n, ne, pbase.as<uint64_t>(), d_out_ps);
-    RFX_HIP(hipGetLastError());
-    return dyn_emit(ctx, in, desc, (int64_t)ne, pbase.as<uint64_t>(), P, start_marker, out);
+    RFX_LAUNCH_N(k_dyn_heads, n, v.key, n, d_ps, P, lmin, head.as<uint32_t>());
+    RFX_LAUNCH(k_dyn_walk<false>, dim3((unsigned)ceil_div(n, 128)), dim3(128), 0, v, n, head.as<uint32_t>(), stage,
+               start_iteration, cnt.as<uint32_t>(), (const uint64_t *)nullptr, (DynDesc *)nullptr);
+    int64_t ne = 0;
+    RFX_TRY(scan_keep(ctx, cnt.as<uint32_t>(), n, base.as<uint64_t>(), &ne));
+    RFX_LAUNCH(k_dyn_walk<true>, dim3((unsigned)ceil_div(n, 128)), dim3(128), 0, v, n, head.as<uint32_t>(), stage,
+               start_iteration, (uint32_t *)nullptr, base.as<uint64_t>(), desc.as<DynDesc>());
+    RFX_LAUNCH(k_dyn_pbase, dim3(1), dim3(64), 0, d_ps, P, base.as<uint64_t>(), n, (uint64_t)ne, pbase.as<uint64_t>(), d_out_ps);
+    return dyn_emit(ctx, in, desc, ne, pbase.as<uint64_t>(), P, start_marker, out);
 }
 namespace {
 
 static int dyn_reflect(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, DynDev &out) {
     DevBuf desc, pbase;
-    RFX_HIP(desc.alloc((size_t)std::max<int64_t>(in.n, 1) * sizeof(DynDesc), ctx->stream));
-    RFX_HIP(pbase.alloc((size_t)(P + 1) * 8, ctx->stream));
-    hipLaunchKernelGGL(k_dyn_identity_desc, RFX_GRID(in.n), in.n, desc.as<DynDesc>());
-    hipLaunchKernelGGL(k_dyn_copy_u64, dim3(1), dim3(64), 0, ctx->stream, d_ps, P + 1, pbase.as<uint64_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_ALLOC(desc, DynDesc, std::max<int64_t>(in.n, 1));
+    RFX_ALLOC(pbase, uint64_t, P + 1);
+    RFX_LAUNCH_N(k_dyn_identity_desc, in.n, in.n, desc.as<DynDesc>());
+    RFX_LAUNCH(k_dyn_copy_u64, dim3(1), dim3(64), 0, d_ps, P + 1, pbase.as<uint64_t>());
     return dyn_emit(ctx, in, desc, in.n, pbase.as<uint64_t>(), P, 2, out);
 }
 
@@ -522,8 +503,8 @@ static int dyn_pack_host(rfx_ctx *ctx, const rfx_dyn_records *h, DynDev &d) {
     }
     DevBuf kb, eb, ko, eo, ew, flags;
     RFX_HIP(kb.alloc((size_t)std::max<int64_t>(nk, 1), ctx->stream)); RFX_HIP(eb.alloc((size_t)std::max<int64_t>(ne, 1), ctx->stream));
-    RFX_HIP(ko.alloc((size_t)(n + 1) * 8, ctx->stream)); RFX_HIP(eo.alloc((size_t)(n + 1) * 8, ctx->stream));
-    RFX_HIP(ew.alloc((size_t)n * 4, ctx->stream));
+    RFX_ALLOC(ko, int64_t, n + 1); RFX_ALLOC(eo, int64_t, n + 1);
+    RFX_ALLOC(ew, uint32_t, n);
     RFX_TRY(call_flags_init(ctx, flags));
     if (nk) RFX_HIP(hipMemcpyAsync(kb.p, h->key, (size_t)nk, hipMemcpyHostToDevice, ctx->stream));
     if (ne) RFX_HIP(hipMemcpyAsync(eb.p, h->ext, (size_t)ne, hipMemcpyHostToDevice, ctx->stream));
@@ -532,21 +513,18 @@ static int dyn_pack_host(rfx_ctx *ctx, const rfx_dyn_records *h, DynDev &d) {
     RFX_HIP(hipMemcpyAsync(d.marker.p, h->marker, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     RFX_HIP(hipMemcpyAsync(d.left.p, h->left, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     RFX_HIP(hipMemcpyAsync(d.right.p, h->right, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_dyn_pack_sizes, RFX_GRID(n), (const int64_t *)ko.as<int64_t>(), (const int64_t *)eo.as<int64_t>(), n, d.key_len.as<uint8_t>(),
-                       d.ext_len.as<int32_t>(), ew.as<uint32_t>(), flags.as<CallFlags>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_dyn_pack_sizes, n, ko.as<int64_t>(), eo.as<int64_t>(), n, d.key_len.as<uint8_t>(),
+                 d.ext_len.as<int32_t>(), ew.as<uint32_t>(), flags.as<CallFlags>());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, ew.as<uint32_t>(), d.ext_off.as<uint64_t>(), n));
     CallFlags f{};
     RFX_TRY(call_flags_read(ctx, flags, nullptr, nullptr, nullptr, &f));
     if (f.bad & DYN_BAD_OFFSETS) { ctx->last_error = "dynamic-k: record offsets that run backwards"; return RFX_E_ARG; }
     if (f.bad & DYN_TOO_LONG) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
-    hipLaunchKernelGGL(k_dyn_pack_key, RFX_GRID(n * DYN_KW), (const uint8_t *)kb.as<uint8_t>(), (const int64_t *)ko.as<int64_t>(),
-                       (const uint8_t *)d.key_len.as<uint8_t>(), n, d.key.as<uint64_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_dyn_pack_key, n * DYN_KW, kb.as<uint8_t>(), ko.as<int64_t>(),
+                 d.key_len.as<uint8_t>(), n, d.key.as<uint64_t>());
     if (d.words > 0) {
-        hipLaunchKernelGGL(k_dyn_pack_ext, RFX_GRID(d.words), (const uint8_t *)eb.as<uint8_t>(), (const int64_t *)eo.as<int64_t>(),
-                           (const int32_t *)d.ext_len.as<int32_t>(), n, (const int64_t *)d.ext_off.as<int64_t>(), d.ext.as<uint64_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_dyn_pack_ext, d.words, eb.as<uint8_t>(), eo.as<int64_t>(),
+                     d.ext_len.as<int32_t>(), n, d.ext_off.as<int64_t>(), d.ext.as<uint64_t>());
     }
     return sync_checked(ctx);                                     // (the staging buffers are read by the copies queued above)
 }
@@ -573,12 +551,11 @@ __global__ __launch_bounds__(256) void k_dyn_unpack_bases(const uint64_t *__rest
 static int dyn_unpack_host(rfx_ctx *ctx, const DynDev &d, rfx_dyn_records *h) {
     const int64_t n = d.n;
     DevBuf ks, es, kso, eso, kb, eb;
-    RFX_HIP(ks.alloc((size_t)std::max<int64_t>(n, 1) * 4, ctx->stream)); RFX_HIP(es.alloc((size_t)std::max<int64_t>(n, 1) * 4, ctx->stream));
-    RFX_HIP(kso.alloc((size_t)(n + 1) * 8, ctx->stream)); RFX_HIP(eso.alloc((size_t)(n + 1) * 8, ctx->stream));
+    RFX_ALLOC(ks, uint32_t, std::max<int64_t>(n, 1)); RFX_ALLOC(es, uint32_t, std::max<int64_t>(n, 1));
+    RFX_ALLOC(kso, uint64_t, n + 1); RFX_ALLOC(eso, uint64_t, n + 1);
     if (n > 0) {
-        hipLaunchKernelGGL(k_dyn_unpack_sizes, RFX_GRID(n), (const uint8_t *)d.key_len.as<uint8_t>(), (const int32_t *)d.ext_len.as<int32_t>(), n,
-                           ks.as<uint32_t>(), es.as<uint32_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_dyn_unpack_sizes, n, d.key_len.as<uint8_t>(), d.ext_len.as<int32_t>(), n,
+                     ks.as<uint32_t>(), es.as<uint32_t>());
     }
     RFX_TRY(exclusive_scan2_u32_to_u64(ctx, ks.as<uint32_t>(), es.as<uint32_t>(), kso.as<uint64_t>(), eso.as<uint64_t>(), n));
     uint64_t tot[2] = {0, 0};
@@ -590,15 +567,13 @@ static int dyn_unpack_host(rfx_ctx *ctx, const DynDev &d, rfx_dyn_records *h) {
     if (n > h->cap_n || nk > h->cap_key || ne > h->cap_ext) return RFX_E_CAP;
     RFX_HIP(kb.alloc((size_t)std::max<int64_t>(nk, 1), ctx->stream)); RFX_HIP(eb.alloc((size_t)std::max<int64_t>(ne, 1), ctx->stream));
     if (nk) {
-        hipLaunchKernelGGL(k_dyn_unpack_bases, RFX_GRID(nk), (const uint64_t *)d.key.as<uint64_t>(), (const int64_t *)nullptr, (const uint64_t *)kso.as<uint64_t>(),
-                           n, nk, kb.as<uint8_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_dyn_unpack_bases, nk, d.key.as<uint64_t>(), (const int64_t *)nullptr, kso.as<uint64_t>(),
+                     n, nk, kb.as<uint8_t>());
         RFX_HIP(hipMemcpyAsync(h->key, kb.p, (size_t)nk, hipMemcpyDeviceToHost, ctx->stream));
     }
     if (ne) {
-        hipLaunchKernelGGL(k_dyn_unpack_bases, RFX_GRID(ne), (const uint64_t *)d.ext.as<uint64_t>(), (const int64_t *)d.ext_off.as<int64_t>(),
-                           (const uint64_t *)eso.as<uint64_t>(), n, ne, eb.as<uint8_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_dyn_unpack_bases, ne, d.ext.as<uint64_t>(), d.ext_off.as<int64_t>(),
+                     eso.as<uint64_t>(), n, ne, eb.as<uint8_t>());
         RFX_HIP(hipMemcpyAsync(h->ext, eb.p, (size_t)ne, hipMemcpyDeviceToHost, ctx->stream));
     }
     RFX_HIP(hipMemcpyAsync(h->key_off, kso.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -623,6 +598,7 @@ int rfx::dyn_empty(rfx_ctx *ctx, DynDev &d) {
     RFX_HIP(hipMemsetAsync(d.ext_off.p, 0, 8, ctx->stream));
     return RFX_OK;
 }
+bool rfx::parts_ok(int P) { return P >= 1 && P <= 63; }
 int rfx::check_part_starts(rfx_ctx *ctx, const int64_t *d_ps, int P, int64_t n, const char *stage_name) {
     int64_t h[65];
     RFX_TRY(small_readback(ctx, h, d_ps, (size_t)(P + 1) * 8));
@@ -643,11 +619,54 @@ __global__ void k_put_totals(const uint64_t *__restrict__ a, const uint64_t *__r
 }
 }  // namespace
 int rfx::call_flags_read(rfx_ctx *ctx, const DevBuf &flags, const uint64_t *d_t0, const uint64_t *d_t1, const uint64_t *d_t2, CallFlags *h) {
-    if (d_t0 || d_t1 || d_t2) {
-        hipLaunchKernelGGL(k_put_totals, dim3(1), dim3(1), 0, ctx->stream, d_t0, d_t1, d_t2, flags.as<CallFlags>());
-        RFX_HIP(hipGetLastError());
-    }
+    if (d_t0 || d_t1 || d_t2) RFX_LAUNCH(k_put_totals, dim3(1), dim3(1), 0, d_t0, d_t1, d_t2, flags.as<CallFlags>());
     return small_readback(ctx, h, flags.p, sizeof(CallFlags));
+}
+// ---- the host steps the stages share (rfx_internal.h) -----------------------------------------------------------------------------
+namespace {
+__global__ void k_out_part_starts(const int64_t *__restrict__ ps, int P, const uint64_t *__restrict__ off, int64_t *__restrict__ out_ps) {
+    const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (p <= P) out_ps[p] = (int64_t)off[ps[p]];
+}
+__global__ __launch_bounds__(256) void k_index_kept(const uint32_t *__restrict__ keep, const uint64_t *__restrict__ rank, int64_t n, int64_t *__restrict__ idx) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && keep[i]) idx[rank[i]] = i;
+}
+}  // namespace
+int rfx::scan_keep(rfx_ctx *ctx, const uint32_t *d_keep, int64_t n, uint64_t *d_rank, int64_t *total) {
+    RFX_TRY(exclusive_scan_u32_to_u64(ctx, d_keep, d_rank, n));
+    uint64_t t = 0;
+    RFX_TRY(small_readback(ctx, &t, d_rank + n, 8));
+    *total = (int64_t)t;
+    return RFX_OK;
+}
+int rfx::part_starts_alloc(rfx_ctx *ctx, DevBuf &out_ps, int P, bool zeroed) {
+    RFX_ALLOC(out_ps, int64_t, P + 1);
+    if (zeroed) RFX_HIP(hipMemsetAsync(out_ps.p, 0, (size_t)(P + 1) * sizeof(int64_t), ctx->stream));
+    return RFX_OK;
+}
+int rfx::part_starts_store(rfx_ctx *ctx, int64_t *d_dst, const DevBuf &ops, int P) {
+    RFX_HIP(hipMemcpyAsync(d_dst, ops.p, (size_t)(P + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, ctx->stream));
+    return sync_checked(ctx);
+}
+int rfx::out_part_starts(rfx_ctx *ctx, const int64_t *d_ps, int P, const uint64_t *d_prefix, int64_t *d_out) {
+    RFX_LAUNCH(k_out_part_starts, dim3(1), dim3(64), 0, d_ps, P, d_prefix, d_out);
+    return RFX_OK;
+}
+int rfx::index_kept(rfx_ctx *ctx, const uint32_t *d_keep, const uint64_t *d_rank, int64_t n, int64_t *d_idx) {
+    RFX_LAUNCH_N(k_index_kept, n, d_keep, d_rank, n, d_idx);
+    return RFX_OK;
+}
+int rfx::text_to_host(rfx_ctx *ctx, std::initializer_list<TextOut> outs, bool fill_to_cap) {
+    bool too_short = false;
+    for (const TextOut &o : outs) { *o.out_len = o.total; too_short |= o.total > o.cap; }
+    if (too_short && !fill_to_cap) return RFX_E_CAP;
+    for (const TextOut &o : outs) {
+        const int64_t lim = std::min<int64_t>(o.total, o.cap);
+        if (lim > 0) RFX_HIP(hipMemcpyAsync(o.out, o.d.p, (size_t)lim, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    RFX_TRY(sync_checked(ctx));
+    return too_short ? RFX_E_CAP : RFX_OK;
 }
 // ---- the caller's packed arrays (rfx_dyn_packed, device pointers) <-> DynDev ---------------------------------------------------
 // a view of the caller's input set: nothing is copied, nothing is freed
@@ -756,37 +775,30 @@ __global__ __launch_bounds__(256) void k_dyn_bin_ext(const char *__restrict__ te
 }  // namespace
 // text in HBM (row r = d_text[d_row_off[r], d_row_off[r + 1])) -> a packed set in the library's own buffers
 int rfx::dyn_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, int form, DynDev &d) {
-    if (n == 0) {
-        RFX_TRY(dyn_alloc(ctx, d, 0, 0));
-        RFX_HIP(hipMemsetAsync(d.ext_off.p, 0, 8, ctx->stream));
-        return RFX_OK;
-    }
+    if (n == 0) return dyn_empty(ctx, d);
     DevBuf kbeg, ebeg, ew, flags;
     const size_t m = (size_t)n;
     // (everything but the extension words, whose number the scan gives)
-    RFX_HIP(d.key.alloc(m * DYN_KW * 8, ctx->stream)); RFX_HIP(d.key_len.alloc(m, ctx->stream)); RFX_HIP(d.ext_off.alloc((m + 1) * 8, ctx->stream));
-    RFX_HIP(d.ext_len.alloc(m * 4, ctx->stream)); RFX_HIP(d.marker.alloc(m * 4, ctx->stream)); RFX_HIP(d.left.alloc(m * 4, ctx->stream));
-    RFX_HIP(d.right.alloc(m * 4, ctx->stream));
-    RFX_HIP(kbeg.alloc(m * 8, ctx->stream)); RFX_HIP(ebeg.alloc(m * 8, ctx->stream)); RFX_HIP(ew.alloc(m * 4, ctx->stream));
+    RFX_ALLOC(d.key, uint64_t, m * DYN_KW); RFX_HIP(d.key_len.alloc(m, ctx->stream)); RFX_ALLOC(d.ext_off, uint64_t, m + 1);
+    RFX_ALLOC(d.ext_len, int32_t, m); RFX_ALLOC(d.marker, int32_t, m); RFX_ALLOC(d.left, int32_t, m);
+    RFX_ALLOC(d.right, int32_t, m);
+    RFX_ALLOC(kbeg, int64_t, m); RFX_ALLOC(ebeg, int64_t, m); RFX_ALLOC(ew, uint32_t, m);
     RFX_TRY(call_flags_init(ctx, flags));
     d.n = n;
-    hipLaunchKernelGGL(k_dyn_bin_sizes, RFX_GRID(n), d_text, d_row_off, n, form, dyn_out(d), kbeg.as<int64_t>(), ebeg.as<int64_t>(), ew.as<uint32_t>(),
-                       flags.as<CallFlags>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_dyn_bin_sizes, n, d_text, d_row_off, n, form, dyn_out(d), kbeg.as<int64_t>(), ebeg.as<int64_t>(), ew.as<uint32_t>(),
+                 flags.as<CallFlags>());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, ew.as<uint32_t>(), d.ext_off.as<uint64_t>(), n));
     CallFlags f{};
     RFX_TRY(call_flags_read(ctx, flags, d.ext_off.as<uint64_t>() + n, nullptr, nullptr, &f));
     if (f.bad & DYN_BAD_OFFSETS) { ctx->last_error = "dynamic-k binarizer: row offsets that run backwards"; return RFX_E_ARG; }
     if (f.bad & DYN_TOO_LONG) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
     d.words = (int64_t)f.total[0];
-    RFX_HIP(d.ext.alloc((size_t)std::max<int64_t>(d.words, 1) * 8, ctx->stream));
-    hipLaunchKernelGGL(k_dyn_bin_key, RFX_GRID(n * DYN_KW), d_text, (const int64_t *)kbeg.as<int64_t>(), (const uint8_t *)d.key_len.as<uint8_t>(), n,
-                       d.key.as<uint64_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_ALLOC(d.ext, uint64_t, std::max<int64_t>(d.words, 1));
+    RFX_LAUNCH_N(k_dyn_bin_key, n * DYN_KW, d_text, kbeg.as<int64_t>(), d.key_len.as<uint8_t>(), n,
+                 d.key.as<uint64_t>());
     if (d.words > 0) {
-        hipLaunchKernelGGL(k_dyn_bin_ext, RFX_GRID(d.words), d_text, (const int64_t *)ebeg.as<int64_t>(), (const int32_t *)d.ext_len.as<int32_t>(), n,
-                           (const int64_t *)d.ext_off.as<int64_t>(), d.ext.as<uint64_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_dyn_bin_ext, d.words, d_text, ebeg.as<int64_t>(), d.ext_len.as<int32_t>(), n,
+                     d.ext_off.as<int64_t>(), d.ext.as<uint64_t>());
     }
     return RFX_OK;
 }
@@ -795,7 +807,7 @@ int rfx::dyn_upload_text(rfx_ctx *ctx, const char *text, const int64_t *row_off,
     for (int64_t i = 0; i < n_rows; i++) if (row_off[i + 1] < row_off[i]) return RFX_E_ARG;
     const int64_t nb = n_rows ? row_off[n_rows] - row_off[0] : 0;
     RFX_HIP(d_text.alloc((size_t)std::max<int64_t>(nb, 1), ctx->stream));
-    RFX_HIP(d_off.alloc((size_t)(n_rows + 1) * 8, ctx->stream));
+    RFX_ALLOC(d_off, int64_t, n_rows + 1);
     if (n_rows == 0) return RFX_OK;
     std::vector<int64_t> rel((size_t)n_rows + 1);
     for (int64_t i = 0; i <= n_rows; i++) rel[(size_t)i] = row_off[i] - row_off[0];
@@ -845,10 +857,9 @@ int rfx::dyn_to_text(rfx_ctx *ctx, const DynDev &d, char *d_text, int64_t cap, i
     *total = 0;
     if (n == 0) return RFX_OK;
     DevBuf sz, toff;
-    RFX_HIP(sz.alloc((size_t)n * 8, ctx->stream)); RFX_HIP(toff.alloc((size_t)(n + 1) * 8, ctx->stream));
+    RFX_ALLOC(sz, uint64_t, n); RFX_ALLOC(toff, uint64_t, n + 1);
     const DynView v = dyn_view(d);
-    hipLaunchKernelGGL(k_dyn_text_sizes, RFX_GRID(n), v, n, sz.as<uint64_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_dyn_text_sizes, n, v, n, sz.as<uint64_t>());
     RFX_TRY(exclusive_scan_u64(ctx, sz.as<uint64_t>(), toff.as<uint64_t>(), n));
     uint64_t t = 0;
     RFX_TRY(small_readback(ctx, &t, toff.as<uint64_t>() + n, 8));
@@ -859,8 +870,7 @@ int rfx::dyn_to_text(rfx_ctx *ctx, const DynDev &d, char *d_text, int64_t cap, i
     }
     const int64_t lim = std::min<int64_t>(*total, cap);
     if (lim > 0) {
-        hipLaunchKernelGGL(k_dyn_text_fill, RFX_GRID(lim), v, n, (const uint64_t *)toff.as<uint64_t>(), lim, d_text);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_dyn_text_fill, lim, v, n, toff.as<uint64_t>(), lim, d_text);
     }
     return sync_checked(ctx);
 }
@@ -877,7 +887,7 @@ static int dyn_run(rfx_ctx *ctx, DynDev &a, int P, int random_reflection, int pa
     if (random_reflection) {
         std::vector<int64_t> st((size_t)P + 1);
         for (int p = 0; p <= P; p++) st[(size_t)p] = p == P ? a.n : (int64_t)(((__int128)p * (__int128)a.n) / P);
-        RFX_HIP(ps.alloc((size_t)(P + 1) * 8, ctx->stream));
+        RFX_ALLOC(ps, int64_t, P + 1);
         RFX_HIP(hipMemcpyAsync(ps.p, st.data(), (size_t)(P + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
         RFX_TRY(sync_checked(ctx));
         DynDev b;
@@ -926,7 +936,7 @@ int rfx_dev_dyn_unpack(rfx_ctx *ctx, const rfx_dyn_packed *d_in, rfx_dyn_records
 } RFX_API_CATCH(ctx)
 
 int rfx_dev_dyn_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, int form, rfx_dyn_packed *d_out) try {
-    if (!ctx || !dyn_packed_out_ok(d_out) || n_rows < 0 || (n_rows > 0 && (!d_text || !d_row_off)) || (form != 0 && form != 1)) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_out_ok(d_out) || !text_rows_ok(d_text, d_row_off, n_rows) || (form != 0 && form != 1)) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a;
     RFX_TRY(dyn_binarize(ctx, d_text, d_row_off, n_rows, form, a));
@@ -934,7 +944,7 @@ int rfx_dev_dyn_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_
 } RFX_API_CATCH(ctx)
 
 int rfx_dev_dyn_sort(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int P, rfx_dyn_packed *d_out, int64_t *d_part_start) try {
-    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out) || !d_part_start || P < 1 || P > 63) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out) || !d_part_start || !parts_ok(P)) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a, b;
     DevBuf ps;
@@ -942,12 +952,11 @@ int rfx_dev_dyn_sort(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int P, rfx_dyn_pa
     RFX_TRY(dyn_borrow(ctx, d_in, a));
     RFX_TRY(dyn_sort(ctx, a, P, b, ps, &lmin));
     RFX_TRY(dyn_store(ctx, b, d_out));
-    RFX_HIP(hipMemcpyAsync(d_part_start, ps.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    return sync_checked(ctx);
+    return part_starts_store(ctx, d_part_start, ps, P);
 } RFX_API_CATCH(ctx)
 
 int rfx_dev_dyn_random_reflection(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const int64_t *d_part_start, int P, rfx_dyn_packed *d_out) try {
-    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out) || !d_part_start || P < 1 || P > 63) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out) || !d_part_start || !parts_ok(P)) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a, b;
     uint32_t lmin = 0;
@@ -959,7 +968,7 @@ int rfx_dev_dyn_random_reflection(rfx_ctx *ctx, const rfx_dyn_packed *d_in, cons
 
 int rfx_dev_dyn_extend_pass(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const int64_t *d_part_start, int P, int stage, int start_iteration,
                             int start_marker, rfx_dyn_packed *d_out, int64_t *d_out_part_start) try {
-    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out) || !d_part_start || P < 1 || P > 63 || (stage != 0 && stage != 1) ||
+    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out) || !d_part_start || !parts_ok(P) || (stage != 0 && stage != 1) ||
         (start_marker != 1 && start_marker != 2))
         return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
@@ -968,16 +977,15 @@ int rfx_dev_dyn_extend_pass(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const int6
     uint32_t lmin = 0;
     RFX_TRY(dyn_borrow(ctx, d_in, a));
     RFX_TRY(dyn_check_lengths(ctx, a, &lmin));
-    RFX_HIP(ops.alloc((size_t)(P + 1) * 8, ctx->stream));
+    RFX_TRY(part_starts_alloc(ctx, ops, P, false));
     RFX_TRY(dyn_pass(ctx, a, d_part_start, P, lmin, stage, start_iteration, start_marker, b, ops.as<int64_t>()));
     RFX_TRY(dyn_store(ctx, b, d_out));
-    if (d_out_part_start) RFX_HIP(hipMemcpyAsync(d_out_part_start, ops.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    return sync_checked(ctx);
+    return d_out_part_start ? part_starts_store(ctx, d_out_part_start, ops, P) : sync_checked(ctx);
 } RFX_API_CATCH(ctx)
 
 int rfx_dev_dyn_run(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int P, int random_reflection, int passes_first_four, int start_iteration,
                     int end_iteration, rfx_dyn_packed *d_out, int64_t *trace, int64_t trace_cap, int64_t *n_trace) try {
-    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out) || P < 1 || P > 63 || passes_first_four < 0) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out) || !parts_ok(P) || passes_first_four < 0) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a;
     uint32_t lmin = 0;
@@ -1004,7 +1012,7 @@ int rfx_dev_dyn_to_text(rfx_ctx *ctx, const rfx_dyn_packed *d_in, char *d_text, 
 int rfx_dyn_run_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int form, int P, int random_reflection,
                      int passes_first_four, int start_iteration, int end_iteration, char *out, int64_t cap, int64_t *out_len, int64_t *trace,
                      int64_t trace_cap, int64_t *n_trace) try {
-    if (!ctx || n_rows < 0 || (n_rows > 0 && (!text || !row_off)) || (form != 0 && form != 1) || P < 1 || P > 63 || passes_first_four < 0 ||
+    if (!ctx || !text_rows_ok(text, row_off, n_rows) || (form != 0 && form != 1) || !parts_ok(P) || passes_first_four < 0 ||
         !out_len || cap < 0 || (cap > 0 && !out))
         return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
@@ -1012,29 +1020,25 @@ int rfx_dyn_run_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int
     DynDev a;
     int64_t total = 0;
     RFX_TRY(dyn_upload_text(ctx, text, row_off, n_rows, d_text, d_off));
-    RFX_TRY(dyn_binarize(ctx, (const char *)d_text.p, (const int64_t *)d_off.as<int64_t>(), n_rows, form, a));
+    RFX_TRY(dyn_binarize(ctx, (const char *)d_text.p, d_off.as<int64_t>(), n_rows, form, a));
     RFX_TRY(dyn_run(ctx, a, P, random_reflection, passes_first_four, start_iteration, end_iteration, trace, trace_cap, n_trace));
     RFX_TRY(dyn_to_text(ctx, a, nullptr, 0, &total, &d_out));
-    *out_len = total;
-    const int64_t lim = std::min<int64_t>(total, cap);
-    if (lim > 0) RFX_HIP(hipMemcpyAsync(out, d_out.p, (size_t)lim, hipMemcpyDeviceToHost, ctx->stream));
-    RFX_TRY(sync_checked(ctx));
-    return total > cap ? RFX_E_CAP : RFX_OK;
+    return text_to_host(ctx, {{d_out, total, out, cap, out_len}}, true);
 } RFX_API_CATCH(ctx)
 
 // ---- the host forms: pack -> the same kernels -> unpack -----------------------------------------------------------------------
 int rfx_dyn_binarize(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int form, rfx_dyn_records *out) try {
-    if (!ctx || !out || n_rows < 0 || (n_rows > 0 && (!text || !row_off)) || (form != 0 && form != 1)) return RFX_E_ARG;
+    if (!ctx || !out || !text_rows_ok(text, row_off, n_rows) || (form != 0 && form != 1)) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     DevBuf d_text, d_off;
     DynDev a;
     RFX_TRY(dyn_upload_text(ctx, text, row_off, n_rows, d_text, d_off));
-    RFX_TRY(dyn_binarize(ctx, (const char *)d_text.p, (const int64_t *)d_off.as<int64_t>(), n_rows, form, a));
+    RFX_TRY(dyn_binarize(ctx, (const char *)d_text.p, d_off.as<int64_t>(), n_rows, form, a));
     return dyn_unpack_host(ctx, a, out);
 } RFX_API_CATCH(ctx)
 
 int rfx_dyn_sort(rfx_ctx *ctx, const rfx_dyn_records *in, int P, rfx_dyn_records *out, int64_t *part_start) try {
-    if (!ctx || !in || !out || !part_start || P < 1 || P > 63) return RFX_E_ARG;
+    if (!ctx || !in || !out || !part_start || !parts_ok(P)) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a, b;
     DevBuf ps;
@@ -1047,12 +1051,12 @@ int rfx_dyn_sort(rfx_ctx *ctx, const rfx_dyn_records *in, int P, rfx_dyn_records
 } RFX_API_CATCH(ctx)
 
 int rfx_dyn_random_reflection(rfx_ctx *ctx, const rfx_dyn_records *in, const int64_t *part_start, int P, rfx_dyn_records *out) try {
-    if (!ctx || !in || !out || !part_start || P < 1 || P > 63) return RFX_E_ARG;
+    if (!ctx || !in || !out || !part_start || !parts_ok(P)) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a, b;
     DevBuf ps;
     RFX_TRY(dyn_pack_host(ctx, in, a));
-    RFX_HIP(ps.alloc((size_t)(P + 1) * 8, ctx->stream));
+    RFX_ALLOC(ps, int64_t, P + 1);
     RFX_HIP(hipMemcpyAsync(ps.p, part_start, (size_t)(P + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     RFX_TRY(dyn_reflect(ctx, a, ps.as<int64_t>(), P, b));
     return dyn_unpack_host(ctx, b, out);
@@ -1060,13 +1064,13 @@ int rfx_dyn_random_reflection(rfx_ctx *ctx, const rfx_dyn_records *in, const int
 
 int rfx_dyn_extend_pass(rfx_ctx *ctx, const rfx_dyn_records *in, const int64_t *part_start, int P, int stage, int start_iteration,
                         int start_marker, rfx_dyn_records *out, int64_t *out_part_start) try {
-    if (!ctx || !in || !out || !part_start || P < 1 || P > 63 || (stage != 0 && stage != 1) || (start_marker != 1 && start_marker != 2))
+    if (!ctx || !in || !out || !part_start || !parts_ok(P) || (stage != 0 && stage != 1) || (start_marker != 1 && start_marker != 2))
         return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a, b;
     DevBuf ps, ops;
     RFX_TRY(dyn_pack_host(ctx, in, a));
-    RFX_HIP(ps.alloc((size_t)(P + 1) * 8, ctx->stream)); RFX_HIP(ops.alloc((size_t)(P + 1) * 8, ctx->stream));
+    RFX_ALLOC(ps, int64_t, P + 1); RFX_ALLOC(ops, int64_t, P + 1);
     RFX_HIP(hipMemcpyAsync(ps.p, part_start, (size_t)(P + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     int64_t lmin = INT64_MAX;
     for (int64_t i = 0; i < in->n; i++) lmin = std::min(lmin, in->key_off[i + 1] - in->key_off[i]);
@@ -1079,7 +1083,7 @@ int rfx_dyn_extend_pass(rfx_ctx *ctx, const rfx_dyn_records *in, const int64_t *
 
 int rfx_dyn_run(rfx_ctx *ctx, const rfx_dyn_records *in, int P, int random_reflection, int passes_first_four, int start_iteration,
                 int end_iteration, rfx_dyn_records *out, int64_t *trace, int64_t trace_cap, int64_t *n_trace) try {
-    if (!ctx || !in || !out || P < 1 || P > 63 || passes_first_four < 0) return RFX_E_ARG;
+    if (!ctx || !in || !out || !parts_ok(P) || passes_first_four < 0) return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a;
     RFX_TRY(dyn_pack_host(ctx, in, a));

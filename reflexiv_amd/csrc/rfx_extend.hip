@@ -715,7 +715,6 @@ __global__ void k_out_part_start(const int64_t *__restrict__ ps, int P, const ui
     }
 }
 
-inline unsigned grid_for(int64_t n, int block = 256) { return (unsigned)ceil_div(n > 0 ? n : 1, block); }
 
 }  // namespace
 
@@ -739,8 +738,8 @@ static int desc_tail(rfx_ctx *ctx, const DevRecords &in, int64_t nd, DevBuf &len
                      DevRecords &out, DevBuf &out_part_start, PartCarry *carry_hook = nullptr) {
     const int sub = k - 1, kw = in.kw;
     DevBuf oidx, owoff;
-    RFX_HIP(oidx.alloc((size_t)(nd + 1) * 8, ctx->stream));
-    RFX_HIP(owoff.alloc((size_t)(nd + 1) * 8, ctx->stream));
+    RFX_ALLOC(oidx, uint64_t, nd + 1);
+    RFX_ALLOC(owoff, uint64_t, nd + 1);
     // single-word stage: every emission has exactly one word (a longer one is the RFX_E_STATE below), so the word
     // offsets ARE the emission indices
     if (single_word) {
@@ -753,31 +752,28 @@ static int desc_tail(rfx_ctx *ctx, const DevRecords &in, int64_t nd, DevBuf &len
     // and the emission -- on the device, no host wait (rfx_shard.hip)
     const int32_t *d_carry = nullptr;
     if (carry_hook) RFX_TRY(carry_hook->compute(ctx, d_part_start, P, oidx.as<uint64_t>(), nd, &d_carry));
-    RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_emit<KW>, dim3(grid_for(nd + 1)), dim3(256), 0, ctx->stream, (const Desc *)desc.as<Desc>(),
-                       (const uint32_t *)flag.as<uint32_t>(), (const uint64_t *)oidx.as<uint64_t>(),
-                       (const uint64_t *)owoff.as<uint64_t>(), nd, d_part_start, P, sub, start_marker, d_carry,
-                       (const KeyW<KW> *)in.key.as<KeyW<KW>>(), (const int32_t *)in.marker.as<int32_t>(),
-                       (const int64_t *)in.ext_off.as<int64_t>(), (const uint64_t *)in.ext.as<uint64_t>(),
-                       (const uint32_t *)len.as<uint32_t>(), out.key.as<KeyW<KW>>(), out.marker.as<int32_t>(),
-                       out.ext_off.as<int64_t>(), out.ext.as<uint64_t>(), out.left.as<int32_t>(),
-                       out.right.as<int32_t>()));
-    RFX_HIP(hipGetLastError());
+    RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_emit<KW>, nd + 1, desc.as<Desc>(),
+                                   flag.as<uint32_t>(), oidx.as<uint64_t>(),
+                                   owoff.as<uint64_t>(), nd, d_part_start, P, sub, start_marker, d_carry,
+                                   in.key.as<KeyW<KW>>(), in.marker.as<int32_t>(),
+                                   in.ext_off.as<int64_t>(), in.ext.as<uint64_t>(),
+                                   len.as<uint32_t>(), out.key.as<KeyW<KW>>(), out.marker.as<int32_t>(),
+                                   out.ext_off.as<int64_t>(), out.ext.as<uint64_t>(), out.left.as<int32_t>(),
+                                   out.right.as<int32_t>()));
     if (words_bound > nd || in.words > in.n) {          // some record may have more than one word
-        RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_emit_words<KW>, dim3(grid_for(words_bound)), dim3(256), 0, ctx->stream, (const Desc *)desc.as<Desc>(),
-                           (const uint64_t *)oidx.as<uint64_t>(), (const uint64_t *)owoff.as<uint64_t>(), nd, d_part_start, P,
-                           sub, start_marker, d_carry, (const KeyW<KW> *)in.key.as<KeyW<KW>>(), (const int32_t *)in.marker.as<int32_t>(),
-                           (const int64_t *)in.ext_off.as<int64_t>(), (const uint64_t *)in.ext.as<uint64_t>(),
-                           (const uint32_t *)len.as<uint32_t>(), out.ext.as<uint64_t>()));
-        RFX_HIP(hipGetLastError());
+        RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_emit_words<KW>, words_bound, desc.as<Desc>(),
+                                       oidx.as<uint64_t>(), owoff.as<uint64_t>(), nd, d_part_start, P,
+                                       sub, start_marker, d_carry, in.key.as<KeyW<KW>>(), in.marker.as<int32_t>(),
+                                       in.ext_off.as<int64_t>(), in.ext.as<uint64_t>(),
+                                       len.as<uint32_t>(), out.ext.as<uint64_t>()));
     }
     DevBuf summary;
     RFX_HIP(summary.alloc(24, ctx->stream));
     const uint64_t seq = P + 1 <= 256 ? mailbox_next(ctx) : 0;          // (the posting kernel is one workgroup)
-    hipLaunchKernelGGL(k_out_part_start, dim3(grid_for(P + 1)), dim3(256), 0, ctx->stream, d_part_start, P,
-                       (const uint64_t *)oidx.as<uint64_t>(), out_part_start.as<int64_t>(),
-                       (const uint64_t *)owoff.as<uint64_t>(), nd, (const int *)status.as<int>(), summary.as<uint64_t>(),
-                       seq ? ctx->mailbox : (volatile uint64_t *)nullptr, seq);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_out_part_start, P + 1, d_part_start, P,
+                 oidx.as<uint64_t>(), out_part_start.as<int64_t>(),
+                 owoff.as<uint64_t>(), nd, status.as<int>(), summary.as<uint64_t>(),
+                 seq ? ctx->mailbox : (volatile uint64_t *)nullptr, seq);
     uint64_t tot[3] = {0, 0, 0};
     if (seq) RFX_TRY(mailbox_wait(ctx, seq, tot, 3));
     else {
@@ -797,26 +793,24 @@ int extend_pass(rfx_ctx *ctx, const DevRecords &in, const int64_t *d_part_start,
     if (n > (int64_t)0xFFFFFFFFLL) return RFX_E_LIMIT;
     if (kw != sub_words(k) || (start_marker != 1 && start_marker != 2)) return RFX_E_ARG;
     RFX_TRY(dev_records_alloc(ctx, out, n, in.words, kw));
-    RFX_HIP(out_part_start.alloc((size_t)(P + 1) * 8, ctx->stream));
+    RFX_ALLOC(out_part_start, int64_t, P + 1);
     DevBuf len, desc, flag, onw, status;
     const int64_t a = n ? n : 1;
-    RFX_HIP(len.alloc((size_t)a * 4, ctx->stream));
-    RFX_HIP(desc.alloc((size_t)a * sizeof(Desc), ctx->stream));
-    RFX_HIP(flag.alloc((size_t)a * 4, ctx->stream));
-    RFX_HIP(onw.alloc((size_t)a * 4, ctx->stream));
+    RFX_ALLOC(len, uint32_t, a);
+    RFX_ALLOC(desc, Desc, a);
+    RFX_ALLOC(flag, uint32_t, a);
+    RFX_ALLOC(onw, uint32_t, a);
     RFX_HIP(status.alloc(4, ctx->stream));
     RFX_HIP(hipMemsetAsync(status.p, 0, 4, ctx->stream));
     if (n > 0) {
-        hipLaunchKernelGGL(k_ext_len, dim3(grid_for(n)), dim3(256), 0, ctx->stream,
-                           (const int64_t *)in.ext_off.as<int64_t>(), (const uint64_t *)in.ext.as<uint64_t>(), n,
-                           len.as<uint32_t>());
-        RFX_HIP(hipGetLastError());
-        RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_resolve<KW>, dim3(grid_for(n)), dim3(256), 0, ctx->stream,
-                           (const KeyW<KW> *)in.key.as<KeyW<KW>>(), (const int32_t *)in.marker.as<int32_t>(),
-                           (const int32_t *)in.left.as<int32_t>(), (const int32_t *)in.right.as<int32_t>(),
-                           (const uint32_t *)len.as<uint32_t>(), n, twin, stage, desc.as<Desc>(),
-                           flag.as<uint32_t>(), onw.as<uint32_t>(), status.as<int>()));
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_ext_len, n,
+                     in.ext_off.as<int64_t>(), in.ext.as<uint64_t>(), n,
+                     len.as<uint32_t>());
+        RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_resolve<KW>, n,
+                                       in.key.as<KeyW<KW>>(), in.marker.as<int32_t>(),
+                                       in.left.as<int32_t>(), in.right.as<int32_t>(),
+                                       len.as<uint32_t>(), n, twin, stage, desc.as<Desc>(),
+                                       flag.as<uint32_t>(), onw.as<uint32_t>(), status.as<int>()));
     }
     return desc_tail(ctx, in, n, len, desc, flag, onw, status, d_part_start, P, k, stage == 0, start_marker, in.words, out, out_part_start,
                      carry_hook);
@@ -831,13 +825,13 @@ int extras_operator(rfx_ctx *ctx, int op, const DevRecords &in, const int64_t *d
     if (kw != sub_words(k) || op < 0 || op > 6) return RFX_E_ARG;
     const int64_t nd = op == 0 ? 2 * n : n, wcap = op == 0 ? 2 * in.words : in.words;
     RFX_TRY(dev_records_alloc(ctx, out, nd, wcap, kw));
-    RFX_HIP(out_part_start.alloc((size_t)(P + 1) * 8, ctx->stream));
+    RFX_ALLOC(out_part_start, int64_t, P + 1);
     DevBuf len, desc, flag, onw, status, w0, ps1;
     const int64_t a = nd ? nd : 1;
-    RFX_HIP(len.alloc((size_t)(n ? n : 1) * 4, ctx->stream));
-    RFX_HIP(desc.alloc((size_t)a * sizeof(Desc), ctx->stream));
-    RFX_HIP(flag.alloc((size_t)a * 4, ctx->stream));
-    RFX_HIP(onw.alloc((size_t)a * 4, ctx->stream));
+    RFX_ALLOC(len, uint32_t, n ? n : 1);
+    RFX_ALLOC(desc, Desc, a);
+    RFX_ALLOC(flag, uint32_t, a);
+    RFX_ALLOC(onw, uint32_t, a);
     RFX_HIP(status.alloc(4, ctx->stream));
     RFX_HIP(hipMemsetAsync(status.p, 0, 4, ctx->stream));
     const int64_t *ps = d_part_start;
@@ -852,29 +846,26 @@ int extras_operator(rfx_ctx *ctx, int op, const DevRecords &in, const int64_t *d
         ps = ps1.as<int64_t>(); Pn = 1;
     }
     if (n > 0) {
-        hipLaunchKernelGGL(k_ext_len, dim3(grid_for(n)), dim3(256), 0, ctx->stream, (const int64_t *)in.ext_off.as<int64_t>(),
-                           (const uint64_t *)in.ext.as<uint64_t>(), n, len.as<uint32_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_ext_len, n, in.ext_off.as<int64_t>(),
+                     in.ext.as<uint64_t>(), n, len.as<uint32_t>());
         if (op == 0) {
-            hipLaunchKernelGGL(k_desc_double, dim3(grid_for(n)), dim3(256), 0, ctx->stream, (const int32_t *)in.marker.as<int32_t>(),
-                               (const int32_t *)in.left.as<int32_t>(), (const int32_t *)in.right.as<int32_t>(), (const uint32_t *)len.as<uint32_t>(),
-                               n, desc.as<Desc>(), flag.as<uint32_t>(), onw.as<uint32_t>());
+            RFX_LAUNCH_N(k_desc_double, n, in.marker.as<int32_t>(),
+                         in.left.as<int32_t>(), in.right.as<int32_t>(), len.as<uint32_t>(),
+                         n, desc.as<Desc>(), flag.as<uint32_t>(), onw.as<uint32_t>());
         } else if (op >= 5) {
-            hipLaunchKernelGGL(k_desc_flip_all, dim3(grid_for(n)), dim3(256), 0, ctx->stream, (const int32_t *)in.left.as<int32_t>(),
-                               (const int32_t *)in.right.as<int32_t>(), (const uint32_t *)len.as<uint32_t>(), n, op == 5 ? 1 : 2,
-                               desc.as<Desc>(), flag.as<uint32_t>(), onw.as<uint32_t>());
+            RFX_LAUNCH_N(k_desc_flip_all, n, in.left.as<int32_t>(),
+                         in.right.as<int32_t>(), len.as<uint32_t>(), n, op == 5 ? 1 : 2,
+                         desc.as<Desc>(), flag.as<uint32_t>(), onw.as<uint32_t>());
         } else {
-            RFX_HIP(w0.alloc((size_t)n * 8, ctx->stream));
-            hipLaunchKernelGGL(k_word0, dim3(grid_for(n)), dim3(256), 0, ctx->stream, (const int64_t *)in.ext_off.as<int64_t>(),
-                               (const uint64_t *)in.ext.as<uint64_t>(), n, w0.as<uint64_t>());
-            RFX_HIP(hipGetLastError());
-            RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_key_filter<KW>, dim3(grid_for(n)), dim3(256), 0, ctx->stream, op,
-                               (const KeyW<KW> *)in.key.as<KeyW<KW>>(), (const int32_t *)in.marker.as<int32_t>(),
-                               (const int32_t *)in.left.as<int32_t>(), (const int32_t *)in.right.as<int32_t>(),
-                               (const uint32_t *)len.as<uint32_t>(), (const uint64_t *)w0.as<uint64_t>(), n, d_part_start, P,
-                               desc.as<Desc>(), flag.as<uint32_t>(), onw.as<uint32_t>()));
+            RFX_ALLOC(w0, uint64_t, n);
+            RFX_LAUNCH_N(k_word0, n, in.ext_off.as<int64_t>(),
+                         in.ext.as<uint64_t>(), n, w0.as<uint64_t>());
+            RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_key_filter<KW>, n, op,
+                                           in.key.as<KeyW<KW>>(), in.marker.as<int32_t>(),
+                                           in.left.as<int32_t>(), in.right.as<int32_t>(),
+                                           len.as<uint32_t>(), w0.as<uint64_t>(), n, d_part_start, P,
+                                           desc.as<Desc>(), flag.as<uint32_t>(), onw.as<uint32_t>()));
         }
-        RFX_HIP(hipGetLastError());
     }
     DevBuf ops_tmp;
     RFX_TRY(desc_tail(ctx, in, nd, len, desc, flag, onw, status, ps, Pn, k, false, 2, wcap, out, op == 0 ? ops_tmp_alloc(ctx, ops_tmp, Pn) : out_part_start));
@@ -904,15 +895,15 @@ int small_passes(rfx_ctx *ctx, DevRecords &recs, int k, int twin, bool wide, int
     RFX_TRY(dev_records_alloc(ctx, other, capn, capw, kw));
     DevBuf skey, smarker, sleft, sright, slen, sext, desc, flag, onw, oidx, owoff, ps, status, state, dtrace;
     RFX_HIP(skey.alloc((size_t)capn * 8 * kw, ctx->stream));
-    RFX_HIP(smarker.alloc((size_t)capn * 4, ctx->stream)); RFX_HIP(sleft.alloc((size_t)capn * 4, ctx->stream));
-    RFX_HIP(sright.alloc((size_t)capn * 4, ctx->stream)); RFX_HIP(slen.alloc((size_t)capn * 4, ctx->stream));
-    RFX_HIP(sext.alloc((size_t)capn * 8, ctx->stream)); RFX_HIP(desc.alloc((size_t)capn * sizeof(Desc), ctx->stream));
-    RFX_HIP(flag.alloc((size_t)capn * 4, ctx->stream)); RFX_HIP(onw.alloc((size_t)capn * 4, ctx->stream));
-    RFX_HIP(oidx.alloc((size_t)(capn + 1) * 8, ctx->stream)); RFX_HIP(owoff.alloc((size_t)(capn + 1) * 8, ctx->stream));
-    RFX_HIP(ps.alloc((size_t)(SP_MAXP + 1) * 8, ctx->stream)); RFX_HIP(status.alloc(4, ctx->stream));
+    RFX_ALLOC(smarker, int32_t, capn); RFX_ALLOC(sleft, int32_t, capn);
+    RFX_ALLOC(sright, int32_t, capn); RFX_ALLOC(slen, uint32_t, capn);
+    RFX_ALLOC(sext, int64_t, capn); RFX_ALLOC(desc, Desc, capn);
+    RFX_ALLOC(flag, uint32_t, capn); RFX_ALLOC(onw, uint32_t, capn);
+    RFX_ALLOC(oidx, uint64_t, capn + 1); RFX_ALLOC(owoff, uint64_t, capn + 1);
+    RFX_ALLOC(ps, int64_t, SP_MAXP + 1); RFX_HIP(status.alloc(4, ctx->stream));
     RFX_HIP(state.alloc(sizeof(SmallState), ctx->stream));
     const int64_t tcap = max_iter + 8;
-    RFX_HIP(dtrace.alloc((size_t)tcap * 8, ctx->stream));
+    RFX_ALLOC(dtrace, int64_t, tcap);
     SmallState h{};
     h.n = recs.n; h.words = recs.words; h.contig_number = *contig_number; h.nt = 0;
     h.iterations = *iterations; h.scramble = *scramble; h.P = *P; h.partition_number = *partition_number;
@@ -931,13 +922,11 @@ int small_passes(rfx_ctx *ctx, DevRecords &recs, int k, int twin, bool wide, int
     int64_t words_bound = recs.words;
     for (;;) {
         for (int b = 0; b < BATCH; b++) {
-            RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_small_pass<KW>, dim3(1), dim3(SP_T), 0, ctx->stream, A, B, sc, state.as<SmallState>(), rule,
-                                                 dtrace.as<int64_t>()));
-            RFX_HIP(hipGetLastError());
+            RFX_KW_SWITCH(kw, RFX_LAUNCH(k_small_pass<KW>, dim3(1), dim3(SP_T), 0, A, B, sc, state.as<SmallState>(), rule,
+                                         dtrace.as<int64_t>()));
             if (words_bound > 0) {
-                RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_small_words<KW>, dim3(grid_for(words_bound)), dim3(256), 0, ctx->stream, A, B, sc,
-                                                     (const SmallState *)state.as<SmallState>(), sub, (int64_t)0));
-                RFX_HIP(hipGetLastError());
+                RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_small_words<KW>, words_bound, A, B, sc,
+                                               state.as<SmallState>(), sub, (int64_t)0));
             }
         }
         RFX_HIP(hipMemcpyAsync(&h, state.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));

@@ -43,10 +43,6 @@ namespace {
 enum { FX_BAD_KEY = 1, FX_BAD_EXT = 2, FX_BAD_VALUE = 4 };
 
 // ---- a compaction: output record q := input record idx[q] -------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_fx_index(const uint32_t *__restrict__ keep, const uint64_t *__restrict__ rank, int64_t n, int64_t *__restrict__ idx) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && keep[i]) idx[rank[i]] = i;
-}
 __global__ __launch_bounds__(256) void k_fx_gather_rec(const DynView v, const int64_t *__restrict__ idx, int64_t m, const DynOut o, uint32_t *__restrict__ ew) {
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= m) return;
@@ -214,11 +210,6 @@ __global__ __launch_bounds__(256) void k_fx_fold_keep(const DynView v, int64_t n
     }
     keep[i] = kp;
 }
-// where the partitions begin in the output: P + 1 entries
-__global__ void k_fx_out_ps(const int64_t *__restrict__ ps, int P, const uint64_t *__restrict__ rank, int64_t *__restrict__ out_ps) {
-    const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (p <= P) out_ps[p] = (int64_t)rank[ps[p]];
-}
 
 // ---- step 7: DSChangingFixingKmerToReflectedKmer -- key = the LAST 30 bases of the contig, extension = its front, marker 2.  The key
 // has 30 bases before and after, so every extension keeps its length and its words: threads [0, 4 n) write the key words and the
@@ -260,8 +251,7 @@ static int fx_check(rfx_ctx *ctx, const DynDev &in) {
     if (in.n == 0) return RFX_OK;
     DevBuf flags;
     RFX_TRY(call_flags_init(ctx, flags));
-    hipLaunchKernelGGL(k_fx_check, RFX_GRID(in.n), dyn_view(in), in.n, flags.as<CallFlags>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_fx_check, in.n, dyn_view(in), in.n, flags.as<CallFlags>());
     CallFlags f{};
     RFX_TRY(call_flags_read(ctx, flags, nullptr, nullptr, nullptr, &f));
     if (f.bad) {
@@ -275,18 +265,15 @@ static int fx_compact(rfx_ctx *ctx, const DynDev &in, const DevBuf &keep, const 
     if (m == 0) return dyn_empty(ctx, out);
     const int64_t n = in.n;
     DevBuf idx, ew;
-    RFX_HIP(idx.alloc((size_t)m * 8, ctx->stream)); RFX_HIP(ew.alloc((size_t)m * 4, ctx->stream));
+    RFX_ALLOC(idx, int64_t, m); RFX_ALLOC(ew, uint32_t, m);
     RFX_TRY(dyn_alloc(ctx, out, m, in.words));
     const DynView v = dyn_view(in);
-    hipLaunchKernelGGL(k_fx_index, RFX_GRID(n), (const uint32_t *)keep.as<uint32_t>(), (const uint64_t *)rank.as<uint64_t>(), n, idx.as<int64_t>());
-    RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_fx_gather_rec, RFX_GRID(m), v, (const int64_t *)idx.as<int64_t>(), m, dyn_out(out), ew.as<uint32_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_TRY(index_kept(ctx, keep.as<uint32_t>(), rank.as<uint64_t>(), n, idx.as<int64_t>()));
+    RFX_LAUNCH_N(k_fx_gather_rec, m, v, idx.as<int64_t>(), m, dyn_out(out), ew.as<uint32_t>());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, ew.as<uint32_t>(), out.ext_off.as<uint64_t>(), m));
     if (in.words > 0) {
-        hipLaunchKernelGGL(k_fx_gather_ext, RFX_GRID(in.words), v, (const int64_t *)idx.as<int64_t>(), m, (const uint64_t *)out.ext_off.as<uint64_t>(),
-                           out.ext.as<uint64_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_fx_gather_ext, in.words, v, idx.as<int64_t>(), m, out.ext_off.as<uint64_t>(),
+                     out.ext.as<uint64_t>());
     }
     return RFX_OK;
 }
@@ -298,14 +285,12 @@ static int fx_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_of
     DynDev a;
     RFX_TRY(dyn_binarize(ctx, d_text, d_row_off, n, 1, a));
     DevBuf keep, rank;
-    RFX_HIP(keep.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(rank.alloc((size_t)(n + 1) * 8, ctx->stream));
-    hipLaunchKernelGGL(k_fx_long_enough, RFX_GRID(n), (const uint8_t *)a.key_len.as<uint8_t>(), (const int32_t *)a.ext_len.as<int32_t>(), n, 2 * prm.max_k,
-                       keep.as<uint32_t>());
-    RFX_HIP(hipGetLastError());
-    RFX_TRY(exclusive_scan_u32_to_u64(ctx, keep.as<uint32_t>(), rank.as<uint64_t>(), n));
-    uint64_t m = 0;
-    RFX_TRY(small_readback(ctx, &m, rank.as<uint64_t>() + n, 8));
-    return fx_compact(ctx, a, keep, rank, (int64_t)m, out);
+    RFX_ALLOC(keep, uint32_t, n); RFX_ALLOC(rank, uint64_t, n + 1);
+    RFX_LAUNCH_N(k_fx_long_enough, n, a.key_len.as<uint8_t>(), a.ext_len.as<int32_t>(), n, 2 * prm.max_k,
+                 keep.as<uint32_t>());
+    int64_t m = 0;
+    RFX_TRY(scan_keep(ctx, keep.as<uint32_t>(), n, rank.as<uint64_t>(), &m));
+    return fx_compact(ctx, a, keep, rank, m, out);
 }
 
 // steps 2-3: the long records, and the 31-mers in emission order (contig by contig, i = 0 .. max_k - 31, left then right)
@@ -315,13 +300,12 @@ static int fx_contig_ends(rfx_ctx *ctx, const DynDev &in, const FxParams &prm, D
     RFX_HIP(kmers.alloc(8, ctx->stream));
     if (n == 0) return dyn_empty(ctx, out);
     DevBuf nk, nl, nw, koff, loff, woff, flags;
-    RFX_HIP(nk.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(nl.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(nw.alloc((size_t)n * 4, ctx->stream));
-    RFX_HIP(koff.alloc((size_t)(n + 1) * 8, ctx->stream)); RFX_HIP(loff.alloc((size_t)(n + 1) * 8, ctx->stream));
-    RFX_HIP(woff.alloc((size_t)(n + 1) * 8, ctx->stream));
+    RFX_ALLOC(nk, uint32_t, n); RFX_ALLOC(nl, uint32_t, n); RFX_ALLOC(nw, uint32_t, n);
+    RFX_ALLOC(koff, uint64_t, n + 1); RFX_ALLOC(loff, uint64_t, n + 1);
+    RFX_ALLOC(woff, uint64_t, n + 1);
     RFX_TRY(call_flags_init(ctx, flags));
     const DynView v = dyn_view(in);
-    hipLaunchKernelGGL(k_fx_ends_sizes, RFX_GRID(n), v.key_len, v.ext_len, n, prm.max_k, nk.as<uint32_t>(), nl.as<uint32_t>(), nw.as<uint32_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_fx_ends_sizes, n, v.key_len, v.ext_len, n, prm.max_k, nk.as<uint32_t>(), nl.as<uint32_t>(), nw.as<uint32_t>());
     RFX_TRY(exclusive_scan2_u32_to_u64(ctx, nk.as<uint32_t>(), nl.as<uint32_t>(), koff.as<uint64_t>(), loff.as<uint64_t>(), n));
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, nw.as<uint32_t>(), woff.as<uint64_t>(), n));
     CallFlags f{};
@@ -329,13 +313,11 @@ static int fx_contig_ends(rfx_ctx *ctx, const DynDev &in, const FxParams &prm, D
     const int64_t n31 = (int64_t)f.total[0], m = (int64_t)f.total[1], words = (int64_t)f.total[2];
     *n_kmers = n31;
     if (m == 0) return dyn_empty(ctx, out);
-    RFX_HIP(kmers.alloc((size_t)n31 * 8, ctx->stream));
+    RFX_ALLOC(kmers, uint64_t, n31);
     RFX_TRY(dyn_alloc(ctx, out, m, words));
-    hipLaunchKernelGGL(k_fx_ends_kmers, RFX_GRID(n31), v, n, (const uint64_t *)koff.as<uint64_t>(), kmers.as<uint64_t>());
-    RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_fx_ends_long, RFX_GRID(PK_KW * m + words), v, n, prm.max_k, (const uint64_t *)loff.as<uint64_t>(), (const uint64_t *)woff.as<uint64_t>(),
-                       dyn_out(out));
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_fx_ends_kmers, n31, v, n, koff.as<uint64_t>(), kmers.as<uint64_t>());
+    RFX_LAUNCH_N(k_fx_ends_long, PK_KW * m + words, v, n, prm.max_k, loff.as<uint64_t>(), woff.as<uint64_t>(),
+                 dyn_out(out));
     return RFX_OK;
 }
 
@@ -345,16 +327,14 @@ static int fx_kmer_set(rfx_ctx *ctx, const uint64_t *d_kmers, int64_t n31, const
     int64_t d = 0;
     DevBuf val, idx, tk, tv, head, rank;
     if (n31 > 0) {
-        RFX_HIP(val.alloc((size_t)n31 * 8, ctx->stream)); RFX_HIP(idx.alloc((size_t)n31 * 4, ctx->stream)); RFX_HIP(tk.alloc((size_t)n31 * 8, ctx->stream));
-        RFX_HIP(tv.alloc((size_t)n31 * 4, ctx->stream)); RFX_HIP(head.alloc((size_t)n31 * 4, ctx->stream)); RFX_HIP(rank.alloc((size_t)(n31 + 1) * 8, ctx->stream));
+        RFX_ALLOC(val, uint64_t, n31); RFX_ALLOC(idx, uint32_t, n31); RFX_ALLOC(tk, uint64_t, n31);
+        RFX_ALLOC(tv, uint32_t, n31); RFX_ALLOC(head, uint32_t, n31); RFX_ALLOC(rank, uint64_t, n31 + 1);
         RFX_HIP(hipMemcpyAsync(val.p, d_kmers, (size_t)n31 * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_fx_iota, RFX_GRID(n31), n31, idx.as<uint32_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_fx_iota, n31, n31, idx.as<uint32_t>());
         RFX_TRY(sort_pairs(ctx, val.as<uint64_t>(), idx.as<uint32_t>(), n31, 2 * FX_K, tk.as<uint64_t>(), tv.as<uint32_t>()));
         DevBuf flags;
         RFX_TRY(call_flags_init(ctx, flags));
-        hipLaunchKernelGGL(k_fx_value_heads, RFX_GRID(n31), (const uint64_t *)val.as<uint64_t>(), n31, head.as<uint32_t>(), flags.as<CallFlags>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_fx_value_heads, n31, val.as<uint64_t>(), n31, head.as<uint32_t>(), flags.as<CallFlags>());
         RFX_TRY(exclusive_scan_u32_to_u64(ctx, head.as<uint32_t>(), rank.as<uint64_t>(), n31));
         CallFlags f{};
         RFX_TRY(call_flags_read(ctx, flags, rank.as<uint64_t>() + n31, nullptr, nullptr, &f));
@@ -364,12 +344,10 @@ static int fx_kmer_set(rfx_ctx *ctx, const uint64_t *d_kmers, int64_t n31, const
     if (d + lng.n == 0) return dyn_empty(ctx, out);
     RFX_TRY(dyn_alloc(ctx, out, d + lng.n, d + lng.words));
     if (d > 0) {
-        hipLaunchKernelGGL(k_fx_set_kmers, RFX_GRID(n31), (const uint64_t *)val.as<uint64_t>(), (const uint32_t *)head.as<uint32_t>(),
-                           (const uint64_t *)rank.as<uint64_t>(), n31, dyn_out(out));
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_fx_set_kmers, n31, val.as<uint64_t>(), head.as<uint32_t>(),
+                     rank.as<uint64_t>(), n31, dyn_out(out));
     }
-    hipLaunchKernelGGL(k_fx_set_long, RFX_GRID(std::max(lng.n, lng.words)), dyn_view(lng), lng.n, lng.words, d, dyn_out(out));
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_fx_set_long, std::max(lng.n, lng.words), dyn_view(lng), lng.n, lng.words, d, dyn_out(out));
     return RFX_OK;
 }
 
@@ -377,37 +355,31 @@ static int fx_kmer_set(rfx_ctx *ctx, const uint64_t *d_kmers, int64_t n31, const
 // which is a one-base extension's only one), so `reflected` selects nothing here
 static int fx_fold(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, DynDev &out, DevBuf &out_ps) {
     const int64_t n = in.n;
-    RFX_HIP(out_ps.alloc((size_t)(P + 1) * 8, ctx->stream));
+    RFX_TRY(part_starts_alloc(ctx, out_ps, P, false));
     RFX_TRY(check_part_starts(ctx, d_ps, P, n, "contig fixing"));
-    if (n == 0) {
-        RFX_HIP(hipMemsetAsync(out_ps.p, 0, (size_t)(P + 1) * 8, ctx->stream));
+    if (n == 0) {                                                 // (zeroed here, behind the check's read-back: DESIGN.md section 23)
+        RFX_HIP(hipMemsetAsync(out_ps.p, 0, (size_t)(P + 1) * sizeof(int64_t), ctx->stream));
         return dyn_empty(ctx, out);
     }
     if (n >= ((int64_t)1 << 32)) { ctx->last_error = "contig fixing: 2^32 records or more"; return RFX_E_LIMIT; }
     RFX_TRY(fx_check(ctx, in));
     DevBuf head, run, best, keep, rank;
-    RFX_HIP(head.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(run.alloc((size_t)(n + 1) * 8, ctx->stream)); RFX_HIP(best.alloc((size_t)n * 8, ctx->stream));
-    RFX_HIP(keep.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(rank.alloc((size_t)(n + 1) * 8, ctx->stream));
+    RFX_ALLOC(head, uint32_t, n); RFX_ALLOC(run, uint64_t, n + 1); RFX_ALLOC(best, unsigned long long, n);
+    RFX_ALLOC(keep, uint32_t, n); RFX_ALLOC(rank, uint64_t, n + 1);
     RFX_HIP(hipMemsetAsync(head.p, 0, (size_t)n * 4, ctx->stream));
     RFX_HIP(hipMemsetAsync(best.p, 0xFF, (size_t)n * 8, ctx->stream));
     const DynView v = dyn_view(in);
-    hipLaunchKernelGGL(k_fx_part_heads, dim3(1), dim3(64), 0, ctx->stream, d_ps, P, head.as<uint32_t>());
-    RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_fx_key_heads, RFX_GRID(n), v.key, n, head.as<uint32_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH(k_fx_part_heads, dim3(1), dim3(64), 0, d_ps, P, head.as<uint32_t>());
+    RFX_LAUNCH_N(k_fx_key_heads, n, v.key, n, head.as<uint32_t>());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, head.as<uint32_t>(), run.as<uint64_t>(), n));
-    hipLaunchKernelGGL(k_fx_fold_contest, RFX_GRID(n), v, n, (const uint32_t *)head.as<uint32_t>(), (const uint64_t *)run.as<uint64_t>(),
-                       best.as<unsigned long long>());
-    RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_fx_fold_keep, RFX_GRID(n), v, n, (const uint32_t *)head.as<uint32_t>(), (const uint64_t *)run.as<uint64_t>(),
-                       (const unsigned long long *)best.as<unsigned long long>(), keep.as<uint32_t>());
-    RFX_HIP(hipGetLastError());
-    RFX_TRY(exclusive_scan_u32_to_u64(ctx, keep.as<uint32_t>(), rank.as<uint64_t>(), n));
-    uint64_t m = 0;
-    RFX_TRY(small_readback(ctx, &m, rank.as<uint64_t>() + n, 8));
-    hipLaunchKernelGGL(k_fx_out_ps, dim3(1), dim3(64), 0, ctx->stream, d_ps, P, (const uint64_t *)rank.as<uint64_t>(), out_ps.as<int64_t>());
-    RFX_HIP(hipGetLastError());
-    return fx_compact(ctx, in, keep, rank, (int64_t)m, out);
+    RFX_LAUNCH_N(k_fx_fold_contest, n, v, n, head.as<uint32_t>(), run.as<uint64_t>(),
+                 best.as<unsigned long long>());
+    RFX_LAUNCH_N(k_fx_fold_keep, n, v, n, head.as<uint32_t>(), run.as<uint64_t>(),
+                 best.as<unsigned long long>(), keep.as<uint32_t>());
+    int64_t m = 0;
+    RFX_TRY(scan_keep(ctx, keep.as<uint32_t>(), n, rank.as<uint64_t>(), &m));
+    RFX_TRY(out_part_starts(ctx, d_ps, P, rank.as<uint64_t>(), out_ps.as<int64_t>()));
+    return fx_compact(ctx, in, keep, rank, m, out);
 }
 
 // step 7
@@ -416,8 +388,7 @@ static int fx_reflect(rfx_ctx *ctx, const DynDev &in, DynDev &out) {
     if (n == 0) return dyn_empty(ctx, out);
     RFX_TRY(fx_check(ctx, in));
     RFX_TRY(dyn_alloc(ctx, out, n, in.words));
-    hipLaunchKernelGGL(k_fx_reflect, RFX_GRID(PK_KW * n + in.words), dyn_view(in), n, dyn_out(out));
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_fx_reflect, PK_KW * n + in.words, dyn_view(in), n, dyn_out(out));
     return RFX_OK;
 }
 
@@ -501,7 +472,7 @@ int rfx_dev_fix_kmer_set(rfx_ctx *ctx, const uint64_t *d_kmers, int64_t n_kmers,
 
 int rfx_dev_fix_fork_filter(rfx_ctx *ctx, int reflected, const rfx_dyn_packed *d_sorted, const int64_t *d_part_start, int P, rfx_dyn_packed *d_out,
                             int64_t *d_out_part_start) try {
-    if (!ctx || !dyn_packed_ok(d_sorted) || !dyn_packed_out_ok(d_out) || !d_part_start || !d_out_part_start || P < 1 || P > 63 || (reflected != 0 && reflected != 1))
+    if (!ctx || !dyn_packed_ok(d_sorted) || !dyn_packed_out_ok(d_out) || !d_part_start || !d_out_part_start || !parts_ok(P) || (reflected != 0 && reflected != 1))
         return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a, b;
@@ -509,8 +480,7 @@ int rfx_dev_fix_fork_filter(rfx_ctx *ctx, int reflected, const rfx_dyn_packed *d
     RFX_TRY(dyn_borrow(ctx, d_sorted, a));
     RFX_TRY(fx_fold(ctx, a, d_part_start, P, b, ops));
     RFX_TRY(dyn_store(ctx, b, d_out));                                // (both capacities are checked before anything is copied)
-    RFX_HIP(hipMemcpyAsync(d_out_part_start, ops.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    return sync_checked(ctx);
+    return part_starts_store(ctx, d_out_part_start, ops, P);
 } RFX_API_CATCH(ctx)
 
 int rfx_dev_fix_reflect(rfx_ctx *ctx, const rfx_dyn_packed *d_in, rfx_dyn_packed *d_out) try {
@@ -524,7 +494,7 @@ int rfx_dev_fix_reflect(rfx_ctx *ctx, const rfx_dyn_packed *d_in, rfx_dyn_packed
 
 int rfx_dev_fix_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, int P, const rfx_fix_params *params,
                     rfx_dyn_packed *d_out) try {
-    if (!ctx || !dyn_packed_out_ok(d_out) || !text_rows_ok(d_text, d_row_off, n_rows) || P < 1 || P > 63) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_out_ok(d_out) || !text_rows_ok(d_text, d_row_off, n_rows) || !parts_ok(P)) return RFX_E_ARG;
     FxParams prm;
     RFX_TRY(fx_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -536,7 +506,7 @@ int rfx_dev_fix_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, 
 // host text in, host text out; everything between packed and in HBM: upload, run, to-text, one copy back
 int rfx_fix_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
                  int64_t *out_len) try {
-    if (!ctx || !text_rows_ok(text, row_off, n_rows) || P < 1 || P > 63 || !out_len || cap < 0 || (cap > 0 && !out)) return RFX_E_ARG;
+    if (!ctx || !text_rows_ok(text, row_off, n_rows) || !parts_ok(P) || !out_len || cap < 0 || (cap > 0 && !out)) return RFX_E_ARG;
     FxParams prm;
     RFX_TRY(fx_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -544,12 +514,9 @@ int rfx_fix_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t
     DynDev a;
     int64_t total = 0;
     RFX_TRY(dyn_upload_text(ctx, text, row_off, n_rows, d_text, d_off));
-    RFX_TRY(fx_run(ctx, (const char *)d_text.p, (const int64_t *)d_off.as<int64_t>(), n_rows, P, prm, a));
+    RFX_TRY(fx_run(ctx, (const char *)d_text.p, d_off.as<int64_t>(), n_rows, P, prm, a));
     RFX_TRY(dyn_to_text(ctx, a, nullptr, 0, &total, &d_o));
-    *out_len = total;
-    if (total > cap) return RFX_E_CAP;                                // (nothing written)
-    if (total > 0) RFX_HIP(hipMemcpyAsync(out, d_o.p, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
-    return sync_checked(ctx);
+    return text_to_host(ctx, {{d_o, total, out, cap, out_len}}, false);
 } RFX_API_CATCH(ctx)
 
 }  // extern "C"

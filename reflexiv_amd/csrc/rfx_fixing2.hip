@@ -209,9 +209,8 @@ static int fx2_check(rfx_ctx *ctx, const DynDev &in) {
     if (in.n == 0) return RFX_OK;
     DevBuf flags;
     RFX_TRY(call_flags_init(ctx, flags));
-    hipLaunchKernelGGL(k_fx2_check, RFX_GRID(in.n), (const uint8_t *)in.key_len.as<uint8_t>(), (const int32_t *)in.ext_len.as<int32_t>(), in.n,
-                       flags.as<CallFlags>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_fx2_check, in.n, in.key_len.as<uint8_t>(), in.ext_len.as<int32_t>(), in.n,
+                 flags.as<CallFlags>());
     CallFlags f{};
     RFX_TRY(call_flags_read(ctx, flags, nullptr, nullptr, nullptr, &f));
     if (f.bad) {
@@ -268,12 +267,11 @@ int rfx::fx2_contigs_plan(rfx_ctx *ctx, const DynDev &in, int max_k, Fx2Plan &pl
     if (n == 0) return RFX_OK;
     if (n >= ((int64_t)1 << 31)) { ctx->last_error = "contig fixing, round two: 2^31 records or more"; return RFX_E_LIMIT; }
     DevBuf nw, flags;
-    RFX_HIP(plan.keep.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(nw.alloc((size_t)n * 4, ctx->stream));
-    RFX_HIP(plan.rank.alloc((size_t)(n + 1) * 8, ctx->stream)); RFX_HIP(plan.woff.alloc((size_t)(n + 1) * 8, ctx->stream));
+    RFX_ALLOC(plan.keep, uint32_t, n); RFX_ALLOC(nw, uint32_t, n);
+    RFX_ALLOC(plan.rank, uint64_t, n + 1); RFX_ALLOC(plan.woff, uint64_t, n + 1);
     RFX_TRY(call_flags_init(ctx, flags));
-    hipLaunchKernelGGL(k_fx2_cat_sizes, RFX_GRID(n), (const uint8_t *)in.key_len.as<uint8_t>(), (const int32_t *)in.ext_len.as<int32_t>(), n, 2 * max_k,
-                       plan.keep.as<uint32_t>(), nw.as<uint32_t>(), flags.as<CallFlags>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_fx2_cat_sizes, n, in.key_len.as<uint8_t>(), in.ext_len.as<int32_t>(), n, 2 * max_k,
+                 plan.keep.as<uint32_t>(), nw.as<uint32_t>(), flags.as<CallFlags>());
     RFX_TRY(exclusive_scan2_u32_to_u64(ctx, plan.keep.as<uint32_t>(), nw.as<uint32_t>(), plan.rank.as<uint64_t>(), plan.woff.as<uint64_t>(), n));
     CallFlags f{};
     RFX_TRY(call_flags_read(ctx, flags, plan.rank.as<uint64_t>() + n, plan.woff.as<uint64_t>() + n, nullptr, &f));
@@ -290,9 +288,8 @@ int rfx::fx2_contigs_fill(rfx_ctx *ctx, const DynDev &in, const Fx2Plan &plan, u
         RFX_HIP(hipMemsetAsync(d_word_off, 0, 8, ctx->stream));
         return RFX_OK;
     }
-    hipLaunchKernelGGL(k_fx2_cat, RFX_GRID(n + plan.words), dyn_view(in), n, (const uint32_t *)plan.keep.as<uint32_t>(), (const uint64_t *)plan.rank.as<uint64_t>(),
-                       (const uint64_t *)plan.woff.as<uint64_t>(), d_words, d_word_off, d_len, d_left, d_right);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_fx2_cat, n + plan.words, dyn_view(in), n, plan.keep.as<uint32_t>(), plan.rank.as<uint64_t>(),
+                 plan.woff.as<uint64_t>(), d_words, d_word_off, d_len, d_left, d_right);
     return RFX_OK;
 }
 
@@ -304,10 +301,9 @@ int rfx::fx2_text(rfx_ctx *ctx, const Fx2View &v, int ends, char *d_text, int64_
     if (n == 0) return RFX_OK;
     if (n >= ((int64_t)1 << 31)) { ctx->last_error = "contig fixing, round two: 2^31 contigs or more"; return RFX_E_LIMIT; }
     DevBuf sz, toff, flags;
-    RFX_HIP(sz.alloc((size_t)n * 8, ctx->stream)); RFX_HIP(toff.alloc((size_t)(n + 1) * 8, ctx->stream));
+    RFX_ALLOC(sz, uint64_t, n); RFX_ALLOC(toff, uint64_t, n + 1);
     RFX_TRY(call_flags_init(ctx, flags));
-    hipLaunchKernelGGL(k_fx2_text_sizes, RFX_GRID(n), v.woff, v.len, v.left, v.right, n, ends, sz.as<uint64_t>(), flags.as<CallFlags>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_fx2_text_sizes, n, v.woff, v.len, v.left, v.right, n, ends, sz.as<uint64_t>(), flags.as<CallFlags>());
     RFX_TRY(exclusive_scan_u64(ctx, sz.as<uint64_t>(), toff.as<uint64_t>(), n));
     CallFlags f{};
     RFX_TRY(call_flags_read(ctx, flags, toff.as<uint64_t>() + n, nullptr, nullptr, &f));
@@ -322,9 +318,8 @@ int rfx::fx2_text(rfx_ctx *ctx, const Fx2View &v, int ends, char *d_text, int64_
     if (lim > 0) {
         const int skew = (int)((uintptr_t)d_text & 15);
         const int64_t chunks = ceil_div(lim + skew, 16);
-        hipLaunchKernelGGL(k_fx2_text_fill, RFX_GRID(chunks), v.w, v.woff, v.len, v.left, v.right, n, ends, (const uint64_t *)toff.as<uint64_t>(), lim, skew, chunks,
-                           d_text);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_fx2_text_fill, chunks, v.w, v.woff, v.len, v.left, v.right, n, ends, toff.as<uint64_t>(), lim, skew, chunks,
+                     d_text);
     }
     return sync_checked(ctx);
 }

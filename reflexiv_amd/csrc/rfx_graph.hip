@@ -442,7 +442,6 @@ __global__ void k_random_reflection(const KeyW<KW> *__restrict__ key, const int3
     okey[i] = kk; omarker[i] = m; oext[i] = e; oleft[i] = left[i]; oright[i] = right[i]; oext_off[i] = i;
 }
 
-inline unsigned grid_for(int64_t n, int block = 256) { return (unsigned)ceil_div(n > 0 ? n : 1, block); }
 
 }  // namespace
 
@@ -463,11 +462,11 @@ int dev_records_alloc(rfx_ctx *ctx, DevRecords &r, int64_t cap_n, int64_t cap_wo
     if (kw < 1 || kw > MAX_KEY_WORDS) return RFX_E_ARG;
     r.kw = kw;
     RFX_HIP(r.key.alloc((size_t)cap_n * 8 * kw, ctx->stream));
-    RFX_HIP(r.marker.alloc((size_t)cap_n * 4, ctx->stream));
-    RFX_HIP(r.ext_off.alloc((size_t)(cap_n + 1) * 8, ctx->stream));
-    RFX_HIP(r.ext.alloc((size_t)cap_words * 8, ctx->stream));
-    RFX_HIP(r.left.alloc((size_t)cap_n * 4, ctx->stream));
-    RFX_HIP(r.right.alloc((size_t)cap_n * 4, ctx->stream));
+    RFX_ALLOC(r.marker, int32_t, cap_n);
+    RFX_ALLOC(r.ext_off, int64_t, cap_n + 1);
+    RFX_ALLOC(r.ext, uint64_t, cap_words);
+    RFX_ALLOC(r.left, int32_t, cap_n);
+    RFX_ALLOC(r.right, int32_t, cap_n);
     r.n = 0; r.words = 0;
     return RFX_OK;
 }
@@ -518,16 +517,14 @@ int rc_expand_subkmer(rfx_ctx *ctx, const uint64_t *d_kmers, const int32_t *d_co
     const int kw = sub_words(k);
     RFX_TRY(dev_records_alloc(ctx, out, 2 * n, 2 * n, kw));
     if (n > 0 && k <= 31) {
-        hipLaunchKernelGGL(k_rc_expand, dim3(grid_for(n)), dim3(256), 0, ctx->stream, d_kmers, d_counts, n, k,
-                           out.key.as<uint64_t>(), out.marker.as<int32_t>(), out.ext_off.as<int64_t>(),
-                           out.ext.as<uint64_t>(), out.left.as<int32_t>(), out.right.as<int32_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_rc_expand, n, d_kmers, d_counts, n, k,
+                     out.key.as<uint64_t>(), out.marker.as<int32_t>(), out.ext_off.as<int64_t>(),
+                     out.ext.as<uint64_t>(), out.left.as<int32_t>(), out.right.as<int32_t>());
     } else if (n > 0) {
-        RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_rc_expand_w<KW>, dim3(grid_for(n)), dim3(256), 0, ctx->stream, d_kmers,
-                                             asm_words(k), d_counts, n, k, out.key.as<KeyW<KW>>(), out.marker.as<int32_t>(),
-                                             out.ext_off.as<int64_t>(), out.ext.as<uint64_t>(), out.left.as<int32_t>(),
-                                             out.right.as<int32_t>()));
-        RFX_HIP(hipGetLastError());
+        RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_rc_expand_w<KW>, n, d_kmers,
+                                       asm_words(k), d_counts, n, k, out.key.as<KeyW<KW>>(), out.marker.as<int32_t>(),
+                                       out.ext_off.as<int64_t>(), out.ext.as<uint64_t>(), out.left.as<int32_t>(),
+                                       out.right.as<int32_t>()));
     } else {
         RFX_HIP(hipMemsetAsync(out.ext_off.p, 0, 8, ctx->stream));
     }
@@ -541,21 +538,20 @@ int sort_records(rfx_ctx *ctx, const DevRecords &in, int P, int key_bits, DevRec
     if (n > (int64_t)0xFFFFFFFFLL) return RFX_E_LIMIT;
     if (kw > 1 && k != 0 && sub_words(k) != kw) return RFX_E_ARG;
     RFX_TRY(dev_records_alloc(ctx, out, n, in.words, kw));
-    RFX_HIP(part_start.alloc((size_t)(P + 1) * 8, ctx->stream));
+    RFX_ALLOC(part_start, int64_t, P + 1);
     DevBuf perm, tk, tv, nw, wscan, long_list, long_n;
-    RFX_HIP(perm.alloc((size_t)(n ? n : 1) * 4, ctx->stream));
-    RFX_HIP(tk.alloc((size_t)(n ? n : 1) * 8, ctx->stream));
-    RFX_HIP(tv.alloc((size_t)(n ? n : 1) * 4, ctx->stream));
-    RFX_HIP(nw.alloc((size_t)(n ? n : 1) * 4, ctx->stream));
-    RFX_HIP(wscan.alloc((size_t)(n + 1) * 8, ctx->stream));
+    RFX_ALLOC(perm, uint32_t, n ? n : 1);
+    RFX_ALLOC(tk, uint64_t, n ? n : 1);
+    RFX_ALLOC(tv, uint32_t, n ? n : 1);
+    RFX_ALLOC(nw, uint32_t, n ? n : 1);
+    RFX_ALLOC(wscan, uint64_t, n + 1);
     // chunk items: at most one per record plus one per LONG_CHUNK words
-    RFX_HIP(long_list.alloc((size_t)((n ? n : 1) + in.words / LONG_CHUNK + 1) * 8, ctx->stream));
+    RFX_ALLOC(long_list, uint64_t, (n ? n : 1) + in.words / LONG_CHUNK + 1);
     RFX_HIP(long_n.alloc(8, ctx->stream));
     RFX_HIP(hipMemsetAsync(long_n.p, 0, 8, ctx->stream));
     if (n > 0 && kw == 1) {
         RFX_HIP(hipMemcpyAsync(out.key.p, in.key.p, (size_t)n * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_iota_u32, dim3(grid_for(n)), dim3(256), 0, ctx->stream, perm.as<uint32_t>(), n);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_iota_u32, n, perm.as<uint32_t>(), n);
         RFX_TRY(sort_pairs(ctx, out.key.as<uint64_t>(), perm.as<uint32_t>(), n, key_bits, tk.as<uint64_t>(),
                            tv.as<uint32_t>()));
     } else if (n > 0) {
@@ -563,9 +559,8 @@ int sort_records(rfx_ctx *ctx, const DevRecords &in, int P, int key_bits, DevRec
         // their current order is gathered, sorted together with the permutation, and so on; then the whole
         // keys are gathered once
         DevBuf wk;
-        RFX_HIP(wk.alloc((size_t)n * 8, ctx->stream));
-        hipLaunchKernelGGL(k_iota_u32, dim3(grid_for(n)), dim3(256), 0, ctx->stream, perm.as<uint32_t>(), n);
-        RFX_HIP(hipGetLastError());
+        RFX_ALLOC(wk, uint64_t, n);
+        RFX_LAUNCH_N(k_iota_u32, n, perm.as<uint32_t>(), n);
         const int res = k > 0 ? (k - 1) - 31 * (kw - 1) : 31;      // k unknown: every word may use its 62 bits
         bool done = false;
         if (kw == 2) {       // (k unknown: res = 31, a prefix that splits less but orders the same)
@@ -573,74 +568,63 @@ int sort_records(rfx_ctx *ctx, const DevRecords &in, int P, int key_bits, DevRec
             DevBuf flag;
             RFX_HIP(flag.alloc(4, ctx->stream));
             RFX_HIP(hipMemsetAsync(flag.p, 0, 4, ctx->stream));
-            hipLaunchKernelGGL(k_key_prefix2, dim3(grid_for(n)), dim3(256), 0, ctx->stream, (const KeyW<2> *)in.key.as<KeyW<2>>(), n, res,
-                               wk.as<uint64_t>());
-            RFX_HIP(hipGetLastError());
+            RFX_LAUNCH_N(k_key_prefix2, n, in.key.as<KeyW<2>>(), n, res,
+                         wk.as<uint64_t>());
             const int pbits = 62 + 2 * res < 64 ? 62 + 2 * res : 64;
             RFX_TRY(sort_pairs(ctx, wk.as<uint64_t>(), perm.as<uint32_t>(), n, pbits, tk.as<uint64_t>(), tv.as<uint32_t>()));
-            hipLaunchKernelGGL(k_tie_fix2, dim3(grid_for(n)), dim3(256), 0, ctx->stream, (const uint64_t *)wk.as<uint64_t>(),
-                               perm.as<uint32_t>(), n, (const KeyW<2> *)in.key.as<KeyW<2>>(), res, flag.as<int>());
-            RFX_HIP(hipGetLastError());
+            RFX_LAUNCH_N(k_tie_fix2, n, wk.as<uint64_t>(),
+                         perm.as<uint32_t>(), n, in.key.as<KeyW<2>>(), res, flag.as<int>());
             int h_flag = 0;
             RFX_TRY(small_readback(ctx, &h_flag, flag.p, 4));
             done = h_flag == 0;
             if (!done) {                       // a long run of equal prefixes: start over with the two passes below
-                hipLaunchKernelGGL(k_iota_u32, dim3(grid_for(n)), dim3(256), 0, ctx->stream, perm.as<uint32_t>(), n);
-                RFX_HIP(hipGetLastError());
+                RFX_LAUNCH_N(k_iota_u32, n, perm.as<uint32_t>(), n);
             }
         }
         for (int w = kw - 1; w >= 0 && !done; w--) {
             const uint32_t *pp = w == kw - 1 ? nullptr : perm.as<uint32_t>();
-            RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_key_word<KW>, dim3(grid_for(n)), dim3(256), 0, ctx->stream,
-                                                 (const KeyW<KW> *)in.key.as<KeyW<KW>>(), pp, n, w, wk.as<uint64_t>()));
-            RFX_HIP(hipGetLastError());
+            RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_key_word<KW>, n,
+                                           in.key.as<KeyW<KW>>(), pp, n, w, wk.as<uint64_t>()));
             RFX_TRY(sort_pairs(ctx, wk.as<uint64_t>(), perm.as<uint32_t>(), n, 2 * (w == kw - 1 ? res : 31), tk.as<uint64_t>(),
                                tv.as<uint32_t>()));
         }
-        RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_gather_key<KW>, dim3(grid_for(n)), dim3(256), 0, ctx->stream,
-                                             (const KeyW<KW> *)in.key.as<KeyW<KW>>(), (const uint32_t *)perm.as<uint32_t>(), n,
-                                             out.key.as<KeyW<KW>>()));
-        RFX_HIP(hipGetLastError());
+        RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_gather_key<KW>, n,
+                                       in.key.as<KeyW<KW>>(), perm.as<uint32_t>(), n,
+                                       out.key.as<KeyW<KW>>()));
     }
     if (in.words == n) {
         // (ext_off is the identity on both sides)
-        hipLaunchKernelGGL(k_gather_single, dim3(grid_for(n + 1)), dim3(256), 0, ctx->stream, (const uint32_t *)perm.as<uint32_t>(), n,
-                           (const int32_t *)in.marker.as<int32_t>(), (const int32_t *)in.left.as<int32_t>(),
-                           (const int32_t *)in.right.as<int32_t>(), (const uint64_t *)in.ext.as<uint64_t>(), out.marker.as<int32_t>(),
-                           out.left.as<int32_t>(), out.right.as<int32_t>(), out.ext_off.as<int64_t>(), out.ext.as<uint64_t>());
-        RFX_HIP(hipGetLastError());
-        RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_partition_starts<KW>, dim3(grid_for(P + 1)), dim3(256), 0, ctx->stream,
-                                             (const KeyW<KW> *)out.key.as<KeyW<KW>>(), n, P, part_start.as<int64_t>()));
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_gather_single, n + 1, perm.as<uint32_t>(), n,
+                     in.marker.as<int32_t>(), in.left.as<int32_t>(),
+                     in.right.as<int32_t>(), in.ext.as<uint64_t>(), out.marker.as<int32_t>(),
+                     out.left.as<int32_t>(), out.right.as<int32_t>(), out.ext_off.as<int64_t>(), out.ext.as<uint64_t>());
+        RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_partition_starts<KW>, P + 1,
+                                       out.key.as<KeyW<KW>>(), n, P, part_start.as<int64_t>()));
         out.n = n; out.words = in.words;
         return RFX_OK;
     }
     if (n > 0) {
-        hipLaunchKernelGGL(k_gather_fixed, dim3(grid_for(n)), dim3(256), 0, ctx->stream,
-                           (const uint32_t *)perm.as<uint32_t>(), n, (const int32_t *)in.marker.as<int32_t>(),
-                           (const int32_t *)in.left.as<int32_t>(), (const int32_t *)in.right.as<int32_t>(),
-                           (const int64_t *)in.ext_off.as<int64_t>(), out.marker.as<int32_t>(),
-                           out.left.as<int32_t>(), out.right.as<int32_t>(), nw.as<uint32_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_gather_fixed, n,
+                     perm.as<uint32_t>(), n, in.marker.as<int32_t>(),
+                     in.left.as<int32_t>(), in.right.as<int32_t>(),
+                     in.ext_off.as<int64_t>(), out.marker.as<int32_t>(),
+                     out.left.as<int32_t>(), out.right.as<int32_t>(), nw.as<uint32_t>());
     }
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, nw.as<uint32_t>(), wscan.as<uint64_t>(), n));
-    hipLaunchKernelGGL(k_gather_ext, dim3(grid_for(n + 1)), dim3(256), 0, ctx->stream,
-                       (const uint32_t *)perm.as<uint32_t>(), n, (const int64_t *)in.ext_off.as<int64_t>(),
-                       (const uint64_t *)in.ext.as<uint64_t>(), (const uint64_t *)wscan.as<uint64_t>(),
-                       out.ext_off.as<int64_t>(), out.ext.as<uint64_t>(), long_list.as<uint64_t>(),
-                       long_n.as<unsigned long long>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_gather_ext, n + 1,
+                 perm.as<uint32_t>(), n, in.ext_off.as<int64_t>(),
+                 in.ext.as<uint64_t>(), wscan.as<uint64_t>(),
+                 out.ext_off.as<int64_t>(), out.ext.as<uint64_t>(), long_list.as<uint64_t>(),
+                 long_n.as<unsigned long long>());
     if (in.words > n) {     // some record has more than one word: a long one may exist
-        hipLaunchKernelGGL(k_gather_ext_long, dim3(1024), dim3(256), 0, ctx->stream,
-                           (const uint32_t *)perm.as<uint32_t>(), (const int64_t *)in.ext_off.as<int64_t>(),
-                           (const uint64_t *)in.ext.as<uint64_t>(), (const int64_t *)out.ext_off.as<int64_t>(),
-                           out.ext.as<uint64_t>(), (const uint64_t *)long_list.as<uint64_t>(),
-                           (const unsigned long long *)long_n.as<unsigned long long>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_gather_ext_long, dim3(1024), dim3(256), 0,
+                   perm.as<uint32_t>(), in.ext_off.as<int64_t>(),
+                   in.ext.as<uint64_t>(), out.ext_off.as<int64_t>(),
+                   out.ext.as<uint64_t>(), long_list.as<uint64_t>(),
+                   long_n.as<unsigned long long>());
     }
-    RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_partition_starts<KW>, dim3(grid_for(P + 1)), dim3(256), 0, ctx->stream,
-                                         (const KeyW<KW> *)out.key.as<KeyW<KW>>(), n, P, part_start.as<int64_t>()));
-    RFX_HIP(hipGetLastError());
+    RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_partition_starts<KW>, P + 1,
+                                   out.key.as<KeyW<KW>>(), n, P, part_start.as<int64_t>()));
     out.n = n; out.words = in.words;
     return RFX_OK;
 }
@@ -652,38 +636,35 @@ int fork_filter(rfx_ctx *ctx, bool reflected, const DevRecords &in, const int64_
     const int kw = in.kw;
     if (kw != sub_words(k)) return RFX_E_ARG;
     RFX_TRY(dev_records_alloc(ctx, out, n, n, kw));
-    RFX_HIP(out_part_start.alloc((size_t)(P + 1) * 8, ctx->stream));
+    RFX_ALLOC(out_part_start, int64_t, P + 1);
     DevBuf flag, pos;
-    RFX_HIP(flag.alloc((size_t)(n ? n : 1) * 4, ctx->stream));
-    RFX_HIP(pos.alloc((size_t)(n + 1) * 8, ctx->stream));
+    RFX_ALLOC(flag, uint32_t, n ? n : 1);
+    RFX_ALLOC(pos, uint64_t, n + 1);
     if (n > 0) {
-        RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_head_flags<KW>, dim3(grid_for(n)), dim3(256), 0, ctx->stream,
-                                             (const KeyW<KW> *)in.key.as<KeyW<KW>>(), n, flag.as<uint32_t>()));
-        RFX_HIP(hipGetLastError());
+        RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_head_flags<KW>, n,
+                                       in.key.as<KeyW<KW>>(), n, flag.as<uint32_t>()));
     }
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, flag.as<uint32_t>(), pos.as<uint64_t>(), n));
     const int ds_ec = (twin == RFX_TWIN_DS && min_error_cov != 0) ? 1 : 0;
     if (!reflected) {
-        RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_fork_forward<KW>, dim3(grid_for(n + 1)), dim3(256), 0, ctx->stream,
-                           (const KeyW<KW> *)in.key.as<KeyW<KW>>(), (const int32_t *)in.marker.as<int32_t>(),
-                           (const uint64_t *)in.ext.as<uint64_t>(), (const int32_t *)in.left.as<int32_t>(), n,
-                           (const uint32_t *)flag.as<uint32_t>(), (const uint64_t *)pos.as<uint64_t>(), k - 1,
-                           min_error_cov, ds_ec, out.key.as<KeyW<KW>>(), out.marker.as<int32_t>(),
-                           out.ext_off.as<int64_t>(), out.ext.as<uint64_t>(), out.left.as<int32_t>(),
-                           out.right.as<int32_t>()));
+        RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_fork_forward<KW>, n + 1,
+                                       in.key.as<KeyW<KW>>(), in.marker.as<int32_t>(),
+                                       in.ext.as<uint64_t>(), in.left.as<int32_t>(), n,
+                                       flag.as<uint32_t>(), pos.as<uint64_t>(), k - 1,
+                                       min_error_cov, ds_ec, out.key.as<KeyW<KW>>(), out.marker.as<int32_t>(),
+                                       out.ext_off.as<int64_t>(), out.ext.as<uint64_t>(), out.left.as<int32_t>(),
+                                       out.right.as<int32_t>()));
     } else {
-        RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_fork_reflected<KW>, dim3(grid_for(n + 1)), dim3(256), 0, ctx->stream,
-                           (const KeyW<KW> *)in.key.as<KeyW<KW>>(), (const int32_t *)in.marker.as<int32_t>(),
-                           (const uint64_t *)in.ext.as<uint64_t>(), (const int32_t *)in.left.as<int32_t>(),
-                           (const int32_t *)in.right.as<int32_t>(), n, (const uint32_t *)flag.as<uint32_t>(),
-                           (const uint64_t *)pos.as<uint64_t>(), k - 1, min_error_cov, ds_ec,
-                           out.key.as<KeyW<KW>>(), out.marker.as<int32_t>(), out.ext_off.as<int64_t>(),
-                           out.ext.as<uint64_t>(), out.left.as<int32_t>(), out.right.as<int32_t>()));
+        RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_fork_reflected<KW>, n + 1,
+                                       in.key.as<KeyW<KW>>(), in.marker.as<int32_t>(),
+                                       in.ext.as<uint64_t>(), in.left.as<int32_t>(),
+                                       in.right.as<int32_t>(), n, flag.as<uint32_t>(),
+                                       pos.as<uint64_t>(), k - 1, min_error_cov, ds_ec,
+                                       out.key.as<KeyW<KW>>(), out.marker.as<int32_t>(), out.ext_off.as<int64_t>(),
+                                       out.ext.as<uint64_t>(), out.left.as<int32_t>(), out.right.as<int32_t>()));
     }
-    RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_map_part_start, dim3(grid_for(P + 1)), dim3(256), 0, ctx->stream, d_part_start, P,
-                       (const uint64_t *)pos.as<uint64_t>(), out_part_start.as<int64_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_map_part_start, P + 1, d_part_start, P,
+                 pos.as<uint64_t>(), out_part_start.as<int64_t>());
     uint64_t m = 0;
     RFX_TRY(small_readback(ctx, &m, pos.as<uint64_t>() + n, 8));
     out.n = (int64_t)m; out.words = (int64_t)m;
@@ -696,12 +677,11 @@ int reflect_from_forward(rfx_ctx *ctx, const DevRecords &in, int k, DevRecords &
     const int kw = in.kw;
     if (kw != sub_words(k)) return RFX_E_ARG;
     RFX_TRY(dev_records_alloc(ctx, out, n, n, kw));
-    RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_reflect<KW>, dim3(grid_for(n + 1)), dim3(256), 0, ctx->stream,
-                       (const KeyW<KW> *)in.key.as<KeyW<KW>>(), (const uint64_t *)in.ext.as<uint64_t>(),
-                       (const int32_t *)in.left.as<int32_t>(), (const int32_t *)in.right.as<int32_t>(), n, k - 1,
-                       out.key.as<KeyW<KW>>(), out.marker.as<int32_t>(), out.ext_off.as<int64_t>(),
-                       out.ext.as<uint64_t>(), out.left.as<int32_t>(), out.right.as<int32_t>()));
-    RFX_HIP(hipGetLastError());
+    RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_reflect<KW>, n + 1,
+                                   in.key.as<KeyW<KW>>(), in.ext.as<uint64_t>(),
+                                   in.left.as<int32_t>(), in.right.as<int32_t>(), n, k - 1,
+                                   out.key.as<KeyW<KW>>(), out.marker.as<int32_t>(), out.ext_off.as<int64_t>(),
+                                   out.ext.as<uint64_t>(), out.left.as<int32_t>(), out.right.as<int32_t>()));
     out.n = n; out.words = n;
     return RFX_OK;
 }
@@ -713,13 +693,12 @@ int random_reflection(rfx_ctx *ctx, const DevRecords &in, const int64_t *d_part_
     const int kw = in.kw;
     if (kw != sub_words(k)) return RFX_E_ARG;
     RFX_TRY(dev_records_alloc(ctx, out, n, n, kw));
-    RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_random_reflection<KW>, dim3(grid_for(n + 1)), dim3(256), 0, ctx->stream,
-                       (const KeyW<KW> *)in.key.as<KeyW<KW>>(), (const int32_t *)in.marker.as<int32_t>(),
-                       (const uint64_t *)in.ext.as<uint64_t>(), (const int32_t *)in.left.as<int32_t>(),
-                       (const int32_t *)in.right.as<int32_t>(), n, d_part_start, P, k - 1, d_carry,
-                       out.key.as<KeyW<KW>>(), out.marker.as<int32_t>(), out.ext_off.as<int64_t>(),
-                       out.ext.as<uint64_t>(), out.left.as<int32_t>(), out.right.as<int32_t>()));
-    RFX_HIP(hipGetLastError());
+    RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_random_reflection<KW>, n + 1,
+                                   in.key.as<KeyW<KW>>(), in.marker.as<int32_t>(),
+                                   in.ext.as<uint64_t>(), in.left.as<int32_t>(),
+                                   in.right.as<int32_t>(), n, d_part_start, P, k - 1, d_carry,
+                                   out.key.as<KeyW<KW>>(), out.marker.as<int32_t>(), out.ext_off.as<int64_t>(),
+                                   out.ext.as<uint64_t>(), out.left.as<int32_t>(), out.right.as<int32_t>()));
     out.n = n; out.words = n;
     return RFX_OK;
 }
@@ -730,15 +709,13 @@ int counter_to_asm(rfx_ctx *ctx, const uint64_t *d_keys32, const int64_t *d_coun
     *out_n = 0;
     if (n == 0) return RFX_OK;
     DevBuf flag, pos;
-    RFX_HIP(flag.alloc((size_t)n * 4, ctx->stream));
-    RFX_HIP(pos.alloc((size_t)(n + 1) * 8, ctx->stream));
-    hipLaunchKernelGGL(k_counter_keep, dim3(grid_for(n)), dim3(256), 0, ctx->stream, d_counts64, n, min_cov, max_cov,
-                       flag.as<uint32_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_ALLOC(flag, uint32_t, n);
+    RFX_ALLOC(pos, uint64_t, n + 1);
+    RFX_LAUNCH_N(k_counter_keep, n, d_counts64, n, min_cov, max_cov,
+                 flag.as<uint32_t>());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, flag.as<uint32_t>(), pos.as<uint64_t>(), n));
-    hipLaunchKernelGGL(k_counter_to_asm, dim3(grid_for(n)), dim3(256), 0, ctx->stream, d_keys32, d_counts64, n, k,
-                       (const uint32_t *)flag.as<uint32_t>(), (const uint64_t *)pos.as<uint64_t>(), d_out31, d_out_counts);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_counter_to_asm, n, d_keys32, d_counts64, n, k,
+                 flag.as<uint32_t>(), pos.as<uint64_t>(), d_out31, d_out_counts);
     uint64_t m = 0;
     RFX_TRY(small_readback(ctx, &m, pos.as<uint64_t>() + n, 8));
     *out_n = (int64_t)m;

@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <time.h>
 #include <algorithm>
+#include <initializer_list>
 #include <string>
 #include <vector>
 #include <map>
@@ -291,8 +292,18 @@ struct ScopedTimer {
 };
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-// the launch shape of the one-thread-per-item kernels: ceil(n / 256) blocks (one for n = 0) of 256 threads on the context's stream
-#define RFX_GRID(n) dim3((unsigned)ceil_div(std::max<int64_t>((n), 1), 256)), dim3(256), 0, ctx->stream
+// Every kernel launch of the library: on the context's stream, and checked -- a launch that failed (a bad shape, too much LDS)
+// returns RFX_E_HIP from the CALLER with the line of the launch in last_error, which is why these are macros.
+#define RFX_LAUNCH(kernel, grid, block, lds_bytes, ...)                                          \
+    do {                                                                                         \
+        hipLaunchKernelGGL(kernel, grid, block, lds_bytes, ctx->stream, ##__VA_ARGS__);          \
+        RFX_HIP(hipGetLastError());                                                              \
+    } while (0)
+// the shape of the one-thread-per-item kernels: ceil(n / 256) blocks (one for n = 0) of 256 threads, no LDS
+#define RFX_LAUNCH_N(kernel, n, ...) \
+    RFX_LAUNCH(kernel, dim3((unsigned)ceil_div(std::max<int64_t>((n), 1), 256)), dim3(256), 0, ##__VA_ARGS__)
+// scratch for `count` elements of T
+#define RFX_ALLOC(buf, T, count) RFX_HIP((buf).alloc((size_t)(count) * sizeof(T), ctx->stream))
 
 namespace rfx {
 
@@ -491,6 +502,24 @@ bool dyn_packed_ok(const rfx_dyn_packed *p);
 bool text_rows_ok(const char *text, const int64_t *row_off, int64_t n);
 int dyn_empty(rfx_ctx *ctx, DynDev &d);
 int check_part_starts(rfx_ctx *ctx, const int64_t *d_ps, int P, int64_t n, const char *stage_name);
+#pragma GCC visibility push(hidden)                               // (the library's own: its exported symbols stay as they were)
+bool parts_ok(int P);                                              // 1 <= P <= 63: what the one-workgroup partition kernels take
+// host steps the stages share.  scan_keep: d_rank[0..n] = the exclusive scan of n keep flags, *total = d_rank[n] read back (one host
+// wait; a site whose CallFlags read-back carries the total does not use it).  part_starts_alloc: out_ps = int64[P + 1], zeros when
+// `zeroed` (the empty set).  part_starts_store: P + 1 entries of ops into the caller's device array, then the wait that ends the call.
+// out_part_starts: d_out[p] = d_prefix[d_ps[p]], p = 0..P (one workgroup of 64).  index_kept: d_idx[d_rank[i]] = i where d_keep[i]
+int scan_keep(rfx_ctx *ctx, const uint32_t *d_keep, int64_t n, uint64_t *d_rank, int64_t *total);
+int part_starts_alloc(rfx_ctx *ctx, DevBuf &out_ps, int P, bool zeroed);
+int part_starts_store(rfx_ctx *ctx, int64_t *d_dst, const DevBuf &ops, int P);
+int out_part_starts(rfx_ctx *ctx, const int64_t *d_ps, int P, const uint64_t *d_prefix, int64_t *d_out);
+int index_kept(rfx_ctx *ctx, const uint32_t *d_keep, const uint64_t *d_rank, int64_t n, int64_t *d_idx);
+// The tail of the host-text entry points: every length out, then the texts from the library's buffers to the caller's, one wait.
+// A buffer that is too short gives RFX_E_CAP with every length set, and there are two behaviours, kept per entry point:
+// fill_to_cap (rfx_dyn_run_text, rfx_ksort_text): each buffer is filled up to its capacity; otherwise (rfx_reduce_text, rfx_fix_text,
+// rfx_fix2_text): nothing is written and nothing is waited for
+struct TextOut { const DevBuf &d; int64_t total; char *out; int64_t cap; int64_t *out_len; };
+int text_to_host(rfx_ctx *ctx, std::initializer_list<TextOut> outs, bool fill_to_cap);
+#pragma GCC visibility pop
 // sort("k-1") + the cut into P logical partitions: in -> out (sorted), d_ps[P + 1]; *lmin = the shortest key
 int dyn_sort(rfx_ctx *ctx, const DynDev &in, int P, DynDev &out, DevBuf &d_ps, uint32_t *lmin);
 // a view of the caller's input set (nothing copied, nothing freed) / the result into the caller's arrays (both capacities are

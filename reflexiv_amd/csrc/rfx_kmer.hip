@@ -3271,18 +3271,16 @@ int encode_reads(rfx_ctx *ctx, const uint8_t *d_bases, const int64_t *d_read_off
                  int words_per_read, uint64_t *d_words, uint32_t *d_read_len) {
     int64_t total = n_reads * words_per_read;
     if (total <= 0) return RFX_OK;
-    hipLaunchKernelGGL(k_encode, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, ctx->stream, d_bases,
-                       d_read_off, n_reads, words_per_read, d_words, d_read_len);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH(k_encode, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, d_bases,
+               d_read_off, n_reads, words_per_read, d_words, d_read_len);
     return RFX_OK;
 }
 
 int kmer_counts_per_read(rfx_ctx *ctx, const int64_t *d_read_off, int64_t n_reads, int k, int front_clip,
                          int end_clip, uint64_t *d_nk) {
     if (n_reads <= 0) return RFX_OK;
-    hipLaunchKernelGGL(k_nk_per_read, dim3((unsigned)ceil_div(n_reads, 256)), dim3(256), 0, ctx->stream,
-                       d_read_off, n_reads, k, front_clip, end_clip, d_nk);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH(k_nk_per_read, dim3((unsigned)ceil_div(n_reads, 256)), dim3(256), 0,
+               d_read_off, n_reads, k, front_clip, end_clip, d_nk);
     return RFX_OK;
 }
 
@@ -3290,9 +3288,8 @@ int extract_ordered_packed(rfx_ctx *ctx, const uint64_t *d_words, int wpr, const
                            int64_t n_reads, int k, int front_clip, uint64_t *d_out) {
     if (n_reads <= 0) return RFX_OK;
     int64_t threads = n_reads * 64;
-    hipLaunchKernelGGL(k_extract_ordered, dim3((unsigned)ceil_div(threads, 256)), dim3(256), 0, ctx->stream,
-                       d_words, wpr, d_kmer_off, n_reads, k, front_clip, d_out);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH(k_extract_ordered, dim3((unsigned)ceil_div(threads, 256)), dim3(256), 0,
+               d_words, wpr, d_kmer_off, n_reads, k, front_clip, d_out);
     return RFX_OK;
 }
 
@@ -3301,11 +3298,10 @@ int ragged_instances(rfx_ctx *ctx, const uint32_t *d_read_len, int64_t n_reads, 
     *out_total = 0;
     if (n_reads <= 0) return RFX_OK;
     DevBuf nk, off;
-    RFX_HIP(nk.alloc((size_t)n_reads * 8, ctx->stream));
-    RFX_HIP(off.alloc((size_t)(n_reads + 1) * 8, ctx->stream));
-    hipLaunchKernelGGL(wide ? k_nk_from_len_w : k_nk_from_len, dim3((unsigned)ceil_div(n_reads, 256)), dim3(256), 0, ctx->stream,
-                       d_read_len, n_reads, k, front_clip, end_clip, nk.as<uint64_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_ALLOC(nk, uint64_t, n_reads);
+    RFX_ALLOC(off, uint64_t, n_reads + 1);
+    RFX_LAUNCH(wide ? k_nk_from_len_w : k_nk_from_len, dim3((unsigned)ceil_div(n_reads, 256)), dim3(256), 0,
+               d_read_len, n_reads, k, front_clip, end_clip, nk.as<uint64_t>());
     RFX_TRY(exclusive_scan_u64(ctx, nk.as<uint64_t>(), off.as<uint64_t>(), n_reads));
     uint64_t t = 0;
     RFX_HIP(hipMemcpyAsync(&t, off.as<uint64_t>() + n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -3400,11 +3396,10 @@ static int finish_leaves(rfx_ctx *ctx, const typename LeafElem<ELEM>::T *elems, 
     // a table takes ~3300 keys before probe sequences run long); measured neutral for pairs and not used there
     const uint32_t presplit = getenv("RFX_PRESPLIT") ? (uint32_t)atoi(getenv("RFX_PRESPLIT")) : ELEM == 1 ? 8000u : 0u;
     DevBuf nsl, spos;
-    RFX_HIP(nsl.alloc((size_t)nleaf * 8, ctx->stream));
-    RFX_HIP(spos.alloc((size_t)(nleaf + 1) * 8, ctx->stream));
-    hipLaunchKernelGGL(k_heavy_count, dim3((unsigned)ceil_div(nleaf, 256)), dim3(256), 0, ctx->stream, d_leaf_off, d_leaf_end, nleaf,
-                       heavy, slice, nsl.as<uint64_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_ALLOC(nsl, uint64_t, nleaf);
+    RFX_ALLOC(spos, uint64_t, nleaf + 1);
+    RFX_LAUNCH(k_heavy_count, dim3((unsigned)ceil_div(nleaf, 256)), dim3(256), 0, d_leaf_off, d_leaf_end, nleaf,
+               heavy, slice, nsl.as<uint64_t>());
     RFX_TRY(exclusive_scan_u64(ctx, nsl.as<uint64_t>(), spos.as<uint64_t>(), nleaf));
     uint64_t n_slices = 0;
     RFX_HIP(hipMemcpyAsync(&n_slices, spos.as<uint64_t>() + nleaf, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -3417,36 +3412,33 @@ static int finish_leaves(rfx_ctx *ctx, const typename LeafElem<ELEM>::T *elems, 
         int64_t grid = std::min<int64_t>(nleaf, (int64_t)ctx->num_cu * leaf_per_cu);      // persistent, <= 78 KB LDS each
         auto *kern = k_leaf_count<ELEM, 0>;
         if (RECS && k == 31) kern = k_leaf_count<ELEM, RECS ? 31 : 0>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(LT), 0, ctx->stream, elems, d_leaf_off, d_leaf_end, nleaf,
-                           (const uint64_t *)nullptr, (const uint64_t *)nullptr, heavy, (uint64_t)elem_count, k, min_cov,
-                           max_cov, apply, d_out_keys, d_out_counts, (unsigned long long)cap, co_buf.as<CountOut>(),
-                           (int)pair_out, presplit);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(kern, dim3((unsigned)grid), dim3(LT), 0, elems, d_leaf_off, d_leaf_end, nleaf,
+                   (const uint64_t *)nullptr, (const uint64_t *)nullptr, heavy, (uint64_t)elem_count, k, min_cov,
+                   max_cov, apply, d_out_keys, d_out_counts, (unsigned long long)cap, co_buf.as<CountOut>(),
+                   (int)pair_out, presplit);
     }
     RFX_TRY(sync_checked(ctx));
     if (n_slices > 0) {
         DevBuf sb, se, co2, pk, pc, tk, tv;
-        RFX_HIP(sb.alloc((size_t)n_slices * 8, ctx->stream));
-        RFX_HIP(se.alloc((size_t)n_slices * 8, ctx->stream));
+        RFX_ALLOC(sb, uint64_t, n_slices);
+        RFX_ALLOC(se, uint64_t, n_slices);
         RFX_HIP(co2.alloc(sizeof(CountOut), ctx->stream));
-        hipLaunchKernelGGL(k_heavy_fill, dim3((unsigned)ceil_div(nleaf, 256)), dim3(256), 0, ctx->stream, d_leaf_off, d_leaf_end, nleaf,
-                           (const uint64_t *)spos.as<uint64_t>(), sb.as<uint64_t>(), se.as<uint64_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_heavy_fill, dim3((unsigned)ceil_div(nleaf, 256)), dim3(256), 0, d_leaf_off, d_leaf_end, nleaf,
+                   spos.as<uint64_t>(), sb.as<uint64_t>(), se.as<uint64_t>());
         // partial counts: every distinct key of every slice; grow on demand
         uint64_t pcap = std::max<uint64_t>(pcap_min, n_slices * 64);
         CountOut c2{};
         for (;;) {
-            RFX_HIP(pk.alloc((size_t)pcap * 8, ctx->stream));
-            RFX_HIP(pc.alloc((size_t)pcap * 4, ctx->stream));
+            RFX_ALLOC(pk, uint64_t, pcap);
+            RFX_ALLOC(pc, int32_t, pcap);
             RFX_HIP(hipMemsetAsync(co2.p, 0, sizeof(CountOut), ctx->stream));
             {
                 ScopedTimer t(ctx, "leaf");
                 int64_t grid = std::min<int64_t>((int64_t)n_slices, (int64_t)ctx->num_cu * 2);
-                hipLaunchKernelGGL(k_leaf_count<ELEM>, dim3((unsigned)grid), dim3(LT), 0, ctx->stream, elems, d_leaf_off, d_leaf_end,
-                                   (int64_t)n_slices, (const uint64_t *)sb.as<uint64_t>(), (const uint64_t *)se.as<uint64_t>(),
-                                   (uint64_t)0, (uint64_t)elem_count, k, min_cov, max_cov, 0, pk.as<uint64_t>(),
-                                   pc.as<int32_t>(), (unsigned long long)pcap, co2.as<CountOut>(), 0, 0u);
-                RFX_HIP(hipGetLastError());
+                RFX_LAUNCH(k_leaf_count<ELEM>, dim3((unsigned)grid), dim3(LT), 0, elems, d_leaf_off, d_leaf_end,
+                           (int64_t)n_slices, sb.as<uint64_t>(), se.as<uint64_t>(),
+                           (uint64_t)0, (uint64_t)elem_count, k, min_cov, max_cov, 0, pk.as<uint64_t>(),
+                           pc.as<int32_t>(), (unsigned long long)pcap, co2.as<CountOut>(), 0, 0u);
             }
             RFX_HIP(hipMemcpyAsync(&c2, co2.p, sizeof c2, hipMemcpyDeviceToHost, ctx->stream));
             RFX_TRY(sync_checked(ctx));
@@ -3455,16 +3447,15 @@ static int finish_leaves(rfx_ctx *ctx, const typename LeafElem<ELEM>::T *elems, 
             pcap = c2.n_out;
         }
         if (c2.n_out >= (1ULL << 32)) { ctx->last_error = "too many partial counts"; ScopedTimer::collect(ctx); return RFX_E_LIMIT; }
-        RFX_HIP(tk.alloc((size_t)c2.n_out * 8, ctx->stream));
-        RFX_HIP(tv.alloc((size_t)c2.n_out * 4, ctx->stream));
+        RFX_ALLOC(tk, uint64_t, c2.n_out);
+        RFX_ALLOC(tv, uint32_t, c2.n_out);
         ScopedTimer t(ctx, "leaf");
         RFX_TRY(sort_pairs(ctx, pk.as<uint64_t>(), pc.as<uint32_t>(), (int64_t)c2.n_out, key_bits, tk.as<uint64_t>(),
                            tv.as<uint32_t>()));
-        hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)ceil_div((int64_t)c2.n_out, 256)), dim3(256), 0, ctx->stream,
-                           (const uint64_t *)pk.as<uint64_t>(), (const uint32_t *)pc.as<uint32_t>(), (int64_t)c2.n_out,
-                           min_cov, max_cov, apply, d_out_keys, d_out_counts, (unsigned long long)cap, co_buf.as<CountOut>(),
-                           (int)pair_out);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_reduce_partials, dim3((unsigned)ceil_div((int64_t)c2.n_out, 256)), dim3(256), 0,
+                   pk.as<uint64_t>(), pc.as<uint32_t>(), (int64_t)c2.n_out,
+                   min_cov, max_cov, apply, d_out_keys, d_out_counts, (unsigned long long)cap, co_buf.as<CountOut>(),
+                   (int)pair_out);
         t.stop();
         if (getenv("RFX_TRACE"))
             fprintf(stderr, "heavy leaves: %llu slices, %llu partial counts\n", (unsigned long long)n_slices, c2.n_out);
@@ -3485,8 +3476,8 @@ static int finish_leaves(rfx_ctx *ctx, const typename LeafElem<ELEM>::T *elems, 
     // ascending k-mer order (order contract B.0)
     if (!pair_out) {
         DevBuf tk, tv;
-        RFX_HIP(tk.alloc((size_t)co.n_out * 8, ctx->stream));
-        RFX_HIP(tv.alloc((size_t)co.n_out * 4, ctx->stream));
+        RFX_ALLOC(tk, uint64_t, co.n_out);
+        RFX_ALLOC(tv, uint32_t, co.n_out);
         ScopedTimer t(ctx, "sort");
         RFX_TRY(sort_pairs(ctx, d_out_keys, reinterpret_cast<uint32_t *>(d_out_counts), (int64_t)co.n_out, key_bits,
                            tk.as<uint64_t>(), tv.as<uint32_t>()));
@@ -3504,38 +3495,38 @@ static bool superkmer_enabled(int k) {
 
 #define RFX_SK_W_CASES(X) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18)
 template <bool DESC, bool WIDE = false, class... Args>
-static void launch_sk_hist(int W, dim3 grid, hipStream_t st, Args... args) {
+static int launch_sk_hist(rfx_ctx *ctx, int W, dim3 grid, Args... args) {
     if constexpr (WIDE) {                  // the central window is 30 or 31 bases: W = 18 or 19
-        if (W == 18) hipLaunchKernelGGL((k_sk_hist<18, DESC, true>), grid, dim3(SKT), 0, st, args...);
-        else hipLaunchKernelGGL((k_sk_hist<19, DESC, true>), grid, dim3(SKT), 0, st, args...);
-        return;
+        if (W == 18) RFX_LAUNCH((k_sk_hist<18, DESC, true>), grid, dim3(SKT), 0, args...);
+        else RFX_LAUNCH((k_sk_hist<19, DESC, true>), grid, dim3(SKT), 0, args...);
+        return RFX_OK;
     }
     switch (W) {
-#define X(w) case w: hipLaunchKernelGGL((k_sk_hist<w, DESC>), grid, dim3(SKT), 0, st, args...); break;
+#define X(w) case w: RFX_LAUNCH((k_sk_hist<w, DESC>), grid, dim3(SKT), 0, args...); break;
         RFX_SK_W_CASES(X)
 #undef X
-        default: hipLaunchKernelGGL((k_sk_hist<19, DESC>), grid, dim3(SKT), 0, st, args...); break;
+        default: RFX_LAUNCH((k_sk_hist<19, DESC>), grid, dim3(SKT), 0, args...); break;
     }
+    return RFX_OK;
 }
 
 template <int W, bool DESC, bool WIDE, class... Args>
-static hipError_t launch_sk_scatter_w(dim3 grid, size_t lds, hipStream_t st, Args... args) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_sk_scatter<W, DESC, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_sk_scatter<W, DESC, WIDE>), grid, dim3(SKT), lds, st, args...);
-    return hipGetLastError();
+static int launch_sk_scatter_w(rfx_ctx *ctx, dim3 grid, size_t lds, Args... args) {
+    RFX_HIP(hipFuncSetAttribute((const void *)k_sk_scatter<W, DESC, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    RFX_LAUNCH((k_sk_scatter<W, DESC, WIDE>), grid, dim3(SKT), lds, args...);
+    return RFX_OK;
 }
 template <bool DESC, bool WIDE, class... Args>
-static hipError_t launch_sk_scatter(int W, dim3 grid, size_t lds, hipStream_t st, Args... args) {
+static int launch_sk_scatter(rfx_ctx *ctx, int W, dim3 grid, size_t lds, Args... args) {
     if constexpr (WIDE) {                  // the central window is 30 or 31 bases: W = 18 or 19
-        if (W == 18) return launch_sk_scatter_w<18, DESC, true>(grid, lds, st, args...);
-        return launch_sk_scatter_w<19, DESC, true>(grid, lds, st, args...);
+        if (W == 18) return launch_sk_scatter_w<18, DESC, true>(ctx, grid, lds, args...);
+        return launch_sk_scatter_w<19, DESC, true>(ctx, grid, lds, args...);
     } else {
         switch (W) {
-#define X(w) case w: return launch_sk_scatter_w<w, DESC, false>(grid, lds, st, args...);
+#define X(w) case w: return launch_sk_scatter_w<w, DESC, false>(ctx, grid, lds, args...);
             RFX_SK_W_CASES(X)
 #undef X
-            default: return launch_sk_scatter_w<19, DESC, false>(grid, lds, st, args...);
+            default: return launch_sk_scatter_w<19, DESC, false>(ctx, grid, lds, args...);
         }
     }
 }
@@ -3557,8 +3548,8 @@ static int records_from_reads(rfx_ctx *ctx, const ReadSrc &rsrc, const Level &lv
     const int per_cu = sk_lds <= 80 * 1024 ? 8 : 1;
     const unsigned G = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(rsrc.n_threads, SKT), (int64_t)ctx->num_cu * per_cu));
     DevBuf bh, scanned;
-    RFX_HIP(bh.alloc((size_t)nb * G * 8, ctx->stream));
-    RFX_HIP(scanned.alloc(((size_t)nb * G + 1) * 8, ctx->stream));
+    RFX_ALLOC(bh, uint64_t, (size_t)nb * G);
+    RFX_ALLOC(scanned, uint64_t, (size_t)nb * G + 1);
     // run descriptors (hist -> scatter) live in the workspace slot the records do not use yet
     uint32_t *desc = nullptr;
     const bool want_desc = lv.n_owners <= 64 && !(getenv("RFX_SK_DESC") && atoi(getenv("RFX_SK_DESC")) == 0);
@@ -3566,14 +3557,12 @@ static int records_from_reads(rfx_ctx *ctx, const ReadSrc &rsrc, const Level &lv
     if (want_desc) desc = (uint32_t *)ctx->ws_get(use_ws && ws_slot == 1 ? 0 : 1, (size_t)(3 + SKD) * 4 * (size_t)rsrc.n_threads);
     {
         ScopedTimer t(ctx, hn);
-        if (desc) launch_sk_hist<true, WIDE>(W, dim3(G), ctx->stream, rsrc, lv, bh.as<uint64_t>(), desc);
-        else launch_sk_hist<false, WIDE>(W, dim3(G), ctx->stream, rsrc, lv, bh.as<uint64_t>(), (uint32_t *)nullptr);
-        RFX_HIP(hipGetLastError());
+        if (desc) RFX_TRY((launch_sk_hist<true, WIDE>(ctx, W, dim3(G), rsrc, lv, bh.as<uint64_t>(), desc)));
+        else RFX_TRY((launch_sk_hist<false, WIDE>(ctx, W, dim3(G), rsrc, lv, bh.as<uint64_t>(), (uint32_t *)nullptr)));
     }
     RFX_TRY(exclusive_scan_u64(ctx, bh.as<uint64_t>(), scanned.as<uint64_t>(), (int64_t)nb * G));
-    hipLaunchKernelGGL(k_bin_offsets, dim3((unsigned)ceil_div(nb + 1, 256)), dim3(256), 0, ctx->stream,
-                       (const uint64_t *)scanned.as<uint64_t>(), nb, (int64_t)G, d_seg_off);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH(k_bin_offsets, dim3((unsigned)ceil_div(nb + 1, 256)), dim3(256), 0,
+               scanned.as<uint64_t>(), nb, (int64_t)G, d_seg_off);
     uint64_t R = 0;
     RFX_HIP(hipMemcpyAsync(&R, scanned.as<uint64_t>() + (size_t)nb * G, 8, hipMemcpyDeviceToHost, ctx->stream));
     RFX_TRY(sync_checked(ctx));
@@ -3587,10 +3576,8 @@ static int records_from_reads(rfx_ctx *ctx, const ReadSrc &rsrc, const Level &lv
     }
     {
         ScopedTimer t(ctx, pn);
-        if (desc) RFX_HIP((launch_sk_scatter<true, WIDE>(W, dim3(G), sk_lds, ctx->stream, rsrc, lv,
-                                                         (const uint64_t *)scanned.as<uint64_t>(), dst, (const uint32_t *)desc)));
-        else RFX_HIP((launch_sk_scatter<false, WIDE>(W, dim3(G), sk_lds, ctx->stream, rsrc, lv,
-                                                     (const uint64_t *)scanned.as<uint64_t>(), dst, (const uint32_t *)nullptr)));
+        if (desc) RFX_TRY((launch_sk_scatter<true, WIDE>(ctx, W, dim3(G), sk_lds, rsrc, lv, scanned.as<uint64_t>(), dst, (const uint32_t *)desc)));
+        else RFX_TRY((launch_sk_scatter<false, WIDE>(ctx, W, dim3(G), sk_lds, rsrc, lv, scanned.as<uint64_t>(), dst, (const uint32_t *)nullptr)));
     }
     *out_recs = dst;
     return RFX_OK;
@@ -3627,31 +3614,29 @@ static int records_onesweep(rfx_ctx *ctx, const ReadSrc &rsrc_in, const Level &l
     const int cap_pct = getenv("RFX_SK_ONESWEEP_CAP") ? std::max(1, atoi(getenv("RFX_SK_ONESWEEP_CAP"))) : 100;
     DevBuf hist, reg_start, reg_cap, cursor, totals, holes;
     RFX_HIP(hist.alloc((size_t)nb * 8 + 16, ctx->stream));                 // + the overflow flag
-    RFX_HIP(reg_start.alloc((size_t)(nb + 1) * 8, ctx->stream));
-    RFX_HIP(reg_cap.alloc((size_t)nb * 4, ctx->stream));
-    RFX_HIP(cursor.alloc((size_t)nb * OS_CSTRIDE * 8, ctx->stream));
+    RFX_ALLOC(reg_start, uint64_t, nb + 1);
+    RFX_ALLOC(reg_cap, uint32_t, nb);
+    RFX_ALLOC(cursor, unsigned long long, (size_t)nb * OS_CSTRIDE);
     RFX_HIP(totals.alloc(24, ctx->stream));
-    RFX_HIP(holes.alloc((size_t)nb * OS_HOLES * G * 8, ctx->stream));
+    RFX_ALLOC(holes, uint64_t, (size_t)nb * OS_HOLES * G);
     RFX_HIP(hipMemsetAsync(hist.p, 0, (size_t)nb * 8 + 16, ctx->stream));
     int *d_overflow = (int *)(hist.as<unsigned long long>() + nb);
     {
         ScopedTimer t(ctx, hn);
         const dim3 gs((unsigned)std::min<int64_t>(n_sampled, (int64_t)ctx->num_cu * 8));
         if constexpr (WIDE) {
-            if (W == 18) hipLaunchKernelGGL((k_sk_sample_hist<18, 16, true>), gs, dim3(SKT), 0, ctx->stream, rsrc, lv, sample, hist.as<unsigned long long>());
-            else hipLaunchKernelGGL((k_sk_sample_hist<19, 16, true>), gs, dim3(SKT), 0, ctx->stream, rsrc, lv, sample, hist.as<unsigned long long>());
+            if (W == 18) RFX_LAUNCH((k_sk_sample_hist<18, 16, true>), gs, dim3(SKT), 0, rsrc, lv, sample, hist.as<unsigned long long>());
+            else RFX_LAUNCH((k_sk_sample_hist<19, 16, true>), gs, dim3(SKT), 0, rsrc, lv, sample, hist.as<unsigned long long>());
         } else switch (W) {
-#define X(w) case w: if (seg32) hipLaunchKernelGGL((k_sk_sample_hist<w, 32>), gs, dim3(SKT), 0, ctx->stream, rsrc, lv, sample, hist.as<unsigned long long>()); \
-                     else hipLaunchKernelGGL((k_sk_sample_hist<w>), gs, dim3(SKT), 0, ctx->stream, rsrc, lv, sample, hist.as<unsigned long long>()); break;
+#define X(w) case w: if (seg32) RFX_LAUNCH((k_sk_sample_hist<w, 32>), gs, dim3(SKT), 0, rsrc, lv, sample, hist.as<unsigned long long>()); \
+                     else RFX_LAUNCH((k_sk_sample_hist<w>), gs, dim3(SKT), 0, rsrc, lv, sample, hist.as<unsigned long long>()); break;
             RFX_SK_W_CASES(X)
             default: X(19)
 #undef X
         }
-        RFX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_plan_regions, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned long long *)hist.as<unsigned long long>(), nb,
-                           (double)ntile_s / (double)n_sampled, G, cap_pct, (double)ntile, reg_start.as<uint64_t>(), reg_cap.as<uint32_t>(),
-                           cursor.as<unsigned long long>(), totals.as<unsigned long long>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_plan_regions, dim3(1), dim3(1024), 0, hist.as<unsigned long long>(), nb,
+                   (double)ntile_s / (double)n_sampled, G, cap_pct, (double)ntile, reg_start.as<uint64_t>(), reg_cap.as<uint32_t>(),
+                   cursor.as<unsigned long long>(), totals.as<unsigned long long>());
     }
     unsigned long long h_tot[3] = {0, 0, 0};
     RFX_HIP(hipMemcpyAsync(h_tot, totals.p, 24, hipMemcpyDeviceToHost, ctx->stream));
@@ -3678,29 +3663,27 @@ static int records_onesweep(rfx_ctx *ctx, const ReadSrc &rsrc_in, const Level &l
         if constexpr (WIDE) {                  // the central window is 30 or 31 bases: W = 18 or 19
             if (W == 18) {
                 RFX_HIP(hipFuncSetAttribute((const void *)k_sk_onesweep<18, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL((k_sk_onesweep<18, true>), dim3((unsigned)G), dim3(SKT), lds, ctx->stream, rsrc, lv, os, dst);
+                RFX_LAUNCH((k_sk_onesweep<18, true>), dim3((unsigned)G), dim3(SKT), lds, rsrc, lv, os, dst);
             } else {
                 RFX_HIP(hipFuncSetAttribute((const void *)k_sk_onesweep<19, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL((k_sk_onesweep<19, true>), dim3((unsigned)G), dim3(SKT), lds, ctx->stream, rsrc, lv, os, dst);
+                RFX_LAUNCH((k_sk_onesweep<19, true>), dim3((unsigned)G), dim3(SKT), lds, rsrc, lv, os, dst);
             }
         } else {
             switch (W) {
 #define X(w) case w: if (seg32) { \
                          RFX_HIP(hipFuncSetAttribute((const void *)k_sk_onesweep<w, false, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-                         hipLaunchKernelGGL((k_sk_onesweep<w, false, 32>), dim3((unsigned)G), dim3(OST), lds, ctx->stream, rsrc, lv, os, dst); \
+                         RFX_LAUNCH((k_sk_onesweep<w, false, 32>), dim3((unsigned)G), dim3(OST), lds, rsrc, lv, os, dst); \
                      } else { \
                          RFX_HIP(hipFuncSetAttribute((const void *)k_sk_onesweep<w>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-                         hipLaunchKernelGGL((k_sk_onesweep<w>), dim3((unsigned)G), dim3(SKT), lds, ctx->stream, rsrc, lv, os, dst); \
+                         RFX_LAUNCH((k_sk_onesweep<w>), dim3((unsigned)G), dim3(SKT), lds, rsrc, lv, os, dst); \
                      } break;
                 RFX_SK_W_CASES(X)
                 default: X(19)
 #undef X
             }
         }
-        RFX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_fix_holes<Rec>, dim3((unsigned)nb), dim3(FH_T), 0, ctx->stream, os, G, dst, d_seg_begin, d_seg_end,
-                           totals.as<unsigned long long>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_fix_holes<Rec>, dim3((unsigned)nb), dim3(FH_T), 0, os, G, dst, d_seg_begin, d_seg_end,
+                   totals.as<unsigned long long>());
     }
     int h_over = 0;
     RFX_HIP(hipMemcpyAsync(h_tot, totals.p, 16, hipMemcpyDeviceToHost, ctx->stream));
@@ -3746,18 +3729,16 @@ static int records_resweep(rfx_ctx *ctx, const typename LevelElem<MODE>::T *recs
     const int64_t n_sampled = ceil_div(nchunk, sample);
     DevBuf hist, reg_start, cursor;
     RFX_HIP(hist.alloc((size_t)nb * 8 + 8, ctx->stream));                  // + the overflow flag
-    RFX_HIP(reg_start.alloc((size_t)(nb + 1) * 8, ctx->stream));
-    RFX_HIP(cursor.alloc((size_t)nb * 8, ctx->stream));
+    RFX_ALLOC(reg_start, uint64_t, nb + 1);
+    RFX_ALLOC(cursor, unsigned long long, nb);
     RFX_HIP(hipMemsetAsync(hist.p, 0, (size_t)nb * 8 + 8, ctx->stream));
     const ClaimPlan pl{reg_start.as<uint64_t>(), cursor.as<unsigned long long>(), (int *)(hist.as<unsigned long long>() + nb)};
     {
         ScopedTimer t(ctx, hn);
-        hipLaunchKernelGGL(k_rec_sample_hist<MODE>, dim3((unsigned)std::min<int64_t>(n_sampled, (int64_t)ctx->num_cu * 8)), dim3(PT), 0, ctx->stream,
-                           recs, (uint64_t)n_recs, lv, used, sample, hist.as<unsigned long long>());
-        RFX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_claim_plan, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned long long *)hist.as<unsigned long long>(), nb,
-                           (double)nchunk / (double)n_sampled, pl);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_rec_sample_hist<MODE>, dim3((unsigned)std::min<int64_t>(n_sampled, (int64_t)ctx->num_cu * 8)), dim3(PT), 0,
+                   recs, (uint64_t)n_recs, lv, used, sample, hist.as<unsigned long long>());
+        RFX_LAUNCH(k_claim_plan, dim3(1), dim3(1024), 0, hist.as<unsigned long long>(), nb,
+                   (double)nchunk / (double)n_sampled, pl);
     }
     uint64_t total = 0;
     RFX_HIP(hipMemcpyAsync(&total, reg_start.as<uint64_t>() + nb, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -3773,11 +3754,9 @@ static int records_resweep(rfx_ctx *ctx, const typename LevelElem<MODE>::T *recs
         //  With four times as many, started in four shifts, a minimiser site's records lay in four short stretches of its bucket
         //  and the next level's 1/16 sample misjudged a few children in every generation)
         const int per_cu = lds <= 72 * 1024 ? 2 : 1;
-        hipLaunchKernelGGL((k_rec_claim_scatter<B, MODE>), dim3((unsigned)std::min<int64_t>(ceil_div(n_recs, CHUNK), (int64_t)ctx->num_cu * per_cu)), dim3(WCT), lds, ctx->stream, recs, (uint64_t)n_recs, lv, used,
-                           pl, dst);
-        RFX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_claim_ends, dim3((unsigned)ceil_div(nb, 256)), dim3(256), 0, ctx->stream, pl, nb, d_seg_begin, d_seg_end);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH((k_rec_claim_scatter<B, MODE>), dim3((unsigned)std::min<int64_t>(ceil_div(n_recs, CHUNK), (int64_t)ctx->num_cu * per_cu)), dim3(WCT), lds, recs, (uint64_t)n_recs, lv, used,
+                   pl, dst);
+        RFX_LAUNCH(k_claim_ends, dim3((unsigned)ceil_div(nb, 256)), dim3(256), 0, pl, nb, d_seg_begin, d_seg_end);
     }
     int h_over = 0;
     RFX_HIP(hipMemcpyAsync(&h_over, pl.overflow, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -3835,30 +3814,27 @@ static int partition_record_levels(rfx_ctx *ctx, const typename LevelElem<MODE>:
         const int tpb = (int)std::min<int64_t>(32, std::max<int64_t>(1, total_tiles / ((int64_t)ctx->num_cu * 8)));
         const int64_t v_bound = ceil_div(std::max<int64_t>(n_recs, 1), (int64_t)tpb * PTILE) + nseg;
         DevBuf nvb, vb_start, table, scanned;
-        RFX_HIP(nvb.alloc((size_t)nseg * 8, ctx->stream));
-        RFX_HIP(vb_start.alloc((size_t)(nseg + 1) * 8, ctx->stream));
-        RFX_HIP(table.alloc((size_t)nb * v_bound * 4, ctx->stream));
-        RFX_HIP(scanned.alloc(((size_t)nb * v_bound + 1) * 8, ctx->stream));
+        RFX_ALLOC(nvb, uint64_t, nseg);
+        RFX_ALLOC(vb_start, uint64_t, nseg + 1);
+        RFX_ALLOC(table, uint32_t, (size_t)nb * v_bound);
+        RFX_ALLOC(scanned, uint64_t, (size_t)nb * v_bound + 1);
         RFX_HIP(seg_next->alloc((size_t)(nchild + 1) * 8, ctx->stream));
         RFX_HIP(hipMemsetAsync(table.p, 0, (size_t)nb * v_bound * 4, ctx->stream));
         const uint64_t *seg_end = seg_end_cur;
-        hipLaunchKernelGGL(k_vb_per_seg, dim3((unsigned)ceil_div(nseg, 256)), dim3(256), 0, ctx->stream,
-                           (const uint64_t *)seg_cur->as<uint64_t>(), seg_end, nseg, tpb, nvb.as<uint64_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_vb_per_seg, dim3((unsigned)ceil_div(nseg, 256)), dim3(256), 0,
+                   seg_cur->as<uint64_t>(), seg_end, nseg, tpb, nvb.as<uint64_t>());
         RFX_TRY(exclusive_scan_u64(ctx, nvb.as<uint64_t>(), vb_start.as<uint64_t>(), nseg));
         VbMap vm{seg_cur->as<uint64_t>(), vb_start.as<uint64_t>(), nseg, tpb, seg_end};
         const char *hn = l == 0 ? "hist1" : l == 1 ? "hist2" : "hist3";
         const char *pn = l == 0 ? "part1" : l == 1 ? "part2" : "part3";
         {
             ScopedTimer t(ctx, hn);
-            hipLaunchKernelGGL(k_rec_hist<MODE>, dim3((unsigned)v_bound), dim3(PT), 0, ctx->stream, cur, vm, lv, used,
-                               table.as<uint32_t>());
-            RFX_HIP(hipGetLastError());
+            RFX_LAUNCH(k_rec_hist<MODE>, dim3((unsigned)v_bound), dim3(PT), 0, cur, vm, lv, used,
+                       table.as<uint32_t>());
         }
         RFX_TRY(exclusive_scan_u32_to_u64(ctx, table.as<uint32_t>(), scanned.as<uint64_t>(), (int64_t)nb * v_bound));
-        hipLaunchKernelGGL(k_child_offsets, dim3((unsigned)ceil_div(nchild + 1, 256)), dim3(256), 0, ctx->stream,
-                           (const uint64_t *)scanned.as<uint64_t>(), vm, nb, (uint64_t)n_recs, seg_next->as<uint64_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_child_offsets, dim3((unsigned)ceil_div(nchild + 1, 256)), dim3(256), 0,
+                   scanned.as<uint64_t>(), vm, nb, (uint64_t)n_recs, seg_next->as<uint64_t>());
         slot = slot == 0 ? 1 : 0;
         Rec *dst = (Rec *)ctx->ws_get(slot, (size_t)std::max<int64_t>(n_recs, 1) * sizeof(Rec));
         if (!dst) { ctx->last_error = "workspace allocation failed"; return RFX_E_HIP; }
@@ -3869,29 +3845,28 @@ static int partition_record_levels(rfx_ctx *ctx, const typename LevelElem<MODE>:
                 if (lv.bits > 9) {                   // 1024 bins: 4 slots each (64-byte lines)
                     const size_t lds = (size_t)nb * (4 * sizeof(Rec) + 16);
                     RFX_HIP(hipFuncSetAttribute((const void *)k_rec_scatter_wc<4, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    hipLaunchKernelGGL((k_rec_scatter_wc<4, MODE>), dim3((unsigned)v_bound), dim3(WCT), lds, ctx->stream, cur, vm, lv,
-                                       used, (const uint64_t *)scanned.as<uint64_t>(), dst);
+                    RFX_LAUNCH((k_rec_scatter_wc<4, MODE>), dim3((unsigned)v_bound), dim3(WCT), lds, cur, vm, lv,
+                               used, scanned.as<uint64_t>(), dst);
                 } else {
                     const size_t lds = (size_t)nb * (8 * sizeof(Rec) + 16);
                     RFX_HIP(hipFuncSetAttribute((const void *)k_rec_scatter_wc<8, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    hipLaunchKernelGGL((k_rec_scatter_wc<8, MODE>), dim3((unsigned)v_bound), dim3(WCT), lds, ctx->stream, cur, vm, lv,
-                                       used, (const uint64_t *)scanned.as<uint64_t>(), dst);
+                    RFX_LAUNCH((k_rec_scatter_wc<8, MODE>), dim3((unsigned)v_bound), dim3(WCT), lds, cur, vm, lv,
+                               used, scanned.as<uint64_t>(), dst);
                 }
             } else if (wc && lv.bits <= 9) {
                 const size_t lds = (size_t)nb * (16 * sizeof(Rec) + 16);
                 RFX_HIP(hipFuncSetAttribute((const void *)k_rec_scatter_wc<16, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL((k_rec_scatter_wc<16, MODE>), dim3((unsigned)v_bound), dim3(WCT), lds, ctx->stream, cur, vm, lv,
-                                   used, (const uint64_t *)scanned.as<uint64_t>(), dst);
+                RFX_LAUNCH((k_rec_scatter_wc<16, MODE>), dim3((unsigned)v_bound), dim3(WCT), lds, cur, vm, lv,
+                           used, scanned.as<uint64_t>(), dst);
             } else if (wc) {
                 const size_t lds = (size_t)nb * (8 * sizeof(Rec) + 16);
                 RFX_HIP(hipFuncSetAttribute((const void *)k_rec_scatter_wc<8, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL((k_rec_scatter_wc<8, MODE>), dim3((unsigned)v_bound), dim3(WCT), lds, ctx->stream, cur, vm, lv,
-                                   used, (const uint64_t *)scanned.as<uint64_t>(), dst);
+                RFX_LAUNCH((k_rec_scatter_wc<8, MODE>), dim3((unsigned)v_bound), dim3(WCT), lds, cur, vm, lv,
+                           used, scanned.as<uint64_t>(), dst);
             } else {
-                hipLaunchKernelGGL(k_rec_scatter<MODE>, dim3((unsigned)v_bound), dim3(PT), 0, ctx->stream, cur, vm, lv, used,
-                                   (const uint64_t *)scanned.as<uint64_t>(), dst);
+                RFX_LAUNCH(k_rec_scatter<MODE>, dim3((unsigned)v_bound), dim3(PT), 0, cur, vm, lv, used,
+                           scanned.as<uint64_t>(), dst);
             }
-            RFX_HIP(hipGetLastError());
         }
         cur = dst;
         used += lv.bits;
@@ -3928,44 +3903,39 @@ static int last_level_sweep(rfx_ctx *ctx, const typename LevelElem<MODE>::T *cur
     RT *dst = (RT *)ctx->ws_get(oslot, (size_t)bound * sizeof(RT));
     if (!dst) { ctx->last_error = "workspace allocation failed"; return RFX_E_HIP; }
     DevBuf sampled, ccap, flags, spill_rec, spill_child;
-    RFX_HIP(spill_rec.alloc((size_t)spill_cap * sizeof(RT), ctx->stream));
-    RFX_HIP(spill_child.alloc((size_t)spill_cap * 4, ctx->stream));
-    RFX_HIP(sampled.alloc((size_t)nchild * 4, ctx->stream)); RFX_HIP(ccap.alloc((size_t)nchild * 4, ctx->stream));
-    RFX_HIP(cstart.alloc((size_t)(nchild + 1) * 8, ctx->stream));
+    RFX_ALLOC(spill_rec, RT, spill_cap);
+    RFX_ALLOC(spill_child, uint32_t, spill_cap);
+    RFX_ALLOC(sampled, uint32_t, nchild); RFX_ALLOC(ccap, uint32_t, nchild);
+    RFX_ALLOC(cstart, uint64_t, nchild + 1);
     RFX_HIP(flags.alloc(32, ctx->stream));                     // two flags, the spill cursor, the cursor of the room behind the regions
-    RFX_HIP(lend.alloc((size_t)nchild * 8, ctx->stream));
+    RFX_ALLOC(lend, uint64_t, nchild);
     RFX_HIP(hipMemsetAsync(sampled.p, 0, (size_t)nchild * 4, ctx->stream));
-    L2Plan pl{sb, seg_end ? seg_end : sb + 1, (const uint64_t *)cstart.as<uint64_t>(), flags.as<int>(), spill_rec.p, spill_child.as<uint32_t>(),
+    L2Plan pl{sb, seg_end ? seg_end : sb + 1, cstart.as<uint64_t>(), flags.as<int>(), spill_rec.p, spill_child.as<uint32_t>(),
               flags.as<unsigned long long>() + 1, spill_cap, flags.as<unsigned long long>() + 2, bound};
     Level lv{};
     lv.bits = bits_last;
     {
         ScopedTimer t(ctx, level_index == 0 ? "hist1" : level_index == 1 ? "hist2" : "hist3");
-        hipLaunchKernelGGL(k_l2_sample<MODE>, dim3((unsigned)nseg_h, 8), dim3(PT), 0, ctx->stream, cur_h, pl, lv, used_h, sampled.as<uint32_t>());
-        RFX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_l2_caps, dim3((unsigned)ceil_div(nchild, 256)), dim3(256), 0, ctx->stream, (const uint32_t *)sampled.as<uint32_t>(), nchild,
-                           ccap.as<uint32_t>(), getenv("RFX_L2_SQUEEZE") ? std::max(1, atoi(getenv("RFX_L2_SQUEEZE"))) : 100);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_l2_sample<MODE>, dim3((unsigned)nseg_h, 8), dim3(PT), 0, cur_h, pl, lv, used_h, sampled.as<uint32_t>());
+        RFX_LAUNCH(k_l2_caps, dim3((unsigned)ceil_div(nchild, 256)), dim3(256), 0, sampled.as<uint32_t>(), nchild,
+                   ccap.as<uint32_t>(), getenv("RFX_L2_SQUEEZE") ? std::max(1, atoi(getenv("RFX_L2_SQUEEZE"))) : 100);
     }
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, ccap.as<uint32_t>(), cstart.as<uint64_t>(), nchild));
     {
         ScopedTimer t(ctx, level_index == 0 ? "part1" : level_index == 1 ? "part2" : "part3");
-        hipLaunchKernelGGL(k_l2_check, dim3(1), dim3(1024), 0, ctx->stream, pl, (int)nseg_h, nchild, bound);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_l2_check, dim3(1), dim3(1024), 0, pl, (int)nseg_h, nchild, bound);
         // ring slots per child: what fills the LDS (16-byte elements: 16 at 512 children, 8 at 1024; the 32-byte records 8 and 4)
         constexpr int B9 = MODE == 3 ? 8 : 16, B10 = B9 / 2;
         if (bits_last <= 9) {
             const size_t lds = (size_t)nb * (B9 * sizeof(RT) + 24);
             RFX_HIP(hipFuncSetAttribute((const void *)k_rec_l2sweep<B9, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_rec_l2sweep<B9, MODE>), dim3((unsigned)nseg_h), dim3(WCT), lds, ctx->stream, cur_h, pl, lv, used_h, dst, lend.as<uint64_t>());
+            RFX_LAUNCH((k_rec_l2sweep<B9, MODE>), dim3((unsigned)nseg_h), dim3(WCT), lds, cur_h, pl, lv, used_h, dst, lend.as<uint64_t>());
         } else {
             const size_t lds = (size_t)nb * (B10 * sizeof(RT) + 24);
             RFX_HIP(hipFuncSetAttribute((const void *)k_rec_l2sweep<B10, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_rec_l2sweep<B10, MODE>), dim3((unsigned)nseg_h), dim3(WCT), lds, ctx->stream, cur_h, pl, lv, used_h, dst, lend.as<uint64_t>());
+            RFX_LAUNCH((k_rec_l2sweep<B10, MODE>), dim3((unsigned)nseg_h), dim3(WCT), lds, cur_h, pl, lv, used_h, dst, lend.as<uint64_t>());
         }
-        RFX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_l2_spill_fix<RT>, dim3(1), dim3(L2F_T), 0, ctx->stream, pl, cstart.as<uint64_t>(), lend.as<uint64_t>(), dst);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_l2_spill_fix<RT>, dim3(1), dim3(L2F_T), 0, pl, cstart.as<uint64_t>(), lend.as<uint64_t>(), dst);
     }
     unsigned long long h_fl[3] = {0, 0, 0};                    // {flags[0] | flags[1] << 32, spilled records, end of the room in use}
     uint64_t h_tot = 0;
@@ -4028,7 +3998,7 @@ static int partition_to_leaves(rfx_ctx *ctx, const typename LevelElem<MODE>::T *
     using RT = typename LevelElem<MODE>::T;
     *leaf_end = nullptr;
     if (bits.size() <= first_level) {                          // (no level left: the segments are the leaves)
-        *cur_out = recs; *elem_count = n_recs; *leaf_off = (const uint64_t *)seg_cur->as<uint64_t>(); *nleaf = nseg;
+        *cur_out = recs; *elem_count = n_recs; *leaf_off = seg_cur->as<uint64_t>(); *nleaf = nseg;
         *leaf_end = seg_end_first;
         return RFX_OK;
     }
@@ -4049,16 +4019,16 @@ static int partition_to_leaves(rfx_ctx *ctx, const typename LevelElem<MODE>::T *
     const RT *dst = nullptr;
     int64_t nchild = 0;
     uint64_t total = 0;
-    RFX_TRY(last_level_sweep<MODE>(ctx, cur_h, n_recs, slot, bits[last], used_h, (const uint64_t *)sc->as<uint64_t>(), seg_end, nseg_h, last, &dst, cstart,
+    RFX_TRY(last_level_sweep<MODE>(ctx, cur_h, n_recs, slot, bits[last], used_h, sc->as<uint64_t>(), seg_end, nseg_h, last, &dst, cstart,
                                    lend, &nchild, &total, &ok));
     if (ok) {
-        *cur_out = dst; *elem_count = (int64_t)total; *leaf_off = (const uint64_t *)cstart.as<uint64_t>();
-        *leaf_end = (const uint64_t *)lend.as<uint64_t>(); *nleaf = nchild;
+        *cur_out = dst; *elem_count = (int64_t)total; *leaf_off = cstart.as<uint64_t>();
+        *leaf_end = lend.as<uint64_t>(); *nleaf = nchild;
         return RFX_OK;
     }
     const RT *cur = nullptr;
     RFX_TRY(partition_record_levels<MODE>(ctx, cur_h, n_recs, slot, bits, last, used_h, &sc, &sn, &nseg_h, &cur, seg_end));
-    *cur_out = cur; *elem_count = n_recs; *leaf_off = (const uint64_t *)sc->as<uint64_t>(); *nleaf = nseg_h;
+    *cur_out = cur; *elem_count = n_recs; *leaf_off = sc->as<uint64_t>(); *nleaf = nseg_h;
     return RFX_OK;
 }
 
@@ -4097,7 +4067,7 @@ static int count_reads_superkmer(rfx_ctx *ctx, const ReadStore *reads, int min_c
     lv.bits = bits[0];
     StageArena stage_arena(ctx, ((size_t)64 << 20) + (size_t)n / 8);
     DevBuf segA, segB;
-    RFX_HIP(segA.alloc(((size_t)(1 << lv.bits) + 1) * 8, ctx->stream));
+    RFX_ALLOC(segA, uint64_t, (size_t)(1 << lv.bits) + 1);
     Rec *recs = nullptr;
     int64_t R = 0;
     // level 1 in one sweep when the input is large enough for a sampled histogram to size the regions (and another
@@ -4106,19 +4076,19 @@ static int count_reads_superkmer(rfx_ctx *ctx, const ReadStore *reads, int min_c
     bool swept = false;
     DevBuf segE;
     if (os_mode && bits.size() >= 2 && (os_mode == 2 || rsrc.n_threads >= ((int64_t)1 << 22))) {
-        RFX_HIP(segE.alloc((size_t)(1 << lv.bits) * 8, ctx->stream));
+        RFX_ALLOC(segE, uint64_t, 1 << lv.bits);
         RFX_TRY(records_onesweep(ctx, rsrc, lv, 0, segA.as<uint64_t>(), segE.as<uint64_t>(), &recs, &R, &swept, "hist1", "part1"));
     }
     if (!swept) RFX_TRY(records_from_reads(ctx, rsrc, lv, true, 0, nullptr, 0, segA.as<uint64_t>(), &recs, &R, "hist1", "part1"));
     return count_records_levels(ctx, recs, R, 0, bits, 1, lv.bits, &segA, &segB, (int64_t)1 << lv.bits, reads->k,
                                 min_cov, max_cov, twin, d_out_keys, d_out_counts, cap, out_n, out_distinct, pair_out,
-                                swept ? (const uint64_t *)segE.as<uint64_t>() : nullptr);
+                                swept ? segE.as<uint64_t>() : nullptr);
 }
 
 // the segment table of input that is not partitioned yet: one segment [0, n)
 static int one_segment(rfx_ctx *ctx, DevBuf &seg, int64_t n) {
     const uint64_t seg_init[2] = {0, (uint64_t)n};
-    RFX_HIP(seg.alloc(2 * 8, ctx->stream));
+    RFX_ALLOC(seg, uint64_t, 2);
     RFX_HIP(hipMemcpyAsync(seg.p, seg_init, 16, hipMemcpyHostToDevice, ctx->stream));
     return sync_checked(ctx);       // seg_init lives on the stack
 }
@@ -4188,22 +4158,19 @@ int count_filter(rfx_ctx *ctx, const ReadStore *reads, const uint64_t *d_kmers, 
             const int nb = 1 << lv.bits;
             const unsigned G = reads_grid(ctx, rsrc, nb <= 512 ? 2 : 1);
             DevBuf bh, scanned;
-            RFX_HIP(bh.alloc((size_t)nb * G * 8, ctx->stream));
-            RFX_HIP(scanned.alloc(((size_t)nb * G + 1) * 8, ctx->stream));
+            RFX_ALLOC(bh, uint64_t, (size_t)nb * G);
+            RFX_ALLOC(scanned, uint64_t, (size_t)nb * G + 1);
             {
                 ScopedTimer t(ctx, hn);
-                hipLaunchKernelGGL(k_reads_hist, dim3(G), dim3(PT), 0, ctx->stream, rsrc, lv, bh.as<uint64_t>());
-                RFX_HIP(hipGetLastError());
+                RFX_LAUNCH(k_reads_hist, dim3(G), dim3(PT), 0, rsrc, lv, bh.as<uint64_t>());
             }
             RFX_TRY(exclusive_scan_u64(ctx, bh.as<uint64_t>(), scanned.as<uint64_t>(), (int64_t)nb * G));
-            hipLaunchKernelGGL(k_bin_offsets, dim3((unsigned)ceil_div(nb + 1, 256)), dim3(256), 0, ctx->stream,
-                               (const uint64_t *)scanned.as<uint64_t>(), nb, (int64_t)G, seg_next->as<uint64_t>());
-            RFX_HIP(hipGetLastError());
+            RFX_LAUNCH(k_bin_offsets, dim3((unsigned)ceil_div(nb + 1, 256)), dim3(256), 0,
+                       scanned.as<uint64_t>(), nb, (int64_t)G, seg_next->as<uint64_t>());
             {
                 ScopedTimer t(ctx, pn);
-                hipLaunchKernelGGL(k_reads_scatter, dim3(G), dim3(PT), scatter_lds_bytes(nb), ctx->stream, rsrc,
-                                   lv, (const uint64_t *)scanned.as<uint64_t>(), out_buf->as<uint64_t>());
-                RFX_HIP(hipGetLastError());
+                RFX_LAUNCH(k_reads_scatter, dim3(G), dim3(PT), scatter_lds_bytes(nb), rsrc,
+                           lv, scanned.as<uint64_t>(), out_buf->as<uint64_t>());
             }
         } else {
             // virtual workgroups of tpb tiles inside every parent; table rows -> scan -> private cursors
@@ -4212,31 +4179,27 @@ int count_filter(rfx_ctx *ctx, const ReadStore *reads, const uint64_t *d_kmers, 
             const int tpb = (int)std::min<int64_t>(32, std::max<int64_t>(1, total_tiles / ((int64_t)ctx->num_cu * 8)));
             const int64_t v_bound = ceil_div(n, (int64_t)tpb * PTILE) + nseg;
             DevBuf nvb, vb_start, table, scanned;
-            RFX_HIP(nvb.alloc((size_t)nseg * 8, ctx->stream));
-            RFX_HIP(vb_start.alloc((size_t)(nseg + 1) * 8, ctx->stream));
-            RFX_HIP(table.alloc((size_t)nb * v_bound * 4, ctx->stream));
-            RFX_HIP(scanned.alloc(((size_t)nb * v_bound + 1) * 8, ctx->stream));
+            RFX_ALLOC(nvb, uint64_t, nseg);
+            RFX_ALLOC(vb_start, uint64_t, nseg + 1);
+            RFX_ALLOC(table, uint32_t, (size_t)nb * v_bound);
+            RFX_ALLOC(scanned, uint64_t, (size_t)nb * v_bound + 1);
             RFX_HIP(hipMemsetAsync(table.p, 0, (size_t)nb * v_bound * 4, ctx->stream));
-            hipLaunchKernelGGL(k_vb_per_seg, dim3((unsigned)ceil_div(nseg, 256)), dim3(256), 0, ctx->stream,
-                               (const uint64_t *)seg_cur->as<uint64_t>(), (const uint64_t *)nullptr, nseg, tpb, nvb.as<uint64_t>());
-            RFX_HIP(hipGetLastError());
+            RFX_LAUNCH(k_vb_per_seg, dim3((unsigned)ceil_div(nseg, 256)), dim3(256), 0,
+                       seg_cur->as<uint64_t>(), (const uint64_t *)nullptr, nseg, tpb, nvb.as<uint64_t>());
             RFX_TRY(exclusive_scan_u64(ctx, nvb.as<uint64_t>(), vb_start.as<uint64_t>(), nseg));
             VbMap vm{seg_cur->as<uint64_t>(), vb_start.as<uint64_t>(), nseg, tpb};
             {
                 ScopedTimer t(ctx, hn);
-                hipLaunchKernelGGL(k_vb_hist, dim3((unsigned)v_bound), dim3(PT), 0, ctx->stream, cur_arr, vm, lv,
-                                   table.as<uint32_t>());
-                RFX_HIP(hipGetLastError());
+                RFX_LAUNCH(k_vb_hist, dim3((unsigned)v_bound), dim3(PT), 0, cur_arr, vm, lv,
+                           table.as<uint32_t>());
             }
             RFX_TRY(exclusive_scan_u32_to_u64(ctx, table.as<uint32_t>(), scanned.as<uint64_t>(), (int64_t)nb * v_bound));
-            hipLaunchKernelGGL(k_child_offsets, dim3((unsigned)ceil_div(nchild + 1, 256)), dim3(256), 0, ctx->stream,
-                               (const uint64_t *)scanned.as<uint64_t>(), vm, nb, (uint64_t)n, seg_next->as<uint64_t>());
-            RFX_HIP(hipGetLastError());
+            RFX_LAUNCH(k_child_offsets, dim3((unsigned)ceil_div(nchild + 1, 256)), dim3(256), 0,
+                       scanned.as<uint64_t>(), vm, nb, (uint64_t)n, seg_next->as<uint64_t>());
             {
                 ScopedTimer t(ctx, pn);
-                hipLaunchKernelGGL(k_vb_scatter, dim3((unsigned)v_bound), dim3(PT), scatter_lds_bytes(nb), ctx->stream,
-                                   cur_arr, vm, lv, (const uint64_t *)scanned.as<uint64_t>(), out_buf->as<uint64_t>());
-                RFX_HIP(hipGetLastError());
+                RFX_LAUNCH(k_vb_scatter, dim3((unsigned)v_bound), dim3(PT), scatter_lds_bytes(nb),
+                           cur_arr, vm, lv, scanned.as<uint64_t>(), out_buf->as<uint64_t>());
             }
         }
         cur_arr = out_buf->as<uint64_t>();
@@ -4246,7 +4209,7 @@ int count_filter(rfx_ctx *ctx, const ReadStore *reads, const uint64_t *d_kmers, 
         nseg = nchild;
     }
 
-    return finish_leaves<0>(ctx, cur_arr, n, (const uint64_t *)seg_cur->as<uint64_t>(), nseg, from_reads ? reads->k : 31,
+    return finish_leaves<0>(ctx, cur_arr, n, seg_cur->as<uint64_t>(), nseg, from_reads ? reads->k : 31,
                             min_cov, max_cov, twin, from_reads ? k_bits : 64, d_out_keys, d_out_counts, cap, out_n,
                             out_distinct, pair_out);
 }
@@ -4263,18 +4226,15 @@ int bucket_by_owner(rfx_ctx *ctx, const ReadStore *reads, int n_owners, uint64_t
     lv.bits = 6; lv.shift = 0; lv.parent_shift = 64; lv.n_owners = n_owners;
     const unsigned G = reads_grid(ctx, rsrc, 2);
     DevBuf bh, scanned;
-    RFX_HIP(bh.alloc((size_t)n_owners * G * 8, ctx->stream));
-    RFX_HIP(scanned.alloc(((size_t)n_owners * G + 1) * 8, ctx->stream));
+    RFX_ALLOC(bh, uint64_t, (size_t)n_owners * G);
+    RFX_ALLOC(scanned, uint64_t, (size_t)n_owners * G + 1);
     if (n > 0) {
-        hipLaunchKernelGGL(k_reads_hist, dim3(G), dim3(PT), 0, ctx->stream, rsrc, lv, bh.as<uint64_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_reads_hist, dim3(G), dim3(PT), 0, rsrc, lv, bh.as<uint64_t>());
         RFX_TRY(exclusive_scan_u64(ctx, bh.as<uint64_t>(), scanned.as<uint64_t>(), (int64_t)n_owners * G));
-        hipLaunchKernelGGL(k_bin_offsets, dim3(1), dim3(256), 0, ctx->stream, (const uint64_t *)scanned.as<uint64_t>(),
-                           n_owners, (int64_t)G, reinterpret_cast<uint64_t *>(d_owner_off));
-        RFX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_reads_scatter, dim3(G), dim3(PT), scatter_lds_bytes(n_owners), ctx->stream, rsrc, lv,
-                           (const uint64_t *)scanned.as<uint64_t>(), d_out);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_bin_offsets, dim3(1), dim3(256), 0, scanned.as<uint64_t>(),
+                   n_owners, (int64_t)G, reinterpret_cast<uint64_t *>(d_owner_off));
+        RFX_LAUNCH(k_reads_scatter, dim3(G), dim3(PT), scatter_lds_bytes(n_owners), rsrc, lv,
+                   scanned.as<uint64_t>(), d_out);
     } else {
         RFX_HIP(hipMemsetAsync(d_owner_off, 0, (size_t)(n_owners + 1) * 8, ctx->stream));
     }
@@ -4372,10 +4332,10 @@ static int owner_sweep(rfx_ctx *ctx, const ReadSrc &rsrc, int n_owners, void *d_
     lv.bits = 9;
     const int nb = 1 << lv.bits, S = 1 << lv.sub_bits;
     DevBuf segB, segE, ob, oe, flt;
-    RFX_HIP(segB.alloc((size_t)(nb + 1) * 8, ctx->stream));
-    RFX_HIP(segE.alloc((size_t)nb * 8, ctx->stream));
-    RFX_HIP(ob.alloc((size_t)n_owners * 8, ctx->stream));
-    RFX_HIP(oe.alloc((size_t)n_owners * 8, ctx->stream));
+    RFX_ALLOC(segB, uint64_t, nb + 1);
+    RFX_ALLOC(segE, uint64_t, nb);
+    RFX_ALLOC(ob, uint64_t, n_owners);
+    RFX_ALLOC(oe, uint64_t, n_owners);
     RFX_HIP(flt.alloc(4, ctx->stream));
     RFX_HIP(hipMemsetAsync(flt.p, 0, 4, ctx->stream));
     RT *recs = nullptr;
@@ -4387,9 +4347,8 @@ static int owner_sweep(rfx_ctx *ctx, const ReadSrc &rsrc, int n_owners, void *d_
     if (st != RFX_OK || !swept) return st;
     {
         ScopedTimer t(ctx, "part1");
-        hipLaunchKernelGGL(k_close_gaps<RT>, dim3((unsigned)n_owners, 16), dim3(1024), 0, ctx->stream, recs, (const uint64_t *)segB.as<uint64_t>(),
-                           (const uint64_t *)segE.as<uint64_t>(), S, ob.as<uint64_t>(), oe.as<uint64_t>(), flt.as<int>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_close_gaps<RT>, dim3((unsigned)n_owners, 16), dim3(1024), 0, recs, segB.as<uint64_t>(),
+                   segE.as<uint64_t>(), S, ob.as<uint64_t>(), oe.as<uint64_t>(), flt.as<int>());
     }
     int h_fault = 0;
     static_assert(sizeof(int64_t) == sizeof(uint64_t), "offsets");
@@ -4449,24 +4408,21 @@ int bucket_pairs_by_owner(rfx_ctx *ctx, const void *d_pairs, int64_t n, int n_ow
     const int64_t v_bound = ceil_div(n, (int64_t)tpb * PTILE) + 1;
     RFX_HIP(nvb.alloc(8, ctx->stream));
     RFX_HIP(vb_start.alloc(16, ctx->stream));
-    RFX_HIP(table.alloc((size_t)nb * v_bound * 4, ctx->stream));
-    RFX_HIP(scanned.alloc(((size_t)nb * v_bound + 1) * 8, ctx->stream));
+    RFX_ALLOC(table, uint32_t, (size_t)nb * v_bound);
+    RFX_ALLOC(scanned, uint64_t, (size_t)nb * v_bound + 1);
     RFX_HIP(hipMemsetAsync(table.p, 0, (size_t)nb * v_bound * 4, ctx->stream));
-    hipLaunchKernelGGL(k_vb_per_seg, dim3(1), dim3(256), 0, ctx->stream, (const uint64_t *)seg.as<uint64_t>(), (const uint64_t *)nullptr, (int64_t)1, tpb,
-                       nvb.as<uint64_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH(k_vb_per_seg, dim3(1), dim3(256), 0, seg.as<uint64_t>(), (const uint64_t *)nullptr, (int64_t)1, tpb,
+               nvb.as<uint64_t>());
     RFX_TRY(exclusive_scan_u64(ctx, nvb.as<uint64_t>(), vb_start.as<uint64_t>(), 1));
     VbMap vm{seg.as<uint64_t>(), vb_start.as<uint64_t>(), 1, tpb};
     const Rec *src = (const Rec *)d_pairs;
     {
         ScopedTimer t(ctx, "pair_hist");
-        hipLaunchKernelGGL(k_rec_hist<2>, dim3((unsigned)v_bound), dim3(PT), 0, ctx->stream, src, vm, lv, 0, table.as<uint32_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_rec_hist<2>, dim3((unsigned)v_bound), dim3(PT), 0, src, vm, lv, 0, table.as<uint32_t>());
     }
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, table.as<uint32_t>(), scanned.as<uint64_t>(), (int64_t)nb * v_bound));
-    hipLaunchKernelGGL(k_child_offsets, dim3((unsigned)ceil_div(nb + 1, 256)), dim3(256), 0, ctx->stream,
-                       (const uint64_t *)scanned.as<uint64_t>(), vm, nb, (uint64_t)n, reinterpret_cast<uint64_t *>(d_owner_off));
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH(k_child_offsets, dim3((unsigned)ceil_div(nb + 1, 256)), dim3(256), 0,
+               scanned.as<uint64_t>(), vm, nb, (uint64_t)n, reinterpret_cast<uint64_t *>(d_owner_off));
     // holes (count 0) are not counted: the end of the last bucket is the histogram's total, not n
     RFX_HIP(hipMemcpyAsync(d_owner_off + n_owners, scanned.as<uint64_t>() + (size_t)nb * v_bound, 8, hipMemcpyDeviceToDevice,
                            ctx->stream));
@@ -4475,13 +4431,12 @@ int bucket_pairs_by_owner(rfx_ctx *ctx, const void *d_pairs, int64_t n, int n_ow
         if (nb >= 16) {
             const size_t lds = (size_t)nb * (16 * sizeof(Rec) + 16);
             RFX_HIP(hipFuncSetAttribute((const void *)k_rec_scatter_wc<16, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_rec_scatter_wc<16, 2>), dim3((unsigned)v_bound), dim3(WCT), lds, ctx->stream, src, vm, lv, 0,
-                               (const uint64_t *)scanned.as<uint64_t>(), (Rec *)d_out);
+            RFX_LAUNCH((k_rec_scatter_wc<16, 2>), dim3((unsigned)v_bound), dim3(WCT), lds, src, vm, lv, 0,
+                       scanned.as<uint64_t>(), (Rec *)d_out);
         } else {
-            hipLaunchKernelGGL(k_rec_scatter<2>, dim3((unsigned)v_bound), dim3(PT), 0, ctx->stream, src, vm, lv, 0,
-                               (const uint64_t *)scanned.as<uint64_t>(), (Rec *)d_out);
+            RFX_LAUNCH(k_rec_scatter<2>, dim3((unsigned)v_bound), dim3(PT), 0, src, vm, lv, 0,
+                       scanned.as<uint64_t>(), (Rec *)d_out);
         }
-        RFX_HIP(hipGetLastError());
     }
     if (h_owner_off) {
         RFX_HIP(hipMemcpyAsync(h_owner_off, d_owner_off, (size_t)(n_owners + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -4507,7 +4462,7 @@ int merge_pairs(rfx_ctx *ctx, const void *d_pairs, int64_t n, int k, int min_cov
     int64_t nseg = 1;
     const Rec *cur = nullptr;
     RFX_TRY(partition_record_levels<2>(ctx, (const Rec *)d_pairs, n, 1, bits, 0, 0, &seg_cur, &seg_next, &nseg, &cur));
-    return finish_leaves<2>(ctx, cur, n, (const uint64_t *)seg_cur->as<uint64_t>(), nseg, k, min_cov, max_cov, twin, 2 * k,
+    return finish_leaves<2>(ctx, cur, n, seg_cur->as<uint64_t>(), nseg, k, min_cov, max_cov, twin, 2 * k,
                             d_out_keys, d_out_counts, cap, out_n, out_distinct);
 }
 
@@ -4539,10 +4494,9 @@ static int finish_wide_records(rfx_ctx *ctx, const WRec *cur, const uint64_t *d_
     {
         ScopedTimer t(ctx, "leaf");
         const int64_t grid = std::min<int64_t>(nseg, (int64_t)ctx->num_cu);          // one workgroup per CU
-        hipLaunchKernelGGL(k_leaf_count_wrec, dim3((unsigned)grid), dim3(WLT), 0, ctx->stream, cur, d_leaf_off, d_leaf_end, nseg, k,
-                           min_cov, max_cov, d_out_keys, d_out_counts, (unsigned long long)cap, co_buf.as<CountOut>(),
-                           (uint32_t)(getenv("RFX_WIDE_PRESPLIT") ? atoi(getenv("RFX_WIDE_PRESPLIT")) : 2600));
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_leaf_count_wrec, dim3((unsigned)grid), dim3(WLT), 0, cur, d_leaf_off, d_leaf_end, nseg, k,
+                   min_cov, max_cov, d_out_keys, d_out_counts, (unsigned long long)cap, co_buf.as<CountOut>(),
+                   (uint32_t)(getenv("RFX_WIDE_PRESPLIT") ? atoi(getenv("RFX_WIDE_PRESPLIT")) : 2600));
     }
     return wide_leaves_done(ctx, co_buf, nseg, cap, out_n, out_distinct);
 }
@@ -4599,7 +4553,7 @@ static int count_wide2_reads_records(rfx_ctx *ctx, const uint64_t *d_words, int6
     Level lv{};
     lv.bits = bits[0];
     DevBuf segA, segB;
-    RFX_HIP(segA.alloc(((size_t)(1 << lv.bits) + 1) * 8, ctx->stream));
+    RFX_ALLOC(segA, uint64_t, (size_t)(1 << lv.bits) + 1);
     WRec *recs = nullptr;
     int64_t R = 0;
     // level 1 in one sweep, as on the k <= 31 path (count_reads_superkmer)
@@ -4607,7 +4561,7 @@ static int count_wide2_reads_records(rfx_ctx *ctx, const uint64_t *d_words, int6
     bool swept = false;
     DevBuf segE;
     if (os_mode && bits.size() >= 2 && (os_mode == 2 || rsrc.n_threads >= ((int64_t)1 << 22))) {
-        RFX_HIP(segE.alloc((size_t)(1 << lv.bits) * 8, ctx->stream));
+        RFX_ALLOC(segE, uint64_t, 1 << lv.bits);
         RFX_TRY(records_onesweep<true>(ctx, rsrc, lv, 0, segA.as<uint64_t>(), segE.as<uint64_t>(), &recs, &R, &swept, "hist1", "part1"));
     }
     if (!swept) RFX_TRY(records_from_reads<true>(ctx, rsrc, lv, true, 0, nullptr, 0, segA.as<uint64_t>(), &recs, &R, "hist1", "part1"));
@@ -4616,7 +4570,7 @@ static int count_wide2_reads_records(rfx_ctx *ctx, const uint64_t *d_words, int6
     int64_t ec = 0, nleaf = 0;
     DevBuf cstart, le;
     RFX_TRY(partition_to_leaves<3>(ctx, recs, R, 0, bits, 1, lv.bits, &segA, &segB, (int64_t)1 << lv.bits,
-                                   swept ? (const uint64_t *)segE.as<uint64_t>() : nullptr, &cur, &ec, &loff, &lend, &nleaf, cstart, le));
+                                   swept ? segE.as<uint64_t>() : nullptr, &cur, &ec, &loff, &lend, &nleaf, cstart, le));
     return finish_wide_records(ctx, cur, loff, lend, nleaf, k, min_cov, max_cov, d_out_keys, d_out_counts, cap, out_n, out_distinct);
 }
 
@@ -4699,10 +4653,9 @@ static int finish_wide(rfx_ctx *ctx, const KmerW<W> *cur, const uint64_t *d_leaf
         ScopedTimer t(ctx, "leaf");
         const int64_t grid = std::min<int64_t>(nseg, (int64_t)ctx->num_cu);          // one workgroup per CU
         // (elements one table takes before a leaf starts in parts: none by default -- the levels aim at WIDE_N_TARGET)
-        hipLaunchKernelGGL(k_leaf_count_wn<W>, dim3((unsigned)grid), dim3(WLT), 0, ctx->stream, cur, d_leaf_off, d_leaf_off + 1, nseg,
-                           min_cov, max_cov, d_out_keys, d_out_counts, (unsigned long long)cap, co_buf.as<CountOut>(),
-                           (uint32_t)(getenv("RFX_WIDE_PRESPLIT") ? atoi(getenv("RFX_WIDE_PRESPLIT")) : 0));
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_leaf_count_wn<W>, dim3((unsigned)grid), dim3(WLT), 0, cur, d_leaf_off, d_leaf_off + 1, nseg,
+                   min_cov, max_cov, d_out_keys, d_out_counts, (unsigned long long)cap, co_buf.as<CountOut>(),
+                   (uint32_t)(getenv("RFX_WIDE_PRESPLIT") ? atoi(getenv("RFX_WIDE_PRESPLIT")) : 0));
     }
     return wide_leaves_done(ctx, co_buf, nseg, cap, out_n, out_distinct);
 }
@@ -4715,24 +4668,21 @@ static int wide_level1_n(rfx_ctx *ctx, const WideSrcN &ws, const Level &lv, Kmer
     const int nb = lv.n_owners > 0 ? lv.n_owners : (1 << lv.bits);
     const unsigned G = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(ws.total, WL1_T), (int64_t)ctx->num_cu));
     DevBuf bh, scanned;
-    RFX_HIP(bh.alloc((size_t)nb * G * 8, ctx->stream));
-    RFX_HIP(scanned.alloc(((size_t)nb * G + 1) * 8, ctx->stream));
+    RFX_ALLOC(bh, uint64_t, (size_t)nb * G);
+    RFX_ALLOC(scanned, uint64_t, (size_t)nb * G + 1);
     {
         ScopedTimer t(ctx, "hist1");
-        hipLaunchKernelGGL(k_wn_hist<W>, dim3(G), dim3(WL1_T), 0, ctx->stream, ws, lv, bh.as<uint64_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_wn_hist<W>, dim3(G), dim3(WL1_T), 0, ws, lv, bh.as<uint64_t>());
     }
     RFX_TRY(exclusive_scan_u64(ctx, bh.as<uint64_t>(), scanned.as<uint64_t>(), (int64_t)nb * G));
-    hipLaunchKernelGGL(k_bin_offsets, dim3((unsigned)ceil_div(nb + 1, 256)), dim3(256), 0, ctx->stream,
-                       (const uint64_t *)scanned.as<uint64_t>(), nb, (int64_t)G, d_seg_off);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH(k_bin_offsets, dim3((unsigned)ceil_div(nb + 1, 256)), dim3(256), 0,
+               scanned.as<uint64_t>(), nb, (int64_t)G, d_seg_off);
     {
         ScopedTimer t(ctx, "part1");
         const size_t lds = (size_t)nb * (WL1_B<W> * sizeof(KmerW<W>) + 16);
         RFX_HIP(hipFuncSetAttribute((const void *)k_wn_scatter<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_wn_scatter<W>, dim3(G), dim3(WL1_T), lds, ctx->stream, ws, lv, (const uint64_t *)scanned.as<uint64_t>(),
-                           d_dst);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_wn_scatter<W>, dim3(G), dim3(WL1_T), lds, ws, lv, scanned.as<uint64_t>(),
+                   d_dst);
     }
     return RFX_OK;
 }
@@ -4757,7 +4707,7 @@ static int count_wide_n(rfx_ctx *ctx, const void *d_elems, int64_t n, int min_co
     int64_t nseg = 1;
     const KmerW<W> *cur = nullptr;
     RFX_TRY(partition_record_levels<WIDE_MODE<W>>(ctx, (const KmerW<W> *)d_elems, n, 1, bits, 0, 0, &seg_cur, &seg_next, &nseg, &cur));
-    return finish_wide<W>(ctx, cur, (const uint64_t *)seg_cur->as<uint64_t>(), nseg, min_cov, max_cov, d_out_keys, d_out_counts,
+    return finish_wide<W>(ctx, cur, seg_cur->as<uint64_t>(), nseg, min_cov, max_cov, d_out_keys, d_out_counts,
                           cap, out_n, out_distinct);
 }
 
@@ -4789,7 +4739,7 @@ static int count_wide_n_reads(rfx_ctx *ctx, const WideSrcN &ws, int64_t n, int m
     lv.bits = bits[0];
     const int nb = 1 << lv.bits;
     DevBuf segA, segB;
-    RFX_HIP(segA.alloc(((size_t)nb + 1) * 8, ctx->stream));
+    RFX_ALLOC(segA, uint64_t, (size_t)nb + 1);
     KmerW<W> *dst = (KmerW<W> *)ctx->ws_get(0, (size_t)n * sizeof(KmerW<W>));
     if (!dst) { ctx->last_error = "workspace allocation failed"; return RFX_E_HIP; }
     RFX_TRY(wide_level1_n<W>(ctx, ws, lv, dst, segA.as<uint64_t>()));
@@ -4804,7 +4754,7 @@ static int count_wide_n_reads(rfx_ctx *ctx, const WideSrcN &ws, int64_t n, int m
     int64_t nseg = nb;
     const KmerW<W> *cur = nullptr;
     RFX_TRY(partition_record_levels<WIDE_MODE<W>>(ctx, dst, n, 0, bits, 1, lv.bits, &seg_cur, &seg_next, &nseg, &cur));
-    return finish_wide<W>(ctx, cur, (const uint64_t *)seg_cur->as<uint64_t>(), nseg, min_cov, max_cov, d_out_keys, d_out_counts,
+    return finish_wide<W>(ctx, cur, seg_cur->as<uint64_t>(), nseg, min_cov, max_cov, d_out_keys, d_out_counts,
                           cap, out_n, out_distinct);
 }
 
@@ -4887,9 +4837,8 @@ int count_wide2_reads(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, in
 int synth_genome(rfx_ctx *ctx, uint64_t seed, int64_t genome_len, uint64_t *d_genome) {
     int64_t nw = (genome_len + 31) / 32;
     if (nw <= 0) return RFX_E_ARG;
-    hipLaunchKernelGGL(k_synth_genome, dim3((unsigned)ceil_div(nw, 256)), dim3(256), 0, ctx->stream,
-                       splitmix64(seed ^ TAG_GENOME), nw, d_genome);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH(k_synth_genome, dim3((unsigned)ceil_div(nw, 256)), dim3(256), 0,
+               splitmix64(seed ^ TAG_GENOME), nw, d_genome);
     return RFX_OK;
 }
 
@@ -4899,10 +4848,9 @@ int synth_reads(rfx_ctx *ctx, uint64_t seed, const uint64_t *d_genome, int64_t g
     if (read_len > genome_len || words_per_read * 32 < read_len) return RFX_E_ARG;
     int64_t total = n_reads * words_per_read;
     if (total <= 0) return RFX_OK;
-    hipLaunchKernelGGL(k_synth_reads, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, ctx->stream,
-                       splitmix64(seed ^ TAG_PAIRS), splitmix64(seed ^ TAG_ERRORS), d_genome, genome_len,
-                       first_read, n_reads, read_len, err, words_per_read, d_words);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH(k_synth_reads, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0,
+               splitmix64(seed ^ TAG_PAIRS), splitmix64(seed ^ TAG_ERRORS), d_genome, genome_len,
+               first_read, n_reads, read_len, err, words_per_read, d_words);
     return RFX_OK;
 }
 

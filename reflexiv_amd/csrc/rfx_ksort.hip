@@ -291,11 +291,10 @@ static int ks_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_of
     if (n == 0) return dyn_empty(ctx, d);
     if (n >= ((int64_t)1 << 31)) { ctx->last_error = "k-mer sorting: 2^31 rows or more"; return RFX_E_LIMIT; }
     DevBuf keep, slot, kbeg, cnt, flags;
-    RFX_HIP(keep.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(slot.alloc((size_t)(n + 1) * 8, ctx->stream));
-    RFX_HIP(kbeg.alloc((size_t)n * 8, ctx->stream)); RFX_HIP(cnt.alloc((size_t)n * 4, ctx->stream));
+    RFX_ALLOC(keep, uint32_t, n); RFX_ALLOC(slot, uint64_t, n + 1);
+    RFX_ALLOC(kbeg, int64_t, n); RFX_ALLOC(cnt, int32_t, n);
     RFX_TRY(call_flags_init(ctx, flags));
-    hipLaunchKernelGGL(k_ks_bin_sizes, RFX_GRID(n), d_text, d_row_off, n, prm, keep.as<uint32_t>(), kbeg.as<int64_t>(), cnt.as<int32_t>(), flags.as<CallFlags>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_ks_bin_sizes, n, d_text, d_row_off, n, prm, keep.as<uint32_t>(), kbeg.as<int64_t>(), cnt.as<int32_t>(), flags.as<CallFlags>());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, keep.as<uint32_t>(), slot.as<uint64_t>(), n));
     CallFlags f{};
     RFX_TRY(call_flags_read(ctx, flags, slot.as<uint64_t>() + n, nullptr, nullptr, &f));
@@ -303,9 +302,8 @@ static int ks_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_of
     const int64_t n_out = 2 * (int64_t)f.total[0];
     if (n_out == 0) return dyn_empty(ctx, d);
     RFX_TRY(dyn_alloc(ctx, d, n_out, n_out));
-    hipLaunchKernelGGL(k_ks_bin_emit, RFX_GRID(n), d_text, n, prm, (const uint32_t *)keep.as<uint32_t>(), (const uint64_t *)slot.as<uint64_t>(),
-                       (const int64_t *)kbeg.as<int64_t>(), (const int32_t *)cnt.as<int32_t>(), n_out, dyn_out(d));
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_ks_bin_emit, n, d_text, n, prm, keep.as<uint32_t>(), slot.as<uint64_t>(),
+                 kbeg.as<int64_t>(), cnt.as<int32_t>(), n_out, dyn_out(d));
     return RFX_OK;
 }
 
@@ -322,20 +320,18 @@ static int ks_fold(rfx_ctx *ctx, bool reflected, const DynDev &in, const KsParam
     const int64_t n = in.n;
     if (n == 0) return dyn_empty(ctx, out);
     DevBuf head, rank, flags;
-    RFX_HIP(head.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(rank.alloc((size_t)(n + 1) * 8, ctx->stream));
+    RFX_ALLOC(head, uint32_t, n); RFX_ALLOC(rank, uint64_t, n + 1);
     RFX_TRY(call_flags_init(ctx, flags));
     const DynView v = dyn_view(in);
-    hipLaunchKernelGGL(k_ks_heads, RFX_GRID(n), v, n, head.as<uint32_t>(), flags.as<CallFlags>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_ks_heads, n, v, n, head.as<uint32_t>(), flags.as<CallFlags>());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, head.as<uint32_t>(), rank.as<uint64_t>(), n));
     CallFlags f{};
     RFX_TRY(call_flags_read(ctx, flags, rank.as<uint64_t>() + n, nullptr, nullptr, &f));
     RFX_TRY(ks_check(ctx, f, true, 124));
     const int64_t ns = (int64_t)f.total[0];
     RFX_TRY(dyn_alloc(ctx, out, ns, ns));
-    if (reflected) hipLaunchKernelGGL(k_ks_fold<true>, RFX_GRID(n), v, n, (const uint32_t *)head.as<uint32_t>(), (const uint64_t *)rank.as<uint64_t>(), prm, dyn_out(out));
-    else hipLaunchKernelGGL(k_ks_fold<false>, RFX_GRID(n), v, n, (const uint32_t *)head.as<uint32_t>(), (const uint64_t *)rank.as<uint64_t>(), prm, dyn_out(out));
-    RFX_HIP(hipGetLastError());
+    if (reflected) RFX_LAUNCH_N(k_ks_fold<true>, n, v, n, head.as<uint32_t>(), rank.as<uint64_t>(), prm, dyn_out(out));
+    else RFX_LAUNCH_N(k_ks_fold<false>, n, v, n, head.as<uint32_t>(), rank.as<uint64_t>(), prm, dyn_out(out));
     return RFX_OK;
 }
 
@@ -346,15 +342,13 @@ static int ks_map(rfx_ctx *ctx, bool full, const DynDev &in, DynDev &out) {
     DevBuf flags;
     RFX_TRY(call_flags_init(ctx, flags));
     const DynView v = dyn_view(in);
-    hipLaunchKernelGGL(k_ks_lengths, RFX_GRID(n), v, n, flags.as<CallFlags>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_ks_lengths, n, v, n, flags.as<CallFlags>());
     CallFlags f{};
     RFX_TRY(call_flags_read(ctx, flags, nullptr, nullptr, nullptr, &f));
     RFX_TRY(ks_check(ctx, f, !full, full ? 123 : 124));
     RFX_TRY(dyn_alloc(ctx, out, n, full ? 0 : n));
-    if (full) hipLaunchKernelGGL(k_ks_full, RFX_GRID(n), v, n, dyn_out(out));
-    else hipLaunchKernelGGL(k_ks_reflect, RFX_GRID(n), v, n, dyn_out(out));
-    RFX_HIP(hipGetLastError());
+    if (full) RFX_LAUNCH_N(k_ks_full, n, v, n, dyn_out(out));
+    else RFX_LAUNCH_N(k_ks_reflect, n, v, n, dyn_out(out));
     return RFX_OK;
 }
 
@@ -385,11 +379,10 @@ static int ks_to_text(rfx_ctx *ctx, const DynDev &d, int k, char *d_text, int64_
         return sync_checked(ctx);
     }
     DevBuf sz, toff, keep, rank;
-    RFX_HIP(sz.alloc((size_t)n * 8, ctx->stream)); RFX_HIP(toff.alloc((size_t)(n + 1) * 8, ctx->stream));
-    RFX_HIP(keep.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(rank.alloc((size_t)(n + 1) * 8, ctx->stream));
+    RFX_ALLOC(sz, uint64_t, n); RFX_ALLOC(toff, uint64_t, n + 1);
+    RFX_ALLOC(keep, uint32_t, n); RFX_ALLOC(rank, uint64_t, n + 1);
     const DynView v = dyn_view(d);
-    hipLaunchKernelGGL(k_ks_text_sizes, RFX_GRID(n), v, n, k, sz.as<uint64_t>(), keep.as<uint32_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_ks_text_sizes, n, v, n, k, sz.as<uint64_t>(), keep.as<uint32_t>());
     RFX_TRY(exclusive_scan_u64(ctx, sz.as<uint64_t>(), toff.as<uint64_t>(), n));
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, keep.as<uint32_t>(), rank.as<uint64_t>(), n));
     uint64_t t = 0, nr = 0;
@@ -401,14 +394,12 @@ static int ks_to_text(rfx_ctx *ctx, const DynDev &d, int k, char *d_text, int64_
         d_text = own->as<char>(); cap = *total;
     }
     if (d_row_off) {
-        hipLaunchKernelGGL(k_ks_text_offsets, RFX_GRID(n), (const uint32_t *)keep.as<uint32_t>(), (const uint64_t *)rank.as<uint64_t>(),
-                           (const uint64_t *)toff.as<uint64_t>(), n, d_row_off);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_ks_text_offsets, n, keep.as<uint32_t>(), rank.as<uint64_t>(),
+                     toff.as<uint64_t>(), n, d_row_off);
     }
     const int64_t lim = std::min<int64_t>(*total, cap);
     if (lim > 0) {
-        hipLaunchKernelGGL(k_ks_text_fill, RFX_GRID(ceil_div(lim, 8)), v, n, (const uint64_t *)toff.as<uint64_t>(), lim, d_text);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_ks_text_fill, ceil_div(lim, 8), v, n, toff.as<uint64_t>(), lim, d_text);
     }
     return sync_checked(ctx);
 }
@@ -430,7 +421,7 @@ void rfx_ksort_default_params(rfx_ksort_params *p, int k) try {
 
 int rfx_dev_ksort_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, const rfx_ksort_params *params,
                            rfx_dyn_packed *d_out) try {
-    if (!ctx || !dyn_packed_out_ok(d_out) || n_rows < 0 || (n_rows > 0 && (!d_text || !d_row_off))) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_out_ok(d_out) || !text_rows_ok(d_text, d_row_off, n_rows)) return RFX_E_ARG;
     KsParams prm;
     RFX_TRY(ks_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -483,7 +474,7 @@ int rfx_dev_ksort_to_text(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int k, char 
 
 int rfx_dev_ksort_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, const rfx_ksort_params *params,
                       rfx_dyn_packed *d_out) try {
-    if (!ctx || !dyn_packed_out_ok(d_out) || n_rows < 0 || (n_rows > 0 && (!d_text || !d_row_off))) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_out_ok(d_out) || !text_rows_ok(d_text, d_row_off, n_rows)) return RFX_E_ARG;
     KsParams prm;
     RFX_TRY(ks_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -495,7 +486,7 @@ int rfx_dev_ksort_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off
 // host text in, host text out; everything between packed and in HBM: upload, run, to-text, one copy back
 int rfx_ksort_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, const rfx_ksort_params *params, char *out, int64_t cap,
                    int64_t *out_len) try {
-    if (!ctx || n_rows < 0 || (n_rows > 0 && (!text || !row_off)) || !out_len || cap < 0 || (cap > 0 && !out)) return RFX_E_ARG;
+    if (!ctx || !text_rows_ok(text, row_off, n_rows) || !out_len || cap < 0 || (cap > 0 && !out)) return RFX_E_ARG;
     KsParams prm;
     RFX_TRY(ks_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -503,13 +494,9 @@ int rfx_ksort_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64
     DynDev a;
     int64_t total = 0, rows = 0;
     RFX_TRY(dyn_upload_text(ctx, text, row_off, n_rows, d_text, d_off));
-    RFX_TRY(ks_run(ctx, (const char *)d_text.p, (const int64_t *)d_off.as<int64_t>(), n_rows, prm, params->bubble, a));
+    RFX_TRY(ks_run(ctx, (const char *)d_text.p, d_off.as<int64_t>(), n_rows, prm, params->bubble, a));
     RFX_TRY(ks_to_text(ctx, a, prm.k, nullptr, 0, &total, nullptr, &rows, &d_out));
-    *out_len = total;
-    const int64_t lim = std::min<int64_t>(total, cap);
-    if (lim > 0) RFX_HIP(hipMemcpyAsync(out, d_out.p, (size_t)lim, hipMemcpyDeviceToHost, ctx->stream));
-    RFX_TRY(sync_checked(ctx));
-    return total > cap ? RFX_E_CAP : RFX_OK;
+    return text_to_host(ctx, {{d_out, total, out, cap, out_len}}, true);
 } RFX_API_CATCH(ctx)
 
 }  // extern "C"

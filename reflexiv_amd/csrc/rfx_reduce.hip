@@ -293,20 +293,11 @@ __global__ __launch_bounds__(256) void k_rd_emit(const DynView v, int64_t n, con
     if (st.f.emit) q = rd_put_step<RIGHT>(v, o, q, i - 1, st.f);      // (a flush of two: i >= 1; its emit has no third bit)
     if (st.one) rd_put<RIGHT>(v, o, q, i, -1);
 }
-// where the partitions begin in the output: P + 1 entries
-__global__ void k_rd_out_ps(const int64_t *__restrict__ ps, int P, const uint64_t *__restrict__ off, int64_t *__restrict__ out_ps) {
-    const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (p <= P) out_ps[p] = (int64_t)off[ps[p]];
-}
 
 // ---- step 11: ShorterKmerNeutralization -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_rd_nt_long(const DynView v, int64_t n, int k2, uint32_t *__restrict__ isl) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) isl[i] = (int)v.key_len[i] == k2 ? 1u : 0u;
-}
-__global__ __launch_bounds__(256) void k_rd_nt_scatter(const uint32_t *__restrict__ isl, const uint64_t *__restrict__ lrank, int64_t n, int64_t *__restrict__ lidx) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && isl[i]) lidx[lrank[i]] = i;
 }
 // a short row: near[i] = the nearest long row before it in its partition (-1: none), brk[i] = 1 when there is none or the row is
 // no prefix of it -- the row breaks the stretch of dropped rows behind that long row
@@ -372,8 +363,7 @@ static int rd_bad(rfx_ctx *ctx, uint32_t bad) {
 static int rd_check(rfx_ctx *ctx, const DynDev &in, int la, int lb, int ext_len) {
     DevBuf flags;
     RFX_TRY(call_flags_init(ctx, flags));
-    hipLaunchKernelGGL(k_rd_check, RFX_GRID(in.n), dyn_view(in), in.n, la, lb, ext_len, flags.as<CallFlags>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_rd_check, in.n, dyn_view(in), in.n, la, lb, ext_len, flags.as<CallFlags>());
     CallFlags f{};
     RFX_TRY(call_flags_read(ctx, flags, nullptr, nullptr, nullptr, &f));
     return f.bad ? rd_bad(ctx, f.bad) : RFX_OK;
@@ -385,15 +375,13 @@ static int rd_bin_sizes(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_o
     if (n == 0) return RFX_OK;
     if (n >= ((int64_t)1 << 31)) { ctx->last_error = "k-mer reduction: 2^31 rows or more"; return RFX_E_LIMIT; }
     DevBuf flags;
-    RFX_HIP(b.len.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(b.keep.alloc((size_t)n * 4, ctx->stream));
-    RFX_HIP(b.slot.alloc((size_t)(n + 1) * 8, ctx->stream)); RFX_HIP(b.kbeg.alloc((size_t)n * 8, ctx->stream));
-    RFX_HIP(b.mlr.alloc((size_t)n * 12, ctx->stream));
+    RFX_ALLOC(b.len, uint32_t, n); RFX_ALLOC(b.keep, uint32_t, n);
+    RFX_ALLOC(b.slot, uint64_t, n + 1); RFX_ALLOC(b.kbeg, int64_t, n);
+    RFX_ALLOC(b.mlr, int32_t, 3 * n);
     RFX_TRY(call_flags_init(ctx, flags));
-    hipLaunchKernelGGL(k_rd_bin_sizes, RFX_GRID(n), d_text, d_row_off, n, prm, b.len.as<uint32_t>(), b.kbeg.as<int64_t>(), b.mlr.as<int32_t>(),
-                       flags.as<CallFlags>());
-    RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_rd_bin_flag, RFX_GRID(n), (const uint32_t *)b.len.as<uint32_t>(), n, b.keep.as<uint32_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_rd_bin_sizes, n, d_text, d_row_off, n, prm, b.len.as<uint32_t>(), b.kbeg.as<int64_t>(), b.mlr.as<int32_t>(),
+                 flags.as<CallFlags>());
+    RFX_LAUNCH_N(k_rd_bin_flag, n, b.len.as<uint32_t>(), n, b.keep.as<uint32_t>());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, b.keep.as<uint32_t>(), b.slot.as<uint64_t>(), n));
     CallFlags f{};
     RFX_TRY(call_flags_read(ctx, flags, b.slot.as<uint64_t>() + n, nullptr, nullptr, &f));
@@ -403,9 +391,8 @@ static int rd_bin_sizes(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_o
 }
 static int rd_bin_emit(rfx_ctx *ctx, const char *d_text, int64_t n, const RdBin &b, int64_t base, DynDev &d) {
     if (n == 0 || b.kept == 0) return RFX_OK;
-    hipLaunchKernelGGL(k_rd_bin_emit, RFX_GRID(n), d_text, n, (const uint32_t *)b.len.as<uint32_t>(), (const uint64_t *)b.slot.as<uint64_t>(),
-                       (const int64_t *)b.kbeg.as<int64_t>(), (const int32_t *)b.mlr.as<int32_t>(), base, dyn_out(d));
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_rd_bin_emit, n, d_text, n, b.len.as<uint32_t>(), b.slot.as<uint64_t>(),
+                 b.kbeg.as<int64_t>(), b.mlr.as<int32_t>(), base, dyn_out(d));
     return RFX_OK;
 }
 // steps 1-2: both texts -> one set of full k-mer records, the longer input's first
@@ -427,49 +414,36 @@ static int rd_prepare(rfx_ctx *ctx, bool right, const DynDev &in, const RdParams
     if (n == 0) return dyn_empty(ctx, out);
     RFX_TRY(right ? rd_check(ctx, in, prm.k1 - 1, prm.k2 - 1, 1) : rd_check(ctx, in, prm.k1, prm.k2, 0));
     RFX_TRY(dyn_alloc(ctx, out, n, n));
-    if (right) hipLaunchKernelGGL(k_rd_right_prep, RFX_GRID(n), dyn_view(in), n, dyn_out(out));
-    else hipLaunchKernelGGL(k_rd_left_prep, RFX_GRID(n), dyn_view(in), n, dyn_out(out));
-    RFX_HIP(hipGetLastError());
+    if (right) RFX_LAUNCH_N(k_rd_right_prep, n, dyn_view(in), n, dyn_out(out));
+    else RFX_LAUNCH_N(k_rd_left_prep, n, dyn_view(in), n, dyn_out(out));
     return RFX_OK;
 }
 // steps 5 and 8 over a sorted set cut into P partitions
 template <bool RIGHT>
 static int rd_adjust_t(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, const RdParams &prm, DynDev &out, DevBuf &out_ps) {
     const int64_t n = in.n;
-    RFX_HIP(out_ps.alloc((size_t)(P + 1) * 8, ctx->stream));
-    if (n == 0) {
-        RFX_HIP(hipMemsetAsync(out_ps.p, 0, (size_t)(P + 1) * 8, ctx->stream));
-        return dyn_empty(ctx, out);
-    }
+    RFX_TRY(part_starts_alloc(ctx, out_ps, P, n == 0));
+    if (n == 0) return dyn_empty(ctx, out);
     RFX_TRY(check_part_starts(ctx, d_ps, P, n, "k-mer reduction"));
     RFX_TRY(rd_check(ctx, in, prm.k1 - 1, prm.k2 - 1, 1));
     const int64_t nb = ceil_div(n, 256);
     DevBuf info, maps, agg, cnt, off;
-    RFX_HIP(info.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(maps.alloc((size_t)n, ctx->stream)); RFX_HIP(agg.alloc((size_t)nb, ctx->stream));
-    RFX_HIP(cnt.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(off.alloc((size_t)(n + 1) * 8, ctx->stream));
+    RFX_ALLOC(info, uint32_t, n); RFX_HIP(maps.alloc((size_t)n, ctx->stream)); RFX_HIP(agg.alloc((size_t)nb, ctx->stream));
+    RFX_ALLOC(cnt, uint32_t, n); RFX_ALLOC(off, uint64_t, n + 1);
     RFX_HIP(hipMemsetAsync(info.p, 0, (size_t)n * 4, ctx->stream));
     const DynView v = dyn_view(in);
-    hipLaunchKernelGGL(k_rd_marks, dim3(1), dim3(64), 0, ctx->stream, d_ps, P, info.as<uint32_t>());
-    RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_rd_window<RIGHT>, RFX_GRID(n), v, n, prm.k1 - 1, info.as<uint32_t>(), maps.as<uint8_t>());
-    RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_rd_scan_reduce, RFX_GRID(n), (const uint8_t *)maps.as<uint8_t>(), n, agg.as<uint8_t>());
-    RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_rd_scan_aggs, dim3(1), dim3(256), 0, ctx->stream, agg.as<uint8_t>(), nb);
-    RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_rd_scan_apply<RIGHT>, RFX_GRID(n), (const uint8_t *)maps.as<uint8_t>(), (const uint8_t *)agg.as<uint8_t>(), n, info.as<uint32_t>(),
-                       cnt.as<uint32_t>());
-    RFX_HIP(hipGetLastError());
-    RFX_TRY(exclusive_scan_u32_to_u64(ctx, cnt.as<uint32_t>(), off.as<uint64_t>(), n));
-    uint64_t total = 0;
-    RFX_TRY(small_readback(ctx, &total, off.as<uint64_t>() + n, 8));
-    if ((int64_t)total > n) { ctx->last_error = "k-mer reduction: an adjustment would write more rows than it read"; return RFX_E_STATE; }
-    RFX_TRY(dyn_alloc(ctx, out, (int64_t)total, (int64_t)total));
-    hipLaunchKernelGGL(k_rd_emit<RIGHT>, RFX_GRID(n), v, n, (const uint32_t *)info.as<uint32_t>(), (const uint64_t *)off.as<uint64_t>(), dyn_out(out));
-    RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_rd_out_ps, dim3(1), dim3(64), 0, ctx->stream, d_ps, P, (const uint64_t *)off.as<uint64_t>(), out_ps.as<int64_t>());
-    RFX_HIP(hipGetLastError());
-    return RFX_OK;
+    RFX_LAUNCH(k_rd_marks, dim3(1), dim3(64), 0, d_ps, P, info.as<uint32_t>());
+    RFX_LAUNCH_N(k_rd_window<RIGHT>, n, v, n, prm.k1 - 1, info.as<uint32_t>(), maps.as<uint8_t>());
+    RFX_LAUNCH_N(k_rd_scan_reduce, n, maps.as<uint8_t>(), n, agg.as<uint8_t>());
+    RFX_LAUNCH(k_rd_scan_aggs, dim3(1), dim3(256), 0, agg.as<uint8_t>(), nb);
+    RFX_LAUNCH_N(k_rd_scan_apply<RIGHT>, n, maps.as<uint8_t>(), agg.as<uint8_t>(), n, info.as<uint32_t>(),
+                 cnt.as<uint32_t>());
+    int64_t total = 0;
+    RFX_TRY(scan_keep(ctx, cnt.as<uint32_t>(), n, off.as<uint64_t>(), &total));
+    if (total > n) { ctx->last_error = "k-mer reduction: an adjustment would write more rows than it read"; return RFX_E_STATE; }
+    RFX_TRY(dyn_alloc(ctx, out, total, total));
+    RFX_LAUNCH_N(k_rd_emit<RIGHT>, n, v, n, info.as<uint32_t>(), off.as<uint64_t>(), dyn_out(out));
+    return out_part_starts(ctx, d_ps, P, off.as<uint64_t>(), out_ps.as<int64_t>());
 }
 static int rd_adjust(rfx_ctx *ctx, bool right, const DynDev &in, const int64_t *d_ps, int P, const RdParams &prm, DynDev &out, DevBuf &out_ps) {
     return right ? rd_adjust_t<true>(ctx, in, d_ps, P, prm, out, out_ps) : rd_adjust_t<false>(ctx, in, d_ps, P, prm, out, out_ps);
@@ -477,39 +451,28 @@ static int rd_adjust(rfx_ctx *ctx, bool right, const DynDev &in, const int64_t *
 // step 11 over a sorted set of full k-mers cut into P partitions
 static int rd_neutralize(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, const RdParams &prm, DynDev &out, DevBuf &out_ps) {
     const int64_t n = in.n;
-    RFX_HIP(out_ps.alloc((size_t)(P + 1) * 8, ctx->stream));
-    if (n == 0) {
-        RFX_HIP(hipMemsetAsync(out_ps.p, 0, (size_t)(P + 1) * 8, ctx->stream));
-        return dyn_empty(ctx, out);
-    }
+    RFX_TRY(part_starts_alloc(ctx, out_ps, P, n == 0));
+    if (n == 0) return dyn_empty(ctx, out);
     RFX_TRY(check_part_starts(ctx, d_ps, P, n, "k-mer reduction"));
     RFX_TRY(rd_check(ctx, in, prm.k1, prm.k2, 0));
     DevBuf isl, lrank, lidx, near, brk, cbrk, keep, rank;
-    RFX_HIP(isl.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(lrank.alloc((size_t)(n + 1) * 8, ctx->stream)); RFX_HIP(lidx.alloc((size_t)n * 8, ctx->stream));
-    RFX_HIP(near.alloc((size_t)n * 8, ctx->stream)); RFX_HIP(brk.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(cbrk.alloc((size_t)(n + 1) * 8, ctx->stream));
-    RFX_HIP(keep.alloc((size_t)n * 4, ctx->stream)); RFX_HIP(rank.alloc((size_t)(n + 1) * 8, ctx->stream));
+    RFX_ALLOC(isl, uint32_t, n); RFX_ALLOC(lrank, uint64_t, n + 1); RFX_ALLOC(lidx, int64_t, n);
+    RFX_ALLOC(near, int64_t, n); RFX_ALLOC(brk, uint32_t, n); RFX_ALLOC(cbrk, uint64_t, n + 1);
+    RFX_ALLOC(keep, uint32_t, n); RFX_ALLOC(rank, uint64_t, n + 1);
     const DynView v = dyn_view(in);
-    hipLaunchKernelGGL(k_rd_nt_long, RFX_GRID(n), v, n, prm.k2, isl.as<uint32_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_rd_nt_long, n, v, n, prm.k2, isl.as<uint32_t>());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, isl.as<uint32_t>(), lrank.as<uint64_t>(), n));
-    hipLaunchKernelGGL(k_rd_nt_scatter, RFX_GRID(n), (const uint32_t *)isl.as<uint32_t>(), (const uint64_t *)lrank.as<uint64_t>(), n, lidx.as<int64_t>());
-    RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_rd_nt_break, RFX_GRID(n), v, n, (const uint32_t *)isl.as<uint32_t>(), (const uint64_t *)lrank.as<uint64_t>(),
-                       (const int64_t *)lidx.as<int64_t>(), d_ps, P, near.as<int64_t>(), brk.as<uint32_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_TRY(index_kept(ctx, isl.as<uint32_t>(), lrank.as<uint64_t>(), n, lidx.as<int64_t>()));
+    RFX_LAUNCH_N(k_rd_nt_break, n, v, n, isl.as<uint32_t>(), lrank.as<uint64_t>(),
+                 lidx.as<int64_t>(), d_ps, P, near.as<int64_t>(), brk.as<uint32_t>());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, brk.as<uint32_t>(), cbrk.as<uint64_t>(), n));
-    hipLaunchKernelGGL(k_rd_nt_keep, RFX_GRID(n), v, n, (const uint32_t *)isl.as<uint32_t>(), (const int64_t *)near.as<int64_t>(),
-                       (const uint64_t *)cbrk.as<uint64_t>(), d_ps, P, keep.as<uint32_t>());
-    RFX_HIP(hipGetLastError());
-    RFX_TRY(exclusive_scan_u32_to_u64(ctx, keep.as<uint32_t>(), rank.as<uint64_t>(), n));
-    uint64_t total = 0;
-    RFX_TRY(small_readback(ctx, &total, rank.as<uint64_t>() + n, 8));
-    RFX_TRY(dyn_alloc(ctx, out, (int64_t)total, 0));
-    hipLaunchKernelGGL(k_rd_compact, RFX_GRID(n), v, n, (const uint32_t *)keep.as<uint32_t>(), (const uint64_t *)rank.as<uint64_t>(), dyn_out(out));
-    RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_rd_out_ps, dim3(1), dim3(64), 0, ctx->stream, d_ps, P, (const uint64_t *)rank.as<uint64_t>(), out_ps.as<int64_t>());
-    RFX_HIP(hipGetLastError());
-    return RFX_OK;
+    RFX_LAUNCH_N(k_rd_nt_keep, n, v, n, isl.as<uint32_t>(), near.as<int64_t>(),
+                 cbrk.as<uint64_t>(), d_ps, P, keep.as<uint32_t>());
+    int64_t total = 0;
+    RFX_TRY(scan_keep(ctx, keep.as<uint32_t>(), n, rank.as<uint64_t>(), &total));
+    RFX_TRY(dyn_alloc(ctx, out, total, 0));
+    RFX_LAUNCH_N(k_rd_compact, n, v, n, keep.as<uint32_t>(), rank.as<uint64_t>(), dyn_out(out));
+    return out_part_starts(ctx, d_ps, P, rank.as<uint64_t>(), out_ps.as<int64_t>());
 }
 
 // the driver; the set stays in HBM between the operators
@@ -574,7 +537,7 @@ int rfx_dev_reduce_right_prepare(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const
 
 int rfx_dev_reduce_adjust(rfx_ctx *ctx, int right, const rfx_dyn_packed *d_sorted, const int64_t *d_part_start, int P, const rfx_reduce_params *params,
                           rfx_dyn_packed *d_out, int64_t *d_out_part_start) try {
-    if (!ctx || !dyn_packed_ok(d_sorted) || !dyn_packed_out_ok(d_out) || !d_part_start || !d_out_part_start || P < 1 || P > 63 || (right != 0 && right != 1)) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_ok(d_sorted) || !dyn_packed_out_ok(d_out) || !d_part_start || !d_out_part_start || !parts_ok(P) || (right != 0 && right != 1)) return RFX_E_ARG;
     RdParams prm;
     RFX_TRY(rd_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -583,8 +546,7 @@ int rfx_dev_reduce_adjust(rfx_ctx *ctx, int right, const rfx_dyn_packed *d_sorte
     RFX_TRY(dyn_borrow(ctx, d_sorted, a));
     RFX_TRY(rd_adjust(ctx, right != 0, a, d_part_start, P, prm, b, ops));
     RFX_TRY(dyn_store(ctx, b, d_out));                                // (both capacities are checked before anything is copied)
-    RFX_HIP(hipMemcpyAsync(d_out_part_start, ops.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    return sync_checked(ctx);
+    return part_starts_store(ctx, d_out_part_start, ops, P);
 } RFX_API_CATCH(ctx)
 
 int rfx_dev_reduce_full_kmers(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rfx_reduce_params *params, rfx_dyn_packed *d_out) try {
@@ -601,7 +563,7 @@ int rfx_dev_reduce_full_kmers(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rf
 
 int rfx_dev_reduce_neutralize(rfx_ctx *ctx, const rfx_dyn_packed *d_sorted, const int64_t *d_part_start, int P, const rfx_reduce_params *params,
                               rfx_dyn_packed *d_out, int64_t *d_out_part_start) try {
-    if (!ctx || !dyn_packed_ok(d_sorted) || !dyn_packed_out_ok(d_out) || !d_part_start || !d_out_part_start || P < 1 || P > 63) return RFX_E_ARG;
+    if (!ctx || !dyn_packed_ok(d_sorted) || !dyn_packed_out_ok(d_out) || !d_part_start || !d_out_part_start || !parts_ok(P)) return RFX_E_ARG;
     RdParams prm;
     RFX_TRY(rd_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -610,14 +572,13 @@ int rfx_dev_reduce_neutralize(rfx_ctx *ctx, const rfx_dyn_packed *d_sorted, cons
     RFX_TRY(dyn_borrow(ctx, d_sorted, a));
     RFX_TRY(rd_neutralize(ctx, a, d_part_start, P, prm, b, ops));
     RFX_TRY(dyn_store(ctx, b, d_out));
-    RFX_HIP(hipMemcpyAsync(d_out_part_start, ops.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    return sync_checked(ctx);
+    return part_starts_store(ctx, d_out_part_start, ops, P);
 } RFX_API_CATCH(ctx)
 
 int rfx_dev_reduce_run(rfx_ctx *ctx, const char *d_text_short, const int64_t *d_row_off_short, int64_t n_short, const char *d_text_long,
                        const int64_t *d_row_off_long, int64_t n_long, int P, const rfx_reduce_params *params, rfx_dyn_packed *d_out) try {
     if (!ctx || !dyn_packed_out_ok(d_out) || !text_rows_ok(d_text_short, d_row_off_short, n_short) || !text_rows_ok(d_text_long, d_row_off_long, n_long) ||
-        P < 1 || P > 63) return RFX_E_ARG;
+        !parts_ok(P)) return RFX_E_ARG;
     RdParams prm;
     RFX_TRY(rd_params(ctx, params, &prm));
     RFX_HIP(hipSetDevice(ctx->device));
@@ -630,7 +591,7 @@ int rfx_dev_reduce_run(rfx_ctx *ctx, const char *d_text_short, const int64_t *d_
 int rfx_reduce_text(rfx_ctx *ctx, const char *text_short, const int64_t *row_off_short, int64_t n_short, const char *text_long,
                     const int64_t *row_off_long, int64_t n_long, int P, const rfx_reduce_params *params, char *out_short, int64_t cap_short,
                     int64_t *out_len_short, char *out_long, int64_t cap_long, int64_t *out_len_long) try {
-    if (!ctx || !text_rows_ok(text_short, row_off_short, n_short) || !text_rows_ok(text_long, row_off_long, n_long) || P < 1 || P > 63 || !out_len_short ||
+    if (!ctx || !text_rows_ok(text_short, row_off_short, n_short) || !text_rows_ok(text_long, row_off_long, n_long) || !parts_ok(P) || !out_len_short ||
         !out_len_long || cap_short < 0 || cap_long < 0 || (cap_short > 0 && !out_short) || (cap_long > 0 && !out_long)) return RFX_E_ARG;
     RdParams prm;
     RFX_TRY(rd_params(ctx, params, &prm));
@@ -640,15 +601,11 @@ int rfx_reduce_text(rfx_ctx *ctx, const char *text_short, const int64_t *row_off
     int64_t t1 = 0, t2 = 0, rows = 0;
     RFX_TRY(dyn_upload_text(ctx, text_short, row_off_short, n_short, d_ts, d_os));
     RFX_TRY(dyn_upload_text(ctx, text_long, row_off_long, n_long, d_tl, d_ol));
-    RFX_TRY(rd_run(ctx, (const char *)d_ts.p, (const int64_t *)d_os.as<int64_t>(), n_short, (const char *)d_tl.p, (const int64_t *)d_ol.as<int64_t>(), n_long,
+    RFX_TRY(rd_run(ctx, (const char *)d_ts.p, d_os.as<int64_t>(), n_short, (const char *)d_tl.p, d_ol.as<int64_t>(), n_long,
                    P, prm, a));
     RFX_TRY(ks_set_to_text(ctx, a, prm.k1, nullptr, 0, &t1, nullptr, &rows, &d_o1));
     RFX_TRY(ks_set_to_text(ctx, a, prm.k2, nullptr, 0, &t2, nullptr, &rows, &d_o2));
-    *out_len_short = t1; *out_len_long = t2;
-    if (t1 > cap_short || t2 > cap_long) return RFX_E_CAP;           // (nothing written)
-    if (t1 > 0) RFX_HIP(hipMemcpyAsync(out_short, d_o1.p, (size_t)t1, hipMemcpyDeviceToHost, ctx->stream));
-    if (t2 > 0) RFX_HIP(hipMemcpyAsync(out_long, d_o2.p, (size_t)t2, hipMemcpyDeviceToHost, ctx->stream));
-    return sync_checked(ctx);
+    return text_to_host(ctx, {{d_o1, t1, out_short, cap_short, out_len_short}, {d_o2, t2, out_long, cap_long, out_len_long}}, false);
 } RFX_API_CATCH(ctx)
 
 }  // extern "C"

@@ -201,12 +201,11 @@ int scan_lookback(rfx_ctx *ctx, const uint32_t *a, const uint32_t *b, uint64_t *
     }
     const unsigned long long tb = ctx->scan_tickets_issued;
     if (b)
-        hipLaunchKernelGGL(k_scan_lookback<true>, dim3((unsigned)nt), dim3(LB_THREADS), 0, ctx->stream, a, b, n, oa, ob, ctx->scan_desc,
-                           ctx->scan_ticket, tb, ctx->scan_epoch, ctx->scan_fault);
+        RFX_LAUNCH(k_scan_lookback<true>, dim3((unsigned)nt), dim3(LB_THREADS), 0, a, b, n, oa, ob, ctx->scan_desc,
+                   ctx->scan_ticket, tb, ctx->scan_epoch, ctx->scan_fault);
     else
-        hipLaunchKernelGGL(k_scan_lookback<false>, dim3((unsigned)nt), dim3(LB_THREADS), 0, ctx->stream, a, (const uint32_t *)nullptr, n, oa,
-                           (uint64_t *)nullptr, ctx->scan_desc, ctx->scan_ticket, tb, ctx->scan_epoch, ctx->scan_fault);
-    RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_scan_lookback<false>, dim3((unsigned)nt), dim3(LB_THREADS), 0, a, (const uint32_t *)nullptr, n, oa,
+                   (uint64_t *)nullptr, ctx->scan_desc, ctx->scan_ticket, tb, ctx->scan_epoch, ctx->scan_fault);
     ctx->scan_tickets_issued += (unsigned long long)nt;        // only once the launch is known to be queued: the device counter moves with it
     return RFX_OK;
 }
@@ -214,27 +213,23 @@ int scan_lookback(rfx_ctx *ctx, const uint32_t *a, const uint32_t *b, uint64_t *
 template <class T>
 int scan_impl(rfx_ctx *ctx, const T *d_in, uint64_t *d_out, int64_t n) {
     if (n <= 0) {
-        hipLaunchKernelGGL(k_zero_total, dim3(1), dim3(1), 0, ctx->stream, d_out);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_zero_total, dim3(1), dim3(1), 0, d_out);
         return RFX_OK;
     }
     int64_t nt = ceil_div(n, SCAN_TILE);
     if (nt == 1) {
-        hipLaunchKernelGGL(k_tile_scan<T>, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, d_in, n,
-                           (const uint64_t *)nullptr, d_out);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_tile_scan<T>, dim3(1), dim3(SCAN_THREADS), 0, d_in, n,
+                   (const uint64_t *)nullptr, d_out);
         return RFX_OK;
     }
     DevBuf sums, offs;
-    RFX_HIP(sums.alloc((size_t)nt * 8, ctx->stream));
-    RFX_HIP(offs.alloc((size_t)(nt + 1) * 8, ctx->stream));
-    hipLaunchKernelGGL(k_tile_sums<T>, dim3((unsigned)nt), dim3(SCAN_THREADS), 0, ctx->stream, d_in, n,
-                       sums.as<uint64_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_ALLOC(sums, uint64_t, nt);
+    RFX_ALLOC(offs, uint64_t, nt + 1);
+    RFX_LAUNCH(k_tile_sums<T>, dim3((unsigned)nt), dim3(SCAN_THREADS), 0, d_in, n,
+               sums.as<uint64_t>());
     RFX_TRY(scan_impl<uint64_t>(ctx, sums.as<uint64_t>(), offs.as<uint64_t>(), nt));
-    hipLaunchKernelGGL(k_tile_scan<T>, dim3((unsigned)nt), dim3(SCAN_THREADS), 0, ctx->stream, d_in, n,
-                       (const uint64_t *)offs.as<uint64_t>(), d_out);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH(k_tile_scan<T>, dim3((unsigned)nt), dim3(SCAN_THREADS), 0, d_in, n,
+               offs.as<uint64_t>(), d_out);
     return RFX_OK;
 }
 
@@ -246,8 +241,7 @@ int small_readback(rfx_ctx *ctx, void *h_dst, const void *d_src, size_t nbytes) 
         RFX_HIP(hipMemcpyAsync(h_dst, d_src, nbytes, hipMemcpyDeviceToHost, ctx->stream));
         return sync_checked(ctx);
     }
-    hipLaunchKernelGGL(k_mailbox_post, dim3(1), dim3(64), 0, ctx->stream, (const uint8_t *)d_src, (int)nbytes, ctx->mailbox, seq);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH(k_mailbox_post, dim3(1), dim3(64), 0, (const uint8_t *)d_src, (int)nbytes, ctx->mailbox, seq);
     uint64_t v[7] = {0, 0, 0, 0, 0, 0, 0};
     RFX_TRY(mailbox_wait(ctx, seq, v, (int)((nbytes + 7) / 8)));
     memcpy(h_dst, v, nbytes);

@@ -34,7 +34,6 @@ namespace {
 
 constexpr int SH_MAXW = 64;                 // ranks (rfx_comm_init's limit)
 
-inline unsigned grid_for(int64_t n, int block = 256) { return (unsigned)ceil_div(n > 0 ? n : 1, block); }
 
 #define RFX_KW_SWITCH(kw, ...)                                                \
     switch (kw) {                                                             \
@@ -306,11 +305,9 @@ struct Shard : PartCarry {
     // ---- PartCarry: the parity this rank's first partition brings from the ranks before (device -> device, no host wait)
     int compute(rfx_ctx *, const int64_t *d_ps, int P, const uint64_t *d_cum, int64_t n, const int32_t **d_carry) override {
         int32_t *out = (int32_t *)(d + o_carry()) + 2 * (carry_slot++ & 3);
-        hipLaunchKernelGGL(k_sh_trailing, dim3(1), dim3(64), 0, ctx->stream, d_ps, P, d_cum, n, d + o_trail());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_sh_trailing, dim3(1), dim3(64), 0, d_ps, P, d_cum, n, d + o_trail());
         RFX_NCCL(nccl().AllGather(d + o_trail(), d + o_trall(), 4, ncclInt64, c->comm, ctx->stream));
-        hipLaunchKernelGGL(k_sh_carry, dim3(1), dim3(64), 0, ctx->stream, (const int64_t *)(d + o_trall()), W, me, out);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_sh_carry, dim3(1), dim3(64), 0, (const int64_t *)(d + o_trall()), W, me, out);
         *d_carry = out;
         return RFX_OK;
     }
@@ -383,11 +380,15 @@ struct Shard : PartCarry {
         // the fixed parts go through the send buffer (packed; room_to_send() made it large enough before the matrix went
         // round), the extension words leave from where they lie
         if (st_local == RFX_OK && src.n > 0) {
-            RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_sh_pack<KW>, dim3(grid_for(src.n)), dim3(256), 0, ctx->stream,
-                                                 (const KeyW<KW> *)src.key.as<KeyW<KW>>(), (const int32_t *)src.marker.as<int32_t>(),
-                                                 (const int32_t *)src.left.as<int32_t>(), (const int32_t *)src.right.as<int32_t>(),
-                                                 (const int64_t *)src.ext_off.as<int64_t>(), src.n, (uint64_t *)c->send));
-            if (hipGetLastError() != hipSuccess) { st_local = RFX_E_HIP; ctx->last_error = "rfx_dev_sharded_assemble: pack launch failed"; }
+            auto pack = [&]() -> int {
+                RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_sh_pack<KW>, src.n, src.key.as<KeyW<KW>>(), src.marker.as<int32_t>(),
+                                               src.left.as<int32_t>(), src.right.as<int32_t>(), src.ext_off.as<int64_t>(), src.n,
+                                               (uint64_t *)c->send));
+                return RFX_OK;
+            };
+            const int sp = pack();
+            if (sp == RFX_E_HIP) { st_local = RFX_E_HIP; ctx->last_error = "rfx_dev_sharded_assemble: pack launch failed"; }
+            else if (sp != RFX_OK) return sp;
         }
         RFX_TRY(alltoallv_words(c, (const uint64_t *)c->send, soff.data(), scnt.data(), (uint64_t *)c->recv, roff.data(), rcnt.data(), rounds, 1, ctx->stream));
         RFX_TRY(alltoallv_words(c, src.ext.as<uint64_t>(), swoff.data(), swcnt.data(), (uint64_t *)c->recv, rwoff.data(), rwcnt.data(), rounds, 1, ctx->stream));
@@ -396,12 +397,11 @@ struct Shard : PartCarry {
         auto unpack = [&]() -> int {
             RFX_TRY(dev_records_alloc(ctx, dst, n_in, w_in, kw));
             DevBuf nw;
-            RFX_HIP(nw.alloc((size_t)std::max<int64_t>(1, n_in) * 4, ctx->stream));
+            RFX_ALLOC(nw, uint32_t, std::max<int64_t>(1, n_in));
             if (n_in > 0) {
-                RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_sh_unpack<KW>, dim3(grid_for(n_in)), dim3(256), 0, ctx->stream, (const uint64_t *)c->recv, n_in,
-                                                     dst.key.as<KeyW<KW>>(), dst.marker.as<int32_t>(), dst.left.as<int32_t>(), dst.right.as<int32_t>(),
-                                                     nw.as<uint32_t>()));
-                RFX_HIP(hipGetLastError());
+                RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_sh_unpack<KW>, n_in, (const uint64_t *)c->recv, n_in,
+                                               dst.key.as<KeyW<KW>>(), dst.marker.as<int32_t>(), dst.left.as<int32_t>(), dst.right.as<int32_t>(),
+                                               nw.as<uint32_t>()));
             }
             RFX_TRY(exclusive_scan_u32_to_u64(ctx, nw.as<uint32_t>(), (uint64_t *)dst.ext_off.as<int64_t>(), n_in));
             if (w_in > 0)
@@ -431,9 +431,8 @@ struct Shard : PartCarry {
         // sample -> splitters -> cuts -> this rank's row of the matrix, all on the device
         auto plan = [&]() -> int {
             if (st_local != RFX_OK) { RFX_HIP(hipMemsetAsync(d + o_row(), 0, (size_t)(2 * W) * 8, ctx->stream)); RFX_HIP(hipMemsetAsync(d + o_aux(), 0, (size_t)(2 * W + 2) * 8, ctx->stream)); }
-            RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_sh_sample<KW>, dim3(grid_for(S + 1)), dim3(256), 0, ctx->stream,
-                                                 (const KeyW<KW> *)sorted.key.as<KeyW<KW>>(), sorted.n, S, (uint64_t *)(d + o_samp())));
-            RFX_HIP(hipGetLastError());
+            RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_sh_sample<KW>, S + 1,
+                                           sorted.key.as<KeyW<KW>>(), sorted.n, S, (uint64_t *)(d + o_samp())));
             return RFX_OK;
         };
         if (st_local == RFX_OK) { const int sp = plan(); if (sp != RFX_OK) st_local = sp; }
@@ -441,13 +440,11 @@ struct Shard : PartCarry {
         RFX_NCCL(nccl().AllGather(d + o_samp(), d + o_sall(), (size_t)(S * kw + 1), ncclInt64, c->comm, ctx->stream));
         if (st_local == RFX_OK) {
             auto cuts = [&]() -> int {
-                RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_sh_splitters<KW>, dim3(1), dim3(1024), 0, ctx->stream, (const uint64_t *)(d + o_sall()), W, S,
-                                                     (uint64_t *)(d + o_split())));
-                RFX_HIP(hipGetLastError());
-                RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_sh_cuts<KW>, dim3(1), dim3(128), 0, ctx->stream, (const KeyW<KW> *)sorted.key.as<KeyW<KW>>(), sorted.n,
-                                                     (const uint64_t *)(d + o_split()), W, (const int64_t *)sorted.ext_off.as<int64_t>(),
-                                                     d + o_row(), d + o_aux()));
-                RFX_HIP(hipGetLastError());
+                RFX_KW_SWITCH(kw, RFX_LAUNCH(k_sh_splitters<KW>, dim3(1), dim3(1024), 0, (const uint64_t *)(d + o_sall()), W, S,
+                                             (uint64_t *)(d + o_split())));
+                RFX_KW_SWITCH(kw, RFX_LAUNCH(k_sh_cuts<KW>, dim3(1), dim3(128), 0, sorted.key.as<KeyW<KW>>(), sorted.n,
+                                             (const uint64_t *)(d + o_split()), W, sorted.ext_off.as<int64_t>(),
+                                             d + o_row(), d + o_aux()));
                 return RFX_OK;
             };
             const int sc = cuts();
@@ -461,10 +458,9 @@ struct Shard : PartCarry {
             auto fin = [&]() -> int {
                 RFX_TRY(sort_records(ctx, merged, 1, key_bits, out, ps0, k_eff));
                 if (P > 0) {
-                    RFX_HIP(ps.alloc((size_t)(P + 1) * 8, ctx->stream));
-                    RFX_KW_SWITCH(kw, hipLaunchKernelGGL(k_sh_part_starts<KW>, dim3(grid_for(P + 1)), dim3(256), 0, ctx->stream,
-                                                         (const KeyW<KW> *)out.key.as<KeyW<KW>>(), out.n, N, off, P, ps.as<int64_t>()));
-                    RFX_HIP(hipGetLastError());
+                    RFX_ALLOC(ps, int64_t, P + 1);
+                    RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_sh_part_starts<KW>, P + 1,
+                                                   out.key.as<KeyW<KW>>(), out.n, N, off, P, ps.as<int64_t>()));
                 }
                 return RFX_OK;
             };
@@ -579,8 +575,7 @@ int rfx_dev_sharded_assemble(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_keys, 
                 RFX_HIP(hipMemsetAsync(kr.right.p, 0, (size_t)n * 4, ctx->stream));
                 RFX_HIP(hipMemsetAsync(kr.ext.p, 0, (size_t)n * 8, ctx->stream));
             }
-            hipLaunchKernelGGL(k_sh_iota, dim3(grid_for(n + 1)), dim3(256), 0, ctx->stream, kr.ext_off.as<int64_t>(), n);
-            RFX_HIP(hipGetLastError());
+            RFX_LAUNCH_N(k_sh_iota, n + 1, kr.ext_off.as<int64_t>(), n);
             kr.n = n; kr.words = n;
             return RFX_OK;
         };
@@ -643,7 +638,7 @@ int rfx_dev_sharded_assemble(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_keys, 
     sh.next_arena();
     {
         const int32_t *d_carry = nullptr;
-        if (sh.st_local != RFX_OK) { b.n = 0; b.words = 0; b.kw = kw; RFX_HIP(ops.alloc((size_t)(P + 1) * 8, ctx->stream)); RFX_HIP(hipMemsetAsync(ops.p, 0, (size_t)(P + 1) * 8, ctx->stream)); }
+        if (sh.st_local != RFX_OK) { b.n = 0; b.words = 0; b.kw = kw; RFX_ALLOC(ops, int64_t, P + 1); RFX_HIP(hipMemsetAsync(ops.p, 0, (size_t)(P + 1) * 8, ctx->stream)); }
         RFX_TRY(sh.compute(ctx, ops.as<int64_t>(), P, nullptr, b.n, &d_carry));
         SH_LOCAL(random_reflection(ctx, b, ops.as<int64_t>(), P, k, a, d_carry));
         if (sh.st_local != RFX_OK) { a.n = 0; a.words = 0; a.kw = kw; }
@@ -655,7 +650,7 @@ int rfx_dev_sharded_assemble(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_keys, 
         if (sh.st_local != RFX_OK) {                                                  // (the carry's collective must still be met)
             const int32_t *dc = nullptr;
             DevBuf z;
-            RFX_HIP(z.alloc((size_t)(P + 1) * 8, ctx->stream));
+            RFX_ALLOC(z, int64_t, P + 1);
             RFX_HIP(hipMemsetAsync(z.p, 0, (size_t)(P + 1) * 8, ctx->stream));
             RFX_TRY(sh.compute(ctx, z.as<int64_t>(), P, nullptr, 0, &dc));
             a.n = 0; a.words = 0; a.kw = kw;
@@ -667,7 +662,7 @@ int rfx_dev_sharded_assemble(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_keys, 
                 sh.st_local = se; a.n = 0; a.words = 0; a.kw = kw;
                 if (sh.carry_slot == before) {                                    // the pass failed before its carry: the peers are in that all-gather
                     const int32_t *dc = nullptr;
-                    RFX_HIP(ops.alloc((size_t)(P + 1) * 8, ctx->stream));
+                    RFX_ALLOC(ops, int64_t, P + 1);
                     RFX_HIP(hipMemsetAsync(ops.p, 0, (size_t)(P + 1) * 8, ctx->stream));
                     RFX_TRY(sh.compute(ctx, ops.as<int64_t>(), P, nullptr, 0, &dc));
                 }

@@ -351,14 +351,13 @@ int sort_pairs(rfx_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, int64_t n, int 
     if (key_bits > 64) key_bits = 64;
     const int passes = (key_bits + 7) / 8;
     if (n <= STILE) {
-        hipLaunchKernelGGL(k_sort_small, dim3(1), dim3(ST), 0, ctx->stream, d_keys, d_vals, (int)n, key_bits);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_sort_small, dim3(1), dim3(ST), 0, d_keys, d_vals, (int)n, key_bits);
         return RFX_OK;
     }
     const int64_t ntiles = ceil_div(n, STILE);
     DevBuf table, offs;
-    RFX_HIP(table.alloc((size_t)ntiles * 256 * 4, ctx->stream));
-    RFX_HIP(offs.alloc((size_t)(ntiles * 256 + 1) * 8, ctx->stream));
+    RFX_ALLOC(table, uint32_t, (size_t)ntiles * 256);
+    RFX_ALLOC(offs, uint64_t, ntiles * 256 + 1);
     uint64_t *sk = d_keys, *dk = d_tmp_keys;
     uint32_t *sv = d_vals, *dv = d_tmp_vals;
     const bool inline_scan = ntiles <= 64;           // <= 128 K pairs
@@ -376,59 +375,48 @@ int sort_pairs(rfx_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, int64_t n, int 
         const int NP2 = 65536;
         const int64_t vmax2 = ntiles + 256, vmax3 = ntiles + NP2;
         DevBuf table2, offs2, maps1, bounds2, tstart2, table3, offs3, bounds3;
-        RFX_HIP(table2.alloc((size_t)vmax2 * 256 * 4, ctx->stream));
-        RFX_HIP(offs2.alloc((size_t)(vmax2 * 256 + 1) * 8, ctx->stream));
-        RFX_HIP(maps1.alloc(2 * 257 * 4, ctx->stream));
-        RFX_HIP(bounds2.alloc((size_t)(NP2 + 2) * 4, ctx->stream));
-        RFX_HIP(tstart2.alloc((size_t)(NP2 + 1) * 4, ctx->stream));
-        RFX_HIP(table3.alloc((size_t)vmax3 * D3 * 4, ctx->stream));
-        RFX_HIP(offs3.alloc((size_t)(vmax3 * D3 + 1) * 8, ctx->stream));
-        RFX_HIP(bounds3.alloc((size_t)((size_t)NP2 * D3 + 2) * 4, ctx->stream));
+        RFX_ALLOC(table2, uint32_t, (size_t)vmax2 * 256);
+        RFX_ALLOC(offs2, uint64_t, vmax2 * 256 + 1);
+        RFX_ALLOC(maps1, uint32_t, 2 * 257);
+        RFX_ALLOC(bounds2, uint32_t, NP2 + 2);
+        RFX_ALLOC(tstart2, uint32_t, NP2 + 1);
+        RFX_ALLOC(table3, uint32_t, (size_t)vmax3 * D3);
+        RFX_ALLOC(offs3, uint64_t, vmax3 * D3 + 1);
+        RFX_ALLOC(bounds3, uint32_t, (size_t)NP2 * D3 + 2);
         uint32_t *d_b1 = maps1.as<uint32_t>(), *d_t1 = maps1.as<uint32_t>() + 257;
         uint32_t *d_max2 = bounds2.as<uint32_t>() + NP2 + 1, *d_max3 = bounds3.as<uint32_t>() + (size_t)NP2 * D3 + 1;
         // level 1: sk -> dk
-        hipLaunchKernelGGL(k_hist<false>, dim3((unsigned)ntiles), dim3(ST), 0, ctx->stream, sk, n, shift1, table.as<uint32_t>(), ntiles, nomap);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_hist<false>, dim3((unsigned)ntiles), dim3(ST), 0, sk, n, shift1, table.as<uint32_t>(), ntiles, nomap);
         RFX_TRY(exclusive_scan_u32_to_u64(ctx, table.as<uint32_t>(), offs.as<uint64_t>(), ntiles * 256));
-        hipLaunchKernelGGL(k_scatter<false>, dim3((unsigned)ntiles), dim3(ST), 0, ctx->stream, sk, sv, n, shift1,
-                           (const uint64_t *)offs.as<uint64_t>(), ntiles, dk, dv, (const uint32_t *)table.as<uint32_t>(), nomap);
-        RFX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_l2_setup, dim3(1), dim3(256), 0, ctx->stream, (const uint64_t *)offs.as<uint64_t>(), ntiles, n, d_b1, d_t1);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_scatter<false>, dim3((unsigned)ntiles), dim3(ST), 0, sk, sv, n, shift1,
+                   offs.as<uint64_t>(), ntiles, dk, dv, table.as<uint32_t>(), nomap);
+        RFX_LAUNCH(k_l2_setup, dim3(1), dim3(256), 0, offs.as<uint64_t>(), ntiles, n, d_b1, d_t1);
         // level 2: dk -> sk, 256 digits inside every level-1 bucket
         const SegMap sm2{d_b1, d_t1, 256, 256};
         RFX_HIP(hipMemsetAsync(table2.p, 0, (size_t)vmax2 * 256 * 4, ctx->stream));
         RFX_HIP(hipMemsetAsync(d_max2, 0, 4, ctx->stream));
-        hipLaunchKernelGGL(k_hist<true>, dim3((unsigned)vmax2), dim3(ST), 0, ctx->stream, (const uint64_t *)dk, n, shift2, table2.as<uint32_t>(), vmax2, sm2);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_hist<true>, dim3((unsigned)vmax2), dim3(ST), 0, dk, n, shift2, table2.as<uint32_t>(), vmax2, sm2);
         RFX_TRY(exclusive_scan_u32_to_u64(ctx, table2.as<uint32_t>(), offs2.as<uint64_t>(), vmax2 * 256));
-        hipLaunchKernelGGL(k_scatter<true>, dim3((unsigned)vmax2), dim3(ST), 0, ctx->stream, (const uint64_t *)dk, (const uint32_t *)dv, n, shift2,
-                           (const uint64_t *)offs2.as<uint64_t>(), vmax2, sk, sv, (const uint32_t *)table2.as<uint32_t>(), sm2);
-        RFX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_l3_bounds, dim3((unsigned)ceil_div(NP2 + 1, 256)), dim3(256), 0, ctx->stream,
-                           (const uint64_t *)offs2.as<uint64_t>(), sm2, n, bounds2.as<uint32_t>(), d_max2);
-        RFX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_seg_setup, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t *)bounds2.as<uint32_t>(), NP2, tstart2.as<uint32_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_scatter<true>, dim3((unsigned)vmax2), dim3(ST), 0, dk, dv, n, shift2,
+                   offs2.as<uint64_t>(), vmax2, sk, sv, table2.as<uint32_t>(), sm2);
+        RFX_LAUNCH(k_l3_bounds, dim3((unsigned)ceil_div(NP2 + 1, 256)), dim3(256), 0,
+                   offs2.as<uint64_t>(), sm2, n, bounds2.as<uint32_t>(), d_max2);
+        RFX_LAUNCH(k_seg_setup, dim3(1), dim3(1024), 0, bounds2.as<uint32_t>(), NP2, tstart2.as<uint32_t>());
         // level 3: sk -> dk, D3 digits inside every level-2 bucket
         const SegMap sm3{bounds2.as<uint32_t>(), tstart2.as<uint32_t>(), D3, NP2};
         RFX_HIP(hipMemsetAsync(table3.p, 0, (size_t)vmax3 * D3 * 4, ctx->stream));
         RFX_HIP(hipMemsetAsync(d_max3, 0, 4, ctx->stream));
-        hipLaunchKernelGGL(k_hist<true>, dim3((unsigned)vmax3), dim3(ST), 0, ctx->stream, (const uint64_t *)sk, n, shift3, table3.as<uint32_t>(), vmax3, sm3);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_hist<true>, dim3((unsigned)vmax3), dim3(ST), 0, sk, n, shift3, table3.as<uint32_t>(), vmax3, sm3);
         RFX_TRY(exclusive_scan_u32_to_u64(ctx, table3.as<uint32_t>(), offs3.as<uint64_t>(), vmax3 * D3));
-        hipLaunchKernelGGL(k_scatter<true>, dim3((unsigned)vmax3), dim3(ST), 0, ctx->stream, (const uint64_t *)sk, (const uint32_t *)sv, n, shift3,
-                           (const uint64_t *)offs3.as<uint64_t>(), vmax3, dk, dv, (const uint32_t *)table3.as<uint32_t>(), sm3);
-        RFX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_l3_bounds, dim3((unsigned)ceil_div((int64_t)NP2 * D3 + 1, 256)), dim3(256), 0, ctx->stream,
-                           (const uint64_t *)offs3.as<uint64_t>(), sm3, n, bounds3.as<uint32_t>(), d_max3);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_scatter<true>, dim3((unsigned)vmax3), dim3(ST), 0, sk, sv, n, shift3,
+                   offs3.as<uint64_t>(), vmax3, dk, dv, table3.as<uint32_t>(), sm3);
+        RFX_LAUNCH(k_l3_bounds, dim3((unsigned)ceil_div((int64_t)NP2 * D3 + 1, 256)), dim3(256), 0,
+                   offs3.as<uint64_t>(), sm3, n, bounds3.as<uint32_t>(), d_max3);
         uint32_t maxc = 0;
         RFX_TRY(small_readback(ctx, &maxc, d_max3, 4));
         if (maxc <= (uint32_t)STILE) {
-            hipLaunchKernelGGL(k_sort_buckets, dim3((unsigned)((int64_t)NP2 * D3)), dim3(ST), 0, ctx->stream, (const uint64_t *)dk, (const uint32_t *)dv,
-                               (const uint32_t *)bounds3.as<uint32_t>(), shift3, d_keys, d_vals);
-            RFX_HIP(hipGetLastError());
+            RFX_LAUNCH(k_sort_buckets, dim3((unsigned)((int64_t)NP2 * D3)), dim3(ST), 0, dk, dv,
+                       bounds3.as<uint32_t>(), shift3, d_keys, d_vals);
             return RFX_OK;
         }
         // skewed: (dk, dv) hold a stable regrouping of the input; the LSD passes finish it from there
@@ -446,38 +434,31 @@ int sort_pairs(rfx_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, int64_t n, int 
         const int shift2 = shift1 - b2, D2 = 1 << b2;
         const int64_t vmax = ntiles + 256;               // upper bound of the virtual tiles
         DevBuf table2, offs2, maps, b3;
-        RFX_HIP(table2.alloc((size_t)vmax * D2 * 4, ctx->stream));
-        RFX_HIP(offs2.alloc((size_t)(vmax * D2 + 1) * 8, ctx->stream));
-        RFX_HIP(maps.alloc(2 * 257 * 4, ctx->stream));
-        RFX_HIP(b3.alloc((size_t)(256 * D2 + 2) * 4, ctx->stream));
+        RFX_ALLOC(table2, uint32_t, (size_t)vmax * D2);
+        RFX_ALLOC(offs2, uint64_t, vmax * D2 + 1);
+        RFX_ALLOC(maps, uint32_t, 2 * 257);
+        RFX_ALLOC(b3, uint32_t, 256 * D2 + 2);
         uint32_t *d_bstart = maps.as<uint32_t>(), *d_tstart = maps.as<uint32_t>() + 257;
         uint32_t *d_maxc = b3.as<uint32_t>() + 256 * D2 + 1;
-        hipLaunchKernelGGL(k_hist<false>, dim3((unsigned)ntiles), dim3(ST), 0, ctx->stream, sk, n, shift1, table.as<uint32_t>(), ntiles, nomap);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_hist<false>, dim3((unsigned)ntiles), dim3(ST), 0, sk, n, shift1, table.as<uint32_t>(), ntiles, nomap);
         RFX_TRY(exclusive_scan_u32_to_u64(ctx, table.as<uint32_t>(), offs.as<uint64_t>(), ntiles * 256));
-        hipLaunchKernelGGL(k_scatter<false>, dim3((unsigned)ntiles), dim3(ST), 0, ctx->stream, sk, sv, n, shift1,
-                           (const uint64_t *)offs.as<uint64_t>(), ntiles, dk, dv, (const uint32_t *)table.as<uint32_t>(), nomap);
-        RFX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_l2_setup, dim3(1), dim3(256), 0, ctx->stream, (const uint64_t *)offs.as<uint64_t>(), ntiles, n, d_bstart, d_tstart);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_scatter<false>, dim3((unsigned)ntiles), dim3(ST), 0, sk, sv, n, shift1,
+                   offs.as<uint64_t>(), ntiles, dk, dv, table.as<uint32_t>(), nomap);
+        RFX_LAUNCH(k_l2_setup, dim3(1), dim3(256), 0, offs.as<uint64_t>(), ntiles, n, d_bstart, d_tstart);
         const SegMap sm{d_bstart, d_tstart, D2};
         RFX_HIP(hipMemsetAsync(table2.p, 0, (size_t)vmax * D2 * 4, ctx->stream));
         RFX_HIP(hipMemsetAsync(d_maxc, 0, 4, ctx->stream));
-        hipLaunchKernelGGL(k_hist<true>, dim3((unsigned)vmax), dim3(ST), 0, ctx->stream, (const uint64_t *)dk, n, shift2, table2.as<uint32_t>(), vmax, sm);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_hist<true>, dim3((unsigned)vmax), dim3(ST), 0, dk, n, shift2, table2.as<uint32_t>(), vmax, sm);
         RFX_TRY(exclusive_scan_u32_to_u64(ctx, table2.as<uint32_t>(), offs2.as<uint64_t>(), vmax * D2));
-        hipLaunchKernelGGL(k_scatter<true>, dim3((unsigned)vmax), dim3(ST), 0, ctx->stream, (const uint64_t *)dk, (const uint32_t *)dv, n, shift2,
-                           (const uint64_t *)offs2.as<uint64_t>(), vmax, sk, sv, (const uint32_t *)table2.as<uint32_t>(), sm);
-        RFX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_l3_bounds, dim3((unsigned)ceil_div(256 * D2 + 1, 256)), dim3(256), 0, ctx->stream,
-                           (const uint64_t *)offs2.as<uint64_t>(), sm, n, b3.as<uint32_t>(), d_maxc);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_scatter<true>, dim3((unsigned)vmax), dim3(ST), 0, dk, dv, n, shift2,
+                   offs2.as<uint64_t>(), vmax, sk, sv, table2.as<uint32_t>(), sm);
+        RFX_LAUNCH(k_l3_bounds, dim3((unsigned)ceil_div(256 * D2 + 1, 256)), dim3(256), 0,
+                   offs2.as<uint64_t>(), sm, n, b3.as<uint32_t>(), d_maxc);
         uint32_t maxc = 0;
         RFX_TRY(small_readback(ctx, &maxc, d_maxc, 4));
         if (maxc <= (uint32_t)STILE) {
-            hipLaunchKernelGGL(k_sort_buckets, dim3((unsigned)(256 * D2)), dim3(ST), 0, ctx->stream, (const uint64_t *)sk, (const uint32_t *)sv,
-                               (const uint32_t *)b3.as<uint32_t>(), shift2, d_keys, d_vals);
-            RFX_HIP(hipGetLastError());
+            RFX_LAUNCH(k_sort_buckets, dim3((unsigned)(256 * D2)), dim3(ST), 0, sk, sv,
+                       b3.as<uint32_t>(), shift2, d_keys, d_vals);
             return RFX_OK;
         }
         // skewed: (sk, sv) = (d_keys, d_vals) hold a stable regrouping of the input; the LSD passes finish it
@@ -487,13 +468,11 @@ int sort_pairs(rfx_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, int64_t n, int 
         // the LSD passes below instead)
         const int shift = key_bits - 8;
         DevBuf bounds;
-        RFX_HIP(bounds.alloc(258 * 4, ctx->stream));
-        hipLaunchKernelGGL(k_hist<false>, dim3((unsigned)ntiles), dim3(ST), 0, ctx->stream, sk, n, shift, table.as<uint32_t>(), ntiles, nomap);
-        RFX_HIP(hipGetLastError());
+        RFX_ALLOC(bounds, uint32_t, 258);
+        RFX_LAUNCH(k_hist<false>, dim3((unsigned)ntiles), dim3(ST), 0, sk, n, shift, table.as<uint32_t>(), ntiles, nomap);
         const uint64_t seq = mailbox_next(ctx);
-        hipLaunchKernelGGL(k_bucket_bounds, dim3(1), dim3(256), 0, ctx->stream, (const uint32_t *)table.as<uint32_t>(), ntiles,
-                           bounds.as<uint32_t>(), bounds.as<uint32_t>() + 257, seq ? ctx->mailbox : (volatile uint64_t *)nullptr, seq);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_bucket_bounds, dim3(1), dim3(256), 0, table.as<uint32_t>(), ntiles,
+                   bounds.as<uint32_t>(), bounds.as<uint32_t>() + 257, seq ? ctx->mailbox : (volatile uint64_t *)nullptr, seq);
         uint32_t maxc = 0;
         if (seq) { uint64_t v = 0; RFX_TRY(mailbox_wait(ctx, seq, &v, 1)); maxc = (uint32_t)v; }
         else {
@@ -502,26 +481,22 @@ int sort_pairs(rfx_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, int64_t n, int 
         }
         if (maxc <= (uint32_t)STILE) {
             if (!inline_scan) RFX_TRY(exclusive_scan_u32_to_u64(ctx, table.as<uint32_t>(), offs.as<uint64_t>(), ntiles * 256));
-            hipLaunchKernelGGL(k_scatter<false>, dim3((unsigned)ntiles), dim3(ST), 0, ctx->stream, sk, sv, n, shift,
-                               inline_scan ? (const uint64_t *)nullptr : (const uint64_t *)offs.as<uint64_t>(), ntiles, dk, dv,
-                               (const uint32_t *)table.as<uint32_t>(), nomap);
-            RFX_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_sort_buckets, dim3(256), dim3(ST), 0, ctx->stream, (const uint64_t *)dk, (const uint32_t *)dv,
-                               (const uint32_t *)bounds.as<uint32_t>(), shift, d_keys, d_vals);
-            RFX_HIP(hipGetLastError());
+            RFX_LAUNCH(k_scatter<false>, dim3((unsigned)ntiles), dim3(ST), 0, sk, sv, n, shift,
+                       inline_scan ? (const uint64_t *)nullptr : offs.as<uint64_t>(), ntiles, dk, dv,
+                       table.as<uint32_t>(), nomap);
+            RFX_LAUNCH(k_sort_buckets, dim3(256), dim3(ST), 0, dk, dv,
+                       bounds.as<uint32_t>(), shift, d_keys, d_vals);
             return RFX_OK;
         }
     }
     for (int p = 0; p < passes; p++) {
         const int shift = 8 * p;
-        hipLaunchKernelGGL(k_hist<false>, dim3((unsigned)ntiles), dim3(ST), 0, ctx->stream, sk, n, shift,
-                           table.as<uint32_t>(), ntiles, nomap);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_hist<false>, dim3((unsigned)ntiles), dim3(ST), 0, sk, n, shift,
+                   table.as<uint32_t>(), ntiles, nomap);
         if (!inline_scan) RFX_TRY(exclusive_scan_u32_to_u64(ctx, table.as<uint32_t>(), offs.as<uint64_t>(), ntiles * 256));
-        hipLaunchKernelGGL(k_scatter<false>, dim3((unsigned)ntiles), dim3(ST), 0, ctx->stream, sk, sv, n, shift,
-                           inline_scan ? (const uint64_t *)nullptr : (const uint64_t *)offs.as<uint64_t>(), ntiles, dk, dv,
-                           (const uint32_t *)table.as<uint32_t>(), nomap);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_scatter<false>, dim3((unsigned)ntiles), dim3(ST), 0, sk, sv, n, shift,
+                   inline_scan ? (const uint64_t *)nullptr : offs.as<uint64_t>(), ntiles, dk, dv,
+                   table.as<uint32_t>(), nomap);
         uint64_t *tk = sk; sk = dk; dk = tk;
         uint32_t *tv = sv; sv = dv; dv = tv;
     }

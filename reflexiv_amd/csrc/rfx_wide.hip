@@ -211,7 +211,6 @@ __global__ void k_permute_wn(const uint64_t *__restrict__ aos, const int64_t *__
     ocnt[i] = cnt[s];
 }
 
-inline unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, ceil_div(n, 256)); }
 
 }  // namespace
 
@@ -224,9 +223,8 @@ int64_t kmers_per_read_w(int read_len, int k, int fc, int ec) { return nk_of_w(r
 int kmer_counts_per_read_w(rfx_ctx *ctx, const int64_t *d_read_off, int64_t n_reads, int k, int fc, int ec,
                            uint64_t *d_nk) {
     if (n_reads <= 0) return RFX_OK;
-    hipLaunchKernelGGL(k_nk_per_read_w, dim3(grid_for(n_reads)), dim3(256), 0, ctx->stream, d_read_off, n_reads, k, fc,
-                       ec, d_nk);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_nk_per_read_w, n_reads, d_read_off, n_reads, k, fc,
+                 ec, d_nk);
     return RFX_OK;
 }
 
@@ -237,35 +235,30 @@ int extract_w(rfx_ctx *ctx, const uint64_t *d_words, int wpr, const uint64_t *d_
     if (!d_kmer_off && aos && k / 32 + 1 == 2) {
         const int64_t total = n_reads * ceil_div(nk_uniform, WSEG);
         const int64_t blocks = std::min<int64_t>(ceil_div(total, 256), (int64_t)ctx->num_cu * 32);
-        hipLaunchKernelGGL(k_extract_w2_roll, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_words, wpr, nk_uniform,
-                           n_reads, k, fc, d_soa);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_extract_w2_roll, dim3((unsigned)blocks), dim3(256), 0, d_words, wpr, nk_uniform,
+                   n_reads, k, fc, d_soa);
         return RFX_OK;
     }
     if (!d_kmer_off) {
         const int64_t blocks = std::min<int64_t>(ceil_div(N, 256), (int64_t)ctx->num_cu * 32);
-        hipLaunchKernelGGL(k_extract_w_flat, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_words, wpr, nk_uniform, N, k,
-                           fc, d_soa, aos);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH(k_extract_w_flat, dim3((unsigned)blocks), dim3(256), 0, d_words, wpr, nk_uniform, N, k,
+                   fc, d_soa, aos);
         return RFX_OK;
     }
-    hipLaunchKernelGGL(k_extract_w, dim3(grid_for(n_reads * 64)), dim3(256), 0, ctx->stream, d_words, wpr, d_kmer_off,
-                       nk_uniform, n_reads, k, fc, d_soa, N, aos);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_extract_w, n_reads * 64, d_words, wpr, d_kmer_off,
+                 nk_uniform, n_reads, k, fc, d_soa, N, aos);
     return RFX_OK;
 }
 
 int aos_to_soa(rfx_ctx *ctx, const uint64_t *d_aos, int64_t n, int W, uint64_t *d_soa) {
     if (n <= 0) return RFX_OK;
-    hipLaunchKernelGGL(k_aos_to_soa, dim3(grid_for(n * W)), dim3(256), 0, ctx->stream, d_aos, n, W, d_soa);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_aos_to_soa, n * W, d_aos, n, W, d_soa);
     return RFX_OK;
 }
 
 int soa_to_aos(rfx_ctx *ctx, const uint64_t *d_soa, int64_t n, int W, uint64_t *d_aos) {
     if (n <= 0) return RFX_OK;
-    hipLaunchKernelGGL(k_soa_to_aos, dim3(grid_for(n * W)), dim3(256), 0, ctx->stream, d_soa, n, W, d_aos);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_soa_to_aos, n * W, d_soa, n, W, d_aos);
     return RFX_OK;
 }
 
@@ -303,31 +296,28 @@ int order_wide2(rfx_ctx *ctx, uint64_t *d_out_keys, int64_t *d_out_counts, int64
     ScopedTimer t(ctx, "sort");
     DevBuf soa, idx, idx2, keys, keys2, oaos, ocnt;
     RFX_HIP(soa.alloc((size_t)m * 8 * W, ctx->stream));
-    RFX_HIP(idx.alloc((size_t)m * 4, ctx->stream));
-    RFX_HIP(idx2.alloc((size_t)m * 4, ctx->stream));
-    RFX_HIP(keys.alloc((size_t)m * 8, ctx->stream));
-    RFX_HIP(keys2.alloc((size_t)m * 8, ctx->stream));
+    RFX_ALLOC(idx, uint32_t, m);
+    RFX_ALLOC(idx2, uint32_t, m);
+    RFX_ALLOC(keys, uint64_t, m);
+    RFX_ALLOC(keys2, uint64_t, m);
     RFX_TRY(aos_to_soa(ctx, d_out_keys, m, W, soa.as<uint64_t>()));
-    hipLaunchKernelGGL(k_iota, dim3(grid_for(m)), dim3(256), 0, ctx->stream, idx.as<uint32_t>(), m);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_iota, m, idx.as<uint32_t>(), m);
     for (int w = W - 1; w >= 0; w--) {
-        hipLaunchKernelGGL(k_gather_u64, dim3(grid_for(m)), dim3(256), 0, ctx->stream, soa.as<uint64_t>() + (int64_t)w * m,
-                           (const uint32_t *)idx.as<uint32_t>(), m, keys.as<uint64_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_gather_u64, m, soa.as<uint64_t>() + (int64_t)w * m,
+                     idx.as<uint32_t>(), m, keys.as<uint64_t>());
         RFX_TRY(sort_pairs(ctx, keys.as<uint64_t>(), idx.as<uint32_t>(), m, w == W - 1 ? 2 * res : 64, keys2.as<uint64_t>(),
                            idx2.as<uint32_t>()));
     }
     RFX_HIP(oaos.alloc((size_t)m * 8 * W, ctx->stream));
-    RFX_HIP(ocnt.alloc((size_t)m * 8, ctx->stream));
+    RFX_ALLOC(ocnt, int64_t, m);
     if (W == 2)
-        hipLaunchKernelGGL(k_permute_w2, dim3(grid_for(m)), dim3(256), 0, ctx->stream, (const uint64_t *)d_out_keys,
-                           (const int64_t *)d_out_counts, (const uint32_t *)idx.as<uint32_t>(), m, oaos.as<uint64_t>(),
-                           ocnt.as<int64_t>());
+        RFX_LAUNCH_N(k_permute_w2, m, d_out_keys,
+                     d_out_counts, idx.as<uint32_t>(), m, oaos.as<uint64_t>(),
+                     ocnt.as<int64_t>());
     else
-        hipLaunchKernelGGL(k_permute_wn, dim3(grid_for(m)), dim3(256), 0, ctx->stream, (const uint64_t *)d_out_keys,
-                           (const int64_t *)d_out_counts, (const uint32_t *)idx.as<uint32_t>(), m, W, oaos.as<uint64_t>(),
-                           ocnt.as<int64_t>());
-    RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_permute_wn, m, d_out_keys,
+                     d_out_counts, idx.as<uint32_t>(), m, W, oaos.as<uint64_t>(),
+                     ocnt.as<int64_t>());
     RFX_HIP(hipMemcpyAsync(d_out_keys, oaos.p, (size_t)m * 8 * W, hipMemcpyDeviceToDevice, ctx->stream));
     RFX_HIP(hipMemcpyAsync(d_out_counts, ocnt.p, (size_t)m * 8, hipMemcpyDeviceToDevice, ctx->stream));
     t.stop();
@@ -352,47 +342,41 @@ int count_filter_w(rfx_ctx *ctx, uint64_t *d_soa, int64_t N, int k, int min_cov,
     }
     if (N >= (1LL << 32)) { ctx->last_error = "k > 31 count: at most 2^32-1 instances per call"; return RFX_E_ARG; }
     DevBuf idx, idx2, keys, keys2, sorted, head, pos;
-    RFX_HIP(idx.alloc((size_t)N * 4, ctx->stream));
-    RFX_HIP(idx2.alloc((size_t)N * 4, ctx->stream));
-    RFX_HIP(keys.alloc((size_t)N * 8, ctx->stream));
-    RFX_HIP(keys2.alloc((size_t)N * 8, ctx->stream));
-    hipLaunchKernelGGL(k_iota, dim3(grid_for(N)), dim3(256), 0, ctx->stream, idx.as<uint32_t>(), N);
-    RFX_HIP(hipGetLastError());
+    RFX_ALLOC(idx, uint32_t, N);
+    RFX_ALLOC(idx2, uint32_t, N);
+    RFX_ALLOC(keys, uint64_t, N);
+    RFX_ALLOC(keys2, uint64_t, N);
+    RFX_LAUNCH_N(k_iota, N, idx.as<uint32_t>(), N);
     // least significant word first; every pass is stable, so the result is ordered by (w0, w1, ...)
     for (int w = W - 1; w >= 0; w--) {
-        hipLaunchKernelGGL(k_gather_u64, dim3(grid_for(N)), dim3(256), 0, ctx->stream, d_soa + (int64_t)w * N,
-                           (const uint32_t *)idx.as<uint32_t>(), N, keys.as<uint64_t>());
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_gather_u64, N, d_soa + (int64_t)w * N,
+                     idx.as<uint32_t>(), N, keys.as<uint64_t>());
         RFX_TRY(sort_pairs(ctx, keys.as<uint64_t>(), idx.as<uint32_t>(), N, w == W - 1 ? 2 * res : 64, keys2.as<uint64_t>(),
                            idx2.as<uint32_t>()));
     }
     keys.release(); keys2.release(); idx2.release();
-    RFX_HIP(sorted.alloc((size_t)N * W * 8, ctx->stream));
+    RFX_ALLOC(sorted, uint64_t, (size_t)N * W);
     for (int w = 0; w < W; w++) {
-        hipLaunchKernelGGL(k_gather_u64, dim3(grid_for(N)), dim3(256), 0, ctx->stream, d_soa + (int64_t)w * N,
-                           (const uint32_t *)idx.as<uint32_t>(), N, sorted.as<uint64_t>() + (int64_t)w * N);
-        RFX_HIP(hipGetLastError());
+        RFX_LAUNCH_N(k_gather_u64, N, d_soa + (int64_t)w * N,
+                     idx.as<uint32_t>(), N, sorted.as<uint64_t>() + (int64_t)w * N);
     }
-    RFX_HIP(head.alloc((size_t)N * 4, ctx->stream));
-    RFX_HIP(pos.alloc((size_t)(N + 1) * 8, ctx->stream));
-    hipLaunchKernelGGL(k_heads_w, dim3(grid_for(N)), dim3(256), 0, ctx->stream, (const uint64_t *)sorted.as<uint64_t>(), N, W,
-                       head.as<uint32_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_ALLOC(head, uint32_t, N);
+    RFX_ALLOC(pos, uint64_t, N + 1);
+    RFX_LAUNCH_N(k_heads_w, N, sorted.as<uint64_t>(), N, W,
+                 head.as<uint32_t>());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, head.as<uint32_t>(), pos.as<uint64_t>(), N));
     uint64_t D = 0;
     RFX_HIP(hipMemcpyAsync(&D, pos.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, ctx->stream));
     RFX_TRY(sync_checked(ctx));
     if (out_distinct) *out_distinct = (int64_t)D;
     DevBuf start, keep, opos;
-    RFX_HIP(start.alloc((size_t)(D + 1) * 8, ctx->stream));
-    RFX_HIP(keep.alloc((size_t)D * 4, ctx->stream));
-    RFX_HIP(opos.alloc((size_t)(D + 1) * 8, ctx->stream));
-    hipLaunchKernelGGL(k_starts_w, dim3(grid_for(N)), dim3(256), 0, ctx->stream, (const uint32_t *)head.as<uint32_t>(),
-                       (const uint64_t *)pos.as<uint64_t>(), N, start.as<uint64_t>());
-    RFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_keep_w, dim3(grid_for((int64_t)D)), dim3(256), 0, ctx->stream, (const uint64_t *)start.as<uint64_t>(),
-                       (int64_t)D, min_cov, max_cov, keep.as<uint32_t>());
-    RFX_HIP(hipGetLastError());
+    RFX_ALLOC(start, uint64_t, D + 1);
+    RFX_ALLOC(keep, uint32_t, D);
+    RFX_ALLOC(opos, uint64_t, D + 1);
+    RFX_LAUNCH_N(k_starts_w, N, head.as<uint32_t>(),
+                 pos.as<uint64_t>(), N, start.as<uint64_t>());
+    RFX_LAUNCH_N(k_keep_w, (int64_t)D, start.as<uint64_t>(),
+                 (int64_t)D, min_cov, max_cov, keep.as<uint32_t>());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, keep.as<uint32_t>(), opos.as<uint64_t>(), (int64_t)D));
     uint64_t M = 0;
     RFX_HIP(hipMemcpyAsync(&M, opos.as<uint64_t>() + D, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -400,10 +384,9 @@ int count_filter_w(rfx_ctx *ctx, uint64_t *d_soa, int64_t N, int k, int min_cov,
     *out_n = (int64_t)M;
     if ((int64_t)M > cap) return RFX_E_CAP;
     if (M == 0) return RFX_OK;
-    hipLaunchKernelGGL(k_emit_w, dim3(grid_for((int64_t)D)), dim3(256), 0, ctx->stream, (const uint64_t *)sorted.as<uint64_t>(),
-                       N, W, (const uint64_t *)start.as<uint64_t>(), (const uint32_t *)keep.as<uint32_t>(),
-                       (const uint64_t *)opos.as<uint64_t>(), (int64_t)D, cap, d_out_keys, d_out_counts);
-    RFX_HIP(hipGetLastError());
+    RFX_LAUNCH_N(k_emit_w, (int64_t)D, sorted.as<uint64_t>(),
+                 N, W, start.as<uint64_t>(), keep.as<uint32_t>(),
+                 opos.as<uint64_t>(), (int64_t)D, cap, d_out_keys, d_out_counts);
     return RFX_OK;
 }
 
