@@ -33,7 +33,7 @@
  *        output arrays are unspecified, nothing at or past `cap` is written;
  *      - text buffers (rfx_contigs_text, rfx_dev_assemble[_w], rfx_assemble_counts_w,
  *        rfx_assemble_reads, the sharded drivers, rfx_dedup_contigs / rfx_dedup_contig_text,
- *        rfx_dev_contigs_to_text, rfx_dev_fix2_to_text, rfx_dev_fix2_ends_text)
+ *        rfx_dev_contigs_to_text, rfx_dev_fix2_to_text, rfx_dev_fix2_ends_text, rfx_dev_endext_to_text)
  *        are filled up to `cap`: the bytes below it are unspecified (a prefix of the text),
  *        nothing at or past `cap` is written;
  *  - re-entrant per context; one context = one device + one HIP stream.
@@ -921,6 +921,60 @@ int rfx_dev_fix2_ends_text(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const i
                            int64_t *out_len);
 int rfx_fix2_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
                   int64_t *out_len, char *ends_out, int64_t ends_cap, int64_t *ends_len);
+
+/* The END EXTENSION of contigs from alignment rows (Assembly_intermediate/07EndExtend) on the same packed sets in
+ * HBM: P/ReflexivDSDynamicKmerMapping.java BEHIND its aligner (driver :305-347).  The caller runs any aligner on 06ContigEnds and hands
+ * over its rows "name \t start \t cigar \t seq" (RNAME, POS, CIGAR, SEQ of a SAM line; a seq that is exactly L, R or L-R is a repeat
+ * marker), as text in HBM in the form rfx_dev_dyn_binarize takes (d_text + d_row_off, a trailing "\n" or "\r\n" is not part of a row).  The
+ * input contigs are what rfx_dev_fix2_contigs returns (the set, d_left, d_right), so fix2 feeds this stage with no text in between;
+ * contig i is named Contig_<len[i]>_<left[i]>_<right[i]>_<i>, with -L or -R behind it for an end of 200 bases.
+ *   rfx_dev_endext_consensus  SAMString2ROW (:369-388: a row of fewer than 4 fields is skipped) + DSProcessSAMandExtendContigs (:564-994):
+ *                             per contig the two [300][4] pile-ups and their consensus (the highest count, a tie to the HIGHER code, at
+ *                             most 300 bases) as two packed contig sets of in.n entries each -- left: from the base next to the contig
+ *                             OUTWARDS, right: in read order -- and flags[i]: 1 = two or more left repeat markers, 2 = right
+ *   rfx_dev_endext_contigs    the union with 05FixingAgain, sort("ID") (:320-331), DSExtendContigs (:413-562) and the index and filter of
+ *                             zipWithIndex + TagStringContigRDDID (:1268-1286) without the text: the contigs of 07EndExtend in OUTPUT order
+ *                             (the byte order of the ID strings: Contig_100_ sorts ahead of Contig_99_) as a packed contig set of BASES
+ *                             ONLY, reversed left consensus || contig || right consensus, with per contig left_len / right_len (the
+ *                             lengths the ID carries: 3 more on a flagged side), flags, the new left / right (a flagged side's field
+ *                             becomes 1 where it was 1 or less), src_idx (the input contig) and new_idx (the position among ALL spliced
+ *                             contigs; only those of at least 2 max_k TEXT characters are in the set).  The literals "-1l" / "r1-" that
+ *                             the reference leaves in a flagged contig's text live in flags, not in the words
+ *   rfx_dev_endext_to_text    the rows ">Contig_<L>_<left>_<right>_<idx>_<ll>_<rl>_<new>,<sequence>\n" (L the ORIGINAL length, as in the
+ *                             reference), the literals at the two seams, byte for byte
+ *   rfx_endext_text           host form: the text of 05FixingAgain (row i must be Contig_<L>_<left>_<right>_<i>,<L bases of ACGT>: RFX_E_ARG
+ *                             otherwise) + the row text in, the text of 07EndExtend out; one upload each and one copy back
+ * DEVIATIONS, all stated.  (1) All alignment rows form ONE logical partition: every row of a contig is counted, in any order of the
+ * rows, so the stage takes no P (for P > 1 the reference cuts a contig's rows between partitions and the last part wins in an order
+ * Spark does not define).  (2) RFX_E_ARG for the set, nothing written, where the reference throws: a row that is no marker whose CIGAR is
+ * not ([0-9]+[A-Z=])+ (operations of up to 9 digits), whose start is no decimal int, or whose overhang would index outside seq.  (3) A
+ * row whose name is not the ID of the contig at its <idx> (L, left and right all equal, as Integer.toString writes them, one suffix at
+ * most) is ignored before anything else of it is read, as the reference's result ignores it.
+ * CAPACITIES, derived from the input.  consensus: cap_n >= in.n and cap_words >= 10 in.n for each of the two sets (a consensus has at
+ * most 300 bases = 10 words).  contigs: a spliced contig of cl + L + cr bases takes ceil((cl + L + cr) / 32) <= ceil(L / 32) + ceil(cl /
+ * 32) + ceil(cr / 32) words, so cap_n >= in.n and cap_words >= in.word_off[in.n] + 20 in.n always suffice (+ in.n more covers any other
+ * rounding).  A short output: RFX_E_CAP with need_n / need_words set and nothing written.  rfx_dev_endext_to_text follows the
+ * text-buffer rule: filled up to cap, nothing at or past it, RFX_E_CAP with *out_len = the need; d_text may have any alignment;
+ * rfx_endext_text with a short buffer writes nothing.  RFX_E_ARG, nothing written: the cases above; max_k outside 31..124; a null pointer;
+ * a set whose word_off and len disagree, a consensus of more than 300 bases, flags other than 0..3.  RFX_E_LIMIT: 2^31 rows or contigs, a
+ * contig of 2^30 bases.  n = 0 and n_rows = 0 are valid everywhere.  All run on the context's stream and return after it has drained. */
+typedef struct {
+    rfx_contigs_packed left, right;   /* in.n entries each; left: from the base next to the contig outwards      */
+    int32_t *flags;                   /* cap_n entries: 1 = left flagged, 2 = right flagged                       */
+} rfx_endext_consensus;               /* every pointer is a DEVICE pointer, the struct lives on the host          */
+typedef struct {
+    rfx_contigs_packed set;           /* bases only, in output order                                              */
+    int32_t *left, *right;            /* cap_n entries each, as every array below                                 */
+    int32_t *left_len, *right_len;    /* text characters of both consensus strings (3 more where flagged)        */
+    int32_t *flags, *src_idx, *new_idx;
+} rfx_endext_set;
+int rfx_dev_endext_consensus(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, const char *d_text,
+                             const int64_t *d_row_off, int64_t n_rows, rfx_endext_consensus *d_out);
+int rfx_dev_endext_contigs(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right,
+                           const rfx_endext_consensus *d_cons, int max_k, rfx_endext_set *d_out);
+int rfx_dev_endext_to_text(rfx_ctx *ctx, const rfx_endext_set *d_in, char *d_text, int64_t cap, int64_t *out_len);
+int rfx_endext_text(rfx_ctx *ctx, const char *contig_text, const int64_t *contig_off, int64_t n_contigs, const char *row_text, const int64_t *row_off,
+                    int64_t n_rows, int max_k, char *out, int64_t cap, int64_t *out_len);
 
 /* Synthetic reads: integer-only counter-based generator, bit-identical to
  * oracle/reflexiv_oracle.c orc_synth_*.  Writes packed reads straight into HBM. */

@@ -68,6 +68,17 @@ class CContigsPacked(C.Structure):
                 ("cap_words", C.c_int64), ("need_n", C.c_int64), ("need_words", C.c_int64)]
 
 
+class CEndextConsensus(C.Structure):
+    """rfx_endext_consensus: every pointer is a DEVICE pointer."""
+    _fields_ = [("left", CContigsPacked), ("right", CContigsPacked), ("flags", C.c_void_p)]
+
+
+class CEndextSet(C.Structure):
+    """rfx_endext_set: every pointer is a DEVICE pointer."""
+    _fields_ = [("set", CContigsPacked), ("left", C.c_void_p), ("right", C.c_void_p), ("left_len", C.c_void_p), ("right_len", C.c_void_p),
+                ("flags", C.c_void_p), ("src_idx", C.c_void_p), ("new_idx", C.c_void_p)]
+
+
 class CRecords(C.Structure):
     """rfx_records."""
     _fields_ = [("n", C.c_int64), ("key", C.c_void_p), ("marker", C.c_void_p), ("ext_off", C.c_void_p),
@@ -108,10 +119,12 @@ SYMBOLS = [
     "rfx_fix_default_params", "rfx_dev_fix_binarize", "rfx_dev_fix_contig_ends", "rfx_dev_fix_kmer_set", "rfx_dev_fix_fork_filter",
     "rfx_dev_fix_reflect", "rfx_dev_fix_run", "rfx_fix_text",
     "rfx_dev_fix2_binarize", "rfx_dev_fix2_run", "rfx_dev_fix2_contigs", "rfx_dev_fix2_to_text", "rfx_dev_fix2_ends_text", "rfx_fix2_text",
+    "rfx_dev_endext_consensus", "rfx_dev_endext_contigs", "rfx_dev_endext_to_text", "rfx_endext_text",
 ]
 
 # prototypes of the packed entry points (ctx, then as include/reflexiv_hip.h declares them)
 _PK, _HR, _CP, _KP, _RP, _FP, _I, _L, _P = "PK", "HR", "CP", "KP", "RP", "FP", C.c_int, C.c_int64, C.c_void_p
+_EC, _ES = "EC", "ES"
 _DYN_PACKED_ARGS = {
     "rfx_dev_dyn_pack": (_HR, _PK),
     "rfx_dev_dyn_unpack": (_PK, _HR),
@@ -154,6 +167,11 @@ _DYN_PACKED_ARGS = {
     "rfx_dev_fix2_to_text": (_CP, _P, _P, _P, _L, _P),
     "rfx_dev_fix2_ends_text": (_CP, _P, _P, _P, _L, _P),
     "rfx_fix2_text": (_P, _P, _L, _I, _FP, _P, _L, _P, _P, _L, _P),
+    # the end extension from alignment rows: a packed contig set and rows in, consensus sets, the spliced set and its text out
+    "rfx_dev_endext_consensus": (_CP, _P, _P, _P, _P, _L, _EC),
+    "rfx_dev_endext_contigs": (_CP, _P, _P, _EC, _I, _ES),
+    "rfx_dev_endext_to_text": (_ES, _P, _L, _P),
+    "rfx_endext_text": (_P, _P, _L, _P, _P, _L, _I, _P, _L, _P),
     # the packed contig set of the de-duplication (rfx_contigs_packed)
     "rfx_dev_contigs_pack": (_P, _P, _L, _CP),
     "rfx_dev_contigs_unpack": (_CP, _P, _L, _P, _L, _P),
@@ -208,7 +226,8 @@ def lib():
                 fn.restype = C.c_int
                 fn.argtypes = [C.c_void_p] + [C.POINTER(CDynPacked) if a == _PK else C.POINTER(CDynRecords) if a == _HR else
                                               C.POINTER(CContigsPacked) if a == _CP else C.POINTER(CKsortParams) if a == _KP else C.POINTER(CReduceParams) if a == _RP else
-                                              C.POINTER(CFixParams) if a == _FP else a for a in _DYN_PACKED_ARGS[name]]
+                                              C.POINTER(CFixParams) if a == _FP else C.POINTER(CEndextConsensus) if a == _EC else
+                                              C.POINTER(CEndextSet) if a == _ES else a for a in _DYN_PACKED_ARGS[name]]
                 continue
             if name == "rfx_dyn_attribute_unpack":
                 fn.restype = None

@@ -234,6 +234,51 @@ class ContigsPacked:
         return (self.words_t[:self.words].cpu().numpy().view(np.uint64), self.word_off[:n + 1].cpu().numpy(), self.len[:n].cpu().numpy())
 
 
+class EndextConsensus:
+    """The two consensus sets of the end extension (rfx_endext_consensus) over torch tensors in HBM: `left` and `right` are
+    ContigsPacked of one entry per input contig (left: from the base next to the contig outwards), `flags` int32 (1 = left flagged,
+    2 = right flagged)."""
+
+    def __init__(self, cap_n: int, cap_words_left: int = None, cap_words_right: int = None, device="cuda"):
+        import torch
+        self.left = ContigsPacked(cap_n, 10 * cap_n if cap_words_left is None else cap_words_left, device)
+        self.right = ContigsPacked(cap_n, 10 * cap_n if cap_words_right is None else cap_words_right, device)
+        self.flags = torch.empty(max(1, int(cap_n)), dtype=torch.int32, device=device)
+
+    def _c(self) -> "_lib.CEndextConsensus":
+        c = _lib.CEndextConsensus()
+        c.left, c.right, c.flags = self.left._c(), self.right._c(), self.flags.data_ptr()
+        return c
+
+
+class EndextSet:
+    """The contigs of 07EndExtend in output order (rfx_endext_set) over torch tensors in HBM: `set` is a ContigsPacked of BASES ONLY
+    (reversed left consensus || contig || right consensus), the int32 arrays hold per contig the new left / right, the lengths the ID
+    carries, the flags, the input contig and the new index."""
+    ARRAYS = ("left", "right", "left_len", "right_len", "flags", "src_idx", "new_idx")
+
+    def __init__(self, cap_n: int, cap_words: int, device="cuda"):
+        import torch
+        self.set = ContigsPacked(cap_n, cap_words, device)
+        for a in self.ARRAYS:
+            setattr(self, a, torch.empty(max(1, int(cap_n)), dtype=torch.int32, device=device))
+
+    @property
+    def n(self) -> int:
+        return self.set.n
+
+    def _c(self) -> "_lib.CEndextSet":
+        c = _lib.CEndextSet()
+        c.set = self.set._c()
+        for a in self.ARRAYS:
+            setattr(c, a, getattr(self, a).data_ptr())
+        return c
+
+    def host(self):
+        """{array name: numpy int32 of the n entries in use}"""
+        return {a: getattr(self, a)[:self.n].cpu().numpy() for a in self.ARRAYS}
+
+
 def as_records(r) -> Records:
     """Accept any object with key/marker/ext_off/ext/left/right arrays (e.g. the oracle's Records)."""
     return Records(np.ascontiguousarray(r.key, np.uint64), np.ascontiguousarray(r.marker, np.int32),
@@ -1242,6 +1287,61 @@ class Reflexiv:
         return tuple(self._host_text_call("rfx_fix2_text", [cap1, cap2], lambda o, c, ln: self.L.rfx_fix2_text(
             self.ctx, text, off.ctypes.data, n_rows, int(P), C.byref(params), o[0].ctypes.data, c[0], C.addressof(ln[0]), o[1].ctypes.data, c[1],
             C.addressof(ln[1]))))
+
+    # ---- the end extension of contigs from alignment rows (07EndExtend) on packed sets (rfx_dev_endext_*)
+    def endext_consensus(self, c: "ContigsPacked", d_left, d_right, d_text, d_row_off, out: "EndextConsensus" = None) -> "EndextConsensus":
+        """rfx_dev_endext_consensus: the contigs rfx_dev_fix2_contigs returns + alignment rows "name \\t start \\t cigar \\t seq" (torch
+        uint8 tensor in HBM + int64 row offsets, n_rows + 1) -> the consensus of both ends of every contig, and its flags"""
+        ci = c._c()
+        n_rows = int(d_row_off.numel()) - 1
+        out = out or EndextConsensus(c.n, device=c.word_off.device)
+        while True:
+            co = out._c()
+            t0 = time.perf_counter()
+            st = self.L.rfx_dev_endext_consensus(self.ctx, C.byref(ci), d_left.data_ptr(), d_right.data_ptr(), d_text.data_ptr(), d_row_off.data_ptr(),
+                                                 n_rows, C.byref(co))
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
+            if st == RFX_E_CAP:
+                out = EndextConsensus(max(out.left.cap_n, int(co.left.need_n)), max(out.left.cap_words, int(co.left.need_words)),
+                                      max(out.right.cap_words, int(co.right.need_words)), c.word_off.device)
+                continue
+            self._check(st, "rfx_dev_endext_consensus")
+            out.left.n, out.right.n = int(co.left.n), int(co.right.n)
+            return out
+
+    def endext_contigs(self, c: "ContigsPacked", d_left, d_right, cons: "EndextConsensus", max_k: int, out: "EndextSet" = None) -> "EndextSet":
+        """rfx_dev_endext_contigs: the splice and the order -> the contigs of 07EndExtend, in output order, with their arrays"""
+        ci, cc = c._c(), cons._c()
+        out = out or EndextSet(c.n, c.words + 21 * c.n, c.word_off.device)
+        while True:
+            co = out._c()
+            t0 = time.perf_counter()
+            st = self.L.rfx_dev_endext_contigs(self.ctx, C.byref(ci), d_left.data_ptr(), d_right.data_ptr(), C.byref(cc), int(max_k), C.byref(co))
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
+            if st == RFX_E_CAP:
+                out = EndextSet(max(out.set.cap_n, int(co.set.need_n)), max(out.set.cap_words, int(co.set.need_words)), c.word_off.device)
+                continue
+            self._check(st, "rfx_dev_endext_contigs")
+            out.set.n = int(co.set.n)
+            return out
+
+    def endext_to_text(self, s: "EndextSet", d_text=None):
+        """rfx_dev_endext_to_text -> (torch uint8 tensor in HBM holding the rows of 07EndExtend, its length)"""
+        import torch
+        ci = s._c()
+        if d_text is None:
+            d_text = torch.empty(max(1, 128 * s.n + 32 * s.set.words + 64), dtype=torch.uint8, device=s.set.word_off.device)
+        return self._dev_text_call("rfx_dev_endext_to_text", d_text, lambda t, ln: self.L.rfx_dev_endext_to_text(
+            self.ctx, C.byref(ci), t.data_ptr(), int(t.numel()), C.addressof(ln)))
+
+    def endext_text(self, contig_text: bytes, row_text: bytes, max_k: int) -> bytes:
+        """rfx_endext_text: the rows of 05FixingAgain and the alignment rows (bytes, one row per line) -> the rows of 07EndExtend"""
+        ct, rt = bytes(contig_text), bytes(row_text)
+        offc, nc = self._row_offsets(ct)
+        offr, nr = self._row_offsets(rt)
+        cap = len(ct) + 700 * nc + 64
+        return self._host_text_call("rfx_endext_text", [cap], lambda o, c, ln: self.L.rfx_endext_text(
+            self.ctx, ct, offc.ctypes.data, nc, rt, offr.ctypes.data, nr, int(max_k), o[0].ctypes.data, c[0], C.addressof(ln[0])))[0]
 
     # ------------------------------------------------ f-4: contig RC de-duplication
     def dedup_contigs(self, contigs, min_contig=500):

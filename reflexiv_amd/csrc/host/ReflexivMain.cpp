@@ -482,6 +482,37 @@ void ReflexivMain::contigFixingRoundTwo(const std::string &csvText, int partitio
     *contigRows = std::move(o1); *contigEnds = std::move(o2);
 }
 
+std::string ReflexivMain::contigEndExtend(const std::string &contigText, const std::string &samText) {
+    std::string contigs, lines, rows;
+    std::vector<int64_t> coff, loff, roff(1, 0);
+    rowsOf(contigText, contigs, coff);
+    rowsOf(samText, lines, loff);
+    for (size_t i = 0; i + 1 < loff.size(); i++) {
+        const size_t b = (size_t)loff[i], e = (size_t)loff[i + 1];
+        std::vector<size_t> tabs;
+        for (size_t p = b; p < e; p++) if (lines[p] == '\t') tabs.push_back(p);
+        if (tabs.size() >= 10) {                                  // a full SAM line: RNAME, POS, CIGAR, SEQ
+            auto field = [&](size_t f) { return lines.substr(tabs[f - 1] + 1, tabs[f] - tabs[f - 1] - 1); };
+            if (lines[b] == '@' || field(2) == "*") continue;
+            rows += field(2) + "\t" + field(3) + "\t" + field(5) + "\t" + field(9);
+        } else {
+            rows.append(lines, b, e - b);
+        }
+        roff.push_back((int64_t)rows.size());
+    }
+    const int64_t n = (int64_t)coff.size() - 1, nr = (int64_t)roff.size() - 1;
+    std::string out(contigs.size() + 700 * (size_t)n + 64, '\0');
+    int64_t len = 0;
+    for (;;) {
+        const int st = rfx_endext_text(ctx, contigs.data(), coff.data(), n, rows.data(), roff.data(), nr, lastKmerOfList(), out.data(), (int64_t)out.size(), &len);
+        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
+        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_endext_text: ") + rfx_last_error(ctx));
+        break;
+    }
+    out.resize((size_t)len);
+    return out;
+}
+
 std::string ReflexivMain::dedupContigText(const std::string &contigText) {
     std::string out(contigText.size() + 4096, '\0');
     int64_t len = 0, nc = 0;

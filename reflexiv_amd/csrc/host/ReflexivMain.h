@@ -172,6 +172,11 @@ public:
     // 04Fixing -> the rows "ID,contig" of Assembly_intermediate/05FixingAgain and the FASTA of contig ends of 06ContigEnds.  One call
     // (rfx_fix2_text): everything between on the device.  maxKmerSize is the last k of the k list.
     void contigFixingRoundTwo(const std::string &csvText, int partitions, std::string *contigRows, std::string *contigEnds);
+    // ReflexivDSDynamicKmerMapping.assemblyFromKmer BEHIND its aligner (P/ReflexivDSDynamicKmerMapping.java:305-347) -- `endextend`: the
+    // rows of 05FixingAgain and the alignment rows "contig \t start \t cigar \t seq" of any aligner run on 06ContigEnds -> the rows of
+    // Assembly_intermediate/07EndExtend.  A line of 11 fields or more is a full SAM line: header and `*` lines are skipped, fields 3, 4, 6
+    // and 10 taken (the commented awk of :1189).  One call (rfx_endext_text).  maxKmerSize is the last k of the k list.
+    std::string contigEndExtend(const std::string &contigText, const std::string &samText);
     int lastKmerOfList() const;                      // param.kmerListInt[length - 1]
 
     rfx_ctx *ctx = nullptr;

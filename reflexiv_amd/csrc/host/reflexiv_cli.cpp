@@ -4,7 +4,8 @@
 // Count_<K2>_sorted, or Count_<K2>_reduced when K2 is the last k of the list), `reflexiv_host reduce -kmerc DIR -klist ... -partition P
 // -outfile O` (DIR/Count_<k> of every k of the list: each through `sort`, then the pairs in the list's order),
 // `reflexiv_host fixing -kmerc ITERATION_OUT [-klist ...] -partition P -outfile O` (O/Assembly_intermediate/04Fixing),
-// `reflexiv_host fixing2 -kmerc O/Assembly_intermediate/04Fixing [-klist ...] -partition P -outfile O` (05FixingAgain and 06ContigEnds)
+// `reflexiv_host fixing2 -kmerc O/Assembly_intermediate/04Fixing [-klist ...] -partition P -outfile O` (05FixingAgain and 06ContigEnds),
+// `reflexiv_host endextend -kmerc O/Assembly_intermediate/05FixingAgain -sam ROWS [-klist ...] -outfile O` (07EndExtend)
 // the two launcher sub-commands of bin/reflexiv:252-271 that reach the hot path
 // (M/Main.java:59-79, M/MainOfCounter.java:60-80), on one MI355X instead of spark-submit.
 #include <zlib.h>
@@ -38,7 +39,8 @@ int main(int argc, char **argv) {
                                    "       reflexiv_host reduce -kmerc SHORT -kmerc2 LONG -kmer K1 -kmer2 K2 [-klist ...] -partition P -outfile DIR\n"
                                    "       reflexiv_host reduce -kmerc COUNTS_DIR -klist K1,K2,... -partition P -outfile DIR\n"
                                    "       reflexiv_host fixing -kmerc ITERATION_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"
-                                   "       reflexiv_host fixing2 -kmerc FIXING_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"; return 2; }
+                                   "       reflexiv_host fixing2 -kmerc FIXING_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"
+                                   "       reflexiv_host endextend -kmerc FIXING_AGAIN_OUT -sam ROWS [-klist 23,31,...,95] -outfile DIR\n"; return 2; }
         std::string cmd = argv[1];
         std::vector<std::string> args(argv + 2, argv + argc);
         reflexiv::DefaultParam param = reflexiv::importCommandLine(args);
@@ -56,6 +58,8 @@ int main(int argc, char **argv) {
             throw std::runtime_error("fixing needs -kmerc ITERATION_OUT [-klist 23,31,...] -partition P [-maxiter M -scramble S] -outfile DIR");
         if (cmd == "fixing2" && (param.inputKmerPath.empty() || param.outputPath.empty()))
             throw std::runtime_error("fixing2 needs -kmerc FIXING_OUT [-klist 23,31,...] -partition P [-maxiter M -scramble S] -outfile DIR");
+        if (cmd == "endextend" && (param.inputKmerPath.empty() || param.inputSamPath.empty() || param.outputPath.empty()))
+            throw std::runtime_error("endextend needs -kmerc FIXING_AGAIN_OUT -sam ROWS [-klist 23,31,...] -outfile DIR");
         if (param.outputPath.empty()) throw std::runtime_error("-outfile is required");
         if (param.inputFqPath.empty() && param.inputKmerPath.empty()) throw std::runtime_error("-fastq or -kmerc is required");
         auto read_all = [&](const std::string &paths) {
@@ -175,6 +179,13 @@ int main(int argc, char **argv) {
                 std::ofstream(d + "/_SUCCESS", std::ios::binary);
             }
             return 0;
+        } else if (cmd == "endextend") {
+            // Pipelines.java:1065-1085 behind the aligner: the rows of 05FixingAgain and the alignment rows (contig, start, cigar, seq -- or
+            // full SAM lines) -> 07EndExtend; maxKmerSize is the last k of the list
+            if (m.lastKmerOfList() < 31 || m.lastKmerOfList() > 124) throw std::runtime_error("endextend: the last k of -klist must be 31..124");
+            out = m.contigEndExtend(read_all(param.inputKmerPath), read_all(param.inputSamPath));
+            dir += "/Assembly_intermediate"; mkdir(dir.c_str(), 0755);
+            dir += "/07EndExtend"; mkdir(dir.c_str(), 0755);
         } else if (cmd == "counter") {
             // --resident at k = 33..100 (not 64 or 96): the same rows through the device count of the packed reads
             out = param.resident && param.kmerSize >= 33 && param.kmerSize % 32 != 0 ? m.counterResident(read_all(param.inputFqPath))
@@ -182,7 +193,7 @@ int main(int argc, char **argv) {
             dir += "/Count_" + std::to_string(param.kmerSize);               // P/ReflexivDataFrameCounter.java:222-233
             mkdir(dir.c_str(), 0755);
         } else throw std::runtime_error("unknown command " + cmd);
-        std::ofstream(dir + (cmd == "counter" || cmd == "sort" || cmd == "firstfour" || cmd == "iteration" || cmd == "fixing" ? "/part-00000.csv" : "/part-00000"), std::ios::binary) << out;   // saveAsTextFile / csv
+        std::ofstream(dir + (cmd == "counter" || cmd == "sort" || cmd == "firstfour" || cmd == "iteration" || cmd == "fixing" || cmd == "endextend" ? "/part-00000.csv" : "/part-00000"), std::ios::binary) << out;   // saveAsTextFile / csv
         std::ofstream(dir + "/_SUCCESS", std::ios::binary);
         return 0;
     } catch (const std::exception &e) {

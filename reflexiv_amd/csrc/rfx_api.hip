@@ -1674,3 +1674,116 @@ int rfx_fix2_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_
 } RFX_API_CATCH(ctx)
 
 }  // extern "C"
+
+// ---- the end extension of contigs from alignment rows (rfx_endext.hip) -------------------------------------------
+namespace {
+bool ee_set_ok(const rfx_endext_set *s) {
+    return s && fx2_contigs_ok(&s->set) && s->left && s->right && s->left_len && s->right_len && s->flags && s->src_idx && s->new_idx;
+}
+bool ee_cons_ok(const rfx_endext_consensus *c) { return c && fx2_contigs_ok(&c->left) && fx2_contigs_ok(&c->right) && c->flags; }
+bool ee_max_k(rfx_ctx *ctx, int max_k) {
+    if (max_k >= 31 && max_k <= 124) return true;
+    ctx->last_error = "end extension: max_k must be 31..124";
+    return false;
+}
+}  // namespace
+
+extern "C" {
+
+// SAMString2ROW (:369-388) + DSProcessSAMandExtendContigs (:564-994) of P/ReflexivDSDynamicKmerMapping.java
+int rfx_dev_endext_consensus(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, const char *d_text,
+                             const int64_t *d_row_off, int64_t n_rows, rfx_endext_consensus *d_out) try {
+    if (!ctx || !fx2_contigs_ok(d_in) || d_in->n < 0 || (d_in->n > 0 && (!d_left || !d_right)) || !text_rows_ok(d_text, d_row_off, n_rows) ||
+        !ee_cons_ok(d_out))
+        return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    const Fx2View v{d_in->n, d_in->words, d_in->word_off, d_in->len, d_left, d_right};
+    EeConsPlan plan;
+    RFX_TRY(ee_consensus_plan(ctx, v, d_text, d_row_off, n_rows, plan));
+    d_out->left.need_n = d_out->right.need_n = plan.n;
+    d_out->left.need_words = plan.lwords; d_out->right.need_words = plan.rwords;
+    if (plan.n > d_out->left.cap_n || plan.n > d_out->right.cap_n || plan.lwords > d_out->left.cap_words || plan.rwords > d_out->right.cap_words)
+        return RFX_E_CAP;                                           // (nothing written)
+    RFX_TRY(ee_consensus_fill(ctx, plan, EeConsOut{d_out->left.words, d_out->left.word_off, d_out->left.len, d_out->right.words,
+                                                   d_out->right.word_off, d_out->right.len, d_out->flags}));
+    d_out->left.n = d_out->right.n = plan.n;
+    return sync_checked(ctx);
+} RFX_API_CATCH(ctx)
+
+// the union, sort("ID") (:320-331), DSExtendContigs (:413-562), the index and filter of TagStringContigRDDID (:1268-1286)
+int rfx_dev_endext_contigs(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right,
+                           const rfx_endext_consensus *d_cons, int max_k, rfx_endext_set *d_out) try {
+    if (!ctx || !fx2_contigs_ok(d_in) || d_in->n < 0 || (d_in->n > 0 && (!d_left || !d_right)) || !ee_cons_ok(d_cons) || d_cons->left.n != d_in->n ||
+        d_cons->right.n != d_in->n || !ee_set_ok(d_out) || !ee_max_k(ctx, max_k))
+        return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    const Fx2View v{d_in->n, d_in->words, d_in->word_off, d_in->len, d_left, d_right};
+    const EeConsIn c{d_cons->left.words, d_cons->left.word_off, d_cons->left.len, d_cons->right.words, d_cons->right.word_off, d_cons->right.len,
+                     d_cons->flags};
+    EePlan plan;
+    RFX_TRY(ee_contigs_plan(ctx, v, c, max_k, plan));
+    d_out->set.need_n = plan.m; d_out->set.need_words = plan.words;
+    if (plan.m > d_out->set.cap_n || plan.words > d_out->set.cap_words) return RFX_E_CAP;       // (nothing written)
+    RFX_TRY(ee_contigs_fill(ctx, v, c, plan, EeSetOut{d_out->set.words, d_out->set.word_off, d_out->set.len, d_out->left, d_out->right, d_out->left_len,
+                                                      d_out->right_len, d_out->flags, d_out->src_idx, d_out->new_idx}));
+    d_out->set.n = plan.m;
+    return sync_checked(ctx);
+} RFX_API_CATCH(ctx)
+
+// zipWithIndex + TagStringContigRDDID (:1268-1286): the rows of 07EndExtend
+int rfx_dev_endext_to_text(rfx_ctx *ctx, const rfx_endext_set *d_in, char *d_text, int64_t cap, int64_t *out_len) try {
+    if (!ctx || !ee_set_ok(d_in) || d_in->set.n < 0 || !out_len || cap < 0 || (cap > 0 && !d_text)) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    const EeSetIn s{d_in->set.n, d_in->set.words, d_in->set.word_off, d_in->set.len, d_in->left, d_in->right, d_in->left_len, d_in->right_len,
+                    d_in->flags, d_in->src_idx, d_in->new_idx};
+    int64_t total = 0;
+    RFX_TRY(ee_text(ctx, s, d_text, cap, &total, nullptr));
+    *out_len = total;
+    return total > cap ? RFX_E_CAP : RFX_OK;
+} RFX_API_CATCH(ctx)
+
+// host form of the driver behind the aligner (:305-347): the text of 05FixingAgain and the alignment rows in, 07EndExtend out;
+// everything between packed and in HBM: one upload each, consensus, splice and order, the text, one copy back
+int rfx_endext_text(rfx_ctx *ctx, const char *contig_text, const int64_t *contig_off, int64_t n_contigs, const char *row_text, const int64_t *row_off,
+                    int64_t n_rows, int max_k, char *out, int64_t cap, int64_t *out_len) try {
+    if (!ctx || !text_rows_ok(contig_text, contig_off, n_contigs) || !text_rows_ok(row_text, row_off, n_rows) || !out_len || cap < 0 || (cap > 0 && !out) ||
+        !ee_max_k(ctx, max_k))
+        return RFX_E_ARG;
+    if (n_contigs >= ((int64_t)1 << 31) || n_rows >= ((int64_t)1 << 31)) {       // (before an offset is read or a byte uploaded)
+        ctx->last_error = "end extension: 2^31 rows or contigs, or more";
+        return RFX_E_LIMIT;
+    }
+    RFX_HIP(hipSetDevice(ctx->device));
+    DevBuf d_ct, d_co, d_rt, d_ro, w, woff, len, left, right, d_rows;
+    RFX_TRY(dyn_upload_text(ctx, contig_text, contig_off, n_contigs, d_ct, d_co));
+    RFX_TRY(dyn_upload_text(ctx, row_text, row_off, n_rows, d_rt, d_ro));
+    RFX_TRY(ee_contigs_from_rows(ctx, (const char *)d_ct.p, d_co.as<int64_t>(), n_contigs, w, woff, len, left, right));
+    const Fx2View v{n_contigs, w.as<uint64_t>(), woff.as<int64_t>(), len.as<int64_t>(), left.as<int32_t>(), right.as<int32_t>()};
+    EeConsPlan cp;
+    RFX_TRY(ee_consensus_plan(ctx, v, (const char *)d_rt.p, d_ro.as<int64_t>(), n_rows, cp));
+    const size_t n1 = (size_t)std::max<int64_t>(n_contigs, 1);
+    DevBuf lw, lwoff, llen, rw, rwoff, rlen, cflags;
+    RFX_ALLOC(lw, uint64_t, std::max<int64_t>(cp.lwords, 1)); RFX_ALLOC(lwoff, int64_t, n1 + 1); RFX_ALLOC(llen, int64_t, n1);
+    RFX_ALLOC(rw, uint64_t, std::max<int64_t>(cp.rwords, 1)); RFX_ALLOC(rwoff, int64_t, n1 + 1); RFX_ALLOC(rlen, int64_t, n1);
+    RFX_ALLOC(cflags, int32_t, n1);
+    RFX_TRY(ee_consensus_fill(ctx, cp, EeConsOut{lw.as<uint64_t>(), lwoff.as<int64_t>(), llen.as<int64_t>(), rw.as<uint64_t>(), rwoff.as<int64_t>(),
+                                                 rlen.as<int64_t>(), cflags.as<int32_t>()}));
+    const EeConsIn c{lw.as<uint64_t>(), lwoff.as<int64_t>(), llen.as<int64_t>(), rw.as<uint64_t>(), rwoff.as<int64_t>(), rlen.as<int64_t>(),
+                     cflags.as<int32_t>()};
+    EePlan plan;
+    RFX_TRY(ee_contigs_plan(ctx, v, c, max_k, plan));
+    const size_t m1 = (size_t)std::max<int64_t>(plan.m, 1);
+    DevBuf ow, owoff, olen, o32;
+    RFX_ALLOC(ow, uint64_t, std::max<int64_t>(plan.words, 1)); RFX_ALLOC(owoff, int64_t, m1 + 1); RFX_ALLOC(olen, int64_t, m1);
+    RFX_ALLOC(o32, int32_t, 7 * m1);
+    int32_t *a = o32.as<int32_t>();
+    RFX_TRY(ee_contigs_fill(ctx, v, c, plan, EeSetOut{ow.as<uint64_t>(), owoff.as<int64_t>(), olen.as<int64_t>(), a, a + m1, a + 2 * m1, a + 3 * m1,
+                                                      a + 4 * m1, a + 5 * m1, a + 6 * m1}));
+    const EeSetIn s{plan.m, ow.as<uint64_t>(), owoff.as<int64_t>(), olen.as<int64_t>(), a, a + m1, a + 2 * m1, a + 3 * m1, a + 4 * m1, a + 5 * m1,
+                    a + 6 * m1};
+    int64_t total = 0;
+    RFX_TRY(ee_text(ctx, s, nullptr, 0, &total, &d_rows));
+    return text_to_host(ctx, {{d_rows, total, out, cap, out_len}}, false);
+} RFX_API_CATCH(ctx)
+
+}  // extern "C"

@@ -415,6 +415,25 @@ int rfx::dyn_sort(rfx_ctx *ctx, const DynDev &in, int P, DynDev &out, DevBuf &d_
                out.key_len.as<uint8_t>(), n, P, d_ps.as<int64_t>());
     return RFX_OK;
 }
+namespace {
+__global__ __launch_bounds__(256) void k_dyn_iota(uint32_t *__restrict__ perm, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) perm[i] = (uint32_t)i;
+}
+}  // namespace
+// a stable sort of n < 2^32 items by a key of W 64-bit words held as W columns of n entries (word j of item i = d_cols[j n + i], the
+// most significant word first): d_perm[q] = the item at position q.  LSD over the columns, as dyn_sort runs over its blocks
+int rfx::sort_columns(rfx_ctx *ctx, const uint64_t *d_cols, int W, int64_t n, uint32_t *d_perm) {
+    if (n == 0) return RFX_OK;
+    DevBuf tk, tv, keys;
+    RFX_ALLOC(tk, uint64_t, n); RFX_ALLOC(tv, uint32_t, n); RFX_ALLOC(keys, uint64_t, n);
+    RFX_LAUNCH_N(k_dyn_iota, n, d_perm, n);
+    for (int j = W - 1; j >= 0; j--) {
+        RFX_LAUNCH_N(k_dyn_gather_u64, n, d_cols + (int64_t)j * n, d_perm, n, keys.as<uint64_t>());
+        RFX_TRY(sort_pairs(ctx, keys.as<uint64_t>(), d_perm, n, 64, tk.as<uint64_t>(), tv.as<uint32_t>()));
+    }
+    return sync_checked(ctx);                                     // (the scratch above is read until here)
+}
 // one pass over sorted records: in (sorted), d_ps -> out, d_out_ps (optional)
 int rfx::dyn_pass(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, int P, uint32_t lmin, int stage, int start_iteration, int start_marker,
                   DynDev &out, int64_t *d_out_ps) {

@@ -173,12 +173,8 @@ __global__ __launch_bounds__(256) void k_fx2_text_fill(const uint64_t *__restric
     const char first = fx2_byte(r, ends, q, &t, &run);
     if (whole && first == 0 && run >= 16) {
         // 16 bases out of one or two words
-        const int wi = t >> 5, sh = (t & 31) * 2;
-        uint64_t x = r.w[wi] << sh;
-        if (sh > 32) x |= r.w[wi + 1] >> (64 - sh);
-        const uint32_t y = (uint32_t)(x >> 32);
-#pragma unroll
-        for (int j = 0; j < 16; j++) o[j >> 2] |= pk_letter((y >> (30 - 2 * j)) & 3u) << (8 * (j & 3));
+        const Pk16 y = pk_letters16(r.w, t);
+        o[0] = y.a; o[1] = y.b; o[2] = y.c; o[3] = y.d;
     } else {
 #pragma unroll
         for (int j = 0; j < 16; j++) {

@@ -522,6 +522,8 @@ int text_to_host(rfx_ctx *ctx, std::initializer_list<TextOut> outs, bool fill_to
 #pragma GCC visibility pop
 // sort("k-1") + the cut into P logical partitions: in -> out (sorted), d_ps[P + 1]; *lmin = the shortest key
 int dyn_sort(rfx_ctx *ctx, const DynDev &in, int P, DynDev &out, DevBuf &d_ps, uint32_t *lmin);
+// a stable sort by a key of W 64-bit words in W columns of n entries, the most significant first: d_perm[q] = the item at position q
+int sort_columns(rfx_ctx *ctx, const uint64_t *d_cols, int W, int64_t n, uint32_t *d_perm);
 // a view of the caller's input set (nothing copied, nothing freed) / the result into the caller's arrays (both capacities are
 // checked before anything is copied) / host text rows -> HBM with offsets relative to the first row
 int dyn_borrow(rfx_ctx *ctx, const rfx_dyn_packed *p, DynDev &d);
@@ -553,5 +555,25 @@ int fx2_contigs_plan(rfx_ctx *ctx, const DynDev &in, int max_k, Fx2Plan &plan);
 int fx2_contigs_fill(rfx_ctx *ctx, const DynDev &in, const Fx2Plan &plan, uint64_t *d_words, int64_t *d_word_off, int64_t *d_len, int32_t *d_left,
                      int32_t *d_right);
 int fx2_text(rfx_ctx *ctx, const Fx2View &v, int ends, char *d_text, int64_t cap, int64_t *total, DevBuf *own);
+
+
+// ---- rfx_endext.hip : the end extension of contigs from alignment rows; its entry points are in rfx_api.hip
+// the consensus of both ends of every contig of a set (Fx2View: a packed contig set with left / right) from text rows "name \t start
+// \t cigar \t seq" in HBM: what both consensus sets take (plan), then into arrays that hold it (fill) / the order of the IDs and what
+// the spliced set takes (plan), then reversed left || contig || right in output order (fill) / the rows of 07EndExtend (own: a buffer of
+// the library's) / the rows of 05FixingAgain in HBM -> a packed contig set with left / right in the library's buffers
+struct EeConsPlan { int64_t n = 0, lwords = 0, rwords = 0; DevBuf cons, clen, cflags, offl, offr; };
+struct EeConsOut { uint64_t *lw; int64_t *lwoff, *llen; uint64_t *rw; int64_t *rwoff, *rlen; int32_t *flags; };
+struct EeConsIn { const uint64_t *lw; const int64_t *lwoff, *llen; const uint64_t *rw; const int64_t *rwoff, *rlen; const int32_t *flags; };
+struct EePlan { int64_t m = 0, words = 0; DevBuf perm, keep, nidx, opos, woff; };
+struct EeSetOut { uint64_t *w; int64_t *woff, *len; int32_t *left, *right, *left_len, *right_len, *flags, *src_idx, *new_idx; };
+struct EeSetIn { int64_t n; const uint64_t *w; const int64_t *woff, *len; const int32_t *left, *right, *left_len, *right_len, *flags, *src_idx, *new_idx; };
+int ee_consensus_plan(rfx_ctx *ctx, const Fx2View &in, const char *d_text, const int64_t *d_row_off, int64_t n_rows, EeConsPlan &plan);
+int ee_consensus_fill(rfx_ctx *ctx, const EeConsPlan &plan, const EeConsOut &o);
+int ee_contigs_plan(rfx_ctx *ctx, const Fx2View &in, const EeConsIn &c, int max_k, EePlan &plan);
+int ee_contigs_fill(rfx_ctx *ctx, const Fx2View &in, const EeConsIn &c, const EePlan &plan, const EeSetOut &o);
+int ee_text(rfx_ctx *ctx, const EeSetIn &s, char *d_text, int64_t cap, int64_t *total, DevBuf *own);
+int ee_contigs_from_rows(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, DevBuf &w, DevBuf &woff, DevBuf &len, DevBuf &left,
+                         DevBuf &right);
 
 }  // namespace rfx

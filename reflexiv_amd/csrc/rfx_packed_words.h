@@ -1,6 +1,6 @@
 // rfx_packed_words.h -- the word helpers of every stage that works on packed record sets (rfx_dyn_packed: rfx_dynamic.hip,
-// rfx_ksort.hip, rfx_reduce.hip, rfx_fixing.hip, rfx_fixing2.hip) and of the contig de-duplication (rfx_dedup.hip), one definition
-// each.  A packed sequence is 2 bits per base, 32 bases per 64-bit word, the first base in the two highest
+// rfx_ksort.hip, rfx_reduce.hip, rfx_fixing.hip, rfx_fixing2.hip, rfx_endext.hip) and of the contig de-duplication (rfx_dedup.hip),
+// one definition each.  A packed sequence is 2 bits per base, 32 bases per 64-bit word, the first base in the two highest
 // bits, every bit past the last base 0; a key is RFX_DYN_KEY_WORDS such words.  Everything in the first part is plain integer
 // arithmetic, `__host__ __device__` and force-inlined on the device, so a host program can compile it with the two words defined
 // away (tests/packed_words_main.cpp compares every helper with a byte model).  The last part, which needs the wave, is device-only.
@@ -32,6 +32,20 @@ __host__ __device__ PK_INLINE uint32_t pk_letter(uint32_t code) { return (0x5447
 __host__ __device__ PK_INLINE uint64_t pk_code(char ch) { return (uint64_t)(ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : 3); }
 __host__ __device__ PK_INLINE uint32_t pk_base_of(const uint64_t *__restrict__ w, int t) { return (uint32_t)(w[t >> 5] >> (62 - 2 * (t & 31))) & 3u; }
 __host__ __device__ PK_INLINE int32_t pk_clamp(int32_t v) { return v >= PK_CLAMP ? PK_CLAMP : v <= -PK_CLAMP ? -PK_CLAMP : v; }
+
+// the letters of the 16 bases that start at base t of a packed sequence, as the 16 bytes of a text in four registers (the caller
+// knows that the sequence has them: a word behind the last base is never read)
+struct Pk16 { uint32_t a, b, c, d; };
+__host__ __device__ PK_INLINE Pk16 pk_letters16(const uint64_t *__restrict__ w, int t) {
+    const int wi = t >> 5, sh = (t & 31) * 2;
+    uint64_t x = w[wi] << sh;
+    if (sh > 32) x |= w[wi + 1] >> (64 - sh);
+    const uint32_t y = (uint32_t)(x >> 32);
+    uint32_t o[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 16; j++) o[j >> 2] |= pk_letter((y >> (30 - 2 * j)) & 3u) << (8 * (j & 3));
+    return Pk16{o[0], o[1], o[2], o[3]};
+}
 
 // ---- segments ---------------------------------------------------------------------------------------------------------------------
 // the 32 bases that start at base t of one packed segment of len bases (t < 0: the segment begins -t bases into the window); 0

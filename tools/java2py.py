@@ -12,7 +12,8 @@ Java's integer semantics:
   * `Long.numberOfLeadingZeros`, `Long.SIZE`, `Long.parseLong`, `Integer.parseInt`, `Math.*`;
   * `Row` (`getLong/getInt/getSeq/getString/get`), Scala `Seq` (`apply/length/size`), `RowFactory.create`, the
     `JavaConverters...toSeq()` wrappers (= the sequence of the wrapped array's elements), `ArrayList`, `Iterator`,
-    `Tuple2`, `String` methods, `HashMap` -- as small shims (`RT` below).
+    `Tuple2`, `String` methods and `String.join`, `HashMap`, `Pattern.compile` / `Matcher.find` / `group`, `Arrays.copyOfRange` --
+    as small shims (`RT` below).
 
 tests/golden/make_reference_vectors.py uses it to run the reference's own operator classes on seeded inputs and
 commits inputs + outputs as fixtures: a pin of the oracle to the reference's code that does not go through anybody's
@@ -1408,6 +1409,13 @@ class _Arrays:
             return JList(a[0])
         return JList(a)
 
+    @staticmethod
+    def copyOfRange(a, lo, hi):
+        lo, hi = int(lo), int(hi)
+        if lo > hi or lo > len(a):
+            raise _JavaThrow("IllegalArgumentException / ArrayIndexOutOfBounds: copyOfRange")
+        return list(a[lo:hi]) + [None] * (hi - max(len(a), lo))
+
 
 class _Conv:
     def __init__(self, x): self.x = x
@@ -1524,6 +1532,43 @@ def _new(name, *args):
     raise TypeError(f"java2py: new {name}")
 
 
+class _Matcher:
+    """java.util.regex.Matcher, as far as find() and group(i) go"""
+
+    def __init__(self, rx, s):
+        self.rx, self.s, self.pos, self.m = rx, s, 0, None
+
+    def find(self):
+        self.m = self.rx.search(self.s, self.pos)
+        if self.m is not None:
+            self.pos = self.m.end() if self.m.end() > self.m.start() else self.m.end() + 1
+        return self.m is not None
+
+    def group(self, i=0):
+        if self.m is None:
+            raise _JavaThrow("IllegalStateException: No match found")
+        return self.m.group(int(i))
+
+
+class _Pattern:
+    def __init__(self, rx): self.rx = rx
+    def matcher(self, s): return _Matcher(self.rx, s)
+
+    @staticmethod
+    def compile(p):
+        return _Pattern(re.compile(p))
+
+
+class _String:
+    @staticmethod
+    def join(sep, parts):
+        return sep.join(parts.items if isinstance(parts, JList) else parts)
+
+    @staticmethod
+    def valueOf(x):
+        return str(x.v) if isinstance(x, J) else str(x)
+
+
 class _Collections:
     @staticmethod
     def sort(lst):
@@ -1539,7 +1584,7 @@ class _StringUtils:
 RUNTIME = dict(Collections=_Collections, StringUtils=_StringUtils, _cast_double=_cast_double, _L=_L, _I=_I, _C=_C, _cast_int=_cast_int, _cast_long=_cast_long, _cast_char=_cast_char, _box_long=_box_long,
                _box_int=_box_int, _ushr=_ushr, _eq=_eq, _add=_add, _len=_len, _newarr=_newarr, _iterate=_iterate,
                _instanceof=_instanceof, _call=_call, _new=_new, _JavaThrow=_JavaThrow, Long=_Long, Integer=_Integer,
-               Math=_Math, RowFactory=_RowFactory, Arrays=_Arrays, JavaConverters=_JavaConverters, System=_Sys)
+               Math=_Math, RowFactory=_RowFactory, Arrays=_Arrays, JavaConverters=_JavaConverters, System=_Sys, Pattern=_Pattern, String=_String)
 
 
 # ------------------------------------------------------------------------------------------------ driver
