@@ -33,7 +33,8 @@
  *        output arrays are unspecified, nothing at or past `cap` is written;
  *      - text buffers (rfx_contigs_text, rfx_dev_assemble[_w], rfx_assemble_counts_w,
  *        rfx_assemble_reads, the sharded drivers, rfx_dedup_contigs / rfx_dedup_contig_text,
- *        rfx_dev_contigs_to_text, rfx_dev_fix2_to_text, rfx_dev_fix2_ends_text, rfx_dev_endext_to_text)
+ *        rfx_dev_contigs_to_text, rfx_dev_fix2_to_text, rfx_dev_fix2_ends_text, rfx_dev_endext_to_text,
+ *        rfx_dev_ext2_to_text)
  *        are filled up to `cap`: the bytes below it are unspecified (a prefix of the text),
  *        nothing at or past `cap` is written;
  *  - re-entrant per context; one context = one device + one HIP stream.
@@ -975,6 +976,63 @@ int rfx_dev_endext_contigs(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const i
 int rfx_dev_endext_to_text(rfx_ctx *ctx, const rfx_endext_set *d_in, char *d_text, int64_t cap, int64_t *out_len);
 int rfx_endext_text(rfx_ctx *ctx, const char *contig_text, const int64_t *contig_off, int64_t n_contigs, const char *row_text, const int64_t *row_off,
                     int64_t n_rows, int max_k, char *out, int64_t cap, int64_t *out_len);
+
+/* The contig EXTENSION stages (Assembly_intermediate/08Extend and 09ExtendAgain) on the same packed sets in HBM:
+ * P/ReflexivDSDynamicKmerExtend.java `assemblyFromKmer` (:125-254) and P/ReflexivDSDynamicKmerExtendRoundTwo.java (:125-221).  08Extend is
+ * the contig fixing stage (rfx_dev_fix_*) with another binarizer and other contig ends; its input is the set rfx_dev_endext_contigs
+ * leaves -- no text in between -- or the text of 07EndExtend.  09ExtendAgain is rfx_dev_fix2_binarize + rfx_dev_fix2_run +
+ * rfx_dev_fix2_contigs, called as they are, and another row header; the contig set it leaves is what rfx_dev_dedup_contigs takes.
+ *   rfx_dev_ext_from_text     DynamicKmerBinarizerFromReducedToSubKmer (:3118-3219) up to the packed set: the rows
+ *                             ">Contig_<L>_<left>_<right>_<idx>_<ll>_<rl>_<new>,<sequence>" of 07EndExtend (d_text + d_row_off, as
+ *                             rfx_dev_dyn_binarize takes them) -> an rfx_endext_set of the rows whose sequence has 2 max_k characters or
+ *                             more (:3157), in order: every character other than A, C and G is a T base (the literals "-1l" / "r1-" of
+ *                             a flagged seam among them), flags 0, left / right / left_len / right_len / src_idx / new_idx = the
+ *                             header's <left> / <right> / <ll> / <rl> / <idx> / <new> (the stage reads neither index)
+ *   rfx_dev_ext_contig_ends   DSExtractFixingKmerFromContigEnds (:1189-1267) + DSgetFixingLongKmer (:514-535) + DSgetFixingKmer
+ *                             (:853-870) on a set with flags 0..3.  With T = the TEXT length of a contig (len + 3 per flagged side, the
+ *                             three characters of a flagged seam read as T bases at [left_len - 3, left_len) and [T - right_len, T -
+ *                             right_len + 3)): d_kmers receives the end 31-mers as 62-bit values, contig by contig in the reference's
+ *                             emission order -- characters [i, i + 31) for i = 0 .. left_len - 1, then [T - i - 31, T - i) for i =
+ *                             right_len - 1 .. 0; d_out_long one record per contig: the cut contig [left_len, T - right_len), which is the
+ *                             original contig of 05FixingAgain, key = its first 30 bases, extension = the rest, marker 1, left and right
+ *                             KEPT (clamped to +-30000 as buildingAlongFromThreeInt clamps them; the fixing stage's replacement by
+ *                             max_k + 3 is commented out in this class).  A contig of fewer than 2 max_k characters gives nothing (:1207)
+ *   rfx_dev_ext_run           the set and P -> the record set of 08Extend, resident between the operators: the contig ends above, then
+ *                             steps 4-9 of the fixing stage, the same code (the distinct 31-mers, union, sort, fold, reflection, sort,
+ *                             fold, DSExtendFixingKmerLoop once unsorted and min(max_iteration + 1, 17) times behind a sort, :206-243);
+ *                             max_iteration = -1 runs the unsorted first pass only.  The output file is rfx_dev_dyn_to_text of the result
+ *   rfx_ext_text              host text of 07EndExtend in, host text of 08Extend out: one upload and one copy back
+ *   rfx_dev_ext2_to_text      zipWithIndex + TagRowContigRDDID (ExtendRoundTwo :674-692) behind DSBinaryFixingKmerToFullKmer (:415-456, which
+ *                             is rfx_dev_fix2_contigs): the rows ">Contig-<len>-<idx>,<contig>\n" of a packed contig set, idx = the
+ *                             position in the set
+ *   rfx_ext2_text             host text of 08Extend in, host text of 09ExtendAgain out: one upload, the second fixing stage's binarizer,
+ *                             min(max_iteration + 1, 29) x (sort, loop) and contigs, the text, one copy back
+ * DEVIATIONS, all stated.  (1) A kept contig whose cut part, T - left_len - right_len characters, is below 32 is RFX_E_ARG for the set:
+ * the reference turns 31 characters into an end 31-mer and anything shorter into a record with a short key; 05FixingAgain holds no contig
+ * below 2 max_k >= 62.  (2) The distinct 31-mers come out ascending, as in rfx_dev_fix_kmer_set; nothing from the first fold on depends
+ * on it (tests/golden/make_extend_vectors.py runs every case under two orders and fails if a later stage differs).  (3) A contig of
+ * 10,000,000 bases or more is RFX_E_LIMIT in rfx_dev_ext2_to_text and rfx_ext2_text: the reference's changeLine would put a line break
+ * inside the csv field.
+ * CAPACITIES, from the input alone.  from_text: cap_n >= n_rows and cap_words >= n_rows + text bytes / 32.  contig_ends: cap_kmers >=
+ * sum(left_len + right_len) -- 606 in.n always suffices --, cap_n >= in.n and cap_words >= in.word_off[in.n].  run: cap_n >= 607 in.n and
+ * cap_words >= cap_n + in.word_off[in.n].  A short output: RFX_E_CAP with the needs set (need_n / need_words; n / need_words and
+ * *n_kmers; *out_len) and nothing written; contig_ends checks both of its outputs before it writes either.  rfx_dev_ext2_to_text follows
+ * the text-buffer rule: filled up to cap, nothing at or past it, RFX_E_CAP with *out_len = the need; d_text may have any alignment; the
+ * host forms write nothing into a short buffer.  RFX_E_ARG, nothing written: max_k outside 31..124; max_iteration < -1; P outside 1..63;
+ * a null pointer; a set whose word_off and len disagree; flags outside 0..3; left_len or right_len outside 0..303, or below 3 on a
+ * flagged side; deviation (1); a row whose ID is not ">Contig_" and seven decimal ints separated by '_' with a ',' behind them; a
+ * sequence that starts with '('.  RFX_E_LIMIT: 2^31 rows or contigs, a contig of 2^30 bases, 2^32 end 31-mers.  n = 0 and n_rows = 0 are
+ * valid everywhere.  All run on the context's stream and return after it has drained. */
+int rfx_dev_ext_from_text(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, const rfx_fix_params *params,
+                          rfx_endext_set *d_out);
+int rfx_dev_ext_contig_ends(rfx_ctx *ctx, const rfx_endext_set *d_in, const rfx_fix_params *params, rfx_dyn_packed *d_out_long, uint64_t *d_kmers,
+                            int64_t cap_kmers, int64_t *n_kmers);
+int rfx_dev_ext_run(rfx_ctx *ctx, const rfx_endext_set *d_in, int P, const rfx_fix_params *params, rfx_dyn_packed *d_out);
+int rfx_ext_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
+                 int64_t *out_len);
+int rfx_dev_ext2_to_text(rfx_ctx *ctx, const rfx_contigs_packed *d_in, char *d_text, int64_t cap, int64_t *out_len);
+int rfx_ext2_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
+                  int64_t *out_len);
 
 /* Synthetic reads: integer-only counter-based generator, bit-identical to
  * oracle/reflexiv_oracle.c orc_synth_*.  Writes packed reads straight into HBM. */

@@ -120,6 +120,7 @@ SYMBOLS = [
     "rfx_dev_fix_reflect", "rfx_dev_fix_run", "rfx_fix_text",
     "rfx_dev_fix2_binarize", "rfx_dev_fix2_run", "rfx_dev_fix2_contigs", "rfx_dev_fix2_to_text", "rfx_dev_fix2_ends_text", "rfx_fix2_text",
     "rfx_dev_endext_consensus", "rfx_dev_endext_contigs", "rfx_dev_endext_to_text", "rfx_endext_text",
+    "rfx_dev_ext_from_text", "rfx_dev_ext_contig_ends", "rfx_dev_ext_run", "rfx_ext_text", "rfx_dev_ext2_to_text", "rfx_ext2_text",
 ]
 
 # prototypes of the packed entry points (ctx, then as include/reflexiv_hip.h declares them)
@@ -172,6 +173,13 @@ _DYN_PACKED_ARGS = {
     "rfx_dev_endext_contigs": (_CP, _P, _P, _EC, _I, _ES),
     "rfx_dev_endext_to_text": (_ES, _P, _L, _P),
     "rfx_endext_text": (_P, _P, _L, _P, _P, _L, _I, _P, _L, _P),
+    # the contig extension stages: the set of 07EndExtend in, the record set of 08Extend and the text of 09ExtendAgain out
+    "rfx_dev_ext_from_text": (_P, _P, _L, _FP, _ES),
+    "rfx_dev_ext_contig_ends": (_ES, _FP, _PK, _P, _L, _P),
+    "rfx_dev_ext_run": (_ES, _I, _FP, _PK),
+    "rfx_ext_text": (_P, _P, _L, _I, _FP, _P, _L, _P),
+    "rfx_dev_ext2_to_text": (_CP, _P, _L, _P),
+    "rfx_ext2_text": (_P, _P, _L, _I, _FP, _P, _L, _P),
     # the packed contig set of the de-duplication (rfx_contigs_packed)
     "rfx_dev_contigs_pack": (_P, _P, _L, _CP),
     "rfx_dev_contigs_unpack": (_CP, _P, _L, _P, _L, _P),

@@ -1343,6 +1343,84 @@ class Reflexiv:
         return self._host_text_call("rfx_endext_text", [cap], lambda o, c, ln: self.L.rfx_endext_text(
             self.ctx, ct, offc.ctypes.data, nc, rt, offr.ctypes.data, nr, int(max_k), o[0].ctypes.data, c[0], C.addressof(ln[0])))[0]
 
+    # ---- the contig extension stages (08Extend, 09ExtendAgain) on packed sets (rfx_dev_ext_*, rfx_dev_ext2_*)
+    def ext_from_text(self, d_text, d_row_off, params, out: "EndextSet" = None) -> "EndextSet":
+        """rfx_dev_ext_from_text: the rows of 07EndExtend (torch uint8 tensor in HBM + int64 row offsets, n_rows + 1) -> the set of the
+        rows of at least 2 max_k characters, the literals of a flagged seam as T bases, flags 0"""
+        n_rows = int(d_row_off.numel()) - 1
+        out = out or EndextSet(n_rows, n_rows + int(d_text.numel()) // 32, d_text.device)
+        while True:
+            co = out._c()
+            t0 = time.perf_counter()
+            st = self.L.rfx_dev_ext_from_text(self.ctx, d_text.data_ptr(), d_row_off.data_ptr(), n_rows, C.byref(params), C.byref(co))
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
+            if st == RFX_E_CAP:
+                out = EndextSet(max(out.set.cap_n, int(co.set.need_n)), max(out.set.cap_words, int(co.set.need_words)), d_text.device)
+                continue
+            self._check(st, "rfx_dev_ext_from_text")
+            out.set.n = int(co.set.n)
+            return out
+
+    def ext_contig_ends(self, s: "EndextSet", params, out: "DynPacked" = None, d_kmers=None):
+        """rfx_dev_ext_contig_ends -> (the long records: the cut contigs, key 30 / rest, the end 31-mers in emission order: torch int64
+        tensor in HBM holding 62-bit values, their count)"""
+        import torch
+        ci = s._c()
+        nk = C.c_int64(0)
+        dev = s.set.word_off.device
+        if d_kmers is None:
+            d_kmers = torch.empty(max(1, 606 * s.n), dtype=torch.int64, device=dev)
+        out = out or DynPacked(s.n, s.set.words, dev)
+        while True:
+            co = out._c()
+            t0 = time.perf_counter()
+            st = self.L.rfx_dev_ext_contig_ends(self.ctx, C.byref(ci), C.byref(params), C.byref(co), d_kmers.data_ptr(), int(d_kmers.numel()),
+                                                C.addressof(nk))
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
+            if st == RFX_E_CAP:
+                if nk.value > d_kmers.numel():
+                    d_kmers = torch.empty(nk.value, dtype=torch.int64, device=dev)
+                if int(co.n) > out.cap_n or int(co.need_words) > out.cap_words:
+                    out = DynPacked(max(out.cap_n, int(co.n)), max(out.cap_words, int(co.need_words)), dev)
+                continue
+            self._check(st, "rfx_dev_ext_contig_ends")
+            out.n = int(co.n)
+            return out, d_kmers, int(nk.value)
+
+    def ext_run(self, s: "EndextSet", P: int, params, out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_ext_run: 08Extend with the set resident in HBM -> the set behind the last loop pass (the output file is
+        dyn_to_text_dev of it; fix2_run takes it as it is)"""
+        ci = s._c()
+        cap_n = 607 * s.n
+        return self._dyn_dev_call(self.L.rfx_dev_ext_run, "rfx_dev_ext_run", out or DynPacked(cap_n, cap_n + s.set.words, s.set.word_off.device),
+                                  lambda co: (C.byref(ci), int(P), C.byref(params), C.byref(co)))
+
+    def ext_text(self, text: bytes, P: int, params) -> bytes:
+        """rfx_ext_text: the rows of 07EndExtend (bytes, one row per line) -> the rows of 08Extend"""
+        text = bytes(text)
+        off, n_rows = self._row_offsets(text)
+        cap = len(text) + 48 * 607 * n_rows + 64
+        return self._host_text_call("rfx_ext_text", [cap], lambda o, c, ln: self.L.rfx_ext_text(
+            self.ctx, text, off.ctypes.data, n_rows, int(P), C.byref(params), o[0].ctypes.data, c[0], C.addressof(ln[0])))[0]
+
+    def ext2_to_text(self, c: "ContigsPacked", d_text=None):
+        """rfx_dev_ext2_to_text -> (torch uint8 tensor in HBM holding the rows ">Contig-<len>-<idx>,<contig>\n" of 09ExtendAgain, its
+        length)"""
+        import torch
+        ci = c._c()
+        if d_text is None:
+            d_text = torch.empty(max(1, 48 * c.n + 32 * c.words + 64), dtype=torch.uint8, device=c.word_off.device)
+        return self._dev_text_call("rfx_dev_ext2_to_text", d_text, lambda t, ln: self.L.rfx_dev_ext2_to_text(
+            self.ctx, C.byref(ci), t.data_ptr(), int(t.numel()), C.addressof(ln)))
+
+    def ext2_text(self, text: bytes, P: int, params) -> bytes:
+        """rfx_ext2_text: the rows of 08Extend (bytes, one `SUBKMER,m|l|r,EXTENSION` row per line) -> the rows of 09ExtendAgain"""
+        text = bytes(text)
+        off, n_rows = self._row_offsets(text)
+        cap = len(text) + 64 * n_rows + 64
+        return self._host_text_call("rfx_ext2_text", [cap], lambda o, c, ln: self.L.rfx_ext2_text(
+            self.ctx, text, off.ctypes.data, n_rows, int(P), C.byref(params), o[0].ctypes.data, c[0], C.addressof(ln[0])))[0]
+
     # ------------------------------------------------ f-4: contig RC de-duplication
     def dedup_contigs(self, contigs, min_contig=500):
         """rfx_dedup_contigs (P/ReflexivDSDynamicKmerDedup.java :138-339) on a list of contig strings (ids = positions) ->

@@ -432,27 +432,43 @@ void ReflexivMain::kmerReduction(const std::string &shortText, const std::string
     *reducedShort = std::move(o1); *rewrittenLong = std::move(o2);
 }
 
-std::string ReflexivMain::contigFixing(const std::string &csvText, int partitions) {
+// the host forms that take rows and rfx_fix_params and give one text (rfx_fix_text, rfx_ext_text, rfx_ext2_text): the call, again with the
+// length it reported where the buffer was short.  min_commas: what a row must hold to be one of the stage's; stage: the word that a
+// refused row's message begins with
+std::string ReflexivMain::fixParamsText(int (*fn)(rfx_ctx *, const char *, const int64_t *, int64_t, int, const rfx_fix_params *, char *, int64_t, int64_t *),
+                                        const char *name, const char *stage, const std::string &csvText, int partitions, int min_commas) {
     std::string rows;
     std::vector<int64_t> off;
     rowsOf(csvText, rows, off);
     const int64_t n = (int64_t)off.size() - 1;
     for (int64_t i = 0; i < n; i++)
-        if (std::count(rows.begin() + off[(size_t)i], rows.begin() + off[(size_t)i + 1], ',') < 2)
-            throw std::runtime_error("fixing row: " + rows.substr((size_t)off[(size_t)i], (size_t)(off[(size_t)i + 1] - off[(size_t)i])));
+        if (std::count(rows.begin() + off[(size_t)i], rows.begin() + off[(size_t)i + 1], ',') < min_commas)
+            throw std::runtime_error(std::string(stage) + " row: " + rows.substr((size_t)off[(size_t)i], (size_t)(off[(size_t)i + 1] - off[(size_t)i])));
     rfx_fix_params prm;
     rfx_fix_default_params(&prm, lastKmerOfList());
     prm.scramble = param.scramble; prm.max_iteration = param.maximumIteration;
     std::string out(rows.size() + 64 * (size_t)n + 64, '\0');
     int64_t len = 0;
     for (;;) {
-        const int st = rfx_fix_text(ctx, rows.data(), off.data(), n, partitions, &prm, out.data(), (int64_t)out.size(), &len);
+        const int st = fn(ctx, rows.data(), off.data(), n, partitions, &prm, out.data(), (int64_t)out.size(), &len);
         if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
-        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_fix_text: ") + rfx_last_error(ctx));
+        if (st != RFX_OK) throw std::runtime_error(std::string(name) + ": " + rfx_last_error(ctx));
         break;
     }
     out.resize((size_t)len);
     return out;
+}
+
+std::string ReflexivMain::contigFixing(const std::string &csvText, int partitions) {
+    return fixParamsText(rfx_fix_text, "rfx_fix_text", "fixing", csvText, partitions, 2);
+}
+
+std::string ReflexivMain::contigExtend(const std::string &csvText, int partitions) {
+    return fixParamsText(rfx_ext_text, "rfx_ext_text", "extend", csvText, partitions, 1);
+}
+
+std::string ReflexivMain::contigExtendAgain(const std::string &csvText, int partitions) {
+    return fixParamsText(rfx_ext2_text, "rfx_ext2_text", "extend2", csvText, partitions, 2);
 }
 
 void ReflexivMain::contigFixingRoundTwo(const std::string &csvText, int partitions, std::string *contigRows, std::string *contigEnds) {

@@ -177,11 +177,19 @@ public:
     // Assembly_intermediate/07EndExtend.  A line of 11 fields or more is a full SAM line: header and `*` lines are skipped, fields 3, 4, 6
     // and 10 taken (the commented awk of :1189).  One call (rfx_endext_text).  maxKmerSize is the last k of the k list.
     std::string contigEndExtend(const std::string &contigText, const std::string &samText);
+    // ReflexivDSDynamicKmerExtend.assemblyFromKmer (P/ReflexivDSDynamicKmerExtend.java:125-254) -- `extend`: the rows of 07EndExtend -> the
+    // rows "SUBKMER,marker|left|right,EXTENSION" of Assembly_intermediate/08Extend.  One call (rfx_ext_text).
+    std::string contigExtend(const std::string &csvText, int partitions);
+    // ReflexivDSDynamicKmerExtendRoundTwo.assemblyFromKmer (P/ReflexivDSDynamicKmerExtendRoundTwo.java:125-221) -- `extend2`: the rows of
+    // 08Extend -> the rows ">Contig-<len>-<idx>,<contig>" of Assembly_intermediate/09ExtendAgain.  One call (rfx_ext2_text).
+    std::string contigExtendAgain(const std::string &csvText, int partitions);
     int lastKmerOfList() const;                      // param.kmerListInt[length - 1]
 
     rfx_ctx *ctx = nullptr;
     DefaultParam param;
     void check(int st, const char *where) const;
+    std::string fixParamsText(int (*fn)(rfx_ctx *, const char *, const int64_t *, int64_t, int, const rfx_fix_params *, char *, int64_t, int64_t *),
+                              const char *name, const char *stage, const std::string &csvText, int partitions, int min_commas);
 };
 
 }  // namespace reflexiv

@@ -5,7 +5,9 @@
 // -outfile O` (DIR/Count_<k> of every k of the list: each through `sort`, then the pairs in the list's order),
 // `reflexiv_host fixing -kmerc ITERATION_OUT [-klist ...] -partition P -outfile O` (O/Assembly_intermediate/04Fixing),
 // `reflexiv_host fixing2 -kmerc O/Assembly_intermediate/04Fixing [-klist ...] -partition P -outfile O` (05FixingAgain and 06ContigEnds),
-// `reflexiv_host endextend -kmerc O/Assembly_intermediate/05FixingAgain -sam ROWS [-klist ...] -outfile O` (07EndExtend)
+// `reflexiv_host endextend -kmerc O/Assembly_intermediate/05FixingAgain -sam ROWS [-klist ...] -outfile O` (07EndExtend),
+// `reflexiv_host extend -kmerc O/Assembly_intermediate/07EndExtend [-klist ...] -partition P [-maxiter M] -outfile O` (08Extend),
+// `reflexiv_host extend2 -kmerc O/Assembly_intermediate/08Extend [-klist ...] -partition P [-maxiter M] -outfile O` (09ExtendAgain)
 // the two launcher sub-commands of bin/reflexiv:252-271 that reach the hot path
 // (M/Main.java:59-79, M/MainOfCounter.java:60-80), on one MI355X instead of spark-submit.
 #include <zlib.h>
@@ -40,7 +42,9 @@ int main(int argc, char **argv) {
                                    "       reflexiv_host reduce -kmerc COUNTS_DIR -klist K1,K2,... -partition P -outfile DIR\n"
                                    "       reflexiv_host fixing -kmerc ITERATION_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"
                                    "       reflexiv_host fixing2 -kmerc FIXING_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"
-                                   "       reflexiv_host endextend -kmerc FIXING_AGAIN_OUT -sam ROWS [-klist 23,31,...,95] -outfile DIR\n"; return 2; }
+                                   "       reflexiv_host endextend -kmerc FIXING_AGAIN_OUT -sam ROWS [-klist 23,31,...,95] -outfile DIR\n"
+                                   "       reflexiv_host extend -kmerc END_EXTEND_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"
+                                   "       reflexiv_host extend2 -kmerc EXTEND_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"; return 2; }
         std::string cmd = argv[1];
         std::vector<std::string> args(argv + 2, argv + argc);
         reflexiv::DefaultParam param = reflexiv::importCommandLine(args);
@@ -60,6 +64,10 @@ int main(int argc, char **argv) {
             throw std::runtime_error("fixing2 needs -kmerc FIXING_OUT [-klist 23,31,...] -partition P [-maxiter M -scramble S] -outfile DIR");
         if (cmd == "endextend" && (param.inputKmerPath.empty() || param.inputSamPath.empty() || param.outputPath.empty()))
             throw std::runtime_error("endextend needs -kmerc FIXING_AGAIN_OUT -sam ROWS [-klist 23,31,...] -outfile DIR");
+        if (cmd == "extend" && (param.inputKmerPath.empty() || param.outputPath.empty()))
+            throw std::runtime_error("extend needs -kmerc END_EXTEND_OUT [-klist 23,31,...] -partition P [-maxiter M -scramble S] -outfile DIR");
+        if (cmd == "extend2" && (param.inputKmerPath.empty() || param.outputPath.empty()))
+            throw std::runtime_error("extend2 needs -kmerc EXTEND_OUT [-klist 23,31,...] -partition P [-maxiter M -scramble S] -outfile DIR");
         if (param.outputPath.empty()) throw std::runtime_error("-outfile is required");
         if (param.inputFqPath.empty() && param.inputKmerPath.empty()) throw std::runtime_error("-fastq or -kmerc is required");
         auto read_all = [&](const std::string &paths) {
@@ -186,6 +194,15 @@ int main(int argc, char **argv) {
             out = m.contigEndExtend(read_all(param.inputKmerPath), read_all(param.inputSamPath));
             dir += "/Assembly_intermediate"; mkdir(dir.c_str(), 0755);
             dir += "/07EndExtend"; mkdir(dir.c_str(), 0755);
+        } else if (cmd == "extend" || cmd == "extend2") {
+            // the two steps behind it (Pipelines.java:840-1291): the rows of 07EndExtend -> 08Extend, the rows of 08Extend -> 09ExtendAgain,
+            // which the de-duplication reads; maxKmerSize is the last k of the list
+            const int P = param.partitions > 0 ? param.partitions : param.logicalPartitions;
+            if (P < 1 || P > 63) throw std::runtime_error(cmd + ": -partition must be 1..63");
+            if (m.lastKmerOfList() < 31 || m.lastKmerOfList() > 124) throw std::runtime_error(cmd + ": the last k of -klist must be 31..124");
+            out = cmd == "extend" ? m.contigExtend(read_all(param.inputKmerPath), P) : m.contigExtendAgain(read_all(param.inputKmerPath), P);
+            dir += "/Assembly_intermediate"; mkdir(dir.c_str(), 0755);
+            dir += cmd == "extend" ? "/08Extend" : "/09ExtendAgain"; mkdir(dir.c_str(), 0755);
         } else if (cmd == "counter") {
             // --resident at k = 33..100 (not 64 or 96): the same rows through the device count of the packed reads
             out = param.resident && param.kmerSize >= 33 && param.kmerSize % 32 != 0 ? m.counterResident(read_all(param.inputFqPath))
@@ -193,7 +210,7 @@ int main(int argc, char **argv) {
             dir += "/Count_" + std::to_string(param.kmerSize);               // P/ReflexivDataFrameCounter.java:222-233
             mkdir(dir.c_str(), 0755);
         } else throw std::runtime_error("unknown command " + cmd);
-        std::ofstream(dir + (cmd == "counter" || cmd == "sort" || cmd == "firstfour" || cmd == "iteration" || cmd == "fixing" || cmd == "endextend" ? "/part-00000.csv" : "/part-00000"), std::ios::binary) << out;   // saveAsTextFile / csv
+        std::ofstream(dir + (cmd == "counter" || cmd == "sort" || cmd == "firstfour" || cmd == "iteration" || cmd == "fixing" || cmd == "endextend" || cmd == "extend" || cmd == "extend2" ? "/part-00000.csv" : "/part-00000"), std::ios::binary) << out;   // saveAsTextFile / csv
         std::ofstream(dir + "/_SUCCESS", std::ios::binary);
         return 0;
     } catch (const std::exception &e) {

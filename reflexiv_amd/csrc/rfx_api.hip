@@ -1582,21 +1582,39 @@ int rfx_assemble_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_o
 // ---- the second contig fixing stage (rfx_fixing2.hip) -----------------------------------------------------------
 namespace {
 bool fx2_contigs_ok(const rfx_contigs_packed *p) { return p && p->words && p->word_off && p->len; }
-int fx2_params(rfx_ctx *ctx, const rfx_fix_params *p, int P) {
+int fx2_params(rfx_ctx *ctx, const rfx_fix_params *p, int P, const char *stage = "contig fixing, round two") {
     if (!p || !parts_ok(P)) return RFX_E_ARG;
-    if (p->max_k < 31 || p->max_k > 124) { ctx->last_error = "contig fixing, round two: max_k must be 31..124"; return RFX_E_ARG; }
-    if (p->max_iteration < -1) { ctx->last_error = "contig fixing, round two: max_iteration below -1"; return RFX_E_ARG; }
+    if (p->max_k < 31 || p->max_k > 124) { ctx->last_error = std::string(stage) + ": max_k must be 31..124"; return RFX_E_ARG; }
+    if (p->max_iteration < -1) { ctx->last_error = std::string(stage) + ": max_iteration below -1"; return RFX_E_ARG; }
     return RFX_OK;
 }
 int fx2_text_call(rfx_ctx *ctx, int ends, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, char *d_text, int64_t cap,
                   int64_t *out_len) {
-    if (!ctx || !fx2_contigs_ok(d_in) || d_in->n < 0 || (d_in->n > 0 && (!d_left || !d_right)) || !out_len || cap < 0 || (cap > 0 && !d_text)) return RFX_E_ARG;
+    if (!ctx || !fx2_contigs_ok(d_in) || d_in->n < 0 || (ends != 2 && d_in->n > 0 && (!d_left || !d_right)) || !out_len || cap < 0 || (cap > 0 && !d_text))
+        return RFX_E_ARG;
     RFX_HIP(hipSetDevice(ctx->device));
     const Fx2View v{d_in->n, d_in->words, d_in->word_off, d_in->len, d_left, d_right};
     int64_t total = 0;
     RFX_TRY(fx2_text(ctx, v, ends, d_text, cap, &total, nullptr));
     *out_len = total;
     return total > cap ? RFX_E_CAP : RFX_OK;
+}
+// the front of the host forms of 05FixingAgain and 09ExtendAgain: one upload, binarize, run, the contigs in the library's buffers
+struct Fx2Contigs { DevBuf w, woff, len, left, right; int64_t m = 0; };
+int fx2_contigs_of_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, Fx2Contigs &c) {
+    DevBuf d_text, d_off;
+    DynDev a, b;
+    Fx2Plan plan;
+    RFX_TRY(dyn_upload_text(ctx, text, row_off, n_rows, d_text, d_off));
+    RFX_TRY(fx2_binarize(ctx, (const char *)d_text.p, d_off.as<int64_t>(), n_rows, a));
+    RFX_TRY(fx2_run(ctx, a, P, params->scramble, params->max_iteration, b));
+    RFX_TRY(fx2_contigs_plan(ctx, b, params->max_k, plan));
+    const size_t m = (size_t)std::max<int64_t>(plan.m, 1);
+    RFX_ALLOC(c.w, uint64_t, std::max<int64_t>(plan.words, 1)); RFX_ALLOC(c.woff, int64_t, m + 1);
+    RFX_ALLOC(c.len, int64_t, m); RFX_ALLOC(c.left, int32_t, m); RFX_ALLOC(c.right, int32_t, m);
+    RFX_TRY(fx2_contigs_fill(ctx, b, plan, c.w.as<uint64_t>(), c.woff.as<int64_t>(), c.len.as<int64_t>(), c.left.as<int32_t>(), c.right.as<int32_t>()));
+    c.m = plan.m;
+    return RFX_OK;
 }
 }  // namespace
 
@@ -1655,19 +1673,11 @@ int rfx_fix2_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_
         return RFX_E_ARG;
     RFX_TRY(fx2_params(ctx, params, P));
     RFX_HIP(hipSetDevice(ctx->device));
-    DevBuf d_text, d_off, d_rows, d_ends, w, woff, len, left, right;
-    DynDev a, b;
-    Fx2Plan plan;
+    DevBuf d_rows, d_ends;
+    Fx2Contigs c;
     int64_t t_rows = 0, t_ends = 0;
-    RFX_TRY(dyn_upload_text(ctx, text, row_off, n_rows, d_text, d_off));
-    RFX_TRY(fx2_binarize(ctx, (const char *)d_text.p, d_off.as<int64_t>(), n_rows, a));
-    RFX_TRY(fx2_run(ctx, a, P, params->scramble, params->max_iteration, b));
-    RFX_TRY(fx2_contigs_plan(ctx, b, params->max_k, plan));
-    const size_t m = (size_t)std::max<int64_t>(plan.m, 1);
-    RFX_ALLOC(w, uint64_t, std::max<int64_t>(plan.words, 1)); RFX_ALLOC(woff, int64_t, m + 1);
-    RFX_ALLOC(len, int64_t, m); RFX_ALLOC(left, int32_t, m); RFX_ALLOC(right, int32_t, m);
-    RFX_TRY(fx2_contigs_fill(ctx, b, plan, w.as<uint64_t>(), woff.as<int64_t>(), len.as<int64_t>(), left.as<int32_t>(), right.as<int32_t>()));
-    const Fx2View v{plan.m, w.as<uint64_t>(), woff.as<int64_t>(), len.as<int64_t>(), left.as<int32_t>(), right.as<int32_t>()};
+    RFX_TRY(fx2_contigs_of_text(ctx, text, row_off, n_rows, P, params, c));
+    const Fx2View v{c.m, c.w.as<uint64_t>(), c.woff.as<int64_t>(), c.len.as<int64_t>(), c.left.as<int32_t>(), c.right.as<int32_t>()};
     RFX_TRY(fx2_text(ctx, v, 0, nullptr, 0, &t_rows, &d_rows));
     RFX_TRY(fx2_text(ctx, v, 1, nullptr, 0, &t_ends, &d_ends));
     return text_to_host(ctx, {{d_rows, t_rows, out, cap, out_len}, {d_ends, t_ends, ends_out, ends_cap, ends_len}}, false);
@@ -1783,6 +1793,116 @@ int rfx_endext_text(rfx_ctx *ctx, const char *contig_text, const int64_t *contig
                     a + 6 * m1};
     int64_t total = 0;
     RFX_TRY(ee_text(ctx, s, nullptr, 0, &total, &d_rows));
+    return text_to_host(ctx, {{d_rows, total, out, cap, out_len}}, false);
+} RFX_API_CATCH(ctx)
+
+}  // extern "C"
+
+// ---- the contig extension stages (rfx_ctgext.hip) ---------------------------------------------------------------
+namespace {
+const char *const EX_STAGE = "contig extension";
+EeSetIn ex_set_in(const rfx_endext_set *s) {
+    return EeSetIn{s->set.n, s->set.words, s->set.word_off, s->set.len, s->left, s->right, s->left_len, s->right_len, s->flags, s->src_idx, s->new_idx};
+}
+// the rows of 07EndExtend in HBM -> a set in the library's buffers (i32: seven arrays of max(m, 1) entries)
+struct ExSetBufs { DevBuf w, woff, len, i32; };
+int ex_set_of_rows(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, int max_k, ExSetBufs &b, EeSetIn *s) {
+    ExRowsPlan plan;
+    RFX_TRY(ex_rows_plan(ctx, d_text, d_row_off, n_rows, max_k, plan));
+    const size_t m1 = (size_t)std::max<int64_t>(plan.m, 1);
+    RFX_ALLOC(b.w, uint64_t, std::max<int64_t>(plan.words, 1)); RFX_ALLOC(b.woff, int64_t, m1 + 1); RFX_ALLOC(b.len, int64_t, m1);
+    RFX_ALLOC(b.i32, int32_t, 7 * m1);
+    int32_t *a = b.i32.as<int32_t>();
+    RFX_TRY(ex_rows_fill(ctx, d_text, plan, EeSetOut{b.w.as<uint64_t>(), b.woff.as<int64_t>(), b.len.as<int64_t>(), a, a + m1, a + 2 * m1, a + 3 * m1,
+                                                     a + 4 * m1, a + 5 * m1, a + 6 * m1}));
+    *s = EeSetIn{plan.m, b.w.as<uint64_t>(), b.woff.as<int64_t>(), b.len.as<int64_t>(), a, a + m1, a + 2 * m1, a + 3 * m1, a + 4 * m1, a + 5 * m1, a + 6 * m1};
+    return RFX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// DynamicKmerBinarizerFromReducedToSubKmer of P/ReflexivDSDynamicKmerExtend.java (:3118-3219), up to the packed set
+int rfx_dev_ext_from_text(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, const rfx_fix_params *params, rfx_endext_set *d_out) try {
+    if (!ctx || !text_rows_ok(d_text, d_row_off, n_rows) || !ee_set_ok(d_out)) return RFX_E_ARG;
+    RFX_TRY(fx2_params(ctx, params, 1, EX_STAGE));
+    RFX_HIP(hipSetDevice(ctx->device));
+    ExRowsPlan plan;
+    RFX_TRY(ex_rows_plan(ctx, d_text, d_row_off, n_rows, params->max_k, plan));
+    d_out->set.need_n = plan.m; d_out->set.need_words = plan.words;
+    if (plan.m > d_out->set.cap_n || plan.words > d_out->set.cap_words) return RFX_E_CAP;       // (nothing written)
+    RFX_TRY(ex_rows_fill(ctx, d_text, plan, EeSetOut{d_out->set.words, d_out->set.word_off, d_out->set.len, d_out->left, d_out->right, d_out->left_len,
+                                                     d_out->right_len, d_out->flags, d_out->src_idx, d_out->new_idx}));
+    d_out->set.n = plan.m;
+    return sync_checked(ctx);
+} RFX_API_CATCH(ctx)
+
+// DSExtractFixingKmerFromContigEnds (:1189-1267) + DSgetFixingLongKmer (:514-535) + DSgetFixingKmer (:853-870)
+int rfx_dev_ext_contig_ends(rfx_ctx *ctx, const rfx_endext_set *d_in, const rfx_fix_params *params, rfx_dyn_packed *d_out_long, uint64_t *d_kmers,
+                            int64_t cap_kmers, int64_t *n_kmers) try {
+    if (!ctx || !ee_set_ok(d_in) || d_in->set.n < 0 || !dyn_packed_out_ok(d_out_long) || !n_kmers || cap_kmers < 0 || (cap_kmers > 0 && !d_kmers)) return RFX_E_ARG;
+    RFX_TRY(fx2_params(ctx, params, 1, EX_STAGE));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev b;
+    DevBuf kmers;
+    int64_t n31 = 0;
+    RFX_TRY(ex_contig_ends(ctx, ex_set_in(d_in), params->max_k, b, kmers, &n31));
+    return fx_ends_store(ctx, b, kmers, n31, d_out_long, d_kmers, cap_kmers, n_kmers);
+} RFX_API_CATCH(ctx)
+
+// the driver of 08Extend (:125-254) behind its binarizer, the set resident between the operators
+int rfx_dev_ext_run(rfx_ctx *ctx, const rfx_endext_set *d_in, int P, const rfx_fix_params *params, rfx_dyn_packed *d_out) try {
+    if (!ctx || !ee_set_ok(d_in) || d_in->set.n < 0 || !dyn_packed_out_ok(d_out)) return RFX_E_ARG;
+    RFX_TRY(fx2_params(ctx, params, P, EX_STAGE));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev lng, out;
+    DevBuf kmers;
+    int64_t n31 = 0;
+    RFX_TRY(ex_contig_ends(ctx, ex_set_in(d_in), params->max_k, lng, kmers, &n31));
+    RFX_TRY(fx_from_ends(ctx, kmers.as<uint64_t>(), n31, lng, P, params->scramble, params->max_iteration, out));
+    return dyn_store(ctx, out, d_out);
+} RFX_API_CATCH(ctx)
+
+// host form of the driver of 08Extend (:125-254): the text of 07EndExtend in, the text of 08Extend out; everything between packed and in
+// HBM: one upload, the set, the contig ends, the fixing stage's steps 4-9, the text, one copy back
+int rfx_ext_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
+                 int64_t *out_len) try {
+    if (!ctx || !text_rows_ok(text, row_off, n_rows) || !out_len || cap < 0 || (cap > 0 && !out)) return RFX_E_ARG;
+    RFX_TRY(fx2_params(ctx, params, P, EX_STAGE));
+    if (n_rows >= ((int64_t)1 << 31)) { ctx->last_error = "contig extension: 2^31 rows or more"; return RFX_E_LIMIT; }      // (before a byte is uploaded)
+    RFX_HIP(hipSetDevice(ctx->device));
+    DevBuf d_text, d_off, kmers, d_o;
+    ExSetBufs bufs;
+    EeSetIn s{};
+    DynDev lng, a;
+    int64_t n31 = 0, total = 0;
+    RFX_TRY(dyn_upload_text(ctx, text, row_off, n_rows, d_text, d_off));
+    RFX_TRY(ex_set_of_rows(ctx, (const char *)d_text.p, d_off.as<int64_t>(), n_rows, params->max_k, bufs, &s));
+    RFX_TRY(ex_contig_ends(ctx, s, params->max_k, lng, kmers, &n31));
+    RFX_TRY(fx_from_ends(ctx, kmers.as<uint64_t>(), n31, lng, P, params->scramble, params->max_iteration, a));
+    RFX_TRY(dyn_to_text(ctx, a, nullptr, 0, &total, &d_o));
+    return text_to_host(ctx, {{d_o, total, out, cap, out_len}}, false);
+} RFX_API_CATCH(ctx)
+
+// zipWithIndex + TagRowContigRDDID of P/ReflexivDSDynamicKmerExtendRoundTwo.java (:674-692): the rows of 09ExtendAgain
+int rfx_dev_ext2_to_text(rfx_ctx *ctx, const rfx_contigs_packed *d_in, char *d_text, int64_t cap, int64_t *out_len) try {
+    return fx2_text_call(ctx, 2, d_in, nullptr, nullptr, d_text, cap, out_len);
+} RFX_API_CATCH(ctx)
+
+// host form of the driver of 09ExtendAgain (:125-221): the text of 08Extend in, the text of 09ExtendAgain out; one upload, the second
+// fixing stage's binarizer, loop and contigs (DSBinaryFixingKmerToFullKmer :415-456), the text, one copy back
+int rfx_ext2_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
+                  int64_t *out_len) try {
+    if (!ctx || !text_rows_ok(text, row_off, n_rows) || !out_len || cap < 0 || (cap > 0 && !out)) return RFX_E_ARG;
+    RFX_TRY(fx2_params(ctx, params, P, "contig extension, round two"));
+    if (n_rows >= ((int64_t)1 << 31)) { ctx->last_error = "contig extension, round two: 2^31 rows or more"; return RFX_E_LIMIT; }      // (before an offset is read)
+    RFX_HIP(hipSetDevice(ctx->device));
+    DevBuf d_rows;
+    Fx2Contigs c;
+    int64_t total = 0;
+    RFX_TRY(fx2_contigs_of_text(ctx, text, row_off, n_rows, P, params, c));
+    const Fx2View v{c.m, c.w.as<uint64_t>(), c.woff.as<int64_t>(), c.len.as<int64_t>(), nullptr, nullptr};
+    RFX_TRY(fx2_text(ctx, v, 2, nullptr, 0, &total, &d_rows));
     return text_to_host(ctx, {{d_rows, total, out, cap, out_len}}, false);
 } RFX_API_CATCH(ctx)
 

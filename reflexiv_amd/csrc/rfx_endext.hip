@@ -39,34 +39,18 @@ __device__ __forceinline__ uint32_t ee_code(char ch) {
     const char u = (char)(ch & 0xDF);
     return u == 'A' ? 0u : u == 'C' ? 1u : u == 'G' ? 2u : 3u;
 }
-// a decimal int in t[p, e), p left behind its digits.  sign: '-' allowed; plus: '+' too (Integer.parseInt); canon: as
-// Integer.toString writes it (no leading zero, no "-0").  false: no int there
-__device__ __forceinline__ bool ee_int(const char *__restrict__ t, int64_t &p, int64_t e, bool sign, bool plus, bool canon, int *out) {
-    bool neg = false;
-    if (p < e && ((sign && t[p] == '-') || (plus && t[p] == '+'))) { neg = t[p] == '-'; p++; }
-    const int64_t d0 = p;
-    int64_t v = 0;
-    while (p < e && t[p] >= '0' && t[p] <= '9' && p - d0 < 11) { v = v * 10 + (t[p] - '0'); p++; }
-    const int nd = (int)(p - d0);
-    if (nd == 0 || nd > 10) return false;
-    if (canon && ((nd > 1 && t[d0] == '0') || (neg && v == 0))) return false;
-    if (neg) v = -v;
-    if (v < -2147483648LL || v > 2147483647LL) return false;
-    *out = (int)v;
-    return true;
-}
 // "Contig_<L>_<left>_<right>_<idx>" at t[p, e), p left behind it
 __device__ __forceinline__ bool ee_id(const char *__restrict__ t, int64_t &p, int64_t e, int *L, int *left, int *right, int *idx) {
     if (e - p < 7) return false;
     bool ok = t[p] == 'C' && t[p + 1] == 'o' && t[p + 2] == 'n' && t[p + 3] == 't' && t[p + 4] == 'i' && t[p + 5] == 'g' && t[p + 6] == '_';
     p += 7;
-    ok = ok && ee_int(t, p, e, false, false, true, L) && p < e && t[p] == '_';
+    ok = ok && pk_dec_int(t, p, e, false, false, true, L) && p < e && t[p] == '_';
     p++;
-    ok = ok && ee_int(t, p, e, true, false, true, left) && p < e && t[p] == '_';
+    ok = ok && pk_dec_int(t, p, e, true, false, true, left) && p < e && t[p] == '_';
     p++;
-    ok = ok && ee_int(t, p, e, true, false, true, right) && p < e && t[p] == '_';
+    ok = ok && pk_dec_int(t, p, e, true, false, true, right) && p < e && t[p] == '_';
     p++;
-    return ok && ee_int(t, p, e, false, false, true, idx);
+    return ok && pk_dec_int(t, p, e, false, false, true, idx);
 }
 
 // ---- parse: SAMString2ROW (:369-388) and the per-row half of DSProcessSAMandExtendContigs (:668-869) -------------------------------
@@ -112,7 +96,7 @@ __global__ __launch_bounds__(256) void k_ee_parse(const char *__restrict__ text,
         uint32_t bad = 0;
         int start = 0;
         p = t1 + 1;
-        if (!ee_int(text, p, t2, true, true, false, &start) || p != t2) bad |= EE_BAD_START;
+        if (!pk_dec_int(text, p, t2, true, true, false, &start) || p != t2) bad |= EE_BAD_START;
         // one walk over the CIGAR ([0-9]+[A-Z=])+: the first and the last operation, and the sum from the first M (from the first
         // operation where there is no M) up to the operation ahead of the last, I subtracting (:734-749).  An operation is added
         // when the next one is read, so the last never is

@@ -392,24 +392,33 @@ static int fx_reflect(rfx_ctx *ctx, const DynDev &in, DynDev &out) {
     return RFX_OK;
 }
 
-// steps 1-9; the set stays in HBM between the operators.  The loop is the dynamic-k pass below iteration 61 (stage 1): once on the right
-// fold's partitions without a sort, then behind a sort min(max_iteration + 1, 17) times
+// steps 1-3, then rfx::fx_from_ends
 static int fx_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, int P, const FxParams &prm, DynDev &out) {
     DynDev a, b;
-    DevBuf kmers, ps, ops;
+    DevBuf kmers;
     int64_t n31 = 0;
-    uint32_t lmin = 0;
-    const int start_marker = prm.scramble == 3 ? 1 : 2;
     RFX_TRY(fx_binarize(ctx, d_text, d_row_off, n_rows, prm, a));
     RFX_TRY(fx_contig_ends(ctx, a, prm, b, kmers, &n31));
-    RFX_TRY(fx_kmer_set(ctx, kmers.as<uint64_t>(), n31, b, a));
+    return fx_from_ends(ctx, kmers.as<uint64_t>(), n31, b, P, prm.scramble, prm.max_iteration, out);
+}
+
+}  // namespace
+
+// steps 4-9 behind the contig ends; the set stays in HBM between the operators.  The loop is the dynamic-k pass below iteration 61
+// (stage 1): once on the right fold's partitions without a sort, then behind a sort min(max_iteration + 1, 17) times
+int rfx::fx_from_ends(rfx_ctx *ctx, const uint64_t *d_kmers, int64_t n31, const DynDev &lng, int P, int scramble, int max_iteration, DynDev &out) {
+    DynDev a, b;
+    DevBuf ps, ops;
+    uint32_t lmin = 0;
+    const int start_marker = scramble == 3 ? 1 : 2;
+    RFX_TRY(fx_kmer_set(ctx, d_kmers, n31, lng, a));
     RFX_TRY(dyn_sort(ctx, a, P, b, ps, &lmin));
     RFX_TRY(fx_fold(ctx, b, ps.as<int64_t>(), P, a, ops));
     RFX_TRY(fx_reflect(ctx, a, b));
     RFX_TRY(dyn_sort(ctx, b, P, a, ps, &lmin));
     RFX_TRY(fx_fold(ctx, a, ps.as<int64_t>(), P, b, ops));
     RFX_TRY(dyn_pass(ctx, b, ops.as<int64_t>(), P, b.n ? FX_KEY : 0, 1, 5, start_marker, out, nullptr));
-    const int rounds = std::min(prm.max_iteration + 1, 17);
+    const int rounds = std::min(max_iteration + 1, 17);
     for (int it = 0; it < rounds; it++) {
         DynDev s;
         RFX_TRY(dyn_sort(ctx, out, P, s, ps, &lmin));
@@ -419,7 +428,16 @@ static int fx_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, in
     return RFX_OK;
 }
 
-}  // namespace
+int rfx::fx_ends_store(rfx_ctx *ctx, const DynDev &lng, const DevBuf &kmers, int64_t n31, rfx_dyn_packed *d_out_long, uint64_t *d_kmers, int64_t cap_kmers,
+                       int64_t *n_kmers) {
+    *n_kmers = n31;
+    if (n31 > cap_kmers || lng.n > d_out_long->cap_n || lng.words > d_out_long->cap_words) {
+        d_out_long->n = lng.n; d_out_long->need_words = lng.words;
+        return RFX_E_CAP;
+    }
+    if (n31 > 0) RFX_HIP(hipMemcpyAsync(d_kmers, kmers.p, (size_t)n31 * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    return dyn_store(ctx, lng, d_out_long);
+}
 
 extern "C" {
 
@@ -447,17 +465,10 @@ int rfx_dev_fix_contig_ends(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rfx_
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a, b;
     DevBuf kmers;
-    int64_t n31 = 0, words = 0;
+    int64_t n31 = 0;
     RFX_TRY(dyn_borrow(ctx, d_in, a));
     RFX_TRY(fx_contig_ends(ctx, a, prm, b, kmers, &n31));
-    *n_kmers = n31;
-    if (b.n > 0) RFX_TRY(small_readback(ctx, &words, b.ext_off.as<int64_t>() + b.n, 8));
-    if (n31 > cap_kmers || b.n > d_out_long->cap_n || words > d_out_long->cap_words) {      // (both outputs are checked before either is written)
-        d_out_long->n = b.n; d_out_long->need_words = words;
-        return RFX_E_CAP;
-    }
-    if (n31 > 0) RFX_HIP(hipMemcpyAsync(d_kmers, kmers.p, (size_t)n31 * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    return dyn_store(ctx, b, d_out_long);
+    return fx_ends_store(ctx, b, kmers, n31, d_out_long, d_kmers, cap_kmers, n_kmers);
 } RFX_API_CATCH(ctx)
 
 int rfx_dev_fix_kmer_set(rfx_ctx *ctx, const uint64_t *d_kmers, int64_t n_kmers, const rfx_dyn_packed *d_long, rfx_dyn_packed *d_out) try {

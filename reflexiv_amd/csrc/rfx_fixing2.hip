@@ -29,7 +29,7 @@ namespace {
 #define FX2_END 200                  // bases of a contig end (:278-279); a contig of 2 FX2_END bases or more gives two ends
 
 // what is wrong with a call's input (CallFlags::bad)
-enum { FX2_BAD_KEY = 1, FX2_BAD_EXT = 2, FX2_BAD_LAYOUT = 4, FX2_TOO_LONG = 8 };
+enum { FX2_BAD_KEY = 1, FX2_BAD_EXT = 2, FX2_BAD_LAYOUT = 4, FX2_TOO_LONG = 8, FX2_LINE_BREAK = 16 };
 
 // ---- what the stage asks of its records: keys of 30 bases (ONE long in the reference), extensions of one base or more -----------
 __global__ __launch_bounds__(256) void k_fx2_check(const uint8_t *__restrict__ key_len, const int32_t *__restrict__ ext_len, int64_t n,
@@ -76,18 +76,30 @@ __global__ __launch_bounds__(256) void k_fx2_cat(const DynView v, int64_t n, con
 }
 
 // ---- steps 4-5: the two texts ------------------------------------------------------------------------------------------------
-// a record of either text: "Contig_<L>_<left>_<right>_<idx>" is its ID of h characters
+// a record of any of the texts: "Contig_<L>_<left>_<right>_<idx>" is its ID of h characters; ends 2 (the rows of 09ExtendAgain,
+// TagRowContigRDDID of P/ReflexivDSDynamicKmerExtendRoundTwo.java :674-692): ">Contig-<L>-<idx>", no left / right (never read)
+#define FX2_LINE_MAX 10000000        // a contig of that many bases or more is refused for ends 2 (the reference's changeLine would break the field)
 struct Fx2Rec { int L, left, right, idx, cL, cl, cr, h; const uint64_t *w; };
+__device__ __forceinline__ int fx2_id_chars(int cL, int left, int right, int idx, int ends) {
+    return ends == 2 ? 8 + cL + 1 + pk_int_chars(idx) : 7 + cL + 1 + pk_int_chars(left) + 1 + pk_int_chars(right) + 1 + pk_int_chars(idx);
+}
 __device__ __forceinline__ Fx2Rec fx2_rec(const uint64_t *__restrict__ words, const int64_t *__restrict__ woff, const int64_t *__restrict__ len,
-                                          const int32_t *__restrict__ left, const int32_t *__restrict__ right, int64_t i) {
+                                          const int32_t *__restrict__ left, const int32_t *__restrict__ right, int64_t i, int ends) {
     Fx2Rec r;
-    r.L = (int)len[i]; r.left = left[i]; r.right = right[i]; r.idx = (int)i;
+    r.L = (int)len[i]; r.left = ends == 2 ? 0 : left[i]; r.right = ends == 2 ? 0 : right[i]; r.idx = (int)i;
     r.cL = pk_int_chars(r.L); r.cl = pk_int_chars(r.left); r.cr = pk_int_chars(r.right);
-    r.h = 7 + r.cL + 1 + r.cl + 1 + r.cr + 1 + pk_int_chars(r.idx);
+    r.h = fx2_id_chars(r.cL, r.left, r.right, r.idx, ends);
     r.w = words + woff[i];
     return r;
 }
-__device__ __forceinline__ char fx2_id_char(const Fx2Rec &r, int q) {
+__device__ __forceinline__ char fx2_id_char(const Fx2Rec &r, int q, int ends) {
+    if (ends == 2) {
+        if (q < 8) return ">Contig-"[q];
+        q -= 8;
+        if (q < r.cL) return pk_int_char(r.L, q);
+        q -= r.cL;
+        return q == 0 ? '-' : pk_int_char(r.idx, q - 1);
+    }
     if (q < 7) return "Contig_"[q];
     q -= 7;
     if (q < r.cL) return pk_int_char(r.L, q);
@@ -100,16 +112,16 @@ __device__ __forceinline__ char fx2_id_char(const Fx2Rec &r, int q) {
     q -= 1 + r.cr;
     return q == 0 ? '_' : pk_int_char(r.idx, q - 1);
 }
-// bytes of a record.  ends 0: "<ID>,<contig>\n".  ends 1: L >= 400 gives ">ID-L\n" + bases [0, 200) + "\n" + ">ID-R\n" + bases
+// bytes of a record.  ends 0 and 2: "<ID>,<contig>\n".  ends 1: L >= 400 gives ">ID-L\n" + bases [0, 200) + "\n" + ">ID-R\n" + bases
 // [L - 200, L) + "\n", anything shorter ">ID\n" + the contig + "\n"
 __device__ __forceinline__ int64_t fx2_rec_bytes(int L, int h, int ends) {
-    if (!ends) return (int64_t)h + 1 + L + 1;
+    if (ends != 1) return (int64_t)h + 1 + L + 1;
     return L >= 2 * FX2_END ? 2 * ((int64_t)h + 4 + FX2_END + 1) : (int64_t)h + 2 + L + 1;
 }
 // byte q of a record: a character, or (ch = 0) base *t of the contig with *run bases of that run left, this one included
 __device__ __forceinline__ char fx2_byte(const Fx2Rec &r, int ends, int64_t q, int *t, int *run) {
-    if (!ends) {
-        if (q < r.h) return fx2_id_char(r, (int)q);
+    if (ends != 1) {
+        if (q < r.h) return fx2_id_char(r, (int)q, ends);
         if (q == r.h) return ',';
         q -= r.h + 1;
         if (q >= r.L) return '\n';
@@ -118,7 +130,7 @@ __device__ __forceinline__ char fx2_byte(const Fx2Rec &r, int ends, int64_t q, i
     }
     if (q == 0) return '>';
     if (r.L < 2 * FX2_END) {
-        if (q < 1 + r.h) return fx2_id_char(r, (int)q - 1);
+        if (q < 1 + r.h) return fx2_id_char(r, (int)q - 1, 0);
         q -= 1 + r.h;
         if (q == 0) return '\n';
         q -= 1;
@@ -130,7 +142,7 @@ __device__ __forceinline__ char fx2_byte(const Fx2Rec &r, int ends, int64_t q, i
     const bool right = q >= half;
     if (right) q -= half;
     if (q == 0) return '>';
-    if (q < 1 + r.h) return fx2_id_char(r, (int)q - 1);
+    if (q < 1 + r.h) return fx2_id_char(r, (int)q - 1, 0);
     q -= 1 + r.h;
     if (q == 0) return '-';
     if (q == 1) return right ? 'R' : 'L';
@@ -151,8 +163,9 @@ __global__ __launch_bounds__(256) void k_fx2_text_sizes(const int64_t *__restric
     const bool bad = L < 0 || woff[i + 1] - woff[i] != ((L + 31) >> 5) || (i == 0 && woff[0] != 0);
     if (bad) atomicOr(&flags->bad, (uint32_t)FX2_BAD_LAYOUT);
     if (!bad && L >= ((int64_t)1 << 30)) atomicOr(&flags->bad, (uint32_t)FX2_TOO_LONG);
+    if (!bad && ends == 2 && L >= FX2_LINE_MAX) atomicOr(&flags->bad, (uint32_t)FX2_LINE_BREAK);
     const int Lc = bad || L >= ((int64_t)1 << 30) ? 0 : (int)L;
-    const int h = 7 + pk_int_chars(Lc) + 1 + pk_int_chars(left[i]) + 1 + pk_int_chars(right[i]) + 1 + pk_int_chars((int)i);
+    const int h = fx2_id_chars(pk_int_chars(Lc), ends == 2 ? 0 : left[i], ends == 2 ? 0 : right[i], (int)i, ends);
     sz[i] = (uint64_t)fx2_rec_bytes(Lc, h, ends);
 }
 // one thread per 16-byte chunk of the destination: chunk c holds the text's bytes [16 c - skew, 16 c - skew + 16) cut to [0, lim),
@@ -166,7 +179,7 @@ __global__ __launch_bounds__(256) void k_fx2_text_fill(const uint64_t *__restric
     const int64_t b0 = start < 0 ? 0 : start, b1 = start + 16 < lim ? start + 16 : lim;
     const bool whole = b1 - b0 == 16;
     int64_t i = pk_find(toff, n, b0);
-    Fx2Rec r = fx2_rec(words, woff, len, left, right, i);
+    Fx2Rec r = fx2_rec(words, woff, len, left, right, i, ends);
     int64_t q = b0 - (int64_t)toff[i], next = (int64_t)toff[i + 1];
     uint32_t o[4] = {0u, 0u, 0u, 0u};
     int t = 0, run = 0;
@@ -182,7 +195,7 @@ __global__ __launch_bounds__(256) void k_fx2_text_fill(const uint64_t *__restric
             if (b < b1) {
                 if (b >= next) {                                  // the chunk crosses into the next record
                     i++;
-                    r = fx2_rec(words, woff, len, left, right, i);
+                    r = fx2_rec(words, woff, len, left, right, i, ends);
                     q = 0; next = (int64_t)toff[i + 1];
                 }
                 char ch = fx2_byte(r, ends, q, &t, &run);
@@ -289,7 +302,7 @@ int rfx::fx2_contigs_fill(rfx_ctx *ctx, const DynDev &in, const Fx2Plan &plan, u
     return RFX_OK;
 }
 
-// steps 4-5: 05FixingAgain (ends 0) or 06ContigEnds (ends 1) into d_text (filled up to cap, nothing at or past it); *total = the text's
+// steps 4-5: 05FixingAgain (ends 0), 06ContigEnds (ends 1) or 09ExtendAgain (ends 2: v.left / v.right are not read) into d_text (filled up to cap, nothing at or past it); *total = the text's
 // length; own: a buffer of the library's, as long as the text
 int rfx::fx2_text(rfx_ctx *ctx, const Fx2View &v, int ends, char *d_text, int64_t cap, int64_t *total, DevBuf *own) {
     const int64_t n = v.n;
@@ -305,6 +318,7 @@ int rfx::fx2_text(rfx_ctx *ctx, const Fx2View &v, int ends, char *d_text, int64_
     RFX_TRY(call_flags_read(ctx, flags, toff.as<uint64_t>() + n, nullptr, nullptr, &f));
     if (f.bad & FX2_BAD_LAYOUT) { ctx->last_error = "contigs: word_off and len disagree (word_off[0] = 0, word_off[i+1] - word_off[i] = (len[i] + 31) / 32)"; return RFX_E_ARG; }
     if (f.bad & FX2_TOO_LONG) { ctx->last_error = "contig fixing, round two: a contig of 2^30 bases or more"; return RFX_E_LIMIT; }
+    if (f.bad & FX2_LINE_BREAK) { ctx->last_error = "contig extension, round two: a contig of 10,000,000 bases or more"; return RFX_E_LIMIT; }
     *total = (int64_t)f.total[0];
     if (own) {
         RFX_HIP(own->alloc((size_t)std::max<int64_t>(*total, 1), ctx->stream));

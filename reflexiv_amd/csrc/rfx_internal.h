@@ -542,11 +542,20 @@ int dyn_to_text(rfx_ctx *ctx, const DynDev &d, char *d_text, int64_t cap, int64_
 int ks_set_full_kmers(rfx_ctx *ctx, const DynDev &in, DynDev &out);
 int ks_set_to_text(rfx_ctx *ctx, const DynDev &d, int k, char *d_text, int64_t cap, int64_t *total, int64_t *d_row_off, int64_t *n_rows, DevBuf *own);
 
+// ---- rfx_fixing.hip, shared with rfx_ctgext.hip: everything of the fixing stage behind its contig ends --
+// the distinct end 31-mers (d_kmers, n31 values in emission order, left as they are) as one-base records + the long records, sort,
+// fold, reflection, sort, fold, the loop once on the fold's partitions and min(max_iteration + 1, 17) times behind a sort
+int fx_from_ends(rfx_ctx *ctx, const uint64_t *d_kmers, int64_t n31, const DynDev &lng, int P, int scramble, int max_iteration, DynDev &out);
+// what a stage's contig ends left (lng as dyn_alloc or dyn_empty made it, so lng.words is the exact count) into the caller's arrays;
+// both outputs are checked before either is written
+int fx_ends_store(rfx_ctx *ctx, const DynDev &lng, const DevBuf &kmers, int64_t n31, rfx_dyn_packed *d_out_long, uint64_t *d_kmers, int64_t cap_kmers,
+                  int64_t *n_kmers);
+
 // ---- rfx_fixing2.hip : the second contig fixing stage; its entry points are in rfx_api.hip
 // text rows -> a packed set (form 1, no length filter; keys of 30 bases and extensions of one base or more, RFX_E_ARG otherwise) /
 // min(max_iteration + 1, 29) x (sort, loop) on a set of such records, zero rounds copy it / the contigs of at least 2 max_k bases:
 // what they take (plan), then into arrays that hold it (fill) / the rows of 05FixingAgain (ends 0) or the lines of 06ContigEnds
-// (ends 1) of a packed contig set (own: a buffer of the library's)
+// (ends 1) or the rows of 09ExtendAgain (ends 2: left / right are not read) of a packed contig set (own: a buffer of the library's)
 struct Fx2Plan { int64_t m = 0, words = 0; DevBuf keep, rank, woff; };
 struct Fx2View { int64_t n; const uint64_t *w; const int64_t *woff, *len; const int32_t *left, *right; };
 int fx2_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, DynDev &out);
@@ -575,5 +584,14 @@ int ee_contigs_fill(rfx_ctx *ctx, const Fx2View &in, const EeConsIn &c, const Ee
 int ee_text(rfx_ctx *ctx, const EeSetIn &s, char *d_text, int64_t cap, int64_t *total, DevBuf *own);
 int ee_contigs_from_rows(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, DevBuf &w, DevBuf &woff, DevBuf &len, DevBuf &left,
                          DevBuf &right);
+
+// ---- rfx_ctgext.hip : the contig extension stages; their entry points are in rfx_api.hip
+// the rows of 07EndExtend in HBM -> what the set of the rows of at least 2 max_k characters takes (plan), then into arrays that hold it
+// (fill: the literals of a flagged seam as T bases, flags 0) / a set (flags 0..3) -> the long records of its cut contigs and the end
+// 31-mers in emission order (kmers: a buffer of the library's)
+struct ExRowsPlan { int64_t n = 0, m = 0, words = 0; DevBuf keep, rank, woff, fld, sbeg, slen; };
+int ex_rows_plan(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, int max_k, ExRowsPlan &plan);
+int ex_rows_fill(rfx_ctx *ctx, const char *d_text, const ExRowsPlan &plan, const EeSetOut &o);
+int ex_contig_ends(rfx_ctx *ctx, const EeSetIn &s, int max_k, DynDev &out, DevBuf &kmers, int64_t *n_kmers);
 
 }  // namespace rfx

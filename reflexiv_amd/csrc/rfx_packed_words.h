@@ -1,5 +1,5 @@
 // rfx_packed_words.h -- the word helpers of every stage that works on packed record sets (rfx_dyn_packed: rfx_dynamic.hip,
-// rfx_ksort.hip, rfx_reduce.hip, rfx_fixing.hip, rfx_fixing2.hip, rfx_endext.hip) and of the contig de-duplication (rfx_dedup.hip),
+// rfx_ksort.hip, rfx_reduce.hip, rfx_fixing.hip, rfx_fixing2.hip, rfx_endext.hip, rfx_ctgext.hip) and of the contig de-duplication (rfx_dedup.hip),
 // one definition each.  A packed sequence is 2 bits per base, 32 bases per 64-bit word, the first base in the two highest
 // bits, every bit past the last base 0; a key is RFX_DYN_KEY_WORDS such words.  Everything in the first part is plain integer
 // arithmetic, `__host__ __device__` and force-inlined on the device, so a host program can compile it with the two words defined
@@ -152,6 +152,23 @@ __host__ __device__ PK_INLINE int pk_parse_int(const char *__restrict__ t, int64
     while (i < e && t[i] >= '0' && t[i] <= '9') { if (v < 100000000LL) v = v * 10 + (t[i] - '0'); i++; }
     if (i < e && t[i] == '|') i++;
     return (int)(neg ? -v : v);
+}
+
+// a decimal int in t[p, e), p left behind its digits.  sign: '-' allowed; plus: '+' too (Integer.parseInt); canon: as
+// Integer.toString writes it (no leading zero, no "-0").  false: no int there
+__host__ __device__ PK_INLINE bool pk_dec_int(const char *__restrict__ t, int64_t &p, int64_t e, bool sign, bool plus, bool canon, int *out) {
+    bool neg = false;
+    if (p < e && ((sign && t[p] == '-') || (plus && t[p] == '+'))) { neg = t[p] == '-'; p++; }
+    const int64_t d0 = p;
+    int64_t v = 0;
+    while (p < e && t[p] >= '0' && t[p] <= '9' && p - d0 < 11) { v = v * 10 + (t[p] - '0'); p++; }
+    const int nd = (int)(p - d0);
+    if (nd == 0 || nd > 10) return false;
+    if (canon && ((nd > 1 && t[d0] == '0') || (neg && v == 0))) return false;
+    if (neg) v = -v;
+    if (v < -2147483648LL || v > 2147483647LL) return false;
+    *out = (int)v;
+    return true;
 }
 
 // ---- device only ------------------------------------------------------------------------------------------------------------------
