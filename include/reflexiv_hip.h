@@ -34,7 +34,7 @@
  *      - text buffers (rfx_contigs_text, rfx_dev_assemble[_w], rfx_assemble_counts_w,
  *        rfx_assemble_reads, the sharded drivers, rfx_dedup_contigs / rfx_dedup_contig_text,
  *        rfx_dev_contigs_to_text, rfx_dev_fix2_to_text, rfx_dev_fix2_ends_text, rfx_dev_endext_to_text,
- *        rfx_dev_ext2_to_text)
+ *        rfx_dev_ext2_to_text, rfx_dev_map_to_text)
  *        are filled up to `cap`: the bytes below it are unspecified (a prefix of the text),
  *        nothing at or past `cap` is written;
  *  - re-entrant per context; one context = one device + one HIP stream.
@@ -1033,6 +1033,63 @@ int rfx_ext_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t
 int rfx_dev_ext2_to_text(rfx_ctx *ctx, const rfx_contigs_packed *d_in, char *d_text, int64_t cap, int64_t *out_len);
 int rfx_ext2_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
                   int64_t *out_len);
+
+/* READS ONTO THE CONTIG ENDS (the front half of the Mapping stage) on the same packed sets in HBM.  The reference
+ * pipes every read through an external `minimap2 -x sr` on 06ContigEnds and a script it does not ship
+ * (P/ReflexivDSDynamicKmerMapping.java :162-223, :1157-1266); rfx_dev_endext_consensus only uses rows that hang over an end of a target.
+ * So this stage is an ungapped END-OVERHANG mapper whose SEMANTICS ARE ITS OWN (stated deviation: nothing here is compared with the
+ * reference or with minimap2, whose sensitivity nobody has measured against it).  With it the device chain is rfx_dev_fix2_contigs ->
+ * rfx_dev_map_ends -> rfx_dev_map_to_text -> rfx_dev_endext_consensus -> ... with nothing on the host.
+ * TARGETS: the records of 06ContigEnds as rfx_dev_fix2_ends_text defines them, from the set rfx_dev_fix2_contigs returns.  Contig i of
+ * L >= 400 bases gives ID-L = bases [0, 200) with a LEFT end only and ID-R = bases [L - 200, L) with a RIGHT end only; a shorter one gives
+ * ID = the whole contig with both ends; ID = Contig_<L>_<left>_<right>_<i>.  End number = 2 i + side (0 left, 1 right): contig ascending,
+ * left before right.  A target shorter than `seed` has no ends.
+ * READS: the 2-bit read store as rfx_dev_count_reads_ragged takes it (d_words, d_read_len, n_reads, words_per_read); codes A0 C1 G2,
+ * anything else 3, so an N reads as T, here and in the seq written out; words and bits past a read's length may hold anything.  Each read
+ * is tried as stored (strand 0) and as its reverse complement (strand 1); r is that orientation, n its length.
+ * LEFT END of target T, read offset o, 1 <= o <= n - seed: the seed matches exactly, r[o, o + seed) == T[0, seed); v = min(n - o, len T),
+ * p = n - o - v; valid iff v >= min_overlap and r[o, o + v) differs from T[0, v) at max_mismatch positions at most (on codes).  Row:
+ * "name \t 1 \t <o>S<v>M[<p>S] \t r \n", the <p>S part only where p > 0.
+ * RIGHT END, read offset q, 0 <= q, q + seed <= n - 1: r[q, q + seed) == T[len - seed, len); overhang o = n - q - seed >= 1; v = min(q +
+ * seed, len T), p = q + seed - v; r[p, p + v) against T[len - v, len).  Row: "name \t <len - v + 1> \t [<p>S]<v>M<o>S \t r \n".
+ * WHOLE-CONTIG targets: a placement with p > 0 (read bases past BOTH ends) is emitted by neither end.  Two targets with the same end seed
+ * each get their rows; one read may give several rows; a palindromic seed is treated like any other, each strand on its own.  No
+ * repeat-marker rows (seq L, R, L-R) are written, so `flags` stay 0 behind this stage (stated deviation: they come from the script).
+ * ORDER of rows: read index, strand (0 first), end number, offset (o at a left end, q at a right end).
+ * (A fact of the consumer, left as it is: rfx_dev_endext_consensus adds nothing for a LEFT overhang of exactly one base -- it computes
+ * clip - start, start is 1 here, and 0 is skipped (:683-713).  The row is written all the same.)
+ *   rfx_map_default_params  seed 21 (minimap2 -x sr uses k = 21), min_overlap 31, max_mismatch 2
+ *   rfx_dev_map_ends        the rows as rfx_map_hits: device arrays of cap_n entries, one entry per row in the order above -- read
+ *                           index, end number, strand, offset, v -- and the host fields n, need_n and seed (the seed of the call, which
+ *                           rfx_dev_map_to_text needs for a right end's clips)
+ *   rfx_dev_map_to_text     the rows as text in HBM and their n + 1 int64 offsets into d_row_off (cap_rows entries), in exactly the form
+ *                           rfx_dev_endext_consensus takes; `hits` must be what rfx_dev_map_ends wrote for the same contigs and reads
+ *                           (every hit is checked against them before anything indexes with it, except that a read index cannot be
+ *                           checked against n_reads, which the call does not take)
+ *   rfx_map_text            host form: the text of 05FixingAgain (as rfx_endext_text takes it) and ASCII reads (bases + n_reads + 1
+ *                           offsets) in, the row text out; one upload each and one copy back
+ * A short output.  map_ends: RFX_E_CAP with need_n set and nothing written.  map_to_text follows the text-buffer rule: filled up to cap,
+ * nothing at or past it, RFX_E_CAP with *out_len = the need, d_text may have any alignment; cap_rows below n + 1 is RFX_E_CAP with
+ * *out_len set and NOTHING written.  rfx_map_text with a short buffer writes nothing.  RFX_E_ARG, nothing written: seed outside 11..31,
+ * min_overlap outside seed..200, max_mismatch outside 0..31; a null pointer; a contig set whose word_off and len disagree;
+ * words_per_read < 1; a d_read_len[i] above 32 words_per_read (found by the counting pass); a hit that map_ends cannot have written.
+ * RFX_E_LIMIT: 2^31 hits or reads, 2^29 contigs, a contig of 2^30 bases.  n_reads = 0 and n = 0 are valid everywhere.  All run on the
+ * context's stream and return after it has drained. */
+typedef struct { int seed, min_overlap, max_mismatch; } rfx_map_params;
+typedef struct {
+    int64_t n;                                    /* rows (host field, set by rfx_dev_map_ends)                    */
+    int32_t *read, *end, *strand, *offset, *v;    /* cap_n entries each                                            */
+    int64_t cap_n, need_n;
+    int32_t seed;                                 /* the seed of the call that wrote them (host field)             */
+} rfx_map_hits;                                   /* every pointer is a DEVICE pointer, the struct lives on the host */
+void rfx_map_default_params(rfx_map_params *p);
+int rfx_dev_map_ends(rfx_ctx *ctx, const rfx_contigs_packed *d_contigs, const int32_t *d_left, const int32_t *d_right, const uint64_t *d_words,
+                     const uint32_t *d_read_len, int64_t n_reads, int words_per_read, const rfx_map_params *params, rfx_map_hits *d_out);
+int rfx_dev_map_to_text(rfx_ctx *ctx, const rfx_contigs_packed *d_contigs, const int32_t *d_left, const int32_t *d_right, const uint64_t *d_words,
+                        const uint32_t *d_read_len, int words_per_read, const rfx_map_hits *hits, char *d_text, int64_t cap, int64_t *out_len,
+                        int64_t *d_row_off, int64_t cap_rows);
+int rfx_map_text(rfx_ctx *ctx, const char *contig_text, const int64_t *contig_off, int64_t n_contigs, const uint8_t *bases, const int64_t *read_off,
+                 int64_t n_reads, const rfx_map_params *params, char *out, int64_t cap, int64_t *out_len);
 
 /* Synthetic reads: integer-only counter-based generator, bit-identical to
  * oracle/reflexiv_oracle.c orc_synth_*.  Writes packed reads straight into HBM. */

@@ -79,6 +79,17 @@ class CEndextSet(C.Structure):
                 ("flags", C.c_void_p), ("src_idx", C.c_void_p), ("new_idx", C.c_void_p)]
 
 
+class CMapParams(C.Structure):
+    """rfx_map_params."""
+    _fields_ = [("seed", C.c_int), ("min_overlap", C.c_int), ("max_mismatch", C.c_int)]
+
+
+class CMapHits(C.Structure):
+    """rfx_map_hits: every pointer is a DEVICE pointer."""
+    _fields_ = [("n", C.c_int64), ("read", C.c_void_p), ("end", C.c_void_p), ("strand", C.c_void_p), ("offset", C.c_void_p), ("v", C.c_void_p),
+                ("cap_n", C.c_int64), ("need_n", C.c_int64), ("seed", C.c_int32)]
+
+
 class CRecords(C.Structure):
     """rfx_records."""
     _fields_ = [("n", C.c_int64), ("key", C.c_void_p), ("marker", C.c_void_p), ("ext_off", C.c_void_p),
@@ -121,11 +132,12 @@ SYMBOLS = [
     "rfx_dev_fix2_binarize", "rfx_dev_fix2_run", "rfx_dev_fix2_contigs", "rfx_dev_fix2_to_text", "rfx_dev_fix2_ends_text", "rfx_fix2_text",
     "rfx_dev_endext_consensus", "rfx_dev_endext_contigs", "rfx_dev_endext_to_text", "rfx_endext_text",
     "rfx_dev_ext_from_text", "rfx_dev_ext_contig_ends", "rfx_dev_ext_run", "rfx_ext_text", "rfx_dev_ext2_to_text", "rfx_ext2_text",
+    "rfx_map_default_params", "rfx_dev_map_ends", "rfx_dev_map_to_text", "rfx_map_text",
 ]
 
 # prototypes of the packed entry points (ctx, then as include/reflexiv_hip.h declares them)
 _PK, _HR, _CP, _KP, _RP, _FP, _I, _L, _P = "PK", "HR", "CP", "KP", "RP", "FP", C.c_int, C.c_int64, C.c_void_p
-_EC, _ES = "EC", "ES"
+_EC, _ES, _MP, _MH = "EC", "ES", "MP", "MH"
 _DYN_PACKED_ARGS = {
     "rfx_dev_dyn_pack": (_HR, _PK),
     "rfx_dev_dyn_unpack": (_PK, _HR),
@@ -180,6 +192,10 @@ _DYN_PACKED_ARGS = {
     "rfx_ext_text": (_P, _P, _L, _I, _FP, _P, _L, _P),
     "rfx_dev_ext2_to_text": (_CP, _P, _L, _P),
     "rfx_ext2_text": (_P, _P, _L, _I, _FP, _P, _L, _P),
+    # reads onto the contig ends: a packed contig set and the read store in, the hits and their row text out
+    "rfx_dev_map_ends": (_CP, _P, _P, _P, _P, _L, _I, _MP, _MH),
+    "rfx_dev_map_to_text": (_CP, _P, _P, _P, _P, _I, _MH, _P, _L, _P, _P, _L),
+    "rfx_map_text": (_P, _P, _L, _P, _P, _L, _MP, _P, _L, _P),
     # the packed contig set of the de-duplication (rfx_contigs_packed)
     "rfx_dev_contigs_pack": (_P, _P, _L, _CP),
     "rfx_dev_contigs_unpack": (_CP, _P, _L, _P, _L, _P),
@@ -235,7 +251,8 @@ def lib():
                 fn.argtypes = [C.c_void_p] + [C.POINTER(CDynPacked) if a == _PK else C.POINTER(CDynRecords) if a == _HR else
                                               C.POINTER(CContigsPacked) if a == _CP else C.POINTER(CKsortParams) if a == _KP else C.POINTER(CReduceParams) if a == _RP else
                                               C.POINTER(CFixParams) if a == _FP else C.POINTER(CEndextConsensus) if a == _EC else
-                                              C.POINTER(CEndextSet) if a == _ES else a for a in _DYN_PACKED_ARGS[name]]
+                                              C.POINTER(CEndextSet) if a == _ES else C.POINTER(CMapParams) if a == _MP else
+                                              C.POINTER(CMapHits) if a == _MH else a for a in _DYN_PACKED_ARGS[name]]
                 continue
             if name == "rfx_dyn_attribute_unpack":
                 fn.restype = None
@@ -251,6 +268,10 @@ def lib():
             if name == "rfx_fix_default_params":
                 fn.restype = None
                 fn.argtypes = [C.POINTER(CFixParams), C.c_int]
+                continue
+            if name == "rfx_map_default_params":
+                fn.restype = None
+                fn.argtypes = [C.POINTER(CMapParams)]
                 continue
             if name in ("rfx_comm_last_bytes_bucketed", "rfx_ctx_workspace_bytes"):
                 fn.restype = C.c_int64

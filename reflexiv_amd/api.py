@@ -279,6 +279,30 @@ class EndextSet:
         return {a: getattr(self, a)[:self.n].cpu().numpy() for a in self.ARRAYS}
 
 
+class MapHits:
+    """The rows of the end mapping (rfx_map_hits) over torch int32 tensors in HBM, one entry per row in row order: read index, target
+    end number (2 contig + side), strand, offset (o at a left end, q at a right end) and v.  `n` rows are in use; `seed` is the seed
+    of the call that wrote them."""
+    ARRAYS = ("read", "end", "strand", "offset", "v")
+
+    def __init__(self, cap_n: int, device="cuda"):
+        import torch
+        self.cap_n, self.n, self.seed = int(cap_n), 0, 0
+        for a in self.ARRAYS:
+            setattr(self, a, torch.empty(max(1, self.cap_n), dtype=torch.int32, device=device))
+
+    def _c(self) -> "_lib.CMapHits":
+        c = _lib.CMapHits()
+        c.n, c.cap_n, c.need_n, c.seed = self.n, self.cap_n, 0, self.seed
+        for a in self.ARRAYS:
+            setattr(c, a, getattr(self, a).data_ptr())
+        return c
+
+    def host(self):
+        """{array name: numpy int32 of the n entries in use}"""
+        return {a: getattr(self, a)[:self.n].cpu().numpy() for a in self.ARRAYS}
+
+
 def as_records(r) -> Records:
     """Accept any object with key/marker/ext_off/ext/left/right arrays (e.g. the oracle's Records)."""
     return Records(np.ascontiguousarray(r.key, np.uint64), np.ascontiguousarray(r.marker, np.int32),
@@ -1342,6 +1366,64 @@ class Reflexiv:
         cap = len(ct) + 700 * nc + 64
         return self._host_text_call("rfx_endext_text", [cap], lambda o, c, ln: self.L.rfx_endext_text(
             self.ctx, ct, offc.ctypes.data, nc, rt, offr.ctypes.data, nr, int(max_k), o[0].ctypes.data, c[0], C.addressof(ln[0])))[0]
+
+    # ---- reads onto the contig ends, the front half of the Mapping stage (rfx_dev_map_*)
+    def map_params(self, **kw) -> "_lib.CMapParams":
+        """rfx_map_default_params (seed 21, min_overlap 31, max_mismatch 2), then **kw"""
+        return self._params(_lib.CMapParams, self.L.rfx_map_default_params, "rfx_map_params", **kw)
+
+    def map_ends(self, c: "ContigsPacked", d_left, d_right, d_words, d_read_len, n_reads: int, words_per_read: int, params=None,
+                 out: "MapHits" = None) -> "MapHits":
+        """rfx_dev_map_ends: the contigs rfx_dev_fix2_contigs returns + the 2-bit read store (torch tensors in HBM: the words as int64 bit
+        patterns, the lengths as int32 bit patterns of uint32) -> the rows that hang over a contig end, in row order"""
+        ci = c._c()
+        params = params or self.map_params()
+        out = out or MapHits(64 + int(n_reads) // 2, c.word_off.device)     # (a short one is replaced by one of the need the call reports)
+        while True:
+            co = out._c()
+            t0 = time.perf_counter()
+            st = self.L.rfx_dev_map_ends(self.ctx, C.byref(ci), d_left.data_ptr(), d_right.data_ptr(), d_words.data_ptr(), d_read_len.data_ptr(),
+                                         int(n_reads), int(words_per_read), C.byref(params), C.byref(co))
+            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
+            if st == RFX_E_CAP:
+                out = MapHits(int(co.need_n), c.word_off.device)
+                continue
+            self._check(st, "rfx_dev_map_ends")
+            out.n, out.seed = int(co.n), int(co.seed)
+            return out
+
+    def map_to_text(self, c: "ContigsPacked", d_left, d_right, d_words, d_read_len, words_per_read: int, hits: "MapHits", d_text=None):
+        """rfx_dev_map_to_text -> (torch uint8 tensor in HBM holding the rows "name \\t start \\t cigar \\t seq \\n", its length, the
+        int64 row offsets, hits.n + 1) -- what endext_consensus takes"""
+        import torch
+        ci, ch = c._c(), hits._c()
+        dev = c.word_off.device
+        d_row_off = torch.empty(hits.n + 1, dtype=torch.int64, device=dev)
+        if d_text is None:
+            d_text = torch.empty(max(1, hits.n * (32 * int(words_per_read) + 96)), dtype=torch.uint8, device=dev)
+        d_text, ln = self._dev_text_call("rfx_dev_map_to_text", d_text, lambda t, ln: self.L.rfx_dev_map_to_text(
+            self.ctx, C.byref(ci), d_left.data_ptr(), d_right.data_ptr(), d_words.data_ptr(), d_read_len.data_ptr(), int(words_per_read), C.byref(ch),
+            t.data_ptr(), int(t.numel()), C.addressof(ln), d_row_off.data_ptr(), int(d_row_off.numel())))
+        return d_text, ln, d_row_off
+
+    def map_text(self, contig_text: bytes, reads, params=None) -> bytes:
+        """rfx_map_text: the rows of 05FixingAgain (bytes, one row per line) and the reads -- a list of bytes, or (the bases as one
+        numpy uint8 array, the n + 1 int64 offsets) -- -> the row text"""
+        ct = bytes(contig_text)
+        offc, nc = self._row_offsets(ct)
+        params = params or self.map_params()
+        if isinstance(reads, tuple):
+            bases, offr = np.ascontiguousarray(reads[0], np.uint8), np.ascontiguousarray(reads[1], np.int64)
+        else:
+            reads = [bytes(r) for r in reads]
+            bases = np.frombuffer(b"".join(reads), np.uint8)
+            offr = np.zeros(len(reads) + 1, np.int64)
+            np.cumsum([len(r) for r in reads], out=offr[1:])
+        nr = len(offr) - 1
+        cap = 4 * len(bases) + 256 * nr + 64
+        return self._host_text_call("rfx_map_text", [cap], lambda o, c, ln: self.L.rfx_map_text(
+            self.ctx, ct, offc.ctypes.data, nc, bases.ctypes.data, offr.ctypes.data, nr, C.byref(params), o[0].ctypes.data, c[0],
+            C.addressof(ln[0])))[0]
 
     # ---- the contig extension stages (08Extend, 09ExtendAgain) on packed sets (rfx_dev_ext_*, rfx_dev_ext2_*, DESIGN.md section 25)
     def ext_from_text(self, d_text, d_row_off, params, out: "EndextSet" = None) -> "EndextSet":

@@ -12,6 +12,7 @@ struct DefaultParam {
     std::string inputFqPath;                 // -fastq
     std::string inputKmerPath;               // -kmerc
     std::string inputSamPath;                // -sam         the alignment rows of `endextend`: contig, start, cigar, seq -- or full SAM lines
+    std::string rowsOutPath;                 // -rowsout     `mapping`: also write the alignment rows it made to this file
     std::string inputKmerPath2;              // -kmerc2      the LONGER k-mers of `reduce` (param.inputKmerPath2)
     int kmerSize2 = 0;                       // -kmer2       the longer k of `reduce` (param.kmerSize2); -kmer is kmerSize1 there
     std::string outputPath;                  // -outfile
@@ -56,6 +57,7 @@ inline DefaultParam importCommandLine(const std::vector<std::string> &args) {
         else if (a == "-kmerc") p.inputKmerPath = need(i++);
         else if (a == "-kmerc2") p.inputKmerPath2 = need(i++);
         else if (a == "-sam") p.inputSamPath = need(i++);
+        else if (a == "-rowsout") p.rowsOutPath = need(i++);
         else if (a == "-kmer2") p.kmerSize2 = std::stoi(need(i++));
         else if (a == "-outfile") p.outputPath = need(i++);
         else if (a == "-kmer") {

@@ -529,6 +529,29 @@ std::string ReflexivMain::contigEndExtend(const std::string &contigText, const s
     return out;
 }
 
+std::string ReflexivMain::contigMapping(const std::string &contigText, const std::string &fastqText, std::string *rows) {
+    std::string contigs;
+    std::vector<int64_t> coff;
+    rowsOf(contigText, contigs, coff);
+    std::vector<uint8_t> bases; std::vector<int64_t> readOff;
+    DSFastqFilterOnlySeq{*this}.call(fastqText, bases, readOff);
+    const int64_t n = (int64_t)coff.size() - 1, nr = (int64_t)readOff.size() - 1;
+    rfx_map_params prm;
+    rfx_map_default_params(&prm);
+    std::string out(bases.size() + 256 * (size_t)nr + 64, '\0');
+    int64_t len = 0;
+    for (;;) {
+        const int st = rfx_map_text(ctx, contigs.data(), coff.data(), n, bases.data(), readOff.data(), nr, &prm, out.data(), (int64_t)out.size(), &len);
+        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
+        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_map_text: ") + rfx_last_error(ctx));
+        break;
+    }
+    out.resize((size_t)len);
+    std::string ext = contigEndExtend(contigText, out);
+    if (rows) *rows = std::move(out);
+    return ext;
+}
+
 std::string ReflexivMain::dedupContigText(const std::string &contigText) {
     std::string out(contigText.size() + 4096, '\0');
     int64_t len = 0, nc = 0;

@@ -177,6 +177,12 @@ public:
     // Assembly_intermediate/07EndExtend.  A line of 11 fields or more is a full SAM line: header and `*` lines are skipped, fields 3, 4, 6
     // and 10 taken (the commented awk of :1189).  One call (rfx_endext_text).  maxKmerSize is the last k of the k list.
     std::string contigEndExtend(const std::string &contigText, const std::string &samText);
+    // The FRONT half of ReflexivDSDynamicKmerMapping.assemblyFromKmer (P/ReflexivDSDynamicKmerMapping.java:162-223, :1157-1266: every read
+    // through an external aligner on 06ContigEnds) -- `mapping`: the rows of 05FixingAgain and the FASTQ text (DSFastqFilterOnlySeq, as the
+    // driver reads it, :285-294) -> the rows of Assembly_intermediate/07EndExtend, with the library's own end-overhang mapper in the
+    // aligner's place (rfx_map_text, DESIGN.md section 26: semantics of this project's own) and contigEndExtend behind it.  rows (optional)
+    // receives the alignment rows "name \t start \t cigar \t seq" the mapper made.
+    std::string contigMapping(const std::string &contigText, const std::string &fastqText, std::string *rows = nullptr);
     // ReflexivDSDynamicKmerExtend.assemblyFromKmer (P/ReflexivDSDynamicKmerExtend.java:125-254) -- `extend`: the rows of 07EndExtend -> the
     // rows "SUBKMER,marker|left|right,EXTENSION" of Assembly_intermediate/08Extend.  One call (rfx_ext_text).
     std::string contigExtend(const std::string &csvText, int partitions);

@@ -6,6 +6,8 @@
 // `reflexiv_host fixing -kmerc ITERATION_OUT [-klist ...] -partition P -outfile O` (O/Assembly_intermediate/04Fixing),
 // `reflexiv_host fixing2 -kmerc O/Assembly_intermediate/04Fixing [-klist ...] -partition P -outfile O` (05FixingAgain and 06ContigEnds),
 // `reflexiv_host endextend -kmerc O/Assembly_intermediate/05FixingAgain -sam ROWS [-klist ...] -outfile O` (07EndExtend),
+// `reflexiv_host mapping -kmerc O/Assembly_intermediate/05FixingAgain -fastq F[,F2...] [-klist ...] -outfile O [-rowsout FILE]` (the whole
+// Mapping stage: the library's own end-overhang mapper in the aligner's place, then the end extension -> 07EndExtend),
 // `reflexiv_host extend -kmerc O/Assembly_intermediate/07EndExtend [-klist ...] -partition P [-maxiter M] -outfile O` (08Extend),
 // `reflexiv_host extend2 -kmerc O/Assembly_intermediate/08Extend [-klist ...] -partition P [-maxiter M] -outfile O` (09ExtendAgain)
 // the two launcher sub-commands of bin/reflexiv:252-271 that reach the hot path
@@ -43,6 +45,7 @@ int main(int argc, char **argv) {
                                    "       reflexiv_host fixing -kmerc ITERATION_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"
                                    "       reflexiv_host fixing2 -kmerc FIXING_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"
                                    "       reflexiv_host endextend -kmerc FIXING_AGAIN_OUT -sam ROWS [-klist 23,31,...,95] -outfile DIR\n"
+                                   "       reflexiv_host mapping -kmerc FIXING_AGAIN_OUT -fastq F[,F2...] [-klist 23,31,...,95] -outfile DIR [-rowsout FILE]\n"
                                    "       reflexiv_host extend -kmerc END_EXTEND_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"
                                    "       reflexiv_host extend2 -kmerc EXTEND_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"; return 2; }
         std::string cmd = argv[1];
@@ -64,6 +67,8 @@ int main(int argc, char **argv) {
             throw std::runtime_error("fixing2 needs -kmerc FIXING_OUT [-klist 23,31,...] -partition P [-maxiter M -scramble S] -outfile DIR");
         if (cmd == "endextend" && (param.inputKmerPath.empty() || param.inputSamPath.empty() || param.outputPath.empty()))
             throw std::runtime_error("endextend needs -kmerc FIXING_AGAIN_OUT -sam ROWS [-klist 23,31,...] -outfile DIR");
+        if (cmd == "mapping" && (param.inputKmerPath.empty() || param.inputFqPath.empty() || param.outputPath.empty()))
+            throw std::runtime_error("mapping needs -kmerc FIXING_AGAIN_OUT -fastq F[,F2...] [-klist 23,31,...] -outfile DIR [-rowsout FILE]");
         if (cmd == "extend" && (param.inputKmerPath.empty() || param.outputPath.empty()))
             throw std::runtime_error("extend needs -kmerc END_EXTEND_OUT [-klist 23,31,...] -partition P [-maxiter M -scramble S] -outfile DIR");
         if (cmd == "extend2" && (param.inputKmerPath.empty() || param.outputPath.empty()))
@@ -194,6 +199,15 @@ int main(int argc, char **argv) {
             out = m.contigEndExtend(read_all(param.inputKmerPath), read_all(param.inputSamPath));
             dir += "/Assembly_intermediate"; mkdir(dir.c_str(), 0755);
             dir += "/07EndExtend"; mkdir(dir.c_str(), 0755);
+        } else if (cmd == "mapping") {
+            // the whole Mapping stage (Pipelines.java:1065-1085) with no program outside this one: the rows of 05FixingAgain and the reads ->
+            // the library's end-overhang mapper -> the end extension -> 07EndExtend; maxKmerSize is the last k of the list
+            if (m.lastKmerOfList() < 31 || m.lastKmerOfList() > 124) throw std::runtime_error("mapping: the last k of -klist must be 31..124");
+            std::string rows;
+            out = m.contigMapping(read_all(param.inputKmerPath), read_all(param.inputFqPath), &rows);
+            if (!param.rowsOutPath.empty()) std::ofstream(param.rowsOutPath, std::ios::binary) << rows;
+            dir += "/Assembly_intermediate"; mkdir(dir.c_str(), 0755);
+            dir += "/07EndExtend"; mkdir(dir.c_str(), 0755);
         } else if (cmd == "extend" || cmd == "extend2") {
             // the two steps behind it (Pipelines.java:840-1291): the rows of 07EndExtend -> 08Extend, the rows of 08Extend -> 09ExtendAgain,
             // which the de-duplication reads; maxKmerSize is the last k of the list
@@ -210,7 +224,7 @@ int main(int argc, char **argv) {
             dir += "/Count_" + std::to_string(param.kmerSize);               // P/ReflexivDataFrameCounter.java:222-233
             mkdir(dir.c_str(), 0755);
         } else throw std::runtime_error("unknown command " + cmd);
-        std::ofstream(dir + (cmd == "counter" || cmd == "sort" || cmd == "firstfour" || cmd == "iteration" || cmd == "fixing" || cmd == "endextend" || cmd == "extend" || cmd == "extend2" ? "/part-00000.csv" : "/part-00000"), std::ios::binary) << out;   // saveAsTextFile / csv
+        std::ofstream(dir + (cmd == "counter" || cmd == "sort" || cmd == "firstfour" || cmd == "iteration" || cmd == "fixing" || cmd == "endextend" || cmd == "mapping" || cmd == "extend" || cmd == "extend2" ? "/part-00000.csv" : "/part-00000"), std::ios::binary) << out;   // saveAsTextFile / csv
         std::ofstream(dir + "/_SUCCESS", std::ios::binary);
         return 0;
     } catch (const std::exception &e) {

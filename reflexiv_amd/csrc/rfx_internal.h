@@ -594,4 +594,19 @@ int ex_rows_plan(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int
 int ex_rows_fill(rfx_ctx *ctx, const char *d_text, const ExRowsPlan &plan, const EeSetOut &o);
 int ex_contig_ends(rfx_ctx *ctx, const EeSetIn &s, int max_k, DynDev &out, DevBuf &kmers, int64_t *n_kmers);
 
+// ---- rfx_endmap.hip : reads onto the contig ends; its entry points are in rfx_api.hip
+// the parameters are in range (last_error says which is not) / the seed table of a contig set, the counting pass over the read store
+// (d_words, d_read_len, words_per_read as rfx_dev_count_reads_ragged takes them) and the scan of its counts: plan.hits rows / the rows
+// into arrays that hold them, in order / the rows as text "name \t start \t cigar \t seq \n" (filled up to cap) and their n + 1
+// offsets (own: a buffer of the library's)
+struct MpPlan { int64_t hits = 0, m = 0; DevBuf keys, vals, filter, cnt, hoff; };
+struct MpHits { int32_t *read, *end, *strand, *off, *v; };
+bool mp_params_ok(rfx_ctx *ctx, const rfx_map_params *p);
+int mp_plan(rfx_ctx *ctx, const Fx2View &c, const uint64_t *d_words, const uint32_t *d_read_len, int64_t n_reads, int wpr, const rfx_map_params &p,
+            MpPlan &plan);
+int mp_fill(rfx_ctx *ctx, const Fx2View &c, const uint64_t *d_words, const uint32_t *d_read_len, int64_t n_reads, int wpr, const rfx_map_params &p,
+            const MpPlan &plan, const MpHits &o);
+int mp_text(rfx_ctx *ctx, const Fx2View &c, const uint64_t *d_words, const uint32_t *d_read_len, int wpr, const MpHits &hits, int64_t n, int seed,
+            char *d_text, int64_t cap, int64_t *total, int64_t *d_row_off, DevBuf *own);
+
 }  // namespace rfx

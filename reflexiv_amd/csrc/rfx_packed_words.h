@@ -1,5 +1,5 @@
 // rfx_packed_words.h -- the word helpers of every stage that works on packed record sets (rfx_dyn_packed: rfx_dynamic.hip,
-// rfx_ksort.hip, rfx_reduce.hip, rfx_fixing.hip, rfx_fixing2.hip, rfx_endext.hip, rfx_ctgext.hip) and of the contig de-duplication (rfx_dedup.hip),
+// rfx_ksort.hip, rfx_reduce.hip, rfx_fixing.hip, rfx_fixing2.hip, rfx_endext.hip, rfx_ctgext.hip, rfx_endmap.hip) and of the contig de-duplication (rfx_dedup.hip),
 // one definition each.  A packed sequence is 2 bits per base, 32 bases per 64-bit word, the first base in the two highest
 // bits, every bit past the last base 0; a key is RFX_DYN_KEY_WORDS such words.  Everything in the first part is plain integer
 // arithmetic, `__host__ __device__` and force-inlined on the device, so a host program can compile it with the two words defined
@@ -58,6 +58,17 @@ __host__ __device__ PK_INLINE uint64_t pk_seg32(const uint64_t *__restrict__ w, 
     uint64_t r = w[wi] << sh;
     if (sh && wi + 1 < ((len + 31) >> 5)) r |= w[wi + 1] >> (64 - sh);
     return r;
+}
+// among the first m of the 32 bases of a and b, the positions at which the two differ (compared on codes: either bit of a pair)
+__host__ __device__ PK_INLINE int pk_mismatch32(uint64_t a, uint64_t b, int m) {
+    const uint64_t x = pk_keep(a ^ b, m);
+    return __builtin_popcountll((x | (x >> 1)) & 0x5555555555555555ull);
+}
+// the 32 bases that start at base t (0 <= t < len) of the REVERSE COMPLEMENT of a segment of len bases, 0 behind its last base: base
+// x of it is 3 - base len - 1 - x of the segment, so the window is the segment's 32 bases from len - t - 32, turned round and
+// complemented.  Nothing at or past base len of the segment is used, so the segment needs no zero padding (a read of the read store)
+__host__ __device__ PK_INLINE uint64_t pk_rc_seg32(const uint64_t *__restrict__ w, int len, int t) {
+    return pk_keep(pk_rev2(~pk_seg32(w, len, len - t - 32)), len - t);
 }
 // a contig as its record holds it: key || extension for marker 1, extension || key otherwise (V: DynView, or a host stand-in)
 struct FxCat { const uint64_t *w0, *w1; int l0, l1; };
