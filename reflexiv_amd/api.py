@@ -191,6 +191,15 @@ class DynPacked:
         c.cap_n, c.cap_words, c.need_words = self.cap_n, self.cap_words, 0
         return c
 
+    def _grown(self, co, device=None) -> "DynPacked":
+        """after RFX_E_CAP: a set that holds what the call reported (co.n records, co.need_words words); this one where it already does"""
+        if int(co.n) <= self.cap_n and int(co.need_words) <= self.cap_words:
+            return self
+        return DynPacked(max(self.cap_n, int(co.n)), max(self.cap_words, int(co.need_words)), device or self.key.device)
+
+    def _take(self, co):
+        self.n = int(co.n)
+
     def host(self):
         """the raw arrays in use, as numpy: (key [n, 4] uint64, key_len, ext uint64, ext_off, ext_len, marker, left, right)"""
         n = self.n
@@ -228,6 +237,13 @@ class ContigsPacked:
         c.cap_n, c.cap_words, c.need_n, c.need_words = self.cap_n, self.cap_words, 0, 0
         return c
 
+    def _grown(self, co, device=None) -> "ContigsPacked":
+        """after RFX_E_CAP: a set that holds what the call reported (co.need_n contigs, co.need_words words)"""
+        return ContigsPacked(max(self.cap_n, int(co.need_n)), max(self.cap_words, int(co.need_words)), device or self.word_off.device)
+
+    def _take(self, co):
+        self.n = int(co.n)
+
     def host(self):
         """the raw arrays in use, as numpy: (words uint64, word_off, len)"""
         n = self.n
@@ -249,6 +265,14 @@ class EndextConsensus:
         c = _lib.CEndextConsensus()
         c.left, c.right, c.flags = self.left._c(), self.right._c(), self.flags.data_ptr()
         return c
+
+    def _grown(self, co, device=None) -> "EndextConsensus":
+        """after RFX_E_CAP: sets that hold what the call reported; the words of the left and of the right set each on their own"""
+        return EndextConsensus(max(self.left.cap_n, int(co.left.need_n)), max(self.left.cap_words, int(co.left.need_words)),
+                               max(self.right.cap_words, int(co.right.need_words)), device or self.flags.device)
+
+    def _take(self, co):
+        self.left.n, self.right.n = int(co.left.n), int(co.right.n)
 
 
 class EndextSet:
@@ -274,6 +298,13 @@ class EndextSet:
             setattr(c, a, getattr(self, a).data_ptr())
         return c
 
+    def _grown(self, co, device=None) -> "EndextSet":
+        """after RFX_E_CAP: a set that holds what the call reported (co.set.need_n contigs, co.set.need_words words)"""
+        return EndextSet(max(self.set.cap_n, int(co.set.need_n)), max(self.set.cap_words, int(co.set.need_words)), device or self.set.word_off.device)
+
+    def _take(self, co):
+        self.set.n = int(co.set.n)
+
     def host(self):
         """{array name: numpy int32 of the n entries in use}"""
         return {a: getattr(self, a)[:self.n].cpu().numpy() for a in self.ARRAYS}
@@ -297,6 +328,13 @@ class MapHits:
         for a in self.ARRAYS:
             setattr(c, a, getattr(self, a).data_ptr())
         return c
+
+    def _grown(self, co, device=None) -> "MapHits":
+        """after RFX_E_CAP: room for the co.need_n rows the call reported, as it is"""
+        return MapHits(int(co.need_n), device or self.read.device)
+
+    def _take(self, co):
+        self.n, self.seed = int(co.n), int(co.seed)
 
     def host(self):
         """{array name: numpy int32 of the n entries in use}"""
@@ -886,25 +924,30 @@ class Reflexiv:
         return out, [int(x) for x in trace[:ntr.value]]
 
     # ---- the same passes on a packed record set that stays in HBM (rfx_dev_dyn_*)
-    def _dyn_dev_call(self, fn, name, out: "DynPacked", args_of):
-        """one rfx_dev_dyn_* call into `out` (grown and called again on RFX_E_CAP) -> out"""
+    def _grow_call(self, fn, name, out, args_of, device=None, on_cap=None):
+        """one call fn(ctx, *args_of(co)) with a packed output -- a DynPacked, ContigsPacked, EndextConsensus, EndextSet or MapHits --
+        into `out` -> out.  On RFX_E_CAP `out` is replaced by what its class builds from the needs the call reported (out._grown: on
+        `device`, or where `out` lives) and the call made again; on_cap(): whatever else the caller has to regrow first.  On success
+        the class takes what it keeps from the C struct (out._take)."""
         while True:
             co = out._c()
             t0 = time.perf_counter()
             st = fn(self.ctx, *args_of(co))
             self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
             if st == RFX_E_CAP:
-                out = DynPacked(max(out.cap_n, int(co.n)), max(out.cap_words, int(co.need_words)), out.key.device)
+                if on_cap:
+                    on_cap()
+                out = out._grown(co, device)
                 continue
             self._check(st, name)
-            out.n = int(co.n)
+            out._take(co)
             return out
 
     def dyn_pack(self, r: DynRecords, out: "DynPacked" = None) -> "DynPacked":
         """rfx_dev_dyn_pack: host base codes -> a packed set in HBM"""
         out = out or DynPacked(r.n, r.n + len(r.ext) // 32)
         ci = r._c()
-        return self._dyn_dev_call(self.L.rfx_dev_dyn_pack, "rfx_dev_dyn_pack", out, lambda co: (C.byref(ci), C.byref(co)))
+        return self._grow_call(self.L.rfx_dev_dyn_pack, "rfx_dev_dyn_pack", out, lambda co: (C.byref(ci), C.byref(co)))
 
     def dyn_unpack(self, d: "DynPacked") -> DynRecords:
         """rfx_dev_dyn_unpack: a packed set -> host base codes"""
@@ -927,7 +970,7 @@ class Reflexiv:
         """rfx_dev_dyn_binarize: text (torch uint8 tensor in HBM) + row offsets (torch int64 tensor, n_rows + 1) -> a packed set"""
         n_rows = int(d_row_off.numel()) - 1
         out = out or DynPacked(n_rows, n_rows + int(d_text.numel()) // 32)
-        return self._dyn_dev_call(self.L.rfx_dev_dyn_binarize, "rfx_dev_dyn_binarize", out,
+        return self._grow_call(self.L.rfx_dev_dyn_binarize, "rfx_dev_dyn_binarize", out,
                                   lambda co: (d_text.data_ptr(), d_row_off.data_ptr(), n_rows, form, C.byref(co)))
 
     def dyn_sort_dev(self, d: "DynPacked", P: int, out: "DynPacked" = None):
@@ -935,14 +978,14 @@ class Reflexiv:
         import torch
         ps = torch.empty(max(P, 0) + 1, dtype=torch.int64, device=d.key.device)
         ci = d._c()
-        out = self._dyn_dev_call(self.L.rfx_dev_dyn_sort, "rfx_dev_dyn_sort", out or DynPacked(d.n, d.words),
+        out = self._grow_call(self.L.rfx_dev_dyn_sort, "rfx_dev_dyn_sort", out or DynPacked(d.n, d.words),
                                  lambda co: (C.byref(ci), P, C.byref(co), ps.data_ptr()))
         return out, ps
 
     def dyn_random_reflection_dev(self, d: "DynPacked", d_part_start, out: "DynPacked" = None) -> "DynPacked":
         ci = d._c()
         P = int(d_part_start.numel()) - 1
-        return self._dyn_dev_call(self.L.rfx_dev_dyn_random_reflection, "rfx_dev_dyn_random_reflection", out or DynPacked(d.n, d.words),
+        return self._grow_call(self.L.rfx_dev_dyn_random_reflection, "rfx_dev_dyn_random_reflection", out or DynPacked(d.n, d.words),
                                   lambda co: (C.byref(ci), d_part_start.data_ptr(), P, C.byref(co)))
 
     def dyn_extend_pass_dev(self, d: "DynPacked", d_part_start, stage=0, start_iteration=5, start_marker=2, out: "DynPacked" = None):
@@ -951,7 +994,7 @@ class Reflexiv:
         ci = d._c()
         P = int(d_part_start.numel()) - 1
         ops = torch.empty(P + 1, dtype=torch.int64, device=d.key.device)
-        out = self._dyn_dev_call(self.L.rfx_dev_dyn_extend_pass, "rfx_dev_dyn_extend_pass", out or DynPacked(d.n, d.words),
+        out = self._grow_call(self.L.rfx_dev_dyn_extend_pass, "rfx_dev_dyn_extend_pass", out or DynPacked(d.n, d.words),
                                  lambda co: (C.byref(ci), d_part_start.data_ptr(), P, stage, start_iteration, start_marker, C.byref(co),
                                              ops.data_ptr()))
         return out, ops
@@ -962,7 +1005,7 @@ class Reflexiv:
         ci = d._c()
         trace = np.zeros(256, np.int64)
         ntr = C.c_int64(0)
-        out = self._dyn_dev_call(self.L.rfx_dev_dyn_run, "rfx_dev_dyn_run", out or DynPacked(d.n, d.words),
+        out = self._grow_call(self.L.rfx_dev_dyn_run, "rfx_dev_dyn_run", out or DynPacked(d.n, d.words),
                                  lambda co: (C.byref(ci), P, int(random_reflection), passes_first_four, start_iteration, end_iteration,
                                              C.byref(co), trace.ctypes.data, len(trace), C.addressof(ntr)))
         return out, [int(x) for x in trace[:ntr.value]]
@@ -1048,29 +1091,29 @@ class Reflexiv:
         """rfx_dev_ksort_binarize: `KMER,count` rows (torch uint8 tensor in HBM + int64 row offsets, n_rows + 1) -> two records per
         kept row"""
         n_rows = int(d_row_off.numel()) - 1
-        return self._dyn_dev_call(self.L.rfx_dev_ksort_binarize, "rfx_dev_ksort_binarize", out or DynPacked(2 * n_rows, 2 * n_rows),
+        return self._grow_call(self.L.rfx_dev_ksort_binarize, "rfx_dev_ksort_binarize", out or DynPacked(2 * n_rows, 2 * n_rows),
                                   lambda co: (d_text.data_ptr(), d_row_off.data_ptr(), n_rows, C.byref(params), C.byref(co)))
 
     def ksort_fork_filter(self, d: "DynPacked", reflected: bool, params, out: "DynPacked" = None) -> "DynPacked":
         """rfx_dev_ksort_fork_filter over a sorted set: one survivor per run of equal keys"""
         ci = d._c()
-        return self._dyn_dev_call(self.L.rfx_dev_ksort_fork_filter, "rfx_dev_ksort_fork_filter", out or DynPacked(d.n, d.n),
+        return self._grow_call(self.L.rfx_dev_ksort_fork_filter, "rfx_dev_ksort_fork_filter", out or DynPacked(d.n, d.n),
                                   lambda co: (int(reflected), C.byref(ci), C.byref(params), C.byref(co)))
 
     def ksort_reflect(self, d: "DynPacked", out: "DynPacked" = None) -> "DynPacked":
         ci = d._c()
-        return self._dyn_dev_call(self.L.rfx_dev_ksort_reflect, "rfx_dev_ksort_reflect", out or DynPacked(d.n, d.n),
+        return self._grow_call(self.L.rfx_dev_ksort_reflect, "rfx_dev_ksort_reflect", out or DynPacked(d.n, d.n),
                                   lambda co: (C.byref(ci), C.byref(co)))
 
     def ksort_full_kmers(self, d: "DynPacked", out: "DynPacked" = None) -> "DynPacked":
         ci = d._c()
-        return self._dyn_dev_call(self.L.rfx_dev_ksort_full_kmers, "rfx_dev_ksort_full_kmers", out or DynPacked(d.n, 0),
+        return self._grow_call(self.L.rfx_dev_ksort_full_kmers, "rfx_dev_ksort_full_kmers", out or DynPacked(d.n, 0),
                                   lambda co: (C.byref(ci), C.byref(co)))
 
     def ksort_run(self, d_text, d_row_off, params, out: "DynPacked" = None) -> "DynPacked":
         """rfx_dev_ksort_run: steps 1-8 with the set resident in HBM -> the full k-mers"""
         n_rows = int(d_row_off.numel()) - 1
-        return self._dyn_dev_call(self.L.rfx_dev_ksort_run, "rfx_dev_ksort_run", out or DynPacked(2 * n_rows, 0),
+        return self._grow_call(self.L.rfx_dev_ksort_run, "rfx_dev_ksort_run", out or DynPacked(2 * n_rows, 0),
                                   lambda co: (d_text.data_ptr(), d_row_off.data_ptr(), n_rows, C.byref(params), C.byref(co)))
 
     def ksort_to_text_dev(self, d: "DynPacked", k: int, d_text=None, want_offsets=True):
@@ -1105,18 +1148,18 @@ class Reflexiv:
         """rfx_dev_reduce_union: two `KMER,m|l|r` texts (torch uint8 tensors in HBM + int64 row offsets, rows + 1) -> the full k-mer
         records of the longer text, then the shorter one's"""
         ns, nl = int(d_off_short.numel()) - 1, int(d_off_long.numel()) - 1
-        return self._dyn_dev_call(self.L.rfx_dev_reduce_union, "rfx_dev_reduce_union", out or DynPacked(ns + nl, 0),
+        return self._grow_call(self.L.rfx_dev_reduce_union, "rfx_dev_reduce_union", out or DynPacked(ns + nl, 0),
                                   lambda co: (d_text_short.data_ptr(), d_off_short.data_ptr(), ns, d_text_long.data_ptr(), d_off_long.data_ptr(), nl,
                                               C.byref(params), C.byref(co)))
 
     def reduce_left_prepare(self, d: "DynPacked", params, out: "DynPacked" = None) -> "DynPacked":
         ci = d._c()
-        return self._dyn_dev_call(self.L.rfx_dev_reduce_left_prepare, "rfx_dev_reduce_left_prepare", out or DynPacked(d.n, d.n),
+        return self._grow_call(self.L.rfx_dev_reduce_left_prepare, "rfx_dev_reduce_left_prepare", out or DynPacked(d.n, d.n),
                                   lambda co: (C.byref(ci), C.byref(params), C.byref(co)))
 
     def reduce_right_prepare(self, d: "DynPacked", params, out: "DynPacked" = None) -> "DynPacked":
         ci = d._c()
-        return self._dyn_dev_call(self.L.rfx_dev_reduce_right_prepare, "rfx_dev_reduce_right_prepare", out or DynPacked(d.n, d.n),
+        return self._grow_call(self.L.rfx_dev_reduce_right_prepare, "rfx_dev_reduce_right_prepare", out or DynPacked(d.n, d.n),
                                   lambda co: (C.byref(ci), C.byref(params), C.byref(co)))
 
     def reduce_adjust(self, d: "DynPacked", right: bool, d_part_start, params, out: "DynPacked" = None):
@@ -1125,13 +1168,13 @@ class Reflexiv:
         ci = d._c()
         P = int(d_part_start.numel()) - 1
         ops = torch.empty(max(P, 0) + 1, dtype=torch.int64, device=d.key.device)
-        out = self._dyn_dev_call(self.L.rfx_dev_reduce_adjust, "rfx_dev_reduce_adjust", out or DynPacked(d.n, d.n),
+        out = self._grow_call(self.L.rfx_dev_reduce_adjust, "rfx_dev_reduce_adjust", out or DynPacked(d.n, d.n),
                                  lambda co: (int(right), C.byref(ci), d_part_start.data_ptr(), P, C.byref(params), C.byref(co), ops.data_ptr()))
         return out, ops
 
     def reduce_full_kmers(self, d: "DynPacked", params, out: "DynPacked" = None) -> "DynPacked":
         ci = d._c()
-        return self._dyn_dev_call(self.L.rfx_dev_reduce_full_kmers, "rfx_dev_reduce_full_kmers", out or DynPacked(d.n, 0),
+        return self._grow_call(self.L.rfx_dev_reduce_full_kmers, "rfx_dev_reduce_full_kmers", out or DynPacked(d.n, 0),
                                   lambda co: (C.byref(ci), C.byref(params), C.byref(co)))
 
     def reduce_neutralize(self, d: "DynPacked", d_part_start, params, out: "DynPacked" = None):
@@ -1140,7 +1183,7 @@ class Reflexiv:
         ci = d._c()
         P = int(d_part_start.numel()) - 1
         ops = torch.empty(max(P, 0) + 1, dtype=torch.int64, device=d.key.device)
-        out = self._dyn_dev_call(self.L.rfx_dev_reduce_neutralize, "rfx_dev_reduce_neutralize", out or DynPacked(d.n, 0),
+        out = self._grow_call(self.L.rfx_dev_reduce_neutralize, "rfx_dev_reduce_neutralize", out or DynPacked(d.n, 0),
                                  lambda co: (C.byref(ci), d_part_start.data_ptr(), P, C.byref(params), C.byref(co), ops.data_ptr()))
         return out, ops
 
@@ -1148,7 +1191,7 @@ class Reflexiv:
         """rfx_dev_reduce_run: the whole driver with the set resident in HBM -> the final full k-mers (both lengths; the two
         output texts are ksort_to_text_dev of it with k = k1 and with k = k2)"""
         ns, nl = int(d_off_short.numel()) - 1, int(d_off_long.numel()) - 1
-        return self._dyn_dev_call(self.L.rfx_dev_reduce_run, "rfx_dev_reduce_run", out or DynPacked(ns + nl, 0),
+        return self._grow_call(self.L.rfx_dev_reduce_run, "rfx_dev_reduce_run", out or DynPacked(ns + nl, 0),
                                   lambda co: (d_text_short.data_ptr(), d_off_short.data_ptr(), ns, d_text_long.data_ptr(), d_off_long.data_ptr(), nl,
                                               int(P), C.byref(params), C.byref(co)))
 
@@ -1180,7 +1223,7 @@ class Reflexiv:
         """rfx_dev_fix_binarize: `SUBKMER,m|l|r,EXTENSION` rows (torch uint8 tensor in HBM + int64 row offsets, n_rows + 1) -> the
         records of the rows that hold 2 max_k bases or more"""
         n_rows = int(d_row_off.numel()) - 1
-        return self._dyn_dev_call(self.L.rfx_dev_fix_binarize, "rfx_dev_fix_binarize", out or DynPacked(n_rows, n_rows + int(d_text.numel()) // 32),
+        return self._grow_call(self.L.rfx_dev_fix_binarize, "rfx_dev_fix_binarize", out or DynPacked(n_rows, n_rows + int(d_text.numel()) // 32),
                                   lambda co: (d_text.data_ptr(), d_row_off.data_ptr(), n_rows, C.byref(params), C.byref(co)))
 
     def fix_contig_ends(self, d: "DynPacked", params, out: "DynPacked" = None, d_kmers=None):
@@ -1188,33 +1231,30 @@ class Reflexiv:
         torch int64 tensor in HBM holding 62-bit values, their count)"""
         import torch
         ci = d._c()
-        nk = C.c_int64(0)
         if d_kmers is None:
             d_kmers = torch.empty(max(1, 2 * (int(params.max_k) - 30) * d.n), dtype=torch.int64, device=d.key.device)
+        return self._contig_ends_call(self.L.rfx_dev_fix_contig_ends, "rfx_dev_fix_contig_ends", ci, params, out or DynPacked(d.n, d.words + 4 * d.n),
+                                      d_kmers, None, d.key.device)
 
-        def args(co):
-            return (C.byref(ci), C.byref(params), C.byref(co), d_kmers.data_ptr(), int(d_kmers.numel()), C.addressof(nk))
-        out = out or DynPacked(d.n, d.words + 4 * d.n)
-        while True:
-            co = out._c()
-            t0 = time.perf_counter()
-            st = self.L.rfx_dev_fix_contig_ends(self.ctx, *args(co))
-            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
-            if st == RFX_E_CAP:
-                if nk.value > d_kmers.numel():
-                    d_kmers = torch.empty(nk.value, dtype=torch.int64, device=d.key.device)
-                if int(co.n) > out.cap_n or int(co.need_words) > out.cap_words:
-                    out = DynPacked(max(out.cap_n, int(co.n)), max(out.cap_words, int(co.need_words)), out.key.device)
-                continue
-            self._check(st, "rfx_dev_fix_contig_ends")
-            out.n = int(co.n)
-            return out, d_kmers, int(nk.value)
+    def _contig_ends_call(self, fn, name, ci, params, out: "DynPacked", d_kmers, device, kmers_device):
+        """the call of fix_contig_ends / ext_contig_ends: the long records into `out` and the end 31-mers into d_kmers, each regrown on
+        its own when the call reports that it is short -> (out, d_kmers, the 31-mers' count)"""
+        import torch
+        nk = C.c_int64(0)
+        km = [d_kmers]
+
+        def regrow_kmers():
+            if nk.value > km[0].numel():
+                km[0] = torch.empty(nk.value, dtype=torch.int64, device=kmers_device)
+        out = self._grow_call(fn, name, out, lambda co: (C.byref(ci), C.byref(params), C.byref(co), km[0].data_ptr(), int(km[0].numel()), C.addressof(nk)),
+                              device, regrow_kmers)
+        return out, km[0], int(nk.value)
 
     def fix_kmer_set(self, d_kmers, n_kmers: int, d_long: "DynPacked", out: "DynPacked" = None) -> "DynPacked":
         """rfx_dev_fix_kmer_set: the distinct 31-mers as one-base records (ascending), then the long records"""
         ci = d_long._c()
         out = out or DynPacked(n_kmers + d_long.n, n_kmers + d_long.words)
-        return self._dyn_dev_call(self.L.rfx_dev_fix_kmer_set, "rfx_dev_fix_kmer_set", out,
+        return self._grow_call(self.L.rfx_dev_fix_kmer_set, "rfx_dev_fix_kmer_set", out,
                                   lambda co: (d_kmers.data_ptr() if n_kmers else None, int(n_kmers), C.byref(ci), C.byref(co)))
 
     def fix_fork_filter(self, d: "DynPacked", reflected: bool, d_part_start, out: "DynPacked" = None):
@@ -1223,13 +1263,13 @@ class Reflexiv:
         ci = d._c()
         P = int(d_part_start.numel()) - 1
         ops = torch.empty(max(P, 0) + 1, dtype=torch.int64, device=d.key.device)
-        out = self._dyn_dev_call(self.L.rfx_dev_fix_fork_filter, "rfx_dev_fix_fork_filter", out or DynPacked(d.n, d.words),
+        out = self._grow_call(self.L.rfx_dev_fix_fork_filter, "rfx_dev_fix_fork_filter", out or DynPacked(d.n, d.words),
                                  lambda co: (int(reflected), C.byref(ci), d_part_start.data_ptr(), P, C.byref(co), ops.data_ptr()))
         return out, ops
 
     def fix_reflect(self, d: "DynPacked", out: "DynPacked" = None) -> "DynPacked":
         ci = d._c()
-        return self._dyn_dev_call(self.L.rfx_dev_fix_reflect, "rfx_dev_fix_reflect", out or DynPacked(d.n, d.words),
+        return self._grow_call(self.L.rfx_dev_fix_reflect, "rfx_dev_fix_reflect", out or DynPacked(d.n, d.words),
                                   lambda co: (C.byref(ci), C.byref(co)))
 
     def fix_run(self, d_text, d_row_off, P: int, params, out: "DynPacked" = None) -> "DynPacked":
@@ -1237,7 +1277,7 @@ class Reflexiv:
         dyn_to_text_dev of it)"""
         n_rows = int(d_row_off.numel()) - 1
         cap_n = n_rows * (2 * (int(params.max_k) - 30) + 1)
-        return self._dyn_dev_call(self.L.rfx_dev_fix_run, "rfx_dev_fix_run", out or DynPacked(cap_n, cap_n + int(d_text.numel()) // 32),
+        return self._grow_call(self.L.rfx_dev_fix_run, "rfx_dev_fix_run", out or DynPacked(cap_n, cap_n + int(d_text.numel()) // 32),
                                   lambda co: (d_text.data_ptr(), d_row_off.data_ptr(), n_rows, int(P), C.byref(params), C.byref(co)))
 
     def fix_text(self, text: bytes, P: int, params) -> bytes:
@@ -1254,13 +1294,13 @@ class Reflexiv:
         """rfx_dev_fix2_binarize: the rows of 04Fixing (torch uint8 tensor in HBM + int64 row offsets, n_rows + 1) -> their records;
         no length filter"""
         n_rows = int(d_row_off.numel()) - 1
-        return self._dyn_dev_call(self.L.rfx_dev_fix2_binarize, "rfx_dev_fix2_binarize", out or DynPacked(n_rows, n_rows + int(d_text.numel()) // 32),
+        return self._grow_call(self.L.rfx_dev_fix2_binarize, "rfx_dev_fix2_binarize", out or DynPacked(n_rows, n_rows + int(d_text.numel()) // 32),
                                   lambda co: (d_text.data_ptr(), d_row_off.data_ptr(), n_rows, C.byref(co)))
 
     def fix2_run(self, d: "DynPacked", P: int, params, out: "DynPacked" = None) -> "DynPacked":
         """rfx_dev_fix2_run: min(max_iteration + 1, 29) x (sort, loop) on a packed set -- the output of fix_run feeds it as it is"""
         ci = d._c()
-        return self._dyn_dev_call(self.L.rfx_dev_fix2_run, "rfx_dev_fix2_run", out or DynPacked(d.n, d.words),
+        return self._grow_call(self.L.rfx_dev_fix2_run, "rfx_dev_fix2_run", out or DynPacked(d.n, d.words),
                                   lambda co: (C.byref(ci), int(P), C.byref(params), C.byref(co)))
 
     def fix2_contigs(self, d: "DynPacked", params, out: "ContigsPacked" = None, d_left=None, d_right=None):
@@ -1268,22 +1308,16 @@ class Reflexiv:
         cap_n entries each)"""
         import torch
         ci = d._c()
-        out = out or ContigsPacked(d.n, d.words + 4 * d.n, d.key.device)
-        while True:
-            if d_left is None or d_left.numel() < max(1, out.cap_n):
-                d_left = torch.empty(max(1, out.cap_n), dtype=torch.int32, device=d.key.device)
-            if d_right is None or d_right.numel() < max(1, out.cap_n):
-                d_right = torch.empty(max(1, out.cap_n), dtype=torch.int32, device=d.key.device)
-            co = out._c()
-            t0 = time.perf_counter()
-            st = self.L.rfx_dev_fix2_contigs(self.ctx, C.byref(ci), C.byref(params), C.byref(co), d_left.data_ptr(), d_right.data_ptr())
-            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
-            if st == RFX_E_CAP:
-                out = ContigsPacked(max(out.cap_n, int(co.need_n)), max(out.cap_words, int(co.need_words)), d.key.device)
-                continue
-            self._check(st, "rfx_dev_fix2_contigs")
-            out.n = int(co.n)
-            return out, d_left, d_right
+        lr = [d_left, d_right]
+
+        def args(co):                      # left / right follow the capacity of the set each attempt writes
+            for i in (0, 1):
+                if lr[i] is None or lr[i].numel() < max(1, int(co.cap_n)):
+                    lr[i] = torch.empty(max(1, int(co.cap_n)), dtype=torch.int32, device=d.key.device)
+            return (C.byref(ci), C.byref(params), C.byref(co), lr[0].data_ptr(), lr[1].data_ptr())
+        out = self._grow_call(self.L.rfx_dev_fix2_contigs, "rfx_dev_fix2_contigs", out or ContigsPacked(d.n, d.words + 4 * d.n, d.key.device), args,
+                              d.key.device)
+        return out, lr[0], lr[1]
 
     def _fix2_text_dev(self, fn, name, c: "ContigsPacked", d_left, d_right, d_text):
         import torch
@@ -1318,36 +1352,15 @@ class Reflexiv:
         uint8 tensor in HBM + int64 row offsets, n_rows + 1) -> the consensus of both ends of every contig, and its flags"""
         ci = c._c()
         n_rows = int(d_row_off.numel()) - 1
-        out = out or EndextConsensus(c.n, device=c.word_off.device)
-        while True:
-            co = out._c()
-            t0 = time.perf_counter()
-            st = self.L.rfx_dev_endext_consensus(self.ctx, C.byref(ci), d_left.data_ptr(), d_right.data_ptr(), d_text.data_ptr(), d_row_off.data_ptr(),
-                                                 n_rows, C.byref(co))
-            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
-            if st == RFX_E_CAP:
-                out = EndextConsensus(max(out.left.cap_n, int(co.left.need_n)), max(out.left.cap_words, int(co.left.need_words)),
-                                      max(out.right.cap_words, int(co.right.need_words)), c.word_off.device)
-                continue
-            self._check(st, "rfx_dev_endext_consensus")
-            out.left.n, out.right.n = int(co.left.n), int(co.right.n)
-            return out
+        return self._grow_call(self.L.rfx_dev_endext_consensus, "rfx_dev_endext_consensus", out or EndextConsensus(c.n, device=c.word_off.device),
+                               lambda co: (C.byref(ci), d_left.data_ptr(), d_right.data_ptr(), d_text.data_ptr(), d_row_off.data_ptr(), n_rows, C.byref(co)),
+                               c.word_off.device)
 
     def endext_contigs(self, c: "ContigsPacked", d_left, d_right, cons: "EndextConsensus", max_k: int, out: "EndextSet" = None) -> "EndextSet":
         """rfx_dev_endext_contigs: the splice and the order -> the contigs of 07EndExtend, in output order, with their arrays"""
         ci, cc = c._c(), cons._c()
-        out = out or EndextSet(c.n, c.words + 21 * c.n, c.word_off.device)
-        while True:
-            co = out._c()
-            t0 = time.perf_counter()
-            st = self.L.rfx_dev_endext_contigs(self.ctx, C.byref(ci), d_left.data_ptr(), d_right.data_ptr(), C.byref(cc), int(max_k), C.byref(co))
-            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
-            if st == RFX_E_CAP:
-                out = EndextSet(max(out.set.cap_n, int(co.set.need_n)), max(out.set.cap_words, int(co.set.need_words)), c.word_off.device)
-                continue
-            self._check(st, "rfx_dev_endext_contigs")
-            out.set.n = int(co.set.n)
-            return out
+        return self._grow_call(self.L.rfx_dev_endext_contigs, "rfx_dev_endext_contigs", out or EndextSet(c.n, c.words + 21 * c.n, c.word_off.device),
+                               lambda co: (C.byref(ci), d_left.data_ptr(), d_right.data_ptr(), C.byref(cc), int(max_k), C.byref(co)), c.word_off.device)
 
     def endext_to_text(self, s: "EndextSet", d_text=None):
         """rfx_dev_endext_to_text -> (torch uint8 tensor in HBM holding the rows of 07EndExtend, its length)"""
@@ -1379,18 +1392,9 @@ class Reflexiv:
         ci = c._c()
         params = params or self.map_params()
         out = out or MapHits(64 + int(n_reads) // 2, c.word_off.device)     # (a short one is replaced by one of the need the call reports)
-        while True:
-            co = out._c()
-            t0 = time.perf_counter()
-            st = self.L.rfx_dev_map_ends(self.ctx, C.byref(ci), d_left.data_ptr(), d_right.data_ptr(), d_words.data_ptr(), d_read_len.data_ptr(),
-                                         int(n_reads), int(words_per_read), C.byref(params), C.byref(co))
-            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
-            if st == RFX_E_CAP:
-                out = MapHits(int(co.need_n), c.word_off.device)
-                continue
-            self._check(st, "rfx_dev_map_ends")
-            out.n, out.seed = int(co.n), int(co.seed)
-            return out
+        return self._grow_call(self.L.rfx_dev_map_ends, "rfx_dev_map_ends", out, lambda co: (
+            C.byref(ci), d_left.data_ptr(), d_right.data_ptr(), d_words.data_ptr(), d_read_len.data_ptr(), int(n_reads), int(words_per_read),
+            C.byref(params), C.byref(co)), c.word_off.device)
 
     def map_to_text(self, c: "ContigsPacked", d_left, d_right, d_words, d_read_len, words_per_read: int, hits: "MapHits", d_text=None):
         """rfx_dev_map_to_text -> (torch uint8 tensor in HBM holding the rows "name \\t start \\t cigar \\t seq \\n", its length, the
@@ -1430,51 +1434,26 @@ class Reflexiv:
         """rfx_dev_ext_from_text: the rows of 07EndExtend (torch uint8 tensor in HBM + int64 row offsets, n_rows + 1) -> the set of the
         rows of at least 2 max_k characters, the literals of a flagged seam as T bases, flags 0"""
         n_rows = int(d_row_off.numel()) - 1
-        out = out or EndextSet(n_rows, n_rows + int(d_text.numel()) // 32, d_text.device)
-        while True:
-            co = out._c()
-            t0 = time.perf_counter()
-            st = self.L.rfx_dev_ext_from_text(self.ctx, d_text.data_ptr(), d_row_off.data_ptr(), n_rows, C.byref(params), C.byref(co))
-            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
-            if st == RFX_E_CAP:
-                out = EndextSet(max(out.set.cap_n, int(co.set.need_n)), max(out.set.cap_words, int(co.set.need_words)), d_text.device)
-                continue
-            self._check(st, "rfx_dev_ext_from_text")
-            out.set.n = int(co.set.n)
-            return out
+        return self._grow_call(self.L.rfx_dev_ext_from_text, "rfx_dev_ext_from_text", out or EndextSet(n_rows, n_rows + int(d_text.numel()) // 32, d_text.device),
+                               lambda co: (d_text.data_ptr(), d_row_off.data_ptr(), n_rows, C.byref(params), C.byref(co)), d_text.device)
 
     def ext_contig_ends(self, s: "EndextSet", params, out: "DynPacked" = None, d_kmers=None):
         """rfx_dev_ext_contig_ends -> (the long records: the cut contigs, key 30 / rest, the end 31-mers in emission order: torch int64
         tensor in HBM holding 62-bit values, their count)"""
         import torch
         ci = s._c()
-        nk = C.c_int64(0)
         dev = s.set.word_off.device
         if d_kmers is None:
             d_kmers = torch.empty(max(1, 606 * s.n), dtype=torch.int64, device=dev)
-        out = out or DynPacked(s.n, s.set.words, dev)
-        while True:
-            co = out._c()
-            t0 = time.perf_counter()
-            st = self.L.rfx_dev_ext_contig_ends(self.ctx, C.byref(ci), C.byref(params), C.byref(co), d_kmers.data_ptr(), int(d_kmers.numel()),
-                                                C.addressof(nk))
-            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
-            if st == RFX_E_CAP:
-                if nk.value > d_kmers.numel():
-                    d_kmers = torch.empty(nk.value, dtype=torch.int64, device=dev)
-                if int(co.n) > out.cap_n or int(co.need_words) > out.cap_words:
-                    out = DynPacked(max(out.cap_n, int(co.n)), max(out.cap_words, int(co.need_words)), dev)
-                continue
-            self._check(st, "rfx_dev_ext_contig_ends")
-            out.n = int(co.n)
-            return out, d_kmers, int(nk.value)
+        return self._contig_ends_call(self.L.rfx_dev_ext_contig_ends, "rfx_dev_ext_contig_ends", ci, params, out or DynPacked(s.n, s.set.words, dev),
+                                      d_kmers, dev, dev)
 
     def ext_run(self, s: "EndextSet", P: int, params, out: "DynPacked" = None) -> "DynPacked":
         """rfx_dev_ext_run: 08Extend with the set resident in HBM -> the set behind the last loop pass (the output file is
         dyn_to_text_dev of it; fix2_run takes it as it is)"""
         ci = s._c()
         cap_n = 607 * s.n
-        return self._dyn_dev_call(self.L.rfx_dev_ext_run, "rfx_dev_ext_run", out or DynPacked(cap_n, cap_n + s.set.words, s.set.word_off.device),
+        return self._grow_call(self.L.rfx_dev_ext_run, "rfx_dev_ext_run", out or DynPacked(cap_n, cap_n + s.set.words, s.set.word_off.device),
                                   lambda co: (C.byref(ci), int(P), C.byref(params), C.byref(co)))
 
     def ext_text(self, text: bytes, P: int, params) -> bytes:
@@ -1538,20 +1517,6 @@ class Reflexiv:
         return bytes(out[:ln.value]).decode(), int(nc.value), [int(x) for x in rn]
 
     # ---- the same on a packed contig set that stays in HBM (rfx_dev_contigs_*, rfx_dev_dedup_contigs)
-    def _contigs_dev_call(self, fn, name, out: "ContigsPacked", args_of):
-        """one call with a packed output into `out` (grown and called again on RFX_E_CAP) -> out"""
-        while True:
-            co = out._c()
-            t0 = time.perf_counter()
-            st = fn(self.ctx, *args_of(co))
-            self.last_call_ms = (time.perf_counter() - t0) * 1e3    # inside the C ABI (the last attempt)
-            if st == RFX_E_CAP:
-                out = ContigsPacked(max(out.cap_n, int(co.need_n)), max(out.cap_words, int(co.need_words)), out.word_off.device)
-                continue
-            self._check(st, name)
-            out.n = int(co.n)
-            return out
-
     def contigs_pack(self, contigs, out: "ContigsPacked" = None) -> "ContigsPacked":
         """rfx_dev_contigs_pack: a list of contig strings -> a packed set in HBM (a letter that is not ACGT is code 3)"""
         n = len(contigs)
@@ -1559,7 +1524,7 @@ class Reflexiv:
         off[1:] = np.cumsum([len(c) for c in contigs])
         bases = np.frombuffer("".join(contigs).encode(), np.uint8) if off[-1] else np.zeros(1, np.uint8)
         out = out or ContigsPacked(n, n + int(off[-1]) // 32)
-        return self._contigs_dev_call(self.L.rfx_dev_contigs_pack, "rfx_dev_contigs_pack", out,
+        return self._grow_call(self.L.rfx_dev_contigs_pack, "rfx_dev_contigs_pack", out,
                                       lambda co: (bases.ctypes.data, off.ctypes.data, n, C.byref(co)))
 
     def contigs_unpack(self, d: "ContigsPacked"):
@@ -1577,7 +1542,7 @@ class Reflexiv:
         """rfx_dev_contigs_from_text: the contig text the path writes (torch uint8 tensor in HBM) -> a packed set"""
         length = int(d_text.numel()) if length is None else int(length)
         out = out or ContigsPacked(max(16, length // 64), length // 32 + max(16, length // 64))
-        return self._contigs_dev_call(self.L.rfx_dev_contigs_from_text, "rfx_dev_contigs_from_text", out,
+        return self._grow_call(self.L.rfx_dev_contigs_from_text, "rfx_dev_contigs_from_text", out,
                                       lambda co: (d_text.data_ptr(), length, C.byref(co)))
 
     def contigs_to_text_dev(self, d: "ContigsPacked", min_contig=500, d_text=None):
@@ -1596,7 +1561,7 @@ class Reflexiv:
         """rfx_dev_dedup_contigs: the three rounds, packed in, packed out -> (ContigsPacked, [contigs after round 1, 2, 3])"""
         ci = d._c()
         rn = (C.c_int64 * 3)()
-        out = self._contigs_dev_call(self.L.rfx_dev_dedup_contigs, "rfx_dev_dedup_contigs", out or ContigsPacked(d.n, d.words),
+        out = self._grow_call(self.L.rfx_dev_dedup_contigs, "rfx_dev_dedup_contigs", out or ContigsPacked(d.n, d.words),
                                      lambda co: (C.byref(ci), C.byref(co), C.addressof(rn)))
         return out, [int(x) for x in rn]
 

@@ -1578,421 +1578,3 @@ int rfx_assemble_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_o
 } RFX_API_CATCH(ctx)
 
 }  // extern "C"
-
-// ---- the second contig fixing stage (rfx_fixing2.hip) -----------------------------------------------------------
-namespace {
-bool fx2_contigs_ok(const rfx_contigs_packed *p) { return p && p->words && p->word_off && p->len; }
-int fx2_params(rfx_ctx *ctx, const rfx_fix_params *p, int P, const char *stage = "contig fixing, round two") {
-    if (!p || !parts_ok(P)) return RFX_E_ARG;
-    if (p->max_k < 31 || p->max_k > 124) { ctx->last_error = std::string(stage) + ": max_k must be 31..124"; return RFX_E_ARG; }
-    if (p->max_iteration < -1) { ctx->last_error = std::string(stage) + ": max_iteration below -1"; return RFX_E_ARG; }
-    return RFX_OK;
-}
-int fx2_text_call(rfx_ctx *ctx, int ends, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, char *d_text, int64_t cap,
-                  int64_t *out_len) {
-    if (!ctx || !fx2_contigs_ok(d_in) || d_in->n < 0 || (ends != 2 && d_in->n > 0 && (!d_left || !d_right)) || !out_len || cap < 0 || (cap > 0 && !d_text))
-        return RFX_E_ARG;
-    RFX_HIP(hipSetDevice(ctx->device));
-    const Fx2View v{d_in->n, d_in->words, d_in->word_off, d_in->len, d_left, d_right};
-    int64_t total = 0;
-    RFX_TRY(fx2_text(ctx, v, ends, d_text, cap, &total, nullptr));
-    *out_len = total;
-    return total > cap ? RFX_E_CAP : RFX_OK;
-}
-// the front of the host forms of 05FixingAgain and 09ExtendAgain: one upload, binarize, run, the contigs in the library's buffers
-struct Fx2Contigs { DevBuf w, woff, len, left, right; int64_t m = 0; };
-int fx2_contigs_of_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, Fx2Contigs &c) {
-    DevBuf d_text, d_off;
-    DynDev a, b;
-    Fx2Plan plan;
-    RFX_TRY(dyn_upload_text(ctx, text, row_off, n_rows, d_text, d_off));
-    RFX_TRY(fx2_binarize(ctx, (const char *)d_text.p, d_off.as<int64_t>(), n_rows, a));
-    RFX_TRY(fx2_run(ctx, a, P, params->scramble, params->max_iteration, b));
-    RFX_TRY(fx2_contigs_plan(ctx, b, params->max_k, plan));
-    const size_t m = (size_t)std::max<int64_t>(plan.m, 1);
-    RFX_ALLOC(c.w, uint64_t, std::max<int64_t>(plan.words, 1)); RFX_ALLOC(c.woff, int64_t, m + 1);
-    RFX_ALLOC(c.len, int64_t, m); RFX_ALLOC(c.left, int32_t, m); RFX_ALLOC(c.right, int32_t, m);
-    RFX_TRY(fx2_contigs_fill(ctx, b, plan, c.w.as<uint64_t>(), c.woff.as<int64_t>(), c.len.as<int64_t>(), c.left.as<int32_t>(), c.right.as<int32_t>()));
-    c.m = plan.m;
-    return RFX_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int rfx_dev_fix2_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, rfx_dyn_packed *d_out) try {
-    if (!ctx || !dyn_packed_out_ok(d_out) || !text_rows_ok(d_text, d_row_off, n_rows)) return RFX_E_ARG;
-    RFX_HIP(hipSetDevice(ctx->device));
-    DynDev a;
-    RFX_TRY(fx2_binarize(ctx, d_text, d_row_off, n_rows, a));
-    return dyn_store(ctx, a, d_out);
-} RFX_API_CATCH(ctx)
-
-int rfx_dev_fix2_run(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int P, const rfx_fix_params *params, rfx_dyn_packed *d_out) try {
-    if (!ctx || !dyn_packed_out_ok(d_in) || d_in->n < 0 || !dyn_packed_out_ok(d_out)) return RFX_E_ARG;
-    RFX_TRY(fx2_params(ctx, params, P));
-    RFX_HIP(hipSetDevice(ctx->device));
-    DynDev a, b;
-    RFX_TRY(dyn_borrow(ctx, d_in, a));
-    RFX_TRY(fx2_run(ctx, a, P, params->scramble, params->max_iteration, b));
-    return dyn_store(ctx, b, d_out);
-} RFX_API_CATCH(ctx)
-
-int rfx_dev_fix2_contigs(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rfx_fix_params *params, rfx_contigs_packed *d_out, int32_t *d_left,
-                         int32_t *d_right) try {
-    if (!ctx || !dyn_packed_out_ok(d_in) || d_in->n < 0 || !fx2_contigs_ok(d_out) || !d_left || !d_right) return RFX_E_ARG;
-    RFX_TRY(fx2_params(ctx, params, 1));
-    RFX_HIP(hipSetDevice(ctx->device));
-    DynDev a;
-    Fx2Plan plan;
-    RFX_TRY(dyn_borrow(ctx, d_in, a));
-    RFX_TRY(fx2_contigs_plan(ctx, a, params->max_k, plan));
-    d_out->need_n = plan.m; d_out->need_words = plan.words;
-    if (plan.m > d_out->cap_n || plan.words > d_out->cap_words) return RFX_E_CAP;       // (nothing written)
-    RFX_TRY(fx2_contigs_fill(ctx, a, plan, d_out->words, d_out->word_off, d_out->len, d_left, d_right));
-    d_out->n = plan.m;
-    return sync_checked(ctx);
-} RFX_API_CATCH(ctx)
-
-int rfx_dev_fix2_to_text(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, char *d_text, int64_t cap,
-                         int64_t *out_len) try {
-    return fx2_text_call(ctx, 0, d_in, d_left, d_right, d_text, cap, out_len);
-} RFX_API_CATCH(ctx)
-
-int rfx_dev_fix2_ends_text(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, char *d_text, int64_t cap,
-                           int64_t *out_len) try {
-    return fx2_text_call(ctx, 1, d_in, d_left, d_right, d_text, cap, out_len);
-} RFX_API_CATCH(ctx)
-
-// host text in, both host texts out; everything between packed and in HBM: one upload, binarize, run, the contigs, both texts, one
-// copy back each.  A short buffer: RFX_E_CAP with BOTH lengths set and NEITHER buffer written
-int rfx_fix2_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
-                  int64_t *out_len, char *ends_out, int64_t ends_cap, int64_t *ends_len) try {
-    if (!ctx || !text_rows_ok(text, row_off, n_rows) || !out_len || !ends_len || cap < 0 || (cap > 0 && !out) || ends_cap < 0 ||
-        (ends_cap > 0 && !ends_out))
-        return RFX_E_ARG;
-    RFX_TRY(fx2_params(ctx, params, P));
-    RFX_HIP(hipSetDevice(ctx->device));
-    DevBuf d_rows, d_ends;
-    Fx2Contigs c;
-    int64_t t_rows = 0, t_ends = 0;
-    RFX_TRY(fx2_contigs_of_text(ctx, text, row_off, n_rows, P, params, c));
-    const Fx2View v{c.m, c.w.as<uint64_t>(), c.woff.as<int64_t>(), c.len.as<int64_t>(), c.left.as<int32_t>(), c.right.as<int32_t>()};
-    RFX_TRY(fx2_text(ctx, v, 0, nullptr, 0, &t_rows, &d_rows));
-    RFX_TRY(fx2_text(ctx, v, 1, nullptr, 0, &t_ends, &d_ends));
-    return text_to_host(ctx, {{d_rows, t_rows, out, cap, out_len}, {d_ends, t_ends, ends_out, ends_cap, ends_len}}, false);
-} RFX_API_CATCH(ctx)
-
-}  // extern "C"
-
-// ---- the end extension of contigs from alignment rows (rfx_endext.hip) -------------------------------------------
-namespace {
-bool ee_set_ok(const rfx_endext_set *s) {
-    return s && fx2_contigs_ok(&s->set) && s->left && s->right && s->left_len && s->right_len && s->flags && s->src_idx && s->new_idx;
-}
-bool ee_cons_ok(const rfx_endext_consensus *c) { return c && fx2_contigs_ok(&c->left) && fx2_contigs_ok(&c->right) && c->flags; }
-bool ee_max_k(rfx_ctx *ctx, int max_k) {
-    if (max_k >= 31 && max_k <= 124) return true;
-    ctx->last_error = "end extension: max_k must be 31..124";
-    return false;
-}
-}  // namespace
-
-extern "C" {
-
-// SAMString2ROW (:369-388) + DSProcessSAMandExtendContigs (:564-994) of P/ReflexivDSDynamicKmerMapping.java
-int rfx_dev_endext_consensus(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, const char *d_text,
-                             const int64_t *d_row_off, int64_t n_rows, rfx_endext_consensus *d_out) try {
-    if (!ctx || !fx2_contigs_ok(d_in) || d_in->n < 0 || (d_in->n > 0 && (!d_left || !d_right)) || !text_rows_ok(d_text, d_row_off, n_rows) ||
-        !ee_cons_ok(d_out))
-        return RFX_E_ARG;
-    RFX_HIP(hipSetDevice(ctx->device));
-    const Fx2View v{d_in->n, d_in->words, d_in->word_off, d_in->len, d_left, d_right};
-    EeConsPlan plan;
-    RFX_TRY(ee_consensus_plan(ctx, v, d_text, d_row_off, n_rows, plan));
-    d_out->left.need_n = d_out->right.need_n = plan.n;
-    d_out->left.need_words = plan.lwords; d_out->right.need_words = plan.rwords;
-    if (plan.n > d_out->left.cap_n || plan.n > d_out->right.cap_n || plan.lwords > d_out->left.cap_words || plan.rwords > d_out->right.cap_words)
-        return RFX_E_CAP;                                           // (nothing written)
-    RFX_TRY(ee_consensus_fill(ctx, plan, EeConsOut{d_out->left.words, d_out->left.word_off, d_out->left.len, d_out->right.words,
-                                                   d_out->right.word_off, d_out->right.len, d_out->flags}));
-    d_out->left.n = d_out->right.n = plan.n;
-    return sync_checked(ctx);
-} RFX_API_CATCH(ctx)
-
-// the union, sort("ID") (:320-331), DSExtendContigs (:413-562), the index and filter of TagStringContigRDDID (:1268-1286)
-int rfx_dev_endext_contigs(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right,
-                           const rfx_endext_consensus *d_cons, int max_k, rfx_endext_set *d_out) try {
-    if (!ctx || !fx2_contigs_ok(d_in) || d_in->n < 0 || (d_in->n > 0 && (!d_left || !d_right)) || !ee_cons_ok(d_cons) || d_cons->left.n != d_in->n ||
-        d_cons->right.n != d_in->n || !ee_set_ok(d_out) || !ee_max_k(ctx, max_k))
-        return RFX_E_ARG;
-    RFX_HIP(hipSetDevice(ctx->device));
-    const Fx2View v{d_in->n, d_in->words, d_in->word_off, d_in->len, d_left, d_right};
-    const EeConsIn c{d_cons->left.words, d_cons->left.word_off, d_cons->left.len, d_cons->right.words, d_cons->right.word_off, d_cons->right.len,
-                     d_cons->flags};
-    EePlan plan;
-    RFX_TRY(ee_contigs_plan(ctx, v, c, max_k, plan));
-    d_out->set.need_n = plan.m; d_out->set.need_words = plan.words;
-    if (plan.m > d_out->set.cap_n || plan.words > d_out->set.cap_words) return RFX_E_CAP;       // (nothing written)
-    RFX_TRY(ee_contigs_fill(ctx, v, c, plan, EeSetOut{d_out->set.words, d_out->set.word_off, d_out->set.len, d_out->left, d_out->right, d_out->left_len,
-                                                      d_out->right_len, d_out->flags, d_out->src_idx, d_out->new_idx}));
-    d_out->set.n = plan.m;
-    return sync_checked(ctx);
-} RFX_API_CATCH(ctx)
-
-// zipWithIndex + TagStringContigRDDID (:1268-1286): the rows of 07EndExtend
-int rfx_dev_endext_to_text(rfx_ctx *ctx, const rfx_endext_set *d_in, char *d_text, int64_t cap, int64_t *out_len) try {
-    if (!ctx || !ee_set_ok(d_in) || d_in->set.n < 0 || !out_len || cap < 0 || (cap > 0 && !d_text)) return RFX_E_ARG;
-    RFX_HIP(hipSetDevice(ctx->device));
-    const EeSetIn s{d_in->set.n, d_in->set.words, d_in->set.word_off, d_in->set.len, d_in->left, d_in->right, d_in->left_len, d_in->right_len,
-                    d_in->flags, d_in->src_idx, d_in->new_idx};
-    int64_t total = 0;
-    RFX_TRY(ee_text(ctx, s, d_text, cap, &total, nullptr));
-    *out_len = total;
-    return total > cap ? RFX_E_CAP : RFX_OK;
-} RFX_API_CATCH(ctx)
-
-// host form of the driver behind the aligner (:305-347): the text of 05FixingAgain and the alignment rows in, 07EndExtend out;
-// everything between packed and in HBM: one upload each, consensus, splice and order, the text, one copy back
-int rfx_endext_text(rfx_ctx *ctx, const char *contig_text, const int64_t *contig_off, int64_t n_contigs, const char *row_text, const int64_t *row_off,
-                    int64_t n_rows, int max_k, char *out, int64_t cap, int64_t *out_len) try {
-    if (!ctx || !text_rows_ok(contig_text, contig_off, n_contigs) || !text_rows_ok(row_text, row_off, n_rows) || !out_len || cap < 0 || (cap > 0 && !out) ||
-        !ee_max_k(ctx, max_k))
-        return RFX_E_ARG;
-    if (n_contigs >= ((int64_t)1 << 31) || n_rows >= ((int64_t)1 << 31)) {       // (before an offset is read or a byte uploaded)
-        ctx->last_error = "end extension: 2^31 rows or contigs, or more";
-        return RFX_E_LIMIT;
-    }
-    RFX_HIP(hipSetDevice(ctx->device));
-    DevBuf d_ct, d_co, d_rt, d_ro, w, woff, len, left, right, d_rows;
-    RFX_TRY(dyn_upload_text(ctx, contig_text, contig_off, n_contigs, d_ct, d_co));
-    RFX_TRY(dyn_upload_text(ctx, row_text, row_off, n_rows, d_rt, d_ro));
-    RFX_TRY(ee_contigs_from_rows(ctx, (const char *)d_ct.p, d_co.as<int64_t>(), n_contigs, w, woff, len, left, right));
-    const Fx2View v{n_contigs, w.as<uint64_t>(), woff.as<int64_t>(), len.as<int64_t>(), left.as<int32_t>(), right.as<int32_t>()};
-    EeConsPlan cp;
-    RFX_TRY(ee_consensus_plan(ctx, v, (const char *)d_rt.p, d_ro.as<int64_t>(), n_rows, cp));
-    const size_t n1 = (size_t)std::max<int64_t>(n_contigs, 1);
-    DevBuf lw, lwoff, llen, rw, rwoff, rlen, cflags;
-    RFX_ALLOC(lw, uint64_t, std::max<int64_t>(cp.lwords, 1)); RFX_ALLOC(lwoff, int64_t, n1 + 1); RFX_ALLOC(llen, int64_t, n1);
-    RFX_ALLOC(rw, uint64_t, std::max<int64_t>(cp.rwords, 1)); RFX_ALLOC(rwoff, int64_t, n1 + 1); RFX_ALLOC(rlen, int64_t, n1);
-    RFX_ALLOC(cflags, int32_t, n1);
-    RFX_TRY(ee_consensus_fill(ctx, cp, EeConsOut{lw.as<uint64_t>(), lwoff.as<int64_t>(), llen.as<int64_t>(), rw.as<uint64_t>(), rwoff.as<int64_t>(),
-                                                 rlen.as<int64_t>(), cflags.as<int32_t>()}));
-    const EeConsIn c{lw.as<uint64_t>(), lwoff.as<int64_t>(), llen.as<int64_t>(), rw.as<uint64_t>(), rwoff.as<int64_t>(), rlen.as<int64_t>(),
-                     cflags.as<int32_t>()};
-    EePlan plan;
-    RFX_TRY(ee_contigs_plan(ctx, v, c, max_k, plan));
-    const size_t m1 = (size_t)std::max<int64_t>(plan.m, 1);
-    DevBuf ow, owoff, olen, o32;
-    RFX_ALLOC(ow, uint64_t, std::max<int64_t>(plan.words, 1)); RFX_ALLOC(owoff, int64_t, m1 + 1); RFX_ALLOC(olen, int64_t, m1);
-    RFX_ALLOC(o32, int32_t, 7 * m1);
-    int32_t *a = o32.as<int32_t>();
-    RFX_TRY(ee_contigs_fill(ctx, v, c, plan, EeSetOut{ow.as<uint64_t>(), owoff.as<int64_t>(), olen.as<int64_t>(), a, a + m1, a + 2 * m1, a + 3 * m1,
-                                                      a + 4 * m1, a + 5 * m1, a + 6 * m1}));
-    const EeSetIn s{plan.m, ow.as<uint64_t>(), owoff.as<int64_t>(), olen.as<int64_t>(), a, a + m1, a + 2 * m1, a + 3 * m1, a + 4 * m1, a + 5 * m1,
-                    a + 6 * m1};
-    int64_t total = 0;
-    RFX_TRY(ee_text(ctx, s, nullptr, 0, &total, &d_rows));
-    return text_to_host(ctx, {{d_rows, total, out, cap, out_len}}, false);
-} RFX_API_CATCH(ctx)
-
-}  // extern "C"
-
-// ---- the contig extension stages (rfx_ctgext.hip) ---------------------------------------------------------------
-namespace {
-const char *const EX_STAGE = "contig extension";
-EeSetIn ex_set_in(const rfx_endext_set *s) {
-    return EeSetIn{s->set.n, s->set.words, s->set.word_off, s->set.len, s->left, s->right, s->left_len, s->right_len, s->flags, s->src_idx, s->new_idx};
-}
-// the rows of 07EndExtend in HBM -> a set in the library's buffers (i32: seven arrays of max(m, 1) entries)
-struct ExSetBufs { DevBuf w, woff, len, i32; };
-int ex_set_of_rows(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, int max_k, ExSetBufs &b, EeSetIn *s) {
-    ExRowsPlan plan;
-    RFX_TRY(ex_rows_plan(ctx, d_text, d_row_off, n_rows, max_k, plan));
-    const size_t m1 = (size_t)std::max<int64_t>(plan.m, 1);
-    RFX_ALLOC(b.w, uint64_t, std::max<int64_t>(plan.words, 1)); RFX_ALLOC(b.woff, int64_t, m1 + 1); RFX_ALLOC(b.len, int64_t, m1);
-    RFX_ALLOC(b.i32, int32_t, 7 * m1);
-    int32_t *a = b.i32.as<int32_t>();
-    RFX_TRY(ex_rows_fill(ctx, d_text, plan, EeSetOut{b.w.as<uint64_t>(), b.woff.as<int64_t>(), b.len.as<int64_t>(), a, a + m1, a + 2 * m1, a + 3 * m1,
-                                                     a + 4 * m1, a + 5 * m1, a + 6 * m1}));
-    *s = EeSetIn{plan.m, b.w.as<uint64_t>(), b.woff.as<int64_t>(), b.len.as<int64_t>(), a, a + m1, a + 2 * m1, a + 3 * m1, a + 4 * m1, a + 5 * m1, a + 6 * m1};
-    return RFX_OK;
-}
-}  // namespace
-
-extern "C" {
-
-// DynamicKmerBinarizerFromReducedToSubKmer of P/ReflexivDSDynamicKmerExtend.java (:3118-3219), up to the packed set
-int rfx_dev_ext_from_text(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, const rfx_fix_params *params, rfx_endext_set *d_out) try {
-    if (!ctx || !text_rows_ok(d_text, d_row_off, n_rows) || !ee_set_ok(d_out)) return RFX_E_ARG;
-    RFX_TRY(fx2_params(ctx, params, 1, EX_STAGE));
-    RFX_HIP(hipSetDevice(ctx->device));
-    ExRowsPlan plan;
-    RFX_TRY(ex_rows_plan(ctx, d_text, d_row_off, n_rows, params->max_k, plan));
-    d_out->set.need_n = plan.m; d_out->set.need_words = plan.words;
-    if (plan.m > d_out->set.cap_n || plan.words > d_out->set.cap_words) return RFX_E_CAP;       // (nothing written)
-    RFX_TRY(ex_rows_fill(ctx, d_text, plan, EeSetOut{d_out->set.words, d_out->set.word_off, d_out->set.len, d_out->left, d_out->right, d_out->left_len,
-                                                     d_out->right_len, d_out->flags, d_out->src_idx, d_out->new_idx}));
-    d_out->set.n = plan.m;
-    return sync_checked(ctx);
-} RFX_API_CATCH(ctx)
-
-// DSExtractFixingKmerFromContigEnds (:1189-1267) + DSgetFixingLongKmer (:514-535) + DSgetFixingKmer (:853-870)
-int rfx_dev_ext_contig_ends(rfx_ctx *ctx, const rfx_endext_set *d_in, const rfx_fix_params *params, rfx_dyn_packed *d_out_long, uint64_t *d_kmers,
-                            int64_t cap_kmers, int64_t *n_kmers) try {
-    if (!ctx || !ee_set_ok(d_in) || d_in->set.n < 0 || !dyn_packed_out_ok(d_out_long) || !n_kmers || cap_kmers < 0 || (cap_kmers > 0 && !d_kmers)) return RFX_E_ARG;
-    RFX_TRY(fx2_params(ctx, params, 1, EX_STAGE));
-    RFX_HIP(hipSetDevice(ctx->device));
-    DynDev b;
-    DevBuf kmers;
-    int64_t n31 = 0;
-    RFX_TRY(ex_contig_ends(ctx, ex_set_in(d_in), params->max_k, b, kmers, &n31));
-    return fx_ends_store(ctx, b, kmers, n31, d_out_long, d_kmers, cap_kmers, n_kmers);
-} RFX_API_CATCH(ctx)
-
-// the driver of 08Extend (:125-254) behind its binarizer, the set resident between the operators
-int rfx_dev_ext_run(rfx_ctx *ctx, const rfx_endext_set *d_in, int P, const rfx_fix_params *params, rfx_dyn_packed *d_out) try {
-    if (!ctx || !ee_set_ok(d_in) || d_in->set.n < 0 || !dyn_packed_out_ok(d_out)) return RFX_E_ARG;
-    RFX_TRY(fx2_params(ctx, params, P, EX_STAGE));
-    RFX_HIP(hipSetDevice(ctx->device));
-    DynDev lng, out;
-    DevBuf kmers;
-    int64_t n31 = 0;
-    RFX_TRY(ex_contig_ends(ctx, ex_set_in(d_in), params->max_k, lng, kmers, &n31));
-    RFX_TRY(fx_from_ends(ctx, kmers.as<uint64_t>(), n31, lng, P, params->scramble, params->max_iteration, out));
-    return dyn_store(ctx, out, d_out);
-} RFX_API_CATCH(ctx)
-
-// host form of the driver of 08Extend (:125-254): the text of 07EndExtend in, the text of 08Extend out; everything between packed and in
-// HBM: one upload, the set, the contig ends, the fixing stage's steps 4-9, the text, one copy back
-int rfx_ext_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
-                 int64_t *out_len) try {
-    if (!ctx || !text_rows_ok(text, row_off, n_rows) || !out_len || cap < 0 || (cap > 0 && !out)) return RFX_E_ARG;
-    RFX_TRY(fx2_params(ctx, params, P, EX_STAGE));
-    if (n_rows >= ((int64_t)1 << 31)) { ctx->last_error = "contig extension: 2^31 rows or more"; return RFX_E_LIMIT; }      // (before a byte is uploaded)
-    RFX_HIP(hipSetDevice(ctx->device));
-    DevBuf d_text, d_off, kmers, d_o;
-    ExSetBufs bufs;
-    EeSetIn s{};
-    DynDev lng, a;
-    int64_t n31 = 0, total = 0;
-    RFX_TRY(dyn_upload_text(ctx, text, row_off, n_rows, d_text, d_off));
-    RFX_TRY(ex_set_of_rows(ctx, (const char *)d_text.p, d_off.as<int64_t>(), n_rows, params->max_k, bufs, &s));
-    RFX_TRY(ex_contig_ends(ctx, s, params->max_k, lng, kmers, &n31));
-    RFX_TRY(fx_from_ends(ctx, kmers.as<uint64_t>(), n31, lng, P, params->scramble, params->max_iteration, a));
-    RFX_TRY(dyn_to_text(ctx, a, nullptr, 0, &total, &d_o));
-    return text_to_host(ctx, {{d_o, total, out, cap, out_len}}, false);
-} RFX_API_CATCH(ctx)
-
-// zipWithIndex + TagRowContigRDDID of P/ReflexivDSDynamicKmerExtendRoundTwo.java (:674-692): the rows of 09ExtendAgain
-int rfx_dev_ext2_to_text(rfx_ctx *ctx, const rfx_contigs_packed *d_in, char *d_text, int64_t cap, int64_t *out_len) try {
-    return fx2_text_call(ctx, 2, d_in, nullptr, nullptr, d_text, cap, out_len);
-} RFX_API_CATCH(ctx)
-
-// host form of the driver of 09ExtendAgain (:125-221): the text of 08Extend in, the text of 09ExtendAgain out; one upload, the second
-// fixing stage's binarizer, loop and contigs (DSBinaryFixingKmerToFullKmer :415-456), the text, one copy back
-int rfx_ext2_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
-                  int64_t *out_len) try {
-    if (!ctx || !text_rows_ok(text, row_off, n_rows) || !out_len || cap < 0 || (cap > 0 && !out)) return RFX_E_ARG;
-    RFX_TRY(fx2_params(ctx, params, P, "contig extension, round two"));
-    if (n_rows >= ((int64_t)1 << 31)) { ctx->last_error = "contig extension, round two: 2^31 rows or more"; return RFX_E_LIMIT; }      // (before an offset is read)
-    RFX_HIP(hipSetDevice(ctx->device));
-    DevBuf d_rows;
-    Fx2Contigs c;
-    int64_t total = 0;
-    RFX_TRY(fx2_contigs_of_text(ctx, text, row_off, n_rows, P, params, c));
-    const Fx2View v{c.m, c.w.as<uint64_t>(), c.woff.as<int64_t>(), c.len.as<int64_t>(), nullptr, nullptr};
-    RFX_TRY(fx2_text(ctx, v, 2, nullptr, 0, &total, &d_rows));
-    return text_to_host(ctx, {{d_rows, total, out, cap, out_len}}, false);
-} RFX_API_CATCH(ctx)
-
-}  // extern "C"
-
-// ---- reads onto the contig ends (rfx_endmap.hip) ----------------------------------------------------------------
-namespace {
-bool mp_hits_ok(const rfx_map_hits *h) { return h && h->read && h->end && h->strand && h->offset && h->v && h->cap_n >= 0; }
-bool mp_contigs_ok(const rfx_contigs_packed *c, const int32_t *d_left, const int32_t *d_right) {
-    return fx2_contigs_ok(c) && c->n >= 0 && (c->n == 0 || (d_left && d_right));
-}
-}  // namespace
-
-extern "C" {
-
-void rfx_map_default_params(rfx_map_params *p) try {
-    if (!p) return;
-    p->seed = 21; p->min_overlap = 31; p->max_mismatch = 2;
-} RFX_API_CATCH_VOID(nullptr)
-
-int rfx_dev_map_ends(rfx_ctx *ctx, const rfx_contigs_packed *d_contigs, const int32_t *d_left, const int32_t *d_right, const uint64_t *d_words,
-                     const uint32_t *d_read_len, int64_t n_reads, int words_per_read, const rfx_map_params *params, rfx_map_hits *d_out) try {
-    if (!ctx || !mp_contigs_ok(d_contigs, d_left, d_right) || n_reads < 0 || (n_reads > 0 && (!d_words || !d_read_len)) || words_per_read < 1 ||
-        !mp_hits_ok(d_out) || !mp_params_ok(ctx, params))
-        return RFX_E_ARG;
-    RFX_HIP(hipSetDevice(ctx->device));
-    const Fx2View v{d_contigs->n, d_contigs->words, d_contigs->word_off, d_contigs->len, d_left, d_right};
-    MpPlan plan;
-    RFX_TRY(mp_plan(ctx, v, d_words, d_read_len, n_reads, words_per_read, *params, plan));
-    d_out->need_n = plan.hits;
-    if (plan.hits > d_out->cap_n) return RFX_E_CAP;                 // (nothing written)
-    RFX_TRY(mp_fill(ctx, v, d_words, d_read_len, n_reads, words_per_read, *params, plan, MpHits{d_out->read, d_out->end, d_out->strand, d_out->offset, d_out->v}));
-    d_out->n = plan.hits; d_out->seed = params->seed;
-    return sync_checked(ctx);
-} RFX_API_CATCH(ctx)
-
-int rfx_dev_map_to_text(rfx_ctx *ctx, const rfx_contigs_packed *d_contigs, const int32_t *d_left, const int32_t *d_right, const uint64_t *d_words,
-                        const uint32_t *d_read_len, int words_per_read, const rfx_map_hits *hits, char *d_text, int64_t cap, int64_t *out_len,
-                        int64_t *d_row_off, int64_t cap_rows) try {
-    if (!ctx || !mp_contigs_ok(d_contigs, d_left, d_right) || words_per_read < 1 || !mp_hits_ok(hits) || hits->n < 0 || hits->n > hits->cap_n ||
-        (hits->n > 0 && (!d_words || !d_read_len || hits->seed < 11 || hits->seed > 31)) || !out_len || cap < 0 || (cap > 0 && !d_text) || !d_row_off ||
-        cap_rows < 0)
-        return RFX_E_ARG;
-    RFX_HIP(hipSetDevice(ctx->device));
-    const Fx2View v{d_contigs->n, d_contigs->words, d_contigs->word_off, d_contigs->len, d_left, d_right};
-    const MpHits h{hits->read, hits->end, hits->strand, hits->offset, hits->v};
-    const bool rows_fit = cap_rows >= hits->n + 1;
-    int64_t total = 0;
-    // too few row offsets: the sizes only (a text buffer of 0 bytes takes nothing)
-    RFX_TRY(mp_text(ctx, v, d_words, d_read_len, words_per_read, h, hits->n, hits->seed, d_text, rows_fit ? cap : 0, &total, rows_fit ? d_row_off : nullptr,
-                    nullptr));
-    *out_len = total;
-    return total > cap || !rows_fit ? RFX_E_CAP : RFX_OK;
-} RFX_API_CATCH(ctx)
-
-// host form: the text of 05FixingAgain and ASCII reads in, the row text out; everything between packed and in HBM: one upload each, the
-// contigs and the read store, the index, both passes, the text, one copy back
-int rfx_map_text(rfx_ctx *ctx, const char *contig_text, const int64_t *contig_off, int64_t n_contigs, const uint8_t *bases, const int64_t *read_off,
-                 int64_t n_reads, const rfx_map_params *params, char *out, int64_t cap, int64_t *out_len) try {
-    if (!ctx || !text_rows_ok(contig_text, contig_off, n_contigs) || !text_rows_ok((const char *)bases, read_off, n_reads) || !out_len || cap < 0 ||
-        (cap > 0 && !out) || !mp_params_ok(ctx, params))
-        return RFX_E_ARG;
-    if (n_contigs >= ((int64_t)1 << 29) || n_reads >= ((int64_t)1 << 31)) {       // (before an offset is read or a byte uploaded)
-        ctx->last_error = "end mapping: 2^29 contigs or 2^31 reads, or more";
-        return RFX_E_LIMIT;
-    }
-    int64_t longest = 1;
-    for (int64_t i = 0; i < n_reads; i++) longest = std::max(longest, read_off[i + 1] - read_off[i]);
-    if (longest >= ((int64_t)1 << 30)) { ctx->last_error = "end mapping: a read of 2^30 bases or more"; return RFX_E_LIMIT; }
-    RFX_HIP(hipSetDevice(ctx->device));
-    const int wpr = (int)((longest + 31) >> 5);
-    DevBuf d_ct, d_co, d_b, d_ro, w, woff, len, left, right, d_words, d_len, d_rows;
-    RFX_TRY(dyn_upload_text(ctx, contig_text, contig_off, n_contigs, d_ct, d_co));
-    RFX_TRY(dyn_upload_text(ctx, (const char *)bases, read_off, n_reads, d_b, d_ro));
-    RFX_TRY(ee_contigs_from_rows(ctx, (const char *)d_ct.p, d_co.as<int64_t>(), n_contigs, w, woff, len, left, right));
-    const int64_t r1 = std::max<int64_t>(n_reads, 1);
-    RFX_ALLOC(d_words, uint64_t, r1 * wpr); RFX_ALLOC(d_len, uint32_t, r1);
-    if (n_reads > 0) RFX_TRY(encode_reads(ctx, d_b.as<uint8_t>(), d_ro.as<int64_t>(), n_reads, wpr, d_words.as<uint64_t>(), d_len.as<uint32_t>()));
-    const Fx2View v{n_contigs, w.as<uint64_t>(), woff.as<int64_t>(), len.as<int64_t>(), left.as<int32_t>(), right.as<int32_t>()};
-    MpPlan plan;
-    RFX_TRY(mp_plan(ctx, v, d_words.as<uint64_t>(), d_len.as<uint32_t>(), n_reads, wpr, *params, plan));
-    const size_t h1 = (size_t)std::max<int64_t>(plan.hits, 1);
-    DevBuf h32;
-    RFX_ALLOC(h32, int32_t, 5 * h1);
-    int32_t *a = h32.as<int32_t>();
-    const MpHits h{a, a + h1, a + 2 * h1, a + 3 * h1, a + 4 * h1};
-    RFX_TRY(mp_fill(ctx, v, d_words.as<uint64_t>(), d_len.as<uint32_t>(), n_reads, wpr, *params, plan, h));
-    int64_t total = 0;
-    RFX_TRY(mp_text(ctx, v, d_words.as<uint64_t>(), d_len.as<uint32_t>(), wpr, h, plan.hits, params->seed, nullptr, 0, &total, nullptr, &d_rows));
-    return text_to_host(ctx, {{d_rows, total, out, cap, out_len}}, false);
-} RFX_API_CATCH(ctx)
-
-}  // extern "C"

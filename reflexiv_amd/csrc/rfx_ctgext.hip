@@ -242,3 +242,100 @@ int rfx::ex_contig_ends(rfx_ctx *ctx, const EeSetIn &s, int max_k, DynDev &out, 
     RFX_LAUNCH_N(k_ex_ends_long, PK_KW * m + words, s, loff.as<uint64_t>(), woff.as<uint64_t>(), dyn_out(out));
     return RFX_OK;
 }
+
+// ---- the entry points ------------------------------------------------------------------------------------------------------------
+namespace {
+const char *const EX_STAGE = "contig extension";
+// the rows of 07EndExtend in HBM -> a set in the library's buffers
+int ex_set_of_rows(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, int max_k, EeSetDev &s) {
+    ExRowsPlan plan;
+    RFX_TRY(ex_rows_plan(ctx, d_text, d_row_off, n_rows, max_k, plan));
+    RFX_TRY(ee_set_alloc(ctx, s, plan.m, plan.words));
+    return ex_rows_fill(ctx, d_text, plan, ee_set_out(s));
+}
+}  // namespace
+
+extern "C" {
+
+// DynamicKmerBinarizerFromReducedToSubKmer of P/ReflexivDSDynamicKmerExtend.java (:3118-3219), up to the packed set
+int rfx_dev_ext_from_text(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, const rfx_fix_params *params, rfx_endext_set *d_out) try {
+    if (!ctx || !text_rows_ok(d_text, d_row_off, n_rows) || !ee_set_ok(d_out)) return RFX_E_ARG;
+    RFX_TRY(fx2_params(ctx, params, 1, EX_STAGE));
+    RFX_HIP(hipSetDevice(ctx->device));
+    ExRowsPlan plan;
+    RFX_TRY(ex_rows_plan(ctx, d_text, d_row_off, n_rows, params->max_k, plan));
+    if (!packed_out_fits(&d_out->set, plan.m, plan.words)) return RFX_E_CAP;
+    RFX_TRY(ex_rows_fill(ctx, d_text, plan, ee_set_out(d_out)));
+    d_out->set.n = plan.m;
+    return sync_checked(ctx);
+} RFX_API_CATCH(ctx)
+
+// DSExtractFixingKmerFromContigEnds (:1189-1267) + DSgetFixingLongKmer (:514-535) + DSgetFixingKmer (:853-870)
+int rfx_dev_ext_contig_ends(rfx_ctx *ctx, const rfx_endext_set *d_in, const rfx_fix_params *params, rfx_dyn_packed *d_out_long, uint64_t *d_kmers,
+                            int64_t cap_kmers, int64_t *n_kmers) try {
+    if (!ctx || !ee_set_ok(d_in) || d_in->set.n < 0 || !dyn_packed_out_ok(d_out_long) || !n_kmers || cap_kmers < 0 || (cap_kmers > 0 && !d_kmers)) return RFX_E_ARG;
+    RFX_TRY(fx2_params(ctx, params, 1, EX_STAGE));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev b;
+    DevBuf kmers;
+    int64_t n31 = 0;
+    RFX_TRY(ex_contig_ends(ctx, ee_set_in(d_in), params->max_k, b, kmers, &n31));
+    return fx_ends_store(ctx, b, kmers, n31, d_out_long, d_kmers, cap_kmers, n_kmers);
+} RFX_API_CATCH(ctx)
+
+// the driver of 08Extend (:125-254) behind its binarizer, the set resident between the operators
+int rfx_dev_ext_run(rfx_ctx *ctx, const rfx_endext_set *d_in, int P, const rfx_fix_params *params, rfx_dyn_packed *d_out) try {
+    if (!ctx || !ee_set_ok(d_in) || d_in->set.n < 0 || !dyn_packed_out_ok(d_out)) return RFX_E_ARG;
+    RFX_TRY(fx2_params(ctx, params, P, EX_STAGE));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev lng, out;
+    DevBuf kmers;
+    int64_t n31 = 0;
+    RFX_TRY(ex_contig_ends(ctx, ee_set_in(d_in), params->max_k, lng, kmers, &n31));
+    RFX_TRY(fx_from_ends(ctx, kmers.as<uint64_t>(), n31, lng, P, params->scramble, params->max_iteration, out));
+    return dyn_store(ctx, out, d_out);
+} RFX_API_CATCH(ctx)
+
+// host form of the driver of 08Extend (:125-254): the text of 07EndExtend in, the text of 08Extend out; everything between packed and in
+// HBM: one upload, the set, the contig ends, the fixing stage's steps 4-9, the text, one copy back
+int rfx_ext_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
+                 int64_t *out_len) try {
+    if (!ctx || !text_rows_ok(text, row_off, n_rows) || !text_out_ok(out, cap, out_len)) return RFX_E_ARG;
+    RFX_TRY(fx2_params(ctx, params, P, EX_STAGE));
+    if (n_rows >= ((int64_t)1 << 31)) { ctx->last_error = "contig extension: 2^31 rows or more"; return RFX_E_LIMIT; }      // (before a byte is uploaded)
+    RFX_HIP(hipSetDevice(ctx->device));
+    DevBuf d_text, d_off, kmers, d_o;
+    EeSetDev set;
+    DynDev lng, a;
+    int64_t n31 = 0, total = 0;
+    RFX_TRY(dyn_upload_text(ctx, text, row_off, n_rows, d_text, d_off));
+    RFX_TRY(ex_set_of_rows(ctx, (const char *)d_text.p, d_off.as<int64_t>(), n_rows, params->max_k, set));
+    RFX_TRY(ex_contig_ends(ctx, ee_set_in(set), params->max_k, lng, kmers, &n31));
+    RFX_TRY(fx_from_ends(ctx, kmers.as<uint64_t>(), n31, lng, P, params->scramble, params->max_iteration, a));
+    RFX_TRY(dyn_to_text(ctx, a, nullptr, 0, &total, &d_o));
+    return text_to_host(ctx, {{d_o, total, out, cap, out_len}}, false);
+} RFX_API_CATCH(ctx)
+
+// zipWithIndex + TagRowContigRDDID of P/ReflexivDSDynamicKmerExtendRoundTwo.java (:674-692): the rows of 09ExtendAgain
+int rfx_dev_ext2_to_text(rfx_ctx *ctx, const rfx_contigs_packed *d_in, char *d_text, int64_t cap, int64_t *out_len) try {
+    return fx2_text_call(ctx, 2, d_in, nullptr, nullptr, d_text, cap, out_len);
+} RFX_API_CATCH(ctx)
+
+// host form of the driver of 09ExtendAgain (:125-221): the text of 08Extend in, the text of 09ExtendAgain out; one upload, the second
+// fixing stage's binarizer, loop and contigs (DSBinaryFixingKmerToFullKmer :415-456), the text (ends 2 reads neither left nor right),
+// one copy back
+int rfx_ext2_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
+                  int64_t *out_len) try {
+    if (!ctx || !text_rows_ok(text, row_off, n_rows) || !text_out_ok(out, cap, out_len)) return RFX_E_ARG;
+    RFX_TRY(fx2_params(ctx, params, P, "contig extension, round two"));
+    if (n_rows >= ((int64_t)1 << 31)) { ctx->last_error = "contig extension, round two: 2^31 rows or more"; return RFX_E_LIMIT; }      // (before an offset is read)
+    RFX_HIP(hipSetDevice(ctx->device));
+    DevBuf d_rows;
+    CtgDev c;
+    int64_t total = 0;
+    RFX_TRY(fx2_contigs_of_text(ctx, text, row_off, n_rows, P, params, c));
+    RFX_TRY(fx2_text(ctx, fx2_view(c), 2, nullptr, 0, &total, &d_rows));
+    return text_to_host(ctx, {{d_rows, total, out, cap, out_len}}, false);
+} RFX_API_CATCH(ctx)
+
+}  // extern "C"

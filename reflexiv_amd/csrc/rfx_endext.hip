@@ -586,29 +586,116 @@ int rfx::ee_text(rfx_ctx *ctx, const EeSetIn &s, char *d_text, int64_t cap, int6
 }
 
 // the rows of 05FixingAgain in HBM -> a packed contig set with left / right in the library's buffers
-int rfx::ee_contigs_from_rows(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, DevBuf &w, DevBuf &woff, DevBuf &len, DevBuf &left,
-                              DevBuf &right) {
+int rfx::ee_contigs_from_rows(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, CtgDev &c) {
     if (n >= ((int64_t)1 << 31)) { ctx->last_error = "end extension: 2^31 contigs or more"; return RFX_E_LIMIT; }
-    const int64_t m = std::max<int64_t>(n, 1);
-    RFX_ALLOC(woff, int64_t, m + 1); RFX_ALLOC(len, int64_t, m); RFX_ALLOC(left, int32_t, m); RFX_ALLOC(right, int32_t, m);
+    RFX_TRY(ctg_alloc_rows(ctx, c, n));
     if (n == 0) {
-        RFX_ALLOC(w, uint64_t, 1);
-        RFX_HIP(hipMemsetAsync(woff.p, 0, 8, ctx->stream));
+        RFX_TRY(ctg_alloc_words(ctx, c, 0));
+        RFX_HIP(hipMemsetAsync(c.woff.p, 0, 8, ctx->stream));
         return RFX_OK;
     }
     DevBuf bbeg, nw, off, flags;
     RFX_ALLOC(bbeg, int64_t, n); RFX_ALLOC(nw, uint32_t, n); RFX_ALLOC(off, uint64_t, n + 1);
     RFX_TRY(call_flags_init(ctx, flags));
-    RFX_LAUNCH_N(k_ee_ctg_parse, n, d_text, d_row_off, n, len.as<int64_t>(), left.as<int32_t>(), right.as<int32_t>(), bbeg.as<int64_t>(),
+    RFX_LAUNCH_N(k_ee_ctg_parse, n, d_text, d_row_off, n, c.len.as<int64_t>(), c.left.as<int32_t>(), c.right.as<int32_t>(), bbeg.as<int64_t>(),
                  nw.as<uint32_t>(), flags.as<CallFlags>());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, nw.as<uint32_t>(), off.as<uint64_t>(), n));
     CallFlags f{};
     RFX_TRY(call_flags_read(ctx, flags, off.as<uint64_t>() + n, nullptr, nullptr, &f));
     RFX_TRY(ee_bad(ctx, f.bad));
-    const int64_t words = (int64_t)f.total[0];
-    RFX_ALLOC(w, uint64_t, std::max<int64_t>(words, 1));
-    RFX_LAUNCH_N(k_ee_ctg_pack, std::max<int64_t>(words, n + 1), d_text, bbeg.as<int64_t>(), len.as<int64_t>(), off.as<uint64_t>(), n,
-                 w.as<uint64_t>(), woff.as<int64_t>(), flags.as<CallFlags>());
+    RFX_TRY(ctg_alloc_words(ctx, c, (int64_t)f.total[0]));
+    RFX_LAUNCH_N(k_ee_ctg_pack, std::max<int64_t>(c.words, n + 1), d_text, bbeg.as<int64_t>(), c.len.as<int64_t>(), off.as<uint64_t>(), n,
+                 c.w.as<uint64_t>(), c.woff.as<int64_t>(), flags.as<CallFlags>());
     RFX_TRY(call_flags_read(ctx, flags, nullptr, nullptr, nullptr, &f));      // (the scratch above is read until here)
     return ee_bad(ctx, f.bad);
 }
+
+// ---- the entry points ------------------------------------------------------------------------------------------------------------
+bool rfx::ee_set_ok(const rfx_endext_set *s) {
+    return s && fx2_contigs_ok(&s->set) && s->left && s->right && s->left_len && s->right_len && s->flags && s->src_idx && s->new_idx;
+}
+namespace {
+bool ee_cons_ok(const rfx_endext_consensus *c) { return c && fx2_contigs_ok(&c->left) && fx2_contigs_ok(&c->right) && c->flags; }
+bool ee_max_k(rfx_ctx *ctx, int max_k) {
+    if (max_k >= 31 && max_k <= 124) return true;
+    ctx->last_error = "end extension: max_k must be 31..124";
+    return false;
+}
+}  // namespace
+
+extern "C" {
+
+// SAMString2ROW (:369-388) + DSProcessSAMandExtendContigs (:564-994) of P/ReflexivDSDynamicKmerMapping.java
+int rfx_dev_endext_consensus(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, const char *d_text,
+                             const int64_t *d_row_off, int64_t n_rows, rfx_endext_consensus *d_out) try {
+    if (!ctx || !fx2_contigs_in_ok(d_in, d_left, d_right) || !text_rows_ok(d_text, d_row_off, n_rows) || !ee_cons_ok(d_out)) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    EeConsPlan plan;
+    RFX_TRY(ee_consensus_plan(ctx, fx2_view(d_in, d_left, d_right), d_text, d_row_off, n_rows, plan));
+    const bool lfits = packed_out_fits(&d_out->left, plan.n, plan.lwords), rfits = packed_out_fits(&d_out->right, plan.n, plan.rwords);
+    if (!lfits || !rfits) return RFX_E_CAP;
+    RFX_TRY(ee_consensus_fill(ctx, plan, ee_cons_out(d_out)));
+    d_out->left.n = d_out->right.n = plan.n;
+    return sync_checked(ctx);
+} RFX_API_CATCH(ctx)
+
+// the union, sort("ID") (:320-331), DSExtendContigs (:413-562), the index and filter of TagStringContigRDDID (:1268-1286)
+int rfx_dev_endext_contigs(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right,
+                           const rfx_endext_consensus *d_cons, int max_k, rfx_endext_set *d_out) try {
+    if (!ctx || !fx2_contigs_in_ok(d_in, d_left, d_right) || !ee_cons_ok(d_cons) || d_cons->left.n != d_in->n || d_cons->right.n != d_in->n ||
+        !ee_set_ok(d_out) || !ee_max_k(ctx, max_k))
+        return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    const Fx2View v = fx2_view(d_in, d_left, d_right);
+    EePlan plan;
+    RFX_TRY(ee_contigs_plan(ctx, v, ee_cons_in(d_cons), max_k, plan));
+    if (!packed_out_fits(&d_out->set, plan.m, plan.words)) return RFX_E_CAP;
+    RFX_TRY(ee_contigs_fill(ctx, v, ee_cons_in(d_cons), plan, ee_set_out(d_out)));
+    d_out->set.n = plan.m;
+    return sync_checked(ctx);
+} RFX_API_CATCH(ctx)
+
+// zipWithIndex + TagStringContigRDDID (:1268-1286): the rows of 07EndExtend
+int rfx_dev_endext_to_text(rfx_ctx *ctx, const rfx_endext_set *d_in, char *d_text, int64_t cap, int64_t *out_len) try {
+    if (!ctx || !ee_set_ok(d_in) || d_in->set.n < 0 || !text_out_ok(d_text, cap, out_len)) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    int64_t total = 0;
+    RFX_TRY(ee_text(ctx, ee_set_in(d_in), d_text, cap, &total, nullptr));
+    *out_len = total;
+    return total > cap ? RFX_E_CAP : RFX_OK;
+} RFX_API_CATCH(ctx)
+
+// host form of the driver behind the aligner (:305-347): the text of 05FixingAgain and the alignment rows in, 07EndExtend out;
+// everything between packed and in HBM: one upload each, consensus, splice and order, the text, one copy back
+int rfx_endext_text(rfx_ctx *ctx, const char *contig_text, const int64_t *contig_off, int64_t n_contigs, const char *row_text, const int64_t *row_off,
+                    int64_t n_rows, int max_k, char *out, int64_t cap, int64_t *out_len) try {
+    if (!ctx || !text_rows_ok(contig_text, contig_off, n_contigs) || !text_rows_ok(row_text, row_off, n_rows) || !text_out_ok(out, cap, out_len) ||
+        !ee_max_k(ctx, max_k))
+        return RFX_E_ARG;
+    if (n_contigs >= ((int64_t)1 << 31) || n_rows >= ((int64_t)1 << 31)) {       // (before an offset is read or a byte uploaded)
+        ctx->last_error = "end extension: 2^31 rows or contigs, or more";
+        return RFX_E_LIMIT;
+    }
+    RFX_HIP(hipSetDevice(ctx->device));
+    DevBuf d_ct, d_co, d_rt, d_ro, d_rows;
+    CtgDev ctg;
+    EeConsDev cons;
+    EeSetDev set;
+    RFX_TRY(dyn_upload_text(ctx, contig_text, contig_off, n_contigs, d_ct, d_co));
+    RFX_TRY(dyn_upload_text(ctx, row_text, row_off, n_rows, d_rt, d_ro));
+    RFX_TRY(ee_contigs_from_rows(ctx, (const char *)d_ct.p, d_co.as<int64_t>(), n_contigs, ctg));
+    EeConsPlan cp;
+    RFX_TRY(ee_consensus_plan(ctx, fx2_view(ctg), (const char *)d_rt.p, d_ro.as<int64_t>(), n_rows, cp));
+    RFX_TRY(ee_cons_alloc(ctx, cons, n_contigs, cp.lwords, cp.rwords));
+    RFX_TRY(ee_consensus_fill(ctx, cp, ee_cons_out(cons)));
+    EePlan plan;
+    RFX_TRY(ee_contigs_plan(ctx, fx2_view(ctg), ee_cons_in(cons), max_k, plan));
+    RFX_TRY(ee_set_alloc(ctx, set, plan.m, plan.words));
+    RFX_TRY(ee_contigs_fill(ctx, fx2_view(ctg), ee_cons_in(cons), plan, ee_set_out(set)));
+    int64_t total = 0;
+    RFX_TRY(ee_text(ctx, ee_set_in(set), nullptr, 0, &total, &d_rows));
+    return text_to_host(ctx, {{d_rows, total, out, cap, out_len}}, false);
+} RFX_API_CATCH(ctx)
+
+}  // extern "C"
+

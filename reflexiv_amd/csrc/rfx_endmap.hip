@@ -408,3 +408,83 @@ int rfx::mp_text(rfx_ctx *ctx, const Fx2View &c, const uint64_t *d_words, const 
     }
     return sync_checked(ctx);
 }
+
+// ---- the entry points ------------------------------------------------------------------------------------------------------------
+namespace {
+bool mp_hits_ok(const rfx_map_hits *h) { return h && h->read && h->end && h->strand && h->offset && h->v && h->cap_n >= 0; }
+}  // namespace
+
+extern "C" {
+
+void rfx_map_default_params(rfx_map_params *p) try {
+    if (!p) return;
+    p->seed = 21; p->min_overlap = 31; p->max_mismatch = 2;
+} RFX_API_CATCH_VOID(nullptr)
+
+int rfx_dev_map_ends(rfx_ctx *ctx, const rfx_contigs_packed *d_contigs, const int32_t *d_left, const int32_t *d_right, const uint64_t *d_words,
+                     const uint32_t *d_read_len, int64_t n_reads, int words_per_read, const rfx_map_params *params, rfx_map_hits *d_out) try {
+    if (!ctx || !fx2_contigs_in_ok(d_contigs, d_left, d_right) || n_reads < 0 || (n_reads > 0 && (!d_words || !d_read_len)) || words_per_read < 1 ||
+        !mp_hits_ok(d_out) || !mp_params_ok(ctx, params))
+        return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    const Fx2View v = fx2_view(d_contigs, d_left, d_right);
+    MpPlan plan;
+    RFX_TRY(mp_plan(ctx, v, d_words, d_read_len, n_reads, words_per_read, *params, plan));
+    if (!packed_out_fits(d_out, plan.hits)) return RFX_E_CAP;
+    RFX_TRY(mp_fill(ctx, v, d_words, d_read_len, n_reads, words_per_read, *params, plan, mp_hits(d_out)));
+    d_out->n = plan.hits; d_out->seed = params->seed;
+    return sync_checked(ctx);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_map_to_text(rfx_ctx *ctx, const rfx_contigs_packed *d_contigs, const int32_t *d_left, const int32_t *d_right, const uint64_t *d_words,
+                        const uint32_t *d_read_len, int words_per_read, const rfx_map_hits *hits, char *d_text, int64_t cap, int64_t *out_len,
+                        int64_t *d_row_off, int64_t cap_rows) try {
+    if (!ctx || !fx2_contigs_in_ok(d_contigs, d_left, d_right) || words_per_read < 1 || !mp_hits_ok(hits) || hits->n < 0 || hits->n > hits->cap_n ||
+        (hits->n > 0 && (!d_words || !d_read_len || hits->seed < 11 || hits->seed > 31)) || !text_out_ok(d_text, cap, out_len) || !d_row_off || cap_rows < 0)
+        return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    const bool rows_fit = cap_rows >= hits->n + 1;
+    int64_t total = 0;
+    // too few row offsets: the sizes only (a text buffer of 0 bytes takes nothing)
+    RFX_TRY(mp_text(ctx, fx2_view(d_contigs, d_left, d_right), d_words, d_read_len, words_per_read, mp_hits(hits), hits->n, hits->seed, d_text,
+                    rows_fit ? cap : 0, &total, rows_fit ? d_row_off : nullptr, nullptr));
+    *out_len = total;
+    return total > cap || !rows_fit ? RFX_E_CAP : RFX_OK;
+} RFX_API_CATCH(ctx)
+
+// host form: the text of 05FixingAgain and ASCII reads in, the row text out; everything between packed and in HBM: one upload each, the
+// contigs and the read store, the index, both passes, the text, one copy back
+int rfx_map_text(rfx_ctx *ctx, const char *contig_text, const int64_t *contig_off, int64_t n_contigs, const uint8_t *bases, const int64_t *read_off,
+                 int64_t n_reads, const rfx_map_params *params, char *out, int64_t cap, int64_t *out_len) try {
+    if (!ctx || !text_rows_ok(contig_text, contig_off, n_contigs) || !text_rows_ok((const char *)bases, read_off, n_reads) || !text_out_ok(out, cap, out_len) ||
+        !mp_params_ok(ctx, params))
+        return RFX_E_ARG;
+    if (n_contigs >= ((int64_t)1 << 29) || n_reads >= ((int64_t)1 << 31)) {       // (before an offset is read or a byte uploaded)
+        ctx->last_error = "end mapping: 2^29 contigs or 2^31 reads, or more";
+        return RFX_E_LIMIT;
+    }
+    int64_t longest = 1;
+    for (int64_t i = 0; i < n_reads; i++) longest = std::max(longest, read_off[i + 1] - read_off[i]);
+    if (longest >= ((int64_t)1 << 30)) { ctx->last_error = "end mapping: a read of 2^30 bases or more"; return RFX_E_LIMIT; }
+    RFX_HIP(hipSetDevice(ctx->device));
+    const int wpr = (int)((longest + 31) >> 5);
+    DevBuf d_ct, d_co, d_b, d_ro, d_words, d_len, d_rows;
+    CtgDev ctg;
+    MpHitsDev hits;
+    RFX_TRY(dyn_upload_text(ctx, contig_text, contig_off, n_contigs, d_ct, d_co));
+    RFX_TRY(dyn_upload_text(ctx, (const char *)bases, read_off, n_reads, d_b, d_ro));
+    RFX_TRY(ee_contigs_from_rows(ctx, (const char *)d_ct.p, d_co.as<int64_t>(), n_contigs, ctg));
+    const int64_t r1 = std::max<int64_t>(n_reads, 1);
+    RFX_ALLOC(d_words, uint64_t, r1 * wpr); RFX_ALLOC(d_len, uint32_t, r1);
+    if (n_reads > 0) RFX_TRY(encode_reads(ctx, d_b.as<uint8_t>(), d_ro.as<int64_t>(), n_reads, wpr, d_words.as<uint64_t>(), d_len.as<uint32_t>()));
+    const Fx2View v = fx2_view(ctg);
+    MpPlan plan;
+    RFX_TRY(mp_plan(ctx, v, d_words.as<uint64_t>(), d_len.as<uint32_t>(), n_reads, wpr, *params, plan));
+    RFX_TRY(mp_hits_alloc(ctx, hits, plan.hits));
+    RFX_TRY(mp_fill(ctx, v, d_words.as<uint64_t>(), d_len.as<uint32_t>(), n_reads, wpr, *params, plan, mp_hits(hits)));
+    int64_t total = 0;
+    RFX_TRY(mp_text(ctx, v, d_words.as<uint64_t>(), d_len.as<uint32_t>(), wpr, mp_hits(hits), plan.hits, params->seed, nullptr, 0, &total, nullptr, &d_rows));
+    return text_to_host(ctx, {{d_rows, total, out, cap, out_len}}, false);
+} RFX_API_CATCH(ctx)
+
+}  // extern "C"

@@ -333,3 +333,99 @@ int rfx::fx2_text(rfx_ctx *ctx, const Fx2View &v, int ends, char *d_text, int64_
     }
     return sync_checked(ctx);
 }
+
+// ---- the entry points, and what those of the later stages on contig sets share with them (rfx_internal.h) ------------------------------
+bool rfx::fx2_contigs_ok(const rfx_contigs_packed *p) { return p && p->words && p->word_off && p->len; }
+bool rfx::fx2_contigs_in_ok(const rfx_contigs_packed *p, const int32_t *d_left, const int32_t *d_right) {
+    return fx2_contigs_ok(p) && p->n >= 0 && (p->n == 0 || (d_left && d_right));
+}
+int rfx::fx2_params(rfx_ctx *ctx, const rfx_fix_params *p, int P, const char *stage) {
+    if (!p || !parts_ok(P)) return RFX_E_ARG;
+    if (p->max_k < 31 || p->max_k > 124) { ctx->last_error = std::string(stage) + ": max_k must be 31..124"; return RFX_E_ARG; }
+    if (p->max_iteration < -1) { ctx->last_error = std::string(stage) + ": max_iteration below -1"; return RFX_E_ARG; }
+    return RFX_OK;
+}
+int rfx::fx2_text_call(rfx_ctx *ctx, int ends, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, char *d_text, int64_t cap,
+                       int64_t *out_len) {
+    if (!ctx || !fx2_contigs_ok(d_in) || d_in->n < 0 || (ends != 2 && d_in->n > 0 && (!d_left || !d_right)) || !text_out_ok(d_text, cap, out_len))
+        return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    int64_t total = 0;
+    RFX_TRY(fx2_text(ctx, fx2_view(d_in, d_left, d_right), ends, d_text, cap, &total, nullptr));
+    *out_len = total;
+    return total > cap ? RFX_E_CAP : RFX_OK;
+}
+int rfx::fx2_contigs_of_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, CtgDev &c) {
+    DevBuf d_text, d_off;
+    DynDev a, b;
+    Fx2Plan plan;
+    RFX_TRY(dyn_upload_text(ctx, text, row_off, n_rows, d_text, d_off));
+    RFX_TRY(fx2_binarize(ctx, (const char *)d_text.p, d_off.as<int64_t>(), n_rows, a));
+    RFX_TRY(fx2_run(ctx, a, P, params->scramble, params->max_iteration, b));
+    RFX_TRY(fx2_contigs_plan(ctx, b, params->max_k, plan));
+    RFX_TRY(ctg_alloc(ctx, c, plan.m, plan.words));
+    return fx2_contigs_fill(ctx, b, plan, c.w.as<uint64_t>(), c.woff.as<int64_t>(), c.len.as<int64_t>(), c.left.as<int32_t>(), c.right.as<int32_t>());
+}
+
+extern "C" {
+
+int rfx_dev_fix2_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, rfx_dyn_packed *d_out) try {
+    if (!ctx || !dyn_packed_out_ok(d_out) || !text_rows_ok(d_text, d_row_off, n_rows)) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a;
+    RFX_TRY(fx2_binarize(ctx, d_text, d_row_off, n_rows, a));
+    return dyn_store(ctx, a, d_out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_fix2_run(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int P, const rfx_fix_params *params, rfx_dyn_packed *d_out) try {
+    if (!ctx || !dyn_packed_out_ok(d_in) || d_in->n < 0 || !dyn_packed_out_ok(d_out)) return RFX_E_ARG;
+    RFX_TRY(fx2_params(ctx, params, P));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a, b;
+    RFX_TRY(dyn_borrow(ctx, d_in, a));
+    RFX_TRY(fx2_run(ctx, a, P, params->scramble, params->max_iteration, b));
+    return dyn_store(ctx, b, d_out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_fix2_contigs(rfx_ctx *ctx, const rfx_dyn_packed *d_in, const rfx_fix_params *params, rfx_contigs_packed *d_out, int32_t *d_left,
+                         int32_t *d_right) try {
+    if (!ctx || !dyn_packed_out_ok(d_in) || d_in->n < 0 || !fx2_contigs_ok(d_out) || !d_left || !d_right) return RFX_E_ARG;
+    RFX_TRY(fx2_params(ctx, params, 1));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a;
+    Fx2Plan plan;
+    RFX_TRY(dyn_borrow(ctx, d_in, a));
+    RFX_TRY(fx2_contigs_plan(ctx, a, params->max_k, plan));
+    if (!packed_out_fits(d_out, plan.m, plan.words)) return RFX_E_CAP;
+    RFX_TRY(fx2_contigs_fill(ctx, a, plan, d_out->words, d_out->word_off, d_out->len, d_left, d_right));
+    d_out->n = plan.m;
+    return sync_checked(ctx);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_fix2_to_text(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, char *d_text, int64_t cap,
+                         int64_t *out_len) try {
+    return fx2_text_call(ctx, 0, d_in, d_left, d_right, d_text, cap, out_len);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_fix2_ends_text(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, char *d_text, int64_t cap,
+                           int64_t *out_len) try {
+    return fx2_text_call(ctx, 1, d_in, d_left, d_right, d_text, cap, out_len);
+} RFX_API_CATCH(ctx)
+
+// host text in, both host texts out; everything between packed and in HBM: one upload, binarize, run, the contigs, both texts, one
+// copy back each.  A short buffer: RFX_E_CAP with BOTH lengths set and NEITHER buffer written
+int rfx_fix2_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
+                  int64_t *out_len, char *ends_out, int64_t ends_cap, int64_t *ends_len) try {
+    if (!ctx || !text_rows_ok(text, row_off, n_rows) || !text_out_ok(out, cap, out_len) || !text_out_ok(ends_out, ends_cap, ends_len)) return RFX_E_ARG;
+    RFX_TRY(fx2_params(ctx, params, P));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DevBuf d_rows, d_ends;
+    CtgDev c;
+    int64_t t_rows = 0, t_ends = 0;
+    RFX_TRY(fx2_contigs_of_text(ctx, text, row_off, n_rows, P, params, c));
+    RFX_TRY(fx2_text(ctx, fx2_view(c), 0, nullptr, 0, &t_rows, &d_rows));
+    RFX_TRY(fx2_text(ctx, fx2_view(c), 1, nullptr, 0, &t_ends, &d_ends));
+    return text_to_host(ctx, {{d_rows, t_rows, out, cap, out_len}, {d_ends, t_ends, ends_out, ends_cap, ends_len}}, false);
+} RFX_API_CATCH(ctx)
+
+}  // extern "C"

@@ -551,7 +551,7 @@ int fx_from_ends(rfx_ctx *ctx, const uint64_t *d_kmers, int64_t n31, const DynDe
 int fx_ends_store(rfx_ctx *ctx, const DynDev &lng, const DevBuf &kmers, int64_t n31, rfx_dyn_packed *d_out_long, uint64_t *d_kmers, int64_t cap_kmers,
                   int64_t *n_kmers);
 
-// ---- rfx_fixing2.hip : the second contig fixing stage; its entry points are in rfx_api.hip
+// ---- rfx_fixing2.hip : the second contig fixing stage
 // text rows -> a packed set (form 1, no length filter; keys of 30 bases and extensions of one base or more, RFX_E_ARG otherwise) /
 // min(max_iteration + 1, 29) x (sort, loop) on a set of such records, zero rounds copy it / the contigs of at least 2 max_k bases:
 // what they take (plan), then into arrays that hold it (fill) / the rows of 05FixingAgain (ends 0) or the lines of 06ContigEnds
@@ -565,8 +565,7 @@ int fx2_contigs_fill(rfx_ctx *ctx, const DynDev &in, const Fx2Plan &plan, uint64
                      int32_t *d_right);
 int fx2_text(rfx_ctx *ctx, const Fx2View &v, int ends, char *d_text, int64_t cap, int64_t *total, DevBuf *own);
 
-
-// ---- rfx_endext.hip : the end extension of contigs from alignment rows; its entry points are in rfx_api.hip
+// ---- rfx_endext.hip : the end extension of contigs from alignment rows
 // the consensus of both ends of every contig of a set (Fx2View: a packed contig set with left / right) from text rows "name \t start
 // \t cigar \t seq" in HBM: what both consensus sets take (plan), then into arrays that hold it (fill) / the order of the IDs and what
 // the spliced set takes (plan), then reversed left || contig || right in output order (fill) / the rows of 07EndExtend (own: a buffer of
@@ -577,15 +576,15 @@ struct EeConsIn { const uint64_t *lw; const int64_t *lwoff, *llen; const uint64_
 struct EePlan { int64_t m = 0, words = 0; DevBuf perm, keep, nidx, opos, woff; };
 struct EeSetOut { uint64_t *w; int64_t *woff, *len; int32_t *left, *right, *left_len, *right_len, *flags, *src_idx, *new_idx; };
 struct EeSetIn { int64_t n; const uint64_t *w; const int64_t *woff, *len; const int32_t *left, *right, *left_len, *right_len, *flags, *src_idx, *new_idx; };
+struct CtgDev;
 int ee_consensus_plan(rfx_ctx *ctx, const Fx2View &in, const char *d_text, const int64_t *d_row_off, int64_t n_rows, EeConsPlan &plan);
 int ee_consensus_fill(rfx_ctx *ctx, const EeConsPlan &plan, const EeConsOut &o);
 int ee_contigs_plan(rfx_ctx *ctx, const Fx2View &in, const EeConsIn &c, int max_k, EePlan &plan);
 int ee_contigs_fill(rfx_ctx *ctx, const Fx2View &in, const EeConsIn &c, const EePlan &plan, const EeSetOut &o);
 int ee_text(rfx_ctx *ctx, const EeSetIn &s, char *d_text, int64_t cap, int64_t *total, DevBuf *own);
-int ee_contigs_from_rows(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, DevBuf &w, DevBuf &woff, DevBuf &len, DevBuf &left,
-                         DevBuf &right);
+int ee_contigs_from_rows(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n, CtgDev &c);
 
-// ---- rfx_ctgext.hip : the contig extension stages; their entry points are in rfx_api.hip
+// ---- rfx_ctgext.hip : the contig extension stages
 // the rows of 07EndExtend in HBM -> what the set of the rows of at least 2 max_k characters takes (plan), then into arrays that hold it
 // (fill: the literals of a flagged seam as T bases, flags 0) / a set (flags 0..3) -> the long records of its cut contigs and the end
 // 31-mers in emission order (kmers: a buffer of the library's)
@@ -594,7 +593,7 @@ int ex_rows_plan(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int
 int ex_rows_fill(rfx_ctx *ctx, const char *d_text, const ExRowsPlan &plan, const EeSetOut &o);
 int ex_contig_ends(rfx_ctx *ctx, const EeSetIn &s, int max_k, DynDev &out, DevBuf &kmers, int64_t *n_kmers);
 
-// ---- rfx_endmap.hip : reads onto the contig ends; its entry points are in rfx_api.hip
+// ---- rfx_endmap.hip : reads onto the contig ends
 // the parameters are in range (last_error says which is not) / the seed table of a contig set, the counting pass over the read store
 // (d_words, d_read_len, words_per_read as rfx_dev_count_reads_ragged takes them) and the scan of its counts: plan.hits rows / the rows
 // into arrays that hold them, in order / the rows as text "name \t start \t cigar \t seq \n" (filled up to cap) and their n + 1
@@ -608,5 +607,87 @@ int mp_fill(rfx_ctx *ctx, const Fx2View &c, const uint64_t *d_words, const uint3
             const MpPlan &plan, const MpHits &o);
 int mp_text(rfx_ctx *ctx, const Fx2View &c, const uint64_t *d_words, const uint32_t *d_read_len, int wpr, const MpHits &hits, int64_t n, int seed,
             char *d_text, int64_t cap, int64_t *total, int64_t *d_row_off, DevBuf *own);
+
+// ---- packed contig sets in HBM (rfx_contigs_packed and what is built on it), shared by the four stages above: DESIGN.md section 27
+#pragma GCC visibility push(hidden)
+// What owns the buffers of a set the library makes for itself.  Every array has max(n, 1) entries (woff one more) and w max(words, 1)
+// words, so an empty set still has something to point at; the *_alloc functions are the only places that know these rules.
+struct CtgDev { int64_t n = 0, words = 0; DevBuf w, woff, len, left, right; };                  // a packed contig set with left / right
+struct EeSetDev { int64_t n = 0, words = 0; DevBuf w, woff, len, i32; };                         // a set of 07EndExtend; i32: its seven int32 arrays, one block
+struct EeConsDev { int64_t n = 0, lwords = 0, rwords = 0; DevBuf lw, lwoff, llen, rw, rwoff, rlen, flags; };    // both consensus sets of n contigs, their flags
+struct MpHitsDev { int64_t n = 0; DevBuf i32; };                                                 // n rows of the end mapping; i32: its five int32 arrays, one block
+inline size_t at_least_1(int64_t n) { return (size_t)std::max<int64_t>(n, 1); }
+// (ee_contigs_from_rows learns the words only after it has filled the other arrays: it allocates the two halves apart, rows first)
+inline int ctg_alloc_rows(rfx_ctx *ctx, CtgDev &c, int64_t n) {
+    const size_t m = at_least_1(n);
+    c.n = n;
+    RFX_ALLOC(c.woff, int64_t, m + 1); RFX_ALLOC(c.len, int64_t, m); RFX_ALLOC(c.left, int32_t, m); RFX_ALLOC(c.right, int32_t, m);
+    return RFX_OK;
+}
+inline int ctg_alloc_words(rfx_ctx *ctx, CtgDev &c, int64_t words) { c.words = words; RFX_ALLOC(c.w, uint64_t, at_least_1(words)); return RFX_OK; }
+inline int ctg_alloc(rfx_ctx *ctx, CtgDev &c, int64_t n, int64_t words) { RFX_TRY(ctg_alloc_words(ctx, c, words)); return ctg_alloc_rows(ctx, c, n); }
+inline int ee_set_alloc(rfx_ctx *ctx, EeSetDev &s, int64_t n, int64_t words) {
+    const size_t m = at_least_1(n);
+    s.n = n; s.words = words;
+    RFX_ALLOC(s.w, uint64_t, at_least_1(words)); RFX_ALLOC(s.woff, int64_t, m + 1); RFX_ALLOC(s.len, int64_t, m); RFX_ALLOC(s.i32, int32_t, 7 * m);
+    return RFX_OK;
+}
+inline int ee_cons_alloc(rfx_ctx *ctx, EeConsDev &c, int64_t n, int64_t lwords, int64_t rwords) {
+    const size_t m = at_least_1(n);
+    c.n = n; c.lwords = lwords; c.rwords = rwords;
+    RFX_ALLOC(c.lw, uint64_t, at_least_1(lwords)); RFX_ALLOC(c.lwoff, int64_t, m + 1); RFX_ALLOC(c.llen, int64_t, m);
+    RFX_ALLOC(c.rw, uint64_t, at_least_1(rwords)); RFX_ALLOC(c.rwoff, int64_t, m + 1); RFX_ALLOC(c.rlen, int64_t, m);
+    RFX_ALLOC(c.flags, int32_t, m);
+    return RFX_OK;
+}
+inline int mp_hits_alloc(rfx_ctx *ctx, MpHitsDev &h, int64_t n) { h.n = n; RFX_ALLOC(h.i32, int32_t, 5 * at_least_1(n)); return RFX_OK; }
+// What the kernels take, by name, from a set of the library's or from the caller's public struct (whose arrays the entry point has
+// checked): the ONLY places that write one of these six structs as a list of pointers, or carve an int32 block (tests/
+// test_source_idioms.py).  An *_out of a const owner is what dyn_out is: the owner stays, what it points at is written.
+inline Fx2View fx2_view(const CtgDev &c) { return Fx2View{c.n, c.w.as<uint64_t>(), c.woff.as<int64_t>(), c.len.as<int64_t>(), c.left.as<int32_t>(), c.right.as<int32_t>()}; }
+inline Fx2View fx2_view(const rfx_contigs_packed *p, const int32_t *d_left, const int32_t *d_right) { return Fx2View{p->n, p->words, p->word_off, p->len, d_left, d_right}; }
+inline EeSetOut ee_set_out(const EeSetDev &s) {
+    const size_t m = at_least_1(s.n);
+    int32_t *a = s.i32.as<int32_t>();
+    return EeSetOut{s.w.as<uint64_t>(), s.woff.as<int64_t>(), s.len.as<int64_t>(), a, a + m, a + 2 * m, a + 3 * m, a + 4 * m, a + 5 * m, a + 6 * m};
+}
+inline EeSetOut ee_set_out(const rfx_endext_set *s) {
+    return EeSetOut{s->set.words, s->set.word_off, s->set.len, s->left, s->right, s->left_len, s->right_len, s->flags, s->src_idx, s->new_idx};
+}
+inline EeSetIn ee_set_in(int64_t n, const EeSetOut &o) { return EeSetIn{n, o.w, o.woff, o.len, o.left, o.right, o.left_len, o.right_len, o.flags, o.src_idx, o.new_idx}; }
+inline EeSetIn ee_set_in(const EeSetDev &s) { return ee_set_in(s.n, ee_set_out(s)); }
+inline EeSetIn ee_set_in(const rfx_endext_set *s) { return ee_set_in(s->set.n, ee_set_out(s)); }
+inline EeConsOut ee_cons_out(const EeConsDev &c) {
+    return EeConsOut{c.lw.as<uint64_t>(), c.lwoff.as<int64_t>(), c.llen.as<int64_t>(), c.rw.as<uint64_t>(), c.rwoff.as<int64_t>(), c.rlen.as<int64_t>(), c.flags.as<int32_t>()};
+}
+inline EeConsOut ee_cons_out(const rfx_endext_consensus *c) { return EeConsOut{c->left.words, c->left.word_off, c->left.len, c->right.words, c->right.word_off, c->right.len, c->flags}; }
+inline EeConsIn ee_cons_in(const EeConsOut &o) { return EeConsIn{o.lw, o.lwoff, o.llen, o.rw, o.rwoff, o.rlen, o.flags}; }
+inline EeConsIn ee_cons_in(const EeConsDev &c) { return ee_cons_in(ee_cons_out(c)); }
+inline EeConsIn ee_cons_in(const rfx_endext_consensus *c) { return ee_cons_in(ee_cons_out(c)); }
+inline MpHits mp_hits(const MpHitsDev &h) {
+    const size_t m = at_least_1(h.n);
+    int32_t *a = h.i32.as<int32_t>();
+    return MpHits{a, a + m, a + 2 * m, a + 3 * m, a + 4 * m};
+}
+inline MpHits mp_hits(const rfx_map_hits *h) { return MpHits{h->read, h->end, h->strand, h->offset, h->v}; }
+// host checks of the entry points on these sets, beside text_rows_ok / dyn_packed_out_ok above: a caller's text output (a capacity of 0
+// takes no buffer) / the gate between plan and fill: what the plan found goes into need_n / need_words, and the answer is whether the
+// caller's output holds it -- where it does not, the entry point returns RFX_E_CAP with n untouched and no array written
+inline bool text_out_ok(const char *out, int64_t cap, const int64_t *out_len) { return out_len && cap >= 0 && (cap == 0 || out); }
+inline bool packed_out_fits(rfx_contigs_packed *o, int64_t n, int64_t words) { o->need_n = n; o->need_words = words; return n <= o->cap_n && words <= o->cap_words; }
+inline bool packed_out_fits(rfx_map_hits *o, int64_t n) { o->need_n = n; return n <= o->cap_n; }
+// shared by the entry points of rfx_fixing2.hip, rfx_endext.hip, rfx_ctgext.hip and rfx_endmap.hip (defined in rfx_fixing2.hip): a
+// caller's contig set has its arrays / as an input: n >= 0 too, and left / right where n > 0 / max_k 31..124, max_iteration >= -1 and
+// parts_ok(P), last_error in the name of `stage` / the body of the rfx_dev_*_to_text entry points on a contig set (ends as fx2_text) /
+// the front of the host forms of 05FixingAgain and 09ExtendAgain: one upload, binarize, run, the contigs in the library's buffers
+bool fx2_contigs_ok(const rfx_contigs_packed *p);
+bool fx2_contigs_in_ok(const rfx_contigs_packed *p, const int32_t *d_left, const int32_t *d_right);
+int fx2_params(rfx_ctx *ctx, const rfx_fix_params *p, int P, const char *stage = "contig fixing, round two");
+int fx2_text_call(rfx_ctx *ctx, int ends, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, char *d_text, int64_t cap,
+                  int64_t *out_len);
+int fx2_contigs_of_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, CtgDev &c);
+// ... and of rfx_endext.hip with rfx_ctgext.hip: a caller's set of 07EndExtend has its arrays
+bool ee_set_ok(const rfx_endext_set *s);
+#pragma GCC visibility pop
 
 }  // namespace rfx

@@ -150,7 +150,7 @@ def test_the_header_declares_the_entry_points_and_the_bindings_hold_them():
         assert name in _lib.SYMBOLS and name in _lib._DYN_PACKED_ARGS, name
     _lib.lib()
     assert "rfx_ctgext.hip" in open(os.path.join(ROOT, "reflexiv_amd", "csrc", "Makefile")).read()
-    src = open(os.path.join(ROOT, "reflexiv_amd", "csrc", "rfx_api.hip")).read()
+    src = open(os.path.join(ROOT, "reflexiv_amd", "csrc", "rfx_ctgext.hip")).read()
     for name in SYMBOLS:
         body = src[src.index("int %s(" % name):]
         body = body[:body.index("RFX_API_CATCH")]

@@ -1,6 +1,7 @@
 """The host code in reflexiv_amd/csrc launches kernels through RFX_LAUNCH / RFX_LAUNCH_N (rfx_internal.h: on the context's
 stream, checked) and nowhere else, has no launch-shape helper of its own, and passes `x.as<T>()` to a `const T *` parameter
-without a cast.  Text only: nothing is compiled, nothing else is checked."""
+without a cast; the views of a packed contig set and the arrays of an int32 block are made by the named
+makers of rfx_internal.h and nowhere else (section 27).  Text only: nothing is compiled, nothing else is checked."""
 import os
 import re
 
@@ -36,7 +37,11 @@ def test_sources_found():
     (r"hipLaunchKernelGGL|<<<", ("rfx_internal.h",)),                    # a launch outside the two macros
     (r"\bgrid_for\s*\(|#\s*define\s+RFX_GRID\b|\bRFX_GRID\s*\(", ()),      # a launch-shape helper beside RFX_LAUNCH_N
     (r"\(\s*const\s+([^()*]+?)\s*\*\s*\)\s*[\w.\[\]>-]+\.as<\s*\1\s*>\(\)", ()),  # (const X *)y.as<X>()
-], ids=["raw_launch", "launch_shape_helper", "const_cast_of_as"])
+    # a kernel-facing view of a packed contig set written out as a list of pointers, as a temporary or as a variable (DESIGN.md
+    # section 27: the named makers in rfx_internal.h write them); `X{}` and `X v{}` stay legal, and so does MpHitsIn
+    (r"\b(Fx2View|EeSetIn|EeSetOut|EeConsIn|EeConsOut|MpHits)\b(\s+\w+)?\s*\{\s*[^}\s]", ("rfx_internal.h",)),
+    (r"\+\s*\d+\s*\*\s*[a-z]1\b", ("rfx_internal.h",)),                   # `a + 2 * m1`: the arrays of one int32 block carved by hand
+], ids=["raw_launch", "launch_shape_helper", "const_cast_of_as", "contig_view_as_a_pointer_list", "int32_block_carved_by_hand"])
 def test_idiom_absent(pattern, skip):
     found = hits(pattern, skip)
     assert not found, "\n".join(found)
