@@ -34,7 +34,7 @@
  *      - text buffers (rfx_contigs_text, rfx_dev_assemble[_w], rfx_assemble_counts_w,
  *        rfx_assemble_reads, the sharded drivers, rfx_dedup_contigs / rfx_dedup_contig_text,
  *        rfx_dev_contigs_to_text, rfx_dev_fix2_to_text, rfx_dev_fix2_ends_text, rfx_dev_endext_to_text,
- *        rfx_dev_ext2_to_text, rfx_dev_map_to_text)
+ *        rfx_dev_ext2_to_text, rfx_dev_map_to_text, rfx_dev_mercy_to_text)
  *        are filled up to `cap`: the bytes below it are unspecified (a prefix of the text),
  *        nothing at or past `cap` is written;
  *  - re-entrant per context; one context = one device + one HIP stream.
@@ -1090,6 +1090,44 @@ int rfx_dev_map_to_text(rfx_ctx *ctx, const rfx_contigs_packed *d_contigs, const
                         int64_t *d_row_off, int64_t cap_rows);
 int rfx_map_text(rfx_ctx *ctx, const char *contig_text, const int64_t *contig_off, int64_t n_contigs, const uint8_t *bases, const int64_t *read_off,
                  int64_t n_reads, const rfx_map_params *params, char *out, int64_t cap, int64_t *out_len);
+
+/* THE MERCY K-MER STAGE (Count_<k>_mercy) on the 2-bit read store in HBM: P/ReflexivDSDynamicMercyKmer.java
+ * `assemblyFromKmer` (:157-322), which the reference runs behind the counter for every k <= 31 in -sensitive mode.  It replaces
+ * ReverseComplementKmerBinaryExtractionFromDataset (:1680-1960), DynamicKmerBinarizer (:477-660), sort("seed"), RamenReadExtraction
+ * (:1414-1605), sort("ID"), RamenReadRangeCal (:1233-1412), FastqTuple2Dataset (:1607-1678), sort("ID"), ExtractMercyKmerFromRead
+ * (:913-1232) and DSBinaryKmerToString (:831-911).
+ * SOLID SET: the k-mers of the Count_<k> rows whose k-mer has k bases; on the device the counter's d_out_keys (ascending, one word each,
+ * the last base in the lowest bits).  LETTERS: any base other than A, C, G reads as T (the read store does this); the canonical form is
+ * the smaller of a k-mer and its reverse complement.  A READ GIVES NOTHING when len - k - end_clip + 1 <= 0, when front_clip > len, when
+ * len - 15 - end_clip <= 1 (FastqTuple2Dataset's filter, whose 15 is fixed), or when it has 32 bases or more and its first 31 are A (its
+ * first block is 0, which ExtractMercyKmerFromRead :932 takes for a marker row).  HITS: the window positions p, front_clip <= p <= len -
+ * end_clip - k, whose canonical k-mer is solid.  GAPS: for neighbouring hits a < b, g = b - a - 1 is kept iff g >= 1 and not k - 1 <= g
+ * <= k + 1 (the footprint of one substitution, :1336); nothing before the first or behind the last hit is rescued.  OUTPUT: for every
+ * kept gap and every j in (a, b) the canonical k-mer of read[j, j + k), count 1, in (read, j) order, duplicates not merged; text rows
+ * "KMER,1\n".  Equal seeds and equal IDs never straddle a Spark range partition, so the stage takes no partition count.
+ *   rfx_dev_mercy_kmers    the solid keys and the read store (as rfx_dev_count_reads_ragged takes it) -> the mercy k-mers in the counter's
+ *                          key format; *out_n of them.  RFX_E_CAP: *out_n = the need, nothing written
+ *   rfx_dev_mercy_to_text  n keys -> the rows in HBM (text-buffer rule: filled up to cap, nothing at or past it, RFX_E_CAP with *out_len
+ *                          = the need; d_text may have any alignment) and their n + 1 int64 offsets into d_row_off (nullable), so that
+ *                          both can go straight to rfx_dev_ksort_binarize
+ *   rfx_mercy_text         host form: the rows of Count_<k> (read as rfx_dev_ksort_binarize reads them: a leading '(' and a trailing ')'
+ *                          dropped, a trailing newline ignored; rows of another length are dropped; the rest are sorted and made
+ *                          distinct on the device, since a text file promises no order) and ASCII reads (bases + n_reads + 1 offsets)
+ *                          in, the row text out; one upload each and one copy back; a short buffer is not written
+ * DEVIATIONS, all stated: (1) one call handles ONE k.  (2) The count column of a solid row is not read (the reference parses it and
+ * drops it); it must still be decimal digits.  (3) The reference's RamenReadRangeCal throws on an empty partition; here an empty input
+ * gives an empty output.  (4) rfx_mercy_text sorts the count rows itself; rfx_dev_mercy_kmers requires them ascending, as the counter
+ * returns them.  The reference stores window indices clamped at 30000, so a read of 30000 bases or more is refused.
+ * RFX_E_ARG, nothing written: k outside 8..31; a negative clip; words_per_read < 1 or above 937 (rfx_dev_mercy_kmers); a null pointer;
+ * solid keys not strictly ascending or not below 4^k; a d_read_len[i] above 32 words_per_read or of 30000 or more; a count row without a
+ * comma or with a count that is not digits.  RFX_E_LIMIT: 2^31 reads, solid keys or mercy k-mers.  n_solid = 0, n_reads = 0 and an
+ * empty result are valid.  Words and bits past a read's length may hold anything and reach no result.  All run on the context's stream
+ * and return after it has drained. */
+int rfx_dev_mercy_kmers(rfx_ctx *ctx, const uint64_t *d_solid_keys, int64_t n_solid, const uint64_t *d_words, const uint32_t *d_read_len, int64_t n_reads,
+                        int words_per_read, int k, int front_clip, int end_clip, uint64_t *d_out_keys, int64_t cap, int64_t *out_n);
+int rfx_dev_mercy_to_text(rfx_ctx *ctx, const uint64_t *d_keys, int64_t n, int k, char *d_text, int64_t cap, int64_t *out_len, int64_t *d_row_off);
+int rfx_mercy_text(rfx_ctx *ctx, const char *count_text, const int64_t *count_row_off, int64_t n_rows, const uint8_t *bases, const int64_t *read_off,
+                   int64_t n_reads, int k, int front_clip, int end_clip, char *out, int64_t cap, int64_t *out_len);
 
 /* Synthetic reads: integer-only counter-based generator, bit-identical to
  * oracle/reflexiv_oracle.c orc_synth_*.  Writes packed reads straight into HBM. */

@@ -133,6 +133,7 @@ SYMBOLS = [
     "rfx_dev_endext_consensus", "rfx_dev_endext_contigs", "rfx_dev_endext_to_text", "rfx_endext_text",
     "rfx_dev_ext_from_text", "rfx_dev_ext_contig_ends", "rfx_dev_ext_run", "rfx_ext_text", "rfx_dev_ext2_to_text", "rfx_ext2_text",
     "rfx_map_default_params", "rfx_dev_map_ends", "rfx_dev_map_to_text", "rfx_map_text",
+    "rfx_dev_mercy_kmers", "rfx_dev_mercy_to_text", "rfx_mercy_text",
 ]
 
 # prototypes of the packed entry points (ctx, then as include/reflexiv_hip.h declares them)
@@ -196,6 +197,10 @@ _DYN_PACKED_ARGS = {
     "rfx_dev_map_ends": (_CP, _P, _P, _P, _P, _L, _I, _MP, _MH),
     "rfx_dev_map_to_text": (_CP, _P, _P, _P, _P, _I, _MH, _P, _L, _P, _P, _L),
     "rfx_map_text": (_P, _P, _L, _P, _P, _L, _MP, _P, _L, _P),
+    # the mercy k-mer stage: the counter's solid keys and the read store in, the mercy k-mers and their row text out
+    "rfx_dev_mercy_kmers": (_P, _L, _P, _P, _L, _I, _I, _I, _I, _P, _L, _P),
+    "rfx_dev_mercy_to_text": (_P, _L, _I, _P, _L, _P, _P),
+    "rfx_mercy_text": (_P, _P, _L, _P, _P, _L, _I, _I, _I, _P, _L, _P),
     # the packed contig set of the de-duplication (rfx_contigs_packed)
     "rfx_dev_contigs_pack": (_P, _P, _L, _CP),
     "rfx_dev_contigs_unpack": (_CP, _P, _L, _P, _L, _P),

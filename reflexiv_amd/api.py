@@ -341,6 +341,35 @@ class MapHits:
         return {a: getattr(self, a)[:self.n].cpu().numpy() for a in self.ARRAYS}
 
 
+class MercyKmers:
+    """The mercy k-mers of one call (rfx_dev_mercy_kmers) over a torch int64 tensor in HBM: the counter's key format (bit patterns of
+    uint64, the last base in the lowest bits), in (read, position) order.  `n` of them are in use."""
+
+    def __init__(self, cap_n: int, device="cuda"):
+        import torch
+        self.cap_n, self.n = int(cap_n), 0
+        self.keys = torch.empty(max(1, self.cap_n), dtype=torch.int64, device=device)
+
+    class _Call:
+        """what one call takes and writes (the entry point has plain arguments, no struct): the array, its capacity, *out_n"""
+        def __init__(self, keys: int, cap_n: int):
+            self.keys, self.cap_n, self.n = keys, cap_n, C.c_int64(0)
+
+    def _c(self) -> "MercyKmers._Call":
+        return MercyKmers._Call(self.keys.data_ptr(), self.cap_n)
+
+    def _grown(self, co, device=None) -> "MercyKmers":
+        """after RFX_E_CAP: room for the co.n k-mers the call reported, as it is"""
+        return MercyKmers(int(co.n.value), device or self.keys.device)
+
+    def _take(self, co):
+        self.n = int(co.n.value)
+
+    def host(self):
+        """numpy uint64 of the n keys in use"""
+        return self.keys[:self.n].cpu().numpy().view(np.uint64)
+
+
 def as_records(r) -> Records:
     """Accept any object with key/marker/ext_off/ext/left/right arrays (e.g. the oracle's Records)."""
     return Records(np.ascontiguousarray(r.key, np.uint64), np.ascontiguousarray(r.marker, np.int32),
@@ -925,7 +954,7 @@ class Reflexiv:
 
     # ---- the same passes on a packed record set that stays in HBM (rfx_dev_dyn_*)
     def _grow_call(self, fn, name, out, args_of, device=None, on_cap=None):
-        """one call fn(ctx, *args_of(co)) with a packed output -- a DynPacked, ContigsPacked, EndextConsensus, EndextSet or MapHits --
+        """one call fn(ctx, *args_of(co)) with a packed output -- a DynPacked, ContigsPacked, EndextConsensus, EndextSet, MapHits or MercyKmers --
         into `out` -> out.  On RFX_E_CAP `out` is replaced by what its class builds from the needs the call reported (out._grown: on
         `device`, or where `out` lives) and the call made again; on_cap(): whatever else the caller has to regrow first.  On success
         the class takes what it keeps from the C struct (out._take)."""
@@ -1428,6 +1457,46 @@ class Reflexiv:
         return self._host_text_call("rfx_map_text", [cap], lambda o, c, ln: self.L.rfx_map_text(
             self.ctx, ct, offc.ctypes.data, nc, bases.ctypes.data, offr.ctypes.data, nr, C.byref(params), o[0].ctypes.data, c[0],
             C.addressof(ln[0])))[0]
+
+    # ---- the mercy k-mer stage (Count_<k>_mercy) on the read store (rfx_dev_mercy_*)
+    def mercy_kmers(self, d_solid_keys, n_solid: int, d_words, d_read_len, n_reads: int, words_per_read: int, k: int, front_clip=0, end_clip=0,
+                    out: "MercyKmers" = None) -> "MercyKmers":
+        """rfx_dev_mercy_kmers: the counter's surviving keys (ascending) + the 2-bit read store (torch tensors in HBM: keys and words as
+        int64 bit patterns, the lengths as int32 bit patterns of uint32) -> the k-mers of the holes between two solid windows of a read"""
+        out = out or MercyKmers(64 + int(n_reads), d_words.device)      # (a short one is replaced by one of the need the call reports)
+        return self._grow_call(self.L.rfx_dev_mercy_kmers, "rfx_dev_mercy_kmers", out, lambda co: (
+            d_solid_keys.data_ptr(), int(n_solid), d_words.data_ptr(), d_read_len.data_ptr(), int(n_reads), int(words_per_read), int(k),
+            int(front_clip), int(end_clip), co.keys, co.cap_n, C.addressof(co.n)), d_words.device)
+
+    def mercy_to_text(self, keys, n: int, k: int, d_text=None, want_offsets=True):
+        """rfx_dev_mercy_to_text: n keys (a MercyKmers' tensor, or any torch int64 tensor in HBM) -> (torch uint8 tensor in HBM holding
+        the rows "KMER,1\\n", its length, the n + 1 int64 row offsets in HBM or None) -- what ksort_binarize takes"""
+        import torch
+        n = int(n)
+        d_off = torch.empty(n + 1, dtype=torch.int64, device=keys.device) if want_offsets else None
+        if d_text is None:
+            d_text = torch.empty(max(1, n * (int(k) + 3)), dtype=torch.uint8, device=keys.device)
+        d_text, ln = self._dev_text_call("rfx_dev_mercy_to_text", d_text, lambda t, ln: self.L.rfx_dev_mercy_to_text(
+            self.ctx, keys.data_ptr(), n, int(k), t.data_ptr(), int(t.numel()), C.addressof(ln), d_off.data_ptr() if want_offsets else None))
+        return d_text, ln, d_off
+
+    def mercy_text(self, count_text: bytes, reads, k: int, front_clip=0, end_clip=0) -> bytes:
+        """rfx_mercy_text: the rows of Count_<k> (bytes, one `KMER,count` row per line, in any order) and the reads -- a list of bytes, or
+        (the bases as one numpy uint8 array, the n + 1 int64 offsets) -- -> the rows of Count_<k>_mercy"""
+        ct = bytes(count_text)
+        offc, nc = self._row_offsets(ct)
+        if isinstance(reads, tuple):
+            bases, offr = np.ascontiguousarray(reads[0], np.uint8), np.ascontiguousarray(reads[1], np.int64)
+        else:
+            reads = [bytes(r) for r in reads]
+            bases = np.frombuffer(b"".join(reads), np.uint8)
+            offr = np.zeros(len(reads) + 1, np.int64)
+            np.cumsum([len(r) for r in reads], out=offr[1:])
+        nr = len(offr) - 1
+        cap = (int(k) + 3) * (nr + 64)
+        return self._host_text_call("rfx_mercy_text", [cap], lambda o, c, ln: self.L.rfx_mercy_text(
+            self.ctx, ct, offc.ctypes.data, nc, bases.ctypes.data, offr.ctypes.data, nr, int(k), int(front_clip), int(end_clip),
+            o[0].ctypes.data, c[0], C.addressof(ln[0])))[0]
 
     # ---- the contig extension stages (08Extend, 09ExtendAgain) on packed sets (rfx_dev_ext_*, rfx_dev_ext2_*, DESIGN.md section 25)
     def ext_from_text(self, d_text, d_row_off, params, out: "EndextSet" = None) -> "EndextSet":

@@ -552,6 +552,26 @@ std::string ReflexivMain::contigMapping(const std::string &contigText, const std
     return ext;
 }
 
+std::string ReflexivMain::mercyKmers(const std::string &countText, const std::string &fastqText) {
+    std::string counts;
+    std::vector<int64_t> coff;
+    rowsOf(countText, counts, coff);
+    std::vector<uint8_t> bases; std::vector<int64_t> readOff;
+    DSFastqFilterOnlySeq{*this}.call(fastqText, bases, readOff);
+    const int64_t n = (int64_t)coff.size() - 1, nr = (int64_t)readOff.size() - 1;
+    std::string out((size_t)(param.kmerSize + 3) * (size_t)(nr + 64), '\0');
+    int64_t len = 0;
+    for (;;) {
+        const int st = rfx_mercy_text(ctx, counts.data(), coff.data(), n, bases.data(), readOff.data(), nr, param.kmerSize, param.frontClip, param.endClip,
+                                      out.data(), (int64_t)out.size(), &len);
+        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
+        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_mercy_text: ") + rfx_last_error(ctx));
+        break;
+    }
+    out.resize((size_t)len);
+    return out;
+}
+
 std::string ReflexivMain::dedupContigText(const std::string &contigText) {
     std::string out(contigText.size() + 4096, '\0');
     int64_t len = 0, nc = 0;

@@ -159,6 +159,11 @@ public:
     // -kmer K`: CSV rows "KMER,count" of `counter` -> the rows "KMER,1|left|right" of Count_<K>_sorted, which `firstfour` reads.
     // One call (rfx_ksort_text): binarizer, reverse complement, both sorts, both fork filters and the text writer on the device.
     std::string kmerSorting(const std::string &csvText);
+    // ReflexivDSDynamicMercyKmer.assemblyFromKmer (P/ReflexivDSDynamicMercyKmer.java:157-322; -sensitive, every k <= 31) -- `mercy -kmerc
+    // O/Count_<K> -fastq F -kmer K`: the rows "KMER,count" of `counter` and the FASTQ text (DSFastqFilterOnlySeq, as the driver reads it,
+    // :208-209) -> the rows "KMER,1" of Count_<K>_mercy: the k-mers of the holes between two solid windows of one read.  One call
+    // (rfx_mercy_text): the solid set, the read store, the index, both passes and the text writer on the device.
+    std::string mercyKmers(const std::string &countText, const std::string &fastqText);
     // ReflexivDSDynamicKmerRuduction.assemblyFromKmer (P/ReflexivDSDynamicKmerRuduction.java:143-287) -- `reduce`: the rows
     // "KMER,marker|left|right" of Count_<k1>_sorted and Count_<k2>_sorted -> the rows of Count_<k1>_reduced (reducedShort) and of the
     // rewritten Count_<k2>_sorted / Count_<k2>_reduced (rewrittenLong).  One call (rfx_reduce_text): everything between on the device.

@@ -1,5 +1,7 @@
 // reflexiv_cli.cpp -- `reflexiv_host run|counter -fastq F [-kmer K -cover C ...] -outfile O`,
 // `reflexiv_host sort -kmerc COUNTS -kmer K [-klist 23,31,...] -outfile O` (Count_<K>_sorted), `firstfour`, `iteration`,
+// `reflexiv_host mercy -kmerc O/Count_<K> -fastq F[,F2...] -kmer K [-clipf N -clipe N] -outfile O` (Count_<K>_mercy; `sort -kmerc
+// O/Count_<K>,O/Count_<K>_mercy` then reads both, in the order Spark lists them),
 // `reflexiv_host reduce -kmerc SHORT -kmerc2 LONG -kmer K1 -kmer2 K2 [-klist ...] -partition P -outfile O` (Count_<K1>_reduced and
 // Count_<K2>_sorted, or Count_<K2>_reduced when K2 is the last k of the list), `reflexiv_host reduce -kmerc DIR -klist ... -partition P
 // -outfile O` (DIR/Count_<k> of every k of the list: each through `sort`, then the pairs in the list's order),
@@ -39,7 +41,8 @@ static std::string slurp(const std::string &path) {
 int main(int argc, char **argv) {
     try {
         if (argc < 2) { std::cerr << "usage: reflexiv_host <run|counter|sort|firstfour|iteration> -fastq F[,F2...] -outfile DIR [-kmer 31 -cover 2 ...]\n"
-                                   "       reflexiv_host sort -kmerc COUNTS -kmer K [-klist 23,31,41,53,67,81,95] -outfile DIR\n"
+                                   "       reflexiv_host sort -kmerc COUNTS[,MERCY] -kmer K [-klist 23,31,41,53,67,81,95] -outfile DIR\n"
+                                   "       reflexiv_host mercy -kmerc COUNTS -fastq F[,F2...] -kmer K [-clipf N -clipe N] -outfile DIR\n"
                                    "       reflexiv_host reduce -kmerc SHORT -kmerc2 LONG -kmer K1 -kmer2 K2 [-klist ...] -partition P -outfile DIR\n"
                                    "       reflexiv_host reduce -kmerc COUNTS_DIR -klist K1,K2,... -partition P -outfile DIR\n"
                                    "       reflexiv_host fixing -kmerc ITERATION_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"
@@ -55,6 +58,10 @@ int main(int argc, char **argv) {
             throw std::runtime_error("sort needs -kmerc COUNTS -kmer K [-klist 23,31,...] -outfile DIR");
         if (cmd == "sort" && (param.kmerSize < 8 || (param.kmerSize - 1) % 31 == 0))
             throw std::runtime_error("sort: -kmer " + std::to_string(param.kmerSize) + " is not supported (8..124 except 32, 63, 94)");
+        if (cmd == "mercy" && (param.inputKmerPath.empty() || param.inputFqPath.empty() || param.outputPath.empty()))
+            throw std::runtime_error("mercy needs -kmerc COUNTS -fastq F[,F2...] -kmer K [-clipf N -clipe N] -outfile DIR");
+        if (cmd == "mercy" && (param.kmerSize < 8 || param.kmerSize > 31))
+            throw std::runtime_error("mercy: -kmer " + std::to_string(param.kmerSize) + " is not supported (8..31)");
         if (cmd == "reduce" && (param.inputKmerPath.empty() || param.outputPath.empty()))
             throw std::runtime_error("reduce needs -kmerc SHORT -kmerc2 LONG -kmer K1 -kmer2 K2 [-klist ...] -partition P -outfile DIR, or -kmerc COUNTS_DIR "
                                      "-klist K1,K2,... -partition P -outfile DIR");
@@ -122,6 +129,11 @@ int main(int argc, char **argv) {
             // (P/ReflexivDSKmerLeftAndRightSorting.java:228-240)
             out = m.kmerSorting(read_all(param.inputKmerPath));
             dir += "/Count_" + std::to_string(param.kmerSize) + "_sorted"; mkdir(dir.c_str(), 0755);
+        } else if (cmd == "mercy") {
+            // Pipelines.java:1385-1391 (-sensitive, behind the counter for every k <= 31): the rows "KMER,count" of Count_<k> and the reads
+            // -> Count_<k>_mercy (P/ReflexivDSDynamicMercyKmer.java:307-318), which the sorter reads through the glob Count_<k>*/part*
+            out = m.mercyKmers(read_all(param.inputKmerPath), read_all(param.inputFqPath));
+            dir += "/Count_" + std::to_string(param.kmerSize) + "_mercy"; mkdir(dir.c_str(), 0755);
         } else if (cmd == "reduce") {
             // Pipelines.reflexivDSDynamicKmerReductionPipe() (Pipelines.java:1343-1365 walks the pairs of the k list); the second output
             // is Count_<k2>_reduced when k2 is the last k of the list, Count_<k2>_sorted otherwise (P/ReflexivDSDynamicKmerRuduction.java:257-283)
@@ -224,7 +236,7 @@ int main(int argc, char **argv) {
             dir += "/Count_" + std::to_string(param.kmerSize);               // P/ReflexivDataFrameCounter.java:222-233
             mkdir(dir.c_str(), 0755);
         } else throw std::runtime_error("unknown command " + cmd);
-        std::ofstream(dir + (cmd == "counter" || cmd == "sort" || cmd == "firstfour" || cmd == "iteration" || cmd == "fixing" || cmd == "endextend" || cmd == "mapping" || cmd == "extend" || cmd == "extend2" ? "/part-00000.csv" : "/part-00000"), std::ios::binary) << out;   // saveAsTextFile / csv
+        std::ofstream(dir + (cmd == "counter" || cmd == "sort" || cmd == "mercy" || cmd == "firstfour" || cmd == "iteration" || cmd == "fixing" || cmd == "endextend" || cmd == "mapping" || cmd == "extend" || cmd == "extend2" ? "/part-00000.csv" : "/part-00000"), std::ios::binary) << out;   // saveAsTextFile / csv
         std::ofstream(dir + "/_SUCCESS", std::ios::binary);
         return 0;
     } catch (const std::exception &e) {
