@@ -2700,6 +2700,26 @@ __global__ __launch_bounds__(1024) void k_l2_check(L2Plan pl, int nseg, int64_t 
     }
 }
 
+// The sweep touches every record once on the way in and once on the way out, 9 + 9 GB a step, and nothing of it is used again
+// before the leaves stream it: both sides carry the non-temporal hint (`nt` on the global_load / global_store), so the stream
+// does not take cache lines as if it were to be re-used.  (4.36 -> 3.8 ms; the hint on the loads alone
+// is a loss, on the stores alone two thirds of the gain.)  Records move as native 16-byte vectors, one or two each.
+typedef unsigned long long l2_v2 __attribute__((ext_vector_type(2)));
+template <class RT>
+__device__ __forceinline__ RT l2_load_stream(const RT *p) {
+    static_assert(sizeof(RT) == 16 || sizeof(RT) == 32, "16- or 32-byte records");
+    const l2_v2 a = __builtin_nontemporal_load((const l2_v2 *)p);
+    if constexpr (sizeof(RT) == 32) {
+        const l2_v2 b = __builtin_nontemporal_load((const l2_v2 *)p + 1);
+        return RT{a.x, a.y, b.x, b.y};
+    } else return RT{a.x, a.y};
+}
+template <class RT>
+__device__ __forceinline__ void l2_store_stream(RT *p, const RT &r) {
+    const uint64_t *w = (const uint64_t *)&r;
+    __builtin_nontemporal_store(l2_v2{w[0], w[1]}, (l2_v2 *)p);
+    if constexpr (sizeof(RT) == 32) __builtin_nontemporal_store(l2_v2{w[2], w[3]}, (l2_v2 *)p + 1);
+}
 template <int B, int MODE>
 __global__ __launch_bounds__(WCT) void k_rec_l2sweep(const typename LevelElem<MODE>::T *__restrict__ recs, L2Plan pl, Level lv, int used,
                                                      typename LevelElem<MODE>::T *__restrict__ out, uint64_t *__restrict__ leaf_end) {
@@ -2734,7 +2754,7 @@ __global__ __launch_bounds__(WCT) void k_rec_l2sweep(const typename LevelElem<MO
                 nh = e;
             }
             const unsigned long long g = h + j;
-            if (g < e) out[g] = buf[(size_t)d * B + (g & (B - 1))];
+            if (g < e) l2_store_stream(out + g, buf[(size_t)d * B + (g & (B - 1))]);
             if (j == 0) head[d] = nh;
         }
     };
@@ -2743,7 +2763,7 @@ __global__ __launch_bounds__(WCT) void k_rec_l2sweep(const typename LevelElem<MO
 #pragma unroll
         for (int i = 0; i < WC_PER; i++) {
             const uint64_t idx = b0 + (uint64_t)i * WCT + threadIdx.x;
-            r[i] = recs[idx < qe ? idx : qe - 1];
+            r[i] = l2_load_stream(recs + (idx < qe ? idx : qe - 1));
         }
 #pragma unroll
         for (int i = 0; i < WC_PER; i++) {
@@ -3945,6 +3965,7 @@ static int last_level_sweep(rfx_ctx *ctx, const typename LevelElem<MODE>::T *cur
     const int h_flags[2] = {(int)(h_fl[0] & 0xffffffffULL), (int)(h_fl[0] >> 32)};
     if (!h_flags[0] && !h_flags[1]) ctx->timing["stat_l2_spilled"].launches += (int64_t)h_fl[1];     // records moved by k_l2_spill_fix
     if (!h_flags[0] && h_flags[1]) ctx->timing["stat_l2_void"].launches += 1;                        // sweeps given up for the exact form
+    if (!h_flags[0] && !h_flags[1]) ctx->timing["stat_l2_sweeps"].launches += 1;                     // sweeps that ran and stood
     if (getenv("RFX_TRACE")) {
         fprintf(stderr, "last level in one sweep: %lld records in regions of %llu%s\n", (long long)n_recs, (unsigned long long)h_tot,
                 h_flags[0] ? " -- not tried (skew, or no room): the exact form instead" : h_flags[1] ? " -- more spilled than the list takes: the exact form instead" : "");
