@@ -565,6 +565,29 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
     return x;
 }
 
+// Record streams of the radix levels.  The last level's sweep (k_rec_l2sweep) touches every record once on the way in and once
+// on the way out, 9 + 9 GB a step, and nothing of it is used again before the leaves stream it: both sides carry the
+// non-temporal hint (`nt` on the global_load / global_store), so the stream does not take cache lines as if it were to be
+// re-used.  (4.36 -> 3.8 ms; the hint on the loads alone is a loss, on the stores alone two thirds of
+// the gain.)  Records move as native 16-byte vectors, one or two each.
+// Level 1's sweep (k_sk_onesweep) writes its rings' lines the same way (section 30).
+typedef unsigned long long l2_v2 __attribute__((ext_vector_type(2)));
+template <class RT>
+__device__ __forceinline__ RT l2_load_stream(const RT *p) {
+    static_assert(sizeof(RT) == 16 || sizeof(RT) == 32, "16- or 32-byte records");
+    const l2_v2 a = __builtin_nontemporal_load((const l2_v2 *)p);
+    if constexpr (sizeof(RT) == 32) {
+        const l2_v2 b = __builtin_nontemporal_load((const l2_v2 *)p + 1);
+        return RT{a.x, a.y, b.x, b.y};
+    } else return RT{a.x, a.y};
+}
+template <class RT>
+__device__ __forceinline__ void l2_store_stream(RT *p, const RT &r) {
+    const uint64_t *w = (const uint64_t *)&r;
+    __builtin_nontemporal_store(l2_v2{w[0], w[1]}, (l2_v2 *)p);
+    if constexpr (sizeof(RT) == 32) __builtin_nontemporal_store(l2_v2{w[2], w[3]}, (l2_v2 *)p + 1);
+}
+
 // KC: the k-mer length as a compile-time constant (0 = the run-time argument): the window shifts, the reverse
 // complement's alignment and the masks of the record path fold into immediates
 template <int ELEM, int KC = 0>
@@ -1992,9 +2015,9 @@ struct OneSweep {
     const uint32_t *reg_cap;             // [nb] records a region holds
     unsigned long long *cursor;          // [nb * OS_CSTRIDE] next record to hand out (absolute; starts at reg_start)
     uint64_t *holes;                     // [nb][OS_HOLES * G] (absolute start << 16) | length, 0 = none
-    int *overflow;
+    int *overflow;                       // [0] the sweep is void (1; 2: k_fix_holes' books do not balance), [1] a round raised it
     uint64_t total;                      // records allocated (regions + the dump extent)
-    unsigned long long *tile_counter;    // tiles of SKT segments handed out beyond every workgroup's first
+    unsigned long long *tile_counter;    // tiles of SKT segments handed out beyond every workgroup's first two
     uint32_t ose, ose_shift;             // records per extent (a power of two)
 };
 
@@ -2076,8 +2099,10 @@ __global__ __launch_bounds__(1024) void k_plan_regions(const unsigned long long 
 template <int SEG, bool WIDE> struct OsGeo {
     static constexpr int T = SEG > 16 && !WIDE ? 512 : SKT;                  // threads per workgroup = segments per tile
 };
+// (four waves per SIMD in every form: the rings of 512 buckets let two workgroups of 512 threads share a CU, those of
+// 1024 buckets -- the only case that runs the 16-window form of the 16-byte records -- and of the 32-byte records one of 1024)
 template <int W, bool WIDE = false, int SEG = 16>
-__global__ __launch_bounds__((OsGeo<SEG, WIDE>::T), WIDE || SEG > 16 ? 4 : 8) void k_sk_onesweep(ReadSrc s, Level lv, OneSweep os,
+__global__ __launch_bounds__((OsGeo<SEG, WIDE>::T), 4) void k_sk_onesweep(ReadSrc s, Level lv, OneSweep os,
                                                                std::conditional_t<WIDE, WRec, Rec> *__restrict__ out) {
     using RT = std::conditional_t<WIDE, WRec, Rec>;
     constexpr int SKT = OsGeo<SEG, WIDE>::T;                                  // (shadows the file-wide workgroup size)
@@ -2096,9 +2121,11 @@ __global__ __launch_bounds__((OsGeo<SEG, WIDE>::T), WIDE || SEG > 16 ? 4 : 8) vo
     // An extent off bucket d's cursor.  Only the END OF THE ALLOCATION is checked here (no load on this path): an extent
     // past the bucket's own region lands in its neighbour's, which k_fix_holes sees from the cursor and declares the
     // whole sweep void.
-    auto grab = [&](int d) __attribute__((always_inline)) -> uint32_t {
-        const unsigned long long b = atomicAdd(&os.cursor[(size_t)d * OS_CSTRIDE], (unsigned long long)OSE);
+    auto extent_of = [&](unsigned long long b) __attribute__((always_inline)) -> uint32_t {
         return b + OSE <= dump_at ? (uint32_t)(b >> OSH) : DUMP;
+    };
+    auto grab = [&](int d) __attribute__((always_inline)) -> uint32_t {
+        return extent_of(atomicAdd(&os.cursor[(size_t)d * OS_CSTRIDE], (unsigned long long)OSE));
     };
     // where local position v of a bucket lives (v - cs < 2 * OSE)
     auto phys = [&](uint32_t v, uint32_t cs, uint32_t cb, uint32_t nx) __attribute__((always_inline)) -> uint64_t {
@@ -2137,47 +2164,72 @@ __global__ __launch_bounds__((OsGeo<SEG, WIDE>::T), WIDE || SEG > 16 ? 4 : 8) vo
 #pragma unroll
             for (int q = 0; q < SKB / LPB; q++) {
                 const uint32_t g = h + j + q * LPB;
-                if (g < e) out[phys(g, cs, cb, nx)] = buf[(size_t)d * SKB + (g & (SKB - 1))];
+                if (g < e) l2_store_stream(out + phys(g, cs, cb, nx), buf[(size_t)d * SKB + (g & (SKB - 1))]);
             }
             if (j == 0) {
                 head[d] = nh;
-                // extents that lie wholly behind the stored position are done with: move up (the 8 lanes of this
-                // bucket read the old values above, in lock-step)
+                // The extent that lies wholly behind the stored position is done with: move up ONE extent (the lanes of
+                // this bucket read the old values above, in lock-step).  No claim here: a returning atomic in this loop
+                // puts an s_waitcnt vmcnt(0) on its back edge, and every iteration then waits for its own stores.
+                // One step is enough.  The emit takes positions below cstart + 2 OSE only, so nh - cs <= 2 OSE while
+                // the flag is down, and after the step nh - cstart <= OSE.  At equality the current extent is exactly
+                // full and nothing lies in the next one: the coming round has one extent of room where it has two
+                // otherwise, the step after it is due at the next drain, and `used == OSE` leaves no hole below.
+                // pbase[d] is valid here: it is refilled at the top of every round that finds it NONE.  Only the last
+                // drain can find NONE (the drain before it took the extent): nothing is stored after it, so the
+                // bucket goes on without a next extent (DUMP: no hole).
+                // With the flag up, tail runs ahead of what was stored and the bookkeeping may be anything; phys()
+                // still returns (cbase or nbase or the dump extent) + (offset & (OSE - 1)), and neither cbase nor
+                // nbase is ever NONE, so every store lands in an extent this workgroup claimed or in the dump extent.
                 if (nh - cs >= (uint32_t)OSE) {
-                    uint32_t c = cs, b0 = cb, b1 = nx, b2 = pbase[d];
-                    while (nh - c >= (uint32_t)OSE) { c += OSE; b0 = b1; b1 = b2 != NONE ? b2 : grab(d); b2 = NONE; }
-                    cstart[d] = c; cbase[d] = b0; nbase[d] = b1; pbase[d] = b2;
+                    const uint32_t b2 = pbase[d];
+                    cstart[d] = cs + OSE; cbase[d] = nx; nbase[d] = final && b2 == NONE ? DUMP : b2; pbase[d] = NONE;
                 }
             }
         }
     };
-    // Tiles of SKT segments are handed out by a global counter (the first one is the workgroup's number): the
-    // workgroups stay as few as the holes allow and still finish together.  The next tile is asked for at the top of a
-    // round, like the extents.
+    // Tiles of SKT segments are handed out by a global counter (a workgroup's first two are its number and its number
+    // + gridDim.x): the workgroups stay as few as the holes allow and still finish together.  The tile after the next is
+    // asked for at the top of a round, like the extents: the next one is then known, and its words travel during the round.
     __shared__ long long tile_lds[2];
     const int64_t ntile = (s.n_threads + SKT - 1) / SKT;
     const int my_d = (int)threadIdx.x;                  // the bucket this thread keeps supplied (nb <= SKT)
     int64_t T = blockIdx.x;
+    // where the thread's segment of a tile lies, and its words on their way (no branch, so no wait of its own: a lane
+    // past the last segment, or a tile past the last, reads the last segment's words, and `in` drops them)
+    auto fetch = [&](int64_t tile, SegPos &q, int &nk_r, uint64_t (&w)[3]) __attribute__((always_inline)) {
+        const int64_t g = tile * SKT + threadIdx.x;
+        const int64_t gc = g < s.n_threads ? g : s.n_threads - 1;
+        q.r = gc / s.segs;
+        q.sgm = (int)(gc - q.r * s.segs);
+        seg_load<SEG>(s, q, w);
+        nk_r = read_nk<WIDE>(s, q.r);
+    };
+    int64_t T1 = (int64_t)gridDim.x + blockIdx.x;      // the tile after this one (the counter hands out from 2 gridDim.x)
+    SegPos qn{0, 0};
+    int nkn = 0;
+    uint64_t wn[3] = {0, 0, 0};
+    if (T < ntile) fetch(T, qn, nkn, wn);
+    asm volatile("" : "+v"(wn[0]), "+v"(wn[1]), "+v"(wn[2]), "+v"(nkn));
     for (int rnd = 0; T < ntile; rnd++) {
-        long long t_next = 0;
-        if (threadIdx.x == SKT - 1) t_next = (long long)gridDim.x + (long long)atomicAdd(os.tile_counter, 1ULL);
-        const bool ask = my_d < nb && pbase[my_d] == NONE;
-        uint32_t req = DUMP;
-        if (ask) req = grab(my_d);
+        // A round waits for memory ONCE, after its arithmetic.  The words of this round's tile were requested a round
+        // ago; the next tile's (known a round ahead: the counter is asked for the tile after the next) are requested here
+        // with the extent claim and the tile claim, and every lane awaits all of it after seg_runs, before the drain --
+        // whatever branch it takes, so that nothing but stores is in flight at the drain and at the next round's top (a
+        // result that some path never uses counts as in flight there, and the wait the compiler then puts is a vmcnt(0)
+        // that also waits for the drain's stores).
         // (SEG = 32: every lane calls seg_runs, which swaps run ends with the neighbour lanes; a lane past the last
         // segment brings no windows)
-        const int64_t g = T * SKT + threadIdx.x;
-        const bool in = g < s.n_threads;
-        SegPos q{0, 0};
-        int nk_r = 0;
-        uint64_t w[3] = {0, 0, 0}, hi = 0, lo = 0;
+        const bool in = T * SKT + threadIdx.x < s.n_threads;
+        SegPos q{in ? qn.r : 0, in ? qn.sgm : 0};
+        int nk_r = in ? nkn : 0;
+        uint64_t w[3] = {in ? wn[0] : 0, in ? wn[1] : 0, in ? wn[2] : 0}, hi = 0, lo = 0;
         uint32_t past = 0;                              // the 13 bases after (hi, lo), from the next lane (SEG = 32)
-        if (in) {
-            q.r = g / s.segs;
-            q.sgm = (int)(g - q.r * s.segs);
-            seg_load<SEG>(s, q, w);
-            nk_r = read_nk<WIDE>(s, q.r);
-        }
+        unsigned long long t_raw = 0, req_raw = 0;
+        const bool ask = my_d < nb && pbase[my_d] == NONE;
+        if (ask) req_raw = atomicAdd(&os.cursor[(size_t)my_d * OS_CSTRIDE], (unsigned long long)OSE);
+        fetch(T1, qn, nkn, wn);
+        if (threadIdx.x == SKT - 1) t_raw = atomicAdd(os.tile_counter, 1ULL);
         if (SEG == 32 || in) {
             seg_runs<W, true, SEG>(s, nk_r, q.sgm, w, [&](int i0, int n, uint32_t canon) {
                 const uint64_t hh = mmer_hash64(canon);
@@ -2200,30 +2252,41 @@ __global__ __launch_bounds__((OsGeo<SEG, WIDE>::T), WIDE || SEG > 16 ? 4 : 8) vo
                     r.hd = ((uint64_t)(n - 1) << 32) | (uint64_t)hdr;
                 } else {
                     // (a run that starts after window 18 reaches into the next lane's bases -- a merged tail needs them)
-                    const int sft = 2 * i0;
-                    const uint64_t x = (uint64_t)past << 32;
-                    r.w0 = sft ? (hi << sft) | (lo >> (64 - sft)) : hi;
-                    r.w1 = ((sft ? (lo << sft) | (x >> (64 - sft)) : lo) & 0xFFFFFFF000000000ULL) | ((uint64_t)(n - 1) << 32) | (uint64_t)hdr;
+                    // 92 bits from bit 2 i0 of the 160-bit string (hi, lo, past), by 32-bit funnel shifts: the string
+                    // shifted right by one bit (e0..e4, the same for every run of the thread) makes the shift 31 - t with
+                    // t = 2 (i0 & 15), in 1..31 -- v_alignbit_b32 takes no shift of 32 -- and i0 >> 4 picks the first word
+                    const uint32_t d0 = (uint32_t)(hi >> 32), d1 = (uint32_t)hi, d2 = (uint32_t)(lo >> 32), d3 = (uint32_t)lo;
+                    const uint32_t e0 = d0 >> 1, e1 = __builtin_amdgcn_alignbit(d0, d1, 1), e2 = __builtin_amdgcn_alignbit(d1, d2, 1);
+                    const uint32_t e3 = __builtin_amdgcn_alignbit(d2, d3, 1), e4 = __builtin_amdgcn_alignbit(d3, past, 1);
+                    const bool up = i0 >= 16;
+                    const uint32_t a0 = up ? e1 : e0, a1 = up ? e2 : e1, a2 = up ? e3 : e2, a3 = up ? e4 : e3;
+                    const uint32_t sh = 31u - 2u * ((uint32_t)i0 & 15u);
+                    const uint32_t w0h = __builtin_amdgcn_alignbit(a0, a1, sh), w0l = __builtin_amdgcn_alignbit(a1, a2, sh);
+                    const uint32_t w1h = (__builtin_amdgcn_alignbit(a2, a3, sh) & 0xFFFFFFF0u) | (uint32_t)(n - 1);
+                    r.w0 = ((uint64_t)w0h << 32) | w0l;
+                    r.w1 = ((uint64_t)w1h << 32) | (uint64_t)hdr;
                 }
                 const uint32_t pos = atomicAdd(&tail[d], 1u);
                 if (pos - head[d] < (uint32_t)SKB) buf[(size_t)d * SKB + (pos & (SKB - 1))] = r;
                 else {
                     const uint32_t cs = cstart[d];
                     if (pos - cs < 2u * OSE) out[phys(pos, cs, cbase[d], nbase[d])] = r;
-                    else *os.overflow = 1;             // more than the two extents in hand take: the caller starts over
+                    else { os.overflow[0] = 1; os.overflow[1] = 1; }   // more than the two extents in hand take: the caller starts over
                 }
             }, &hi, &lo, nullptr, &past);
         }
-        if (threadIdx.x == SKT - 1) tile_lds[rnd & 1] = t_next;
-        if (ask) pbase[my_d] = req;
+        asm volatile("" : "+v"(wn[0]), "+v"(wn[1]), "+v"(wn[2]), "+v"(nkn), "+v"(t_raw), "+v"(req_raw));
+        if (threadIdx.x == SKT - 1) tile_lds[rnd & 1] = 2LL * (long long)gridDim.x + (long long)t_raw;
+        if (ask) pbase[my_d] = extent_of(req_raw);
         __syncthreads();
         drain(false);
-        T = tile_lds[rnd & 1];
+        T = T1;
+        T1 = tile_lds[rnd & 1];
         __syncthreads();
     }
     drain(true);
     __syncthreads();
-    // what is left of the extents in hand (after the last drain: head == tail, tail - cstart < OSE)
+    // what is left of the extents in hand (after the last drain: head == tail, tail - cstart <= OSE)
     for (int d = threadIdx.x; d < nb; d += SKT) {
         const uint32_t used = tail[d] - cstart[d], cb = cbase[d], nx = nbase[d], px = pbase[d];
         uint64_t *hl = os.holes + ((size_t)d * gridDim.x + blockIdx.x) * OS_HOLES;
@@ -2700,26 +2763,6 @@ __global__ __launch_bounds__(1024) void k_l2_check(L2Plan pl, int nseg, int64_t 
     }
 }
 
-// The sweep touches every record once on the way in and once on the way out, 9 + 9 GB a step, and nothing of it is used again
-// before the leaves stream it: both sides carry the non-temporal hint (`nt` on the global_load / global_store), so the stream
-// does not take cache lines as if it were to be re-used.  (4.36 -> 3.8 ms; the hint on the loads alone
-// is a loss, on the stores alone two thirds of the gain.)  Records move as native 16-byte vectors, one or two each.
-typedef unsigned long long l2_v2 __attribute__((ext_vector_type(2)));
-template <class RT>
-__device__ __forceinline__ RT l2_load_stream(const RT *p) {
-    static_assert(sizeof(RT) == 16 || sizeof(RT) == 32, "16- or 32-byte records");
-    const l2_v2 a = __builtin_nontemporal_load((const l2_v2 *)p);
-    if constexpr (sizeof(RT) == 32) {
-        const l2_v2 b = __builtin_nontemporal_load((const l2_v2 *)p + 1);
-        return RT{a.x, a.y, b.x, b.y};
-    } else return RT{a.x, a.y};
-}
-template <class RT>
-__device__ __forceinline__ void l2_store_stream(RT *p, const RT &r) {
-    const uint64_t *w = (const uint64_t *)&r;
-    __builtin_nontemporal_store(l2_v2{w[0], w[1]}, (l2_v2 *)p);
-    if constexpr (sizeof(RT) == 32) __builtin_nontemporal_store(l2_v2{w[2], w[3]}, (l2_v2 *)p + 1);
-}
 template <int B, int MODE>
 __global__ __launch_bounds__(WCT) void k_rec_l2sweep(const typename LevelElem<MODE>::T *__restrict__ recs, L2Plan pl, Level lv, int used,
                                                      typename LevelElem<MODE>::T *__restrict__ out, uint64_t *__restrict__ leaf_end) {
@@ -3705,10 +3748,12 @@ static int records_onesweep(rfx_ctx *ctx, const ReadSrc &rsrc_in, const Level &l
         RFX_LAUNCH(k_fix_holes<Rec>, dim3((unsigned)nb), dim3(FH_T), 0, os, G, dst, d_seg_begin, d_seg_end,
                    totals.as<unsigned long long>());
     }
-    int h_over = 0;
+    int h_flag[2] = {0, 0};
     RFX_HIP(hipMemcpyAsync(h_tot, totals.p, 16, hipMemcpyDeviceToHost, ctx->stream));
-    RFX_HIP(hipMemcpyAsync(&h_over, d_overflow, 4, hipMemcpyDeviceToHost, ctx->stream));
+    RFX_HIP(hipMemcpyAsync(h_flag, d_overflow, 8, hipMemcpyDeviceToHost, ctx->stream));
     RFX_TRY(sync_checked(ctx));
+    const int h_over = h_flag[0];
+    if (h_flag[1]) ctx->timing["stat_l1_void_rounds"].launches += 1;     // a round outran its two extents (not: a region ran out)
     if (getenv("RFX_TRACE"))
         fprintf(stderr, "one-sweep level 1: %llu records in regions of %llu (sample 1/%d, %d workgroups, extents of %u)%s\n", h_tot[1], h_tot[0], sample, G, ose,
                 h_over ? " -- a region overflowed: two passes instead" : "");
