@@ -51,7 +51,7 @@ struct rfx_ctx {
     void *ws_get(int slot, size_t bytes) {
         WsSlot &w = ws[slot];
         if (w.bytes >= bytes && w.p) {
-            // slots 0 and 1 are only ever asked for as the DESTINATION of the next kernel (rfx_kmer.hip)
+            // slots 0 and 1 are only ever asked for as the DESTINATION of the next kernel (rfx_kmer.hip, rfx_count_sk.hip)
             if ((rfx_poison() & 4) && slot < 2) (void)hipMemsetAsync(w.p, 0xA5, bytes, stream);
             return w.p;
         }
@@ -318,7 +318,8 @@ int exclusive_scan2_u32_to_u64(rfx_ctx *ctx, const uint32_t *d_in_a, const uint3
 int sort_pairs(rfx_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, int64_t n, int key_bits,
                uint64_t *d_tmp_keys, uint32_t *d_tmp_vals);   // result in d_keys/d_vals
 
-// ---- rfx_kmer.hip
+// ---- the count stage: rfx_kmer.hip, and rfx_count_sk.hip for level 1 of the record paths (the bucket_*records_by_owner* calls);
+// what the two units share among themselves is in rfx_count.h
 struct ReadStore {
     const uint64_t *words; int64_t n_reads; int words_per_read; int read_len;
     int k, front_clip, end_clip;
@@ -381,6 +382,7 @@ int count_wide_n_from_reads(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_rea
                             int64_t *out_distinct, const uint32_t *d_read_len = nullptr, int ec = 0, int64_t n_inst = -1);
 int bucket_wide_n_by_owner(rfx_ctx *ctx, const uint64_t *d_words, int64_t n_reads, int wpr, int64_t nk, int k, int fc,
                            const uint32_t *d_read_len, int ec, int n_owners, void *d_out, int64_t *d_owner_off, int64_t *h_owner_off);
+// ---- rfx_synth.hip : the benchmark's reads, generated on the device
 int synth_genome(rfx_ctx *ctx, uint64_t seed, int64_t genome_len, uint64_t *d_genome);
 int synth_reads(rfx_ctx *ctx, uint64_t seed, const uint64_t *d_genome, int64_t genome_len,
                 int64_t first_read, int64_t n_reads, int read_len, uint32_t err, int words_per_read,
