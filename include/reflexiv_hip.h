@@ -738,6 +738,26 @@ int rfx_dev_ksort_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off
                       rfx_dyn_packed *d_out);
 int rfx_ksort_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, const rfx_ksort_params *params, char *out,
                    int64_t cap, int64_t *out_len);
+/* The same stage straight from the counter's arrays in HBM, no text between the counter and the set.
+ *   rfx_dev_ksort_from_counts  steps 1-4: EXACTLY the set rfx_dev_ksort_binarize gives for the rows `KMER,count\n` of the n rows of
+ *                              (d_keys, d_counts) followed by the rows `KMER,1\n` of the n_extra keys of d_extra_keys (the mercy
+ *                              k-mers: duplicates allowed, nothing is merged) -- record for record, every word of the set included
+ *   rfx_dev_ksort_run_counts   steps 1-8 behind that binarizer: EXACTLY the set of rfx_dev_ksort_run on those rows
+ * KEYS: the counter's format, params->k / 32 + 1 words a row -- k <= 31: one word, the last base in the two lowest bits (what
+ * rfx_dev_count_reads_ragged and rfx_dev_mercy_kmers write); k > 31: 32 bases a full word, the first in the two highest bits, and the
+ * k % 32 last bases in the lowest bits of the last word (rfx_dev_count_reads_ragged_w).  Whatever the last word holds above its
+ * bases is ignored.  The rows are taken in array order (the counter's is ascending; nothing here depends on it).
+ * COUNTS: count_bytes 4 (int32, the k <= 31 counter) or 8 (int64, the k > 31 counter).  A count is read as the text path reads its
+ * digits: 1,000,000,000 or more behaves as 1,000,000,000; a row is kept when that value is <= max_cov (an extra row when 1 <=
+ * max_cov), and left = right = the value clamped to 30000.  A negative count has no text the binarizer takes: RFX_E_ARG.
+ * Everything else as rfx_dev_ksort_binarize / _run with n + n_extra in place of n_rows: the supported k (and k % 32 == 0 is refused
+ * here, RFX_E_ARG: the counter writes no keys of such a k), the parameter checks, cap_n >= 2 (n + n_extra), cap_words >= 2 (n +
+ * n_extra) for from_counts and 0 for run_counts, RFX_E_CAP with n and need_words set and nothing written, n + n_extra = 0 valid,
+ * 2^31 rows or more RFX_E_LIMIT.  count_bytes other than 4 or 8, a negative n, a null array where its n > 0: RFX_E_ARG. */
+int rfx_dev_ksort_from_counts(rfx_ctx *ctx, const uint64_t *d_keys, const void *d_counts, int count_bytes, int64_t n,
+                              const uint64_t *d_extra_keys, int64_t n_extra, const rfx_ksort_params *params, rfx_dyn_packed *d_out);
+int rfx_dev_ksort_run_counts(rfx_ctx *ctx, const uint64_t *d_keys, const void *d_counts, int count_bytes, int64_t n,
+                             const uint64_t *d_extra_keys, int64_t n_extra, const rfx_ksort_params *params, rfx_dyn_packed *d_out);
 
 /* The k-mer reduction stage (Count_<k1>_reduced and the rewritten Count_<k2>_sorted / Count_<k2>_reduced) on
  * the same PACKED record sets in HBM: P/ReflexivDSDynamicKmerRuduction.java `assemblyFromKmer` (:143-287).  It compares the sorted
@@ -808,6 +828,79 @@ int rfx_dev_reduce_run(rfx_ctx *ctx, const char *d_text_short, const int64_t *d_
 int rfx_reduce_text(rfx_ctx *ctx, const char *text_short, const int64_t *row_off_short, int64_t n_short, const char *text_long,
                     const int64_t *row_off_long, int64_t n_long, int P, const rfx_reduce_params *params, char *out_short, int64_t cap_short,
                     int64_t *out_len_short, char *out_long, int64_t cap_long, int64_t *out_len_long);
+/* The same stage on two PACKED sets of full k-mers, as rfx_dev_ksort_run / rfx_dev_reduce_run return them: no text between the
+ * sorter and the reduction or between one pair and the next.
+ *   rfx_dev_reduce_union_packed   EXACTLY the set of rfx_dev_reduce_union on the texts rfx_dev_ksort_to_text(d_short, k1) and
+ *                                 rfx_dev_ksort_to_text(d_long, k2): the records of d_long whose key has k2 bases, then those of
+ *                                 d_short whose key has k1 bases, each in its own order; a record of any other key length is
+ *                                 dropped -- so the final set of the pair (k0, k1) is the short input of the pair (k1, k2) as it is
+ *   rfx_dev_reduce_run_packed     the whole driver behind that union: EXACTLY the set of rfx_dev_reduce_run on those two texts
+ * A field goes through what the text would do to it: the key's bases and nothing behind them, the marker as nine decimal digits
+ * hold it, left / right the same and clamped to +-30000; an extension of the input is not read (the text writer prints none).
+ * Capacities cap_n >= d_short->n + d_long->n, cap_words 0; RFX_E_CAP with n and need_words set and nothing written.  RFX_E_ARG,
+ * nothing written: a bad pair, P outside 1..63, a null pointer or an input set without its arrays.  d_out's arrays must not be
+ * the inputs'.  Either input, or both, may be empty. */
+int rfx_dev_reduce_union_packed(rfx_ctx *ctx, const rfx_dyn_packed *d_short, const rfx_dyn_packed *d_long, const rfx_reduce_params *params,
+                                rfx_dyn_packed *d_out);
+int rfx_dev_reduce_run_packed(rfx_ctx *ctx, const rfx_dyn_packed *d_short, const rfx_dyn_packed *d_long, int P,
+                              const rfx_reduce_params *params, rfx_dyn_packed *d_out);
+/* Full k-mers back to the sub-k-mer records of the dynamic-k passes without their text: d_sets is a HOST
+ * array of n_sets (0..64) packed sets of full k-mers, key_lens a host array of as many key lengths (1..124).  The output is, set
+ * after set in array order, EXACTLY what rfx_dev_dyn_binarize form 0 gives for the rows rfx_dev_ksort_to_text(d_sets[j],
+ * key_lens[j]) writes: of every record whose key has key_lens[j] bases, in set order, key = the k-mer without its last base,
+ * extension = that base, marker 1, left / right through their decimal text and clamped to +-30000.  The same set may stand in the
+ * array more than once, with another length each time.  Capacities cap_n >= the sum of the sets' n and cap_words the same (a
+ * one-base extension takes one word); RFX_E_CAP with n and need_words set and nothing written; RFX_E_ARG, nothing written: n_sets or
+ * a key length out of range, a null pointer, a set without its arrays. */
+int rfx_dev_dyn_from_kmers(rfx_ctx *ctx, const rfx_dyn_packed *d_sets, const int *key_lens, int n_sets, rfx_dyn_packed *d_out);
+/* REDUCE FROM READS in one resident call: Pipelines.reflexivDSDynamicReductionPipe (Pipelines.java:1315-1737,
+ * `reflexiv reduce -fastq reads -klist ...`) on the 2-bit read store in HBM, which the caller encodes ONCE (rfx_dev_encode_reads).
+ * For every k of klist, in order: (1) rfx_dev_count_reads_ragged (k <= 31) or rfx_dev_count_reads_ragged_w (k > 31) with min_cov,
+ * max_cov and the clips; (2) if sensitive and k <= 31, rfx_dev_mercy_kmers on those solid keys; (3) rfx_dev_ksort_run_counts with
+ * max_k = the last k of the list and E by the rule below; (4) from the second k on rfx_dev_reduce_run_packed(previous, this, P): the
+ * records of k1 bases of its result are Count_<k1>_reduced, the whole result is the next pair's short input, and the last pair's
+ * records of k_last bases are Count_<k_last>_reduced.  d_out receives what rfx_dev_dyn_from_kmers makes of all Count_*_reduced in
+ * the order of the k list -- the set rfx_dev_dyn_run takes for the first-four passes -- and out_n_per_k (a HOST array of n_k
+ * entries) each k's row count.  No text passes between the counter and that set.
+ * THE E RULE (Pipelines.java:1412-1416, :1489-1493; the reference mutates param, so it is sticky): sorting the FIRST k of the list
+ * sets E = 3 min_cov iff (k >= 61 and the second k < 81) or k >= 81; sorting any later k sets it iff k >= 61; once set it stays
+ * set; until then E = min_error_cov.
+ * DEVIATION, stated: the reference reads the glob Count_*_reduced (Pipelines.java:857), whose order differs from the list's once a
+ * list reaches k >= 100 (Count_101 sorts ahead of Count_23); here the order is the list's, always.
+ * RFX_E_ARG, nothing written: n_k outside 2..16; a list that is not strictly ascending; a k outside 8..124, or 32, 63, 94 (the
+ * sorter refuses them), or 64, 96 (the k > 31 counter does); P outside 1..63; a negative clip, max_cov or min_cov; a switch that is
+ * not 0 or 1; min_cov above 10000 (3 min_cov is the sorter's int E); words_per_read < 1 or 32 words_per_read < max_read_len; a null
+ * pointer; and -- checked for EVERY k with the E the rule gives it, before any work -- whatever the stages themselves refuse
+ * (min_error_cov <= 0 -- also 3 min_cov <= 0 where the rule sets it --, min_repeat_fold < 1, sensitive with more than 937 words a
+ * read, a read of 30000 bases or more in sensitive mode).  n_reads = 0 gives an empty set.  A short d_out: RFX_E_CAP with n and
+ * need_words set and NOTHING written -- the sets are not kept, so the caller's retry with arrays that hold them runs the whole call
+ * again.  MEMORY: two k's sets and one stage's scratch at a time, beside the Count_<k>_reduced records of the k already done (a
+ * pair's final set is cut down to them as soon as the next pair has consumed it). */
+typedef struct {
+    int    min_cov;          /* minKmerCoverage (2)                                          */
+    int    max_cov;          /* maxKmerCoverage (10000000)                                   */
+    int    min_error_cov;    /* minErrorCoverage, E, until the rule above replaces it (8)    */
+    int    bubble;           /* param.bubble (1)                                             */
+    int    sensitive;        /* -sensitive: the mercy k-mers of every k <= 31 (0)            */
+    int    front_clip;       /* (0)                                                          */
+    int    end_clip;         /* (0)                                                          */
+    int    P;                /* the partitions of the reduction's sorts (8)                  */
+    double min_repeat_fold;  /* minRepeatFold, F (1.5)                                       */
+} rfx_reduce_reads_params;
+void rfx_reduce_reads_default_params(rfx_reduce_reads_params *p);
+int rfx_dev_reduce_reads(rfx_ctx *ctx, const uint64_t *d_words, const uint32_t *d_read_len, int64_t n_reads, int words_per_read,
+                         int max_read_len, const int *klist, int n_k, const rfx_reduce_reads_params *params, rfx_dyn_packed *d_out,
+                         int64_t *out_n_per_k);
+/* HOST FORM: ASCII reads (bases + n_reads + 1 offsets, as rfx_mercy_text takes them; any base other than A, C, G reads as T) in, ONE
+ * text buffer out that holds the rows `KMER,marker|left|right\n` of Count_<k>_reduced of every k in list order; out_off (a host
+ * array of n_k + 1 entries) receives where each k's rows begin and end, *out_len = out_off[n_k].  One upload and one 2-bit encode of
+ * the reads, the stages as in rfx_dev_reduce_reads, one copy back per k.  The rows of k are rfx_dev_ksort_to_text's of the set that
+ * holds Count_<k>_reduced, so the text equals what `sort` per k and `reduce` pair by pair write, E rule included.  A short buffer
+ * follows rfx_reduce_text's rule: RFX_E_CAP with *out_len and every out_off set and NOTHING written.  RFX_E_ARG as
+ * rfx_dev_reduce_reads (words_per_read is the longest read's); offsets that run backwards; a null pointer.  RFX_E_LIMIT: 2^31 reads
+ * or more.  n_reads = 0 gives an empty text. */
+int rfx_reduce_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_off, int64_t n_reads, const int *klist, int n_k,
+                     const rfx_reduce_reads_params *params, char *out, int64_t cap, int64_t *out_len, int64_t *out_off);
 
 /* The contig fixing stage (Assembly_intermediate/04Fixing) on the same PACKED record sets in HBM:
  * P/ReflexivDSDynamicKmerFixing.java `assemblyFromKmer` (:125-260).  It is the stage directly behind the last dynamic-k iteration: its

@@ -57,6 +57,12 @@ class CReduceParams(C.Structure):
     _fields_ = [("k1", C.c_int), ("k2", C.c_int), ("max_k", C.c_int)]
 
 
+class CReduceReadsParams(C.Structure):
+    """rfx_reduce_reads_params."""
+    _fields_ = [("min_cov", C.c_int), ("max_cov", C.c_int), ("min_error_cov", C.c_int), ("bubble", C.c_int), ("sensitive", C.c_int),
+                ("front_clip", C.c_int), ("end_clip", C.c_int), ("P", C.c_int), ("min_repeat_fold", C.c_double)]
+
+
 class CFixParams(C.Structure):
     """rfx_fix_params."""
     _fields_ = [("max_k", C.c_int), ("scramble", C.c_int), ("max_iteration", C.c_int)]
@@ -125,6 +131,8 @@ SYMBOLS = [
     "rfx_dev_dyn_extend_pass", "rfx_dev_dyn_run", "rfx_dev_dyn_to_text", "rfx_dyn_run_text",
     "rfx_ksort_default_params", "rfx_dev_ksort_binarize", "rfx_dev_ksort_fork_filter", "rfx_dev_ksort_reflect",
     "rfx_dev_ksort_full_kmers", "rfx_dev_ksort_to_text", "rfx_dev_ksort_run", "rfx_ksort_text",
+    "rfx_dev_ksort_from_counts", "rfx_dev_ksort_run_counts", "rfx_dev_reduce_union_packed", "rfx_dev_reduce_run_packed",
+    "rfx_dev_dyn_from_kmers", "rfx_reduce_reads_default_params", "rfx_dev_reduce_reads", "rfx_reduce_reads",
     "rfx_reduce_default_params", "rfx_dev_reduce_union", "rfx_dev_reduce_left_prepare", "rfx_dev_reduce_adjust",
     "rfx_dev_reduce_right_prepare", "rfx_dev_reduce_full_kmers", "rfx_dev_reduce_neutralize", "rfx_dev_reduce_run", "rfx_reduce_text",
     "rfx_fix_default_params", "rfx_dev_fix_binarize", "rfx_dev_fix_contig_ends", "rfx_dev_fix_kmer_set", "rfx_dev_fix_fork_filter",
@@ -138,7 +146,7 @@ SYMBOLS = [
 
 # prototypes of the packed entry points (ctx, then as include/reflexiv_hip.h declares them)
 _PK, _HR, _CP, _KP, _RP, _FP, _I, _L, _P = "PK", "HR", "CP", "KP", "RP", "FP", C.c_int, C.c_int64, C.c_void_p
-_EC, _ES, _MP, _MH = "EC", "ES", "MP", "MH"
+_EC, _ES, _MP, _MH, _RR = "EC", "ES", "MP", "MH", "RR"
 _DYN_PACKED_ARGS = {
     "rfx_dev_dyn_pack": (_HR, _PK),
     "rfx_dev_dyn_unpack": (_PK, _HR),
@@ -157,6 +165,15 @@ _DYN_PACKED_ARGS = {
     "rfx_dev_ksort_to_text": (_PK, _I, _P, _L, _P, _P, _P),
     "rfx_dev_ksort_run": (_P, _P, _L, _KP, _PK),
     "rfx_ksort_text": (_P, _P, _L, _KP, _P, _L, _P),
+    "rfx_dev_ksort_from_counts": (_P, _P, _I, _L, _P, _L, _KP, _PK),
+    "rfx_dev_ksort_run_counts": (_P, _P, _I, _L, _P, _L, _KP, _PK),
+    # the packed seams of the reduction: two packed sets in, and an array of packed sets with one key length each
+    "rfx_dev_reduce_union_packed": (_PK, _PK, _RP, _PK),
+    "rfx_dev_reduce_run_packed": (_PK, _PK, _I, _RP, _PK),
+    "rfx_dev_dyn_from_kmers": (_P, _P, _I, _PK),
+    # the driver from reads: the read store and the k list in, the set of the first-four passes and each k's row count out
+    "rfx_dev_reduce_reads": (_P, _P, _L, _I, _I, _P, _I, _RR, _PK, _P),
+    "rfx_reduce_reads": (_P, _P, _L, _P, _I, _RR, _P, _L, _P, _P),
     # the k-mer reduction stage on the same packed sets (rfx_reduce_params)
     "rfx_dev_reduce_union": (_P, _P, _L, _P, _P, _L, _RP, _PK),
     "rfx_dev_reduce_left_prepare": (_PK, _RP, _PK),
@@ -257,7 +274,7 @@ def lib():
                                               C.POINTER(CContigsPacked) if a == _CP else C.POINTER(CKsortParams) if a == _KP else C.POINTER(CReduceParams) if a == _RP else
                                               C.POINTER(CFixParams) if a == _FP else C.POINTER(CEndextConsensus) if a == _EC else
                                               C.POINTER(CEndextSet) if a == _ES else C.POINTER(CMapParams) if a == _MP else
-                                              C.POINTER(CMapHits) if a == _MH else a for a in _DYN_PACKED_ARGS[name]]
+                                              C.POINTER(CMapHits) if a == _MH else C.POINTER(CReduceReadsParams) if a == _RR else a for a in _DYN_PACKED_ARGS[name]]
                 continue
             if name == "rfx_dyn_attribute_unpack":
                 fn.restype = None
@@ -273,6 +290,10 @@ def lib():
             if name == "rfx_fix_default_params":
                 fn.restype = None
                 fn.argtypes = [C.POINTER(CFixParams), C.c_int]
+                continue
+            if name == "rfx_reduce_reads_default_params":
+                fn.restype = None
+                fn.argtypes = [C.POINTER(CReduceReadsParams)]
                 continue
             if name == "rfx_map_default_params":
                 fn.restype = None

@@ -1145,6 +1145,29 @@ class Reflexiv:
         return self._grow_call(self.L.rfx_dev_ksort_run, "rfx_dev_ksort_run", out or DynPacked(2 * n_rows, 0),
                                   lambda co: (d_text.data_ptr(), d_row_off.data_ptr(), n_rows, C.byref(params), C.byref(co)))
 
+    def _ksort_counts_call(self, fn, name, d_keys, d_counts, n, d_extra, n_extra, params, out):
+        """the two entry points on the counter's arrays: keys (torch int64 in HBM, k // 32 + 1 words a row), counts (torch int32 or
+        int64; its dtype is the count_bytes), extra keys of count 1 (None: none)"""
+        n = int(d_counts.numel()) if n is None else int(n)
+        W = int(params.k) // 32 + 1
+        n_extra = (int(d_extra.numel()) // W if d_extra is not None else 0) if n_extra is None else int(n_extra)
+        count_bytes = int(d_counts.element_size()) if d_counts is not None else 4
+        out = out or DynPacked(2 * (n + n_extra), 0 if name.endswith("run_counts") else 2 * (n + n_extra))
+        return self._grow_call(fn, name, out, lambda co: (
+            d_keys.data_ptr() if d_keys is not None else None, d_counts.data_ptr() if d_counts is not None else None, count_bytes, n,
+            d_extra.data_ptr() if d_extra is not None else None, n_extra, C.byref(params), C.byref(co)))
+
+    def ksort_from_counts(self, d_keys, d_counts, params, n=None, d_extra=None, n_extra=None, out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_ksort_from_counts: the counter's keys and counts in HBM (count_reads_ragged[_w]_dev), then the mercy k-mers (count
+        1) -> the set ksort_binarize gives for their `KMER,count` rows, without the text"""
+        return self._ksort_counts_call(self.L.rfx_dev_ksort_from_counts, "rfx_dev_ksort_from_counts", d_keys, d_counts, n, d_extra, n_extra,
+                                       params, out)
+
+    def ksort_run_counts(self, d_keys, d_counts, params, n=None, d_extra=None, n_extra=None, out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_ksort_run_counts: steps 1-8 on the counter's arrays -> the full k-mers, as ksort_run on their rows"""
+        return self._ksort_counts_call(self.L.rfx_dev_ksort_run_counts, "rfx_dev_ksort_run_counts", d_keys, d_counts, n, d_extra, n_extra,
+                                       params, out)
+
     def ksort_to_text_dev(self, d: "DynPacked", k: int, d_text=None, want_offsets=True):
         """rfx_dev_ksort_to_text -> (torch uint8 tensor in HBM holding the rows "KMER,1|l|r\n", its length, the row offsets
         (torch int64 in HBM, rows + 1 entries in use; None without want_offsets), the rows)"""
@@ -1223,6 +1246,71 @@ class Reflexiv:
         return self._grow_call(self.L.rfx_dev_reduce_run, "rfx_dev_reduce_run", out or DynPacked(ns + nl, 0),
                                   lambda co: (d_text_short.data_ptr(), d_off_short.data_ptr(), ns, d_text_long.data_ptr(), d_off_long.data_ptr(), nl,
                                               int(P), C.byref(params), C.byref(co)))
+
+    def reduce_union_packed(self, short: "DynPacked", long: "DynPacked", params, out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_reduce_union_packed: two packed sets of full k-mers (ksort_run / reduce_run results) -> what reduce_union gives for
+        their ksort_to_text_dev texts (k1 of `short`, k2 of `long`), without the texts"""
+        cs, cl = short._c(), long._c()
+        return self._grow_call(self.L.rfx_dev_reduce_union_packed, "rfx_dev_reduce_union_packed", out or DynPacked(short.n + long.n, 0),
+                                  lambda co: (C.byref(cs), C.byref(cl), C.byref(params), C.byref(co)))
+
+    def reduce_run_packed(self, short: "DynPacked", long: "DynPacked", P: int, params, out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_reduce_run_packed: the whole driver on two packed sets of full k-mers -> the final full k-mers (both lengths)"""
+        cs, cl = short._c(), long._c()
+        return self._grow_call(self.L.rfx_dev_reduce_run_packed, "rfx_dev_reduce_run_packed", out or DynPacked(short.n + long.n, 0),
+                                  lambda co: (C.byref(cs), C.byref(cl), int(P), C.byref(params), C.byref(co)))
+
+    def dyn_from_kmers(self, sets, key_lens, out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_dyn_from_kmers: packed sets of full k-mers and one key length each -> set after set, the sub-k-mer records
+        dyn_binarize_dev form 0 gives for the ksort_to_text_dev rows of that length"""
+        sets, key_lens = list(sets), [int(x) for x in key_lens]
+        assert len(sets) == len(key_lens)
+        m = len(sets)
+        arr = (_lib.CDynPacked * max(m, 1))(*[s._c() for s in sets])
+        lens = (C.c_int * max(m, 1))(*key_lens)
+        total = sum(s.n for s in sets)
+        return self._grow_call(self.L.rfx_dev_dyn_from_kmers, "rfx_dev_dyn_from_kmers", out or DynPacked(total, total),
+                                  lambda co: (C.addressof(arr), C.addressof(lens), m, C.byref(co)))
+
+    def reduce_reads_params(self, **kw) -> "_lib.CReduceReadsParams":
+        """rfx_reduce_reads_default_params (min_cov 2, max_cov 10000000, min_error_cov 8, min_repeat_fold 1.5, bubble 1, sensitive 0,
+        no clips, P 8), then **kw"""
+        return self._params(_lib.CReduceReadsParams, self.L.rfx_reduce_reads_default_params, "rfx_reduce_reads_params", **kw)
+
+    def reduce_reads_dev(self, d_words, d_read_len, n_reads: int, words_per_read: int, max_read_len: int, klist, params=None,
+                         out: "DynPacked" = None):
+        """rfx_dev_reduce_reads: the 2-bit read store in HBM (torch tensors, as encode_reads_dev writes them) and a k list -> (the set of
+        the first-four passes: the sub-k-mer records of every Count_<k>_reduced in list order, [each k's row count]).  A set that
+        turns out too small is regrown and the call made again."""
+        klist = [int(k) for k in klist]
+        params = params or self.reduce_reads_params()
+        ks = (C.c_int * max(len(klist), 1))(*klist)
+        per_k = (C.c_int64 * max(len(klist), 1))()
+        out = self._grow_call(self.L.rfx_dev_reduce_reads, "rfx_dev_reduce_reads", out or DynPacked(1 << 16, 1 << 16), lambda co: (
+            d_words.data_ptr() if d_words is not None else None, d_read_len.data_ptr() if d_read_len is not None else None, int(n_reads),
+            int(words_per_read), int(max_read_len), C.addressof(ks), len(klist), C.byref(params), C.byref(co), C.addressof(per_k)))
+        return out, [int(x) for x in per_k[:len(klist)]]
+
+    def reduce_reads_text(self, reads, klist, params=None):
+        """rfx_reduce_reads: the reads -- a list of bytes, or (the bases as one numpy uint8 array, the n + 1 int64 offsets) -- and a k
+        list -> [the rows of Count_<k>_reduced as bytes, one entry per k]; one upload, everything between in HBM"""
+        klist = [int(k) for k in klist]
+        params = params or self.reduce_reads_params()
+        if isinstance(reads, tuple):
+            bases, off = np.ascontiguousarray(reads[0], np.uint8), np.ascontiguousarray(reads[1], np.int64)
+        else:
+            reads = [bytes(r) for r in reads]
+            bases = np.frombuffer(b"".join(reads), np.uint8) if reads else np.zeros(0, np.uint8)
+            off = np.zeros(len(reads) + 1, np.int64)
+            off[1:] = np.cumsum([len(r) for r in reads])
+        n = len(off) - 1
+        bases = bases if len(bases) else np.zeros(1, np.uint8)
+        ks = (C.c_int * max(len(klist), 1))(*klist)
+        offs = np.zeros(len(klist) + 1, np.int64)
+        text, = self._host_text_call("rfx_reduce_reads", [max(1 << 16, 4 * len(bases))], lambda o, c, ln: self.L.rfx_reduce_reads(
+            self.ctx, bases.ctypes.data, off.ctypes.data, n, C.addressof(ks), len(klist), C.byref(params), o[0].ctypes.data, c[0], C.addressof(ln[0]),
+            offs.ctypes.data))
+        return [text[int(a):int(b)] for a, b in zip(offs[:-1], offs[1:])]
 
     @staticmethod
     def _row_offsets(text: bytes):

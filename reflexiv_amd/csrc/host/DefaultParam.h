@@ -25,6 +25,7 @@ struct DefaultParam {
     std::string kmerList = "23,31,41,53,67,81,95";   // -klist   :87; `sort` reads its LAST entry (param.kmerListInt, :157-160)
     int minContig = 500;                     // -mincontig   :107
     bool bubble = true;                      // -bubble clears it (Parameter.java:422-424)
+    bool sensitive = false;                  // -sensitive: the mercy k-mers of every k <= 31 (`reduce -fastq`)
     int partitions = 0;                      // -partition   :112
     int maximumIteration = 150;              // -maxiter     :114
     int minimumIteration = 15;               // -miniter     :115
@@ -77,6 +78,7 @@ inline DefaultParam importCommandLine(const std::vector<std::string> &args) {
         else if (a == "-partition") p.partitions = std::stoi(need(i++));
         else if (a == "-partitionredu") p.shufflePartition = std::stoi(need(i++));
         else if (a == "-bubble") p.bubble = false;
+        else if (a == "-sensitive") p.sensitive = true;
         else if (a == "--logical-partitions") p.logicalPartitions = std::stoi(need(i++));
         else if (a == "--twin") p.twin = need(i++) == "ds" ? 0 : 1;
         else if (a == "--resident") p.resident = true;

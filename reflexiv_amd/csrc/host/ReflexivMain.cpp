@@ -432,6 +432,31 @@ void ReflexivMain::kmerReduction(const std::string &shortText, const std::string
     *reducedShort = std::move(o1); *rewrittenLong = std::move(o2);
 }
 
+std::vector<std::string> ReflexivMain::kmerReductionFromReads(const std::string &fastqText, const std::vector<int> &klist, int partitions) {
+    std::vector<uint8_t> bases; std::vector<int64_t> readOff;
+    DSFastqFilterOnlySeq{*this}.call(fastqText, bases, readOff);      // as counter()
+    const int64_t nr = (int64_t)readOff.size() - 1;
+    rfx_reduce_reads_params prm;
+    rfx_reduce_reads_default_params(&prm);
+    prm.min_cov = param.minKmerCoverage; prm.max_cov = param.maxKmerCoverage; prm.min_error_cov = param.minErrorCoverage;
+    prm.min_repeat_fold = param.minRepeatFold; prm.bubble = param.bubble ? 1 : 0; prm.sensitive = param.sensitive ? 1 : 0;
+    prm.front_clip = param.frontClip; prm.end_clip = param.endClip; prm.P = partitions;
+    if (bases.empty()) bases.push_back(0);
+    std::string out(std::max<size_t>(4 * bases.size(), 1 << 16), '\0');
+    std::vector<int64_t> off(klist.size() + 1, 0);
+    int64_t len = 0;
+    for (;;) {
+        const int st = rfx_reduce_reads(ctx, bases.data(), readOff.data(), nr, klist.data(), (int)klist.size(), &prm, out.data(), (int64_t)out.size(), &len,
+                                        off.data());
+        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
+        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_reduce_reads: ") + rfx_last_error(ctx));
+        break;
+    }
+    std::vector<std::string> texts;
+    for (size_t i = 0; i < klist.size(); i++) texts.push_back(out.substr((size_t)off[i], (size_t)(off[i + 1] - off[i])));
+    return texts;
+}
+
 // the host forms that take rows and rfx_fix_params and give one text (rfx_fix_text, rfx_ext_text, rfx_ext2_text): the call, again with the
 // length it reported where the buffer was short.  min_commas: what a row must hold to be one of the stage's; stage: the word that a
 // refused row's message begins with

@@ -169,6 +169,11 @@ public:
     // rewritten Count_<k2>_sorted / Count_<k2>_reduced (rewrittenLong).  One call (rfx_reduce_text): everything between on the device.
     void kmerReduction(const std::string &shortText, const std::string &longText, int k1, int k2, int partitions, std::string *reducedShort,
                        std::string *rewrittenLong);
+    // Pipelines.reflexivDSDynamicReductionPipe (P/Pipelines.java:1315-1737) -- `reduce -fastq F -klist K1,K2,... -partition P [-sensitive]`:
+    // the FASTQ text (DSFastqFilterOnlySeq, as the counter reads it) -> the rows of Count_<k>_reduced of every k of the list, in list
+    // order.  One call (rfx_reduce_reads): one upload and one 2-bit encode of the reads; counter, mercy k-mers, sorter and the reduction
+    // of every pair on the device with no text between them; minErrorCoverage follows the orchestrator's rule (:1412-1416, :1489-1493).
+    std::vector<std::string> kmerReductionFromReads(const std::string &fastqText, const std::vector<int> &klist, int partitions);
     // ReflexivDSDynamicKmerFixing.assemblyFromKmer (P/ReflexivDSDynamicKmerFixing.java:125-260) -- `fixing`: the rows
     // "SUBKMER,marker|left|right,EXTENSION" of the last iteration's output -> the rows of Assembly_intermediate/04Fixing.  One call
     // (rfx_fix_text): everything between on the device.  maxKmerSize is the last k of the k list.

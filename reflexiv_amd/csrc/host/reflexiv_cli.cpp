@@ -3,7 +3,8 @@
 // `reflexiv_host mercy -kmerc O/Count_<K> -fastq F[,F2...] -kmer K [-clipf N -clipe N] -outfile O` (Count_<K>_mercy; `sort -kmerc
 // O/Count_<K>,O/Count_<K>_mercy` then reads both, in the order Spark lists them),
 // `reflexiv_host reduce -kmerc SHORT -kmerc2 LONG -kmer K1 -kmer2 K2 [-klist ...] -partition P -outfile O` (Count_<K1>_reduced and
-// Count_<K2>_sorted, or Count_<K2>_reduced when K2 is the last k of the list), `reflexiv_host reduce -kmerc DIR -klist ... -partition P
+// Count_<K2>_sorted, or Count_<K2>_reduced when K2 is the last k of the list), `reflexiv_host reduce -fastq F -klist ... -partition P
+// -outfile O [-sensitive]` (Count_<k>_reduced of every k from the reads in one run), `reflexiv_host reduce -kmerc DIR -klist ... -partition P
 // -outfile O` (DIR/Count_<k> of every k of the list: each through `sort`, then the pairs in the list's order),
 // `reflexiv_host fixing -kmerc ITERATION_OUT [-klist ...] -partition P -outfile O` (O/Assembly_intermediate/04Fixing),
 // `reflexiv_host fixing2 -kmerc O/Assembly_intermediate/04Fixing [-klist ...] -partition P -outfile O` (05FixingAgain and 06ContigEnds),
@@ -45,6 +46,7 @@ int main(int argc, char **argv) {
                                    "       reflexiv_host mercy -kmerc COUNTS -fastq F[,F2...] -kmer K [-clipf N -clipe N] -outfile DIR\n"
                                    "       reflexiv_host reduce -kmerc SHORT -kmerc2 LONG -kmer K1 -kmer2 K2 [-klist ...] -partition P -outfile DIR\n"
                                    "       reflexiv_host reduce -kmerc COUNTS_DIR -klist K1,K2,... -partition P -outfile DIR\n"
+                                   "       reflexiv_host reduce -fastq F[,F2...] -klist K1,K2,... -partition P -outfile DIR [-sensitive]\n"
                                    "       reflexiv_host fixing -kmerc ITERATION_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"
                                    "       reflexiv_host fixing2 -kmerc FIXING_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"
                                    "       reflexiv_host endextend -kmerc FIXING_AGAIN_OUT -sam ROWS [-klist 23,31,...,95] -outfile DIR\n"
@@ -62,7 +64,9 @@ int main(int argc, char **argv) {
             throw std::runtime_error("mercy needs -kmerc COUNTS -fastq F[,F2...] -kmer K [-clipf N -clipe N] -outfile DIR");
         if (cmd == "mercy" && (param.kmerSize < 8 || param.kmerSize > 31))
             throw std::runtime_error("mercy: -kmer " + std::to_string(param.kmerSize) + " is not supported (8..31)");
-        if (cmd == "reduce" && (param.inputKmerPath.empty() || param.outputPath.empty()))
+        if (cmd == "reduce" && !param.inputFqPath.empty() && param.inputKmerPath.empty() && param.outputPath.empty())
+            throw std::runtime_error("reduce needs -fastq F[,F2...] -klist K1,K2,... -partition P -outfile DIR [-sensitive]");
+        if (cmd == "reduce" && param.inputFqPath.empty() && (param.inputKmerPath.empty() || param.outputPath.empty()))
             throw std::runtime_error("reduce needs -kmerc SHORT -kmerc2 LONG -kmer K1 -kmer2 K2 [-klist ...] -partition P -outfile DIR, or -kmerc COUNTS_DIR "
                                      "-klist K1,K2,... -partition P -outfile DIR");
         if (cmd == "reduce" && !param.inputKmerPath2.empty() && (param.kmerSize < 8 || param.kmerSize >= param.kmerSize2 || param.kmerSize2 > 124))
@@ -153,7 +157,14 @@ int main(int argc, char **argv) {
                 write("Count_" + std::to_string(k2) + (k2 == m.lastKmerOfList() ? "_reduced" : "_sorted"), o2);
                 return o2;
             };
-            if (!param.inputKmerPath2.empty()) {
+            if (!param.inputFqPath.empty() && param.inputKmerPath.empty()) {
+                // Pipelines.reflexivDSDynamicReductionPipe() from the reads in one run: Count_<k>_reduced of every k of the list
+                std::vector<int> ks;
+                std::stringstream ss(param.kmerList);
+                for (std::string one; std::getline(ss, one, ',');) ks.push_back(std::stoi(one));
+                const std::vector<std::string> texts = m.kmerReductionFromReads(read_all(param.inputFqPath), ks, P);
+                for (size_t i = 0; i < ks.size(); i++) write("Count_" + std::to_string(ks[i]) + "_reduced", texts[i]);
+            } else if (!param.inputKmerPath2.empty()) {
                 pair(read_all(param.inputKmerPath), read_all(param.inputKmerPath2), param.kmerSize, param.kmerSize2);
             } else {
                 std::vector<int> ks;

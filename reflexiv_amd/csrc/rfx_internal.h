@@ -543,6 +543,15 @@ int dyn_to_text(rfx_ctx *ctx, const DynDev &d, char *d_text, int64_t cap, int64_
 // extension one base) / the rows "KMER,marker|left|right\n" of the records whose key has k bases (own: a buffer of the library's)
 int ks_set_full_kmers(rfx_ctx *ctx, const DynDev &in, DynDev &out);
 int ks_set_to_text(rfx_ctx *ctx, const DynDev &d, int k, char *d_text, int64_t cap, int64_t *total, int64_t *d_row_off, int64_t *n_rows, DevBuf *own);
+// ... and the choice that text writer makes, without the text: keep flags of the records whose key has len bases, their exclusive
+// scan (n + 1 entries) and the total (one host wait; an empty set allocates nothing)
+int ks_select_length(rfx_ctx *ctx, const DynDev &in, int len, DevBuf &keep, DevBuf &rank, int64_t *total);
+// ... and for the driver from reads (rfx_reduce.hip): the body of rfx_dev_ksort_run_counts (its argument checks
+// included) into a set of the library's / the body of rfx_dev_dyn_from_kmers on sets of the library's
+int ks_run_counts(rfx_ctx *ctx, const uint64_t *d_keys, const void *d_counts, int count_bytes, int64_t n, const uint64_t *d_extra, int64_t n_extra,
+                  const rfx_ksort_params *params, DynDev &out);
+int ks_kmers_to_records(rfx_ctx *ctx, const DynDev *const *sets, const int *key_lens, int n_sets, DynDev &out, int64_t *kept_per_set = nullptr);
+int ks_params_check(rfx_ctx *ctx, const rfx_ksort_params *params);   // what the sorter refuses of its parameters, nothing else
 
 // ---- rfx_fixing.hip, shared with rfx_ctgext.hip: everything of the fixing stage behind its contig ends --
 // the distinct end 31-mers (d_kmers, n31 values in emission order, left as they are) as one-base records + the long records, sort,

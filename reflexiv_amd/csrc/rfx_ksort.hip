@@ -19,7 +19,8 @@
 //
 // Kernels: k_ks_bin_sizes (one thread per row: the cut at the comma, the count, keep or drop), a scan, k_ks_bin_emit (the
 // k-mer's words from its letters, the reverse complement word-wise: complement, 2-bit group reversal of the four words, one
-// funnel shift); k_ks_heads + a scan + k_ks_fold<REFLECTED> (the thread at a run's head walks the run with the reference's
+// funnel shift); k_kc_keep, a scan, k_kc_emit (the same set straight from the counter's keys and counts, one thread per row and
+// orientation: DESIGN.md section 32); k_ks_heads + a scan + k_ks_fold<REFLECTED> (the thread at a run's head walks the run with the reference's
 // rules and writes the survivor); k_ks_reflect / k_ks_full (the key shifted by one base across its words, the extension base
 // put in at the other end); k_ks_text_sizes + two scans + k_ks_text_offsets + k_ks_text_fill (one thread per 8 output bytes).
 #include <algorithm>
@@ -82,9 +83,18 @@ __global__ __launch_bounds__(256) void k_ks_bin_sizes(const char *__restrict__ t
     cnt[r] = cv;
     if (bad) atomicOr(&flags->bad, bad);
 }
+// record q of the binarizers' output from a k-mer w: key = the first k - 1 bases, extension = base k - 1 at the top of one word,
+// marker 1 (the sub-k-mer record of the binarizers here and of rfx_dyn_binarize form 0)
+__device__ __forceinline__ void ks_emit(const DynOut &o, int64_t q, const Pk4 &w, int k, int32_t l, int32_t r) {
+    pk_store(o.key, q, pk_keep4(w, k - 1));
+    o.key_len[q] = (uint8_t)(k - 1);
+    o.ext[q] = pk_base(w, k - 1) << 62;
+    o.ext_off[q] = q;
+    o.ext_len[q] = 1;
+    o.marker[q] = 1; o.left[q] = l; o.right[q] = r;
+}
 // One thread per row; a kept row writes records 2 s and 2 s + 1 (s = its rank among the kept rows): the k-mer's and then its
-// reverse complement's.  key = the first k - 1 bases, extension = base k - 1 at the top of one word, marker 1, left = right =
-// the clamped count.
+// reverse complement's.
 __global__ __launch_bounds__(256) void k_ks_bin_emit(const char *__restrict__ text, int64_t n, const KsParams prm, const uint32_t *__restrict__ keep,
                                                      const uint64_t *__restrict__ slot, const int64_t *__restrict__ kbeg, const int32_t *__restrict__ cnt,
                                                      int64_t n_out, const DynOut o) {
@@ -98,20 +108,54 @@ __global__ __launch_bounds__(256) void k_ks_bin_emit(const char *__restrict__ te
         const char ch = s[j];
         pk_or(f, j >> 5, pk_at(pk_code(ch), j));
     }
-    // reverse complement: complement every base, reverse the 128 groups (the k-mer is then the LAST k), move it to the front
-    const Pk4 rv{pk_rev2(~f.w3), pk_rev2(~f.w2), pk_rev2(~f.w1), pk_rev2(~f.w0)};
-    const Pk4 rc = pk_keep4(pk_shl(rv, 128 - k), k);
+    const Pk4 rc = pk_revcomp(f, k);
     const int32_t c = cnt[r];
-    for (int h = 0; h < 2; h++) {
-        const Pk4 &w = h ? rc : f;
-        const int64_t q = 2 * (int64_t)slot[r] + h;
-        pk_store(o.key, q, pk_keep4(w, k - 1));
-        o.key_len[q] = (uint8_t)(k - 1);
-        o.ext[q] = pk_base(w, k - 1) << 62;
-        o.ext_off[q] = q;
-        o.ext_len[q] = 1;
-        o.marker[q] = 1; o.left[q] = c; o.right[q] = c;
-    }
+    for (int h = 0; h < 2; h++) ks_emit(o, 2 * (int64_t)slot[r] + h, h ? rc : f, k, c, c);
+}
+
+// ---- steps 1-4 straight from the counter's arrays (rfx_dev_ksort_from_counts): no text between the counter and the set ---------------
+// n rows of the counter (keys of k / 32 + 1 words a row as rfx_dev_count_reads_ragged / _ragged_w write them, counts of 4 or 8
+// bytes), then n_extra keys of the same form whose count is 1 (the mercy k-mers)
+struct KcIn { const uint64_t *keys; const void *counts; int64_t n; int count_bytes; const uint64_t *extra; int64_t n_extra; };
+__device__ __forceinline__ int64_t kc_count(const KcIn &in, int64_t r) {
+    return r >= in.n ? 1 : in.count_bytes == 8 ? static_cast<const int64_t *>(in.counts)[r] : (int64_t)static_cast<const int32_t *>(in.counts)[r];
+}
+// One thread per row.  The count is read as k_ks_bin_sizes reads its digits (ten or more: 1,000,000,000); keep = it is <= max_cov
+// (every key has k bases).  A negative count has no text the binarizer takes: KS_BAD_COUNT.
+__global__ __launch_bounds__(256) void k_kc_keep(const KcIn in, const KsParams prm, uint32_t *__restrict__ keep, CallFlags *__restrict__ flags) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= in.n + in.n_extra) return;
+    const int64_t c = kc_count(in, r);
+    keep[r] = (c >= 0 && pk_count_as_text(c) <= (int64_t)prm.max_cov) ? 1u : 0u;
+    if (c < 0) atomicOr(&flags->bad, (uint32_t)KS_BAD_COUNT);
+}
+// One thread per (row, orientation): thread 2 r + h writes record 2 s + h of a kept row (s = its rank among the kept rows), h = 0
+// the k-mer's and h = 1 its reverse complement's -- neighbouring threads write neighbouring records of every array.
+__global__ __launch_bounds__(256) void k_kc_emit(const KcIn in, const KsParams prm, const uint32_t *__restrict__ keep, const uint64_t *__restrict__ slot,
+                                                 int64_t n_out, const DynOut o) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, r = t >> 1;
+    if (t == 0) o.ext_off[n_out] = n_out;
+    if (r >= in.n + in.n_extra || !keep[r]) return;
+    const int k = prm.k, W = (k >> 5) + 1, h = (int)(t & 1);
+    const Pk4 f = pk_from_counter(r < in.n ? in.keys + (int64_t)W * r : in.extra + (int64_t)W * (r - in.n), k);
+    const int32_t c = pk_clamp((int32_t)pk_count_as_text(kc_count(in, r)));
+    ks_emit(o, 2 * (int64_t)slot[r] + h, h ? pk_revcomp(f, k) : f, k, c, c);
+}
+
+// ---- full k-mers back to the sub-k-mer records of the dynamic-k passes (rfx_dev_dyn_from_kmers), and the choice by key length ------
+// keep = the record's key has len bases
+__global__ __launch_bounds__(256) void k_ks_len_keep(const uint8_t *__restrict__ key_len, int64_t n, int len, uint32_t *__restrict__ keep) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) keep[i] = (int)key_len[i] == len ? 1u : 0u;
+}
+// One thread per record of one input set; a kept record writes output record base + (its rank among the kept): what k_ks_text_fill
+// prints of it and rfx_dyn_binarize form 0 reads back -- left / right through their decimal text, then clamped; the marker is 1
+__global__ __launch_bounds__(256) void k_ks_kmer_emit(const DynView v, int64_t n, const uint32_t *__restrict__ keep, const uint64_t *__restrict__ rank,
+                                                      int64_t base, int64_t n_out, const DynOut o) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) o.ext_off[n_out] = n_out;
+    if (i >= n || !keep[i]) return;
+    ks_emit(o, base + (int64_t)rank[i], pk_load(v.key, i), (int)v.key_len[i], pk_clamp(pk_int_as_text(v.left[i])), pk_clamp(pk_int_as_text(v.right[i])));
 }
 
 // ---- steps 5 and 7: the two folds over runs of equal keys -----------------------------------------------------------------------
@@ -352,10 +396,38 @@ static int ks_map(rfx_ctx *ctx, bool full, const DynDev &in, DynDev &out) {
     return RFX_OK;
 }
 
-// steps 1-8; the set stays in HBM between the operators
-static int ks_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, const KsParams &prm, int bubble, DynDev &out) {
-    DynDev a, b;
-    RFX_TRY(ks_binarize(ctx, d_text, d_row_off, n_rows, prm, a));
+// steps 1-4 from the counter's arrays -> a packed set in the library's own buffers: what ks_binarize gives for their rows
+static bool kc_in_ok(const KcIn &in) {
+    return in.n >= 0 && in.n_extra >= 0 && (in.count_bytes == 4 || in.count_bytes == 8) && (in.n == 0 || (in.keys && in.counts)) &&
+           (in.n_extra == 0 || in.extra);
+}
+static int kc_k_ok(rfx_ctx *ctx, int k) {
+    if (k % 32 != 0) return RFX_OK;
+    ctx->last_error = "k-mer sorting from counts: k is a multiple of 32 (the counter writes no keys of that k)";
+    return RFX_E_ARG;
+}
+static int ks_from_counts(rfx_ctx *ctx, const KcIn &in, const KsParams &prm, DynDev &d) {
+    const int64_t n = in.n + in.n_extra;
+    if (n == 0) return dyn_empty(ctx, d);
+    if (n >= ((int64_t)1 << 31)) { ctx->last_error = "k-mer sorting: 2^31 rows or more"; return RFX_E_LIMIT; }
+    DevBuf keep, slot, flags;
+    RFX_ALLOC(keep, uint32_t, n); RFX_ALLOC(slot, uint64_t, n + 1);
+    RFX_TRY(call_flags_init(ctx, flags));
+    RFX_LAUNCH_N(k_kc_keep, n, in, prm, keep.as<uint32_t>(), flags.as<CallFlags>());
+    RFX_TRY(exclusive_scan_u32_to_u64(ctx, keep.as<uint32_t>(), slot.as<uint64_t>(), n));
+    CallFlags f{};
+    RFX_TRY(call_flags_read(ctx, flags, slot.as<uint64_t>() + n, nullptr, nullptr, &f));
+    if (f.bad) { ctx->last_error = "k-mer sorting from counts: a negative count"; return RFX_E_ARG; }
+    const int64_t n_out = 2 * (int64_t)f.total[0];
+    if (n_out == 0) return dyn_empty(ctx, d);
+    RFX_TRY(dyn_alloc(ctx, d, n_out, n_out));
+    RFX_LAUNCH_N(k_kc_emit, 2 * n, in, prm, keep.as<uint32_t>(), slot.as<uint64_t>(), n_out, dyn_out(d));
+    return RFX_OK;
+}
+
+// steps 5-8 behind either binarizer (a is used up); the set stays in HBM between the operators
+static int ks_run_set(rfx_ctx *ctx, DynDev &a, const KsParams &prm, int bubble, DynDev &out) {
+    DynDev b;
     if (bubble) {
         DevBuf ps;
         uint32_t lmin = 0;
@@ -367,6 +439,12 @@ static int ks_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, in
         return ks_map(ctx, true, b, out);
     }
     return ks_map(ctx, true, a, out);
+}
+// steps 1-8 from text
+static int ks_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, const KsParams &prm, int bubble, DynDev &out) {
+    DynDev a;
+    RFX_TRY(ks_binarize(ctx, d_text, d_row_off, n_rows, prm, a));
+    return ks_run_set(ctx, a, prm, bubble, out);
 }
 
 // the text of a set into d_text (filled up to cap); *total = its length, *n_rows = its rows; own: a buffer of the library's
@@ -410,6 +488,55 @@ static int ks_to_text(rfx_ctx *ctx, const DynDev &d, int k, char *d_text, int64_
 int rfx::ks_set_full_kmers(rfx_ctx *ctx, const DynDev &in, DynDev &out) { return ks_map(ctx, true, in, out); }
 int rfx::ks_set_to_text(rfx_ctx *ctx, const DynDev &d, int k, char *d_text, int64_t cap, int64_t *total, int64_t *d_row_off, int64_t *n_rows, DevBuf *own) {
     return ks_to_text(ctx, d, k, d_text, cap, total, d_row_off, n_rows, own);
+}
+// the records of a set whose key has len bases: keep flags, their exclusive scan (n + 1 entries) and the total (nothing allocated for
+// an empty set)
+int rfx::ks_select_length(rfx_ctx *ctx, const DynDev &in, int len, DevBuf &keep, DevBuf &rank, int64_t *total) {
+    *total = 0;
+    if (in.n == 0) return RFX_OK;
+    RFX_ALLOC(keep, uint32_t, in.n); RFX_ALLOC(rank, uint64_t, in.n + 1);
+    RFX_LAUNCH_N(k_ks_len_keep, in.n, in.key_len.as<uint8_t>(), in.n, len, keep.as<uint32_t>());
+    return scan_keep(ctx, keep.as<uint32_t>(), in.n, rank.as<uint64_t>(), total);
+}
+
+// set j's records of key_lens[j] bases, set after set, as the sub-k-mer records rfx_dyn_binarize form 0 makes of their text rows
+int rfx::ks_kmers_to_records(rfx_ctx *ctx, const DynDev *const *sets, const int *key_lens, int n_sets, DynDev &out, int64_t *kept_per_set) {
+    std::vector<DevBuf> keep((size_t)n_sets), rank((size_t)n_sets);
+    std::vector<int64_t> kept((size_t)n_sets, 0);
+    int64_t n_out = 0;
+    for (int j = 0; j < n_sets; j++) {
+        RFX_TRY(ks_select_length(ctx, *sets[j], key_lens[j], keep[(size_t)j], rank[(size_t)j], &kept[(size_t)j]));
+        n_out += kept[(size_t)j];
+        if (kept_per_set) kept_per_set[j] = kept[(size_t)j];
+    }
+    if (n_out == 0) return dyn_empty(ctx, out);
+    RFX_TRY(dyn_alloc(ctx, out, n_out, n_out));
+    int64_t base = 0;
+    for (int j = 0; j < n_sets; j++) {
+        if (kept[(size_t)j] == 0) continue;
+        const DynDev &s = *sets[j];
+        RFX_LAUNCH_N(k_ks_kmer_emit, s.n, dyn_view(s), s.n, keep[(size_t)j].as<uint32_t>(), rank[(size_t)j].as<uint64_t>(), base, n_out, dyn_out(out));
+        base += kept[(size_t)j];
+    }
+    return RFX_OK;
+}
+// the sorter's parameter check alone
+int rfx::ks_params_check(rfx_ctx *ctx, const rfx_ksort_params *params) {
+    KsParams prm;
+    RFX_TRY(ks_params(ctx, params, &prm));
+    return kc_k_ok(ctx, prm.k);
+}
+// steps 1-8 from the counter's arrays (the body of rfx_dev_ksort_run_counts), for the driver in rfx_reduce.hip
+int rfx::ks_run_counts(rfx_ctx *ctx, const uint64_t *d_keys, const void *d_counts, int count_bytes, int64_t n, const uint64_t *d_extra, int64_t n_extra,
+                       const rfx_ksort_params *params, DynDev &out) {
+    const KcIn in{d_keys, d_counts, n, count_bytes, d_extra, n_extra};
+    if (!kc_in_ok(in)) return RFX_E_ARG;
+    KsParams prm;
+    RFX_TRY(ks_params(ctx, params, &prm));
+    RFX_TRY(kc_k_ok(ctx, prm.k));
+    DynDev a;
+    RFX_TRY(ks_from_counts(ctx, in, prm, a));
+    return ks_run_set(ctx, a, prm, params->bubble, out);
 }
 
 extern "C" {
@@ -480,6 +607,46 @@ int rfx_dev_ksort_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off
     RFX_HIP(hipSetDevice(ctx->device));
     DynDev a;
     RFX_TRY(ks_run(ctx, d_text, d_row_off, n_rows, prm, params->bubble, a));
+    return dyn_store(ctx, a, d_out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_ksort_from_counts(rfx_ctx *ctx, const uint64_t *d_keys, const void *d_counts, int count_bytes, int64_t n, const uint64_t *d_extra_keys,
+                              int64_t n_extra, const rfx_ksort_params *params, rfx_dyn_packed *d_out) try {
+    const KcIn in{d_keys, d_counts, n, count_bytes, d_extra_keys, n_extra};
+    if (!ctx || !dyn_packed_out_ok(d_out) || !kc_in_ok(in)) return RFX_E_ARG;
+    KsParams prm;
+    RFX_TRY(ks_params(ctx, params, &prm));
+    RFX_TRY(kc_k_ok(ctx, prm.k));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a;
+    RFX_TRY(ks_from_counts(ctx, in, prm, a));
+    return dyn_store(ctx, a, d_out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_ksort_run_counts(rfx_ctx *ctx, const uint64_t *d_keys, const void *d_counts, int count_bytes, int64_t n, const uint64_t *d_extra_keys,
+                             int64_t n_extra, const rfx_ksort_params *params, rfx_dyn_packed *d_out) try {
+    if (!ctx || !dyn_packed_out_ok(d_out)) return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a;
+    RFX_TRY(ks_run_counts(ctx, d_keys, d_counts, count_bytes, n, d_extra_keys, n_extra, params, a));
+    return dyn_store(ctx, a, d_out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_dyn_from_kmers(rfx_ctx *ctx, const rfx_dyn_packed *d_sets, const int *key_lens, int n_sets, rfx_dyn_packed *d_out) try {
+    if (!ctx || !dyn_packed_out_ok(d_out) || n_sets < 0 || n_sets > 64 || (n_sets > 0 && (!d_sets || !key_lens))) return RFX_E_ARG;
+    for (int j = 0; j < n_sets; j++) {
+        if (!dyn_packed_ok(&d_sets[j])) return RFX_E_ARG;
+        if (key_lens[j] < 1 || key_lens[j] > 124) { ctx->last_error = "full k-mers to sub-k-mer records: a key length outside 1..124"; return RFX_E_ARG; }
+    }
+    RFX_HIP(hipSetDevice(ctx->device));
+    std::vector<DynDev> in((size_t)n_sets);
+    std::vector<const DynDev *> ptr((size_t)n_sets);
+    for (int j = 0; j < n_sets; j++) {
+        RFX_TRY(dyn_borrow(ctx, &d_sets[j], in[(size_t)j]));
+        ptr[(size_t)j] = &in[(size_t)j];
+    }
+    DynDev a;
+    RFX_TRY(ks_kmers_to_records(ctx, ptr.data(), key_lens, n_sets, a));
     return dyn_store(ctx, a, d_out);
 } RFX_API_CATCH(ctx)
 

@@ -138,6 +138,20 @@ __host__ __device__ PK_INLINE void pk_store(uint64_t *__restrict__ key, int64_t 
     p[0] = a.w0; p[1] = a.w1; p[2] = a.w2; p[3] = a.w3;
 }
 
+// the reverse complement of the first len (0..128) bases at the front, zeros behind: the complemented padding turns up ahead of the
+// bases and is shifted out
+__host__ __device__ PK_INLINE Pk4 pk_revcomp(const Pk4 &a, int len) { return pk_reverse(Pk4{~a.w0, ~a.w1, ~a.w2, ~a.w3}, len); }
+// a k-mer as the counter writes it (rfx_dev_count_reads_ragged / _ragged_w: k / 32 full words of 32 bases, then one word with the
+// k % 32 last bases in its LOWEST bits; k <= 31 is that word alone) as a key: k = 1..127, zeros behind the last base; whatever the
+// last word holds above its bases is dropped, and a word the format does not have (k % 32 == 0: none behind the full ones) is not read
+__host__ __device__ PK_INLINE Pk4 pk_from_counter(const uint64_t *__restrict__ w, int k) {
+    const int f = k >> 5, res = k & 31;
+    const uint64_t last = res ? w[f] << (64 - 2 * res) : 0ull;
+    return Pk4{f > 0 ? w[0] : last, f > 1 ? w[1] : f == 1 ? last : 0ull, f > 2 ? w[2] : f == 2 ? last : 0ull, f == 3 ? last : 0ull};
+}
+// what DynamicKmerBinarizer reads out of the decimal text of a count c >= 0: ten digits or more are 1,000,000,000
+__host__ __device__ PK_INLINE int64_t pk_count_as_text(int64_t c) { return c >= 1000000000LL ? 1000000000LL : c; }
+
 // ---- the decimal text of an int, and an int out of text ---------------------------------------------------------------------------
 // (32-bit unsigned arithmetic: 0u - (uint32_t)v is |v| for every int, INT_MIN included)
 __host__ __device__ PK_INLINE int pk_int_chars(int v) {               // characters of std::to_string(v)
@@ -163,6 +177,12 @@ __host__ __device__ PK_INLINE int pk_parse_int(const char *__restrict__ t, int64
     while (i < e && t[i] >= '0' && t[i] <= '9') { if (v < 100000000LL) v = v * 10 + (t[i] - '0'); i++; }
     if (i < e && t[i] == '|') i++;
     return (int)(neg ? -v : v);
+}
+
+// what pk_parse_int reads out of the text pk_int_char writes for v: v itself up to nine digits, the first nine of ten
+__host__ __device__ PK_INLINE int pk_int_as_text(int v) {
+    const uint32_t a = v < 0 ? 0u - (uint32_t)v : (uint32_t)v, t = a >= 1000000000u ? a / 10u : a;
+    return v < 0 ? -(int)t : (int)t;
 }
 
 // a decimal int in t[p, e), p left behind its digits.  sign: '-' allowed; plus: '+' too (Integer.parseInt); canon: as

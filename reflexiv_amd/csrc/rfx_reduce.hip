@@ -117,6 +117,22 @@ __global__ __launch_bounds__(256) void k_rd_bin_emit(const char *__restrict__ te
     o.marker[q] = mlr[3 * r]; o.left[q] = mlr[3 * r + 1]; o.right[q] = mlr[3 * r + 2];
 }
 
+// the same record from a packed set of full k-mers (rfx_dev_reduce_union_packed): one thread per input record, a kept one writes
+// record base + (its rank among the kept) -- what k_ks_text_fill prints of it and k_rd_bin_sizes / k_rd_bin_emit read back: the key's
+// bases (nothing behind them), the marker through its decimal text, left / right through theirs and clamped, no extension
+__global__ __launch_bounds__(256) void k_rd_pk_emit(const DynView v, int64_t n, const uint32_t *__restrict__ keep, const uint64_t *__restrict__ rank,
+                                                    int64_t base, const DynOut o) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !keep[i]) return;
+    const int64_t q = base + (int64_t)rank[i];
+    const int len = (int)v.key_len[i];
+    pk_store(o.key, q, pk_keep4(pk_load(v.key, i), len));
+    o.key_len[q] = (uint8_t)len;
+    o.ext_off[q] = 0;
+    o.ext_len[q] = 0;
+    o.marker[q] = pk_int_as_text(v.marker[i]); o.left[q] = pk_clamp(pk_int_as_text(v.left[i])); o.right[q] = pk_clamp(pk_int_as_text(v.right[i]));
+}
+
 // ---- what an operator asks of its input: keys of la or lb bases, every extension of ext_len bases ------------------------------------
 __global__ __launch_bounds__(256) void k_rd_check(const DynView v, int64_t n, int la, int lb, int ext_len, CallFlags *__restrict__ flags) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -475,13 +491,28 @@ static int rd_neutralize(rfx_ctx *ctx, const DynDev &in, const int64_t *d_ps, in
     return out_part_starts(ctx, d_ps, P, rank.as<uint64_t>(), out_ps.as<int64_t>());
 }
 
-// the driver; the set stays in HBM between the operators
-static int rd_run(rfx_ctx *ctx, const char *d_ts, const int64_t *d_os, int64_t ns, const char *d_tl, const int64_t *d_ol, int64_t nl, int P,
-                  const RdParams &prm, DynDev &out) {
-    DynDev a, b;
+// steps 1-2 from two packed sets of full k-mers: the long set's records of k2 bases, then the short set's of k1 bases -- the set
+// rd_union makes of ks_set_to_text(lng, k2) and ks_set_to_text(sht, k1)
+static int rd_union_packed(rfx_ctx *ctx, const DynDev &sht, const DynDev &lng, const RdParams &prm, DynDev &d) {
+    if (sht.n >= ((int64_t)1 << 31) || lng.n >= ((int64_t)1 << 31)) { ctx->last_error = "k-mer reduction: 2^31 rows or more"; return RFX_E_LIMIT; }
+    DevBuf ks, rs, kl, rl;
+    int64_t ms = 0, ml = 0;
+    RFX_TRY(ks_select_length(ctx, lng, prm.k2, kl, rl, &ml));
+    RFX_TRY(ks_select_length(ctx, sht, prm.k1, ks, rs, &ms));
+    const int64_t n = ml + ms;
+    if (n == 0) return dyn_empty(ctx, d);
+    RFX_TRY(dyn_alloc(ctx, d, n, 0));
+    RFX_HIP(hipMemsetAsync(d.ext_off.as<int64_t>() + n, 0, 8, ctx->stream));
+    if (ml) RFX_LAUNCH_N(k_rd_pk_emit, lng.n, dyn_view(lng), lng.n, kl.as<uint32_t>(), rl.as<uint64_t>(), (int64_t)0, dyn_out(d));
+    if (ms) RFX_LAUNCH_N(k_rd_pk_emit, sht.n, dyn_view(sht), sht.n, ks.as<uint32_t>(), rs.as<uint64_t>(), ml, dyn_out(d));
+    return RFX_OK;
+}
+
+// the driver behind either union (a is used up); the set stays in HBM between the operators
+static int rd_run_set(rfx_ctx *ctx, DynDev &a, int P, const RdParams &prm, DynDev &out) {
+    DynDev b;
     DevBuf ps, ops;
     uint32_t lmin = 0;
-    RFX_TRY(rd_union(ctx, d_ts, d_os, ns, d_tl, d_ol, nl, prm, a));
     RFX_TRY(rd_prepare(ctx, false, a, prm, b));
     RFX_TRY(dyn_sort(ctx, b, P, a, ps, &lmin));
     RFX_TRY(rd_adjust(ctx, false, a, ps.as<int64_t>(), P, prm, b, ops));
@@ -492,10 +523,217 @@ static int rd_run(rfx_ctx *ctx, const char *d_ts, const int64_t *d_os, int64_t n
     RFX_TRY(dyn_sort(ctx, b, P, a, ps, &lmin));
     return rd_neutralize(ctx, a, ps.as<int64_t>(), P, prm, out, ops);
 }
+static int rd_run(rfx_ctx *ctx, const char *d_ts, const int64_t *d_os, int64_t ns, const char *d_tl, const int64_t *d_ol, int64_t nl, int P,
+                  const RdParams &prm, DynDev &out) {
+    DynDev a;
+    RFX_TRY(rd_union(ctx, d_ts, d_os, ns, d_tl, d_ol, nl, prm, a));
+    return rd_run_set(ctx, a, P, prm, out);
+}
 
+// ---- the driver from reads (rfx_dev_reduce_reads): Pipelines.reflexivDSDynamicReductionPipe on the read store ----
+static bool rr_k_ok(int k) { return k >= 8 && k <= 124 && k != 32 && k != 63 && k != 94 && k != 64 && k != 96; }
+// E of every k of the list (Pipelines.java:1412-1416, :1489-1493: the reference mutates param, so the value stays): sorting the first k
+// sets 3 min_cov iff (k >= 61 and the second k < 81) or k >= 81, sorting a later k iff k >= 61
+static std::vector<int> rr_error_cov(const int *klist, int n_k, const rfx_reduce_reads_params &p) {
+    std::vector<int> out((size_t)n_k);
+    int E = p.min_error_cov;
+    for (int i = 0; i < n_k; i++) {
+        const int k = klist[i];
+        if (i == 0 ? ((k >= 61 && klist[1] < 81) || k >= 81) : k >= 61) E = 3 * p.min_cov;
+        out[(size_t)i] = E;
+    }
+    return out;
+}
+static rfx_ksort_params rr_ksort_params(const int *klist, int n_k, int i, int E, const rfx_reduce_reads_params &p) {
+    return rfx_ksort_params{klist[i], klist[n_k - 1], E, p.max_cov, p.bubble, p.min_repeat_fold};
+}
+static int rr_args(rfx_ctx *ctx, const uint64_t *d_words, const uint32_t *d_read_len, int64_t n_reads, int wpr, int max_read_len, const int *klist, int n_k,
+                   const rfx_reduce_reads_params *p) {
+    if (!klist || !p || n_reads < 0 || (n_reads > 0 && (!d_words || !d_read_len)) || wpr < 1 || max_read_len < 0 || (int64_t)wpr * 32 < max_read_len) return RFX_E_ARG;
+    if (n_k < 2 || n_k > 16) { ctx->last_error = "reduction from reads: the k list must hold 2..16 values"; return RFX_E_ARG; }
+    for (int i = 0; i < n_k; i++) {
+        if (!rr_k_ok(klist[i])) { ctx->last_error = "reduction from reads: a k outside 8..124, or 32, 63, 94 (the sorter refuses them), or 64, 96 (the counter does)"; return RFX_E_ARG; }
+        if (i > 0 && klist[i] <= klist[i - 1]) { ctx->last_error = "reduction from reads: the k list is not strictly ascending"; return RFX_E_ARG; }
+        if (p->sensitive && klist[i] <= 31 && wpr > 937) { ctx->last_error = "reduction from reads: sensitive mode takes reads of at most 937 words"; return RFX_E_ARG; }
+    }
+    if (!parts_ok(p->P)) { ctx->last_error = "reduction from reads: P outside 1..63"; return RFX_E_ARG; }
+    if (p->front_clip < 0 || p->end_clip < 0 || p->max_cov < 0 || p->min_cov < 0 || p->min_cov > 10000 || (p->bubble != 0 && p->bubble != 1) ||
+        (p->sensitive != 0 && p->sensitive != 1)) { ctx->last_error = "reduction from reads: a clip, a coverage or a switch out of range"; return RFX_E_ARG; }
+    // what the sorter itself refuses, for every k with the E the rule gives it, ahead of any work
+    const std::vector<int> E = rr_error_cov(klist, n_k, *p);
+    for (int i = 0; i < n_k; i++) {
+        const rfx_ksort_params kp = rr_ksort_params(klist, n_k, i, E[(size_t)i], *p);
+        RFX_TRY(ks_params_check(ctx, &kp));
+    }
+    return RFX_OK;
+}
+static double rr_now_ms() { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e3 + t.tv_nsec * 1e-6; }
+// one k: count (and the mercy k-mers of a k <= 31 in sensitive mode), then steps 1-8 of the sorter on the counter's arrays
+static int rr_sorted(rfx_ctx *ctx, const uint64_t *d_words, const uint32_t *d_read_len, int64_t n_reads, int wpr, int max_read_len, int k,
+                     const rfx_reduce_reads_params &p, const rfx_ksort_params &kp, DynDev &out) {
+    const int W = k / 32 + 1, cb = k <= 31 ? 4 : 8;
+    const double t_enter = rr_now_ms();
+    // every survivor has min_cov instances or more, and a read has at most len - k + 1 windows: that bound always holds, but at depth
+    // it is many times the survivors (12 x at depth 30) and the scratch is the call's largest allocation -- so an eighth of it first,
+    // and where that is short the counter says what it needs and one more count (milliseconds) follows
+    const int64_t inst = n_reads * (int64_t)std::max(max_read_len - k + 1, 0);
+    int64_t cap = inst / std::max(p.min_cov, 1) / 8 + 1024, n = 0, distinct = 0, instances = 0;
+    DevBuf keys, counts, extra;
+    for (int attempt = 0;; attempt++) {
+        RFX_ALLOC(keys, uint64_t, cap * W); RFX_HIP(counts.alloc((size_t)cap * cb, ctx->stream));
+        const int st = k <= 31 ? rfx_dev_count_reads_ragged(ctx, d_words, d_read_len, n_reads, wpr, max_read_len, k, p.front_clip, p.end_clip, p.min_cov, p.max_cov,
+                                                            RFX_TWIN_DS, keys.as<uint64_t>(), counts.as<int32_t>(), cap, &n, &distinct, &instances)
+                               : rfx_dev_count_reads_ragged_w(ctx, d_words, d_read_len, n_reads, wpr, max_read_len, k, p.front_clip, p.end_clip, p.min_cov, p.max_cov,
+                                                              keys.as<uint64_t>(), counts.as<int64_t>(), cap, &n, &distinct, &instances);
+        if (st == RFX_E_CAP && attempt == 0) { cap = n > cap ? n : inst / std::max(p.min_cov, 1) + 1; continue; }
+        if (st == RFX_E_CAP) { ctx->last_error = "reduction from reads: the counter's output did not fit the capacity it asked for"; return RFX_E_STATE; }
+        RFX_TRY(st);
+        break;
+    }
+    const double t_counted = rr_now_ms();
+    int64_t n_extra = 0;
+    if (p.sensitive && k <= 31) {
+        const int st = rfx_dev_mercy_kmers(ctx, keys.as<uint64_t>(), n, d_words, d_read_len, n_reads, wpr, k, p.front_clip, p.end_clip, nullptr, 0, &n_extra);
+        if (st != RFX_E_CAP) RFX_TRY(st);
+        if (n_extra > 0) {
+            RFX_ALLOC(extra, uint64_t, n_extra);
+            RFX_TRY(rfx_dev_mercy_kmers(ctx, keys.as<uint64_t>(), n, d_words, d_read_len, n_reads, wpr, k, p.front_clip, p.end_clip, extra.as<uint64_t>(), n_extra,
+                                        &n_extra));
+        }
+    }
+    const double t_sort = rr_now_ms();
+    const int st = ks_run_counts(ctx, keys.as<uint64_t>(), counts.p, cb, n, extra.as<uint64_t>(), n_extra, &kp, out);
+    if (getenv("RFX_REDUCE_TRACE"))
+        fprintf(stderr, "reduce_reads: k %d: scratch + count %.1f ms (%lld rows of a capacity of %lld), mercy %.1f ms, sort %.1f ms\n", k, t_counted - t_enter,
+                (long long)n, (long long)cap, t_sort - t_counted, rr_now_ms() - t_sort);
+    return st;
+}
+// a pair's final set, once the next pair has consumed it, cut down to its records of len bases (k_rd_pk_emit again: what it does to a
+// field, rfx_dev_dyn_from_kmers does once more anyway, and the marker is not read there)
+static int rr_keep_length(rfx_ctx *ctx, DynDev &d, int len) {
+    DevBuf keep, rank;
+    int64_t m = 0;
+    DynDev half;
+    RFX_TRY(ks_select_length(ctx, d, len, keep, rank, &m));
+    if (m == 0) RFX_TRY(dyn_empty(ctx, half));
+    else {
+        RFX_TRY(dyn_alloc(ctx, half, m, 0));
+        RFX_HIP(hipMemsetAsync(half.ext_off.as<int64_t>() + m, 0, 8, ctx->stream));
+        RFX_LAUNCH_N(k_rd_pk_emit, d.n, dyn_view(d), d.n, keep.as<uint32_t>(), rank.as<uint64_t>(), (int64_t)0, dyn_out(half));
+    }
+    d = std::move(half);                                                  // (d's old buffers are freed in stream order, behind the launch)
+    return RFX_OK;
+}
+// Every k of the list in order: its sorted set, and from the second k on the reduction of the pair (previous, this), whose short
+// input is the pair before's final set as it is.  res[i] = the final set of the pair (k_i, k_i+1): its records of k_i bases are
+// Count_<k_i>_reduced (all that is kept of it once the next pair has consumed it), the last one's records of k_last bases
+// Count_<k_last>_reduced.  sets[i] = where Count_<k_i>_reduced lies.
+// RFX_REDUCE_TRACE (set to anything): one line per k on stderr with the host time of each stage of the driver (every stage returns
+// after the stream has drained, so these are the stages' whole times)
+static int rr_pairs(rfx_ctx *ctx, const uint64_t *d_words, const uint32_t *d_read_len, int64_t n_reads, int wpr, int max_read_len, const int *klist, int n_k,
+                    const rfx_reduce_reads_params &p, std::vector<DynDev> &res, std::vector<const DynDev *> &sets) {
+    const std::vector<int> E = rr_error_cov(klist, n_k, p);
+    DynDev first;                                                      // the first k's sorted set: the short input of the first pair
+    const bool trace = getenv("RFX_REDUCE_TRACE") != nullptr;
+    for (int i = 0; i < n_k; i++) {
+        const int k = klist[i];
+        const rfx_ksort_params kp = rr_ksort_params(klist, n_k, i, E[(size_t)i], p);
+        const double t0 = rr_now_ms();
+        if (i == 0) {
+            RFX_TRY(rr_sorted(ctx, d_words, d_read_len, n_reads, wpr, max_read_len, k, p, kp, first));
+            if (trace) fprintf(stderr, "reduce_reads: k %d E %d: count + sort %.1f ms, %lld records\n", k, kp.min_error_cov, rr_now_ms() - t0, (long long)first.n);
+            continue;
+        }
+        DynDev cur, uni;
+        RFX_TRY(rr_sorted(ctx, d_words, d_read_len, n_reads, wpr, max_read_len, k, p, kp, cur));
+        const double t1 = rr_now_ms();
+        const RdParams prm{klist[i - 1], k};
+        DynDev &sht = i == 1 ? first : res[(size_t)i - 2];
+        RFX_TRY(rd_union_packed(ctx, sht, cur, prm, uni));
+        if (i == 1) first = DynDev();                                   // (consumed: the union holds what the pair needs of it)
+        else RFX_TRY(rr_keep_length(ctx, res[(size_t)i - 2], klist[i - 2]));   // (what is left of it is Count_<k>_reduced alone)
+        const int64_t n_cur = cur.n;
+        cur = DynDev();
+        const double t2 = rr_now_ms();
+        RFX_TRY(rd_run_set(ctx, uni, p.P, prm, res[(size_t)i - 1]));
+        if (trace) fprintf(stderr, "reduce_reads: k %d E %d: count + sort %.1f ms, %lld records; union %.1f ms; reduction of (%d, %d) %.1f ms, %lld records\n", k,
+                           kp.min_error_cov, t1 - t0, (long long)n_cur, t2 - t1, klist[i - 1], k, rr_now_ms() - t2, (long long)res[(size_t)i - 1].n);
+    }
+    for (int i = 0; i < n_k; i++) sets[(size_t)i] = &res[(size_t)std::min(i, n_k - 2)];
+    return RFX_OK;
+}
 }  // namespace
 
 extern "C" {
+
+void rfx_reduce_reads_default_params(rfx_reduce_reads_params *p) try {
+    if (!p) return;
+    p->min_cov = 2; p->max_cov = 10000000; p->min_error_cov = 8; p->min_repeat_fold = 1.5; p->bubble = 1; p->sensitive = 0;
+    p->front_clip = 0; p->end_clip = 0; p->P = 8;
+} RFX_API_CATCH_VOID(nullptr)
+
+int rfx_dev_reduce_reads(rfx_ctx *ctx, const uint64_t *d_words, const uint32_t *d_read_len, int64_t n_reads, int words_per_read, int max_read_len,
+                         const int *klist, int n_k, const rfx_reduce_reads_params *params, rfx_dyn_packed *d_out, int64_t *out_n_per_k) try {
+    if (!ctx || !dyn_packed_out_ok(d_out) || !out_n_per_k) return RFX_E_ARG;
+    RFX_TRY(rr_args(ctx, d_words, d_read_len, n_reads, words_per_read, max_read_len, klist, n_k, params));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev a;
+    std::vector<int64_t> per_k((size_t)n_k, 0);
+    if (n_reads == 0) RFX_TRY(dyn_empty(ctx, a));
+    else {
+        std::vector<DynDev> res((size_t)n_k - 1);
+        std::vector<const DynDev *> sets((size_t)n_k);
+        RFX_TRY(rr_pairs(ctx, d_words, d_read_len, n_reads, words_per_read, max_read_len, klist, n_k, *params, res, sets));
+        RFX_TRY(ks_kmers_to_records(ctx, sets.data(), klist, n_k, a, per_k.data()));
+        RFX_TRY(sync_checked(ctx));                                     // (the sets go back to the pool here: their last reader is behind us)
+    }
+    RFX_TRY(dyn_store(ctx, a, d_out));                                  // (RFX_E_CAP: n and need_words set, nothing written)
+    for (int i = 0; i < n_k; i++) out_n_per_k[i] = per_k[(size_t)i];
+    return RFX_OK;
+} RFX_API_CATCH(ctx)
+
+// host form: ASCII reads in, the rows of every Count_<k>_reduced out in list order; one upload, one encode, one copy back
+int rfx_reduce_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_off, int64_t n_reads, const int *klist, int n_k,
+                     const rfx_reduce_reads_params *params, char *out, int64_t cap, int64_t *out_len, int64_t *out_off) try {
+    if (!ctx || !text_rows_ok((const char *)bases, read_off, n_reads) || !text_out_ok(out, cap, out_len) || !out_off) return RFX_E_ARG;
+    if (n_reads >= ((int64_t)1 << 31)) { ctx->last_error = "reduction from reads: 2^31 reads or more"; return RFX_E_LIMIT; }
+    int64_t longest = 1;
+    for (int64_t i = 0; i < n_reads; i++) {
+        if (read_off[i + 1] < read_off[i]) return RFX_E_ARG;
+        longest = std::max(longest, read_off[i + 1] - read_off[i]);
+    }
+    if (longest > 32 * (int64_t)30000) { ctx->last_error = "reduction from reads: a read of more than 960000 bases"; return RFX_E_LIMIT; }
+    const int wpr = (int)((longest + 31) >> 5);
+    // (a device pointer is not needed to check the arguments: any non-null stands in for the read store)
+    const uint64_t *probe_w = (const uint64_t *)read_off;
+    RFX_TRY(rr_args(ctx, probe_w, (const uint32_t *)read_off, n_reads, wpr, (int)longest, klist, n_k, params));
+    RFX_HIP(hipSetDevice(ctx->device));
+    std::vector<int64_t> offs((size_t)n_k + 1, 0);
+    std::vector<DevBuf> text((size_t)n_k);
+    if (n_reads > 0) {
+        DevBuf d_b, d_ro, d_words, d_len;
+        RFX_TRY(dyn_upload_text(ctx, (const char *)bases, read_off, n_reads, d_b, d_ro));
+        RFX_ALLOC(d_words, uint64_t, n_reads * wpr); RFX_ALLOC(d_len, uint32_t, n_reads);
+        RFX_TRY(encode_reads(ctx, d_b.as<uint8_t>(), d_ro.as<int64_t>(), n_reads, wpr, d_words.as<uint64_t>(), d_len.as<uint32_t>()));
+        d_b.release(); d_ro.release();
+        std::vector<DynDev> res((size_t)n_k - 1);
+        std::vector<const DynDev *> sets((size_t)n_k);
+        RFX_TRY(rr_pairs(ctx, d_words.as<uint64_t>(), d_len.as<uint32_t>(), n_reads, wpr, (int)longest, klist, n_k, *params, res, sets));
+        for (int i = 0; i < n_k; i++) {
+            int64_t total = 0, rows = 0;
+            RFX_TRY(ks_set_to_text(ctx, *sets[(size_t)i], klist[i], nullptr, 0, &total, nullptr, &rows, &text[(size_t)i]));
+            offs[(size_t)i + 1] = offs[(size_t)i] + total;
+        }
+    }
+    *out_len = offs[(size_t)n_k];
+    for (int i = 0; i <= n_k; i++) out_off[i] = offs[(size_t)i];
+    if (*out_len > cap) return RFX_E_CAP;                                 // (rfx_reduce_text's rule: the lengths set, nothing written)
+    for (int i = 0; i < n_k; i++) {
+        const int64_t len = offs[(size_t)i + 1] - offs[(size_t)i];
+        if (len > 0) RFX_HIP(hipMemcpyAsync(out + offs[(size_t)i], text[(size_t)i].p, (size_t)len, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return sync_checked(ctx);
+} RFX_API_CATCH(ctx)
 
 void rfx_reduce_default_params(rfx_reduce_params *p, int k1, int k2) try {
     if (!p) return;
@@ -585,6 +823,33 @@ int rfx_dev_reduce_run(rfx_ctx *ctx, const char *d_text_short, const int64_t *d_
     DynDev a;
     RFX_TRY(rd_run(ctx, d_text_short, d_row_off_short, n_short, d_text_long, d_row_off_long, n_long, P, prm, a));
     return dyn_store(ctx, a, d_out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_reduce_union_packed(rfx_ctx *ctx, const rfx_dyn_packed *d_short, const rfx_dyn_packed *d_long, const rfx_reduce_params *params,
+                                rfx_dyn_packed *d_out) try {
+    if (!ctx || !dyn_packed_ok(d_short) || !dyn_packed_ok(d_long) || !dyn_packed_out_ok(d_out)) return RFX_E_ARG;
+    RdParams prm;
+    RFX_TRY(rd_params(ctx, params, &prm));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev s, l, a;
+    RFX_TRY(dyn_borrow(ctx, d_short, s));
+    RFX_TRY(dyn_borrow(ctx, d_long, l));
+    RFX_TRY(rd_union_packed(ctx, s, l, prm, a));
+    return dyn_store(ctx, a, d_out);
+} RFX_API_CATCH(ctx)
+
+int rfx_dev_reduce_run_packed(rfx_ctx *ctx, const rfx_dyn_packed *d_short, const rfx_dyn_packed *d_long, int P, const rfx_reduce_params *params,
+                              rfx_dyn_packed *d_out) try {
+    if (!ctx || !dyn_packed_ok(d_short) || !dyn_packed_ok(d_long) || !dyn_packed_out_ok(d_out) || !parts_ok(P)) return RFX_E_ARG;
+    RdParams prm;
+    RFX_TRY(rd_params(ctx, params, &prm));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev s, l, a, b;
+    RFX_TRY(dyn_borrow(ctx, d_short, s));
+    RFX_TRY(dyn_borrow(ctx, d_long, l));
+    RFX_TRY(rd_union_packed(ctx, s, l, prm, a));
+    RFX_TRY(rd_run_set(ctx, a, P, prm, b));
+    return dyn_store(ctx, b, d_out);
 } RFX_API_CATCH(ctx)
 
 // two host texts in, two host texts out; everything between packed and in HBM: upload, run, to-text twice, one copy back each
