@@ -1,7 +1,12 @@
 """Reduce from reads in one resident call (rfx_dev_reduce_reads).  The expected set is always built by a Python
 helper that chains the entry points that existed before it, with text between them: count_reads_ragged[_w]_dev, the rows printed from
 the downloaded keys, mercy_text when sensitive, ksort_text, reduce_text pair by pair, dyn_binarize_dev form 0 over the concatenated
-Count_<k>_reduced texts -- and the E rule applied per k in Python.  Sets are compared array by array, whole words."""
+Count_<k>_reduced texts -- and the E rule applied per k in Python.  Sets are compared array by array, whole words.
+
+That expected set comes from the library itself, so this file holds the driver to its own stages and the contracts of the call
+(capacities, refused arguments, the command against its older modes).  What holds the call to something independent -- the composed string
+models from the reads to the rows, on reads where a later k's E reaches the output and where the counter's second count runs -- is
+tests/test_gpu_reduce_reads_model.py."""
 import ctypes as C
 import gzip
 import os
@@ -158,9 +163,10 @@ def test_synthetic_reads_through_every_branch_of_the_e_rule(rfx, synthetic, klis
 def test_the_e_rule_changes_the_result(rfx, synthetic):
     """the list (81, 95) lies past 61, E = 6 from its first k on: the helper's chain with E fixed at 8 must give a DIFFERENT set, or
     the input is too weak to show that the rule is applied.  (The string models say the same of these reads: the planted fork's two
-    95-mers end `1|98|-1` / `1|-1|98` under E = 6 and `1|-1|-1` under E = 8.  Behind a third, shorter k the reduction rewrites those
-    markers either way, so the lists that start below 61 do not show it: for a LATER k the rule is held only by the equality with
-    the chain in the tests above, and on these reads a driver that ignored it there would not be caught.)"""
+    95-mers end `1|98|-1` / `1|-1|98` under E = 6 and `1|-1|-1` under E = 8.  Behind a shorter k the reduction forces those markers to
+    -1 either way, because this fork is an error at the short k too (7 <= 8), so on THESE reads the lists that start below 61 do not
+    show a later k's E.  The `forked` reads of tests/reduce_reads_model.py do: tests/test_reduce_reads_model.py asserts which list
+    separates which wrong rule, and tests/test_gpu_reduce_reads_model.py holds the driver to the model's texts on those lists.)"""
     klist = (81, 95)
     prm = rfx.reduce_reads_params(P=8)
     ruled, n_ruled, _, _ = chain(rfx, synthetic, klist, prm)
