@@ -340,14 +340,24 @@ def ksort_rows(k):
     return [rows[i] for i in rng.permutation(len(rows))]
 
 
+_ksort_cache = {}
+
+
+def ksort_model_run(k):
+    """ksort_rows(k) through ksort_model.run_stages with the default parameters, once per process and k"""
+    if k not in _ksort_cache:
+        rows, p = ksort_rows(k), K.default_params(k)
+        _ksort_cache[k] = dict(rows=rows, p=p, st=K.run_stages(rows, p))
+    return _ksort_cache[k]
+
+
 @pytest.mark.parametrize("k", [31, 95])
 def test_ksort_chain_on_70000_rows(rfx, k):
     """~140,000 records: the folds' aggregate scans and the chained sorts past one tile; every stage of the chain composed from the
     operators, the resident chain and its text, against the string model"""
-    rows = ksort_rows(k)
-    p = K.default_params(k)
+    run = ksort_model_run(k)
+    rows, p, want = run["rows"], run["p"], run["st"]
     assert 68_000 < len(rows) < 72_000
-    want = K.run_stages(rows, p)
     assert {2, 3, 4} <= set(Counter(rec[0] for rec in want["s5_sort"]).values())
     got = TK.chain(rfx, rows, p)
     for s in K.STAGES:
@@ -364,12 +374,18 @@ REDUCE_MIN_ROWS = 131_500
 _reduce_cache = {}
 
 
+def reduce_rows():
+    """crafted_rows of test_gpu_reduce.py with 35,000 groups -> (short rows, long rows), once per process"""
+    if "rows" not in _reduce_cache:
+        _reduce_cache["rows"] = crafted_rows(np.random.default_rng(REDUCE_SEED), *REDUCE_K, groups=REDUCE_GROUPS)
+    return _reduce_cache["rows"]
+
+
 def reduce_model_run():
-    """crafted_rows of test_gpu_reduce.py with 35,000 groups through reduce_model.run_stages, once per process"""
-    if not _reduce_cache:
-        rs, rl = crafted_rows(np.random.default_rng(REDUCE_SEED), *REDUCE_K, groups=REDUCE_GROUPS)
-        st, ps = R.run_stages(rs, rl, *REDUCE_K, REDUCE_P)
-        _reduce_cache.update(rows=(rs, rl), st=st, ps=ps)
+    """reduce_rows() through reduce_model.run_stages, once per process"""
+    if "st" not in _reduce_cache:
+        st, ps = R.run_stages(*reduce_rows(), *REDUCE_K, REDUCE_P)
+        _reduce_cache.update(st=st, ps=ps)
     return _reduce_cache
 
 
