@@ -971,6 +971,17 @@ int rfx_dev_fix_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, 
                     rfx_dyn_packed *d_out);
 int rfx_fix_text(rfx_ctx *ctx, const char *text, const int64_t *row_off, int64_t n_rows, int P, const rfx_fix_params *params, char *out, int64_t cap,
                  int64_t *out_len);
+/* The seam between the last dynamic-k iteration and this stage without the text: the result is exactly what
+ * rfx_dev_fix_run gives for the rows rfx_dev_dyn_to_text writes of d_in.  Step 1 becomes form 1's READING of the set -- of every record
+ * the key's and the extension's bases and nothing behind them, the marker through its decimal text (pk_int_as_text: nine digits of ten),
+ * left / right through theirs and then clamped to +-30000, as rfx_dev_dyn_from_kmers states it -- followed by the same length filter (a
+ * record is kept iff key + extension >= 2 max_k bases) and steps 2-9 unchanged.  Capacities as rfx_dev_fix_run's with "text bytes / 32"
+ * replaced by what the set bounds it with: cap_n >= in.n (2 (max_k - 30) + 1) and cap_words >= cap_n + in.ext_off[in.n] + 4 in.n.  A short
+ * output: RFX_E_CAP with n and need_words set and nothing written.  RFX_E_ARG, nothing written: what rfx_dev_fix_run refuses of P and
+ * params; a null pointer; a record without an extension (ext_len < 1), kept or dropped: it cannot be printed as a form-1 row; extension
+ * offsets that do not follow the extension lengths (the rfx_dyn_packed layout; checked for every record before a kernel indexes with
+ * them).  RFX_E_LIMIT: a key of more than 124 bases, kept or dropped; 2^31 records or more.  in.n = 0 is valid. */
+int rfx_dev_fix_run_packed(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int P, const rfx_fix_params *params, rfx_dyn_packed *d_out);
 
 /* The SECOND contig fixing stage (Assembly_intermediate/05FixingAgain and 06ContigEnds) on the same packed sets in
  * HBM: P/ReflexivDSDynamicKmerFixingRoundTwo.java `assemblyFromKmer` (:138-263).  Its input is the text of 04Fixing -- or the packed set
@@ -1183,6 +1194,16 @@ int rfx_dev_map_to_text(rfx_ctx *ctx, const rfx_contigs_packed *d_contigs, const
                         int64_t *d_row_off, int64_t cap_rows);
 int rfx_map_text(rfx_ctx *ctx, const char *contig_text, const int64_t *contig_off, int64_t n_contigs, const uint8_t *bases, const int64_t *read_off,
                  int64_t n_reads, const rfx_map_params *params, char *out, int64_t cap, int64_t *out_len);
+/* The seam between this stage and the end extension (rfx_dev_endext_consensus above) without the row text: the result is exactly what rfx_dev_endext_consensus gives on the rows rfx_dev_map_to_text writes for the same contigs, reads
+ * (d_words, d_read_len, words_per_read) and hits.  What a hit adds follows from (read, end, strand, offset, v), the seed, the read's and
+ * the contig's length (reflexiv_amd/csrc/rfx_endext_hits.h restates the row and what the row parser reads out of it); the bases come out of
+ * the 2-bit read store, strand 1 as the reverse complement.  flags stay 0: the mapper writes no repeat-marker rows.  Capacities as
+ * rfx_dev_endext_consensus; a short output: RFX_E_CAP with need_n / need_words set and nothing written.  RFX_E_ARG, nothing written: what
+ * rfx_dev_map_to_text refuses -- a null pointer, words_per_read < 1, n above cap_n, a seed outside 11..31 where there are hits, a hit that
+ * rfx_dev_map_ends cannot have written for these contigs and reads (every hit is checked before anything indexes with it, except that a
+ * read index cannot be checked against n_reads, which the call does not take).  RFX_E_LIMIT: 2^31 hits or contigs. */
+int rfx_dev_endext_consensus_hits(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, const uint64_t *d_words,
+                                  const uint32_t *d_read_len, int words_per_read, const rfx_map_hits *hits, rfx_endext_consensus *d_out);
 
 /* THE MERCY K-MER STAGE (Count_<k>_mercy) on the 2-bit read store in HBM: P/ReflexivDSDynamicMercyKmer.java
  * `assemblyFromKmer` (:157-322), which the reference runs behind the counter for every k <= 31 in -sensitive mode.  It replaces
@@ -1221,6 +1242,73 @@ int rfx_dev_mercy_kmers(rfx_ctx *ctx, const uint64_t *d_solid_keys, int64_t n_so
 int rfx_dev_mercy_to_text(rfx_ctx *ctx, const uint64_t *d_keys, int64_t n, int k, char *d_text, int64_t cap, int64_t *out_len, int64_t *d_row_off);
 int rfx_mercy_text(rfx_ctx *ctx, const char *count_text, const int64_t *count_row_off, int64_t n_rows, const uint8_t *bases, const int64_t *read_off,
                    int64_t n_reads, int k, int front_clip, int end_clip, char *out, int64_t cap, int64_t *out_len);
+
+/* READS TO CONTIGS with the dynamic-k ("meta") assembler in ONE resident call: `reflexiv reduce` + `reflexiv meta`,
+ * i.e. the orchestrator Pipelines.reflexivDSDynamicAssemblyStepsPipe (Pipelines.java:840-1291) over the stages above.  The sets between
+ * the stages are the library's own and stay in HBM; no text is made between two stages (the two seams that went through text are
+ * rfx_dev_fix_run_packed and rfx_dev_endext_consensus_hits); nothing goes to the caller's arrays but the final set; at most one stage's
+ * input, output and scratch are live beside the read store.
+ * STAGES, in order (the values of stop_after): 00firstFour (the random reflection and 4 passes); the EIGHT iteration jobs 5-9, 10-14,
+ * 15-19 (:886), 21-30, 31-40, 41-50, 51-60, 61-70 (:925) -- there is no iteration 20 --, each an rfx_dev_dyn_run with ITS OWN
+ * start_iteration, which a pass reads: only the job 61-70 drops the shorter forward records; between two jobs the set is read as the
+ * file between them would be (marker, left, right through their decimal text, left / right clamped to +-30000); 04Fixing
+ * (rfx_dev_fix_run_packed); 05FixingAgain and 06ContigEnds (rfx_dev_fix2_run, rfx_dev_fix2_contigs); the end mapping on the read store
+ * (rfx_dev_map_ends); 07EndExtend (rfx_dev_endext_consensus_hits, rfx_dev_endext_contigs); 08Extend (rfx_dev_ext_run); 09ExtendAgain
+ * (rfx_dev_fix2_run, rfx_dev_fix2_contigs); Assembly (rfx_dev_dedup_contigs).
+ * THE PARTITION RULE (Pipelines.java:877-883, 914-921, 954-974, repeated ahead of every later stage) is the driver's: O = params->P, one P
+ * for `partitions` and `shufflePartition` alike, integer divisions.  First four: O.  Iterations 5-19: O >= 10 ? O * 80 / 100 : O.
+ * Iterations 21-70: O >= 10 ? O * 60 / 100 : O.  Fixing, fixing again, extend, extend again: O >= 10 ? O * 40 / 100 : O.  The reference's
+ * 20 % and 10 % tiers need O >= 100, which the stages' limit of 63 excludes.  The contig set is a function of P.
+ * STATED DEVIATIONS are those of the stages: the end mapping is this library's own and takes no P, the de-duplication takes no P, all
+ * alignment rows form one partition, no repeat-marker rows are written.  The reduction takes reduce_params->P as rfx_dev_reduce_reads does.
+ *   rfx_meta_default_params     P 8, scramble 2, max_iteration 150, min_contig 500, the mapper's 21 / 31 / 2, stop_after = Assembly
+ *   rfx_dev_meta_from_reduced   the set rfx_dev_reduce_reads leaves + the read store (as rfx_dev_map_ends takes it) + max_k (the LAST k of
+ *                               the list) -> the de-duplicated contigs as an rfx_contigs_packed
+ *   rfx_dev_meta_reads          the read store and the k list -> the same; the reduction (the body of rfx_dev_reduce_reads) first
+ *   rfx_meta_reads              host form: ASCII reads in (as rfx_reduce_reads takes them), ONE text out: the file of the stage
+ *                               stop_after names, written by that stage's existing writer -- rfx_dev_dyn_to_text's rows for 00firstFour,
+ *                               every 01Iteration*, 04Fixing and 08Extend; rfx_dev_fix2_to_text's for 05FixingAgain;
+ *                               rfx_dev_fix2_ends_text's for 06ContigEnds; rfx_dev_map_to_text's for the mapper's rows;
+ *                               rfx_dev_endext_to_text's for 07EndExtend; rfx_dev_ext2_to_text's for 09ExtendAgain;
+ *                               rfx_dev_contigs_to_text with min_contig for Assembly.  report may be null
+ * rfx_meta_report (host): n_reduced = the records the reduction leaves; n[s] = the records or contigs the stage s leaves (06ContigEnds
+ * repeats 05FixingAgain's, the mapper's entry is its rows, as `hits`); stages behind stop_after stay 0.
+ * CONTRACTS.  Every argument of every stage is checked before any work: what rfx_dev_reduce_reads refuses; P outside 1..63; max_k outside
+ * 31..124; max_iteration < -1; min_contig < 0; the mapper's parameters out of range; stop_after outside the enum, or other than
+ * RFX_META_ASSEMBLY in a device form; a null pointer: RFX_E_ARG, nothing written.  A short d_out: RFX_E_CAP with need_n / need_words
+ * set and nothing written; the sets are not kept, so the retry runs the call again.  A short text buffer: RFX_E_CAP with *out_len set
+ * and nothing written.  No reads give an empty set and empty texts.  RFX_META_TRACE (environment, set to anything) prints each stage's
+ * host time on stderr.  All run on the context's stream and return after it has drained. */
+enum {
+    RFX_META_FIRST_FOUR = 0,
+    RFX_META_ITERATION_5_9, RFX_META_ITERATION_10_14, RFX_META_ITERATION_15_19, RFX_META_ITERATION_21_30, RFX_META_ITERATION_31_40,
+    RFX_META_ITERATION_41_50, RFX_META_ITERATION_51_60, RFX_META_ITERATION_61_70,
+    RFX_META_FIXING, RFX_META_FIXING_AGAIN, RFX_META_CONTIG_ENDS, RFX_META_MAPPING, RFX_META_END_EXTEND, RFX_META_EXTEND, RFX_META_EXTEND_AGAIN,
+    RFX_META_ASSEMBLY,
+    RFX_META_STAGES
+};
+typedef struct {
+    int P;                 /* the caller's partition count O; the rule above derives every stage's                 */
+    int scramble;          /* param.scramble (2)                                                                    */
+    int max_iteration;     /* param.maximumIteration (150): the loop rounds of the fixing and extension stages      */
+    int min_contig;        /* param.minContig (500): the shortest contig the Assembly text holds                    */
+    int map_seed, map_min_overlap, map_max_mismatch;   /* rfx_map_params (21, 31, 2)                               */
+    int stop_after;        /* RFX_META_*: the stage whose file rfx_meta_reads writes (RFX_META_ASSEMBLY)            */
+} rfx_meta_params;
+typedef struct {
+    int64_t n_reduced;
+    int64_t n[RFX_META_STAGES];
+    int64_t hits;
+} rfx_meta_report;
+void rfx_meta_default_params(rfx_meta_params *p);
+int rfx_dev_meta_from_reduced(rfx_ctx *ctx, const rfx_dyn_packed *d_reduced, const uint64_t *d_words, const uint32_t *d_read_len, int64_t n_reads,
+                              int words_per_read, int max_k, const rfx_meta_params *params, rfx_meta_report *report, rfx_contigs_packed *d_out);
+int rfx_dev_meta_reads(rfx_ctx *ctx, const uint64_t *d_words, const uint32_t *d_read_len, int64_t n_reads, int words_per_read, int max_read_len,
+                       const int *klist, int n_k, const rfx_reduce_reads_params *reduce_params, const rfx_meta_params *params, rfx_meta_report *report,
+                       rfx_contigs_packed *d_out);
+int rfx_meta_reads(rfx_ctx *ctx, const uint8_t *bases, const int64_t *read_off, int64_t n_reads, const int *klist, int n_k,
+                   const rfx_reduce_reads_params *reduce_params, const rfx_meta_params *params, rfx_meta_report *report, char *out, int64_t cap,
+                   int64_t *out_len);
 
 /* Synthetic reads: integer-only counter-based generator, bit-identical to
  * oracle/reflexiv_oracle.c orc_synth_*.  Writes packed reads straight into HBM. */

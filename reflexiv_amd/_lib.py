@@ -96,6 +96,21 @@ class CMapHits(C.Structure):
                 ("cap_n", C.c_int64), ("need_n", C.c_int64), ("seed", C.c_int32)]
 
 
+META_STAGES = ("00firstFour", "01Iteration5_9", "01Iteration10_14", "01Iteration15_19", "01Iteration21_30", "01Iteration31_40", "01Iteration41_50",
+               "01Iteration51_60", "01Iteration61_70", "04Fixing", "05FixingAgain", "06ContigEnds", "Mapping", "07EndExtend", "08Extend", "09ExtendAgain",
+               "Assembly")     # RFX_META_*: the values of rfx_meta_params.stop_after, in order
+
+
+class CMetaParams(C.Structure):
+    """rfx_meta_params."""
+    _fields_ = [(n, C.c_int) for n in ("P", "scramble", "max_iteration", "min_contig", "map_seed", "map_min_overlap", "map_max_mismatch", "stop_after")]
+
+
+class CMetaReport(C.Structure):
+    """rfx_meta_report."""
+    _fields_ = [("n_reduced", C.c_int64), ("n", C.c_int64 * len(META_STAGES)), ("hits", C.c_int64)]
+
+
 class CRecords(C.Structure):
     """rfx_records."""
     _fields_ = [("n", C.c_int64), ("key", C.c_void_p), ("marker", C.c_void_p), ("ext_off", C.c_void_p),
@@ -136,17 +151,18 @@ SYMBOLS = [
     "rfx_reduce_default_params", "rfx_dev_reduce_union", "rfx_dev_reduce_left_prepare", "rfx_dev_reduce_adjust",
     "rfx_dev_reduce_right_prepare", "rfx_dev_reduce_full_kmers", "rfx_dev_reduce_neutralize", "rfx_dev_reduce_run", "rfx_reduce_text",
     "rfx_fix_default_params", "rfx_dev_fix_binarize", "rfx_dev_fix_contig_ends", "rfx_dev_fix_kmer_set", "rfx_dev_fix_fork_filter",
-    "rfx_dev_fix_reflect", "rfx_dev_fix_run", "rfx_fix_text",
+    "rfx_dev_fix_reflect", "rfx_dev_fix_run", "rfx_fix_text", "rfx_dev_fix_run_packed",
     "rfx_dev_fix2_binarize", "rfx_dev_fix2_run", "rfx_dev_fix2_contigs", "rfx_dev_fix2_to_text", "rfx_dev_fix2_ends_text", "rfx_fix2_text",
-    "rfx_dev_endext_consensus", "rfx_dev_endext_contigs", "rfx_dev_endext_to_text", "rfx_endext_text",
+    "rfx_dev_endext_consensus", "rfx_dev_endext_consensus_hits", "rfx_dev_endext_contigs", "rfx_dev_endext_to_text", "rfx_endext_text",
     "rfx_dev_ext_from_text", "rfx_dev_ext_contig_ends", "rfx_dev_ext_run", "rfx_ext_text", "rfx_dev_ext2_to_text", "rfx_ext2_text",
     "rfx_map_default_params", "rfx_dev_map_ends", "rfx_dev_map_to_text", "rfx_map_text",
     "rfx_dev_mercy_kmers", "rfx_dev_mercy_to_text", "rfx_mercy_text",
+    "rfx_meta_default_params", "rfx_dev_meta_from_reduced", "rfx_dev_meta_reads", "rfx_meta_reads",
 ]
 
 # prototypes of the packed entry points (ctx, then as include/reflexiv_hip.h declares them)
 _PK, _HR, _CP, _KP, _RP, _FP, _I, _L, _P = "PK", "HR", "CP", "KP", "RP", "FP", C.c_int, C.c_int64, C.c_void_p
-_EC, _ES, _MP, _MH, _RR = "EC", "ES", "MP", "MH", "RR"
+_EC, _ES, _MP, _MH, _RR, _MT, _MR = "EC", "ES", "MP", "MH", "RR", "MT", "MR"
 _DYN_PACKED_ARGS = {
     "rfx_dev_dyn_pack": (_HR, _PK),
     "rfx_dev_dyn_unpack": (_PK, _HR),
@@ -191,6 +207,7 @@ _DYN_PACKED_ARGS = {
     "rfx_dev_fix_reflect": (_PK, _PK),
     "rfx_dev_fix_run": (_P, _P, _L, _I, _FP, _PK),
     "rfx_fix_text": (_P, _P, _L, _I, _FP, _P, _L, _P),
+    "rfx_dev_fix_run_packed": (_PK, _I, _FP, _PK),
     # the second contig fixing stage: packed sets in, a packed contig set and the two texts out
     "rfx_dev_fix2_binarize": (_P, _P, _L, _PK),
     "rfx_dev_fix2_run": (_PK, _I, _FP, _PK),
@@ -200,6 +217,7 @@ _DYN_PACKED_ARGS = {
     "rfx_fix2_text": (_P, _P, _L, _I, _FP, _P, _L, _P, _P, _L, _P),
     # the end extension from alignment rows: a packed contig set and rows in, consensus sets, the spliced set and its text out
     "rfx_dev_endext_consensus": (_CP, _P, _P, _P, _P, _L, _EC),
+    "rfx_dev_endext_consensus_hits": (_CP, _P, _P, _P, _P, _I, _MH, _EC),
     "rfx_dev_endext_contigs": (_CP, _P, _P, _EC, _I, _ES),
     "rfx_dev_endext_to_text": (_ES, _P, _L, _P),
     "rfx_endext_text": (_P, _P, _L, _P, _P, _L, _I, _P, _L, _P),
@@ -218,6 +236,10 @@ _DYN_PACKED_ARGS = {
     "rfx_dev_mercy_kmers": (_P, _L, _P, _P, _L, _I, _I, _I, _I, _P, _L, _P),
     "rfx_dev_mercy_to_text": (_P, _L, _I, _P, _L, _P, _P),
     "rfx_mercy_text": (_P, _P, _L, _P, _P, _L, _I, _I, _I, _P, _L, _P),
+    # reads to contigs in one resident call: the read store (or ASCII reads) and the k list in, the contig set (or one stage's text) out
+    "rfx_dev_meta_from_reduced": (_PK, _P, _P, _L, _I, _I, _MT, _MR, _CP),
+    "rfx_dev_meta_reads": (_P, _P, _L, _I, _I, _P, _I, _RR, _MT, _MR, _CP),
+    "rfx_meta_reads": (_P, _P, _L, _P, _I, _RR, _MT, _MR, _P, _L, _P),
     # the packed contig set of the de-duplication (rfx_contigs_packed)
     "rfx_dev_contigs_pack": (_P, _P, _L, _CP),
     "rfx_dev_contigs_unpack": (_CP, _P, _L, _P, _L, _P),
@@ -274,7 +296,8 @@ def lib():
                                               C.POINTER(CContigsPacked) if a == _CP else C.POINTER(CKsortParams) if a == _KP else C.POINTER(CReduceParams) if a == _RP else
                                               C.POINTER(CFixParams) if a == _FP else C.POINTER(CEndextConsensus) if a == _EC else
                                               C.POINTER(CEndextSet) if a == _ES else C.POINTER(CMapParams) if a == _MP else
-                                              C.POINTER(CMapHits) if a == _MH else C.POINTER(CReduceReadsParams) if a == _RR else a for a in _DYN_PACKED_ARGS[name]]
+                                              C.POINTER(CMapHits) if a == _MH else C.POINTER(CReduceReadsParams) if a == _RR else
+                                              C.POINTER(CMetaParams) if a == _MT else C.POINTER(CMetaReport) if a == _MR else a for a in _DYN_PACKED_ARGS[name]]
                 continue
             if name == "rfx_dyn_attribute_unpack":
                 fn.restype = None
@@ -294,6 +317,10 @@ def lib():
             if name == "rfx_reduce_reads_default_params":
                 fn.restype = None
                 fn.argtypes = [C.POINTER(CReduceReadsParams)]
+                continue
+            if name == "rfx_meta_default_params":
+                fn.restype = None
+                fn.argtypes = [C.POINTER(CMetaParams)]
                 continue
             if name == "rfx_map_default_params":
                 fn.restype = None

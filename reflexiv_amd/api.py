@@ -1312,6 +1312,65 @@ class Reflexiv:
             offs.ctypes.data))
         return [text[int(a):int(b)] for a, b in zip(offs[:-1], offs[1:])]
 
+    # ---- reads to contigs in one resident call (rfx_dev_meta_*, rfx_meta_reads)
+    def meta_params(self, **kw) -> "_lib.CMetaParams":
+        """rfx_meta_default_params (P 8, scramble 2, max_iteration 150, min_contig 500, the mapper's 21 / 31 / 2, stop_after Assembly),
+        then **kw; stop_after may be a name of _lib.META_STAGES"""
+        if isinstance(kw.get("stop_after"), str):
+            kw["stop_after"] = _lib.META_STAGES.index(kw["stop_after"])
+        return self._params(_lib.CMetaParams, self.L.rfx_meta_default_params, "rfx_meta_params", **kw)
+
+    @staticmethod
+    def _meta_report(rep) -> dict:
+        out = {name: int(rep.n[i]) for i, name in enumerate(_lib.META_STAGES)}
+        out["reduced"], out["hits"] = int(rep.n_reduced), int(rep.hits)
+        return out
+
+    def meta_from_reduced_dev(self, reduced: "DynPacked", d_words, d_read_len, n_reads: int, words_per_read: int, max_k: int, params=None,
+                              out: "ContigsPacked" = None):
+        """rfx_dev_meta_from_reduced: the set reduce_reads_dev leaves and the read store -> (the de-duplicated contigs as a ContigsPacked,
+        the report as a dict: stage name -> records or contigs left, "reduced", "hits").  A set that turns out too small is regrown and
+        the call made again."""
+        params = params or self.meta_params()
+        ci, rep = reduced._c(), _lib.CMetaReport()
+        out = self._grow_call(self.L.rfx_dev_meta_from_reduced, "rfx_dev_meta_from_reduced", out or ContigsPacked(1 << 12, 1 << 16, reduced.key.device), lambda co: (
+            C.byref(ci), d_words.data_ptr() if d_words is not None else None, d_read_len.data_ptr() if d_read_len is not None else None, int(n_reads),
+            int(words_per_read), int(max_k), C.byref(params), C.byref(rep), C.byref(co)), reduced.key.device)
+        return out, self._meta_report(rep)
+
+    def meta_reads_dev(self, d_words, d_read_len, n_reads: int, words_per_read: int, max_read_len: int, klist, reduce_params=None, params=None,
+                       out: "ContigsPacked" = None):
+        """rfx_dev_meta_reads: the 2-bit read store in HBM and a k list -> (the de-duplicated contigs, the report)"""
+        klist = [int(k) for k in klist]
+        reduce_params, params = reduce_params or self.reduce_reads_params(), params or self.meta_params()
+        ks = (C.c_int * max(len(klist), 1))(*klist)
+        rep = _lib.CMetaReport()
+        out = self._grow_call(self.L.rfx_dev_meta_reads, "rfx_dev_meta_reads", out or ContigsPacked(1 << 12, 1 << 16), lambda co: (
+            d_words.data_ptr() if d_words is not None else None, d_read_len.data_ptr() if d_read_len is not None else None, int(n_reads),
+            int(words_per_read), int(max_read_len), C.addressof(ks), len(klist), C.byref(reduce_params), C.byref(params), C.byref(rep), C.byref(co)))
+        return out, self._meta_report(rep)
+
+    def meta_reads_text(self, reads, klist, reduce_params=None, params=None, with_report=False):
+        """rfx_meta_reads: the reads -- a list of bytes, or (the bases as one numpy uint8 array, the n + 1 int64 offsets) -- and a k list ->
+        the file of the stage params.stop_after names, as bytes (and the report); one upload, everything between in HBM"""
+        klist = [int(k) for k in klist]
+        reduce_params, params = reduce_params or self.reduce_reads_params(), params or self.meta_params()
+        if isinstance(reads, tuple):
+            bases, off = np.ascontiguousarray(reads[0], np.uint8), np.ascontiguousarray(reads[1], np.int64)
+        else:
+            reads = [bytes(r) for r in reads]
+            bases = np.frombuffer(b"".join(reads), np.uint8) if reads else np.zeros(0, np.uint8)
+            off = np.zeros(len(reads) + 1, np.int64)
+            off[1:] = np.cumsum([len(r) for r in reads])
+        n = len(off) - 1
+        bases = bases if len(bases) else np.zeros(1, np.uint8)
+        ks = (C.c_int * max(len(klist), 1))(*klist)
+        rep = _lib.CMetaReport()
+        text, = self._host_text_call("rfx_meta_reads", [max(1 << 16, 2 * len(bases))], lambda o, c, ln: self.L.rfx_meta_reads(
+            self.ctx, bases.ctypes.data, off.ctypes.data, n, C.addressof(ks), len(klist), C.byref(reduce_params), C.byref(params), C.byref(rep),
+            o[0].ctypes.data, c[0], C.addressof(ln[0])))
+        return (text, self._meta_report(rep)) if with_report else text
+
     @staticmethod
     def _row_offsets(text: bytes):
         buf = np.frombuffer(text, np.uint8)
@@ -1397,6 +1456,14 @@ class Reflexiv:
         return self._grow_call(self.L.rfx_dev_fix_run, "rfx_dev_fix_run", out or DynPacked(cap_n, cap_n + int(d_text.numel()) // 32),
                                   lambda co: (d_text.data_ptr(), d_row_off.data_ptr(), n_rows, int(P), C.byref(params), C.byref(co)))
 
+    def fix_run_packed(self, d: "DynPacked", P: int, params, out: "DynPacked" = None) -> "DynPacked":
+        """rfx_dev_fix_run_packed: fix_run on the rows dyn_to_text_dev would write of `d`, with no text made -- the last iteration's
+        set feeds it as it is"""
+        ci = d._c()
+        cap_n = d.n * (2 * (int(params.max_k) - 30) + 1)
+        return self._grow_call(self.L.rfx_dev_fix_run_packed, "rfx_dev_fix_run_packed", out or DynPacked(cap_n, cap_n + d.words + 4 * d.n),
+                                  lambda co: (C.byref(ci), int(P), C.byref(params), C.byref(co)))
+
     def fix_text(self, text: bytes, P: int, params) -> bytes:
         """rfx_fix_text: the rows of the last iteration's output (bytes, one `SUBKMER,m|l|r,EXTENSION` row per line) -> the rows of
         04Fixing"""
@@ -1472,6 +1539,15 @@ class Reflexiv:
         return self._grow_call(self.L.rfx_dev_endext_consensus, "rfx_dev_endext_consensus", out or EndextConsensus(c.n, device=c.word_off.device),
                                lambda co: (C.byref(ci), d_left.data_ptr(), d_right.data_ptr(), d_text.data_ptr(), d_row_off.data_ptr(), n_rows, C.byref(co)),
                                c.word_off.device)
+
+    def endext_consensus_hits(self, c: "ContigsPacked", d_left, d_right, d_words, d_read_len, words_per_read: int, hits: "MapHits",
+                              out: "EndextConsensus" = None) -> "EndextConsensus":
+        """rfx_dev_endext_consensus_hits: endext_consensus on the rows map_to_text would write for these contigs, reads and hits, with no
+        text made"""
+        ci, ch = c._c(), hits._c()
+        return self._grow_call(self.L.rfx_dev_endext_consensus_hits, "rfx_dev_endext_consensus_hits", out or EndextConsensus(c.n, device=c.word_off.device),
+                               lambda co: (C.byref(ci), d_left.data_ptr(), d_right.data_ptr(), d_words.data_ptr(), d_read_len.data_ptr(), int(words_per_read),
+                                           C.byref(ch), C.byref(co)), c.word_off.device)
 
     def endext_contigs(self, c: "ContigsPacked", d_left, d_right, cons: "EndextConsensus", max_k: int, out: "EndextSet" = None) -> "EndextSet":
         """rfx_dev_endext_contigs: the splice and the order -> the contigs of 07EndExtend, in output order, with their arrays"""

@@ -41,6 +41,7 @@ struct DefaultParam {
     int startIteration = 5, endIteration = 9;  // -start / -end of `iteration` (U/DefaultParam.java:118-119)
     bool dedup = false;                      // --dedup: the contig text through rfx_dedup_contig_text (ReflexivDSDynamicKmerDedup)
     int gpus = 1;                            // --gpus N (with --resident): one host thread + context + RCCL communicator per GPU
+    bool intermediate = false;               // -intermediate (`meta`): every file of Assembly_intermediate/ too
 
     void setKmerSize(int k) { kmerSize = k; subKmerSize = k - 1; }   // Parameter.java:345-360
 };
@@ -79,6 +80,7 @@ inline DefaultParam importCommandLine(const std::vector<std::string> &args) {
         else if (a == "-partitionredu") p.shufflePartition = std::stoi(need(i++));
         else if (a == "-bubble") p.bubble = false;
         else if (a == "-sensitive") p.sensitive = true;
+        else if (a == "-intermediate") p.intermediate = true;
         else if (a == "--logical-partitions") p.logicalPartitions = std::stoi(need(i++));
         else if (a == "--twin") p.twin = need(i++) == "ds" ? 0 : 1;
         else if (a == "--resident") p.resident = true;

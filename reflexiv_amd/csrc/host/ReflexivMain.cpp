@@ -457,6 +457,63 @@ std::vector<std::string> ReflexivMain::kmerReductionFromReads(const std::string 
     return texts;
 }
 
+std::string ReflexivMain::metaAssemblyFromReads(const std::string &fastqText, const std::vector<int> &klist, int partitions, int stopAfter) {
+    std::vector<uint8_t> bases; std::vector<int64_t> readOff;
+    DSFastqFilterOnlySeq{*this}.call(fastqText, bases, readOff);      // as counter()
+    const int64_t nr = (int64_t)readOff.size() - 1;
+    rfx_reduce_reads_params rp;
+    rfx_reduce_reads_default_params(&rp);
+    rp.min_cov = param.minKmerCoverage; rp.max_cov = param.maxKmerCoverage; rp.min_error_cov = param.minErrorCoverage;
+    rp.min_repeat_fold = param.minRepeatFold; rp.bubble = param.bubble ? 1 : 0; rp.sensitive = param.sensitive ? 1 : 0;
+    rp.front_clip = param.frontClip; rp.end_clip = param.endClip; rp.P = partitions;
+    rfx_meta_params mp;
+    rfx_meta_default_params(&mp);
+    mp.P = partitions; mp.scramble = param.scramble; mp.max_iteration = param.maximumIteration; mp.min_contig = param.minContig;
+    mp.stop_after = stopAfter;
+    if (bases.empty()) bases.push_back(0);
+    std::string out(std::max<size_t>(2 * bases.size(), 1 << 16), '\0');
+    int64_t len = 0;
+    for (;;) {
+        const int st = rfx_meta_reads(ctx, bases.data(), readOff.data(), nr, klist.data(), (int)klist.size(), &rp, &mp, nullptr, out.data(), (int64_t)out.size(),
+                                      &len);
+        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
+        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_meta_reads: ") + rfx_last_error(ctx));
+        break;
+    }
+    out.resize((size_t)len);
+    return out;
+}
+
+std::string ReflexivMain::dedupContigRows(const std::string &csvText) {
+    std::string rows;
+    std::vector<int64_t> off;
+    rowsOf(csvText, rows, off);
+    const int64_t n = (int64_t)off.size() - 1;
+    std::vector<uint8_t> bases;
+    std::vector<int64_t> coff(1, 0);
+    for (int64_t i = 0; i < n; i++) {
+        const std::string row = rows.substr((size_t)off[(size_t)i], (size_t)(off[(size_t)i + 1] - off[(size_t)i]));
+        const size_t c = row.find(',');
+        if (c == std::string::npos || row.compare(0, 8, ">Contig-") != 0) throw std::runtime_error("dedup row: " + row);
+        size_t e = row.size();
+        while (e > c + 1 && (row[e - 1] == '\n' || row[e - 1] == '\r')) e--;
+        bases.insert(bases.end(), row.begin() + (long)c + 1, row.begin() + (long)e);
+        coff.push_back((int64_t)bases.size());
+    }
+    if (bases.empty()) bases.push_back(0);
+    std::string out(2 * bases.size() + 64 * (size_t)(n + 2) + 4096, '\0');
+    int64_t len = 0;
+    for (;;) {
+        const int st = rfx_dedup_contigs(ctx, bases.data(), coff.data(), n, param.minContig, nullptr, 0, nullptr, 0, nullptr, out.data(), (int64_t)out.size(), &len,
+                                         nullptr);
+        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
+        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_dedup_contigs: ") + rfx_last_error(ctx));
+        break;
+    }
+    out.resize((size_t)len);
+    return out;
+}
+
 // the host forms that take rows and rfx_fix_params and give one text (rfx_fix_text, rfx_ext_text, rfx_ext2_text): the call, again with the
 // length it reported where the buffer was short.  min_commas: what a row must hold to be one of the stage's; stage: the word that a
 // refused row's message begins with

@@ -199,6 +199,15 @@ public:
     // ReflexivDSDynamicKmerExtendRoundTwo.assemblyFromKmer (P/ReflexivDSDynamicKmerExtendRoundTwo.java:125-221) -- `extend2`: the rows of
     // 08Extend -> the rows ">Contig-<len>-<idx>,<contig>" of Assembly_intermediate/09ExtendAgain.  One call (rfx_ext2_text).
     std::string contigExtendAgain(const std::string &csvText, int partitions);
+    // Pipelines.reflexivDSDynamicReductionPipe + Pipelines.reflexivDSDynamicAssemblyStepsPipe (P/Pipelines.java:1315-1737, :840-1291) --
+    // `meta -fastq F -klist K1,K2,... -partition P`: the FASTQ text -> the file of ONE stage of the run from reads to contigs, stopAfter
+    // = RFX_META_* (RFX_META_ASSEMBLY: the de-duplicated contigs of at least -mincontig bases).  One call (rfx_meta_reads): one upload
+    // and one 2-bit encode of the reads, every stage on the device with no text between them, the partition rule the driver's.
+    std::string metaAssemblyFromReads(const std::string &fastqText, const std::vector<int> &klist, int partitions, int stopAfter);
+    // ReflexivDSDynamicKmerDedup.assemblyFromKmer (P/ReflexivDSDynamicKmerDedup.java:138-339) -- `dedup`: the rows
+    // ">Contig-<len>-<idx>,<contig>" of 09ExtendAgain -> the text of Assembly (contigs of at least -mincontig bases).  One call
+    // (rfx_dedup_contigs: pack, the three rounds and the text on the device).
+    std::string dedupContigRows(const std::string &csvText);
     int lastKmerOfList() const;                      // param.kmerListInt[length - 1]
 
     rfx_ctx *ctx = nullptr;

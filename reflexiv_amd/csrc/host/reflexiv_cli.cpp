@@ -12,7 +12,10 @@
 // `reflexiv_host mapping -kmerc O/Assembly_intermediate/05FixingAgain -fastq F[,F2...] [-klist ...] -outfile O [-rowsout FILE]` (the whole
 // Mapping stage: the library's own end-overhang mapper in the aligner's place, then the end extension -> 07EndExtend),
 // `reflexiv_host extend -kmerc O/Assembly_intermediate/07EndExtend [-klist ...] -partition P [-maxiter M] -outfile O` (08Extend),
-// `reflexiv_host extend2 -kmerc O/Assembly_intermediate/08Extend [-klist ...] -partition P [-maxiter M] -outfile O` (09ExtendAgain)
+// `reflexiv_host extend2 -kmerc O/Assembly_intermediate/08Extend [-klist ...] -partition P [-maxiter M] -outfile O` (09ExtendAgain),
+// `reflexiv_host meta -fastq F[,F2...] -klist K1,K2,... -partition P -outfile O [-sensitive] [-intermediate]` (reads to contigs in one
+// resident run: O/Assembly; with -intermediate every file of O/Assembly_intermediate/ under the reference's names too, one run a stage),
+// `reflexiv_host dedup -kmerc O/Assembly_intermediate/09ExtendAgain -outfile O [-mincontig N]` (the last stage alone: O/Assembly)
 // the two launcher sub-commands of bin/reflexiv:252-271 that reach the hot path
 // (M/Main.java:59-79, M/MainOfCounter.java:60-80), on one MI355X instead of spark-submit.
 #include <zlib.h>
@@ -52,7 +55,9 @@ int main(int argc, char **argv) {
                                    "       reflexiv_host endextend -kmerc FIXING_AGAIN_OUT -sam ROWS [-klist 23,31,...,95] -outfile DIR\n"
                                    "       reflexiv_host mapping -kmerc FIXING_AGAIN_OUT -fastq F[,F2...] [-klist 23,31,...,95] -outfile DIR [-rowsout FILE]\n"
                                    "       reflexiv_host extend -kmerc END_EXTEND_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"
-                                   "       reflexiv_host extend2 -kmerc EXTEND_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"; return 2; }
+                                   "       reflexiv_host extend2 -kmerc EXTEND_OUT [-klist 23,31,...,95] -partition P -outfile DIR\n"
+                                   "       reflexiv_host meta -fastq F[,F2...] -klist K1,K2,... -partition P -outfile DIR [-sensitive] [-intermediate]\n"
+                                   "       reflexiv_host dedup -kmerc EXTEND_AGAIN_OUT -outfile DIR [-mincontig N]\n"; return 2; }
         std::string cmd = argv[1];
         std::vector<std::string> args(argv + 2, argv + argc);
         reflexiv::DefaultParam param = reflexiv::importCommandLine(args);
@@ -84,6 +89,10 @@ int main(int argc, char **argv) {
             throw std::runtime_error("extend needs -kmerc END_EXTEND_OUT [-klist 23,31,...] -partition P [-maxiter M -scramble S] -outfile DIR");
         if (cmd == "extend2" && (param.inputKmerPath.empty() || param.outputPath.empty()))
             throw std::runtime_error("extend2 needs -kmerc EXTEND_OUT [-klist 23,31,...] -partition P [-maxiter M -scramble S] -outfile DIR");
+        if (cmd == "meta" && (param.inputFqPath.empty() || param.outputPath.empty()))
+            throw std::runtime_error("meta needs -fastq F[,F2...] -klist K1,K2,... -partition P -outfile DIR [-sensitive] [-intermediate]");
+        if (cmd == "dedup" && (param.inputKmerPath.empty() || param.outputPath.empty()))
+            throw std::runtime_error("dedup needs -kmerc EXTEND_AGAIN_OUT -outfile DIR [-mincontig N]");
         if (param.outputPath.empty()) throw std::runtime_error("-outfile is required");
         if (param.inputFqPath.empty() && param.inputKmerPath.empty()) throw std::runtime_error("-fastq or -kmerc is required");
         auto read_all = [&](const std::string &paths) {
@@ -240,6 +249,36 @@ int main(int argc, char **argv) {
             out = cmd == "extend" ? m.contigExtend(read_all(param.inputKmerPath), P) : m.contigExtendAgain(read_all(param.inputKmerPath), P);
             dir += "/Assembly_intermediate"; mkdir(dir.c_str(), 0755);
             dir += cmd == "extend" ? "/08Extend" : "/09ExtendAgain"; mkdir(dir.c_str(), 0755);
+        } else if (cmd == "meta") {
+            // Pipelines.reflexivDSDynamicReductionPipe + reflexivDSDynamicAssemblyStepsPipe (Pipelines.java:1315-1737, :840-1291) in one
+            // resident run; the partition rule of the later stages is the library's (rfx_meta.hip)
+            const int P = param.partitions > 0 ? param.partitions : param.logicalPartitions;
+            if (P < 1 || P > 63) throw std::runtime_error("meta: -partition must be 1..63");
+            std::vector<int> ks;
+            std::stringstream ss(param.kmerList);
+            for (std::string one; std::getline(ss, one, ',');) ks.push_back(std::stoi(one));
+            const std::string fastq = read_all(param.inputFqPath);
+            if (param.intermediate) {
+                static const char *const NAMES[RFX_META_ASSEMBLY] = {"00firstFour", "01Iteration5_9", "01Iteration10_14", "01Iteration15_19", "01Iteration21_30",
+                    "01Iteration31_40", "01Iteration41_50", "01Iteration51_60", "01Iteration61_70", "04Fixing", "05FixingAgain", "06ContigEnds", "Mapping",
+                    "07EndExtend", "08Extend", "09ExtendAgain"};
+                const std::string ai = dir + "/Assembly_intermediate";
+                mkdir(ai.c_str(), 0755);
+                for (int s = RFX_META_FIRST_FOUR; s < RFX_META_ASSEMBLY; s++) {
+                    const std::string d = ai + "/" + NAMES[s];
+                    mkdir(d.c_str(), 0755);
+                    // (06ContigEnds is a FASTA and the mapper's rows are a table: neither is a csv)
+                    std::ofstream(d + (s == RFX_META_CONTIG_ENDS ? "/part-00000" : s == RFX_META_MAPPING ? "/part-00000.tsv" : "/part-00000.csv"), std::ios::binary)
+                        << m.metaAssemblyFromReads(fastq, ks, P, s);
+                    std::ofstream(d + "/_SUCCESS", std::ios::binary);
+                }
+            }
+            out = m.metaAssemblyFromReads(fastq, ks, P, RFX_META_ASSEMBLY);
+            dir += "/Assembly"; mkdir(dir.c_str(), 0755);
+        } else if (cmd == "dedup") {
+            // Pipelines.java:1230-1290: the rows of 09ExtendAgain -> Assembly
+            out = m.dedupContigRows(read_all(param.inputKmerPath));
+            dir += "/Assembly"; mkdir(dir.c_str(), 0755);
         } else if (cmd == "counter") {
             // --resident at k = 33..100 (not 64 or 96): the same rows through the device count of the packed reads
             out = param.resident && param.kmerSize >= 33 && param.kmerSize % 32 != 0 ? m.counterResident(read_all(param.inputFqPath))

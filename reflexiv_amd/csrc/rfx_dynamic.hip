@@ -932,6 +932,10 @@ static int dyn_run(rfx_ctx *ctx, DynDev &a, int P, int random_reflection, int pa
 }
 
 }  // namespace
+// ... for the driver from reads to contigs (rfx_meta.hip): the body of rfx_dev_dyn_run on a set of the library's, replaced by the result
+int rfx::dyn_run_set(rfx_ctx *ctx, DynDev &a, int P, int random_reflection, int passes_first_four, int start_iteration, int end_iteration) {
+    return dyn_run(ctx, a, P, random_reflection, passes_first_four, start_iteration, end_iteration, nullptr, 0, nullptr);
+}
 
 extern "C" {
 

@@ -17,6 +17,7 @@
 #include <algorithm>
 #include "rfx_internal.h"
 #include "rfx_packed_words.h"
+#include "rfx_endext_hits.h"
 
 using namespace rfx;
 
@@ -29,7 +30,7 @@ namespace {
 #define EE_WAVES 4                   // waves of the pile-up's workgroup
 
 // what is wrong with a call's input (CallFlags::bad)
-enum { EE_BAD_CIGAR = 1, EE_BAD_START = 2, EE_BAD_RANGE = 4, EE_BAD_LAYOUT = 8, EE_TOO_LONG = 16, EE_BAD_ID = 32 };
+enum { EE_BAD_CIGAR = 1, EE_BAD_START = 2, EE_BAD_RANGE = 4, EE_BAD_LAYOUT = 8, EE_TOO_LONG = 16, EE_BAD_ID = 32, EE_BAD_HIT = 64 };
 
 // what a row adds: lcnt bases read DOWN from text[lsrc] to the left table from j = 0, rcnt bases read UP from text[rsrc] to the right one
 struct EeRow { int64_t lsrc, rsrc; int32_t contig, lcnt, rcnt; uint32_t rep; };
@@ -163,30 +164,10 @@ __global__ __launch_bounds__(256) void k_ee_first(const uint64_t *__restrict__ k
 }
 
 // ---- pile-up and consensus (:597-655, :883-949): one workgroup per contig ----------------------------------------------------------
-__global__ __launch_bounds__(64 * EE_WAVES) void k_ee_pile(const char *__restrict__ text, const EeRow *__restrict__ rows, const uint32_t *__restrict__ order,
-                                                           const int64_t *__restrict__ first, uint64_t *__restrict__ cons /* [n][2][EE_CW] */,
-                                                           int32_t *__restrict__ clen /* [n][2] */, int32_t *__restrict__ cflags) {
-    __shared__ uint32_t tab[2 * EE_LONGEST * 4];
-    __shared__ uint32_t rep[2], cnt[2];
-    __shared__ uint8_t best[2 * EE_LONGEST];
-    const int64_t c = blockIdx.x;
-    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    for (int t = tid; t < 2 * EE_LONGEST * 4; t += 64 * EE_WAVES) tab[t] = 0u;
-    if (tid < 2) { rep[tid] = 0u; cnt[tid] = 0u; }
-    __syncthreads();
-    const int64_t r1 = first[c + 1];
-    for (int64_t q = first[c] + wave; q < r1; q += EE_WAVES) {        // a wave per row, so any row count works
-        const EeRow r = rows[order[q]];
-        if (lane == 0 && (r.rep & 1u)) atomicAdd(&rep[0], 1u);
-        if (lane == 0 && (r.rep & 2u)) atomicAdd(&rep[1], 1u);
-        for (int t = lane; t < r.lcnt + r.rcnt; t += 64) {            // a lane per contributed base
-            const bool right = t >= r.lcnt;
-            const int j = right ? t - r.lcnt : t;
-            const char ch = right ? text[r.rsrc + j] : text[r.lsrc - j];
-            atomicAdd(&tab[((right ? EE_LONGEST : 0) + j) * 4 + ee_code(ch)], 1u);
-        }
-    }
-    __syncthreads();
+// the tail of a pile-up's workgroup, behind the barrier that ends the counting: the argmax of every position, then the two consensus
+// sequences, their lengths and the flags of contig c
+__device__ __forceinline__ void ee_pile_finish(const uint32_t *tab, const uint32_t *rep, uint32_t *cnt, uint8_t *best, int64_t c, int tid,
+                                               uint64_t *__restrict__ cons, int32_t *__restrict__ clen, int32_t *__restrict__ cflags) {
     for (int t = tid; t < 2 * EE_LONGEST; t += 64 * EE_WAVES) {       // a lane per position: the highest count, a tie to the HIGHER code
         uint32_t hi = 0u;
         int code = -1;
@@ -212,6 +193,94 @@ __global__ __launch_bounds__(64 * EE_WAVES) void k_ee_pile(const char *__restric
         clen[2 * c] = (int32_t)cnt[0]; clen[2 * c + 1] = (int32_t)cnt[1];
         cflags[c] = (rep[0] >= 2u ? 1 : 0) | (rep[1] >= 2u ? 2 : 0);
     }
+}
+__global__ __launch_bounds__(64 * EE_WAVES) void k_ee_pile(const char *__restrict__ text, const EeRow *__restrict__ rows, const uint32_t *__restrict__ order,
+                                                           const int64_t *__restrict__ first, uint64_t *__restrict__ cons /* [n][2][EE_CW] */,
+                                                           int32_t *__restrict__ clen /* [n][2] */, int32_t *__restrict__ cflags) {
+    __shared__ uint32_t tab[2 * EE_LONGEST * 4];
+    __shared__ uint32_t rep[2], cnt[2];
+    __shared__ uint8_t best[2 * EE_LONGEST];
+    const int64_t c = blockIdx.x;
+    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    for (int t = tid; t < 2 * EE_LONGEST * 4; t += 64 * EE_WAVES) tab[t] = 0u;
+    if (tid < 2) { rep[tid] = 0u; cnt[tid] = 0u; }
+    __syncthreads();
+    const int64_t r1 = first[c + 1];
+    for (int64_t q = first[c] + wave; q < r1; q += EE_WAVES) {        // a wave per row, so any row count works
+        const EeRow r = rows[order[q]];
+        if (lane == 0 && (r.rep & 1u)) atomicAdd(&rep[0], 1u);
+        if (lane == 0 && (r.rep & 2u)) atomicAdd(&rep[1], 1u);
+        for (int t = lane; t < r.lcnt + r.rcnt; t += 64) {            // a lane per contributed base
+            const bool right = t >= r.lcnt;
+            const int j = right ? t - r.lcnt : t;
+            const char ch = right ? text[r.rsrc + j] : text[r.lsrc - j];
+            atomicAdd(&tab[((right ? EE_LONGEST : 0) + j) * 4 + ee_code(ch)], 1u);
+        }
+    }
+    __syncthreads();
+    ee_pile_finish(tab, rep, cnt, best, c, tid, cons, clen, cflags);
+}
+// ---- the same pile-up from the hits of the end mapping, no row text (rfx_dev_endext_consensus_hits) ---------------------------------------
+// one thread per hit: checked as rfx_dev_map_to_text checks it (mp_row, rfx_endmap.hip) BEFORE anything indexes with it, then what
+// k_ee_parse would read out of its row (rfx_endext_hits.h).  The mapper writes no repeat-marker rows: rep stays 0
+struct EhHit { int64_t read; int32_t contig, n, strand, lsrc, lcnt, rsrc, rcnt; };
+__global__ __launch_bounds__(256) void k_eh_rows(const Fx2View c, const uint32_t *__restrict__ read_len, int wpr, const MpHits h, int64_t n_hits, int seed,
+                                                 EhHit *__restrict__ rows, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals, CallFlags *__restrict__ flags) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_hits) return;
+    const int end = h.end[q], strand = h.strand[q], off = h.off[q], v = h.v[q];
+    const int64_t read = h.read[q];
+    EhHit r{0, -1, 0, 0, 0, 0, 0, 0};
+    uint32_t bad = 0u;
+    bool ok = end >= 0 && (int64_t)end < 2 * c.n && !(strand & ~1) && read >= 0;
+    if (ok) {
+        const int64_t ci = end >> 1, L64 = c.len[ci];
+        ok = L64 >= seed && L64 < ((int64_t)1 << 30) && c.woff[ci + 1] - c.woff[ci] == ((L64 + 31) >> 5);
+        const uint32_t n32 = ok ? read_len[read] : 0u;
+        ok = ok && n32 <= 32u * (uint32_t)wpr;
+        EhRow row;
+        if (ok && eh_row(end & 1, (int)L64, (int)n32, off, v, seed, &row)) {
+            const EhAdd a = eh_add(row, (int)n32, (int)L64);
+            if (a.bad) bad = a.bad == 1 ? (uint32_t)EE_BAD_CIGAR : (uint32_t)EE_BAD_RANGE;
+            r = EhHit{read, (int32_t)ci, (int32_t)n32, strand, a.lsrc, a.lcnt, a.rsrc, a.rcnt};
+        } else {
+            ok = false;
+        }
+    }
+    if (!ok) bad = (uint32_t)EE_BAD_HIT;
+    if (bad) atomicOr(&flags->bad, bad);
+    rows[q] = r;
+    keys[q] = r.contig >= 0 ? (uint64_t)r.contig : (uint64_t)c.n;
+    vals[q] = (uint32_t)q;
+}
+// one workgroup per contig, both tables in LDS, a wave per hit and a lane per contributed base, as k_ee_pile; the base comes out of the
+// 2-bit read store: position t of the orientation that matched is base t of the read, or the complement of its base n - 1 - t
+__global__ __launch_bounds__(64 * EE_WAVES) void k_eh_pile(const uint64_t *__restrict__ words, int wpr, const EhHit *__restrict__ rows,
+                                                           const uint32_t *__restrict__ order, const int64_t *__restrict__ first,
+                                                           uint64_t *__restrict__ cons /* [n][2][EE_CW] */, int32_t *__restrict__ clen /* [n][2] */,
+                                                           int32_t *__restrict__ cflags) {
+    __shared__ uint32_t tab[2 * EE_LONGEST * 4];
+    __shared__ uint32_t rep[2], cnt[2];
+    __shared__ uint8_t best[2 * EE_LONGEST];
+    const int64_t c = blockIdx.x;
+    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    for (int t = tid; t < 2 * EE_LONGEST * 4; t += 64 * EE_WAVES) tab[t] = 0u;
+    if (tid < 2) { rep[tid] = 0u; cnt[tid] = 0u; }
+    __syncthreads();
+    const int64_t r1 = first[c + 1];
+    for (int64_t q = first[c] + wave; q < r1; q += EE_WAVES) {
+        const EhHit r = rows[order[q]];
+        const uint64_t *rw = words + r.read * wpr;
+        for (int t = lane; t < r.lcnt + r.rcnt; t += 64) {
+            const bool right = t >= r.lcnt;
+            const int j = right ? t - r.lcnt : t;
+            const int pos = right ? r.rsrc + j : r.lsrc - j;
+            const uint32_t code = r.strand ? 3u - pk_base_of(rw, r.n - 1 - pos) : pk_base_of(rw, pos);
+            atomicAdd(&tab[((right ? EE_LONGEST : 0) + j) * 4 + code], 1u);
+        }
+    }
+    __syncthreads();
+    ee_pile_finish(tab, rep, cnt, best, c, tid, cons, clen, cflags);
 }
 __global__ __launch_bounds__(256) void k_ee_cons_sizes(const int32_t *__restrict__ clen, int64_t n, uint32_t *__restrict__ nwl, uint32_t *__restrict__ nwr) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -468,6 +537,7 @@ static int ee_bad(rfx_ctx *ctx, uint32_t bad) {
     if (bad & EE_BAD_LAYOUT) { ctx->last_error = "end extension: a set whose word_off and len disagree, or lengths and flags that no consensus has"; return RFX_E_ARG; }
     if (bad & EE_TOO_LONG) { ctx->last_error = "end extension: a contig of 2^30 bases or more"; return RFX_E_LIMIT; }
     if (bad & EE_BAD_ID) { ctx->last_error = "end extension: a contig row that is not Contig_<L>_<left>_<right>_<idx>,<L bases of ACGT> with idx its position"; return RFX_E_ARG; }
+    if (bad & EE_BAD_HIT) { ctx->last_error = "end extension: a hit that rfx_dev_map_ends does not write for these contigs and reads"; return RFX_E_ARG; }
     if (bad & EE_BAD_START) { ctx->last_error = "end extension: an alignment row whose start is no int"; return RFX_E_ARG; }
     if (bad & EE_BAD_CIGAR) { ctx->last_error = "end extension: an alignment row whose CIGAR is not ([0-9]+[A-Z=])+"; return RFX_E_ARG; }
     if (bad & EE_BAD_RANGE) { ctx->last_error = "end extension: an alignment row whose overhang lies outside its sequence"; return RFX_E_ARG; }
@@ -506,6 +576,44 @@ int rfx::ee_consensus_plan(rfx_ctx *ctx, const Fx2View &in, const char *d_text, 
     CallFlags f{};
     RFX_TRY(call_flags_read(ctx, flags, plan.offl.as<uint64_t>() + n, plan.offr.as<uint64_t>() + n, nullptr, &f));
     RFX_TRY(ee_bad(ctx, f.bad));
+    plan.lwords = (int64_t)f.total[0]; plan.rwords = (int64_t)f.total[1];
+    return RFX_OK;
+}
+// the same plan from the hits of the end mapping and the read store: check and contributions, group, pile-up
+int rfx::ee_consensus_plan_hits(rfx_ctx *ctx, const Fx2View &in, const uint64_t *d_words, const uint32_t *d_read_len, int wpr, const MpHits &hits,
+                                int64_t n_hits, int seed, EeConsPlan &plan) {
+    const int64_t n = in.n;
+    plan.n = n; plan.lwords = 0; plan.rwords = 0;
+    if (n >= ((int64_t)1 << 31)) { ctx->last_error = "end extension: 2^31 contigs or more"; return RFX_E_LIMIT; }
+    if (n_hits >= ((int64_t)1 << 31)) { ctx->last_error = "end extension: 2^31 rows or more"; return RFX_E_LIMIT; }
+    if (n == 0) {
+        if (n_hits > 0) { ctx->last_error = "end extension: a hit that rfx_dev_map_ends does not write for these contigs and reads"; return RFX_E_ARG; }
+        return RFX_OK;
+    }
+    DevBuf rows, keys, vals, tk, tv, first, nwl, nwr, flags;
+    const int64_t nr = std::max<int64_t>(n_hits, 1);
+    RFX_ALLOC(rows, EhHit, nr); RFX_ALLOC(keys, uint64_t, nr); RFX_ALLOC(vals, uint32_t, nr);
+    RFX_ALLOC(tk, uint64_t, nr); RFX_ALLOC(tv, uint32_t, nr); RFX_ALLOC(first, int64_t, n + 1);
+    RFX_ALLOC(plan.cons, uint64_t, 2 * EE_CW * n); RFX_ALLOC(plan.clen, int32_t, 2 * n); RFX_ALLOC(plan.cflags, int32_t, n);
+    RFX_ALLOC(nwl, uint32_t, n); RFX_ALLOC(nwr, uint32_t, n);
+    RFX_ALLOC(plan.offl, uint64_t, n + 1); RFX_ALLOC(plan.offr, uint64_t, n + 1);
+    RFX_TRY(call_flags_init(ctx, flags));
+    CallFlags f{};
+    if (n_hits > 0) {
+        RFX_LAUNCH_N(k_eh_rows, n_hits, in, d_read_len, wpr, hits, n_hits, seed, rows.as<EhHit>(), keys.as<uint64_t>(), vals.as<uint32_t>(),
+                     flags.as<CallFlags>());
+        RFX_TRY(call_flags_read(ctx, flags, nullptr, nullptr, nullptr, &f));      // (a refused hit is not indexed with)
+        RFX_TRY(ee_bad(ctx, f.bad));
+        int bits = 1;
+        while (((int64_t)1 << bits) <= n) bits++;                   // (keys run to n)
+        RFX_TRY(sort_pairs(ctx, keys.as<uint64_t>(), vals.as<uint32_t>(), n_hits, bits, tk.as<uint64_t>(), tv.as<uint32_t>()));
+    }
+    RFX_LAUNCH_N(k_ee_first, n + 1, keys.as<uint64_t>(), n_hits, n, first.as<int64_t>());
+    RFX_LAUNCH(k_eh_pile, dim3((unsigned)n), dim3(64 * EE_WAVES), 0, d_words, wpr, rows.as<EhHit>(), vals.as<uint32_t>(), first.as<int64_t>(),
+               plan.cons.as<uint64_t>(), plan.clen.as<int32_t>(), plan.cflags.as<int32_t>());
+    RFX_LAUNCH_N(k_ee_cons_sizes, n, plan.clen.as<int32_t>(), n, nwl.as<uint32_t>(), nwr.as<uint32_t>());
+    RFX_TRY(exclusive_scan2_u32_to_u64(ctx, nwl.as<uint32_t>(), nwr.as<uint32_t>(), plan.offl.as<uint64_t>(), plan.offr.as<uint64_t>(), n));
+    RFX_TRY(call_flags_read(ctx, flags, plan.offl.as<uint64_t>() + n, plan.offr.as<uint64_t>() + n, nullptr, &f));
     plan.lwords = (int64_t)f.total[0]; plan.rwords = (int64_t)f.total[1];
     return RFX_OK;
 }
@@ -632,6 +740,24 @@ int rfx_dev_endext_consensus(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const
     RFX_HIP(hipSetDevice(ctx->device));
     EeConsPlan plan;
     RFX_TRY(ee_consensus_plan(ctx, fx2_view(d_in, d_left, d_right), d_text, d_row_off, n_rows, plan));
+    const bool lfits = packed_out_fits(&d_out->left, plan.n, plan.lwords), rfits = packed_out_fits(&d_out->right, plan.n, plan.rwords);
+    if (!lfits || !rfits) return RFX_E_CAP;
+    RFX_TRY(ee_consensus_fill(ctx, plan, ee_cons_out(d_out)));
+    d_out->left.n = d_out->right.n = plan.n;
+    return sync_checked(ctx);
+} RFX_API_CATCH(ctx)
+
+// the same from the hits of the end mapping and the read store: what rfx_dev_endext_consensus gives on the rows rfx_dev_map_to_text
+// writes of them, with no text made
+int rfx_dev_endext_consensus_hits(rfx_ctx *ctx, const rfx_contigs_packed *d_in, const int32_t *d_left, const int32_t *d_right, const uint64_t *d_words,
+                                  const uint32_t *d_read_len, int words_per_read, const rfx_map_hits *hits, rfx_endext_consensus *d_out) try {
+    if (!ctx || !fx2_contigs_in_ok(d_in, d_left, d_right) || words_per_read < 1 || !hits || !hits->read || !hits->end || !hits->strand || !hits->offset ||
+        !hits->v || hits->cap_n < 0 || hits->n < 0 || hits->n > hits->cap_n ||
+        (hits->n > 0 && (!d_words || !d_read_len || hits->seed < 11 || hits->seed > 31)) || !ee_cons_ok(d_out))
+        return RFX_E_ARG;
+    RFX_HIP(hipSetDevice(ctx->device));
+    EeConsPlan plan;
+    RFX_TRY(ee_consensus_plan_hits(ctx, fx2_view(d_in, d_left, d_right), d_words, d_read_len, words_per_read, mp_hits(hits), hits->n, hits->seed, plan));
     const bool lfits = packed_out_fits(&d_out->left, plan.n, plan.lwords), rfits = packed_out_fits(&d_out->right, plan.n, plan.rwords);
     if (!lfits || !rfits) return RFX_E_CAP;
     RFX_TRY(ee_consensus_fill(ctx, plan, ee_cons_out(d_out)));

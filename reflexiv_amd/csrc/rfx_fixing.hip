@@ -40,28 +40,39 @@ namespace {
 #define FX_KEY (FX_K - 1)            // the key of every record behind the contig ends
 
 // what is wrong with a call's input (CallFlags::bad)
-enum { FX_BAD_KEY = 1, FX_BAD_EXT = 2, FX_BAD_VALUE = 4 };
+enum { FX_BAD_KEY = 1, FX_BAD_EXT = 2, FX_BAD_VALUE = 4, FX_TOO_LONG = 8, FX_BAD_OFFSETS = 16 };
 
 // ---- a compaction: output record q := input record idx[q] -------------------------------------------------------------------------------
+// AS_ROW (rfx_dev_fix_run_packed): the record as form 1 of the binarizer reads it out of the row k_dyn_text_fill prints of it -- the key's
+// and the extension's bases and nothing behind them, the marker through its decimal text, left / right through theirs and clamped
+template <bool AS_ROW>
 __global__ __launch_bounds__(256) void k_fx_gather_rec(const DynView v, const int64_t *__restrict__ idx, int64_t m, const DynOut o, uint32_t *__restrict__ ew) {
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= m) return;
     const int64_t i = idx[q];
-    const uint64_t *s = v.key + PK_KW * i;
-    uint64_t *d = o.key + PK_KW * q;
-    d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3];
+    if (AS_ROW) {
+        pk_store(o.key, q, pk_keep4(pk_load(v.key, i), (int)v.key_len[i]));
+        o.marker[q] = pk_int_as_text(v.marker[i]); o.left[q] = pk_clamp(pk_int_as_text(v.left[i])); o.right[q] = pk_clamp(pk_int_as_text(v.right[i]));
+    } else {
+        const uint64_t *s = v.key + PK_KW * i;
+        uint64_t *d = o.key + PK_KW * q;
+        d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3];
+        o.marker[q] = v.marker[i]; o.left[q] = v.left[i]; o.right[q] = v.right[i];
+    }
     o.key_len[q] = v.key_len[i];
     o.ext_len[q] = v.ext_len[i];
-    o.marker[q] = v.marker[i]; o.left[q] = v.left[i]; o.right[q] = v.right[i];
     ew[q] = (uint32_t)((v.ext_len[i] + 31) >> 5);
 }
 // one thread per output extension word (the grid covers a bound; the exact count is ooff[m])
+template <bool AS_ROW>
 __global__ __launch_bounds__(256) void k_fx_gather_ext(const DynView v, const int64_t *__restrict__ idx, int64_t m, const uint64_t *__restrict__ ooff,
                                                        uint64_t *__restrict__ oext) {
     const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (m <= 0 || w >= (int64_t)ooff[m]) return;
     const int64_t q = pk_find(ooff, m, w);
-    oext[w] = v.ext[v.ext_off[idx[q]] + (w - (int64_t)ooff[q])];
+    const int64_t i = idx[q], r = w - (int64_t)ooff[q];
+    const uint64_t x = v.ext[v.ext_off[i] + r];
+    oext[w] = AS_ROW ? pk_keep(x, v.ext_len[i] - (int)(32 * r)) : x;
 }
 
 // ---- step 1: the length filter behind the binarizer ---------------------------------------------------------------------------------------
@@ -69,6 +80,18 @@ __global__ __launch_bounds__(256) void k_fx_long_enough(const uint8_t *__restric
                                                         uint32_t *__restrict__ keep) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) keep[i] = (int64_t)key_len[i] + ext_len[i] >= min_len ? 1u : 0u;
+}
+// ... and on a caller's set, which no binarizer made: a key of more than 124 bases, a record without an extension (it has no form-1
+// row) and extension offsets that do not follow the lengths (the gather would index with them) are noted, and such a record is not kept
+__global__ __launch_bounds__(256) void k_fx_row_long_enough(const DynView v, int64_t n, int min_len, uint32_t *__restrict__ keep, CallFlags *__restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int kl = (int)v.key_len[i], el = v.ext_len[i];
+    const int64_t b = v.ext_off[i], e = v.ext_off[i + 1];
+    uint32_t bad = (kl > 124 ? (uint32_t)FX_TOO_LONG : 0u) | (el < 1 ? (uint32_t)FX_BAD_EXT : 0u);
+    if (b < 0 || (el >= 1 && e - b != (((int64_t)el + 31) >> 5))) bad |= FX_BAD_OFFSETS;
+    if (bad) atomicOr(&flags->bad, bad);
+    keep[i] = (!bad && (int64_t)kl + el >= min_len) ? 1u : 0u;
 }
 
 // ---- steps 2-3: the contig ends -----------------------------------------------------------------------------------------------------------
@@ -261,6 +284,7 @@ static int fx_check(rfx_ctx *ctx, const DynDev &in) {
     return RFX_OK;
 }
 // the kept records of a set, in order (keep / rank: n flags and their exclusive scan, rank[n] = m)
+template <bool AS_ROW = false>
 static int fx_compact(rfx_ctx *ctx, const DynDev &in, const DevBuf &keep, const DevBuf &rank, int64_t m, DynDev &out) {
     if (m == 0) return dyn_empty(ctx, out);
     const int64_t n = in.n;
@@ -269,10 +293,10 @@ static int fx_compact(rfx_ctx *ctx, const DynDev &in, const DevBuf &keep, const 
     RFX_TRY(dyn_alloc(ctx, out, m, in.words));
     const DynView v = dyn_view(in);
     RFX_TRY(index_kept(ctx, keep.as<uint32_t>(), rank.as<uint64_t>(), n, idx.as<int64_t>()));
-    RFX_LAUNCH_N(k_fx_gather_rec, m, v, idx.as<int64_t>(), m, dyn_out(out), ew.as<uint32_t>());
+    RFX_LAUNCH_N(k_fx_gather_rec<AS_ROW>, m, v, idx.as<int64_t>(), m, dyn_out(out), ew.as<uint32_t>());
     RFX_TRY(exclusive_scan_u32_to_u64(ctx, ew.as<uint32_t>(), out.ext_off.as<uint64_t>(), m));
     if (in.words > 0) {
-        RFX_LAUNCH_N(k_fx_gather_ext, in.words, v, idx.as<int64_t>(), m, out.ext_off.as<uint64_t>(),
+        RFX_LAUNCH_N(k_fx_gather_ext<AS_ROW>, in.words, v, idx.as<int64_t>(), m, out.ext_off.as<uint64_t>(),
                      out.ext.as<uint64_t>());
     }
     return RFX_OK;
@@ -291,6 +315,25 @@ static int fx_binarize(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_of
     int64_t m = 0;
     RFX_TRY(scan_keep(ctx, keep.as<uint32_t>(), n, rank.as<uint64_t>(), &m));
     return fx_compact(ctx, a, keep, rank, m, out);
+}
+
+// step 1 on a packed set (a view of the caller's): form 1's reading of every record, then the same filter -- what fx_binarize gives
+// for the rows dyn_to_text writes of the set, with no text made
+static int fx_binarize_packed(rfx_ctx *ctx, const DynDev &in, const FxParams &prm, DynDev &out) {
+    const int64_t n = in.n;
+    if (n == 0) return dyn_empty(ctx, out);
+    if (n >= ((int64_t)1 << 31)) { ctx->last_error = "contig fixing: 2^31 rows or more"; return RFX_E_LIMIT; }
+    DevBuf keep, rank, flags;
+    RFX_ALLOC(keep, uint32_t, n); RFX_ALLOC(rank, uint64_t, n + 1);
+    RFX_TRY(call_flags_init(ctx, flags));
+    RFX_LAUNCH_N(k_fx_row_long_enough, n, dyn_view(in), n, 2 * prm.max_k, keep.as<uint32_t>(), flags.as<CallFlags>());
+    RFX_TRY(exclusive_scan_u32_to_u64(ctx, keep.as<uint32_t>(), rank.as<uint64_t>(), n));
+    CallFlags f{};
+    RFX_TRY(call_flags_read(ctx, flags, rank.as<uint64_t>() + n, nullptr, nullptr, &f));
+    if (f.bad & FX_TOO_LONG) { ctx->last_error = "dynamic-k: a key longer than 124 bases"; return RFX_E_LIMIT; }
+    if (f.bad & FX_BAD_EXT) { ctx->last_error = "contig fixing: a record without an extension has no row"; return RFX_E_ARG; }
+    if (f.bad & FX_BAD_OFFSETS) { ctx->last_error = "contig fixing: extension offsets that do not follow the extension lengths"; return RFX_E_ARG; }
+    return fx_compact<true>(ctx, in, keep, rank, (int64_t)f.total[0], out);
 }
 
 // steps 2-3: the long records, and the 31-mers in emission order (contig by contig, i = 0 .. max_k - 31, left then right)
@@ -392,14 +435,18 @@ static int fx_reflect(rfx_ctx *ctx, const DynDev &in, DynDev &out) {
     return RFX_OK;
 }
 
-// steps 1-3, then rfx::fx_from_ends
-static int fx_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, int P, const FxParams &prm, DynDev &out) {
-    DynDev a, b;
+// steps 2-3 on step 1's set, then rfx::fx_from_ends
+static int fx_run_binarized(rfx_ctx *ctx, const DynDev &a, int P, const FxParams &prm, DynDev &out) {
+    DynDev b;
     DevBuf kmers;
     int64_t n31 = 0;
-    RFX_TRY(fx_binarize(ctx, d_text, d_row_off, n_rows, prm, a));
     RFX_TRY(fx_contig_ends(ctx, a, prm, b, kmers, &n31));
     return fx_from_ends(ctx, kmers.as<uint64_t>(), n31, b, P, prm.scramble, prm.max_iteration, out);
+}
+static int fx_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, int64_t n_rows, int P, const FxParams &prm, DynDev &out) {
+    DynDev a;
+    RFX_TRY(fx_binarize(ctx, d_text, d_row_off, n_rows, prm, a));
+    return fx_run_binarized(ctx, a, P, prm, out);
 }
 
 }  // namespace
@@ -426,6 +473,14 @@ int rfx::fx_from_ends(rfx_ctx *ctx, const uint64_t *d_kmers, int64_t n31, const 
         RFX_TRY(sync_checked(ctx));                               // (s and the pass's temporaries are read until here)
     }
     return RFX_OK;
+}
+
+// ... for the driver from reads to contigs (rfx_meta.hip): the body of rfx_dev_fix_run_packed on a set of the library's (params checked)
+int rfx::fx_run_set(rfx_ctx *ctx, const DynDev &in, int P, const rfx_fix_params &params, DynDev &out) {
+    const FxParams prm{params.max_k, params.scramble, params.max_iteration};
+    DynDev a;
+    RFX_TRY(fx_binarize_packed(ctx, in, prm, a));
+    return fx_run_binarized(ctx, a, P, prm, out);
 }
 
 int rfx::fx_ends_store(rfx_ctx *ctx, const DynDev &lng, const DevBuf &kmers, int64_t n31, rfx_dyn_packed *d_out_long, uint64_t *d_kmers, int64_t cap_kmers,
@@ -512,6 +567,19 @@ int rfx_dev_fix_run(rfx_ctx *ctx, const char *d_text, const int64_t *d_row_off, 
     DynDev a;
     RFX_TRY(fx_run(ctx, d_text, d_row_off, n_rows, P, prm, a));
     return dyn_store(ctx, a, d_out);
+} RFX_API_CATCH(ctx)
+
+// the last iteration's set straight into the stage: no text between them
+int rfx_dev_fix_run_packed(rfx_ctx *ctx, const rfx_dyn_packed *d_in, int P, const rfx_fix_params *params, rfx_dyn_packed *d_out) try {
+    if (!ctx || !dyn_packed_ok(d_in) || !dyn_packed_out_ok(d_out) || !parts_ok(P)) return RFX_E_ARG;
+    FxParams prm;
+    RFX_TRY(fx_params(ctx, params, &prm));
+    RFX_HIP(hipSetDevice(ctx->device));
+    DynDev in, a, o;
+    RFX_TRY(dyn_borrow(ctx, d_in, in));
+    RFX_TRY(fx_binarize_packed(ctx, in, prm, a));
+    RFX_TRY(fx_run_binarized(ctx, a, P, prm, o));
+    return dyn_store(ctx, o, d_out);
 } RFX_API_CATCH(ctx)
 
 // host text in, host text out; everything between packed and in HBM: upload, run, to-text, one copy back

@@ -618,6 +618,18 @@ int mp_fill(rfx_ctx *ctx, const Fx2View &c, const uint64_t *d_words, const uint3
             const MpPlan &plan, const MpHits &o);
 int mp_text(rfx_ctx *ctx, const Fx2View &c, const uint64_t *d_words, const uint32_t *d_read_len, int wpr, const MpHits &hits, int64_t n, int seed,
             char *d_text, int64_t cap, int64_t *total, int64_t *d_row_off, DevBuf *own);
+// ... and rfx_endext.hip on those rows without their text: ee_consensus_plan from the hits and the read store
+int ee_consensus_plan_hits(rfx_ctx *ctx, const Fx2View &in, const uint64_t *d_words, const uint32_t *d_read_len, int wpr, const MpHits &hits,
+                           int64_t n_hits, int seed, EeConsPlan &plan);
+
+// ---- for rfx_meta.hip, the driver from reads to contigs: the bodies of rfx_dev_dyn_run (a is replaced by the
+// result), rfx_dev_reduce_reads (and its argument checks) and rfx_dev_fix_run_packed on sets of the library's
+int dyn_run_set(rfx_ctx *ctx, DynDev &a, int P, int random_reflection, int passes_first_four, int start_iteration, int end_iteration);
+int rr_check_args(rfx_ctx *ctx, const uint64_t *d_words, const uint32_t *d_read_len, int64_t n_reads, int wpr, int max_read_len, const int *klist, int n_k,
+                  const rfx_reduce_reads_params *p);
+int rr_reduce_set(rfx_ctx *ctx, const uint64_t *d_words, const uint32_t *d_read_len, int64_t n_reads, int wpr, int max_read_len, const int *klist, int n_k,
+                  const rfx_reduce_reads_params &p, DynDev &a, int64_t *per_k);
+int fx_run_set(rfx_ctx *ctx, const DynDev &in, int P, const rfx_fix_params &params, DynDev &out);
 
 // ---- packed contig sets in HBM (rfx_contigs_packed and what is built on it), shared by the four stages above: DESIGN.md section 27
 #pragma GCC visibility push(hidden)

@@ -663,6 +663,22 @@ static int rr_pairs(rfx_ctx *ctx, const uint64_t *d_words, const uint32_t *d_rea
     return RFX_OK;
 }
 }  // namespace
+// ... for the driver from reads to contigs (rfx_meta.hip): what rfx_dev_reduce_reads checks of its arguments / its body, into a set of
+// the library's (per_k: n_k row counts, nullable)
+int rfx::rr_check_args(rfx_ctx *ctx, const uint64_t *d_words, const uint32_t *d_read_len, int64_t n_reads, int wpr, int max_read_len, const int *klist, int n_k,
+                       const rfx_reduce_reads_params *p) {
+    return rr_args(ctx, d_words, d_read_len, n_reads, wpr, max_read_len, klist, n_k, p);
+}
+int rfx::rr_reduce_set(rfx_ctx *ctx, const uint64_t *d_words, const uint32_t *d_read_len, int64_t n_reads, int wpr, int max_read_len, const int *klist, int n_k,
+                       const rfx_reduce_reads_params &p, DynDev &a, int64_t *per_k) {
+    if (per_k) for (int i = 0; i < n_k; i++) per_k[i] = 0;
+    if (n_reads == 0) return dyn_empty(ctx, a);
+    std::vector<DynDev> res((size_t)n_k - 1);
+    std::vector<const DynDev *> sets((size_t)n_k);
+    RFX_TRY(rr_pairs(ctx, d_words, d_read_len, n_reads, wpr, max_read_len, klist, n_k, p, res, sets));
+    RFX_TRY(ks_kmers_to_records(ctx, sets.data(), klist, n_k, a, per_k));
+    return sync_checked(ctx);                                           // (the sets go back to the pool here: their last reader is behind us)
+}
 
 extern "C" {
 
