@@ -1078,221 +1078,153 @@ int rfx_last_count_timing(rfx_ctx *ctx, const char *name, float *ms, int64_t *la
 
 }  // extern "C"  (the driver below is C++: rfx_shard.hip calls it too)
 
-// Driver: P/ReflexivMain.java:168-310 (DS P/ReflexivDSMain.java:221-352); wide = the k > 31 driver
-// ReflexivDSMain64.assemblyFromKmer (P/ReflexivDSMain64.java:374-826) without the extras of :584-619 and :672-712
-// (SURVEY.md 8f-3): its loop :621-661 iterates all records, checks the count from minimumIteration + 3 on, the
-// first repeat of the count flips param.scramble 2 -> 3 (every later pass starts its marker at 1, :7484-7486) and
-// only the second stops; the survivors are sorted once more before they become text (:714).
-// resume: the loop taken up where the sharded driver (rfx_shard.hip) left it -- its record set gathered on this rank in
-// global arrival order, `passes_done` passes behind it, the driver's variables as they stood.  d_keys / d_counts / n unused.
-int rfx::assemble_impl(rfx_ctx *ctx, bool wide, const uint64_t *d_keys, const int32_t *d_counts, int64_t n,
-                       const rfx_params *prm, char *out, int64_t cap, int64_t *out_len, int64_t *out_contigs,
-                       int64_t *trace, int64_t trace_cap, int64_t *n_trace, rfx::AsmResume *resume) {
-    if (!ctx || !prm || !out_len || n < 0) return RFX_E_ARG;
-    if (wide) { RFX_TRY(check_k_rec(prm->k)); if (prm->k <= 31) return RFX_E_ARG; }
-    else RFX_TRY(check_k(prm->k));
-    RFX_HIP(hipSetDevice(ctx->device));
-    const int k = prm->k, twin = wide ? RFX_TWIN_DS : prm->twin;
-    int P = prm->partitions > 0 ? prm->partitions : 1;
-    const int key_bits = 2 * (k - 1);
-    const int kw = sub_words(k);
-    int64_t nt = resume ? resume->nt : 0;
-    DevRecords a, b;
-    DevBuf ps, ops;
-    // two alternating bump arenas hold every temporary and record set of a pass / stage
-    Arena arena[2];
-    {
-        const size_t per = (resume ? (size_t)(resume->recs->n + resume->recs->words) : (size_t)(2 * n)) * (176 + 24 * (size_t)(kw - 1)) + ((size_t)64 << 20);
-        for (int i = 0; i < 2; i++) {
-            arena[i].base = (char *)ctx->ws_get(2 + i, per);
-            if (!arena[i].base) { ctx->last_error = "workspace allocation failed"; return RFX_E_HIP; }
-            arena[i].cap = per;
-        }
-    }
-    timespec ts_enter; clock_gettime(CLOCK_MONOTONIC, &ts_enter);
-    const double t_enter = ts_enter.tv_sec * 1e3 + ts_enter.tv_nsec * 1e-6;
-    struct ArenaGuard { ~ArenaGuard() { tl_arena = nullptr; } } arena_guard;
-    int arena_turn = 0;
-    auto next_arena = [&]() { Arena *ar = &arena[arena_turn++ & 1]; ar->off = 0; tl_arena = ar; };
-    next_arena();
-    if (!resume) {
-    // KmerReverseComplement + ForwardSubKmerExtraction  :168-176
-    RFX_TRY(rc_expand_subkmer(ctx, d_keys, d_counts, n, k, a));
-    // sortByKey + FilterForkSubKmer[WithErrorCorrection]  :179-186
-    next_arena();
-    RFX_TRY(sort_records(ctx, a, P, key_bits, b, ps, k));
-    next_arena();
-    RFX_TRY(fork_filter(ctx, false, b, ps.as<int64_t>(), P, k, prm->min_error_cov, twin, a, ops));
-    // ReflectedSubKmerExtractionFromForward  :188-189
-    next_arena();
-    RFX_TRY(reflect_from_forward(ctx, a, k, b));
-    // sortByKey + FilterForkReflectedSubKmer[WithErrorCorrection]  :191-198
-    next_arena();
-    RFX_TRY(sort_records(ctx, b, P, key_bits, a, ps, k));
-    next_arena();
-    RFX_TRY(fork_filter(ctx, true, a, ps.as<int64_t>(), P, k, prm->min_error_cov, twin, b, ops));
-    // kmerRandomReflection on the filter's output partitions  :204-205
-    next_arena();
-    RFX_TRY(random_reflection(ctx, b, ops.as<int64_t>(), P, k, a));
-    } else {
-        // (the gathered set lives in plain stream-ordered allocations, outside the arenas: the first sort reads it from there)
-        a.n = resume->recs->n; a.words = resume->recs->words; a.kw = resume->recs->kw;
-        a.key = std::move(resume->recs->key); a.marker = std::move(resume->recs->marker); a.ext_off = std::move(resume->recs->ext_off);
-        a.ext = std::move(resume->recs->ext); a.left = std::move(resume->recs->left); a.right = std::move(resume->recs->right);
-        P = resume->P;
-    }
+namespace {
 
-    const bool verbose = getenv("RFX_TRACE") != nullptr;
-    auto now_ms = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
-    const double t_loop0 = verbose ? ((void)hipStreamSynchronize(ctx->stream), now_ms()) : 0;
-    if (verbose) fprintf(stderr, "assemble: stages before the loop %.3f ms\n", t_loop0 - t_enter);
-    auto one_pass = [&](int stage, int start_marker = 2) -> int {
-        const double t0 = verbose ? now_ms() : 0;
-        next_arena();                     // `a` (this pass's input) stays valid in the other arena
-        RFX_TRY(sort_records(ctx, a, P, key_bits, b, ps, k));                     // sortByKey :211,:235,:247,:286
-        if (verbose) (void)hipStreamSynchronize(ctx->stream);
-        const double t1 = verbose ? now_ms() : 0;
-        RFX_TRY(extend_pass(ctx, b, ps.as<int64_t>(), P, k, twin, stage, a, ops, start_marker));
-        if (verbose) fprintf(stderr, "pass %lld: n_in %lld words %lld sort %.3f ms extend %.3f ms -> n %lld\n", (long long)nt,
-                             (long long)b.n, (long long)b.words, t1 - t0, now_ms() - t1, (long long)a.n);
-        if (trace && nt < trace_cap) trace[nt] = a.n;
-        nt++;
-        return RFX_OK;
-    };
-    int iterations = resume ? resume->iterations : 0;
-    // the five passes before the loop: :221-222 (stage 0), :233-241 (three more, iterations 1..3), :247-254 (first-array)
-    for (int np = resume ? resume->passes_done : 0; np < 5; np++) {
-        if (np >= 1) iterations++;
-        RFX_TRY(one_pass(np < 4 ? 0 : 1));
-    }
-    int partitionNumber = resume ? resume->partition_number : P;
-    int64_t contigNumber = resume ? resume->contig_number : 0;
-    int scramble = resume ? resume->scramble : 2;                                 // U/DefaultParam.java:131
-    // once the record set is small the rest of the loop runs as two launches per pass with the loop state in HBM
-    const bool extras = wide && prm->extras != 0;
+double now_ms() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
+
+// a whole record set copied into `dst`, which has room for it
+int records_clone(rfx_ctx *ctx, const DevRecords &src, DevRecords &dst) {
+    RFX_TRY(dev_records_copy(ctx, src, dst));
+    RFX_HIP(hipMemcpyAsync(dst.ext_off.p, src.ext_off.p, (size_t)(src.n + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    dst.n = src.n; dst.words = src.words;
+    return RFX_OK;
+}
+
+// Driver: P/ReflexivMain.java:168-310 (DS P/ReflexivDSMain.java:221-352); wide = the k > 31 driver
+// ReflexivDSMain64.assemblyFromKmer (P/ReflexivDSMain64.java:374-826) with the extras of :584-619 and :672-712 where
+// prm->extras says so: its loop :621-661 iterates all records, and the survivors are sorted once more before
+// they become text (:714).  The loop's variables and its stop rule are rfx_asm_loop.h's.
+// Every temporary and record set of a step lives in one of two alternating bump arenas: each arenas.next() decides which
+// buffers stay valid, the input of a step in the arena of the step before.
+struct AsmDriver {
+    rfx_ctx *ctx;
+    const rfx_params *prm;
+    const bool wide;
+    int64_t *trace;
+    const int64_t trace_cap;
+    const int k, twin, key_bits, kw;
+    const bool extras, verbose;
+    const AsmRule rule;
+    ArenaPair arenas;
+    DevRecords a, b;                        // the record set, and what a step makes of it
+    DevBuf ps, ops;                         // partition starts of a sorted set / of an operator's output
+    AsmLoop loop;
     bool split_done = false;
     DevRecords unext;                       // UnExtendableReflexivKmer (64 :605); lives outside the alternating arenas
-    auto small_tail = [&](bool *took) -> int {
+
+    AsmDriver(rfx_ctx *c, bool w, const rfx_params *p, int64_t *tr, int64_t tcap)
+        : ctx(c), prm(p), wide(w), trace(tr), trace_cap(tcap), k(p->k), twin(w ? RFX_TWIN_DS : p->twin), key_bits(2 * (p->k - 1)),
+          kw(sub_words(p->k)), extras(w && p->extras != 0), verbose(getenv("RFX_TRACE") != nullptr),
+          rule{w ? 1 : 0, p->coalesce, p->min_iter, p->max_iter} {}
+
+    // the stages before the loop on the filtered (k-mer, count) list -- or, resumed, the gathered set and the loop's variables
+    // as the sharded driver left them (the set lives in plain stream-ordered allocations, outside the arenas: the first sort
+    // reads it from there)
+    int start(const uint64_t *d_keys, const int32_t *d_counts, int64_t n, AsmResume *resume) {
+        arenas.next();
+        if (resume) { a = std::move(*resume->recs); loop = resume->loop; return RFX_OK; }
+        const int P = loop.P = loop.partition_number = prm->partitions > 0 ? prm->partitions : 1;
+        // KmerReverseComplement + ForwardSubKmerExtraction  :168-176
+        RFX_TRY(rc_expand_subkmer(ctx, d_keys, d_counts, n, k, a));
+        // sortByKey + FilterForkSubKmer[WithErrorCorrection]  :179-186
+        arenas.next();
+        RFX_TRY(sort_records(ctx, a, P, key_bits, b, ps, k));
+        arenas.next();
+        RFX_TRY(fork_filter(ctx, false, b, ps.as<int64_t>(), P, k, prm->min_error_cov, twin, a, ops));
+        // ReflectedSubKmerExtractionFromForward  :188-189
+        arenas.next();
+        RFX_TRY(reflect_from_forward(ctx, a, k, b));
+        // sortByKey + FilterForkReflectedSubKmer[WithErrorCorrection]  :191-198
+        arenas.next();
+        RFX_TRY(sort_records(ctx, b, P, key_bits, a, ps, k));
+        arenas.next();
+        RFX_TRY(fork_filter(ctx, true, a, ps.as<int64_t>(), P, k, prm->min_error_cov, twin, b, ops));
+        // kmerRandomReflection on the filter's output partitions  :204-205
+        arenas.next();
+        RFX_TRY(random_reflection(ctx, b, ops.as<int64_t>(), P, k, a));
+        return RFX_OK;
+    }
+
+    int one_pass(int stage, int start_marker) {
+        const double t0 = verbose ? now_ms() : 0;
+        arenas.next();                    // `a` (this pass's input) stays valid in the other arena
+        RFX_TRY(sort_records(ctx, a, loop.P, key_bits, b, ps, k));                // sortByKey :211,:235,:247,:286
+        if (verbose) (void)hipStreamSynchronize(ctx->stream);
+        const double t1 = verbose ? now_ms() : 0;
+        RFX_TRY(extend_pass(ctx, b, ps.as<int64_t>(), loop.P, k, twin, stage, a, ops, start_marker));
+        if (verbose) fprintf(stderr, "pass %lld: n_in %lld words %lld sort %.3f ms extend %.3f ms -> n %lld\n", (long long)loop.nt,
+                             (long long)b.n, (long long)b.words, t1 - t0, now_ms() - t1, (long long)a.n);
+        if (trace && loop.nt < trace_cap) trace[loop.nt] = a.n;
+        loop.nt++;
+        loop.passes_done++;
+        return RFX_OK;
+    }
+
+    // once the record set is small the rest of the loop runs as two launches per pass with the loop state in HBM
+    int small_tail(bool *took) {
         *took = false;
-        if (a.n > small_pass_limit() || P > small_pass_max_partitions()) return RFX_OK;
-        if (extras && !split_done && iterations + 1 <= prm->min_iter + 3) return RFX_OK;   // the split of 64 :584-619 comes first
-        Arena *saved = tl_arena;
-        tl_arena = nullptr;                 // its second record set and scratch outlive the alternating arenas
+        if (a.n > small_pass_limit() || loop.P > small_pass_max_partitions()) return RFX_OK;
+        if (extras && !split_done && loop.iterations + 1 <= prm->min_iter + 3) return RFX_OK;   // the split of 64 :584-619 comes first
+        ArenaOff off;                       // its second record set and scratch outlive the alternating arenas
         const double t0 = verbose ? now_ms() : 0;
         const int64_t n0 = a.n;
-        const int st = small_passes(ctx, a, k, twin, wide, prm->coalesce, prm->min_iter, prm->max_iter, &iterations, &contigNumber,
-                                    &scramble, &P, &partitionNumber, trace, trace_cap, &nt);
-        tl_arena = saved;
+        RFX_TRY(small_passes(ctx, a, k, twin, loop, rule, trace, trace_cap));
         if (verbose) fprintf(stderr, "small passes from n %lld: %.3f ms -> n %lld after pass %lld\n", (long long)n0, now_ms() - t0,
-                             (long long)a.n, (long long)nt);
-        *took = st == RFX_OK;
-        return st;
-    };
-    // a record set copied out of the arenas (plain stream-ordered allocations)
-    auto detach = [&](const DevRecords &src, DevRecords &dst) -> int {
-        Arena *saved = tl_arena;
-        tl_arena = nullptr;
-        int st = dev_records_alloc(ctx, dst, src.n, src.words, src.kw);
-        tl_arena = saved;
-        RFX_TRY(st);
-        if (src.n > 0) {
-            RFX_HIP(hipMemcpyAsync(dst.key.p, src.key.p, (size_t)src.n * 8 * src.kw, hipMemcpyDeviceToDevice, ctx->stream));
-            RFX_HIP(hipMemcpyAsync(dst.marker.p, src.marker.p, (size_t)src.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-            RFX_HIP(hipMemcpyAsync(dst.left.p, src.left.p, (size_t)src.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-            RFX_HIP(hipMemcpyAsync(dst.right.p, src.right.p, (size_t)src.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-            if (src.words > 0) RFX_HIP(hipMemcpyAsync(dst.ext.p, src.ext.p, (size_t)src.words * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        RFX_HIP(hipMemcpyAsync(dst.ext_off.p, src.ext_off.p, (size_t)(src.n + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        dst.n = src.n; dst.words = src.words;
+                             (long long)a.n, (long long)loop.nt);
+        *took = true;
         return RFX_OK;
-    };
-    while (wide && iterations <= prm->max_iter) {                                 // 64 :582
-        { bool took; RFX_TRY(small_tail(&took)); if (took) break; }
-        iterations++;
-        if (extras && iterations == prm->min_iter + 3) {                          // 64 :584-619
-            DevRecords dbl, pe, pu, tmp;
-            // sort, DSReflexivAndForwardKmer, sort  (:587-590)
-            next_arena();
+    }
+
+    // a record set copied out of the arenas (plain stream-ordered allocations)
+    int detach(const DevRecords &src, DevRecords &dst) {
+        { ArenaOff off; RFX_TRY(dev_records_alloc(ctx, dst, src.n, src.words, src.kw)); }
+        return records_clone(ctx, src, dst);
+    }
+
+    // 64 :584-619: the set doubled, split into ExtendableReflexivKmer, which the loop goes on with, and
+    // UnExtendableReflexivKmer, which waits for the union
+    int split() {
+        const int P = loop.P;
+        DevRecords dbl, pe, pu, tmp;
+        // sort, DSReflexivAndForwardKmer, sort  (:587-590)
+        arenas.next();
+        RFX_TRY(sort_records(ctx, a, P, key_bits, b, ps, k));
+        arenas.next();
+        RFX_TRY(extras_operator(ctx, RFX_OP_DOUBLE, b, ps.as<int64_t>(), P, k, a, ops));
+        RFX_TRY(detach(a, tmp));                                              // (the doubled set is read twice below)
+        arenas.next();
+        RFX_TRY(sort_records(ctx, tmp, P, key_bits, b, ps, k));
+        RFX_TRY(detach(b, dbl));
+        DevBuf dps;
+        { ArenaOff off; RFX_HIP(dps.alloc((size_t)(P + 1) * 8, ctx->stream)); }
+        RFX_HIP(hipMemcpyAsync(dps.p, ps.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        // the two filters on the doubled set, each followed by sort + first-of-key  (:593-605)
+        for (int t = 0; t < 2; t++) {
+            arenas.next();
+            RFX_TRY(extras_operator(ctx, t == 0 ? RFX_OP_EXTENDABLE_PAIRS : RFX_OP_UNEXTENDABLE, dbl, dps.as<int64_t>(), P, k, a, ops));
+            arenas.next();
             RFX_TRY(sort_records(ctx, a, P, key_bits, b, ps, k));
-            next_arena();
-            RFX_TRY(extras_operator(ctx, RFX_OP_DOUBLE, b, ps.as<int64_t>(), P, k, a, ops));
-            RFX_TRY(detach(a, tmp));                                              // (the doubled set is read twice below)
-            next_arena();
-            RFX_TRY(sort_records(ctx, tmp, P, key_bits, b, ps, k));
-            RFX_TRY(detach(b, dbl));
-            DevBuf dps;
-            { Arena *sv = tl_arena; tl_arena = nullptr; hipError_t e = dps.alloc((size_t)(P + 1) * 8, ctx->stream); tl_arena = sv; RFX_HIP(e); }
-            RFX_HIP(hipMemcpyAsync(dps.p, ps.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-            // the two filters on the doubled set, each followed by sort + first-of-key  (:593-605)
-            for (int t = 0; t < 2; t++) {
-                next_arena();
-                RFX_TRY(extras_operator(ctx, t == 0 ? RFX_OP_EXTENDABLE_PAIRS : RFX_OP_UNEXTENDABLE, dbl, dps.as<int64_t>(), P, k, a, ops));
-                next_arena();
-                RFX_TRY(sort_records(ctx, a, P, key_bits, b, ps, k));
-                next_arena();
-                RFX_TRY(extras_operator(ctx, RFX_OP_FIRST_OF_KEY, b, ps.as<int64_t>(), P, k, a, ops));
-                RFX_TRY(detach(a, t == 0 ? pe : pu));
-            }
-            // ExtendableReflexivKmer is what the loop goes on with; UnExtendableReflexivKmer waits for the union
-            next_arena();
-            RFX_TRY(detach(pu, unext));
-            {   // pe -> a in the current arena
-                RFX_TRY(dev_records_alloc(ctx, a, pe.n, pe.words, pe.kw));
-                if (pe.n > 0) {
-                    RFX_HIP(hipMemcpyAsync(a.key.p, pe.key.p, (size_t)pe.n * 8 * pe.kw, hipMemcpyDeviceToDevice, ctx->stream));
-                    RFX_HIP(hipMemcpyAsync(a.marker.p, pe.marker.p, (size_t)pe.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-                    RFX_HIP(hipMemcpyAsync(a.left.p, pe.left.p, (size_t)pe.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-                    RFX_HIP(hipMemcpyAsync(a.right.p, pe.right.p, (size_t)pe.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-                    if (pe.words > 0) RFX_HIP(hipMemcpyAsync(a.ext.p, pe.ext.p, (size_t)pe.words * 8, hipMemcpyDeviceToDevice, ctx->stream));
-                }
-                RFX_HIP(hipMemcpyAsync(a.ext_off.p, pe.ext_off.p, (size_t)(pe.n + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-                a.n = pe.n; a.words = pe.words;
-            }
-            RFX_TRY(sync_checked(ctx));
-            split_done = true;
+            arenas.next();
+            RFX_TRY(extras_operator(ctx, RFX_OP_FIRST_OF_KEY, b, ps.as<int64_t>(), P, k, a, ops));
+            RFX_TRY(detach(a, t == 0 ? pe : pu));
         }
-        if (iterations >= prm->min_iter + 3 && iterations % 3 == 0) {             // 64 :621-622
-            const int64_t current = a.n;                                          // 64 :633-635
-            if (contigNumber == current) {                                        // 64 :639
-                if (scramble == 2) { scramble = 3; contigNumber = current; }      // 64 :640-642
-                else break;                                                       // 64 :644
-            } else contigNumber = current;                                        // 64 :647
-            // the coalesce of 64 :651-655 is assigned to a variable the loop does not read: no effect
-        }
-        RFX_TRY(one_pass(2, scramble == 3 ? 1 : 2));                              // 64 :659-660, :667-669
+        arenas.next();
+        RFX_TRY(detach(pu, unext));
+        RFX_TRY(dev_records_alloc(ctx, a, pe.n, pe.words, pe.kw));              // pe -> a in the current arena
+        RFX_TRY(records_clone(ctx, pe, a));
+        RFX_TRY(sync_checked(ctx));
+        split_done = true;
+        return RFX_OK;
     }
-    while (!wide && iterations <= prm->max_iter) {                                // :265-296
-        { bool took; RFX_TRY(small_tail(&took)); if (took) break; }
-        iterations++;
-        if (iterations >= prm->min_iter && iterations % 3 == 0) {
-            const int64_t current = a.n;                                          // count() :270
-            if (contigNumber == current) break;
-            contigNumber = current;
-            if (prm->coalesce && partitionNumber >= 16 && current / partitionNumber <= 20) {
-                partitionNumber = partitionNumber / 4 + 1;                        // :277-281
-                P = partitionNumber;
-            }
-        }
-        RFX_TRY(one_pass(2));
-    }
-    if (n_trace) *n_trace = nt;
-    if (split_done) {                                                             // 64 :672-712
+
+    // 64 :672-712: the union of the two sets, then the end filters
+    int unite() {
+        const int P = loop.P;
         // union: the extendable set's records, then the unextendable set's (:678)
         DevRecords u;
-        { Arena *sv = tl_arena; tl_arena = nullptr; int st = dev_records_alloc(ctx, u, a.n + unext.n, a.words + unext.words, kw); tl_arena = sv; RFX_TRY(st); }
-        const DevRecords *two[2] = {&a, &unext};
-        int64_t m = 0, w = 0;
-        for (int t = 0; t < 2; t++) {
-            const DevRecords &r = *two[t];
-            if (r.n > 0) {
-                RFX_HIP(hipMemcpyAsync(u.key.as<uint64_t>() + m * kw, r.key.p, (size_t)r.n * 8 * kw, hipMemcpyDeviceToDevice, ctx->stream));
-                RFX_HIP(hipMemcpyAsync(u.marker.as<int32_t>() + m, r.marker.p, (size_t)r.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-                RFX_HIP(hipMemcpyAsync(u.left.as<int32_t>() + m, r.left.p, (size_t)r.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-                RFX_HIP(hipMemcpyAsync(u.right.as<int32_t>() + m, r.right.p, (size_t)r.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-                if (r.words > 0) RFX_HIP(hipMemcpyAsync(u.ext.as<uint64_t>() + w, r.ext.p, (size_t)r.words * 8, hipMemcpyDeviceToDevice, ctx->stream));
-            }
-            m += r.n; w += r.words;
-        }
+        { ArenaOff off; RFX_TRY(dev_records_alloc(ctx, u, a.n + unext.n, a.words + unext.words, kw)); }
+        RFX_TRY(dev_records_copy(ctx, a, u));
+        RFX_TRY(dev_records_copy(ctx, unext, u, a.n, a.words));
         // ext_off of the union: built on the host (the sets are small by now)
         {
             std::vector<int64_t> ha((size_t)a.n + 1), hu((size_t)unext.n + 1), ho((size_t)(a.n + unext.n) + 1);
@@ -1307,52 +1239,91 @@ int rfx::assemble_impl(rfx_ctx *ctx, bool wide, const uint64_t *d_keys, const in
         u.n = a.n + unext.n; u.words = a.words + unext.words;
         // left ends: all forward, sort, longer-of-key; right ends: all reflected, sort, longer-of-key  (:689-707)
         DevBuf one;
-        { Arena *sv = tl_arena; tl_arena = nullptr; hipError_t e = one.alloc(16, ctx->stream); tl_arena = sv; RFX_HIP(e); }
+        { ArenaOff off; RFX_HIP(one.alloc(16, ctx->stream)); }
         const DevRecords *cur = &u;
         for (int side = 0; side < 2; side++) {
             int64_t h1[2] = {0, cur->n};
             RFX_HIP(hipMemcpyAsync(one.p, h1, 16, hipMemcpyHostToDevice, ctx->stream));
             RFX_TRY(sync_checked(ctx));
-            next_arena();
+            arenas.next();
             DevBuf ops1;
             RFX_TRY(extras_operator(ctx, side == 0 ? RFX_OP_ALL_FORWARD : RFX_OP_ALL_REFLECTED, *cur, one.as<int64_t>(), 1, k, b, ops1));
-            next_arena();
+            arenas.next();
             DevRecords srt;
             RFX_TRY(sort_records(ctx, b, P, key_bits, srt, ps, k));
-            next_arena();
+            arenas.next();
             RFX_TRY(extras_operator(ctx, RFX_OP_LONGER_OF_KEY, srt, ps.as<int64_t>(), P, k, a, ops));
             cur = &a;
             if (side == 0) { RFX_TRY(detach(a, u)); cur = &u; }                   // (a's arena is about to be reused)
         }
+        return RFX_OK;
     }
-    DevRecords *fin = &a;
-    if (wide) {                                                                   // 64 :714
-        next_arena();
-        RFX_TRY(sort_records(ctx, a, P, key_bits, b, ps, k));
-        fin = &b;
+
+    // the surviving records, sorted once more at k > 31 (64 :714), come down through the context's pinned staging block and
+    // become text; t_loop0: when the loop began (RFX_TRACE)
+    int finish(char *out, int64_t cap, int64_t *out_len, int64_t *out_contigs, double t_loop0) {
+        const DevRecords *fin = &a;
+        if (wide) {
+            arenas.next();
+            RFX_TRY(sort_records(ctx, a, loop.P, key_bits, b, ps, k));
+            fin = &b;
+        }
+        const double t_loop1 = verbose ? now_ms() : 0;
+        const int64_t hn = std::max<int64_t>(fin->n, 1), hw = std::max<int64_t>(fin->words, 1);
+        const size_t need = (size_t)hn * 8 * kw + (size_t)(hn + 1) * 8 + (size_t)hw * 8 + (size_t)hn * 12 + 64;
+        char *pin = (char *)ctx->pinned_get(need);
+        if (!pin) { ctx->last_error = "pinned staging allocation failed"; return RFX_E_HIP; }
+        rfx_records hv{};
+        hv.key = (uint64_t *)pin; pin += (size_t)hn * 8 * kw;
+        hv.ext_off = (int64_t *)pin; pin += (size_t)(hn + 1) * 8;
+        hv.ext = (uint64_t *)pin; pin += (size_t)hw * 8;
+        hv.marker = (int32_t *)pin; pin += (size_t)hn * 4;
+        hv.left = (int32_t *)pin; pin += (size_t)hn * 4;
+        hv.right = (int32_t *)pin;
+        hv.cap_n = fin->n; hv.cap_words = fin->words;
+        RFX_TRY(dev_records_download(ctx, *fin, &hv));
+        const double t_dl = verbose ? now_ms() : 0;
+        const int64_t len = contigs_text_host(&hv, k, prm->min_contig, twin, out, out ? cap : 0, out_contigs);
+        if (verbose) fprintf(stderr, "assemble: loop %.3f ms, download %.3f ms, text %.3f ms\n", t_loop1 - t_loop0, t_dl - t_loop1,
+                             now_ms() - t_dl);
+        *out_len = len;
+        return len > cap ? RFX_E_CAP : RFX_OK;
     }
-    const double t_loop1 = verbose ? now_ms() : 0;
-    // the surviving records come down through the context's pinned staging block
-    const DevRecords &a_fin = *fin;
-    const int64_t hn = std::max<int64_t>(a_fin.n, 1), hw = std::max<int64_t>(a_fin.words, 1);
-    const size_t need = (size_t)hn * 8 * kw + (size_t)(hn + 1) * 8 + (size_t)hw * 8 + (size_t)hn * 12 + 64;
-    char *pin = (char *)ctx->pinned_get(need);
-    if (!pin) { ctx->last_error = "pinned staging allocation failed"; return RFX_E_HIP; }
-    rfx_records hv{};
-    hv.key = (uint64_t *)pin; pin += (size_t)hn * 8 * kw;
-    hv.ext_off = (int64_t *)pin; pin += (size_t)(hn + 1) * 8;
-    hv.ext = (uint64_t *)pin; pin += (size_t)hw * 8;
-    hv.marker = (int32_t *)pin; pin += (size_t)hn * 4;
-    hv.left = (int32_t *)pin; pin += (size_t)hn * 4;
-    hv.right = (int32_t *)pin;
-    hv.cap_n = a_fin.n; hv.cap_words = a_fin.words;
-    RFX_TRY(dev_records_download(ctx, a_fin, &hv));
-    const double t_dl = verbose ? now_ms() : 0;
-    int64_t len = contigs_text_host(&hv, k, prm->min_contig, twin, out, out ? cap : 0, out_contigs);
-    if (verbose) fprintf(stderr, "assemble: loop %.3f ms, download %.3f ms, text %.3f ms\n", t_loop1 - t_loop0, t_dl - t_loop1,
-                         now_ms() - t_dl);
-    *out_len = len;
-    return len > cap ? RFX_E_CAP : RFX_OK;
+};
+
+}  // namespace
+
+// resume: the loop taken up where the sharded driver (rfx_shard.hip) left it -- its record set gathered on this rank in
+// global arrival order, the driver's variables as they stood.  d_keys / d_counts / n unused.
+int rfx::assemble_impl(rfx_ctx *ctx, bool wide, const uint64_t *d_keys, const int32_t *d_counts, int64_t n,
+                       const rfx_params *prm, char *out, int64_t cap, int64_t *out_len, int64_t *out_contigs,
+                       int64_t *trace, int64_t trace_cap, int64_t *n_trace, rfx::AsmResume *resume) {
+    if (!ctx || !prm || !out_len || n < 0) return RFX_E_ARG;
+    if (wide) { RFX_TRY(check_k_rec(prm->k)); if (prm->k <= 31) return RFX_E_ARG; }
+    else RFX_TRY(check_k(prm->k));
+    RFX_HIP(hipSetDevice(ctx->device));
+    AsmDriver d(ctx, wide, prm, trace, trace_cap);
+    const size_t recs = resume ? (size_t)(resume->recs->n + resume->recs->words) : (size_t)(2 * n);
+    if (!d.arenas.init(ctx, recs * (176 + 24 * (size_t)(d.kw - 1)) + ((size_t)64 << 20))) {
+        ctx->last_error = "workspace allocation failed";
+        return RFX_E_HIP;
+    }
+    const double t_enter = now_ms();
+    RFX_TRY(d.start(d_keys, d_counts, n, resume));
+    const double t_loop0 = d.verbose ? ((void)hipStreamSynchronize(ctx->stream), now_ms()) : 0;
+    if (d.verbose) fprintf(stderr, "assemble: stages before the loop %.3f ms\n", t_loop0 - t_enter);
+    for (int stage; (stage = asm_loop_before(d.loop)) >= 0;) RFX_TRY(d.one_pass(stage, 2));
+    while (asm_loop_open(d.loop, d.rule)) {                                       // :265 / 64 :582
+        { bool took; RFX_TRY(d.small_tail(&took)); if (took) break; }
+        // 64 :584-619 comes between the increment and the check, which then counts what the split left
+        if (d.extras && d.loop.iterations + 1 == prm->min_iter + 3) RFX_TRY(d.split());
+        const int start_marker = asm_loop_head(d.loop, d.rule, d.a.n);
+        if (!start_marker) break;
+        RFX_TRY(d.one_pass(2, start_marker));                                     // :286-291 / 64 :659-660, :667-669
+    }
+    if (n_trace) *n_trace = d.loop.nt;
+    if (d.split_done) RFX_TRY(d.unite());
+    return d.finish(out, cap, out_len, out_contigs, t_loop0);
 }
 
 extern "C" {

@@ -32,21 +32,11 @@
 
 using namespace rfx;
 
-namespace {
-
 #define DYN_KW PK_KW                        /* key words per record */
 #define DYN_MAXB 4                          // 31-base blocks per key: keys up to 124 bases (the reference's k-mer list ends at 95)
 #define DYN_MAXK (31 * DYN_MAXB)
 
 // (DynDev, DynView, DynOut, dyn_view and dyn_out: rfx_internal.h -- rfx_ksort.hip works on the same sets)
-static void buf_swap(DevBuf &x, DevBuf &y) { std::swap(x.p, y.p); std::swap(x.s, y.s); std::swap(x.borrowed, y.borrowed); }
-static void dyn_swap(DynDev &x, DynDev &y) {
-    std::swap(x.n, y.n); std::swap(x.words, y.words);
-    buf_swap(x.key, y.key); buf_swap(x.key_len, y.key_len); buf_swap(x.ext, y.ext); buf_swap(x.ext_off, y.ext_off);
-    buf_swap(x.ext_len, y.ext_len); buf_swap(x.marker, y.marker); buf_swap(x.left, y.left); buf_swap(x.right, y.right);
-}
-
-}  // namespace
 // (the functions defined as rfx::... are the ones rfx_ksort.hip shares: rfx_internal.h declares them)
 int rfx::dyn_alloc(rfx_ctx *ctx, DynDev &d, int64_t n, int64_t words) {
     const size_t m = (size_t)std::max<int64_t>(n, 1);
@@ -911,7 +901,7 @@ static int dyn_run(rfx_ctx *ctx, DynDev &a, int P, int random_reflection, int pa
         RFX_TRY(sync_checked(ctx));
         DynDev b;
         RFX_TRY(dyn_reflect(ctx, a, ps.as<int64_t>(), P, b));
-        dyn_swap(a, b);
+        std::swap(a, b);
     }
     auto one = [&](int stage, int start_it) -> int {
         uint32_t lmin = 0;
@@ -920,7 +910,7 @@ static int dyn_run(rfx_ctx *ctx, DynDev &a, int P, int random_reflection, int pa
         DynDev o;
         RFX_TRY(dyn_pass(ctx, s, ps.as<int64_t>(), P, lmin, stage, start_it, 2, o, nullptr));
         RFX_TRY(sync_checked(ctx));
-        dyn_swap(a, o);
+        std::swap(a, o);
         if (trace && nt < trace_cap) trace[nt] = a.n;
         nt++;
         return RFX_OK;

@@ -418,15 +418,17 @@ constexpr int SP_W = SP_T / 64;
 constexpr int SP_MAXP = 1024;           // logical partitions the single workgroup handles
 
 struct SmallState {
-    int64_t n, words, contig_number, nt;
-    int32_t iterations, scramble, P, partition_number, cur, io, done, status, start_marker, pad;
+    int64_t n;                  // records in the current set
+    rfx::AsmLoop loop;          // the driver's variables (its nt is the caller's: not touched here)
+    int32_t cur, io, done, status, start_marker, pad;
+    int64_t words, nt;          // words in the current set; trace entries of THIS call
 };
 struct SmallSet { void *key; int32_t *marker; int64_t *ext_off; uint64_t *ext; int32_t *left; int32_t *right; };
 struct SmallScratch {
     void *skey; int32_t *smarker, *sleft, *sright; uint32_t *slen; int64_t *sext;
     Desc *desc; uint32_t *flag, *onw; uint64_t *oidx, *owoff; int64_t *ps; int *status;
 };
-struct SmallRule { int wide, coalesce, min_iter, max_iter, twin, sub, res_bits; int64_t trace_cap; };
+struct SmallRule { rfx::AsmRule rule; int twin, sub, res_bits; int64_t trace_cap; };
 
 template <int KW>
 __global__ __launch_bounds__(SP_T) void k_small_pass(SmallSet A, SmallSet B, SmallScratch sc, SmallState *__restrict__ st,
@@ -439,34 +441,14 @@ __global__ __launch_bounds__(SP_T) void k_small_pass(SmallSet A, SmallSet B, Sma
     __shared__ int sh_go, sh_P, sh_start;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) {
-        // the driver's loop head: P/ReflexivMain.java:265-283 (k <= 31), P/ReflexivDSMain64.java:582, 621-655 (k > 31)
+        // the driver's loop head (rfx_asm_loop.h); passes queued after a stop find `done` set
         int go = 0;
         if (!st->done) {
-            if (st->iterations <= rule.max_iter) {
-                st->iterations++;
-                go = 1;
-                const int64_t current = st->n;
-                if (!rule.wide) {
-                    if (st->iterations >= rule.min_iter && st->iterations % 3 == 0) {
-                        if (st->contig_number == current) go = 0;
-                        else {
-                            st->contig_number = current;
-                            if (rule.coalesce && st->partition_number >= 16 && current / st->partition_number <= 20) {
-                                st->partition_number = st->partition_number / 4 + 1;
-                                st->P = st->partition_number;
-                            }
-                        }
-                    }
-                } else if (st->iterations >= rule.min_iter + 3 && st->iterations % 3 == 0) {
-                    if (st->contig_number == current) {
-                        if (st->scramble == 2) st->scramble = 3; else go = 0;
-                    } else st->contig_number = current;
-                }
-            }
+            go = rfx::asm_loop_head(st->loop, rule.rule, st->n);
             if (!go) st->done = 1;
         }
-        if (go) { st->io = st->cur; st->start_marker = (rule.wide && st->scramble == 3) ? 1 : 2; }
-        sh_go = go; sh_P = st->P; sh_start = st->start_marker;
+        if (go) { st->io = st->cur; st->start_marker = go; }
+        sh_go = go; sh_P = st->loop.P; sh_start = st->start_marker;
     }
     __syncthreads();
     if (!sh_go) return;
@@ -607,7 +589,7 @@ __global__ void k_small_words(SmallSet A, SmallSet B, SmallScratch sc, const Sma
     const SmallSet &in = st->io ? B : A;
     const SmallSet &out = st->io ? A : B;
     // the scans' last entries hold this pass's record count / word total; n_in = number of descriptors = ps[P]
-    const int P = st->P;
+    const int P = st->loop.P;
     const int64_t n_in = sc.ps[P];
     emit_word_at<KW>((int64_t)blockIdx.x * blockDim.x + threadIdx.x, sc.desc, sc.oidx, sc.owoff, n_in, sc.ps, P, sub, st->start_marker, nullptr,
                      (const KeyW<KW> *)sc.skey, sc.smarker, sc.sext, in.ext, sc.slen, out.ext);
@@ -882,14 +864,12 @@ int extras_operator(rfx_ctx *ctx, int op, const DevRecords &in, const int64_t *d
 }
 
 // Runs the rest of the driver's loop (P/ReflexivMain.java:265-296; k > 31: P/ReflexivDSMain64.java:582-670) on a record set of
-// at most SP_N records: see k_small_pass.  io: iterations / contig_number / scramble / P / partition_number as the host
-// loop left them; on return they are what the loop would have left, `recs` holds the surviving records and the trace has
-// grown by the passes run.
-int small_passes(rfx_ctx *ctx, DevRecords &recs, int k, int twin, bool wide, int coalesce, int min_iter, int max_iter,
-                 int *iterations, int64_t *contig_number, int *scramble, int *P, int *partition_number,
-                 int64_t *trace, int64_t trace_cap, int64_t *nt) {
+// at most SP_N records: see k_small_pass.  loop: the variables as the host loop left them; on return they are what the loop
+// would have left, `recs` holds the surviving records and the trace has grown by the passes run.
+int small_passes(rfx_ctx *ctx, DevRecords &recs, int k, int twin, AsmLoop &loop, const AsmRule &rule, int64_t *trace,
+                 int64_t trace_cap) {
     const int kw = recs.kw, sub = k - 1;
-    if (recs.n > SP_N || *P > SP_MAXP || *P < 1) return RFX_E_ARG;
+    if (recs.n > SP_N || loop.P > SP_MAXP || loop.P < 1) return RFX_E_ARG;
     const int64_t capn = recs.n > 0 ? recs.n : 1, capw = recs.words > 0 ? recs.words : 1;
     DevRecords other;
     RFX_TRY(dev_records_alloc(ctx, other, capn, capw, kw));
@@ -902,12 +882,11 @@ int small_passes(rfx_ctx *ctx, DevRecords &recs, int k, int twin, bool wide, int
     RFX_ALLOC(oidx, uint64_t, capn + 1); RFX_ALLOC(owoff, uint64_t, capn + 1);
     RFX_ALLOC(ps, int64_t, SP_MAXP + 1); RFX_HIP(status.alloc(4, ctx->stream));
     RFX_HIP(state.alloc(sizeof(SmallState), ctx->stream));
-    const int64_t tcap = max_iter + 8;
+    const int64_t tcap = rule.max_iter + 8;
     RFX_ALLOC(dtrace, int64_t, tcap);
     SmallState h{};
-    h.n = recs.n; h.words = recs.words; h.contig_number = *contig_number; h.nt = 0;
-    h.iterations = *iterations; h.scramble = *scramble; h.P = *P; h.partition_number = *partition_number;
-    h.cur = 0; h.io = 0; h.done = 0; h.status = 0; h.start_marker = 2;
+    h.n = recs.n; h.words = recs.words; h.loop = loop;
+    h.start_marker = 2;
     RFX_HIP(hipMemcpyAsync(state.p, &h, sizeof h, hipMemcpyHostToDevice, ctx->stream));
     const SmallSet A{recs.key.p, recs.marker.as<int32_t>(), recs.ext_off.as<int64_t>(), recs.ext.as<uint64_t>(),
                      recs.left.as<int32_t>(), recs.right.as<int32_t>()};
@@ -917,12 +896,12 @@ int small_passes(rfx_ctx *ctx, DevRecords &recs, int k, int twin, bool wide, int
                           sext.as<int64_t>(), desc.as<Desc>(), flag.as<uint32_t>(), onw.as<uint32_t>(), oidx.as<uint64_t>(),
                           owoff.as<uint64_t>(), ps.as<int64_t>(), status.as<int>()};
     const int res = sub - 31 * (kw - 1);
-    const SmallRule rule{wide ? 1 : 0, coalesce, min_iter, max_iter, twin, sub, 2 * res, tcap};
+    const SmallRule srule{rule, twin, sub, 2 * res, tcap};
     constexpr int BATCH = 6;                 // passes queued between two looks at the state (two checks of the stop rule)
     int64_t words_bound = recs.words;
     for (;;) {
         for (int b = 0; b < BATCH; b++) {
-            RFX_KW_SWITCH(kw, RFX_LAUNCH(k_small_pass<KW>, dim3(1), dim3(SP_T), 0, A, B, sc, state.as<SmallState>(), rule,
+            RFX_KW_SWITCH(kw, RFX_LAUNCH(k_small_pass<KW>, dim3(1), dim3(SP_T), 0, A, B, sc, state.as<SmallState>(), srule,
                                          dtrace.as<int64_t>()));
             if (words_bound > 0) {
                 RFX_KW_SWITCH(kw, RFX_LAUNCH_N(k_small_words<KW>, words_bound, A, B, sc,
@@ -932,7 +911,7 @@ int small_passes(rfx_ctx *ctx, DevRecords &recs, int k, int twin, bool wide, int
         RFX_HIP(hipMemcpyAsync(&h, state.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
         RFX_TRY(sync_checked(ctx));
         words_bound = h.words;                // the word total never grows from pass to pass
-        if (h.done || h.iterations > max_iter) break;
+        if (h.done || !asm_loop_open(h.loop, rule)) break;
     }
     if (h.status) { ctx->last_error = "extend pass: impossible record state"; return RFX_E_STATE; }
     std::vector<int64_t> ht((size_t)(h.nt > 0 ? h.nt : 1));
@@ -940,18 +919,10 @@ int small_passes(rfx_ctx *ctx, DevRecords &recs, int k, int twin, bool wide, int
         RFX_HIP(hipMemcpyAsync(ht.data(), dtrace.p, (size_t)h.nt * 8, hipMemcpyDeviceToHost, ctx->stream));
         RFX_TRY(sync_checked(ctx));
     }
-    for (int64_t i = 0; i < h.nt; i++) { if (trace && *nt < trace_cap) trace[*nt] = ht[(size_t)i]; (*nt)++; }
-    if (h.cur == 1) {        // the survivors are in the second set: hand its buffers over
-        std::swap(recs.key.p, other.key.p); std::swap(recs.key.borrowed, other.key.borrowed); std::swap(recs.key.s, other.key.s);
-        std::swap(recs.marker.p, other.marker.p); std::swap(recs.marker.borrowed, other.marker.borrowed); std::swap(recs.marker.s, other.marker.s);
-        std::swap(recs.ext_off.p, other.ext_off.p); std::swap(recs.ext_off.borrowed, other.ext_off.borrowed); std::swap(recs.ext_off.s, other.ext_off.s);
-        std::swap(recs.ext.p, other.ext.p); std::swap(recs.ext.borrowed, other.ext.borrowed); std::swap(recs.ext.s, other.ext.s);
-        std::swap(recs.left.p, other.left.p); std::swap(recs.left.borrowed, other.left.borrowed); std::swap(recs.left.s, other.left.s);
-        std::swap(recs.right.p, other.right.p); std::swap(recs.right.borrowed, other.right.borrowed); std::swap(recs.right.s, other.right.s);
-    }
+    loop = h.loop;                                 // (its nt came back as it went)
+    for (int64_t i = 0; i < h.nt; i++) { if (trace && loop.nt < trace_cap) trace[loop.nt] = ht[(size_t)i]; loop.nt++; }
+    if (h.cur == 1) std::swap(recs, other);        // the survivors are in the second set: hand its buffers over
     recs.n = h.n; recs.words = h.words;
-    *iterations = h.iterations; *contig_number = h.contig_number; *scramble = h.scramble; *P = h.P;
-    *partition_number = h.partition_number;
     return RFX_OK;
 }
 

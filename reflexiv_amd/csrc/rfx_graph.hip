@@ -471,6 +471,19 @@ int dev_records_alloc(rfx_ctx *ctx, DevRecords &r, int64_t cap_n, int64_t cap_wo
     return RFX_OK;
 }
 
+int dev_records_copy(rfx_ctx *ctx, const DevRecords &src, DevRecords &dst, int64_t record_at, int64_t word_at) {
+    const int64_t n = src.n;
+    const int kw = src.kw;
+    if (n <= 0) return RFX_OK;
+    RFX_HIP(hipMemcpyAsync(dst.key.as<uint64_t>() + record_at * kw, src.key.p, (size_t)n * 8 * kw, hipMemcpyDeviceToDevice, ctx->stream));
+    RFX_HIP(hipMemcpyAsync(dst.marker.as<int32_t>() + record_at, src.marker.p, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    RFX_HIP(hipMemcpyAsync(dst.left.as<int32_t>() + record_at, src.left.p, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    RFX_HIP(hipMemcpyAsync(dst.right.as<int32_t>() + record_at, src.right.p, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    if (src.words > 0)
+        RFX_HIP(hipMemcpyAsync(dst.ext.as<uint64_t>() + word_at, src.ext.p, (size_t)src.words * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    return RFX_OK;
+}
+
 int dev_records_upload(rfx_ctx *ctx, const rfx_records *h, DevRecords &d) {
     const int64_t n = h->n;
     const int64_t words = n > 0 ? h->ext_off[n] : 0;

@@ -12,6 +12,7 @@
 #include <vector>
 #include <map>
 #include "../../include/reflexiv_hip.h"
+#include "rfx_asm_loop.h"
 
 struct rfx_timing_slot { float ms = 0.f; int64_t launches = 0; };
 // a kernel timer that has been stopped and not yet read (ScopedTimer below): events of the context's own pool
@@ -215,6 +216,7 @@ struct DevBuf {
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), s(o.s), borrowed(o.borrowed) { o.p = nullptr; o.borrowed = false; }
     DevBuf &operator=(DevBuf &&o) noexcept {
         if (this != &o) { release(); p = o.p; s = o.s; borrowed = o.borrowed; o.p = nullptr; o.borrowed = false; }
         return *this;
@@ -261,6 +263,35 @@ struct StageArena {
     ~StageArena() { if (on) tl_arena = prev; }
     StageArena(const StageArena &) = delete;
     StageArena &operator=(const StageArena &) = delete;
+};
+
+// The two alternating bump arenas of the extend drivers (workspace slots 2 and 3, `bytes` each): next() turns to the other
+// one and empties it, so what the step before allocated stays valid for exactly one more step.  No arena once it is gone.
+struct ArenaPair {
+    Arena arena[2];
+    int turn = 0;
+    Arena *prev;
+    ArenaPair() : prev(tl_arena) {}
+    ~ArenaPair() { tl_arena = prev; }
+    ArenaPair(const ArenaPair &) = delete;
+    ArenaPair &operator=(const ArenaPair &) = delete;
+    bool init(rfx_ctx *ctx, size_t bytes) {
+        for (int i = 0; i < 2; i++) {
+            arena[i].base = (char *)ctx->ws_get(2 + i, bytes);
+            if (!arena[i].base) return false;
+            arena[i].cap = bytes;
+        }
+        return true;
+    }
+    void next() { Arena *a = &arena[turn++ & 1]; a->off = 0; tl_arena = a; }
+};
+// No arena inside this block: what is allocated here comes from the stream-ordered allocator and outlives the arenas' turns.
+struct ArenaOff {
+    Arena *prev;
+    ArenaOff() : prev(tl_arena) { tl_arena = nullptr; }
+    ~ArenaOff() { tl_arena = prev; }
+    ArenaOff(const ArenaOff &) = delete;
+    ArenaOff &operator=(const ArenaOff &) = delete;
 };
 
 // Event pair that accumulates into ctx->timing[name].
@@ -418,6 +449,9 @@ constexpr int MAX_KEY_WORDS = 4;                                           // k 
 int dev_records_alloc(rfx_ctx *ctx, DevRecords &r, int64_t cap_n, int64_t cap_words, int kw = 1);
 int dev_records_upload(rfx_ctx *ctx, const rfx_records *h, DevRecords &d);
 int dev_records_download(rfx_ctx *ctx, const DevRecords &d, rfx_records *h);
+// the fixed fields and the extension words of `src` into `dst` from record `record_at` / word `word_at` on (queued; ext_off, n
+// and words of `dst` are the caller's: only a copy to the front keeps the offsets)
+int dev_records_copy(rfx_ctx *ctx, const DevRecords &src, DevRecords &dst, int64_t record_at = 0, int64_t word_at = 0);
 
 int rc_expand_subkmer(rfx_ctx *ctx, const uint64_t *d_kmers, const int32_t *d_counts, int64_t n,
                       int k, DevRecords &out);
@@ -450,20 +484,15 @@ int extras_operator(rfx_ctx *ctx, int op, const DevRecords &in, const int64_t *d
                     DevBuf &out_part_start);
 // the driver (rfx_api.hip), and the state with which the sharded driver (rfx_shard.hip) hands its loop over to it
 struct AsmResume {
-    DevRecords *recs;            // the record set, in global arrival order (its buffers are taken over)
-    int passes_done;             // extend passes behind it (0..4: the passes before the loop are still to come)
-    int iterations;
-    int64_t contig_number;
-    int scramble, P, partition_number;
-    int64_t nt;                  // trace entries already written
+    DevRecords *recs;            // the record set, in global arrival order (taken over)
+    AsmLoop loop;                // the loop's variables as they stood (passes_done 0..4: passes before the loop are still to come)
 };
 int assemble_impl(rfx_ctx *ctx, bool wide, const uint64_t *d_keys, const int32_t *d_counts, int64_t n, const rfx_params *prm,
                   char *out, int64_t cap, int64_t *out_len, int64_t *out_contigs, int64_t *trace, int64_t trace_cap,
                   int64_t *n_trace, AsmResume *resume);
 // the rest of the driver's loop on <= small_pass_limit() records: two launches per pass, state in HBM (rfx_extend.hip)
-int small_passes(rfx_ctx *ctx, DevRecords &recs, int k, int twin, bool wide, int coalesce, int min_iter, int max_iter,
-                 int *iterations, int64_t *contig_number, int *scramble, int *P, int *partition_number,
-                 int64_t *trace, int64_t trace_cap, int64_t *nt);
+int small_passes(rfx_ctx *ctx, DevRecords &recs, int k, int twin, AsmLoop &loop, const AsmRule &rule, int64_t *trace,
+                 int64_t trace_cap);
 int small_pass_limit();
 int small_pass_max_partitions();
 

@@ -248,8 +248,7 @@ struct Shard : PartCarry {
     // device scratch of the communicator (grow-only): rows, samples, splitters, cuts, carry
     int64_t *d = nullptr, *h = nullptr;
     int S = 256;
-    Arena arena[2];
-    int turn = 0;
+    ArenaPair arenas;
     // statistics of the call (RFX_TRACE)
     int64_t exchanged_records = 0, exchanged_words = 0;
     int n_exchanges = 0;
@@ -284,14 +283,13 @@ struct Shard : PartCarry {
                 arena_bytes = std::min(arena_bytes, (free_b + held) / 3);
             }
         }
-        for (int i = 0; i < 2; i++) {
-            arena[i].base = (char *)ctx->ws_get(2 + i, arena_bytes);
-            if (!arena[i].base) { ctx->last_error = "rfx_dev_sharded_assemble: workspace allocation failed"; return RFX_E_HIP; }
-            arena[i].cap = arena_bytes;
-        }
+        if (!arenas.init(ctx, arena_bytes)) { ctx->last_error = "rfx_dev_sharded_assemble: workspace allocation failed"; return RFX_E_HIP; }
         return RFX_OK;
     }
-    void next_arena() { Arena *a = &arena[turn++ & 1]; a->off = 0; tl_arena = a; }
+    // after a failure of this rank's own: the set it goes on with is empty (the peers still meet every collective)
+    void drop_if_failed(DevRecords &r, int kw) const {
+        if (st_local != RFX_OK) { r.n = 0; r.words = 0; r.kw = kw; }
+    }
 
     // ---- collective: RFX_OK only if every rank says so (a tiny all-reduce; used where no matrix travels anyway)
     int agree(const char *what) {
@@ -421,12 +419,12 @@ struct Shard : PartCarry {
         const int kw = in.kw;
         DevRecords sorted, merged;
         DevBuf ps0;
-        next_arena();
+        arenas.next();
         if (st_local == RFX_OK) {
             const int s1 = sort_records(ctx, in, 1, key_bits, sorted, ps0, k_eff);
             if (s1 != RFX_OK) st_local = s1;
         }
-        if (st_local != RFX_OK) { sorted.n = 0; sorted.words = 0; sorted.kw = kw; }
+        drop_if_failed(sorted, kw);
         room_to_send(sorted.n, kw);
         // sample -> splitters -> cuts -> this rank's row of the matrix, all on the device
         auto plan = [&]() -> int {
@@ -450,10 +448,10 @@ struct Shard : PartCarry {
             const int sc = cuts();
             if (sc != RFX_OK) st_local = sc;
         }
-        next_arena();                                     // (`in` is dead: its arena takes what arrives)
+        arenas.next();                                    // (`in` is dead: its arena takes what arrives)
         int64_t N = 0, off = 0;
         RFX_TRY(exchange(sorted, kw, merged, &N, &off));
-        next_arena();                                     // (`sorted` is dead once the exchange, stream-ordered before us, has read it)
+        arenas.next();                                    // (`sorted` is dead once the exchange, stream-ordered before us, has read it)
         if (st_local == RFX_OK) {
             auto fin = [&]() -> int {
                 RFX_TRY(sort_records(ctx, merged, 1, key_bits, out, ps0, k_eff));
@@ -467,7 +465,7 @@ struct Shard : PartCarry {
             const int sf = fin();
             if (sf != RFX_OK) st_local = sf;
         }
-        if (st_local != RFX_OK) { out.n = 0; out.words = 0; out.kw = kw; }
+        drop_if_failed(out, kw);
         if (N_out) *N_out = N;
         return RFX_OK;
     }
@@ -486,16 +484,36 @@ struct Shard : PartCarry {
         for (int i = 0; i < 2 * (W + 1); i++) h[o_aux() + i] = aux[i];
         RFX_HIP(hipMemcpyAsync(d + o_row(), h + o_row(), (size_t)(2 * W) * 8, hipMemcpyHostToDevice, ctx->stream));
         RFX_HIP(hipMemcpyAsync(d + o_aux(), h + o_aux(), (size_t)(2 * W + 2) * 8, hipMemcpyHostToDevice, ctx->stream));
-        Arena *saved = tl_arena;
-        tl_arena = nullptr;
+        ArenaOff outside;
         int64_t N = 0, off = 0;
         DevRecords empty;
         empty.kw = kw;
-        const int st = exchange(st_local == RFX_OK ? in : empty, kw, dst, &N, &off);
-        tl_arena = saved;
-        return st;
+        return exchange(st_local == RFX_OK ? in : empty, kw, dst, &N, &off);
     }
 };
+
+// Rank 0 runs the one-GPU driver (`drive`, which fills the length, the contig count and the trace count); then every rank
+// learns its outcome: a short text buffer is RFX_E_CAP on EVERY rank with the length needed, so that the callers' retries
+// stay collective.  The driver brings its own arenas.
+template <class Drive>
+int rank0_drives(rfx_ctx *ctx, rfx_comm *c, int64_t *out_len, int64_t *out_contigs, int64_t *n_trace, Drive drive) {
+    ArenaOff outside;
+    int64_t len = 0, ncont = 0, ntr = 0;
+    int st_asm = RFX_OK;
+    if (c->rank == 0) {
+        try { st_asm = drive(&len, &ncont, &ntr); } catch (...) { st_asm = rfx_api_exception(ctx, "rfx_dev_sharded_assemble"); }
+    }
+    int64_t res[3] = {st_asm == RFX_E_CAP ? 1 : 0, st_asm == RFX_E_CAP ? len : 0, (st_asm != RFX_OK && st_asm != RFX_E_CAP) ? 1 : 0};
+    RFX_TRY(rfx_comm_all_reduce_i64(c, res, 3, 1));
+    if (res[2]) {
+        if (st_asm != RFX_OK) return st_asm;
+        ctx->last_error = "rfx_dev_sharded_assemble: the driver failed on rank 0; see its rfx_last_error()";
+        return RFX_E_STATE;
+    }
+    if (res[0]) { *out_len = res[1]; return RFX_E_CAP; }
+    if (c->rank == 0) { *out_len = len; if (out_contigs) *out_contigs = ncont; if (n_trace) *n_trace = ntr; }
+    return RFX_OK;
+}
 
 }  // namespace
 
@@ -522,7 +540,10 @@ int rfx_dev_sharded_assemble(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_keys, 
         gather_below = e ? atoll(e) : (int64_t)32 << 20;
     }
     const int twin = wide ? RFX_TWIN_DS : prm->twin;
-    int P = prm->partitions > 0 ? prm->partitions : 1;
+    // the driver's variables (rfx_asm_loop.h); P: the partitions of the stages before the loop
+    AsmLoop loop;
+    const int P = loop.P = loop.partition_number = prm->partitions > 0 ? prm->partitions : 1;
+    const AsmRule rule{wide ? 1 : 0, prm->coalesce, prm->min_iter, prm->max_iter};
     const int key_bits = 2 * (k - 1);
     const bool verbose = getenv("RFX_TRACE") != nullptr;
 
@@ -536,14 +557,9 @@ int rfx_dev_sharded_assemble(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_keys, 
         const int64_t share = (2 * n_all) / c->world + (2 * n_all) / (4 * c->world) + (1 << 16);
         RFX_TRY(sh.init((size_t)std::max<int64_t>(share, 2 * n) * (176 + 24 * (size_t)(std::max(kw, aw) - 1)) + ((size_t)64 << 20)));
     }
-    struct ArenaGuard { ~ArenaGuard() { tl_arena = nullptr; } } arena_guard;
-    int64_t nt = 0;
     DevRecords a, b;
     DevBuf ps, ops;
-
-    // the driver's variables (rfx_api.hip assemble_impl)
-    int passes_done = 0, iterations = 0, partitionNumber = P, scramble = 2;
-    int64_t contigNumber = 0, n_glob = 0;
+    int64_t n_glob = 0;
     const bool extras = wide && prm->extras != 0;
 
     // a local step whose failure is this rank's own: remembered, not returned (the peers are waiting at the next collective)
@@ -552,18 +568,9 @@ int rfx_dev_sharded_assemble(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_keys, 
         if (sh.st_local == RFX_OK) { const int s_ = (call); if (s_ != RFX_OK) sh.st_local = s_; } \
     } while (0)
 
-    bool gathered = false;
-    DevRecords fin;                                   // the set on rank 0 once gathered
-    auto gather_now = [&](const DevRecords &r) -> int {
-        RFX_TRY(sh.gather_to_root(r, fin));
-        RFX_TRY(sh.agree("gather"));
-        gathered = true;
-        return RFX_OK;
-    };
-
     // 0. the count stage's order contract: ascending canonical k-mer over the ranks -> range-shard the survivors first
     //    (as records: key = the k-mer, marker = its count, one dummy extension word)
-    sh.next_arena();
+    sh.arenas.next();
     DevRecords kr;
     {
         auto make = [&]() -> int {
@@ -580,7 +587,7 @@ int rfx_dev_sharded_assemble(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_keys, 
             return RFX_OK;
         };
         SH_LOCAL(make());
-        if (sh.st_local != RFX_OK) { kr.n = 0; kr.words = 0; kr.kw = aw; }
+        sh.drop_if_failed(kr, aw);
     }
     if (2 * n_all <= gather_below) {
         // few enough from the start (a bacterial genome: D' << N): the survivors themselves go to rank 0, are put in
@@ -588,64 +595,50 @@ int rfx_dev_sharded_assemble(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_keys, 
         DevRecords all_k;
         RFX_TRY(sh.gather_to_root(kr, all_k));
         RFX_TRY(sh.agree("gather of the survivors"));
-        tl_arena = nullptr;
-        int64_t len = 0, ncont = 0, ntr = 0;
-        int st_asm = RFX_OK;
-        if (sh.me == 0) {
-            auto drive = [&]() -> int {
-                DevRecords ks;
-                DevBuf ps0;
-                RFX_TRY(sort_records(ctx, all_k, 1, 2 * k, ks, ps0, k + 1));
-                return assemble_impl(ctx, wide, ks.key.as<uint64_t>(), ks.marker.as<int32_t>(), ks.n, prm, out, cap, &len, &ncont, trace, trace_cap, &ntr, nullptr);
-            };
-            try { st_asm = drive(); } catch (...) { st_asm = rfx_api_exception(ctx, "rfx_dev_sharded_assemble"); }
-        }
-        int64_t res[3] = {st_asm == RFX_E_CAP ? 1 : 0, st_asm == RFX_E_CAP ? len : 0, (st_asm != RFX_OK && st_asm != RFX_E_CAP) ? 1 : 0};
-        RFX_TRY(rfx_comm_all_reduce_i64(c, res, 3, 1));
-        if (res[2]) {
-            if (st_asm != RFX_OK) return st_asm;
-            ctx->last_error = "rfx_dev_sharded_assemble: the driver failed on rank 0; see its rfx_last_error()";
-            return RFX_E_STATE;
-        }
-        if (res[0]) { *out_len = res[1]; return RFX_E_CAP; }
-        if (sh.me == 0) { *out_len = len; if (out_contigs) *out_contigs = ncont; if (n_trace) *n_trace = ntr; }
-        return RFX_OK;
+        return rank0_drives(ctx, c, out_len, out_contigs, n_trace, [&](int64_t *len, int64_t *ncont, int64_t *ntr) -> int {
+            DevRecords ks;
+            DevBuf ps0;
+            RFX_TRY(sort_records(ctx, all_k, 1, 2 * k, ks, ps0, k + 1));
+            return assemble_impl(ctx, wide, ks.key.as<uint64_t>(), ks.marker.as<int32_t>(), ks.n, prm, out, cap, len, ncont, trace, trace_cap, ntr, nullptr);
+        });
     }
     {
         DevRecords ks;
         int64_t Nk = 0;
         RFX_TRY(sh.sort_exchange(kr, 0, k + 1, 2 * k, ks, ps, &Nk));
         // KmerReverseComplement + ForwardSubKmerExtraction  :168-176 on this rank's range of the ascending list
-        sh.next_arena();
+        sh.arenas.next();
         SH_LOCAL(rc_expand_subkmer(ctx, ks.key.as<uint64_t>(), ks.marker.as<int32_t>(), ks.n, k, a));
-        if (sh.st_local != RFX_OK) { a.n = 0; a.words = 0; a.kw = kw; }
+        sh.drop_if_failed(a, kw);
     }
     const double t0 = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }();
     // sortByKey + FilterForkSubKmer[WithErrorCorrection]  :179-186
     RFX_TRY(sh.sort_exchange(a, P, k, key_bits, b, ps, &n_glob));
-    sh.next_arena();
+    sh.arenas.next();
     SH_LOCAL(fork_filter(ctx, false, b, ps.as<int64_t>(), P, k, prm->min_error_cov, twin, a, ops));
     // ReflectedSubKmerExtractionFromForward  :188-189
-    sh.next_arena();
+    sh.arenas.next();
     SH_LOCAL(reflect_from_forward(ctx, a, k, b));
-    if (sh.st_local != RFX_OK) { b.n = 0; b.words = 0; b.kw = kw; }
+    sh.drop_if_failed(b, kw);
     // sortByKey + FilterForkReflectedSubKmer[WithErrorCorrection]  :191-198
     RFX_TRY(sh.sort_exchange(b, P, k, key_bits, a, ps, &n_glob));
-    sh.next_arena();
+    sh.arenas.next();
     SH_LOCAL(fork_filter(ctx, true, a, ps.as<int64_t>(), P, k, prm->min_error_cov, twin, b, ops));
     // kmerRandomReflection on the filter's output partitions  :204-205 -- a partition that began on an earlier rank brings
     // the parity of its surviving records there
-    sh.next_arena();
+    sh.arenas.next();
     {
         const int32_t *d_carry = nullptr;
-        if (sh.st_local != RFX_OK) { b.n = 0; b.words = 0; b.kw = kw; RFX_ALLOC(ops, int64_t, P + 1); RFX_HIP(hipMemsetAsync(ops.p, 0, (size_t)(P + 1) * 8, ctx->stream)); }
+        sh.drop_if_failed(b, kw);
+        if (sh.st_local != RFX_OK) { RFX_ALLOC(ops, int64_t, P + 1); RFX_HIP(hipMemsetAsync(ops.p, 0, (size_t)(P + 1) * 8, ctx->stream)); }
         RFX_TRY(sh.compute(ctx, ops.as<int64_t>(), P, nullptr, b.n, &d_carry));
         SH_LOCAL(random_reflection(ctx, b, ops.as<int64_t>(), P, k, a, d_carry));
-        if (sh.st_local != RFX_OK) { a.n = 0; a.words = 0; a.kw = kw; }
+        sh.drop_if_failed(a, kw);
     }
 
     // one pass of the loop, sharded; -> the record count over all ranks (count() of the stop rule, the trace)
     auto one_pass = [&](int stage, int start_marker) -> int {
+        const int P = loop.P;                                                         // (the coalesce rule may have lowered it)
         RFX_TRY(sh.sort_exchange(a, P, k, key_bits, b, ps, nullptr));                 // sortByKey :211,:235,:247,:286
         if (sh.st_local != RFX_OK) {                                                  // (the carry's collective must still be met)
             const int32_t *dc = nullptr;
@@ -653,13 +646,14 @@ int rfx_dev_sharded_assemble(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_keys, 
             RFX_ALLOC(z, int64_t, P + 1);
             RFX_HIP(hipMemsetAsync(z.p, 0, (size_t)(P + 1) * 8, ctx->stream));
             RFX_TRY(sh.compute(ctx, z.as<int64_t>(), P, nullptr, 0, &dc));
-            a.n = 0; a.words = 0; a.kw = kw;
+            sh.drop_if_failed(a, kw);
         } else {
-            sh.next_arena();
+            sh.arenas.next();
             const int before = sh.carry_slot;
             const int se = extend_pass(ctx, b, ps.as<int64_t>(), P, k, twin, stage, a, ops, start_marker, &sh);
             if (se != RFX_OK) {
-                sh.st_local = se; a.n = 0; a.words = 0; a.kw = kw;
+                sh.st_local = se;
+                sh.drop_if_failed(a, kw);
                 if (sh.carry_slot == before) {                                    // the pass failed before its carry: the peers are in that all-gather
                     const int32_t *dc = nullptr;
                     RFX_ALLOC(ops, int64_t, P + 1);
@@ -673,10 +667,10 @@ int rfx_dev_sharded_assemble(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_keys, 
         if (sh.st_local != RFX_OK) return sh.st_local;
         if (v[2]) { ctx->last_error = "rfx_dev_sharded_assemble: a peer failed in an extend pass; see its rfx_last_error()"; return RFX_E_STATE; }
         n_glob = v[0];
-        if (trace && nt < trace_cap) trace[nt] = n_glob;
-        nt++;
-        passes_done++;
-        if (verbose && sh.me == 0) fprintf(stderr, "sharded pass %d: %lld records on all ranks (%lld here)\n", passes_done, (long long)n_glob, (long long)a.n);
+        if (trace && loop.nt < trace_cap) trace[loop.nt] = n_glob;
+        loop.nt++;
+        loop.passes_done++;
+        if (verbose && sh.me == 0) fprintf(stderr, "sharded pass %d: %lld records on all ranks (%lld here)\n", loop.passes_done, (long long)n_glob, (long long)a.n);
         return RFX_OK;
     };
     // records on all ranks before the first pass
@@ -687,62 +681,32 @@ int rfx_dev_sharded_assemble(rfx_ctx *ctx, rfx_comm *c, const uint64_t *d_keys, 
         if (v[1]) { ctx->last_error = "rfx_dev_sharded_assemble: a peer failed before the loop; see its rfx_last_error()"; return RFX_E_STATE; }
         n_glob = v[0];
     }
-    // the five passes before the loop (:221-254), then the loop (:265-296; k > 31: 64 :582-661) -- sharded while the set is large
-    while (!gathered) {
-        if (n_glob <= gather_below) { RFX_TRY(gather_now(a)); break; }
-        if (passes_done < 5) {
-            if (passes_done >= 1) iterations++;
-            RFX_TRY(one_pass(passes_done < 4 ? 0 : 1, 2));
-            continue;
-        }
-        if (iterations > prm->max_iter) { RFX_TRY(gather_now(a)); break; }
-        if (extras && iterations + 1 >= prm->min_iter + 3) { RFX_TRY(gather_now(a)); break; }     // 64 :584-619 wants the whole set
-        // (from here on the one-GPU driver's loop, statement for statement, on global counts)
-        iterations++;
-        bool stop = false;
-        if (wide) {
-            if (iterations >= prm->min_iter + 3 && iterations % 3 == 0) {         // 64 :621-647
-                if (contigNumber == n_glob) { if (scramble == 2) { scramble = 3; contigNumber = n_glob; } else stop = true; }
-                else contigNumber = n_glob;
-            }
-        } else if (iterations >= prm->min_iter && iterations % 3 == 0) {          // :267-283
-            if (contigNumber == n_glob) stop = true;
-            else {
-                contigNumber = n_glob;
-                if (prm->coalesce && partitionNumber >= 16 && n_glob / partitionNumber <= 20) { partitionNumber = partitionNumber / 4 + 1; P = partitionNumber; }
-            }
-        }
-        if (stop) { iterations = prm->max_iter + 1; RFX_TRY(gather_now(a)); break; }     // (the resumed driver runs no further pass)
-        RFX_TRY(one_pass(2, wide && scramble == 3 ? 1 : 2));
+    // the five passes before the loop, then the loop (rfx_asm_loop.h), decided on the count over all ranks -- sharded while
+    // the set is large; every way out of it leads to the one gather
+    for (;;) {
+        if (n_glob <= gather_below) break;
+        const int stage = asm_loop_before(loop);
+        if (stage >= 0) { RFX_TRY(one_pass(stage, 2)); continue; }
+        if (!asm_loop_open(loop, rule)) break;
+        if (extras && loop.iterations + 1 >= prm->min_iter + 3) break;                // 64 :584-619 wants the whole set
+        const int start_marker = asm_loop_head(loop, rule, n_glob);
+        if (!start_marker) { loop.iterations = prm->max_iter + 1; break; }            // (the resumed driver runs no further pass)
+        RFX_TRY(one_pass(2, start_marker));
     }
+    DevRecords fin;                                   // the set on rank 0
+    RFX_TRY(sh.gather_to_root(a, fin));
+    RFX_TRY(sh.agree("gather"));
     if (verbose && sh.me == 0) {
         timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts);
         fprintf(stderr, "sharded extend: %d passes sharded, %d exchanges (%lld records, %lld words left this rank), %.3f ms; gathered %lld records\n",
-                passes_done, sh.n_exchanges, (long long)sh.exchanged_records, (long long)sh.exchanged_words, ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6 - t0,
+                loop.passes_done, sh.n_exchanges, (long long)sh.exchanged_records, (long long)sh.exchanged_words, ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6 - t0,
                 (long long)n_glob);
     }
-    tl_arena = nullptr;
-
-    // rank 0: the one-GPU driver takes the loop up; its outcome is every rank's (a short text buffer is RFX_E_CAP on EVERY
-    // rank with the length needed, so that the callers' retries stay collective)
-    int64_t len = 0, ncont = 0, ntr = nt;
-    int st_asm = RFX_OK;
-    if (sh.me == 0) {
-        AsmResume rs{&fin, passes_done, iterations, contigNumber, scramble, P, partitionNumber, nt};
-        try {
-            st_asm = assemble_impl(ctx, wide, nullptr, nullptr, 0, prm, out, cap, &len, &ncont, trace, trace_cap, &ntr, &rs);
-        } catch (...) { st_asm = rfx_api_exception(ctx, "rfx_dev_sharded_assemble"); }
-    }
-    int64_t res[3] = {st_asm == RFX_E_CAP ? 1 : 0, st_asm == RFX_E_CAP ? len : 0, (st_asm != RFX_OK && st_asm != RFX_E_CAP) ? 1 : 0};
-    RFX_TRY(rfx_comm_all_reduce_i64(c, res, 3, 1));
-    if (res[2]) {
-        if (st_asm != RFX_OK) return st_asm;
-        ctx->last_error = "rfx_dev_sharded_assemble: the driver failed on rank 0; see its rfx_last_error()";
-        return RFX_E_STATE;
-    }
-    if (res[0]) { *out_len = res[1]; return RFX_E_CAP; }
-    if (sh.me == 0) { *out_len = len; if (out_contigs) *out_contigs = ncont; if (n_trace) *n_trace = ntr; }
-    return RFX_OK;
+    // rank 0: the one-GPU driver takes the loop up
+    return rank0_drives(ctx, c, out_len, out_contigs, n_trace, [&](int64_t *len, int64_t *ncont, int64_t *ntr) -> int {
+        AsmResume rs{&fin, loop};
+        return assemble_impl(ctx, wide, nullptr, nullptr, 0, prm, out, cap, len, ncont, trace, trace_cap, ntr, &rs);
+    });
 #undef SH_LOCAL
 } RFX_API_CATCH(ctx)
 

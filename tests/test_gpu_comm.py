@@ -323,3 +323,25 @@ def test_sharded_extend_behind_the_c_abi_one_rank_real_rccl(golden_dir):
             assert (text, nc, trace) == (otext, onc, otrace), extras
     finally:
         rfx.close()
+
+
+def test_sharded_extend_handed_over_before_the_five_passes_are_done(golden_dir):
+    """the hand-over with fewer than five passes behind the record set: the documented example holds 6,918 records after the
+    first pass and 5,230 after the second, so gather_below = 5,500 gathers with two passes done and the one-GPU driver runs the
+    remaining three passes before the loop; 3,000 gathers with four done.  The oracle's golden contigs and trace."""
+    import torch
+    import reflexiv_amd
+    ex = np.load(os.path.join(golden_dir, "example.npz"))
+    want = [int(x) for x in ex["trace_ds_P4"]]
+    assert want[0] > 5500 >= want[1] and want[2] > 3000 >= want[3]
+    rfx = make_comm({"RFX_COMM_SELF_VIA_RCCL": "1"})
+    try:
+        dk = torch.from_numpy(ex["keys_cov3"].view(np.int64).copy()).cuda()
+        dc = torch.from_numpy(ex["counts_cov3"].astype(np.int32)).cuda()
+        torch.cuda.synchronize()
+        prm = reflexiv_amd.default_params(min_cov=3, partitions=4, twin=reflexiv_amd.TWIN_DS)
+        for gb in (5500, 3000):
+            text, nc, trace = rfx.sharded_assemble_dev(dk.data_ptr(), dc.data_ptr(), len(dc), prm, gather_below=gb)
+            assert text == str(ex["contigs_ds_P4"]) and trace == want, gb
+    finally:
+        rfx.close()

@@ -251,6 +251,19 @@ def test_assemble_with_the_coalesce_rule(rfx, torch_mod, ex, planted, P):
         assert trace == otrace and (text, nc) == (otext, onc)
 
 
+@pytest.mark.parametrize("coalesce", [0, 1])
+def test_assemble_with_more_partitions_than_the_small_pass_kernel_takes(rfx, torch_mod, ex, planted, coalesce):
+    """partitions = 1025: the small-pass tail is refused although the record set is small.  Without the coalesce rule the
+    whole loop runs as big passes; with it the host loop's check lowers the partition number to 257 (892 / 903 records on 1025
+    partitions), the tail takes over at the next head and goes on lowering it."""
+    import reflexiv_amd
+    for keys, counts, cov, mc in ((ex["keys_cov3"], ex["counts_cov3"], 3, 500), (planted["k31_keys"], planted["k31_counts"], 2, 100)):
+        prm = reflexiv_amd.default_params(min_cov=cov, partitions=1025, coalesce=coalesce, min_contig=mc)
+        text, nc, trace = dev_assemble(rfx, torch_mod, keys, counts, prm)
+        otext, onc, otrace, _ = O.assemble_from_counts(keys, counts, O.default_params(min_cov=cov, partitions=1025, coalesce=coalesce, min_contig=mc))
+        assert trace == otrace and (text, nc) == (otext, onc)
+
+
 def test_documented_known_answer_on_gpu(rfx, torch_mod, ex):
     """docs/example.html:303,320-343 end to end on the GPU: reads -> k-mers -> contigs."""
     import reflexiv_amd
