@@ -252,10 +252,13 @@ _DYN_PACKED_ARGS = {
 def build(force: bool = False) -> str:
     """Compile the HIP sources for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src = os.path.join(_HERE, "csrc")
+    host = os.path.join(src, "host")
     newest = max(os.path.getmtime(os.path.join(src, f)) for f in os.listdir(src)
                  if f.endswith((".hip", ".h")) or f == "Makefile")
     newest = max(newest, os.path.getmtime(os.path.join(_HERE, "..", "include", "reflexiv_hip.h")))
-    if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < newest:
+    newest_host = max([newest] + [os.path.getmtime(os.path.join(host, f)) for f in os.listdir(host)])
+    built = [(LIB_PATH, newest), (os.path.join(_HERE, "reflexiv_host"), newest_host)]     # (make rebuilds what is behind its sources)
+    if force or any(not os.path.exists(p) or os.path.getmtime(p) < t for p, t in built):
         subprocess.check_call(["make", "-s", "-j4", "-C", src])
     return LIB_PATH
 

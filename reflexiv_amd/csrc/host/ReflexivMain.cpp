@@ -36,47 +36,11 @@ void ReflexivMain::check(int st, const char *where) const {
     if (st != RFX_OK) throw RfxException(st, where, rfx_last_error(ctx));
 }
 
-// FastqFilterWithQual.call + FastqUnitFilter.call  P/ReflexivMain.java:3080-3113: the 4-line state
-// machine; emits the sequence line of every completed record.
-void ReflexivMain::FastqFilterWithQual::call(const std::string &text, std::vector<uint8_t> &bases,
-                                             std::vector<int64_t> &readOff) const {
-    int lineMark = 0;
-    size_t pos = 0, seqOff = 0, seqLen = 0;
-    bases.clear(); readOff.assign(1, 0);
-    while (pos < text.size()) {
-        size_t e = text.find('\n', pos);
-        if (e == std::string::npos) e = text.size();
-        size_t l = e - pos;
-        if (l > 0 && text[e - 1] == '\r') l--;
-        if (lineMark == 2) lineMark++;                                  // :3093-3096
-        else if (lineMark == 3) {                                       // :3097-3100
-            lineMark++;
-            bases.insert(bases.end(), text.begin() + seqOff, text.begin() + seqOff + seqLen);
-            readOff.push_back((int64_t)bases.size());
-        } else if (l > 0 && text[pos] == '@') lineMark = 1;             // :3101-3104
-        else if (lineMark == 1) { seqOff = pos; seqLen = l; lineMark++; }   // :3105-3108
-        pos = e + 1;
-    }
+void ReflexivMain::FastqFilterWithQual::call(const std::string &text, std::vector<uint8_t> &bases, std::vector<int64_t> &readOff) const {
+    fastqFilterWithQual(text, bases, readOff);
 }
-
-void ReflexivMain::DSFastqFilterOnlySeq::call(const std::string &text, std::vector<uint8_t> &bases,
-                                              std::vector<int64_t> &readOff) const {
-    auto checkSeq = [](char a) { return a == 'A' || a == 'T' || a == 'C' || a == 'G' || a == 'N'; };   // :268-289
-    size_t pos = 0;
-    bases.clear(); readOff.assign(1, 0);
-    while (pos < text.size()) {
-        size_t e = text.find('\n', pos);
-        if (e == std::string::npos) e = text.size();
-        size_t l = e - pos;
-        if (l > 0 && text[e - 1] == '\r') l--;
-        const char *s = text.data() + pos;
-        if (l > 20 && s[0] != '@' && s[0] != '+' && checkSeq(s[0]) && checkSeq(s[4]) && checkSeq(s[9]) &&
-            checkSeq(s[14]) && checkSeq(s[19])) {                      // :245-262
-            bases.insert(bases.end(), text.begin() + pos, text.begin() + pos + l);
-            readOff.push_back((int64_t)bases.size());
-        }
-        pos = e + 1;
-    }
+void ReflexivMain::DSFastqFilterOnlySeq::call(const std::string &text, std::vector<uint8_t> &bases, std::vector<int64_t> &readOff) const {
+    dsFastqFilterOnlySeq(text, bases, readOff);
 }
 
 std::vector<uint64_t> ReflexivMain::ReverseComplementKmerBinaryExtraction::call(
@@ -274,13 +238,16 @@ std::string ReflexivMain::assembly(const std::string &fastqText, std::vector<int
     return assemblyFromCounts(counts, trace);
 }
 
-std::string ReflexivMain::assemblyResident(const std::string &fastqText, std::vector<int64_t> *trace) {
-    if (!param.bubble)
-        throw std::runtime_error("-bubble (no fork filtering) is unusable in the reference too (SURVEY.md C.6)");
-    std::vector<uint8_t> bases; std::vector<int64_t> readOff;
-    // k > 31: the reads as `counter` takes them (ReflexivDataFrameCounter64), the first step of the two-step route
-    if (param.kmerSize > 31) DSFastqFilterOnlySeq{*this}.call(fastqText, bases, readOff);
-    else FastqFilterWithQual{*this}.call(fastqText, bases, readOff);
+namespace {
+static_assert(GROW_OK == RFX_OK && GROW_E_CAP == RFX_E_CAP, "HostText.h's retry reads the library's statuses");
+
+// the retry of HostText.h; a failure is `name: detail`
+template <class Call> void growOrThrow(rfx_ctx *ctx, const char *name, std::initializer_list<GrowBuf> bufs, Call &&call) {
+    if (growCall(bufs, call) != RFX_OK) throw std::runtime_error(std::string(name) + ": " + rfx_last_error(ctx));
+}
+}  // namespace
+
+rfx_params ReflexivMain::assembleParams() const {
     rfx_params prm;
     rfx_default_params(&prm);
     prm.k = param.kmerSize; prm.min_cov = param.minKmerCoverage; prm.max_cov = param.maxKmerCoverage;
@@ -288,18 +255,45 @@ std::string ReflexivMain::assemblyResident(const std::string &fastqText, std::ve
     prm.min_iter = param.minimumIteration; prm.max_iter = param.maximumIteration;
     prm.front_clip = param.frontClip; prm.end_clip = param.endClip;
     prm.partitions = std::max(1, param.logicalPartitions); prm.twin = param.twin;
+    return prm;
+}
+
+rfx_reduce_reads_params ReflexivMain::reduceReadsParams(int partitions) const {
+    rfx_reduce_reads_params prm;
+    rfx_reduce_reads_default_params(&prm);
+    prm.min_cov = param.minKmerCoverage; prm.max_cov = param.maxKmerCoverage; prm.min_error_cov = param.minErrorCoverage;
+    prm.min_repeat_fold = param.minRepeatFold; prm.bubble = param.bubble ? 1 : 0; prm.sensitive = param.sensitive ? 1 : 0;
+    prm.front_clip = param.frontClip; prm.end_clip = param.endClip; prm.P = partitions;
+    return prm;
+}
+
+rfx_fix_params ReflexivMain::fixParams() const {
+    rfx_fix_params prm;
+    rfx_fix_default_params(&prm, lastKmerOfList());
+    prm.scramble = param.scramble; prm.max_iteration = param.maximumIteration;
+    return prm;
+}
+
+// the reads of the resident drivers.  k > 31: as `counter` takes them (ReflexivDataFrameCounter64), the first step of the two-step route
+void ReflexivMain::residentReads(const std::string &fastqText, std::vector<uint8_t> &bases, std::vector<int64_t> &readOff) {
+    if (!param.bubble)
+        throw std::runtime_error("-bubble (no fork filtering) is unusable in the reference too (SURVEY.md C.6)");
+    if (param.kmerSize > 31) DSFastqFilterOnlySeq{*this}.call(fastqText, bases, readOff);
+    else FastqFilterWithQual{*this}.call(fastqText, bases, readOff);
+}
+
+std::string ReflexivMain::assemblyResident(const std::string &fastqText, std::vector<int64_t> *trace) {
+    std::vector<uint8_t> bases; std::vector<int64_t> readOff;
+    residentReads(fastqText, bases, readOff);
+    const rfx_params prm = assembleParams();
     const int64_t nr = (int64_t)readOff.size() - 1;
     std::vector<int64_t> tr((size_t)param.maximumIteration + 8);
     int64_t len = 0, nc = 0, nt = 0, kept = 0;
     std::string out((size_t)1 << 20, '\0');
-    for (;;) {
-        int st = rfx_assemble_reads(ctx, bases.data(), readOff.data(), nr, &prm, out.data(), (int64_t)out.size(), &len, &nc,
-                                    tr.data(), (int64_t)tr.size(), &nt, &kept);
-        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
-        check(st, "rfx_assemble_reads");
-        break;
-    }
-    out.resize((size_t)len);
+    check(growCall({{out, len}}, [&] {
+        return rfx_assemble_reads(ctx, bases.data(), readOff.data(), nr, &prm, out.data(), (int64_t)out.size(), &len, &nc,
+                                  tr.data(), (int64_t)tr.size(), &nt, &kept);
+    }), "rfx_assemble_reads");
     if (trace) trace->assign(tr.begin(), tr.begin() + nt);
     return out;
 }
@@ -311,35 +305,14 @@ namespace {
 // device behind rfx_dyn_run_text, on the packed record set.
 std::string dynRunText(rfx_ctx *ctx, const std::string &csv, bool kmers, int P, int reflect, int four, int start, int end,
                        std::vector<int64_t> *trace) {
-    std::string rows;                      // the non-empty lines, back to back
-    std::vector<int64_t> off{0};
-    size_t pos = 0;
-    while (pos < csv.size()) {
-        size_t e = csv.find('\n', pos);
-        if (e == std::string::npos) e = csv.size();
-        size_t le = e;
-        if (le > pos && csv[le - 1] == '\r') le--;
-        if (le > pos) {
-            size_t commas = 0;
-            for (size_t i = pos; i < le; i++) commas += csv[i] == ',';
-            if (commas + 1 < (kmers ? 2u : 3u)) throw std::runtime_error("dynamic-k row: " + csv.substr(pos, le - pos));
-            rows.append(csv, pos, le - pos);
-            off.push_back((int64_t)rows.size());
-        }
-        pos = e + 1;
-    }
-    const int64_t n = (int64_t)off.size() - 1;
-    std::string out(rows.size() + 32 * (size_t)n + 64, '\0');
+    const Rows rows = rowsOf(csv, kmers ? 1 : 2, "dynamic-k");
+    std::string out(rows.text.size() + 32 * (size_t)rows.n() + 64, '\0');
     std::vector<int64_t> tr(256);
     int64_t nt = 0, len = 0;
-    for (;;) {
-        const int st = rfx_dyn_run_text(ctx, rows.data(), off.data(), n, kmers ? 0 : 1, P, reflect, four, start, end, out.data(),
-                                        (int64_t)out.size(), &len, tr.data(), (int64_t)tr.size(), &nt);
-        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
-        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_dyn_run_text: ") + rfx_last_error(ctx));
-        break;
-    }
-    out.resize((size_t)len);
+    growOrThrow(ctx, "rfx_dyn_run_text", {{out, len}}, [&] {
+        return rfx_dyn_run_text(ctx, rows.text.data(), rows.off.data(), rows.n(), kmers ? 0 : 1, P, reflect, four, start, end, out.data(),
+                                (int64_t)out.size(), &len, tr.data(), (int64_t)tr.size(), &nt);
+    });
     if (trace) trace->assign(tr.begin(), tr.begin() + std::min<int64_t>(nt, (int64_t)tr.size()));
     return out;
 }
@@ -356,79 +329,35 @@ std::string ReflexivMain::assemblyDynamicIteration(const std::string &csvText, i
 }
 
 std::string ReflexivMain::kmerSorting(const std::string &csvText) {
-    std::string rows;
-    std::vector<int64_t> off{0};
-    for (size_t pos = 0; pos < csvText.size();) {                  // one row per non-empty line
-        size_t e = csvText.find('\n', pos);
-        if (e == std::string::npos) e = csvText.size();
-        size_t le = e;
-        if (le > pos && csvText[le - 1] == '\r') le--;
-        if (le > pos) { rows.append(csvText, pos, le - pos); off.push_back((int64_t)rows.size()); }
-        pos = e + 1;
-    }
+    const Rows rows = rowsOf(csvText);
     rfx_ksort_params prm;
     rfx_ksort_default_params(&prm, param.kmerSize);
-    const size_t c = param.kmerList.rfind(',');                    // maxKmerSize = kmerListInt[length - 1]
-    prm.max_k = std::stoi(param.kmerList.substr(c == std::string::npos ? 0 : c + 1));
+    prm.max_k = lastKmerOfList();                                  // maxKmerSize = kmerListInt[length - 1]
     prm.min_error_cov = param.minErrorCoverage; prm.max_cov = param.maxKmerCoverage; prm.bubble = param.bubble ? 1 : 0;
     prm.min_repeat_fold = param.minRepeatFold;
-    const int64_t n = (int64_t)off.size() - 1;
-    std::string out(2 * (rows.size() + 24 * (size_t)n) + 64, '\0');
+    std::string out(2 * (rows.text.size() + 24 * (size_t)rows.n()) + 64, '\0');
     int64_t len = 0;
-    for (;;) {
-        const int st = rfx_ksort_text(ctx, rows.data(), off.data(), n, &prm, out.data(), (int64_t)out.size(), &len);
-        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
-        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_ksort_text: ") + rfx_last_error(ctx));
-        break;
-    }
-    out.resize((size_t)len);
+    growOrThrow(ctx, "rfx_ksort_text", {{out, len}}, [&] {
+        return rfx_ksort_text(ctx, rows.text.data(), rows.off.data(), rows.n(), &prm, out.data(), (int64_t)out.size(), &len);
+    });
     return out;
 }
 
-namespace {
-// one row per non-empty line, the line ends dropped
-void rowsOf(const std::string &csvText, std::string &rows, std::vector<int64_t> &off) {
-    off.assign(1, 0);
-    for (size_t pos = 0; pos < csvText.size();) {
-        size_t e = csvText.find('\n', pos);
-        if (e == std::string::npos) e = csvText.size();
-        size_t le = e;
-        if (le > pos && csvText[le - 1] == '\r') le--;
-        if (le > pos) { rows.append(csvText, pos, le - pos); off.push_back((int64_t)rows.size()); }
-        pos = e + 1;
-    }
-}
-}  // namespace
-
-int ReflexivMain::lastKmerOfList() const {
-    const size_t c = param.kmerList.rfind(',');
-    return std::stoi(param.kmerList.substr(c == std::string::npos ? 0 : c + 1));
-}
+int ReflexivMain::lastKmerOfList() const { return lastKmerOf(param.kmerList); }
 
 void ReflexivMain::kmerReduction(const std::string &shortText, const std::string &longText, int k1, int k2, int partitions, std::string *reducedShort,
                                  std::string *rewrittenLong) {
-    std::string rs, rl;
-    std::vector<int64_t> os, ol;
-    rowsOf(shortText, rs, os);
-    rowsOf(longText, rl, ol);
+    const Rows s = rowsOf(shortText), l = rowsOf(longText);
     rfx_reduce_params prm;
     rfx_reduce_default_params(&prm, k1, k2);
     prm.max_k = std::max(k2, lastKmerOfList());
-    const int64_t ns = (int64_t)os.size() - 1, nl = (int64_t)ol.size() - 1;
     // (a row comes back with its newline, and an edited marker may be one character longer)
-    std::string o1(rs.size() + 2 * (size_t)ns + 64, '\0'), o2(rl.size() + 2 * (size_t)nl + 64, '\0');
+    std::string o1(s.text.size() + 2 * (size_t)s.n() + 64, '\0'), o2(l.text.size() + 2 * (size_t)l.n() + 64, '\0');
     int64_t l1 = 0, l2 = 0;
-    for (;;) {
-        const int st = rfx_reduce_text(ctx, rs.data(), os.data(), ns, rl.data(), ol.data(), nl, partitions, &prm, o1.data(), (int64_t)o1.size(), &l1,
-                                       o2.data(), (int64_t)o2.size(), &l2);
-        if (st == RFX_E_CAP && (l1 > (int64_t)o1.size() || l2 > (int64_t)o2.size())) {
-            o1.assign((size_t)std::max<int64_t>(l1, (int64_t)o1.size()), '\0'); o2.assign((size_t)std::max<int64_t>(l2, (int64_t)o2.size()), '\0');
-            continue;
-        }
-        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_reduce_text: ") + rfx_last_error(ctx));
-        break;
-    }
-    o1.resize((size_t)l1); o2.resize((size_t)l2);
+    growOrThrow(ctx, "rfx_reduce_text", {{o1, l1}, {o2, l2}}, [&] {
+        return rfx_reduce_text(ctx, s.text.data(), s.off.data(), s.n(), l.text.data(), l.off.data(), l.n(), partitions, &prm, o1.data(),
+                               (int64_t)o1.size(), &l1, o2.data(), (int64_t)o2.size(), &l2);
+    });
     *reducedShort = std::move(o1); *rewrittenLong = std::move(o2);
 }
 
@@ -436,22 +365,15 @@ std::vector<std::string> ReflexivMain::kmerReductionFromReads(const std::string 
     std::vector<uint8_t> bases; std::vector<int64_t> readOff;
     DSFastqFilterOnlySeq{*this}.call(fastqText, bases, readOff);      // as counter()
     const int64_t nr = (int64_t)readOff.size() - 1;
-    rfx_reduce_reads_params prm;
-    rfx_reduce_reads_default_params(&prm);
-    prm.min_cov = param.minKmerCoverage; prm.max_cov = param.maxKmerCoverage; prm.min_error_cov = param.minErrorCoverage;
-    prm.min_repeat_fold = param.minRepeatFold; prm.bubble = param.bubble ? 1 : 0; prm.sensitive = param.sensitive ? 1 : 0;
-    prm.front_clip = param.frontClip; prm.end_clip = param.endClip; prm.P = partitions;
+    const rfx_reduce_reads_params prm = reduceReadsParams(partitions);
     if (bases.empty()) bases.push_back(0);
     std::string out(std::max<size_t>(4 * bases.size(), 1 << 16), '\0');
     std::vector<int64_t> off(klist.size() + 1, 0);
     int64_t len = 0;
-    for (;;) {
-        const int st = rfx_reduce_reads(ctx, bases.data(), readOff.data(), nr, klist.data(), (int)klist.size(), &prm, out.data(), (int64_t)out.size(), &len,
-                                        off.data());
-        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
-        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_reduce_reads: ") + rfx_last_error(ctx));
-        break;
-    }
+    growOrThrow(ctx, "rfx_reduce_reads", {{out, len}}, [&] {
+        return rfx_reduce_reads(ctx, bases.data(), readOff.data(), nr, klist.data(), (int)klist.size(), &prm, out.data(), (int64_t)out.size(), &len,
+                                off.data());
+    });
     std::vector<std::string> texts;
     for (size_t i = 0; i < klist.size(); i++) texts.push_back(out.substr((size_t)off[i], (size_t)(off[i + 1] - off[i])));
     return texts;
@@ -461,11 +383,7 @@ std::string ReflexivMain::metaAssemblyFromReads(const std::string &fastqText, co
     std::vector<uint8_t> bases; std::vector<int64_t> readOff;
     DSFastqFilterOnlySeq{*this}.call(fastqText, bases, readOff);      // as counter()
     const int64_t nr = (int64_t)readOff.size() - 1;
-    rfx_reduce_reads_params rp;
-    rfx_reduce_reads_default_params(&rp);
-    rp.min_cov = param.minKmerCoverage; rp.max_cov = param.maxKmerCoverage; rp.min_error_cov = param.minErrorCoverage;
-    rp.min_repeat_fold = param.minRepeatFold; rp.bubble = param.bubble ? 1 : 0; rp.sensitive = param.sensitive ? 1 : 0;
-    rp.front_clip = param.frontClip; rp.end_clip = param.endClip; rp.P = partitions;
+    const rfx_reduce_reads_params rp = reduceReadsParams(partitions);
     rfx_meta_params mp;
     rfx_meta_default_params(&mp);
     mp.P = partitions; mp.scramble = param.scramble; mp.max_iteration = param.maximumIteration; mp.min_contig = param.minContig;
@@ -473,26 +391,20 @@ std::string ReflexivMain::metaAssemblyFromReads(const std::string &fastqText, co
     if (bases.empty()) bases.push_back(0);
     std::string out(std::max<size_t>(2 * bases.size(), 1 << 16), '\0');
     int64_t len = 0;
-    for (;;) {
-        const int st = rfx_meta_reads(ctx, bases.data(), readOff.data(), nr, klist.data(), (int)klist.size(), &rp, &mp, nullptr, out.data(), (int64_t)out.size(),
-                                      &len);
-        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
-        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_meta_reads: ") + rfx_last_error(ctx));
-        break;
-    }
-    out.resize((size_t)len);
+    growOrThrow(ctx, "rfx_meta_reads", {{out, len}}, [&] {
+        return rfx_meta_reads(ctx, bases.data(), readOff.data(), nr, klist.data(), (int)klist.size(), &rp, &mp, nullptr, out.data(), (int64_t)out.size(),
+                              &len);
+    });
     return out;
 }
 
 std::string ReflexivMain::dedupContigRows(const std::string &csvText) {
-    std::string rows;
-    std::vector<int64_t> off;
-    rowsOf(csvText, rows, off);
-    const int64_t n = (int64_t)off.size() - 1;
+    const Rows rows = rowsOf(csvText);
+    const int64_t n = rows.n();
     std::vector<uint8_t> bases;
     std::vector<int64_t> coff(1, 0);
     for (int64_t i = 0; i < n; i++) {
-        const std::string row = rows.substr((size_t)off[(size_t)i], (size_t)(off[(size_t)i + 1] - off[(size_t)i]));
+        const std::string row = rows.row(i);
         const size_t c = row.find(',');
         if (c == std::string::npos || row.compare(0, 8, ">Contig-") != 0) throw std::runtime_error("dedup row: " + row);
         size_t e = row.size();
@@ -503,41 +415,23 @@ std::string ReflexivMain::dedupContigRows(const std::string &csvText) {
     if (bases.empty()) bases.push_back(0);
     std::string out(2 * bases.size() + 64 * (size_t)(n + 2) + 4096, '\0');
     int64_t len = 0;
-    for (;;) {
-        const int st = rfx_dedup_contigs(ctx, bases.data(), coff.data(), n, param.minContig, nullptr, 0, nullptr, 0, nullptr, out.data(), (int64_t)out.size(), &len,
-                                         nullptr);
-        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
-        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_dedup_contigs: ") + rfx_last_error(ctx));
-        break;
-    }
-    out.resize((size_t)len);
+    growOrThrow(ctx, "rfx_dedup_contigs", {{out, len}}, [&] {
+        return rfx_dedup_contigs(ctx, bases.data(), coff.data(), n, param.minContig, nullptr, 0, nullptr, 0, nullptr, out.data(), (int64_t)out.size(), &len,
+                                 nullptr);
+    });
     return out;
 }
 
-// the host forms that take rows and rfx_fix_params and give one text (rfx_fix_text, rfx_ext_text, rfx_ext2_text): the call, again with the
-// length it reported where the buffer was short.  min_commas: what a row must hold to be one of the stage's; stage: the word that a
-// refused row's message begins with
-std::string ReflexivMain::fixParamsText(int (*fn)(rfx_ctx *, const char *, const int64_t *, int64_t, int, const rfx_fix_params *, char *, int64_t, int64_t *),
-                                        const char *name, const char *stage, const std::string &csvText, int partitions, int min_commas) {
-    std::string rows;
-    std::vector<int64_t> off;
-    rowsOf(csvText, rows, off);
-    const int64_t n = (int64_t)off.size() - 1;
-    for (int64_t i = 0; i < n; i++)
-        if (std::count(rows.begin() + off[(size_t)i], rows.begin() + off[(size_t)i + 1], ',') < min_commas)
-            throw std::runtime_error(std::string(stage) + " row: " + rows.substr((size_t)off[(size_t)i], (size_t)(off[(size_t)i + 1] - off[(size_t)i])));
-    rfx_fix_params prm;
-    rfx_fix_default_params(&prm, lastKmerOfList());
-    prm.scramble = param.scramble; prm.max_iteration = param.maximumIteration;
-    std::string out(rows.size() + 64 * (size_t)n + 64, '\0');
+// the host forms that take rows and rfx_fix_params and give one text (rfx_fix_text, rfx_ext_text, rfx_ext2_text).  min_commas: what a
+// row must hold to be one of the stage's; stage: the word that a refused row's message begins with
+std::string ReflexivMain::fixParamsText(FixTextFn fn, const char *name, const char *stage, const std::string &csvText, int partitions, int min_commas) {
+    const Rows rows = rowsOf(csvText, min_commas, stage);
+    const rfx_fix_params prm = fixParams();
+    std::string out(rows.text.size() + 64 * (size_t)rows.n() + 64, '\0');
     int64_t len = 0;
-    for (;;) {
-        const int st = fn(ctx, rows.data(), off.data(), n, partitions, &prm, out.data(), (int64_t)out.size(), &len);
-        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
-        if (st != RFX_OK) throw std::runtime_error(std::string(name) + ": " + rfx_last_error(ctx));
-        break;
-    }
-    out.resize((size_t)len);
+    growOrThrow(ctx, name, {{out, len}}, [&] {
+        return fn(ctx, rows.text.data(), rows.off.data(), rows.n(), partitions, &prm, out.data(), (int64_t)out.size(), &len);
+    });
     return out;
 }
 
@@ -554,103 +448,57 @@ std::string ReflexivMain::contigExtendAgain(const std::string &csvText, int part
 }
 
 void ReflexivMain::contigFixingRoundTwo(const std::string &csvText, int partitions, std::string *contigRows, std::string *contigEnds) {
-    std::string rows;
-    std::vector<int64_t> off;
-    rowsOf(csvText, rows, off);
-    const int64_t n = (int64_t)off.size() - 1;
-    for (int64_t i = 0; i < n; i++)
-        if (std::count(rows.begin() + off[(size_t)i], rows.begin() + off[(size_t)i + 1], ',') < 2)
-            throw std::runtime_error("fixing2 row: " + rows.substr((size_t)off[(size_t)i], (size_t)(off[(size_t)i + 1] - off[(size_t)i])));
-    rfx_fix_params prm;
-    rfx_fix_default_params(&prm, lastKmerOfList());
-    prm.scramble = param.scramble; prm.max_iteration = param.maximumIteration;
-    std::string o1(rows.size() + 64 * (size_t)n + 64, '\0'), o2(rows.size() + 64 * (size_t)n + 64, '\0');
+    const Rows rows = rowsOf(csvText, 2, "fixing2");
+    const rfx_fix_params prm = fixParams();
+    std::string o1(rows.text.size() + 64 * (size_t)rows.n() + 64, '\0'), o2(o1.size(), '\0');
     int64_t l1 = 0, l2 = 0;
-    for (;;) {
-        const int st = rfx_fix2_text(ctx, rows.data(), off.data(), n, partitions, &prm, o1.data(), (int64_t)o1.size(), &l1, o2.data(), (int64_t)o2.size(), &l2);
-        if (st == RFX_E_CAP && (l1 > (int64_t)o1.size() || l2 > (int64_t)o2.size())) {
-            if (l1 > (int64_t)o1.size()) o1.assign((size_t)l1, '\0');
-            if (l2 > (int64_t)o2.size()) o2.assign((size_t)l2, '\0');
-            continue;
-        }
-        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_fix2_text: ") + rfx_last_error(ctx));
-        break;
-    }
-    o1.resize((size_t)l1); o2.resize((size_t)l2);
+    growOrThrow(ctx, "rfx_fix2_text", {{o1, l1}, {o2, l2}}, [&] {
+        return rfx_fix2_text(ctx, rows.text.data(), rows.off.data(), rows.n(), partitions, &prm, o1.data(), (int64_t)o1.size(), &l1, o2.data(),
+                             (int64_t)o2.size(), &l2);
+    });
     *contigRows = std::move(o1); *contigEnds = std::move(o2);
 }
 
 std::string ReflexivMain::contigEndExtend(const std::string &contigText, const std::string &samText) {
-    std::string contigs, lines, rows;
-    std::vector<int64_t> coff, loff, roff(1, 0);
-    rowsOf(contigText, contigs, coff);
-    rowsOf(samText, lines, loff);
-    for (size_t i = 0; i + 1 < loff.size(); i++) {
-        const size_t b = (size_t)loff[i], e = (size_t)loff[i + 1];
-        std::vector<size_t> tabs;
-        for (size_t p = b; p < e; p++) if (lines[p] == '\t') tabs.push_back(p);
-        if (tabs.size() >= 10) {                                  // a full SAM line: RNAME, POS, CIGAR, SEQ
-            auto field = [&](size_t f) { return lines.substr(tabs[f - 1] + 1, tabs[f] - tabs[f - 1] - 1); };
-            if (lines[b] == '@' || field(2) == "*") continue;
-            rows += field(2) + "\t" + field(3) + "\t" + field(5) + "\t" + field(9);
-        } else {
-            rows.append(lines, b, e - b);
-        }
-        roff.push_back((int64_t)rows.size());
-    }
-    const int64_t n = (int64_t)coff.size() - 1, nr = (int64_t)roff.size() - 1;
-    std::string out(contigs.size() + 700 * (size_t)n + 64, '\0');
+    const Rows contigs = rowsOf(contigText), rows = samRows(samText);
+    std::string out(contigs.text.size() + 700 * (size_t)contigs.n() + 64, '\0');
     int64_t len = 0;
-    for (;;) {
-        const int st = rfx_endext_text(ctx, contigs.data(), coff.data(), n, rows.data(), roff.data(), nr, lastKmerOfList(), out.data(), (int64_t)out.size(), &len);
-        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
-        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_endext_text: ") + rfx_last_error(ctx));
-        break;
-    }
-    out.resize((size_t)len);
+    growOrThrow(ctx, "rfx_endext_text", {{out, len}}, [&] {
+        return rfx_endext_text(ctx, contigs.text.data(), contigs.off.data(), contigs.n(), rows.text.data(), rows.off.data(), rows.n(), lastKmerOfList(),
+                               out.data(), (int64_t)out.size(), &len);
+    });
     return out;
 }
 
 std::string ReflexivMain::contigMapping(const std::string &contigText, const std::string &fastqText, std::string *rows) {
-    std::string contigs;
-    std::vector<int64_t> coff;
-    rowsOf(contigText, contigs, coff);
+    const Rows contigs = rowsOf(contigText);
     std::vector<uint8_t> bases; std::vector<int64_t> readOff;
     DSFastqFilterOnlySeq{*this}.call(fastqText, bases, readOff);
-    const int64_t n = (int64_t)coff.size() - 1, nr = (int64_t)readOff.size() - 1;
+    const int64_t nr = (int64_t)readOff.size() - 1;
     rfx_map_params prm;
     rfx_map_default_params(&prm);
     std::string out(bases.size() + 256 * (size_t)nr + 64, '\0');
     int64_t len = 0;
-    for (;;) {
-        const int st = rfx_map_text(ctx, contigs.data(), coff.data(), n, bases.data(), readOff.data(), nr, &prm, out.data(), (int64_t)out.size(), &len);
-        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
-        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_map_text: ") + rfx_last_error(ctx));
-        break;
-    }
-    out.resize((size_t)len);
+    growOrThrow(ctx, "rfx_map_text", {{out, len}}, [&] {
+        return rfx_map_text(ctx, contigs.text.data(), contigs.off.data(), contigs.n(), bases.data(), readOff.data(), nr, &prm, out.data(),
+                            (int64_t)out.size(), &len);
+    });
     std::string ext = contigEndExtend(contigText, out);
     if (rows) *rows = std::move(out);
     return ext;
 }
 
 std::string ReflexivMain::mercyKmers(const std::string &countText, const std::string &fastqText) {
-    std::string counts;
-    std::vector<int64_t> coff;
-    rowsOf(countText, counts, coff);
+    const Rows counts = rowsOf(countText);
     std::vector<uint8_t> bases; std::vector<int64_t> readOff;
     DSFastqFilterOnlySeq{*this}.call(fastqText, bases, readOff);
-    const int64_t n = (int64_t)coff.size() - 1, nr = (int64_t)readOff.size() - 1;
+    const int64_t nr = (int64_t)readOff.size() - 1;
     std::string out((size_t)(param.kmerSize + 3) * (size_t)(nr + 64), '\0');
     int64_t len = 0;
-    for (;;) {
-        const int st = rfx_mercy_text(ctx, counts.data(), coff.data(), n, bases.data(), readOff.data(), nr, param.kmerSize, param.frontClip, param.endClip,
-                                      out.data(), (int64_t)out.size(), &len);
-        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }
-        if (st != RFX_OK) throw std::runtime_error(std::string("rfx_mercy_text: ") + rfx_last_error(ctx));
-        break;
-    }
-    out.resize((size_t)len);
+    growOrThrow(ctx, "rfx_mercy_text", {{out, len}}, [&] {
+        return rfx_mercy_text(ctx, counts.text.data(), counts.off.data(), counts.n(), bases.data(), readOff.data(), nr, param.kmerSize, param.frontClip,
+                              param.endClip, out.data(), (int64_t)out.size(), &len);
+    });
     return out;
 }
 
@@ -664,19 +512,9 @@ std::string ReflexivMain::dedupContigText(const std::string &contigText) {
 }
 
 std::string ReflexivMain::assemblyResidentSharded(const std::string &fastqText, int nGpus, std::vector<int64_t> *trace, int64_t gatherBelow) {
-    if (!param.bubble)
-        throw std::runtime_error("-bubble (no fork filtering) is unusable in the reference too (SURVEY.md C.6)");
     std::vector<uint8_t> bases; std::vector<int64_t> readOff;
-    // k > 31: the reads as `counter` takes them (ReflexivDataFrameCounter64), the first step of the two-step route
-    if (param.kmerSize > 31) DSFastqFilterOnlySeq{*this}.call(fastqText, bases, readOff);
-    else FastqFilterWithQual{*this}.call(fastqText, bases, readOff);
-    rfx_params prm;
-    rfx_default_params(&prm);
-    prm.k = param.kmerSize; prm.min_cov = param.minKmerCoverage; prm.max_cov = param.maxKmerCoverage;
-    prm.min_error_cov = param.minErrorCoverage; prm.min_contig = param.minContig;
-    prm.min_iter = param.minimumIteration; prm.max_iter = param.maximumIteration;
-    prm.front_clip = param.frontClip; prm.end_clip = param.endClip;
-    prm.partitions = std::max(1, param.logicalPartitions); prm.twin = param.twin;
+    residentReads(fastqText, bases, readOff);
+    const rfx_params prm = assembleParams();
     const int64_t nr = (int64_t)readOff.size() - 1;
     uint8_t id[128];
     check(rfx_comm_unique_id(id), "rfx_comm_unique_id");
@@ -693,15 +531,11 @@ std::string ReflexivMain::assemblyResidentSharded(const std::string &fastqText, 
                 const int64_t a = nr * r / nGpus, b = nr * (r + 1) / nGpus;            // contiguous shares of the reads
                 std::string out(r == 0 ? (size_t)3 * (size_t)(readOff[nr] - readOff[0]) + ((size_t)1 << 20) : (size_t)1 << 12, '\0');
                 int64_t len = 0, nc = 0, n_tr = 0, tot[3];
-                for (;;) {
-                    const int st = rfx_sharded_assemble_reads(c, comm, bases.data(), readOff.data() + a, b - a, &prm, 4, gatherBelow, out.data(),
-                                                              (int64_t)out.size(), &len, &nc, r == 0 ? tr.data() : nullptr,
-                                                              r == 0 ? (int64_t)tr.size() : 0, &n_tr, tot);
-                    if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.assign((size_t)len, '\0'); continue; }   // (on every rank at once: the retry is collective)
-                    if (st != RFX_OK) throw std::runtime_error(std::string("rfx_sharded_assemble_reads: ") + rfx_last_error(c));
-                    break;
-                }
-                out.resize((size_t)len);
+                growOrThrow(c, "rfx_sharded_assemble_reads", {{out, len}}, [&] {      // (on every rank at once: the retry is collective)
+                    return rfx_sharded_assemble_reads(c, comm, bases.data(), readOff.data() + a, b - a, &prm, 4, gatherBelow, out.data(),
+                                                      (int64_t)out.size(), &len, &nc, r == 0 ? tr.data() : nullptr,
+                                                      r == 0 ? (int64_t)tr.size() : 0, &n_tr, tot);
+                });
                 outs[(size_t)r] = out;
                 if (r == 0) nt = n_tr;
             } catch (const std::exception &e) { errs[(size_t)r] = e.what(); }
@@ -714,37 +548,16 @@ std::string ReflexivMain::assemblyResidentSharded(const std::string &fastqText, 
     return outs[0];
 }
 
-// KmerBinarizer.call  P/ReflexivDSMain.java:3883-3931: "KMER,count" or "(KMER,count)"; a count of
-// ten or more digits saturates at 1,000,000,000; bases A0 C1 G2, anything else 3.
+// KmerBinarizer.call  P/ReflexivDSMain.java:3883-3931: the rows of countRow(); bases A0 C1 G2, anything else 3, 32 to the word
 KmerBinaryRDD ReflexivMain::KmerBinarizer::call(const std::string &csvText) const {
     KmerBinaryRDD o;
     const int k = m.param.kmerSize;
-    size_t pos = 0;
-    while (pos < csvText.size()) {
-        size_t e = csvText.find('\n', pos);
-        if (e == std::string::npos) e = csvText.size();
-        size_t l = e - pos;
-        if (l > 0 && csvText[e - 1] == '\r') l--;
-        std::string line = csvText.substr(pos, l);
-        pos = e + 1;
-        if (line.empty()) continue;
-        size_t comma = line.find(',');
-        if (comma == std::string::npos) throw std::runtime_error("k-mer count row without a comma: " + line);
-        std::string kmer = line.substr(0, comma), cnt = line.substr(comma + 1);
-        if (!kmer.empty() && kmer[0] == '(') kmer = kmer.substr(1);                    // :3892-3894
-        int cover;
-        if (!cnt.empty() && cnt.back() == ')') {                                       // :3896-3901
-            cover = cnt.size() >= 11 ? 1000000000 : std::stoi(cnt.substr(0, cnt.size() - 1));
-        } else {                                                                       // :3902-3908
-            cover = cnt.size() >= 10 ? 1000000000 : std::stoi(cnt);
-        }
-        if ((int)kmer.size() < k) throw std::runtime_error("k-mer shorter than -kmer: " + kmer);
+    const Rows rows = rowsOf(csvText);
+    for (int64_t r = 0; r < rows.n(); r++) {
+        const KmerCount row = countRow(rows.row(r), k);
         uint64_t b = 0;
-        for (int i = 0; i < k; i++) {                                                  // :3912-3919
-            char c = kmer[(size_t)i];
-            b = (b << 2) | (c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : 3u);
-        }
-        o.kmer.push_back(b); o.count.push_back(cover);
+        for (int i = 0; i < k; i++) b = (b << 2) | baseCode(row.kmer[(size_t)i]);      // :3912-3919
+        o.kmer.push_back(b); o.count.push_back(row.count);
     }
     return o;
 }
@@ -765,30 +578,14 @@ std::string ReflexivMain::assemblyFromKmer(const std::string &csvText, std::vect
 // KmerBinarizer.call  P/ReflexivDSMain64.java:10772-10836: the same row rules as above, the k-mer into words of 31 bases
 void ReflexivMain::KmerBinarizer64::call(const std::string &csvText, std::vector<uint64_t> &kmers, std::vector<int32_t> &counts) const {
     const int k = m.param.kmerSize, W = (k - 1) / 31 + 1;                                 // kmerBinarySlotsAssemble
-    size_t pos = 0;
-    while (pos < csvText.size()) {
-        size_t e = csvText.find('\n', pos);
-        if (e == std::string::npos) e = csvText.size();
-        size_t l = e - pos;
-        if (l > 0 && csvText[e - 1] == '\r') l--;
-        std::string line = csvText.substr(pos, l);
-        pos = e + 1;
-        if (line.empty()) continue;
-        size_t comma = line.find(',');
-        if (comma == std::string::npos) throw std::runtime_error("k-mer count row without a comma: " + line);
-        std::string kmer = line.substr(0, comma), cnt = line.substr(comma + 1);
-        if (!kmer.empty() && kmer[0] == '(') kmer = kmer.substr(1);                       // :10790-10792
-        int cover;
-        if (!cnt.empty() && cnt.back() == ')') cover = cnt.size() >= 11 ? 1000000000 : std::stoi(cnt.substr(0, cnt.size() - 1));   // :10794-10799
-        else cover = cnt.size() >= 10 ? 1000000000 : std::stoi(cnt);                      // :10800-10806
-        if ((int)kmer.size() < k) throw std::runtime_error("k-mer shorter than -kmer: " + kmer);
+    const Rows rows = rowsOf(csvText);
+    for (int64_t r = 0; r < rows.n(); r++) {
+        const KmerCount row = countRow(rows.row(r), k);
         const size_t at = kmers.size();
         kmers.resize(at + (size_t)W, 0);
-        for (int i = 0; i < k; i++) {                                                     // :10811-10819
-            const char c = kmer[(size_t)i];
-            kmers[at + (size_t)(i / 31)] = (kmers[at + (size_t)(i / 31)] << 2) | (c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : 3u);
-        }
-        counts.push_back(cover);
+        for (int i = 0; i < k; i++)                                                       // :10811-10819
+            kmers[at + (size_t)(i / 31)] = (kmers[at + (size_t)(i / 31)] << 2) | baseCode(row.kmer[(size_t)i]);
+        counts.push_back(row.count);
     }
 }
 
@@ -806,22 +603,16 @@ std::string ReflexivMain::assemblyFromKmer64(const std::string &csvText, std::ve
     });
     std::vector<uint64_t> fk; std::vector<int32_t> fc;
     for (size_t i : idx) { fk.insert(fk.end(), km.begin() + i * W, km.begin() + (i + 1) * W); fc.push_back(cn[i]); }
-    rfx_params prm; rfx_default_params(&prm);
-    prm.k = param.kmerSize; prm.min_cov = param.minKmerCoverage; prm.max_cov = param.maxKmerCoverage;
-    prm.min_error_cov = param.minErrorCoverage; prm.min_contig = param.minContig; prm.min_iter = param.minimumIteration;
-    prm.max_iter = param.maximumIteration; prm.front_clip = param.frontClip; prm.end_clip = param.endClip;
-    prm.partitions = param.logicalPartitions;
+    rfx_params prm = assembleParams();
+    // this route's own: the partition count as given (no floor of 1), and the twin at the library's default (the k > 31 passes ignore it)
+    prm.partitions = param.logicalPartitions; prm.twin = RFX_TWIN_DS;
     std::vector<int64_t> tr((size_t)param.maximumIteration + 8);
     int64_t nt = 0, nc = 0, len = 0;
     std::string out((size_t)(4 * (fc.size() + 16) * (size_t)(param.kmerSize + 8) + 1024), '\0');
-    for (;;) {
-        const int st = rfx_assemble_counts_w(ctx, fk.data(), fc.data(), (int64_t)fc.size(), &prm, &out[0], (int64_t)out.size(), &len, &nc,
-                                             tr.data(), (int64_t)tr.size(), &nt);
-        if (st == RFX_E_CAP && len > (int64_t)out.size()) { out.resize((size_t)len); continue; }
-        check(st, "rfx_assemble_counts_w");
-        break;
-    }
-    out.resize((size_t)len);
+    check(growCall({{out, len}}, [&] {
+        return rfx_assemble_counts_w(ctx, fk.data(), fc.data(), (int64_t)fc.size(), &prm, out.data(), (int64_t)out.size(), &len, &nc,
+                                     tr.data(), (int64_t)tr.size(), &nt);
+    }), "rfx_assemble_counts_w");
     if (trace) trace->assign(tr.begin(), tr.begin() + nt);
     return out;
 }

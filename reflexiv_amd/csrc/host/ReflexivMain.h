@@ -15,6 +15,7 @@
 
 #include "../../../include/reflexiv_hip.h"
 #include "DefaultParam.h"
+#include "HostText.h"
 
 namespace reflexiv {
 
@@ -212,9 +213,14 @@ public:
 
     rfx_ctx *ctx = nullptr;
     DefaultParam param;
-    void check(int st, const char *where) const;
-    std::string fixParamsText(int (*fn)(rfx_ctx *, const char *, const int64_t *, int64_t, int, const rfx_fix_params *, char *, int64_t, int64_t *),
-                              const char *name, const char *stage, const std::string &csvText, int partitions, int min_commas);
+    void check(int st, const char *where) const;     // a failure is `where: status N -- detail`
+    // the library's parameter structs from param, each filled in one place
+    rfx_params assembleParams() const;
+    rfx_reduce_reads_params reduceReadsParams(int partitions) const;
+    rfx_fix_params fixParams() const;                // maxKmerSize is the last k of the k list
+    void residentReads(const std::string &fastqText, std::vector<uint8_t> &bases, std::vector<int64_t> &readOff);
+    using FixTextFn = int (*)(rfx_ctx *, const char *, const int64_t *, int64_t, int, const rfx_fix_params *, char *, int64_t, int64_t *);
+    std::string fixParamsText(FixTextFn fn, const char *name, const char *stage, const std::string &csvText, int partitions, int min_commas);
 };
 
 }  // namespace reflexiv
